@@ -25,11 +25,24 @@ has touched the GPU — and relays rank 0's line and a non-zero exit code of any
 the dominant slot is a latency-bound n-space kernel (the 512 x 64 shapes, one problem) it carries the WHOLE STEP's
 fractions instead (`scope: whole_step`): algorithmic bytes / ms_per_step against HBM, the Gram's flops / ms_per_step
 against the FP64 MFMA peak — figures the committed kernel stats reproduce.
-Every config prints the same JSON shape with its own SURVEY 8(d) bytes / flops.  The default (c2)
-line also carries, at N = 1: `side_configs` (the other configs' rates, same process, short runs),
-`householder_only` (the same workload with the normal-equations front end off), `h2d_inclusive`
-(the host-pointer API: numpy in, numpy out) and `cpu_baseline`; at N > 1 a `c5_tsqr` side figure
-(the tall problem over all ranks).  Side figures are never `value`.
+A plain run (no --full) does only what the headline figure needs: it sets up, warms up (W steps, then a settle run of
+min(K, 10), at least 2, untimed steps), times exactly K steps when --steps is given, writes the outputs if
+--dump-outputs is given, and prints `metric`, `value`, `unit`, `higher_is_better`, `dtype`, `ms_per_step` and the
+workload.  Without --steps the timed region is at least --min-time seconds (5 for the headline config, 1 otherwise: a
+shorter region is repeated as one region of r x steps steps).
+--full adds what the headline figure does not need: the settle steps fill the per-kernel table (`kernels_ms_per_step`),
+events around the dominant kernel in the timed region give the `roofline` (with the measured peaks of
+blsq_debug_probe), `parity` checks --check problems (default 2) against the oracle, and every config prints the same
+JSON shape with its own SURVEY 8(d) bytes / flops.  The default (c2) line then also carries, at N = 1:
+`side_configs` (the other configs' rates, same process, short runs), `householder_only` (the same workload with the
+normal-equations front end off), the conditioning legs, `h2d_inclusive` (the host-pointer API: numpy in, numpy out),
+the front end on one problem and `cpu_baseline`; at N > 1 `rccl` (the library's communicator, brought up after the
+timed region) and a `c5_tsqr` side figure (the tall problem over all ranks).  Side figures are never `value`.
+--dump-outputs DIR: after the timed steps, what the last timed step left for a caller of the path — the outputs of the
+factor call and of the step (the arrays factor() / step() of the host API return), one DIR/<name>.npy each, float64
+(integer masks and counters converted exactly); rank 0's problems.  Above 64 MB in all, a fixed seeded sample of the
+problems (the same rows of every array; DIR/problem_index.npy names them).  The inputs are seeded: the same arguments
+give the same inputs in every run.
 """
 import argparse
 import json
@@ -402,10 +415,12 @@ class Bench:
         return out
 
 
-def time_steps(bench, steps, warmup, fence, min_time=0.0, reduce_max=None):
+def time_steps(bench, steps, warmup, fence, min_time=0.0, reduce_max=None, profile=True):
     """W warm-up steps, a short PROFILE region (two HIP events around every launch -> the per-kernel table; untimed:
     those events cost a step about 2 %), then `steps` timed steps between two fences (barrier + device sync) with
     events around the launches of the dominant kernel only (its live average duration: the roofline).
+    profile=False (a plain run): the same steps without any event — the profile region is a settle run only — and
+    bench.profile = bench.dom = None.
     min_time > 0: if the timed region was shorter, it is repeated as ONE region of r x steps steps with
     r = ceil(min_time / elapsed) — every rank derives r from the same max-over-ranks figure — and that
     longer region is what is reported.  -> (elapsed of this rank, steps actually timed);
@@ -416,8 +431,9 @@ def time_steps(bench, steps, warmup, fence, min_time=0.0, reduce_max=None):
 
     def region(k, only):
         fence()
-        ctx.timing(True, only=only)
-        ctx.timing_reset()
+        if profile:
+            ctx.timing(True, only=only)
+            ctx.timing_reset()
         ctx.gram_stats(reset=True)
         ctx.cqr2_stats(reset=True)
         t0 = time.perf_counter()
@@ -426,12 +442,14 @@ def time_steps(bench, steps, warmup, fence, min_time=0.0, reduce_max=None):
         ctx.sync()
         el = time.perf_counter() - t0
         fence()
+        if not profile:
+            return el, None
         tm = ctx.timing_read()
         ctx.timing(False)
         return el, tm
     kp = max(2, min(steps, 10))
     _, prof = region(kp, None)
-    dom = max(prof, key=lambda k: prof[k][0])
+    dom = max(prof, key=lambda k: prof[k][0]) if profile else None
     elapsed, tm = region(steps, dom)
     if min_time > 0.0:
         seen = reduce_max(elapsed) if reduce_max else elapsed
@@ -439,8 +457,8 @@ def time_steps(bench, steps, warmup, fence, min_time=0.0, reduce_max=None):
             reps = int(min(400, max(2, -(-min_time // max(seen, 1e-6)))))
             steps = steps * reps
             elapsed, tm = region(steps, dom)
-    bench.profile = (prof, kp)
-    bench.dom = (dom, tm[dom])
+    bench.profile = (prof, kp) if profile else None
+    bench.dom = (dom, tm[dom]) if profile else None
     return elapsed, steps
 
 
@@ -451,13 +469,34 @@ def profile_table(bench):
 
 
 def record(bench, cfg_name, elapsed, steps, warmup, world, probe):
-    """The JSON record of one timed config (rank 0)."""
+    """The JSON record of one timed config (rank 0).  Without a profile region (a plain run: bench.profile is None)
+    the headline keys only — no roofline, no per-kernel table."""
     ctx = bench.ctx
     kind, B, m, n = bench.kind, bench.B, bench.m, bench.n
     akind = "dogbox" if kind == "dogbox" else "trf"
     units = (1 if kind == "tsqr" else B * world) * steps         # step-solves in the timed region
     value = units / elapsed
     ms_per_step = 1e3 * elapsed / steps
+    gs = ctx.gram_stats()
+    metric = ("dogbox" if kind == "dogbox" else "TRF") + " step-solves/sec (batched m x n dense Jacobian)"
+    out = {
+        "metric": metric, "value": value, "unit": "step-solves/s", "n_gpus": world, "steps": steps,
+        "warmup": warmup, "ms_per_step": ms_per_step, "higher_is_better": True,
+        "scaling": "weak", "vs_baseline": None, "dtype": "f64", "data": "synthetic",
+        "config": {"workload": "%s, %d problem%s per GPU, %s, inputs resident in HBM" % (
+                       CONFIGS[cfg_name]["label"] if (m, n) == (CONFIGS[cfg_name]["m"], CONFIGS[cfg_name]["n"])
+                       else "%s step-solve, m=%d n=%d" % (akind, m, n), B, "" if B == 1 else "s",
+                       ("Delta = 0.02" if kind == "dogbox" else "Delta mix 10/0.5 (reflective/feasible)")
+                       + ("; two input sets alternate between calls" if bench.d2 is not None else
+                          "; the same inputs every step (best case of the optimistic device API: its guess always holds)")),
+                   "name": cfg_name, "m": m, "n": n, "batch_per_gpu": B,
+                   "sharding": ("by rows: %d rows per rank, one ncclAllReduce of the Gram per factor call"
+                                % m) if kind == "tsqr" else "by problem, no collective"},
+    }
+    paths = {"normal_equations": gs[0], "householder_tree": gs[1]}
+    if bench.profile is None:
+        out["factorisation_paths"] = paths
+        return out
     per_step_ms = profile_table(bench)                           # (every slot: the profile region)
     dom, (dom_total_ms, dom_launches) = bench.dom                # (the dominant kernel: live, over the timed region)
     dom_ms = dom_total_ms / steps                                # dominant kernel, per step
@@ -519,28 +558,39 @@ def record(bench, cfg_name, elapsed, steps, warmup, world, probe):
                     "SURVEY 8(d) bytes x problems / ms_per_step and Gram flops x problems / ms_per_step" % dom})
         if probe:
             roof["peak_measured"] = probe
-    gs = ctx.gram_stats()
-    metric = ("dogbox" if kind == "dogbox" else "TRF") + " step-solves/sec (batched m x n dense Jacobian)"
-    return {
-        "metric": metric, "value": value, "unit": "step-solves/s", "n_gpus": world, "steps": steps,
-        "warmup": warmup, "ms_per_step": ms_per_step, "higher_is_better": True,
-        "scaling": "weak", "vs_baseline": None, "dtype": "f64", "data": "synthetic",
-        "config": {"workload": "%s, %d problem%s per GPU, %s, inputs resident in HBM" % (
-                       CONFIGS[cfg_name]["label"] if (m, n) == (CONFIGS[cfg_name]["m"], CONFIGS[cfg_name]["n"])
-                       else "%s step-solve, m=%d n=%d" % (akind, m, n), B, "" if B == 1 else "s",
-                       ("Delta = 0.02" if kind == "dogbox" else "Delta mix 10/0.5 (reflective/feasible)")
-                       + ("; two input sets alternate between calls" if bench.d2 is not None else
-                          "; the same inputs every step (best case of the optimistic device API: its guess always holds)")),
-                   "name": cfg_name, "m": m, "n": n, "batch_per_gpu": B,
-                   "sharding": ("by rows: %d rows per rank, one ncclAllReduce of the Gram per factor call"
-                                % m) if kind == "tsqr" else "by problem, no collective"},
-        "roofline": roof,
-        "factorisation_paths": {"normal_equations": gs[0], "householder_tree": gs[1]},
-        "kernels_ms_per_step": per_step_ms,
-        "kernels_note": "the dominant slot: HIP events over the timed region; the others: a profile region of %d "
-                        "steps before it (events around every launch cost a step about 2 %%, so the timed region "
-                        "carries them for the dominant kernel only)" % bench.profile[1],
-    }
+    out["roofline"] = roof
+    out["factorisation_paths"] = paths
+    out["kernels_ms_per_step"] = per_step_ms
+    out["kernels_note"] = ("the dominant slot: HIP events over the timed region; the others: a profile region of %d "
+                           "steps before it (events around every launch cost a step about 2 %%, so the timed region "
+                           "carries them for the dominant kernel only)" % bench.profile[1])
+    return out
+
+
+DUMP_MAX_BYTES = 60_000_000        # (--dump-outputs: under 64 MB in all, .npy headers included)
+
+
+def dump_outputs(bench, outdir):
+    """--dump-outputs: the outputs of the last factor call and step of `bench` -> outdir/<name>.npy (float64), a
+    fixed seeded sample of the problems if they exceed DUMP_MAX_BYTES in all."""
+    from bounded_lsq._hip_step import TrfStepOut
+    s = bench.sol.fetch_step()
+    fields = dict(bench.sol.fetch_factor()._asdict())
+    if bench.kind == "dogbox":
+        fields.update(s._asdict())
+    else:                                                      # (what step() returns, not the debug detail)
+        fields.update((k, getattr(s, k)) for k in TrfStepOut._fields)
+    arrays = {k: np.asarray(v, dtype=np.float64) for k, v in fields.items()}
+    B = next(iter(arrays.values())).shape[0]
+    per_problem = sum(a.nbytes for a in arrays.values()) // B
+    if per_problem * B > DUMP_MAX_BYTES:
+        keep = DUMP_MAX_BYTES // (per_problem + 8)
+        idx = np.sort(np.random.default_rng(20240607).choice(B, keep, replace=False))
+        arrays = {k: a[idx] for k, a in arrays.items()}
+        arrays["problem_index"] = idx.astype(np.float64)
+    os.makedirs(outdir, exist_ok=True)
+    for k, a in arrays.items():
+        np.save(os.path.join(outdir, k + ".npy"), a)
 
 
 def side_run(name, ctx, steps, warmup, probe, **kw):
@@ -597,11 +647,18 @@ def main():
     ap.add_argument("--no-cpu", action="store_true", help="skip the CPU baseline leg")
     ap.add_argument("--no-h2d", action="store_true", help="skip the host-pointer (PCIe-inclusive) leg")
     ap.add_argument("--no-probe", action="store_true", help="skip the measured-peak probes")
-    ap.add_argument("--check", type=int, default=2, help="problems checked against the oracle")
+    ap.add_argument("--check", type=int, default=None,
+                    help="problems checked against the oracle (default: 2 with --full, none otherwise)")
     ap.add_argument("--min-time", type=float, default=None,
-                    help="shortest timed region in seconds (default: 5 for the headline config, 1 otherwise): a shorter "
-                         "--steps region is repeated as one region of r x steps steps (reported as `steps`, with "
-                         "`steps_requested`); 0: exactly --steps")
+                    help="shortest timed region in seconds (default: exactly --steps when it is given; otherwise 5 for "
+                         "the headline config, 1 for the others): a shorter region is repeated as one region of "
+                         "r x steps steps (reported as `steps`, with `steps_requested`); 0: exactly the steps")
+    ap.add_argument("--full", action="store_true",
+                    help="also everything beside the headline figure: per-kernel table and roofline with the measured "
+                         "peaks, parity against the oracle, the side configs and legs, the CPU baseline, and at N > 1 "
+                         "the communicator and the tall problem over all ranks")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the outputs of the last timed step as DIR/<name>.npy (float64)")
     ap.add_argument("--cpu-child", type=int, default=None, help=argparse.SUPPRESS)   # (internal: the CPU leg's process)
     args = ap.parse_args()
     if args.cpu_child is not None:
@@ -633,7 +690,10 @@ def main():
     local_rank = int(os.environ.get("LOCAL_RANK", "0"))
     main_line = name == "c2" and not (args.m or args.n)
     if args.min_time is None:
-        args.min_time = 5.0 if main_line else 1.0
+        args.min_time = 0.0 if args.steps is not None else (5.0 if main_line else 1.0)
+    if args.check is None:
+        args.check = 2 if args.full else 0
+    full = args.full
     if args.gpus != world and rank == 0:
         print("bench.py: --gpus %d but the launcher started %d rank(s): reporting n_gpus = %d"
               % (args.gpus, world, world), file=sys.stderr)
@@ -699,7 +759,7 @@ def main():
         return [float(x.item()) for x in g]
 
     probe = None
-    if not args.no_probe:
+    if full and not args.no_probe:
         try:
             probe = {"mfma_f64_tflops": ctx.probe("mfma_f64", 2)[0],
                      "hbm_copy_gbs": ctx.probe("copy", 1024)[0],
@@ -731,8 +791,10 @@ def main():
             raise RuntimeError("c5 at N > 1 needs the RCCL communicator: %s" % comm_error)
     bench = Bench(name, ctx, rank, world, batch=args.batch, m=args.m, n=args.n, comm_ready=comm_ready)
     steps_requested = steps
-    own_elapsed, steps = time_steps(bench, steps, warmup, fence, args.min_time, max_over_ranks)
+    own_elapsed, steps = time_steps(bench, steps, warmup, fence, args.min_time, max_over_ranks, profile=full)
     elapsed = max_over_ranks(own_elapsed)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(bench, args.dump_outputs)                 # (before any other leg touches the plan)
     out = record(bench, name, elapsed, steps, warmup, world, probe) if rank == 0 else None
     per_rank = all_ranks(own_elapsed)
     if out is not None:
@@ -740,7 +802,7 @@ def main():
         units_rank = (1 if bench.kind == "tsqr" else bench.B) * steps
         out["per_rank"] = {"elapsed_s": per_rank, "step_solves_per_s": [units_rank / e for e in per_rank],
                            "note": "each rank's own clock over the same fenced region; `value` uses the max"}
-    if world > 1 and not comm_ready:
+    if world > 1 and not comm_ready and full:
         # The batch configs have no data-path collective and their `value` is in hand; NOW — never in front of the
         # timed region — every N > 1 run also brings up the library's RCCL communicator, so that the line shows which
         # librccl the ranks resolved and that it spans them all (the `c5_tsqr` leg below then reuses it).
@@ -754,7 +816,7 @@ def main():
 
     extras = {}
     side_hung = False
-    if world == 1 and main_line:
+    if world == 1 and main_line and full:
         B, m, n = bench.B, bench.m, bench.n
         if not args.no_householder:
             # the same workload with the normal-equations front end off: every problem through the
@@ -916,7 +978,7 @@ def main():
                     side_hung = True
                     break
             extras["side_configs"] = side
-    if world > 1 and main_line and not args.no_side and not comm_hung:
+    if world > 1 and main_line and full and not args.no_side and not comm_hung:
         # the tall problem of config 5 over ALL ranks (250 000 rows each): the library's own RCCL
         # communicator, Gram all-reduce inside blsq_tsqr_factor_dev.  A side figure: guarded, timed out.
         def c5_leg():
@@ -957,13 +1019,13 @@ def main():
             # this ctx (a helper thread may still sit in the stuck collective), no teardown, no re-exec.
             os._exit(3)
 
-    if world == 1 and main_line and not args.no_h2d and not side_hung:
+    if world == 1 and main_line and full and not args.no_h2d and not side_hung:
         # (the last GPU leg: its numpy callbacks wake the BLAS thread pool, whose workers then spin for tens of
         #  milliseconds on the box's CPU share — measured: a latency-bound side leg that followed at once ran at HALF
         #  speed; the CPU leg below waits a moment for them to go back to sleep)
         front_end_leg()
         time.sleep(1.0)
-    if rank == 0 and world == 1 and not args.no_cpu and main_line and not side_hung:
+    if rank == 0 and world == 1 and full and not args.no_cpu and main_line and not side_hung:
         # The CPU leg LAST, after every GPU leg (so that the GPU work of this run is contiguous), and in a child
         # process of its own: this one has initialised the GPU and must not fork worker pools.
         try:
@@ -999,7 +1061,8 @@ def main():
                 digest[k] = [round(extras[k]["value"], 1), round(extras[k]["ms_per_step"], 4), None]
         if "c5_tsqr" in extras and isinstance(extras["c5_tsqr"], dict) and "value" in extras["c5_tsqr"]:
             digest["c5_tsqr"] = [round(extras["c5_tsqr"]["value"], 1), round(extras["c5_tsqr"]["ms_per_step"], 4), None]
-        out["side_summary"] = digest
+        if full:
+            out["side_summary"] = digest
         print(json.dumps(out), flush=True)
     if comm_hung:
         # the communicator's bring-up never came back (its helper thread still sits in librccl): the line is out and

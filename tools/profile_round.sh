@@ -10,7 +10,7 @@ cd /tmp && export TMPDIR=/tmp && cd "$GRAFT_REPO_ROOT" || exit 1
 O=gpurun_out
 SHORT="--no-cpu --no-householder --no-side --no-h2d --no-probe --check 0 --min-time 0"
 if [ "$2" != "nobench" ]; then
-timeout -k 10 600 python bench.py > $O/${TAG}_bench.json 2> $O/${TAG}_bench.err || exit 1
+timeout -k 10 600 python bench.py --full > $O/${TAG}_bench.json 2> $O/${TAG}_bench.err || exit 1
 tail -c 400 $O/${TAG}_bench.json; echo
 fi
 timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/${TAG}_stats -o run -- python3 bench.py --steps 20 --warmup 2 $SHORT > $O/${TAG}_stats.log 2>&1 || exit 1
