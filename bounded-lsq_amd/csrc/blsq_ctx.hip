@@ -10,15 +10,10 @@ __global__ void publish_ints_kernel(const int* __restrict__ src, int n, int* dst
   publish_ints(PublishArgs{src, n, dst, seq});
 }
 
-hipError_t blsq_ctx::publish(const int* src, int n, int* slot, hipEvent_t ev, int* expect) {
-    if (!pub_direct()) {
-      hipError_t e = hipMemcpyAsync(slot, src, n * sizeof(int), hipMemcpyDeviceToHost, stream);
-      if (e == hipSuccess) e = hipEventRecord(ev, stream);
-      return e;
-    }
-    *expect = ++pub_seq;
-    hipLaunchKernelGGL(publish_ints_kernel, dim3(1), dim3(64), 0, stream, src, n, slot, *expect);
-    return hipGetLastError();
+hipError_t blsq_ctx::publish(const int* src, int n, int* slot, int* expect) {
+  *expect = ++pub_seq;
+  hipLaunchKernelGGL(publish_ints_kernel, dim3(1), dim3(64), 0, stream, src, n, slot, *expect);
+  return hipGetLastError();
 }
 
 namespace blsq_host {
@@ -71,8 +66,7 @@ extern "C" int blsq_ctx_create(int device_id, blsq_ctx** out) {
   if (e != hipSuccess) { hipStreamDestroy(c->stream); delete c; return (int)e; }
   memset(c->pinned, 0, 128 * sizeof(int));
   c->opt = options_from_env();
-  for (int i = 0; i < 2 && e == hipSuccess; ++i) e = hipEventCreateWithFlags(&c->lm_ev[i], hipEventDisableTiming);
-  if (e == hipSuccess) e = hipMalloc((void**)&c->cq_accept_dev, sizeof(unsigned long long));
+  e = hipMalloc((void**)&c->cq_accept_dev, sizeof(unsigned long long));
   if (e == hipSuccess) e = hipMemset(c->cq_accept_dev, 0, sizeof(unsigned long long));
   if (e != hipSuccess) { hipHostFree(c->pinned); hipStreamDestroy(c->stream); delete c; return (int)e; }
   *out = c;
@@ -87,7 +81,6 @@ extern "C" int blsq_ctx_destroy(blsq_ctx* ctx) {
   if (ctx->comm && g_rccl.CommDestroy) g_rccl.CommDestroy(ctx->comm);
   ctx->comm = nullptr;
   for (auto e : ctx->pool) hipEventDestroy(e);
-  for (auto e : ctx->lm_ev) if (e) hipEventDestroy(e);
   for (auto e : ctx->copy_ev) hipEventDestroy(e);
   if (ctx->copy_stream) hipStreamDestroy(ctx->copy_stream);
   hipStreamDestroy(ctx->stream);

@@ -78,17 +78,13 @@ int dog_put(blsq_dogbox_plan* p, const double* x, const double* lb, const double
   blsq_ctx* ctx = p->ctx;
   int rc;
   if (kind == hipMemcpyDeviceToDevice) {
+    p->pack_pend = zero_counts && p->tree.gram;          // (the Gram stage's prep launch does it: dog_factor_core)
+    p->tree.fb_zeroed = p->pack_pend;
     PackVecs pv{{x, lb, ub, scale, on_bound}, {p->st.x, p->st.lb, p->st.ub, p->st.scale, p->st.on_bound},
-                (zero_counts && p->tree.gram) ? p->tree.fb_count() : nullptr, 3};
-    p->pack_pend = false;
-    if (zero_counts && p->tree.gram && ctx->fuse_pack()) {   // (the Gram stage's prep launch does it: dog_factor_core)
-      p->pack_pv = pv; p->pack_pend = true;
-      p->tree.fb_zeroed = true;
-      return 0;
-    }
+                p->pack_pend ? p->tree.fb_count() : nullptr, 3};
+    if (p->pack_pend) { p->pack_pv = pv; return 0; }
     hipError_t e = launch_pack_vecs(pv, p->n, p->ld, p->B, ctx->stream);
     if (e != hipSuccess) return ctx->fail(e, "launch_pack_vecs");
-    p->tree.fb_zeroed = zero_counts && p->tree.gram;
     return 0;
   }
   if ((rc = put_vec(ctx, p->st.x, p->ld, x, p->n, p->B, kind))) return rc;
@@ -358,8 +354,7 @@ int dog_factor_core(blsq_dogbox_plan* p, const double* dJ, const double* df, int
   e = launch_gram_chol(c, p->B, ctx->stream);
   ctx->end();
   if (e != hipSuccess) return ctx->fail(e, "launch_gram_chol(free block)");
-  const bool defer = may_defer && !mask && verdict_may_guess(p) && p->svdfree_enable && p->pend_pin &&
-                     p->pend_ev;
+  const bool defer = may_defer && !mask && verdict_may_guess(p) && p->svdfree_enable && p->pend_pin;
   // second guess (N <= 80): the Cholesky kernel settles EVERY problem itself, as it did in the last call —
   // then the certificate, gate and solve launches would all be empty and are not enqueued at all
   const bool skip_tail = defer && p->guess_settled && c.dog.g != nullptr;
@@ -367,7 +362,7 @@ int dog_factor_core(blsq_dogbox_plan* p, const double* dJ, const double* df, int
   if (!skip_tail && (rc = dog_gate_tail(p, c))) return rc;
   int nfb = 0;
   if (defer) {                              // guess: nobody leaves the path, nobody needs the SVD (dog_resolve checks)
-    if ((rc = verdict_arm(p, skip_tail, dJ, df, ldJ, scale_mode))) return rc;
+    verdict_arm(p, skip_tail, dJ, df, ldJ, scale_mode);
   } else {
     HIPCHK(ctx, hipMemcpyAsync(ctx->pinned + 1, t.fb_count(), 3 * sizeof(int), hipMemcpyDeviceToHost,
                                ctx->stream));
@@ -409,7 +404,6 @@ extern "C" int blsq_dogbox_plan_create(blsq_ctx* ctx, int B, int m, int n,
     p->optimistic = ctx->opt.on(OPT_OPTIMISTIC);
     hipError_t e = hipHostMalloc((void**)&p->pend_pin, 4 * sizeof(int), hipHostMallocCoherent);
     if (e == hipSuccess) memset(p->pend_pin, 0, 4 * sizeof(int));
-    if (e == hipSuccess) e = hipEventCreateWithFlags(&p->pend_ev, hipEventDisableTiming);
     if (e != hipSuccess) rc = ctx->fail(e, "optimistic-verdict resources");
   }
   if (rc != 0) { blsq_dogbox_plan_destroy(p); return rc; }
@@ -425,7 +419,6 @@ extern "C" int blsq_dogbox_plan_destroy(blsq_dogbox_plan* p) {
   hipStreamSynchronize(p->ctx->stream);
   { auto& v = p->ctx->dog_plans; v.erase(std::remove(v.begin(), v.end(), p), v.end()); }
   if (p->pend_pin) hipHostFree(p->pend_pin);
-  if (p->pend_ev) hipEventDestroy(p->pend_ev);
   p->tree.release();
   p->S.release(); p->X.release(); p->vecs.release(); p->ivecs.release(); p->scal2.release();
   p->sweeps.release(); p->active.release(); p->onb.release(); p->o_vec.release();

@@ -71,10 +71,6 @@ struct blsq_ctx {
                                     // ([0..3] one-shot read-backs, [32 + 4 r ..] the slot of Newton round r)
   int pub_seq = 0;                  // sequence number of the last publish()
   blsq::Options opt;                // the switches of this ctx (blsq_options.h: environment at creation, blsq_ctx_set_option)
-  bool pub_direct() const { return opt.on(OPT_PUBLISH); }        // 0: hipMemcpyAsync + event instead of the publishing kernel
-  bool fuse_pack() const { return opt.on(OPT_FUSE_PACK); }       // 0: the caller's vectors are packed by a launch of their own
-  bool pub_ride() const { return opt.on(OPT_PUBLISH_RIDE); }     // 0: the verdict's counters get a publishing launch of their own
-  hipEvent_t lm_ev[2] = {nullptr, nullptr};   // read-back of the counter of round r has landed (r & 1)
   long long gram_fast = 0, gram_fallback = 0;   // problems factored by the normal equations / handed to the QR tree
   unsigned long long* cq_accept_dev = nullptr;  // device counter: rejected problems the CholeskyQR2 tier factored
   // CSNE tier (csne_kernels.hip): problems routed to it by factor calls, step-solves it delivered, step-solves it
@@ -92,12 +88,10 @@ struct blsq_ctx {
     err = std::string(where) + ": " + hipGetErrorString(e);
     return (int)e;
   }
-  // n <= 3 device ints -> the 16-byte pinned slot `slot` ([3] = sequence number, returned in *expect); `ev` is
-  // recorded on the blit route only
-  hipError_t publish(const int* src, int n, int* slot, hipEvent_t ev, int* expect);   // (blsq_ctx.hip)
+  // n <= 3 device ints -> the 16-byte pinned slot `slot` ([3] = sequence number, returned in *expect)
+  hipError_t publish(const int* src, int n, int* slot, int* expect);   // (blsq_ctx.hip)
   // ... and the wait for it: polls the slot; looks at the stream now and then so that a failed launch cannot hang it
-  hipError_t await(const int* slot, hipEvent_t ev, int expect) {
-    if (!pub_direct()) return hipEventSynchronize(ev);
+  hipError_t await(const int* slot, int expect) {
     for (unsigned long it = 1;; ++it) {
       if (__atomic_load_n(slot + 3, __ATOMIC_ACQUIRE) == expect) return hipSuccess;
       if ((it & 0x3fff) == 0) {
@@ -649,12 +643,10 @@ struct VerdictState {
   // and gate launches are not even enqueued; checked with the same read-back.
   bool guess_settled = false, pend_tail = false;
   int* pend_pin = nullptr;          // 4 pinned ints of this plan ([3]: sequence number of the publish)
-  hipEvent_t pend_ev = nullptr;
   int pend_seq = 0;
   bool pend_unpub = false;          // the verdict's counters have not been sent yet: the step kernel of the next
                                     // step call stores them on its way in (or verdict_published() sends them now)
   // the caller's vectors of a device-resident factor call, copied into the state layout by the prep launch
-  // (option `fuse_pack` = 0: by a pack_vecs launch in front of the Gram)
   bool pack_pend = false;
   PackVecs pack_pv{};
   const double* pend_dJ = nullptr; const double* pend_df = nullptr;
@@ -712,7 +704,6 @@ struct blsq_trf_plan : VerdictState {
   // written them (zeroed at allocation); the stacked QR and the Jacobi SVD write there.  While clean, the
   // Cholesky of the augmented system does not store those zeros again (half of its bytes).
   bool x_dirty = true;
-  int lm_expect0 = 0;               // problems the first Newton round of the last step call worked on (kernel choice hint)
   int lm_rounds_last = 12;          // Newton rounds that had work in the last step call (run-ahead only over those)
   int njac = -1;                    // problems it sent to the Jacobi SVD (-1: unknown)
 };
@@ -771,7 +762,7 @@ int verdict_published(Plan* p) {
   if (!p->pend_unpub) return 0;
   p->pend_unpub = false;
   blsq_ctx* ctx = p->ctx;
-  HIPCHK(ctx, ctx->publish(p->tree.fb_count(), 3, p->pend_pin, p->pend_ev, &p->pend_seq));
+  HIPCHK(ctx, ctx->publish(p->tree.fb_count(), 3, p->pend_pin, &p->pend_seq));
   return 0;
 }
 // ... and the arguments with which the step kernel of this call takes them along (dst == nullptr: nothing to do)
@@ -809,7 +800,7 @@ int verdict_drop(Plan* p) {
   blsq_ctx* ctx = p->ctx;
   p->pending = false;
   { int rc_ = verdict_published(p); if (rc_) return rc_; }
-  HIPCHK(ctx, ctx->await(p->pend_pin, p->pend_ev, p->pend_seq));
+  HIPCHK(ctx, ctx->await(p->pend_pin, p->pend_seq));
   const int nfb_ = p->pend_pin[0], njac_ = p->pend_pin[1];
   if (p->pend_tail) { if (!verdict_settled(p)) p->guess_settled = false; }
   else if (nfb_ > 0 || njac_ > 0) {
@@ -820,18 +811,16 @@ int verdict_drop(Plan* p) {
   return 0;
 }
 
-// The counters of this factor call travel (or ride on the next step kernel); the verdict is read by verdict_resolve.
-// skip_tail: the second guess — the gate launches were not enqueued.
+// The counters of this factor call ride on the next step kernel (verdict_rides; verdict_published sends them if nothing
+// took them along); the verdict is read by verdict_resolve.  skip_tail: the second guess — the gate launches were not
+// enqueued.
 template <class Plan>
-int verdict_arm(Plan* p, bool skip_tail, const double* dJ, const double* df, int ldJ, int scale_mode) {
-  blsq_ctx* ctx = p->ctx;
-  p->pend_unpub = ctx->pub_direct() && ctx->pub_ride();
-  if (!p->pend_unpub) HIPCHK(ctx, ctx->publish(p->tree.fb_count(), 3, p->pend_pin, p->pend_ev, &p->pend_seq));
+void verdict_arm(Plan* p, bool skip_tail, const double* dJ, const double* df, int ldJ, int scale_mode) {
+  p->pend_unpub = true;
   p->pending = true; p->pend_tail = skip_tail;
   p->pend_dJ = dJ; p->pend_df = df; p->pend_ldJ = ldJ; p->pend_scale_mode = scale_mode;
   p->gate_done = true;
   p->njac = 0;
-  return 0;
 }
 
 // The verdict of an optimistic factor call.  *redo = false: nothing was pending, or the guess held.  *redo = true: it
@@ -846,7 +835,7 @@ int verdict_resolve(Plan* p, bool* redo, GateTail gate_tail, Repair repair) {
   QrTree& t = p->tree;
   p->pending = false;
   { int rc_ = verdict_published(p); if (rc_) return rc_; }
-  HIPCHK(ctx, ctx->await(p->pend_pin, p->pend_ev, p->pend_seq));
+  HIPCHK(ctx, ctx->await(p->pend_pin, p->pend_seq));
   int nfb = p->pend_pin[0], njac = p->pend_pin[1];
   const bool settled = verdict_settled(p);
   if (p->pend_tail) {

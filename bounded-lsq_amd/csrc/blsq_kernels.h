@@ -91,7 +91,7 @@ struct GramCholArgs {
                           // zeros there and its readers never look: the Newton-round factors, read by the
                           // triangular solves only) — half of the bytes a factorisation stores are those zeros
   const int* count_dev;   // optional [1]: the launch is over an upper bound; entries beyond *count_dev leave
-  int expect;             // > 0: number of problems the launch is expected to work on (kernel choice; default: its size)
+  const Options* opt;     // host only: the ctx's switches (nullptr: the table's defaults)
   // optional principal sub-matrix (dogbox: free columns ++ rhs): H = Gsrc[idx, idx] with
   // idx = gather[b][0 .. N_b-2] ++ [n], N_b = ncols_dev[b] (0: nothing to do); gather is increasing
   const int* ncols_dev;   // [B]
@@ -165,7 +165,6 @@ struct GramCholArgs {
   int* unsettled;
   double* pmin_out;       // optional [B] out: the smallest squared pivot of R' the factorisation met (the CSNE tier's
                           // own floor is far below the gate's, csne_kernels.hip); not written by a shifted launch
-  const Options* opt;     // host only: the ctx's switches (nullptr: the table's defaults)
 };
 // A problem stays on the normal-equations path only if the PROVEN bound K2 >= kappa_2(R'^T R') of its
 // equilibrated system is at most GRAM_K2_MAX (chol_kernels.hip, gram_cond_kernel).  Consequence used

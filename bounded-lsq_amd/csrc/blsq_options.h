@@ -18,19 +18,13 @@ enum Opt {
   OPT_SVDFREE_MIN_N,       // Householder-path problems with 16 < n < this use the Jacobi SVD (0: no band)
   OPT_GRAM_K2_MAX,         // > 0: a TIGHTER gate than gram_k2_max(m) (it can only tighten)
   // ---- per call
-  OPT_PUBLISH,             // device counters to the host by a publishing store; 0: hipMemcpyAsync + event
-  OPT_FUSE_PACK,           // the caller's vectors packed by the prep launch; 0: a pack launch of their own
-  OPT_PUBLISH_RIDE,        // counters ride on a kernel that runs anyway; 0: a publishing launch of their own
   OPT_CERT0,               // stage 0 of the certificate (comparison-matrix bound); 0: the norm stage for every problem
   OPT_CERT_DIRECT,         // open pure-Jacobian systems go to the shifted factorisation directly; 0: through the norm stage
-  OPT_SETTLE0,             // second guess for N > 80 (empty gate launches left out); 0: always enqueued
   OPT_LM_CHOL_QRPATH,      // Newton systems of Householder-path problems by Cholesky where alpha allows; 0: stacked QR
   OPT_LM_FUSED,            // N <= 80: all Newton rounds of a problem in one launch; 0: lock-step rounds
   OPT_H2D_PIPE,            // host-pointer API: -1 sub-batched copies for page-locked sources only, 0 never, 1 always
   // ---- kernel selection (same bits whatever the choice unless noted)
-  OPT_CHOL_REG,            // N <= 80: register-resident right-looking Cholesky; 0: left-looking one-wave kernel
-  OPT_CHOL_RL,             // N > 80: -1 right-looking (default), 0 left-looking, 1 right-looking
-  OPT_CHOL_RL2,            // N > 80 right-looking: flag-driven kernel; 0: barrier-synchronous one
+  OPT_CHOL_RL,             // N > 80: right-looking flag-driven kernel; 0: the left-looking reference kernel
   OPT_GRAM16,              // 16 column tiles: static tile rows per wave; 0: the generic Gram kernel
   OPT_GRAM8,               // 8 column tiles: k-split static-tile kernel; 0: generic (ANOTHER summation order)
   OPT_GRAM_PAIR,           // two row chunks summed inside the kernel; 0: reduction pass

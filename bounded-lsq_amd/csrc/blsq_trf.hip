@@ -272,10 +272,7 @@ int trf_gram_stage(blsq_trf_plan* p, int scale_mode, const int* mask, int* nfb, 
   // N > 80: stage 0 of the certificate is still launched (it IS what settles a problem there) — the norm stage, the
   // shifted factorisation and the rank gate, three launches that would find nothing to do, are not.
   bool skip_tail = defer && p->guess_settled && c.lmfin.fast != nullptr;
-  if (skip_tail && p->ld > 80) {
-    // (settle0 = 0: the whole gate tail for N > 80, as before)
-    if (!c.cert_ym || !ctx->opt.on(OPT_CERT0) || !ctx->opt.on(OPT_SETTLE0)) skip_tail = false;
-  }
+  if (skip_tail && p->ld > 80 && (!c.cert_ym || !ctx->opt.on(OPT_CERT0))) skip_tail = false;
   int rc;
   if (skip_tail) {
     p->lm.path = t.path_rw();
@@ -288,14 +285,14 @@ int trf_gram_stage(blsq_trf_plan* p, int scale_mode, const int* mask, int* nfb, 
     }
   } else if ((rc = trf_gate_tail(p, c, mask == nullptr))) return rc;
   if (defer) {                              // the counters travel; the verdict is read by trf_resolve
-    if ((rc = verdict_arm(p, skip_tail, p->pend_dJ, p->pend_df, p->pend_ldJ, p->pend_scale_mode))) return rc;
+    verdict_arm(p, skip_tail, p->pend_dJ, p->pend_df, p->pend_ldJ, p->pend_scale_mode);
     *nfb = 0;
   } else {
     // (the synchronous verdict: published and polled for — slot [4 .. 8) of the pinned ints — instead of a blit and a
     //  stream synchronisation)
     int seq = 0;
-    HIPCHK(ctx, ctx->publish(t.fb_count(), 3, ctx->pinned + 4, ctx->lm_ev[0], &seq));
-    HIPCHK(ctx, ctx->await(ctx->pinned + 4, ctx->lm_ev[0], seq));
+    HIPCHK(ctx, ctx->publish(t.fb_count(), 3, ctx->pinned + 4, &seq));
+    HIPCHK(ctx, ctx->await(ctx->pinned + 4, seq));
     *nfb = ctx->pinned[4];
     p->gate_done = (*nfb == 0);
     p->njac = p->gate_done ? ctx->pinned[5] : -1;
@@ -413,8 +410,7 @@ int trf_factor_core(blsq_trf_plan* p, const double* dJ, const double* df, int ld
   if (!mask) p->ncsne = 0;                                // (the prep launch clears every flag; trf_csne_select sets them anew)
   int nfb = 0;
   // (never in the n-band that always takes the SVD, nor right after a wrong guess)
-  const bool defer = may_defer && !mask && verdict_may_guess(p) && p->lm_enable && p->pend_pin &&
-                     p->pend_ev;
+  const bool defer = may_defer && !mask && verdict_may_guess(p) && p->lm_enable && p->pend_pin;
   if ((rc = trf_gram_stage(p, scale_mode, mask, &nfb, defer))) return rc;
   if (defer) { p->pend_dJ = dJ; p->pend_df = df; p->pend_ldJ = ldJ; p->pend_scale_mode = scale_mode; }
   else if (!mask) p->guess_ok = (nfb == 0 && p->njac == 0);
@@ -488,13 +484,13 @@ int trf_lm_rounds(blsq_trf_plan* p, const double* dDelta, const double* dalpha_i
   e = launch_lm_start(p->lm, dDelta, dalpha_in, ctx->stream);
   ctx->end();
   if (e != hipSuccess) return ctx->fail(e, "launch_lm_start");
-  auto read_back = [&](int r) -> hipError_t {            // counter of round r -> pin[r], event r & 1
+  auto read_back = [&](int r) -> hipError_t {            // counter of round r -> pin[r]
     // (a round that is enqueued ahead of its counter takes the counter along: lm_update_kernel of that round stores it)
-    if (ride_rounds > r && ctx->pub_direct() && ctx->pub_ride()) { rides[r] = true; return hipSuccess; }
-    return ctx->publish(counts + r, 1, pin + 4 * r, ctx->lm_ev[r & 1], &pin_seq[r]);
+    if (ride_rounds > r) { rides[r] = true; return hipSuccess; }
+    return ctx->publish(counts + r, 1, pin + 4 * r, &pin_seq[r]);
   };
-  auto landed = [&](int r) -> hipError_t { return ctx->await(pin + 4 * r, ctx->lm_ev[r & 1], pin_seq[r]); };
-  auto chol_round = [&](int round, int grid, int expect, const int* count_dev) -> hipError_t {
+  auto landed = [&](int r) -> hipError_t { return ctx->await(pin + 4 * r, pin_seq[r]); };
+  auto chol_round = [&](int round, int grid, const int* count_dev) -> hipError_t {
     // R_alpha = chol(D G D + E^2 + alpha I) straight from the Gram, active Gram-path problems
     GramCholArgs c{};
     c.opt = &ctx->opt;
@@ -503,7 +499,7 @@ int trf_lm_rounds(blsq_trf_plan* p, const double* dDelta, const double* dalpha_i
     c.batch_list = p->lm.active_list + (size_t)(round & 1) * p->B;
     c.skip_path = p->path;
     c.qr_mask = p->lm.hmax ? p->lm.ncols_lm : nullptr;
-    c.count_dev = count_dev; c.expect = expect;
+    c.count_dev = count_dev;
     c.skip_zero = 1;                                    // (lm_Xa: zeroed at allocation, read by lm_update's solves only)
     ctx->begin(K_LM_CHOL);
     hipError_t ee = launch_gram_chol(c, grid, ctx->stream);
@@ -538,7 +534,6 @@ int trf_lm_rounds(blsq_trf_plan* p, const double* dDelta, const double* dalpha_i
   // problem whose mask is 0.  Their triangles dirty the lm_Xa slots outside the factor: the solves never look.
   if (chol_any) {
     int bound = p->B;                                   // upper bound of the count of the round being enqueued
-    int expect = p->lm_expect0 > 0 ? p->lm_expect0 : p->B;   // (kernel choice only: last call's first count)
     // Rounds that had work in the LAST call of this plan are enqueued ahead of their counter, as described
     // above; from the first round that was empty last time on, the host looks at the counter first — the
     // GPU idles for one host round trip (~10 us) instead of running a round of three empty launches.
@@ -549,11 +544,10 @@ int trf_lm_rounds(blsq_trf_plan* p, const double* dDelta, const double* dalpha_i
       if (!ahead) {
         HIPCHK(ctx, landed(round));
         const int active = pin[4 * round];
-        if (round == 0) p->lm_expect0 = active > 0 ? active : -1;
         if (active == 0) break;
-        bound = expect = active;
+        bound = active;
       }
-      e = chol_round(round, bound, expect, counts + round);
+      e = chol_round(round, bound, counts + round);
       if (e != hipSuccess) return ctx->fail(e, "launch_gram_chol(lm)");
       if (p->use_qr) {
         e = qr_round(round, bound, counts + round);
@@ -573,9 +567,8 @@ int trf_lm_rounds(blsq_trf_plan* p, const double* dDelta, const double* dalpha_i
       if (ahead) {
         HIPCHK(ctx, landed(round));
         const int active = pin[4 * round];                  // what round `round` really worked on
-        if (round == 0) p->lm_expect0 = active > 0 ? active : -1;
         if (active == 0) break;                         // (the round just enqueued is empty)
-        bound = expect = active;
+        bound = active;
       }
       done_rounds = round + 1;
     }
@@ -589,7 +582,7 @@ int trf_lm_rounds(blsq_trf_plan* p, const double* dDelta, const double* dalpha_i
   for (int round = 0; round < 12 && active > 0; ++round) {
     p->lm_rounds_done = round + 1;
     if (p->use_chol && !p->lm.fused_gram) {
-      e = chol_round(round, active, active, nullptr);
+      e = chol_round(round, active, nullptr);
       if (e != hipSuccess) return ctx->fail(e, "launch_gram_chol(lm)");
     }
     if (p->use_qr) {
@@ -648,8 +641,8 @@ int trf_csne_verdict(blsq_trf_plan* p, int ncs, bool* redo) {
   CsneState& cs = p->cs;
   QrTree& t = p->tree;
   int seq = 0;
-  HIPCHK(ctx, ctx->publish(cs.counts + 1, 1, ctx->pinned + 12, ctx->lm_ev[0], &seq));
-  HIPCHK(ctx, ctx->await(ctx->pinned + 12, ctx->lm_ev[0], seq));
+  HIPCHK(ctx, ctx->publish(cs.counts + 1, 1, ctx->pinned + 12, &seq));
+  HIPCHK(ctx, ctx->await(ctx->pinned + 12, seq));
   const int nfail = ctx->pinned[12];
   ctx->csne_steps += (unsigned long long)(ncs - nfail);
   ctx->csne_declined += (unsigned long long)nfail;
@@ -688,7 +681,6 @@ extern "C" int blsq_trf_plan_create(blsq_ctx* ctx, int B, int m, int n, blsq_trf
     p->optimistic = ctx->opt.on(OPT_OPTIMISTIC);
     hipError_t e = hipHostMalloc((void**)&p->pend_pin, 4 * sizeof(int), hipHostMallocCoherent);
     if (e == hipSuccess) memset(p->pend_pin, 0, 4 * sizeof(int));
-    if (e == hipSuccess) e = hipEventCreateWithFlags(&p->pend_ev, hipEventDisableTiming);
     if (e != hipSuccess) rc = ctx->fail(e, "optimistic-verdict resources");
   }
   if (rc != 0) { blsq_trf_plan_destroy(p); return rc; }
@@ -703,7 +695,6 @@ extern "C" int blsq_trf_plan_destroy(blsq_trf_plan* p) {
   hipStreamSynchronize(p->ctx->stream);
   { auto& v = p->ctx->trf_plans; v.erase(std::remove(v.begin(), v.end(), p), v.end()); }
   if (p->pend_pin) hipHostFree(p->pend_pin);
-  if (p->pend_ev) hipEventDestroy(p->pend_ev);
   p->tree.release(); p->Rcomb.release(); p->Rstack.release();
   p->X.release(); p->vecs.release(); p->scal2.release(); p->sweeps.release();
   p->o_vec.release(); p->o_hits.release(); p->o_act.release(); p->o_scal.release();
@@ -722,18 +713,15 @@ static int trf_put_bounds(blsq_trf_plan* p, const double* x, const double* lb, c
   blsq_ctx* ctx = p->ctx;
   int rc;
   if (kind == hipMemcpyDeviceToDevice) {                // one launch instead of four strided copies
-    // (the two gate counters of the factor call that follows are cleared by the same launch)
+    // (in front of a Gram-stage factor call the prep launch of that stage does it and clears the two gate counters
+    //  of the call: trf_gram_stage)
+    p->pack_pend = zero_counts && p->tree.gram;
+    p->tree.fb_zeroed = p->pack_pend;
     PackVecs pv{{x, lb, ub, scale, nullptr}, {p->st.x, p->st.lb, p->st.ub, p->st.scale, nullptr},
-                (zero_counts && p->tree.gram) ? p->tree.fb_count() : nullptr, 3};
-    p->pack_pend = false;
-    if (zero_counts && p->tree.gram && ctx->fuse_pack()) {   // (the Gram stage's prep launch does it: trf_gram_stage)
-      p->pack_pv = pv; p->pack_pend = true;
-      p->tree.fb_zeroed = true;
-      return 0;
-    }
+                p->pack_pend ? p->tree.fb_count() : nullptr, 3};
+    if (p->pack_pend) { p->pack_pv = pv; return 0; }
     hipError_t e = launch_pack_vecs(pv, p->n, p->ld, p->B, ctx->stream);
     if (e != hipSuccess) return ctx->fail(e, "launch_pack_vecs");
-    p->tree.fb_zeroed = zero_counts && p->tree.gram;
     return 0;
   }
   if ((rc = put_vec(ctx, p->st.x, p->ld, x, p->n, p->B, kind))) return rc;

@@ -1,6 +1,6 @@
 // Factorisation side of the normal-equations path (gram_kernels.hip computes the Grams):
 //
-//   gram_chol_kernel<NWP>, gram_chol_rl_kernel, gram_chol_reg_kernel
+//   gram_chol_reg_kernel, gram_chol_rl2_kernel, gram_chol_kernel
 //                           equilibrated blocked Cholesky of D G D + E^2 (+ alpha I) or of a gathered
 //                           principal sub-matrix, straight from the kept Gram (chol16.h: the 16 x 16 chain)
 //   lm_rounds_reg_kernel    N <= 80: the whole trust-region sub-problem after the factor in one launch
@@ -47,32 +47,18 @@ __device__ __forceinline__ void colinfo_wave(const double* sq, int n, int lane, 
 // whose Cholesky factor is the triangle of [R D | c; E | 0] (and of [R_aug; sqrt(alpha) I]).  With
 // C = equil(G):  equil(H) = Theta^1/2 C Theta^1/2 + (I - Theta),  0 < Theta <= I diagonal, so its
 // extreme eigenvalues lie inside those of C: a problem that passed the gate on C needs no new one.
-// NWP waves work on one problem: 8 (a whole workgroup; any size) or 1 (N <= 80: eight problems per
-// workgroup, no workgroup barrier at all — the 16x16 chain of one problem overlaps the MFMAs of
-// the others on the same SIMD, and sixteen instead of two problems are resident per CU).
-template <int NWP>
+// One workgroup (eight waves) per problem, N > 80: the left-looking reference of gram_chol_rl2_kernel, bit for bit
+// (option chol_rl = 0; no default launch runs it).
 __global__ __launch_bounds__(GR_NT, 4) void gram_chol_kernel(GramCholArgs a) {
-  constexpr int PT = WAVE * NWP;                        // threads per problem
-  constexpr int UMAX = (NWP == 8) ? 3 : 5;              // tiles of a row block per wave
-  constexpr int PPW = GR_NW / NWP;                      // problems per workgroup
-  extern __shared__ double sh_all[];
+  constexpr int UMAX = 3;                               // tiles of a row block per wave
+  extern __shared__ double sh[];
   __shared__ double red[32];
-  __shared__ double pmin_all[GR_NW];
-  const int wv = __builtin_amdgcn_readfirstlane((int)threadIdx.x >> 6);
-  const int pslot = wv / NWP;                           // problem slot inside the workgroup
-  const int pidx = (int)blockIdx.x * PPW + pslot;
-  if (pidx >= a.count) return;                          // (NWP == 1 only: wave-uniform)
+  __shared__ double pminsh;
+  const int pidx = (int)blockIdx.x;
   if (a.count_dev && pidx >= *a.count_dev) return;
   const int b = a.batch_list ? a.batch_list[pidx] : pidx;
-  const int tid = (int)threadIdx.x % PT, lane = tid & 63;
-  const int w = wv % NWP;
-  double* sh = sh_all + (size_t)pslot * (4 * (size_t)a.NPAD + 512);
-  double& pminsh = pmin_all[pslot];
-  // synchronisation among the threads of one problem
-  auto psync = [&]() {
-    if (NWP == 8) __syncthreads();
-    else asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");   // one wave: program order
-  };
+  const int tid = (int)threadIdx.x, lane = tid & 63;
+  const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int lr = lane >> 4, lc = lane & 15;
   const int NPAD = a.NPAD;
   if (a.mask && a.mask[b] <= 1) {
@@ -109,7 +95,7 @@ __global__ __launch_bounds__(GR_NT, 4) void gram_chol_kernel(GramCholArgs a) {
   const double sa = a.diag_sqrt ? a.diag_sqrt[b] : 0.0;
   // 0. column scales from the diagonal of H
   int bad = 0;
-  for (int j = tid; j < NPAD; j += PT) {
+  for (int j = tid; j < NPAD; j += GR_NT) {
     const double cs = (csv && j < n) ? csv[j] : 1.0;
     const double ej = (edv && j < n) ? edv[j] : 0.0;
     const double add = (j < n) ? fma(ej, ej, sa * sa) : 0.0;
@@ -128,13 +114,9 @@ __global__ __launch_bounds__(GR_NT, 4) void gram_chol_kernel(GramCholArgs a) {
     if (a.dsc) a.dsc[(long)b * NPAD + j] = d;
   }
   if (a.colinfo) {                                      // (uniform) column-norm summary for the rank gate
-    psync();
+    __syncthreads();
     double mn = __builtin_inf(), sm = 0.0, mx = 0.0;
-    if (NWP == 8) {
-      if (w == 0) colinfo_wave(sq, n, lane, mn, mx, sm);
-    } else if (tid == 0) {
-      for (int j = 0; j < n; ++j) { const double v = sq[j]; mn = v < mn ? v : mn; mx = v > mx ? v : mx; sm = fma(v, v, sm); }
-    }
+    if (w == 0) colinfo_wave(sq, n, lane, mn, mx, sm);
     if (tid == 0) {
       a.colinfo[2 * (long)b] = mn; a.colinfo[2 * (long)b + 1] = sm;
       if (a.hmax) a.hmax[b] = mx * mx;
@@ -142,13 +124,13 @@ __global__ __launch_bounds__(GR_NT, 4) void gram_chol_kernel(GramCholArgs a) {
     }
   }
   // strictly lower tiles are part of the triangle's image: zero
-  for (int r = 16 + w; r < (a.skip_zero ? 0 : NPAD); r += NWP) {
+  for (int r = 16 + w; r < (a.skip_zero ? 0 : NPAD); r += GR_NW) {
     const int cend = r & ~15;
     for (int c = lane; c < cend; c += WAVE) Gb[(long)r * NPAD + c] = 0.0;
   }
-  if (NWP == 8) bad = block_or(bad, red); else bad = __any(bad);
+  bad = block_or(bad, red);
   if (tid == 0) pminsh = 1.0;
-  psync();
+  __syncthreads();
   if (bad) {                                            // uniform: hand the problem to the QR tree
     if (tid == 0 && a.fb_mask) {
       a.fb_mask[b] = a.n + 1; { const int fi_ = atomicAdd(a.fail_count, 1); if (a.fail_list) a.fail_list[fi_] = b; }   // (the tree factors ALL n + 1 columns)
@@ -159,7 +141,7 @@ __global__ __launch_bounds__(GR_NT, 4) void gram_chol_kernel(GramCholArgs a) {
     return;
   }
 
-  const bool stp = (NWP == 8) && pidx == (a.count > 300 ? 300 : 0) && !a.cert_shift;   // (diagnostic stamps)
+  const bool stp = pidx == (a.count > 300 ? 300 : 0) && !a.cert_shift;   // (diagnostic stamps)
   (void)stp;
   for (int kb = 0; kb < NT; ++kb) {
     CST(stp && w == 0, 0, kb, 0); CST(stp && w == 3, 1, kb, 0);
@@ -168,7 +150,7 @@ __global__ __launch_bounds__(GR_NT, 4) void gram_chol_kernel(GramCholArgs a) {
     const double dk = dl[16 * kb + lc];
 #pragma unroll
     for (int u = 0; u < UMAX; ++u) {
-      const int j = kb + w + NWP * u;
+      const int j = kb + w + GR_NW * u;
       S[u] = v4d{0.0, 0.0, 0.0, 0.0};
       if (j < NT) {
         const double dj = dl[16 * j + lc];
@@ -207,9 +189,9 @@ __global__ __launch_bounds__(GR_NT, 4) void gram_chol_kernel(GramCholArgs a) {
       if (lane == 0) pminsh = pm;
     }
     CST(stp && w == 0, 0, kb, 2);
-    psync();
+    __syncthreads();
     CST(stp && w == 0, 0, kb, 3); CST(stp && w == 3, 1, kb, 3);
-    if (a.rinv && w == NWP - 1) {                       // kept for the conditioning certificate (off the chain)
+    if (a.rinv && w == GR_NW - 1) {                     // kept for the conditioning certificate (off the chain)
       double* ro = a.rinv + ((long)b * (NPAD / 16) + kb) * 256;
 #pragma unroll
       for (int q = 0; q < 4; ++q) ro[q * 64 + lane] = Ri[q * 64 + lane];
@@ -217,7 +199,7 @@ __global__ __launch_bounds__(GR_NT, 4) void gram_chol_kernel(GramCholArgs a) {
     // ---- C. R'_{kb,j} = R'_{kb,kb}^-T S_j, stored as R = R' D^-1 ----
 #pragma unroll
     for (int u = 0; u < UMAX; ++u) {
-      const int j = kb + w + NWP * u;
+      const int j = kb + w + GR_NW * u;
       if (j < NT) {
         v4d X = {0.0, 0.0, 0.0, 0.0};
         if (j == kb) {
@@ -239,11 +221,11 @@ __global__ __launch_bounds__(GR_NT, 4) void gram_chol_kernel(GramCholArgs a) {
       }
     }
     CST(stp && w == 0, 0, kb, 4); CST(stp && w == 3, 1, kb, 4);
-    psync();
+    __syncthreads();
     CST(stp && w == 0, 0, kb, 5); CST(stp && w == 3, 1, kb, 5);
   }
   if (16 * NT < NPAD && !a.skip_zero) {                  // sub-matrix: the rest of the slot is zero
-    for (int r = w; r < NPAD; r += NWP) {
+    for (int r = w; r < NPAD; r += GR_NW) {
       const int c0 = (r < 16 * NT) ? 16 * NT : (r & ~15);
       for (int c = c0 + lane; c < NPAD; c += WAVE) Gb[(long)r * NPAD + c] = 0.0;
     }
@@ -269,9 +251,9 @@ __global__ __launch_bounds__(GR_NT, 4) void gram_chol_kernel(GramCholArgs a) {
 // the diagonal tile straight from its accumulator (chol16.h), R'_{kb,j} = R'_kk^-T S_j by MFMA, and
 // the right-looking update of the remaining tiles — whose MFMA operands are the rows just solved,
 // already in the right layout (register s of a tile in the accumulator layout holds rows 4 s + lr:
-// the operand fragment of k-step s).  No L2 round trip inside the factorisation (the left-looking
-// kernel above pays one per tile and finished row block: 20 exposed latencies at N = 65), no barrier.
-// Same arguments, outputs and gate bookkeeping as gram_chol_kernel<1>; eight problems per workgroup.
+// the operand fragment of k-step s).  No L2 round trip inside the factorisation (a left-looking
+// kernel pays one per tile and finished row block: 20 exposed latencies at N = 65), no barrier.
+// Same arguments, outputs and gate bookkeeping as gram_chol_kernel; eight problems per workgroup.
 __global__ __launch_bounds__(REG_NT, 1) void gram_chol_reg_kernel(GramCholArgs a) {
   constexpr int MT = 5;                                 // tile rows at most (N <= 80)
   extern __shared__ double sh_all[];
@@ -1089,308 +1071,13 @@ hipError_t launch_lm_rounds_reg(const GramCholArgs& c, const LmState& lm, const 
   return hipGetLastError();
 }
 
-// ---- right-looking variant: the whole (scaled) matrix lives in accumulators ----------------------
-// The NT (NT + 1) / 2 <= 153 upper tiles are dealt CYCLICALLY (row-major tile q -> wave q % 8, slot
-// q / 8) so that the shrinking trailing matrix stays balanced, and never leave the registers until
-// their row block is final.  Per row block kb: the diagonal tile goes through LDS to wave 0 for the
-// 16x16 Cholesky + inverse, the owners of the tiles (kb, j) solve them by MFMA and publish them in an
-// LDS row buffer, and every wave updates its own trailing tiles from that buffer — no global-memory
-// round trip inside the factorisation (the left-looking kernel above re-reads finished rows from L2).
-// Same arguments, same outputs, same gate bookkeeping as gram_chol_kernel.
-// SL tile slots per worker wave, the first KL of them kept in LDS instead of registers: the cyclic
-// tile table gives slot t the tiles 7 t .. 7 t + 6 in row-major order, so the first slots hold the top
-// rows — solved after at most three trailing updates and dead afterwards.  With all 22 slots in
-// registers (176 VGPRs) the compiler spilled 76 VGPRs to scratch and reloaded / stored them in
-// every row-block step; with eight slots in LDS (112 KB) 28 remain (two Newton rounds of 4096 x 256,
-// 512 problems: 0.404 -> 0.376 ms; same operations in the same order, same bits).
-// The factorisation of ONE problem by the calling workgroup (GR_NT threads): the body of gram_chol_rl_kernel.  sh: the dynamic LDS (launch_gram_chol sizes it),
-// red: 32 doubles, pminsh / flagsh: one double / int of static LDS.  All exits are uniform over the workgroup.
-template <int SL, int KL>
-__device__ __forceinline__ void chol_rl_body(const GramCholArgs& a, const int b, double* sh, double* red,
-                                             double& pminsh, int& flagsh) {
-  const int tid = threadIdx.x, lane = tid & 63;
-  const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int lr = lane >> 4, lc = lane & 15;
-  const int NPAD = a.NPAD;
-  const bool stp0 = (int)blockIdx.x == 100 && !a.cert_shift; (void)stp0;
-  CST(stp0 && (w == 0 || w == 2), w == 0 ? 2 : 3, 17, 0);
-  if (a.mask && a.mask[b] <= 1) {
-    if (tid == 0 && a.fb_mask) a.fb_mask[b] = 0;
-    return;
-  }
-  if (a.skip_path && a.skip_path[b] != 0 && !(a.qr_mask && a.qr_mask[b] == 0)) return;
-  double tau = 0.0;                                     // certificate stage 3: factor C - tau I
-  if (a.cert_shift) {
-    if (!a.cert_flag[b]) return;                        // (uniform)
-    tau = a.cert_tau[b];
-  }
-  const int N = a.ncols_dev ? a.ncols_dev[b] : a.n + 1;
-  if (N <= 1) {                                         // (dogbox: every variable active — nothing to factor)
-    if (tid == 0 && a.fb_mask) a.fb_mask[b] = 0;
-    return;
-  }
-  const int n = N - 1;
-  const int NT = (N + 15) / 16;
-  const int* gidx = a.gather ? a.gather + (long)b * a.stride_vec : nullptr;
-  auto src = [&](int i) -> int { return gidx ? (i < n ? gidx[i] : a.n) : i; };
-  const double* Gs = a.Gsrc + (long)b * NPAD * NPAD;
-  double* Gb = a.G + (long)b * NPAD * NPAD;
-  double* dl = sh;                 // [NPAD]
-  double* sq = dl + NPAD;          // [NPAD]
-  double* sc = sq + NPAD;          // [NPAD]
-  double* td = sc + NPAD;          // [NPAD]
-  double* Dt = td + NPAD;          // [256]
-  double* Ri = Dt + 256;           // [256]
-  double* Rrow = Ri + 256;         // [NT][256] finished tiles of the current row block
-  double* accL = Rrow + (NPAD / 16) * 256;   // [KL][7][256] the LDS-resident tile slots
-  const double* csv = a.colscale ? a.colscale + (long)b * a.stride_vec : nullptr;
-  const double* edv = a.diag_vec ? a.diag_vec + (long)b * a.stride_vec : nullptr;
-  const double sa = a.diag_sqrt ? a.diag_sqrt[b] : 0.0;
-  int bad = 0;
-  for (int j = tid; j < NPAD; j += GR_NT) {
-    const double cs = (csv && j < n) ? csv[j] : 1.0;
-    const double ej = (edv && j < n) ? edv[j] : 0.0;
-    const double add = (j < n) ? fma(ej, ej, sa * sa) : 0.0;
-    const int sj_ = (j < N) ? src(j) : j;
-    const double g = (j < N) ? fma(Gs[(long)sj_ * NPAD + sj_] * cs, cs, add) : 0.0;
-    const bool okc = (g > 0.0) && is_finite(g);
-    if (j < n && !okc) bad = 1;
-    double d = 1.0, s = 1.0;
-    if (j < N && okc) {
-      d = __builtin_amdgcn_rsq(g);
-      d = d * fma(-0.5 * g * d, d, 1.5);
-      d = d * fma(-0.5 * g * d, d, 1.5);
-      s = g * d;
-    }
-    dl[j] = d; sq[j] = s; sc[j] = cs * d; td[j] = add * d * d - ((j < n) ? tau : 0.0);
-    if (a.dsc) a.dsc[(long)b * NPAD + j] = d;
-  }
-  if (a.colinfo) {
-    __syncthreads();
-    double mn = __builtin_inf(), sm = 0.0, mx = 0.0;
-    if (w == 0) colinfo_wave(sq, n, lane, mn, mx, sm);
-    if (tid == 0) {
-      a.colinfo[2 * (long)b] = mn; a.colinfo[2 * (long)b + 1] = sm;
-      if (a.hmax) a.hmax[b] = mx * mx;
-      if (a.lam_out) a.lam_out[b] = (double)n;
-    }
-  }
-  bad = block_or(bad, red);
-  if (tid == 0) { pminsh = 1.0; flagsh = 0; }
-  __syncthreads();
-  if (bad) {
-    if (tid == 0 && a.fb_mask) {
-      a.fb_mask[b] = a.n + 1; { const int fi_ = atomicAdd(a.fail_count, 1); if (a.fail_list) a.fail_list[fi_] = b; }   // (the tree factors ALL n + 1 columns)
-      if (a.pmin_out && !a.cert_shift) a.pmin_out[b] = 0.0;
-      if (a.path_out) a.path_out[b] = a.n + 1;
-      if (a.k2_out && !a.cert_shift) a.k2_out[b] = 0.0;
-    }
-    return;
-  }
-  CST(stp0 && (w == 0 || w == 2), w == 0 ? 2 : 3, 17, 1);
-  // ROLES: wave 0 only runs the 16x16 chains (its registers hold the column / inverse vectors, no
-  // tiles); waves 1..7 own the tiles.  LOOKAHEAD: in the trailing update of row block kb the owner
-  // of the next diagonal tile updates it first, puts it into LDS and raises a flag; wave 0 starts
-  // the chain of block kb + 1 on that flag while the other tiles are still being updated.  Both
-  // loops pass the same two barriers per row block.
-  constexpr int NWK = GR_NW - 1;                        // worker waves
-  const int ntile = NT * (NT + 1) / 2;
-  const bool stp = (int)blockIdx.x == 100 && !a.cert_shift;   // (diagnostic stamps)
-  (void)stp;
-  // zeros outside the factor: strictly lower tiles, and everything beyond 16 NT (sub-matrix use)
-  auto zero_fill = [&]() {
-    for (int r = w; r < (a.skip_zero ? 0 : NPAD); r += GR_NW) {
-      const int cend = (r < 16 * NT) ? (r & ~15) : NPAD;
-      for (int c = lane; c < cend; c += WAVE) Gb[(unsigned)(r * NPAD + c)] = 0.0;
-      if (r < 16 * NT)
-        for (int c = 16 * NT + lane; c < NPAD; c += WAVE) Gb[(unsigned)(r * NPAD + c)] = 0.0;
-    }
-  };
-  if (w == 0) {
-    __syncthreads();                                    // X: workers have read the source, Dt holds tile (0, 0)
-    CST(stp, 2, 17, 3);
-    zero_fill();
-    CST(stp, 2, 17, 4);
-    double pmin = 1.0;
-    for (int kb = 0; kb < NT; ++kb) {
-      if (kb > 0) {                                     // wait for the updated diagonal tile kb
-        while (__hip_atomic_load(&flagsh, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP) < kb)
-          __builtin_amdgcn_s_sleep(1);
-        asm volatile("" ::: "memory");
-      }
-      CST(stp, 2, kb, 0);
-      pmin = chol16_blocked3(Dt, Ri, n - 16 * kb, pmin);   // (chol16.h)
-      CST(stp, 2, kb, 1);
-      if (a.rinv) {                                     // kept for the conditioning certificate
-        double* ro = a.rinv + ((long)b * (NPAD / 16) + kb) * 256;
-#pragma unroll
-        for (int q = 0; q < 4; ++q) ro[q * 64 + lane] = Ri[q * 64 + lane];
-      }
-      __syncthreads();                                  // B: R'_kk and its inverse are in LDS
-      CST(stp, 2, kb, 2);
-      __syncthreads();                                  // C: (workers published the row block)
-      CST(stp, 2, kb, 3);
-    }
-    if (lane == 0) pminsh = pmin;
-  } else {
-    // tile table (cyclic over the worker waves: the shrinking trailing matrix stays balanced) and
-    // the scaled source tiles -> accumulators; the source may alias the output, so everything is
-    // read before anything is written
-    const int ww = w - 1;
-    int ti[SL], tj[SL];
-    v4d accR[SL - KL];                                  // slots KL .. SL-1 (registers)
-    auto slot = [&](int t) -> double* { return accL + ((size_t)t * NWK + ww) * 256 + lane; };   // [g * 64]
-#define RL_ACC_GET(t, dst)                                                        \
-    do {                                                                          \
-      if ((t) < KL) { const double* p_ = slot(t);                                 \
-        dst = v4d{p_[0], p_[64], p_[128], p_[192]}; }                             \
-      else dst = accR[(t) < KL ? 0 : (t) - KL];                                   \
-    } while (0)
-#define RL_ACC_PUT(t, src)                                                        \
-    do {                                                                          \
-      if ((t) < KL) { double* p_ = slot(t);                                       \
-        p_[0] = (src)[0]; p_[64] = (src)[1]; p_[128] = (src)[2]; p_[192] = (src)[3]; } \
-      else accR[(t) < KL ? 0 : (t) - KL] = src;                                   \
-    } while (0)
-#pragma unroll
-    for (int t = 0; t < SL; ++t) {
-      int q = ww + NWK * t;
-      const bool valid = q < ntile;
-      int i = 0;
-      while (valid && q >= NT - i) { q -= NT - i; ++i; }
-      ti[t] = valid ? i : -1;
-      tj[t] = valid ? i + q : -1;
-      v4d a0 = v4d{0.0, 0.0, 0.0, 0.0};
-      if (valid) {
-        const int j = tj[t];
-        const double scj = sc[16 * j + lc];
-#pragma unroll
-        for (int g = 0; g < 4; ++g) {
-          const int row = 16 * i + lr + 4 * g, col = 16 * j + lc;
-          double v = 0.0;
-          if (row < N && col < N) {
-            int sr_ = src(row), sc_ = src(col);
-            if (sr_ > sc_) { const int t_ = sr_; sr_ = sc_; sc_ = t_; }
-            v = Gs[(unsigned)(sr_ * NPAD + sc_)] * sc[row] * scj;
-          }
-          if (j == i && lr + 4 * g == lc) v += td[row];
-          a0[g] = v;
-        }
-        if (i == 0 && j == 0) {
-#pragma unroll
-          for (int g = 0; g < 4; ++g) Dt[(lr + 4 * g) * 16 + lc] = a0[g];
-        }
-      }
-      RL_ACC_PUT(t, a0);
-    }
-    CST(stp && w == 2, 3, 17, 2);
-    __syncthreads();                                    // X: all source reads done before the first store
-    CST(stp && w == 2, 3, 17, 3);
-    zero_fill();
-    CST(stp && w == 2, 3, 17, 4);
-    for (int kb = 0; kb < NT; ++kb) {
-      CST(stp && w == 2, 3, kb, 5);
-      __syncthreads();                                  // B: wave 0 finished the chain of block kb
-      CST(stp && w == 2, 3, kb, 0);
-      // c. the row block: R'_{kb,j} = R'_{kb,kb}^-T S_j -> LDS row buffer and (unscaled) to memory
-#pragma unroll
-      for (int t = 0; t < SL; ++t) {
-        if (ti[t] == kb) {
-          const int j = tj[t];
-          v4d X = {0.0, 0.0, 0.0, 0.0};
-          if (j == kb) {
-#pragma unroll
-            for (int g = 0; g < 4; ++g) X[g] = Dt[(lr + 4 * g) * 16 + lc];
-          } else {
-            v4d S;
-            RL_ACC_GET(t, S);
-#pragma unroll
-            for (int s = 0; s < 4; ++s) X = gmfma(Ri[(4 * s + lr) * 16 + lc], S[s], X);
-          }
-          const double sj = sq[16 * j + lc];
-          const double dj = dl[16 * j + lc];
-#pragma unroll
-          for (int g = 0; g < 4; ++g) {
-            const int row = 16 * kb + lr + 4 * g;
-            const int colg = 16 * j + lc;
-            double val = X[g] * sj;
-            if (row >= n || row > colg || colg > n) val = 0.0;
-            Gb[(unsigned)(row * NPAD + colg)] = val;
-            // the operand of the trailing updates is what the left-looking kernel reads back: the
-            // STORED entry times its column's equilibration — the two kernels agree bit for bit
-            if (j != kb) Rrow[j * 256 + (lr + 4 * g) * 16 + lc] = val * dj;
-          }
-        }
-      }
-      CST(stp && w == 2, 3, kb, 1);
-      __syncthreads();                                  // C: the row block is in the LDS buffer
-      CST(stp && w == 2, 3, kb, 2);
-      // d. trailing update: the next diagonal tile first (-> LDS, flag for wave 0), then the rest
-#pragma unroll
-      for (int t = 0; t < SL; ++t) {
-        if (ti[t] == kb + 1 && tj[t] == kb + 1) {
-          const double* Ra = Rrow + ti[t] * 256 + lr * 16 + lc;
-          v4d S;
-          RL_ACC_GET(t, S);
-#pragma unroll
-          for (int s = 0; s < 4; ++s) S = gmfma(-Ra[64 * s], Ra[64 * s], S);
-          RL_ACC_PUT(t, S);
-#pragma unroll
-          for (int g = 0; g < 4; ++g) Dt[(lr + 4 * g) * 16 + lc] = S[g];
-          asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-          if (lane == 0) __hip_atomic_store(&flagsh, kb + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-        }
-      }
-      CST(stp && w == 2, 3, kb, 3);
-#pragma unroll
-      for (int t = 0; t < SL; ++t) {
-        if (ti[t] > kb && !(ti[t] == kb + 1 && tj[t] == kb + 1)) {
-          const double* Ra = Rrow + ti[t] * 256 + lr * 16 + lc;
-          const double* Rb = Rrow + tj[t] * 256 + lr * 16 + lc;
-          v4d S;
-          RL_ACC_GET(t, S);
-#pragma unroll
-          for (int s = 0; s < 4; ++s) S = gmfma(-Ra[64 * s], Rb[64 * s], S);
-          RL_ACC_PUT(t, S);
-        }
-      }
-      CST(stp && w == 2, 3, kb, 4);
-    }
-#undef RL_ACC_GET
-#undef RL_ACC_PUT
-  }
-  CST(stp && (w == 0 || w == 2), w == 0 ? 2 : 3, 18, 0);
-  __syncthreads();
-  CST(stp && (w == 0 || w == 2), w == 0 ? 2 : 3, 18, 1);
-  if (tid == 0 && a.fb_mask) {
-    const bool fail = !(pminsh >= (a.pivot_floor > 0.0 ? a.pivot_floor : 1.0 / GRAM_K2_MAX));
-    if (a.pmin_out && !a.cert_shift) a.pmin_out[b] = pminsh;
-    a.fb_mask[b] = fail ? a.n + 1 : 0;
-    if (a.path_out) a.path_out[b] = fail ? a.n + 1 : 0;
-    if (fail) { const int fi_ = atomicAdd(a.fail_count, 1); if (a.fail_list) a.fail_list[fi_] = b; }
-    if (fail && !a.cert_shift && a.k2_out) a.k2_out[b] = 0.0;      // (no bound for this factorisation)
-    if (a.cert_shift) {
-      a.cert_flag[b] = 0;
-      if (!fail && a.k2_out) a.k2_out[b] = a.k2_max;    // proven: kappa_2 <= Lambda / tau
-    }
-  }
-}
-
-template <int SL, int KL>
-__global__ __launch_bounds__(GR_NT, 2) void gram_chol_rl_kernel(GramCholArgs a) {
-  extern __shared__ double sh[];
-  __shared__ double red[32];
-  __shared__ double pminsh;
-  __shared__ int flagsh;                                // last diagonal tile handed to wave 0
-  const int pidx = (int)blockIdx.x;
-  if (a.count_dev && pidx >= *a.count_dev) return;
-  const int b = a.batch_list ? a.batch_list[pidx] : pidx;
-  chol_rl_body<SL, KL>(a, b, sh, red, pminsh, flagsh);
-}
-
-// ---- right-looking, flag-driven: no workgroup barrier inside the factorisation -------------------
-// The arithmetic of gram_chol_rl_kernel (same tiles, same operands, same order: the same bits), scheduled along its
-// critical path  chain(kb) -> R'_{kb,kb+1} -> S_{kb+1,kb+1} -> chain(kb + 1):
+// ---- N > 80, right-looking, flag-driven: no workgroup barrier inside the factorisation ----------
+// The whole (scaled) matrix lives in accumulators: the NT (NT + 1) / 2 <= 153 upper tiles are dealt CYCLICALLY over the
+// seven worker waves (row-major tile q -> wave 1 + q % 7, slot q / 7) so that the shrinking trailing matrix stays
+// balanced, and never leave the registers until their row block is final — no global-memory round trip inside the
+// factorisation (gram_chol_kernel, the left-looking reference, re-reads finished rows from L2).  The arithmetic is
+// that of gram_chol_kernel (same operands, same order: the same bits), scheduled along the critical path
+// chain(kb) -> R'_{kb,kb+1} -> S_{kb+1,kb+1} -> chain(kb + 1):
 //   * wave 0 only runs the 16x16 chains: it waits for the flag "diagonal tile kb is in Dt", factors, raises "R'_kk
 //     and its inverse are in LDS" — it never meets a barrier, nor the stores of the workers;
 //   * the owner of tile (kb, kb+1) solves it first and raises a flag; the owner of (kb+1, kb+1) waits for exactly
@@ -2067,7 +1754,8 @@ __global__ __launch_bounds__(TRI_NT) void gram_cert0_kernel(GramCholArgs a) {
 //     K2 = ||R'||_1 ||R'||_inf ||Y||_1 ||Y||_inf  >=  kappa_2(C)
 // (all four norms are exact sums of absolute values, accumulated in a fixed order) and keeps the
 // problem on the normal-equations path only if K2 <= GRAM_K2_MAX.  DESIGN.md 3.0 has the error bound
-// this gives for the step.  NWP waves per problem as in gram_chol_kernel.
+// this gives for the step.  NWP waves work on one problem: 8 (a whole workgroup) or 1 (N <= 80: eight problems per
+// workgroup, no workgroup barrier).
 template <int NWP>
 __global__ __launch_bounds__(GR_NT, 4) void gram_cond_kernel(GramCholArgs a) {
   constexpr int PT = WAVE * NWP;
@@ -2422,65 +2110,38 @@ bool gram_supported(int m, int n) {
 hipError_t launch_gram_chol(const GramCholArgs& a_in, int B, hipStream_t s) {
   GramCholArgs a = a_in;
   a.count = B;
-  const size_t per = sizeof(double) * (4 * (size_t)a.NPAD + 512);
   if (a.NPAD <= 80) {                                   // one wave per problem, eight per workgroup
-    // (register-resident right-looking kernel; BLSQ_CHOL_REG = 0: the left-looking one-wave kernel)
-    if (!options_or_default(a.opt).on(OPT_CHOL_REG)) {
-      // (this kernel has no finish blocks: nothing is settled, nobody is done)
-      hipError_t me = hipSuccess;
-      if (a.unsettled) me = hipMemsetD32Async((hipDeviceptr_t)a.unsettled, 1, 1, s);
-      if (me == hipSuccess && a.dog.done) me = hipMemsetAsync(a.dog.done, 0, sizeof(int) * (size_t)B, s);
-      if (me != hipSuccess) return me;
-      hipLaunchKernelGGL(gram_chol_kernel<1>, dim3((B + GR_NW - 1) / GR_NW), dim3(GR_NT), per * GR_NW,
-                         s, a);
-    } else {
-      const size_t per_reg = sizeof(double) * (8 * (size_t)a.NPAD + 256 + 5 * 256 + 64 + 16);
+    const size_t per_reg = sizeof(double) * (8 * (size_t)a.NPAD + 256 + 5 * 256 + 64 + 16);
+    static std::atomic<size_t> granted[64];
+    hipError_t ge = gram_grant_lds(gram_chol_reg_kernel, per_reg * REG_NW, granted);
+    if (ge != hipSuccess) return ge;
+    hipLaunchKernelGGL(gram_chol_reg_kernel, dim3(reg_grid(B)), dim3(REG_NT), per_reg * REG_NW, s, a);
+  } else if (options_or_default(a.opt).i(OPT_CHOL_RL) != 0) {   // (per launch: tests compare the kernels)
+    // Right-looking register kernel, flag-driven: 0.12 ms per problem on a CU of its own (one workgroup per CU)
+    // against 0.27 ms for a PAIR of problems on a CU through the left-looking kernel (its Schur-complement phase
+    // waits for L2: 190 of its 275 us, tools/chol_stamps.py).  BLSQ_CHOL_RL = 0 runs the left-looking one: the two
+    // agree bit for bit (same operands, same order), so it is the reference, never a faster choice.
+    constexpr int R2_KL = 5;
+    const size_t lds = sizeof(double) * (4 * (size_t)a.NPAD + 1024 + 2 * (size_t)(a.NPAD / 16) * 256 +
+                                         (size_t)R2_KL * (GR_NW - 1) * 256 + 2 * (size_t)a.NPAD) +
+                       sizeof(int) * (size_t)a.NPAD;
+    if (a.cert_ym && !a.cert_shift) {
       static std::atomic<size_t> granted[64];
-      hipError_t ge = gram_grant_lds(gram_chol_reg_kernel, per_reg * REG_NW, granted);
+      hipError_t ge = gram_grant_lds(gram_chol_rl2_kernel<22, R2_KL, true>, lds, granted);
       if (ge != hipSuccess) return ge;
-      hipLaunchKernelGGL(gram_chol_reg_kernel, dim3(reg_grid(B)), dim3(REG_NT), per_reg * REG_NW,
-                         s, a);
+      hipLaunchKernelGGL((gram_chol_rl2_kernel<22, R2_KL, true>), dim3(B), dim3(GR_NT), lds, s, a);
+    } else {
+      static std::atomic<size_t> granted[64];
+      hipError_t ge = gram_grant_lds(gram_chol_rl2_kernel<22, R2_KL, false>, lds, granted);
+      if (ge != hipSuccess) return ge;
+      hipLaunchKernelGGL((gram_chol_rl2_kernel<22, R2_KL, false>), dim3(B), dim3(GR_NT), lds, s, a);
     }
   } else {
-    // Right-looking register kernel, flag-driven: 0.12 ms per problem on a CU of its own (one workgroup per
-    // CU) against 0.27 ms for a PAIR of problems on a CU through the left-looking kernel (its Schur-complement
-    // phase waits for L2: 190 of its 275 us, tools/chol_stamps.py) — the right-looking one serves every launch
-    // (512 problems: two generations, 0.241 against 0.262 ms).  BLSQ_CHOL_RL = 0 / 1 forces either;
-    // BLSQ_CHOL_RL2 = 0 selects the barrier-synchronous right-looking kernel (<= 256 problems: 0.187 ms).
-    // All three agree bit for bit (same operands, same order), so the choice is speed only.
-    const Options& opt = options_or_default(a.opt);    // (per launch: tests compare the kernels)
-    const bool rl = opt.i(OPT_CHOL_RL) != 0;           // (-1 / 1: right-looking)
-    const bool rl2 = rl && opt.on(OPT_CHOL_RL2);       // 0: the barrier-synchronous right-looking kernel
-    if (a.cert_ym && !rl2) {                            // (only the flag-driven kernel has a share in stage 0)
+    if (a.cert_ym) {                                    // (only the flag-driven kernel has a share in stage 0)
       hipError_t me = hipMemsetAsync(a.cert_ym, 0, sizeof(double) * (size_t)B, s);
       if (me != hipSuccess) return me;
     }
-    if (rl2) {
-      constexpr int R2_KL = 5;
-      const size_t lds = sizeof(double) * (4 * (size_t)a.NPAD + 1024 + 2 * (size_t)(a.NPAD / 16) * 256 +
-                                           (size_t)R2_KL * (GR_NW - 1) * 256 + 2 * (size_t)a.NPAD) +
-                         sizeof(int) * (size_t)a.NPAD;
-      if (a.cert_ym && !a.cert_shift) {
-        static std::atomic<size_t> granted[64];
-        hipError_t ge = gram_grant_lds(gram_chol_rl2_kernel<22, R2_KL, true>, lds, granted);
-        if (ge != hipSuccess) return ge;
-        hipLaunchKernelGGL((gram_chol_rl2_kernel<22, R2_KL, true>), dim3(B), dim3(GR_NT), lds, s, a);
-      } else {
-        static std::atomic<size_t> granted[64];
-        hipError_t ge = gram_grant_lds(gram_chol_rl2_kernel<22, R2_KL, false>, lds, granted);
-        if (ge != hipSuccess) return ge;
-        hipLaunchKernelGGL((gram_chol_rl2_kernel<22, R2_KL, false>), dim3(B), dim3(GR_NT), lds, s, a);
-      }
-    } else if (rl) {
-      constexpr int RL_KL = 8;                          // tile slots per worker wave kept in LDS
-      const size_t lds = per + sizeof(double) * 256 * ((size_t)(a.NPAD / 16) + (size_t)RL_KL * (GR_NW - 1));
-      static std::atomic<size_t> granted[64];
-      hipError_t ge = gram_grant_lds(gram_chol_rl_kernel<22, RL_KL>, lds, granted);
-      if (ge != hipSuccess) return ge;
-      hipLaunchKernelGGL((gram_chol_rl_kernel<22, RL_KL>), dim3(B), dim3(GR_NT), lds, s, a);
-    } else {
-      hipLaunchKernelGGL(gram_chol_kernel<8>, dim3(B), dim3(GR_NT), per, s, a);
-    }
+    hipLaunchKernelGGL(gram_chol_kernel, dim3(B), dim3(GR_NT), sizeof(double) * (4 * (size_t)a.NPAD + 512), s, a);
   }
   return hipGetLastError();
 }
@@ -2495,7 +2156,6 @@ hipError_t launch_gram_cert_shift(const GramCholArgs& a_in, int B, hipStream_t s
   a.dog = GramCholArgs::DogFinish{}; a.lmfin = GramCholArgs::LmFinish{};
   a.batch_list = nullptr; a.count_dev = nullptr; a.skip_path = nullptr; a.diag_sqrt = nullptr;
   a.qr_mask = nullptr; a.hmax = nullptr; a.lam_out = nullptr; a.pmin_out = nullptr;
-  a.expect = B;                                         // (left-looking kernel: most workgroups leave at once)
   return launch_gram_chol(a, B, s);
 }
 

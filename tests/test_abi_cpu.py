@@ -119,7 +119,7 @@ def test_unknown_negative_status_raises_value_error_not_key_error():
     raise_step_errors(np.array([0, 1, 3]))                   # termination codes: nothing raised
 
 
-def test_option_table_is_documented():
+def test_option_table_is_exactly_the_22_documented_switches():
     """Every switch of the library's option table (blsq_option_info needs no GPU) appears in INTEGRATION.md with its
     environment variable, and no getenv("BLSQ_...") is left in the sources outside the table and the RCCL loader."""
     import ctypes as C
@@ -129,14 +129,23 @@ def test_option_table_is_documented():
     lib = _abi.load()
     doc = open(os.path.join(ROOT, "INTEGRATION.md")).read()
     n = lib.blsq_option_count()
-    assert n >= 26
+    names = set()
     for i in range(n):
         nm, ev, dc = C.c_char_p(), C.c_char_p(), C.c_char_p()
         df = C.c_double()
         assert lib.blsq_option_info(i, C.byref(nm), C.byref(ev), C.byref(df), C.byref(dc)) == 0
         assert "`%s`" % nm.value.decode() in doc and "`%s`" % ev.value.decode() in doc, nm.value
         assert ev.value.decode() == "BLSQ_" + nm.value.decode().upper()
+        names.add(nm.value.decode())
     assert lib.blsq_option_info(n, None, None, None, None) != 0
+    assert names == {"gram", "cqr2", "csne", "optimistic", "no_svdfree", "svdfree_min_n", "gram_k2_max", "cert0",
+                     "cert_direct", "lm_chol_qrpath", "lm_fused", "h2d_pipe", "chol_rl", "gram16", "gram8", "gram_pair",
+                     "gram_tile_groups", "gram_direct_nw", "gram_direct_max_nt", "qr_cqr", "gram1", "csne_mfma"}
+    assert n == len(names) == 22
+    retired = {"publish", "fuse_pack", "publish_ride", "settle0", "chol_reg", "chol_rl2"}
+    assert not names & retired
+    for nm in retired:                                       # (neither key nor environment variable is known)
+        assert "`%s`" % nm not in doc and "`BLSQ_%s`" % nm.upper() not in doc, nm
     left = []
     for path in glob.glob(os.path.join(ROOT, "bounded-lsq_amd", "csrc", "*")):
         if not path.endswith((".hip", ".h", ".cpp")) or path.endswith("blsq_options.cpp"):

@@ -665,13 +665,13 @@ def test_optimistic_verdict_of_the_dogbox_device_api(bl, monkeypatch, blsq_opt):
 
 
 @pytest.mark.parametrize("solver", ["trf", "dogbox"])
-def test_counter_and_vector_routes_of_the_device_api_give_the_same_bits(bl, monkeypatch, solver, blsq_opt):
-    """Two routes of the device-resident calls that change no arithmetic: the verdict / Newton-round counters reach
-    the host through a one-lane kernel and a polled pinned slot (BLSQ_PUBLISH = 0: hipMemcpyAsync + event), and the
-    caller's x / lb / ub / scale / on_bound are packed into the state layout by the prep launch (BLSQ_FUSE_PACK = 0:
-    by a launch of their own in front of the Gram); the verdict's counters ride on the step kernel of the next step call
-    (BLSQ_PUBLISH_RIDE = 0: a publishing launch of their own at the end of the factor call).  Right and wrong guesses,
-    three calls on the same plan, several Newton rounds: same bits, same path statistics on every combination."""
+def test_riding_and_polled_verdict_counters_of_the_device_api_give_the_same_bits(bl, monkeypatch, solver, blsq_opt):
+    """The verdict's counters reach the host in two ways that change no arithmetic: by default (optimistic) they ride
+    on the step kernel of the next step call and the host polls a pinned slot for them; with BLSQ_OPTIMISTIC = 0 the
+    factor call reads them before it returns (TRF: through a publishing launch of its own and the same poll).  Either
+    way the Newton rounds' counters ride on their update kernels, and the caller's x / lb / ub / scale / on_bound are
+    packed into the state layout by the prep launch.  Right and wrong guesses, three calls on the same plan, several
+    Newton rounds: same bits, same path statistics.  The retired switch of the blit route is an unknown option."""
     from bounded_lsq import _synth, _abi
     B, m, n = 6, 700, 64
     if solver == "trf":
@@ -689,12 +689,11 @@ def test_counter_and_vector_routes_of_the_device_api_give_the_same_bits(bl, monk
         mixed["on_bound"][2] = 0
     for P, expect_fb in ((good, 0), (mixed, 1)):
         outs = []
-        for publish, fuse, ride in (("1", "1", "1"), ("0", "1", "1"), ("1", "0", "1"), ("0", "0", "1"), ("1", "1", "0"),
-                                    ("1", "0", "0")):
-            blsq_opt("BLSQ_PUBLISH", publish)
-            blsq_opt("BLSQ_FUSE_PACK", fuse)
-            blsq_opt("BLSQ_PUBLISH_RIDE", ride)
+        for optimistic in ("1", "0"):
+            blsq_opt("BLSQ_OPTIMISTIC", optimistic)
             ctx = _abi.Context(0)
+            with pytest.raises(_abi.BlsqError, match="unknown option"):
+                ctx.set_option("publish", 1)
             sol = (bl.TrfStepSolver if solver == "trf" else bl.DogboxStepSolver)(B, m, n, ctx=ctx)
             d = {k: ctx.to_device(P[k]) for k in keys}
             extra = [ctx.to_device(Delta)] + ([ctx.to_device(np.zeros(B))] if solver == "trf" else [])
@@ -703,7 +702,7 @@ def test_counter_and_vector_routes_of_the_device_api_give_the_same_bits(bl, monk
                 sol.factor_dev(*[d[k] for k in keys])
                 sol.step_dev(*extra)
             S = sol.fetch_step()
-            assert ctx.gram_stats() == (3 * (B - expect_fb), 3 * expect_fb), (publish, fuse, ride)
+            assert ctx.gram_stats() == (3 * (B - expect_fb), 3 * expect_fb), optimistic
             if solver == "trf":
                 outs.append((S.step.copy(), np.asarray(S.alpha).copy(), np.asarray(S.n_iter).copy(), S.hits.copy(),
                              sol.fetch_factor().g.copy()))
@@ -807,12 +806,11 @@ def test_round_loop_follows_the_round_count_of_the_last_call(bl):
 
 
 @pytest.mark.parametrize("shape", [(700, 64), (900, 150)])
-def test_second_guess_of_the_trf_device_api(bl, monkeypatch, shape, blsq_opt):
+def test_second_guess_of_the_trf_device_api_gives_the_synchronous_bits(bl, monkeypatch, shape, blsq_opt):
     """TRF: after a call in which the Cholesky kernel (N <= 80; N > 80: stage 0 of the certificate, which is still
     launched) settled every problem (first certificate bound + the rank gate's column-norm bound), the remaining
     certificate and gate launches of the next call are not enqueued.  Guess holds / fails softly (a column of norm
-    1e-12) / fails hard (certificate; rank deficiency) / holds again: the bits of the synchronous mode at every call
-    (and, N > 80, of BLSQ_SETTLE0 = 0, which always enqueues the whole tail)."""
+    1e-12) / fails hard (certificate; rank deficiency) / holds again: the bits of the synchronous mode at every call."""
     from bounded_lsq import _synth, _abi
     m, n = shape
     B = 6
@@ -830,9 +828,8 @@ def test_second_guess_of_the_trf_device_api(bl, monkeypatch, shape, blsq_opt):
     Delta = np.array([0.5, 0.05, 5.0, 0.2, 0.3, 1.0])
     for scale_mode in (0, 1):
         runs = []
-        for opt, settle in (("1", "1"), ("0", "1"), ("1", "0")):
+        for opt in ("1", "0"):
             blsq_opt("BLSQ_OPTIMISTIC", opt)
-            blsq_opt("BLSQ_SETTLE0", settle)
             ctx = _abi.Context(0)
             sol = bl.TrfStepSolver(B, m, n, ctx=ctx)
             dD, dA = ctx.to_device(Delta), ctx.to_device(np.zeros(B))
@@ -924,21 +921,18 @@ def test_chunk_pairs_summed_in_the_kernel_match_the_reduction_pass(bl, monkeypat
             assert rel(outs[0][1][b], P["J"][b].T @ P["f"][b]) < 1e-13
 
 
-def test_both_cholesky_kernels_agree_bit_for_bit(bl, monkeypatch, blsq_opt):
-    """N > 80: launches of at most 256 problems use the right-looking register kernel (flag-driven schedule;
-    BLSQ_CHOL_RL2 = 0: the barrier-synchronous one), larger ones the
-    left-looking one (BLSQ_CHOL_RL forces either).  All apply the same operands in the same order —
-    the right-looking kernel publishes the STORED entry times its equilibration, exactly what the
-    left-looking one reads back — so which one ran (i.e. how many problems shared the launch, or were
-    still active in a Newton round) never shows in the results."""
+def test_left_looking_reference_and_default_cholesky_agree_bit_for_bit(bl, monkeypatch, blsq_opt):
+    """N > 80: every launch runs the right-looking register kernel (flag-driven schedule); BLSQ_CHOL_RL = 0 runs the
+    left-looking reference kernel instead.  Both apply the same operands in the same order — the right-looking kernel
+    publishes the STORED entry times its equilibration, exactly what the left-looking one reads back — so the results
+    are the same bits."""
     from bounded_lsq import _synth, _abi
     for (B, m, n, kind) in [(4, 1000, 200, "trf"), (3, 2100, 128, "trf"), (2, 4096, 256, "trf"),
                             (4, 600, 100, "trf"), (4, 900, 120, "dogbox")]:
         P = _synth.trf_batch(70 + n, B, m, n) if kind == "trf" else _synth.dogbox_batch(70 + n, B, m, n)
         outs = []
-        for rl, rl2 in (("0", "1"), ("1", "1"), ("1", "0")):       # left-looking, flag-driven, barrier-synchronous
+        for rl in ("0", "1"):                                       # left-looking, flag-driven
             blsq_opt("BLSQ_CHOL_RL", rl)
-            blsq_opt("BLSQ_CHOL_RL2", rl2)
             ctx = _abi.Context(0)
             got = []
             if kind == "trf":
@@ -955,8 +949,8 @@ def test_both_cholesky_kernels_agree_bit_for_bit(bl, monkeypatch, blsq_opt):
                     got += [S.step.copy(), S.predicted_reduction.copy()]
             sol.close(); ctx.close()
             outs.append(got)
-        for x0, x1, x2 in zip(*outs):
-            assert np.array_equal(x0, x1) and np.array_equal(x0, x2)
+        for x0, x1 in zip(*outs):
+            assert np.array_equal(x0, x1)
 
 
 def test_k_split_kernel_for_eight_column_tiles(bl, monkeypatch, blsq_opt):
