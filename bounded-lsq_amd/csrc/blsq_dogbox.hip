@@ -30,25 +30,10 @@ int dog_alloc_state(blsq_dogbox_plan* p) {
   ALLOC(p->gate_ints, sizeof(int) * 3 * (size_t)B);
   ALLOC(p->colinfo, sizeof(double) * 2 * (size_t)B);
   p->svdfree_enable = ctx->opt.i(OPT_NO_SVDFREE) == 1 ? 0 : 1;
-  p->csne_on = p->tree.gram && csne_supported(p->m, p->n) && ctx->opt.on(OPT_CSNE) && p->svdfree_enable;
-  if (p->csne_on) {
-    ALLOC(p->cs_ints, sizeof(int) * (5 * (size_t)B + 8));
-    ALLOC(p->cs_pmin, sizeof(double) * (size_t)B);
-    ALLOC(p->cs_eta, sizeof(double) * (size_t)B);
-    ALLOC(p->cs_k2, sizeof(double) * (size_t)B);
-    ALLOC(p->cs_alpha, sizeof(double) * (size_t)B * CSNE_MAXE);
-    HIPCHK(ctx, hipMemsetAsync(p->cs_ints.p, 0, p->cs_ints.bytes, ctx->stream));
-    HIPCHK(ctx, hipMemsetAsync(p->cs_pmin.p, 0, p->cs_pmin.bytes, ctx->stream));
-    HIPCHK(ctx, hipMemsetAsync(p->cs_eta.p, 0, p->cs_eta.bytes, ctx->stream));
-    HIPCHK(ctx, hipMemsetAsync(p->cs_k2.p, 0, p->cs_k2.bytes, ctx->stream));
-    CsneState& cs = p->cs;
-    cs.B = B; cs.m = p->m; cs.n = p->n; cs.ld = ld;
-    int* ii = p->cs_ints.as<int>();
-    cs.flag = ii; cs.list = ii + B; cs.fail_list = ii + 2 * (size_t)B; cs.ne = ii + 3 * (size_t)B;
-    cs.counts = ii + 5 * (size_t)B;
-    cs.ralpha = p->cs_alpha.as<double>(); cs.eta = p->cs_eta.as<double>();
-    csne_geometry(p->m, &cs.rows_per_wg, &cs.nchunk);
-    cs.NE = 1;
+  if (p->tree.gram && csne_supported(p->m, p->n) && ctx->opt.on(OPT_CSNE) && p->svdfree_enable) {
+    int rc = p->csne.build(ctx, B, p->m, p->n, ld, /*with_hp=*/false);
+    if (rc) return rc;
+    p->st.csne = p->csne.cs.flag; p->st.csne_k2 = p->csne.k2.as<double>();
   }
   HIPCHK(ctx, hipMemsetAsync(p->gate_ints.p, 0, p->gate_ints.bytes, ctx->stream));
   HIPCHK(ctx, hipMemsetAsync(p->S.p, 0, p->S.bytes, ctx->stream));
@@ -65,7 +50,6 @@ int dog_alloc_state(blsq_dogbox_plan* p) {
   st.free_idx = p->ivecs.as<int>(); st.ncols = p->ivecs.as<int>() + vs;
   st.srange = p->scal2.as<double>(); st.g_norm = p->scal2.as<double>() + 2 * (size_t)B;
   st.active = p->active.as<unsigned char>();
-  if (p->csne_on) { st.csne = p->cs.flag; st.csne_k2 = p->cs_k2.as<double>(); }
   p->out.step = p->o_vec.as<double>(); p->out.x_new = p->o_vec.as<double>() + vs;
   p->out.on_bound_new = p->o_onb.as<long long>();
   p->out.scal = p->o_scal.as<double>(); p->out.info = p->o_info.as<int>();
@@ -170,7 +154,7 @@ GramCholArgs dog_chol_args(blsq_dogbox_plan* p, const int* mask) {
   c.k2_max = t.k2_max; c.pivot_floor = 1.0 / t.k2_max;
   c.cert_flag = t.gram_cflag.as<int>(); c.cert_tau = t.gram_ctau.as<double>();
   c.colinfo = p->colinfo.as<double>();
-  if (p->csne_on) c.pmin_out = p->cs_pmin.as<double>();
+  if (p->csne.on) c.pmin_out = p->csne.pmin.as<double>();
   if (p->ld <= 80) {                        // (the register-resident kernel also finishes the gate / Newton / Cauchy work)
     int* gf_ = p->gate_ints.as<int>();
     c.dog.g = p->st.g; c.dog.newton = p->st.newton; c.dog.cauchy = p->st.cauchy;
@@ -204,44 +188,18 @@ int dog_gate_tail(blsq_dogbox_plan* p, const GramCholArgs& c) {
 // CSNE tier, dogbox (csne_kernels.hip).  Of the nfb problems the certificate has just rejected
 // (tree.fb_list()) those whose free-block factor qualifies keep it as a preconditioner; *ntree = the others.
 int dog_csne_select(blsq_dogbox_plan* p, int nfb, int* ntree, bool masked) {
-  blsq_ctx* ctx = p->ctx;
+  CsneTier& tier = p->csne;
   QrTree& t = p->tree;
-  const int B = p->B;
   *ntree = nfb;
-  if (!p->csne_on) return 0;
-  hipError_t e = hipSuccess;
-  if (!p->cs_vec.p) {                                     // first use: the recording (one evaluation: the Newton step)
-    e = p->cs_vec.alloc(sizeof(double) * (size_t)B * CSNE_MAXE * 3 * p->ld);
-    if (e != hipSuccess) { (void)hipGetLastError(); p->csne_on = false; p->st.csne = nullptr; return 0; }
-    p->cs.rvec = p->cs_vec.as<double>();
-  }
-  int* sel = p->cs_ints.as<int>() + 4 * (size_t)B;
-  int* scratch = p->cs.counts + 4;
-  HIPCHK(ctx, hipMemsetAsync(sel, 0, sizeof(int) * (size_t)B, ctx->stream));
-  GramCholArgs cy = dog_chol_args(p, t.fb_mask());        // (mask: the rejected problems only; same gather)
-  cy.fb_mask = sel; cy.fail_count = scratch; cy.fail_list = nullptr; cy.path_out = nullptr;
-  cy.cert_done = nullptr; cy.cert_flag = nullptr; cy.cert_tau = nullptr; cy.cert_open = nullptr;
-  cy.unsettled = nullptr; cy.dog = GramCholArgs::DogFinish{};
-  cy.colinfo = nullptr; cy.pmin_out = nullptr;
-  cy.k2_max = CSNE_K2_MAX; cy.k2_out = p->cs_k2.as<double>();
-  ctx->begin(K_GRAM_GATE);
-  e = launch_gram_gate(cy, B, ctx->stream);
-  ctx->end();
-  if (e != hipSuccess) return ctx->fail(e, "launch_gram_gate(csne bound, dogbox)");
+  if (!tier.on) return 0;
+  if (!tier.ensure_recordings()) { tier.on = false; p->st.csne = nullptr; return 0; }
   int* gfast = p->gate_ints.as<int>();
-  e = launch_csne_select_dog(p->cs, p->m, p->st.ncols, gfast, gfast + B, nfb, t.fb_list(), t.fb_mask(), t.fb_count(),
-                             t.path_rw(), sel, p->cs_k2.as<double>(), p->cs_pmin.as<double>(), p->colinfo.as<double>(),
-                             ctx->stream);
-  if (e != hipSuccess) return ctx->fail(e, "launch_csne_select_dog");
-  HIPCHK(ctx, hipMemcpyAsync(ctx->pinned + 8, t.fb_count(), sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
-  HIPCHK(ctx, hipMemcpyAsync(ctx->pinned + 9, p->cs.counts, sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
-  HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-  *ntree = ctx->pinned[8];
-  p->ncsne = ctx->pinned[9];
-  ctx->csne_routed += (unsigned long long)(nfb - *ntree);
-  if (!masked) t.any_qr = *ntree > 0;
-  t.any_gram = t.any_gram || *ntree < nfb;
-  return 0;
+  // (the bound over the plan's factor arguments: the same gather)
+  return tier.select(p->ctx, t, dog_chol_args(p, t.fb_mask()), nfb, ntree, masked, [&](const int* sel) {
+    return launch_csne_select_dog(tier.cs, p->m, p->st.ncols, gfast, gfast + p->B, nfb, t.fb_list(), t.fb_mask(),
+                                  t.fb_count(), t.path_rw(), sel, tier.k2.as<double>(), tier.pmin.as<double>(),
+                                  p->colinfo.as<double>(), p->ctx->stream);
+  });
 }
 
 // ... and the correction itself, at FACTOR time (the Newton step of dogbox.py:197 does not depend on Delta): the cheap
@@ -249,42 +207,29 @@ int dog_csne_select(blsq_dogbox_plan* p, int nfb, int* ntree, bool masked) {
 // whose measured correction is too large leave the tier: *nfail of them, listed in tree.fb_list() / fb_mask().
 int dog_csne_correct(blsq_dogbox_plan* p, const double* dJ, const double* df, int ldJ, int* nfail) {
   blsq_ctx* ctx = p->ctx;
-  CsneState& cs = p->cs;
-  QrTree& t = p->tree;
+  CsneTier& tier = p->csne;
+  CsneState& cs = tier.cs;
   *nfail = 0;
-  if (p->ncsne <= 0) return 0;
+  if (tier.count <= 0) return 0;
   cs.J = dJ; cs.strideJ = (long)p->m * ldJ; cs.ldJ = ldJ; cs.F = df; cs.strideF = p->m;
   cs.NE = 1;
-  const size_t need = (size_t)p->ncsne * cs.nchunk * ((size_t)p->ld + 16);
-  if (need > p->cs_part_cap) {
-    p->cs_part.release();
-    const size_t cap = std::max(need, 2 * p->cs_part_cap);
-    hipError_t ae = p->cs_part.alloc(sizeof(double) * cap);
-    if (ae != hipSuccess) { p->cs_part_cap = 0; return ctx->fail(ae, "hipMalloc(CSNE partial sums)"); }
-    p->cs_part_cap = cap;
-    cs.part = p->cs_part.as<double>();
-  }
+  { int rc_ = tier.grow_part(ctx, (size_t)tier.count * cs.nchunk * ((size_t)p->ld + 16)); if (rc_) return rc_; }
   HIPCHK(ctx, hipMemsetAsync(cs.counts + 1, 0, sizeof(int), ctx->stream));
   ctx->begin(K_CSNE_PASS);
-  hipError_t e = launch_dog_csne_scatter(cs, p->st, p->ncsne, ctx->stream);
-  if (e == hipSuccess) e = launch_csne_pass(cs, nullptr, p->ncsne, ctx->stream);
+  hipError_t e = launch_dog_csne_scatter(cs, p->st, tier.count, ctx->stream);
+  if (e == hipSuccess) e = launch_csne_pass(cs, nullptr, tier.count, ctx->stream);
   ctx->end();
   if (e != hipSuccess) return ctx->fail(e, "launch_csne_pass(dogbox)");
   ctx->begin(K_CSNE_FIX);
-  e = launch_dog_csne_fix(cs, p->st, p->ncsne, ctx->stream);
+  e = launch_dog_csne_fix(cs, p->st, tier.count, ctx->stream);
   ctx->end();
   if (e != hipSuccess) return ctx->fail(e, "launch_dog_csne_fix");
   HIPCHK(ctx, hipMemcpyAsync(ctx->pinned + 12, cs.counts + 1, sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
   HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
   *nfail = ctx->pinned[12];
-  ctx->csne_steps += (unsigned long long)(p->ncsne - *nfail);
+  ctx->csne_steps += (unsigned long long)(tier.count - *nfail);
   ctx->csne_declined += (unsigned long long)*nfail;
-  if (*nfail > 0) {
-    e = launch_csne_reroute(cs, *nfail, t.fb_list(), t.fb_mask(), t.path_rw(), ctx->stream);
-    if (e != hipSuccess) return ctx->fail(e, "launch_csne_reroute(dogbox)");
-    p->ncsne -= *nfail;
-    t.any_qr = true;
-  }
+  if (*nfail > 0) return tier.reroute(ctx, p->tree, *nfail);
   return 0;
 }
 
@@ -299,12 +244,8 @@ int dog_repair(blsq_dogbox_plan* p, const double* dJ, const double* df, int ldJ,
     int ntree = nfb;
     if ((rc = dog_csne_select(p, nfb, &ntree, masked))) return rc;
     nfb = ntree;
-  } else if (masked && p->ncsne > 0) {                     // (refreshed problems have left the tier: the list from the flags)
-    hipError_t e = launch_csne_reroute(p->cs, -1, nullptr, nullptr, nullptr, ctx->stream);
-    if (e != hipSuccess) return ctx->fail(e, "launch_csne_reroute(relist)");
-    HIPCHK(ctx, hipMemcpyAsync(ctx->pinned + 9, p->cs.counts, sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
-    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-    p->ncsne = ctx->pinned[9];
+  } else if (masked && p->csne.count > 0) {                // (refreshed problems have left the tier: the list from the flags)
+    if ((rc = p->csne.relist(ctx))) return rc;
   }
   for (int pass = 0; pass < 2; ++pass) {
     if (nfb > 0) {
@@ -314,7 +255,7 @@ int dog_repair(blsq_dogbox_plan* p, const double* dJ, const double* df, int ldJ,
       ctx->end();
       if (e != hipSuccess) return ctx->fail(e, "launch_dog_prep(redo)");
     }
-    if ((rc = dog_finish(p, t.path_rw(), t.any_qr, t.any_gram, pass > 0 && p->csne_on ? p->cs.flag : nullptr))) return rc;
+    if ((rc = dog_finish(p, t.path_rw(), t.any_qr, t.any_gram, pass > 0 && p->csne.on ? p->csne.cs.flag : nullptr))) return rc;
     int nfail = 0;
     if (pass == 0 && (rc = dog_csne_correct(p, dJ, df, ldJ, &nfail))) return rc;
     if (nfail == 0) break;
@@ -373,7 +314,7 @@ int dog_factor_core(blsq_dogbox_plan* p, const double* dJ, const double* df, int
     if (!mask) { p->guess_ok = (nfb == 0 && p->njac == 0); p->guess_settled = (c.unsettled && ctx->pinned[3] == 0); }
   }
   t.note_paths(ctx, nfb, mask != nullptr);
-  if (!mask) p->ncsne = 0;                                // (the prep launch cleared every flag; dog_csne_select sets them anew)
+  if (!mask) p->csne.count = 0;                           // (the prep launch cleared every flag; dog_csne_select sets them anew)
   if (skip_tail) { p->gate_done = false; return 0; }
   return dog_repair(p, dJ, df, ldJ, scale_mode, nfb, mask != nullptr);
 }
@@ -414,12 +355,11 @@ extern "C" int blsq_dogbox_plan_create(blsq_ctx* ctx, int B, int m, int n,
 }
 
 extern "C" int blsq_dogbox_plan_destroy(blsq_dogbox_plan* p) {
-  if (p) { p->cs_ints.release(); p->cs_pmin.release(); p->cs_eta.release(); p->cs_alpha.release(); p->cs_k2.release(); p->cs_vec.release(); p->cs_part.release(); }
   if (!p) return -1;
   hipStreamSynchronize(p->ctx->stream);
   { auto& v = p->ctx->dog_plans; v.erase(std::remove(v.begin(), v.end(), p), v.end()); }
   if (p->pend_pin) hipHostFree(p->pend_pin);
-  p->tree.release();
+  p->tree.release(); p->csne.release();
   p->S.release(); p->X.release(); p->vecs.release(); p->ivecs.release(); p->scal2.release();
   p->sweeps.release(); p->active.release(); p->onb.release(); p->o_vec.release();
   p->o_onb.release(); p->o_scal.release(); p->o_info.release(); p->in_J.release();

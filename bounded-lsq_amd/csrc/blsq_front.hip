@@ -1,0 +1,404 @@
+// The factorisation front end of a plan (QrTree: Gram / certificate / CholeskyQR2 / Householder tree) and the CSNE
+// tier's host state (CsneTier), shared by the TRF and the dogbox plans (blsq_host.h).
+#include "blsq_host.h"
+
+namespace blsq_host {
+
+int QrTree::build(blsq_ctx* ctx, int B_, int rows, int n_, size_t extra_rp_rows) {
+  B = B_; m = rows; n = n_; opt = &ctx->opt;
+  N = n + 1; NPAD = round_up(N, 16); NP = NPAD / 16;
+  if (NPAD > RMAX) return ctx->bad(4, "n too large (n + 1 must be <= 1024)");
+  int cur_rows = rows;
+  bool first = true;
+  size_t max_slot_rows = extra_rp_rows;   // max over launches of nslot*RP
+  size_t max_slots = (size_t)B;
+  while (true) {
+    Level L;
+    L.rowsA = cur_rows;
+    if (first) {
+      L.nleaf = std::max(1, (cur_rows + RMAX - 1) / RMAX);
+      if (L.nleaf > 1 && !merge_fits(n))
+        return ctx->bad(4, "m > 1024 needs n <= 512 (TSQR merge capacity)");
+      L.rows_per_leaf = round_up((cur_rows + L.nleaf - 1) / L.nleaf, 16);
+      if (L.rows_per_leaf < NPAD && L.nleaf > 1) L.rows_per_leaf = NPAD;
+      L.nleaf = std::max(1, (cur_rows + L.rows_per_leaf - 1) / L.rows_per_leaf);
+    } else {
+      const int G = merge_group(n);   // triangles merged per workgroup (>= 2)
+      L.rows_per_leaf = G * NPAD;
+      L.nleaf = (cur_rows + L.rows_per_leaf - 1) / L.rows_per_leaf;
+    }
+    L.RP = std::max(round_up(std::min(L.rows_per_leaf, std::max(cur_rows, 1)), 16), NPAD);
+    if (qr_staged_tiles(L.RP, first ? 0 : NPAD, N) > QR_MAX_TILES)
+      return ctx->bad(3, "leaf does not fit LDS");
+    L.LDP = 0;
+    hipError_t e = L.R.alloc(sizeof(double) * (size_t)B * L.nleaf * NPAD * NPAD);
+    if (e != hipSuccess) return ctx->fail(e, "hipMalloc(R level)");
+    max_slot_rows = std::max(max_slot_rows, (size_t)B * L.nleaf * L.RP);
+    max_slots = std::max(max_slots, (size_t)B * L.nleaf);
+    levels.push_back(L);
+    if (L.nleaf == 1) break;
+    cur_rows = L.nleaf * NPAD;
+    first = false;
+  }
+  hipError_t e = V.alloc(sizeof(double) * max_slot_rows * NP * 16);
+  if (e != hipSuccess) return ctx->fail(e, "hipMalloc(V scratch)");
+  e = T.alloc(sizeof(double) * max_slots * NP * 256);
+  if (e != hipSuccess) return ctx->fail(e, "hipMalloc(T scratch)");
+  gram = gram_supported(rows, n) && ctx->opt.on(OPT_GRAM);
+  if (gram) {
+    gram_nchunk = gram_chunks(B, rows);
+    if (gram_nchunk > 1) {
+      e = gram_part.alloc(sizeof(double) * (size_t)B * gram_nchunk * NPAD * NPAD);
+      if (e != hipSuccess) return ctx->fail(e, "hipMalloc(partial Grams)");
+    }
+    e = gram_dsc.alloc(sizeof(double) * (size_t)B * NPAD);
+    if (e != hipSuccess) return ctx->fail(e, "hipMalloc(Gram scales)");
+    e = gram_keep.alloc(sizeof(double) * (size_t)B * NPAD * NPAD);
+    if (e != hipSuccess) return ctx->fail(e, "hipMalloc(Grams)");
+    e = gram_rinv.alloc(sizeof(double) * (size_t)B * NP * 256);
+    if (e != hipSuccess) return ctx->fail(e, "hipMalloc(Gram tile inverses)");
+    e = gram_ywork.alloc(sizeof(double) * (size_t)B * NPAD * NPAD);
+    if (e != hipSuccess) return ctx->fail(e, "hipMalloc(Gram gate work)");
+    e = gram_k2.alloc(sizeof(double) * (size_t)B);
+    if (e != hipSuccess) return ctx->fail(e, "hipMalloc(Gram gate bound)");
+    e = gram_cert.alloc(sizeof(int) * (size_t)B);
+    if (e != hipSuccess) return ctx->fail(e, "hipMalloc(Gram certificate flags)");
+    e = gram_cflag.alloc(sizeof(int) * (size_t)B);
+    if (e == hipSuccess) e = gram_ctau.alloc(sizeof(double) * (size_t)B);
+    if (e == hipSuccess) e = hipMemsetAsync(gram_cflag.p, 0, gram_cflag.bytes, ctx->stream);
+    if (e != hipSuccess) return ctx->fail(e, "hipMalloc(certificate stage 3)");
+    k2_max = gram_k2_max(rows, ctx->opt.d(OPT_GRAM_K2_MAX));
+    cqr2 = cqr2_supported(rows, n) && ctx->opt.on(OPT_CQR2);
+    e = hipMemsetAsync(gram_cert.p, 0, gram_cert.bytes, ctx->stream);
+    if (e != hipSuccess) return ctx->fail(e, "hipMemsetAsync(Gram certificate flags)");
+    e = hipMemsetAsync(gram_k2.p, 0, gram_k2.bytes, ctx->stream);
+    if (e != hipSuccess) return ctx->fail(e, "hipMemsetAsync(Gram gate bound)");
+    e = gram_ints.alloc(sizeof(int) * (3 * (size_t)B + 4));     // launch mask, count, path, fallback list
+    if (e != hipSuccess) return ctx->fail(e, "hipMalloc(Gram mask)");
+    e = hipMemsetAsync(gram_keep.p, 0, gram_keep.bytes, ctx->stream);      // (lower tiles are never written)
+    if (e != hipSuccess) return ctx->fail(e, "hipMemsetAsync(Grams)");
+    e = hipMemsetAsync(gram_ints.p, 0xFF, gram_ints.bytes, ctx->stream);   // path: all QR until factored
+    if (e != hipSuccess) return ctx->fail(e, "hipMemsetAsync(Gram mask)");
+  }
+  return 0;
+}
+
+void QrTree::release() {
+  for (auto& L : levels) L.R.release();
+  V.release(); T.release();
+  gram_part.release(); gram_dsc.release(); gram_ints.release(); gram_keep.release();
+  gram_rinv.release(); gram_ywork.release(); gram_k2.release(); gram_cert.release();
+  gram_cflag.release(); gram_ctau.release();
+  cq_W.release(); cq_Wf.release(); cq_G2.release(); cq_R1.release(); cq_R2.release(); cq_z.release(); cq_ints.release();
+}
+
+hipError_t QrTree::gram_sum(blsq_ctx* ctx, GramArgs g, double* Gp, double* Gout, int count, const int* red_mask,
+                            int red_count) {
+  g.G = gram_nchunk > 1 ? Gp : Gout;
+  ctx->begin(K_GRAM);
+  bool fused = false;
+  hipError_t e = launch_gram(g, gram_nchunk, count, ctx->stream, Gout, &fused);
+  if (e == hipSuccess && gram_nchunk > 1 && !fused)
+    e = launch_gram_reduce(Gp, gram_nchunk, NPAD, Gout, red_mask, red_count, ctx->stream);
+  ctx->end();
+  return e;
+}
+
+int QrTree::run_gram(blsq_ctx* ctx, const double* dJ, const double* df, int ldJ, const int* mask,
+                     int* nfallback, bool collective) {
+  int* fb = gram_ints.as<int>();
+  int* cnt = fb + B;
+  HIPCHK(ctx, hipMemsetAsync(cnt, 0, sizeof(int), ctx->stream));
+  int rc = run_gram_only(ctx, dJ, df, ldJ, mask, collective);
+  if (rc) return rc;
+  GramCholArgs c{};
+  c.opt = opt;
+  c.Gsrc = gram_keep.as<double>(); c.G = levels.back().R.as<double>(); c.NPAD = NPAD; c.n = n; c.mask = mask;
+  c.fb_mask = fb; c.fail_count = cnt;
+  c.path_out = fb + B + 4;
+  c.dsc = gram_dsc.as<double>();
+  c.rinv = gram_rinv.as<double>(); c.ywork = gram_ywork.as<double>(); c.k2_out = gram_k2.as<double>();
+  c.k2_max = k2_max; c.pivot_floor = 1.0 / k2_max;
+  c.cert_flag = gram_cflag.as<int>(); c.cert_tau = gram_ctau.as<double>();
+  ctx->begin(K_GRAM_CHOL);
+  hipError_t e = launch_gram_chol(c, B, ctx->stream);
+  ctx->end();
+  if (e != hipSuccess) return ctx->fail(e, "launch_gram_chol");
+  ctx->begin(K_GRAM_GATE);
+  e = launch_gram_gate(c, B, ctx->stream);
+  if (e == hipSuccess) e = launch_gram_cert_shift(c, B, ctx->stream);
+  ctx->end();
+  if (e != hipSuccess) return ctx->fail(e, "launch_gram_gate");
+  HIPCHK(ctx, hipMemcpyAsync(ctx->pinned + 1, cnt, sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
+  HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+  *nfallback = ctx->pinned[1];
+  return 0;
+}
+
+int QrTree::run_gram_only(blsq_ctx* ctx, const double* dJ, const double* df, int ldJ, const int* mask,
+                          bool collective, int k0, int nb) {
+  if (nb < 0) nb = B;
+  const size_t tri = (size_t)NPAD * NPAD;
+  GramArgs g{};
+  g.opt = opt;
+  g.J = dJ + (size_t)k0 * m * ldJ; g.strideJ = (long)m * ldJ; g.ldJ = ldJ; g.F = df + (size_t)k0 * m; g.strideF = m;
+  g.m = m; g.n = n; g.NPAD = NPAD; g.mask = mask ? mask + k0 : nullptr;
+  double* Gk = gram_keep.as<double>() + (size_t)k0 * tri;
+  double* Gp = gram_nchunk > 1 ? gram_part.as<double>() + (size_t)k0 * gram_nchunk * tri : nullptr;
+  hipError_t e = gram_sum(ctx, g, Gp, Gk, nb, g.mask, nb);
+  if (e != hipSuccess) return ctx->fail(e, "launch_gram");
+  if (collective && ctx->comm && ctx->comm_ranks > 1)
+    RCCLCHK(ctx, g_rccl.AllReduce(Gk, Gk, (size_t)nb * NPAD * NPAD, ncclDouble, ncclSum, ctx->comm,
+                                  ctx->stream));
+  return 0;
+}
+
+int QrTree::run_levels(blsq_ctx* ctx, const double* dJ, const double* df, int ldJ, const int* ncols_mask,
+                       const int* list, int count) {
+  for (size_t l = 0; l < levels.size(); ++l) {
+    const Level& L = levels[l];
+    QrArgs q = base_args();
+    q.ncols_dev = ncols_mask;
+    q.batch_list = list;
+    if (l == 0) {
+      q.A = dJ; q.strideA = (long)m * ldJ; q.ldA = ldJ; q.rowsA = m;
+      q.F = df; q.strideF = m;
+    } else {
+      const Level& Pv = levels[l - 1];
+      q.A = Pv.R.as<double>(); q.strideA = (long)Pv.nleaf * NPAD * NPAD;
+      q.ldA = NPAD; q.rowsA = Pv.nleaf * NPAD; q.F = nullptr; q.strideF = 0;
+      q.stack_rows = NPAD;
+    }
+    q.rows_per_leaf = L.rows_per_leaf; q.RP = L.RP; q.LDP = L.LDP;
+    q.Rout = L.R.as<double>();
+    ctx->begin(l == 0 ? K_QR_LEAF : K_QR_MERGE);
+    hipError_t e = launch_qr(q, L.nleaf, list ? count : B, ctx->stream);
+    ctx->end();
+    if (e != hipSuccess) return ctx->fail(e, "launch_qr");
+  }
+  return 0;
+}
+
+int QrTree::run_fallback(blsq_ctx* ctx, const double* dJ, const double* df, int ldJ, int nfb) {
+  if (!cqr2 || !gram) return run_levels(ctx, dJ, df, ldJ, fb_mask(), fb_list(), nfb);
+  hipError_t e = hipSuccess;
+  // W = J R1^-1 and w_f for the LISTED problems only (list position, not problem index): sized by the high-water mark
+  // of the list, grown geometrically — a single rejected problem of a 512-problem batch costs 8 MB, not 4.3 GB.
+  if ((size_t)nfb > cq_cap) {
+    const size_t cap = std::min<size_t>((size_t)B, std::max<size_t>((size_t)nfb, 2 * cq_cap));
+    cq_W.release(); cq_Wf.release();
+    e = cq_W.alloc(sizeof(double) * cap * m * n);
+    if (e == hipSuccess) e = cq_Wf.alloc(sizeof(double) * cap * m);
+    if (e != hipSuccess) {                              // no room for the second pass: the tree does it all
+      cq_W.release(); cq_Wf.release(); cq_cap = 0;
+      (void)hipGetLastError();
+      return run_levels(ctx, dJ, df, ldJ, fb_mask(), fb_list(), nfb);
+    }
+    cq_cap = cap;
+  }
+  if (!cq_G2.p) {
+    e = cq_G2.alloc(sizeof(double) * (size_t)B * NPAD * NPAD);
+    if (e == hipSuccess) e = cq_R2.alloc(sizeof(double) * (size_t)B * NPAD * NPAD);
+    if (e == hipSuccess) e = cq_R1.alloc(sizeof(double) * (size_t)B * NPAD * NPAD);
+    if (e == hipSuccess) e = hipMemsetAsync(cq_R1.p, 0, cq_R1.bytes, ctx->stream);
+    if (e == hipSuccess) e = cq_z.alloc(sizeof(double) * (size_t)B * NPAD);
+    if (e == hipSuccess) e = cq_ints.alloc(sizeof(int) * (4 * (size_t)B + 4));
+    if (e == hipSuccess) e = hipMemsetAsync(cq_G2.p, 0, cq_G2.bytes, ctx->stream);   // (lower tiles are never written)
+    if (e == hipSuccess) e = hipMemsetAsync(cq_R2.p, 0, cq_R2.bytes, ctx->stream);
+    if (e == hipSuccess) e = hipMemsetAsync(cq_ints.p, 0, cq_ints.bytes, ctx->stream);
+    if (e != hipSuccess) {                              // no room for the second pass: the tree does it all
+      cq_G2.release(); cq_R1.release(); cq_R2.release(); cq_z.release(); cq_ints.release();
+      cqr2 = false;
+      (void)hipGetLastError();
+      return run_levels(ctx, dJ, df, ldJ, fb_mask(), fb_list(), nfb);
+    }
+  }
+  int* piv1 = cq_ints.as<int>();
+  int* runm = piv1 + B;
+  int* piv2 = piv1 + 2 * (size_t)B;
+  int* tmask = piv1 + 3 * (size_t)B;
+  int* cnt = piv1 + 4 * (size_t)B;
+  double* Rf = levels.back().R.as<double>();
+  double* R1 = cq_R1.as<double>();
+  // 1. R1 | c = chol of the plain Gram (listed problems) into scratch, its tile inverses and scales
+  GramCholArgs c{};
+  c.opt = opt;
+  c.Gsrc = gram_keep.as<double>(); c.G = R1; c.NPAD = NPAD; c.n = n; c.skip_zero = 1;
+  c.batch_list = fb_list(); c.fb_mask = piv1; c.fail_count = cnt;
+  c.dsc = gram_dsc.as<double>(); c.rinv = gram_rinv.as<double>(); c.ywork = gram_ywork.as<double>();
+  c.k2_max = 1e300; c.pivot_floor = 1e-14;
+  ctx->begin(K_GRAM_CHOL);
+  e = launch_gram_chol(c, nfb, ctx->stream);
+  ctx->end();
+  if (e != hipSuccess) return ctx->fail(e, "launch_gram_chol(cqr2 first factor)");
+  // 2. Y = R1'^-T by the certificate's kernel, which also bounds kappa_2 of the equilibrated plain Gram: the
+  //    second pass multiplies by the EXPLICIT inverse, whose error enters the triangle as eps kappa(J) (measured:
+  //    step error 2e-18 kappa, tools/cqr2_check.py), so the tier takes a problem only if that PROVEN bound is
+  //    below CQR2_K2_MAX = 1e12 (kappa(J D) <= 1e6: error <= 2e-12); beyond, the Householder tree.
+  GramCholArgs cy = c;
+  cy.batch_list = nullptr; cy.mask = fb_mask(); cy.k2_max = CQR2_K2_MAX;
+  // (the bound on the PLAIN equilibrated Gram also bounds the augmented system's — its spectrum lies inside,
+  //  chol_kernels.hip — so it replaces the missing / larger bound of a rejected problem: the rank gate uses it)
+  cy.k2_out = gram_k2.as<double>();
+  ctx->begin(K_GRAM_GATE);
+  e = launch_gram_gate(cy, B, ctx->stream);
+  ctx->end();
+  if (e != hipSuccess) return ctx->fail(e, "launch_gram_gate(cqr2 inverse)");
+  // 3. z = R^-1 c, launch mask;  4. W = J R^-1, w_f = f - J z
+  Cqr2Args q{};
+  q.J = dJ; q.strideJ = (long)m * ldJ; q.ldJ = ldJ; q.F = df; q.strideF = m;
+  q.m = m; q.n = n; q.NPAD = NPAD; q.list = fb_list(); q.run = runm;
+  q.Y = gram_ywork.as<double>(); q.dsc = gram_dsc.as<double>(); q.R1 = R1; q.z = cq_z.as<double>();
+  q.Wj = cq_W.as<double>(); q.strideW = (long)m * n; q.Wf = cq_Wf.as<double>(); q.strideWf = m;
+  ctx->begin(K_CQR2_APPLY);
+  e = launch_cqr2_prep(q, nfb, piv1, runm, ctx->stream);
+  if (e == hipSuccess) e = launch_cqr2_apply(q, nfb, ctx->stream);
+  ctx->end();
+  if (e != hipSuccess) return ctx->fail(e, "launch_cqr2_apply");
+  // 5. G2 = [W w_f]^T [W w_f]  (the launch over the list, the reduction over the run mask)
+  GramArgs g{};
+  g.opt = opt;
+  g.J = q.Wj; g.strideJ = q.strideW; g.ldJ = n; g.F = q.Wf; g.strideF = m;
+  g.m = m; g.n = n; g.NPAD = NPAD; g.mask = runm; g.list = fb_list();   // (compacted: all XCDs)
+  g.src_by_pos = 1;                                   // (W holds the listed problems only)
+  double* G2 = cq_G2.as<double>();
+  e = gram_sum(ctx, g, gram_part.as<double>(), G2, nfb, runm, B);
+  if (e != hipSuccess) return ctx->fail(e, "launch_gram(cqr2 second pass)");
+  // 6. R2 | c2 = chol(G2)
+  GramCholArgs c2{};
+  c2.opt = opt;
+  c2.Gsrc = G2; c2.G = cq_R2.as<double>(); c2.NPAD = NPAD; c2.n = n;
+  c2.batch_list = fb_list(); c2.mask = runm; c2.fb_mask = piv2; c2.fail_count = cnt + 1;
+  c2.k2_max = 1e300; c2.pivot_floor = 0.25;           // (G2 ~ I: a pivot below 1/2 means the first pass failed)
+  ctx->begin(K_GRAM_CHOL);
+  e = launch_gram_chol(c2, nfb, ctx->stream);
+  ctx->end();
+  if (e != hipSuccess) return ctx->fail(e, "launch_gram_chol(cqr2 second factor)");
+  // 7. acceptance + R~ = R2 [R c; 0 1] into the triangle slot;  8. the tree for what is left
+  ctx->begin(K_CQR2_COMBINE);
+  e = launch_cqr2_combine(q, nfb, runm, piv2, G2, cq_R2.as<double>(), Rf, tmask, ctx->cq_accept_dev, ctx->stream);
+  ctx->end();
+  if (e != hipSuccess) return ctx->fail(e, "launch_cqr2_combine");
+  return run_levels(ctx, dJ, df, ldJ, tmask, fb_list(), nfb);
+}
+
+void QrTree::note_paths(blsq_ctx* ctx, int nfb, bool masked) {
+  ctx->gram_fallback += nfb;
+  ctx->gram_fast += B - nfb;              // (masked problems count as fast: diagnostics only)
+  // a masked call refreshes some problems only: the others keep their earlier path
+  if (!masked || !path_valid) { any_qr = nfb > 0 || masked; any_gram = nfb < B; }
+  else { any_qr = any_qr || nfb > 0; any_gram = true; }
+  path_valid = true;
+}
+
+int QrTree::run(blsq_ctx* ctx, const double* dJ, const double* df, int ldJ, const int* ncols_mask, bool collective) {
+  if (gram && df != nullptr) {
+    int nfb = 0;
+    int rc = run_gram(ctx, dJ, df, ldJ, ncols_mask, &nfb, collective);
+    if (rc) return rc;
+    note_paths(ctx, nfb, ncols_mask != nullptr);
+    if (nfb == 0) return 0;
+    ncols_mask = fb_mask();                 // only the problems the gate rejected
+  }
+  else { any_gram = false; any_qr = true; path_valid = false; }
+  return run_levels(ctx, dJ, df, ldJ, ncols_mask);
+}
+
+}  // namespace blsq_host
+
+// ---- CSNE tier ------------------------------------------------------------------------------------
+
+int CsneTier::build(blsq_ctx* ctx, int B, int m, int n, int ld, bool with_hp) {
+  hipError_t e = ints.alloc(sizeof(int) * (5 * (size_t)B + 8));
+  if (e == hipSuccess) e = pmin.alloc(sizeof(double) * (size_t)B);
+  if (e == hipSuccess) e = eta.alloc(sizeof(double) * (size_t)B);
+  if (e == hipSuccess) e = k2.alloc(sizeof(double) * (size_t)B);
+  if (e == hipSuccess) e = alpha.alloc(sizeof(double) * (size_t)B * CSNE_MAXE);
+  if (e == hipSuccess && with_hp) e = hp.alloc(sizeof(double) * (size_t)B * ld);
+  if (e != hipSuccess) return ctx->fail(e, "hipMalloc(CSNE state)");
+  for (DevBuf* b : {&ints, &pmin, &eta, &k2}) HIPCHK(ctx, hipMemsetAsync(b->p, 0, b->bytes, ctx->stream));
+  cs.B = B; cs.m = m; cs.n = n; cs.ld = ld;
+  int* ii = ints.as<int>();
+  cs.flag = ii; cs.list = ii + B; cs.fail_list = ii + 2 * (size_t)B; cs.ne = ii + 3 * (size_t)B;
+  cs.counts = ii + 5 * (size_t)B;                     // (sel_mask: ii + 4 B; scratch counter: counts + 4)
+  cs.ralpha = alpha.as<double>(); cs.hp = hp.as<double>(); cs.eta = eta.as<double>();
+  csne_geometry(m, &cs.rows_per_wg, &cs.nchunk);
+  cs.NE = 1;
+  on = true;
+  return 0;
+}
+
+void CsneTier::release() {
+  for (DevBuf* b : {&ints, &pmin, &eta, &alpha, &hp, &k2, &vec, &part}) b->release();
+}
+
+// (TRF: 52 KB per problem at n = 256; dogbox records one evaluation, the Newton step)
+bool CsneTier::ensure_recordings() {
+  if (!vec.p && vec.alloc(sizeof(double) * (size_t)cs.B * CSNE_MAXE * 3 * cs.ld) != hipSuccess) {
+    (void)hipGetLastError();
+    return false;
+  }
+  cs.rvec = vec.as<double>();
+  return true;
+}
+
+// (grows geometrically; hipFree waits for the stream)
+int CsneTier::grow_part(blsq_ctx* ctx, size_t need) {
+  if (need <= part_cap) return 0;
+  part.release();
+  const size_t cap = std::max(need, 2 * part_cap);
+  hipError_t e = part.alloc(sizeof(double) * cap);
+  if (e != hipSuccess) { part_cap = 0; return ctx->fail(e, "hipMalloc(CSNE partial sums)"); }
+  part_cap = cap;
+  cs.part = part.as<double>();
+  return 0;
+}
+
+int CsneTier::relist(blsq_ctx* ctx) {
+  hipError_t e = launch_csne_reroute(cs, -1, nullptr, nullptr, nullptr, ctx->stream);
+  if (e != hipSuccess) return ctx->fail(e, "launch_csne_reroute(relist)");
+  HIPCHK(ctx, hipMemcpyAsync(ctx->pinned + 9, cs.counts, sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
+  HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+  count = ctx->pinned[9];
+  return 0;
+}
+
+int CsneTier::reroute(blsq_ctx* ctx, QrTree& t, int nfail) {
+  hipError_t e = launch_csne_reroute(cs, nfail, t.fb_list(), t.fb_mask(), t.path_rw(), ctx->stream);
+  if (e != hipSuccess) return ctx->fail(e, "launch_csne_reroute");
+  count -= nfail;
+  t.any_qr = true;
+  return 0;
+}
+
+int CsneTier::select(blsq_ctx* ctx, QrTree& t, const GramCholArgs& chol, int nfb, int* ntree, bool masked,
+                     const std::function<hipError_t(const int* sel_mask)>& launch_select) {
+  const int B = cs.B;
+  int* sel = ints.as<int>() + 4 * (size_t)B;
+  HIPCHK(ctx, hipMemsetAsync(sel, 0, sizeof(int) * (size_t)B, ctx->stream));
+  // the norm stage alone, into the tier's own outputs: everything else either solver's factor / certificate launches
+  // would write or read is cleared (a field the solver never set is null already)
+  GramCholArgs cy = chol;
+  cy.fb_mask = sel; cy.fail_count = cs.counts + 4; cy.fail_list = nullptr; cy.path_out = nullptr;
+  cy.cert_done = nullptr; cy.cert_flag = nullptr; cy.cert_tau = nullptr; cy.cert_open = nullptr;
+  cy.cert_ym = nullptr; cy.cert_r1 = nullptr; cy.unsettled = nullptr;
+  cy.lmfin = GramCholArgs::LmFinish{}; cy.dog = GramCholArgs::DogFinish{};
+  cy.lam_out = nullptr; cy.hmax = nullptr; cy.colinfo = nullptr; cy.pmin_out = nullptr;
+  cy.k2_max = CSNE_K2_MAX; cy.k2_out = k2.as<double>();
+  ctx->begin(K_GRAM_GATE);
+  hipError_t e = launch_gram_gate(cy, B, ctx->stream);
+  ctx->end();
+  if (e != hipSuccess) return ctx->fail(e, "launch_gram_gate(csne bound)");
+  e = launch_select(sel);
+  if (e != hipSuccess) return ctx->fail(e, "launch_csne_select");
+  // two counters to the host: the problems left for the tree, the problems on the tier
+  HIPCHK(ctx, hipMemcpyAsync(ctx->pinned + 8, t.fb_count(), sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
+  HIPCHK(ctx, hipMemcpyAsync(ctx->pinned + 9, cs.counts, sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
+  HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+  *ntree = ctx->pinned[8];
+  count = ctx->pinned[9];
+  ctx->csne_routed += (unsigned long long)(nfb - *ntree);
+  if (!masked) t.any_qr = *ntree > 0;                     // (a masked call keeps the others' paths: any_qr stays)
+  t.any_gram = t.any_gram || *ntree < nfb;
+  return 0;
+}

@@ -1,7 +1,8 @@
 // Host side of the C-ABI (include/blsq.h), shared by its translation units: contexts, the RCCL binding, device buffers,
-// the factorisation front end of a plan (QrTree: Gram / certificate / CholeskyQR2 / Householder tree) and the plan
-// structures.  blsq_ctx.hip: contexts, memory, timing, communicator, diagnostics; blsq_trf.hip: TRF and the row-split
-// (TSQR) plans; blsq_dogbox.hip: dogbox plans; blsq_outer.hip: the batched outer drivers and finite differences.
+// the factorisation front end of a plan (QrTree: Gram / certificate / CholeskyQR2 / Householder tree), the CSNE tier's
+// host state (CsneTier) and the plan structures.  blsq_ctx.hip: contexts, memory, timing, communicator, diagnostics;
+// blsq_front.hip: the bodies of QrTree and CsneTier; blsq_trf.hip: TRF and the row-split (TSQR) plans; blsq_dogbox.hip:
+// dogbox plans; blsq_outer.hip: the batched outer drivers and finite differences.
 // Internal: nothing here is part of the ABI.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -12,6 +13,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <functional>
 #include <string>
 #include <vector>
 
@@ -255,92 +257,8 @@ struct QrTree {
   const int* gram_path() const { return gram ? gram_ints.as<int>() + B + 4 : nullptr; }
 
   // rows: source rows per problem at level 0
-  int build(blsq_ctx* ctx, int B_, int rows, int n_, size_t extra_rp_rows) {
-    B = B_; m = rows; n = n_; opt = &ctx->opt;
-    N = n + 1; NPAD = round_up(N, 16); NP = NPAD / 16;
-    if (NPAD > RMAX) return ctx->bad(4, "n too large (n + 1 must be <= 1024)");
-    int cur_rows = rows;
-    bool first = true;
-    size_t max_slot_rows = extra_rp_rows;   // max over launches of nslot*RP
-    size_t max_slots = (size_t)B;
-    while (true) {
-      Level L;
-      L.rowsA = cur_rows;
-      if (first) {
-        L.nleaf = std::max(1, (cur_rows + RMAX - 1) / RMAX);
-        if (L.nleaf > 1 && !merge_fits(n))
-          return ctx->bad(4, "m > 1024 needs n <= 512 (TSQR merge capacity)");
-        L.rows_per_leaf = round_up((cur_rows + L.nleaf - 1) / L.nleaf, 16);
-        if (L.rows_per_leaf < NPAD && L.nleaf > 1) L.rows_per_leaf = NPAD;
-        L.nleaf = std::max(1, (cur_rows + L.rows_per_leaf - 1) / L.rows_per_leaf);
-      } else {
-        const int G = merge_group(n);   // triangles merged per workgroup (>= 2)
-        L.rows_per_leaf = G * NPAD;
-        L.nleaf = (cur_rows + L.rows_per_leaf - 1) / L.rows_per_leaf;
-      }
-      L.RP = std::max(round_up(std::min(L.rows_per_leaf, std::max(cur_rows, 1)), 16), NPAD);
-      if (qr_staged_tiles(L.RP, first ? 0 : NPAD, N) > QR_MAX_TILES)
-        return ctx->bad(3, "leaf does not fit LDS");
-      L.LDP = 0;
-      hipError_t e = L.R.alloc(sizeof(double) * (size_t)B * L.nleaf * NPAD * NPAD);
-      if (e != hipSuccess) return ctx->fail(e, "hipMalloc(R level)");
-      max_slot_rows = std::max(max_slot_rows, (size_t)B * L.nleaf * L.RP);
-      max_slots = std::max(max_slots, (size_t)B * L.nleaf);
-      levels.push_back(L);
-      if (L.nleaf == 1) break;
-      cur_rows = L.nleaf * NPAD;
-      first = false;
-    }
-    hipError_t e = V.alloc(sizeof(double) * max_slot_rows * NP * 16);
-    if (e != hipSuccess) return ctx->fail(e, "hipMalloc(V scratch)");
-    e = T.alloc(sizeof(double) * max_slots * NP * 256);
-    if (e != hipSuccess) return ctx->fail(e, "hipMalloc(T scratch)");
-    gram = gram_supported(rows, n) && ctx->opt.on(OPT_GRAM);
-    if (gram) {
-      gram_nchunk = gram_chunks(B, rows);
-      if (gram_nchunk > 1) {
-        e = gram_part.alloc(sizeof(double) * (size_t)B * gram_nchunk * NPAD * NPAD);
-        if (e != hipSuccess) return ctx->fail(e, "hipMalloc(partial Grams)");
-      }
-      e = gram_dsc.alloc(sizeof(double) * (size_t)B * NPAD);
-      if (e != hipSuccess) return ctx->fail(e, "hipMalloc(Gram scales)");
-      e = gram_keep.alloc(sizeof(double) * (size_t)B * NPAD * NPAD);
-      if (e != hipSuccess) return ctx->fail(e, "hipMalloc(Grams)");
-      e = gram_rinv.alloc(sizeof(double) * (size_t)B * NP * 256);
-      if (e != hipSuccess) return ctx->fail(e, "hipMalloc(Gram tile inverses)");
-      e = gram_ywork.alloc(sizeof(double) * (size_t)B * NPAD * NPAD);
-      if (e != hipSuccess) return ctx->fail(e, "hipMalloc(Gram gate work)");
-      e = gram_k2.alloc(sizeof(double) * (size_t)B);
-      if (e != hipSuccess) return ctx->fail(e, "hipMalloc(Gram gate bound)");
-      e = gram_cert.alloc(sizeof(int) * (size_t)B);
-      if (e != hipSuccess) return ctx->fail(e, "hipMalloc(Gram certificate flags)");
-      e = gram_cflag.alloc(sizeof(int) * (size_t)B);
-      if (e == hipSuccess) e = gram_ctau.alloc(sizeof(double) * (size_t)B);
-      if (e == hipSuccess) e = hipMemsetAsync(gram_cflag.p, 0, gram_cflag.bytes, ctx->stream);
-      if (e != hipSuccess) return ctx->fail(e, "hipMalloc(certificate stage 3)");
-      k2_max = gram_k2_max(rows, ctx->opt.d(OPT_GRAM_K2_MAX));
-      cqr2 = cqr2_supported(rows, n) && ctx->opt.on(OPT_CQR2);
-      e = hipMemsetAsync(gram_cert.p, 0, gram_cert.bytes, ctx->stream);
-      if (e != hipSuccess) return ctx->fail(e, "hipMemsetAsync(Gram certificate flags)");
-      e = hipMemsetAsync(gram_k2.p, 0, gram_k2.bytes, ctx->stream);
-      if (e != hipSuccess) return ctx->fail(e, "hipMemsetAsync(Gram gate bound)");
-      e = gram_ints.alloc(sizeof(int) * (3 * (size_t)B + 4));     // launch mask, count, path, fallback list
-      if (e != hipSuccess) return ctx->fail(e, "hipMalloc(Gram mask)");
-      e = hipMemsetAsync(gram_keep.p, 0, gram_keep.bytes, ctx->stream);      // (lower tiles are never written)
-      if (e != hipSuccess) return ctx->fail(e, "hipMemsetAsync(Grams)");
-      e = hipMemsetAsync(gram_ints.p, 0xFF, gram_ints.bytes, ctx->stream);   // path: all QR until factored
-      if (e != hipSuccess) return ctx->fail(e, "hipMemsetAsync(Gram mask)");
-    }
-    return 0;
-  }
-  void release() {
-    for (auto& L : levels) L.R.release();
-    V.release(); T.release();
-    gram_part.release(); gram_dsc.release(); gram_ints.release(); gram_keep.release();
-    gram_rinv.release(); gram_ywork.release(); gram_k2.release(); gram_cert.release();
-    gram_cflag.release(); gram_ctau.release();
-    cq_W.release(); cq_Wf.release(); cq_G2.release(); cq_R1.release(); cq_R2.release(); cq_z.release(); cq_ints.release();
-  }
+  int build(blsq_ctx* ctx, int B_, int rows, int n_, size_t extra_rp_rows);
+  void release();
   // [J f] -> triangle by the normal equations where the conditioning gate allows it.
   // Returns the number of problems left for the Householder tree in *nfallback; their indices
   // are flagged in the fallback mask (n + 1 / 0 per problem).
@@ -348,227 +266,27 @@ struct QrTree {
   // are summed over the ranks (ONE ncclAllReduce on the ctx stream) before the factorisation, which
   // is then replicated: every rank holds the same bits, so every rank takes the same gate decision.
   int run_gram(blsq_ctx* ctx, const double* dJ, const double* df, int ldJ, const int* mask,
-               int* nfallback, bool collective) {
-    int* fb = gram_ints.as<int>();
-    int* cnt = fb + B;
-    HIPCHK(ctx, hipMemsetAsync(cnt, 0, sizeof(int), ctx->stream));
-    double* Rf = levels.back().R.as<double>();
-    GramArgs g{};
-    g.opt = opt;
-    g.J = dJ; g.strideJ = (long)m * ldJ; g.ldJ = ldJ; g.F = df; g.strideF = m;
-    g.m = m; g.n = n; g.NPAD = NPAD; g.mask = mask;
-    double* Gk = gram_keep.as<double>();
-    g.G = gram_nchunk > 1 ? gram_part.as<double>() : Gk;
-    ctx->begin(K_GRAM);
-    bool fused = false;
-    hipError_t e = launch_gram(g, gram_nchunk, B, ctx->stream, Gk, &fused);
-    if (e == hipSuccess && gram_nchunk > 1 && !fused)
-      e = launch_gram_reduce(gram_part.as<double>(), gram_nchunk, NPAD, Gk, mask, B, ctx->stream);
-    ctx->end();
-    if (e != hipSuccess) return ctx->fail(e, "launch_gram");
-    if (collective && ctx->comm && ctx->comm_ranks > 1)
-      RCCLCHK(ctx, g_rccl.AllReduce(Gk, Gk, (size_t)B * NPAD * NPAD, ncclDouble, ncclSum, ctx->comm,
-                                    ctx->stream));
-    GramCholArgs c{};
-    c.opt = opt;
-    c.Gsrc = Gk; c.G = Rf; c.NPAD = NPAD; c.n = n; c.mask = mask; c.fb_mask = fb; c.fail_count = cnt;
-    c.path_out = fb + B + 4;
-    c.dsc = gram_dsc.as<double>();
-    c.rinv = gram_rinv.as<double>(); c.ywork = gram_ywork.as<double>(); c.k2_out = gram_k2.as<double>();
-    c.k2_max = k2_max; c.pivot_floor = 1.0 / k2_max;
-    c.cert_flag = gram_cflag.as<int>(); c.cert_tau = gram_ctau.as<double>();
-    ctx->begin(K_GRAM_CHOL);
-    e = launch_gram_chol(c, B, ctx->stream);
-    ctx->end();
-    if (e != hipSuccess) return ctx->fail(e, "launch_gram_chol");
-    ctx->begin(K_GRAM_GATE);
-    e = launch_gram_gate(c, B, ctx->stream);
-    if (e == hipSuccess) e = launch_gram_cert_shift(c, B, ctx->stream);
-    ctx->end();
-    if (e != hipSuccess) return ctx->fail(e, "launch_gram_gate");
-    HIPCHK(ctx, hipMemcpyAsync(ctx->pinned + 1, cnt, sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
-    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-    *nfallback = ctx->pinned[1];
-    return 0;
-  }
+               int* nfallback, bool collective);
   // Gram front end ONLY: G = [J f]^T [J f] into gram_keep (+ the cross-rank sum); nothing is factored.
   // (k0, nb): problems k0 .. k0 + nb - 1 only (the host-pointer API feeds the Grams in sub-batches behind
   // the copies; the result does not depend on the split — a problem's chunks and their order are functions of m)
   int run_gram_only(blsq_ctx* ctx, const double* dJ, const double* df, int ldJ, const int* mask,
-                    bool collective, int k0 = 0, int nb = -1) {
-    if (nb < 0) nb = B;
-    const size_t tri = (size_t)NPAD * NPAD;
-    GramArgs g{};
-    g.opt = opt;
-    g.J = dJ + (size_t)k0 * m * ldJ; g.strideJ = (long)m * ldJ; g.ldJ = ldJ; g.F = df + (size_t)k0 * m; g.strideF = m;
-    g.m = m; g.n = n; g.NPAD = NPAD; g.mask = mask ? mask + k0 : nullptr;
-    double* Gk = gram_keep.as<double>() + (size_t)k0 * tri;
-    double* Gp = gram_nchunk > 1 ? gram_part.as<double>() + (size_t)k0 * gram_nchunk * tri : nullptr;
-    g.G = gram_nchunk > 1 ? Gp : Gk;
-    ctx->begin(K_GRAM);
-    bool fused = false;
-    hipError_t e = launch_gram(g, gram_nchunk, nb, ctx->stream, Gk, &fused);
-    if (e == hipSuccess && gram_nchunk > 1 && !fused)
-      e = launch_gram_reduce(Gp, gram_nchunk, NPAD, Gk, g.mask, nb, ctx->stream);
-    ctx->end();
-    if (e != hipSuccess) return ctx->fail(e, "launch_gram");
-    if (collective && ctx->comm && ctx->comm_ranks > 1)
-      RCCLCHK(ctx, g_rccl.AllReduce(Gk, Gk, (size_t)nb * NPAD * NPAD, ncclDouble, ncclSum, ctx->comm,
-                                    ctx->stream));
-    return 0;
-  }
+                    bool collective, int k0 = 0, int nb = -1);
   // Householder TSQR tree only (problems selected by ncols_mask; nullptr: all)
   // list / count (optional): compacted indices of the selected problems — a masked launch whose
   // active workgroups alternate with idle ones lands on a fraction of the XCDs
   int run_levels(blsq_ctx* ctx, const double* dJ, const double* df, int ldJ, const int* ncols_mask,
-                 const int* list = nullptr, int count = 0) {
-    for (size_t l = 0; l < levels.size(); ++l) {
-      const Level& L = levels[l];
-      QrArgs q = base_args();
-      q.ncols_dev = ncols_mask;
-      q.batch_list = list;
-      if (l == 0) {
-        q.A = dJ; q.strideA = (long)m * ldJ; q.ldA = ldJ; q.rowsA = m;
-        q.F = df; q.strideF = m;
-      } else {
-        const Level& Pv = levels[l - 1];
-        q.A = Pv.R.as<double>(); q.strideA = (long)Pv.nleaf * NPAD * NPAD;
-        q.ldA = NPAD; q.rowsA = Pv.nleaf * NPAD; q.F = nullptr; q.strideF = 0;
-        q.stack_rows = NPAD;
-      }
-      q.rows_per_leaf = L.rows_per_leaf; q.RP = L.RP; q.LDP = L.LDP;
-      q.Rout = L.R.as<double>();
-      ctx->begin(l == 0 ? K_QR_LEAF : K_QR_MERGE);
-      hipError_t e = launch_qr(q, L.nleaf, list ? count : B, ctx->stream);
-      ctx->end();
-      if (e != hipSuccess) return ctx->fail(e, "launch_qr");
-    }
-    return 0;
-  }
+                 const int* list = nullptr, int count = 0);
   // The problems the certificate rejected (fb_list(), nfb of them; fb_mask() = n + 1 for each): a triangle of
   // [J f] of Householder quality into their Rfinal slots — by CholeskyQR2 where its acceptance test passes
   // (second pass over J through the MFMA pipe, cqr2_kernels.hip), by the Householder TSQR tree for the rest.
-  int run_fallback(blsq_ctx* ctx, const double* dJ, const double* df, int ldJ, int nfb) {
-    if (!cqr2 || !gram) return run_levels(ctx, dJ, df, ldJ, fb_mask(), fb_list(), nfb);
-    hipError_t e = hipSuccess;
-    // W = J R1^-1 and w_f for the LISTED problems only (list position, not problem index): sized by the high-water mark
-    // of the list, grown geometrically — a single rejected problem of a 512-problem batch costs 8 MB, not 4.3 GB.
-    if ((size_t)nfb > cq_cap) {
-      const size_t cap = std::min<size_t>((size_t)B, std::max<size_t>((size_t)nfb, 2 * cq_cap));
-      cq_W.release(); cq_Wf.release();
-      e = cq_W.alloc(sizeof(double) * cap * m * n);
-      if (e == hipSuccess) e = cq_Wf.alloc(sizeof(double) * cap * m);
-      if (e != hipSuccess) {                              // no room for the second pass: the tree does it all
-        cq_W.release(); cq_Wf.release(); cq_cap = 0;
-        (void)hipGetLastError();
-        return run_levels(ctx, dJ, df, ldJ, fb_mask(), fb_list(), nfb);
-      }
-      cq_cap = cap;
-    }
-    if (!cq_G2.p) {
-      e = cq_G2.alloc(sizeof(double) * (size_t)B * NPAD * NPAD);
-      if (e == hipSuccess) e = cq_R2.alloc(sizeof(double) * (size_t)B * NPAD * NPAD);
-      if (e == hipSuccess) e = cq_R1.alloc(sizeof(double) * (size_t)B * NPAD * NPAD);
-      if (e == hipSuccess) e = hipMemsetAsync(cq_R1.p, 0, cq_R1.bytes, ctx->stream);
-      if (e == hipSuccess) e = cq_z.alloc(sizeof(double) * (size_t)B * NPAD);
-      if (e == hipSuccess) e = cq_ints.alloc(sizeof(int) * (4 * (size_t)B + 4));
-      if (e == hipSuccess) e = hipMemsetAsync(cq_G2.p, 0, cq_G2.bytes, ctx->stream);   // (lower tiles are never written)
-      if (e == hipSuccess) e = hipMemsetAsync(cq_R2.p, 0, cq_R2.bytes, ctx->stream);
-      if (e == hipSuccess) e = hipMemsetAsync(cq_ints.p, 0, cq_ints.bytes, ctx->stream);
-      if (e != hipSuccess) {                              // no room for the second pass: the tree does it all
-        cq_G2.release(); cq_R1.release(); cq_R2.release(); cq_z.release(); cq_ints.release();
-        cqr2 = false;
-        (void)hipGetLastError();
-        return run_levels(ctx, dJ, df, ldJ, fb_mask(), fb_list(), nfb);
-      }
-    }
-    int* piv1 = cq_ints.as<int>();
-    int* runm = piv1 + B;
-    int* piv2 = piv1 + 2 * (size_t)B;
-    int* tmask = piv1 + 3 * (size_t)B;
-    int* cnt = piv1 + 4 * (size_t)B;
-    double* Rf = levels.back().R.as<double>();
-    double* R1 = cq_R1.as<double>();
-    // 1. R1 | c = chol of the plain Gram (listed problems) into scratch, its tile inverses and scales
-    GramCholArgs c{};
-    c.opt = opt;
-    c.Gsrc = gram_keep.as<double>(); c.G = R1; c.NPAD = NPAD; c.n = n; c.skip_zero = 1;
-    c.batch_list = fb_list(); c.fb_mask = piv1; c.fail_count = cnt;
-    c.dsc = gram_dsc.as<double>(); c.rinv = gram_rinv.as<double>(); c.ywork = gram_ywork.as<double>();
-    c.k2_max = 1e300; c.pivot_floor = 1e-14;
-    ctx->begin(K_GRAM_CHOL);
-    e = launch_gram_chol(c, nfb, ctx->stream);
-    ctx->end();
-    if (e != hipSuccess) return ctx->fail(e, "launch_gram_chol(cqr2 first factor)");
-    // 2. Y = R1'^-T by the certificate's kernel, which also bounds kappa_2 of the equilibrated plain Gram: the
-    //    second pass multiplies by the EXPLICIT inverse, whose error enters the triangle as eps kappa(J) (measured:
-    //    step error 2e-18 kappa, tools/cqr2_check.py), so the tier takes a problem only if that PROVEN bound is
-    //    below CQR2_K2_MAX = 1e12 (kappa(J D) <= 1e6: error <= 2e-12); beyond, the Householder tree.
-    GramCholArgs cy = c;
-    cy.batch_list = nullptr; cy.mask = fb_mask(); cy.k2_max = CQR2_K2_MAX;
-    // (the bound on the PLAIN equilibrated Gram also bounds the augmented system's — its spectrum lies inside,
-    //  chol_kernels.hip — so it replaces the missing / larger bound of a rejected problem: the rank gate uses it)
-    cy.k2_out = gram_k2.as<double>();
-    ctx->begin(K_GRAM_GATE);
-    e = launch_gram_gate(cy, B, ctx->stream);
-    ctx->end();
-    if (e != hipSuccess) return ctx->fail(e, "launch_gram_gate(cqr2 inverse)");
-    // 3. z = R^-1 c, launch mask;  4. W = J R^-1, w_f = f - J z
-    Cqr2Args q{};
-    q.J = dJ; q.strideJ = (long)m * ldJ; q.ldJ = ldJ; q.F = df; q.strideF = m;
-    q.m = m; q.n = n; q.NPAD = NPAD; q.list = fb_list(); q.run = runm;
-    q.Y = gram_ywork.as<double>(); q.dsc = gram_dsc.as<double>(); q.R1 = R1; q.z = cq_z.as<double>();
-    q.Wj = cq_W.as<double>(); q.strideW = (long)m * n; q.Wf = cq_Wf.as<double>(); q.strideWf = m;
-    ctx->begin(K_CQR2_APPLY);
-    e = launch_cqr2_prep(q, nfb, piv1, runm, ctx->stream);
-    if (e == hipSuccess) e = launch_cqr2_apply(q, nfb, ctx->stream);
-    ctx->end();
-    if (e != hipSuccess) return ctx->fail(e, "launch_cqr2_apply");
-    // 5. G2 = [W w_f]^T [W w_f]
-    GramArgs g{};
-    g.opt = opt;
-    g.J = q.Wj; g.strideJ = q.strideW; g.ldJ = n; g.F = q.Wf; g.strideF = m;
-    g.m = m; g.n = n; g.NPAD = NPAD; g.mask = runm; g.list = fb_list();   // (compacted: all XCDs)
-    g.src_by_pos = 1;                                   // (W holds the listed problems only)
-    double* G2 = cq_G2.as<double>();
-    g.G = gram_nchunk > 1 ? gram_part.as<double>() : G2;
-    ctx->begin(K_GRAM);
-    bool fused = false;
-    e = launch_gram(g, gram_nchunk, nfb, ctx->stream, G2, &fused);
-    if (e == hipSuccess && gram_nchunk > 1 && !fused)
-      e = launch_gram_reduce(gram_part.as<double>(), gram_nchunk, NPAD, G2, runm, B, ctx->stream);
-    ctx->end();
-    if (e != hipSuccess) return ctx->fail(e, "launch_gram(cqr2 second pass)");
-    // 6. R2 | c2 = chol(G2)
-    GramCholArgs c2{};
-    c2.opt = opt;
-    c2.Gsrc = G2; c2.G = cq_R2.as<double>(); c2.NPAD = NPAD; c2.n = n;
-    c2.batch_list = fb_list(); c2.mask = runm; c2.fb_mask = piv2; c2.fail_count = cnt + 1;
-    c2.k2_max = 1e300; c2.pivot_floor = 0.25;           // (G2 ~ I: a pivot below 1/2 means the first pass failed)
-    ctx->begin(K_GRAM_CHOL);
-    e = launch_gram_chol(c2, nfb, ctx->stream);
-    ctx->end();
-    if (e != hipSuccess) return ctx->fail(e, "launch_gram_chol(cqr2 second factor)");
-    // 7. acceptance + R~ = R2 [R c; 0 1] into the triangle slot;  8. the tree for what is left
-    ctx->begin(K_CQR2_COMBINE);
-    e = launch_cqr2_combine(q, nfb, runm, piv2, G2, cq_R2.as<double>(), Rf, tmask, ctx->cq_accept_dev, ctx->stream);
-    ctx->end();
-    if (e != hipSuccess) return ctx->fail(e, "launch_cqr2_combine");
-    return run_levels(ctx, dJ, df, ldJ, tmask, fb_list(), nfb);
-  }
+  int run_fallback(blsq_ctx* ctx, const double* dJ, const double* df, int ldJ, int nfb);
   int* fb_mask() const { return gram_ints.as<int>(); }
   int* fb_count() const { return gram_ints.as<int>() + B; }
   int* path_rw() const { return gram_ints.as<int>() + B + 4; }
   int* fb_list() const { return gram_ints.as<int>() + 2 * (size_t)B + 4; }
   // host bookkeeping after a gate verdict: nfb of the problems refreshed by this call failed
-  void note_paths(blsq_ctx* ctx, int nfb, bool masked) {
-    ctx->gram_fallback += nfb;
-    ctx->gram_fast += B - nfb;              // (masked problems count as fast: diagnostics only)
-    // a masked call refreshes some problems only: the others keep their earlier path
-    if (!masked || !path_valid) { any_qr = nfb > 0 || masked; any_gram = nfb < B; }
-    else { any_qr = any_qr || nfb > 0; any_gram = true; }
-    path_valid = true;
-  }
+  void note_paths(blsq_ctx* ctx, int nfb, bool masked);
   const double* Rfinal() const { return levels.back().R.as<double>(); }
 
   QrArgs base_args() const {
@@ -578,51 +296,47 @@ struct QrTree {
     q.V = V.as<double>(); q.T = T.as<double>();
     return q;
   }
-  // [J f] -> R~  (levels 0..end); first_level lets TSQR-combine skip level 0
-  // ncols_mask (optional, device [B]): problems with an entry <= 1 are skipped — their
-  // triangles of the previous run stay in place (outer driver: only fresh Jacobians are factored)
+  // [J f] -> R~: by the normal equations where the gate allows it, the Householder tree for the problems it rejects
+  // (for all without the Gram front end or f).  ncols_mask (optional, device [B]): problems with an entry <= 1 are
+  // skipped — their triangles of the previous run stay in place (outer driver: only fresh Jacobians are factored)
   int run(blsq_ctx* ctx, const double* dJ, const double* df, int ldJ,
-          const int* ncols_mask = nullptr, bool collective = false) {
-    if (gram && df != nullptr) {
-      int nfb = 0;
-      int rc = run_gram(ctx, dJ, df, ldJ, ncols_mask, &nfb, collective);
-      if (rc) return rc;
-      ctx->gram_fallback += nfb;
-      ctx->gram_fast += B - nfb;            // (masked problems count as fast: diagnostics only)
-      // a masked call refreshes some problems only: the others keep their earlier path
-      if (ncols_mask == nullptr || !path_valid) { any_qr = nfb > 0 || ncols_mask != nullptr; any_gram = nfb < B; }
-      else { any_qr = any_qr || nfb > 0; any_gram = true; }
-      path_valid = true;
-      if (nfb == 0) return 0;
-      ncols_mask = gram_ints.as<int>();     // only the problems the gate rejected
-    }
-    else { any_gram = false; any_qr = true; path_valid = false; }
-    for (size_t l = 0; l < levels.size(); ++l) {
-      const Level& L = levels[l];
-      QrArgs q = base_args();
-      q.ncols_dev = ncols_mask;
-      if (l == 0) {
-        q.A = dJ; q.strideA = (long)m * ldJ; q.ldA = ldJ; q.rowsA = m;
-        q.F = df; q.strideF = m;
-      } else {
-        const Level& Pv = levels[l - 1];
-        q.A = Pv.R.as<double>(); q.strideA = (long)Pv.nleaf * NPAD * NPAD;
-        q.ldA = NPAD; q.rowsA = Pv.nleaf * NPAD; q.F = nullptr; q.strideF = 0;
-        q.stack_rows = NPAD;
-      }
-      q.rows_per_leaf = L.rows_per_leaf; q.RP = L.RP; q.LDP = L.LDP;
-      q.Rout = L.R.as<double>();
-      ctx->begin(l == 0 ? K_QR_LEAF : K_QR_MERGE);
-      hipError_t e = launch_qr(q, L.nleaf, B, ctx->stream);
-      ctx->end();
-      if (e != hipSuccess) return ctx->fail(e, "launch_qr");
-    }
-    return 0;
-  }
+          const int* ncols_mask = nullptr, bool collective = false);
+
+ private:
+  // the Grams of the `count` problems of g into Gout: launch_gram (several row chunks: partials into Gp), then the
+  // reduction of the partials over red_count problems (red_mask) unless the launch has fused it
+  hipError_t gram_sum(blsq_ctx* ctx, GramArgs g, double* Gp, double* Gout, int count, const int* red_mask,
+                      int red_count);
 };
 
 }  // namespace blsq_host
 using namespace blsq_host;
+
+// The CSNE tier (csne_kernels.hip), ONE host state for the TRF and the dogbox plans: rejected problems
+// whose Gram-Cholesky factor qualifies keep it as a preconditioner, their steps corrected against J in one streaming
+// pass.  The select launch, the correction and its read-back differ between the solvers and stay with them.
+struct CsneTier {
+  bool on = false;                  // the plan's shape is supported and option `csne` != 0 (build ran)
+  int count = 0;                    // problems on the tier now (host copy of cs.counts[0])
+  DevBuf ints;                      // flag [B], list [B], fail_list [B], ne [B], sel_mask [B], counts [4], scratch [4]
+  DevBuf pmin, eta, alpha, hp;      // (hp: TRF only)
+  DevBuf k2;                        // [B] the bound on kappa_2 of the COMPUTED system (the certificate's own output, gram_k2, keeps its meaning)
+  DevBuf vec, part;                 // the recordings (allocated on first use), the partial sums of the pass
+  size_t part_cap = 0;              // (list positions x chunks x NE) the partial-sum buffer holds
+  CsneState cs{};
+
+  int build(blsq_ctx* ctx, int B, int m, int n, int ld, bool with_hp);   // buffers, zeroed, and cs over them; on = true
+  void release();
+  bool ensure_recordings();         // false: no room for them (the caller takes the tier out of service)
+  int grow_part(blsq_ctx* ctx, size_t need);
+  int relist(blsq_ctx* ctx);        // a masked factor call refreshed some problems: the list from the flags
+  int reroute(blsq_ctx* ctx, QrTree& t, int nfail);   // cs.fail_list leaves the tier for t.fb_list()
+  // which of the nfb problems the certificate has just rejected (t.fb_list()) the tier takes: the bound from the
+  // certificate's norm stage over `chol` (the plan's factor arguments) with CSNE_K2_MAX as its gate, then the plan's
+  // select launch; *ntree = the problems left for the other tiers
+  int select(blsq_ctx* ctx, QrTree& t, const GramCholArgs& chol, int nfb, int* ntree, bool masked,
+             const std::function<hipError_t(const int* sel_mask)>& launch_select);
+};
 
 // The optimistic verdict of a device-resident factor call — ONE state machine for the TRF and the dogbox plans
 // (verdict_drop / verdict_arm / verdict_resolve below).  blsq_*_factor_dev does not wait for the gate's counters
@@ -670,16 +384,10 @@ struct blsq_trf_plan : VerdictState {
   DevBuf aug_hmax;                  // [B] largest diagonal entry of H (LmState::hmax: which Newton systems of a
                                     // Householder-path problem may be factored from the Gram)
   bool gram_valid = false;          // tree.gram_keep holds the Grams of the current factor call's problems
-  // CSNE tier (csne_kernels.hip): rejected problems whose steps are corrected against J in one streaming pass
+  // CSNE tier: rejected problems whose steps are corrected against J in one streaming pass, at step time
+  CsneTier csne;
   int last_scale_mode = 0;          // scale_mode of the last factor call (a problem that leaves the tier at step time is prepared again)
   int lm_rounds_done = 0;           // Newton rounds the last trf_lm_rounds call ran (the deepest recording: 1 + that)
-  bool csne_on = false;             // the shape is supported and BLSQ_CSNE != 0
-  int ncsne = 0;                    // problems on the tier now (host copy of cs.counts[0])
-  DevBuf cs_ints;                   // flag [B], list [B], fail_list [B], ne [B], sel_mask [B], counts [4], scratch [4]
-  DevBuf cs_pmin, cs_eta, cs_alpha, cs_hp, cs_vec, cs_part;
-  DevBuf cs_k2;                     // [B] the bound on kappa_2 of the COMPUTED system (the certificate's own output, gram_k2, keeps its meaning)
-  size_t cs_part_cap = 0;           // (list positions x chunks x NE) the partial-sum buffer holds
-  CsneState cs{};
   // TSQR (multi-rank) extras
   int nranks = 1, m_total = 0;
   bool ranks_agreed = false;        // the ranks have compared their plan configuration (first factor call)
@@ -720,12 +428,8 @@ struct blsq_dogbox_plan : VerdictState {
   DevBuf gate_ints;                 // [3B] fast flags, Jacobi launch mask, finished-in-the-Cholesky-kernel flags
   DevBuf colinfo;                   // [B][2] column-norm summary of the free block (Gram-path problems)
   int svdfree_enable = 1;
-  // CSNE tier (csne_kernels.hip): the Newton step of a rejected problem's free block corrected against J at factor time
-  bool csne_on = false;
-  int ncsne = 0;
-  DevBuf cs_ints, cs_pmin, cs_eta, cs_alpha, cs_k2, cs_vec, cs_part;
-  size_t cs_part_cap = 0;
-  CsneState cs{};
+  // CSNE tier: the Newton step of a rejected problem's free block corrected against J at factor time
+  CsneTier csne;
   DogState st{};
   DogStepOut out{};
 };
@@ -773,8 +477,6 @@ PublishArgs verdict_rides(Plan* p) {
   p->pend_seq = ++p->ctx->pub_seq;
   return PublishArgs{p->tree.fb_count(), 3, p->pend_pin, p->pend_seq};
 }
-
-// prep from the Gram, Cholesky of H with the pivot gate, conditioning gate; *nfb = problems of this
 
 // the back-off of a plan's guessing (VerdictState::guess_pause)
 inline void verdict_wrong(VerdictState* p) {

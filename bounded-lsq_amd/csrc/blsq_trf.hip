@@ -83,31 +83,13 @@ int trf_alloc_state(blsq_trf_plan* p) {
     p->lm_enable = ctx->opt.i(OPT_NO_SVDFREE) == 1 ? 0 : 1;
     p->lm_gate_mask = p->lm_enable ? (band ? 2 : 3) : 0;
   }
-  {
-    // CSNE tier: single-rank plans of its shapes with the normal-equations front end on (BLSQ_CSNE = 0: off)
-    p->csne_on = p->tree.gram && p->nranks == 1 && csne_supported(p->m, p->n) && ctx->opt.on(OPT_CSNE);
-    if (p->csne_on) {
-      ALLOC(p->cs_ints, sizeof(int) * (5 * (size_t)B + 8));
-      ALLOC(p->cs_pmin, sizeof(double) * (size_t)B);
-      ALLOC(p->cs_eta, sizeof(double) * (size_t)B);
-      ALLOC(p->cs_k2, sizeof(double) * (size_t)B);
-      HIPCHK(ctx, hipMemsetAsync(p->cs_k2.p, 0, p->cs_k2.bytes, ctx->stream));
-      ALLOC(p->cs_alpha, sizeof(double) * (size_t)B * CSNE_MAXE);
-      ALLOC(p->cs_hp, sizeof(double) * vs);
-      HIPCHK(ctx, hipMemsetAsync(p->cs_ints.p, 0, p->cs_ints.bytes, ctx->stream));
-      HIPCHK(ctx, hipMemsetAsync(p->cs_pmin.p, 0, p->cs_pmin.bytes, ctx->stream));
-      HIPCHK(ctx, hipMemsetAsync(p->cs_eta.p, 0, p->cs_eta.bytes, ctx->stream));
-      CsneState& cs = p->cs;
-      cs.B = B; cs.m = p->m; cs.n = p->n; cs.ld = ld;
-      int* ii = p->cs_ints.as<int>();
-      cs.flag = ii; cs.list = ii + B; cs.fail_list = ii + 2 * (size_t)B; cs.ne = ii + 3 * (size_t)B;
-      cs.counts = ii + 5 * (size_t)B;                     // (sel_mask: ii + 4 B; scratch counter: counts + 4)
-      cs.ralpha = p->cs_alpha.as<double>(); cs.hp = p->cs_hp.as<double>(); cs.eta = p->cs_eta.as<double>();
-      csne_geometry(p->m, &cs.rows_per_wg, &cs.nchunk);
-      cs.NE = 1;
-      p->st.csne = cs.flag; p->st.csne_hp = cs.hp;
-      p->lm.csne = cs.flag; p->lm.csne_ne = cs.ne; p->lm.csne_alpha = cs.ralpha;
-    }
+  // CSNE tier: single-rank plans of its shapes with the normal-equations front end on (BLSQ_CSNE = 0: off)
+  if (p->tree.gram && p->nranks == 1 && csne_supported(p->m, p->n) && ctx->opt.on(OPT_CSNE)) {
+    int rc = p->csne.build(ctx, B, p->m, p->n, ld, /*with_hp=*/true);
+    if (rc) return rc;
+    const CsneState& cs = p->csne.cs;
+    p->st.csne = cs.flag; p->st.csne_hp = cs.hp;
+    p->lm.csne = cs.flag; p->lm.csne_ne = cs.ne; p->lm.csne_alpha = cs.ralpha;
   }
   p->aug_RP = std::max(aug_rows(p->n), ld);
   if (aug_rows(p->n) > RMAX) return ctx->bad(4, "n too large for the augmented system (n <= 512)");
@@ -205,7 +187,7 @@ GramCholArgs trf_chol_args(blsq_trf_plan* p, const int* mask) {
   c.cert_flag = t.gram_cflag.as<int>(); c.cert_tau = t.gram_ctau.as<double>();
   c.colinfo = p->aug_colinfo.as<double>();
   c.hmax = p->aug_hmax.as<double>(); c.lam_out = p->aug_lam.as<double>();
-  if (p->csne_on) c.pmin_out = p->cs_pmin.as<double>();
+  if (p->csne.on) c.pmin_out = p->csne.pmin.as<double>();
   if (p->ld > 80) {
     c.cert_ym = p->aug_ym.as<double>(); c.cert_r1 = p->aug_r1.as<double>();
     // (cert_direct = 0: every open problem through the norm stage, the explicit inverse)
@@ -246,6 +228,7 @@ int trf_gate_tail(blsq_trf_plan* p, const GramCholArgs& c, bool full = true) {
   return 0;
 }
 
+// prep from the Gram, Cholesky of H with the pivot gate, conditioning gate; *nfb = problems of this
 // call that must go to the Householder tree (their indices are flagged in tree.fb_mask()).
 int trf_gram_stage(blsq_trf_plan* p, int scale_mode, const int* mask, int* nfb, bool defer = false) {
   blsq_ctx* ctx = p->ctx;
@@ -317,65 +300,28 @@ int trf_gram_stage(blsq_trf_plan* p, int scale_mode, const int* mask, int* nfb, 
   return 0;
 }
 
-// the problems the gate rejected: Householder tree on [J f], prep again from the triangle
-// (a masked factor call has refreshed some problems: the tier's list is rebuilt from the flags)
-int trf_csne_relist(blsq_trf_plan* p) {
-  blsq_ctx* ctx = p->ctx;
-  hipError_t e = launch_csne_reroute(p->cs, -1, nullptr, nullptr, nullptr, ctx->stream);
-  if (e != hipSuccess) return ctx->fail(e, "launch_csne_reroute(relist)");
-  HIPCHK(ctx, hipMemcpyAsync(ctx->pinned + 9, p->cs.counts, sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
-  HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-  p->ncsne = ctx->pinned[9];
-  return 0;
-}
-
-// CSNE tier, factor side: which of the nfb problems the certificate has just rejected (tree.fb_list()) keep their
-// Gram-Cholesky factor as a preconditioner and have their steps corrected against J (csne_kernels.hip).  The bound on
-// kappa_2 of the COMPUTED augmented system comes from the certificate's norm stage run with CSNE_K2_MAX as its gate
-// (explicit inverse, as the CholeskyQR2 tier does for the plain system); *ntree = the problems left for the other tiers.
+// CSNE tier, factor side: which of the nfb problems the certificate has just rejected keep their Gram-Cholesky factor
+// as a preconditioner and have their steps corrected against J (CsneTier::select); *ntree = the problems left for the
+// other tiers.
 int trf_csne_select(blsq_trf_plan* p, const double* dJ, const double* df, int ldJ, int nfb, int* ntree, bool masked) {
-  blsq_ctx* ctx = p->ctx;
+  CsneTier& tier = p->csne;
   QrTree& t = p->tree;
-  const int B = p->B;
   *ntree = nfb;
-  if (!p->csne_on || !p->lm_enable) return 0;
-  hipError_t e = hipSuccess;
-  if (!p->cs_vec.p) {                                     // first use: the recordings (52 KB per problem at n = 256)
-    e = p->cs_vec.alloc(sizeof(double) * (size_t)B * CSNE_MAXE * 3 * p->ld);
-    if (e != hipSuccess) { (void)hipGetLastError(); p->csne_on = false; return 0; }   // (no room: the other tiers)
-    p->cs.rvec = p->cs_vec.as<double>();
-    p->lm.csne_vec = p->cs.rvec;
-  }
-  int* sel = p->cs_ints.as<int>() + 4 * (size_t)B;
-  int* scratch = p->cs.counts + 4;
-  HIPCHK(ctx, hipMemsetAsync(sel, 0, sizeof(int) * (size_t)B, ctx->stream));
-  GramCholArgs cy = trf_chol_args(p, t.fb_mask());        // (mask: the rejected problems only)
-  cy.fb_mask = sel; cy.fail_count = scratch; cy.fail_list = nullptr; cy.path_out = nullptr;
-  cy.cert_done = nullptr; cy.cert_flag = nullptr; cy.cert_tau = nullptr; cy.cert_open = nullptr;
-  cy.cert_ym = nullptr; cy.cert_r1 = nullptr; cy.unsettled = nullptr; cy.lmfin = GramCholArgs::LmFinish{};
-  cy.lam_out = nullptr; cy.hmax = nullptr; cy.colinfo = nullptr; cy.pmin_out = nullptr;
-  cy.k2_max = CSNE_K2_MAX; cy.k2_out = p->cs_k2.as<double>();
-  ctx->begin(K_GRAM_GATE);
-  e = launch_gram_gate(cy, B, ctx->stream);
-  ctx->end();
-  if (e != hipSuccess) return ctx->fail(e, "launch_gram_gate(csne bound)");
-  e = launch_csne_select(p->cs, p->lm, nfb, t.fb_list(), t.fb_mask(), t.fb_count(), t.path_rw(), sel,
-                         p->cs_k2.as<double>(), p->cs_pmin.as<double>(), p->aug_colinfo.as<double>(), ctx->stream);
-  if (e != hipSuccess) return ctx->fail(e, "launch_csne_select");
-  // two counters to the host: the problems left for the tree, the problems on the tier
-  HIPCHK(ctx, hipMemcpyAsync(ctx->pinned + 8, t.fb_count(), sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
-  HIPCHK(ctx, hipMemcpyAsync(ctx->pinned + 9, p->cs.counts, sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
-  HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-  *ntree = ctx->pinned[8];
-  p->ncsne = ctx->pinned[9];
-  ctx->csne_routed += (unsigned long long)(nfb - *ntree);
-  p->cs.J = dJ; p->cs.strideJ = (long)p->m * ldJ; p->cs.ldJ = ldJ; p->cs.F = df; p->cs.strideF = p->m;
-  if (!masked) t.any_qr = *ntree > 0;                     // (a masked call keeps the others' paths: any_qr stays)
-  t.any_gram = t.any_gram || *ntree < nfb;
+  if (!tier.on || !p->lm_enable) return 0;
+  if (!tier.ensure_recordings()) { tier.on = false; return 0; }   // (no room: the other tiers)
+  p->lm.csne_vec = tier.cs.rvec;
+  int rc = tier.select(p->ctx, t, trf_chol_args(p, t.fb_mask()), nfb, ntree, masked, [&](const int* sel) {
+    return launch_csne_select(tier.cs, p->lm, nfb, t.fb_list(), t.fb_mask(), t.fb_count(), t.path_rw(), sel,
+                              tier.k2.as<double>(), tier.pmin.as<double>(), p->aug_colinfo.as<double>(), p->ctx->stream);
+  });
+  if (rc) return rc;
+  tier.cs.J = dJ; tier.cs.strideJ = (long)p->m * ldJ; tier.cs.ldJ = ldJ; tier.cs.F = df; tier.cs.strideF = p->m;
   p->use_chol = t.any_gram; p->use_qr = t.any_qr;
   return 0;
 }
 
+// the problems the gate rejected: the tier takes what it can, the Householder tree on [J f] the rest, which are
+// prepared again from their triangle
 int trf_fallback_stage(blsq_trf_plan* p, const double* dJ, const double* df, int ldJ, int scale_mode,
                        int nfb, bool masked = false) {
   blsq_ctx* ctx = p->ctx;
@@ -407,7 +353,7 @@ int trf_factor_core(blsq_trf_plan* p, const double* dJ, const double* df, int ld
   }
   if (!gram_done && (rc = p->tree.run_gram_only(ctx, dJ, df, ldJ, mask, false))) return rc;
   p->last_scale_mode = scale_mode;
-  if (!mask) p->ncsne = 0;                                // (the prep launch clears every flag; trf_csne_select sets them anew)
+  if (!mask) p->csne.count = 0;                           // (the prep launch clears every flag; trf_csne_select sets them anew)
   int nfb = 0;
   // (never in the n-band that always takes the SVD, nor right after a wrong guess)
   const bool defer = may_defer && !mask && verdict_may_guess(p) && p->lm_enable && p->pend_pin;
@@ -415,7 +361,7 @@ int trf_factor_core(blsq_trf_plan* p, const double* dJ, const double* df, int ld
   if (defer) { p->pend_dJ = dJ; p->pend_df = df; p->pend_ldJ = ldJ; p->pend_scale_mode = scale_mode; }
   else if (!mask) p->guess_ok = (nfb == 0 && p->njac == 0);
   if (nfb > 0 && (rc = trf_fallback_stage(p, dJ, df, ldJ, scale_mode, nfb, mask != nullptr))) return rc;
-  if (nfb == 0 && mask && p->ncsne > 0 && (rc = trf_csne_relist(p))) return rc;   // (refreshed problems have left the tier)
+  if (nfb == 0 && mask && p->csne.count > 0 && (rc = p->csne.relist(ctx))) return rc;   // (refreshed problems have left the tier)
   return trf_finish(p);
 }
 
@@ -606,28 +552,21 @@ int trf_lm_rounds(blsq_trf_plan* p, const double* dDelta, const double* dalpha_i
 // the step kernel).  Problems whose acceptance fails are listed in cs.fail_list (trf_csne_verdict).
 int trf_csne_correct(blsq_trf_plan* p, const double* dDelta, const double* dalpha_in) {
   blsq_ctx* ctx = p->ctx;
-  CsneState& cs = p->cs;
+  CsneTier& tier = p->csne;
+  CsneState& cs = tier.cs;
   const int ne_max = std::min(CSNE_MAXE, 1 + std::max(0, p->lm_rounds_done));
   const bool mfma = ctx->opt.on(OPT_CSNE_MFMA);           // (all eight evaluation slots; the sums do not depend on the depth)
   const int NE = mfma ? CSNE_MAXE : csne_launch_evals(ne_max);   // (else the launch's split over the waves: NEH x G >= ne_max)
   cs.NE = NE;
-  const size_t need = (size_t)p->ncsne * cs.nchunk * ((size_t)NE * p->ld + 16);
-  if (need > p->cs_part_cap) {                            // (grows geometrically; hipFree waits for the stream)
-    p->cs_part.release();
-    const size_t cap = std::max(need, 2 * p->cs_part_cap);
-    hipError_t ae = p->cs_part.alloc(sizeof(double) * cap);
-    if (ae != hipSuccess) { p->cs_part_cap = 0; return ctx->fail(ae, "hipMalloc(CSNE partial sums)"); }
-    p->cs_part_cap = cap;
-    cs.part = p->cs_part.as<double>();
-  }
+  { int rc_ = tier.grow_part(ctx, (size_t)tier.count * cs.nchunk * ((size_t)NE * p->ld + 16)); if (rc_) return rc_; }
   HIPCHK(ctx, hipMemsetAsync(cs.counts + 1, 0, sizeof(int), ctx->stream));
   ctx->begin(K_CSNE_PASS);
-  hipError_t e = mfma ? launch_csne_pass_mfma(cs, p->st.d, p->ncsne, ctx->stream)
-                      : launch_csne_pass(cs, p->st.d, p->ncsne, ctx->stream);
+  hipError_t e = mfma ? launch_csne_pass_mfma(cs, p->st.d, tier.count, ctx->stream)
+                      : launch_csne_pass(cs, p->st.d, tier.count, ctx->stream);
   ctx->end();
   if (e != hipSuccess) return ctx->fail(e, "launch_csne_pass");
   ctx->begin(K_CSNE_FIX);
-  e = launch_csne_fix(cs, p->st, p->lm, dDelta, dalpha_in, p->ncsne, ctx->stream);
+  e = launch_csne_fix(cs, p->st, p->lm, dDelta, dalpha_in, tier.count, ctx->stream);
   ctx->end();
   if (e != hipSuccess) return ctx->fail(e, "launch_csne_fix");
   return 0;
@@ -638,7 +577,7 @@ int trf_csne_correct(blsq_trf_plan* p, const double* dDelta, const double* dalph
 // and the step runs once more (*redo).
 int trf_csne_verdict(blsq_trf_plan* p, int ncs, bool* redo) {
   blsq_ctx* ctx = p->ctx;
-  CsneState& cs = p->cs;
+  const CsneState& cs = p->csne.cs;
   QrTree& t = p->tree;
   int seq = 0;
   HIPCHK(ctx, ctx->publish(cs.counts + 1, 1, ctx->pinned + 12, &seq));
@@ -648,16 +587,14 @@ int trf_csne_verdict(blsq_trf_plan* p, int ncs, bool* redo) {
   ctx->csne_declined += (unsigned long long)nfail;
   if (nfail == 0) return 0;
   *redo = true;
-  hipError_t e = launch_csne_reroute(cs, nfail, t.fb_list(), t.fb_mask(), t.path_rw(), ctx->stream);
-  if (e != hipSuccess) return ctx->fail(e, "launch_csne_reroute");
-  p->ncsne = ncs - nfail;
-  int rc = t.run_fallback(ctx, cs.J, cs.F, cs.ldJ, nfail);
-  if (rc) return rc;
+  int rc;
+  if ((rc = p->csne.reroute(ctx, t, nfail))) return rc;
+  if ((rc = t.run_fallback(ctx, cs.J, cs.F, cs.ldJ, nfail))) return rc;
   ctx->begin(K_PREP);
-  e = launch_trf_prep(p->st, p->last_scale_mode, 0, t.fb_mask(), 1, ctx->stream);
+  hipError_t e = launch_trf_prep(p->st, p->last_scale_mode, 0, t.fb_mask(), 1, ctx->stream);
   ctx->end();
   if (e != hipSuccess) return ctx->fail(e, "launch_trf_prep(csne redo)");
-  t.any_qr = true; p->use_qr = true;
+  p->use_qr = true;
   p->gate_done = false; p->njac = -1;
   return trf_finish(p);
 }
@@ -701,8 +638,7 @@ extern "C" int blsq_trf_plan_destroy(blsq_trf_plan* p) {
   p->o_info.release(); p->in_J.release(); p->in_f.release(); p->in_vec.release();
   p->in_scal.release();
   p->lm_sa.release(); p->lm_Xa.release(); p->lm_ints.release(); p->lm_sc.release();
-  p->cs_k2.release(); p->cs_ints.release(); p->cs_pmin.release(); p->cs_eta.release(); p->cs_alpha.release(); p->cs_hp.release();
-  p->cs_vec.release(); p->cs_part.release();
+  p->csne.release();
   p->lm_ph.release(); p->aug_colinfo.release(); p->aug_hmax.release(); p->aug_lam.release(); p->aug_ym.release(); p->aug_r1.release(); p->aug_open.release(); p->aug_mask.release();
   delete p;
   return 0;
@@ -767,7 +703,7 @@ extern "C" int blsq_trf_step_dev(blsq_trf_plan* p, const double* dDelta, const d
   for (int pass = 0; pass < 4; ++pass) {
     int rc = trf_lm_rounds(p, dDelta, dalpha_in);
     if (rc) return rc;
-    const int ncs = p->ncsne;
+    const int ncs = p->csne.count;
     if (ncs > 0 && (rc = trf_csne_correct(p, dDelta, dalpha_in))) return rc;
     ctx->begin(K_STEP);
     const PublishArgs pub = verdict_rides(p);
@@ -825,12 +761,12 @@ extern "C" int blsq_trf_debug_csne(blsq_trf_plan* p, int32_t* on_tier, double* e
   if (!p) return -1;
   blsq_ctx* ctx = p->ctx;
   { int rc_ = trf_resolve(p, nullptr); if (rc_) return rc_; }
-  if (!p->csne_on) {
+  if (!p->csne.on) {
     for (int b = 0; b < p->B; ++b) { if (on_tier) on_tier[b] = 0; if (eta) eta[b] = 0.0; }
     return 0;
   }
-  if (on_tier) HIPCHK(ctx, hipMemcpyAsync(on_tier, p->cs.flag, sizeof(int) * p->B, hipMemcpyDeviceToHost, ctx->stream));
-  if (eta) HIPCHK(ctx, hipMemcpyAsync(eta, p->cs.eta, sizeof(double) * p->B, hipMemcpyDeviceToHost, ctx->stream));
+  if (on_tier) HIPCHK(ctx, hipMemcpyAsync(on_tier, p->csne.cs.flag, sizeof(int) * p->B, hipMemcpyDeviceToHost, ctx->stream));
+  if (eta) HIPCHK(ctx, hipMemcpyAsync(eta, p->csne.cs.eta, sizeof(double) * p->B, hipMemcpyDeviceToHost, ctx->stream));
   return blsq_sync(ctx);
 }
 
