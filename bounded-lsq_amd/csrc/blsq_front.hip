@@ -238,7 +238,7 @@ int QrTree::run_fallback(blsq_ctx* ctx, const double* dJ, const double* df, int 
   GramCholArgs cy = c;
   cy.batch_list = nullptr; cy.mask = fb_mask(); cy.k2_max = CQR2_K2_MAX;
   // (the bound on the PLAIN equilibrated Gram also bounds the augmented system's — its spectrum lies inside,
-  //  chol_kernels.hip — so it replaces the missing / larger bound of a rejected problem: the rank gate uses it)
+  //  chol_rl.hip — so it replaces the missing / larger bound of a rejected problem: the rank gate uses it)
   cy.k2_out = gram_k2.as<double>();
   ctx->begin(K_GRAM_GATE);
   e = launch_gram_gate(cy, B, ctx->stream);

@@ -235,7 +235,7 @@ struct QrTree {
   const blsq::Options* opt = nullptr;      // the ctx's switches (set by build)
   std::vector<Level> levels;        // levels.back().nleaf == 1
   DevBuf V, T;                      // scratch shared by all QR launches of the plan
-  // normal-equations fast path (gram_kernels.hip, chol_kernels.hip); problems that fail its gate use the levels
+  // normal-equations fast path (gram_kernels.hip, chol_reg.hip, chol_rl.hip); problems that fail its gate use the levels
   bool gram = false;
   int gram_nchunk = 1;
   DevBuf gram_part, gram_dsc, gram_ints;   // partial Grams, column scales, [B] fallback mask + count

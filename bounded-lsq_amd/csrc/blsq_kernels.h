@@ -55,7 +55,7 @@ void set_qr_debug_buffer(double* p);
 hipError_t qr_cqr_stats(unsigned long long out[2], int reset, hipStream_t st);
 
 // ------------------------------------------------- normal-equations fast path ----
-// gram_kernels.hip / chol_kernels.hip: G = [J f]^T [J f] by MFMA, equilibrated blocked Cholesky in place in the
+// gram_kernels.hip / chol_reg.hip / chol_rl.hip: G = [J f]^T [J f] by MFMA, equilibrated blocked Cholesky in place in the
 // triangle slot, conditioning gate; problems that fail it get fb_mask[b] = n + 1 and are
 // factored by the Householder tree instead.
 struct GramArgs {
@@ -167,7 +167,7 @@ struct GramCholArgs {
                           // own floor is far below the gate's, csne_kernels.hip); not written by a shifted launch
 };
 // A problem stays on the normal-equations path only if the PROVEN bound K2 >= kappa_2(R'^T R') of its
-// equilibrated system is at most GRAM_K2_MAX (chol_kernels.hip, gram_cond_kernel).  Consequence used
+// equilibrated system is at most GRAM_K2_MAX (cert_kernels.hip, gram_cond_kernel).  Consequence used
 // by the rank gates: lambda_max >= 1 (unit diagonal), so sigma_min(R') >= 1 / sqrt(GRAM_K2_MAX).
 #ifndef BLSQ_K2_MAX
 #define BLSQ_K2_MAX 2.5e5
@@ -428,10 +428,10 @@ struct LmState {
                           // and the round kernels leave them alone (a problem's arithmetic must not depend
                           // on whether its batch also holds Householder-path problems)
 };
-// rank gate of the SVD-free paths (lm_kernels.hip; the dogbox finish in chol_kernels.hip)
+// rank gate of the SVD-free paths (lm_kernels.hip; the dogbox finish in chol_reg.hip)
 static constexpr double LM_EPS = 2.220446049250313e-16;
 static constexpr double LM_GATE_MARGIN = 1.0e3;
-// slots of LmState.sc / LmState.st, phases of the iteration (lm_kernels.hip; the fused rounds in chol_kernels.hip)
+// slots of LmState.sc / LmState.st, phases of the iteration (lm_kernels.hip; the fused rounds in chol_reg.hip)
 enum { LM_IDLE = 0, LM_EVAL = 1, LM_FINAL = 2 };
 enum { SC_ALPHA = 0, SC_LO, SC_HI, SC_PHI, SC_DPHI, SC_DELTA, SC_SMAX, SC_SMIN };
 enum { ST_IT = 0, ST_PHASE, ST_NITER };
@@ -441,6 +441,8 @@ enum { ST_IT = 0, ST_PHASE, ST_NITER };
 // of the batch (c.rinv / c.dsc = what the augmented Cholesky left)
 hipError_t launch_lm_rounds_reg(const GramCholArgs& c, const LmState& lm, const double* Delta,
                                 const double* alpha_in, hipStream_t s);
+// launch_gram_chol for NPAD <= 80 (chol_reg.hip): gram_chol_reg_kernel, one wave per problem; a.count = problems
+hipError_t launch_gram_chol_reg(const GramCholArgs& a, hipStream_t s);
 hipError_t launch_lm_gate(const LmState& lm, int enable, hipStream_t s);   // enable: bit 0 Householder-path, bit 1 normal-equations-path problems
 hipError_t launch_lm_start(const LmState& lm, const double* Delta, const double* alpha_in,
                            hipStream_t s);

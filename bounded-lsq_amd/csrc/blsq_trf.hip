@@ -402,7 +402,7 @@ int trf_lm_rounds(blsq_trf_plan* p, const double* dDelta, const double* dalpha_i
   p->lm.fused_gram = 0;
   if (p->use_chol && p->lm_enable && p->ld <= 80) {
     // N <= 80: the Gauss-Newton step, the bracket and ALL rounds of every normal-equations-path problem
-    // in ONE launch (one wave per problem iterates to the end; chol_kernels.hip).  Householder-path
+    // in ONE launch (one wave per problem iterates to the end; chol_reg.hip).  Householder-path
     // problems of the same batch go through lm_start and the round loop below.
     // BLSQ_LM_FUSED = 0: lm_start + the round-by-round loop for everybody.
     if (ctx->opt.on(OPT_LM_FUSED)) {

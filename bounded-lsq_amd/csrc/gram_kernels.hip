@@ -1073,12 +1073,33 @@ __global__ __launch_bounds__(GRED_G * GRED_W) void gram_reduce_wide_kernel(
   }
 }
 
-static int gram_chunk_rows(int m) { return m > 131072 ? 1024 : 2048; }
+// Row chunks whose size is a function of m ALONE (never of the batch size): the summation order of
+// a problem's Gram (and so every bit of its result) does not depend on how many problems share the
+// launch.  2048 rows; 1024 for very tall problems (one 250 000 x 128 row block of BASELINE config 5:
+// 245 workgroups fill the 256 CUs, 123 leave half of them idle).
+static int gram_chunk_rows(long long m) { return m > 131072 ? 1024 : 2048; }
 int gram_chunks(int B, int m) {
   (void)B;
   const int r = gram_chunk_rows(m);
   const int c = (m + r - 1) / r;
   return c < 1 ? 1 : c;
+}
+
+double gram_k2_max(long long m_total, double tighter) {
+  auto acc = [](long long m) {                          // rows per chunk and chunks: the Gram's accumulation length
+    const double md = (double)m, chunk = gram_chunk_rows(m);
+    const double rows = md < chunk ? md : chunk;
+    return sqrt(rows) + sqrt(ceil(md / chunk));
+  };
+  const double f = acc(4096) / acc(m_total > 1 ? m_total : 1);
+  double k = GRAM_K2_MAX * (f < 1.0 ? f : 1.0);
+  if (tighter > 0.0 && tighter < k) k = tighter;                   // (option gram_k2_max: may only tighten the gate)
+  return k;
+}
+
+bool gram_supported(int m, int n) {
+  const int NT = (n + 1 + 15) / 16;
+  return NT <= 17 && m >= n && n >= 1;
 }
 
 hipError_t launch_gram(const GramArgs& a_in, int chunks, int B, hipStream_t s, double* Gfinal, bool* fused) {

@@ -1,6 +1,6 @@
 // Device-side bodies of the safeguarded Newton iteration of the SVD-free trust-region path
 // (solve_lsq_trust_region, bounded_lsq/trust_region.py:111-150), shared by the lock-step round kernels of
-// lm_kernels.hip and the fused per-problem kernel of chol_kernels.hip.  Templates on NT, the thread count of
+// lm_kernels.hip and by csne_kernels.hip.  Templates on NT, the thread count of
 // the calling workgroup; one workgroup per problem; `sh` = (3 + 32) * ld doubles of LDS, `red` = 32 doubles.
 #pragma once
 #include "blsq_device.h"

@@ -61,7 +61,7 @@ __global__ __launch_bounds__(TRI_NT) void lm_gate_kernel(LmState lm, int enable)
   // n-band where the SVD is preferred: their Newton rounds are one launch)
   const bool on_gram = lm.path && lm.path[b] == 0;
   int ok = (((enable >> (on_gram ? 1 : 0)) & 1) != 0) && (lm.m >= n);
-  // Gram-path problems (chol_kernels.hip): R_aug = R'_aug diag(sqrt h_jj) with sigma_min(R'_aug) >=
+  // Gram-path problems (chol_reg.hip, chol_rl.hip): R_aug = R'_aug diag(sqrt h_jj) with sigma_min(R'_aug) >=
   // sigma_min(R') >= GRAM_SMIN_PROVEN (the conditioning certificate), so  s_min >= that x min_j sqrt(h_jj)  and  s_max <= sqrt(sum_j h_jj)
   // (the exact Frobenius norm).  When that already clears the threshold below, the iteration is
   // not needed; otherwise (extreme column scaling near the bounds) the estimate runs as always.

@@ -41,7 +41,7 @@ __device__ __forceinline__ unsigned tri_lds_addr(const double* p) {
 static constexpr int TRI_NT = 256;
 static constexpr int TRI_NW = TRI_NT / WAVE;
 // Every routine is a template on NT, the thread count of the calling workgroup (default TRI_NT): the fused
-// Newton-round kernel of chol_kernels.hip runs them with its 512 threads.
+// Newton-round kernel of chol_reg.hip runs them with its 512 threads.
 
 // u = R s   (one wave per row, lanes stride the columns)
 template <int NT = TRI_NT>

@@ -1,4 +1,5 @@
-"""Normal-equations fast path of the factorisation (gram_kernels.hip, chol_kernels.hip) and its conditioning gate.
+"""Normal-equations fast path of the factorisation (gram_kernels.hip, chol_reg.hip, chol_rl.hip, cert_kernels.hip)
+and its conditioning gate.
 
 The step must match the CPU oracle to 1e-10 / bit-exact masks WHICHEVER path factors a problem;
 the diagnostic counter (blsq_debug_gram_stats) shows which one ran.
@@ -45,7 +46,7 @@ K2_MAX = 2.5e5          # GRAM_K2_MAX of csrc/blsq_kernels.h
 
 
 def k2_max_of(m):
-    """gram_k2_max (csrc/chol_kernels.hip): the gate for a Gram accumulated over m rows"""
+    """gram_k2_max (csrc/gram_kernels.hip): the gate for a Gram accumulated over m rows"""
     def acc(mm):
         chunk = 1024.0 if mm > 131072 else 2048.0
         return np.sqrt(min(mm, chunk)) + np.sqrt(np.ceil(mm / chunk))

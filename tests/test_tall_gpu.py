@@ -89,7 +89,7 @@ def test_config5_single_rank_collective_route(tall, gram, monkeypatch, blsq_opt)
 
 
 def _k2_max_of(m):
-    """gram_k2_max (csrc/chol_kernels.hip)"""
+    """gram_k2_max (csrc/gram_kernels.hip)"""
     def acc(mm):
         chunk = 1024.0 if mm > 131072 else 2048.0
         return np.sqrt(min(mm, chunk)) + np.sqrt(np.ceil(mm / chunk))
