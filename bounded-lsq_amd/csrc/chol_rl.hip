@@ -1,7 +1,7 @@
 // Factorisation side of the normal-equations path for N > 80 (gram_kernels.hip computes the Grams; chol_reg.hip
 // factors N <= 80, cert_kernels.hip holds the certificate):
 //
-//   gram_chol_rl2_kernel<SL, KL, CERT>   equilibrated blocked Cholesky of D G D + E^2 (+ alpha I) or of a gathered
+//   gram_chol_rl2_kernel<CERT>           equilibrated blocked Cholesky of D G D + E^2 (+ alpha I) or of a gathered
 //                                        principal sub-matrix, straight from the kept Gram (chol16.h: the 16 x 16 chain)
 //   gram_chol_kernel                     the left-looking reference of the same factor (option chol_rl = 0)
 #include "gram_common.h"
@@ -225,25 +225,30 @@ __global__ __launch_bounds__(GR_NT, 4) void gram_chol_kernel(GramCholArgs a) {
 }
 
 // ---- N > 80, right-looking, flag-driven: no workgroup barrier inside the factorisation ----------
-// The whole (scaled) matrix lives in accumulators: the NT (NT + 1) / 2 <= 153 upper tiles are dealt CYCLICALLY over the
-// seven worker waves (row-major tile q -> wave 1 + q % 7, slot q / 7) so that the shrinking trailing matrix stays
-// balanced, and never leave the registers until their row block is final — no global-memory round trip inside the
-// factorisation (gram_chol_kernel, the left-looking reference, re-reads finished rows from L2).  The arithmetic is
-// that of gram_chol_kernel (same operands, same order: the same bits), scheduled along the critical path
+// One workgroup of sixteen waves per problem: wave 0 runs the 16x16 chains, fifteen worker waves hold the tiles.  The
+// whole (scaled) matrix lives in accumulators: the NT (NT + 1) / 2 <= 153 upper tiles are dealt CYCLICALLY over the
+// fifteen workers (row-major tile q -> wave 1 + q % 15, slot q / 15: at most 11 slots) so that the shrinking trailing
+// matrix stays balanced, and never leave the worker until their row block is final — no global-memory round trip
+// inside the factorisation (gram_chol_kernel, the left-looking reference, re-reads finished rows from L2).  The
+// arithmetic is that of gram_chol_kernel (same operands, same order: the same bits), scheduled along the critical path
 // chain(kb) -> R'_{kb,kb+1} -> S_{kb+1,kb+1} -> chain(kb + 1):
-//   * wave 0 only runs the 16x16 chains: it waits for the flag "diagonal tile kb is in Dt", factors, raises "R'_kk
-//     and its inverse are in LDS" — it never meets a barrier, nor the stores of the workers;
+//   * wave 0 only runs the 16x16 chains (and, with CERT, the certificate's forward solve of the block just factored,
+//     while the workers solve its row): it waits for the flag "diagonal tile kb is in Dt", factors, raises "R'_kk and
+//     its inverse are in LDS" — it never meets a barrier inside the loop, nor the stores of the workers;
 //   * the owner of tile (kb, kb+1) solves it first and raises a flag; the owner of (kb+1, kb+1) waits for exactly
 //     that tile, updates the diagonal tile and hands it to wave 0; only then come the other tiles of the row;
-//   * the trailing update of a worker starts when a COUNTER says that all seven workers have published their
+//   * wave 0 runs at s_setprio 1, and so do those two steps of their owners: each SIMD carries four waves, and the
+//     chain's path must not queue behind the bulk trailing updates of the SIMD's other waves;
+//   * the trailing update of a worker starts when a COUNTER says that all fifteen workers have published their
 //     tiles of the row block — LDS flags and lgkmcnt waits only, so nobody waits for the acknowledgement of the
 //     global stores of the factor (a __syncthreads does: vmcnt counts stores on gfx9);
 //   * Dt, Ri and the row buffer are double-buffered by the parity of kb.  Buffer kb & 1 is written again at row block
 //     kb + 2, whose chain needs S_{kb+2,kb+2}, i.e. its owner's trailing update with row kb, which waited for the
 //     counter of row kb — every worker had then read Ri / Dt of kb and finished its trailing update of kb - 1.
 //   * the source tiles are requested ALL AT ONCE at kernel entry (the old preamble paid one memory round trip per
-//     tile slot: 37 us) and the column summary is a wave reduction (14 -> 3 us).
-// SL tile slots per worker wave, the first KL in LDS (top rows: dead after three row blocks).
+//     tile slot: 37 us); wave 0 computes the column scales meanwhile, and the column summary is a wave reduction.
+// Registers: 1024 threads leave 128 VGPRs per wave.  A worker keeps RL_SLR slots (80 or 72 VGPRs) in registers and
+// the last one or two — the bottom-right tiles, solved last — in LDS (tailL).
 __device__ __forceinline__ void spin_ge(const int* f, int v) {
   while (__hip_atomic_load(f, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP) < v) __builtin_amdgcn_s_sleep(1);
   asm volatile("" ::: "memory");
@@ -253,8 +258,15 @@ __device__ __forceinline__ void raise_flag(int* f, int v, int lane) {      // (a
   if (lane == 0) __hip_atomic_store(f, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
 }
 enum { FL_DIAG = 0, FL_RINV = 1, FL_ROW1 = 2, FL_PUB = 3, FL_BAD = 4, FL_YB = 5, FL_YPUB = 6 };
+static constexpr int RL_NT = 1024;                      // this kernel's workgroup: wave 0 (chains) + 15 workers
+static constexpr int RL_NW = RL_NT / WAVE;
+static constexpr int RL_NWK = RL_NW - 1;                // worker waves
+static constexpr int RL_SL = (17 * 18 / 2 + RL_NWK - 1) / RL_NWK;   // tile slots per worker: 11 for NT <= 17
+// slots in registers: 128 VGPRs hold no eleventh beside the rest of the worker's code, nor a tenth with CERT (both
+// would spill to scratch)
+template <bool CERT> constexpr int RL_SLR = CERT ? RL_SL - 2 : RL_SL - 1;
 
-template <int SL, int KL, bool CERT>
+template <bool CERT>
 __device__ __forceinline__ void chol_rl2_body(const GramCholArgs& a, const int b, double* sh, int* fl, double& pminsh) {
   const int tid = threadIdx.x, lane = tid & 63;
   const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -290,13 +302,14 @@ __device__ __forceinline__ void chol_rl2_body(const GramCholArgs& a, const int b
   double* Dt = td + NPAD;          // [2][256]
   double* Ri = Dt + 512;           // [2][256]
   double* Rrow = Ri + 512;         // [2][NTP][256] finished tiles of a row block (operands of the trailing updates)
-  double* accL = Rrow + 2 * (size_t)NTP * 256;          // [KL][7][256] the LDS-resident tile slots
-  int* gl = reinterpret_cast<int*>(accL + (size_t)KL * (GR_NW - 1) * 256);   // [NPAD] gathered source indices
+  int* gl = reinterpret_cast<int*>(Rrow + 2 * (size_t)NTP * 256);   // [NPAD] gathered source indices
   // The factor kernel's share of the certificate's stage 0 (GramCholArgs::cert_ym): the solve M(R')^T y = e and
   // the column sums of |R'| advance row block by row block as R' is produced — stage 0 then needs ONE pass over
   // the factor (the backward solve, with the row sums on the way) instead of four.  Fixed order: reproducible.
   double* yv = reinterpret_cast<double*>(gl + NPAD);     // [NPAD] y (final for the finished row blocks)
   double* csum = yv + NPAD;                              // [NPAD] sum_i |R'_ij| over the finished row blocks
+  double* tailL = csum + NPAD;                           // [SL - SLR][15][256] the LDS-resident tile slots
+  constexpr int SLR = RL_SLR<CERT>;
   constexpr bool cert = CERT;                            // (a launch with cert_ym set, never the shifted one)
   const double* csv = a.colscale ? a.colscale + (long)b * a.stride_vec : nullptr;
   const double* edv = a.diag_vec ? a.diag_vec + (long)b * a.stride_vec : nullptr;
@@ -304,64 +317,60 @@ __device__ __forceinline__ void chol_rl2_body(const GramCholArgs& a, const int b
   if (tid < 8) fl[tid] = 0;
   if (tid == 0) pminsh = 1.0;
   if (gidx) {                                           // (uniform) the index map of a gathered sub-matrix -> LDS
-    for (int j = tid; j < NPAD; j += GR_NT) gl[j] = j < n ? gidx[j] : a.n;
+    for (int j = tid; j < NPAD; j += RL_NT) gl[j] = j < n ? gidx[j] : a.n;
   }
   __syncthreads();
   auto src = [&](int i) -> int { return gidx ? gl[i] : i; };     // (i < N)
 
-  constexpr int NWK = GR_NW - 1;                        // worker waves
+  constexpr int NWK = RL_NWK, SL = RL_SL;
   const int ww = w - 1;
-  // tile q (row-major over the upper tiles) -> worker q % 7, slot q / 7; packed (i | j << 8) per slot
-  int tij[SL];
-  v4d acc[SL];                                          // (slots < KL leave for LDS after the scaling)
-  if (w > 0) {
-    int i = 0, off = ww;                                // slot 0: q = ww
+  // Wave 0 and the workers part here and meet again at the end: each side passes the barriers S and X on its own
+  // path (wave-uniform branches), so that the tile slots, live only on the workers' side, do not crowd wave 0's code.
+  // Bad column (uniform after X): the problem goes to the QR tree.
+  auto to_tree = [&]() -> bool {
+    if (!__hip_atomic_load(&fl[FL_BAD], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP)) return false;
+    if (tid == 0 && a.fb_mask) {
+      a.fb_mask[b] = a.n + 1; { const int fi_ = atomicAdd(a.fail_count, 1); if (a.fail_list) a.fail_list[fi_] = b; }   // (the tree factors ALL n + 1 columns)
+      if (a.pmin_out && !a.cert_shift) a.pmin_out[b] = 0.0;
+      if (a.path_out) a.path_out[b] = a.n + 1;
+      if (a.k2_out && !a.cert_shift) a.k2_out[b] = 0.0;
+    }
+    return true;
+  };
+  // zeros outside the factor: strictly lower tiles, and everything beyond 16 NT (sub-matrix use)
+  auto zero_rest = [&]() {
+    for (int r = w; r < (a.skip_zero ? 0 : NPAD); r += RL_NW) {
+      const int cend = (r < 16 * NT) ? (r & ~15) : NPAD;
+      for (int c = lane; c < cend; c += WAVE) Gb[(unsigned)(r * NPAD + c)] = 0.0;
+      if (r < 16 * NT)
+        for (int c = 16 * NT + lane; c < NPAD; c += WAVE) Gb[(unsigned)(r * NPAD + c)] = 0.0;
+    }
+  };
+  if (w == 0) {
+    // column scales from the diagonal of H, by wave 0 alone: CW columns per lane in flight at once — their global
+    // stores come after all of their loads
+    int bad = 0;
+    constexpr int CW = (17 * 16 + WAVE - 1) / WAVE;
+    for (int j0 = 0; j0 < NPAD; j0 += CW * WAVE) {
+      double d[CW];
 #pragma unroll
-    for (int t = 0; t < SL; ++t) {
-      while (i < NT && off >= NT - i) { off -= NT - i; ++i; }
-      const bool valid = i < NT;
-      tij[t] = valid ? (i | ((i + off) << 8)) : -1;
-      acc[t] = v4d{0.0, 0.0, 0.0, 0.0};
-      if (valid) {
-        const int j = i + off;
-        const int col = 16 * j + lc;
-        const int scol = col < N ? src(col) : 0;
-#pragma unroll
-        for (int g = 0; g < 4; ++g) {
-          const int row = 16 * i + lr + 4 * g;
-          int sr_ = row < N ? src(row) : 0, sc_ = scol;
-          if (sr_ > sc_) { const int t_ = sr_; sr_ = sc_; sc_ = t_; }       // symmetric: stay in the upper tiles
-          acc[t][g] = Gs[(unsigned)(sr_ * NPAD + sc_)];                     // (raw; selected and scaled below)
+      for (int k = 0; k < CW; ++k) {
+        const int j = j0 + WAVE * k + lane;
+        if (j < NPAD) {
+          int sj;
+          d[k] = col_scale(Gs, NPAD, j, n, src, csv, edv, sa, tau, dl, sq, sc, td, bad, sj);
+          if (cert) { yv[j] = 1.0; csum[j] = 0.0; }
         }
       }
-      off += NWK;
+#pragma unroll
+      for (int k = 0; k < CW; ++k) {
+        const int j = j0 + WAVE * k + lane;
+        if (a.dsc && j < NPAD) a.dsc[(long)b * NPAD + j] = d[k];
+      }
     }
-  }
-  // column scales from the diagonal of H
-  int bad = 0;
-  for (int j = tid; j < NPAD; j += GR_NT) {
-    int sj;
-    const double d = col_scale(Gs, NPAD, j, n, src, csv, edv, sa, tau, dl, sq, sc, td, bad, sj);
-    if (a.dsc) a.dsc[(long)b * NPAD + j] = d;
-    if (cert) { yv[j] = 1.0; csum[j] = 0.0; }
-  }
-  if (__any(bad) && lane == 0) __hip_atomic_store(&fl[FL_BAD], 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-  CST(stp && (w == 0 || w == 2), w == 0 ? 2 : 3, 17, 1);
-  __syncthreads();                                      // S: the scales are in LDS
-  auto slot = [&](int t) -> double* { return accL + ((size_t)t * NWK + ww) * 256 + lane; };   // [g * 64]
-#define RL2_GET(t, dst)                                                           \
-    do {                                                                          \
-      if ((t) < KL) { const double* p_ = slot(t);                                 \
-        dst = v4d{p_[0], p_[64], p_[128], p_[192]}; }                             \
-      else dst = acc[t];                                                          \
-    } while (0)
-#define RL2_PUT(t, srcv)                                                          \
-    do {                                                                          \
-      if ((t) < KL) { double* p_ = slot(t);                                       \
-        p_[0] = (srcv)[0]; p_[64] = (srcv)[1]; p_[128] = (srcv)[2]; p_[192] = (srcv)[3]; } \
-      else acc[t] = srcv;                                                         \
-    } while (0)
-  if (w == 0) {
+    if (__any(bad) && lane == 0) __hip_atomic_store(&fl[FL_BAD], 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+    CST(stp, 2, 17, 1);
+    __syncthreads();                                    // S: the scales are in LDS
     if (a.colinfo) {                                    // column-norm summary for the rank gate
       double mn, mx, sm;
       colinfo_wave(sq, n, lane, mn, mx, sm);
@@ -371,51 +380,12 @@ __device__ __forceinline__ void chol_rl2_body(const GramCholArgs& a, const int b
         if (a.lam_out) a.lam_out[b] = (double)n;
       }
     }
-  } else {
-    // the scaled source tiles (the source may alias the output: everything is read before anything is written)
-#pragma unroll
-    for (int t = 0; t < SL; ++t) {
-      if (tij[t] >= 0) {
-        const int i = tij[t] & 255, j = tij[t] >> 8;
-        const double scj = sc[16 * j + lc];
-        v4d a0;
-#pragma unroll
-        for (int g = 0; g < 4; ++g) {
-          const int row = 16 * i + lr + 4 * g, col = 16 * j + lc;
-          double v = 0.0;
-          if (row < N && col < N) v = acc[t][g] * sc[row] * scj;
-          if (j == i && lr + 4 * g == lc) v += td[row];
-          a0[g] = v;
-        }
-        if (i == 0 && j == 0) {
-#pragma unroll
-          for (int g = 0; g < 4; ++g) Dt[(lr + 4 * g) * 16 + lc] = a0[g];
-        }
-        RL2_PUT(t, a0);
-      }
-    }
-  }
-  CST(stp && w == 2, 3, 17, 2);
-  __syncthreads();                                      // X: all source reads done before the first store
-  CST(stp && (w == 0 || w == 2), w == 0 ? 2 : 3, 17, 3);
-  if (__hip_atomic_load(&fl[FL_BAD], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP)) {   // uniform: to the QR tree
-    if (tid == 0 && a.fb_mask) {
-      a.fb_mask[b] = a.n + 1; { const int fi_ = atomicAdd(a.fail_count, 1); if (a.fail_list) a.fail_list[fi_] = b; }   // (the tree factors ALL n + 1 columns)
-      if (a.pmin_out && !a.cert_shift) a.pmin_out[b] = 0.0;
-      if (a.path_out) a.path_out[b] = a.n + 1;
-      if (a.k2_out && !a.cert_shift) a.k2_out[b] = 0.0;
-    }
-    return;
-  }
-  // zeros outside the factor: strictly lower tiles, and everything beyond 16 NT (sub-matrix use)
-  for (int r = w; r < (a.skip_zero ? 0 : NPAD); r += GR_NW) {
-    const int cend = (r < 16 * NT) ? (r & ~15) : NPAD;
-    for (int c = lane; c < cend; c += WAVE) Gb[(unsigned)(r * NPAD + c)] = 0.0;
-    if (r < 16 * NT)
-      for (int c = 16 * NT + lane; c < NPAD; c += WAVE) Gb[(unsigned)(r * NPAD + c)] = 0.0;
-  }
-  CST(stp && (w == 0 || w == 2), w == 0 ? 2 : 3, 17, 4);
-  if (w == 0) {
+    __syncthreads();                                    // X: all source reads done before the first store
+    CST(stp, 2, 17, 3);
+    if (to_tree()) return;
+    zero_rest();
+    CST(stp, 2, 17, 4);
+    __builtin_amdgcn_s_setprio(1);                      // the chains: the critical path of the whole factor
     double pmin = 1.0;
     for (int kb = 0; kb < NT; ++kb) {
       double* DtC = Dt + (kb & 1) * 256;
@@ -430,17 +400,122 @@ __device__ __forceinline__ void chol_rl2_body(const GramCholArgs& a, const int b
 #pragma unroll
         for (int q = 0; q < 4; ++q) ro[q * 64 + lane] = RiC[q * 64 + lane];
       }
+      if (cert) {
+        // y of the block by forward substitution with |R'_kk| — once every worker has added its share of the row
+        // block before (FL_YPUB) — and the tile's column sums.  Off the chain: the workers are solving row block kb
+        // meanwhile, and wave 0 has the registers that a worker (ten tile slots) lacks.
+        spin_ge(&fl[FL_YPUB], NWK * kb);
+        const int i_ = lane & 15, gi = 16 * kb + i_;
+        double Dc[16], cs_ = 0.0;
+#pragma unroll
+        for (int s_ = 0; s_ < 16; ++s_) {
+          const double v_ = fabs(DtC[s_ * 16 + i_]);
+          Dc[s_] = s_ < i_ ? v_ : 0.0;
+          if (s_ <= i_) cs_ += v_;
+        }
+        const double dg_ = DtC[i_ * 16 + i_];
+        const bool live_ = gi < n && dg_ > 0.0;
+        const double iv_ = live_ ? 1.0 / dg_ : 0.0;
+        double r_ = live_ ? yv[gi] : 0.0;
+#pragma unroll
+        for (int s_ = 0; s_ < 16; ++s_) {
+          const double ys_ = read_lane(r_ * iv_, s_);
+          if (i_ > s_) r_ = fma(Dc[s_], ys_, r_);
+        }
+        if (lane < 16 && gi < n) { yv[gi] = r_ * iv_; csum[gi] += cs_; }
+        raise_flag(&fl[FL_YB], kb + 1, lane);
+      }
     }
     if (lane == 0) pminsh = pmin;
   } else {
+    // tile q (row-major over the upper tiles) -> worker q % 15, slot q / 15; packed (i | j << 8) per slot.  The
+    // source tiles are requested all at once (raw; selected and scaled once the scales are in LDS).
+    int tij[SL];
+    v4d acc[SL];
+    // slots t >= SLR live in LDS once scaled (t: a compile-time index in every unrolled loop below)
+    auto get = [&](int t) -> v4d {
+      if (t < SLR) return acc[t];
+      const double* p_ = tailL + ((size_t)(t - SLR) * NWK + ww) * 256 + lane;
+      return v4d{p_[0], p_[64], p_[128], p_[192]};
+    };
+    auto put = [&](int t, const v4d& v) {
+      if (t < SLR) { acc[t] = v; return; }
+      double* p_ = tailL + ((size_t)(t - SLR) * NWK + ww) * 256 + lane;
+      p_[0] = v[0]; p_[64] = v[1]; p_[128] = v[2]; p_[192] = v[3];
+    };
+    {
+      int i = 0, off = ww;                              // slot 0: q = ww
+#pragma unroll
+      for (int t = 0; t < SL; ++t) {
+        while (i < NT && off >= NT - i) { off -= NT - i; ++i; }
+        tij[t] = i < NT ? (i | ((i + off) << 8)) : -1;
+        off += NWK;
+      }
+    }
+    auto load_raw = [&](int t) -> v4d {                 // (raw; selected and scaled below)
+      v4d v = {0.0, 0.0, 0.0, 0.0};
+      if (tij[t] >= 0) {
+        const int i = tij[t] & 255, j = tij[t] >> 8;
+        const int col = 16 * j + lc;
+        const int scolu = src(col), scol = col < N ? scolu : 0;     // (src reads gl[] below NPAD: unconditionally)
+#pragma unroll
+        for (int g = 0; g < 4; ++g) {
+          const int row = 16 * i + lr + 4 * g;
+          const int srow = src(row);
+          int sr_ = row < N ? srow : 0, sc_ = scol;
+          if (sr_ > sc_) { const int t_ = sr_; sr_ = sc_; sc_ = t_; }       // symmetric: stay in the upper tiles
+          v[g] = Gs[(unsigned)(sr_ * NPAD + sc_)];
+        }
+      }
+      return v;
+    };
+    // all at once: the register slots, then the LDS slots (whose stores wait for every load)
+#pragma unroll
+    for (int t = 0; t < SLR; ++t) acc[t] = load_raw(t);
+#pragma unroll
+    for (int t = SLR; t < SL; ++t) put(t, load_raw(t));
+    CST(stp && w == 2, 3, 17, 1);
+    __syncthreads();                                    // S: the scales are in LDS
+    // the scaled source tiles (the source may alias the output: everything is read before anything is written)
+#pragma unroll
+    for (int t = 0; t < SL; ++t) {
+      if (tij[t] >= 0) {
+        const int i = tij[t] & 255, j = tij[t] >> 8;
+        if (t >= SLR) acc[t] = get(t);
+        const double scj = sc[16 * j + lc];
+#pragma unroll
+        for (int g = 0; g < 4; ++g) {
+          // in place and by selects: both arms are computed on every lane (the empty asm keeps the compiler from
+          // sinking them into exec-masked branches, which spill the tile — no room for a second one)
+          const int row = 16 * i + lr + 4 * g, col = 16 * j + lc;
+          double p = acc[t][g] * sc[row] * scj;
+          asm volatile("" : "+v"(p));
+          double v = (row < N && col < N) ? p : 0.0;
+          double vd = v + td[row];
+          asm volatile("" : "+v"(vd));
+          acc[t][g] = (j == i && lr + 4 * g == lc) ? vd : v;
+        }
+        if (i == 0 && j == 0) {
+#pragma unroll
+          for (int g = 0; g < 4; ++g) Dt[(lr + 4 * g) * 16 + lc] = acc[t][g];
+        }
+        if (t >= SLR) put(t, acc[t]);
+      }
+    }
+    CST(stp && w == 2, 3, 17, 2);
+    __syncthreads();                                    // X
+    CST(stp && w == 2, 3, 17, 3);
+    if (to_tree()) return;
+    zero_rest();
+    CST(stp && w == 2, 3, 17, 4);
     for (int kb = 0; kb < NT; ++kb) {
       const double* DtC = Dt + (kb & 1) * 256;
       const double* RiC = Ri + (kb & 1) * 256;
       double* RrowC = Rrow + (size_t)(kb & 1) * NTP * 256;
       // this wave's slots of row block kb: tiles q0 .. q0 + NT - kb - 1
       const int q0 = kb * NT - kb * (kb - 1) / 2;
-      const int t_lo = (q0 - ww + NWK - 1 + NWK) / NWK - 1;          // ceil((q0 - ww) / 7), q0 - ww >= -6
-      const int t_hi = (q0 + NT - kb - 1 - ww + NWK) / NWK - 1;      // floor(.. / 7)
+      const int t_lo = (q0 - ww + NWK - 1 + NWK) / NWK - 1;          // ceil((q0 - ww) / 15), q0 - ww >= -14
+      const int t_hi = (q0 + NT - kb - 1 - ww + NWK) / NWK - 1;      // floor(.. / 15)
       const int t_one = ((q0 + 1 - ww) % NWK == 0 && kb + 1 < NT) ? (q0 + 1 - ww) / NWK : -1;   // slot of (kb, kb+1)
       const int q1 = q0 + NT - kb;                                     // tile (kb+1, kb+1)
       const int t_dia = ((q1 - ww) % NWK == 0 && kb + 1 < NT) ? (q1 - ww) / NWK : -1;
@@ -475,12 +550,14 @@ __device__ __forceinline__ void chol_rl2_body(const GramCholArgs& a, const int b
           if (j != kb) RrowC[j * 256 + (lr + 4 * g) * 16 + lc] = val * dj;
         }
       };
-      // 1. the critical tile (kb, kb + 1) first
+      // 1. the critical tile (kb, kb + 1) first — steps 1 and 2 at raised priority: they are on the chain's path, the
+      // other waves of the SIMD are in their bulk updates
+      if (t_one >= 0 || t_dia >= 0) __builtin_amdgcn_s_setprio(1);
       if (t_one >= 0) {
         CST(stp, 1, kb, 0);
 #pragma unroll
         for (int t = 0; t < SL; ++t) {
-          if (t == t_one) { v4d S; RL2_GET(t, S); solve_tile(t, S); }
+          if (t == t_one) solve_tile(t, get(t));
         }
         raise_flag(&fl[FL_ROW1], kb + 1, lane);
         CST(stp, 1, kb, 1);
@@ -494,11 +571,10 @@ __device__ __forceinline__ void chol_rl2_body(const GramCholArgs& a, const int b
 #pragma unroll
         for (int t = 0; t < SL; ++t) {
           if (t == t_dia) {
-            v4d S;
-            RL2_GET(t, S);
+            v4d S = get(t);
 #pragma unroll
             for (int s_ = 0; s_ < 4; ++s_) S = gmfma(-Ra[64 * s_], Ra[64 * s_], S);
-            RL2_PUT(t, S);
+            put(t, S);
 #pragma unroll
             for (int g = 0; g < 4; ++g) DtN[(lr + 4 * g) * 16 + lc] = S[g];
           }
@@ -506,35 +582,12 @@ __device__ __forceinline__ void chol_rl2_body(const GramCholArgs& a, const int b
         raise_flag(&fl[FL_DIAG], kb + 1, lane);
         CST(stp, 1, kb, 3);
       }
-      if (cert && (q0 - ww) % NWK == 0) {
-        // this wave owns the diagonal tile: y of the block by forward substitution with |R'_kk| — once every worker
-        // has added its share of the row block before (FL_YPUB) — and the tile's column sums
-        spin_ge(&fl[FL_YPUB], NWK * kb);
-        const int i_ = lane & 15, gi = 16 * kb + i_;
-        double Dc[16], cs_ = 0.0;
-#pragma unroll
-        for (int s_ = 0; s_ < 16; ++s_) {
-          const double v_ = fabs(DtC[s_ * 16 + i_]);
-          Dc[s_] = s_ < i_ ? v_ : 0.0;
-          if (s_ <= i_) cs_ += v_;
-        }
-        const double dg_ = DtC[i_ * 16 + i_];
-        const bool live_ = gi < n && dg_ > 0.0;
-        const double iv_ = live_ ? 1.0 / dg_ : 0.0;
-        double r_ = live_ ? yv[gi] : 0.0;
-#pragma unroll
-        for (int s_ = 0; s_ < 16; ++s_) {
-          const double ys_ = read_lane(r_ * iv_, s_);
-          if (i_ > s_) r_ = fma(Dc[s_], ys_, r_);
-        }
-        if (lane < 16 && gi < n) { yv[gi] = r_ * iv_; csum[gi] += cs_; }
-        raise_flag(&fl[FL_YB], kb + 1, lane);
-      }
+      if (t_one >= 0 || t_dia >= 0) __builtin_amdgcn_s_setprio(0);
       CST(stp && w == 2, 3, kb, 1);
       // 3. the other tiles of the row block
 #pragma unroll
       for (int t = 0; t < SL; ++t) {
-        if (t >= t_lo && t <= t_hi && t != t_one) { v4d S; RL2_GET(t, S); solve_tile(t, S); }
+        if (t >= t_lo && t <= t_hi && t != t_one) solve_tile(t, get(t));
       }
       asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
       if (lane == 0) __hip_atomic_fetch_add(&fl[FL_PUB], 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
@@ -570,18 +623,15 @@ __device__ __forceinline__ void chol_rl2_body(const GramCholArgs& a, const int b
           const int i = tij[t] & 255, j = tij[t] >> 8;
           const double* Ra = RrowC + i * 256 + lr * 16 + lc;
           const double* Rb = RrowC + j * 256 + lr * 16 + lc;
-          v4d S;
-          RL2_GET(t, S);
+          v4d S = get(t);
 #pragma unroll
           for (int s_ = 0; s_ < 4; ++s_) S = gmfma(-Ra[64 * s_], Rb[64 * s_], S);
-          RL2_PUT(t, S);
+          put(t, S);
         }
       }
       CST(stp && w == 2, 3, kb, 4);
     }
   }
-#undef RL2_GET
-#undef RL2_PUT
   CST(stp && (w == 0 || w == 2), w == 0 ? 2 : 3, 18, 0);
   __syncthreads();
   CST(stp && (w == 0 || w == 2), w == 0 ? 2 : 3, 18, 1);
@@ -612,15 +662,15 @@ __device__ __forceinline__ void chol_rl2_body(const GramCholArgs& a, const int b
   }
 }
 
-template <int SL, int KL, bool CERT>
-__global__ __launch_bounds__(GR_NT, 2) void gram_chol_rl2_kernel(GramCholArgs a) {
+template <bool CERT>
+__global__ __launch_bounds__(RL_NT, 1) void gram_chol_rl2_kernel(GramCholArgs a) {
   extern __shared__ double sh[];
   __shared__ double pminsh;
   __shared__ int fl[8];                                 // FL_*: hand-over flags and the publication counter
   const int pidx = (int)blockIdx.x;
   if (a.count_dev && pidx >= *a.count_dev) return;
   const int b = a.batch_list ? a.batch_list[pidx] : pidx;
-  chol_rl2_body<SL, KL, CERT>(a, b, sh, fl, pminsh);
+  chol_rl2_body<CERT>(a, b, sh, fl, pminsh);
 }
 
 hipError_t launch_gram_chol(const GramCholArgs& a_in, int B, hipStream_t s) {
@@ -628,24 +678,25 @@ hipError_t launch_gram_chol(const GramCholArgs& a_in, int B, hipStream_t s) {
   a.count = B;
   if (a.NPAD <= 80) return launch_gram_chol_reg(a, s);  // (chol_reg.hip)
   if (options_or_default(a.opt).i(OPT_CHOL_RL) != 0) {   // (per launch: tests compare the kernels)
-    // Right-looking register kernel, flag-driven: 0.12 ms per problem on a CU of its own (one workgroup per CU)
-    // against 0.27 ms for a PAIR of problems on a CU through the left-looking kernel (its Schur-complement phase
-    // waits for L2: 190 of its 275 us, tools/chol_stamps.py).  BLSQ_CHOL_RL = 0 runs the left-looking one: the two
+    // Right-looking register kernel, flag-driven: 0.106 ms per problem on a CU of its own (one workgroup of 16 waves
+    // per CU) against 0.27 ms for a PAIR of problems on a CU through the left-looking kernel (its Schur-complement
+    // phase waits for L2: 190 of its 275 us, tools/chol_stamps.py).  BLSQ_CHOL_RL = 0 runs the left-looking one: the two
     // agree bit for bit (same operands, same order), so it is the reference, never a faster choice.
-    constexpr int R2_KL = 5;
+    const bool cert = a.cert_ym && !a.cert_shift;
     const size_t lds = sizeof(double) * (4 * (size_t)a.NPAD + 1024 + 2 * (size_t)(a.NPAD / 16) * 256 +
-                                         (size_t)R2_KL * (GR_NW - 1) * 256 + 2 * (size_t)a.NPAD) +
+                                         2 * (size_t)a.NPAD +
+                                         (size_t)(RL_SL - (cert ? RL_SLR<true> : RL_SLR<false>)) * RL_NWK * 256) +
                        sizeof(int) * (size_t)a.NPAD;
-    if (a.cert_ym && !a.cert_shift) {
+    if (cert) {
       static std::atomic<size_t> granted[64];
-      hipError_t ge = gram_grant_lds(gram_chol_rl2_kernel<22, R2_KL, true>, lds, granted);
+      hipError_t ge = gram_grant_lds(gram_chol_rl2_kernel<true>, lds, granted);
       if (ge != hipSuccess) return ge;
-      hipLaunchKernelGGL((gram_chol_rl2_kernel<22, R2_KL, true>), dim3(B), dim3(GR_NT), lds, s, a);
+      hipLaunchKernelGGL((gram_chol_rl2_kernel<true>), dim3(B), dim3(RL_NT), lds, s, a);
     } else {
       static std::atomic<size_t> granted[64];
-      hipError_t ge = gram_grant_lds(gram_chol_rl2_kernel<22, R2_KL, false>, lds, granted);
+      hipError_t ge = gram_grant_lds(gram_chol_rl2_kernel<false>, lds, granted);
       if (ge != hipSuccess) return ge;
-      hipLaunchKernelGGL((gram_chol_rl2_kernel<22, R2_KL, false>), dim3(B), dim3(GR_NT), lds, s, a);
+      hipLaunchKernelGGL((gram_chol_rl2_kernel<false>), dim3(B), dim3(RL_NT), lds, s, a);
     }
   } else {
     if (a.cert_ym) {                                    // (only the flag-driven kernel has a share in stage 0)
