@@ -94,6 +94,9 @@ SIGNATURES = {
     "blsq_outer_fetch": (C.c_int, [vp] + [vp] * 8),
     "blsq_fd_points_dev": (C.c_int, [vp, C.c_int, C.c_int, C.c_int] + [vp] * 7),
     "blsq_fd_assemble_dev": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, C.c_int] + [vp] * 7),
+    "blsq_loss_cost_dev": (C.c_int, [vp, C.c_int, C.c_int, C.c_int] + [vp] * 4),
+    "blsq_loss_scale_dev": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, C.c_int] + [vp] * 5),
+    "blsq_outer_set_loss": (C.c_int, [vp, C.c_int, vp]),
 }
 
 _lib = None
@@ -313,6 +316,17 @@ class Context:
         self.check(self.lib.blsq_debug_probe(self.h, {"mfma_f64": 0, "copy": 1}[kind], int(arg), out),
                    "blsq_debug_probe")
         return float(out[0]), float(out[1]), float(out[2])
+
+    # ---- robust loss functions (blsq_loss_*_dev; loss = index in _hostmath.LOSSES) -------------------------------
+    def loss_cost_dev(self, B, m, loss, d_fscale, d_f, d_obj, d_mask=None):
+        """obj[b] = f_scale[b]^2 sum rho0((f[b] / f_scale[b])^2) for the problems with mask[b] != 0 (device pointers)."""
+        self.check(self.lib.blsq_loss_cost_dev(self.h, int(B), int(m), int(loss), d_fscale, d_f, d_obj, d_mask),
+                   "blsq_loss_cost_dev")
+
+    def loss_scale_dev(self, B, m, n, loss, d_fscale, d_f, d_J, d_fs, d_mask=None):
+        """J[b] <- diag(w) J[b] in place and f_s[b] = f[b] rho1 / w for the problems with mask[b] != 0."""
+        self.check(self.lib.blsq_loss_scale_dev(self.h, int(B), int(m), int(n), int(loss), d_fscale, d_f, d_J, d_fs,
+                                                d_mask), "blsq_loss_scale_dev")
 
     # ---- timing ------------------------------------------------------------
     def timing(self, on=True, only=None):

@@ -22,7 +22,8 @@ from scipy.optimize import OptimizeResult
 from ._frontend import (TERMINATION_MESSAGES, _clamp_tolerances, _checked_scaling, EPS)
 from ._hip_step import (TrfStepSolver, DogboxStepSolver, SCALE_GIVEN, SCALE_JAC_INIT,
                         SCALE_JAC_UPDATE, raise_batch_status)
-from ._hostmath import shift_into_interior, active_mask, cl_vector
+from ._hostmath import (shift_into_interior, active_mask, cl_vector, check_loss, loss_rho, loss_cost,
+                        loss_scale)
 
 
 def _bounds_2d(bounds, B, n):
@@ -38,7 +39,8 @@ def _bounds_2d(bounds, B, n):
 
 def least_squares_batch(fun, x0, jac, bounds=(-np.inf, np.inf), method='trf',
                         ftol=EPS ** 0.5, xtol=EPS ** 0.5, gtol=EPS ** 0.5, max_nfev=None,
-                        scaling=1.0, diff_step=None, args=(), kwargs=None, ctx=None, driver='host'):
+                        scaling=1.0, diff_step=None, args=(), kwargs=None, ctx=None, driver='host',
+                        loss='linear', f_scale=1.0):
     """Solve B bound-constrained least-squares problems of identical shape.
 
     fun : callable, ``fun(X) -> (B, m)`` residuals for ``X`` (B, n)
@@ -49,14 +51,24 @@ def least_squares_batch(fun, x0, jac, bounds=(-np.inf, np.inf), method='trf',
     driver : 'host' — the per-problem accept / update logic runs here in Python around batched
              C-ABI calls; 'device' — it runs on the GPU (``OuterDriver``, blsq_outer_*), x / f / J
              stay resident and only fresh Jacobians are uploaded and factored.
+    loss, f_scale : robust loss as ``least_squares`` (scipy's): a name, or a callable ``z -> (3, m)`` (called per
+             problem; driver='host' only); f_scale a positive scalar or broadcastable to (B,).
     Returns a list of B ``OptimizeResult`` (fields as ``least_squares``).
     """
     if method not in ('trf', 'dogbox'):
         raise ValueError("`method` must be 'trf' or 'dogbox'.")
+    check_loss(loss, f_scale)
+    if callable(loss) and driver == 'device':
+        raise ValueError("a callable `loss` runs on the host: use driver='host'.")
     X0 = np.array(x0, dtype=float)
     if X0.ndim != 2:
         raise ValueError("`x0` must have shape (B, n).")
     B, n = X0.shape
+    try:
+        fsc = np.broadcast_to(np.asarray(f_scale, dtype=float), (B,)).copy()
+    except ValueError:
+        raise ValueError("`f_scale` must be a scalar or broadcastable to (B,).")
+    robust = callable(loss) or loss != 'linear'
     lb, ub = _bounds_2d(bounds, B, n)
     if not callable(fun):
         raise ValueError("`fun` must be callable (vectorised over the batch).")
@@ -114,7 +126,7 @@ def least_squares_batch(fun, x0, jac, bounds=(-np.inf, np.inf), method='trf',
     if driver == 'device':
         try:
             return _device_batch(fun, jac, X0, lb, ub, trf, use_jac, scaling, ftol, xtol, gtol,
-                                 max_nfev, ctx)
+                                 max_nfev, ctx, loss if robust else None, fsc)
         finally:
             _release_fd()
 
@@ -140,6 +152,14 @@ def least_squares_batch(fun, x0, jac, bounds=(-np.inf, np.inf), method='trf',
     if J.shape[1] != m:
         raise RuntimeError("Inconsistent dimensions between the returns of "
                            "`fun` and `jac` on the first iteration.")
+    f_s = f                                  # the residuals the steps are computed from
+    if robust:                               # scipy: diag(w) J (in J) and f * rho1 / w (in f_s); f stays true
+        f_s = np.empty_like(f)
+
+        def rescale(idx, J_src):
+            for b in idx:
+                J[b], f_s[b] = loss_scale(J_src[b], f[b], loss_rho(loss, f[b], fsc[b]))
+        rescale(range(B), J)
     nfev = np.ones(B, dtype=int)
     njev = np.ones(B, dtype=int)
     scale = np.ones((B, n)) if use_jac else np.broadcast_to(1 / np.asarray(scaling, float),
@@ -152,8 +172,8 @@ def least_squares_batch(fun, x0, jac, bounds=(-np.inf, np.inf), method='trf',
     try:
         def factor(mode):
             if trf:
-                return solver.factor(J, f, x, lb, ub, scale, mode)
-            return solver.factor(J, f, x, lb, ub, scale, on_bound, mode)
+                return solver.factor(J, f_s, x, lb, ub, scale, mode)
+            return solver.factor(J, f_s, x, lb, ub, scale, on_bound, mode)
 
         F = factor(SCALE_JAC_INIT if use_jac else SCALE_GIVEN)
         scale = F.scale.copy()
@@ -164,7 +184,10 @@ def least_squares_batch(fun, x0, jac, bounds=(-np.inf, np.inf), method='trf',
             Delta = np.array([norm(X0[b] / scale[b], ord=np.inf) for b in range(B)])
         Delta[Delta == 0] = 1.0
         alpha = np.zeros(B)
-        obj = np.einsum('bi,bi->b', f, f)
+        if robust:
+            obj = np.array([loss_cost(loss, f[b], fsc[b]) for b in range(B)])
+        else:
+            obj = np.einsum('bi,bi->b', f, f)
         status = [None] * B          # termination status found in the inner loop
         done = np.zeros(B, dtype=bool)
         result_status = np.zeros(B, dtype=int)
@@ -220,7 +243,7 @@ def least_squares_batch(fun, x0, jac, bounds=(-np.inf, np.inf), method='trf',
             accepted = np.zeros(B, dtype=bool)
             for b in np.nonzero(act)[0]:
                 nfev[b] += 1
-                obj_new = np.dot(f_new[b], f_new[b])
+                obj_new = loss_cost(loss, f_new[b], fsc[b]) if robust else np.dot(f_new[b], f_new[b])
                 actual[b] = obj[b] - obj_new
                 pred = float(S.predicted_reduction[b])
                 if trf:
@@ -269,6 +292,8 @@ def least_squares_batch(fun, x0, jac, bounds=(-np.inf, np.inf), method='trf',
                     J[b] = J_new[b]
                     njev[b] += 1
                     need_factor[b] = True
+                if robust:
+                    rescale(np.nonzero(accepted)[0], J_new)
         results = []
         for b in range(B):
             mask = active_mask(x[b], lb[b], ub[b], rtol=xtol) if trf else on_bound[b].astype(int)
@@ -284,8 +309,10 @@ def least_squares_batch(fun, x0, jac, bounds=(-np.inf, np.inf), method='trf',
         _release_fd()
 
 
-def _device_batch(fun, jac, X0, lb, ub, trf, use_jac, scaling, ftol, xtol, gtol, max_nfev, ctx):
-    """`least_squares_batch` on the device-resident outer driver (same results, same counts)."""
+def _device_batch(fun, jac, X0, lb, ub, trf, use_jac, scaling, ftol, xtol, gtol, max_nfev, ctx,
+                  loss=None, f_scale=None):
+    """`least_squares_batch` on the device-resident outer driver (same results, same counts).  `loss`: a
+    loss name other than 'linear' (None: sum f^2), applied on the device (blsq_outer_set_loss)."""
     from ._outer import OuterDriver
     B, n = X0.shape
     if trf:                                                   # trf.py:201
@@ -319,6 +346,8 @@ def _device_batch(fun, jac, X0, lb, ub, trf, use_jac, scaling, ftol, xtol, gtol,
     scale = np.ones((B, n)) if use_jac else np.broadcast_to(1 / np.asarray(scaling, float), (B, n))
     drv = OuterDriver('trf' if trf else 'dogbox', B, m, n, ctx=ctx)
     try:
+        if loss is not None:
+            drv.set_loss(loss, f_scale)
         drv.start(X0, xs, lb, ub, scale, use_jac, ftol, xtol, gtol, max_nfev)
         R = drv.run_host(fun_cached, jac_checked)
         Jfin = drv._down(drv.d_J, (B, m, n))

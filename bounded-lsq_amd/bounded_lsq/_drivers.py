@@ -13,7 +13,7 @@ from scipy.optimize import OptimizeResult
 
 from ._hip_step import (TrfStepSolver, DogboxStepSolver, SCALE_GIVEN, SCALE_JAC_INIT,
                         SCALE_JAC_UPDATE, lease_solver, return_solver)
-from ._hostmath import shift_into_interior, active_mask, cl_vector
+from ._hostmath import shift_into_interior, active_mask, cl_vector, loss_rho, loss_cost, loss_scale
 
 EPS = np.finfo(float).eps
 
@@ -32,9 +32,19 @@ def _termination(ftol_ok, xtol_ok):
     return None
 
 
-def trf(fun, jac, x0, lb, ub, ftol, xtol, gtol, max_nfev, scaling, ctx=None):
+def _robust(loss, f_scale):
+    """-> (prepare(J, f) -> (J, f) the step is computed from, objective(f)) for `loss` (scipy's loss=, f_scale=:
+    diag(w) J and f * rho1 / w, f_scale^2 sum rho0); 'linear' hands J and f through and keeps sum f^2."""
+    if not callable(loss) and loss == 'linear':
+        return (lambda J, f: (J, f)), (lambda f: np.dot(f, f))
+    return ((lambda J, f: loss_scale(J, f, loss_rho(loss, f, f_scale))),
+            (lambda f: loss_cost(loss, f, f_scale)))
+
+
+def trf(fun, jac, x0, lb, ub, ftol, xtol, gtol, max_nfev, scaling, ctx=None, loss='linear', f_scale=1.0):
     """Trust Region Reflective driver (same signature / result fields as the
-    reference's ``trf``, trf.py:173)."""
+    reference's ``trf``, trf.py:173; `loss` / `f_scale` as scipy's, its trf.py:217-220,348-379)."""
+    prepare, objective = _robust(loss, f_scale)
     x = shift_into_interior(x0, lb, ub, rstep=1e-10)          # trf.py:201
     f = fun(x)
     nfev = 1
@@ -44,18 +54,19 @@ def trf(fun, jac, x0, lb, ub, ftol, xtol, gtol, max_nfev, scaling, ctx=None):
         raise RuntimeError("Inconsistent dimensions between the returns of "
                            "`fun` and `jac` on the first iteration.")
     m, n = J.shape
+    J, f_s = prepare(J, f)                                    # J: the step's (scaled) Jacobian, f: true residuals
     solver = lease_solver(TrfStepSolver, 1, m, n, ctx=ctx)
     try:
         use_jac = _is_jac(scaling)
         scale = np.ones(n) if use_jac else 1 / np.asarray(scaling, dtype=float)
-        F = solver.factor(J[None], f[None], x[None], lb[None], ub[None], scale[None],
+        F = solver.factor(J[None], f_s[None], x[None], lb[None], ub[None], scale[None],
                           SCALE_JAC_INIT if use_jac else SCALE_GIVEN)
         scale = F.scale[0]
         v = cl_vector(x, F.g[0], lb, ub)
         Delta = norm(x0 / (scale * v ** 0.5))                 # trf.py:223-226 (x0, not x)
         if Delta == 0:
             Delta = 1.0
-        obj_value = np.dot(f, f)
+        obj_value = objective(f)
         alpha = 0.0
         if max_nfev is None:
             max_nfev = x0.size * 100
@@ -64,7 +75,7 @@ def trf(fun, jac, x0, lb, ub, ftol, xtol, gtol, max_nfev, scaling, ctx=None):
         have_factor = True
         while nfev < max_nfev:
             if not have_factor:
-                F = solver.factor(J[None], f[None], x[None], lb[None], ub[None], scale[None],
+                F = solver.factor(J[None], f_s[None], x[None], lb[None], ub[None], scale[None],
                                   SCALE_JAC_UPDATE if use_jac else SCALE_GIVEN)
                 scale = F.scale[0]
                 have_factor = True
@@ -84,7 +95,7 @@ def trf(fun, jac, x0, lb, ub, ftol, xtol, gtol, max_nfev, scaling, ctx=None):
                 x_new = S.x_new[0]
                 f_new = fun(x_new)
                 nfev += 1
-                obj_value_new = np.dot(f_new, f_new)
+                obj_value_new = objective(f_new)
                 actual_reduction = obj_value - obj_value_new
                 predicted = float(S.predicted_reduction[0])
                 if predicted > 0:
@@ -107,7 +118,7 @@ def trf(fun, jac, x0, lb, ub, ftol, xtol, gtol, max_nfev, scaling, ctx=None):
                 x = x_new
                 f = f_new
                 obj_value = obj_value_new
-                J = jac(x, f)
+                J, f_s = prepare(jac(x, f), f)
                 njev += 1
                 have_factor = False
         return OptimizeResult(
@@ -118,8 +129,10 @@ def trf(fun, jac, x0, lb, ub, ftol, xtol, gtol, max_nfev, scaling, ctx=None):
         return_solver(solver)
 
 
-def dogbox(fun, jac, x0, lb, ub, ftol, xtol, gtol, max_nfev, scaling, ctx=None):
-    """Rectangular trust-region dogleg driver (reference: dogbox.py:100)."""
+def dogbox(fun, jac, x0, lb, ub, ftol, xtol, gtol, max_nfev, scaling, ctx=None, loss='linear', f_scale=1.0):
+    """Rectangular trust-region dogleg driver (reference: dogbox.py:100; `loss` / `f_scale` as scipy's,
+    its dogbox.py:413-416,509-541)."""
+    prepare, objective = _robust(loss, f_scale)
     f = fun(x0)
     nfev = 1
     J = jac(x0, f)
@@ -128,6 +141,7 @@ def dogbox(fun, jac, x0, lb, ub, ftol, xtol, gtol, max_nfev, scaling, ctx=None):
         raise RuntimeError("Inconsistent dimensions between the returns of "
                            "`fun` and `jac` on the first iteration.")
     m, n = J.shape
+    J, f_s = prepare(J, f)
     solver = lease_solver(DogboxStepSolver, 1, m, n, ctx=ctx)
     try:
         use_jac = _is_jac(scaling)
@@ -136,13 +150,13 @@ def dogbox(fun, jac, x0, lb, ub, ftol, xtol, gtol, max_nfev, scaling, ctx=None):
         on_bound[np.equal(x0, lb)] = -1
         on_bound[np.equal(x0, ub)] = 1
         x = x0.copy()
-        F = solver.factor(J[None], f[None], x[None], lb[None], ub[None], scale[None],
+        F = solver.factor(J[None], f_s[None], x[None], lb[None], ub[None], scale[None],
                           on_bound[None], SCALE_JAC_INIT if use_jac else SCALE_GIVEN)
         scale = F.scale[0]
         Delta = norm(x0 / scale, ord=np.inf)                  # dogbox.py:148-150
         if Delta == 0:
             Delta = 1.0
-        obj_value = np.dot(f, f)
+        obj_value = objective(f)
         if max_nfev is None:
             max_nfev = x0.size * 100
         status = None
@@ -150,7 +164,7 @@ def dogbox(fun, jac, x0, lb, ub, ftol, xtol, gtol, max_nfev, scaling, ctx=None):
         have_factor = True
         while nfev < max_nfev:
             if not have_factor:
-                F = solver.factor(J[None], f[None], x[None], lb[None], ub[None], scale[None],
+                F = solver.factor(J[None], f_s[None], x[None], lb[None], ub[None], scale[None],
                                   on_bound[None],
                                   SCALE_JAC_UPDATE if use_jac else SCALE_GIVEN)
                 scale = F.scale[0]
@@ -173,7 +187,7 @@ def dogbox(fun, jac, x0, lb, ub, ftol, xtol, gtol, max_nfev, scaling, ctx=None):
                 x_new = S.x_new[0]
                 f_new = fun(x_new)
                 nfev += 1
-                obj_value_new = np.dot(f_new, f_new)
+                obj_value_new = objective(f_new)
                 actual_reduction = obj_value - obj_value_new
                 predicted = float(S.predicted_reduction[0])
                 ratio = actual_reduction / predicted if predicted > 0 else 0
@@ -193,7 +207,7 @@ def dogbox(fun, jac, x0, lb, ub, ftol, xtol, gtol, max_nfev, scaling, ctx=None):
                 x[on_bound == 1] = ub[on_bound == 1]
                 f = f_new
                 obj_value = obj_value_new
-                J = jac(x, f)
+                J, f_s = prepare(jac(x, f), f)
                 njev += 1
                 have_factor = False
         return OptimizeResult(

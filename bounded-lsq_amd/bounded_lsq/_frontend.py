@@ -11,7 +11,7 @@ import numpy as np
 from scipy.optimize._numdiff import approx_derivative
 
 from ._drivers import trf, dogbox
-from ._hostmath import in_bounds, prepare_bounds
+from ._hostmath import in_bounds, prepare_bounds, check_loss
 
 EPS = np.finfo(float).eps
 
@@ -54,7 +54,7 @@ def _checked_scaling(scaling, x0):
 
 def least_squares(fun, x0, jac='2-point', bounds=(-np.inf, np.inf), method='trf',
                   ftol=EPS ** 0.5, xtol=EPS ** 0.5, gtol=EPS ** 0.5, max_nfev=None,
-                  scaling=1.0, diff_step=None, args=(), kwargs={}, options={}):
+                  scaling=1.0, diff_step=None, args=(), kwargs={}, options={}, loss='linear', f_scale=1.0):
     """Minimise ``sum(fun(x)**2)`` subject to ``lb <= x <= ub``.
 
     Parameters and the returned ``OptimizeResult`` fields (x, fun, jac,
@@ -62,9 +62,16 @@ def least_squares(fun, x0, jac='2-point', bounds=(-np.inf, np.inf), method='trf'
     x_covariance) are those of the reference (least_squares.py:120-305).  The
     per-iteration linear algebra runs on the GPU; ``options`` may carry
     ``ctx`` (a ``bounded_lsq._abi.Context``) to choose the device.
+
+    ``loss`` / ``f_scale`` are those of scipy.optimize.least_squares (its successor): 'linear' (the
+    reference's sum f^2), 'huber', 'soft_l1', 'cauchy', 'arctan' or a callable ``z -> (3, m)``; the
+    objective is then ``f_scale**2 * sum(rho(z))``, z = (f / f_scale)**2 (``obj_value``: twice scipy's
+    ``cost``), ``fun`` the true residuals and ``jac`` the scaled Jacobian diag(w) J, as scipy returns it.
     """
     if method not in ['trf', 'dogbox', 'lm']:
         raise ValueError("`method` must be 'trf', 'dogbox' or 'lm'.")
+    check_loss(loss, f_scale)
+    f_scale = float(f_scale)
     if method == 'lm':
         raise NotImplementedError(
             "method='lm' is a MINPACK bridge in the reference and is outside "
@@ -109,8 +116,12 @@ def least_squares(fun, x0, jac='2-point', bounds=(-np.inf, np.inf), method='trf'
             return np.ascontiguousarray(J, dtype=float)
 
     driver = trf if method == 'trf' else dogbox
-    result = driver(residuals, jacobian, x0, lb, ub, ftol, xtol, gtol, max_nfev, scaling,
-                    **options)
+    if not callable(loss) and loss == 'linear':
+        result = driver(residuals, jacobian, x0, lb, ub, ftol, xtol, gtol, max_nfev, scaling,
+                        **options)
+    else:
+        result = driver(residuals, jacobian, x0, lb, ub, ftol, xtol, gtol, max_nfev, scaling,
+                        loss=loss, f_scale=f_scale, **options)
     result.message = TERMINATION_MESSAGES[result.status]
     result.success = result.status > 0
     return result

@@ -62,3 +62,93 @@ def cl_optimality(x, g, lb, ub):
     lb = np.resize(lb, np.shape(x))
     ub = np.resize(ub, np.shape(x))
     return float(np.linalg.norm(cl_vector(np.asarray(x, float), g, lb, ub) * g, ord=np.inf))
+
+
+# ---- robust loss functions (scipy.optimize.least_squares `loss=` / `f_scale=`) --------------------------------------
+# The reference minimises sum f^2.  Its successor scipy (1.15.3) adds a robust loss on top of the same drivers by
+# transforming the step's inputs (_lsq/common.py scale_for_robust_loss_function); restated here for the host drivers
+# (one operation per scipy operation: the same bits).  The device path is loss_kernels.hip.
+LOSSES = ('linear', 'huber', 'soft_l1', 'cauchy', 'arctan')     # scipy's IMPLEMENTED_LOSSES order = BLSQ_LOSS_*
+EPS = np.finfo(float).eps
+
+
+def loss_message():
+    return "`loss` must be one of {0} or a callable.".format(dict.fromkeys(LOSSES).keys())
+
+
+def _rho_builtin(name, z):
+    """(rho0, rho1, rho2) of z for a named loss, before the f_scale factors."""
+    r = np.empty((3,) + z.shape)
+    with np.errstate(divide='ignore', invalid='ignore', over='ignore'):
+        if name == 'linear':                    # rho(z) = z
+            r[0] = z
+            r[1] = 1.0
+            r[2] = 0.0
+        elif name == 'huber':                   # z for z <= 1, 2 sqrt(z) - 1 above
+            lin = z <= 1
+            far = ~lin
+            zf = z[far]
+            r[0][lin] = z[lin]
+            r[1][lin] = 1
+            r[2][lin] = 0
+            r[0][far] = 2 * zf ** 0.5 - 1
+            r[1][far] = zf ** -0.5
+            r[2][far] = -0.5 * zf ** -1.5
+        elif name == 'soft_l1':                 # 2 (sqrt(1 + z) - 1)
+            t = 1 + z
+            r[0] = 2 * (t ** 0.5 - 1)
+            r[1] = t ** -0.5
+            r[2] = -0.5 * t ** -1.5
+        elif name == 'cauchy':                  # log(1 + z)
+            t = 1 + z
+            r[0] = np.log1p(z)
+            r[1] = 1 / t
+            r[2] = -1 / t ** 2
+        elif name == 'arctan':                  # arctan(z)
+            t = 1 + z ** 2
+            r[0] = np.arctan(z)
+            r[1] = 1 / t
+            r[2] = -2 * z / t ** 2
+        else:
+            raise ValueError(loss_message())
+    return r
+
+
+def loss_rho(loss, f, f_scale):
+    """rho (3, m) at the residuals f: scipy's construct_loss_function(m, loss, f_scale)(f) (rho0 *= f_scale^2,
+    rho2 /= f_scale^2).  `loss` is a name of LOSSES or a callable z -> (3, m)."""
+    with np.errstate(divide='ignore', invalid='ignore', over='ignore'):
+        z = (f / f_scale) ** 2
+        rho = np.array(loss(z), dtype=float) if callable(loss) else _rho_builtin(loss, z)
+        rho[0] *= f_scale ** 2
+        rho[2] /= f_scale ** 2
+    return rho
+
+
+def loss_cost(loss, f, f_scale):
+    """The objective f_scale^2 * sum rho0((f / f_scale)^2): the library's convention (no 1/2, so 'linear' with
+    f_scale = 1 is ||f||^2); twice scipy's cost_only value, bit for bit."""
+    with np.errstate(divide='ignore', invalid='ignore', over='ignore'):
+        z = (f / f_scale) ** 2
+        rho0 = np.asarray(loss(z), dtype=float)[0] if callable(loss) else _rho_builtin(loss, z)[0]
+        return f_scale ** 2 * np.sum(rho0)
+
+
+def loss_scale(J, f, rho):
+    """scipy's scale_for_robust_loss_function without the in-place updates: -> (diag(w) J, f * (rho1 / w)),
+    w = sqrt(max(rho1 + 2 rho2 f^2, EPS)) (NaN stays NaN).  J (m, n) and f (m,) are not modified."""
+    with np.errstate(invalid='ignore', over='ignore', divide='ignore'):
+        w = rho[1] + 2 * rho[2] * f ** 2
+        w[w < EPS] = EPS
+        w **= 0.5
+        return J * w[:, np.newaxis], f * (rho[1] / w)
+
+
+def check_loss(loss, f_scale):
+    """Argument checks of `least_squares` (the message of scipy for `loss`; scipy does not check `f_scale`)."""
+    if not callable(loss) and not (isinstance(loss, str) and loss in LOSSES):
+        raise ValueError(loss_message())
+    fs = np.asarray(f_scale, dtype=float)
+    with np.errstate(invalid='ignore'):
+        if fs.size == 0 or not np.all(fs > 0) or not np.all(np.isfinite(fs)):
+            raise ValueError("`f_scale` must be positive.")

@@ -18,6 +18,7 @@ import numpy as np
 
 from . import _abi
 from ._abi import vp, ptr
+from ._hostmath import LOSSES, loss_message
 
 METHODS = {"trf": 0, "dogbox": 1}
 
@@ -67,6 +68,17 @@ class OuterDriver:
         self.close()
 
     # ---- raw protocol ------------------------------------------------------------------
+    def set_loss(self, loss, f_scale=1.0):
+        """Robust loss (scipy's `loss` / `f_scale`; blsq_outer_set_loss): a name of LOSSES, f_scale a positive scalar
+        or (B,).  Before start().  With a loss other than 'linear', buffer J holds diag(w) J after begin / propose
+        and a jac callback after judge() must write the J of the accepted problems ONLY."""
+        if loss not in LOSSES:
+            raise ValueError(loss_message())
+        fs = np.ascontiguousarray(np.broadcast_to(np.asarray(f_scale, dtype=np.float64), (self.B,)))
+        self.ctx.check(self.ctx.lib.blsq_outer_set_loss(self.h, LOSSES.index(loss), ptr(fs)),
+                       "blsq_outer_set_loss")
+        self.loss = loss
+
     def start(self, x0, x_start, lb, ub, scale, jac_scaling, ftol, xtol, gtol, max_nfev):
         arrs = [np.ascontiguousarray(np.broadcast_to(a, (self.B, self.n)), dtype=np.float64)
                 for a in (x0, x_start, lb, ub, scale)]

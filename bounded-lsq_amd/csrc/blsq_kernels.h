@@ -518,11 +518,19 @@ struct OuterState {       // device pointers; method 0 = TRF, 1 = dogbox
   int *nfev, *njev, *pending, *result, *done, *at_top, *accepted;  // [B]
   int* ncols_fac;             // [B]  n + 1 where a fresh Jacobian must be factored, else 0
   int* counts;                // [2]  active problems, accepted problems (of this tick)
+  const double* lobj;         // [B]  robust-loss objective of f (begin) / f_trial (judge); nullptr: sum f^2
 };
 hipError_t launch_outer_begin(const OuterState& o, hipStream_t s);
 hipError_t launch_outer_top(const OuterState& o, hipStream_t s);
 hipError_t launch_outer_trial(const OuterState& o, hipStream_t s);
 hipError_t launch_outer_judge(const OuterState& o, hipStream_t s);
+
+// ------------------------------------------------ robust loss functions ----
+// loss_kernels.hip (blsq_loss_cost_dev / blsq_loss_scale_dev); loss: BLSQ_LOSS_*; mask may be nullptr
+hipError_t launch_loss_cost(int B, int m, int loss, const double* fscale, const double* f, double* obj,
+                            const int* mask, hipStream_t s);
+hipError_t launch_loss_scale(int B, int m, int n, int loss, const double* fscale, const double* f, double* J,
+                             double* fsc, const int* mask, hipStream_t s);
 
 
 // ------------------------------------- finite-difference Jacobians (8f-2) ----

@@ -1,6 +1,8 @@
 // C-ABI entry points (include/blsq.h): the batched, device-resident outer drivers and the finite-difference Jacobians.
 #include "blsq_host.h"
 
+#include <cmath>
+
 // ==================================================== batched outer drivers ===
 struct blsq_outer {
   blsq_ctx* ctx = nullptr;
@@ -8,6 +10,8 @@ struct blsq_outer {
   blsq_trf_plan* trf = nullptr;
   blsq_dogbox_plan* dog = nullptr;
   DevBuf x0, xc, xt, f, ft, J, dvec, ivec, counts;
+  DevBuf fsc, lobj, fscale;            // robust loss only: scaled f [B][m], objective [B], f_scale [B]
+  int loss = BLSQ_LOSS_LINEAR;
   OuterState st{};
   int jac_scaling = 0;
   double xtol = 0.0;
@@ -70,6 +74,7 @@ extern "C" int blsq_outer_destroy(blsq_outer* o) {
   if (o->dog) blsq_dogbox_plan_destroy(o->dog);
   o->x0.release(); o->xc.release(); o->xt.release(); o->f.release(); o->ft.release();
   o->J.release(); o->dvec.release(); o->ivec.release(); o->counts.release();
+  o->fsc.release(); o->lobj.release(); o->fscale.release();
   delete o;
   return 0;
 }
@@ -124,15 +129,61 @@ extern "C" int blsq_outer_start(blsq_outer* o, const double* x0, const double* x
   return 0;
 }
 
+extern "C" int blsq_outer_set_loss(blsq_outer* o, int loss, const double* f_scale) {
+  if (!o) return -1;
+  blsq_ctx* ctx = o->ctx;
+  if (o->started) return ctx->bad(1, "blsq_outer_set_loss must be called before blsq_outer_start");
+  if (loss < BLSQ_LOSS_LINEAR || loss > BLSQ_LOSS_ARCTAN) return ctx->bad(2, "loss must be one of BLSQ_LOSS_*");
+  if (loss == BLSQ_LOSS_LINEAR) {
+    o->loss = loss;
+    o->st.lobj = nullptr;
+    return 0;
+  }
+  if (!f_scale) return ctx->bad(3, "f_scale is NULL");
+  for (int b = 0; b < o->B; ++b)
+    if (!(f_scale[b] > 0.0) || !std::isfinite(f_scale[b])) return ctx->bad(3, "f_scale must be positive and finite");
+  HIPCHK(ctx, hipSetDevice(ctx->device));
+  const size_t vm = sizeof(double) * (size_t)o->B * o->m, vb = sizeof(double) * (size_t)o->B;
+  hipError_t e = hipSuccess;
+  if (!o->fsc.p) e = o->fsc.alloc(vm);
+  if (e == hipSuccess && !o->lobj.p) e = o->lobj.alloc(vb);
+  if (e == hipSuccess && !o->fscale.p) e = o->fscale.alloc(vb);
+  if (e != hipSuccess) return ctx->fail(e, "hipMalloc(outer driver loss)");
+  HIPCHK(ctx, hipMemcpyAsync(o->fscale.p, f_scale, vb, hipMemcpyHostToDevice, ctx->stream));
+  HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+  o->loss = loss;
+  o->st.lobj = o->lobj.as<double>();
+  return 0;
+}
+
 namespace blsq_host {
-// factor the problems selected by `mask` (nullptr: all) from the driver's J / f buffers
+// robust loss: J <- diag(w) J and the scaled f of the problems selected by `mask` (nullptr: all)
+static int outer_loss_scale(blsq_outer* o, const int* mask) {
+  blsq_ctx* ctx = o->ctx;
+  ctx->begin(K_LOSS_SCALE);
+  hipError_t e = launch_loss_scale(o->B, o->m, o->n, o->loss, o->fscale.as<double>(), o->st.f, o->J.as<double>(),
+                                   o->fsc.as<double>(), mask, ctx->stream);
+  ctx->end();
+  return e == hipSuccess ? 0 : ctx->fail(e, "launch_loss_scale");
+}
+// robust loss: the objective of every problem at `f` into st.lobj
+static int outer_loss_cost(blsq_outer* o, const double* f) {
+  blsq_ctx* ctx = o->ctx;
+  ctx->begin(K_LOSS_COST);
+  hipError_t e = launch_loss_cost(o->B, o->m, o->loss, o->fscale.as<double>(), f, o->lobj.as<double>(), nullptr,
+                                  ctx->stream);
+  ctx->end();
+  return e == hipSuccess ? 0 : ctx->fail(e, "launch_loss_cost");
+}
+// factor the problems selected by `mask` (nullptr: all) from the driver's J / f buffers (the scaled f with a loss)
 int outer_factor(blsq_outer* o, int scale_mode, const int* mask) {
+  const double* f = (o->loss != BLSQ_LOSS_LINEAR) ? o->fsc.as<double>() : o->st.f;
   if (o->method == 0) {
     blsq_trf_plan* p = o->trf;
-    return trf_factor_core(p, o->J.as<double>(), o->st.f, p->n, scale_mode, mask);
+    return trf_factor_core(p, o->J.as<double>(), f, p->n, scale_mode, mask);
   }
   blsq_dogbox_plan* p = o->dog;
-  return dog_factor_core(p, o->J.as<double>(), o->st.f, p->n, scale_mode, mask);
+  return dog_factor_core(p, o->J.as<double>(), f, p->n, scale_mode, mask);
 }
 }  // namespace blsq_host
 
@@ -141,7 +192,12 @@ extern "C" int blsq_outer_begin(blsq_outer* o) {
   blsq_ctx* ctx = o->ctx;
   if (!o->started) return ctx->bad(1, "blsq_outer_start has not been called");
   HIPCHK(ctx, hipSetDevice(ctx->device));
-  int rc = outer_factor(o, o->jac_scaling ? BLSQ_SCALE_JAC_INIT : BLSQ_SCALE_GIVEN, nullptr);
+  int rc;
+  if (o->loss != BLSQ_LOSS_LINEAR) {     // every J is fresh
+    if ((rc = outer_loss_scale(o, nullptr))) return rc;
+    if ((rc = outer_loss_cost(o, o->st.f))) return rc;
+  }
+  rc = outer_factor(o, o->jac_scaling ? BLSQ_SCALE_JAC_INIT : BLSQ_SCALE_GIVEN, nullptr);
   if (rc) return rc;
   hipError_t e = launch_outer_begin(o->st, ctx->stream);
   if (e != hipSuccess) return ctx->fail(e, "launch_outer_begin");
@@ -157,6 +213,7 @@ extern "C" int blsq_outer_propose(blsq_outer* o, int32_t* n_active) {
   HIPCHK(ctx, hipSetDevice(ctx->device));
   int rc;
   if (o->last_accepted > 0) {            // fresh Jacobians: factor those problems only
+    if (o->loss != BLSQ_LOSS_LINEAR && (rc = outer_loss_scale(o, o->st.accepted))) return rc;
     rc = outer_factor(o, o->jac_scaling ? BLSQ_SCALE_JAC_UPDATE : BLSQ_SCALE_GIVEN,
                       o->st.ncols_fac);
     if (rc) return rc;
@@ -183,6 +240,8 @@ extern "C" int blsq_outer_judge(blsq_outer* o, int32_t* n_accepted) {
   if (!o->begun) return ctx->bad(1, "blsq_outer_begin has not been called");
   if (!n_accepted) return ctx->bad(2, "n_accepted is NULL");
   HIPCHK(ctx, hipSetDevice(ctx->device));
+  int rc;
+  if (o->loss != BLSQ_LOSS_LINEAR && (rc = outer_loss_cost(o, o->st.ft))) return rc;
   hipError_t e = launch_outer_judge(o->st, ctx->stream);
   if (e != hipSuccess) return ctx->fail(e, "launch_outer_judge");
   HIPCHK(ctx, hipMemcpyAsync(ctx->pinned, o->st.counts + 1, sizeof(int), hipMemcpyDeviceToHost,
@@ -224,6 +283,43 @@ extern "C" int blsq_outer_fetch(blsq_outer* o, double* x, double* f, double* obj
     }
   }
   HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+  return 0;
+}
+
+// ================================================== robust loss functions ===
+extern "C" int blsq_loss_cost_dev(blsq_ctx* ctx, int B, int m, int loss, const double* df_scale, const double* df,
+                                  double* dobj, const int32_t* dmask) {
+  if (!ctx) return -1;
+  if (B <= 0) return ctx->bad(2, "B must be positive");
+  if (m <= 0) return ctx->bad(3, "m must be positive");
+  if (loss < BLSQ_LOSS_LINEAR || loss > BLSQ_LOSS_ARCTAN) return ctx->bad(4, "loss must be one of BLSQ_LOSS_*");
+  if (!df_scale) return ctx->bad(5, "f_scale is NULL");
+  if (!df) return ctx->bad(6, "f is NULL");
+  if (!dobj) return ctx->bad(7, "obj is NULL");
+  HIPCHK(ctx, hipSetDevice(ctx->device));
+  ctx->begin(K_LOSS_COST);
+  hipError_t e = launch_loss_cost(B, m, loss, df_scale, df, dobj, dmask, ctx->stream);
+  ctx->end();
+  if (e != hipSuccess) return ctx->fail(e, "launch_loss_cost");
+  return 0;
+}
+
+extern "C" int blsq_loss_scale_dev(blsq_ctx* ctx, int B, int m, int n, int loss, const double* df_scale,
+                                   const double* df, double* dJ_io, double* df_scaled, const int32_t* dmask) {
+  if (!ctx) return -1;
+  if (B <= 0) return ctx->bad(2, "B must be positive");
+  if (m <= 0) return ctx->bad(3, "m must be positive");
+  if (n <= 0) return ctx->bad(4, "n must be positive");
+  if (loss < BLSQ_LOSS_LINEAR || loss > BLSQ_LOSS_ARCTAN) return ctx->bad(5, "loss must be one of BLSQ_LOSS_*");
+  if (!df_scale) return ctx->bad(6, "f_scale is NULL");
+  if (!df) return ctx->bad(7, "f is NULL");
+  if (!dJ_io) return ctx->bad(8, "J is NULL");
+  if (!df_scaled) return ctx->bad(9, "f_scaled is NULL");
+  HIPCHK(ctx, hipSetDevice(ctx->device));
+  ctx->begin(K_LOSS_SCALE);
+  hipError_t e = launch_loss_scale(B, m, n, loss, df_scale, df, dJ_io, df_scaled, dmask, ctx->stream);
+  ctx->end();
+  if (e != hipSuccess) return ctx->fail(e, "launch_loss_scale");
   return 0;
 }
 

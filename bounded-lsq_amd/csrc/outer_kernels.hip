@@ -32,10 +32,15 @@ __global__ __launch_bounds__(OUT_NT) void outer_begin_kernel(OuterState o) {
   __shared__ double red[32];
   const int b = blockIdx.x, tid = threadIdx.x;
   const int n = o.n, m = o.m, ld = o.ld;
-  const double* f = o.f + (long)b * m;
-  double acc = 0.0;
-  for (int i = tid; i < m; i += OUT_NT) acc += f[i] * f[i];
-  const double obj = block_sum(acc, red);
+  double obj;
+  if (o.lobj) {                                     // robust loss: f_scale^2 sum rho0 (loss_kernels.hip)
+    obj = o.lobj[b];
+  } else {
+    const double* f = o.f + (long)b * m;
+    double acc = 0.0;
+    for (int i = tid; i < m; i += OUT_NT) acc += f[i] * f[i];
+    obj = block_sum(acc, red);
+  }
   // Delta_0 from the UNSHIFTED x0 (trf.py:223-226; dogbox.py:148-150)
   double dn = 0.0;
   if (o.method == 0) {
@@ -116,9 +121,14 @@ __global__ __launch_bounds__(OUT_NT) void outer_judge_kernel(OuterState o) {
   if (o.done[b]) return;                            // frozen (uniform per workgroup)
   const int n = o.n, m = o.m, ld = o.ld;
   const double* ft = o.ft + (long)b * m;
-  double acc = 0.0;
-  for (int i = tid; i < m; i += OUT_NT) acc += ft[i] * ft[i];
-  const double obj_new = block_sum(acc, red);
+  double obj_new;
+  if (o.lobj) {                                     // robust loss: f_scale^2 sum rho0 (loss_kernels.hip)
+    obj_new = o.lobj[b];
+  } else {
+    double acc = 0.0;
+    for (int i = tid; i < m; i += OUT_NT) acc += ft[i] * ft[i];
+    obj_new = block_sum(acc, red);
+  }
   const double obj = o.obj[b];
   const double actual = obj - obj_new;
   double Delta = o.Delta[b], alpha = o.alpha[b];

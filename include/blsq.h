@@ -343,6 +343,36 @@ int blsq_fd_assemble_dev(blsq_ctx* ctx, int B, int m, int n, int method, const d
                          const double* dh, const uint8_t* done_sided, const double* df0,
                          const double* dF, double* dJ, const int32_t* dmask);
 
+/* ---- robust loss functions (scipy.optimize.least_squares `loss=`, `f_scale=`) ----------------------------------
+ * The reference minimises sum f^2 only.  Its successor, scipy.optimize.least_squares (1.15.3), adds a robust loss on
+ * top of the same trf / dogbox drivers by transforming the INPUTS of each step; the step path itself is unchanged.
+ * Losses in scipy's IMPLEMENTED_LOSSES order (_lsq/least_squares.py: huber, soft_l1, cauchy, arctan); append only. */
+enum { BLSQ_LOSS_LINEAR = 0, BLSQ_LOSS_HUBER, BLSQ_LOSS_SOFT_L1, BLSQ_LOSS_CAUCHY, BLSQ_LOSS_ARCTAN };
+/* obj[b] = f_scale[b]^2 * sum_i rho0((f[b][i] / f_scale[b])^2): the objective of problem b (scipy
+ * _lsq/least_squares.py construct_loss_function, cost_only, WITHOUT its factor 1/2: 'linear' with f_scale = 1 is
+ * ||f||^2, the convention of every `obj` here).  Fixed summation order: a problem's bits do not depend on B or on
+ * its batch mates.  Problems with dmask[b] == 0 are skipped (dmask may be NULL).  Device pointers; f_scale [B] > 0. */
+int blsq_loss_cost_dev(blsq_ctx* ctx, int B, int m, int loss, const double* df_scale, const double* df,
+                       double* dobj, const int32_t* dmask);
+/* For the problems with dmask[b] != 0 (dmask may be NULL: all), scipy _lsq/common.py
+ * scale_for_robust_loss_function: w_i = sqrt(max(rho1 + 2 rho2 f_i^2, EPS)) (rho of construct_loss_function, with
+ * rho2 /= f_scale^2), J[b] <- diag(w) J[b] IN PLACE (dJ_io [B][m][n]) and df_scaled[b][i] = f_i * (rho1 / w_i)
+ * ([B][m]; df itself is not written).  Applying it twice scales J twice: call it once per fresh Jacobian. */
+int blsq_loss_scale_dev(blsq_ctx* ctx, int B, int m, int n, int loss, const double* df_scale, const double* df,
+                        double* dJ_io, double* df_scaled, const int32_t* dmask);
+/* Robust loss of a device-resident outer driver (scipy _lsq/trf.py trf_bounds / trf_no_bounds and _lsq/dogbox.py:
+ * the loss cost in the ratio test, scale_for_robust_loss_function after every Jacobian).  Call before
+ * blsq_outer_start (any other order is an argument error); the default after create is BLSQ_LOSS_LINEAR, for which
+ * nothing is launched.  f_scale: [B] host, each > 0 (may be NULL for BLSQ_LOSS_LINEAR).  With another loss:
+ *   - blsq_outer_begin scales every J, blsq_outer_propose scales the J of the problems with accepted[b] != 0 (the
+ *     jac callback after a judge writes J[b] of THOSE problems only: the others hold their scaled Jacobian);
+ *   - buffer `f` keeps the true residuals (callbacks write them, blsq_outer_fetch returns them); the scaled ones
+ *     live in a driver-owned buffer; buffer `J` holds diag(w) J (scipy's result `jac`);
+ *   - `obj` is f_scale^2 * sum rho0, as blsq_loss_cost_dev.
+ * Both the scaled J and the scaled f stay unmodified from a factor call to the next one, as the CSNE tier's
+ * lifetime rule asks. */
+int blsq_outer_set_loss(blsq_outer* o, int loss, const double* f_scale);
+
 #ifdef __cplusplus
 }
 #endif
