@@ -212,14 +212,13 @@ int dog_csne_correct(blsq_dogbox_plan* p, const double* dJ, const double* df, in
   *nfail = 0;
   if (tier.count <= 0) return 0;
   cs.J = dJ; cs.strideJ = (long)p->m * ldJ; cs.ldJ = ldJ; cs.F = df; cs.strideF = p->m;
-  cs.NE = 1;
-  { int rc_ = tier.grow_part(ctx, (size_t)tier.count * cs.nchunk * ((size_t)p->ld + 16)); if (rc_) return rc_; }
+  { int rc_ = tier.grow_part(ctx, (size_t)tier.count * cs.nchunk * ((size_t)cs.NE * p->ld + 16)); if (rc_) return rc_; }
   HIPCHK(ctx, hipMemsetAsync(cs.counts + 1, 0, sizeof(int), ctx->stream));
   ctx->begin(K_CSNE_PASS);
   hipError_t e = launch_dog_csne_scatter(cs, p->st, tier.count, ctx->stream);
-  if (e == hipSuccess) e = launch_csne_pass(cs, nullptr, tier.count, ctx->stream);
+  if (e == hipSuccess) e = launch_csne_pass_dog(cs, tier.count, ctx->stream);
   ctx->end();
-  if (e != hipSuccess) return ctx->fail(e, "launch_csne_pass(dogbox)");
+  if (e != hipSuccess) return ctx->fail(e, "launch_csne_pass_dog");
   ctx->begin(K_CSNE_FIX);
   e = launch_dog_csne_fix(cs, p->st, tier.count, ctx->stream);
   ctx->end();

@@ -323,7 +323,7 @@ int CsneTier::build(blsq_ctx* ctx, int B, int m, int n, int ld, bool with_hp) {
   cs.counts = ii + 5 * (size_t)B;                     // (sel_mask: ii + 4 B; scratch counter: counts + 4)
   cs.ralpha = alpha.as<double>(); cs.hp = hp.as<double>(); cs.eta = eta.as<double>();
   csne_geometry(m, &cs.rows_per_wg, &cs.nchunk);
-  cs.NE = 1;
+  cs.NE = with_hp ? CSNE_MAXE : 1;
   on = true;
   return 0;
 }

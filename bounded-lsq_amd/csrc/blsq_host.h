@@ -388,7 +388,6 @@ struct blsq_trf_plan : VerdictState {
   // CSNE tier: rejected problems whose steps are corrected against J in one streaming pass, at step time
   CsneTier csne;
   int last_scale_mode = 0;          // scale_mode of the last factor call (a problem that leaves the tier at step time is prepared again)
-  int lm_rounds_done = 0;           // Newton rounds the last trf_lm_rounds call ran (the deepest recording: 1 + that)
   // TSQR (multi-rank) extras
   int nranks = 1, m_total = 0;
   bool ranks_agreed = false;        // the ranks have compared their plan configuration (first factor call)

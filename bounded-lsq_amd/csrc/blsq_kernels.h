@@ -255,13 +255,14 @@ struct CsneState {
   int* ne;                // [B]            (LmState::csne_ne)
   double* ralpha;         // [B][CSNE_MAXE] (LmState::csne_alpha)
   double* rvec;           // [B][CSNE_MAXE][3][ld] (LmState::csne_vec)
-  double* part;           // [list position][chunks][NE][ld + 8] partial J_h^T (J_h p~ + f) and |J_h w~|^2 of the row chunks
+  double* part;           // [list position][chunks][csne_part_stride: NE * ld + 16] partial J_h^T (J_h p~ + f), NE vectors
+                          // of ld, and |J_h w~|^2, NE numbers, of the row chunks
   double* hp;             // [B][ld] out: H p_h (TrfState::csne_hp)
   double* eta;            // [B] out: the largest first-order correction measured (diagnostics / acceptance)
-  int rows_per_wg, nchunk, NE;   // set by the host (csne_geometry: functions of m and of the batch's deepest recording)
+  int rows_per_wg, nchunk;       // csne_geometry: functions of m
+  int NE;                        // vectors the partial sums carry: a constant of the plan (TRF: CSNE_MAXE, dogbox: 1)
 };
 void csne_geometry(int m, int* rows_per_wg, int* nchunk);
-int csne_launch_evals(int NE);            // evaluations the pass launch carries for a recording depth of NE (>= NE)
 bool csne_supported(int m, int n);
 struct LmState;
 struct TrfState;
@@ -276,10 +277,11 @@ hipError_t launch_csne_select(const CsneState& cs, const LmState& lm, int nfb, i
 hipError_t launch_csne_select_dog(const CsneState& cs, int m, const int* ncols, int* fast, int* ncols_jac, int nfb,
                                   int* tree_list, int* tree_mask, int* tree_count, int* path, const int* sel_mask,
                                   const double* k2, const double* pmin, const double* colinfo, hipStream_t s);
-// (dvec == nullptr: J_h = J, no column scaling — dogbox)
-hipError_t launch_csne_pass(const CsneState& cs, const double* dvec, int count, hipStream_t s);
-// the same sums with the dot products on the FP64 MFMA pipe (TRF; cs.NE = CSNE_MAXE: all eight evaluation slots)
-hipError_t launch_csne_pass_mfma(const CsneState& cs, const double* dvec, int count, hipStream_t s);
+// the pass of a TRF plan: both products of a 16-row tile on the FP64 MFMA pipe, J_h = J diag(dvec); cs.NE = CSNE_MAXE
+// (all eight evaluation slots)
+hipError_t launch_csne_pass_trf(const CsneState& cs, const double* dvec, int count, hipStream_t s);
+// the pass of a dogbox plan: ONE vector (recording 0), J_h = J, on the vector ALU; cs.NE = 1
+hipError_t launch_csne_pass_dog(const CsneState& cs, int count, hipStream_t s);
 // dogbox on the tier: the Gauss-Newton step of the free block, lstsq(J_free, -f) (dogbox.py:197), is ONE
 // solve — corrected at FACTOR time: scatter the cheap step into a full-length vector (the recording of the pass), the
 // pass, then  newton += -(X^T X)^-1 J_free^T (J_free newton + f)  with the free block's factor X

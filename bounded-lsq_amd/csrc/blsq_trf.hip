@@ -415,7 +415,6 @@ int trf_lm_rounds(blsq_trf_plan* p, const double* dDelta, const double* dalpha_i
       e = launch_lm_rounds_reg(c, p->lm, dDelta, dalpha_in, ctx->stream);
       ctx->end();
       if (e != hipSuccess) return ctx->fail(e, "launch_lm_rounds_reg");
-      p->lm_rounds_done = 0;
       if (!p->use_qr) return 0;
       p->lm.fused_gram = 1;
     }
@@ -519,14 +518,11 @@ int trf_lm_rounds(blsq_trf_plan* p, const double* dDelta, const double* dalpha_i
       done_rounds = round + 1;
     }
     p->lm_rounds_last = done_rounds;
-    p->lm_rounds_done = done_rounds;
     return 0;
   }
   HIPCHK(ctx, landed(0));
   int active = pin[0];
-  p->lm_rounds_done = 0;
   for (int round = 0; round < 12 && active > 0; ++round) {
-    p->lm_rounds_done = round + 1;
     if (p->use_chol && !p->lm.fused_gram) {
       e = chol_round(round, active, nullptr);
       if (e != hipSuccess) return ctx->fail(e, "launch_gram_chol(lm)");
@@ -554,17 +550,12 @@ int trf_csne_correct(blsq_trf_plan* p, const double* dDelta, const double* dalph
   blsq_ctx* ctx = p->ctx;
   CsneTier& tier = p->csne;
   CsneState& cs = tier.cs;
-  const int ne_max = std::min(CSNE_MAXE, 1 + std::max(0, p->lm_rounds_done));
-  const bool mfma = ctx->opt.on(OPT_CSNE_MFMA);           // (all eight evaluation slots; the sums do not depend on the depth)
-  const int NE = mfma ? CSNE_MAXE : csne_launch_evals(ne_max);   // (else the launch's split over the waves: NEH x G >= ne_max)
-  cs.NE = NE;
-  { int rc_ = tier.grow_part(ctx, (size_t)tier.count * cs.nchunk * ((size_t)NE * p->ld + 16)); if (rc_) return rc_; }
+  { int rc_ = tier.grow_part(ctx, (size_t)tier.count * cs.nchunk * ((size_t)cs.NE * p->ld + 16)); if (rc_) return rc_; }
   HIPCHK(ctx, hipMemsetAsync(cs.counts + 1, 0, sizeof(int), ctx->stream));
   ctx->begin(K_CSNE_PASS);
-  hipError_t e = mfma ? launch_csne_pass_mfma(cs, p->st.d, tier.count, ctx->stream)
-                      : launch_csne_pass(cs, p->st.d, tier.count, ctx->stream);
+  hipError_t e = launch_csne_pass_trf(cs, p->st.d, tier.count, ctx->stream);
   ctx->end();
-  if (e != hipSuccess) return ctx->fail(e, "launch_csne_pass");
+  if (e != hipSuccess) return ctx->fail(e, "launch_csne_pass_trf");
   ctx->begin(K_CSNE_FIX);
   e = launch_csne_fix(cs, p->st, p->lm, dDelta, dalpha_in, tier.count, ctx->stream);
   ctx->end();

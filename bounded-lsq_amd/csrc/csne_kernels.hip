@@ -11,7 +11,8 @@
 //
 //   1. the cheap iteration runs as for any normal-equations-path problem and RECORDS every evaluation k:
 //      alpha~_k, p~_k = -M~_k^-1 g_h, w~_k = M~_k^-1 p~_k, z~_k = M~_k^-1 w~_k          (lm_body.h)
-//   2. ONE streaming pass over J (csne_pass_kernel) forms, for all recorded evaluations at once,
+//   2. ONE streaming pass over J (TRF: csne_pass_mfma_kernel; dogbox, whose recording is the one Newton step:
+//      csne_pass_kernel) forms, for all recorded evaluations at once,
 //      y_k = J_h^T (J_h p~_k + f)  and  b_k = ||J_h w~_k||^2 — the residuals of the recorded solves against J
 //      ITSELF, f inside the product so that a small residual J p + f is not lost against g = J^T f
 //   3. csne_fix_kernel (n-space): res_k = y_k + (diag_h + alpha~_k) p~_k, and to first order in rho
@@ -49,84 +50,48 @@ bool csne_supported(int m, int n) { return n + 1 > 80 && n <= 256 && m >= n; }
 
 static constexpr int CS_NT = 256;
 static constexpr int CS_NW = CS_NT / WAVE;
-#ifndef BLSQ_CS_RB
-#define BLSQ_CS_RB 4
-#endif
-static constexpr int CS_RB = BLSQ_CS_RB; // rows per wave and batch
+static constexpr int CS_RB = 4;                           // rows per wave and batch
 
 __host__ __device__ inline long csne_part_stride(int NE, int ld) { return (long)NE * ld + 16; }
 __device__ __forceinline__ constexpr int cs_bitrev4(int i) {
   return ((i & 1) << 3) | ((i & 2) << 1) | ((i & 4) >> 1) | ((i & 8) >> 3);
 }
 
-// ---- the pass over J -------------------------------------------------------------------------------
+// ---- the pass over J with ONE vector on the vector ALU (dogbox) -----------------------------------------
 // grid (row chunks, listed problems) x 256 threads.  Lane l owns columns l + 64 cb.  The rows of a chunk go in batches
-// of four; batch bi belongs to row class bi mod 4, and a problem's sums are DEFINED as
+// of four; batch bi belongs to row class bi mod 4 — wave w takes the batches w, w + 4, ... — and a problem's sums are
+// DEFINED as
 //     ((S_0 + S_1) + S_2) + S_3,   S_c = the batches of class c in increasing order, rows 0 .. 3 of a batch in order
-// — whatever the launch looks like.  The launch splits the NE recorded evaluations over G groups of waves (G = 1, 2, 4;
-// NEH evaluations each): the four waves are G groups of 4 / G members, a member takes the classes c = j mod (4 / G) —
-// G of them, each in its own accumulators — for its group's evaluations.  So the deeper the batch's recordings the
-// fewer evaluations a wave carries (vectors, accumulators and the butterflies of its totals scale with NEH, not NE: the
-// kernel is VALU-issue-bound, not memory-bound, at NEH = 6), each row is then loaded by G waves (the second to fourth
-// from L1 / L2), and a problem's bits do not depend on the depth its batch forces on the launch.
-// Per row and evaluation e: the two dot products  u = J_h[r] . p~_e + f_r,  t = J_h[r] . w~_e  (J_h = J D: the vectors
-// are pre-multiplied by d), their 64-lane totals by transposed butterflies (wave_sum16), then  y_e += u J[r]  (per lane:
-// its columns) and  b_e += t^2  (uniform: broadcast first, so that its order is the rows' order).  J streams straight
-// into registers (the next batch is requested before the current one is consumed); no LDS on the way.
-#ifndef BLSQ_CS_WGS_PER_CU
-#define BLSQ_CS_WGS_PER_CU 1
-#endif
-template <int NCB, int NEH, int G, int NS>
-__global__ __launch_bounds__(CS_NT, BLSQ_CS_WGS_PER_CU) void csne_pass_kernel(CsneState cs, const double* __restrict__ dvec) {
-  static_assert(NS >= 2, "register slots of the row batches: one consumed, NS - 1 in flight");
-  static_assert(G == 1 || G == 2 || G == 4, "groups of waves");
-  constexpr int MEM = CS_NW / G;                          // members (waves) per group
-  constexpr int NV = 2 * NEH;                             // totals per row and wave
-  constexpr int NTOT = CS_RB * NV;                        // ... per batch
-  constexpr int NBF = (NTOT + 15) / 16;                   // butterflies per batch
-  constexpr int NE = NEH * G;                             // evaluations the launch carries (the partial sums' stride)
-  extern __shared__ double ysh[];                         // [group][class][NEH][NCB][64] + [group][class][NEH]
+// Per row: the dot product  u = J[r] . p~ + f_r  (p~: recording 0 of the problem, the scattered Newton step; no column
+// scaling: J_h = J), the four 64-lane totals of a batch by ONE transposed butterfly (wave_sum16: row r in slot 2 r, the
+// other slots zero — sums, order and slots are FIXED: they define a problem's bits), then  y += u J[r]  (per lane: its columns).  J streams straight into registers, no LDS on the way:
+// three register slots, i.e. two batches in flight behind the one being consumed — the bytes a CU keeps in flight are
+// what bounds this kernel (one workgroup per CU).
+template <int NCB>
+__global__ __launch_bounds__(CS_NT, 1) void csne_pass_kernel(CsneState cs) {
+  constexpr int NS = 3;                                   // register slots of the row batches
+  extern __shared__ double ysh[];                         // [class][NCB][64]
   const int li = blockIdx.y, chunk = blockIdx.x;
   const int b = cs.list[li];
   const int tid = threadIdx.x, lane = tid & 63, w = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int grp = w / MEM, mem = w % MEM;                 // (wave-uniform)
   const int n = cs.n, ld = cs.ld;
   const int r0 = chunk * cs.rows_per_wg;
   const int r1 = (r0 + cs.rows_per_wg < cs.m) ? r0 + cs.rows_per_wg : cs.m;
   const double* __restrict__ Jb = cs.J + (long)b * cs.strideJ;
   const double* __restrict__ Fb = cs.F + (long)b * cs.strideF;
-  int ne = cs.ne[b];
-  if (ne > NE) ne = NE;                                   // (deeper recordings are declined by csne_fix_kernel)
-  const int vidx = wave_sum16_index(lane);                // the total this lane receives from a butterfly
-  const int e0 = grp * NEH;                               // this wave's evaluations: e0 .. e0 + NEH - 1
+  const int vrow = wave_sum16_index(lane) / 2;            // the row whose total this lane receives from the butterfly
 
-  // the recorded vectors of the lane's columns, pre-multiplied by d (J_h = J D); zero beyond n and beyond the
-  // problem's recording: columns n .. 64 NCB of J are loaded clamped and count for nothing
-  double V[NEH][2][NCB];
+  // the vector at the lane's columns; zero beyond n: columns n .. 64 NCB of J are loaded clamped and count for nothing
+  double V[NCB], y[NCB];
 #pragma unroll
-  for (int e = 0; e < NEH; ++e)
-#pragma unroll
-    for (int c = 0; c < 2; ++c)
-#pragma unroll
-      for (int cb = 0; cb < NCB; ++cb) {
-        const int col = lane + 64 * cb;
-        double v = 0.0;
-        if (e0 + e < ne && col < n)
-          v = (dvec ? dvec[(long)b * ld + col] : 1.0) * cs.rvec[(((long)b * CSNE_MAXE + e0 + e) * 3 + c) * ld + col];
-        V[e][c][cb] = v;
-      }
-  double y[G][NEH][NCB], accB[G][NEH];                    // per class of this wave
-#pragma unroll
-  for (int ci = 0; ci < G; ++ci)
-#pragma unroll
-    for (int e = 0; e < NEH; ++e) {
-      accB[ci][e] = 0.0;
-#pragma unroll
-      for (int cb = 0; cb < NCB; ++cb) y[ci][e][cb] = 0.0;
-    }
+  for (int cb = 0; cb < NCB; ++cb) {
+    const int col = lane + 64 * cb;
+    V[cb] = col < n ? cs.rvec[(long)b * CSNE_MAXE * 3 * ld + col] : 0.0;
+    y[cb] = 0.0;
+  }
 
   const int nbatch = (r1 - r0 + CS_RB - 1) / CS_RB;
-  double jr[NS][CS_RB][NCB], fr[NS][NBF];
+  double jr[NS][CS_RB][NCB], fr[NS];
   auto issue = [&](int bi, auto slotc) __attribute__((always_inline)) {
     constexpr int slot = decltype(slotc)::value;
     const int rb = r0 + bi * CS_RB;
@@ -140,15 +105,11 @@ __global__ __launch_bounds__(CS_NT, BLSQ_CS_WGS_PER_CU) void csne_pass_kernel(Cs
         jr[slot][r][cb] = __builtin_nontemporal_load(Jb + (long)rc * cs.ldJ + (col < n ? col : n - 1));
       }
     }
-#pragma unroll
-    for (int g = 0; g < NBF; ++g) {
-      const int row = rb + (16 * g + vidx) / NV;
-      fr[slot][g] = Fb[row < r1 ? row : r1 - 1];
-    }
+    const int row = rb + vrow;
+    fr[slot] = Fb[row < r1 ? row : r1 - 1];
   };
-  auto consume = [&](int bi, auto slotc, auto cic) __attribute__((always_inline)) {
+  auto consume = [&](int bi, auto slotc) __attribute__((always_inline)) {
     constexpr int slot = decltype(slotc)::value;
-    constexpr int ci = decltype(cic)::value;
     const int rb = r0 + bi * CS_RB;
     if (rb + CS_RB > r1) {                                 // (uniform; the last batch of a chunk only) rows beyond it: zero
 #pragma unroll
@@ -156,98 +117,64 @@ __global__ __launch_bounds__(CS_NT, BLSQ_CS_WGS_PER_CU) void csne_pass_kernel(Cs
 #pragma unroll
         for (int cb = 0; cb < NCB; ++cb)
           if (rb + r >= r1) jr[slot][r][cb] = 0.0;
-#pragma unroll
-      for (int g = 0; g < NBF; ++g)
-        if (rb + (16 * g + vidx) / NV >= r1) fr[slot][g] = 0.0;
+      if (rb + vrow >= r1) fr[slot] = 0.0;
     }
-    // one butterfly's sixteen totals at a time: their dot products, the butterfly, what the totals feed
     // (compile-time recursion instead of unrolled loops: every register-array index must be a constant)
-    static_for<0, NBF>([&](auto gc) __attribute__((always_inline)) {
-      constexpr int g = decltype(gc)::value;
-      double v[16];
-      static_for<0, 16>([&](auto ic) __attribute__((always_inline)) {
-        constexpr int i = decltype(ic)::value;
-        constexpr int idx = 16 * g + i;
-        double acc = 0.0;
-        if constexpr (idx < NTOT) {
-          constexpr int r = idx / NV, e = (idx % NV) / 2, c = idx % 2;
+    double v[16];
+    static_for<0, 16>([&](auto ic) __attribute__((always_inline)) {
+      constexpr int i = decltype(ic)::value;
+      double acc = 0.0;
+      if constexpr (i < 2 * CS_RB && i % 2 == 0) {
 #pragma unroll
-          for (int cb = 0; cb < NCB; ++cb) acc = fma(jr[slot][r][cb], V[e][c][cb], acc);
-        }
-        v[i] = acc;
-      });
-      wave_sum16(v);
-      const double tot = v[0];
-      const double uu = tot + fr[slot][g];                // (meaningful on the lanes of the u totals: bit 3 clear)
-      static_for<0, 8>([&](auto hc) __attribute__((always_inline)) {   // the (row, evaluation) pairs of this butterfly, in row order
-        constexpr int i = 2 * decltype(hc)::value;
-        constexpr int idx = 16 * g + i;
-        if constexpr (idx < NTOT) {
-          constexpr int r = idx / NV, e = (idx % NV) / 2;
-          const double us = read_lane(uu, cs_bitrev4(i));
-          const double ts = read_lane(tot, cs_bitrev4(i + 1));
-          accB[ci][e] = fma(ts, ts, accB[ci][e]);
+        for (int cb = 0; cb < NCB; ++cb) acc = fma(jr[slot][i / 2][cb], V[cb], acc);
+      }
+      v[i] = acc;
+    });
+    wave_sum16(v);
+    const double uu = v[0] + fr[slot];                    // (meaningful on the lanes of the four totals)
+    static_for<0, CS_RB>([&](auto rc) __attribute__((always_inline)) {   // in row order
+      constexpr int r = decltype(rc)::value;
+      const double us = read_lane(uu, cs_bitrev4(2 * r));
 #pragma unroll
-          for (int cb = 0; cb < NCB; ++cb) y[ci][e][cb] = fma(us, jr[slot][r][cb], y[ci][e][cb]);
-        }
-      });
+      for (int cb = 0; cb < NCB; ++cb) y[cb] = fma(us, jr[slot][r][cb], y[cb]);
     });
   };
-  // member `mem` takes batches mem, mem + MEM, ...: batch mem + MEM k is of class mem + MEM (k mod G), its local class
-  // k mod G.  NS G batches per trip (every register slot and every local class at a compile-time index); NS - 1
-  // batches in flight behind the one being consumed — the bytes a CU keeps in flight are what bounds this kernel.
+  // NS batches per trip (every register slot at a compile-time index), NS - 1 in flight behind the one being consumed
   {
-    int k = 0;
-    auto bat = [&](int kk) { return mem + MEM * kk; };
+    auto bat = [&](int kk) { return w + CS_NW * kk; };
     static_for<0, NS - 1>([&](auto qc) __attribute__((always_inline)) {
       constexpr int q = decltype(qc)::value;
       if (bat(q) < nbatch) issue(bat(q), std::integral_constant<int, q>{});
     });
-    for (; bat(k) < nbatch; k += NS * G) {
-      static_for<0, NS * G>([&](auto qc) __attribute__((always_inline)) {
+    for (int k = 0; bat(k) < nbatch; k += NS) {
+      static_for<0, NS>([&](auto qc) __attribute__((always_inline)) {
         constexpr int q = decltype(qc)::value;
         const int bi = bat(k + q);
         if (bi < nbatch) {                                 // (uniform)
           if (bat(k + q + NS - 1) < nbatch) issue(bat(k + q + NS - 1), std::integral_constant<int, ((q + NS - 1) % NS)>{});
-          consume(bi, std::integral_constant<int, (q % NS)>{}, std::integral_constant<int, q % G>{});
+          consume(bi, qc);
         }
       });
     }
   }
-  // every wave's class sums to LDS; the problem's sums in class order
-  double* bsh = ysh + (size_t)G * 4 * NEH * NCB * WAVE;
+  // every wave's class sum to LDS; the problem's sums in class order
 #pragma unroll
-  for (int ci = 0; ci < G; ++ci) {
-    const int cls = mem + MEM * ci;
-#pragma unroll
-    for (int e = 0; e < NEH; ++e) {
-#pragma unroll
-      for (int cb = 0; cb < NCB; ++cb) ysh[((((size_t)grp * 4 + cls) * NEH + e) * NCB + cb) * WAVE + lane] = y[ci][e][cb];
-      if (lane == 0) bsh[((size_t)grp * 4 + cls) * NEH + e] = accB[ci][e];
-    }
-  }
+  for (int cb = 0; cb < NCB; ++cb) ysh[((size_t)w * NCB + cb) * WAVE + lane] = y[cb];
   __syncthreads();
-  double* out = cs.part + ((long)li * cs.nchunk + chunk) * csne_part_stride(NE, ld);
-  for (int idx = tid; idx < NE * NCB * WAVE; idx += CS_NT) {
-    const int l = idx % WAVE, cb = (idx / WAVE) % NCB, eg = idx / (WAVE * NCB);
-    const int g = eg / NEH, e = eg % NEH;
-    const double* src = ysh + ((((size_t)g * 4) * NEH + e) * NCB + cb) * WAVE + l;
-    const size_t cs_ = (size_t)NEH * NCB * WAVE;           // class stride
+  double* out = cs.part + ((long)li * cs.nchunk + chunk) * csne_part_stride(1, ld);
+  for (int idx = tid; idx < NCB * WAVE; idx += CS_NT) {   // (idx = the column)
+    const double* src = ysh + idx;
+    constexpr size_t cs_ = (size_t)NCB * WAVE;             // class stride
     const double t = ((src[0] + src[cs_]) + src[2 * cs_]) + src[3 * cs_];
-    const int col = l + 64 * cb;
-    if (col < n) out[(long)eg * ld + col] = t;
-  }
-  if (tid < NE) {
-    const int g = tid / NEH, e = tid % NEH;
-    const double* src = bsh + ((size_t)g * 4) * NEH + e;
-    out[(long)NE * ld + tid] = ((src[0] + src[NEH]) + src[2 * NEH]) + src[3 * NEH];
+    if (idx < n) out[idx] = t;
   }
 }
 
 // ---- the pass over J on the matrix pipe (TRF) ------------------------------------------------------------
-// The kernel above spends most of its issue slots on the 64-lane totals of its dot products (VALU-issue-bound at six
-// evaluations: 1.37 ms against the 0.63 ms the same kernel needs with ONE vector, i.e. the streaming rate).  Here
-// both products of a 16-row tile are small GEMMs on the FP64 MFMA pipe (v_mfma_f64_16x16x4):
+// With the recorded evaluations of a TRF problem the scheme of the kernel above spends most of its issue slots on the
+// 64-lane totals of its dot products (it was VALU-issue-bound at six evaluations: 1.37 ms against the 0.63 ms it needs
+// with ONE vector, i.e. the streaming rate).  Here both products of a 16-row tile are small GEMMs on the FP64 MFMA
+// pipe (v_mfma_f64_16x16x4):
 //   T = J_tile V          V = [d p~_0, d w~_0, d p~_1, ...]: sixteen columns = eight evaluations; the reduction over
 //                         the columns happens inside the instruction;
 //   Y += U^T J_tile       U = T (+ f on the even columns): T lands in the accumulator layout (lane (lr, lc), element g:
@@ -433,7 +360,7 @@ static hipError_t csne_pass_mfma_launch(const CsneState& cs, const double* dvec,
   return hipGetLastError();
 }
 // cs.NE must be CSNE_MAXE (the partial sums carry all eight evaluation slots, whatever the batch's depth)
-hipError_t launch_csne_pass_mfma(const CsneState& cs, const double* dvec, int count, hipStream_t s) {
+hipError_t launch_csne_pass_trf(const CsneState& cs, const double* dvec, int count, hipStream_t s) {
   if (count <= 0) return hipSuccess;
   if (cs.NE != CSNE_MAXE || !dvec) return hipErrorInvalidValue;
   const int nst = (cs.n + 63) / 64;                       // column tiles of sixteen per wave
@@ -443,65 +370,23 @@ hipError_t launch_csne_pass_mfma(const CsneState& cs, const double* dvec, int co
   return hipErrorInvalidValue;
 }
 
-// the split of a launch that carries NE evaluations: (NEH, G) with NEH G >= NE.  Measured (512 problems of 4096 x 256,
-// six evaluations): one group 1.51 ms, two groups of three evaluations 1.66 ms — the kernel is bound by the bytes a CU
-// keeps in flight (four waves x one batch of 8 KB: what the loaded latency lets through), and a row requested by two
-// waves halves the UNIQUE bytes in flight; the split stays in the kernel (G > 1 compiles and is tested through
-// BLSQ_CS_GROUPS builds) but the launch takes G = 1.
-#ifndef BLSQ_CS_GROUPS
-#define BLSQ_CS_GROUPS 1
-#endif
-static void csne_split(int NE, int* neh, int* g) {
-  if (BLSQ_CS_GROUPS == 1 || NE <= 3) { *neh = NE < 1 ? 1 : NE; *g = 1; }
-  else if (NE == 4) { *neh = 2; *g = 2; }
-  else if (NE <= 6) { *neh = 3; *g = 2; }
-  else { *neh = 2; *g = 4; }
-}
-int csne_launch_evals(int NE) { int a, b; csne_split(NE, &a, &b); return a * b; }
-
-#ifndef BLSQ_CS_SLOTS_DEEP
-#define BLSQ_CS_SLOTS_DEEP 4           // evaluations up to which THREE register slots (two batches in flight) fit the registers
-#endif
-template <int NCB, int NEH, int G>
-static hipError_t csne_pass_launch1(const CsneState& cs, const double* dvec, int count, hipStream_t s) {
-  constexpr int NS = (NEH <= BLSQ_CS_SLOTS_DEEP) ? 3 : 2;
-  const size_t lds = sizeof(double) * ((size_t)G * 4 * NEH * NCB * WAVE + (size_t)G * 4 * NEH);
+template <int NCB>
+static hipError_t csne_pass_launch(const CsneState& cs, int count, hipStream_t s) {
+  const size_t lds = sizeof(double) * (size_t)CS_NW * NCB * WAVE;
   static std::atomic<size_t> granted[64];
-  hipError_t ge = gram_grant_lds(csne_pass_kernel<NCB, NEH, G, NS>, lds, granted);
+  hipError_t ge = gram_grant_lds(csne_pass_kernel<NCB>, lds, granted);
   if (ge != hipSuccess) return ge;
-  hipLaunchKernelGGL((csne_pass_kernel<NCB, NEH, G, NS>), dim3(cs.nchunk, count), dim3(CS_NT), lds, s, cs, dvec);
+  hipLaunchKernelGGL((csne_pass_kernel<NCB>), dim3(cs.nchunk, count), dim3(CS_NT), lds, s, cs);
   return hipGetLastError();
 }
-template <int NCB>
-static hipError_t csne_pass_launch(const CsneState& cs, const double* dvec, int count, hipStream_t s) {
-  int neh = 1, g = 1;
-  csne_split(cs.NE, &neh, &g);
-  if (neh * g != cs.NE) return hipErrorInvalidValue;       // (the host sizes the partial sums with csne_launch_evals)
-  if (g == 1) {
-    switch (neh) {
-      case 1: return csne_pass_launch1<NCB, 1, 1>(cs, dvec, count, s);
-      case 2: return csne_pass_launch1<NCB, 2, 1>(cs, dvec, count, s);
-      case 3: return csne_pass_launch1<NCB, 3, 1>(cs, dvec, count, s);
-      case 4: return csne_pass_launch1<NCB, 4, 1>(cs, dvec, count, s);
-      case 5: return csne_pass_launch1<NCB, 5, 1>(cs, dvec, count, s);
-      case 6: return csne_pass_launch1<NCB, 6, 1>(cs, dvec, count, s);
-      case 7: return csne_pass_launch1<NCB, 7, 1>(cs, dvec, count, s);
-      case 8: return csne_pass_launch1<NCB, 8, 1>(cs, dvec, count, s);
-    }
-  }
-#if BLSQ_CS_GROUPS != 1
-  if (g == 2 && neh == 2) return csne_pass_launch1<NCB, 2, 2>(cs, dvec, count, s);
-  if (g == 2 && neh == 3) return csne_pass_launch1<NCB, 3, 2>(cs, dvec, count, s);
-  if (g == 4 && neh == 2) return csne_pass_launch1<NCB, 2, 4>(cs, dvec, count, s);
-#endif
-  return hipErrorInvalidValue;
-}
-hipError_t launch_csne_pass(const CsneState& cs, const double* dvec, int count, hipStream_t s) {
+// cs.NE must be 1 (the partial sums carry the one vector of the plan)
+hipError_t launch_csne_pass_dog(const CsneState& cs, int count, hipStream_t s) {
   if (count <= 0) return hipSuccess;
+  if (cs.NE != 1) return hipErrorInvalidValue;
   const int ncb = (cs.n + 63) / 64;
-  if (ncb <= 2) return csne_pass_launch<2>(cs, dvec, count, s);
-  if (ncb == 3) return csne_pass_launch<3>(cs, dvec, count, s);
-  if (ncb == 4) return csne_pass_launch<4>(cs, dvec, count, s);
+  if (ncb <= 2) return csne_pass_launch<2>(cs, count, s);
+  if (ncb == 3) return csne_pass_launch<3>(cs, count, s);
+  if (ncb == 4) return csne_pass_launch<4>(cs, count, s);
   return hipErrorInvalidValue;
 }
 
@@ -781,7 +666,7 @@ __global__ __launch_bounds__(256) void dog_csne_scatter_kernel(CsneState cs, Dog
   const long vo = (long)b * ld;
   double* rec = cs.rvec + ((long)b * CSNE_MAXE) * 3 * ld;
   const int nf = st.ncols[b] - 1;
-  for (int j = tid; j < n; j += 256) { rec[j] = 0.0; rec[ld + j] = 0.0; }
+  for (int j = tid; j < n; j += 256) rec[j] = 0.0;
   __syncthreads();
   for (int q = tid; q < nf; q += 256) rec[st.free_idx[vo + q]] = st.newton[vo + q];
   if (tid == 0) { cs.ne[b] = 1; cs.ralpha[(long)b * CSNE_MAXE] = 0.0; }

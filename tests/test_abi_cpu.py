@@ -119,7 +119,7 @@ def test_unknown_negative_status_raises_value_error_not_key_error():
     raise_step_errors(np.array([0, 1, 3]))                   # termination codes: nothing raised
 
 
-def test_option_table_is_exactly_the_22_documented_switches():
+def test_option_table_is_exactly_the_21_documented_switches():
     """Every switch of the library's option table (blsq_option_info needs no GPU) appears in INTEGRATION.md with its
     environment variable, and no getenv("BLSQ_...") is left in the sources outside the table and the RCCL loader."""
     import ctypes as C
@@ -140,9 +140,9 @@ def test_option_table_is_exactly_the_22_documented_switches():
     assert lib.blsq_option_info(n, None, None, None, None) != 0
     assert names == {"gram", "cqr2", "csne", "optimistic", "no_svdfree", "svdfree_min_n", "gram_k2_max", "cert0",
                      "cert_direct", "lm_chol_qrpath", "lm_fused", "h2d_pipe", "chol_rl", "gram16", "gram8", "gram_pair",
-                     "gram_tile_groups", "gram_direct_nw", "gram_direct_max_nt", "qr_cqr", "gram1", "csne_mfma"}
-    assert n == len(names) == 22
-    retired = {"publish", "fuse_pack", "publish_ride", "settle0", "chol_reg", "chol_rl2"}
+                     "gram_tile_groups", "gram_direct_nw", "gram_direct_max_nt", "qr_cqr", "gram1"}
+    assert n == len(names) == 21
+    retired = {"publish", "fuse_pack", "publish_ride", "settle0", "chol_reg", "chol_rl2", "csne_mfma"}
     assert not names & retired
     for nm in retired:                                       # (neither key nor environment variable is known)
         assert "`%s`" % nm not in doc and "`BLSQ_%s`" % nm.upper() not in doc, nm

@@ -1,5 +1,5 @@
 #!/bin/bash
-# Instruction-mix and wait counters of the CSNE leg's kernels (csne_pass_kernel in particular):
+# Instruction-mix and wait counters of the CSNE leg's kernels (the TRF pass, csne_pass_mfma_kernel, in particular):
 #   tools/pmc_csne.sh <tag>   -> gpurun_out/<tag>_pmc_csne.txt.  Separate --pmc passes with --kernel-trace only.
 set -o pipefail
 TAG=$1
