@@ -265,6 +265,17 @@ class DogboxStepSolver:
         self.ctx.check(self.lib.blsq_dogbox_debug_cond(self.h, ptr(k2)), "blsq_dogbox_debug_cond")
         return k2
 
+    def debug_fast(self):
+        """1 where the last factor call solved the free block without the Jacobi SVD, 0 where through it."""
+        fl = np.empty(self.B, np.int32)
+        self.ctx.check(self.lib.blsq_dogbox_debug_fast(self.h, ptr(fl)), "blsq_dogbox_debug_fast")
+        return fl
+
+    def debug_sweeps(self):
+        sw = np.empty(self.B, np.int32)
+        self.ctx.check(self.lib.blsq_dogbox_debug_sweeps(self.h, ptr(sw)), "blsq_dogbox_debug_sweeps")
+        return sw
+
     def factor_dev(self, dJ, df, dx, dlb, dub, dscale, don_bound, scale_mode=SCALE_GIVEN):
         self.ctx.check(self.lib.blsq_dogbox_factor_dev(self.h, dJ, df, dx, dlb, dub, dscale,
                                                        int(scale_mode), don_bound),

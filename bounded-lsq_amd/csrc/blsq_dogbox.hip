@@ -468,6 +468,26 @@ extern "C" int blsq_dogbox_debug_cond(blsq_dogbox_plan* p, double* k2) {
   return blsq_sync(ctx);
 }
 
+extern "C" int blsq_dogbox_debug_fast(blsq_dogbox_plan* p, int32_t* fast) {
+  if (!p) return -1;
+  blsq_ctx* ctx = p->ctx;
+  if (!fast) return ctx->bad(2, "fast is NULL");
+  { int rc_ = dog_resolve(p, nullptr); if (rc_) return rc_; }
+  HIPCHK(ctx, hipMemcpyAsync(fast, p->gate_ints.p, sizeof(int) * p->B, hipMemcpyDeviceToHost,
+                             ctx->stream));
+  return blsq_sync(ctx);
+}
+
+extern "C" int blsq_dogbox_debug_sweeps(blsq_dogbox_plan* p, int32_t* sweeps) {
+  if (!p) return -1;
+  blsq_ctx* ctx = p->ctx;
+  if (!sweeps) return ctx->bad(2, "sweeps is NULL");
+  { int rc_ = dog_resolve(p, nullptr); if (rc_) return rc_; }
+  HIPCHK(ctx, hipMemcpyAsync(sweeps, p->sweeps.p, sizeof(int) * p->B, hipMemcpyDeviceToHost,
+                             ctx->stream));
+  return blsq_sync(ctx);
+}
+
 extern "C" int blsq_dogbox_fetch_step(blsq_dogbox_plan* p, double* step, double* x_new,
                                       int64_t* on_bound_new, uint8_t* tr_hit,
                                       double* predicted_reduction, double* step_scaled_norm,

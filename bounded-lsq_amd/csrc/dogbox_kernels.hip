@@ -8,6 +8,8 @@
 //                           dropped, rcond = eps*max(m, n_free))
 //   Js = J_free s      =>   Js.Js = |R s_full|^2 ,  Js.f = (R s_full).c
 // Compiled with -ffp-contract=off: masks use exact == (dogbox.py:29-33).
+#include <atomic>
+
 #include "blsq_device.h"
 #include "blsq_kernels.h"
 
@@ -429,6 +431,17 @@ __global__ __launch_bounds__(DG_NT) void dog_step_kernel(DogState st, const doub
 hipError_t launch_dog_step(const DogState& st, const double* Delta, const DogStepOut& out,
                            hipStream_t s, const PublishArgs* pub) {
   const size_t lds = sizeof(double) * 11 * (size_t)st.ld;
+  if (lds > 64 * 1024) {                    // ld > 744: dynamic LDS above 64 KB has to be granted (88 KB at ld = 1024)
+    static std::atomic<size_t> granted[64];
+    int dev = 0;
+    (void)hipGetDevice(&dev);
+    if (lds > granted[dev & 63].load(std::memory_order_acquire)) {
+      hipError_t ge = hipFuncSetAttribute((const void*)dog_step_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                          (int)lds);
+      if (ge != hipSuccess) return ge;
+      granted[dev & 63].store(lds, std::memory_order_release);
+    }
+  }
   hipLaunchKernelGGL(dog_step_kernel, dim3(st.B), dim3(DG_NT), lds, s, st, Delta, out,
                      pub ? *pub : PublishArgs{nullptr, 0, nullptr, 0});
   return hipGetLastError();

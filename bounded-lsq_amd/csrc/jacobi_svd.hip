@@ -105,8 +105,14 @@ __device__ __forceinline__ int rot_regs(double (&u)[EPL], double (&v)[EPL], RowS
   const float gf = (float)__builtin_amdgcn_ldexp(ag, -ex);
   const float rf = __builtin_amdgcn_sqrtf(fmaf(hf, hf, gf * gf));
   float tf = fabsf(gf) * __builtin_amdgcn_rcpf(fabsf(hf) + rf);
+  // tan below the normal f32 range (|t| < 2^-126): a denormal tf is quantised to multiples of 1.4e-45.  A row that
+  // converges to ZERO (an exactly zero column of the source) gets there after ~8 sweeps; its quantised "rotations"
+  // then overshoot, the row oscillates at ~1e-44 of the largest one and is reported as rotated until max_sweeps.
+  // There |zeta| > 1e37 and tan = 1 / (2 zeta) = g / h to more than double precision.
+  const bool tiny = tf < 1.1754944e-38f;
   if ((h < 0.0) != (ag < 0.0)) tf = -tf;
-  const double t = (double)tf;
+  double t = (double)tf;
+  if (__builtin_expect(tiny, 0)) t = g / h;                 // (rare: kept off the common path)
   const double w = fma(t, t, 1.0);
   const double cs = fast_rsqrt(w);
   const double ics = w * cs;                               // 1 / cs

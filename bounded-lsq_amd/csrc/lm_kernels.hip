@@ -41,6 +41,8 @@ static hipError_t grant_lds(K kernel, size_t bytes, std::atomic<size_t>* granted
   return e;
 }
 
+static constexpr size_t LDS_MAX_BYTES = 160 * 1024;   // LDS of one workgroup (CDNA4)
+
 // (LM_EPS, LM_GATE_MARGIN: blsq_kernels.h)
 
 // (phases and the sc[] / st[] slots: blsq_kernels.h)
@@ -291,7 +293,10 @@ __global__ __launch_bounds__(TRI_NT) void dog_gate_solve_kernel(DogState st, int
 hipError_t launch_dog_gate_solve(const DogState& st, int* fast, int* ncols_jac, int enable,
                                  const int* path, const double* colinfo, int* jac_count,
                                  const int* done, hipStream_t s) {
-  const size_t lds = sizeof(double) * (3 + 32) * (size_t)st.ld;
+  size_t lds = sizeof(double) * (3 + 32) * (size_t)st.ld;
+  // ld > 576 (dogbox alone, n >= 577): the DMA staging of the blocked triangular solves does not fit the 160 KB of a
+  // workgroup.  Such problems take the Jacobi SVD (the gate is off, the staging is neither allocated nor touched).
+  if (lds > LDS_MAX_BYTES) { enable = 0; lds = sizeof(double) * 3 * (size_t)st.ld; }
   { static std::atomic<size_t> granted[64]; hipError_t ge = grant_lds(dog_gate_solve_kernel, lds, granted); if (ge != hipSuccess) return ge; }
   hipLaunchKernelGGL(dog_gate_solve_kernel, dim3(st.B), dim3(TRI_NT), lds, s, st, fast,
                      ncols_jac, enable, path, colinfo, jac_count, done);

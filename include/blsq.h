@@ -143,6 +143,7 @@ int blsq_debug_qr_stamps(void* dbuf);
 /* diagnostics: 1 where the last factor call chose the SVD-free trust-region path
  * (full-rank gate passed), 0 where it went through the Jacobi SVD */
 int blsq_trf_debug_fast(blsq_trf_plan* plan, int32_t* fast /*B*/);
+int blsq_dogbox_debug_fast(blsq_dogbox_plan* plan, int32_t* fast /*B*/);
 
 /* diagnostics: the conditioning certificate of the last factor call, per problem: the PROVEN upper
  * bound K2 >= kappa_2 of the equilibrated system the step is solved from on the normal-equations
@@ -151,8 +152,10 @@ int blsq_trf_debug_fast(blsq_trf_plan* plan, int32_t* fast /*B*/);
 int blsq_trf_debug_cond(blsq_trf_plan* plan, double* k2 /*B*/);
 int blsq_dogbox_debug_cond(blsq_dogbox_plan* plan, double* k2 /*B*/);
 
-/* diagnostics: Jacobi sweeps used by the last factor call, per problem */
+/* diagnostics: Jacobi sweeps used by the last factor call, per problem (dogbox: meaningful where
+ * blsq_dogbox_debug_fast gives 0; the kernel writes 0 for a problem it does not decompose) */
 int blsq_trf_debug_sweeps(blsq_trf_plan* plan, int32_t* sweeps /*B*/);
+int blsq_dogbox_debug_sweeps(blsq_dogbox_plan* plan, int32_t* sweeps /*B*/);
 
 /* --------------------------------------------------------------- dogbox --
  * blsq_dogbox_factor replaces dogbox.py:165-199: gradient, active/free split,

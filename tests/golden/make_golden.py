@@ -428,6 +428,51 @@ def make_dog():
     np.savez_compressed(os.path.join(HERE, "dog_large.npz"), **store)
 
 
+def make_wide():
+    """Tuples at the widths past the normal-equations front end (n = 272 ... 1023), inputs by seed:
+    trf_wide.npz (each shape with a Delta on the reflective branch and one that needs Newton rounds)
+    and dog_wide.npz (each shape with tr_hit = 0 and tr_hit = 1).  The asserts below keep both values
+    of every flag in the files;  `python make_golden.py wide` rebuilds the two alone."""
+    store, names = {}, []
+    flags = set()
+    shapes = [(600, 272), (1000, 320), (1024, 512), (4096, 512), (3000, 400), (300, 400), (512, 512)]
+    # (300 x 400 with seed 505: the reference's own p_h_tr moves by 1.1e-11 under one-ulp changes of J at
+    #  Delta = 10 -- m < n, negative alpha beside a pole of 1 / (s^2 + alpha); seed 525 moves by 1.6e-13)
+    seeds = {(300, 400): 525}
+    for i, (m, n) in enumerate(shapes):
+        for Delta in (10.0, 0.5):
+            seed = seeds.get((m, n), 500 + i)
+            P = _synth.trf_problem(seed, m, n)
+            out = ref_trf_tuple(P["J"], P["f"], P["x"], P["lb"], P["ub"], P["scale"], Delta, 0.0)
+            name = "seed%d_%dx%d_D%g" % (seed, m, n, Delta)
+            pack(name, dict(seed=seed, m=m, n=n, Delta=Delta, alpha0=0.0), out, store)
+            names.append(name)
+            flags.add((out["branch"], min(out["n_iter"], 2)))
+            print("trf", name, "branch", out["branch"], "n_iter", out["n_iter"],
+                  "choice", out["choice"], "to_bound %.3g" % out["to_bound"])
+    assert {b for b, _ in flags} == {0, 1} and any(k >= 2 for _, k in flags), flags
+    store["names"] = np.array(names)
+    np.savez_compressed(os.path.join(HERE, "trf_wide.npz"), **store)
+
+    store, names = {}, []
+    hit = set()
+    for i, (m, n) in enumerate([(1000, 320), (4096, 512), (900, 700), (1024, 1023)]):
+        for Delta in (5e-3, 5e-4):
+            seed = 600 + i
+            P = _synth.dogbox_problem(seed, m, n)
+            out = ref_dog_tuple(P["J"], P["f"], P["x"], P["lb"], P["ub"], P["scale"],
+                                P["on_bound"], Delta)
+            name = "seed%d_%dx%d_D%g" % (seed, m, n, Delta)
+            pack(name, dict(seed=seed, m=m, n=n, Delta=Delta), out, store)
+            names.append(name)
+            hit.add((n, int(out["tr_hit"])))
+            print("dog", name, "n_active", int(out["active_set"].sum()), "tr_hit", int(out["tr_hit"]),
+                  "fallback", int(out["fallback"]), "n_on_bound_new", int(np.abs(out["on_bound_new"]).sum()))
+    assert all((n, t) in hit for n in (320, 512, 700, 1023) for t in (0, 1)), hit
+    store["names"] = np.array(names)
+    np.savez_compressed(os.path.join(HERE, "dog_wide.npz"), **store)
+
+
 def make_dog_fallback():
     """Tuples that reach `if predicted_reduction <= 0` of the reference (dogbox.py:211-216).
 
@@ -795,6 +840,9 @@ def make_suite58():
 if __name__ == "__main__":
     if len(sys.argv) > 1 and sys.argv[1] == "dogfb":
         make_dog_fallback()
+        sys.exit(0)
+    if len(sys.argv) > 1 and sys.argv[1] == "wide":
+        make_wide()
         sys.exit(0)
     if len(sys.argv) > 1 and sys.argv[1] == "choice2":
         make_trf_gradient_winners()

@@ -50,6 +50,32 @@ def draw_case(rng, max_m=3000, log_kappa=(0.0, 4.0)):
     return kind, P, Delta
 
 
+def draw_wide_case(rng, log_kappa=(0.0, 4.0)):
+    """One random batch at the widths past the normal-equations front end: TRF (n = 272 ... 512) with probability
+    0.6, otherwise dogbox (half of them n = 513 ... 1023, where m <= 1024); m near n in a fifth of the n <= 512 cases;
+    then the spectrum, column-scaling and Delta draws of draw_case."""
+    from bounded_lsq import _synth
+    kind = "trf" if rng.random() < 0.6 else "dogbox"
+    n = int(rng.integers(272, 513)) if (kind == "trf" or rng.random() < 0.5) else int(rng.integers(513, 1024))
+    if n > 512:
+        m = int(rng.integers(max(n - 40, 1), 1025))
+    else:
+        m = int(n + rng.integers(-40, 40)) if rng.random() < 0.2 else int(rng.integers(n, 5000))
+    B = int(rng.integers(1, 4))
+    seed = int(rng.integers(1 << 30))
+    P = _synth.dogbox_batch(seed, B, m, n) if kind == "dogbox" else _synth.trf_batch(seed, B, m, n)
+    kappa = 10.0 ** rng.uniform(*log_kappa)
+    if rng.random() < 0.7 and m >= n:                       # prescribed spectrum
+        for b in range(B):
+            U, _ = np.linalg.qr(rng.standard_normal((m, n)))
+            V, _ = np.linalg.qr(rng.standard_normal((n, n)))
+            P["J"][b] = (U * np.logspace(0, -np.log10(kappa), n)) @ V.T * np.sqrt(m)
+    if rng.random() < 0.3:                                  # badly scaled columns
+        P["J"] = P["J"] * 10.0 ** rng.uniform(-3, 3, size=(B, 1, n))
+    Delta = 10.0 ** rng.uniform(-2, 1.5, size=B)
+    return kind, P, Delta
+
+
 def oracle_step(kind, P, b, Delta, J=None):
     J = P["J"][b] if J is None else J
     if kind == "trf":
@@ -76,17 +102,15 @@ def oracle_sensitivity(kind, P, b, Delta, So, mask, rng, trials=3):
     return move, mask_stable
 
 
-def run_sweep(count, seed, ctx, budget_s=None, verbose=False, log_kappa=(0.0, 4.0)):
-    """-> (records, violations).  record = (err, kind, B, m, n, cond, paths, excused)."""
+def run_sweep(count, seed, ctx, verbose=False, log_kappa=(0.0, 4.0), draw=draw_case):
+    """-> (records, violations, paths).  record = (err, kind, B, m, n, cond, paths, excused).  Every machine checks
+    the same `count` batches of generator `draw` (no time budget)."""
     import bounded_lsq as bl
     rng = np.random.default_rng(seed)
     prng = np.random.default_rng(seed + 1)                  # perturbation signs
-    t0 = time.time()
     recs, bad, paths = [], [], [0, 0]
     for case in range(count):
-        if budget_s is not None and time.time() - t0 > budget_s:
-            break
-        kind, P, Delta = draw_case(rng, log_kappa=log_kappa)
+        kind, P, Delta = draw(rng, log_kappa=log_kappa)
         B, m, n = P["J"].shape
         ctx.gram_stats(reset=True)
         if kind == "trf":
@@ -123,16 +147,16 @@ def run_sweep(count, seed, ctx, budget_s=None, verbose=False, log_kappa=(0.0, 4.
 
 
 def test_fuzz_sweep_against_oracle():
-    """~200 random batches (two seeds) inside a time budget, kappa(J) up to 1e4: every problem within
-    1e-10 and bit-exact masks, NO case excused."""
+    """200 random batches (two seeds), kappa(J) up to 1e4: every problem within 1e-10 and bit-exact masks,
+    NO case excused."""
     from bounded_lsq import _abi
     ctx = _abi.Context(0)
     try:
         total = 0
         for seed in (0, 1):
-            recs, bad, paths = run_sweep(100, seed, ctx, budget_s=150)
+            recs, bad, paths = run_sweep(100, seed, ctx)
             assert not bad, bad
-            assert len(recs) >= 60, "time budget cut the sweep too short: %d problems" % len(recs)
+            assert len(recs) >= 60, "the sweep is too short: %d problems" % len(recs)
             total += len(recs)
             assert sum(r[7] for r in recs) == 0, [r for r in recs if r[7]]   # the excuse is not needed here
             assert paths[0] > 0 and paths[1] > 0            # both factorisation paths exercised
@@ -148,9 +172,9 @@ def test_fuzz_sweep_of_ill_conditioned_problems():
     from bounded_lsq import _abi
     ctx = _abi.Context(0)
     try:
-        recs, bad, paths = run_sweep(70, 2, ctx, budget_s=100, log_kappa=(4.0, 8.0))
+        recs, bad, paths = run_sweep(70, 2, ctx, log_kappa=(4.0, 8.0))
         assert not bad, bad
-        assert len(recs) >= 40, "time budget cut the sweep too short: %d problems" % len(recs)
+        assert len(recs) >= 40, "the sweep is too short: %d problems" % len(recs)
         assert paths[1] >= 20                               # (bounded problems pass the gate on their augmented system)
         excused = sum(r[7] for r in recs)
         print("fuzz (ill-conditioned): %d problems, paths (Gram, tree) %s, %d beyond 1e-10 and excused by the "
@@ -160,6 +184,27 @@ def test_fuzz_sweep_of_ill_conditioned_problems():
             if r[7]:                                        # every excused case, by name
                 print("  excused: err %.2e  %s B=%d %dx%d  paths %s" % (r[0], r[1], r[2], r[3], r[4], r[6]))
         assert excused <= 0.05 * len(recs), (excused, len(recs))
+    finally:
+        ctx.close()
+
+
+def test_fuzz_sweep_of_wide_problems():
+    """40 random batches (generator seed 3; 79 problems) at n = 272 ... 1023, kappa(J) up to 1e4, where no problem
+    takes the normal-equations front end: zero violations and NO case excused.  The reference meets that on its own:
+    for exactly these batches the oracle's step moves by at most 8.0e-13 under one-ulp changes of J and no mask
+    changes."""
+    from bounded_lsq import _abi
+    ctx = _abi.Context(0)
+    try:
+        t0 = time.time()
+        recs, bad, paths = run_sweep(40, 3, ctx, draw=draw_wide_case)
+        print("fuzz (wide): %d problems in %.0f s, worst error %.2e"
+              % (len(recs), time.time() - t0, max(r[0] for r in recs)))
+        assert not bad, bad
+        assert len(recs) == 79, len(recs)
+        assert sum(r[7] for r in recs) == 0, [r for r in recs if r[7]]
+        assert paths == [0, 0], paths                       # the front end must not claim these widths
+        assert {r[1] for r in recs} == {"trf", "dogbox"} and max(r[4] for r in recs) > 512
     finally:
         ctx.close()
 

@@ -35,7 +35,8 @@ def bl():
 
 
 TRF_CASES = (load_npz("trf_small.npz") + load_npz("trf_large.npz") +
-             load_npz("trf_choice2.npz"))    # find_gradient_step wins (trf.py:159-170, choice 2)
+             load_npz("trf_choice2.npz") +   # find_gradient_step wins (trf.py:159-170, choice 2)
+             load_npz("trf_wide.npz"))       # n = 272 ... 512: past the normal-equations front end
 
 
 @pytest.fixture(params=["gram_front_end", "qr_tree_only"], autouse=True)
@@ -110,7 +111,8 @@ def test_trf_golden(bl, tr_path, name, ins, out):
 
 
 DOG_CASES = (load_npz("dog_small.npz") + load_npz("dog_large.npz") +
-             load_npz("dog_fallback.npz"))   # dogbox.py:211-216 taken (fallback = 1) + near misses
+             load_npz("dog_fallback.npz") +  # dogbox.py:211-216 taken (fallback = 1) + near misses
+             load_npz("dog_wide.npz"))       # n = 320 ... 1023, both tr_hit values
 
 
 @pytest.mark.parametrize("name,ins,out", DOG_CASES, ids=[c[0] for c in DOG_CASES])
@@ -219,17 +221,36 @@ def test_step_is_repeatable_without_refactor(bl):
 
 
 def test_invalid_arguments_are_reported(bl):
+    """The limits of DESIGN.md ("Limits"), pinned from both sides: n + 1 <= 1024 (one workgroup stages 64 row
+    tiles); n <= 512 when m > 1024 (a TSQR merge stacks at least two triangles of ceil(n/16) tiles) and for every
+    TRF plan (the augmented system [R D; E] has 2 * ceil16(n) rows)."""
     from bounded_lsq import _abi
+    from bounded_lsq._multi import TsqrTrfSolver
     with pytest.raises(_abi.BlsqError):
         bl.TrfStepSolver(0, 10, 2)
     with pytest.raises(_abi.BlsqError):
-        bl.TrfStepSolver(1, 10, 2000)          # n + 1 > 1088
+        bl.TrfStepSolver(1, 10, 2000)          # n + 1 > 1024
     with pytest.raises(_abi.BlsqError):
-        bl.TrfStepSolver(1, 5000, 600)         # tall needs n + 1 <= 544
+        bl.TrfStepSolver(1, 5000, 600)         # m > 1024 needs n <= 512
+    bl.TrfStepSolver(1, 600, 512).close()
+    with pytest.raises(_abi.BlsqError):
+        bl.TrfStepSolver(1, 600, 513)          # 2 * ceil16(513) = 1056 rows of [R D; E]
+    bl.DogboxStepSolver(1, 1024, 1023).close()
+    with pytest.raises(_abi.BlsqError):
+        bl.DogboxStepSolver(1, 1024, 1024)     # n + 1 = 1025
+    for cls in (bl.TrfStepSolver, bl.DogboxStepSolver):
+        cls(1, 1025, 512).close()              # two leaves, one merge of two 32-tile triangles: exactly 64 tiles
+        with pytest.raises(_abi.BlsqError):
+            cls(1, 1025, 513)
+    with pytest.raises(_abi.BlsqError) as exc:
+        TsqrTrfSolver(2500, 513, 2, 0, m_total=5000)
+    assert "invalid argument" in str(exc.value), exc.value
 
 
 @pytest.mark.parametrize("m,n,nranks", [(6000, 40, 4), (3000, 128, 3), (20000, 16, 8),
-                                        (6001, 40, 4), (1003, 24, 3)])      # unequal row blocks
+                                        (6001, 40, 4), (1003, 24, 3),       # unequal row blocks
+                                        # the merge limit: three triangles per workgroup, and two of 32 tiles
+                                        (6000, 320, 4), (5000, 512, 2), (5001, 512, 3)])
 def test_tsqr_row_blocks_single_gpu(bl, m, n, nranks):
     """Row-block TSQR, Householder route, rehearsed on ONE GPU: every 'rank'
     factors its row block, the triangles are stacked in rank order (what the all-gather inside

@@ -58,7 +58,8 @@ def test_helper_sphere_and_quadratic():
 
 
 TRF_CASES = (load_npz("trf_small.npz") + load_npz("trf_large.npz") +
-             load_npz("trf_choice2.npz"))    # find_gradient_step wins (trf.py:159-170, choice 2)
+             load_npz("trf_choice2.npz") +   # find_gradient_step wins (trf.py:159-170, choice 2)
+             load_npz("trf_wide.npz"))       # n = 272 ... 512: past the normal-equations front end
 
 
 @pytest.mark.parametrize("name,ins,out", TRF_CASES, ids=[c[0] for c in TRF_CASES])
@@ -90,7 +91,8 @@ def test_trf_tuple_matches_reference(name, ins, out):
 
 
 DOG_CASES = (load_npz("dog_small.npz") + load_npz("dog_large.npz") +
-             load_npz("dog_fallback.npz"))   # dogbox.py:211-216 taken (fallback = 1) + near misses
+             load_npz("dog_fallback.npz") +  # dogbox.py:211-216 taken (fallback = 1) + near misses
+             load_npz("dog_wide.npz"))       # n = 320 ... 1023, both tr_hit values
 
 
 @pytest.mark.parametrize("name,ins,out", DOG_CASES, ids=[c[0] for c in DOG_CASES])

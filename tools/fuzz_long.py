@@ -8,7 +8,7 @@ count = int(sys.argv[1]) if len(sys.argv) > 1 else 150
 ctx = _abi.Context(0)
 tot_bad = 0
 for seed, lk in ((11, (0.0, 4.0)), (12, (2.0, 6.0)), (13, (4.0, 8.0)), (14, (0.0, 8.0)), (15, (2.5, 5.5))):
-    recs, bad, paths = fz.run_sweep(count, seed, ctx, budget_s=150, verbose=False, log_kappa=lk)
+    recs, bad, paths = fz.run_sweep(count, seed, ctx, verbose=False, log_kappa=lk)
     exc = sum(r[7] for r in recs)
     worst = max([r[0] for r in recs if not r[7]] + [0.0])
     print("seed %d log10 kappa %s: %d problems, paths (Gram, rejected) %s, cqr2 so far %d, csne (routed, delivered, declined) so far %s, "
