@@ -77,6 +77,7 @@ SIGNATURES = {
     "blsq_debug_cqr_stats": (C.c_int, [vp, C.POINTER(C.c_uint64), C.c_int]),
     "blsq_debug_gram_stats": (C.c_int, [vp, C.POINTER(C.c_uint64), C.c_int]),
     "blsq_debug_cqr2_stats": (C.c_int, [vp, C.POINTER(C.c_uint64), C.c_int]),
+    "blsq_debug_gram_route": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, C.c_int, c_int32_p]),
     "blsq_option_count": (C.c_int, []),
     "blsq_option_info": (C.c_int, [C.c_int, C.POINTER(C.c_char_p), C.POINTER(C.c_char_p), C.POINTER(C.c_double),
                                    C.POINTER(C.c_char_p)]),

@@ -342,6 +342,15 @@ extern "C" int blsq_debug_gram_stats(blsq_ctx* ctx, uint64_t* out2, int reset) {
   return 0;
 }
 
+extern "C" int blsq_debug_gram_route(const blsq_ctx* ctx, int m, int n, int B, int has_final, int32_t out[16]) {
+  if (!out || B < 1 || !gram_supported(m, n)) return -1;
+  const int chunks = gram_chunks(m);
+  const GramRoute r = gram_route(m, n, chunks, B, has_final != 0, options_or_default(ctx ? &ctx->opt : nullptr));
+  const int32_t v[16] = {r.family, r.key[0], r.key[1], r.key[2], r.grid[0], r.grid[1], r.grid[2], r.block,
+                         (int32_t)r.lds, r.rhs_valu, r.rows_per_chunk, r.tile_groups, r.fused, chunks, 0, 0};
+  memcpy(out, v, sizeof(v));
+  return 0;
+}
 extern "C" int blsq_debug_csne_stats(blsq_ctx* ctx, uint64_t out[3], int reset) {
   if (!ctx) return -1;
   if (out) { out[0] = ctx->csne_routed; out[1] = ctx->csne_steps; out[2] = ctx->csne_declined; }

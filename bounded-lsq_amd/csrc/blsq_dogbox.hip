@@ -9,26 +9,23 @@ int dog_alloc_state(blsq_dogbox_plan* p) {
   const int B = p->B, ld = p->ld;
   const size_t mat = (size_t)ld * ld;
   const size_t vs = (size_t)B * ld;
-#define ALLOC(buf, bytes)                                               \
-  do {                                                                  \
-    hipError_t e__ = (buf).alloc(bytes);                                \
-    if (e__ != hipSuccess) return ctx->fail(e__, "hipMalloc(" #buf ")"); \
-  } while (0)
-  ALLOC(p->S, sizeof(double) * B * mat);
-  ALLOC(p->X, sizeof(double) * B * mat);
-  ALLOC(p->vecs, sizeof(double) * vs * 10);
-  ALLOC(p->ivecs, sizeof(int) * (vs + B));
-  ALLOC(p->scal2, sizeof(double) * (size_t)B * 4);
-  ALLOC(p->sweeps, sizeof(int) * (size_t)B);
-  ALLOC(p->active, vs);
-  ALLOC(p->onb, sizeof(long long) * vs);
-  ALLOC(p->o_vec, sizeof(double) * vs * 2);
-  ALLOC(p->o_onb, sizeof(long long) * vs);
-  ALLOC(p->o_scal, sizeof(double) * (size_t)B * 4);
-  ALLOC(p->o_info, sizeof(int) * (size_t)B * 4);
-  ALLOC(p->in_scal, sizeof(double) * (size_t)B);
-  ALLOC(p->gate_ints, sizeof(int) * 3 * (size_t)B);
-  ALLOC(p->colinfo, sizeof(double) * 2 * (size_t)B);
+  if (int rc_ = alloc_all(ctx, {
+          {&p->S, sizeof(double) * B * mat, "hipMalloc(p->S)"},
+          {&p->X, sizeof(double) * B * mat, "hipMalloc(p->X)"},
+          {&p->vecs, sizeof(double) * vs * 10, "hipMalloc(p->vecs)"},
+          {&p->ivecs, sizeof(int) * (vs + B), "hipMalloc(p->ivecs)"},
+          {&p->scal2, sizeof(double) * (size_t)B * 4, "hipMalloc(p->scal2)"},
+          {&p->sweeps, sizeof(int) * (size_t)B, "hipMalloc(p->sweeps)"},
+          {&p->active, vs, "hipMalloc(p->active)"},
+          {&p->onb, sizeof(long long) * vs, "hipMalloc(p->onb)"},
+          {&p->o_vec, sizeof(double) * vs * 2, "hipMalloc(p->o_vec)"},
+          {&p->o_onb, sizeof(long long) * vs, "hipMalloc(p->o_onb)"},
+          {&p->o_scal, sizeof(double) * (size_t)B * 4, "hipMalloc(p->o_scal)"},
+          {&p->o_info, sizeof(int) * (size_t)B * 4, "hipMalloc(p->o_info)"},
+          {&p->in_scal, sizeof(double) * (size_t)B, "hipMalloc(p->in_scal)"},
+          {&p->gate_ints, sizeof(int) * 3 * (size_t)B, "hipMalloc(p->gate_ints)"},
+          {&p->colinfo, sizeof(double) * 2 * (size_t)B, "hipMalloc(p->colinfo)"},
+      })) return rc_;
   p->svdfree_enable = ctx->opt.i(OPT_NO_SVDFREE) == 1 ? 0 : 1;
   if (p->tree.gram && csne_supported(p->m, p->n) && ctx->opt.on(OPT_CSNE) && p->svdfree_enable) {
     int rc = p->csne.build(ctx, B, p->m, p->n, ld, /*with_hp=*/false);
@@ -54,7 +51,6 @@ int dog_alloc_state(blsq_dogbox_plan* p) {
   p->out.on_bound_new = p->o_onb.as<long long>();
   p->out.scal = p->o_scal.as<double>(); p->out.info = p->o_info.as<int>();
   return 0;
-#undef ALLOC
 }
 
 int dog_put(blsq_dogbox_plan* p, const double* x, const double* lb, const double* ub,
@@ -84,7 +80,6 @@ int dog_put(blsq_dogbox_plan* p, const double* x, const double* lb, const double
 // the free-column QR (Householder-path problems), rank gate + Newton step, SVD for the rest
 int dog_finish(blsq_dogbox_plan* p, const int* path, bool any_qr, bool any_gram, const int* done = nullptr) {
   blsq_ctx* ctx = p->ctx;
-  hipError_t e;
   if (any_qr) {
     QrArgs q = p->tree.base_args();
     q.A = p->st.S; q.strideA = (long)p->ld * p->ld; q.ldA = p->ld; q.rowsA = p->n;
@@ -92,21 +87,20 @@ int dog_finish(blsq_dogbox_plan* p, const int* path, bool any_qr, bool any_gram,
     q.require_path = path;
     q.rows_per_leaf = p->ld; q.RP = p->ld;
     q.Rout = p->st.X;
-    ctx->begin(K_QR_AUG);
-    e = launch_qr(q, 1, p->B, ctx->stream);
-    ctx->end();
-    if (e != hipSuccess) return ctx->fail(e, "launch_qr(free block)");
+    if (int rc_ = ctx->run(K_QR_AUG, "launch_qr(free block)", [&] {
+          return launch_qr(q, 1, p->B, ctx->stream);
+        })) return rc_;
   }
   int* gfast = p->gate_ints.as<int>();
   int* gmask = gfast + p->B;
   p->st.fast = gfast;
   if (!p->gate_done) {
-    ctx->begin(K_LM_GATE);
     // (done: problems whose steps stand already — the CSNE tier's corrected ones when the finish runs a second time)
-    e = launch_dog_gate_solve(p->st, gfast, gmask, p->svdfree_enable, path,
-                              (path && any_gram) ? p->colinfo.as<double>() : nullptr, nullptr, done, ctx->stream);
-    ctx->end();
-    if (e != hipSuccess) return ctx->fail(e, "launch_dog_gate_solve");
+    if (int rc_ = ctx->run(K_LM_GATE, "launch_dog_gate_solve", [&] {
+          return launch_dog_gate_solve(p->st, gfast, gmask, p->svdfree_enable, path,
+                                       (path && any_gram) ? p->colinfo.as<double>() : nullptr, nullptr, done,
+                                       ctx->stream);
+        })) return rc_;
     p->njac = -1;
   }
   p->gate_done = false;
@@ -115,15 +109,11 @@ int dog_finish(blsq_dogbox_plan* p, const int* path, bool any_qr, bool any_gram,
     ja.X = p->st.X; ja.strideX = (long)p->ld * p->ld; ja.ld = p->ld; ja.ncols_dev = gmask;
     ja.N = p->n + 1; ja.s = p->st.s; ja.uf = p->st.uf; ja.srange = p->st.srange;
     ja.sweeps = p->sweeps.as<int>(); ja.max_sweeps = 40;
-    ctx->begin(K_JACOBI);
-    e = launch_jacobi(ja, p->B, ctx->stream);
-    ctx->end();
-    if (e != hipSuccess) return ctx->fail(e, "launch_jacobi");
+    if (int rc_ = ctx->run(K_JACOBI, "launch_jacobi", [&] { return launch_jacobi(ja, p->B, ctx->stream); })) return rc_;
   }
-  ctx->begin(K_STEP);
-  e = launch_dog_solve(p->st, gfast, ctx->stream);
-  ctx->end();
-  if (e != hipSuccess) return ctx->fail(e, "launch_dog_solve");
+  if (int rc_ = ctx->run(K_STEP, "launch_dog_solve", [&] {
+        return launch_dog_solve(p->st, gfast, ctx->stream);
+      })) return rc_;
   return 0;
 }
 
@@ -133,10 +123,9 @@ int dog_after_triangle(blsq_dogbox_plan* p, int scale_mode) {
   p->st.Rt = p->tree.Rfinal(); p->st.Gk = nullptr; p->st.path = nullptr;
   p->tree.path_valid = false; p->tree.any_gram = false; p->tree.any_qr = true;
   p->gate_done = false;
-  ctx->begin(K_PREP);
-  hipError_t e = launch_dog_prep(p->st, scale_mode, 0, nullptr, 0, ctx->stream);
-  ctx->end();
-  if (e != hipSuccess) return ctx->fail(e, "launch_dog_prep");
+  if (int rc_ = ctx->run(K_PREP, "launch_dog_prep", [&] {
+        return launch_dog_prep(p->st, scale_mode, 0, nullptr, 0, ctx->stream);
+      })) return rc_;
   return dog_finish(p, nullptr, true, false);
 }
 
@@ -170,18 +159,17 @@ GramCholArgs dog_chol_args(blsq_dogbox_plan* p, const int* mask) {
 int dog_gate_tail(blsq_dogbox_plan* p, const GramCholArgs& c) {
   blsq_ctx* ctx = p->ctx;
   QrTree& t = p->tree;
-  ctx->begin(K_GRAM_GATE);
-  hipError_t e = launch_gram_gate(c, p->B, ctx->stream);
-  if (e == hipSuccess) e = launch_gram_cert_shift(c, p->B, ctx->stream);
-  ctx->end();
-  if (e != hipSuccess) return ctx->fail(e, "launch_gram_gate");
+  if (int rc_ = ctx->run(K_GRAM_GATE, "launch_gram_gate", [&] {
+        const hipError_t e = launch_gram_gate(c, p->B, ctx->stream);
+        return e == hipSuccess ? launch_gram_cert_shift(c, p->B, ctx->stream) : e;
+      })) return rc_;
   int* gfast = p->gate_ints.as<int>();
   p->st.fast = gfast;
-  ctx->begin(K_LM_GATE);
-  e = launch_dog_gate_solve(p->st, gfast, gfast + p->B, p->svdfree_enable, t.path_rw(),
-                            p->colinfo.as<double>(), t.fb_count() + 1, c.dog.g ? c.dog.done : nullptr, ctx->stream);
-  ctx->end();
-  if (e != hipSuccess) return ctx->fail(e, "launch_dog_gate_solve");
+  if (int rc_ = ctx->run(K_LM_GATE, "launch_dog_gate_solve", [&] {
+        return launch_dog_gate_solve(p->st, gfast, gfast + p->B, p->svdfree_enable, t.path_rw(),
+                                     p->colinfo.as<double>(), t.fb_count() + 1, c.dog.g ? c.dog.done : nullptr,
+                                     ctx->stream);
+      })) return rc_;
   return 0;
 }
 
@@ -214,15 +202,13 @@ int dog_csne_correct(blsq_dogbox_plan* p, const double* dJ, const double* df, in
   cs.J = dJ; cs.strideJ = (long)p->m * ldJ; cs.ldJ = ldJ; cs.F = df; cs.strideF = p->m;
   { int rc_ = tier.grow_part(ctx, (size_t)tier.count * cs.nchunk * ((size_t)cs.NE * p->ld + 16)); if (rc_) return rc_; }
   HIPCHK(ctx, hipMemsetAsync(cs.counts + 1, 0, sizeof(int), ctx->stream));
-  ctx->begin(K_CSNE_PASS);
-  hipError_t e = launch_dog_csne_scatter(cs, p->st, tier.count, ctx->stream);
-  if (e == hipSuccess) e = launch_csne_pass_dog(cs, tier.count, ctx->stream);
-  ctx->end();
-  if (e != hipSuccess) return ctx->fail(e, "launch_csne_pass_dog");
-  ctx->begin(K_CSNE_FIX);
-  e = launch_dog_csne_fix(cs, p->st, tier.count, ctx->stream);
-  ctx->end();
-  if (e != hipSuccess) return ctx->fail(e, "launch_dog_csne_fix");
+  if (int rc_ = ctx->run(K_CSNE_PASS, "launch_csne_pass_dog", [&] {
+        const hipError_t e = launch_dog_csne_scatter(cs, p->st, tier.count, ctx->stream);
+        return e == hipSuccess ? launch_csne_pass_dog(cs, tier.count, ctx->stream) : e;
+      })) return rc_;
+  if (int rc_ = ctx->run(K_CSNE_FIX, "launch_dog_csne_fix", [&] {
+        return launch_dog_csne_fix(cs, p->st, tier.count, ctx->stream);
+      })) return rc_;
   HIPCHK(ctx, hipMemcpyAsync(ctx->pinned + 12, cs.counts + 1, sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
   HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
   *nfail = ctx->pinned[12];
@@ -249,10 +235,9 @@ int dog_repair(blsq_dogbox_plan* p, const double* dJ, const double* df, int ldJ,
   for (int pass = 0; pass < 2; ++pass) {
     if (nfb > 0) {
       if ((rc = t.run_fallback(ctx, dJ, df, ldJ, nfb))) return rc;
-      ctx->begin(K_PREP);
-      hipError_t e = launch_dog_prep(p->st, scale_mode, 0, t.fb_mask(), 1, ctx->stream);
-      ctx->end();
-      if (e != hipSuccess) return ctx->fail(e, "launch_dog_prep(redo)");
+      if (int rc_ = ctx->run(K_PREP, "launch_dog_prep(redo)", [&] {
+            return launch_dog_prep(p->st, scale_mode, 0, t.fb_mask(), 1, ctx->stream);
+          })) return rc_;
     }
     if ((rc = dog_finish(p, t.path_rw(), t.any_qr, t.any_gram, pass > 0 && p->csne.on ? p->csne.cs.flag : nullptr))) return rc;
     int nfail = 0;
@@ -285,15 +270,13 @@ int dog_factor_core(blsq_dogbox_plan* p, const double* dJ, const double* df, int
   p->st.Rt = t.Rfinal(); p->st.Gk = t.gram_keep.as<double>(); p->st.path = t.path_rw();
   const PackVecs* pk = nullptr;
   { int rc_ = take_pack(p, mask, &pk); if (rc_) return rc_; }
-  ctx->begin(K_PREP);
-  hipError_t e = launch_dog_prep(p->st, scale_mode, 1, mask, 0, ctx->stream, pk);
-  ctx->end();
-  if (e != hipSuccess) return ctx->fail(e, "launch_dog_prep(gram)");
+  if (int rc_ = ctx->run(K_PREP, "launch_dog_prep(gram)", [&] {
+        return launch_dog_prep(p->st, scale_mode, 1, mask, 0, ctx->stream, pk);
+      })) return rc_;
   const GramCholArgs c = dog_chol_args(p, mask);
-  ctx->begin(K_AUG_CHOL);
-  e = launch_gram_chol(c, p->B, ctx->stream);
-  ctx->end();
-  if (e != hipSuccess) return ctx->fail(e, "launch_gram_chol(free block)");
+  if (int rc_ = ctx->run(K_AUG_CHOL, "launch_gram_chol(free block)", [&] {
+        return launch_gram_chol(c, p->B, ctx->stream);
+      })) return rc_;
   const bool defer = may_defer && !mask && verdict_may_guess(p) && p->svdfree_enable && p->pend_pin;
   // second guess (N <= 80): the Cholesky kernel settles EVERY problem itself, as it did in the last call —
   // then the certificate, gate and solve launches would all be empty and are not enqueued at all
@@ -400,14 +383,13 @@ extern "C" int blsq_dogbox_step_dev(blsq_dogbox_plan* p, const double* dDelta) {
   if (!dDelta) return ctx->bad(2, "Delta is NULL");
   HIPCHK(ctx, hipSetDevice(ctx->device));
   for (int pass = 0; pass < 2; ++pass) {    // (pass 1 only after a wrong optimistic guess)
-    ctx->begin(K_STEP);
     const PublishArgs pub = verdict_rides(p);
-    hipError_t e = launch_dog_step(p->st, dDelta, p->out, ctx->stream, &pub);
-    ctx->end();
-    if (e != hipSuccess) return ctx->fail(e, "launch_dog_step");
-    bool redo = false;
-    int rc = dog_resolve(p, &redo);
+    int rc = ctx->run(K_STEP, "launch_dog_step", [&] {
+      return launch_dog_step(p->st, dDelta, p->out, ctx->stream, &pub);
+    });
     if (rc) return rc;
+    bool redo = false;
+    if ((rc = dog_resolve(p, &redo))) return rc;
     if (!redo) break;
   }
   return 0;

@@ -31,8 +31,8 @@ int QrTree::build(blsq_ctx* ctx, int B_, int rows, int n_, size_t extra_rp_rows)
     if (qr_staged_tiles(L.RP, first ? 0 : NPAD, N) > QR_MAX_TILES)
       return ctx->bad(3, "leaf does not fit LDS");
     L.LDP = 0;
-    hipError_t e = L.R.alloc(sizeof(double) * (size_t)B * L.nleaf * NPAD * NPAD);
-    if (e != hipSuccess) return ctx->fail(e, "hipMalloc(R level)");
+    if (int rc_ = alloc_all(ctx, {{&L.R, sizeof(double) * (size_t)B * L.nleaf * NPAD * NPAD, "hipMalloc(R level)"}}))
+      return rc_;
     max_slot_rows = std::max(max_slot_rows, (size_t)B * L.nleaf * L.RP);
     max_slots = std::max(max_slots, (size_t)B * L.nleaf);
     levels.push_back(L);
@@ -40,32 +40,26 @@ int QrTree::build(blsq_ctx* ctx, int B_, int rows, int n_, size_t extra_rp_rows)
     cur_rows = L.nleaf * NPAD;
     first = false;
   }
-  hipError_t e = V.alloc(sizeof(double) * max_slot_rows * NP * 16);
-  if (e != hipSuccess) return ctx->fail(e, "hipMalloc(V scratch)");
-  e = T.alloc(sizeof(double) * max_slots * NP * 256);
-  if (e != hipSuccess) return ctx->fail(e, "hipMalloc(T scratch)");
+  if (int rc_ = alloc_all(ctx, {{&V, sizeof(double) * max_slot_rows * NP * 16, "hipMalloc(V scratch)"},
+                                {&T, sizeof(double) * max_slots * NP * 256, "hipMalloc(T scratch)"}}))
+    return rc_;
   gram = gram_supported(rows, n) && ctx->opt.on(OPT_GRAM);
   if (gram) {
-    gram_nchunk = gram_chunks(B, rows);
-    if (gram_nchunk > 1) {
-      e = gram_part.alloc(sizeof(double) * (size_t)B * gram_nchunk * NPAD * NPAD);
-      if (e != hipSuccess) return ctx->fail(e, "hipMalloc(partial Grams)");
-    }
-    e = gram_dsc.alloc(sizeof(double) * (size_t)B * NPAD);
-    if (e != hipSuccess) return ctx->fail(e, "hipMalloc(Gram scales)");
-    e = gram_keep.alloc(sizeof(double) * (size_t)B * NPAD * NPAD);
-    if (e != hipSuccess) return ctx->fail(e, "hipMalloc(Grams)");
-    e = gram_rinv.alloc(sizeof(double) * (size_t)B * NP * 256);
-    if (e != hipSuccess) return ctx->fail(e, "hipMalloc(Gram tile inverses)");
-    e = gram_ywork.alloc(sizeof(double) * (size_t)B * NPAD * NPAD);
-    if (e != hipSuccess) return ctx->fail(e, "hipMalloc(Gram gate work)");
-    e = gram_k2.alloc(sizeof(double) * (size_t)B);
-    if (e != hipSuccess) return ctx->fail(e, "hipMalloc(Gram gate bound)");
-    e = gram_cert.alloc(sizeof(int) * (size_t)B);
-    if (e != hipSuccess) return ctx->fail(e, "hipMalloc(Gram certificate flags)");
-    e = gram_cflag.alloc(sizeof(int) * (size_t)B);
-    if (e == hipSuccess) e = gram_ctau.alloc(sizeof(double) * (size_t)B);
-    if (e == hipSuccess) e = hipMemsetAsync(gram_cflag.p, 0, gram_cflag.bytes, ctx->stream);
+    gram_nchunk = gram_chunks(rows);
+    const size_t tri = sizeof(double) * (size_t)B * NPAD * NPAD;
+    if (int rc_ = alloc_all(ctx, {
+            {&gram_part, gram_nchunk > 1 ? tri * gram_nchunk : 0, "hipMalloc(partial Grams)"},
+            {&gram_dsc, sizeof(double) * (size_t)B * NPAD, "hipMalloc(Gram scales)"},
+            {&gram_keep, tri, "hipMalloc(Grams)"},
+            {&gram_rinv, sizeof(double) * (size_t)B * NP * 256, "hipMalloc(Gram tile inverses)"},
+            {&gram_ywork, tri, "hipMalloc(Gram gate work)"},
+            {&gram_k2, sizeof(double) * (size_t)B, "hipMalloc(Gram gate bound)"},
+            {&gram_cert, sizeof(int) * (size_t)B, "hipMalloc(Gram certificate flags)"},
+            {&gram_cflag, sizeof(int) * (size_t)B, "hipMalloc(certificate stage 3)"},
+            {&gram_ctau, sizeof(double) * (size_t)B, "hipMalloc(certificate stage 3)"},
+            {&gram_ints, sizeof(int) * (3 * (size_t)B + 4), "hipMalloc(Gram mask)"},   // launch mask, count, path, list
+        })) return rc_;
+    hipError_t e = hipMemsetAsync(gram_cflag.p, 0, gram_cflag.bytes, ctx->stream);
     if (e != hipSuccess) return ctx->fail(e, "hipMalloc(certificate stage 3)");
     k2_max = gram_k2_max(rows, ctx->opt.d(OPT_GRAM_K2_MAX));
     cqr2 = cqr2_supported(rows, n) && ctx->opt.on(OPT_CQR2);
@@ -73,8 +67,6 @@ int QrTree::build(blsq_ctx* ctx, int B_, int rows, int n_, size_t extra_rp_rows)
     if (e != hipSuccess) return ctx->fail(e, "hipMemsetAsync(Gram certificate flags)");
     e = hipMemsetAsync(gram_k2.p, 0, gram_k2.bytes, ctx->stream);
     if (e != hipSuccess) return ctx->fail(e, "hipMemsetAsync(Gram gate bound)");
-    e = gram_ints.alloc(sizeof(int) * (3 * (size_t)B + 4));     // launch mask, count, path, fallback list
-    if (e != hipSuccess) return ctx->fail(e, "hipMalloc(Gram mask)");
     e = hipMemsetAsync(gram_keep.p, 0, gram_keep.bytes, ctx->stream);      // (lower tiles are never written)
     if (e != hipSuccess) return ctx->fail(e, "hipMemsetAsync(Grams)");
     e = hipMemsetAsync(gram_ints.p, 0xFF, gram_ints.bytes, ctx->stream);   // path: all QR until factored
@@ -95,13 +87,12 @@ void QrTree::release() {
 hipError_t QrTree::gram_sum(blsq_ctx* ctx, GramArgs g, double* Gp, double* Gout, int count, const int* red_mask,
                             int red_count) {
   g.G = gram_nchunk > 1 ? Gp : Gout;
-  ctx->begin(K_GRAM);
-  bool fused = false;
-  hipError_t e = launch_gram(g, gram_nchunk, count, ctx->stream, Gout, &fused);
-  if (e == hipSuccess && gram_nchunk > 1 && !fused)
-    e = launch_gram_reduce(Gp, gram_nchunk, NPAD, Gout, red_mask, red_count, ctx->stream);
-  ctx->end();
-  return e;
+  return ctx->timed(K_GRAM, [&] {
+    bool fused = false;
+    const hipError_t e = launch_gram(g, gram_nchunk, count, ctx->stream, Gout, &fused);
+    if (e != hipSuccess || gram_nchunk == 1 || fused) return e;
+    return launch_gram_reduce(Gp, gram_nchunk, NPAD, Gout, red_mask, red_count, ctx->stream);
+  });
 }
 
 int QrTree::run_gram(blsq_ctx* ctx, const double* dJ, const double* df, int ldJ, const int* mask,
@@ -120,15 +111,13 @@ int QrTree::run_gram(blsq_ctx* ctx, const double* dJ, const double* df, int ldJ,
   c.rinv = gram_rinv.as<double>(); c.ywork = gram_ywork.as<double>(); c.k2_out = gram_k2.as<double>();
   c.k2_max = k2_max; c.pivot_floor = 1.0 / k2_max;
   c.cert_flag = gram_cflag.as<int>(); c.cert_tau = gram_ctau.as<double>();
-  ctx->begin(K_GRAM_CHOL);
-  hipError_t e = launch_gram_chol(c, B, ctx->stream);
-  ctx->end();
-  if (e != hipSuccess) return ctx->fail(e, "launch_gram_chol");
-  ctx->begin(K_GRAM_GATE);
-  e = launch_gram_gate(c, B, ctx->stream);
-  if (e == hipSuccess) e = launch_gram_cert_shift(c, B, ctx->stream);
-  ctx->end();
-  if (e != hipSuccess) return ctx->fail(e, "launch_gram_gate");
+  if (int rc_ = ctx->run(K_GRAM_CHOL, "launch_gram_chol", [&] {
+        return launch_gram_chol(c, B, ctx->stream);
+      })) return rc_;
+  if (int rc_ = ctx->run(K_GRAM_GATE, "launch_gram_gate", [&] {
+        const hipError_t e = launch_gram_gate(c, B, ctx->stream);
+        return e == hipSuccess ? launch_gram_cert_shift(c, B, ctx->stream) : e;
+      })) return rc_;
   HIPCHK(ctx, hipMemcpyAsync(ctx->pinned + 1, cnt, sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
   HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
   *nfallback = ctx->pinned[1];
@@ -171,10 +160,9 @@ int QrTree::run_levels(blsq_ctx* ctx, const double* dJ, const double* df, int ld
     }
     q.rows_per_leaf = L.rows_per_leaf; q.RP = L.RP; q.LDP = L.LDP;
     q.Rout = L.R.as<double>();
-    ctx->begin(l == 0 ? K_QR_LEAF : K_QR_MERGE);
-    hipError_t e = launch_qr(q, L.nleaf, list ? count : B, ctx->stream);
-    ctx->end();
-    if (e != hipSuccess) return ctx->fail(e, "launch_qr");
+    if (int rc_ = ctx->run(l == 0 ? K_QR_LEAF : K_QR_MERGE, "launch_qr", [&] {
+          return launch_qr(q, L.nleaf, list ? count : B, ctx->stream);
+        })) return rc_;
   }
   return 0;
 }
@@ -227,10 +215,9 @@ int QrTree::run_fallback(blsq_ctx* ctx, const double* dJ, const double* df, int 
   c.batch_list = fb_list(); c.fb_mask = piv1; c.fail_count = cnt;
   c.dsc = gram_dsc.as<double>(); c.rinv = gram_rinv.as<double>(); c.ywork = gram_ywork.as<double>();
   c.k2_max = 1e300; c.pivot_floor = 1e-14;
-  ctx->begin(K_GRAM_CHOL);
-  e = launch_gram_chol(c, nfb, ctx->stream);
-  ctx->end();
-  if (e != hipSuccess) return ctx->fail(e, "launch_gram_chol(cqr2 first factor)");
+  if (int rc_ = ctx->run(K_GRAM_CHOL, "launch_gram_chol(cqr2 first factor)", [&] {
+        return launch_gram_chol(c, nfb, ctx->stream);
+      })) return rc_;
   // 2. Y = R1'^-T by the certificate's kernel, which also bounds kappa_2 of the equilibrated plain Gram: the
   //    second pass multiplies by the EXPLICIT inverse, whose error enters the triangle as eps kappa(J) (measured:
   //    step error 2e-18 kappa, tools/cqr2_check.py), so the tier takes a problem only if that PROVEN bound is
@@ -240,21 +227,19 @@ int QrTree::run_fallback(blsq_ctx* ctx, const double* dJ, const double* df, int 
   // (the bound on the PLAIN equilibrated Gram also bounds the augmented system's — its spectrum lies inside,
   //  chol_rl.hip — so it replaces the missing / larger bound of a rejected problem: the rank gate uses it)
   cy.k2_out = gram_k2.as<double>();
-  ctx->begin(K_GRAM_GATE);
-  e = launch_gram_gate(cy, B, ctx->stream);
-  ctx->end();
-  if (e != hipSuccess) return ctx->fail(e, "launch_gram_gate(cqr2 inverse)");
+  if (int rc_ = ctx->run(K_GRAM_GATE, "launch_gram_gate(cqr2 inverse)", [&] {
+        return launch_gram_gate(cy, B, ctx->stream);
+      })) return rc_;
   // 3. z = R^-1 c, launch mask;  4. W = J R^-1, w_f = f - J z
   Cqr2Args q{};
   q.J = dJ; q.strideJ = (long)m * ldJ; q.ldJ = ldJ; q.F = df; q.strideF = m;
   q.m = m; q.n = n; q.NPAD = NPAD; q.list = fb_list(); q.run = runm;
   q.Y = gram_ywork.as<double>(); q.dsc = gram_dsc.as<double>(); q.R1 = R1; q.z = cq_z.as<double>();
   q.Wj = cq_W.as<double>(); q.strideW = (long)m * n; q.Wf = cq_Wf.as<double>(); q.strideWf = m;
-  ctx->begin(K_CQR2_APPLY);
-  e = launch_cqr2_prep(q, nfb, piv1, runm, ctx->stream);
-  if (e == hipSuccess) e = launch_cqr2_apply(q, nfb, ctx->stream);
-  ctx->end();
-  if (e != hipSuccess) return ctx->fail(e, "launch_cqr2_apply");
+  if (int rc_ = ctx->run(K_CQR2_APPLY, "launch_cqr2_apply", [&] {
+        const hipError_t ep = launch_cqr2_prep(q, nfb, piv1, runm, ctx->stream);
+        return ep == hipSuccess ? launch_cqr2_apply(q, nfb, ctx->stream) : ep;
+      })) return rc_;
   // 5. G2 = [W w_f]^T [W w_f]  (the launch over the list, the reduction over the run mask)
   GramArgs g{};
   g.opt = opt;
@@ -270,15 +255,14 @@ int QrTree::run_fallback(blsq_ctx* ctx, const double* dJ, const double* df, int 
   c2.Gsrc = G2; c2.G = cq_R2.as<double>(); c2.NPAD = NPAD; c2.n = n;
   c2.batch_list = fb_list(); c2.mask = runm; c2.fb_mask = piv2; c2.fail_count = cnt + 1;
   c2.k2_max = 1e300; c2.pivot_floor = 0.25;           // (G2 ~ I: a pivot below 1/2 means the first pass failed)
-  ctx->begin(K_GRAM_CHOL);
-  e = launch_gram_chol(c2, nfb, ctx->stream);
-  ctx->end();
-  if (e != hipSuccess) return ctx->fail(e, "launch_gram_chol(cqr2 second factor)");
+  if (int rc_ = ctx->run(K_GRAM_CHOL, "launch_gram_chol(cqr2 second factor)", [&] {
+        return launch_gram_chol(c2, nfb, ctx->stream);
+      })) return rc_;
   // 7. acceptance + R~ = R2 [R c; 0 1] into the triangle slot;  8. the tree for what is left
-  ctx->begin(K_CQR2_COMBINE);
-  e = launch_cqr2_combine(q, nfb, runm, piv2, G2, cq_R2.as<double>(), Rf, tmask, ctx->cq_accept_dev, ctx->stream);
-  ctx->end();
-  if (e != hipSuccess) return ctx->fail(e, "launch_cqr2_combine");
+  if (int rc_ = ctx->run(K_CQR2_COMBINE, "launch_cqr2_combine", [&] {
+        return launch_cqr2_combine(q, nfb, runm, piv2, G2, cq_R2.as<double>(), Rf, tmask, ctx->cq_accept_dev,
+            ctx->stream);
+      })) return rc_;
   return run_levels(ctx, dJ, df, ldJ, tmask, fb_list(), nfb);
 }
 
@@ -309,13 +293,14 @@ int QrTree::run(blsq_ctx* ctx, const double* dJ, const double* df, int ldJ, cons
 // ---- CSNE tier ------------------------------------------------------------------------------------
 
 int CsneTier::build(blsq_ctx* ctx, int B, int m, int n, int ld, bool with_hp) {
-  hipError_t e = ints.alloc(sizeof(int) * (5 * (size_t)B + 8));
-  if (e == hipSuccess) e = pmin.alloc(sizeof(double) * (size_t)B);
-  if (e == hipSuccess) e = eta.alloc(sizeof(double) * (size_t)B);
-  if (e == hipSuccess) e = k2.alloc(sizeof(double) * (size_t)B);
-  if (e == hipSuccess) e = alpha.alloc(sizeof(double) * (size_t)B * CSNE_MAXE);
-  if (e == hipSuccess && with_hp) e = hp.alloc(sizeof(double) * (size_t)B * ld);
-  if (e != hipSuccess) return ctx->fail(e, "hipMalloc(CSNE state)");
+  const char* what = "hipMalloc(CSNE state)";
+  if (int rc_ = alloc_all(ctx, {{&ints, sizeof(int) * (5 * (size_t)B + 8), what},
+                                {&pmin, sizeof(double) * (size_t)B, what},
+                                {&eta, sizeof(double) * (size_t)B, what},
+                                {&k2, sizeof(double) * (size_t)B, what},
+                                {&alpha, sizeof(double) * (size_t)B * CSNE_MAXE, what},
+                                {&hp, with_hp ? sizeof(double) * (size_t)B * ld : 0, what}}))
+    return rc_;
   for (DevBuf* b : {&ints, &pmin, &eta, &k2}) HIPCHK(ctx, hipMemsetAsync(b->p, 0, b->bytes, ctx->stream));
   cs.B = B; cs.m = m; cs.n = n; cs.ld = ld;
   int* ii = ints.as<int>();
@@ -347,8 +332,10 @@ int CsneTier::grow_part(blsq_ctx* ctx, size_t need) {
   if (need <= part_cap) return 0;
   part.release();
   const size_t cap = std::max(need, 2 * part_cap);
-  hipError_t e = part.alloc(sizeof(double) * cap);
-  if (e != hipSuccess) { part_cap = 0; return ctx->fail(e, "hipMalloc(CSNE partial sums)"); }
+  if (int rc_ = alloc_all(ctx, {{&part, sizeof(double) * cap, "hipMalloc(CSNE partial sums)"}})) {
+    part_cap = 0;
+    return rc_;
+  }
   part_cap = cap;
   cs.part = part.as<double>();
   return 0;
@@ -385,11 +372,10 @@ int CsneTier::select(blsq_ctx* ctx, QrTree& t, const GramCholArgs& chol, int nfb
   cy.lmfin = GramCholArgs::LmFinish{}; cy.dog = GramCholArgs::DogFinish{};
   cy.lam_out = nullptr; cy.hmax = nullptr; cy.colinfo = nullptr; cy.pmin_out = nullptr;
   cy.k2_max = CSNE_K2_MAX; cy.k2_out = k2.as<double>();
-  ctx->begin(K_GRAM_GATE);
-  hipError_t e = launch_gram_gate(cy, B, ctx->stream);
-  ctx->end();
-  if (e != hipSuccess) return ctx->fail(e, "launch_gram_gate(csne bound)");
-  e = launch_select(sel);
+  if (int rc_ = ctx->run(K_GRAM_GATE, "launch_gram_gate(csne bound)", [&] {
+        return launch_gram_gate(cy, B, ctx->stream);
+      })) return rc_;
+  const hipError_t e = launch_select(sel);
   if (e != hipSuccess) return ctx->fail(e, "launch_csne_select");
   // two counters to the host: the problems left for the tree, the problems on the tier
   HIPCHK(ctx, hipMemcpyAsync(ctx->pinned + 8, t.fb_count(), sizeof(int), hipMemcpyDeviceToHost, ctx->stream));

@@ -129,6 +129,20 @@ struct blsq_ctx {
     timing_open = false;
     hipEventRecord(pending.back().b, stream);
   }
+  // The launches of a slot: begin(slot), f() — a callable that launches and returns hipError_t —, end()
+  template <class F>
+  hipError_t timed(int slot, F&& f) {
+    begin(slot);
+    const hipError_t e = f();
+    end();
+    return e;
+  }
+  // ... and 0, or the failure recorded under `name` (what an entry point returns)
+  template <class F>
+  int run(int slot, const char* name, F&& f) {
+    const hipError_t e = timed(slot, f);
+    return e == hipSuccess ? 0 : fail(e, name);
+  }
   void collect() {                  // after a stream sync
     for (auto& p : pending) {
       float ms = 0.f;
@@ -224,6 +238,16 @@ struct DevBuf {
   void release() { if (p) hipFree(p); p = nullptr; }
   template <class T> T* as() const { return reinterpret_cast<T*>(p); }
 };
+
+// The buffers of a list, allocated in turn; 0, or the first failure recorded under its `what`
+struct AllocReq { DevBuf* buf; size_t bytes; const char* what; };
+inline int alloc_all(blsq_ctx* ctx, std::initializer_list<AllocReq> reqs) {
+  for (const AllocReq& r : reqs) {
+    const hipError_t e = r.buf->alloc(r.bytes);
+    if (e != hipSuccess) return ctx->fail(e, r.what);
+  }
+  return 0;
+}
 
 // One level of the TSQR tree: nleaf workgroups per problem.
 struct Level {

@@ -187,7 +187,23 @@ constexpr double GRAM_CERT_PIVOT_FLOOR = 1.0e-9;
 // DESIGN.md 3.0 was calibrated at m = 4096 (a = 46.7) and the gate is tightened by a(4096) / a(m) beyond.
 double gram_k2_max(long long m_total, double tighter = 0.0);   // tighter > 0: the gate if it is below the calibrated one
 bool gram_supported(int m, int n);
-int gram_chunks(int B, int m);
+int gram_chunks(int m);
+// What launch_gram does with a problem shape, decided before anything is launched (a pure host function: no device, no
+// runtime call).  A problem's summation order — and so every bit of its Gram — follows from the family, its key,
+// rows_per_chunk and rhs_valu; none of them may depend on B.
+enum GramFamily { GRAM_DIRECT = 0, GRAM_8, GRAM_1, GRAM_16, GRAM_GENERIC };
+struct GramRoute {
+  int family;             // GramFamily
+  int key[3];             // template instance: direct NTT, RHS, NWD; gram8 RHS; gram16 RHS, PAIR; generic SLOTS, NCB
+  int grid[3], block;
+  size_t lds;             // dynamic LDS bytes
+  int rhs_valu;           // J^T f / f^T f beside the tiles (n a multiple of 16)
+  int rows_per_chunk;
+  int tile_groups;        // workgroups a row chunk's tiles are split over (generic; 1 elsewhere)
+  int fused;              // gram16 PAIR: both row chunks by one workgroup, summed into the final slot (no reduction)
+  int tile_wgs;           // gram1: workgroups of the tile part of one (row chunk, problem) pair
+};
+GramRoute gram_route(int m, int n, int chunks, int B, bool has_final, const Options& opt);
 // Gfinal / fused (optional): where the reduced Gram belongs; *fused = true means the launch produced it
 // there itself (two chunks summed in the kernel) and launch_gram_reduce must not follow
 hipError_t launch_gram(const GramArgs& a, int chunks, int B, hipStream_t s, double* Gfinal = nullptr,

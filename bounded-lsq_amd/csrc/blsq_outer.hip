@@ -160,20 +160,17 @@ namespace blsq_host {
 // robust loss: J <- diag(w) J and the scaled f of the problems selected by `mask` (nullptr: all)
 static int outer_loss_scale(blsq_outer* o, const int* mask) {
   blsq_ctx* ctx = o->ctx;
-  ctx->begin(K_LOSS_SCALE);
-  hipError_t e = launch_loss_scale(o->B, o->m, o->n, o->loss, o->fscale.as<double>(), o->st.f, o->J.as<double>(),
-                                   o->fsc.as<double>(), mask, ctx->stream);
-  ctx->end();
-  return e == hipSuccess ? 0 : ctx->fail(e, "launch_loss_scale");
+  return ctx->run(K_LOSS_SCALE, "launch_loss_scale", [&] {
+    return launch_loss_scale(o->B, o->m, o->n, o->loss, o->fscale.as<double>(), o->st.f, o->J.as<double>(),
+                             o->fsc.as<double>(), mask, ctx->stream);
+  });
 }
 // robust loss: the objective of every problem at `f` into st.lobj
 static int outer_loss_cost(blsq_outer* o, const double* f) {
   blsq_ctx* ctx = o->ctx;
-  ctx->begin(K_LOSS_COST);
-  hipError_t e = launch_loss_cost(o->B, o->m, o->loss, o->fscale.as<double>(), f, o->lobj.as<double>(), nullptr,
-                                  ctx->stream);
-  ctx->end();
-  return e == hipSuccess ? 0 : ctx->fail(e, "launch_loss_cost");
+  return ctx->run(K_LOSS_COST, "launch_loss_cost", [&] {
+    return launch_loss_cost(o->B, o->m, o->loss, o->fscale.as<double>(), f, o->lobj.as<double>(), nullptr, ctx->stream);
+  });
 }
 // factor the problems selected by `mask` (nullptr: all) from the driver's J / f buffers (the scaled f with a loss)
 int outer_factor(blsq_outer* o, int scale_mode, const int* mask) {
@@ -297,10 +294,9 @@ extern "C" int blsq_loss_cost_dev(blsq_ctx* ctx, int B, int m, int loss, const d
   if (!df) return ctx->bad(6, "f is NULL");
   if (!dobj) return ctx->bad(7, "obj is NULL");
   HIPCHK(ctx, hipSetDevice(ctx->device));
-  ctx->begin(K_LOSS_COST);
-  hipError_t e = launch_loss_cost(B, m, loss, df_scale, df, dobj, dmask, ctx->stream);
-  ctx->end();
-  if (e != hipSuccess) return ctx->fail(e, "launch_loss_cost");
+  if (int rc_ = ctx->run(K_LOSS_COST, "launch_loss_cost", [&] {
+        return launch_loss_cost(B, m, loss, df_scale, df, dobj, dmask, ctx->stream);
+      })) return rc_;
   return 0;
 }
 
@@ -316,10 +312,9 @@ extern "C" int blsq_loss_scale_dev(blsq_ctx* ctx, int B, int m, int n, int loss,
   if (!dJ_io) return ctx->bad(8, "J is NULL");
   if (!df_scaled) return ctx->bad(9, "f_scaled is NULL");
   HIPCHK(ctx, hipSetDevice(ctx->device));
-  ctx->begin(K_LOSS_SCALE);
-  hipError_t e = launch_loss_scale(B, m, n, loss, df_scale, df, dJ_io, df_scaled, dmask, ctx->stream);
-  ctx->end();
-  if (e != hipSuccess) return ctx->fail(e, "launch_loss_scale");
+  if (int rc_ = ctx->run(K_LOSS_SCALE, "launch_loss_scale", [&] {
+        return launch_loss_scale(B, m, n, loss, df_scale, df, dJ_io, df_scaled, dmask, ctx->stream);
+      })) return rc_;
   return 0;
 }
 

@@ -9,21 +9,18 @@ int trf_alloc_state(blsq_trf_plan* p) {
   blsq_ctx* ctx = p->ctx;
   const int B = p->B, ld = p->ld;
   const size_t mat = (size_t)ld * ld;
-#define ALLOC(buf, bytes)                                               \
-  do {                                                                  \
-    hipError_t e__ = (buf).alloc(bytes);                                \
-    if (e__ != hipSuccess) return ctx->fail(e__, "hipMalloc(" #buf ")"); \
-  } while (0)
-  ALLOC(p->X, sizeof(double) * B * mat);
-  ALLOC(p->vecs, sizeof(double) * (size_t)B * ld * 13);
-  ALLOC(p->scal2, sizeof(double) * (size_t)B * 8);
-  ALLOC(p->sweeps, sizeof(int) * (size_t)B);
-  ALLOC(p->o_vec, sizeof(double) * (size_t)B * ld * 4);
-  ALLOC(p->o_hits, sizeof(long long) * (size_t)B * ld);
-  ALLOC(p->o_act, sizeof(long long) * (size_t)B * ld);
-  ALLOC(p->o_scal, sizeof(double) * (size_t)B * 8);
-  ALLOC(p->o_info, sizeof(int) * (size_t)B * 4);
-  ALLOC(p->in_scal, sizeof(double) * (size_t)B * 2);
+  if (int rc_ = alloc_all(ctx, {
+          {&p->X, sizeof(double) * B * mat, "hipMalloc(p->X)"},
+          {&p->vecs, sizeof(double) * (size_t)B * ld * 13, "hipMalloc(p->vecs)"},
+          {&p->scal2, sizeof(double) * (size_t)B * 8, "hipMalloc(p->scal2)"},
+          {&p->sweeps, sizeof(int) * (size_t)B, "hipMalloc(p->sweeps)"},
+          {&p->o_vec, sizeof(double) * (size_t)B * ld * 4, "hipMalloc(p->o_vec)"},
+          {&p->o_hits, sizeof(long long) * (size_t)B * ld, "hipMalloc(p->o_hits)"},
+          {&p->o_act, sizeof(long long) * (size_t)B * ld, "hipMalloc(p->o_act)"},
+          {&p->o_scal, sizeof(double) * (size_t)B * 8, "hipMalloc(p->o_scal)"},
+          {&p->o_info, sizeof(int) * (size_t)B * 4, "hipMalloc(p->o_info)"},
+          {&p->in_scal, sizeof(double) * (size_t)B * 2, "hipMalloc(p->in_scal)"},
+      })) return rc_;
   HIPCHK(ctx, hipMemsetAsync(p->vecs.p, 0, p->vecs.bytes, ctx->stream));
   double* v = p->vecs.as<double>();
   const size_t vs = (size_t)B * ld;
@@ -43,18 +40,20 @@ int trf_alloc_state(blsq_trf_plan* p) {
   p->out.active_new = p->o_act.as<long long>();
   p->out.scal = p->o_scal.as<double>();
   p->out.info = p->o_info.as<int>();
-  ALLOC(p->lm_sa, sizeof(double) * (size_t)B);
-  ALLOC(p->lm_Xa, sizeof(double) * B * mat);
-  ALLOC(p->lm_ints, sizeof(int) * ((size_t)B * 9 + 16));
-  ALLOC(p->aug_colinfo, sizeof(double) * (size_t)B * 2);
-  ALLOC(p->aug_hmax, sizeof(double) * (size_t)B);
-  ALLOC(p->aug_lam, sizeof(double) * (size_t)B);
-  ALLOC(p->aug_ym, sizeof(double) * (size_t)B);
-  ALLOC(p->aug_r1, sizeof(double) * (size_t)B);
-  ALLOC(p->aug_open, sizeof(double) * (size_t)B);
-  ALLOC(p->aug_mask, sizeof(int) * (size_t)B);
-  ALLOC(p->lm_sc, sizeof(double) * (size_t)B * 16);
-  ALLOC(p->lm_ph, sizeof(double) * vs);
+  if (int rc_ = alloc_all(ctx, {
+          {&p->lm_sa, sizeof(double) * (size_t)B, "hipMalloc(p->lm_sa)"},
+          {&p->lm_Xa, sizeof(double) * B * mat, "hipMalloc(p->lm_Xa)"},
+          {&p->lm_ints, sizeof(int) * ((size_t)B * 9 + 16), "hipMalloc(p->lm_ints)"},
+          {&p->aug_colinfo, sizeof(double) * (size_t)B * 2, "hipMalloc(p->aug_colinfo)"},
+          {&p->aug_hmax, sizeof(double) * (size_t)B, "hipMalloc(p->aug_hmax)"},
+          {&p->aug_lam, sizeof(double) * (size_t)B, "hipMalloc(p->aug_lam)"},
+          {&p->aug_ym, sizeof(double) * (size_t)B, "hipMalloc(p->aug_ym)"},
+          {&p->aug_r1, sizeof(double) * (size_t)B, "hipMalloc(p->aug_r1)"},
+          {&p->aug_open, sizeof(double) * (size_t)B, "hipMalloc(p->aug_open)"},
+          {&p->aug_mask, sizeof(int) * (size_t)B, "hipMalloc(p->aug_mask)"},
+          {&p->lm_sc, sizeof(double) * (size_t)B * 16, "hipMalloc(p->lm_sc)"},
+          {&p->lm_ph, sizeof(double) * vs, "hipMalloc(p->lm_ph)"},
+      })) return rc_;
   HIPCHK(ctx, hipMemsetAsync(p->lm_sa.p, 0, p->lm_sa.bytes, ctx->stream));
   HIPCHK(ctx, hipMemsetAsync(p->aug_ym.p, 0, p->aug_ym.bytes, ctx->stream));
   HIPCHK(ctx, hipMemsetAsync(p->aug_open.p, 0, p->aug_open.bytes, ctx->stream));
@@ -95,7 +94,6 @@ int trf_alloc_state(blsq_trf_plan* p) {
   if (aug_rows(p->n) > RMAX) return ctx->bad(4, "n too large for the augmented system (n <= 512)");
   p->aug_LDP = 0;
   return 0;
-#undef ALLOC
 }
 
 // ---- after the front end --------------------------------------------------------------------------
@@ -109,14 +107,12 @@ int trf_alloc_state(blsq_trf_plan* p) {
 //                        again from its triangle (trf_fallback_stage).
 int trf_finish(blsq_trf_plan* p) {
   blsq_ctx* ctx = p->ctx;
-  hipError_t e;
   if (p->use_qr || p->njac != 0 || !p->gate_done) p->x_dirty = true;   // (a stacked QR or a Jacobi launch may follow)
   if (p->use_qr) {
     // E = 0 (unbounded problems): [R D | c] is the triangle already — written by a copy, masked out of the QR
-    ctx->begin(K_QR_AUG);
-    e = launch_trf_aug_trivial(p->st, p->path, p->aug_mask.as<int>(), nullptr, ctx->stream);
-    ctx->end();
-    if (e != hipSuccess) return ctx->fail(e, "launch_trf_aug_trivial");
+    if (int rc_ = ctx->run(K_QR_AUG, "launch_trf_aug_trivial", [&] {
+          return launch_trf_aug_trivial(p->st, p->path, p->aug_mask.as<int>(), nullptr, ctx->stream);
+        })) return rc_;
     QrArgs q = p->tree.base_args();
     q.ncols_dev = p->aug_mask.as<int>();
     // source = R read in place, columns scaled by d on the fly, on top of the VIRTUAL block
@@ -129,18 +125,14 @@ int trf_finish(blsq_trf_plan* p) {
     q.rows_per_leaf = p->aug_RP; q.RP = p->aug_RP; q.LDP = p->aug_LDP;
     q.Rout = p->st.X;
     q.stack_rows = aug_block_rows(p->n); // [R D; E]: two upper-triangular blocks
-    ctx->begin(K_QR_AUG);
-    e = launch_qr(q, 1, p->B, ctx->stream);
-    ctx->end();
-    if (e != hipSuccess) return ctx->fail(e, "launch_qr(aug)");
+    if (int rc_ = ctx->run(K_QR_AUG, "launch_qr(aug)", [&] { return launch_qr(q, 1, p->B, ctx->stream); })) return rc_;
   }
   // rank gate: clearly full-rank problems skip the SVD (lm_kernels.hip)
   if (!p->gate_done) {
     p->lm.jac_count = nullptr;
-    ctx->begin(K_LM_GATE);
-    e = launch_lm_gate(p->lm, p->lm_gate_mask, ctx->stream);
-    ctx->end();
-    if (e != hipSuccess) return ctx->fail(e, "launch_lm_gate");
+    if (int rc_ = ctx->run(K_LM_GATE, "launch_lm_gate", [&] {
+          return launch_lm_gate(p->lm, p->lm_gate_mask, ctx->stream);
+        })) return rc_;
     p->njac = -1;
   }
   p->gate_done = false;
@@ -149,10 +141,7 @@ int trf_finish(blsq_trf_plan* p) {
   ja.X = p->st.X; ja.strideX = (long)p->ld * p->ld; ja.ld = p->ld; ja.ncols_dev = p->lm.ncols_jac;
   ja.N = p->n + 1; ja.s = p->st.s; ja.uf = p->st.uf; ja.srange = p->st.srange;
   ja.sweeps = p->sweeps.as<int>(); ja.max_sweeps = 40;
-  ctx->begin(K_JACOBI);
-  e = launch_jacobi(ja, p->B, ctx->stream);
-  ctx->end();
-  if (e != hipSuccess) return ctx->fail(e, "launch_jacobi");
+  if (int rc_ = ctx->run(K_JACOBI, "launch_jacobi", [&] { return launch_jacobi(ja, p->B, ctx->stream); })) return rc_;
   return 0;
 }
 
@@ -165,10 +154,9 @@ int trf_after_triangle(blsq_trf_plan* p, const double* Rt, int scale_mode, int r
   p->lm.path = nullptr; p->lm.colinfo = nullptr; p->lm.hmax = nullptr; p->lm.k2 = nullptr; p->gram_valid = false;
   p->tree.path_valid = false; p->tree.any_gram = false; p->tree.any_qr = true;
   p->gate_done = false;
-  ctx->begin(K_PREP);
-  hipError_t e = launch_trf_prep(p->st, scale_mode, 0, nullptr, redo, ctx->stream);
-  ctx->end();
-  if (e != hipSuccess) return ctx->fail(e, "launch_trf_prep");
+  if (int rc_ = ctx->run(K_PREP, "launch_trf_prep", [&] {
+        return launch_trf_prep(p->st, scale_mode, 0, nullptr, redo, ctx->stream);
+      })) return rc_;
   return trf_finish(p);
 }
 
@@ -206,11 +194,10 @@ GramCholArgs trf_chol_args(blsq_trf_plan* p, const int* mask) {
 int trf_gate_tail(blsq_trf_plan* p, const GramCholArgs& c, bool full = true) {
   blsq_ctx* ctx = p->ctx;
   QrTree& t = p->tree;
-  ctx->begin(K_GRAM_GATE);
-  hipError_t e = launch_gram_gate(c, p->B, ctx->stream);
-  if (e == hipSuccess) e = launch_gram_cert_shift(c, p->B, ctx->stream);
-  ctx->end();
-  if (e != hipSuccess) return ctx->fail(e, "launch_gram_gate");
+  if (int rc_ = ctx->run(K_GRAM_GATE, "launch_gram_gate", [&] {
+        const hipError_t e = launch_gram_gate(c, p->B, ctx->stream);
+        return e == hipSuccess ? launch_gram_cert_shift(c, p->B, ctx->stream) : e;
+      })) return rc_;
   // The rank gate runs BEFORE the verdict is read back: in the common case (no problem leaves this
   // path) its result stands, and the same read-back tells whether anybody needs the Jacobi SVD at all.
   p->lm.path = t.path_rw();
@@ -220,12 +207,10 @@ int trf_gate_tail(blsq_trf_plan* p, const GramCholArgs& c, bool full = true) {
   //  is gated by trf_finish afterwards — estimating the rank of its abandoned factor here cost the latency of one
   //  problem's inverse iteration for nothing; such a problem counts as "needs the SVD" until then, which the verdict
   //  logic ignores whenever a problem left the path)
-  ctx->begin(K_LM_GATE);
   //  (`full`: every problem is refreshed by this call — a masked call keeps the others' state as it is)
-  e = launch_lm_gate(p->lm, full ? (p->lm_gate_mask & 2) : p->lm_gate_mask, ctx->stream);
-  ctx->end();
-  if (e != hipSuccess) return ctx->fail(e, "launch_lm_gate");
-  return 0;
+  return ctx->run(K_LM_GATE, "launch_lm_gate", [&] {
+    return launch_lm_gate(p->lm, full ? (p->lm_gate_mask & 2) : p->lm_gate_mask, ctx->stream);
+  });
 }
 
 // prep from the Gram, Cholesky of H with the pivot gate, conditioning gate; *nfb = problems of this
@@ -238,17 +223,15 @@ int trf_gram_stage(blsq_trf_plan* p, int scale_mode, const int* mask, int* nfb, 
   p->st.Rt = t.Rfinal(); p->st.Gk = t.gram_keep.as<double>(); p->st.path = t.path_rw();
   const PackVecs* pk = nullptr;
   { int rc_ = take_pack(p, mask, &pk); if (rc_) return rc_; }
-  ctx->begin(K_PREP);
-  hipError_t e = launch_trf_prep(p->st, scale_mode, 1, mask, 0, ctx->stream, pk);
-  ctx->end();
-  if (e != hipSuccess) return ctx->fail(e, "launch_trf_prep(gram)");
+  if (int rc_ = ctx->run(K_PREP, "launch_trf_prep(gram)", [&] {
+        return launch_trf_prep(p->st, scale_mode, 1, mask, 0, ctx->stream, pk);
+      })) return rc_;
   GramCholArgs c = trf_chol_args(p, mask);
   c.skip_zero = p->x_dirty ? 0 : 1;
   if (!mask) p->x_dirty = false;                        // (every slot is rewritten, zeros included, by this launch)
-  ctx->begin(K_AUG_CHOL);
-  e = launch_gram_chol(c, p->B, ctx->stream);
-  ctx->end();
-  if (e != hipSuccess) return ctx->fail(e, "launch_gram_chol(aug)");
+  if (int rc_ = ctx->run(K_AUG_CHOL, "launch_gram_chol(aug)", [&] {
+        return launch_gram_chol(c, p->B, ctx->stream);
+      })) return rc_;
   // second guess (N <= 80): the Cholesky kernel settles EVERY problem itself — certificate by its first
   // bound, rank gate by the column-norm bound — as it did in the last call: then the certificate and gate
   // launches would both be empty and are not enqueued (trf_resolve checks the settled counter)
@@ -261,10 +244,9 @@ int trf_gram_stage(blsq_trf_plan* p, int scale_mode, const int* mask, int* nfb, 
     p->lm.path = t.path_rw();
     p->lm.colinfo = p->aug_colinfo.as<double>();
     if (p->ld > 80) {
-      ctx->begin(K_GRAM_GATE);
-      e = launch_gram_gate(c, p->B, ctx->stream, /*stage0_only=*/true);
-      ctx->end();
-      if (e != hipSuccess) return ctx->fail(e, "launch_gram_gate(stage 0)");
+      if (int rc_ = ctx->run(K_GRAM_GATE, "launch_gram_gate(stage 0)", [&] {
+            return launch_gram_gate(c, p->B, ctx->stream, /*stage0_only=*/true);
+          })) return rc_;
     }
   } else if ((rc = trf_gate_tail(p, c, mask == nullptr))) return rc;
   if (defer) {                              // the counters travel; the verdict is read by trf_resolve
@@ -334,10 +316,9 @@ int trf_fallback_stage(blsq_trf_plan* p, const double* dJ, const double* df, int
   }
   rc = p->tree.run_fallback(ctx, dJ, df, ldJ, nfb);
   if (rc) return rc;
-  ctx->begin(K_PREP);
-  hipError_t e = launch_trf_prep(p->st, scale_mode, 0, p->tree.fb_mask(), 1, ctx->stream);
-  ctx->end();
-  if (e != hipSuccess) return ctx->fail(e, "launch_trf_prep(redo)");
+  if (int rc_ = ctx->run(K_PREP, "launch_trf_prep(redo)", [&] {
+        return launch_trf_prep(p->st, scale_mode, 0, p->tree.fb_mask(), 1, ctx->stream);
+      })) return rc_;
   return 0;
 }
 
@@ -411,10 +392,9 @@ int trf_lm_rounds(blsq_trf_plan* p, const double* dDelta, const double* dalpha_i
       c.Gsrc = p->tree.gram_keep.as<double>(); c.NPAD = p->ld; c.n = p->n;
       c.colscale = p->st.d; c.diag_vec = p->st.ediag; c.stride_vec = p->ld;
       c.rinv = p->tree.gram_rinv.as<double>(); c.dsc = p->tree.gram_dsc.as<double>();
-      ctx->begin(K_LM_CHOL);
-      e = launch_lm_rounds_reg(c, p->lm, dDelta, dalpha_in, ctx->stream);
-      ctx->end();
-      if (e != hipSuccess) return ctx->fail(e, "launch_lm_rounds_reg");
+      if (int rc_ = ctx->run(K_LM_CHOL, "launch_lm_rounds_reg", [&] {
+            return launch_lm_rounds_reg(c, p->lm, dDelta, dalpha_in, ctx->stream);
+          })) return rc_;
       if (!p->use_qr) return 0;
       p->lm.fused_gram = 1;
     }
@@ -425,10 +405,9 @@ int trf_lm_rounds(blsq_trf_plan* p, const double* dDelta, const double* dalpha_i
   int ride_rounds = 0;                                   // rounds [0, ride_rounds) are enqueued before their counter is read
   if (!p->lm_counts_clean) HIPCHK(ctx, hipMemsetAsync(counts, 0, 16 * sizeof(int), ctx->stream));
   p->lm_counts_clean = false;
-  ctx->begin(K_LM_SOLVE);
-  e = launch_lm_start(p->lm, dDelta, dalpha_in, ctx->stream);
-  ctx->end();
-  if (e != hipSuccess) return ctx->fail(e, "launch_lm_start");
+  if (int rc_ = ctx->run(K_LM_SOLVE, "launch_lm_start", [&] {
+        return launch_lm_start(p->lm, dDelta, dalpha_in, ctx->stream);
+      })) return rc_;
   auto read_back = [&](int r) -> hipError_t {            // counter of round r -> pin[r]
     // (a round that is enqueued ahead of its counter takes the counter along: lm_update_kernel of that round stores it)
     if (ride_rounds > r) { rides[r] = true; return hipSuccess; }
@@ -446,10 +425,7 @@ int trf_lm_rounds(blsq_trf_plan* p, const double* dDelta, const double* dalpha_i
     c.qr_mask = p->lm.hmax ? p->lm.ncols_lm : nullptr;
     c.count_dev = count_dev;
     c.skip_zero = 1;                                    // (lm_Xa: zeroed at allocation, read by lm_update's solves only)
-    ctx->begin(K_LM_CHOL);
-    hipError_t ee = launch_gram_chol(c, grid, ctx->stream);
-    ctx->end();
-    return ee;
+    return ctx->timed(K_LM_CHOL, [&] { return launch_gram_chol(c, grid, ctx->stream); });
   };
   // the stacked QR of [R_aug; sqrt(alpha) I] for the problems of the round whose mask says so (LmState::ncols_lm)
   auto qr_round = [&](int round, int grid, const int* count_dev) -> hipError_t {
@@ -464,10 +440,7 @@ int trf_lm_rounds(blsq_trf_plan* p, const double* dDelta, const double* dalpha_i
     q.rows_per_leaf = p->aug_RP; q.RP = p->aug_RP; q.LDP = p->aug_LDP;
     q.Rout = p->lm.Xa;
     q.stack_rows = aug_block_rows(p->n);
-    ctx->begin(K_LM_QR);
-    hipError_t ee = launch_qr(q, 1, grid, ctx->stream);
-    ctx->end();
-    return ee;
+    return ctx->timed(K_LM_QR, [&] { return launch_qr(q, 1, grid, ctx->stream); });
   };
   const bool chol_any = p->gram_valid && p->lm_enable && (p->use_chol || p->lm.hmax != nullptr) &&
                         !(p->lm.fused_gram && !p->lm.hmax);
@@ -498,15 +471,13 @@ int trf_lm_rounds(blsq_trf_plan* p, const double* dDelta, const double* dalpha_i
         e = qr_round(round, bound, counts + round);
         if (e != hipSuccess) return ctx->fail(e, "launch_qr(lm)");
       }
-      ctx->begin(K_LM_SOLVE);
       p->lm.round = round;
       if (rides[round]) {
         pin_seq[round] = ++ctx->pub_seq;
         p->lm.pub = PublishArgs{counts + round, 1, pin + 4 * round, pin_seq[round]};
       }
-      e = launch_lm_update(p->lm, bound, ctx->stream);
+      e = ctx->timed(K_LM_SOLVE, [&] { return launch_lm_update(p->lm, bound, ctx->stream); });
       p->lm.pub = PublishArgs{nullptr, 0, nullptr, 0};
-      ctx->end();
       if (e != hipSuccess) return ctx->fail(e, "launch_lm_update");
       HIPCHK(ctx, read_back(round + 1));
       if (ahead) {
@@ -531,11 +502,10 @@ int trf_lm_rounds(blsq_trf_plan* p, const double* dDelta, const double* dalpha_i
       e = qr_round(round, active, nullptr);
       if (e != hipSuccess) return ctx->fail(e, "launch_qr(lm)");
     }
-    ctx->begin(K_LM_SOLVE);
     p->lm.round = round;
-    e = launch_lm_update(p->lm, active, ctx->stream);
-    ctx->end();
-    if (e != hipSuccess) return ctx->fail(e, "launch_lm_update");
+    if (int rc_ = ctx->run(K_LM_SOLVE, "launch_lm_update", [&] {
+          return launch_lm_update(p->lm, active, ctx->stream);
+        })) return rc_;
     HIPCHK(ctx, read_back(round + 1));
     HIPCHK(ctx, landed(round + 1));
     active = pin[4 * (round + 1)];
@@ -552,14 +522,12 @@ int trf_csne_correct(blsq_trf_plan* p, const double* dDelta, const double* dalph
   CsneState& cs = tier.cs;
   { int rc_ = tier.grow_part(ctx, (size_t)tier.count * cs.nchunk * ((size_t)cs.NE * p->ld + 16)); if (rc_) return rc_; }
   HIPCHK(ctx, hipMemsetAsync(cs.counts + 1, 0, sizeof(int), ctx->stream));
-  ctx->begin(K_CSNE_PASS);
-  hipError_t e = launch_csne_pass_trf(cs, p->st.d, tier.count, ctx->stream);
-  ctx->end();
-  if (e != hipSuccess) return ctx->fail(e, "launch_csne_pass_trf");
-  ctx->begin(K_CSNE_FIX);
-  e = launch_csne_fix(cs, p->st, p->lm, dDelta, dalpha_in, tier.count, ctx->stream);
-  ctx->end();
-  if (e != hipSuccess) return ctx->fail(e, "launch_csne_fix");
+  if (int rc_ = ctx->run(K_CSNE_PASS, "launch_csne_pass_trf", [&] {
+        return launch_csne_pass_trf(cs, p->st.d, tier.count, ctx->stream);
+      })) return rc_;
+  if (int rc_ = ctx->run(K_CSNE_FIX, "launch_csne_fix", [&] {
+        return launch_csne_fix(cs, p->st, p->lm, dDelta, dalpha_in, tier.count, ctx->stream);
+      })) return rc_;
   return 0;
 }
 
@@ -581,10 +549,9 @@ int trf_csne_verdict(blsq_trf_plan* p, int ncs, bool* redo) {
   int rc;
   if ((rc = p->csne.reroute(ctx, t, nfail))) return rc;
   if ((rc = t.run_fallback(ctx, cs.J, cs.F, cs.ldJ, nfail))) return rc;
-  ctx->begin(K_PREP);
-  hipError_t e = launch_trf_prep(p->st, p->last_scale_mode, 0, t.fb_mask(), 1, ctx->stream);
-  ctx->end();
-  if (e != hipSuccess) return ctx->fail(e, "launch_trf_prep(csne redo)");
+  if (int rc_ = ctx->run(K_PREP, "launch_trf_prep(csne redo)", [&] {
+        return launch_trf_prep(p->st, p->last_scale_mode, 0, t.fb_mask(), 1, ctx->stream);
+      })) return rc_;
   p->use_qr = true;
   p->gate_done = false; p->njac = -1;
   return trf_finish(p);
@@ -696,12 +663,10 @@ extern "C" int blsq_trf_step_dev(blsq_trf_plan* p, const double* dDelta, const d
     if (rc) return rc;
     const int ncs = p->csne.count;
     if (ncs > 0 && (rc = trf_csne_correct(p, dDelta, dalpha_in))) return rc;
-    ctx->begin(K_STEP);
     const PublishArgs pub = verdict_rides(p);
-    hipError_t e = launch_trf_step(p->st, &p->lm, dDelta, dalpha_in, active_rtol, p->out,
-                                   ctx->stream, &pub);
-    ctx->end();
-    if (e != hipSuccess) return ctx->fail(e, "launch_trf_step");
+    if ((rc = ctx->run(K_STEP, "launch_trf_step", [&] {
+           return launch_trf_step(p->st, &p->lm, dDelta, dalpha_in, active_rtol, p->out, ctx->stream, &pub);
+         }))) return rc;
     p->lm_counts_clean = true;              // (the step kernel leaves the round counters zeroed)
     bool redo = false;
     if ((rc = trf_resolve(p, &redo))) return rc;
@@ -982,10 +947,9 @@ int tsqr_merge_and_finish(blsq_trf_plan* p, const double* dtri_stack, int scale_
     const int nleaf = (ntri + G - 1) / G;
     q.RP = std::max(round_up(std::min(q.rows_per_leaf, q.rowsA), 16), NPAD);
     q.Rout = pp[flip];
-    ctx->begin(K_QR_MERGE);
-    hipError_t e = launch_qr(q, nleaf, 1, ctx->stream);
-    ctx->end();
-    if (e != hipSuccess) return ctx->fail(e, "launch_qr(combine)");
+    if (int rc_ = ctx->run(K_QR_MERGE, "launch_qr(combine)", [&] {
+          return launch_qr(q, nleaf, 1, ctx->stream);
+        })) return rc_;
     src = pp[flip];
     flip ^= 1;
     ntri = nleaf;

@@ -624,10 +624,8 @@ hipError_t launch_gram_gate(const GramCholArgs& a_in, int B, hipStream_t s, bool
   if (a.NPAD > 80 && a.cert_done && a.dsc) {
     if (options_or_default(a.opt).on(OPT_CERT0)) {
       const size_t lds0 = sizeof(double) * (4 + 32 + 1) * (size_t)a.NPAD;
-      static std::atomic<size_t> granted[64];
-      hipError_t ge = gram_grant_lds(gram_cert0_kernel, lds0, granted);
-      if (ge != hipSuccess) return ge;
-      hipLaunchKernelGGL(gram_cert0_kernel, dim3(B), dim3(TRI_NT), lds0, s, a);
+      hipError_t e0 = launch<gram_cert0_kernel>(dim3(B), dim3(TRI_NT), lds0, s, a);
+      if (e0 != hipSuccess) return e0;
     } else {
       hipError_t me = hipMemsetAsync(a.cert_done, 0, sizeof(int) * (size_t)B, s);
       if (me != hipSuccess) return me;
@@ -636,15 +634,12 @@ hipError_t launch_gram_gate(const GramCholArgs& a_in, int B, hipStream_t s, bool
   } else {
     a.cert_open = nullptr;
   }
-  if (stage0_only) return hipGetLastError();
+  if (stage0_only) return hipSuccess;
   const size_t per1 = sizeof(double) * (6 * (size_t)a.NPAD + 16 * 1 + 64);
   const size_t per8 = sizeof(double) * (6 * (size_t)a.NPAD + 16 * 8 + 64);
-  if (a.NPAD <= 80) {                                   // one wave per problem, eight per workgroup
-    hipLaunchKernelGGL(gram_cond_kernel<1>, dim3((B + GR_NW - 1) / GR_NW), dim3(GR_NT), per1 * GR_NW, s, a);
-  } else {
-    hipLaunchKernelGGL(gram_cond_kernel<8>, dim3(B), dim3(GR_NT), per8, s, a);
-  }
-  return hipGetLastError();
+  if (a.NPAD <= 80)                                     // one wave per problem, eight per workgroup
+    return launch<gram_cond_kernel<1>>(dim3((B + GR_NW - 1) / GR_NW), dim3(GR_NT), per1 * GR_NW, s, a);
+  return launch<gram_cond_kernel<8>>(dim3(B), dim3(GR_NT), per8, s, a);
 }
 
 #ifdef BLSQ_CHOL_STAMPS

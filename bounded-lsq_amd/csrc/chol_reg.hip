@@ -762,21 +762,13 @@ __global__ __launch_bounds__(REG_NT, 1) void lm_rounds_reg_kernel(GramCholArgs a
 hipError_t launch_lm_rounds_reg(const GramCholArgs& c, const LmState& lm, const double* Delta,
                                 const double* alpha_in, hipStream_t s) {
   const size_t lds = sizeof(double) * reg_lds_doubles(c.NPAD) * REG_NW;
-  static std::atomic<size_t> granted[64];
-  hipError_t ge = gram_grant_lds(lm_rounds_reg_kernel, lds, granted);
-  if (ge != hipSuccess) return ge;
-  hipLaunchKernelGGL(lm_rounds_reg_kernel, dim3(reg_grid(lm.B)), dim3(REG_NT), lds, s, c, lm, Delta, alpha_in);
-  return hipGetLastError();
+  return launch<lm_rounds_reg_kernel>(dim3(reg_grid(lm.B)), dim3(REG_NT), lds, s, c, lm, Delta, alpha_in);
 }
 
 // launch_gram_chol for NPAD <= 80 (a.count set): one wave per problem, REG_NW per workgroup
 hipError_t launch_gram_chol_reg(const GramCholArgs& a, hipStream_t s) {
   const size_t lds = sizeof(double) * reg_lds_doubles(a.NPAD) * REG_NW;
-  static std::atomic<size_t> granted[64];
-  hipError_t ge = gram_grant_lds(gram_chol_reg_kernel, lds, granted);
-  if (ge != hipSuccess) return ge;
-  hipLaunchKernelGGL(gram_chol_reg_kernel, dim3(reg_grid(a.count)), dim3(REG_NT), lds, s, a);
-  return hipGetLastError();
+  return launch<gram_chol_reg_kernel>(dim3(reg_grid(a.count)), dim3(REG_NT), lds, s, a);
 }
 
 #ifdef BLSQ_CHOL_STAMPS

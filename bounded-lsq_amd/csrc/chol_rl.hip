@@ -687,25 +687,14 @@ hipError_t launch_gram_chol(const GramCholArgs& a_in, int B, hipStream_t s) {
                                          2 * (size_t)a.NPAD +
                                          (size_t)(RL_SL - (cert ? RL_SLR<true> : RL_SLR<false>)) * RL_NWK * 256) +
                        sizeof(int) * (size_t)a.NPAD;
-    if (cert) {
-      static std::atomic<size_t> granted[64];
-      hipError_t ge = gram_grant_lds(gram_chol_rl2_kernel<true>, lds, granted);
-      if (ge != hipSuccess) return ge;
-      hipLaunchKernelGGL((gram_chol_rl2_kernel<true>), dim3(B), dim3(RL_NT), lds, s, a);
-    } else {
-      static std::atomic<size_t> granted[64];
-      hipError_t ge = gram_grant_lds(gram_chol_rl2_kernel<false>, lds, granted);
-      if (ge != hipSuccess) return ge;
-      hipLaunchKernelGGL((gram_chol_rl2_kernel<false>), dim3(B), dim3(RL_NT), lds, s, a);
-    }
-  } else {
-    if (a.cert_ym) {                                    // (only the flag-driven kernel has a share in stage 0)
-      hipError_t me = hipMemsetAsync(a.cert_ym, 0, sizeof(double) * (size_t)B, s);
-      if (me != hipSuccess) return me;
-    }
-    hipLaunchKernelGGL(gram_chol_kernel, dim3(B), dim3(GR_NT), sizeof(double) * (4 * (size_t)a.NPAD + 512), s, a);
+    if (cert) return launch<gram_chol_rl2_kernel<true>>(dim3(B), dim3(RL_NT), lds, s, a);
+    return launch<gram_chol_rl2_kernel<false>>(dim3(B), dim3(RL_NT), lds, s, a);
   }
-  return hipGetLastError();
+  if (a.cert_ym) {                                      // (only the flag-driven kernel has a share in stage 0)
+    hipError_t me = hipMemsetAsync(a.cert_ym, 0, sizeof(double) * (size_t)B, s);
+    if (me != hipSuccess) return me;
+  }
+  return launch<gram_chol_kernel>(dim3(B), dim3(GR_NT), sizeof(double) * (4 * (size_t)a.NPAD + 512), s, a);
 }
 hipError_t launch_gram_cert_shift(const GramCholArgs& a_in, int B, hipStream_t s) {
   if (!a_in.cert_flag || !a_in.cert_tau) return hipSuccess;

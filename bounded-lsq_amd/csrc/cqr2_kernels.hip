@@ -369,19 +369,10 @@ hipError_t launch_cqr2_apply(const Cqr2Args& a_in, int count, hipStream_t s) {
   const size_t lds = sizeof(double) * (2 * GR_RC * (size_t)cqr2_ldx(N) + (size_t)a.NPAD);
   const dim3 grid((a.m + a.rows_per_wg - 1) / a.rows_per_wg, count, 1);
   const int ncb = (a.n + 63) / 64;
-#define BLSQ_CQR2_LAUNCH(CB, FL)                                                         \
-  do {                                                                                   \
-    static std::atomic<size_t> granted[64];                                              \
-    hipError_t ge = gram_grant_lds(cqr2_apply_kernel<CB, FL>, lds, granted);             \
-    if (ge != hipSuccess) return ge;                                                     \
-    hipLaunchKernelGGL((cqr2_apply_kernel<CB, FL>), grid, dim3(GR_NT), lds, s, a);       \
-  } while (0)
-  if (ncb <= 2) BLSQ_CQR2_LAUNCH(2, false);
-  else if (ncb <= 3) BLSQ_CQR2_LAUNCH(3, false);
-  else if ((a.n + 15) / 16 == 16) BLSQ_CQR2_LAUNCH(4, true);
-  else BLSQ_CQR2_LAUNCH(4, false);
-#undef BLSQ_CQR2_LAUNCH
-  return hipGetLastError();
+  if (ncb <= 2) return launch<cqr2_apply_kernel<2, false>>(grid, dim3(GR_NT), lds, s, a);
+  if (ncb <= 3) return launch<cqr2_apply_kernel<3, false>>(grid, dim3(GR_NT), lds, s, a);
+  if ((a.n + 15) / 16 == 16) return launch<cqr2_apply_kernel<4, true>>(grid, dim3(GR_NT), lds, s, a);
+  return launch<cqr2_apply_kernel<4, false>>(grid, dim3(GR_NT), lds, s, a);
 }
 
 hipError_t launch_cqr2_combine(const Cqr2Args& a, int count, const int* run, const int* pivot2, const double* G2,

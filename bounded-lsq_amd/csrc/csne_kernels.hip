@@ -353,11 +353,7 @@ __global__ __launch_bounds__(CS_NT, BLSQ_CSM_OCC) void csne_pass_mfma_kernel(Csn
 template <int NST>
 static hipError_t csne_pass_mfma_launch(const CsneState& cs, const double* dvec, int count, hipStream_t s) {
   const size_t lds = sizeof(double) * ((size_t)CS_NW * CSM_TR * csm_stride(NST) + 2 * CS_NW * 4 * WAVE);
-  static std::atomic<size_t> granted[64];
-  hipError_t ge = gram_grant_lds(csne_pass_mfma_kernel<NST>, lds, granted);
-  if (ge != hipSuccess) return ge;
-  hipLaunchKernelGGL((csne_pass_mfma_kernel<NST>), dim3(cs.nchunk, count), dim3(CS_NT), lds, s, cs, dvec);
-  return hipGetLastError();
+  return launch<csne_pass_mfma_kernel<NST>>(dim3(cs.nchunk, count), dim3(CS_NT), lds, s, cs, dvec);
 }
 // cs.NE must be CSNE_MAXE (the partial sums carry all eight evaluation slots, whatever the batch's depth)
 hipError_t launch_csne_pass_trf(const CsneState& cs, const double* dvec, int count, hipStream_t s) {
@@ -373,11 +369,7 @@ hipError_t launch_csne_pass_trf(const CsneState& cs, const double* dvec, int cou
 template <int NCB>
 static hipError_t csne_pass_launch(const CsneState& cs, int count, hipStream_t s) {
   const size_t lds = sizeof(double) * (size_t)CS_NW * NCB * WAVE;
-  static std::atomic<size_t> granted[64];
-  hipError_t ge = gram_grant_lds(csne_pass_kernel<NCB>, lds, granted);
-  if (ge != hipSuccess) return ge;
-  hipLaunchKernelGGL((csne_pass_kernel<NCB>), dim3(cs.nchunk, count), dim3(CS_NT), lds, s, cs);
-  return hipGetLastError();
+  return launch<csne_pass_kernel<NCB>>(dim3(cs.nchunk, count), dim3(CS_NT), lds, s, cs);
 }
 // cs.NE must be 1 (the partial sums carry the one vector of the plan)
 hipError_t launch_csne_pass_dog(const CsneState& cs, int count, hipStream_t s) {
@@ -567,11 +559,7 @@ hipError_t launch_csne_fix(const CsneState& cs, const TrfState& st, const LmStat
                            const double* alpha_in, int count, hipStream_t s) {
   if (count <= 0) return hipSuccess;
   const size_t lds = sizeof(double) * (6 + 32) * (size_t)cs.ld;
-  static std::atomic<size_t> granted[64];
-  hipError_t ge = gram_grant_lds(csne_fix_kernel, lds, granted);
-  if (ge != hipSuccess) return ge;
-  hipLaunchKernelGGL(csne_fix_kernel, dim3(count), dim3(TRI_NT), lds, s, cs, st, lm, Delta, alpha_in);
-  return hipGetLastError();
+  return launch<csne_fix_kernel>(dim3(count), dim3(TRI_NT), lds, s, cs, st, lm, Delta, alpha_in);
 }
 
 // ---- who is on the tier ---------------------------------------------------------------------------
@@ -722,11 +710,7 @@ __global__ __launch_bounds__(TRI_NT) void dog_csne_fix_kernel(CsneState cs, DogS
 hipError_t launch_dog_csne_fix(const CsneState& cs, const DogState& st, int count, hipStream_t s) {
   if (count <= 0) return hipSuccess;
   const size_t lds = sizeof(double) * (2 + 32) * (size_t)cs.ld;
-  static std::atomic<size_t> granted[64];
-  hipError_t ge = gram_grant_lds(dog_csne_fix_kernel, lds, granted);
-  if (ge != hipSuccess) return ge;
-  hipLaunchKernelGGL(dog_csne_fix_kernel, dim3(count), dim3(TRI_NT), lds, s, cs, st);
-  return hipGetLastError();
+  return launch<dog_csne_fix_kernel>(dim3(count), dim3(TRI_NT), lds, s, cs, st);
 }
 
 // the problems whose acceptance failed in the last step call leave the tier for good (until the next factor call)

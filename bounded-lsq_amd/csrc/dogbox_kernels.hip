@@ -8,10 +8,10 @@
 //                           dropped, rcond = eps*max(m, n_free))
 //   Js = J_free s      =>   Js.Js = |R s_full|^2 ,  Js.f = (R s_full).c
 // Compiled with -ffp-contract=off: masks use exact == (dogbox.py:29-33).
-#include <atomic>
 
 #include "blsq_device.h"
 #include "blsq_kernels.h"
+#include "blsq_launch.h"
 
 namespace blsq {
 
@@ -175,9 +175,8 @@ hipError_t launch_dog_prep(const DogState& st, int jac_scaling, int from_gram, c
                            int redo, hipStream_t s, const PackVecs* pk) {
   const size_t lds = sizeof(double) * 2 * (size_t)st.ld + sizeof(int) * (size_t)st.ld;
   const PackVecs none{{nullptr, nullptr, nullptr, nullptr, nullptr}, {nullptr, nullptr, nullptr, nullptr, nullptr}, nullptr, 0};
-  hipLaunchKernelGGL(dog_prep_kernel, dim3(st.B), dim3(DG_NT), lds, s, st, jac_scaling, from_gram,
-                     sel, redo, (pk && !sel) ? *pk : none);
-  return hipGetLastError();
+  return launch<dog_prep_kernel>(dim3(st.B), dim3(DG_NT), lds, s, st, jac_scaling, from_gram, sel, redo,
+                                 (pk && !sel) ? *pk : none);
 }
 
 // ----------------------------------------------------------------- solve --
@@ -216,8 +215,7 @@ __global__ __launch_bounds__(DG_NT) void dog_solve_kernel(DogState st, const int
 
 hipError_t launch_dog_solve(const DogState& st, const int* skip, hipStream_t s) {
   const size_t lds = sizeof(double) * (size_t)st.ld;
-  hipLaunchKernelGGL(dog_solve_kernel, dim3(st.B), dim3(DG_NT), lds, s, st, skip);
-  return hipGetLastError();
+  return launch<dog_solve_kernel>(dim3(st.B), dim3(DG_NT), lds, s, st, skip);
 }
 
 // ------------------------------------------------------------------ step --
@@ -430,21 +428,9 @@ __global__ __launch_bounds__(DG_NT) void dog_step_kernel(DogState st, const doub
 
 hipError_t launch_dog_step(const DogState& st, const double* Delta, const DogStepOut& out,
                            hipStream_t s, const PublishArgs* pub) {
-  const size_t lds = sizeof(double) * 11 * (size_t)st.ld;
-  if (lds > 64 * 1024) {                    // ld > 744: dynamic LDS above 64 KB has to be granted (88 KB at ld = 1024)
-    static std::atomic<size_t> granted[64];
-    int dev = 0;
-    (void)hipGetDevice(&dev);
-    if (lds > granted[dev & 63].load(std::memory_order_acquire)) {
-      hipError_t ge = hipFuncSetAttribute((const void*)dog_step_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                          (int)lds);
-      if (ge != hipSuccess) return ge;
-      granted[dev & 63].store(lds, std::memory_order_release);
-    }
-  }
-  hipLaunchKernelGGL(dog_step_kernel, dim3(st.B), dim3(DG_NT), lds, s, st, Delta, out,
-                     pub ? *pub : PublishArgs{nullptr, 0, nullptr, 0});
-  return hipGetLastError();
+  const size_t lds = sizeof(double) * 11 * (size_t)st.ld;     // (88 KB at ld = 1024)
+  return launch<dog_step_kernel>(dim3(st.B), dim3(DG_NT), lds, s, st, Delta, out,
+                                 pub ? *pub : PublishArgs{nullptr, 0, nullptr, 0});
 }
 
 }  // namespace blsq

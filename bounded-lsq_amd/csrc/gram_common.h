@@ -1,13 +1,13 @@
 // Shared by gram_kernels.hip (the Gram kernels), chol_reg.hip (N <= 80: Cholesky and fused Newton rounds),
-// chol_rl.hip (N > 80: Cholesky) and cert_kernels.hip (certificate): launch geometry, the LDS grant helper, the FP64
-// MFMA wrapper, the explicit LDS read helpers with counted waits and the column scales of the Cholesky kernels.
+// chol_rl.hip (N > 80: Cholesky) and cert_kernels.hip (certificate): launch geometry, the FP64 MFMA wrapper, the
+// explicit LDS read helpers with counted waits and the column scales of the Cholesky kernels.
 #pragma once
-#include <atomic>
 #include <stdlib.h>
 #include <type_traits>
 
 #include "blsq_device.h"
 #include "blsq_kernels.h"
+#include "blsq_launch.h"
 
 namespace blsq {
 
@@ -22,18 +22,6 @@ static constexpr int REG_NT = REG_NW * WAVE;   // 1024 problems spread over 256 
 __device__ __forceinline__ int reg_problem(int w, int wv) { return (((w >> 3) * REG_NW + wv) << 3) | (w & 7); }
 static inline unsigned reg_grid(int B) { return (unsigned)(((B + 8 * REG_NW - 1) / (8 * REG_NW)) * 8); }
 static constexpr double GRAM_SMIN = GRAM_SMIN_PROVEN;   // early reject: a pivot of R' below what the certificate could accept
-
-template <class K>
-static hipError_t gram_grant_lds(K kernel, size_t bytes, std::atomic<size_t>* granted_dev) {
-  int dev = 0;
-  (void)hipGetDevice(&dev);
-  std::atomic<size_t>& granted = granted_dev[dev & 63];
-  if (bytes <= granted.load(std::memory_order_acquire)) return hipSuccess;
-  hipError_t e = hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                     (int)bytes);
-  if (e == hipSuccess) granted.store(bytes, std::memory_order_release);
-  return e;
-}
 
 __device__ __forceinline__ v4d gmfma(double a, double b, v4d c) {
   return __builtin_amdgcn_mfma_f64_16x16x4f64(a, b, c, 0, 0, 0);

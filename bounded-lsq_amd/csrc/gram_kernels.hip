@@ -1078,8 +1078,7 @@ __global__ __launch_bounds__(GRED_G * GRED_W) void gram_reduce_wide_kernel(
 // launch.  2048 rows; 1024 for very tall problems (one 250 000 x 128 row block of BASELINE config 5:
 // 245 workgroups fill the 256 CUs, 123 leave half of them idle).
 static int gram_chunk_rows(long long m) { return m > 131072 ? 1024 : 2048; }
-int gram_chunks(int B, int m) {
-  (void)B;
+int gram_chunks(int m) {
   const int r = gram_chunk_rows(m);
   const int c = (m + r - 1) / r;
   return c < 1 ? 1 : c;
@@ -1102,108 +1101,64 @@ bool gram_supported(int m, int n) {
   return NT <= 17 && m >= n && n >= 1;
 }
 
-hipError_t launch_gram(const GramArgs& a_in, int chunks, int B, hipStream_t s, double* Gfinal, bool* fused) {
-  GramArgs a = a_in;
-  if (fused) *fused = false;
-  const int NT = (a.n + 1 + 15) / 16;
-  a.rows_per_chunk = chunks > 1 ? gram_chunk_rows(a.m) : a.m;
+GramRoute gram_route(int m, int n, int chunks, int B, bool has_final, const Options& opt) {
+  GramRoute r{};
+  r.grid[0] = chunks; r.grid[1] = B; r.grid[2] = 1;
+  r.block = GR_NT;
+  r.tile_groups = 1;
+  const int NT = (n + 1 + 15) / 16;
+  r.rows_per_chunk = chunks > 1 ? gram_chunk_rows(m) : m;
   const size_t lds = sizeof(double) * 2 * GR_RC * (size_t)gram_ldx(NT);
-  // slot variant a wave needs for `nt` column tiles
-  auto slots_for = [](int nt) {
-    const int per_ = (nt * (nt + 1) / 2 + GR_NW - 1) / GR_NW;
-    return per_ <= 4 ? 4 : per_ <= 8 ? 8 : per_ <= 12 ? 12 : per_ <= 17 ? 17 : 20;
-  };
   // n % 16 == 0: the rhs column would be a tile column of its own (NT tiles for one useful column
   // each) — it is accumulated in registers beside the MFMA stream instead (n = 256: 153 -> 136 tiles)
-  a.rhs_valu = ((a.n + 15) / 16 < NT) ? 1 : 0;
-  (void)slots_for;
-  const int NTJ = a.rhs_valu ? (a.n + 15) / 16 : NT;
+  r.rhs_valu = ((n + 15) / 16 < NT) ? 1 : 0;
+  const int NTJ = r.rhs_valu ? (n + 15) / 16 : NT;
   const int ntile = NTJ * (NTJ + 1) / 2;
-#define BLSQ_GRAM_LAUNCH(SL, CB)                                                              \
-  do {                                                                                        \
-    static std::atomic<size_t> granted[64];                                                   \
-    hipError_t ge = gram_grant_lds(gram_kernel<SL, CB>, lds, granted);                        \
-    if (ge != hipSuccess) return ge;                                                          \
-    hipLaunchKernelGGL((gram_kernel<SL, CB>), dim3(chunks, B, tg), dim3(GR_NT), lds, s, a);   \
-  } while (0)
-#define BLSQ_GRAM_DIRECT_NW(NTT, RHS, NWD)                                                    \
-  do {                                                                                        \
-    constexpr int nt_ = (NTT) * ((NTT) + 1) / 2;                                              \
-    const size_t dl_ = sizeof(double) * ((nt_ < 5 ? nt_ : 5) * (NWD) * 256 + 64);            \
-    static std::atomic<size_t> granted[64];                                                   \
-    hipError_t ge = gram_grant_lds(gram_direct_kernel<NTT, RHS, NWD>, dl_, granted);          \
-    if (ge != hipSuccess) return ge;                                                          \
-    hipLaunchKernelGGL((gram_direct_kernel<NTT, RHS, NWD>), dim3(chunks, B), dim3(64 * (NWD)), dl_, s, a); \
-    return hipGetLastError();                                                                 \
-  } while (0)
-#define BLSQ_GRAM_DIRECT(NTT, RHS)                                                            \
-  do {                                                                                        \
-    if (direct_nw == 4) BLSQ_GRAM_DIRECT_NW(NTT, RHS, 4);                                     \
-    else if (direct_nw == 2) BLSQ_GRAM_DIRECT_NW(NTT, RHS, 2);                                \
-    else BLSQ_GRAM_DIRECT_NW(NTT, RHS, 8);                                                    \
-  } while (0)
   // waves per workgroup of the direct kernel: about 256 rows per wave (a function of m only, so a
   // problem's bits do not depend on its batch).  A short problem on eight waves is four rounds of loads
   // per wave between a cold start and an eight-way reduction, and one workgroup fills the CU: 1024
   // problems of 512 x 64 pass in four lock-step generations.  On two waves, four workgroups share the CU
   // and drift apart: 96 -> 78 us.  BLSQ_GRAM_DIRECT_NW = 2 | 4 | 8 forces one.
-  const Options& opt = options_or_default(a.opt);
   const int dnw_o = opt.i(OPT_GRAM_DIRECT_NW);
-  const int rows_wg = a.m < a.rows_per_chunk ? a.m : a.rows_per_chunk;
+  const int rows_wg = m < r.rows_per_chunk ? m : r.rows_per_chunk;
   // (up to 128 rows eight waves need a single round of loads: nothing to drift, lowest latency)
   const int direct_nw = dnw_o > 0 ? dnw_o : (rows_wg <= 128 ? 8 : rows_wg <= 512 ? 2 : rows_wg <= 1024 ? 4 : 8);
-  {
-    const int dmax = opt.i(OPT_GRAM_DIRECT_MAX_NT);            // tuning / tests: 0 disables; measured: direct wins up to 4 column tiles
-    // n a multiple of 16: the tiles cover J^T J only (n / 16 column tiles), the rhs column is
-    // accumulated from the same fragments (n = 64: 10 tiles instead of 15, and still no LDS staging)
-    if (a.rhs_valu && NTJ <= dmax) {
-      if (NTJ == 1) BLSQ_GRAM_DIRECT(1, true);
-      else if (NTJ == 2) BLSQ_GRAM_DIRECT(2, true);
-      else if (NTJ == 3) BLSQ_GRAM_DIRECT(3, true);
-      else if (NTJ == 4) BLSQ_GRAM_DIRECT(4, true);
-    }
-    if (!a.rhs_valu && NT <= dmax) {
-      if (NT <= 1) BLSQ_GRAM_DIRECT(1, false);
-      else if (NT == 2) BLSQ_GRAM_DIRECT(2, false);
-      else if (NT == 3) BLSQ_GRAM_DIRECT(3, false);
-      else if (NT == 4) BLSQ_GRAM_DIRECT(4, false);
-    }
+  const int dmax = opt.i(OPT_GRAM_DIRECT_MAX_NT);            // tuning / tests: 0 disables; measured: direct wins up to 4 column tiles
+  // n a multiple of 16: the tiles cover J^T J only (n / 16 column tiles), the rhs column is
+  // accumulated from the same fragments (n = 64: 10 tiles instead of 15, and still no LDS staging)
+  if (NTJ <= dmax && NTJ <= 4) {                             // (NTJ = NT without rhs_valu)
+    const int nwd = direct_nw == 4 ? 4 : direct_nw == 2 ? 2 : 8;
+    r.family = GRAM_DIRECT;
+    r.key[0] = NTJ; r.key[1] = r.rhs_valu; r.key[2] = nwd;
+    r.block = 64 * nwd;
+    r.lds = sizeof(double) * ((ntile < 5 ? ntile : 5) * nwd * 256 + 64);
+    return r;
   }
-#undef BLSQ_GRAM_DIRECT
-#undef BLSQ_GRAM_DIRECT_NW
-  {
-    // 8 column tiles of J^T J (n = 113 .. 128): the k-split static-tile kernel, for EVERY batch size
-    // (its summation order defines the result for these widths).  BLSQ_GRAM8 = 0: the generic kernel.
-    if (NTJ == 8 && opt.on(OPT_GRAM8)) {
-      const size_t need = sizeof(double) * 4 * 9 * 256;          // partial tiles of the odd k-steps
-      const size_t l8 = lds > need ? lds : need;
-      if (a.rhs_valu) {
-        static std::atomic<size_t> granted[64];
-        hipError_t ge = gram_grant_lds(gram8_kernel<true>, l8, granted);
-        if (ge != hipSuccess) return ge;
-        hipLaunchKernelGGL((gram8_kernel<true>), dim3(chunks, B, 1), dim3(GR_NT), l8, s, a);
-      } else {
-        static std::atomic<size_t> granted[64];
-        hipError_t ge = gram_grant_lds(gram8_kernel<false>, l8, granted);
-        if (ge != hipSuccess) return ge;
-        hipLaunchKernelGGL((gram8_kernel<false>), dim3(chunks, B, 1), dim3(GR_NT), l8, s, a);
-      }
-      return hipGetLastError();
-    }
+  // 8 column tiles of J^T J (n = 113 .. 128): the k-split static-tile kernel, for EVERY batch size
+  // (its summation order defines the result for these widths).  BLSQ_GRAM8 = 0: the generic kernel.
+  if (NTJ == 8 && opt.on(OPT_GRAM8)) {
+    const size_t need = sizeof(double) * 4 * 9 * 256;          // partial tiles of the odd k-steps
+    r.family = GRAM_8;
+    r.key[0] = r.rhs_valu;
+    r.lds = lds > need ? lds : need;
+    return r;
   }
   // a handful of problems, rhs column outside the tiles, widths whose sums the tile-table kernel defines: one tile per wave
   // straight from global memory (bit-identical; option gram1 = 0: the tile groups below)
-  if (a.rhs_valu && (long)chunks * B <= 4 && NTJ > opt.i(OPT_GRAM_DIRECT_MAX_NT) && NTJ > 4 && !(NTJ == 8 && opt.on(OPT_GRAM8)) &&
+  if (r.rhs_valu && (long)chunks * B <= 4 && NTJ > dmax && NTJ > 4 && !(NTJ == 8 && opt.on(OPT_GRAM8)) &&
       NTJ <= 16 && opt.on(OPT_GRAM1)) {
     int tile_wgs = 0;
     for (int i = 0; i < NTJ; ++i) tile_wgs += (NTJ - i + G1_NW - 1) / G1_NW;
-    const int rhs_wgs = (a.n + 63) / 64;
+    const int rhs_wgs = (n + 63) / 64;
     const int groups = chunks * B, mg_min = 8 / groups;             // (XCDs per (row chunk, problem) pair, at least)
     const int slots = (tile_wgs + rhs_wgs + mg_min - 1) / mg_min;
-    hipLaunchKernelGGL(gram1_kernel, dim3(8 * slots), dim3(G1_NT), 0, s, a, chunks, B, tile_wgs);
-    return hipGetLastError();
+    r.family = GRAM_1;
+    r.tile_wgs = tile_wgs;
+    r.grid[0] = 8 * slots; r.grid[1] = 1;
+    r.block = G1_NT;
+    return r;
   }
-  const int ncb = (a.n + 63) / 64;
+  const int ncb = (n + 63) / 64;
   // tile groups: enough workgroups to occupy the CUs when the batch is small (results identical)
   int tg = 1;
   {
@@ -1221,58 +1176,113 @@ hipError_t launch_gram(const GramArgs& a_in, int chunks, int B, hipStream_t s, d
     if (tg > ntile) tg = ntile;
     if (tg < 1) tg = 1;
   }
-  {
-    // 16 column tiles of J^T J (n = 241 .. 256) and one workgroup per row chunk: the kernel with
-    // static tile rows per wave (BLSQ_GRAM16 = 0 keeps the generic one: tests compare the two)
-    const int g16_env = opt.i(OPT_GRAM16);
-    if (NTJ == 16 && tg == 1 && g16_env != 0 && a.m >= 1) {
-      // two row chunks and enough problems to fill the device with one workgroup each: both chunks by
-      // the same workgroup, summed in the kernel straight into the final slot (bit-identical to the
-      // reduction pass: BLSQ_GRAM_PAIR = 0 keeps that)
-      const bool pair = Gfinal && chunks == 2 && B >= 256 && opt.on(OPT_GRAM_PAIR);
-      if (pair) { a.Gscr = a.G; a.G = Gfinal; if (fused) *fused = true; }
-      const dim3 grid(pair ? 1 : chunks, B, 1);
-#define BLSQ_GRAM16(RHS_, PAIR_)                                                              \
-  do {                                                                                        \
-    static std::atomic<size_t> granted[64];                                                   \
-    hipError_t ge = gram_grant_lds(gram16_kernel<RHS_, PAIR_>, lds, granted);                 \
-    if (ge != hipSuccess) return ge;                                                          \
-    hipLaunchKernelGGL((gram16_kernel<RHS_, PAIR_>), grid, dim3(GR_NT), lds, s, a);           \
-  } while (0)
-      if (a.rhs_valu) { if (pair) BLSQ_GRAM16(true, true); else BLSQ_GRAM16(true, false); }
-      else { if (pair) BLSQ_GRAM16(false, true); else BLSQ_GRAM16(false, false); }
-#undef BLSQ_GRAM16
-      return hipGetLastError();
-    }
+  r.lds = lds;
+  // 16 column tiles of J^T J (n = 241 .. 256) and one workgroup per row chunk: the kernel with
+  // static tile rows per wave (BLSQ_GRAM16 = 0 keeps the generic one: tests compare the two)
+  if (NTJ == 16 && tg == 1 && opt.i(OPT_GRAM16) != 0) {
+    // two row chunks and enough problems to fill the device with one workgroup each: both chunks by
+    // the same workgroup, summed in the kernel straight into the final slot (bit-identical to the
+    // reduction pass: BLSQ_GRAM_PAIR = 0 keeps that)
+    const bool pair = has_final && chunks == 2 && B >= 256 && opt.on(OPT_GRAM_PAIR);
+    r.family = GRAM_16;
+    r.key[0] = r.rhs_valu; r.key[1] = pair;
+    r.fused = pair;
+    if (pair) r.grid[0] = 1;
+    return r;
   }
   const int per = (((ntile + tg - 1) / tg) + GR_NW - 1) / GR_NW;   // tile slots a wave needs
-  if (per <= 1 && tg > 8) {                             // (many tile groups of a tiny launch: one tile per wave)
-    if (ncb <= 1) BLSQ_GRAM_LAUNCH(1, 1);
-    else if (ncb <= 2) BLSQ_GRAM_LAUNCH(1, 2);
-    else BLSQ_GRAM_LAUNCH(1, 5);
-  } else if (per <= 2 && tg > 8) {
-    if (ncb <= 1) BLSQ_GRAM_LAUNCH(2, 1);
-    else if (ncb <= 2) BLSQ_GRAM_LAUNCH(2, 2);
-    else BLSQ_GRAM_LAUNCH(2, 5);
-  } else if (per <= 4) {                                // n <= 111, or tile groups
-    if (ncb <= 1) BLSQ_GRAM_LAUNCH(4, 1);
-    else if (ncb <= 2) BLSQ_GRAM_LAUNCH(4, 2);
-    else BLSQ_GRAM_LAUNCH(4, 5);
-  } else if (per <= 8) {                                // n <= 159, or tile groups
-    if (ncb <= 2) BLSQ_GRAM_LAUNCH(8, 2);
-    else if (ncb <= 3) BLSQ_GRAM_LAUNCH(8, 3);
-    else BLSQ_GRAM_LAUNCH(8, 5);
-  } else if (per <= 12) {                               // n <= 207, or tile groups
-    if (ncb <= 3) BLSQ_GRAM_LAUNCH(12, 3);
-    else if (ncb <= 4) BLSQ_GRAM_LAUNCH(12, 4);
-    else BLSQ_GRAM_LAUNCH(12, 5);
-  } else if (per <= 17) {                               // n <= 256
-    if (ncb <= 4) BLSQ_GRAM_LAUNCH(17, 4); else BLSQ_GRAM_LAUNCH(17, 5);
-  } else {
-    if (ncb <= 4) BLSQ_GRAM_LAUNCH(20, 4); else BLSQ_GRAM_LAUNCH(20, 5);
+  // (column blocks of 64: the instances kept per slot count)
+  auto ncb_of = [ncb](int c0, int c1) { return ncb <= c0 ? c0 : ncb <= c1 ? c1 : 5; };
+  r.family = GRAM_GENERIC;
+  r.tile_groups = r.grid[2] = tg;
+  if (per <= 1 && tg > 8) { r.key[0] = 1; r.key[1] = ncb_of(1, 2); }        // (tile groups of a tiny launch: one tile per wave)
+  else if (per <= 2 && tg > 8) { r.key[0] = 2; r.key[1] = ncb_of(1, 2); }
+  else if (per <= 4) { r.key[0] = 4; r.key[1] = ncb_of(1, 2); }             // n <= 111, or tile groups
+  else if (per <= 8) { r.key[0] = 8; r.key[1] = ncb_of(2, 3); }             // n <= 159, or tile groups
+  else if (per <= 12) { r.key[0] = 12; r.key[1] = ncb_of(3, 4); }           // n <= 207, or tile groups
+  else if (per <= 17) { r.key[0] = 17; r.key[1] = ncb_of(4, 4); }           // n <= 256
+  else { r.key[0] = 20; r.key[1] = ncb_of(4, 4); }
+  return r;
+}
+
+// The dispatch table: one line per kernel instance, keyed by the route.
+hipError_t launch_gram(const GramArgs& a_in, int chunks, int B, hipStream_t s, double* Gfinal, bool* fused) {
+  const GramRoute r = gram_route(a_in.m, a_in.n, chunks, B, Gfinal != nullptr, options_or_default(a_in.opt));
+  GramArgs a = a_in;
+  a.rows_per_chunk = r.rows_per_chunk;
+  a.rhs_valu = r.rhs_valu;
+  if (r.fused) { a.Gscr = a.G; a.G = Gfinal; }
+  if (fused) *fused = r.fused != 0;
+  const dim3 g(r.grid[0], r.grid[1], r.grid[2]), b(r.block);
+  const int k = r.key[0] * 100 + r.key[1] * 10 + r.key[2];
+  switch (r.family) {
+    case GRAM_DIRECT:
+      switch (k) {
+        case 102: return launch<gram_direct_kernel<1, false, 2>>(g, b, r.lds, s, a);
+        case 104: return launch<gram_direct_kernel<1, false, 4>>(g, b, r.lds, s, a);
+        case 108: return launch<gram_direct_kernel<1, false, 8>>(g, b, r.lds, s, a);
+        case 112: return launch<gram_direct_kernel<1, true, 2>>(g, b, r.lds, s, a);
+        case 114: return launch<gram_direct_kernel<1, true, 4>>(g, b, r.lds, s, a);
+        case 118: return launch<gram_direct_kernel<1, true, 8>>(g, b, r.lds, s, a);
+        case 202: return launch<gram_direct_kernel<2, false, 2>>(g, b, r.lds, s, a);
+        case 204: return launch<gram_direct_kernel<2, false, 4>>(g, b, r.lds, s, a);
+        case 208: return launch<gram_direct_kernel<2, false, 8>>(g, b, r.lds, s, a);
+        case 212: return launch<gram_direct_kernel<2, true, 2>>(g, b, r.lds, s, a);
+        case 214: return launch<gram_direct_kernel<2, true, 4>>(g, b, r.lds, s, a);
+        case 218: return launch<gram_direct_kernel<2, true, 8>>(g, b, r.lds, s, a);
+        case 302: return launch<gram_direct_kernel<3, false, 2>>(g, b, r.lds, s, a);
+        case 304: return launch<gram_direct_kernel<3, false, 4>>(g, b, r.lds, s, a);
+        case 308: return launch<gram_direct_kernel<3, false, 8>>(g, b, r.lds, s, a);
+        case 312: return launch<gram_direct_kernel<3, true, 2>>(g, b, r.lds, s, a);
+        case 314: return launch<gram_direct_kernel<3, true, 4>>(g, b, r.lds, s, a);
+        case 318: return launch<gram_direct_kernel<3, true, 8>>(g, b, r.lds, s, a);
+        case 402: return launch<gram_direct_kernel<4, false, 2>>(g, b, r.lds, s, a);
+        case 404: return launch<gram_direct_kernel<4, false, 4>>(g, b, r.lds, s, a);
+        case 408: return launch<gram_direct_kernel<4, false, 8>>(g, b, r.lds, s, a);
+        case 412: return launch<gram_direct_kernel<4, true, 2>>(g, b, r.lds, s, a);
+        case 414: return launch<gram_direct_kernel<4, true, 4>>(g, b, r.lds, s, a);
+        case 418: return launch<gram_direct_kernel<4, true, 8>>(g, b, r.lds, s, a);
+      }
+      break;
+    case GRAM_8:
+      if (r.key[0]) return launch<gram8_kernel<true>>(g, b, r.lds, s, a);
+      return launch<gram8_kernel<false>>(g, b, r.lds, s, a);
+    case GRAM_1:
+      hipLaunchKernelGGL(gram1_kernel, g, b, 0, s, a, chunks, B, r.tile_wgs);
+      return hipGetLastError();
+    case GRAM_16:
+      switch (k) {
+        case 0: return launch<gram16_kernel<false, false>>(g, b, r.lds, s, a);
+        case 10: return launch<gram16_kernel<false, true>>(g, b, r.lds, s, a);
+        case 100: return launch<gram16_kernel<true, false>>(g, b, r.lds, s, a);
+        case 110: return launch<gram16_kernel<true, true>>(g, b, r.lds, s, a);
+      }
+      break;
+    case GRAM_GENERIC:
+      switch (k) {
+        case 110: return launch<gram_kernel<1, 1>>(g, b, r.lds, s, a);
+        case 120: return launch<gram_kernel<1, 2>>(g, b, r.lds, s, a);
+        case 150: return launch<gram_kernel<1, 5>>(g, b, r.lds, s, a);
+        case 210: return launch<gram_kernel<2, 1>>(g, b, r.lds, s, a);
+        case 220: return launch<gram_kernel<2, 2>>(g, b, r.lds, s, a);
+        case 250: return launch<gram_kernel<2, 5>>(g, b, r.lds, s, a);
+        case 410: return launch<gram_kernel<4, 1>>(g, b, r.lds, s, a);
+        case 420: return launch<gram_kernel<4, 2>>(g, b, r.lds, s, a);
+        case 450: return launch<gram_kernel<4, 5>>(g, b, r.lds, s, a);
+        case 820: return launch<gram_kernel<8, 2>>(g, b, r.lds, s, a);
+        case 830: return launch<gram_kernel<8, 3>>(g, b, r.lds, s, a);
+        case 850: return launch<gram_kernel<8, 5>>(g, b, r.lds, s, a);
+        case 1230: return launch<gram_kernel<12, 3>>(g, b, r.lds, s, a);
+        case 1240: return launch<gram_kernel<12, 4>>(g, b, r.lds, s, a);
+        case 1250: return launch<gram_kernel<12, 5>>(g, b, r.lds, s, a);
+        case 1740: return launch<gram_kernel<17, 4>>(g, b, r.lds, s, a);
+        case 1750: return launch<gram_kernel<17, 5>>(g, b, r.lds, s, a);
+        case 2040: return launch<gram_kernel<20, 4>>(g, b, r.lds, s, a);
+        case 2050: return launch<gram_kernel<20, 5>>(g, b, r.lds, s, a);
+      }
+      break;
   }
-#undef BLSQ_GRAM_LAUNCH
-  return hipGetLastError();
+  return hipErrorInvalidValue;                          // (a route without an instance: gram_route and this table differ)
 }
 hipError_t launch_gram_reduce(const double* Gpart, int chunks, int NPAD, double* Gout,
                               const int* mask, int B, hipStream_t s) {

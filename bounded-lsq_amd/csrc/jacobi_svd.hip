@@ -31,10 +31,10 @@
 //     pair costs ONE dot product; tan/cos/sin come from v_rcp_f64 / v_rsq_f64
 //     + Newton steps — any t is a valid rotation, only cos^2+sin^2 = 1 needs
 //     full precision.
-#include <atomic>
 
 #include "blsq_device.h"
 #include "blsq_kernels.h"
+#include "blsq_launch.h"
 
 namespace blsq {
 
@@ -489,29 +489,12 @@ int jacobi_block_rows(int ldx) {
 }
 
 template <int EPL>
-static hipError_t launch_jacobi_t(const JacobiArgs& a, int B, size_t lds, hipStream_t st) {
-  // the attribute is per device; one ctx per host thread: launches may race (a repeated set is harmless)
-  static std::atomic<size_t> configured_dev[64];
-  int dev_ = 0;
-  (void)hipGetDevice(&dev_);
-  std::atomic<size_t>& configured = configured_dev[dev_ & 63];
-  if (lds > configured.load(std::memory_order_acquire)) {
-    hipError_t e = hipFuncSetAttribute((const void*)jacobi_rows_kernel<EPL>,
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e != hipSuccess) return e;
-    configured.store(lds, std::memory_order_release);
-  }
-  hipLaunchKernelGGL(jacobi_rows_kernel<EPL>, dim3(B), dim3(JAC_NT), lds, st, a);
-  return hipGetLastError();
-}
-
-template <int EPL>
 static hipError_t launch_jacobi_e(JacobiArgs a, int B, hipStream_t st) {
   const int ldx = JAC_LPR * EPL;
   a.RB = jacobi_block_rows(ldx);
   const size_t nrow = 2 * (size_t)a.RB + 2;
   const size_t lds = sizeof(double) * (nrow * ldx + 4 * nrow);
-  return launch_jacobi_t<EPL>(a, B, lds, st);
+  return launch<jacobi_rows_kernel<EPL>>(dim3(B), dim3(JAC_NT), lds, st, a);
 }
 
 hipError_t launch_jacobi(const JacobiArgs& a, int B, hipStream_t st) {

@@ -19,29 +19,13 @@
 // everything else — rank-deficient, wide (m < n), badly conditioned — goes through
 // the Jacobi SVD exactly as before.  Batched problems advance in lock-step rounds
 // (one stacked QR per Newton iteration), finished ones drop out.
-#include <atomic>
-
 #include "blsq_device.h"
 #include "blsq_kernels.h"
+#include "blsq_launch.h"
 #include "tri_ops.h"
 #include "lm_body.h"
 
 namespace blsq {
-
-// dynamic LDS above 64 KB has to be granted per kernel once
-template <class K>
-static hipError_t grant_lds(K kernel, size_t bytes, std::atomic<size_t>* granted_dev) {
-  int dev = 0;
-  (void)hipGetDevice(&dev);                      // the attribute is per device
-  std::atomic<size_t>& granted = granted_dev[dev & 63];
-  if (bytes <= granted.load(std::memory_order_acquire)) return hipSuccess;
-  hipError_t e = hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                     (int)bytes);
-  if (e == hipSuccess) granted.store(bytes, std::memory_order_release);   // (a racing second grant is harmless)
-  return e;
-}
-
-static constexpr size_t LDS_MAX_BYTES = 160 * 1024;   // LDS of one workgroup (CDNA4)
 
 // (LM_EPS, LM_GATE_MARGIN: blsq_kernels.h)
 
@@ -144,9 +128,7 @@ __global__ __launch_bounds__(TRI_NT) void lm_gate_kernel(LmState lm, int enable)
 
 hipError_t launch_lm_gate(const LmState& lm, int enable, hipStream_t s) {
   const size_t lds = sizeof(double) * (3 + 32) * (size_t)lm.ld;
-  { static std::atomic<size_t> granted[64]; hipError_t ge = grant_lds(lm_gate_kernel, lds, granted); if (ge != hipSuccess) return ge; }
-  hipLaunchKernelGGL(lm_gate_kernel, dim3(lm.B), dim3(TRI_NT), lds, s, lm, enable);
-  return hipGetLastError();
+  return launch<lm_gate_kernel>(dim3(lm.B), dim3(TRI_NT), lds, s, lm, enable);
 }
 
 // ------------------------------------------------------------------ start --
@@ -163,9 +145,7 @@ __global__ __launch_bounds__(TRI_NT) void lm_start_kernel(LmState lm, const doub
 hipError_t launch_lm_start(const LmState& lm, const double* Delta, const double* alpha_in,
                            hipStream_t s) {
   const size_t lds = sizeof(double) * (3 + 32) * (size_t)lm.ld;
-  { static std::atomic<size_t> granted[64]; hipError_t ge = grant_lds(lm_start_kernel, lds, granted); if (ge != hipSuccess) return ge; }
-  hipLaunchKernelGGL(lm_start_kernel, dim3(lm.B), dim3(TRI_NT), lds, s, lm, Delta, alpha_in);
-  return hipGetLastError();
+  return launch<lm_start_kernel>(dim3(lm.B), dim3(TRI_NT), lds, s, lm, Delta, alpha_in);
 }
 
 // ----------------------------------------------------------------- update --
@@ -183,9 +163,7 @@ __global__ __launch_bounds__(TRI_NT) void lm_update_kernel(LmState lm) {
 
 hipError_t launch_lm_update(const LmState& lm, int active, hipStream_t s) {
   const size_t lds = sizeof(double) * (3 + 32) * (size_t)lm.ld;
-  { static std::atomic<size_t> granted[64]; hipError_t ge = grant_lds(lm_update_kernel, lds, granted); if (ge != hipSuccess) return ge; }
-  hipLaunchKernelGGL(lm_update_kernel, dim3(active), dim3(TRI_NT), lds, s, lm);
-  return hipGetLastError();
+  return launch<lm_update_kernel>(dim3(active), dim3(TRI_NT), lds, s, lm);
 }
 
 
@@ -297,10 +275,8 @@ hipError_t launch_dog_gate_solve(const DogState& st, int* fast, int* ncols_jac, 
   // ld > 576 (dogbox alone, n >= 577): the DMA staging of the blocked triangular solves does not fit the 160 KB of a
   // workgroup.  Such problems take the Jacobi SVD (the gate is off, the staging is neither allocated nor touched).
   if (lds > LDS_MAX_BYTES) { enable = 0; lds = sizeof(double) * 3 * (size_t)st.ld; }
-  { static std::atomic<size_t> granted[64]; hipError_t ge = grant_lds(dog_gate_solve_kernel, lds, granted); if (ge != hipSuccess) return ge; }
-  hipLaunchKernelGGL(dog_gate_solve_kernel, dim3(st.B), dim3(TRI_NT), lds, s, st, fast,
+  return launch<dog_gate_solve_kernel>(dim3(st.B), dim3(TRI_NT), lds, s, st, fast,
                      ncols_jac, enable, path, colinfo, jac_count, done);
-  return hipGetLastError();
 }
 
 }  // namespace blsq

@@ -11,6 +11,7 @@
 // from exact == on computed minima (bounds.py:47-48).
 #include "blsq_device.h"
 #include "blsq_kernels.h"
+#include "blsq_launch.h"
 
 namespace blsq {
 
@@ -779,14 +780,12 @@ hipError_t launch_trf_step(const TrfState& st, const LmState* lm, const double* 
   const PublishArgs pa = pub ? *pub : PublishArgs{nullptr, 0, nullptr, 0};
   const size_t lds = sizeof(double) * 8 * (size_t)st.ld;
   if (st.n >= 128)
-    hipLaunchKernelGGL(trf_step_kernel<true>, dim3(st.B), dim3(NS_NT), lds, s, st,
+    return launch<trf_step_kernel<true>>(dim3(st.B), dim3(NS_NT), lds, s, st,
                        lm ? lm->fast : nullptr, lm ? lm->ph : nullptr, lm ? lm->sc : nullptr,
                        lm ? lm->st : nullptr, Delta, alpha_in, active_rtol, out, lm ? lm->active_count : nullptr, pa);
-  else
-    hipLaunchKernelGGL(trf_step_kernel<false>, dim3(st.B), dim3(NS_NT), lds, s, st,
+  return launch<trf_step_kernel<false>>(dim3(st.B), dim3(NS_NT), lds, s, st,
                        lm ? lm->fast : nullptr, lm ? lm->ph : nullptr, lm ? lm->sc : nullptr,
                        lm ? lm->st : nullptr, Delta, alpha_in, active_rtol, out, lm ? lm->active_count : nullptr, pa);
-  return hipGetLastError();
 }
 
 // ---- caller vectors -> state layout (device to device) -----------------------------------------

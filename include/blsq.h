@@ -271,6 +271,15 @@ int blsq_trf_debug_csne(blsq_trf_plan* plan, int32_t* on_tier /*B*/, double* eta
  * normal-equations fast path (Gram + equilibrated Cholesky, conditioning-gated), out[1] =
  * problems the gate handed to the Householder TSQR tree, since the last reset. */
 int blsq_debug_gram_stats(blsq_ctx* ctx, uint64_t out[2], int reset);
+/* Diagnostics: what the Gram launch of a batch of B problems of m x n does — decided on the host before anything is
+ * launched, so this needs no device (ctx: whose switches to read; NULL: the table's defaults).  has_final: the caller
+ * offers the final slot (a launch may then fuse the reduction of two row chunks).  out[0] family (0 direct, 1 gram8,
+ * 2 gram1, 3 gram16, 4 generic), out[1..3] its template key (direct: NTT, RHS, NWD; gram8: RHS; gram16: RHS, PAIR;
+ * generic: SLOTS, NCB), out[4..6] grid, out[7] block, out[8] dynamic LDS bytes, out[9] rhs_valu, out[10]
+ * rows_per_chunk, out[11] tile groups, out[12] reduction fused, out[13] row chunks; out[14..15] zero.  A problem's
+ * summation order follows from the family, the key, rhs_valu and rows_per_chunk: none of them depends on B.
+ * Returns non-zero for a shape the Gram front end does not take. */
+int blsq_debug_gram_route(const blsq_ctx* ctx, int m, int n, int B, int has_final, int32_t out[16]);
 
 /* Diagnostics: measured peaks of the device the ctx is bound to ("confirm on the
  * box with a copy kernel and an MFMA-f64 probe").
