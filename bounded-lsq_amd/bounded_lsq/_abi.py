@@ -100,6 +100,11 @@ SIGNATURES = {
     "blsq_loss_cost_dev": (C.c_int, [vp, C.c_int, C.c_int, C.c_int] + [vp] * 4),
     "blsq_loss_scale_dev": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, C.c_int] + [vp] * 5),
     "blsq_outer_set_loss": (C.c_int, [vp, C.c_int, vp]),
+    "blsq_cov_plan_create": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, C.POINTER(vp)]),
+    "blsq_cov_plan_destroy": (C.c_int, [vp]),
+    "blsq_cov_dev": (C.c_int, [vp] + [vp] * 5),
+    "blsq_cov": (C.c_int, [vp] + [vp] * 5),
+    "blsq_outer_covariance": (C.c_int, [vp, C.c_int, vp, vp, vp]),
 }
 
 _lib = None

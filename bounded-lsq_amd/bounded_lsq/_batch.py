@@ -24,6 +24,7 @@ from ._hip_step import (TrfStepSolver, DogboxStepSolver, SCALE_GIVEN, SCALE_JAC_
                         SCALE_JAC_UPDATE, raise_batch_status)
 from ._hostmath import (shift_into_interior, active_mask, cl_vector, check_loss, loss_rho, loss_cost,
                         loss_scale)
+from ._cov import check_covariance, attach as _attach_covariance, fill_results as _fill_covariance
 
 
 def _bounds_2d(bounds, B, n):
@@ -40,7 +41,7 @@ def _bounds_2d(bounds, B, n):
 def least_squares_batch(fun, x0, jac, bounds=(-np.inf, np.inf), method='trf',
                         ftol=EPS ** 0.5, xtol=EPS ** 0.5, gtol=EPS ** 0.5, max_nfev=None,
                         scaling=1.0, diff_step=None, args=(), kwargs=None, ctx=None, driver='host',
-                        loss='linear', f_scale=1.0):
+                        loss='linear', f_scale=1.0, covariance=False):
     """Solve B bound-constrained least-squares problems of identical shape.
 
     fun : callable, ``fun(X) -> (B, m)`` residuals for ``X`` (B, n)
@@ -53,11 +54,15 @@ def least_squares_batch(fun, x0, jac, bounds=(-np.inf, np.inf), method='trf',
              stay resident and only fresh Jacobians are uploaded and factored.
     loss, f_scale : robust loss as ``least_squares`` (scipy's): a name, or a callable ``z -> (3, m)`` (called per
              problem; driver='host' only); f_scale a positive scalar or broadcastable to (B,).
+    covariance : False, True or 'free' as ``least_squares``: ``x_covariance`` / ``x_covariance_rcond`` of every
+             problem from ONE batched call on the final Jacobians (driver='device': on the resident ones, only
+             B n^2 + 2 B numbers leave the GPU).
     Returns a list of B ``OptimizeResult`` (fields as ``least_squares``).
     """
     if method not in ('trf', 'dogbox'):
         raise ValueError("`method` must be 'trf' or 'dogbox'.")
     check_loss(loss, f_scale)
+    covariance = check_covariance(covariance)
     if callable(loss) and driver == 'device':
         raise ValueError("a callable `loss` runs on the host: use driver='host'.")
     X0 = np.array(x0, dtype=float)
@@ -126,7 +131,7 @@ def least_squares_batch(fun, x0, jac, bounds=(-np.inf, np.inf), method='trf',
     if driver == 'device':
         try:
             return _device_batch(fun, jac, X0, lb, ub, trf, use_jac, scaling, ftol, xtol, gtol,
-                                 max_nfev, ctx, loss if robust else None, fsc)
+                                 max_nfev, ctx, loss if robust else None, fsc, covariance)
         finally:
             _release_fd()
 
@@ -303,6 +308,8 @@ def least_squares_batch(fun, x0, jac, bounds=(-np.inf, np.inf), method='trf',
             r.message = TERMINATION_MESSAGES[r.status]
             r.success = r.status > 0
             results.append(r)
+        if covariance:
+            _attach_covariance(results, covariance, ctx=solver.ctx)
         return results
     finally:
         solver.close()
@@ -310,7 +317,7 @@ def least_squares_batch(fun, x0, jac, bounds=(-np.inf, np.inf), method='trf',
 
 
 def _device_batch(fun, jac, X0, lb, ub, trf, use_jac, scaling, ftol, xtol, gtol, max_nfev, ctx,
-                  loss=None, f_scale=None):
+                  loss=None, f_scale=None, covariance=False):
     """`least_squares_batch` on the device-resident outer driver (same results, same counts).  `loss`: a
     loss name other than 'linear' (None: sum f^2), applied on the device (blsq_outer_set_loss)."""
     from ._outer import OuterDriver
@@ -350,6 +357,7 @@ def _device_batch(fun, jac, X0, lb, ub, trf, use_jac, scaling, ftol, xtol, gtol,
             drv.set_loss(loss, f_scale)
         drv.start(X0, xs, lb, ub, scale, use_jac, ftol, xtol, gtol, max_nfev)
         R = drv.run_host(fun_cached, jac_checked)
+        cov_out = drv.covariance(free_only=(covariance == 'free')) if covariance else None
         Jfin = drv._down(drv.d_J, (B, m, n))
     finally:
         drv.close()
@@ -364,4 +372,6 @@ def _device_batch(fun, jac, X0, lb, ub, trf, use_jac, scaling, ftol, xtol, gtol,
         r.message = TERMINATION_MESSAGES[r.status]
         r.success = r.status > 0
         results.append(r)
+    if covariance:
+        _fill_covariance(results, covariance, *cov_out)
     return results

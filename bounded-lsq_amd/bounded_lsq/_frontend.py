@@ -12,6 +12,7 @@ from scipy.optimize._numdiff import approx_derivative
 
 from ._drivers import trf, dogbox
 from ._hostmath import in_bounds, prepare_bounds, check_loss
+from ._cov import check_covariance, attach as _attach_covariance
 
 EPS = np.finfo(float).eps
 
@@ -54,7 +55,8 @@ def _checked_scaling(scaling, x0):
 
 def least_squares(fun, x0, jac='2-point', bounds=(-np.inf, np.inf), method='trf',
                   ftol=EPS ** 0.5, xtol=EPS ** 0.5, gtol=EPS ** 0.5, max_nfev=None,
-                  scaling=1.0, diff_step=None, args=(), kwargs={}, options={}, loss='linear', f_scale=1.0):
+                  scaling=1.0, diff_step=None, args=(), kwargs={}, options={}, loss='linear', f_scale=1.0,
+                  covariance=False):
     """Minimise ``sum(fun(x)**2)`` subject to ``lb <= x <= ub``.
 
     Parameters and the returned ``OptimizeResult`` fields (x, fun, jac,
@@ -67,10 +69,18 @@ def least_squares(fun, x0, jac='2-point', bounds=(-np.inf, np.inf), method='trf'
     reference's sum f^2), 'huber', 'soft_l1', 'cauchy', 'arctan' or a callable ``z -> (3, m)``; the
     objective is then ``f_scale**2 * sum(rho(z))``, z = (f / f_scale)**2 (``obj_value``: twice scipy's
     ``cost``), ``fun`` the true residuals and ``jac`` the scaled Jacobian diag(w) J, as scipy returns it.
+
+    ``covariance``: False (``x_covariance`` is None, as the reference leaves it for these methods), True
+    (``x_covariance = inv(J^T J)`` at the solution, J = ``result.jac``: the reference's definition, ``curve_fit``'s
+    ``pcov`` with ``absolute_sigma=True``) or 'free' (the same over the variables with ``active_mask == 0``, zeros in
+    the rows and columns of the others), computed on the GPU (``bounded_lsq.covariance``).  A singular problem
+    keeps ``x_covariance = None``; ``x_covariance_rcond`` is the 1-norm reciprocal condition number of J's triangle
+    either way.  No variance scaling: multiply by ``obj_value / (m - n)`` for ``curve_fit``'s default.
     """
     if method not in ['trf', 'dogbox', 'lm']:
         raise ValueError("`method` must be 'trf', 'dogbox' or 'lm'.")
     check_loss(loss, f_scale)
+    covariance = check_covariance(covariance)
     f_scale = float(f_scale)
     if method == 'lm':
         raise NotImplementedError(
@@ -124,4 +134,6 @@ def least_squares(fun, x0, jac='2-point', bounds=(-np.inf, np.inf), method='trf'
                         loss=loss, f_scale=f_scale, **options)
     result.message = TERMINATION_MESSAGES[result.status]
     result.success = result.status > 0
+    if covariance:
+        _attach_covariance([result], covariance, ctx=options.get("ctx"))
     return result

@@ -109,6 +109,19 @@ class OuterDriver:
                                            "njev", "status")]), "blsq_outer_fetch")
         return out
 
+    def covariance(self, free_only=False):
+        """Covariance of every problem from the resident J (blsq_outer_covariance; after begin(), normally once the
+        loop has ended): ``(cov (B, n, n), rcond (B,), status (B,))``, NaN in cov where status is 1 (singular).
+        free_only: over the variables off their bounds only (dogbox: on_bound == 0; trf: the active mask of the
+        current x with rtol = xtol), zeros in the other rows and columns.  Only these outputs leave the GPU."""
+        B, n = self.B, self.n
+        cov = np.empty((B, n, n))
+        rcond = np.empty(B)
+        status = np.empty(B, dtype=np.int32)
+        self.ctx.check(self.ctx.lib.blsq_outer_covariance(self.h, 1 if free_only else 0, ptr(cov), ptr(rcond),
+                                                          ptr(status)), "blsq_outer_covariance")
+        return cov, rcond, status
+
     # ---- helpers for host-side callbacks -----------------------------------------------
     def _up(self, dptr, arr, shape=None, what="callback"):
         arr = np.ascontiguousarray(arr, dtype=np.float64)

@@ -1,0 +1,191 @@
+// C-ABI entry points (include/blsq.h): parameter covariance from the final Jacobian.
+//   tree (Householder TSQR of the plain J, or of J with its free columns first)  ->  cov_inverse  ->  cov_product
+#include "blsq_host.h"
+
+extern "C" int blsq_cov_plan_create(blsq_ctx* ctx, int B, int m, int n, blsq_cov_plan** out) {
+  if (!ctx) return -1;
+  if (!out) return ctx->bad(5, "out is NULL");
+  *out = nullptr;
+  if (B <= 0 || B > 65535) return ctx->bad(2, "B must be in 1..65535");
+  if (m <= 0) return ctx->bad(3, "m must be positive");
+  if (n <= 0) return ctx->bad(4, "n must be positive");
+  HIPCHK(ctx, hipSetDevice(ctx->device));
+  blsq_cov_plan* p = new blsq_cov_plan();
+  p->ctx = ctx; p->B = B; p->m = m; p->n = n;
+  p->tree.want_gram = false;
+  int rc = 0;
+  const int npad = round_up(n + 1, 16);
+  if (m > RMAX && !merge_fits(n) && npad + 16 <= RMAX) {
+    p->fold = true; p->NPAD = npad;
+    const size_t np = (size_t)npad / 16;
+    rc = alloc_all(ctx, {{&p->fR, sizeof(double) * (size_t)B * npad * npad, "hipMalloc(covariance triangles)"},
+                         {&p->fS, sizeof(double) * (size_t)B * RMAX * npad, "hipMalloc(covariance stack)"},
+                         {&p->fV, sizeof(double) * (size_t)B * np * RMAX * 16, "hipMalloc(V scratch)"},
+                         {&p->fT, sizeof(double) * (size_t)B * np * 256, "hipMalloc(T scratch)"}});
+    if (rc == 0) {
+      const hipError_t e = hipMemsetAsync(p->fS.p, 0, p->fS.bytes, ctx->stream);   // (columns >= n stay zero)
+      if (e != hipSuccess) rc = ctx->fail(e, "hipMemsetAsync(covariance stack)");
+    }
+  } else {
+    rc = p->tree.build(ctx, B, m, n, 0);
+    p->NPAD = p->tree.NPAD;
+  }
+  if (rc == 0) {
+    const size_t tri = sizeof(double) * (size_t)B * p->NPAD * p->NPAD;
+    rc = alloc_all(ctx, {{&p->zf, sizeof(double) * (size_t)B * m, "hipMalloc(covariance rhs)"},
+                         {&p->X, tri, "hipMalloc(covariance inverse)"}});
+  }
+  if (rc == 0) {
+    hipError_t e = hipMemsetAsync(p->zf.p, 0, p->zf.bytes, ctx->stream);
+    if (e == hipSuccess) e = hipMemsetAsync(p->X.p, 0, p->X.bytes, ctx->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
+    if (e != hipSuccess) rc = ctx->fail(e, "hipMemsetAsync(covariance plan)");
+  }
+  if (rc != 0) { blsq_cov_plan_destroy(p); return rc; }
+  *out = p;
+  return 0;
+}
+
+extern "C" int blsq_cov_plan_destroy(blsq_cov_plan* p) {
+  if (!p) return -1;
+  hipStreamSynchronize(p->ctx->stream);
+  p->tree.release();
+  for (DevBuf* b : {&p->fR, &p->fS, &p->fV, &p->fT, &p->zf, &p->X, &p->perm, &p->nfree, &p->Jp, &p->in_J, &p->in_act, &p->o_cov, &p->o_rcond,
+                    &p->o_status})
+    b->release();
+  delete p;
+  return 0;
+}
+
+namespace {
+// The triangle of a plan past the tree's merge capacity (m > 1024, n > 512): the first 1024 rows as one dense leaf,
+// then [R; next rows] again and again — every launch one workgroup per problem on at most 1024 rows.
+int cov_fold(blsq_cov_plan* p, const double* dJ) {
+  blsq_ctx* ctx = p->ctx;
+  const int B = p->B, m = p->m, n = p->n, NPAD = p->NPAD;
+  QrArgs q{};
+  q.opt = &ctx->opt;
+  q.N = n + 1; q.NPAD = NPAD; q.NPmax = NPAD / 16;
+  q.V = p->fV.as<double>(); q.T = p->fT.as<double>();
+  q.Rout = p->fR.as<double>();
+  q.A = dJ; q.strideA = (long)m * n; q.ldA = n; q.rowsA = RMAX;
+  q.F = p->zf.as<double>(); q.strideF = m;
+  q.rows_per_leaf = RMAX; q.RP = RMAX;
+  if (int rc_ = ctx->run(K_QR_LEAF, "launch_qr(covariance fold)", [&] { return launch_qr(q, 1, B, ctx->stream); }))
+    return rc_;
+  const int chunk = RMAX - NPAD;
+  for (int r = RMAX; r < m; r += chunk) {
+    const int c = std::min(chunk, m - r);
+    HIPCHK(ctx, hipMemcpy2DAsync(p->fS.p, sizeof(double) * (size_t)RMAX * NPAD, p->fR.p,
+                                 sizeof(double) * (size_t)NPAD * NPAD, sizeof(double) * (size_t)NPAD * NPAD, B,
+                                 hipMemcpyDeviceToDevice, ctx->stream));
+    QrArgs s = q;
+    s.A = p->fS.as<double>(); s.strideA = (long)RMAX * NPAD; s.ldA = NPAD; s.rowsA = NPAD + c;
+    s.F = nullptr; s.strideF = 0;                     // (column n of the stack: zeros)
+    s.rows_per_leaf = s.RP = round_up(NPAD + c, 16);
+    if (int rc_ = ctx->run(K_QR_MERGE, "launch_qr(covariance fold)", [&] {
+          const hipError_t e = launch_cov_stack(B, m, n, r, c, dJ, p->fS.as<double>(), RMAX, NPAD, ctx->stream);
+          return e == hipSuccess ? launch_qr(s, 1, B, ctx->stream) : e;
+        })) return rc_;
+  }
+  return 0;
+}
+}  // namespace
+
+namespace blsq_host {
+int cov_core(blsq_cov_plan* p, const double* dJ, const long long* dactive, int lda, double* dcov, double* drcond,
+             int* dstatus) {
+  blsq_ctx* ctx = p->ctx;
+  const int B = p->B, m = p->m, n = p->n, NPAD = p->NPAD;
+  const double* src = dJ;
+  const int* perm = nullptr;
+  const int* nfree = nullptr;
+  if (dactive) {
+    if (!p->perm.p) {
+      if (int rc_ = alloc_all(ctx, {{&p->perm, sizeof(int) * (size_t)B * n, "hipMalloc(covariance permutation)"},
+                                    {&p->nfree, sizeof(int) * (size_t)B, "hipMalloc(covariance free counts)"},
+                                    {&p->Jp, sizeof(double) * (size_t)B * m * n, "hipMalloc(covariance gather)"}}))
+        return rc_;
+    }
+    if (int rc_ = ctx->run(K_COV_GATHER, "launch_cov_gather", [&] {
+          const hipError_t e = launch_cov_perm(B, n, dactive, lda, p->perm.as<int>(), p->nfree.as<int>(), ctx->stream);
+          return e == hipSuccess ? launch_cov_gather(B, m, n, dJ, p->perm.as<int>(), p->Jp.as<double>(), ctx->stream)
+                                 : e;
+        })) return rc_;
+    src = p->Jp.as<double>(); perm = p->perm.as<int>(); nfree = p->nfree.as<int>();
+  }
+  if (int rc_ = p->fold ? cov_fold(p, src) : p->tree.run_levels(ctx, src, p->zf.as<double>(), n, nullptr)) return rc_;
+  if (int rc_ = ctx->run(K_COV_INVERSE, "launch_cov_inverse", [&] {
+        return launch_cov_inverse(B, m, n, NPAD, p->Rfinal(), p->X.as<double>(), nfree, dcov, drcond, dstatus,
+                                  ctx->stream);
+      })) return rc_;
+  return ctx->run(K_COV_PRODUCT, "launch_cov_product", [&] {
+    return launch_cov_product(B, n, NPAD, p->X.as<double>(), nfree, perm, dstatus, dcov, ctx->stream);
+  });
+}
+}  // namespace blsq_host
+
+extern "C" int blsq_cov_dev(blsq_cov_plan* p, const double* dJ, const int64_t* dactive, double* dcov, double* drcond,
+                            int32_t* dstatus) {
+  if (!p) return -1;
+  blsq_ctx* ctx = p->ctx;
+  if (!dJ) return ctx->bad(2, "J is NULL");
+  if (!dcov) return ctx->bad(4, "cov is NULL");
+  if (!drcond) return ctx->bad(5, "rcond is NULL");
+  if (!dstatus) return ctx->bad(6, "status is NULL");
+  HIPCHK(ctx, hipSetDevice(ctx->device));
+  return cov_core(p, dJ, reinterpret_cast<const long long*>(dactive), p->n, dcov, drcond, dstatus);
+}
+
+namespace {
+// the device outputs of a plan's host-pointer calls (allocated on first use)
+int cov_outputs(blsq_cov_plan* p) {
+  if (p->o_cov.p) return 0;
+  const size_t B = (size_t)p->B;
+  return alloc_all(p->ctx, {{&p->o_cov, sizeof(double) * B * p->n * p->n, "hipMalloc(covariance output)"},
+                            {&p->o_rcond, sizeof(double) * B, "hipMalloc(covariance output)"},
+                            {&p->o_status, sizeof(int) * B, "hipMalloc(covariance output)"}});
+}
+int cov_download(blsq_cov_plan* p, double* cov, double* rcond, int32_t* status) {
+  blsq_ctx* ctx = p->ctx;
+  HIPCHK(ctx, hipMemcpyAsync(cov, p->o_cov.p, p->o_cov.bytes, hipMemcpyDeviceToHost, ctx->stream));
+  HIPCHK(ctx, hipMemcpyAsync(rcond, p->o_rcond.p, p->o_rcond.bytes, hipMemcpyDeviceToHost, ctx->stream));
+  HIPCHK(ctx, hipMemcpyAsync(status, p->o_status.p, p->o_status.bytes, hipMemcpyDeviceToHost, ctx->stream));
+  HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+  return 0;
+}
+}  // namespace
+
+extern "C" int blsq_cov(blsq_cov_plan* p, const double* J, const int64_t* active, double* cov, double* rcond,
+                        int32_t* status) {
+  if (!p) return -1;
+  blsq_ctx* ctx = p->ctx;
+  if (!J) return ctx->bad(2, "J is NULL");
+  if (!cov) return ctx->bad(4, "cov is NULL");
+  if (!rcond) return ctx->bad(5, "rcond is NULL");
+  if (!status) return ctx->bad(6, "status is NULL");
+  HIPCHK(ctx, hipSetDevice(ctx->device));
+  const size_t B = (size_t)p->B, nJ = sizeof(double) * B * p->m * p->n, nA = sizeof(int64_t) * B * p->n;
+  if (!p->in_J.p)
+    if (int rc_ = alloc_all(ctx, {{&p->in_J, nJ, "hipMalloc(covariance input)"}})) return rc_;
+  if (active && !p->in_act.p)
+    if (int rc_ = alloc_all(ctx, {{&p->in_act, nA, "hipMalloc(covariance input)"}})) return rc_;
+  if (int rc_ = cov_outputs(p)) return rc_;
+  HIPCHK(ctx, hipMemcpyAsync(p->in_J.p, J, nJ, hipMemcpyHostToDevice, ctx->stream));
+  if (active) HIPCHK(ctx, hipMemcpyAsync(p->in_act.p, active, nA, hipMemcpyHostToDevice, ctx->stream));
+  if (int rc_ = cov_core(p, p->in_J.as<double>(), active ? p->in_act.as<long long>() : nullptr, p->n,
+                         p->o_cov.as<double>(), p->o_rcond.as<double>(), p->o_status.as<int>()))
+    return rc_;
+  return cov_download(p, cov, rcond, status);
+}
+
+namespace blsq_host {
+// blsq_outer_covariance (blsq_outer.hip) on the driver's resident J: mask (device, int64 [B][lda]) or nullptr
+int cov_to_host(blsq_cov_plan* p, const double* dJ, const long long* dmask, int lda, double* cov, double* rcond,
+                int32_t* status) {
+  if (int rc_ = cov_outputs(p)) return rc_;
+  if (int rc_ = cov_core(p, dJ, dmask, lda, p->o_cov.as<double>(), p->o_rcond.as<double>(), p->o_status.as<int>()))
+    return rc_;
+  return cov_download(p, cov, rcond, status);
+}
+}  // namespace blsq_host

@@ -43,7 +43,7 @@ int QrTree::build(blsq_ctx* ctx, int B_, int rows, int n_, size_t extra_rp_rows)
   if (int rc_ = alloc_all(ctx, {{&V, sizeof(double) * max_slot_rows * NP * 16, "hipMalloc(V scratch)"},
                                 {&T, sizeof(double) * max_slots * NP * 256, "hipMalloc(T scratch)"}}))
     return rc_;
-  gram = gram_supported(rows, n) && ctx->opt.on(OPT_GRAM);
+  gram = want_gram && gram_supported(rows, n) && ctx->opt.on(OPT_GRAM);
   if (gram) {
     gram_nchunk = gram_chunks(rows);
     const size_t tri = sizeof(double) * (size_t)B * NPAD * NPAD;

@@ -2,7 +2,7 @@
 // the factorisation front end of a plan (QrTree: Gram / certificate / CholeskyQR2 / Householder tree), the CSNE tier's
 // host state (CsneTier) and the plan structures.  blsq_ctx.hip: contexts, memory, timing, communicator, diagnostics;
 // blsq_front.hip: the bodies of QrTree and CsneTier; blsq_trf.hip: TRF and the row-split (TSQR) plans; blsq_dogbox.hip:
-// dogbox plans; blsq_outer.hip: the batched outer drivers and finite differences.
+// dogbox plans; blsq_outer.hip: the batched outer drivers and finite differences; blsq_cov.hip: covariance plans.
 // Internal: nothing here is part of the ABI.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -28,11 +28,11 @@ constexpr int RMAX = QR_MAX_TILES * 16;   // rows a workgroup can stage (qr_pane
 
 enum Slot { K_QR_LEAF = 0, K_QR_MERGE, K_PREP, K_QR_AUG, K_JACOBI, K_STEP, K_LM_GATE, K_LM_QR, K_LM_SOLVE,
             K_GRAM, K_GRAM_CHOL, K_GRAM_GATE, K_AUG_CHOL, K_LM_CHOL, K_CQR2_APPLY, K_CQR2_COMBINE, K_CSNE_PASS,
-            K_CSNE_FIX, K_LOSS_COST, K_LOSS_SCALE, K_NSLOT };
+            K_CSNE_FIX, K_COV_GATHER, K_COV_INVERSE, K_COV_PRODUCT, K_LOSS_COST, K_LOSS_SCALE, K_NSLOT };
 static const char* const kSlotNames[K_NSLOT] = {"qr_leaf", "qr_merge", "prep", "qr_aug", "jacobi_svd", "step",
                                    "lm_gate", "lm_qr", "lm_solve", "gram", "gram_chol", "gram_gate",
                                    "aug_chol", "lm_chol", "cqr2_apply", "cqr2_combine", "csne_pass", "csne_fix",
-                                   "loss_cost", "loss_scale"};
+                                   "cov_gather", "cov_inverse", "cov_product", "loss_cost", "loss_scale"};
 
 inline int round_up(int v, int q) { return (v + q - 1) / q * q; }
 // rows of the stacked systems [R D; E] / [R_aug; sqrt(alpha) I]: two blocks of
@@ -262,6 +262,7 @@ struct QrTree {
   DevBuf V, T;                      // scratch shared by all QR launches of the plan
   // normal-equations fast path (gram_kernels.hip, chol_reg.hip, chol_rl.hip); problems that fail its gate use the levels
   bool gram = false;
+  bool want_gram = true;            // false (set before build): Householder tree only, no Gram buffers (covariance plans)
   int gram_nchunk = 1;
   DevBuf gram_part, gram_dsc, gram_ints;   // partial Grams, column scales, [B] fallback mask + count
   DevBuf gram_keep;                 // [B][NPAD*NPAD] the Grams themselves (kept: the trust-region
@@ -602,5 +603,30 @@ int dog_factor_core(blsq_dogbox_plan* p, const double* dJ, const double* df, int
 int dog_resolve(blsq_dogbox_plan* p, bool* redo);
 // every verdict an optimistic factor call left pending on a plan of this ctx is read, and a wrong guess repaired
 int ctx_resolve_pending(blsq_ctx* ctx);
+}  // namespace blsq_host
+
+// Covariance plan (blsq_cov.hip): the Householder tree of a plain J and the n-space tail of cov_kernels.hip
+struct blsq_cov_plan {
+  blsq_ctx* ctx = nullptr;
+  int B = 0, m = 0, n = 0;
+  QrTree tree;                      // want_gram = false: run_levels only
+  // m > 1024 with n > 512 is past the tree's merge capacity: such a plan folds the rows in sequentially instead —
+  // the first 1024 rows, then [R; next rows] as a dense leaf of at most 1024 rows, until J is used up
+  bool fold = false;
+  int NPAD = 0;                     // leading dimension of the triangles (tree.NPAD, or the fold's)
+  DevBuf fR, fS, fV, fT;            // fold: triangles [B][NPAD*NPAD], stack [B][1024][NPAD], reflector scratch
+  const double* Rfinal() const { return fold ? fR.as<double>() : tree.Rfinal(); }
+  DevBuf zf;                        // [B][m] zeros: the right-hand side column the tree carries along
+  DevBuf X;                         // [B][NPAD*NPAD] the explicit inverse
+  DevBuf perm, nfree, Jp;           // 'free' mode, allocated on first use: permutation, free counts, gathered J
+  DevBuf in_J, in_act, o_cov, o_rcond, o_status;   // staging of the host-pointer call, allocated on first use
+};
+namespace blsq_host {
+// the whole covariance call on device pointers; dactive: int64 [B][lda] or nullptr
+int cov_core(blsq_cov_plan* p, const double* dJ, const long long* dactive, int lda, double* dcov, double* drcond,
+             int* dstatus);
+// ... and with host outputs through the plan's own device buffers (blsq_outer_covariance)
+int cov_to_host(blsq_cov_plan* p, const double* dJ, const long long* dmask, int lda, double* cov, double* rcond,
+                int32_t* status);
 }  // namespace blsq_host
 

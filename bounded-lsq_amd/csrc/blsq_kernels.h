@@ -551,6 +551,22 @@ hipError_t launch_loss_scale(int B, int m, int n, int loss, const double* fscale
                              double* fsc, const int* mask, hipStream_t s);
 
 
+// ------------------------------------------- parameter covariance (7g) ----
+// cov_kernels.hip (blsq_cov_dev).  active: int64 [B][lda] (non-zero = on a bound); perm [B][n] free columns first,
+// nfree [B]; nfree / perm may be nullptr in the inverse / product launches (all variables, identity).  R and X are
+// [B][NPAD][NPAD]; the inverse launch writes rcond, status and the NaN / zero fill of cov, the product launch the rest.
+hipError_t launch_cov_perm(int B, int n, const long long* active, int lda, int* perm, int* nfree, hipStream_t s);
+hipError_t launch_cov_trf_mask(int B, int n, int ld, double rtol, const double* x, const double* lb, const double* ub,
+                               long long* mask, hipStream_t s);
+hipError_t launch_cov_gather(int B, int m, int n, const double* J, const int* perm, double* Jp, hipStream_t s);
+// rows [r0, r0 + c) of every J [B][m][n] under the triangle of a stack S [B][srows][ld] (rows ld .. ld + c - 1)
+hipError_t launch_cov_stack(int B, int m, int n, int r0, int c, const double* J, double* S, int srows, int ld,
+                            hipStream_t s);
+hipError_t launch_cov_inverse(int B, int m, int n, int NPAD, const double* R, double* X, const int* nfree, double* cov,
+                              double* rcond, int* status, hipStream_t s);
+hipError_t launch_cov_product(int B, int n, int NPAD, const double* X, const int* nfree, const int* perm,
+                              const int* status, double* cov, hipStream_t s);
+
 // ------------------------------------- finite-difference Jacobians (8f-2) ----
 // method: 2 = '2-point', 3 = '3-point'.  X [B][P][n] with P = n (2) or 2n (3); F [B][P][m].
 hipError_t launch_fd_points(int B, int n, int method, const double* x, const double* lb,

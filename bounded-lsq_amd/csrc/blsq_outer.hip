@@ -12,6 +12,9 @@ struct blsq_outer {
   DevBuf x0, xc, xt, f, ft, J, dvec, ivec, counts;
   DevBuf fsc, lobj, fscale;            // robust loss only: scaled f [B][m], objective [B], f_scale [B]
   int loss = BLSQ_LOSS_LINEAR;
+  blsq_cov_plan* cov = nullptr;        // blsq_outer_covariance: created on first use
+  DevBuf covmask;                      // [B][n] int64: the active mask of a 'trf' driver (from x, as the host reports it)
+  bool scaled_early = false;           // robust loss: the accepted problems' J were scaled by blsq_outer_covariance
   OuterState st{};
   int jac_scaling = 0;
   double xtol = 0.0;
@@ -72,6 +75,8 @@ extern "C" int blsq_outer_destroy(blsq_outer* o) {
   if (!o) return 0;
   if (o->trf) blsq_trf_plan_destroy(o->trf);
   if (o->dog) blsq_dogbox_plan_destroy(o->dog);
+  if (o->cov) blsq_cov_plan_destroy(o->cov);
+  o->covmask.release();
   o->x0.release(); o->xc.release(); o->xt.release(); o->f.release(); o->ft.release();
   o->J.release(); o->dvec.release(); o->ivec.release(); o->counts.release();
   o->fsc.release(); o->lobj.release(); o->fscale.release();
@@ -124,7 +129,7 @@ extern "C" int blsq_outer_start(blsq_outer* o, const double* x0, const double* x
   }
   st.ftol = ftol; st.xtol = xtol; st.gtol = gtol; st.max_nfev = max_nfev;
   o->xtol = xtol; o->jac_scaling = jac_scaling ? 1 : 0;
-  o->started = true; o->begun = false; o->last_accepted = 0;
+  o->started = true; o->begun = false; o->last_accepted = 0; o->scaled_early = false;
   HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
   return 0;
 }
@@ -210,7 +215,8 @@ extern "C" int blsq_outer_propose(blsq_outer* o, int32_t* n_active) {
   HIPCHK(ctx, hipSetDevice(ctx->device));
   int rc;
   if (o->last_accepted > 0) {            // fresh Jacobians: factor those problems only
-    if (o->loss != BLSQ_LOSS_LINEAR && (rc = outer_loss_scale(o, o->st.accepted))) return rc;
+    if (o->loss != BLSQ_LOSS_LINEAR && !o->scaled_early && (rc = outer_loss_scale(o, o->st.accepted))) return rc;
+    o->scaled_early = false;
     rc = outer_factor(o, o->jac_scaling ? BLSQ_SCALE_JAC_UPDATE : BLSQ_SCALE_GIVEN,
                       o->st.ncols_fac);
     if (rc) return rc;
@@ -281,6 +287,43 @@ extern "C" int blsq_outer_fetch(blsq_outer* o, double* x, double* f, double* obj
   }
   HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
   return 0;
+}
+
+// Covariance of every problem from the driver's resident J.  Under a robust loss J must hold diag(w) J for EVERY
+// problem: blsq_outer_propose scales the Jacobians a judge has just accepted before it factors them, so between a
+// judge and the next propose those are still unscaled — they are scaled here, once (propose then leaves them alone).
+// The mask of free_only: dogbox's on_bound; for 'trf' find_active_constraints(x, lb, ub, rtol = xtol) (trf.py:257), the
+// mask the host reports for the x blsq_outer_fetch returns.
+extern "C" int blsq_outer_covariance(blsq_outer* o, int free_only, double* cov, double* rcond, int32_t* status) {
+  if (!o) return -1;
+  blsq_ctx* ctx = o->ctx;
+  if (!o->begun) return ctx->bad(1, "blsq_outer_begin has not been called");
+  if (!cov) return ctx->bad(3, "cov is NULL");
+  if (!rcond) return ctx->bad(4, "rcond is NULL");
+  if (!status) return ctx->bad(5, "status is NULL");
+  HIPCHK(ctx, hipSetDevice(ctx->device));
+  int rc;
+  if ((rc = ctx_resolve_pending(ctx))) return rc;
+  if (!o->cov && (rc = blsq_cov_plan_create(ctx, o->B, o->m, o->n, &o->cov))) return rc;
+  if (o->loss != BLSQ_LOSS_LINEAR && o->last_accepted > 0 && !o->scaled_early) {
+    if ((rc = outer_loss_scale(o, o->st.accepted))) return rc;
+    o->scaled_early = true;
+  }
+  const long long* mask = nullptr;
+  int lda = o->n;
+  if (free_only) {
+    if (o->method == 1) { mask = reinterpret_cast<const long long*>(o->st.on_bound); lda = o->ld; }
+    else {
+      if (!o->covmask.p)
+        if ((rc = alloc_all(ctx, {{&o->covmask, sizeof(long long) * (size_t)o->B * o->n, "hipMalloc(trf mask)"}})))
+          return rc;
+      const hipError_t e = launch_cov_trf_mask(o->B, o->n, o->ld, o->xtol, o->st.xc, o->st.lb, o->st.ub,
+                                               o->covmask.as<long long>(), ctx->stream);
+      if (e != hipSuccess) return ctx->fail(e, "launch_cov_trf_mask");
+      mask = o->covmask.as<long long>();
+    }
+  }
+  return cov_to_host(o->cov, o->J.as<double>(), mask, lda, cov, rcond, status);
 }
 
 // ================================================== robust loss functions ===

@@ -1,0 +1,342 @@
+// Parameter covariance from the final Jacobian (blsq_cov*, blsq_outer_covariance).
+//
+// C = (J^T J)^-1 = R^-1 R^-T with R the Householder triangle of J (the TSQR tree, qr_panel.hip: a Gram-Cholesky
+// triangle squares the conditioning and is not used here).  With a mask of active variables the free columns of J are
+// moved to the front first: the leading nfree x nfree block of the triangle of the permuted matrix is the triangle
+// of J_F, and C is scattered back through the permutation with zeros in the rows and columns of active variables.
+//
+//   cov_perm_kernel      perm [B][n] (free columns first, both groups in ascending order) and nfree [B] from the
+//                        int64 mask; cov_trf_mask_kernel: the mask of a TRF driver from its x (find_active_constraints)
+//   cov_gather_kernel    one streaming pass: Jp[r][c] = J[r][perm[c]].  Row-chunk grid as loss_scale_kernel (one tall
+//                        problem fills the chip), 16-byte stores where n is even
+//   cov_inverse_kernel   one workgroup per problem: pivot test and ||R||_1, then X = R^-1 by blocked back substitution
+//                        over 16 x 16 tiles — all diagonal tiles first (one wave each, a lane per column, registers),
+//                        then block column j = 1 .. NT-1:  X_ij = -(sum_{k=i}^{j-1} X_ik R_kj) X_jj, the tiles i < j
+//                        dealt over the waves, every product on the FP64 MFMA pipe.  X lives in a plan-owned slot
+//                        [NPAD][NPAD] per problem (L2-resident: n = 256 does not fit LDS).  ||X||_1, rcond_1 and the
+//                        verdict follow; a singular problem's output is filled with NaN, a masked one's with zeros
+//   cov_product_kernel   C_F = X X^T, tile (i, j >= i) = sum_{k >= j} X_ik X_jk^T on the MFMA pipe, written with its
+//                        mirror image through perm: exactly symmetric by construction
+//
+// Every sum has a fixed order and nothing is atomic: a problem's bits depend on its own J, mask, m and n only.
+#include "../../include/blsq.h"
+#include "blsq_device.h"
+#include "blsq_kernels.h"
+#include "blsq_launch.h"
+
+namespace blsq {
+
+static constexpr int COV_NT = 512;
+static constexpr int COV_NW = COV_NT / WAVE;
+static constexpr int COV_PNT = 256;               // product kernel: four waves, one output tile each at a time
+static constexpr int COV_PNW = COV_PNT / WAVE;
+static constexpr int COV_GNT = 256;
+static constexpr int COV_TARGET_ELEMS = 8192;     // J doubles per gather workgroup
+static constexpr double COV_EPS = 2.220446049250313e-16;
+
+__device__ __forceinline__ v4d cov_mfma(double a, double b, v4d c) {
+  return __builtin_amdgcn_mfma_f64_16x16x4f64(a, b, c, 0, 0, 0);
+}
+
+// ---- masks and permutations --------------------------------------------------------------------
+__global__ __launch_bounds__(256) void cov_perm_kernel(int B, int n, const long long* __restrict__ active, int lda,
+                                                       int* __restrict__ perm, int* __restrict__ nfree) {
+  const int b = blockIdx.x * blockDim.x + threadIdx.x;
+  if (b >= B) return;
+  const long long* a = active + (long)b * lda;
+  int* p = perm + (long)b * n;
+  int k = 0;
+  for (int j = 0; j < n; ++j)
+    if (a[j] == 0) p[k++] = j;
+  nfree[b] = k;
+  for (int j = 0; j < n; ++j)
+    if (a[j] != 0) p[k++] = j;
+}
+
+// bounds.py:51-76 (find_active_constraints) with rtol, as the host drivers report it for 'trf'
+__global__ __launch_bounds__(256) void cov_trf_mask_kernel(int B, int n, int ld, double rtol,
+                                                           const double* __restrict__ x, const double* __restrict__ lb,
+                                                           const double* __restrict__ ub, long long* __restrict__ mask) {
+  const long idx = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (idx >= (long)B * n) return;
+  const int b = (int)(idx / n), j = (int)(idx - (long)b * n);
+  const double xv = x[idx], l = lb[(long)b * ld + j], u = ub[(long)b * ld + j];
+  const double dl = xv - l, du = u - xv;
+  const bool lower_nearer = dl < du;
+  const bool on_l = dl < rtol * fmax(1.0, fabs(l));
+  const bool on_u = du < rtol * fmax(1.0, fabs(u));
+  long long v = 0;
+  if (lower_nearer && on_l) v = -1;
+  if (!lower_nearer && on_u) v = 1;
+  mask[idx] = v;
+}
+
+// ---- gather ------------------------------------------------------------------------------------
+template <bool VEC>
+__global__ __launch_bounds__(COV_GNT) void cov_gather_kernel(int m, int n, int rows, int chunks,
+                                                             const double* __restrict__ J,
+                                                             const int* __restrict__ perm, double* __restrict__ Jp) {
+  extern __shared__ int psh[];                       // [n]
+  const int b = blockIdx.x / chunks, r0 = (blockIdx.x - b * chunks) * rows, tid = threadIdx.x;
+  const int nr = min(rows, m - r0);
+  for (int j = tid; j < n; j += COV_GNT) psh[j] = perm[(long)b * n + j];
+  __syncthreads();
+  const long base = ((long)b * m + r0) * n;
+  const double* src = J + base;
+  const unsigned un = (unsigned)n;
+  if (VEC) {
+    typedef double v2d __attribute__((ext_vector_type(2)));
+    v2d* dst = reinterpret_cast<v2d*>(Jp + base);
+    const int L = (nr * n) >> 1;
+    for (int k = tid; k < L; k += COV_GNT) {
+      const unsigned e = 2u * (unsigned)k, r = e / un, c = e - r * un;   // (n even: c and c + 1 are in one row)
+      v2d v;
+      v.x = src[r * un + (unsigned)psh[c]];
+      v.y = src[r * un + (unsigned)psh[c + 1]];
+      dst[k] = v;
+    }
+  } else {
+    double* dst = Jp + base;
+    const int L = nr * n;
+    for (int k = tid; k < L; k += COV_GNT) {
+      const unsigned r = (unsigned)k / un, c = (unsigned)k - r * un;
+      dst[k] = src[r * un + (unsigned)psh[c]];
+    }
+  }
+}
+
+// rows [r0, r0 + c) of J under the triangle of the stack (sequential fold of a plan past the tree's merge capacity)
+__global__ __launch_bounds__(COV_GNT) void cov_stack_kernel(int m, int n, int r0, int c, const double* __restrict__ J,
+                                                            double* __restrict__ S, int srows, int ld) {
+  const int b = blockIdx.y, i = blockIdx.x;          // i < c
+  const double* src = J + ((long)b * m + r0 + i) * n;
+  double* dst = S + ((long)b * srows + ld + i) * ld;
+  for (int j = threadIdx.x; j < n; j += COV_GNT) dst[j] = src[j];
+}
+
+// ---- inverse -----------------------------------------------------------------------------------
+// max over the workgroup in a fixed tree; NaN / Inf inputs are the caller's business (it tests them first)
+template <int NT>
+__device__ __forceinline__ double cov_wg_max(double v, double* red) {
+  const int tid = threadIdx.x;
+  __syncthreads();
+  red[tid] = v;
+  __syncthreads();
+  for (int h = NT / 2; h > 0; h >>= 1) {
+    if (tid < h) red[tid] = fmax(red[tid], red[tid + h]);
+    __syncthreads();
+  }
+  return red[0];
+}
+
+// column sums of |T| over the leading nf x nf upper triangle (thread per column, rows in ascending order)
+__device__ __forceinline__ double cov_norm1_part(const double* T, int ld, int nf, int* bad) {
+  double best = 0.0;
+  for (int c = threadIdx.x; c < nf; c += COV_NT) {
+    double s = 0.0;
+    for (int r = 0; r <= c; ++r) s += fabs(T[(long)r * ld + c]);
+    if (!is_finite(s)) *bad = 1;
+    best = fmax(best, s);
+  }
+  return best;
+}
+
+__device__ __forceinline__ void cov_fill(double* C, long count, double v) {
+  for (long k = threadIdx.x; k < count; k += COV_NT) C[k] = v;
+}
+
+__global__ __launch_bounds__(COV_NT) void cov_inverse_kernel(int m, int n, int NPAD, const double* __restrict__ Rall,
+                                                             double* Xall, const int* __restrict__ nfree,
+                                                             double* __restrict__ cov, double* __restrict__ rcond,
+                                                             int* __restrict__ status) {
+  __shared__ double red[COV_NT];
+  __shared__ double tsh[COV_NW][256];               // per wave: a staged tile (row-major)
+  const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63;
+  const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int nf = nfree ? nfree[b] : n;
+  const int ld = NPAD;
+  const double* R = Rall + (long)b * NPAD * NPAD;
+  double* X = Xall + (long)b * NPAD * NPAD;
+  double* C = cov + (long)b * n * n;
+  const long nn = (long)n * n;
+  if (nf == 0) {                                     // every variable on a bound: nothing to invert
+    cov_fill(C, nn, 0.0);
+    if (tid == 0) { rcond[b] = 1.0; status[b] = 0; }
+    return;
+  }
+  // 1. pivots and ||R||_1
+  int bad = 0;
+  for (int c = tid; c < nf; c += COV_NT) {
+    const double p = R[(long)c * ld + c];
+    if (!(p != 0.0) || !is_finite(p)) bad = 1;
+  }
+  const double rpart = cov_norm1_part(R, ld, nf, &bad);
+  bad = __syncthreads_or(bad);
+  if (bad) {                                         // uniform
+    cov_fill(C, nn, __builtin_nan(""));
+    if (tid == 0) { rcond[b] = 0.0; status[b] = 1; }
+    return;
+  }
+  const double rnorm = cov_wg_max<COV_NT>(rpart, red);
+  const int NTl = (nf + 15) >> 4;                    // tiles of the free block (NTl * 16 <= NPAD: nf <= n < NPAD)
+  // R restricted to the free block and padded with the identity up to the tile edge
+  auto ldR = [&](int r, int c) -> double {
+    return (r < nf && c < nf) ? R[(long)r * ld + c] : ((r == c) ? 1.0 : 0.0);
+  };
+  const int lr = lane >> 4, lc = lane & 15;
+  double* ts = tsh[w];
+  // 2. diagonal tiles: X_jj = R_jj^-1, a wave per tile, lane c < 16 solves R_jj x = e_c in registers
+  for (int j = w; j < NTl; j += COV_NW) {
+    const int o = 16 * j;
+#pragma unroll
+    for (int q = 0; q < 4; ++q) ts[(lr + 4 * q) * 16 + lc] = ldR(o + lr + 4 * q, o + lc);
+    __builtin_amdgcn_wave_barrier();
+    double x[16];
+#pragma unroll
+    for (int i = 15; i >= 0; --i) {
+      double s = (i == lc) ? 1.0 : 0.0;
+#pragma unroll
+      for (int k = i + 1; k < 16; ++k) s = fma(-ts[i * 16 + k], x[k], s);
+      x[i] = s / ts[i * 16 + i];
+    }
+    if (lane < 16) {
+#pragma unroll
+      for (int i = 0; i < 16; ++i) X[(long)(o + i) * ld + o + lc] = (i <= lc) ? x[i] : 0.0;
+    }
+    __builtin_amdgcn_wave_barrier();
+  }
+  __threadfence_block();
+  __syncthreads();
+  // 3. block columns
+  for (int j = 1; j < NTl; ++j) {
+    for (int i = w; i < j; i += COV_NW) {
+      v4d acc = {0.0, 0.0, 0.0, 0.0};
+      for (int k = i; k < j; ++k) {                  // T = sum_k X_ik R_kj
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+          const double a = X[(long)(16 * i + lc) * ld + 16 * k + 4 * q + lr];
+          const double bb = ldR(16 * k + 4 * q + lr, 16 * j + lc);
+          acc = cov_mfma(a, bb, acc);
+        }
+      }
+#pragma unroll
+      for (int g = 0; g < 4; ++g) ts[(lr + 4 * g) * 16 + lc] = acc[g];
+      __builtin_amdgcn_wave_barrier();
+      v4d out = {0.0, 0.0, 0.0, 0.0};
+#pragma unroll
+      for (int q = 0; q < 4; ++q) {                  // X_ij = -T X_jj
+        const double a = ts[lc * 16 + 4 * q + lr];
+        const double bb = X[(long)(16 * j + 4 * q + lr) * ld + 16 * j + lc];
+        out = cov_mfma(a, bb, out);
+      }
+#pragma unroll
+      for (int g = 0; g < 4; ++g) X[(long)(16 * i + lr + 4 * g) * ld + 16 * j + lc] = -out[g];
+      __builtin_amdgcn_wave_barrier();
+    }
+    __threadfence_block();
+    __syncthreads();
+  }
+  // 4. ||X||_1, rcond_1, verdict
+  int xbad = 0;
+  const double xpart = cov_norm1_part(X, ld, nf, &xbad);
+  xbad = __syncthreads_or(xbad);
+  const double xnorm = cov_wg_max<COV_NT>(xpart, red);
+  double rc = 0.0;
+  if (!xbad) rc = 1.0 / (rnorm * xnorm);
+  const double thresh = COV_EPS * (double)(m > nf ? m : nf);
+  const int sing = !(rc >= thresh);
+  if (tid == 0) { rcond[b] = rc; status[b] = sing; }
+  if (sing) cov_fill(C, nn, __builtin_nan(""));
+  else if (nf < n) cov_fill(C, nn, 0.0);
+}
+
+// ---- product -----------------------------------------------------------------------------------
+__global__ __launch_bounds__(COV_PNT) void cov_product_kernel(int n, int NPAD, const double* __restrict__ Xall,
+                                                              const int* __restrict__ nfree,
+                                                              const int* __restrict__ perm,
+                                                              const int* __restrict__ status,
+                                                              double* __restrict__ cov) {
+  const int i = blockIdx.x, b = blockIdx.y, lane = threadIdx.x & 63;
+  const int w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  if (status[b] != 0) return;                        // uniform: the inverse kernel has filled the output
+  const int nf = nfree ? nfree[b] : n;
+  const int NTl = (nf + 15) >> 4;
+  if (i >= NTl) return;
+  const int ld = NPAD;
+  const double* X = Xall + (long)b * NPAD * NPAD;
+  const int* pm = perm ? perm + (long)b * n : nullptr;
+  double* C = cov + (long)b * n * n;
+  const int lr = lane >> 4, lc = lane & 15;
+  for (int j = i + w; j < NTl; j += COV_PNW) {
+    v4d acc = {0.0, 0.0, 0.0, 0.0};
+    const double* xa = X + (long)(16 * i + lc) * ld + lr;
+    const double* xb = X + (long)(16 * j + lc) * ld + lr;
+    for (int k = j; k < NTl; ++k) {
+      double a[4], bb[4];
+#pragma unroll
+      for (int q = 0; q < 4; ++q) { a[q] = xa[16 * k + 4 * q]; bb[q] = xb[16 * k + 4 * q]; }
+#pragma unroll
+      for (int q = 0; q < 4; ++q) acc = cov_mfma(a[q], bb[q], acc);
+    }
+#pragma unroll
+    for (int g = 0; g < 4; ++g) {
+      const int r = 16 * i + lr + 4 * g, c = 16 * j + lc;
+      if (r < nf && c < nf && r <= c) {              // (i < j: always r < c)
+        const int pr = pm ? pm[r] : r, pc = pm ? pm[c] : c;
+        C[(long)pr * n + pc] = acc[g];
+        C[(long)pc * n + pr] = acc[g];
+      }
+    }
+  }
+}
+
+// ---- launches ----------------------------------------------------------------------------------
+hipError_t launch_cov_perm(int B, int n, const long long* active, int lda, int* perm, int* nfree, hipStream_t s) {
+  hipLaunchKernelGGL(cov_perm_kernel, dim3((B + 255) / 256), dim3(256), 0, s, B, n, active, lda, perm, nfree);
+  return hipGetLastError();
+}
+
+hipError_t launch_cov_trf_mask(int B, int n, int ld, double rtol, const double* x, const double* lb, const double* ub,
+                               long long* mask, hipStream_t s) {
+  const long tot = (long)B * n;
+  hipLaunchKernelGGL(cov_trf_mask_kernel, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, s, B, n, ld, rtol, x, lb,
+                     ub, mask);
+  return hipGetLastError();
+}
+
+hipError_t launch_cov_gather(int B, int m, int n, const double* J, const int* perm, double* Jp, hipStream_t s) {
+  int rows = COV_TARGET_ELEMS / n;
+  rows = rows < 1 ? 1 : rows;
+  if (rows > m) rows = m;
+  const int chunks = (m + rows - 1) / rows;
+  const long grid = (long)B * chunks;
+  if (grid > 0x7fffffffL) return hipErrorInvalidValue;
+  const size_t lds = sizeof(int) * (size_t)n;
+  const bool vec = (n % 2 == 0) && ((reinterpret_cast<uintptr_t>(Jp) & 15) == 0);
+  if (vec) return launch<cov_gather_kernel<true>>(dim3((unsigned)grid), dim3(COV_GNT), lds, s, m, n, rows, chunks, J,
+                                                  perm, Jp);
+  return launch<cov_gather_kernel<false>>(dim3((unsigned)grid), dim3(COV_GNT), lds, s, m, n, rows, chunks, J, perm, Jp);
+}
+
+hipError_t launch_cov_stack(int B, int m, int n, int r0, int c, const double* J, double* S, int srows, int ld,
+                            hipStream_t s) {
+  if (c <= 0 || r0 < 0 || r0 + c > m || ld + c > srows || n > ld || B > 65535) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(cov_stack_kernel, dim3(c, B), dim3(COV_GNT), 0, s, m, n, r0, c, J, S, srows, ld);
+  return hipGetLastError();
+}
+
+hipError_t launch_cov_inverse(int B, int m, int n, int NPAD, const double* R, double* X, const int* nfree, double* cov,
+                              double* rcond, int* status, hipStream_t s) {
+  hipLaunchKernelGGL(cov_inverse_kernel, dim3(B), dim3(COV_NT), 0, s, m, n, NPAD, R, X, nfree, cov, rcond, status);
+  return hipGetLastError();
+}
+
+hipError_t launch_cov_product(int B, int n, int NPAD, const double* X, const int* nfree, const int* perm,
+                              const int* status, double* cov, hipStream_t s) {
+  if (B > 65535) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(cov_product_kernel, dim3((n + 15) / 16, B), dim3(COV_PNT), 0, s, n, NPAD, X, nfree, perm, status,
+                     cov);
+  return hipGetLastError();
+}
+
+}  // namespace blsq

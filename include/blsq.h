@@ -32,6 +32,7 @@ extern "C" {
 typedef struct blsq_ctx blsq_ctx;
 typedef struct blsq_trf_plan blsq_trf_plan;
 typedef struct blsq_dogbox_plan blsq_dogbox_plan;
+typedef struct blsq_cov_plan blsq_cov_plan;
 
 enum {
   BLSQ_STATUS_OK = 0,
@@ -384,6 +385,32 @@ int blsq_loss_scale_dev(blsq_ctx* ctx, int B, int m, int n, int loss, const doub
  * Both the scaled J and the scaled f stay unmodified from a factor call to the next one, as the CSNE tier's
  * lifetime rule asks. */
 int blsq_outer_set_loss(blsq_outer* o, int loss, const double* f_scale);
+
+/* ---- parameter covariance from the final Jacobian --------------------------------------------------------------
+ * The reference documents `x_covariance` as the inverse of J^T J at the solution (least_squares.py:248-252) and fills
+ * it only through its MINPACK bridge (method='lm').  Here, per problem, from a Householder triangle R of J (the TSQR
+ * tree: a Gram-Cholesky triangle would square the conditioning):
+ *   active == NULL:  C = (J^T J)^-1 = R^-1 R^-T over all n variables;
+ *   active != NULL:  int64 [B][n]; F = {j : active[j] == 0}; C[F,F] = (J_F^T J_F)^-1, every row and column of an
+ *                    active variable exactly 0.0 (the covariance with the variables on a bound held fixed).
+ * rcond[b] = 1 / (||R||_1 ||R^-1||_1) from the explicit inverse.  status[b] = 1 (singular) when a pivot of R is zero
+ * or not finite (rcond = 0) or rcond < eps * max(m, |F|): cov[b] is then NaN everywhere; 0 otherwise.  A Jacobian
+ * with fewer rows than free columns is singular, not an error.  No residual-variance scaling is applied.  cov is the
+ * full symmetric matrix [B][n][n], exactly symmetric; a problem's bits do not depend on B or on its batch mates.
+ * Shapes: n + 1 <= 1024 as the TSQR tree; m > 1024 with n > 512, past the tree's merge capacity, is factored by folding
+ * the rows in sequentially (1024 at a time under the triangle) and needs n + 1 <= 1008.  B <= 65535.
+ * blsq_cov_dev: device pointers, asynchronous on the ctx stream; J is not modified.  blsq_cov: host pointers, blocking. */
+int blsq_cov_plan_create(blsq_ctx* ctx, int B, int m, int n, blsq_cov_plan** out);
+int blsq_cov_plan_destroy(blsq_cov_plan* plan);
+int blsq_cov_dev(blsq_cov_plan* plan, const double* dJ, const int64_t* dactive /*[B][n] or NULL = all variables*/,
+                 double* dcov /*[B][n][n]*/, double* drcond /*[B]*/, int32_t* dstatus /*[B]: 0 ok, 1 singular*/);
+int blsq_cov(blsq_cov_plan* plan, const double* J, const int64_t* active, double* cov, double* rcond,
+             int32_t* status);
+/* The same for every problem of a device-resident outer driver, from its resident J (under a robust loss: diag(w) J,
+ * scipy's `jac`); after blsq_outer_begin, normally once the loop has ended.  free_only != 0: the active variables are
+ * dogbox's on_bound, and for 'trf' find_active_constraints(x, lb, ub, rtol = xtol) (trf.py:257) of the x that
+ * blsq_outer_fetch returns.  Host outputs: only B n^2 + 2 B numbers leave the GPU. */
+int blsq_outer_covariance(blsq_outer* o, int free_only, double* cov, double* rcond, int32_t* status);
 
 #ifdef __cplusplus
 }

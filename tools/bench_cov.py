@@ -1,0 +1,104 @@
+"""Parameter covariance on the device (cov_kernels.hip, blsq_cov_dev): what it costs.
+
+For 1024 x 512 x 64, 512 x 4096 x 256 and 1 x 250000 x 128, in one run and with HIP-event timing (the per-kernel
+slots of the ctx): blsq_cov_dev as a whole, its Householder tree (qr_leaf + qr_merge), its inverse + product kernels
+(cov_inverse + cov_product), the gather of 'free' mode, and blsq_trf_factor_dev on the same J (the step path's
+factorisation: normal-equations front end, all slots summed).  Wall times per call (stream synchronised) beside them.
+
+usage: python tools/bench_cov.py [--out profiles/cov/bench_cov.json]
+"""
+import ctypes as C
+import json
+import os
+import sys
+import time
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, os.path.join(ROOT, "bounded-lsq_amd"))
+from bounded_lsq import TrfStepSolver, _abi                                # noqa: E402
+from bounded_lsq._abi import vp                                            # noqa: E402
+
+SHAPES = ((1024, 512, 64), (512, 4096, 256), (1, 250000, 128))
+
+
+def _timed(ctx, call, reps):
+    for _ in range(2):
+        call()
+    ctx.sync()
+    ctx.timing(True)
+    ctx.timing_reset()
+    t0 = time.perf_counter()
+    for _ in range(reps):
+        call()
+    ctx.sync()
+    wall = (time.perf_counter() - t0) / reps * 1e3
+    T = {k: v[0] / reps for k, v in ctx.timing_read().items() if v[1]}
+    ctx.timing(False)
+    return wall, T
+
+
+def bench_shape(ctx, B, m, n, reps):
+    rng = np.random.default_rng(0)
+    blk = min(B, 16)
+    Jh = np.tile(rng.standard_normal((blk, m, n)), ((B + blk - 1) // blk, 1, 1))[:B]
+    d_J = ctx.to_device(Jh)
+    del Jh
+    mask = (rng.uniform(size=(B, n)) < 0.1).astype(np.int64)
+    d_mask = ctx.to_device(mask)
+    d_cov, d_rc, d_st = ctx.malloc(8 * B * n * n), ctx.malloc(8 * B), ctx.malloc(4 * B)
+    out = {"shape": [B, m, n]}
+    h = vp()
+    ctx.check(ctx.lib.blsq_cov_plan_create(ctx.h, B, m, n, C.byref(h)), "blsq_cov_plan_create")
+    try:
+        for label, dm in (("all", None), ("free", d_mask)):
+            wall, T = _timed(ctx, lambda: ctx.check(ctx.lib.blsq_cov_dev(h, d_J, dm, d_cov, d_rc, d_st), "cov"), reps)
+            tree = T.get("qr_leaf", 0.0) + T.get("qr_merge", 0.0)
+            tail = T.get("cov_inverse", 0.0) + T.get("cov_product", 0.0)
+            out[label] = {"whole_ms": round(sum(T.values()), 4), "wall_ms": round(wall, 4), "tree_ms": round(tree, 4),
+                          "inverse_ms": round(T.get("cov_inverse", 0.0), 4),
+                          "product_ms": round(T.get("cov_product", 0.0), 4),
+                          "inverse_plus_product_ms": round(tail, 4), "gather_ms": round(T.get("cov_gather", 0.0), 4),
+                          "tail_over_tree": round(tail / tree, 3)}
+        st = ctx.to_host(d_st, (B,), np.int32)
+        out["singular"] = int(st.sum())
+    finally:
+        ctx.lib.blsq_cov_plan_destroy(h)
+    # the step path's factorisation of the same J
+    d_f = ctx.to_device(rng.standard_normal((B, m)))
+    d_x = ctx.to_device(np.zeros((B, n)))
+    d_lb = ctx.to_device(np.full((B, n), -np.inf))
+    d_ub = ctx.to_device(np.full((B, n), np.inf))
+    d_sc = ctx.to_device(np.ones((B, n)))
+    sol = TrfStepSolver(B, m, n, ctx=ctx)
+    try:
+        wall, T = _timed(ctx, lambda: sol.factor_dev(d_J, d_f, d_x, d_lb, d_ub, d_sc), reps)
+        out["trf_factor_dev"] = {"whole_ms": round(sum(T.values()), 4), "wall_ms": round(wall, 4),
+                                 "slots_ms": {k: round(v, 4) for k, v in T.items()}}
+    finally:
+        sol.close()
+        for p in (d_J, d_mask, d_cov, d_rc, d_st, d_f, d_x, d_lb, d_ub, d_sc):
+            ctx.free(p)
+    out["cov_over_factor"] = round(out["all"]["whole_ms"] / out["trf_factor_dev"]["whole_ms"], 3)
+    return out
+
+
+def main():
+    ctx = _abi.Context(0)
+    res = []
+    for shp in SHAPES:
+        r = bench_shape(ctx, *shp, reps=5 if shp[0] * shp[1] * shp[2] > 1 << 28 else 20)
+        print(json.dumps(r), flush=True)
+        res.append(r)
+    ctx.close()
+    if "--out" in sys.argv:
+        path = sys.argv[sys.argv.index("--out") + 1]
+        os.makedirs(os.path.dirname(path) or ".", exist_ok=True)
+        with open(path, "w") as fh:
+            json.dump(res, fh, indent=1)
+            fh.write("\n")
+
+
+if __name__ == "__main__":
+    main()
