@@ -24,7 +24,8 @@ from ._hip_step import (TrfStepSolver, DogboxStepSolver, SCALE_GIVEN, SCALE_JAC_
                         SCALE_JAC_UPDATE, raise_batch_status)
 from ._hostmath import (shift_into_interior, active_mask, cl_vector, check_loss, loss_rho, loss_cost,
                         loss_scale)
-from ._cov import check_covariance, attach as _attach_covariance, fill_results as _fill_covariance
+from ._cov import (check_covariance, attach as _attach_covariance, fill_results as _fill_covariance, is_pinv as _is_pinv,
+                   is_free as _is_free)
 
 
 def _bounds_2d(bounds, B, n):
@@ -41,7 +42,7 @@ def _bounds_2d(bounds, B, n):
 def least_squares_batch(fun, x0, jac, bounds=(-np.inf, np.inf), method='trf',
                         ftol=EPS ** 0.5, xtol=EPS ** 0.5, gtol=EPS ** 0.5, max_nfev=None,
                         scaling=1.0, diff_step=None, args=(), kwargs=None, ctx=None, driver='host',
-                        loss='linear', f_scale=1.0, covariance=False):
+                        loss='linear', f_scale=1.0, covariance=False, _variance_scale=False):
     """Solve B bound-constrained least-squares problems of identical shape.
 
     fun : callable, ``fun(X) -> (B, m)`` residuals for ``X`` (B, n)
@@ -56,7 +57,9 @@ def least_squares_batch(fun, x0, jac, bounds=(-np.inf, np.inf), method='trf',
              problem; driver='host' only); f_scale a positive scalar or broadcastable to (B,).
     covariance : False, True or 'free' as ``least_squares``: ``x_covariance`` / ``x_covariance_rcond`` of every
              problem from ONE batched call on the final Jacobians (driver='device': on the resident ones, only
-             B n^2 + 2 B numbers leave the GPU).
+             B n^2 + 2 B numbers leave the GPU).  'pinv' / 'free-pinv': the pseudo-inverse covariance of any rank
+             (``x_covariance_rank``; ``x_covariance_rcond`` is then s_min / s_max, not the 1-norm figure);
+             ``_variance_scale`` (``curve_fit_batch``'s): times obj_value / (m - n), applied on the GPU.
     Returns a list of B ``OptimizeResult`` (fields as ``least_squares``).
     """
     if method not in ('trf', 'dogbox'):
@@ -131,7 +134,7 @@ def least_squares_batch(fun, x0, jac, bounds=(-np.inf, np.inf), method='trf',
     if driver == 'device':
         try:
             return _device_batch(fun, jac, X0, lb, ub, trf, use_jac, scaling, ftol, xtol, gtol,
-                                 max_nfev, ctx, loss if robust else None, fsc, covariance)
+                                 max_nfev, ctx, loss if robust else None, fsc, covariance, _variance_scale)
         finally:
             _release_fd()
 
@@ -309,7 +312,7 @@ def least_squares_batch(fun, x0, jac, bounds=(-np.inf, np.inf), method='trf',
             r.success = r.status > 0
             results.append(r)
         if covariance:
-            _attach_covariance(results, covariance, ctx=solver.ctx)
+            _attach_covariance(results, covariance, ctx=solver.ctx, variance_scale=_variance_scale and m > n)
         return results
     finally:
         solver.close()
@@ -317,7 +320,7 @@ def least_squares_batch(fun, x0, jac, bounds=(-np.inf, np.inf), method='trf',
 
 
 def _device_batch(fun, jac, X0, lb, ub, trf, use_jac, scaling, ftol, xtol, gtol, max_nfev, ctx,
-                  loss=None, f_scale=None, covariance=False):
+                  loss=None, f_scale=None, covariance=False, variance_scale=False):
     """`least_squares_batch` on the device-resident outer driver (same results, same counts).  `loss`: a
     loss name other than 'linear' (None: sum f^2), applied on the device (blsq_outer_set_loss)."""
     from ._outer import OuterDriver
@@ -357,7 +360,8 @@ def _device_batch(fun, jac, X0, lb, ub, trf, use_jac, scaling, ftol, xtol, gtol,
             drv.set_loss(loss, f_scale)
         drv.start(X0, xs, lb, ub, scale, use_jac, ftol, xtol, gtol, max_nfev)
         R = drv.run_host(fun_cached, jac_checked)
-        cov_out = drv.covariance(free_only=(covariance == 'free')) if covariance else None
+        cov_out = drv.covariance(free_only=_is_free(covariance), pinv=_is_pinv(covariance),
+                                 variance_scale=variance_scale and m > n) if covariance else None
         Jfin = drv._down(drv.d_J, (B, m, n))
     finally:
         drv.close()

@@ -8,7 +8,16 @@ fills it only through its MINPACK bridge.  Here it is computed on the GPU from a
   ``covariance='free'``  F = {j : active_mask[j] == 0}; C[F, F] = (J_F^T J_F)^-1 and every row and column of an
                          active variable exactly 0.0: the covariance with the variables on a bound held fixed.
 
-A problem whose triangle has a zero or non-finite pivot, or whose ``rcond_1 = 1 / (||R||_1 ||R^-1||_1)`` is below
+  ``covariance='pinv'``  the Moore-Penrose covariance ``V diag(1/s^2) V^T`` over the singular values of J above
+                         ``eps * max(m, n) * s_max``: scipy ``curve_fit``'s ``pcov`` (``absolute_sigma=True``) for
+                         any rank (blsq_cov_pinv*, DESIGN.md 7h).  ``x_covariance_rank`` is the number kept;
+  ``covariance='free-pinv'``  the same over the free variables, zeros in the rows and columns of the others.
+
+For the two pinv modes ``x_covariance_rcond`` is ``s_min / s_max`` over all singular values (0 for a rank-deficient
+J), NOT the 1-norm figure of the other two modes, and ``x_covariance`` is None only where J is not finite (scipy's
+``svd`` raises there) or the SVD did not converge.
+
+For True / 'free': a problem whose triangle has a zero or non-finite pivot, or whose ``rcond_1 = 1 / (||R||_1 ||R^-1||_1)`` is below
 ``eps * max(m, |F|)``, is singular: its ``x_covariance`` is None (as the reference's docstring prescribes), its rcond
 is still reported.  No residual-variance scaling is applied: multiply by ``obj_value / (m - n)`` for ``curve_fit``'s
 default (``absolute_sigma=False``).
@@ -20,22 +29,42 @@ import numpy as np
 from ._abi import vp, ptr
 
 
+MODES = ('free', 'pinv', 'free-pinv')
+
+
 def check_covariance(covariance):
-    """-> False, True or 'free'; ValueError for anything else (before any GPU is touched)."""
+    """-> False, True, 'free', 'pinv' or 'free-pinv'; ValueError for anything else (before any GPU is touched)."""
     if isinstance(covariance, (bool, np.bool_)):
         return bool(covariance)
-    if isinstance(covariance, str) and covariance == 'free':
-        return 'free'
-    raise ValueError("`covariance` must be False, True or 'free'.")
+    if isinstance(covariance, str) and covariance in MODES:
+        return covariance
+    raise ValueError("`covariance` must be False, True or 'free', or 'pinv' or 'free-pinv'.")
 
 
-def covariance(J, active_mask=None, ctx=None):
+def is_pinv(mode):
+    return mode in ('pinv', 'free-pinv')
+
+
+def is_free(mode):
+    return mode in ('free', 'free-pinv')
+
+
+def covariance(J, active_mask=None, ctx=None, pinv=False, scale=None):
     """Covariance of one (m, n) Jacobian or of a batch (B, m, n).
 
     active_mask : None (all variables), or integers of shape (n,) / (B, n): non-zero marks a variable on a bound.
     Returns ``(cov, rcond, status)``: cov (n, n) or (B, n, n) — NaN everywhere for a singular problem —, rcond and
     status (0 regular, 1 singular) scalars or (B,).
+
+    pinv=True : the pseudo-inverse covariance (module docstring); returns ``(cov, rank, rcond, kept_rcond, status)``
+    with rcond = s_min / s_max, kept_rcond = (smallest kept singular value) / s_max, status 0, 1 (J not finite: cov
+    NaN) or 2 (SVD not converged: cov NaN).  scale (pinv only): None, a scalar or (B,): cov[b] is multiplied by it
+    on the GPU (the residual variance ``obj_value / (m - n)`` of ``curve_fit``'s ``absolute_sigma=False``).
     """
+    if not isinstance(pinv, (bool, np.bool_)):
+        raise ValueError("`pinv` must be False or True.")
+    if scale is not None and not pinv:
+        raise ValueError("`scale` needs pinv=True.")
     J = np.asarray(J, dtype=np.float64)
     if J.ndim not in (2, 3):
         raise ValueError("`J` must have shape (m, n) or (B, m, n).")
@@ -52,6 +81,12 @@ def covariance(J, active_mask=None, ctx=None):
         if act.shape != (B, n):
             raise ValueError("`active_mask` must have shape (n,) or (B, n) matching `J`.")
         act = np.ascontiguousarray(act != 0, dtype=np.int64)
+    sc = None
+    if scale is not None:
+        try:
+            sc = np.ascontiguousarray(np.broadcast_to(np.asarray(scale, dtype=np.float64), (B,)))
+        except ValueError:
+            raise ValueError("`scale` must be a scalar or have shape (B,).")
     if ctx is None:
         from ._hip_step import default_context
         ctx = default_context()
@@ -61,25 +96,52 @@ def covariance(J, active_mask=None, ctx=None):
         cov = np.empty((B, n, n))
         rcond = np.empty(B)
         status = np.empty(B, dtype=np.int32)
-        ctx.check(ctx.lib.blsq_cov(h, ptr(Jb), ptr(act), ptr(cov), ptr(rcond), ptr(status)), "blsq_cov")
+        if pinv:
+            rank = np.empty(B, dtype=np.int32)
+            kept = np.empty(B)
+            ctx.check(ctx.lib.blsq_cov_pinv(h, ptr(Jb), ptr(act), ptr(sc), ptr(cov), ptr(rank), ptr(rcond), ptr(kept),
+                                            ptr(status)), "blsq_cov_pinv")
+        else:
+            ctx.check(ctx.lib.blsq_cov(h, ptr(Jb), ptr(act), ptr(cov), ptr(rcond), ptr(status)), "blsq_cov")
     finally:
         ctx.lib.blsq_cov_plan_destroy(h)
+    if pinv:
+        if single:
+            return cov[0], int(rank[0]), float(rcond[0]), float(kept[0]), int(status[0])
+        return cov, rank, rcond, kept, status
     if single:
         return cov[0], float(rcond[0]), int(status[0])
     return cov, rcond, status
 
 
-def fill_results(results, mode, cov, rcond, status):
-    """x_covariance (None where singular) and x_covariance_rcond of each result from one batched call's outputs."""
+def fill_results(results, mode, cov, *rest):
+    """x_covariance (None where singular / not finite), x_covariance_rcond and, for the pinv modes,
+    x_covariance_rank of each result from one batched call's outputs (`rest`: rcond, status, or rank, rcond,
+    kept_rcond, status)."""
+    if is_pinv(mode):
+        rank, rcond, kept, status = rest
+    else:
+        rcond, status = rest
     for b, r in enumerate(results):
         r.x_covariance = None if int(status[b]) != 0 else cov[b].copy()
         r.x_covariance_rcond = float(rcond[b])
+        if is_pinv(mode):
+            r.x_covariance_rank = int(rank[b])
     return results
 
 
-def attach(results, mode, ctx=None):
-    """One batched covariance call on the stacked final Jacobians of `results` (`mode`: True or 'free')."""
+def variance_scales(results):
+    """obj_value / (m - n) of each result (curve_fit: "s_sq = cost / (ysize - p0.size)"); needs m > n."""
+    return np.array([r.obj_value / (r.jac.shape[0] - r.jac.shape[1]) for r in results])
+
+
+def attach(results, mode, ctx=None, variance_scale=False):
+    """One batched covariance call on the stacked final Jacobians of `results` (`mode`: as check_covariance returns
+    it).  variance_scale (pinv modes): multiply problem b by obj_value / (m - n) on the GPU."""
     J = np.stack([r.jac for r in results])
-    act = np.stack([np.asarray(r.active_mask) for r in results]) if mode == 'free' else None
-    cov, rcond, status = covariance(J, act, ctx=ctx)
-    return fill_results(results, mode, cov, rcond, status)
+    act = np.stack([np.asarray(r.active_mask) for r in results]) if is_free(mode) else None
+    if is_pinv(mode):
+        out = covariance(J, act, ctx=ctx, pinv=True, scale=variance_scales(results) if variance_scale else None)
+    else:
+        out = covariance(J, act, ctx=ctx)
+    return fill_results(results, mode, *out)

@@ -1,0 +1,270 @@
+"""`curve_fit` and `curve_fit_batch`: scipy.optimize.curve_fit's model-fitting front end over this package's solvers.
+
+``curve_fit`` follows scipy 1.15.3 ``_minpack_py.py::curve_fit`` line by line where its lines apply (the comments cite
+them); the solve is this package's ``least_squares`` and ``pcov`` is the pseudo-inverse covariance of the final Jacobian
+computed on the GPU (``covariance='pinv'``) where scipy takes an SVD on the host.
+"""
+import warnings
+from inspect import getfullargspec
+
+import numpy as np
+from scipy.linalg import cholesky, solve_triangular, LinAlgError
+from scipy.optimize import OptimizeWarning
+
+from ._frontend import least_squares
+from ._batch import least_squares_batch
+from ._hostmath import prepare_bounds
+
+__all__ = ['curve_fit', 'curve_fit_batch']
+
+_COV_WARNING = 'Covariance of the parameters could not be estimated'
+
+
+def _initialize_feasible(lb, ub):
+    """scipy's start point when p0 is None: 1, or the middle of / one unit inside the finite bounds."""
+    p0 = np.ones_like(lb)
+    lo, hi = np.isfinite(lb), np.isfinite(ub)
+    both = lo & hi
+    p0[both] = 0.5 * (lb[both] + ub[both])
+    p0[lo & ~hi] = lb[lo & ~hi] + 1
+    p0[~lo & hi] = ub[~lo & hi] - 1
+    return p0
+
+
+def _memoize_first(fn):
+    """scipy's _lightweight_memoizer: remember the value at the first parameter vector only (the solver and the
+    finite-difference Jacobian both evaluate there), and stop looking once another vector has been seen."""
+    state = {"params": None, "val": None, "skip": False}
+
+    def wrapped(params):
+        if state["skip"]:
+            return fn(params)
+        if np.all(state["params"] == params):
+            return state["val"]
+        if state["params"] is not None:
+            state["skip"] = True
+        val = fn(params)
+        if state["params"] is None:
+            state["params"] = np.copy(params)
+            state["val"] = val
+        return val
+    return wrapped
+
+
+def _transform_of(sigma, ysize):
+    """None, 1 / sigma (scalar or 1-D errors) or the lower Cholesky factor of a 2-D covariance."""
+    if sigma is None:
+        return None
+    sigma = np.asarray(sigma)
+    if sigma.size == 1 or sigma.shape == (ysize,):
+        return 1.0 / sigma
+    if sigma.shape == (ysize, ysize):
+        try:
+            return cholesky(sigma, lower=True)
+        except LinAlgError as e:
+            raise ValueError("`sigma` must be positive definite.") from e
+    raise ValueError("`sigma` has incorrect shape.")
+
+
+def _wrap_func(f, xdata, ydata, transform):
+    if transform is None:
+        return lambda params: f(xdata, *params) - ydata
+    if transform.size == 1 or transform.ndim == 1:
+        return lambda params: transform * (f(xdata, *params) - ydata)
+    # chi^2 = r^T C^-1 r with C = L L^T: minimise |L^-1 r|^2
+    return lambda params: solve_triangular(transform, f(xdata, *params) - ydata, lower=True)
+
+
+def _wrap_jac(jac, xdata, transform):
+    if transform is None:
+        return lambda params: jac(xdata, *params)
+    if transform.ndim == 0:                  # (a scalar sigma: scipy's wrapper sends it to the triangular solve)
+        return lambda params: transform * np.asarray(jac(xdata, *params))
+    if transform.ndim == 1:
+        return lambda params: transform[:, np.newaxis] * np.asarray(jac(xdata, *params))
+    return lambda params: solve_triangular(transform, np.asarray(jac(xdata, *params)), lower=True)
+
+
+def curve_fit(f, xdata, ydata, p0=None, sigma=None, absolute_sigma=False, check_finite=True,
+              bounds=(-np.inf, np.inf), method=None, jac=None, full_output=False, **kwargs):
+    """Fit ``ydata = f(xdata, *p) + eps`` by non-linear least squares; returns ``(popt, pcov)``.
+
+    Parameters, exceptions, warnings and results are scipy.optimize.curve_fit's (1.15.3):
+    p0 None takes the number of parameters from the signature of `f` and starts from 1 (or inside finite bounds);
+    sigma may be a scalar, 1-D errors or a 2-D covariance (its Cholesky factor is solved against on the host);
+    the residual is ``transform * (f(xdata, *p) - ydata)``, a callable `jac` is transformed the same way and
+    ``jac=None`` means '2-point'; ``maxfev`` is renamed to ``max_nfev``; 'args' in kwargs is a ValueError; an
+    unsuccessful solve raises ``RuntimeError("Optimal parameters not found: ...")``.  Other keywords go to this
+    package's ``least_squares`` (``loss=``, ``f_scale=``, tolerances, ``scaling``, ``options``).
+
+    ``pcov`` is the Moore-Penrose covariance of the final Jacobian over its singular values above
+    ``eps * max(m, n) * s_max``, computed on the GPU; unless `absolute_sigma` it is multiplied by
+    ``obj_value / (m - n)``, and filled with inf under an ``OptimizeWarning`` where m <= n.
+    ``full_output=True`` returns ``(popt, pcov, infodict, mesg, ier)`` with infodict keys ``nfev`` and ``fvec``.
+
+    Two deliberate differences from scipy:
+      * ``method=None`` always means 'trf' (scipy chooses 'lm' for an unbounded problem); ``method='lm'`` raises
+        ``NotImplementedError`` here as in ``least_squares``: there is no MINPACK bridge on this step path;
+      * ``nan_policy`` is not taken.
+    """
+    if p0 is None:
+        args = getfullargspec(f).args
+        if len(args) < 2:
+            raise ValueError("Unable to determine number of fit parameters.")
+        n = len(args) - 1
+    else:
+        p0 = np.atleast_1d(p0)
+        n = p0.size
+
+    if hasattr(bounds, 'lb') and hasattr(bounds, 'ub'):      # a scipy.optimize.Bounds instance
+        bounds = (bounds.lb, bounds.ub)
+    lb, ub = prepare_bounds(bounds, np.empty(n))
+    if p0 is None:
+        p0 = _initialize_feasible(lb, ub)
+
+    if method is None:
+        method = 'trf'
+    if method == 'lm':
+        raise NotImplementedError(
+            "method='lm' is a MINPACK bridge in the reference and is outside "
+            "the MI355X step path; use 'trf' or 'dogbox'.")
+
+    # optimisation may produce garbage for float32 inputs: cast to float64
+    ydata = np.asarray_chkfinite(ydata, float) if check_finite else np.asarray(ydata, float)
+    if isinstance(xdata, (list, tuple, np.ndarray)):
+        # `xdata` goes straight to `f`, so anything that is not array_like is left alone
+        xdata = np.asarray_chkfinite(xdata, float) if check_finite else np.asarray(xdata, float)
+    if ydata.size == 0:
+        raise ValueError("`ydata` must not be empty!")
+
+    transform = _transform_of(sigma, ydata.size)
+    func = _memoize_first(_wrap_func(f, xdata, ydata, transform))
+    if callable(jac):
+        jac = _memoize_first(_wrap_jac(jac, xdata, transform))
+    elif jac is None:
+        jac = '2-point'
+
+    if 'args' in kwargs:
+        # the model function takes xdata and the parameters, nothing else
+        raise ValueError("'args' is not a supported keyword argument.")
+    if 'max_nfev' not in kwargs:
+        kwargs['max_nfev'] = kwargs.pop('maxfev', None)
+
+    # the bound checks of scipy's least_squares, in its words (this package's least_squares keeps the reference's)
+    if lb.shape == p0.shape and ub.shape == p0.shape:
+        if np.any(lb >= ub):
+            raise ValueError("Each lower bound must be strictly less than each upper bound.")
+        if not np.all((p0 >= lb) & (p0 <= ub)):
+            raise ValueError("Initial guess is outside of provided bounds")
+
+    res = least_squares(func, p0, jac=jac, bounds=bounds, method=method, covariance='pinv', **kwargs)
+    if not res.success:
+        raise RuntimeError("Optimal parameters not found: " + res.message)
+
+    infodict = dict(nfev=res.nfev, fvec=res.fun)
+    ier, errmsg = res.status, res.message
+    ysize = len(res.fun)
+    cost = res.obj_value                     # sum f^2, or the robust-loss objective (scipy: 2 * res.cost)
+    popt = res.x
+    pcov = res.x_covariance                  # V diag(1 / s^2) V^T over the kept singular values
+
+    warn_cov = False
+    if pcov is None or np.isnan(pcov).any():
+        pcov = np.full((len(popt), len(popt)), np.inf)
+        warn_cov = True
+    elif not absolute_sigma:
+        if ysize > p0.size:
+            pcov = pcov * (cost / (ysize - p0.size))
+        else:
+            pcov.fill(np.inf)
+            warn_cov = True
+    if warn_cov:
+        warnings.warn(_COV_WARNING, category=OptimizeWarning, stacklevel=2)
+
+    if full_output:
+        return popt, pcov, infodict, errmsg, ier
+    return popt, pcov
+
+
+def curve_fit_batch(f, xdata, ydata, p0, sigma=None, absolute_sigma=False, bounds=(-np.inf, np.inf), method='trf',
+                    jac='2-point', driver='host', ctx=None, **kwargs):
+    """``curve_fit`` for B data sets of one model, solved together by ``least_squares_batch``.
+
+    f : ``f(xdata, P) -> (B, m)`` for parameters ``P`` of shape (B, n): vectorised over the batch
+    ydata : (B, m);  p0 : (B, n), required
+    sigma : None, a scalar, (m,) errors shared by all problems or (B, m) per problem (a shape (B, m) is always read
+            this way).  A 2-D covariance is not supported here: ValueError.
+    bounds : pair broadcastable to (B, n);  jac : '2-point', '3-point' or ``jac(xdata, P) -> (B, m, n)``
+    driver, ctx, **kwargs : as ``least_squares_batch`` (tolerances, ``max_nfev`` / ``maxfev``, ``loss=``, ...).
+
+    Returns ``(popt (B, n), pcov (B, n, n), results)``, `results` the B ``OptimizeResult`` of the solve.  pcov[b] is
+    ``curve_fit``'s for problem b alone: the pseudo-inverse covariance of its final Jacobian, times
+    ``obj_value / (m - n)`` unless `absolute_sigma` — multiplied on the GPU; with driver='device' only B n^2 + 4 B
+    numbers leave it — and inf under an ``OptimizeWarning`` where m <= n.  ``results[b].x_covariance`` is that
+    scaled matrix as well.
+
+    A problem that did not converge (``results[b].success`` false) is NOT an exception here, unlike ``curve_fit``:
+    its rows of popt and pcov are NaN and the other problems are returned intact.
+    """
+    ydata = np.asarray(ydata, float)
+    if ydata.ndim != 2:
+        raise ValueError("`ydata` must have shape (B, m).")
+    if ydata.size == 0:
+        raise ValueError("`ydata` must not be empty!")
+    B, m = ydata.shape
+    P0 = np.asarray(p0, float)
+    if P0.ndim != 2 or P0.shape[0] != B:
+        raise ValueError("`p0` must have shape (B, n).")
+    n = P0.shape[1]
+    if isinstance(xdata, (list, tuple, np.ndarray)):
+        xdata = np.asarray(xdata, float)
+
+    transform = None
+    if sigma is not None:
+        sigma = np.asarray(sigma, float)
+        if sigma.size == 1 or sigma.shape == (m,) or sigma.shape == (B, m):
+            transform = 1.0 / sigma
+        elif sigma.ndim == 2:
+            raise ValueError("a 2-D covariance `sigma` is not supported by `curve_fit_batch`.")
+        else:
+            raise ValueError("`sigma` has incorrect shape.")
+
+    if transform is None:
+        def func(P):
+            return np.asarray(f(xdata, P), float) - ydata
+    else:
+        def func(P):
+            return transform * (np.asarray(f(xdata, P), float) - ydata)
+
+    if callable(jac):
+        user_jac = jac
+        tj = None if transform is None else np.broadcast_to(transform, (B, m))[:, :, np.newaxis]
+
+        def jac(P):                                                        # noqa: F811
+            J = np.asarray(user_jac(xdata, P), float)
+            return J if tj is None else tj * J
+
+    if 'args' in kwargs:
+        raise ValueError("'args' is not a supported keyword argument.")
+    if 'max_nfev' not in kwargs:
+        kwargs['max_nfev'] = kwargs.pop('maxfev', None)
+
+    scale_on_gpu = (not absolute_sigma) and m > n
+    results = least_squares_batch(func, P0, jac, bounds=bounds, method=method, driver=driver, ctx=ctx,
+                                  covariance='pinv', _variance_scale=scale_on_gpu, **kwargs)
+    popt = np.full((B, n), np.nan)
+    pcov = np.full((B, n, n), np.nan)
+    warn_cov = False
+    for b, r in enumerate(results):
+        if not r.success:
+            continue
+        popt[b] = r.x
+        C = r.x_covariance
+        if C is None or np.isnan(C).any() or (not absolute_sigma and m <= n):
+            pcov[b] = np.inf
+            warn_cov = True
+        else:
+            pcov[b] = C
+    if warn_cov:
+        warnings.warn(_COV_WARNING, category=OptimizeWarning, stacklevel=2)
+    return popt, pcov, results

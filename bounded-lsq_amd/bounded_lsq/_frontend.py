@@ -76,6 +76,10 @@ def least_squares(fun, x0, jac='2-point', bounds=(-np.inf, np.inf), method='trf'
     the rows and columns of the others), computed on the GPU (``bounded_lsq.covariance``).  A singular problem
     keeps ``x_covariance = None``; ``x_covariance_rcond`` is the 1-norm reciprocal condition number of J's triangle
     either way.  No variance scaling: multiply by ``obj_value / (m - n)`` for ``curve_fit``'s default.
+    'pinv' / 'free-pinv': the Moore-Penrose covariance over the singular values of J above
+    ``eps * max(m, n) * s_max`` (``curve_fit``'s ``pcov`` for any rank; ``bounded_lsq.curve_fit`` is built on it):
+    ``x_covariance_rank`` is the number kept, ``x_covariance_rcond`` is then ``s_min / s_max`` — NOT the 1-norm
+    figure of True / 'free' — and ``x_covariance`` is None only where J is not finite.
     """
     if method not in ['trf', 'dogbox', 'lm']:
         raise ValueError("`method` must be 'trf', 'dogbox' or 'lm'.")

@@ -109,15 +109,30 @@ class OuterDriver:
                                            "njev", "status")]), "blsq_outer_fetch")
         return out
 
-    def covariance(self, free_only=False):
+    def covariance(self, free_only=False, pinv=False, variance_scale=False):
         """Covariance of every problem from the resident J (blsq_outer_covariance; after begin(), normally once the
         loop has ended): ``(cov (B, n, n), rcond (B,), status (B,))``, NaN in cov where status is 1 (singular).
         free_only: over the variables off their bounds only (dogbox: on_bound == 0; trf: the active mask of the
-        current x with rtol = xtol), zeros in the other rows and columns.  Only these outputs leave the GPU."""
+        current x with rtol = xtol), zeros in the other rows and columns.  Only these outputs leave the GPU.
+
+        pinv=True: the pseudo-inverse covariance (blsq_outer_covariance_pinv): ``(cov, rank, rcond, kept_rcond,
+        status)`` as ``bounded_lsq.covariance(..., pinv=True)``; variance_scale=True multiplies problem b by
+        ``obj[b] / (m - n)`` on the GPU (needs m > n)."""
         B, n = self.B, self.n
         cov = np.empty((B, n, n))
         rcond = np.empty(B)
         status = np.empty(B, dtype=np.int32)
+        if variance_scale and not pinv:
+            raise ValueError("`variance_scale` needs pinv=True.")
+        if pinv:
+            if variance_scale and self.m <= self.n:
+                raise ValueError("`variance_scale` needs m > n.")
+            rank = np.empty(B, dtype=np.int32)
+            kept = np.empty(B)
+            self.ctx.check(self.ctx.lib.blsq_outer_covariance_pinv(
+                self.h, 1 if free_only else 0, 1 if variance_scale else 0, ptr(cov), ptr(rank), ptr(rcond), ptr(kept),
+                ptr(status)), "blsq_outer_covariance_pinv")
+            return cov, rank, rcond, kept, status
         self.ctx.check(self.ctx.lib.blsq_outer_covariance(self.h, 1 if free_only else 0, ptr(cov), ptr(rcond),
                                                           ptr(status)), "blsq_outer_covariance")
         return cov, rcond, status

@@ -1,5 +1,7 @@
 // C-ABI entry points (include/blsq.h): parameter covariance from the final Jacobian.
 //   tree (Householder TSQR of the plain J, or of J with its free columns first)  ->  cov_inverse  ->  cov_product
+//   pseudo-inverse route (7h):                                      the same tree  ->  Jacobi SVD of the triangle
+//                                                                   ->  cov_pinv_weights  ->  cov_pinv_product
 #include "blsq_host.h"
 
 extern "C" int blsq_cov_plan_create(blsq_ctx* ctx, int B, int m, int n, blsq_cov_plan** out) {
@@ -51,7 +53,8 @@ extern "C" int blsq_cov_plan_destroy(blsq_cov_plan* p) {
   hipStreamSynchronize(p->ctx->stream);
   p->tree.release();
   for (DevBuf* b : {&p->fR, &p->fS, &p->fV, &p->fT, &p->zf, &p->X, &p->perm, &p->nfree, &p->Jp, &p->in_J, &p->in_act, &p->o_cov, &p->o_rcond,
-                    &p->o_status})
+                    &p->o_status, &p->js, &p->juf, &p->jsrange, &p->jsweeps, &p->jncols, &p->pw, &p->in_scale, &p->o_rank,
+                    &p->o_kept})
     b->release();
   delete p;
   return 0;
@@ -92,14 +95,16 @@ int cov_fold(blsq_cov_plan* p, const double* dJ) {
 }
 }  // namespace
 
-namespace blsq_host {
-int cov_core(blsq_cov_plan* p, const double* dJ, const long long* dactive, int lda, double* dcov, double* drcond,
-             int* dstatus) {
+namespace {
+// The triangle of every problem in the plan's Rfinal slot: of the plain J, or with a mask of J gathered with its free
+// columns first (perm, nfree: the plan's; nullptr without a mask).  want_ncols: nfree + 1 per problem into jncols.
+int cov_triangle(blsq_cov_plan* p, const double* dJ, const long long* dactive, int lda, const int** perm_out,
+                 const int** nfree_out, bool want_ncols) {
   blsq_ctx* ctx = p->ctx;
-  const int B = p->B, m = p->m, n = p->n, NPAD = p->NPAD;
+  const int B = p->B, m = p->m, n = p->n;
   const double* src = dJ;
-  const int* perm = nullptr;
-  const int* nfree = nullptr;
+  *perm_out = nullptr;
+  *nfree_out = nullptr;
   if (dactive) {
     if (!p->perm.p) {
       if (int rc_ = alloc_all(ctx, {{&p->perm, sizeof(int) * (size_t)B * n, "hipMalloc(covariance permutation)"},
@@ -108,19 +113,69 @@ int cov_core(blsq_cov_plan* p, const double* dJ, const long long* dactive, int l
         return rc_;
     }
     if (int rc_ = ctx->run(K_COV_GATHER, "launch_cov_gather", [&] {
-          const hipError_t e = launch_cov_perm(B, n, dactive, lda, p->perm.as<int>(), p->nfree.as<int>(), ctx->stream);
+          const hipError_t e = launch_cov_perm(B, n, dactive, lda, p->perm.as<int>(), p->nfree.as<int>(),
+                                               want_ncols ? p->jncols.as<int>() : nullptr, ctx->stream);
           return e == hipSuccess ? launch_cov_gather(B, m, n, dJ, p->perm.as<int>(), p->Jp.as<double>(), ctx->stream)
                                  : e;
         })) return rc_;
-    src = p->Jp.as<double>(); perm = p->perm.as<int>(); nfree = p->nfree.as<int>();
+    src = p->Jp.as<double>(); *perm_out = p->perm.as<int>(); *nfree_out = p->nfree.as<int>();
   }
-  if (int rc_ = p->fold ? cov_fold(p, src) : p->tree.run_levels(ctx, src, p->zf.as<double>(), n, nullptr)) return rc_;
+  return p->fold ? cov_fold(p, src) : p->tree.run_levels(ctx, src, p->zf.as<double>(), n, nullptr);
+}
+}  // namespace
+
+namespace blsq_host {
+int cov_core(blsq_cov_plan* p, const double* dJ, const long long* dactive, int lda, double* dcov, double* drcond,
+             int* dstatus) {
+  blsq_ctx* ctx = p->ctx;
+  const int B = p->B, m = p->m, n = p->n, NPAD = p->NPAD;
+  const int* perm = nullptr;
+  const int* nfree = nullptr;
+  if (int rc_ = cov_triangle(p, dJ, dactive, lda, &perm, &nfree, false)) return rc_;
   if (int rc_ = ctx->run(K_COV_INVERSE, "launch_cov_inverse", [&] {
         return launch_cov_inverse(B, m, n, NPAD, p->Rfinal(), p->X.as<double>(), nfree, dcov, drcond, dstatus,
                                   ctx->stream);
       })) return rc_;
   return ctx->run(K_COV_PRODUCT, "launch_cov_product", [&] {
     return launch_cov_product(B, n, NPAD, p->X.as<double>(), nfree, perm, dstatus, dcov, ctx->stream);
+  });
+}
+
+// Jacobi sweeps granted to a covariance triangle (as the step plans' factor calls)
+static constexpr int COV_MAX_SWEEPS = 40;
+
+int cov_pinv_core(blsq_cov_plan* p, const double* dJ, const long long* dactive, int lda, const double* dscale,
+                  double* dcov, int* drank, double* drcond, double* dkept, int* dstatus) {
+  blsq_ctx* ctx = p->ctx;
+  const int B = p->B, m = p->m, n = p->n, NPAD = p->NPAD;
+  if (!p->js.p) {
+    const size_t vec = sizeof(double) * (size_t)B * NPAD;
+    if (int rc_ = alloc_all(ctx, {{&p->js, vec, "hipMalloc(covariance singular values)"},
+                                  {&p->juf, vec, "hipMalloc(covariance Jacobi rhs)"},
+                                  {&p->jsrange, sizeof(double) * (size_t)B * 2, "hipMalloc(covariance Jacobi range)"},
+                                  {&p->jsweeps, sizeof(int) * (size_t)B, "hipMalloc(covariance Jacobi sweeps)"},
+                                  {&p->jncols, sizeof(int) * (size_t)B, "hipMalloc(covariance Jacobi widths)"},
+                                  {&p->pw, vec, "hipMalloc(covariance weights)"}}))
+      return rc_;
+  }
+  const int* perm = nullptr;
+  const int* nfree = nullptr;
+  if (int rc_ = cov_triangle(p, dJ, dactive, lda, &perm, &nfree, true)) return rc_;
+  double* tri = const_cast<double*>(p->Rfinal());    // rotated in place: the next call rebuilds it
+  JacobiArgs ja{};
+  ja.X = tri; ja.strideX = (long)NPAD * NPAD; ja.ld = NPAD;
+  ja.ncols_dev = dactive ? p->jncols.as<int>() : nullptr;
+  ja.N = n + 1; ja.s = p->js.as<double>(); ja.uf = p->juf.as<double>(); ja.srange = p->jsrange.as<double>();
+  ja.sweeps = p->jsweeps.as<int>(); ja.max_sweeps = COV_MAX_SWEEPS;
+  if (int rc_ = ctx->run(K_JACOBI, "launch_jacobi(covariance)", [&] { return launch_jacobi(ja, B, ctx->stream); }))
+    return rc_;
+  if (int rc_ = ctx->run(K_COV_PINV_WEIGHTS, "launch_cov_pinv_weights", [&] {
+        return launch_cov_pinv_weights(B, m, n, NPAD, tri, p->js.as<double>(), p->jsweeps.as<int>(), COV_MAX_SWEEPS,
+                                       nfree, p->pw.as<double>(), dcov, drank, drcond, dkept, dstatus, ctx->stream);
+      })) return rc_;
+  return ctx->run(K_COV_PINV_PRODUCT, "launch_cov_pinv_product", [&] {
+    return launch_cov_pinv_product(B, n, NPAD, tri, p->pw.as<double>(), nfree, perm, dstatus, dscale, dcov,
+                                   ctx->stream);
   });
 }
 }  // namespace blsq_host
@@ -179,7 +234,77 @@ extern "C" int blsq_cov(blsq_cov_plan* p, const double* J, const int64_t* active
   return cov_download(p, cov, rcond, status);
 }
 
+namespace {
+int cov_pinv_outputs(blsq_cov_plan* p) {
+  if (int rc_ = cov_outputs(p)) return rc_;
+  if (p->o_rank.p) return 0;
+  const size_t B = (size_t)p->B;
+  return alloc_all(p->ctx, {{&p->o_rank, sizeof(int) * B, "hipMalloc(covariance output)"},
+                            {&p->o_kept, sizeof(double) * B, "hipMalloc(covariance output)"}});
+}
+int cov_pinv_download(blsq_cov_plan* p, double* cov, int32_t* rank, double* rcond, double* kept, int32_t* status) {
+  blsq_ctx* ctx = p->ctx;
+  HIPCHK(ctx, hipMemcpyAsync(rank, p->o_rank.p, p->o_rank.bytes, hipMemcpyDeviceToHost, ctx->stream));
+  HIPCHK(ctx, hipMemcpyAsync(kept, p->o_kept.p, p->o_kept.bytes, hipMemcpyDeviceToHost, ctx->stream));
+  return cov_download(p, cov, rcond, status);
+}
+int cov_pinv_args(blsq_ctx* ctx, const void* J, const void* cov, const void* rank, const void* rcond, const void* kept,
+                  const void* status) {
+  if (!J) return ctx->bad(2, "J is NULL");
+  if (!cov) return ctx->bad(5, "cov is NULL");
+  if (!rank) return ctx->bad(6, "rank is NULL");
+  if (!rcond) return ctx->bad(7, "rcond is NULL");
+  if (!kept) return ctx->bad(8, "kept_rcond is NULL");
+  if (!status) return ctx->bad(9, "status is NULL");
+  return 0;
+}
+}  // namespace
+
+extern "C" int blsq_cov_pinv_dev(blsq_cov_plan* p, const double* dJ, const int64_t* dactive, const double* dscale,
+                                 double* dcov, int32_t* drank, double* drcond, double* dkept_rcond,
+                                 int32_t* dstatus) {
+  if (!p) return -1;
+  blsq_ctx* ctx = p->ctx;
+  if (int rc_ = cov_pinv_args(ctx, dJ, dcov, drank, drcond, dkept_rcond, dstatus)) return rc_;
+  HIPCHK(ctx, hipSetDevice(ctx->device));
+  return cov_pinv_core(p, dJ, reinterpret_cast<const long long*>(dactive), p->n, dscale, dcov, drank, drcond,
+                       dkept_rcond, dstatus);
+}
+
+extern "C" int blsq_cov_pinv(blsq_cov_plan* p, const double* J, const int64_t* active, const double* scale,
+                             double* cov, int32_t* rank, double* rcond, double* kept_rcond, int32_t* status) {
+  if (!p) return -1;
+  blsq_ctx* ctx = p->ctx;
+  if (int rc_ = cov_pinv_args(ctx, J, cov, rank, rcond, kept_rcond, status)) return rc_;
+  HIPCHK(ctx, hipSetDevice(ctx->device));
+  const size_t B = (size_t)p->B, nJ = sizeof(double) * B * p->m * p->n, nA = sizeof(int64_t) * B * p->n;
+  if (!p->in_J.p)
+    if (int rc_ = alloc_all(ctx, {{&p->in_J, nJ, "hipMalloc(covariance input)"}})) return rc_;
+  if (active && !p->in_act.p)
+    if (int rc_ = alloc_all(ctx, {{&p->in_act, nA, "hipMalloc(covariance input)"}})) return rc_;
+  if (scale && !p->in_scale.p)
+    if (int rc_ = alloc_all(ctx, {{&p->in_scale, sizeof(double) * B, "hipMalloc(covariance input)"}})) return rc_;
+  if (int rc_ = cov_pinv_outputs(p)) return rc_;
+  HIPCHK(ctx, hipMemcpyAsync(p->in_J.p, J, nJ, hipMemcpyHostToDevice, ctx->stream));
+  if (active) HIPCHK(ctx, hipMemcpyAsync(p->in_act.p, active, nA, hipMemcpyHostToDevice, ctx->stream));
+  if (scale) HIPCHK(ctx, hipMemcpyAsync(p->in_scale.p, scale, sizeof(double) * B, hipMemcpyHostToDevice, ctx->stream));
+  if (int rc_ = cov_pinv_core(p, p->in_J.as<double>(), active ? p->in_act.as<long long>() : nullptr, p->n,
+                              scale ? p->in_scale.as<double>() : nullptr, p->o_cov.as<double>(), p->o_rank.as<int>(),
+                              p->o_rcond.as<double>(), p->o_kept.as<double>(), p->o_status.as<int>()))
+    return rc_;
+  return cov_pinv_download(p, cov, rank, rcond, kept_rcond, status);
+}
+
 namespace blsq_host {
+int cov_pinv_to_host(blsq_cov_plan* p, const double* dJ, const long long* dmask, int lda, const double* dscale,
+                     double* cov, int32_t* rank, double* rcond, double* kept_rcond, int32_t* status) {
+  if (int rc_ = cov_pinv_outputs(p)) return rc_;
+  if (int rc_ = cov_pinv_core(p, dJ, dmask, lda, dscale, p->o_cov.as<double>(), p->o_rank.as<int>(),
+                              p->o_rcond.as<double>(), p->o_kept.as<double>(), p->o_status.as<int>()))
+    return rc_;
+  return cov_pinv_download(p, cov, rank, rcond, kept_rcond, status);
+}
+
 // blsq_outer_covariance (blsq_outer.hip) on the driver's resident J: mask (device, int64 [B][lda]) or nullptr
 int cov_to_host(blsq_cov_plan* p, const double* dJ, const long long* dmask, int lda, double* cov, double* rcond,
                 int32_t* status) {

@@ -28,11 +28,11 @@ constexpr int RMAX = QR_MAX_TILES * 16;   // rows a workgroup can stage (qr_pane
 
 enum Slot { K_QR_LEAF = 0, K_QR_MERGE, K_PREP, K_QR_AUG, K_JACOBI, K_STEP, K_LM_GATE, K_LM_QR, K_LM_SOLVE,
             K_GRAM, K_GRAM_CHOL, K_GRAM_GATE, K_AUG_CHOL, K_LM_CHOL, K_CQR2_APPLY, K_CQR2_COMBINE, K_CSNE_PASS,
-            K_CSNE_FIX, K_COV_GATHER, K_COV_INVERSE, K_COV_PRODUCT, K_LOSS_COST, K_LOSS_SCALE, K_NSLOT };
+            K_CSNE_FIX, K_COV_PINV_WEIGHTS, K_COV_PINV_PRODUCT, K_COV_GATHER, K_COV_INVERSE, K_COV_PRODUCT, K_LOSS_COST, K_LOSS_SCALE, K_NSLOT };
 static const char* const kSlotNames[K_NSLOT] = {"qr_leaf", "qr_merge", "prep", "qr_aug", "jacobi_svd", "step",
                                    "lm_gate", "lm_qr", "lm_solve", "gram", "gram_chol", "gram_gate",
                                    "aug_chol", "lm_chol", "cqr2_apply", "cqr2_combine", "csne_pass", "csne_fix",
-                                   "cov_gather", "cov_inverse", "cov_product", "loss_cost", "loss_scale"};
+                                   "cov_pinv_weights", "cov_pinv_product", "cov_gather", "cov_inverse", "cov_product", "loss_cost", "loss_scale"};
 
 inline int round_up(int v, int q) { return (v + q - 1) / q * q; }
 // rows of the stacked systems [R D; E] / [R_aug; sqrt(alpha) I]: two blocks of
@@ -620,6 +620,10 @@ struct blsq_cov_plan {
   DevBuf X;                         // [B][NPAD*NPAD] the explicit inverse
   DevBuf perm, nfree, Jp;           // 'free' mode, allocated on first use: permutation, free counts, gathered J
   DevBuf in_J, in_act, o_cov, o_rcond, o_status;   // staging of the host-pointer call, allocated on first use
+  // pseudo-inverse route (blsq_cov_pinv*), allocated on first use: the Jacobi kernel's s, uf [B][NPAD], srange [B][2],
+  // sweeps [B], per-problem widths nfree + 1 [B]; the weights [B][NPAD]; staging of the host-pointer call
+  DevBuf js, juf, jsrange, jsweeps, jncols, pw;
+  DevBuf in_scale, o_rank, o_kept;
 };
 namespace blsq_host {
 // the whole covariance call on device pointers; dactive: int64 [B][lda] or nullptr
@@ -628,5 +632,10 @@ int cov_core(blsq_cov_plan* p, const double* dJ, const long long* dactive, int l
 // ... and with host outputs through the plan's own device buffers (blsq_outer_covariance)
 int cov_to_host(blsq_cov_plan* p, const double* dJ, const long long* dmask, int lda, double* cov, double* rcond,
                 int32_t* status);
+// the pseudo-inverse route on device pointers (dscale [B] or nullptr), and with host outputs (blsq_outer_covariance_pinv)
+int cov_pinv_core(blsq_cov_plan* p, const double* dJ, const long long* dactive, int lda, const double* dscale,
+                  double* dcov, int* drank, double* drcond, double* dkept, int* dstatus);
+int cov_pinv_to_host(blsq_cov_plan* p, const double* dJ, const long long* dmask, int lda, const double* dscale,
+                     double* cov, int32_t* rank, double* rcond, double* kept_rcond, int32_t* status);
 }  // namespace blsq_host
 

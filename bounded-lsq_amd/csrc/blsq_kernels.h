@@ -555,7 +555,9 @@ hipError_t launch_loss_scale(int B, int m, int n, int loss, const double* fscale
 // cov_kernels.hip (blsq_cov_dev).  active: int64 [B][lda] (non-zero = on a bound); perm [B][n] free columns first,
 // nfree [B]; nfree / perm may be nullptr in the inverse / product launches (all variables, identity).  R and X are
 // [B][NPAD][NPAD]; the inverse launch writes rcond, status and the NaN / zero fill of cov, the product launch the rest.
-hipError_t launch_cov_perm(int B, int n, const long long* active, int lda, int* perm, int* nfree, hipStream_t s);
+// (ncols, optional: nfree + 1 per problem, the width the Jacobi kernel takes per problem)
+hipError_t launch_cov_perm(int B, int n, const long long* active, int lda, int* perm, int* nfree, int* ncols,
+                           hipStream_t s);
 hipError_t launch_cov_trf_mask(int B, int n, int ld, double rtol, const double* x, const double* lb, const double* ub,
                                long long* mask, hipStream_t s);
 hipError_t launch_cov_gather(int B, int m, int n, const double* J, const int* perm, double* Jp, hipStream_t s);
@@ -566,6 +568,19 @@ hipError_t launch_cov_inverse(int B, int m, int n, int NPAD, const double* R, do
                               double* rcond, int* status, hipStream_t s);
 hipError_t launch_cov_product(int B, int n, int NPAD, const double* X, const int* nfree, const int* perm,
                               const int* status, double* cov, hipStream_t s);
+// The pseudo-inverse route (7h, blsq_cov_pinv_dev): X [B][NPAD][NPAD] holds the rows s_i v_i^T launch_jacobi left in
+// the triangle slot, s [B][NPAD] its singular values, sweeps [B] its sweep counts.  The weights launch writes
+// w [B][NPAD] (1 / s_i^2 or exactly 0), rank, rcond = sigma_min / sigma_max, kept_rcond, status (0 ok, 1 not finite,
+// 2 Jacobi did not converge) and the NaN / zero fill of cov; the product launch C_F = sum_i (w_i r_i)(w_i r_i)^T times
+// dscale[b] (nullptr: 1), through perm.
+hipError_t launch_cov_pinv_weights(int B, int m, int n, int NPAD, const double* X, const double* s, const int* sweeps,
+                                   int max_sweeps, const int* nfree, double* w, double* cov, int* rank, double* rcond,
+                                   double* kept_rcond, int* status, hipStream_t st);
+hipError_t launch_cov_pinv_product(int B, int n, int NPAD, const double* X, const double* w, const int* nfree,
+                                   const int* perm, const int* status, const double* dscale, double* cov,
+                                   hipStream_t st);
+// dscale[b] = obj[b] / (m - n)  (m > n)
+hipError_t launch_cov_variance(int B, int m, int n, const double* obj, double* dscale, hipStream_t st);
 
 // ------------------------------------- finite-difference Jacobians (8f-2) ----
 // method: 2 = '2-point', 3 = '3-point'.  X [B][P][n] with P = n (2) or 2n (3); F [B][P][m].

@@ -14,6 +14,7 @@ struct blsq_outer {
   int loss = BLSQ_LOSS_LINEAR;
   blsq_cov_plan* cov = nullptr;        // blsq_outer_covariance: created on first use
   DevBuf covmask;                      // [B][n] int64: the active mask of a 'trf' driver (from x, as the host reports it)
+  DevBuf covscale;                     // [B] obj / (m - n): blsq_outer_covariance_pinv with variance_scale
   bool scaled_early = false;           // robust loss: the accepted problems' J were scaled by blsq_outer_covariance
   OuterState st{};
   int jac_scaling = 0;
@@ -76,7 +77,7 @@ extern "C" int blsq_outer_destroy(blsq_outer* o) {
   if (o->trf) blsq_trf_plan_destroy(o->trf);
   if (o->dog) blsq_dogbox_plan_destroy(o->dog);
   if (o->cov) blsq_cov_plan_destroy(o->cov);
-  o->covmask.release();
+  o->covmask.release(); o->covscale.release();
   o->x0.release(); o->xc.release(); o->xt.release(); o->f.release(); o->ft.release();
   o->J.release(); o->dvec.release(); o->ivec.release(); o->counts.release();
   o->fsc.release(); o->lobj.release(); o->fscale.release();
@@ -294,6 +295,35 @@ extern "C" int blsq_outer_fetch(blsq_outer* o, double* x, double* f, double* obj
 // judge and the next propose those are still unscaled — they are scaled here, once (propose then leaves them alone).
 // The mask of free_only: dogbox's on_bound; for 'trf' find_active_constraints(x, lb, ub, rtol = xtol) (trf.py:257), the
 // mask the host reports for the x blsq_outer_fetch returns.
+namespace {
+// what both covariance calls do first: pending verdicts, the plan, the early scaling, the mask of free_only
+int outer_cov_prepare(blsq_outer* o, int free_only, const long long** mask, int* lda) {
+  blsq_ctx* ctx = o->ctx;
+  int rc;
+  if ((rc = ctx_resolve_pending(ctx))) return rc;
+  if (!o->cov && (rc = blsq_cov_plan_create(ctx, o->B, o->m, o->n, &o->cov))) return rc;
+  if (o->loss != BLSQ_LOSS_LINEAR && o->last_accepted > 0 && !o->scaled_early) {
+    if ((rc = outer_loss_scale(o, o->st.accepted))) return rc;
+    o->scaled_early = true;
+  }
+  *mask = nullptr;
+  *lda = o->n;
+  if (free_only) {
+    if (o->method == 1) { *mask = reinterpret_cast<const long long*>(o->st.on_bound); *lda = o->ld; }
+    else {
+      if (!o->covmask.p)
+        if ((rc = alloc_all(ctx, {{&o->covmask, sizeof(long long) * (size_t)o->B * o->n, "hipMalloc(trf mask)"}})))
+          return rc;
+      const hipError_t e = launch_cov_trf_mask(o->B, o->n, o->ld, o->xtol, o->st.xc, o->st.lb, o->st.ub,
+                                               o->covmask.as<long long>(), ctx->stream);
+      if (e != hipSuccess) return ctx->fail(e, "launch_cov_trf_mask");
+      *mask = o->covmask.as<long long>();
+    }
+  }
+  return 0;
+}
+}  // namespace
+
 extern "C" int blsq_outer_covariance(blsq_outer* o, int free_only, double* cov, double* rcond, int32_t* status) {
   if (!o) return -1;
   blsq_ctx* ctx = o->ctx;
@@ -302,28 +332,39 @@ extern "C" int blsq_outer_covariance(blsq_outer* o, int free_only, double* cov, 
   if (!rcond) return ctx->bad(4, "rcond is NULL");
   if (!status) return ctx->bad(5, "status is NULL");
   HIPCHK(ctx, hipSetDevice(ctx->device));
-  int rc;
-  if ((rc = ctx_resolve_pending(ctx))) return rc;
-  if (!o->cov && (rc = blsq_cov_plan_create(ctx, o->B, o->m, o->n, &o->cov))) return rc;
-  if (o->loss != BLSQ_LOSS_LINEAR && o->last_accepted > 0 && !o->scaled_early) {
-    if ((rc = outer_loss_scale(o, o->st.accepted))) return rc;
-    o->scaled_early = true;
-  }
   const long long* mask = nullptr;
   int lda = o->n;
-  if (free_only) {
-    if (o->method == 1) { mask = reinterpret_cast<const long long*>(o->st.on_bound); lda = o->ld; }
-    else {
-      if (!o->covmask.p)
-        if ((rc = alloc_all(ctx, {{&o->covmask, sizeof(long long) * (size_t)o->B * o->n, "hipMalloc(trf mask)"}})))
-          return rc;
-      const hipError_t e = launch_cov_trf_mask(o->B, o->n, o->ld, o->xtol, o->st.xc, o->st.lb, o->st.ub,
-                                               o->covmask.as<long long>(), ctx->stream);
-      if (e != hipSuccess) return ctx->fail(e, "launch_cov_trf_mask");
-      mask = o->covmask.as<long long>();
-    }
-  }
+  if (int rc = outer_cov_prepare(o, free_only, &mask, &lda)) return rc;
   return cov_to_host(o->cov, o->J.as<double>(), mask, lda, cov, rcond, status);
+}
+
+// The pseudo-inverse covariance of every problem (blsq_cov_pinv_dev on the resident J, same rules as above);
+// variance_scale: times obj[b] / (m - n) of the resident objective, applied by the product kernel.
+extern "C" int blsq_outer_covariance_pinv(blsq_outer* o, int free_only, int variance_scale, double* cov, int32_t* rank,
+                                          double* rcond, double* kept_rcond, int32_t* status) {
+  if (!o) return -1;
+  blsq_ctx* ctx = o->ctx;
+  if (!o->begun) return ctx->bad(1, "blsq_outer_begin has not been called");
+  if (variance_scale && o->m <= o->n) return ctx->bad(3, "variance_scale needs m > n");
+  if (!cov) return ctx->bad(4, "cov is NULL");
+  if (!rank) return ctx->bad(5, "rank is NULL");
+  if (!rcond) return ctx->bad(6, "rcond is NULL");
+  if (!kept_rcond) return ctx->bad(7, "kept_rcond is NULL");
+  if (!status) return ctx->bad(8, "status is NULL");
+  HIPCHK(ctx, hipSetDevice(ctx->device));
+  const long long* mask = nullptr;
+  int lda = o->n;
+  if (int rc = outer_cov_prepare(o, free_only, &mask, &lda)) return rc;
+  const double* dscale = nullptr;
+  if (variance_scale) {
+    if (!o->covscale.p)
+      if (int rc = alloc_all(ctx, {{&o->covscale, sizeof(double) * (size_t)o->B, "hipMalloc(variance scale)"}}))
+        return rc;
+    const hipError_t e = launch_cov_variance(o->B, o->m, o->n, o->st.obj, o->covscale.as<double>(), ctx->stream);
+    if (e != hipSuccess) return ctx->fail(e, "launch_cov_variance");
+    dscale = o->covscale.as<double>();
+  }
+  return cov_pinv_to_host(o->cov, o->J.as<double>(), mask, lda, dscale, cov, rank, rcond, kept_rcond, status);
 }
 
 // ================================================== robust loss functions ===

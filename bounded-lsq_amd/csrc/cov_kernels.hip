@@ -18,6 +18,15 @@
 //   cov_product_kernel   C_F = X X^T, tile (i, j >= i) = sum_{k >= j} X_ik X_jk^T on the MFMA pipe, written with its
 //                        mirror image through perm: exactly symmetric by construction
 //
+// The pseudo-inverse route (blsq_cov_pinv*) replaces the last two by the one-sided Jacobi SVD of the
+// triangle (jacobi_svd.hip: row i of the free block becomes s_i v_i^T) and
+//   cov_pinv_weights_kernel  one workgroup per problem: sigma_max, curve_fit's threshold eps max(m, |F|) sigma_max, the
+//                        rank, w_i = 1 / s_i^2 (exactly 0.0 for a dropped row), rcond = sigma_min / sigma_max,
+//                        kept_rcond, the verdict and the NaN / zero fill of cov
+//   cov_pinv_product_kernel  C_F = sum_i (w_i r_i)(w_i r_i)^T = Y^T Y with Y = diag(w) [rows]: tile (i, j >= i) summed
+//                        over the rows in ascending order on the MFMA pipe (operands read along the rows, the weight
+//                        applied on the load), times an optional per-problem scale, written with its mirror image
+//
 // Every sum has a fixed order and nothing is atomic: a problem's bits depend on its own J, mask, m and n only.
 #include "../../include/blsq.h"
 #include "blsq_device.h"
@@ -40,7 +49,8 @@ __device__ __forceinline__ v4d cov_mfma(double a, double b, v4d c) {
 
 // ---- masks and permutations --------------------------------------------------------------------
 __global__ __launch_bounds__(256) void cov_perm_kernel(int B, int n, const long long* __restrict__ active, int lda,
-                                                       int* __restrict__ perm, int* __restrict__ nfree) {
+                                                       int* __restrict__ perm, int* __restrict__ nfree,
+                                                       int* __restrict__ ncols) {
   const int b = blockIdx.x * blockDim.x + threadIdx.x;
   if (b >= B) return;
   const long long* a = active + (long)b * lda;
@@ -49,6 +59,7 @@ __global__ __launch_bounds__(256) void cov_perm_kernel(int B, int n, const long 
   for (int j = 0; j < n; ++j)
     if (a[j] == 0) p[k++] = j;
   nfree[b] = k;
+  if (ncols) ncols[b] = k + 1;                       // (the Jacobi kernel's per-problem width: free block + carried column)
   for (int j = 0; j < n; ++j)
     if (a[j] != 0) p[k++] = j;
 }
@@ -290,9 +301,142 @@ __global__ __launch_bounds__(COV_PNT) void cov_product_kernel(int n, int NPAD, c
   }
 }
 
+// ---- pseudo-inverse: weights and product ---------------------------------------------------------
+// After launch_jacobi row i < nf of the triangle slot is s_i v_i^T and s[b][i] = s_i (unsorted).  The recipe restated
+// (scipy 1.15.3 _minpack_py.py, curve_fit: "threshold = np.finfo(float).eps * max(jac.shape) * s[0]; s = s[s >
+// threshold]; VT = VT[:s.size]; pcov = np.dot(VT.T / s**2, VT)"): status 0 ok, 1 not finite, 2 Jacobi not converged.
+__global__ __launch_bounds__(COV_PNT) void cov_pinv_weights_kernel(int m, int n, int NPAD, const double* __restrict__ Xall,
+                                                                   const double* __restrict__ sall,
+                                                                   const int* __restrict__ sweeps, int max_sweeps,
+                                                                   const int* __restrict__ nfree,
+                                                                   double* __restrict__ wall, double* __restrict__ cov,
+                                                                   int* __restrict__ rank, double* __restrict__ rcond,
+                                                                   double* __restrict__ kept_rcond,
+                                                                   int* __restrict__ status) {
+  __shared__ double red[COV_PNT];
+  __shared__ int ired[COV_PNT];
+  const int b = blockIdx.x, tid = threadIdx.x;
+  const int nf = nfree ? nfree[b] : n;
+  const int ld = NPAD;
+  const double* X = Xall + (long)b * NPAD * NPAD;
+  const double* s = sall + (long)b * ld;
+  double* w = wall + (long)b * ld;
+  double* C = cov + (long)b * n * n;
+  const long nn = (long)n * n;
+  auto fill = [&](double v) { for (long k = tid; k < nn; k += COV_PNT) C[k] = v; };
+  if (nf == 0) {                                     // every variable on a bound
+    fill(0.0);
+    if (tid == 0) { rank[b] = 0; rcond[b] = 1.0; kept_rcond[b] = 1.0; status[b] = 0; }
+    return;
+  }
+  // 1. non-finite singular values or rows (scipy's svd raises on them), a Jacobi run that used all its sweeps
+  int bad = 0;
+  for (int i = tid; i < nf; i += COV_PNT) if (!is_finite(s[i])) bad = 1;
+  for (int k = tid; k < nf * nf; k += COV_PNT) {
+    const int r = k / nf, c = k - r * nf;
+    if (!is_finite(X[(long)r * ld + c])) bad = 1;
+  }
+  bad = __syncthreads_or(bad);
+  const int stalled = sweeps[b] >= max_sweeps;
+  if (bad || stalled) {                              // uniform
+    fill(__builtin_nan(""));
+    if (tid == 0) { rank[b] = 0; rcond[b] = 0.0; kept_rcond[b] = 0.0; status[b] = bad ? 1 : 2; }
+    return;
+  }
+  // 2. sigma_max, sigma_min
+  double mx = 0.0, mn = __builtin_inf();
+  for (int i = tid; i < nf; i += COV_PNT) { mx = fmax(mx, s[i]); mn = fmin(mn, s[i]); }
+  const double smax = cov_wg_max<COV_PNT>(mx, red);
+  const double smin = -cov_wg_max<COV_PNT>(-mn, red);
+  // 3. threshold, rank, weights, smallest kept value
+  const double thresh = COV_EPS * (double)(m > nf ? m : nf) * smax;
+  int cnt = 0;
+  double kmn = __builtin_inf();
+  const int nrow = ((nf + 15) >> 4) << 4;            // (<= NPAD: nf <= n < NPAD)
+  for (int i = tid; i < nrow; i += COV_PNT) {
+    double wi = 0.0;
+    if (i < nf && s[i] > thresh) { wi = 1.0 / (s[i] * s[i]); ++cnt; kmn = fmin(kmn, s[i]); }
+    w[i] = wi;
+  }
+  const double kmin = -cov_wg_max<COV_PNT>(-kmn, red);
+  __syncthreads();
+  ired[tid] = cnt;
+  __syncthreads();
+  for (int h = COV_PNT / 2; h > 0; h >>= 1) {
+    if (tid < h) ired[tid] += ired[tid + h];
+    __syncthreads();
+  }
+  const int rk = ired[0];
+  if (tid == 0) {
+    rank[b] = rk;
+    rcond[b] = smax > 0.0 ? smin / smax : 0.0;
+    kept_rcond[b] = rk > 0 ? kmin / smax : 0.0;
+    status[b] = 0;
+  }
+  if (nf < n) fill(0.0);                             // (the product launch writes the whole free block)
+}
+
+__global__ __launch_bounds__(COV_PNT) void cov_pinv_product_kernel(int n, int NPAD, const double* __restrict__ Xall,
+                                                                   const double* __restrict__ wall,
+                                                                   const int* __restrict__ nfree,
+                                                                   const int* __restrict__ perm,
+                                                                   const int* __restrict__ status,
+                                                                   const double* __restrict__ dscale,
+                                                                   double* __restrict__ cov) {
+  const int i = blockIdx.x, b = blockIdx.y, lane = threadIdx.x & 63;
+  const int w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  if (status[b] != 0) return;                        // uniform: the weights kernel has filled the output
+  const int nf = nfree ? nfree[b] : n;
+  const int NTl = (nf + 15) >> 4;
+  if (i >= NTl) return;
+  const int ld = NPAD;
+  const double* X = Xall + (long)b * NPAD * NPAD;
+  const double* wt = wall + (long)b * ld;
+  const int* pm = perm ? perm + (long)b * n : nullptr;
+  double* C = cov + (long)b * n * n;
+  const double sc = dscale ? dscale[b] : 1.0;
+  const int lr = lane >> 4, lc = lane & 15;
+  for (int j = i + w; j < NTl; j += COV_PNW) {
+    v4d acc = {0.0, 0.0, 0.0, 0.0};
+    const double* xa = X + (long)lr * ld + 16 * i + lc;   // lanes of one lr: 16 consecutive doubles of a row
+    const double* xb = X + (long)lr * ld + 16 * j + lc;
+    for (int k = 0; k < NTl; ++k) {                  // rows 16 k .. 16 k + 15, ascending
+      double a[4], bb[4];
+#pragma unroll
+      for (int q = 0; q < 4; ++q) {
+        const int r = 16 * k + 4 * q + lr;
+        const double wr = wt[r];
+        const double va = xa[(long)(16 * k + 4 * q) * ld], vb = xb[(long)(16 * k + 4 * q) * ld];
+        a[q] = (r < nf) ? va * wr : 0.0;             // (rows >= nf of a masked problem belong to its active columns)
+        bb[q] = (r < nf) ? vb * wr : 0.0;
+      }
+#pragma unroll
+      for (int q = 0; q < 4; ++q) acc = cov_mfma(a[q], bb[q], acc);
+    }
+#pragma unroll
+    for (int g = 0; g < 4; ++g) {
+      const int r = 16 * i + lr + 4 * g, c = 16 * j + lc;
+      if (r < nf && c < nf && r <= c) {
+        const int pr = pm ? pm[r] : r, pc = pm ? pm[c] : c;
+        const double v = acc[g] * sc;
+        C[(long)pr * n + pc] = v;
+        C[(long)pc * n + pr] = v;
+      }
+    }
+  }
+}
+
+// dscale[b] = obj[b] / (m - n): curve_fit's residual variance ("s_sq = cost / (ysize - p0.size)")
+__global__ __launch_bounds__(256) void cov_variance_kernel(int B, double dof, const double* __restrict__ obj,
+                                                           double* __restrict__ dscale) {
+  const int b = blockIdx.x * blockDim.x + threadIdx.x;
+  if (b < B) dscale[b] = obj[b] / dof;
+}
+
 // ---- launches ----------------------------------------------------------------------------------
-hipError_t launch_cov_perm(int B, int n, const long long* active, int lda, int* perm, int* nfree, hipStream_t s) {
-  hipLaunchKernelGGL(cov_perm_kernel, dim3((B + 255) / 256), dim3(256), 0, s, B, n, active, lda, perm, nfree);
+hipError_t launch_cov_perm(int B, int n, const long long* active, int lda, int* perm, int* nfree, int* ncols,
+                           hipStream_t s) {
+  hipLaunchKernelGGL(cov_perm_kernel, dim3((B + 255) / 256), dim3(256), 0, s, B, n, active, lda, perm, nfree, ncols);
   return hipGetLastError();
 }
 
@@ -336,6 +480,29 @@ hipError_t launch_cov_product(int B, int n, int NPAD, const double* X, const int
   if (B > 65535) return hipErrorInvalidValue;
   hipLaunchKernelGGL(cov_product_kernel, dim3((n + 15) / 16, B), dim3(COV_PNT), 0, s, n, NPAD, X, nfree, perm, status,
                      cov);
+  return hipGetLastError();
+}
+
+hipError_t launch_cov_pinv_weights(int B, int m, int n, int NPAD, const double* X, const double* s, const int* sweeps,
+                                   int max_sweeps, const int* nfree, double* w, double* cov, int* rank, double* rcond,
+                                   double* kept_rcond, int* status, hipStream_t st) {
+  hipLaunchKernelGGL(cov_pinv_weights_kernel, dim3(B), dim3(COV_PNT), 0, st, m, n, NPAD, X, s, sweeps, max_sweeps,
+                     nfree, w, cov, rank, rcond, kept_rcond, status);
+  return hipGetLastError();
+}
+
+hipError_t launch_cov_pinv_product(int B, int n, int NPAD, const double* X, const double* w, const int* nfree,
+                                   const int* perm, const int* status, const double* dscale, double* cov,
+                                   hipStream_t st) {
+  if (B > 65535) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(cov_pinv_product_kernel, dim3((n + 15) / 16, B), dim3(COV_PNT), 0, st, n, NPAD, X, w, nfree, perm,
+                     status, dscale, cov);
+  return hipGetLastError();
+}
+
+hipError_t launch_cov_variance(int B, int m, int n, const double* obj, double* dscale, hipStream_t st) {
+  if (m <= n) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(cov_variance_kernel, dim3((B + 255) / 256), dim3(256), 0, st, B, (double)(m - n), obj, dscale);
   return hipGetLastError();
 }
 

@@ -412,6 +412,40 @@ int blsq_cov(blsq_cov_plan* plan, const double* J, const int64_t* active, double
  * blsq_outer_fetch returns.  Host outputs: only B n^2 + 2 B numbers leave the GPU. */
 int blsq_outer_covariance(blsq_outer* o, int free_only, double* cov, double* rcond, int32_t* status);
 
+/* ---- pseudo-inverse covariance (rank-deficient Jacobians, curve_fit's pcov) --------------------------------------
+ * scipy.optimize.curve_fit (scipy 1.15.3 _minpack_py.py) takes the covariance from an SVD of the final Jacobian:
+ *     _, s, VT = svd(res.jac, full_matrices=False)
+ *     threshold = np.finfo(float).eps * max(res.jac.shape) * s[0]
+ *     s = s[s > threshold];  VT = VT[:s.size]
+ *     pcov = np.dot(VT.T / s**2, VT)
+ * the Moore-Penrose inverse of J^T J over the singular values above the threshold.  Here, per problem: the Householder
+ * triangle of J (or of J_F, as blsq_cov_dev) is rotated by the one-sided Jacobi SVD into rows s_i v_i^T, then
+ *     rank[b]       = #{i : s_i > eps * max(m, |F|) * s_max};
+ *     cov[b][F,F]   = scale[b] * sum_{kept i} v_i v_i^T / s_i^2, rows and columns of active variables exactly 0.0;
+ *     rcond[b]      = s_min / s_max over all |F| values (not the 1-norm figure of blsq_cov_dev);
+ *     kept_rcond[b] = (smallest kept s) / s_max.
+ * status[b] = 0; 1 when a singular value or an entry of the triangle is not finite (scipy's svd raises there): cov[b]
+ * is NaN everywhere, rank 0, rcond 0; 2 when the Jacobi SVD used all its sweeps without converging (cov[b] NaN as well).
+ * J = 0 gives rank 0 and cov = 0, as the recipe does (rcond = kept_rcond = 0); |F| = 0 gives cov = 0, rank 0, rcond 1.
+ * A Jacobian with fewer rows than columns is an ordinary rank-deficient input.  scale (dscale): [B] or NULL = 1; the
+ * residual variance of curve_fit's absolute_sigma=False ("s_sq = cost / (ysize - p0.size); pcov = pcov * s_sq") goes
+ * in here.  cov is exactly symmetric; a problem's bits do not depend on B or on its batch mates.  Shape limits and the
+ * plan are those of blsq_cov_plan_create; a plan serves both kinds of call.
+ * blsq_cov_pinv_dev: device pointers, asynchronous on the ctx stream, J is not modified.  blsq_cov_pinv: host pointers,
+ * blocking. */
+int blsq_cov_pinv_dev(blsq_cov_plan* plan, const double* dJ, const int64_t* dactive /*[B][n] or NULL*/,
+                      const double* dscale /*[B] or NULL*/, double* dcov /*[B][n][n]*/, int32_t* drank /*[B]*/,
+                      double* drcond /*[B]*/, double* dkept_rcond /*[B]*/, int32_t* dstatus /*[B]*/);
+int blsq_cov_pinv(blsq_cov_plan* plan, const double* J, const int64_t* active, const double* scale, double* cov,
+                  int32_t* rank, double* rcond, double* kept_rcond, int32_t* status);
+/* The same on the resident J of an outer driver, under the rules of blsq_outer_covariance (robust loss: diag(w) J,
+ * scaled once; free_only: dogbox's on_bound or the TRF mask of x).  variance_scale != 0: problem b is multiplied by
+ * obj[b] / (m - n), obj the resident objective that blsq_outer_fetch returns (under a robust loss the loss objective,
+ * scipy's 2 * cost; curve_fit: "cost = 2 * res.cost ... s_sq = cost / (ysize - p0.size)"); it needs m > n (argument
+ * error otherwise: curve_fit fills pcov with inf there, which the caller does).  Host outputs: B n^2 + 4 B numbers. */
+int blsq_outer_covariance_pinv(blsq_outer* o, int free_only, int variance_scale, double* cov, int32_t* rank,
+                               double* rcond, double* kept_rcond, int32_t* status);
+
 #ifdef __cplusplus
 }
 #endif

@@ -4,6 +4,8 @@ For 1024 x 512 x 64, 512 x 4096 x 256 and 1 x 250000 x 128, in one run and with 
 slots of the ctx): blsq_cov_dev as a whole, its Householder tree (qr_leaf + qr_merge), its inverse + product kernels
 (cov_inverse + cov_product), the gather of 'free' mode, and blsq_trf_factor_dev on the same J (the step path's
 factorisation: normal-equations front end, all slots summed).  Wall times per call (stream synchronised) beside them.
+The pseudo-inverse route (blsq_cov_pinv_dev) on the same J beside it: the same tree, the Jacobi SVD of
+the triangle (jacobi_svd), the weights and the product kernel (cov_pinv_weights + cov_pinv_product).
 
 usage: python tools/bench_cov.py [--out profiles/cov/bench_cov.json]
 """
@@ -48,6 +50,7 @@ def bench_shape(ctx, B, m, n, reps):
     mask = (rng.uniform(size=(B, n)) < 0.1).astype(np.int64)
     d_mask = ctx.to_device(mask)
     d_cov, d_rc, d_st = ctx.malloc(8 * B * n * n), ctx.malloc(8 * B), ctx.malloc(4 * B)
+    d_rk, d_kr = ctx.malloc(4 * B), ctx.malloc(8 * B)
     out = {"shape": [B, m, n]}
     h = vp()
     ctx.check(ctx.lib.blsq_cov_plan_create(ctx.h, B, m, n, C.byref(h)), "blsq_cov_plan_create")
@@ -63,6 +66,19 @@ def bench_shape(ctx, B, m, n, reps):
                           "tail_over_tree": round(tail / tree, 3)}
         st = ctx.to_host(d_st, (B,), np.int32)
         out["singular"] = int(st.sum())
+        for label, dm in (("pinv", None), ("free-pinv", d_mask)):
+            wall, T = _timed(ctx, lambda: ctx.check(ctx.lib.blsq_cov_pinv_dev(h, d_J, dm, None, d_cov, d_rk, d_rc, d_kr,
+                                                                               d_st), "cov_pinv"), reps)
+            tree = T.get("qr_leaf", 0.0) + T.get("qr_merge", 0.0)
+            tail = T.get("cov_pinv_weights", 0.0) + T.get("cov_pinv_product", 0.0)
+            out[label] = {"whole_ms": round(sum(T.values()), 4), "wall_ms": round(wall, 4), "tree_ms": round(tree, 4),
+                          "jacobi_ms": round(T.get("jacobi_svd", 0.0), 4),
+                          "weights_ms": round(T.get("cov_pinv_weights", 0.0), 4),
+                          "product_ms": round(T.get("cov_pinv_product", 0.0), 4),
+                          "weights_plus_product_ms": round(tail, 4), "gather_ms": round(T.get("cov_gather", 0.0), 4),
+                          "jacobi_over_tree": round(T.get("jacobi_svd", 0.0) / tree, 3)}
+        out["pinv_status_nonzero"] = int((ctx.to_host(d_st, (B,), np.int32) != 0).sum())
+        out["pinv_over_inverse"] = round(out["pinv"]["whole_ms"] / out["all"]["whole_ms"], 3)
     finally:
         ctx.lib.blsq_cov_plan_destroy(h)
     # the step path's factorisation of the same J
@@ -78,7 +94,7 @@ def bench_shape(ctx, B, m, n, reps):
                                  "slots_ms": {k: round(v, 4) for k, v in T.items()}}
     finally:
         sol.close()
-        for p in (d_J, d_mask, d_cov, d_rc, d_st, d_f, d_x, d_lb, d_ub, d_sc):
+        for p in (d_J, d_mask, d_cov, d_rc, d_st, d_rk, d_kr, d_f, d_x, d_lb, d_ub, d_sc):
             ctx.free(p)
     out["cov_over_factor"] = round(out["all"]["whole_ms"] / out["trf_factor_dev"]["whole_ms"], 3)
     return out
