@@ -99,21 +99,24 @@ def raise_batch_status(status, active=None):
         raise ValueError("problem %d: %s" % (b, STATUS_MESSAGES.get(int(st[b]), "step status %d" % st[b])))
 
 
-class TrfStepSolver:
+class _StepSolver:
+    """What the two solvers share: the plan's life and the debug fetches, by the symbol prefix `_sym`."""
+    _sym = None                        # "trf" / "dogbox": blsq_<_sym>_plan_create, ...
+
     def __init__(self, B, m, n, ctx=None):
         self.ctx = ctx or default_context()
         self.lib = self.ctx.lib
         self.B, self.m, self.n = int(B), int(m), int(n)
         h = _abi.vp()
-        self.ctx.check(self.lib.blsq_trf_plan_create(self.ctx.h, self.B, self.m, self.n,
-                                                     C.byref(h)), "blsq_trf_plan_create")
+        name = "blsq_%s_plan_create" % self._sym
+        self.ctx.check(getattr(self.lib, name)(self.ctx.h, self.B, self.m, self.n, C.byref(h)), name)
         self.h = h
         self.ctx.adopt(self)
 
     def close(self):
         if getattr(self, "h", None):
             if getattr(self.ctx, "h", None):         # (a closed ctx has closed its plans already)
-                self.lib.blsq_trf_plan_destroy(self.h)
+                getattr(self.lib, "blsq_%s_plan_destroy" % self._sym)(self.h)
             self.h = None
 
     def __del__(self):
@@ -121,6 +124,27 @@ class TrfStepSolver:
             self.close()
         except Exception:
             pass
+
+    def _debug(self, what, dtype):
+        out = np.empty(self.B, dtype)
+        name = "blsq_%s_debug_%s" % (self._sym, what)
+        self.ctx.check(getattr(self.lib, name)(self.h, ptr(out)), name)
+        return out
+
+    def debug_cond(self):
+        """Proven bound K2 >= kappa_2 of the equilibrated system of the last factor call (0: none)."""
+        return self._debug("cond", np.float64)
+
+    def debug_fast(self):
+        """1 where the last factor call went without the Jacobi SVD (dogbox: solved the free block), 0 where through it."""
+        return self._debug("fast", np.int32)
+
+    def debug_sweeps(self):
+        return self._debug("sweeps", np.int32)
+
+
+class TrfStepSolver(_StepSolver):
+    _sym = "trf"
 
     # ---- host-pointer API ---------------------------------------------------
     def factor(self, J, f, x, lb, ub, scale, scale_mode=SCALE_GIVEN):
@@ -172,22 +196,6 @@ class TrfStepSolver:
         out = TrfFactorOut(g, g_norm, theta, scale)
         return (out, sing) if want_singular else out
 
-    def debug_fast(self):
-        fl = np.empty(self.B, np.int32)
-        self.ctx.check(self.lib.blsq_trf_debug_fast(self.h, ptr(fl)), "blsq_trf_debug_fast")
-        return fl
-
-    def debug_cond(self):
-        """Proven bound K2 >= kappa_2 of the equilibrated system of the last factor call (0: none)."""
-        k2 = np.empty(self.B)
-        self.ctx.check(self.lib.blsq_trf_debug_cond(self.h, ptr(k2)), "blsq_trf_debug_cond")
-        return k2
-
-    def debug_sweeps(self):
-        sw = np.empty(self.B, np.int32)
-        self.ctx.check(self.lib.blsq_trf_debug_sweeps(self.h, ptr(sw)), "blsq_trf_debug_sweeps")
-        return sw
-
     def debug_csne(self):
         """-> (on_tier [B] int32, eta [B]): the CSNE tier's problems and the largest first-order correction the last
         step call measured for each (-1: the tier declined the problem in that call)."""
@@ -213,28 +221,8 @@ class TrfStepSolver:
                              branch, status, p_h_tr, to_bound, choice)
 
 
-class DogboxStepSolver:
-    def __init__(self, B, m, n, ctx=None):
-        self.ctx = ctx or default_context()
-        self.lib = self.ctx.lib
-        self.B, self.m, self.n = int(B), int(m), int(n)
-        h = _abi.vp()
-        self.ctx.check(self.lib.blsq_dogbox_plan_create(self.ctx.h, self.B, self.m, self.n,
-                                                        C.byref(h)), "blsq_dogbox_plan_create")
-        self.h = h
-        self.ctx.adopt(self)
-
-    def close(self):
-        if getattr(self, "h", None):
-            if getattr(self.ctx, "h", None):
-                self.lib.blsq_dogbox_plan_destroy(self.h)
-            self.h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+class DogboxStepSolver(_StepSolver):
+    _sym = "dogbox"
 
     def factor(self, J, f, x, lb, ub, scale, on_bound, scale_mode=SCALE_GIVEN):
         B, m, n = self.B, self.m, self.n
@@ -259,22 +247,6 @@ class DogboxStepSolver:
             self.h, ptr(Delta), ptr(step), ptr(x_new), ptr(obn), ptr(tr_hit), ptr(pred),
             ptr(ssn), ptr(fb), ptr(status)), "blsq_dogbox_step")
         return DogStepOut(step, x_new, obn, tr_hit, pred, ssn, fb, status)
-
-    def debug_cond(self):
-        k2 = np.empty(self.B)
-        self.ctx.check(self.lib.blsq_dogbox_debug_cond(self.h, ptr(k2)), "blsq_dogbox_debug_cond")
-        return k2
-
-    def debug_fast(self):
-        """1 where the last factor call solved the free block without the Jacobi SVD, 0 where through it."""
-        fl = np.empty(self.B, np.int32)
-        self.ctx.check(self.lib.blsq_dogbox_debug_fast(self.h, ptr(fl)), "blsq_dogbox_debug_fast")
-        return fl
-
-    def debug_sweeps(self):
-        sw = np.empty(self.B, np.int32)
-        self.ctx.check(self.lib.blsq_dogbox_debug_sweeps(self.h, ptr(sw)), "blsq_dogbox_debug_sweeps")
-        return sw
 
     def factor_dev(self, dJ, df, dx, dlb, dub, dscale, don_bound, scale_mode=SCALE_GIVEN):
         self.ctx.check(self.lib.blsq_dogbox_factor_dev(self.h, dJ, df, dx, dlb, dub, dscale,

@@ -51,11 +51,6 @@ extern "C" int blsq_cov_plan_create(blsq_ctx* ctx, int B, int m, int n, blsq_cov
 extern "C" int blsq_cov_plan_destroy(blsq_cov_plan* p) {
   if (!p) return -1;
   hipStreamSynchronize(p->ctx->stream);
-  p->tree.release();
-  for (DevBuf* b : {&p->fR, &p->fS, &p->fV, &p->fT, &p->zf, &p->X, &p->perm, &p->nfree, &p->Jp, &p->in_J, &p->in_act, &p->o_cov, &p->o_rcond,
-                    &p->o_status, &p->js, &p->juf, &p->jsrange, &p->jsweeps, &p->jncols, &p->pw, &p->in_scale, &p->o_rank,
-                    &p->o_kept})
-    b->release();
   delete p;
   return 0;
 }
@@ -201,6 +196,21 @@ int cov_outputs(blsq_cov_plan* p) {
                             {&p->o_rcond, sizeof(double) * B, "hipMalloc(covariance output)"},
                             {&p->o_status, sizeof(int) * B, "hipMalloc(covariance output)"}});
 }
+// the inputs of a host-pointer call into the plan's staging (allocated on first use): J, the mask and the scale if given
+int cov_stage_inputs(blsq_cov_plan* p, const double* J, const int64_t* active, const double* scale) {
+  blsq_ctx* ctx = p->ctx;
+  const size_t B = (size_t)p->B, nJ = sizeof(double) * B * p->m * p->n, nA = sizeof(int64_t) * B * p->n;
+  if (!p->in_J.p)
+    if (int rc_ = alloc_all(ctx, {{&p->in_J, nJ, "hipMalloc(covariance input)"}})) return rc_;
+  if (active && !p->in_act.p)
+    if (int rc_ = alloc_all(ctx, {{&p->in_act, nA, "hipMalloc(covariance input)"}})) return rc_;
+  if (scale && !p->in_scale.p)
+    if (int rc_ = alloc_all(ctx, {{&p->in_scale, sizeof(double) * B, "hipMalloc(covariance input)"}})) return rc_;
+  HIPCHK(ctx, hipMemcpyAsync(p->in_J.p, J, nJ, hipMemcpyHostToDevice, ctx->stream));
+  if (active) HIPCHK(ctx, hipMemcpyAsync(p->in_act.p, active, nA, hipMemcpyHostToDevice, ctx->stream));
+  if (scale) HIPCHK(ctx, hipMemcpyAsync(p->in_scale.p, scale, sizeof(double) * B, hipMemcpyHostToDevice, ctx->stream));
+  return 0;
+}
 int cov_download(blsq_cov_plan* p, double* cov, double* rcond, int32_t* status) {
   blsq_ctx* ctx = p->ctx;
   HIPCHK(ctx, hipMemcpyAsync(cov, p->o_cov.p, p->o_cov.bytes, hipMemcpyDeviceToHost, ctx->stream));
@@ -220,18 +230,8 @@ extern "C" int blsq_cov(blsq_cov_plan* p, const double* J, const int64_t* active
   if (!rcond) return ctx->bad(5, "rcond is NULL");
   if (!status) return ctx->bad(6, "status is NULL");
   HIPCHK(ctx, hipSetDevice(ctx->device));
-  const size_t B = (size_t)p->B, nJ = sizeof(double) * B * p->m * p->n, nA = sizeof(int64_t) * B * p->n;
-  if (!p->in_J.p)
-    if (int rc_ = alloc_all(ctx, {{&p->in_J, nJ, "hipMalloc(covariance input)"}})) return rc_;
-  if (active && !p->in_act.p)
-    if (int rc_ = alloc_all(ctx, {{&p->in_act, nA, "hipMalloc(covariance input)"}})) return rc_;
-  if (int rc_ = cov_outputs(p)) return rc_;
-  HIPCHK(ctx, hipMemcpyAsync(p->in_J.p, J, nJ, hipMemcpyHostToDevice, ctx->stream));
-  if (active) HIPCHK(ctx, hipMemcpyAsync(p->in_act.p, active, nA, hipMemcpyHostToDevice, ctx->stream));
-  if (int rc_ = cov_core(p, p->in_J.as<double>(), active ? p->in_act.as<long long>() : nullptr, p->n,
-                         p->o_cov.as<double>(), p->o_rcond.as<double>(), p->o_status.as<int>()))
-    return rc_;
-  return cov_download(p, cov, rcond, status);
+  if (int rc_ = cov_stage_inputs(p, J, active, nullptr)) return rc_;
+  return cov_to_host(p, p->in_J.as<double>(), active ? p->in_act.as<long long>() : nullptr, p->n, cov, rcond, status);
 }
 
 namespace {
@@ -277,22 +277,9 @@ extern "C" int blsq_cov_pinv(blsq_cov_plan* p, const double* J, const int64_t* a
   blsq_ctx* ctx = p->ctx;
   if (int rc_ = cov_pinv_args(ctx, J, cov, rank, rcond, kept_rcond, status)) return rc_;
   HIPCHK(ctx, hipSetDevice(ctx->device));
-  const size_t B = (size_t)p->B, nJ = sizeof(double) * B * p->m * p->n, nA = sizeof(int64_t) * B * p->n;
-  if (!p->in_J.p)
-    if (int rc_ = alloc_all(ctx, {{&p->in_J, nJ, "hipMalloc(covariance input)"}})) return rc_;
-  if (active && !p->in_act.p)
-    if (int rc_ = alloc_all(ctx, {{&p->in_act, nA, "hipMalloc(covariance input)"}})) return rc_;
-  if (scale && !p->in_scale.p)
-    if (int rc_ = alloc_all(ctx, {{&p->in_scale, sizeof(double) * B, "hipMalloc(covariance input)"}})) return rc_;
-  if (int rc_ = cov_pinv_outputs(p)) return rc_;
-  HIPCHK(ctx, hipMemcpyAsync(p->in_J.p, J, nJ, hipMemcpyHostToDevice, ctx->stream));
-  if (active) HIPCHK(ctx, hipMemcpyAsync(p->in_act.p, active, nA, hipMemcpyHostToDevice, ctx->stream));
-  if (scale) HIPCHK(ctx, hipMemcpyAsync(p->in_scale.p, scale, sizeof(double) * B, hipMemcpyHostToDevice, ctx->stream));
-  if (int rc_ = cov_pinv_core(p, p->in_J.as<double>(), active ? p->in_act.as<long long>() : nullptr, p->n,
-                              scale ? p->in_scale.as<double>() : nullptr, p->o_cov.as<double>(), p->o_rank.as<int>(),
-                              p->o_rcond.as<double>(), p->o_kept.as<double>(), p->o_status.as<int>()))
-    return rc_;
-  return cov_pinv_download(p, cov, rank, rcond, kept_rcond, status);
+  if (int rc_ = cov_stage_inputs(p, J, active, scale)) return rc_;
+  return cov_pinv_to_host(p, p->in_J.as<double>(), active ? p->in_act.as<long long>() : nullptr, p->n,
+                          scale ? p->in_scale.as<double>() : nullptr, cov, rank, rcond, kept_rcond, status);
 }
 
 namespace blsq_host {

@@ -30,10 +30,8 @@ int put_vec(blsq_ctx* ctx, double* dst, int ld, const double* src, int n, int B,
 }
 
 int ctx_resolve_pending(blsq_ctx* ctx) {
-  for (blsq_trf_plan* p : ctx->trf_plans)
-    if (p->pending) { int rc = trf_resolve(p, nullptr); if (rc) return rc; }
-  for (blsq_dogbox_plan* p : ctx->dog_plans)
-    if (p->pending) { int rc = dog_resolve(p, nullptr); if (rc) return rc; }
+  for (StepPlan* p : ctx->plans)
+    if (p->pending) { int rc = p->resolve(nullptr); if (rc) return rc; }
   return 0;
 }
 }  // namespace blsq_host
@@ -58,17 +56,16 @@ extern "C" int blsq_ctx_create(int device_id, blsq_ctx** out) {
   if (e != hipSuccess) return (int)e;
   blsq_ctx* c = new blsq_ctx();
   c->device = device_id;
+  // (whatever exists when a step fails is given back by ~blsq_ctx)
   e = hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking);
+  if (e == hipSuccess) e = hipStreamCreateWithFlags(&c->copy_stream, hipStreamNonBlocking);
+  if (e == hipSuccess) e = c->pinned.alloc(128, hipHostMallocCoherent);
+  if (e == hipSuccess) {
+    c->opt = options_from_env();
+    e = c->cq_accept_dev.alloc(sizeof(unsigned long long));
+  }
+  if (e == hipSuccess) e = hipMemset(c->cq_accept_dev.p, 0, sizeof(unsigned long long));
   if (e != hipSuccess) { delete c; return (int)e; }
-  e = hipStreamCreateWithFlags(&c->copy_stream, hipStreamNonBlocking);
-  if (e != hipSuccess) { hipStreamDestroy(c->stream); delete c; return (int)e; }
-  e = hipHostMalloc((void**)&c->pinned, 128 * sizeof(int), hipHostMallocCoherent);
-  if (e != hipSuccess) { hipStreamDestroy(c->stream); delete c; return (int)e; }
-  memset(c->pinned, 0, 128 * sizeof(int));
-  c->opt = options_from_env();
-  e = hipMalloc((void**)&c->cq_accept_dev, sizeof(unsigned long long));
-  if (e == hipSuccess) e = hipMemset(c->cq_accept_dev, 0, sizeof(unsigned long long));
-  if (e != hipSuccess) { hipHostFree(c->pinned); hipStreamDestroy(c->stream); delete c; return (int)e; }
   *out = c;
   return 0;
 }
@@ -80,12 +77,6 @@ extern "C" int blsq_ctx_destroy(blsq_ctx* ctx) {
   ctx->collect();
   if (ctx->comm && g_rccl.CommDestroy) g_rccl.CommDestroy(ctx->comm);
   ctx->comm = nullptr;
-  for (auto e : ctx->pool) hipEventDestroy(e);
-  for (auto e : ctx->copy_ev) hipEventDestroy(e);
-  if (ctx->copy_stream) hipStreamDestroy(ctx->copy_stream);
-  hipStreamDestroy(ctx->stream);
-  if (ctx->pinned) hipHostFree(ctx->pinned);
-  if (ctx->cq_accept_dev) hipFree(ctx->cq_accept_dev);
   delete ctx;
   return 0;
 }
@@ -363,8 +354,8 @@ extern "C" int blsq_debug_cqr2_stats(blsq_ctx* ctx, uint64_t* out1, int reset) {
   if (!out1) return ctx->bad(2, "out is NULL");
   HIPCHK(ctx, hipSetDevice(ctx->device));
   unsigned long long v = 0ULL;
-  HIPCHK(ctx, hipMemcpyAsync(&v, ctx->cq_accept_dev, sizeof(v), hipMemcpyDeviceToHost, ctx->stream));
-  if (reset) HIPCHK(ctx, hipMemsetAsync(ctx->cq_accept_dev, 0, sizeof(v), ctx->stream));
+  HIPCHK(ctx, hipMemcpyAsync(&v, ctx->cq_accept_dev.p, sizeof(v), hipMemcpyDeviceToHost, ctx->stream));
+  if (reset) HIPCHK(ctx, hipMemsetAsync(ctx->cq_accept_dev.p, 0, sizeof(v), ctx->stream));
   HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
   out1[0] = v;
   return 0;

@@ -43,37 +43,13 @@ int dog_alloc_state(blsq_dogbox_plan* p) {
   st.x = v; st.lb = v + vs; st.ub = v + 2 * vs; st.scale = v + 3 * vs; st.g = v + 4 * vs;
   st.s = v + 5 * vs; st.uf = v + 6 * vs; st.newton = v + 7 * vs; st.cauchy = v + 8 * vs;
   st.scale_in = v + 9 * vs;
-  st.on_bound = p->onb.as<long long>();
+  st.on_bound = p->on_bound = p->onb.as<long long>();
   st.free_idx = p->ivecs.as<int>(); st.ncols = p->ivecs.as<int>() + vs;
   st.srange = p->scal2.as<double>(); st.g_norm = p->scal2.as<double>() + 2 * (size_t)B;
   st.active = p->active.as<unsigned char>();
   p->out.step = p->o_vec.as<double>(); p->out.x_new = p->o_vec.as<double>() + vs;
   p->out.on_bound_new = p->o_onb.as<long long>();
   p->out.scal = p->o_scal.as<double>(); p->out.info = p->o_info.as<int>();
-  return 0;
-}
-
-int dog_put(blsq_dogbox_plan* p, const double* x, const double* lb, const double* ub,
-            const double* scale, const int64_t* on_bound, hipMemcpyKind kind, bool zero_counts = false) {
-  blsq_ctx* ctx = p->ctx;
-  int rc;
-  if (kind == hipMemcpyDeviceToDevice) {
-    p->pack_pend = zero_counts && p->tree.gram;          // (the Gram stage's prep launch does it: dog_factor_core)
-    p->tree.fb_zeroed = p->pack_pend;
-    PackVecs pv{{x, lb, ub, scale, on_bound}, {p->st.x, p->st.lb, p->st.ub, p->st.scale, p->st.on_bound},
-                p->pack_pend ? p->tree.fb_count() : nullptr, 3};
-    if (p->pack_pend) { p->pack_pv = pv; return 0; }
-    hipError_t e = launch_pack_vecs(pv, p->n, p->ld, p->B, ctx->stream);
-    if (e != hipSuccess) return ctx->fail(e, "launch_pack_vecs");
-    return 0;
-  }
-  if ((rc = put_vec(ctx, p->st.x, p->ld, x, p->n, p->B, kind))) return rc;
-  if ((rc = put_vec(ctx, p->st.lb, p->ld, lb, p->n, p->B, kind))) return rc;
-  if ((rc = put_vec(ctx, p->st.ub, p->ld, ub, p->n, p->B, kind))) return rc;
-  if ((rc = put_vec(ctx, p->st.scale, p->ld, scale, p->n, p->B, kind))) return rc;
-  HIPCHK(ctx, hipMemcpy2DAsync(p->st.on_bound, sizeof(long long) * p->ld, on_bound,
-                               sizeof(long long) * p->n, sizeof(long long) * p->n, p->B, kind,
-                               ctx->stream));
   return 0;
 }
 
@@ -284,7 +260,7 @@ int dog_factor_core(blsq_dogbox_plan* p, const double* dJ, const double* df, int
   p->st.fast = p->gate_ints.as<int>();
   if (!skip_tail && (rc = dog_gate_tail(p, c))) return rc;
   int nfb = 0;
-  if (defer) {                              // guess: nobody leaves the path, nobody needs the SVD (dog_resolve checks)
+  if (defer) {                              // guess: nobody leaves the path, nobody needs the SVD (resolve() checks)
     verdict_arm(p, skip_tail, dJ, df, ldJ, scale_mode);
   } else {
     HIPCHK(ctx, hipMemcpyAsync(ctx->pinned + 1, t.fb_count(), 3 * sizeof(int), hipMemcpyDeviceToHost,
@@ -301,54 +277,29 @@ int dog_factor_core(blsq_dogbox_plan* p, const double* dJ, const double* df, int
   return dog_repair(p, dJ, df, ldJ, scale_mode, nfb, mask != nullptr);
 }
 
-// the verdict of an optimistic dogbox factor call (as trf_resolve)
-int dog_resolve(blsq_dogbox_plan* p, bool* redo) {
+}  // namespace blsq_host
+
+// the verdict of an optimistic dogbox factor call (as blsq_trf_plan::resolve)
+int blsq_dogbox_plan::resolve(bool* redo) {
+  blsq_dogbox_plan* p = this;
   return verdict_resolve(
       p, redo, [&]() { return dog_gate_tail(p, dog_chol_args(p, nullptr)); },
       [&](int nfb) { return dog_repair(p, p->pend_dJ, p->pend_df, p->pend_ldJ, p->pend_scale_mode, nfb, false); });
 }
 
-}  // namespace blsq_host
-
 extern "C" int blsq_dogbox_plan_create(blsq_ctx* ctx, int B, int m, int n,
                                        blsq_dogbox_plan** out) {
   if (!ctx) return -1;
-  if (!out) return ctx->bad(5, "out is NULL");
-  *out = nullptr;
-  if (B <= 0) return ctx->bad(2, "B must be positive");
-  if (m <= 0) return ctx->bad(3, "m must be positive");
-  if (n <= 0) return ctx->bad(4, "n must be positive");
-  HIPCHK(ctx, hipSetDevice(ctx->device));
+  if (out) *out = nullptr;
+  if (int rc_ = step_plan_args(ctx, B, m, n, out)) return rc_;
   blsq_dogbox_plan* p = new blsq_dogbox_plan();
-  p->ctx = ctx; p->B = B; p->m = m; p->n = n;
-  int rc = p->tree.build(ctx, B, m, n, (size_t)B * round_up(n + 1, 16));
-  if (rc == 0) { p->ld = p->tree.NPAD; rc = dog_alloc_state(p); }
-  if (rc == 0) {
-    p->optimistic = ctx->opt.on(OPT_OPTIMISTIC);
-    hipError_t e = hipHostMalloc((void**)&p->pend_pin, 4 * sizeof(int), hipHostMallocCoherent);
-    if (e == hipSuccess) memset(p->pend_pin, 0, 4 * sizeof(int));
-    if (e != hipSuccess) rc = ctx->fail(e, "optimistic-verdict resources");
-  }
-  if (rc != 0) { blsq_dogbox_plan_destroy(p); return rc; }
-  HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-  ctx->dog_plans.push_back(p);
+  if (int rc_ = step_plan_init(ctx, p, B, m, n, (size_t)B * round_up(n + 1, 16), true, [p] { return dog_alloc_state(p); }))
+    return rc_;
   *out = p;
   return 0;
 }
 
-extern "C" int blsq_dogbox_plan_destroy(blsq_dogbox_plan* p) {
-  if (!p) return -1;
-  hipStreamSynchronize(p->ctx->stream);
-  { auto& v = p->ctx->dog_plans; v.erase(std::remove(v.begin(), v.end(), p), v.end()); }
-  if (p->pend_pin) hipHostFree(p->pend_pin);
-  p->tree.release(); p->csne.release();
-  p->S.release(); p->X.release(); p->vecs.release(); p->ivecs.release(); p->scal2.release();
-  p->sweeps.release(); p->active.release(); p->onb.release(); p->o_vec.release();
-  p->o_onb.release(); p->o_scal.release(); p->o_info.release(); p->in_J.release();
-  p->in_f.release(); p->in_vec.release(); p->in_scal.release(); p->gate_ints.release(); p->colinfo.release();
-  delete p;
-  return 0;
-}
+extern "C" int blsq_dogbox_plan_destroy(blsq_dogbox_plan* p) { return step_plan_destroy(p); }
 
 extern "C" int blsq_dogbox_factor_dev(blsq_dogbox_plan* p, const double* dJ, const double* df,
                                       const double* dx, const double* dlb, const double* dub,
@@ -356,25 +307,16 @@ extern "C" int blsq_dogbox_factor_dev(blsq_dogbox_plan* p, const double* dJ, con
                                       const int64_t* don_bound) {
   if (!p) return -1;
   blsq_ctx* ctx = p->ctx;
-  if (!dJ) return ctx->bad(2, "J is NULL");
-  if (!df) return ctx->bad(3, "f is NULL");
-  if (!dx || !dlb || !dub) return ctx->bad(4, "x/lb/ub is NULL");
-  if (!dscale_io) return ctx->bad(7, "scale is NULL");
-  if (scale_mode < 0 || scale_mode > 2) return ctx->bad(8, "scale_mode");
+  if (int rc_ = factor_args(ctx, dJ, df, dx, dlb, dub, dscale_io, scale_mode)) return rc_;
   if (!don_bound) return ctx->bad(9, "on_bound is NULL");
   HIPCHK(ctx, hipSetDevice(ctx->device));
   int rc = verdict_published(p);               // (a verdict nobody read: its counters leave before they are cleared)
   if (rc) return rc;
-  rc = dog_put(p, dx, dlb, dub, dscale_io, don_bound, hipMemcpyDeviceToDevice, true);
+  rc = put_state(p, dx, dlb, dub, dscale_io, don_bound, hipMemcpyDeviceToDevice, true);
   if (rc) return rc;
   p->pend_scale_io = dscale_io;
   if ((rc = dog_factor_core(p, dJ, df, p->n, scale_mode, nullptr, true))) return rc;
-  if (scale_mode != BLSQ_SCALE_GIVEN) {
-    HIPCHK(ctx, hipMemcpy2DAsync(dscale_io, sizeof(double) * p->n, p->st.scale,
-                                 sizeof(double) * p->ld, sizeof(double) * p->n, p->B,
-                                 hipMemcpyDeviceToDevice, ctx->stream));
-  }
-  return 0;
+  return scale_back(p, dscale_io, scale_mode);
 }
 
 extern "C" int blsq_dogbox_step_dev(blsq_dogbox_plan* p, const double* dDelta) {
@@ -389,7 +331,7 @@ extern "C" int blsq_dogbox_step_dev(blsq_dogbox_plan* p, const double* dDelta) {
     });
     if (rc) return rc;
     bool redo = false;
-    if ((rc = dog_resolve(p, &redo))) return rc;
+    if ((rc = p->resolve(&redo))) return rc;
     if (!redo) break;
   }
   return 0;
@@ -402,7 +344,7 @@ extern "C" int blsq_dogbox_fetch_factor(blsq_dogbox_plan* p, double* g, uint8_t*
   blsq_ctx* ctx = p->ctx;
   const int B = p->B, n = p->n, ld = p->ld;
   int rc;
-  if ((rc = dog_resolve(p, nullptr))) return rc;
+  if ((rc = p->resolve(nullptr))) return rc;
   if ((rc = get_vec(ctx, g, n, p->st.g, ld, B))) return rc;
   if ((rc = get_vec(ctx, scale, n, p->st.scale, ld, B))) return rc;
   if ((rc = get_vec(ctx, (unsigned char*)active_set, n, p->st.active, ld, B))) return rc;
@@ -439,35 +381,18 @@ extern "C" int blsq_dogbox_fetch_factor(blsq_dogbox_plan* p, double* g, uint8_t*
   return 0;
 }
 
-extern "C" int blsq_dogbox_debug_cond(blsq_dogbox_plan* p, double* k2) {
-  if (!p) return -1;
-  blsq_ctx* ctx = p->ctx;
-  if (!k2) return ctx->bad(2, "k2 is NULL");
-  if (!p->tree.gram) { for (int b = 0; b < p->B; ++b) k2[b] = 0.0; return 0; }
-  { int rc_ = dog_resolve(p, nullptr); if (rc_) return rc_; }
-  HIPCHK(ctx, hipMemcpyAsync(k2, p->tree.gram_k2.p, sizeof(double) * p->B, hipMemcpyDeviceToHost,
-                             ctx->stream));
-  return blsq_sync(ctx);
-}
+extern "C" int blsq_dogbox_debug_cond(blsq_dogbox_plan* p, double* k2) { return debug_cond(p, k2); }
 
 extern "C" int blsq_dogbox_debug_fast(blsq_dogbox_plan* p, int32_t* fast) {
   if (!p) return -1;
-  blsq_ctx* ctx = p->ctx;
-  if (!fast) return ctx->bad(2, "fast is NULL");
-  { int rc_ = dog_resolve(p, nullptr); if (rc_) return rc_; }
-  HIPCHK(ctx, hipMemcpyAsync(fast, p->gate_ints.p, sizeof(int) * p->B, hipMemcpyDeviceToHost,
-                             ctx->stream));
-  return blsq_sync(ctx);
+  if (!fast) return p->ctx->bad(2, "fast is NULL");
+  return fetch_resolved(p, fast, p->gate_ints.p, sizeof(int));
 }
 
 extern "C" int blsq_dogbox_debug_sweeps(blsq_dogbox_plan* p, int32_t* sweeps) {
   if (!p) return -1;
-  blsq_ctx* ctx = p->ctx;
-  if (!sweeps) return ctx->bad(2, "sweeps is NULL");
-  { int rc_ = dog_resolve(p, nullptr); if (rc_) return rc_; }
-  HIPCHK(ctx, hipMemcpyAsync(sweeps, p->sweeps.p, sizeof(int) * p->B, hipMemcpyDeviceToHost,
-                             ctx->stream));
-  return blsq_sync(ctx);
+  if (!sweeps) return p->ctx->bad(2, "sweeps is NULL");
+  return fetch_resolved(p, sweeps, p->sweeps.p, sizeof(int));
 }
 
 extern "C" int blsq_dogbox_fetch_step(blsq_dogbox_plan* p, double* step, double* x_new,
@@ -505,24 +430,12 @@ extern "C" int blsq_dogbox_factor(blsq_dogbox_plan* p, const double* J, const do
                                   int32_t* all_active) {
   if (!p) return -1;
   blsq_ctx* ctx = p->ctx;
-  if (!J) return ctx->bad(2, "J is NULL");
-  if (!f) return ctx->bad(3, "f is NULL");
-  if (!x || !lb || !ub) return ctx->bad(4, "x/lb/ub is NULL");
-  if (!scale_io) return ctx->bad(7, "scale is NULL");
-  if (scale_mode < 0 || scale_mode > 2) return ctx->bad(8, "scale_mode");
+  if (int rc_ = factor_args(ctx, J, f, x, lb, ub, scale_io, scale_mode)) return rc_;
   if (!on_bound) return ctx->bad(9, "on_bound is NULL");
   HIPCHK(ctx, hipSetDevice(ctx->device));
-  const size_t jb = sizeof(double) * (size_t)p->B * p->m * p->n;
-  const size_t fb = sizeof(double) * (size_t)p->B * p->m;
-  if (!p->in_J.p || !p->in_f.p) {       // lazily, and again if an earlier attempt failed half way
-    hipError_t e = p->in_J.p ? hipSuccess : p->in_J.alloc(jb);
-    if (e != hipSuccess) return ctx->fail(e, "hipMalloc(J staging)");
-    e = p->in_f.p ? hipSuccess : p->in_f.alloc(fb);
-    if (e != hipSuccess) return ctx->fail(e, "hipMalloc(f staging)");
-  }
-  HIPCHK(ctx, hipMemcpyAsync(p->in_J.p, J, jb, hipMemcpyHostToDevice, ctx->stream));
-  HIPCHK(ctx, hipMemcpyAsync(p->in_f.p, f, fb, hipMemcpyHostToDevice, ctx->stream));
-  int rc = dog_put(p, x, lb, ub, scale_io, on_bound, hipMemcpyHostToDevice);
+  int rc = stage_alloc(p);
+  if (rc == 0) rc = stage_upload(p, J, f);
+  if (rc == 0) rc = put_state(p, x, lb, ub, scale_io, on_bound, hipMemcpyHostToDevice);
   if (rc) return rc;
   if ((rc = dog_factor_core(p, p->in_J.as<double>(), p->in_f.as<double>(), p->n, scale_mode, nullptr)))
     return rc;

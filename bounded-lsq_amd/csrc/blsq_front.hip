@@ -1,5 +1,6 @@
-// The factorisation front end of a plan (QrTree: Gram / certificate / CholeskyQR2 / Householder tree) and the CSNE
-// tier's host state (CsneTier), shared by the TRF and the dogbox plans (blsq_host.h).
+// The factorisation front end of a plan (QrTree: Gram / certificate / CholeskyQR2 / Householder tree), the CSNE
+// tier's host state (CsneTier) and the plumbing of the entry points (StepPlan), shared by the TRF and the dogbox plans
+// (blsq_host.h).
 #include "blsq_host.h"
 
 namespace blsq_host {
@@ -35,9 +36,9 @@ int QrTree::build(blsq_ctx* ctx, int B_, int rows, int n_, size_t extra_rp_rows)
       return rc_;
     max_slot_rows = std::max(max_slot_rows, (size_t)B * L.nleaf * L.RP);
     max_slots = std::max(max_slots, (size_t)B * L.nleaf);
-    levels.push_back(L);
-    if (L.nleaf == 1) break;
-    cur_rows = L.nleaf * NPAD;
+    levels.push_back(std::move(L));
+    if (levels.back().nleaf == 1) break;
+    cur_rows = levels.back().nleaf * NPAD;
     first = false;
   }
   if (int rc_ = alloc_all(ctx, {{&V, sizeof(double) * max_slot_rows * NP * 16, "hipMalloc(V scratch)"},
@@ -73,15 +74,6 @@ int QrTree::build(blsq_ctx* ctx, int B_, int rows, int n_, size_t extra_rp_rows)
     if (e != hipSuccess) return ctx->fail(e, "hipMemsetAsync(Gram mask)");
   }
   return 0;
-}
-
-void QrTree::release() {
-  for (auto& L : levels) L.R.release();
-  V.release(); T.release();
-  gram_part.release(); gram_dsc.release(); gram_ints.release(); gram_keep.release();
-  gram_rinv.release(); gram_ywork.release(); gram_k2.release(); gram_cert.release();
-  gram_cflag.release(); gram_ctau.release();
-  cq_W.release(); cq_Wf.release(); cq_G2.release(); cq_R1.release(); cq_R2.release(); cq_z.release(); cq_ints.release();
 }
 
 hipError_t QrTree::gram_sum(blsq_ctx* ctx, GramArgs g, double* Gp, double* Gout, int count, const int* red_mask,
@@ -260,7 +252,7 @@ int QrTree::run_fallback(blsq_ctx* ctx, const double* dJ, const double* df, int 
       })) return rc_;
   // 7. acceptance + R~ = R2 [R c; 0 1] into the triangle slot;  8. the tree for what is left
   if (int rc_ = ctx->run(K_CQR2_COMBINE, "launch_cqr2_combine", [&] {
-        return launch_cqr2_combine(q, nfb, runm, piv2, G2, cq_R2.as<double>(), Rf, tmask, ctx->cq_accept_dev,
+        return launch_cqr2_combine(q, nfb, runm, piv2, G2, cq_R2.as<double>(), Rf, tmask, ctx->cq_accept_dev.as<unsigned long long>(),
             ctx->stream);
       })) return rc_;
   return run_levels(ctx, dJ, df, ldJ, tmask, fb_list(), nfb);
@@ -313,10 +305,6 @@ int CsneTier::build(blsq_ctx* ctx, int B, int m, int n, int ld, bool with_hp) {
   return 0;
 }
 
-void CsneTier::release() {
-  for (DevBuf* b : {&ints, &pmin, &eta, &alpha, &hp, &k2, &vec, &part}) b->release();
-}
-
 // (TRF: 52 KB per problem at n = 256; dogbox records one evaluation, the Newton step)
 bool CsneTier::ensure_recordings() {
   if (!vec.p && vec.alloc(sizeof(double) * (size_t)cs.B * CSNE_MAXE * 3 * cs.ld) != hipSuccess) {
@@ -330,7 +318,6 @@ bool CsneTier::ensure_recordings() {
 // (grows geometrically; hipFree waits for the stream)
 int CsneTier::grow_part(blsq_ctx* ctx, size_t need) {
   if (need <= part_cap) return 0;
-  part.release();
   const size_t cap = std::max(need, 2 * part_cap);
   if (int rc_ = alloc_all(ctx, {{&part, sizeof(double) * cap, "hipMalloc(CSNE partial sums)"}})) {
     part_cap = 0;
@@ -388,3 +375,146 @@ int CsneTier::select(blsq_ctx* ctx, QrTree& t, const GramCholArgs& chol, int nfb
   t.any_gram = t.any_gram || *ntree < nfb;
   return 0;
 }
+
+// ---- what the TRF and the dogbox entry points share (StepPlan) ---------------------------------------------------
+namespace blsq_host {
+
+int step_plan_args(blsq_ctx* ctx, int B, int m, int n, const void* out) {
+  if (!out) return ctx->bad(5, "out is NULL");
+  if (B <= 0) return ctx->bad(2, "B must be positive");
+  if (m <= 0) return ctx->bad(3, "m must be positive");
+  if (n <= 0) return ctx->bad(4, "n must be positive");
+  return 0;
+}
+
+int step_plan_init(blsq_ctx* ctx, StepPlan* p, int B, int m, int n, size_t extra_rp_rows, bool verdicts,
+                   const std::function<int()>& alloc_state) {
+  p->ctx = ctx; p->B = B; p->m = m; p->n = n;
+  hipError_t e = hipSetDevice(ctx->device);
+  int rc = e == hipSuccess ? 0 : ctx->fail(e, "hipSetDevice(ctx->device)");
+  if (rc == 0) rc = p->tree.build(ctx, B, m, n, extra_rp_rows);
+  if (rc == 0) { p->ld = p->tree.NPAD; rc = alloc_state(); }
+  if (rc == 0 && verdicts) {
+    p->optimistic = ctx->opt.on(OPT_OPTIMISTIC);
+    e = p->pend_pin.alloc(4, hipHostMallocCoherent);
+    if (e != hipSuccess) rc = ctx->fail(e, "optimistic-verdict resources");
+  }
+  if (rc == 0 && (e = hipStreamSynchronize(ctx->stream)) != hipSuccess)
+    rc = ctx->fail(e, "hipStreamSynchronize(ctx->stream)");
+  if (rc != 0) { step_plan_destroy(p); return rc; }
+  ctx->plans.push_back(p);
+  return 0;
+}
+
+int step_plan_destroy(StepPlan* p) {
+  if (!p) return -1;
+  hipStreamSynchronize(p->ctx->stream);
+  { auto& v = p->ctx->plans; v.erase(std::remove(v.begin(), v.end(), p), v.end()); }
+  delete p;
+  return 0;
+}
+
+int factor_args(blsq_ctx* ctx, const void* J, const void* f, const void* x, const void* lb, const void* ub,
+                const void* scale, int scale_mode) {
+  if (!J) return ctx->bad(2, "J is NULL");
+  if (!f) return ctx->bad(3, "f is NULL");
+  if (!x || !lb || !ub) return ctx->bad(4, "x/lb/ub is NULL");
+  if (!scale) return ctx->bad(7, "scale is NULL");
+  if (scale_mode < 0 || scale_mode > 2) return ctx->bad(8, "scale_mode");
+  return 0;
+}
+
+int stage_alloc(StepPlan* p) {
+  if (p->in_J.p && p->in_f.p) return 0;
+  return alloc_all(p->ctx, {{&p->in_J, sizeof(double) * (size_t)p->B * p->m * p->n, "hipMalloc(J staging)"},
+                            {&p->in_f, sizeof(double) * (size_t)p->B * p->m, "hipMalloc(f staging)"}});
+}
+
+int stage_upload(StepPlan* p, const double* J, const double* f) {
+  blsq_ctx* ctx = p->ctx;
+  HIPCHK(ctx, hipMemcpyAsync(p->in_J.p, J, p->in_J.bytes, hipMemcpyHostToDevice, ctx->stream));
+  HIPCHK(ctx, hipMemcpyAsync(p->in_f.p, f, p->in_f.bytes, hipMemcpyHostToDevice, ctx->stream));
+  return 0;
+}
+
+int put_state(StepPlan* p, const double* x, const double* lb, const double* ub, const double* scale,
+              const int64_t* on_bound, hipMemcpyKind kind, bool zero_counts) {
+  blsq_ctx* ctx = p->ctx;
+  int rc;
+  if (kind == hipMemcpyDeviceToDevice) {                // one launch instead of four (five) strided copies
+    p->pack_pend = zero_counts && p->tree.gram;
+    p->tree.fb_zeroed = p->pack_pend;
+    PackVecs pv{{x, lb, ub, scale, on_bound}, {p->vec(0), p->vec(1), p->vec(2), p->scale(), on_bound ? p->on_bound : nullptr},
+                p->pack_pend ? p->tree.fb_count() : nullptr, 3};
+    if (p->pack_pend) { p->pack_pv = pv; return 0; }
+    hipError_t e = launch_pack_vecs(pv, p->n, p->ld, p->B, ctx->stream);
+    if (e != hipSuccess) return ctx->fail(e, "launch_pack_vecs");
+    return 0;
+  }
+  if ((rc = put_vec(ctx, p->vec(0), p->ld, x, p->n, p->B, kind))) return rc;
+  if ((rc = put_vec(ctx, p->vec(1), p->ld, lb, p->n, p->B, kind))) return rc;
+  if ((rc = put_vec(ctx, p->vec(2), p->ld, ub, p->n, p->B, kind))) return rc;
+  if ((rc = put_vec(ctx, p->scale(), p->ld, scale, p->n, p->B, kind))) return rc;
+  if (on_bound)
+    HIPCHK(ctx, hipMemcpy2DAsync(p->on_bound, sizeof(long long) * p->ld, on_bound, sizeof(long long) * p->n,
+                                 sizeof(long long) * p->n, p->B, kind, ctx->stream));
+  return 0;
+}
+
+int scale_back(StepPlan* p, double* dscale_io, int scale_mode) {
+  blsq_ctx* ctx = p->ctx;
+  if (scale_mode == BLSQ_SCALE_GIVEN || !dscale_io) return 0;
+  HIPCHK(ctx, hipMemcpy2DAsync(dscale_io, sizeof(double) * p->n, p->scale(), sizeof(double) * p->ld,
+                               sizeof(double) * p->n, p->B, hipMemcpyDeviceToDevice, ctx->stream));
+  return 0;
+}
+
+int fetch_resolved(StepPlan* p, void* dst, const void* src, size_t item) {
+  blsq_ctx* ctx = p->ctx;
+  { int rc_ = p->resolve(nullptr); if (rc_) return rc_; }
+  HIPCHK(ctx, hipMemcpyAsync(dst, src, item * p->B, hipMemcpyDeviceToHost, ctx->stream));
+  return blsq_sync(ctx);
+}
+
+int debug_cond(StepPlan* p, double* k2) {
+  if (!p) return -1;
+  if (!k2) return p->ctx->bad(2, "k2 is NULL");
+  if (!p->tree.gram) { for (int b = 0; b < p->B; ++b) k2[b] = 0.0; return 0; }
+  return fetch_resolved(p, k2, p->tree.gram_k2.p, sizeof(double));
+}
+
+int take_pack(StepPlan* p, const int* mask, const PackVecs** pk) {
+  *pk = nullptr;
+  if (!p->pack_pend) return 0;
+  p->pack_pend = false;
+  if (!mask) { *pk = &p->pack_pv; return 0; }
+  hipError_t e = launch_pack_vecs(p->pack_pv, p->n, p->ld, p->B, p->ctx->stream);
+  if (e != hipSuccess) return p->ctx->fail(e, "launch_pack_vecs");
+  return 0;
+}
+
+int verdict_published(StepPlan* p) {
+  if (!p->pend_unpub) return 0;
+  p->pend_unpub = false;
+  blsq_ctx* ctx = p->ctx;
+  HIPCHK(ctx, ctx->publish(p->tree.fb_count(), 3, p->pend_pin, &p->pend_seq));
+  return 0;
+}
+
+int verdict_drop(StepPlan* p) {
+  if (!p->pending) return 0;
+  blsq_ctx* ctx = p->ctx;
+  p->pending = false;
+  { int rc_ = verdict_published(p); if (rc_) return rc_; }
+  HIPCHK(ctx, ctx->await(p->pend_pin, p->pend_seq));
+  const int nfb_ = p->pend_pin[0], njac_ = p->pend_pin[1];
+  if (p->pend_tail) { if (!verdict_settled(p)) p->guess_settled = false; }
+  else if (nfb_ > 0 || njac_ > 0) {
+    p->guess_ok = false;
+    verdict_wrong(p);
+    ctx->gram_fast -= nfb_; ctx->gram_fallback += nfb_;
+  } else verdict_right(p);
+  return 0;
+}
+
+}  // namespace blsq_host

@@ -1,9 +1,11 @@
 // Host side of the C-ABI (include/blsq.h), shared by its translation units: contexts, the RCCL binding, device buffers,
 // the factorisation front end of a plan (QrTree: Gram / certificate / CholeskyQR2 / Householder tree), the CSNE tier's
 // host state (CsneTier) and the plan structures.  blsq_ctx.hip: contexts, memory, timing, communicator, diagnostics;
-// blsq_front.hip: the bodies of QrTree and CsneTier; blsq_trf.hip: TRF and the row-split (TSQR) plans; blsq_dogbox.hip:
-// dogbox plans; blsq_outer.hip: the batched outer drivers and finite differences; blsq_cov.hip: covariance plans.
+// blsq_front.hip: the bodies of QrTree and CsneTier and the plumbing the step plans' entry points share; blsq_trf.hip: TRF
+// and the row-split (TSQR) plans; blsq_dogbox.hip: dogbox plans; blsq_outer.hip: the batched outer drivers and finite differences; blsq_cov.hip: covariance plans.
 // Internal: nothing here is part of the ABI.
+// Ownership: a plan's device memory is freed by its destructor (DevBuf / PinnedBuf, dev_buf.h) — a new buffer is a new
+// member and nothing else.  A destroy call synchronises the plan's stream, takes the plan off its ctx and deletes it.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <rccl/rccl.h>      // types and prototypes only: the library is dlopen'ed on first use
@@ -19,6 +21,7 @@
 
 #include "../../include/blsq.h"
 #include "blsq_kernels.h"
+#include "dev_buf.h"
 
 using namespace blsq;
 
@@ -57,7 +60,18 @@ static inline void cpu_relax() {
   asm volatile("yield" ::: "memory");
 #endif
 }
+struct StepPlan;
 struct blsq_ctx {
+  blsq_ctx() = default;
+  blsq_ctx(const blsq_ctx&) = delete;
+  blsq_ctx& operator=(const blsq_ctx&) = delete;
+  // (after blsq_ctx_destroy has synchronised the stream; `pinned` and `cq_accept_dev` free themselves)
+  ~blsq_ctx() {
+    for (auto e : pool) hipEventDestroy(e);
+    for (auto e : copy_ev) hipEventDestroy(e);
+    if (copy_stream) hipStreamDestroy(copy_stream);
+    if (stream) hipStreamDestroy(stream);
+  }
   int device = 0;
   hipStream_t stream = nullptr;
   hipStream_t copy_stream = nullptr;              // host-pointer API: H2D of the next problems while the Gram of the last runs
@@ -70,12 +84,12 @@ struct blsq_ctx {
   struct Pending { int slot; hipEvent_t a, b; };
   std::vector<Pending> pending;
   std::vector<hipEvent_t> pool;
-  int* pinned = nullptr;            // 128 pinned host ints: device -> host counters without staging
+  PinnedBuf<int> pinned;            // 128 pinned host ints: device -> host counters without staging
                                     // ([0..3] one-shot read-backs, [32 + 4 r ..] the slot of Newton round r)
   int pub_seq = 0;                  // sequence number of the last publish()
   blsq::Options opt;                // the switches of this ctx (blsq_options.h: environment at creation, blsq_ctx_set_option)
   long long gram_fast = 0, gram_fallback = 0;   // problems factored by the normal equations / handed to the QR tree
-  unsigned long long* cq_accept_dev = nullptr;  // device counter: rejected problems the CholeskyQR2 tier factored
+  DevBuf cq_accept_dev;             // device counter (unsigned long long): rejected problems the CholeskyQR2 tier factored
   // CSNE tier (csne_kernels.hip): problems routed to it by factor calls, step-solves it delivered, step-solves it
   // declined (acceptance failed at step time: the problem went on to CholeskyQR2 / the tree)
   unsigned long long csne_routed = 0, csne_steps = 0, csne_declined = 0;
@@ -84,8 +98,7 @@ struct blsq_ctx {
   int comm_ranks = 1, comm_rank = 0;
   // plans of this ctx (an optimistic factor call leaves a verdict pending on its plan: blsq_sync and
   // the calls that may invalidate the caller's J resolve it, see ctx_resolve_pending)
-  std::vector<blsq_trf_plan*> trf_plans;
-  std::vector<blsq_dogbox_plan*> dog_plans;
+  std::vector<StepPlan*> plans;
 
   int fail(hipError_t e, const char* where) {
     err = std::string(where) + ": " + hipGetErrorString(e);
@@ -227,28 +240,6 @@ int rccl_fail(blsq_ctx* ctx, ncclResult_t r, const char* where);   // (blsq_ctx.
     if (r__ != ncclSuccess) return rccl_fail((ctx), r__, #call);     \
   } while (0)
 
-struct DevBuf {
-  void* p = nullptr;
-  size_t bytes = 0;
-  hipError_t alloc(size_t b) {
-    bytes = b;
-    if (b == 0) return hipSuccess;
-    return hipMalloc(&p, b);
-  }
-  void release() { if (p) hipFree(p); p = nullptr; }
-  template <class T> T* as() const { return reinterpret_cast<T*>(p); }
-};
-
-// The buffers of a list, allocated in turn; 0, or the first failure recorded under its `what`
-struct AllocReq { DevBuf* buf; size_t bytes; const char* what; };
-inline int alloc_all(blsq_ctx* ctx, std::initializer_list<AllocReq> reqs) {
-  for (const AllocReq& r : reqs) {
-    const hipError_t e = r.buf->alloc(r.bytes);
-    if (e != hipSuccess) return ctx->fail(e, r.what);
-  }
-  return 0;
-}
-
 // One level of the TSQR tree: nleaf workgroups per problem.
 struct Level {
   int rowsA, rows_per_leaf, nleaf, RP, LDP;
@@ -284,7 +275,6 @@ struct QrTree {
 
   // rows: source rows per problem at level 0
   int build(blsq_ctx* ctx, int B_, int rows, int n_, size_t extra_rp_rows);
-  void release();
   // [J f] -> triangle by the normal equations where the conditioning gate allows it.
   // Returns the number of problems left for the Householder tree in *nfallback; their indices
   // are flagged in the fallback mask (n + 1 / 0 per problem).
@@ -352,7 +342,6 @@ struct CsneTier {
   CsneState cs{};
 
   int build(blsq_ctx* ctx, int B, int m, int n, int ld, bool with_hp);   // buffers, zeroed, and cs over them; on = true
-  void release();
   bool ensure_recordings();         // false: no room for them (the caller takes the tier out of service)
   int grow_part(blsq_ctx* ctx, size_t need);
   int relist(blsq_ctx* ctx);        // a masked factor call refreshed some problems: the list from the flags
@@ -382,7 +371,7 @@ struct VerdictState {
   // Second guess: every problem is settled inside the factor kernel / stage 0 of the certificate, so the certificate
   // and gate launches are not even enqueued; checked with the same read-back.
   bool guess_settled = false, pend_tail = false;
-  int* pend_pin = nullptr;          // 4 pinned ints of this plan ([3]: sequence number of the publish)
+  PinnedBuf<int> pend_pin;          // 4 pinned ints of this plan ([3]: sequence number of the publish)
   int pend_seq = 0;
   bool pend_unpub = false;          // the verdict's counters have not been sent yet: the step kernel of the next
                                     // step call stores them on its way in (or verdict_published() sends them now)
@@ -394,10 +383,30 @@ struct VerdictState {
   double* pend_scale_io = nullptr;
 };
 
-struct blsq_trf_plan : VerdictState {
+// What the TRF and the dogbox plans share: shape, front end, CSNE tier, the staging of the host-pointer API and the
+// buffers the shared plumbing reads (step_plan_* / put_state / ... below).
+struct StepPlan : VerdictState {
   blsq_ctx* ctx = nullptr;
   int B = 0, m = 0, n = 0, ld = 0;
   QrTree tree;
+  // CSNE tier: rejected problems whose steps are corrected against J in one streaming pass (TRF: at step time; dogbox:
+  // the Newton step of the free block, at factor time)
+  CsneTier csne;
+  bool gate_done = false;           // the rank gate already ran in this factor call (no problem left the normal-equations path)
+  int njac = -1;                    // problems it sent to the Jacobi SVD (-1: unknown)
+  DevBuf vecs;                      // [.][B][ld] n-space vectors; the first four are x, lb, ub, scale in both plans
+  DevBuf sweeps, o_scal, o_info;
+  DevBuf in_J, in_f, in_scal;       // staging for the host-pointer API
+  long long* on_bound = nullptr;    // dogbox: DogState::on_bound
+  bool settles_wide = false;        // TRF: stage 0 of the certificate settles problems of N > 80 too (verdict_settled)
+  double* vec(int k) const { return vecs.as<double>() + (size_t)k * B * ld; }
+  double* scale() const { return vec(3); }
+  virtual ~StepPlan() = default;
+  virtual int resolve(bool* redo) = 0;   // the verdict of an optimistic factor call (verdict_resolve)
+};
+
+struct blsq_trf_plan : StepPlan {
+  blsq_trf_plan() { settles_wide = true; }
   // which kernels factor the augmented / Newton systems of the current triangles (per problem:
   // `path`, see trf_after_triangle)
   const int* path = nullptr;
@@ -410,8 +419,6 @@ struct blsq_trf_plan : VerdictState {
   DevBuf aug_hmax;                  // [B] largest diagonal entry of H (LmState::hmax: which Newton systems of a
                                     // Householder-path problem may be factored from the Gram)
   bool gram_valid = false;          // tree.gram_keep holds the Grams of the current factor call's problems
-  // CSNE tier: rejected problems whose steps are corrected against J in one streaming pass, at step time
-  CsneTier csne;
   int last_scale_mode = 0;          // scale_mode of the last factor call (a problem that leaves the tier at step time is prepared again)
   // TSQR (multi-rank) extras
   int nranks = 1, m_total = 0;
@@ -419,9 +426,8 @@ struct blsq_trf_plan : VerdictState {
   DevBuf Rcomb;                     // [1][NPAD*NPAD] merged triangle
   DevBuf Rstack;                    // [nranks][NPAD*NPAD] gathered triangles (blsq_tsqr_factor_dev)
   // n-space state
-  DevBuf X, vecs, scal2, sweeps;
-  DevBuf o_vec, o_hits, o_act, o_scal, o_info;
-  DevBuf in_J, in_f, in_vec, in_scal;   // staging for the host-pointer API
+  DevBuf X, scal2;
+  DevBuf o_vec, o_hits, o_act;
   TrfState st{};
   TrfStepOut out{};
   double* d_alpha_in = nullptr;
@@ -431,32 +437,24 @@ struct blsq_trf_plan : VerdictState {
   LmState lm{};
   int lm_enable = 1;                // SVD-free trust-region path allowed at all (BLSQ_NO_SVDFREE)
   int lm_gate_mask = 3;             // launch_lm_gate: bit 0 Householder-path problems, bit 1 normal-equations-path problems
-  bool gate_done = false;           // lm_gate already ran in this factor call (no problem left the normal-equations path)
   bool lm_counts_clean = false;     // the Newton-round counters are zero (left so by the last step kernel)
   // The triangle slots st.X hold zeros outside the factors as long as only the Cholesky kernels have
   // written them (zeroed at allocation); the stacked QR and the Jacobi SVD write there.  While clean, the
   // Cholesky of the augmented system does not store those zeros again (half of its bytes).
   bool x_dirty = true;
   int lm_rounds_last = 12;          // Newton rounds that had work in the last step call (run-ahead only over those)
-  int njac = -1;                    // problems it sent to the Jacobi SVD (-1: unknown)
+  int resolve(bool* redo) override;      // (blsq_trf.hip)
 };
 
-struct blsq_dogbox_plan : VerdictState {
-  blsq_ctx* ctx = nullptr;
-  int B = 0, m = 0, n = 0, ld = 0;
-  QrTree tree;
-  DevBuf S, X, vecs, ivecs, scal2, sweeps, active, onb;
-  DevBuf o_vec, o_onb, o_scal, o_info;
-  DevBuf in_J, in_f, in_vec, in_scal;
-  bool gate_done = false;           // as blsq_trf_plan
-  int njac = -1;
+struct blsq_dogbox_plan : StepPlan {
+  DevBuf S, X, ivecs, scal2, active, onb;
+  DevBuf o_vec, o_onb;
   DevBuf gate_ints;                 // [3B] fast flags, Jacobi launch mask, finished-in-the-Cholesky-kernel flags
   DevBuf colinfo;                   // [B][2] column-norm summary of the free block (Gram-path problems)
   int svdfree_enable = 1;
-  // CSNE tier: the Newton step of a rejected problem's free block corrected against J at factor time
-  CsneTier csne;
   DogState st{};
   DogStepOut out{};
+  int resolve(bool* redo) override;      // (blsq_dogbox.hip)
 };
 
 // ---- shared between the translation units -------------------------------------------------------
@@ -471,32 +469,41 @@ int get_vec(blsq_ctx* ctx, T* dst, int n, const T* src, int ld, int B) {
   return 0;
 }
 
+// ---- the plumbing the TRF and the dogbox entry points share (blsq_front.hip) ----------------------------------------
+// A new plan `p` of either kind, after the entry's own argument checks: the front end (extra_rp_rows: scratch rows beyond
+// the tree's own), the plan's alloc_state(), the optimistic verdict's resources (`verdicts`), registration with the ctx.
+// On failure p is destroyed.
+int step_plan_init(blsq_ctx* ctx, StepPlan* p, int B, int m, int n, size_t extra_rp_rows, bool verdicts,
+                   const std::function<int()>& alloc_state);
+int step_plan_destroy(StepPlan* p);    // synchronise the stream, take p off its ctx, delete it
+// B, m, n and `out` of blsq_{trf,dogbox}_plan_create
+int step_plan_args(blsq_ctx* ctx, int B, int m, int n, const void* out);
+// J, f, x / lb / ub, scale and scale_mode of the four factor calls
+int factor_args(blsq_ctx* ctx, const void* J, const void* f, const void* x, const void* lb, const void* ub,
+                const void* scale, int scale_mode);
+// staging of a host-pointer factor call: the plan's in_J / in_f (allocated on first use), and J, f into them
+int stage_alloc(StepPlan* p);
+int stage_upload(StepPlan* p, const double* J, const double* f);
+// x, lb, ub, scale (and on_bound: dogbox) of a factor call into the plan's state layout.  Device to device it is one
+// pack launch — or, zero_counts in front of a Gram-stage factor call, none: the prep launch of that stage does it
+// and clears the gate counters of the call (take_pack)
+int put_state(StepPlan* p, const double* x, const double* lb, const double* ub, const double* scale,
+              const int64_t* on_bound, hipMemcpyKind kind, bool zero_counts = false);
+// the scale a 'jac' scaling mode computed, [B][ld] -> the caller's device [B][n]
+int scale_back(StepPlan* p, double* dscale_io, int scale_mode);
+// resolve the plan's verdict, copy B items of `item` bytes to the host, blsq_sync
+int fetch_resolved(StepPlan* p, void* dst, const void* src, size_t item);
+int debug_cond(StepPlan* p, double* k2);   // blsq_{trf,dogbox}_debug_cond
+
 // the deferred vectors of this factor call: handed to the prep launch (returns them), or — a masked call keeps the
 // other problems' state, so its prep launch cannot do the copy — packed by the stand-alone launch right here
-template <class Plan>
-int take_pack(Plan* p, const int* mask, const PackVecs** pk) {
-  *pk = nullptr;
-  if (!p->pack_pend) return 0;
-  p->pack_pend = false;
-  if (!mask) { *pk = &p->pack_pv; return 0; }
-  hipError_t e = launch_pack_vecs(p->pack_pv, p->n, p->ld, p->B, p->ctx->stream);
-  if (e != hipSuccess) return p->ctx->fail(e, "launch_pack_vecs");
-  return 0;
-}
+int take_pack(StepPlan* p, const int* mask, const PackVecs** pk);
 
 // The counters of a pending verdict are on their way to the host (a stand-alone publish unless a step kernel has
 // taken them along) — to be called before anything waits for them or overwrites them.
-template <class Plan>
-int verdict_published(Plan* p) {
-  if (!p->pend_unpub) return 0;
-  p->pend_unpub = false;
-  blsq_ctx* ctx = p->ctx;
-  HIPCHK(ctx, ctx->publish(p->tree.fb_count(), 3, p->pend_pin, &p->pend_seq));
-  return 0;
-}
+int verdict_published(StepPlan* p);
 // ... and the arguments with which the step kernel of this call takes them along (dst == nullptr: nothing to do)
-template <class Plan>
-PublishArgs verdict_rides(Plan* p) {
+inline PublishArgs verdict_rides(StepPlan* p) {
   if (!p->pend_unpub) return PublishArgs{nullptr, 0, nullptr, 0};
   p->pend_unpub = false;
   p->pend_seq = ++p->ctx->pub_seq;
@@ -516,33 +523,16 @@ inline bool verdict_may_guess(VerdictState* p) {
 }
 
 // has the factor kernel (N <= 80) / stage 0 of the certificate (TRF, N > 80) settled every problem of the call?
-inline bool verdict_settled(const blsq_trf_plan* p) { return p->pend_pin[2] == 0; }
-inline bool verdict_settled(const blsq_dogbox_plan* p) { return p->ld <= 80 && p->pend_pin[2] == 0; }
+inline bool verdict_settled(const StepPlan* p) { return (p->settles_wide || p->ld <= 80) && p->pend_pin[2] == 0; }
 
 // A verdict nobody asked for belongs to a factor that is being overwritten (top of a factor call): no repair, but it is
 // still read — the path statistics and the decision whether to guess again depend on it.
-template <class Plan>
-int verdict_drop(Plan* p) {
-  if (!p->pending) return 0;
-  blsq_ctx* ctx = p->ctx;
-  p->pending = false;
-  { int rc_ = verdict_published(p); if (rc_) return rc_; }
-  HIPCHK(ctx, ctx->await(p->pend_pin, p->pend_seq));
-  const int nfb_ = p->pend_pin[0], njac_ = p->pend_pin[1];
-  if (p->pend_tail) { if (!verdict_settled(p)) p->guess_settled = false; }
-  else if (nfb_ > 0 || njac_ > 0) {
-    p->guess_ok = false;
-    verdict_wrong(p);
-    ctx->gram_fast -= nfb_; ctx->gram_fallback += nfb_;
-  } else verdict_right(p);
-  return 0;
-}
+int verdict_drop(StepPlan* p);
 
 // The counters of this factor call ride on the next step kernel (verdict_rides; verdict_published sends them if nothing
 // took them along); the verdict is read by verdict_resolve.  skip_tail: the second guess — the gate launches were not
 // enqueued.
-template <class Plan>
-void verdict_arm(Plan* p, bool skip_tail, const double* dJ, const double* df, int ldJ, int scale_mode) {
+inline void verdict_arm(StepPlan* p, bool skip_tail, const double* dJ, const double* df, int ldJ, int scale_mode) {
   p->pend_unpub = true;
   p->pending = true; p->pend_tail = skip_tail;
   p->pend_dJ = dJ; p->pend_df = df; p->pend_ldJ = ldJ; p->pend_scale_mode = scale_mode;
@@ -554,8 +544,8 @@ void verdict_arm(Plan* p, bool skip_tail, const double* dJ, const double* df, in
 // did not — after `repair` the state is what the synchronous path would have left, and whatever was computed from the
 // guessed state must be computed again.  gate_tail(): the launches the second guess left out (certificate, rank gate);
 // repair(nfb): the plan's own way from "nfb problems left the normal-equations path" to a finished factor state.
-template <class Plan, class GateTail, class Repair>
-int verdict_resolve(Plan* p, bool* redo, GateTail gate_tail, Repair repair) {
+template <class GateTail, class Repair>
+int verdict_resolve(StepPlan* p, bool* redo, GateTail gate_tail, Repair repair) {
   if (redo) *redo = false;
   if (!p->pending) return 0;
   blsq_ctx* ctx = p->ctx;
@@ -587,20 +577,15 @@ int verdict_resolve(Plan* p, bool* redo, GateTail gate_tail, Repair repair) {
   p->gate_done = (nfb == 0);
   p->njac = p->gate_done ? njac : -1;
   { int rc_ = repair(nfb); if (rc_) return rc_; }
-  if (p->pend_scale_mode != BLSQ_SCALE_GIVEN && p->pend_scale_io)
-    HIPCHK(ctx, hipMemcpy2DAsync(p->pend_scale_io, sizeof(double) * p->n, p->st.scale, sizeof(double) * p->ld,
-                                 sizeof(double) * p->n, p->B, hipMemcpyDeviceToDevice, ctx->stream));
-  return 0;
+  return scale_back(p, p->pend_scale_io, p->pend_scale_mode);
 }
 
-// the whole factor call of a plan from device-resident [J f] (mask: outer driver, fresh Jacobians only), and the verdict
-// of an optimistic one (blsq_trf.hip / blsq_dogbox.hip)
+// the whole factor call of a plan from device-resident [J f] (mask: outer driver, fresh Jacobians only)
+// (blsq_trf.hip / blsq_dogbox.hip)
 int trf_factor_core(blsq_trf_plan* p, const double* dJ, const double* df, int ldJ, int scale_mode,
                     const int* mask, bool may_defer = false, bool gram_done = false);
-int trf_resolve(blsq_trf_plan* p, bool* redo);
 int dog_factor_core(blsq_dogbox_plan* p, const double* dJ, const double* df, int ldJ, int scale_mode,
                     const int* mask, bool may_defer = false);
-int dog_resolve(blsq_dogbox_plan* p, bool* redo);
 // every verdict an optimistic factor call left pending on a plan of this ctx is read, and a wrong guess repaired
 int ctx_resolve_pending(blsq_ctx* ctx);
 }  // namespace blsq_host

@@ -5,6 +5,14 @@
 
 // ==================================================== batched outer drivers ===
 struct blsq_outer {
+  blsq_outer() = default;
+  blsq_outer(const blsq_outer&) = delete;
+  blsq_outer& operator=(const blsq_outer&) = delete;
+  ~blsq_outer() {                      // the driver owns its plans (each destroy synchronises the stream first)
+    if (trf) blsq_trf_plan_destroy(trf);
+    if (dog) blsq_dogbox_plan_destroy(dog);
+    if (cov) blsq_cov_plan_destroy(cov);
+  }
   blsq_ctx* ctx = nullptr;
   int method = 0, B = 0, m = 0, n = 0, ld = 0;
   blsq_trf_plan* trf = nullptr;
@@ -34,7 +42,8 @@ extern "C" int blsq_outer_create(blsq_ctx* ctx, int method, int B, int m, int n,
   int rc = (method == 0) ? blsq_trf_plan_create(ctx, B, m, n, &o->trf)
                          : blsq_dogbox_plan_create(ctx, B, m, n, &o->dog);
   if (rc) { delete o; return rc; }
-  o->ld = (method == 0) ? o->trf->ld : o->dog->ld;
+  StepPlan* sp = (method == 0) ? static_cast<StepPlan*>(o->trf) : o->dog;
+  o->ld = sp->ld;
   const size_t vn = sizeof(double) * (size_t)B * n, vm = sizeof(double) * (size_t)B * m;
   hipError_t e = hipSuccess;
   auto al = [&](DevBuf& b, size_t bytes) { if (e == hipSuccess) e = b.alloc(bytes); };
@@ -44,19 +53,16 @@ extern "C" int blsq_outer_create(blsq_ctx* ctx, int method, int B, int m, int n,
   if (e != hipSuccess) { blsq_outer_destroy(o); return ctx->fail(e, "hipMalloc(outer driver)"); }
   OuterState& st = o->st;
   st.B = B; st.m = m; st.n = n; st.ld = o->ld; st.method = method;
+  st.x = sp->vec(0); st.lb = sp->vec(1); st.ub = sp->vec(2); st.scale = sp->scale();
+  st.o_scal = sp->o_scal.as<double>(); st.o_info = sp->o_info.as<int>();
   if (method == 0) {
     blsq_trf_plan* p = o->trf;
-    st.x = p->st.x; st.lb = p->st.lb; st.ub = p->st.ub; st.scale = p->st.scale;
     st.g_norm_fac = p->st.g_norm; st.v = p->st.v; st.ncols = nullptr; st.on_bound = nullptr;
-    st.o_step = p->out.step; st.o_xnew = p->out.x_new; st.o_scal = p->out.scal;
-    st.o_info = p->out.info; st.o_onb = nullptr;
+    st.o_step = p->out.step; st.o_xnew = p->out.x_new; st.o_onb = nullptr;
   } else {
     blsq_dogbox_plan* p = o->dog;
-    st.x = p->st.x; st.lb = p->st.lb; st.ub = p->st.ub; st.scale = p->st.scale;
-    st.g_norm_fac = p->st.g_norm; st.v = nullptr; st.ncols = p->st.ncols;
-    st.on_bound = p->st.on_bound;
-    st.o_step = p->out.step; st.o_xnew = p->out.x_new; st.o_scal = p->out.scal;
-    st.o_info = p->out.info; st.o_onb = p->out.on_bound_new;
+    st.g_norm_fac = p->st.g_norm; st.v = nullptr; st.ncols = p->st.ncols; st.on_bound = p->st.on_bound;
+    st.o_step = p->out.step; st.o_xnew = p->out.x_new; st.o_onb = p->out.on_bound_new;
   }
   st.x0 = o->x0.as<double>(); st.xc = o->xc.as<double>(); st.xt = o->xt.as<double>();
   st.f = o->f.as<double>(); st.ft = o->ft.as<double>();
@@ -74,13 +80,7 @@ extern "C" int blsq_outer_create(blsq_ctx* ctx, int method, int B, int m, int n,
 
 extern "C" int blsq_outer_destroy(blsq_outer* o) {
   if (!o) return 0;
-  if (o->trf) blsq_trf_plan_destroy(o->trf);
-  if (o->dog) blsq_dogbox_plan_destroy(o->dog);
-  if (o->cov) blsq_cov_plan_destroy(o->cov);
-  o->covmask.release(); o->covscale.release();
-  o->x0.release(); o->xc.release(); o->xt.release(); o->f.release(); o->ft.release();
-  o->J.release(); o->dvec.release(); o->ivec.release(); o->counts.release();
-  o->fsc.release(); o->lobj.release(); o->fscale.release();
+  hipStreamSynchronize(o->ctx->stream);
   delete o;
   return 0;
 }

@@ -234,7 +234,7 @@ int trf_gram_stage(blsq_trf_plan* p, int scale_mode, const int* mask, int* nfb, 
       })) return rc_;
   // second guess (N <= 80): the Cholesky kernel settles EVERY problem itself — certificate by its first
   // bound, rank gate by the column-norm bound — as it did in the last call: then the certificate and gate
-  // launches would both be empty and are not enqueued (trf_resolve checks the settled counter)
+  // launches would both be empty and are not enqueued (resolve() checks the settled counter)
   // N > 80: stage 0 of the certificate is still launched (it IS what settles a problem there) — the norm stage, the
   // shifted factorisation and the rank gate, three launches that would find nothing to do, are not.
   bool skip_tail = defer && p->guess_settled && c.lmfin.fast != nullptr;
@@ -249,7 +249,7 @@ int trf_gram_stage(blsq_trf_plan* p, int scale_mode, const int* mask, int* nfb, 
           })) return rc_;
     }
   } else if ((rc = trf_gate_tail(p, c, mask == nullptr))) return rc;
-  if (defer) {                              // the counters travel; the verdict is read by trf_resolve
+  if (defer) {                              // the counters travel; the verdict is read by resolve()
     verdict_arm(p, skip_tail, p->pend_dJ, p->pend_df, p->pend_ldJ, p->pend_scale_mode);
     *nfb = 0;
   } else {
@@ -346,10 +346,13 @@ int trf_factor_core(blsq_trf_plan* p, const double* dJ, const double* df, int ld
   return trf_finish(p);
 }
 
+}  // namespace blsq_host
+
 // The verdict of an optimistic factor call.  *redo = false: nothing was pending, or the guess held.
 // *redo = true: it did not — the state is now what the synchronous path would have left (fallback
 // stage, rank gate, SVD), and whatever was computed from the guessed state must be computed again.
-int trf_resolve(blsq_trf_plan* p, bool* redo) {
+int blsq_trf_plan::resolve(bool* redo) {
+  blsq_trf_plan* p = this;
   return verdict_resolve(
       p, redo, [&]() { return trf_gate_tail(p, trf_chol_args(p, nullptr)); },
       [&](int nfb) {
@@ -364,6 +367,7 @@ int trf_resolve(blsq_trf_plan* p, bool* redo) {
       });
 }
 
+namespace blsq_host {
 // Safeguarded Newton iteration of the SVD-free problems: lock-step rounds of
 // (factor of the system at the current alpha) + (two triangular solves + update).
 //
@@ -561,92 +565,31 @@ int trf_csne_verdict(blsq_trf_plan* p, int ncs, bool* redo) {
 
 extern "C" int blsq_trf_plan_create(blsq_ctx* ctx, int B, int m, int n, blsq_trf_plan** out) {
   if (!ctx) return -1;
-  if (!out) return ctx->bad(5, "out is NULL");
-  *out = nullptr;
-  if (B <= 0) return ctx->bad(2, "B must be positive");
-  if (m <= 0) return ctx->bad(3, "m must be positive");
-  if (n <= 0) return ctx->bad(4, "n must be positive");
-  HIPCHK(ctx, hipSetDevice(ctx->device));
+  if (out) *out = nullptr;
+  if (int rc_ = step_plan_args(ctx, B, m, n, out)) return rc_;
   blsq_trf_plan* p = new blsq_trf_plan();
-  p->ctx = ctx; p->B = B; p->m = m; p->n = n; p->m_total = m; p->nranks = 1;
+  p->m_total = m; p->nranks = 1;
   const int aug_rp = std::max(aug_rows(n), round_up(n + 1, 16));
-  int rc = p->tree.build(ctx, B, m, n, (size_t)B * aug_rp);
-  if (rc == 0) { p->ld = p->tree.NPAD; rc = trf_alloc_state(p); }
-  if (rc == 0) {
-    p->optimistic = ctx->opt.on(OPT_OPTIMISTIC);
-    hipError_t e = hipHostMalloc((void**)&p->pend_pin, 4 * sizeof(int), hipHostMallocCoherent);
-    if (e == hipSuccess) memset(p->pend_pin, 0, 4 * sizeof(int));
-    if (e != hipSuccess) rc = ctx->fail(e, "optimistic-verdict resources");
-  }
-  if (rc != 0) { blsq_trf_plan_destroy(p); return rc; }
-  HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-  ctx->trf_plans.push_back(p);
+  if (int rc_ = step_plan_init(ctx, p, B, m, n, (size_t)B * aug_rp, true, [p] { return trf_alloc_state(p); })) return rc_;
   *out = p;
   return 0;
 }
 
-extern "C" int blsq_trf_plan_destroy(blsq_trf_plan* p) {
-  if (!p) return -1;
-  hipStreamSynchronize(p->ctx->stream);
-  { auto& v = p->ctx->trf_plans; v.erase(std::remove(v.begin(), v.end(), p), v.end()); }
-  if (p->pend_pin) hipHostFree(p->pend_pin);
-  p->tree.release(); p->Rcomb.release(); p->Rstack.release();
-  p->X.release(); p->vecs.release(); p->scal2.release(); p->sweeps.release();
-  p->o_vec.release(); p->o_hits.release(); p->o_act.release(); p->o_scal.release();
-  p->o_info.release(); p->in_J.release(); p->in_f.release(); p->in_vec.release();
-  p->in_scal.release();
-  p->lm_sa.release(); p->lm_Xa.release(); p->lm_ints.release(); p->lm_sc.release();
-  p->csne.release();
-  p->lm_ph.release(); p->aug_colinfo.release(); p->aug_hmax.release(); p->aug_lam.release(); p->aug_ym.release(); p->aug_r1.release(); p->aug_open.release(); p->aug_mask.release();
-  delete p;
-  return 0;
-}
-
-static int trf_put_bounds(blsq_trf_plan* p, const double* x, const double* lb, const double* ub,
-                          const double* scale, hipMemcpyKind kind, bool zero_counts = false) {
-  blsq_ctx* ctx = p->ctx;
-  int rc;
-  if (kind == hipMemcpyDeviceToDevice) {                // one launch instead of four strided copies
-    // (in front of a Gram-stage factor call the prep launch of that stage does it and clears the two gate counters
-    //  of the call: trf_gram_stage)
-    p->pack_pend = zero_counts && p->tree.gram;
-    p->tree.fb_zeroed = p->pack_pend;
-    PackVecs pv{{x, lb, ub, scale, nullptr}, {p->st.x, p->st.lb, p->st.ub, p->st.scale, nullptr},
-                p->pack_pend ? p->tree.fb_count() : nullptr, 3};
-    if (p->pack_pend) { p->pack_pv = pv; return 0; }
-    hipError_t e = launch_pack_vecs(pv, p->n, p->ld, p->B, ctx->stream);
-    if (e != hipSuccess) return ctx->fail(e, "launch_pack_vecs");
-    return 0;
-  }
-  if ((rc = put_vec(ctx, p->st.x, p->ld, x, p->n, p->B, kind))) return rc;
-  if ((rc = put_vec(ctx, p->st.lb, p->ld, lb, p->n, p->B, kind))) return rc;
-  if ((rc = put_vec(ctx, p->st.ub, p->ld, ub, p->n, p->B, kind))) return rc;
-  if ((rc = put_vec(ctx, p->st.scale, p->ld, scale, p->n, p->B, kind))) return rc;
-  return 0;
-}
+extern "C" int blsq_trf_plan_destroy(blsq_trf_plan* p) { return step_plan_destroy(p); }
 
 extern "C" int blsq_trf_factor_dev(blsq_trf_plan* p, const double* dJ, const double* df,
                                    const double* dx, const double* dlb, const double* dub,
                                    double* dscale_io, int scale_mode) {
   if (!p) return -1;
   blsq_ctx* ctx = p->ctx;
-  if (!dJ) return ctx->bad(2, "J is NULL");
-  if (!df) return ctx->bad(3, "f is NULL");
-  if (!dx || !dlb || !dub) return ctx->bad(4, "x/lb/ub is NULL");
-  if (!dscale_io) return ctx->bad(7, "scale is NULL");
-  if (scale_mode < 0 || scale_mode > 2) return ctx->bad(8, "scale_mode");
+  if (int rc_ = factor_args(ctx, dJ, df, dx, dlb, dub, dscale_io, scale_mode)) return rc_;
   HIPCHK(ctx, hipSetDevice(ctx->device));
   int rc = verdict_published(p);               // (a verdict nobody read: its counters leave before they are cleared)
   if (rc) return rc;
-  if ((rc = trf_put_bounds(p, dx, dlb, dub, dscale_io, hipMemcpyDeviceToDevice, true))) return rc;
+  if ((rc = put_state(p, dx, dlb, dub, dscale_io, nullptr, hipMemcpyDeviceToDevice, true))) return rc;
   p->pend_scale_io = dscale_io;
   if ((rc = trf_factor_core(p, dJ, df, p->n, scale_mode, nullptr, true))) return rc;
-  if (scale_mode != BLSQ_SCALE_GIVEN) {
-    HIPCHK(ctx, hipMemcpy2DAsync(dscale_io, sizeof(double) * p->n, p->st.scale,
-                                 sizeof(double) * p->ld, sizeof(double) * p->n, p->B,
-                                 hipMemcpyDeviceToDevice, ctx->stream));
-  }
-  return 0;
+  return scale_back(p, dscale_io, scale_mode);
 }
 
 extern "C" int blsq_trf_step_dev(blsq_trf_plan* p, const double* dDelta, const double* dalpha_in,
@@ -669,7 +612,7 @@ extern "C" int blsq_trf_step_dev(blsq_trf_plan* p, const double* dDelta, const d
          }))) return rc;
     p->lm_counts_clean = true;              // (the step kernel leaves the round counters zeroed)
     bool redo = false;
-    if ((rc = trf_resolve(p, &redo))) return rc;
+    if ((rc = p->resolve(&redo))) return rc;
     if (!redo && ncs > 0 && (rc = trf_csne_verdict(p, ncs, &redo))) return rc;
     if (!redo) break;
   }
@@ -681,7 +624,7 @@ extern "C" int blsq_trf_fetch_factor(blsq_trf_plan* p, double* g, double* g_norm
   if (!p) return -1;
   blsq_ctx* ctx = p->ctx;
   int rc;
-  if ((rc = trf_resolve(p, nullptr))) return rc;
+  if ((rc = p->resolve(nullptr))) return rc;
   if ((rc = get_vec(ctx, g, p->n, p->st.g, p->ld, p->B))) return rc;
   if ((rc = get_vec(ctx, scale, p->n, p->st.scale, p->ld, p->B))) return rc;
   if ((rc = get_vec(ctx, sing, p->n, p->st.s, p->ld, p->B))) return rc;
@@ -694,29 +637,16 @@ extern "C" int blsq_trf_fetch_factor(blsq_trf_plan* p, double* g, double* g_norm
 
 extern "C" int blsq_trf_debug_fast(blsq_trf_plan* p, int32_t* fast) {
   if (!p) return -1;
-  blsq_ctx* ctx = p->ctx;
-  if (!fast) return ctx->bad(2, "fast is NULL");
-  { int rc_ = trf_resolve(p, nullptr); if (rc_) return rc_; }
-  HIPCHK(ctx, hipMemcpyAsync(fast, p->lm.fast, sizeof(int) * p->B, hipMemcpyDeviceToHost,
-                             ctx->stream));
-  return blsq_sync(ctx);
+  if (!fast) return p->ctx->bad(2, "fast is NULL");
+  return fetch_resolved(p, fast, p->lm.fast, sizeof(int));
 }
 
-extern "C" int blsq_trf_debug_cond(blsq_trf_plan* p, double* k2) {
-  if (!p) return -1;
-  blsq_ctx* ctx = p->ctx;
-  if (!k2) return ctx->bad(2, "k2 is NULL");
-  if (!p->tree.gram) { for (int b = 0; b < p->B; ++b) k2[b] = 0.0; return 0; }
-  { int rc_ = trf_resolve(p, nullptr); if (rc_) return rc_; }
-  HIPCHK(ctx, hipMemcpyAsync(k2, p->tree.gram_k2.p, sizeof(double) * p->B, hipMemcpyDeviceToHost,
-                             ctx->stream));
-  return blsq_sync(ctx);
-}
+extern "C" int blsq_trf_debug_cond(blsq_trf_plan* p, double* k2) { return debug_cond(p, k2); }
 
 extern "C" int blsq_trf_debug_csne(blsq_trf_plan* p, int32_t* on_tier, double* eta) {
   if (!p) return -1;
   blsq_ctx* ctx = p->ctx;
-  { int rc_ = trf_resolve(p, nullptr); if (rc_) return rc_; }
+  { int rc_ = p->resolve(nullptr); if (rc_) return rc_; }
   if (!p->csne.on) {
     for (int b = 0; b < p->B; ++b) { if (on_tier) on_tier[b] = 0; if (eta) eta[b] = 0.0; }
     return 0;
@@ -728,12 +658,8 @@ extern "C" int blsq_trf_debug_csne(blsq_trf_plan* p, int32_t* on_tier, double* e
 
 extern "C" int blsq_trf_debug_sweeps(blsq_trf_plan* p, int32_t* sweeps) {
   if (!p) return -1;
-  blsq_ctx* ctx = p->ctx;
-  if (!sweeps) return ctx->bad(2, "sweeps is NULL");
-  { int rc_ = trf_resolve(p, nullptr); if (rc_) return rc_; }
-  HIPCHK(ctx, hipMemcpyAsync(sweeps, p->sweeps.p, sizeof(int) * p->B, hipMemcpyDeviceToHost,
-                             ctx->stream));
-  return blsq_sync(ctx);
+  if (!sweeps) return p->ctx->bad(2, "sweeps is NULL");
+  return fetch_resolved(p, sweeps, p->sweeps.p, sizeof(int));
 }
 
 extern "C" int blsq_trf_fetch_step(blsq_trf_plan* p, double* alpha_out, double* step_h,
@@ -779,22 +705,11 @@ extern "C" int blsq_trf_factor(blsq_trf_plan* p, const double* J, const double* 
                                double* theta) {
   if (!p) return -1;
   blsq_ctx* ctx = p->ctx;
-  if (!J) return ctx->bad(2, "J is NULL");
-  if (!f) return ctx->bad(3, "f is NULL");
-  if (!x || !lb || !ub) return ctx->bad(4, "x/lb/ub is NULL");
-  if (!scale_io) return ctx->bad(7, "scale is NULL");
-  if (scale_mode < 0 || scale_mode > 2) return ctx->bad(8, "scale_mode");
+  if (int rc_ = factor_args(ctx, J, f, x, lb, ub, scale_io, scale_mode)) return rc_;
   HIPCHK(ctx, hipSetDevice(ctx->device));
-  const size_t jb = sizeof(double) * (size_t)p->B * p->m * p->n;
-  const size_t fb = sizeof(double) * (size_t)p->B * p->m;
-  if (!p->in_J.p || !p->in_f.p) {       // lazily, and again if an earlier attempt failed half way
-    hipError_t e = p->in_J.p ? hipSuccess : p->in_J.alloc(jb);
-    if (e != hipSuccess) return ctx->fail(e, "hipMalloc(J staging)");
-    e = p->in_f.p ? hipSuccess : p->in_f.alloc(fb);
-    if (e != hipSuccess) return ctx->fail(e, "hipMalloc(f staging)");
-  }
-  int rc = trf_put_bounds(p, x, lb, ub, scale_io, hipMemcpyHostToDevice);
+  int rc = stage_alloc(p);
   if (rc) return rc;
+  if ((rc = put_state(p, x, lb, ub, scale_io, nullptr, hipMemcpyHostToDevice))) return rc;
   // [J f] crosses PCIe in sub-batches of problems on a copy stream; the Gram of sub-batch k runs while sub-batch
   // k + 1 is in flight — for caller buffers in page-locked memory (blsq_host_alloc), which are DMA'd straight.
   // BLSQ_H2D_PIPE = 0 / 1: never / always (pageable memory too).
@@ -834,10 +749,7 @@ extern "C" int blsq_trf_factor(blsq_trf_plan* p, const double* J, const double* 
       }
     }
   }
-  if (!piped) {
-    HIPCHK(ctx, hipMemcpyAsync(p->in_J.p, J, jb, hipMemcpyHostToDevice, ctx->stream));
-    HIPCHK(ctx, hipMemcpyAsync(p->in_f.p, f, fb, hipMemcpyHostToDevice, ctx->stream));
-  }
+  if (!piped && (rc = stage_upload(p, J, f))) return rc;
   if ((rc = trf_factor_core(p, p->in_J.as<double>(), p->in_f.as<double>(), p->n, scale_mode, nullptr, false, piped)))
     return rc;
   return blsq_trf_fetch_factor(p, g, g_norm, theta,
@@ -877,37 +789,25 @@ extern "C" int blsq_tsqr_plan_create(blsq_ctx* ctx, int m_local, long long m_tot
   if (m_total < m_local) return ctx->bad(3, "m_total must be >= m_local");
   if (n <= 0) return ctx->bad(4, "n must be positive");
   if (nranks <= 0) return ctx->bad(5, "nranks must be positive");
-  HIPCHK(ctx, hipSetDevice(ctx->device));
+  if (nranks > 1 && !merge_fits(n)) return ctx->bad(4, "TSQR needs n <= 512");
   blsq_trf_plan* p = new blsq_trf_plan();
-  p->ctx = ctx; p->B = 1; p->m = m_local; p->n = n; p->nranks = nranks;
+  p->nranks = nranks;
   // the GLOBAL row count enters the reference's rank test eps * m * s[0] (trust_region.py:109):
   // it must be the same number on every rank, whatever the sizes of the row blocks
   p->m_total = m_total > 2147483647LL ? 2147483647 : (int)m_total;
   const int NPAD = round_up(n + 1, 16);
-  if (nranks > 1 && !merge_fits(n)) {
-    delete p;
-    return ctx->bad(4, "TSQR needs n <= 512");
-  }
   const int aug_rp = std::max(aug_rows(n), NPAD);
   // scratch must also cover the combine merges: nranks triangles, G per workgroup
   const int G = merge_group(n);
   const size_t comb_rows = (size_t)((nranks + G - 1) / G) * (size_t)(G * NPAD);
-  int rc = p->tree.build(ctx, 1, m_local, n, std::max((size_t)aug_rp, comb_rows));
-  if (rc == 0 && p->tree.gram) p->tree.k2_max = gram_k2_max(m_total, ctx->opt.d(OPT_GRAM_K2_MAX));   // (the Gram sums over ALL ranks' rows)
-  if (rc == 0) { p->ld = p->tree.NPAD; rc = trf_alloc_state(p); }
-  if (rc == 0) {
-    // two ping-pong levels for the combine tree
-    hipError_t e = p->Rcomb.alloc(sizeof(double) * 2 * (size_t)((nranks + G - 1) / G + 1) *
-                                  NPAD * NPAD);
-    if (e != hipSuccess) rc = ctx->fail(e, "hipMalloc(Rcomb)");
-  }
-  if (rc == 0) {
-    hipError_t e = p->Rstack.alloc(sizeof(double) * (size_t)nranks * NPAD * NPAD);
-    if (e != hipSuccess) rc = ctx->fail(e, "hipMalloc(Rstack)");
-  }
-  if (rc != 0) { blsq_trf_plan_destroy(p); return rc; }
-  HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-  ctx->trf_plans.push_back(p);
+  // (no optimistic verdicts: blsq_tsqr_factor_dev reads its gate synchronously)
+  if (int rc_ = step_plan_init(ctx, p, 1, m_local, n, std::max((size_t)aug_rp, comb_rows), false, [&] {
+        if (p->tree.gram) p->tree.k2_max = gram_k2_max(m_total, ctx->opt.d(OPT_GRAM_K2_MAX));   // (the Gram sums over ALL ranks' rows)
+        if (int rc = trf_alloc_state(p)) return rc;
+        // Rcomb: two ping-pong levels for the combine tree
+        return alloc_all(ctx, {{&p->Rcomb, sizeof(double) * 2 * (size_t)((nranks + G - 1) / G + 1) * NPAD * NPAD, "hipMalloc(Rcomb)"},
+                               {&p->Rstack, sizeof(double) * (size_t)nranks * NPAD * NPAD, "hipMalloc(Rstack)"}});
+      })) return rc_;
   *out = p;
   return 0;
 }
@@ -974,7 +874,7 @@ extern "C" int blsq_tsqr_combine_dev(blsq_trf_plan* p, const double* dtri_stack,
   if (!dscale_io) return ctx->bad(6, "scale is NULL");
   if (scale_mode < 0 || scale_mode > 2) return ctx->bad(7, "scale_mode");
   HIPCHK(ctx, hipSetDevice(ctx->device));
-  int rc = trf_put_bounds(p, dx, dlb, dub, dscale_io, hipMemcpyDeviceToDevice);
+  int rc = put_state(p, dx, dlb, dub, dscale_io, nullptr, hipMemcpyDeviceToDevice);
   if (rc) return rc;
   return tsqr_merge_and_finish(p, dtri_stack, scale_mode, dscale_io);
 }
@@ -1001,7 +901,7 @@ extern "C" int blsq_tsqr_factor_dev(blsq_trf_plan* p, const double* dJ_block, co
   HIPCHK(ctx, hipSetDevice(ctx->device));
   // (zero_counts: with the normal-equations front end the prep launch of the Gram stage packs the vectors and clears the
   //  gate counters — no pack launch, no fill)
-  int rc = trf_put_bounds(p, dx, dlb, dub, dscale_io, hipMemcpyDeviceToDevice, true);
+  int rc = put_state(p, dx, dlb, dub, dscale_io, nullptr, hipMemcpyDeviceToDevice, true);
   if (rc) return rc;
   auto put_scale = [&]() -> int {
     if (scale_mode != BLSQ_SCALE_GIVEN)
