@@ -13,6 +13,7 @@ from ._frontend import least_squares  # noqa: F401
 from ._batch import least_squares_batch  # noqa: F401
 from ._outer import OuterDriver  # noqa: F401
 from ._cov import covariance  # noqa: F401
+from ._leverage import leverage, prediction_variance, influence  # noqa: F401
 from ._curve_fit import curve_fit, curve_fit_batch  # noqa: F401
 from ._hostmath import (active_mask as find_active_constraints,  # noqa: F401
                         prepare_bounds, cl_optimality as CL_optimality,
@@ -20,4 +21,5 @@ from ._hostmath import (active_mask as find_active_constraints,  # noqa: F401
 
 __all__ = ['dogbox', 'trf', 'find_active_constraints', 'CL_optimality', 'prepare_bounds',
            'make_strictly_feasible', 'least_squares', 'least_squares_batch', 'TrfStepSolver', 'DogboxStepSolver',
-           'OuterDriver', 'covariance', 'curve_fit', 'curve_fit_batch']
+           'OuterDriver', 'covariance', 'curve_fit', 'curve_fit_batch', 'leverage', 'prediction_variance',
+           'influence']

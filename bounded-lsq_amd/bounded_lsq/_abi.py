@@ -108,6 +108,9 @@ SIGNATURES = {
     "blsq_cov_pinv_dev": (C.c_int, [vp] + [vp] * 8),
     "blsq_cov_pinv": (C.c_int, [vp] + [vp] * 8),
     "blsq_outer_covariance_pinv": (C.c_int, [vp, C.c_int, C.c_int, vp, vp, vp, vp, vp]),
+    "blsq_cov_rows_dev": (C.c_int, [vp, C.c_int, vp, vp, vp]),
+    "blsq_cov_rows": (C.c_int, [vp, C.c_int, vp, vp, vp]),
+    "blsq_outer_leverage": (C.c_int, [vp, vp, vp]),
 }
 
 _lib = None

@@ -24,7 +24,7 @@ from ._hip_step import (TrfStepSolver, DogboxStepSolver, SCALE_GIVEN, SCALE_JAC_
                         SCALE_JAC_UPDATE, raise_batch_status)
 from ._hostmath import (shift_into_interior, active_mask, cl_vector, check_loss, loss_rho, loss_cost,
                         loss_scale)
-from ._cov import (check_covariance, attach as _attach_covariance, fill_results as _fill_covariance, is_pinv as _is_pinv,
+from ._cov import (check_covariance, check_leverage, fill_leverage as _fill_leverage, attach as _attach_covariance, fill_results as _fill_covariance, is_pinv as _is_pinv,
                    is_free as _is_free)
 
 
@@ -42,7 +42,7 @@ def _bounds_2d(bounds, B, n):
 def least_squares_batch(fun, x0, jac, bounds=(-np.inf, np.inf), method='trf',
                         ftol=EPS ** 0.5, xtol=EPS ** 0.5, gtol=EPS ** 0.5, max_nfev=None,
                         scaling=1.0, diff_step=None, args=(), kwargs=None, ctx=None, driver='host',
-                        loss='linear', f_scale=1.0, covariance=False, _variance_scale=False):
+                        loss='linear', f_scale=1.0, covariance=False, _variance_scale=False, leverage=False):
     """Solve B bound-constrained least-squares problems of identical shape.
 
     fun : callable, ``fun(X) -> (B, m)`` residuals for ``X`` (B, n)
@@ -60,12 +60,15 @@ def least_squares_batch(fun, x0, jac, bounds=(-np.inf, np.inf), method='trf',
              B n^2 + 2 B numbers leave the GPU).  'pinv' / 'free-pinv': the pseudo-inverse covariance of any rank
              (``x_covariance_rank``; ``x_covariance_rcond`` is then s_min / s_max, not the 1-norm figure);
              ``_variance_scale`` (``curve_fit_batch``'s): times obj_value / (m - n), applied on the GPU.
+    leverage : True (needs a covariance mode) adds ``leverage`` (m,) to every result, as ``least_squares``: from the
+             same plan call (driver='device': through the resident J, B m more numbers leave the GPU).
     Returns a list of B ``OptimizeResult`` (fields as ``least_squares``).
     """
     if method not in ('trf', 'dogbox'):
         raise ValueError("`method` must be 'trf' or 'dogbox'.")
     check_loss(loss, f_scale)
     covariance = check_covariance(covariance)
+    leverage = check_leverage(leverage, covariance)
     if callable(loss) and driver == 'device':
         raise ValueError("a callable `loss` runs on the host: use driver='host'.")
     X0 = np.array(x0, dtype=float)
@@ -134,7 +137,7 @@ def least_squares_batch(fun, x0, jac, bounds=(-np.inf, np.inf), method='trf',
     if driver == 'device':
         try:
             return _device_batch(fun, jac, X0, lb, ub, trf, use_jac, scaling, ftol, xtol, gtol,
-                                 max_nfev, ctx, loss if robust else None, fsc, covariance, _variance_scale)
+                                 max_nfev, ctx, loss if robust else None, fsc, covariance, _variance_scale, leverage)
         finally:
             _release_fd()
 
@@ -312,7 +315,8 @@ def least_squares_batch(fun, x0, jac, bounds=(-np.inf, np.inf), method='trf',
             r.success = r.status > 0
             results.append(r)
         if covariance:
-            _attach_covariance(results, covariance, ctx=solver.ctx, variance_scale=_variance_scale and m > n)
+            _attach_covariance(results, covariance, ctx=solver.ctx, variance_scale=_variance_scale and m > n,
+                               leverage=leverage)
         return results
     finally:
         solver.close()
@@ -320,7 +324,7 @@ def least_squares_batch(fun, x0, jac, bounds=(-np.inf, np.inf), method='trf',
 
 
 def _device_batch(fun, jac, X0, lb, ub, trf, use_jac, scaling, ftol, xtol, gtol, max_nfev, ctx,
-                  loss=None, f_scale=None, covariance=False, variance_scale=False):
+                  loss=None, f_scale=None, covariance=False, variance_scale=False, leverage=False):
     """`least_squares_batch` on the device-resident outer driver (same results, same counts).  `loss`: a
     loss name other than 'linear' (None: sum f^2), applied on the device (blsq_outer_set_loss)."""
     from ._outer import OuterDriver
@@ -362,6 +366,7 @@ def _device_batch(fun, jac, X0, lb, ub, trf, use_jac, scaling, ftol, xtol, gtol,
         R = drv.run_host(fun_cached, jac_checked)
         cov_out = drv.covariance(free_only=_is_free(covariance), pinv=_is_pinv(covariance),
                                  variance_scale=variance_scale and m > n) if covariance else None
+        lev_out = drv.leverage() if leverage else None
         Jfin = drv._down(drv.d_J, (B, m, n))
     finally:
         drv.close()
@@ -378,4 +383,6 @@ def _device_batch(fun, jac, X0, lb, ub, trf, use_jac, scaling, ftol, xtol, gtol,
         results.append(r)
     if covariance:
         _fill_covariance(results, covariance, *cov_out)
+    if leverage:
+        _fill_leverage(results, lev_out[0])
     return results

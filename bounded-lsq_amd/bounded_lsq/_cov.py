@@ -49,22 +49,11 @@ def is_free(mode):
     return mode in ('free', 'free-pinv')
 
 
-def covariance(J, active_mask=None, ctx=None, pinv=False, scale=None):
-    """Covariance of one (m, n) Jacobian or of a batch (B, m, n).
-
-    active_mask : None (all variables), or integers of shape (n,) / (B, n): non-zero marks a variable on a bound.
-    Returns ``(cov, rcond, status)``: cov (n, n) or (B, n, n) — NaN everywhere for a singular problem —, rcond and
-    status (0 regular, 1 singular) scalars or (B,).
-
-    pinv=True : the pseudo-inverse covariance (module docstring); returns ``(cov, rank, rcond, kept_rcond, status)``
-    with rcond = s_min / s_max, kept_rcond = (smallest kept singular value) / s_max, status 0, 1 (J not finite: cov
-    NaN) or 2 (SVD not converged: cov NaN).  scale (pinv only): None, a scalar or (B,): cov[b] is multiplied by it
-    on the GPU (the residual variance ``obj_value / (m - n)`` of ``curve_fit``'s ``absolute_sigma=False``).
-    """
+def checked_inputs(J, active_mask, pinv, scale):
+    """The argument checks of `covariance` (ValueError, before any GPU is touched) -> (Jb (B, m, n) contiguous,
+    act (B, n) int64 or None, sc (B,) or None, single)."""
     if not isinstance(pinv, (bool, np.bool_)):
         raise ValueError("`pinv` must be False or True.")
-    if scale is not None and not pinv:
-        raise ValueError("`scale` needs pinv=True.")
     J = np.asarray(J, dtype=np.float64)
     if J.ndim not in (2, 3):
         raise ValueError("`J` must have shape (m, n) or (B, m, n).")
@@ -87,6 +76,21 @@ def covariance(J, active_mask=None, ctx=None, pinv=False, scale=None):
             sc = np.ascontiguousarray(np.broadcast_to(np.asarray(scale, dtype=np.float64), (B,)))
         except ValueError:
             raise ValueError("`scale` must be a scalar or have shape (B,).")
+    return Jb, act, sc, single
+
+
+def plan_rows(ctx, h, B, rows, A=None, scale=None):
+    """blsq_cov_rows on the plan `h` after its covariance call: (B, rows) row forms of `A` (B, rows, n; None: the J that
+    call staged) through the factor it left, times `scale` (B,) or None."""
+    out = np.empty((B, rows))
+    ctx.check(ctx.lib.blsq_cov_rows(h, int(rows), ptr(A), ptr(scale), ptr(out)), "blsq_cov_rows")
+    return out
+
+
+def plan_call(Jb, act, sc, pinv, ctx=None, after=None):
+    """One plan, one H2D of `Jb`, blsq_cov or blsq_cov_pinv -> (the call's batched outputs, after(ctx, h) or None):
+    `after` runs on the live plan, whose factor blsq_cov_rows reads."""
+    B, m, n = Jb.shape
     if ctx is None:
         from ._hip_step import default_context
         ctx = default_context()
@@ -101,14 +105,40 @@ def covariance(J, active_mask=None, ctx=None, pinv=False, scale=None):
             kept = np.empty(B)
             ctx.check(ctx.lib.blsq_cov_pinv(h, ptr(Jb), ptr(act), ptr(sc), ptr(cov), ptr(rank), ptr(rcond), ptr(kept),
                                             ptr(status)), "blsq_cov_pinv")
+            out = (cov, rank, rcond, kept, status)
         else:
             ctx.check(ctx.lib.blsq_cov(h, ptr(Jb), ptr(act), ptr(cov), ptr(rcond), ptr(status)), "blsq_cov")
+            out = (cov, rcond, status)
+        extra = after(ctx, h) if after is not None else None
     finally:
         ctx.lib.blsq_cov_plan_destroy(h)
+    return out, extra
+
+
+def covariance(J, active_mask=None, ctx=None, pinv=False, scale=None):
+    """Covariance of one (m, n) Jacobian or of a batch (B, m, n).
+
+    active_mask : None (all variables), or integers of shape (n,) / (B, n): non-zero marks a variable on a bound.
+    Returns ``(cov, rcond, status)``: cov (n, n) or (B, n, n) — NaN everywhere for a singular problem —, rcond and
+    status (0 regular, 1 singular) scalars or (B,).
+
+    pinv=True : the pseudo-inverse covariance (module docstring); returns ``(cov, rank, rcond, kept_rcond, status)``
+    with rcond = s_min / s_max, kept_rcond = (smallest kept singular value) / s_max, status 0, 1 (J not finite: cov
+    NaN) or 2 (SVD not converged: cov NaN).  scale (pinv only): None, a scalar or (B,): cov[b] is multiplied by it
+    on the GPU (the residual variance ``obj_value / (m - n)`` of ``curve_fit``'s ``absolute_sigma=False``).
+    """
+    if not isinstance(pinv, (bool, np.bool_)):
+        raise ValueError("`pinv` must be False or True.")
+    if scale is not None and not pinv:
+        raise ValueError("`scale` needs pinv=True.")
+    Jb, act, sc, single = checked_inputs(J, active_mask, pinv, scale)
+    out, _ = plan_call(Jb, act, sc, bool(pinv), ctx)
     if pinv:
+        cov, rank, rcond, kept, status = out
         if single:
             return cov[0], int(rank[0]), float(rcond[0]), float(kept[0]), int(status[0])
         return cov, rank, rcond, kept, status
+    cov, rcond, status = out
     if single:
         return cov[0], float(rcond[0]), int(status[0])
     return cov, rcond, status
@@ -135,13 +165,33 @@ def variance_scales(results):
     return np.array([r.obj_value / (r.jac.shape[0] - r.jac.shape[1]) for r in results])
 
 
-def attach(results, mode, ctx=None, variance_scale=False):
+def fill_leverage(results, h):
+    """``leverage`` of each result from the (B, m) leverages of the same plan call: None wherever x_covariance is."""
+    for b, r in enumerate(results):
+        r.leverage = None if r.x_covariance is None else h[b].copy()
+    return results
+
+
+def check_leverage(leverage, covariance):
+    """-> bool; ValueError for a non-boolean, or for leverage=True without a covariance mode."""
+    if not isinstance(leverage, (bool, np.bool_)):
+        raise ValueError("`leverage` must be False or True.")
+    if leverage and not covariance:
+        raise ValueError("`leverage=True` needs a `covariance` mode: the leverages come from its factor.")
+    return bool(leverage)
+
+
+def attach(results, mode, ctx=None, variance_scale=False, leverage=False):
     """One batched covariance call on the stacked final Jacobians of `results` (`mode`: as check_covariance returns
-    it).  variance_scale (pinv modes): multiply problem b by obj_value / (m - n) on the GPU."""
+    it).  variance_scale (pinv modes): multiply problem b by obj_value / (m - n) on the GPU.  leverage: the leverages
+    of the rows of each Jacobian from the same plan call (blsq_cov_rows on the staged J; never scaled)."""
     J = np.stack([r.jac for r in results])
     act = np.stack([np.asarray(r.active_mask) for r in results]) if is_free(mode) else None
-    if is_pinv(mode):
-        out = covariance(J, act, ctx=ctx, pinv=True, scale=variance_scales(results) if variance_scale else None)
-    else:
-        out = covariance(J, act, ctx=ctx)
-    return fill_results(results, mode, *out)
+    scale = variance_scales(results) if (variance_scale and is_pinv(mode)) else None
+    Jb, act, sc, _ = checked_inputs(J, act, is_pinv(mode), scale)
+    after = (lambda c, h: plan_rows(c, h, Jb.shape[0], Jb.shape[1])) if leverage else None
+    out, lev = plan_call(Jb, act, sc, is_pinv(mode), ctx, after)
+    fill_results(results, mode, *out)
+    if leverage:
+        fill_leverage(results, lev)
+    return results

@@ -100,7 +100,8 @@ def curve_fit(f, xdata, ydata, p0=None, sigma=None, absolute_sigma=False, check_
     ``pcov`` is the Moore-Penrose covariance of the final Jacobian over its singular values above
     ``eps * max(m, n) * s_max``, computed on the GPU; unless `absolute_sigma` it is multiplied by
     ``obj_value / (m - n)``, and filled with inf under an ``OptimizeWarning`` where m <= n.
-    ``full_output=True`` returns ``(popt, pcov, infodict, mesg, ier)`` with infodict keys ``nfev`` and ``fvec``.
+    ``full_output=True`` returns ``(popt, pcov, infodict, mesg, ier)`` with infodict keys ``nfev`` and ``fvec``, and
+    ``leverage`` (``least_squares``'s, of the transformed Jacobian) when ``leverage=True`` is among the keywords.
 
     Two deliberate differences from scipy:
       * ``method=None`` always means 'trf' (scipy chooses 'lm' for an unbounded problem); ``method='lm'`` raises
@@ -162,6 +163,8 @@ def curve_fit(f, xdata, ydata, p0=None, sigma=None, absolute_sigma=False, check_
         raise RuntimeError("Optimal parameters not found: " + res.message)
 
     infodict = dict(nfev=res.nfev, fvec=res.fun)
+    if 'leverage' in res:
+        infodict['leverage'] = res.leverage
     ier, errmsg = res.status, res.message
     ysize = len(res.fun)
     cost = res.obj_value                     # sum f^2, or the robust-loss objective (scipy: 2 * res.cost)

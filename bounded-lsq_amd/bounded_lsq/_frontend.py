@@ -12,7 +12,7 @@ from scipy.optimize._numdiff import approx_derivative
 
 from ._drivers import trf, dogbox
 from ._hostmath import in_bounds, prepare_bounds, check_loss
-from ._cov import check_covariance, attach as _attach_covariance
+from ._cov import check_covariance, check_leverage, attach as _attach_covariance
 
 EPS = np.finfo(float).eps
 
@@ -56,7 +56,7 @@ def _checked_scaling(scaling, x0):
 def least_squares(fun, x0, jac='2-point', bounds=(-np.inf, np.inf), method='trf',
                   ftol=EPS ** 0.5, xtol=EPS ** 0.5, gtol=EPS ** 0.5, max_nfev=None,
                   scaling=1.0, diff_step=None, args=(), kwargs={}, options={}, loss='linear', f_scale=1.0,
-                  covariance=False):
+                  covariance=False, leverage=False):
     """Minimise ``sum(fun(x)**2)`` subject to ``lb <= x <= ub``.
 
     Parameters and the returned ``OptimizeResult`` fields (x, fun, jac,
@@ -80,11 +80,16 @@ def least_squares(fun, x0, jac='2-point', bounds=(-np.inf, np.inf), method='trf'
     ``eps * max(m, n) * s_max`` (``curve_fit``'s ``pcov`` for any rank; ``bounded_lsq.curve_fit`` is built on it):
     ``x_covariance_rank`` is the number kept, ``x_covariance_rcond`` is then ``s_min / s_max`` — NOT the 1-norm
     figure of True / 'free' — and ``x_covariance`` is None only where J is not finite.
+
+    ``leverage=True`` (needs a ``covariance`` mode: ValueError otherwise) adds ``leverage``, the (m,) diagonal of
+    ``J C J^T`` with C that covariance (unscaled), from the same GPU plan call (``bounded_lsq.leverage``); None
+    wherever ``x_covariance`` is None.  With a robust loss it is the leverage of the scaled Jacobian ``result.jac``.
     """
     if method not in ['trf', 'dogbox', 'lm']:
         raise ValueError("`method` must be 'trf', 'dogbox' or 'lm'.")
     check_loss(loss, f_scale)
     covariance = check_covariance(covariance)
+    leverage = check_leverage(leverage, covariance)
     f_scale = float(f_scale)
     if method == 'lm':
         raise NotImplementedError(
@@ -139,5 +144,5 @@ def least_squares(fun, x0, jac='2-point', bounds=(-np.inf, np.inf), method='trf'
     result.message = TERMINATION_MESSAGES[result.status]
     result.success = result.status > 0
     if covariance:
-        _attach_covariance([result], covariance, ctx=options.get("ctx"))
+        _attach_covariance([result], covariance, ctx=options.get("ctx"), leverage=leverage)
     return result

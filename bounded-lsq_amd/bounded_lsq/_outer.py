@@ -137,6 +137,16 @@ class OuterDriver:
                                                           ptr(status)), "blsq_outer_covariance")
         return cov, rcond, status
 
+    def leverage(self):
+        """Leverages of the rows of the resident J through the factor of the last ``covariance()`` call
+        (blsq_outer_leverage): ``(h (B, m), status (B,))``, h NaN where that call's status is non-zero; never scaled.
+        Only B m + B numbers leave the GPU.  Raises if no covariance call has run since the last begin / propose /
+        judge: a stale factor is an error, nothing is recomputed silently."""
+        h = np.empty((self.B, self.m))
+        status = np.empty(self.B, dtype=np.int32)
+        self.ctx.check(self.ctx.lib.blsq_outer_leverage(self.h, ptr(h), ptr(status)), "blsq_outer_leverage")
+        return h, status
+
     # ---- helpers for host-side callbacks -----------------------------------------------
     def _up(self, dptr, arr, shape=None, what="callback"):
         arr = np.ascontiguousarray(arr, dtype=np.float64)

@@ -2,6 +2,8 @@
 //   tree (Householder TSQR of the plain J, or of J with its free columns first)  ->  cov_inverse  ->  cov_product
 //   pseudo-inverse route (7h):                                      the same tree  ->  Jacobi SVD of the triangle
 //                                                                   ->  cov_pinv_weights  ->  cov_pinv_product
+//   row forms (7i, blsq_cov_rows*): the factor either route has left in the plan  ->  cov_rows (pinv: the factor is
+//                                                                   refined by the first such call, cov_pinv_rowfactor)
 #include "blsq_host.h"
 
 extern "C" int blsq_cov_plan_create(blsq_ctx* ctx, int B, int m, int n, blsq_cov_plan** out) {
@@ -35,7 +37,8 @@ extern "C" int blsq_cov_plan_create(blsq_ctx* ctx, int B, int m, int n, blsq_cov
   if (rc == 0) {
     const size_t tri = sizeof(double) * (size_t)B * p->NPAD * p->NPAD;
     rc = alloc_all(ctx, {{&p->zf, sizeof(double) * (size_t)B * m, "hipMalloc(covariance rhs)"},
-                         {&p->X, tri, "hipMalloc(covariance inverse)"}});
+                         {&p->X, tri, "hipMalloc(covariance inverse)"},
+                         {&p->kept_status, sizeof(int) * (size_t)B, "hipMalloc(covariance status)"}});
   }
   if (rc == 0) {
     hipError_t e = hipMemsetAsync(p->zf.p, 0, p->zf.bytes, ctx->stream);
@@ -119,6 +122,18 @@ int cov_triangle(blsq_cov_plan* p, const double* dJ, const long long* dactive, i
 }
 }  // namespace
 
+namespace {
+// A covariance call has run to its end: what blsq_cov_rows* needs of it stays with the plan (the factor is where the
+// route left it; the caller's status buffer is copied, not kept)
+int cov_keep(blsq_cov_plan* p, blsq_cov_plan::Kept route, bool masked, const int* dstatus) {
+  blsq_ctx* ctx = p->ctx;
+  HIPCHK(ctx, hipMemcpyAsync(p->kept_status.p, dstatus, sizeof(int) * (size_t)p->B, hipMemcpyDeviceToDevice,
+                             ctx->stream));
+  p->kept = route; p->kept_masked = masked; p->kept_refined = false;
+  return 0;
+}
+}  // namespace
+
 namespace blsq_host {
 int cov_core(blsq_cov_plan* p, const double* dJ, const long long* dactive, int lda, double* dcov, double* drcond,
              int* dstatus) {
@@ -126,14 +141,38 @@ int cov_core(blsq_cov_plan* p, const double* dJ, const long long* dactive, int l
   const int B = p->B, m = p->m, n = p->n, NPAD = p->NPAD;
   const int* perm = nullptr;
   const int* nfree = nullptr;
+  p->kept = blsq_cov_plan::KEPT_NONE; p->kept_staged = false;   // (the slots are being overwritten)
   if (int rc_ = cov_triangle(p, dJ, dactive, lda, &perm, &nfree, false)) return rc_;
   if (int rc_ = ctx->run(K_COV_INVERSE, "launch_cov_inverse", [&] {
         return launch_cov_inverse(B, m, n, NPAD, p->Rfinal(), p->X.as<double>(), nfree, dcov, drcond, dstatus,
                                   ctx->stream);
       })) return rc_;
-  return ctx->run(K_COV_PRODUCT, "launch_cov_product", [&] {
-    return launch_cov_product(B, n, NPAD, p->X.as<double>(), nfree, perm, dstatus, dcov, ctx->stream);
-  });
+  if (int rc_ = ctx->run(K_COV_PRODUCT, "launch_cov_product", [&] {
+        return launch_cov_product(B, n, NPAD, p->X.as<double>(), nfree, perm, dstatus, dcov, ctx->stream);
+      })) return rc_;
+  return cov_keep(p, blsq_cov_plan::KEPT_REGULAR, dactive != nullptr, dstatus);
+}
+
+int cov_rows_core(blsq_cov_plan* p, int rows, const double* dA, const double* dscale, double* dout) {
+  blsq_ctx* ctx = p->ctx;
+  const bool pinv = p->kept == blsq_cov_plan::KEPT_PINV;
+  const int* perm = p->kept_masked ? p->perm.as<int>() : nullptr;
+  const int* nfree = p->kept_masked ? p->nfree.as<int>() : nullptr;
+  const bool refine = pinv && !p->kept_refined;      // the first row-form call after a pinv covariance call
+  if (refine && !p->rowgram.p)
+    if (int rc_ = alloc_all(ctx, {{&p->rowgram, p->X.bytes, "hipMalloc(covariance row Gram)"}})) return rc_;
+  if (int rc_ = ctx->run(K_COV_ROWS, "launch_cov_rows", [&] {
+        if (refine) {
+          const hipError_t e = launch_cov_pinv_rowfactor(p->B, p->n, p->NPAD, p->Rfinal(), p->pw.as<double>(), nfree,
+                                                         p->kept_status.as<int>(), p->rowgram.as<double>(),
+                                                         p->X.as<double>(), ctx->stream);
+          if (e != hipSuccess) return e;
+        }
+        return launch_cov_rows(p->B, rows, p->n, p->NPAD, pinv ? 1 : 0, dA, perm, nfree, p->X.as<double>(), nullptr,
+                               p->kept_status.as<int>(), dscale, dout, ctx->stream);
+      })) return rc_;
+  if (refine) p->kept_refined = true;
+  return 0;
 }
 
 // Jacobi sweeps granted to a covariance triangle (as the step plans' factor calls)
@@ -155,6 +194,7 @@ int cov_pinv_core(blsq_cov_plan* p, const double* dJ, const long long* dactive, 
   }
   const int* perm = nullptr;
   const int* nfree = nullptr;
+  p->kept = blsq_cov_plan::KEPT_NONE; p->kept_staged = false;
   if (int rc_ = cov_triangle(p, dJ, dactive, lda, &perm, &nfree, true)) return rc_;
   double* tri = const_cast<double*>(p->Rfinal());    // rotated in place: the next call rebuilds it
   JacobiArgs ja{};
@@ -168,10 +208,11 @@ int cov_pinv_core(blsq_cov_plan* p, const double* dJ, const long long* dactive, 
         return launch_cov_pinv_weights(B, m, n, NPAD, tri, p->js.as<double>(), p->jsweeps.as<int>(), COV_MAX_SWEEPS,
                                        nfree, p->pw.as<double>(), dcov, drank, drcond, dkept, dstatus, ctx->stream);
       })) return rc_;
-  return ctx->run(K_COV_PINV_PRODUCT, "launch_cov_pinv_product", [&] {
-    return launch_cov_pinv_product(B, n, NPAD, tri, p->pw.as<double>(), nfree, perm, dstatus, dscale, dcov,
-                                   ctx->stream);
-  });
+  if (int rc_ = ctx->run(K_COV_PINV_PRODUCT, "launch_cov_pinv_product", [&] {
+        return launch_cov_pinv_product(B, n, NPAD, tri, p->pw.as<double>(), nfree, perm, dstatus, dscale, dcov,
+                                       ctx->stream);
+      })) return rc_;
+  return cov_keep(p, blsq_cov_plan::KEPT_PINV, dactive != nullptr, dstatus);
 }
 }  // namespace blsq_host
 
@@ -231,7 +272,11 @@ extern "C" int blsq_cov(blsq_cov_plan* p, const double* J, const int64_t* active
   if (!status) return ctx->bad(6, "status is NULL");
   HIPCHK(ctx, hipSetDevice(ctx->device));
   if (int rc_ = cov_stage_inputs(p, J, active, nullptr)) return rc_;
-  return cov_to_host(p, p->in_J.as<double>(), active ? p->in_act.as<long long>() : nullptr, p->n, cov, rcond, status);
+  if (int rc_ = cov_to_host(p, p->in_J.as<double>(), active ? p->in_act.as<long long>() : nullptr, p->n, cov, rcond,
+                            status))
+    return rc_;
+  p->kept_staged = true;                              // (in_J holds this call's J: blsq_cov_rows with A = NULL)
+  return 0;
 }
 
 namespace {
@@ -278,8 +323,50 @@ extern "C" int blsq_cov_pinv(blsq_cov_plan* p, const double* J, const int64_t* a
   if (int rc_ = cov_pinv_args(ctx, J, cov, rank, rcond, kept_rcond, status)) return rc_;
   HIPCHK(ctx, hipSetDevice(ctx->device));
   if (int rc_ = cov_stage_inputs(p, J, active, scale)) return rc_;
-  return cov_pinv_to_host(p, p->in_J.as<double>(), active ? p->in_act.as<long long>() : nullptr, p->n,
-                          scale ? p->in_scale.as<double>() : nullptr, cov, rank, rcond, kept_rcond, status);
+  if (int rc_ = cov_pinv_to_host(p, p->in_J.as<double>(), active ? p->in_act.as<long long>() : nullptr, p->n,
+                                 scale ? p->in_scale.as<double>() : nullptr, cov, rank, rcond, kept_rcond, status))
+    return rc_;
+  p->kept_staged = true;
+  return 0;
+}
+
+// ---- row forms through the kept factor ------------------------------------------------------------
+extern "C" int blsq_cov_rows_dev(blsq_cov_plan* p, int rows, const double* dA, const double* dscale, double* dout) {
+  if (!p) return -1;
+  blsq_ctx* ctx = p->ctx;
+  if (p->kept == blsq_cov_plan::KEPT_NONE) return ctx->bad(1, "no covariance factor yet (call blsq_cov* first)");
+  if (rows <= 0) return ctx->bad(2, "rows must be positive");
+  if (!dA) return ctx->bad(3, "A is NULL");
+  if (!dout) return ctx->bad(5, "out is NULL");
+  HIPCHK(ctx, hipSetDevice(ctx->device));
+  return cov_rows_core(p, rows, dA, dscale, dout);
+}
+
+extern "C" int blsq_cov_rows(blsq_cov_plan* p, int rows, const double* A, const double* scale, double* out) {
+  if (!p) return -1;
+  blsq_ctx* ctx = p->ctx;
+  if (p->kept == blsq_cov_plan::KEPT_NONE) return ctx->bad(1, "no covariance factor yet (call blsq_cov* first)");
+  if (rows <= 0) return ctx->bad(2, "rows must be positive");
+  if (!A && !p->kept_staged) return ctx->bad(3, 
+                         "A is NULL and the last covariance call staged no J (blsq_cov / blsq_cov_pinv do)");
+  if (!A && rows != p->m) return ctx->bad(2, "A is NULL: rows must be the plan's m");
+  if (!out) return ctx->bad(5, "out is NULL");
+  HIPCHK(ctx, hipSetDevice(ctx->device));
+  const size_t B = (size_t)p->B, nA = sizeof(double) * B * rows * p->n, nO = sizeof(double) * B * rows;
+  if (p->r_out.bytes < nO)                            // staging grows on demand
+    if (int rc_ = alloc_all(ctx, {{&p->r_out, nO, "hipMalloc(row form output)"}})) return rc_;
+  if (A && p->r_A.bytes < nA)
+    if (int rc_ = alloc_all(ctx, {{&p->r_A, nA, "hipMalloc(row form input)"}})) return rc_;
+  if (scale && !p->r_scale.p)
+    if (int rc_ = alloc_all(ctx, {{&p->r_scale, sizeof(double) * B, "hipMalloc(row form scale)"}})) return rc_;
+  if (A) HIPCHK(ctx, hipMemcpyAsync(p->r_A.p, A, nA, hipMemcpyHostToDevice, ctx->stream));
+  if (scale) HIPCHK(ctx, hipMemcpyAsync(p->r_scale.p, scale, sizeof(double) * B, hipMemcpyHostToDevice, ctx->stream));
+  if (int rc_ = cov_rows_core(p, rows, A ? p->r_A.as<double>() : p->in_J.as<double>(),
+                              scale ? p->r_scale.as<double>() : nullptr, p->r_out.as<double>()))
+    return rc_;
+  HIPCHK(ctx, hipMemcpyAsync(out, p->r_out.p, nO, hipMemcpyDeviceToHost, ctx->stream));
+  HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+  return 0;
 }
 
 namespace blsq_host {

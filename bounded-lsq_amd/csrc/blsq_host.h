@@ -31,11 +31,11 @@ constexpr int RMAX = QR_MAX_TILES * 16;   // rows a workgroup can stage (qr_pane
 
 enum Slot { K_QR_LEAF = 0, K_QR_MERGE, K_PREP, K_QR_AUG, K_JACOBI, K_STEP, K_LM_GATE, K_LM_QR, K_LM_SOLVE,
             K_GRAM, K_GRAM_CHOL, K_GRAM_GATE, K_AUG_CHOL, K_LM_CHOL, K_CQR2_APPLY, K_CQR2_COMBINE, K_CSNE_PASS,
-            K_CSNE_FIX, K_COV_PINV_WEIGHTS, K_COV_PINV_PRODUCT, K_COV_GATHER, K_COV_INVERSE, K_COV_PRODUCT, K_LOSS_COST, K_LOSS_SCALE, K_NSLOT };
+            K_CSNE_FIX, K_COV_ROWS, K_COV_PINV_WEIGHTS, K_COV_PINV_PRODUCT, K_COV_GATHER, K_COV_INVERSE, K_COV_PRODUCT, K_LOSS_COST, K_LOSS_SCALE, K_NSLOT };
 static const char* const kSlotNames[K_NSLOT] = {"qr_leaf", "qr_merge", "prep", "qr_aug", "jacobi_svd", "step",
                                    "lm_gate", "lm_qr", "lm_solve", "gram", "gram_chol", "gram_gate",
                                    "aug_chol", "lm_chol", "cqr2_apply", "cqr2_combine", "csne_pass", "csne_fix",
-                                   "cov_pinv_weights", "cov_pinv_product", "cov_gather", "cov_inverse", "cov_product", "loss_cost", "loss_scale"};
+                                   "cov_rows", "cov_pinv_weights", "cov_pinv_product", "cov_gather", "cov_inverse", "cov_product", "loss_cost", "loss_scale"};
 
 inline int round_up(int v, int q) { return (v + q - 1) / q * q; }
 // rows of the stacked systems [R D; E] / [R_aug; sqrt(alpha) I]: two blocks of
@@ -609,6 +609,16 @@ struct blsq_cov_plan {
   // sweeps [B], per-problem widths nfree + 1 [B]; the weights [B][NPAD]; staging of the host-pointer call
   DevBuf js, juf, jsrange, jsweeps, jncols, pw;
   DevBuf in_scale, o_rank, o_kept;
+  // What the last covariance call left behind for blsq_cov_rows* (DESIGN.md 7i): the route — the regular one keeps
+  // X = R^-1 in its slot, the pinv one the rotated triangle and pw —, whether perm / nfree describe it, whether in_J
+  // still holds the J of a host-pointer call, and the plan's own copy of the per-problem status
+  enum Kept { KEPT_NONE = 0, KEPT_REGULAR, KEPT_PINV };
+  Kept kept = KEPT_NONE;
+  bool kept_masked = false, kept_staged = false;
+  bool kept_refined = false;        // pinv route: the X slot holds the refined factor of this covariance call
+  DevBuf kept_status;               // [B]
+  DevBuf rowgram;                   // pinv route, allocated on first use: [B][NPAD*NPAD] W W^T (launch_cov_pinv_rowfactor)
+  DevBuf r_A, r_scale, r_out;       // staging of the host-pointer rows call, grown on demand: [B][rows][n], [B], [B][rows]
 };
 namespace blsq_host {
 // the whole covariance call on device pointers; dactive: int64 [B][lda] or nullptr
@@ -622,5 +632,8 @@ int cov_pinv_core(blsq_cov_plan* p, const double* dJ, const long long* dactive, 
                   double* dcov, int* drank, double* drcond, double* dkept, int* dstatus);
 int cov_pinv_to_host(blsq_cov_plan* p, const double* dJ, const long long* dmask, int lda, const double* dscale,
                      double* cov, int32_t* rank, double* rcond, double* kept_rcond, int32_t* status);
+// out[b][i] = scale[b] |a_i through the kept factor|^2 for the rows of dA [B][rows][n] (blsq_cov_rows_dev without its
+// argument checks; blsq_outer_leverage)
+int cov_rows_core(blsq_cov_plan* p, int rows, const double* dA, const double* dscale, double* dout);
 }  // namespace blsq_host
 

@@ -581,6 +581,18 @@ hipError_t launch_cov_pinv_product(int B, int n, int NPAD, const double* X, cons
                                    hipStream_t st);
 // dscale[b] = obj[b] / (m - n)  (m > n)
 hipError_t launch_cov_variance(int B, int m, int n, const double* obj, double* dscale, hipStream_t st);
+// Row forms through the factor a covariance call has left (7i, blsq_cov_rows_dev): out[b][i] = dscale[b] sum_k t_ik^2 for
+// every row a_i of A [B][rows][n], read through perm (nullptr: all variables free).  pinv = 0: t_i = a_i[F] X over the
+// leading nfree x nfree triangle of X; pinv = 1: t_ik = w[k] (row k of X) . a_i[F] (w = nullptr: 1).  NaN where
+// status[b] != 0, 0.0 where nfree[b] = 0.  A row's bits depend on that row and the problem's factor only.
+// launch_cov_pinv_rowfactor: the pinv route's factor for it, Y = (I - diag(w) offdiag(W W^T)) diag(w) W from the rotated
+// triangle W and the weights w — the rows of W are orthogonal to the Jacobi tolerance only, this removes the first
+// order of what is left (G: scratch for W W^T, Y: the result, both [B][NPAD][NPAD]).
+hipError_t launch_cov_rows(int B, int rows, int n, int NPAD, int pinv, const double* A, const int* perm,
+                           const int* nfree, const double* X, const double* w, const int* status,
+                           const double* dscale, double* out, hipStream_t st);
+hipError_t launch_cov_pinv_rowfactor(int B, int n, int NPAD, const double* W, const double* w, const int* nfree,
+                                     const int* status, double* G, double* Y, hipStream_t st);
 
 // ------------------------------------- finite-difference Jacobians (8f-2) ----
 // method: 2 = '2-point', 3 = '3-point'.  X [B][P][n] with P = n (2) or 2n (3); F [B][P][m].

@@ -24,6 +24,9 @@ struct blsq_outer {
   DevBuf covmask;                      // [B][n] int64: the active mask of a 'trf' driver (from x, as the host reports it)
   DevBuf covscale;                     // [B] obj / (m - n): blsq_outer_covariance_pinv with variance_scale
   bool scaled_early = false;           // robust loss: the accepted problems' J were scaled by blsq_outer_covariance
+  bool cov_fresh = false;              // the covariance plan's factor is that of the resident J (blsq_outer_leverage);
+                                       // cleared by start, begin, propose and judge
+  DevBuf lev;                          // [B][m] leverages
   OuterState st{};
   int jac_scaling = 0;
   double xtol = 0.0;
@@ -130,7 +133,7 @@ extern "C" int blsq_outer_start(blsq_outer* o, const double* x0, const double* x
   }
   st.ftol = ftol; st.xtol = xtol; st.gtol = gtol; st.max_nfev = max_nfev;
   o->xtol = xtol; o->jac_scaling = jac_scaling ? 1 : 0;
-  o->started = true; o->begun = false; o->last_accepted = 0; o->scaled_early = false;
+  o->started = true; o->begun = false; o->last_accepted = 0; o->scaled_early = false; o->cov_fresh = false;
   HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
   return 0;
 }
@@ -195,6 +198,7 @@ extern "C" int blsq_outer_begin(blsq_outer* o) {
   blsq_ctx* ctx = o->ctx;
   if (!o->started) return ctx->bad(1, "blsq_outer_start has not been called");
   HIPCHK(ctx, hipSetDevice(ctx->device));
+  o->cov_fresh = false;
   int rc;
   if (o->loss != BLSQ_LOSS_LINEAR) {     // every J is fresh
     if ((rc = outer_loss_scale(o, nullptr))) return rc;
@@ -214,6 +218,7 @@ extern "C" int blsq_outer_propose(blsq_outer* o, int32_t* n_active) {
   if (!o->begun) return ctx->bad(1, "blsq_outer_begin has not been called");
   if (!n_active) return ctx->bad(2, "n_active is NULL");
   HIPCHK(ctx, hipSetDevice(ctx->device));
+  o->cov_fresh = false;
   int rc;
   if (o->last_accepted > 0) {            // fresh Jacobians: factor those problems only
     if (o->loss != BLSQ_LOSS_LINEAR && !o->scaled_early && (rc = outer_loss_scale(o, o->st.accepted))) return rc;
@@ -244,6 +249,7 @@ extern "C" int blsq_outer_judge(blsq_outer* o, int32_t* n_accepted) {
   if (!o->begun) return ctx->bad(1, "blsq_outer_begin has not been called");
   if (!n_accepted) return ctx->bad(2, "n_accepted is NULL");
   HIPCHK(ctx, hipSetDevice(ctx->device));
+  o->cov_fresh = false;
   int rc;
   if (o->loss != BLSQ_LOSS_LINEAR && (rc = outer_loss_cost(o, o->st.ft))) return rc;
   hipError_t e = launch_outer_judge(o->st, ctx->stream);
@@ -334,8 +340,11 @@ extern "C" int blsq_outer_covariance(blsq_outer* o, int free_only, double* cov, 
   HIPCHK(ctx, hipSetDevice(ctx->device));
   const long long* mask = nullptr;
   int lda = o->n;
+  o->cov_fresh = false;
   if (int rc = outer_cov_prepare(o, free_only, &mask, &lda)) return rc;
-  return cov_to_host(o->cov, o->J.as<double>(), mask, lda, cov, rcond, status);
+  if (int rc = cov_to_host(o->cov, o->J.as<double>(), mask, lda, cov, rcond, status)) return rc;
+  o->cov_fresh = true;
+  return 0;
 }
 
 // The pseudo-inverse covariance of every problem (blsq_cov_pinv_dev on the resident J, same rules as above);
@@ -354,6 +363,7 @@ extern "C" int blsq_outer_covariance_pinv(blsq_outer* o, int free_only, int vari
   HIPCHK(ctx, hipSetDevice(ctx->device));
   const long long* mask = nullptr;
   int lda = o->n;
+  o->cov_fresh = false;
   if (int rc = outer_cov_prepare(o, free_only, &mask, &lda)) return rc;
   const double* dscale = nullptr;
   if (variance_scale) {
@@ -364,7 +374,31 @@ extern "C" int blsq_outer_covariance_pinv(blsq_outer* o, int free_only, int vari
     if (e != hipSuccess) return ctx->fail(e, "launch_cov_variance");
     dscale = o->covscale.as<double>();
   }
-  return cov_pinv_to_host(o->cov, o->J.as<double>(), mask, lda, dscale, cov, rank, rcond, kept_rcond, status);
+  if (int rc = cov_pinv_to_host(o->cov, o->J.as<double>(), mask, lda, dscale, cov, rank, rcond, kept_rcond, status))
+    return rc;
+  o->cov_fresh = true;
+  return 0;
+}
+
+// Leverages h_i = (J C J^T)_ii of the resident J through the factor the driver's last covariance call left in its
+// plan (blsq_cov_rows_dev).  A missing or stale factor is an error: nothing is recomputed silently.
+extern "C" int blsq_outer_leverage(blsq_outer* o, double* h, int32_t* status) {
+  if (!o) return -1;
+  blsq_ctx* ctx = o->ctx;
+  if (!o->cov_fresh || !o->cov)
+    return ctx->bad(1, "no current covariance factor: call blsq_outer_covariance / _pinv after the last begin / propose / judge");
+  if (!h) return ctx->bad(2, "h is NULL");
+  if (!status) return ctx->bad(3, "status is NULL");
+  HIPCHK(ctx, hipSetDevice(ctx->device));
+  const size_t nh = sizeof(double) * (size_t)o->B * o->m;
+  if (!o->lev.p)
+    if (int rc = alloc_all(ctx, {{&o->lev, nh, "hipMalloc(leverages)"}})) return rc;
+  if (int rc = cov_rows_core(o->cov, o->m, o->J.as<double>(), nullptr, o->lev.as<double>())) return rc;
+  HIPCHK(ctx, hipMemcpyAsync(h, o->lev.p, nh, hipMemcpyDeviceToHost, ctx->stream));
+  HIPCHK(ctx, hipMemcpyAsync(status, o->cov->kept_status.p, sizeof(int) * (size_t)o->B, hipMemcpyDeviceToHost,
+                             ctx->stream));
+  HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+  return 0;
 }
 
 // ================================================== robust loss functions ===

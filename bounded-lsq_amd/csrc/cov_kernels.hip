@@ -27,6 +27,12 @@
 //                        over the rows in ascending order on the MFMA pipe (operands read along the rows, the weight
 //                        applied on the load), times an optional per-problem scale, written with its mirror image
 //
+//
+// Row forms through the factor either route leaves behind (blsq_cov_rows*):
+//   cov_rows_kernel      out[i] = scale |a_i[F] X|^2 (regular) or scale sum_k (w_k r_k . a_i[F])^2 (pinv) for every row of
+//                        an [rows][n] matrix: leverages h_i = (J C J^T)_ii and prediction variances diag(A C A^T)
+//                        without forming C.  Row-chunk grid, a wave per 16 rows, the products on the MFMA pipe
+//
 // Every sum has a fixed order and nothing is atomic: a problem's bits depend on its own J, mask, m and n only.
 #include "../../include/blsq.h"
 #include "blsq_device.h"
@@ -426,6 +432,197 @@ __global__ __launch_bounds__(COV_PNT) void cov_pinv_product_kernel(int n, int NP
   }
 }
 
+// ---- row forms through the kept factor (7i) ------------------------------------------------------
+// out[b][i] = scale[b] sum_k t_ik^2 for every row a_i of A [B][rows][n]:  regular route t_i = a_i[F] X (X upper
+// triangular, so output tile j sums the tiles k <= j only), pinv route t_ik = w_k (row k of the rotated triangle) . a_i[F].
+// One workgroup per 64 rows of one problem, a wave per 16 rows; A is read through perm (staged in LDS) on the load, the
+// factor tile by tile from L2.  A wave accumulates COV_RJB output tiles at a time so that an A operand is loaded once per
+// block of tiles; every tile's sum runs over k in ascending order, the squares are added tile by tile in ascending
+// order, and one xor tree over the 16 lanes of a row group finishes a row: its bits depend on the row, the factor,
+// and nothing else.  Outside the leading nf x nf block the X slot holds the identity padding of the last tile and
+// whatever an earlier call with more free variables left, so both operands are masked to r, c < nf.
+// The pinv route's factor for the row forms.  The Jacobi SVD stops rotating a pair of rows once their cosine is below
+// sqrt(n) eps, so the rows W = (s_k v_k^T) are orthogonal to ~16 eps only, and t = diag(w) W a — exact for orthogonal
+// rows — misses  a^T (W^T W)^-1 a = |M^-1 W a|^2, M = W W^T,  by that cosine times the ratio of the components it couples
+// (measured: 1.9 x the test bound at 1030 x 272, kappa 1e3 with column scales).  One Newton step on M^-1 from its diagonal
+// removes the first order:  Y' = (I - N) Y,  Y = diag(w) W,  N = diag(w) offdiag(M);  t = Y' a.  Two launches per
+// covariance call, made by the first row-form call after it; a dropped direction (w_k = 0) keeps an exactly zero row.
+//   cov_pinv_rowgram_kernel    M = W W^T over the free block, tile (i, j) summed over the columns in ascending order
+//   cov_pinv_rowfactor_kernel  Y' tile (i, j) = Y_ij - sum_k N_ik Y_kj into the plan's (otherwise idle) X slot
+__global__ __launch_bounds__(COV_PNT) void cov_pinv_rowgram_kernel(int n, int NPAD, const double* __restrict__ Wall,
+                                                                   const int* __restrict__ nfree,
+                                                                   const int* __restrict__ status,
+                                                                   double* __restrict__ Gall) {
+  const int i = blockIdx.x, b = blockIdx.y, lane = threadIdx.x & 63;
+  const int w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  if (status[b] != 0) return;                        // uniform
+  const int nf = nfree ? nfree[b] : n;
+  const int NTl = (nf + 15) >> 4;
+  if (i >= NTl) return;
+  const int ld = NPAD;
+  const double* W = Wall + (long)b * NPAD * NPAD;
+  double* G = Gall + (long)b * NPAD * NPAD;
+  const int lr = lane >> 4, lc = lane & 15;
+  const int ra = 16 * i + lc;
+  for (int j = w; j < NTl; j += COV_PNW) {
+    const int rb = 16 * j + lc;
+    v4d acc = {0.0, 0.0, 0.0, 0.0};
+    for (int k = 0; k < NTl; ++k) {
+      double a[4], bb[4];
+#pragma unroll
+      for (int q = 0; q < 4; ++q) {
+        const int c = 16 * k + 4 * q + lr;
+        a[q] = (ra < nf && c < nf) ? W[(long)ra * ld + c] : 0.0;
+        bb[q] = (rb < nf && c < nf) ? W[(long)rb * ld + c] : 0.0;
+      }
+#pragma unroll
+      for (int q = 0; q < 4; ++q) acc = cov_mfma(a[q], bb[q], acc);
+    }
+#pragma unroll
+    for (int g = 0; g < 4; ++g) G[(long)(16 * i + lr + 4 * g) * ld + 16 * j + lc] = acc[g];
+  }
+}
+
+__global__ __launch_bounds__(COV_PNT) void cov_pinv_rowfactor_kernel(int n, int NPAD, const double* __restrict__ Wall,
+                                                                     const double* __restrict__ wall,
+                                                                     const double* __restrict__ Gall,
+                                                                     const int* __restrict__ nfree,
+                                                                     const int* __restrict__ status,
+                                                                     double* __restrict__ Yall) {
+  const int i = blockIdx.x, b = blockIdx.y, lane = threadIdx.x & 63;
+  const int w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  if (status[b] != 0) return;                        // uniform
+  const int nf = nfree ? nfree[b] : n;
+  const int NTl = (nf + 15) >> 4;
+  if (i >= NTl) return;
+  const int ld = NPAD;
+  const double* W = Wall + (long)b * NPAD * NPAD;
+  const double* G = Gall + (long)b * NPAD * NPAD;
+  const double* wt = wall + (long)b * ld;
+  double* Y = Yall + (long)b * NPAD * NPAD;
+  const int lr = lane >> 4, lc = lane & 15;
+  const int ra = 16 * i + lc;
+  const double wa = (ra < nf) ? wt[ra] : 0.0;
+  for (int j = w; j < NTl; j += COV_PNW) {
+    const int cb = 16 * j + lc;
+    v4d acc = {0.0, 0.0, 0.0, 0.0};
+    for (int k = 0; k < NTl; ++k) {
+      double a[4], bb[4];
+#pragma unroll
+      for (int q = 0; q < 4; ++q) {
+        const int c = 16 * k + 4 * q + lr;           // column of N = row of Y
+        a[q] = (ra < nf && c < nf && c != ra) ? wa * G[(long)ra * ld + c] : 0.0;
+        bb[q] = (c < nf && cb < nf) ? wt[c] * W[(long)c * ld + cb] : 0.0;
+      }
+#pragma unroll
+      for (int q = 0; q < 4; ++q) acc = cov_mfma(a[q], bb[q], acc);
+    }
+#pragma unroll
+    for (int g = 0; g < 4; ++g) {
+      const int r = 16 * i + lr + 4 * g;
+      const double y = (r < nf && cb < nf) ? wt[r] * W[(long)r * ld + cb] : 0.0;
+      Y[(long)r * ld + cb] = (r < nf && cb < nf) ? y - acc[g] : 0.0;
+    }
+  }
+}
+
+static constexpr int COV_RNT = 256;               // four waves
+static constexpr int COV_RNW = COV_RNT / WAVE;
+static constexpr int COV_RROWS = 16 * COV_RNW;    // rows of A per workgroup
+static constexpr int COV_RJB = 4;                 // output tiles a wave accumulates at a time
+
+template <bool PINV>
+__global__ __launch_bounds__(COV_RNT) void cov_rows_kernel(int rows, int n, int NPAD, int chunks,
+                                                           const double* __restrict__ Aall,
+                                                           const int* __restrict__ perm,
+                                                           const int* __restrict__ nfree,
+                                                           const double* __restrict__ Xall,
+                                                           const double* __restrict__ wall,
+                                                           const int* __restrict__ status,
+                                                           const double* __restrict__ dscale,
+                                                           double* __restrict__ out) {
+  extern __shared__ int psh[];                       // [n] (with a permutation only)
+  const int b = blockIdx.x / chunks, chunk = blockIdx.x - b * chunks;
+  const int tid = threadIdx.x, lane = tid & 63;
+  const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
+  double* o = out + (long)b * rows;
+  const int nf = nfree ? nfree[b] : n;
+  const int st = status[b];
+  if (st != 0 || nf == 0) {                          // uniform: no factor (NaN), or nothing free (0.0)
+    const int r = chunk * COV_RROWS + tid;
+    if (tid < COV_RROWS && r < rows) o[r] = (st != 0) ? __builtin_nan("") : 0.0;
+    return;
+  }
+  if (perm) {
+    for (int j = tid; j < nf; j += COV_RNT) psh[j] = perm[(long)b * n + j];
+    __syncthreads();
+  }
+  const int r0 = chunk * COV_RROWS + 16 * w;         // this wave's 16 rows
+  if (r0 >= rows) return;
+  const int lr = lane >> 4, lc = lane & 15;
+  const int NTl = (nf + 15) >> 4;                    // (16 NTl <= NPAD: nf <= n < NPAD)
+  const int ld = NPAD;
+  const double* X = Xall + (long)b * NPAD * NPAD;
+  const bool arow = r0 + lc < rows;                  // operand A: row lc of the group, column 4 q + lr of the tile
+  const double* a = Aall + ((long)b * rows + (arow ? r0 + lc : r0)) * n;
+  double ssq[4] = {0.0, 0.0, 0.0, 0.0};              // rows lr + 4 g, the columns = lc (mod 16)
+  for (int j0 = 0; j0 < NTl; j0 += COV_RJB) {
+    const int jn = min(COV_RJB, NTl - j0);
+    const int kend = PINV ? NTl : j0 + jn;
+    v4d acc[COV_RJB];
+#pragma unroll
+    for (int jj = 0; jj < COV_RJB; ++jj) acc[jj] = v4d{0.0, 0.0, 0.0, 0.0};
+    for (int k = 0; k < kend; ++k) {
+      double av[4];
+#pragma unroll
+      for (int q = 0; q < 4; ++q) {
+        const int c = 16 * k + 4 * q + lr;
+        av[q] = (arow && c < nf) ? a[perm ? psh[c] : c] : 0.0;
+      }
+#pragma unroll
+      for (int jj = 0; jj < COV_RJB; ++jj) {
+        const int j = j0 + jj;
+        if (jj < jn && (PINV || k <= j)) {           // uniform (regular route: the tiles below the diagonal are skipped)
+          double bv[4];
+#pragma unroll
+          for (int q = 0; q < 4; ++q) {
+            const int r = PINV ? 16 * j + lc : 16 * k + 4 * q + lr;
+            const int c = PINV ? 16 * k + 4 * q + lr : 16 * j + lc;
+            bv[q] = (r < nf && c < nf) ? X[(long)r * ld + c] : 0.0;
+          }
+#pragma unroll
+          for (int q = 0; q < 4; ++q) acc[jj] = cov_mfma(av[q], bv[q], acc[jj]);
+        }
+      }
+    }
+#pragma unroll
+    for (int jj = 0; jj < COV_RJB; ++jj) {
+      if (jj < jn) {
+        double wt = 1.0;
+        if (PINV) {
+          const int kk = 16 * (j0 + jj) + lc;
+          wt = (kk < nf) ? (wall ? wall[(long)b * ld + kk] : 1.0) : 0.0;
+        }
+#pragma unroll
+        for (int g = 0; g < 4; ++g) {
+          double t = acc[jj][g];
+          if (PINV) t = (wt != 0.0) ? t * wt : 0.0;  // (a dropped direction: exactly nothing)
+          ssq[g] = fma(t, t, ssq[g]);
+        }
+      }
+    }
+  }
+  const double sc = dscale ? dscale[b] : 1.0;
+#pragma unroll
+  for (int g = 0; g < 4; ++g) {
+    double v = ssq[g];
+#pragma unroll
+    for (int h = 8; h > 0; h >>= 1) v += __shfl_xor(v, h, 64);
+    const int r = r0 + lr + 4 * g;
+    if (lc == 0 && r < rows) o[r] = sc * v;
+  }
+}
+
 // dscale[b] = obj[b] / (m - n): curve_fit's residual variance ("s_sq = cost / (ysize - p0.size)")
 __global__ __launch_bounds__(256) void cov_variance_kernel(int B, double dof, const double* __restrict__ obj,
                                                            double* __restrict__ dscale) {
@@ -503,6 +700,29 @@ hipError_t launch_cov_pinv_product(int B, int n, int NPAD, const double* X, cons
 hipError_t launch_cov_variance(int B, int m, int n, const double* obj, double* dscale, hipStream_t st) {
   if (m <= n) return hipErrorInvalidValue;
   hipLaunchKernelGGL(cov_variance_kernel, dim3((B + 255) / 256), dim3(256), 0, st, B, (double)(m - n), obj, dscale);
+  return hipGetLastError();
+}
+
+hipError_t launch_cov_rows(int B, int rows, int n, int NPAD, int pinv, const double* A, const int* perm,
+                           const int* nfree, const double* X, const double* w, const int* status,
+                           const double* dscale, double* out, hipStream_t st) {
+  if (rows <= 0 || (perm && !nfree)) return hipErrorInvalidValue;
+  const int chunks = (rows + COV_RROWS - 1) / COV_RROWS;
+  const long grid = (long)B * chunks;
+  if (grid > 0x7fffffffL) return hipErrorInvalidValue;
+  const size_t lds = perm ? sizeof(int) * (size_t)n : 0;
+  if (pinv) return launch<cov_rows_kernel<true>>(dim3((unsigned)grid), dim3(COV_RNT), lds, st, rows, n, NPAD, chunks, A,
+                                                 perm, nfree, X, w, status, dscale, out);
+  return launch<cov_rows_kernel<false>>(dim3((unsigned)grid), dim3(COV_RNT), lds, st, rows, n, NPAD, chunks, A, perm,
+                                        nfree, X, w, status, dscale, out);
+}
+
+hipError_t launch_cov_pinv_rowfactor(int B, int n, int NPAD, const double* W, const double* w, const int* nfree,
+                                     const int* status, double* G, double* Y, hipStream_t st) {
+  if (B > 65535) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(cov_pinv_rowgram_kernel, dim3((n + 15) / 16, B), dim3(COV_PNT), 0, st, n, NPAD, W, nfree, status, G);
+  hipLaunchKernelGGL(cov_pinv_rowfactor_kernel, dim3((n + 15) / 16, B), dim3(COV_PNT), 0, st, n, NPAD, W, w, G, nfree,
+                     status, Y);
   return hipGetLastError();
 }
 

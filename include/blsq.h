@@ -446,6 +446,30 @@ int blsq_cov_pinv(blsq_cov_plan* plan, const double* J, const int64_t* active, c
 int blsq_outer_covariance_pinv(blsq_outer* o, int free_only, int variance_scale, double* cov, int32_t* rank,
                                double* rcond, double* kept_rcond, int32_t* status);
 
+/* ---- row forms through the covariance factor: leverages and prediction variances ---------------------------------
+ * For every row a_i of a row-major matrix A [B][rows][n]:  out[b][i] = scale[b] * a_i C_b a_i^T  with C_b the (unscaled)
+ * covariance the plan's LAST blsq_cov* / blsq_cov_pinv* call computed for problem b — evaluated through the factor
+ * that call left in the plan, not through C: ||a_i[F] R^-1||^2 after blsq_cov*, sum_kept (v_k . a_i[F])^2 / s_k^2
+ * after blsq_cov_pinv* (a dropped singular direction contributes exactly nothing).  With A = J these are the leverages
+ * h_i = (J C J^T)_ii; with A a Jacobian at new points, times the residual variance, the variance of the fitted curve.
+ * Columns of active variables (the mask of that covariance call) are never read.  scale NULL means 1; the scale of a
+ * blsq_cov_pinv* call is NOT applied.  out[b][:] is NaN where that call's status[b] != 0 (the plan keeps its own copy
+ * of the status) and exactly 0.0 where no variable is free.  `rows` is independent of the plan's m.  A row's bits
+ * depend on that row, the problem's factor, and nothing else (not on B, the batch mates or rows).
+ * Before any covariance call on the plan: a negative (bad argument) return, message "no covariance factor yet".
+ * blsq_cov_rows_dev: device pointers, asynchronous on the ctx stream.  blsq_cov_rows: host pointers, blocking; A = NULL
+ * means the J the last HOST-pointer covariance call staged (rows must then be the plan's m; an error if the last
+ * covariance call was a device-pointer one). */
+int blsq_cov_rows_dev(blsq_cov_plan* plan, int rows, const double* dA /*[B][rows][n]*/,
+                      const double* dscale /*[B] or NULL*/, double* dout /*[B][rows]*/);
+int blsq_cov_rows(blsq_cov_plan* plan, int rows, const double* A /*host, or NULL*/,
+                  const double* scale /*host [B] or NULL*/, double* out /*host [B][rows]*/);
+/* Leverages of the resident J of an outer driver through the factor of its last blsq_outer_covariance / _pinv call.
+ * blsq_outer_start, _begin, _propose and _judge invalidate that factor: a stale or missing one is a bad-argument error,
+ * nothing is recomputed silently.  status: the status that covariance call reported.  No scale is applied, even if that
+ * call used variance_scale.  Host outputs: B m + B numbers. */
+int blsq_outer_leverage(blsq_outer* o, double* h /*host [B][m]*/, int32_t* status /*host [B]*/);
+
 #ifdef __cplusplus
 }
 #endif
