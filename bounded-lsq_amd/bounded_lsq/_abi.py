@@ -76,6 +76,7 @@ SIGNATURES = {
     "blsq_tsqr_combine_dev": (C.c_int, [vp] + [vp] * 5 + [C.c_int]),
     "blsq_debug_cqr_stats": (C.c_int, [vp, C.POINTER(C.c_uint64), C.c_int]),
     "blsq_debug_gram_stats": (C.c_int, [vp, C.POINTER(C.c_uint64), C.c_int]),
+    "blsq_debug_tri_reference": (C.c_int, [vp, C.c_int]),
     "blsq_debug_cqr2_stats": (C.c_int, [vp, C.POINTER(C.c_uint64), C.c_int]),
     "blsq_debug_gram_route": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, C.c_int, c_int32_p]),
     "blsq_option_count": (C.c_int, []),
@@ -249,6 +250,11 @@ class Context:
         out = (C.c_uint64 * 2)()
         self.check(self.lib.blsq_debug_cqr_stats(self.h, out, 1 if reset else 0), "cqr_stats")
         return int(out[0]), int(out[1])
+
+    def tri_reference(self, on):
+        """on: the three-barrier reference schedule of the blocked triangular solves (n > 80) for this ctx's later
+        launches; off (a new ctx's state): the look-ahead schedule.  Same bits."""
+        self.check(self.lib.blsq_debug_tri_reference(self.h, 1 if on else 0), "tri_reference")
 
     def gram_stats(self, reset=False):
         """-> (problems factored by the normal-equations fast path, problems handed to the QR tree)."""

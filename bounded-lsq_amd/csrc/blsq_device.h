@@ -36,6 +36,13 @@ __device__ __forceinline__ double read_lane(double v, int src_lane) {
   return __hiloint2double(hi, lo);
 }
 
+// a value every lane holds alike, moved to scalar registers (first active lane)
+__device__ __forceinline__ double wave_uniform(double v) {
+  const int lo = __builtin_amdgcn_readfirstlane(__double2loint(v));
+  const int hi = __builtin_amdgcn_readfirstlane(__double2hiint(v));
+  return __hiloint2double(hi, lo);
+}
+
 // ---- wave reductions (all 64 lanes end with the result) ------------------
 // DPP butterfly inside each 16-lane row, then the 4 row totals through SGPRs:
 // no LDS crossbar (ds_bpermute), fixed order (deterministic).

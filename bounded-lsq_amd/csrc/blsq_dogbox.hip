@@ -38,7 +38,7 @@ int dog_alloc_state(blsq_dogbox_plan* p) {
   HIPCHK(ctx, hipMemsetAsync(p->vecs.p, 0, p->vecs.bytes, ctx->stream));
   double* v = p->vecs.as<double>();
   DogState& st = p->st;
-  st.B = B; st.m = p->m; st.n = p->n; st.ld = ld;
+  st.B = B; st.m = p->m; st.n = p->n; st.ld = ld; st.opt = &ctx->opt;
   st.S = p->S.as<double>(); st.X = p->X.as<double>();
   st.x = v; st.lb = v + vs; st.ub = v + 2 * vs; st.scale = v + 3 * vs; st.g = v + 4 * vs;
   st.s = v + 5 * vs; st.uf = v + 6 * vs; st.newton = v + 7 * vs; st.cauchy = v + 8 * vs;

@@ -92,6 +92,7 @@ struct GramCholArgs {
                           // triangular solves only) — half of the bytes a factorisation stores are those zeros
   const int* count_dev;   // optional [1]: the launch is over an upper bound; entries beyond *count_dev leave
   const Options* opt;     // host only: the ctx's switches (nullptr: the table's defaults)
+  int tri_ref;            // set by launch_gram_gate: 1 = the three-barrier triangular solves (Options::tri_ref)
   // optional principal sub-matrix (dogbox: free columns ++ rhs): H = Gsrc[idx, idx] with
   // idx = gather[b][0 .. N_b-2] ++ [n], N_b = ncols_dev[b] (0: nothing to do); gather is increasing
   const int* ncols_dev;   // [B]
@@ -445,6 +446,8 @@ struct LmState {
   int fused_gram;         // 1: problems with path[b] == 0 belong to lm_rounds_reg_kernel (N <= 80) — lm_start
                           // and the round kernels leave them alone (a problem's arithmetic must not depend
                           // on whether its batch also holds Householder-path problems)
+  const Options* opt;     // host only: the ctx's switches (nullptr: the table's defaults)
+  int tri_ref;            // set by the launches: 1 = the three-barrier triangular solves (Options::tri_ref)
 };
 // rank gate of the SVD-free paths (lm_kernels.hip; the dogbox finish in chol_reg.hip)
 static constexpr double LM_EPS = 2.220446049250313e-16;
@@ -461,6 +464,7 @@ hipError_t launch_lm_rounds_reg(const GramCholArgs& c, const LmState& lm, const 
                                 const double* alpha_in, hipStream_t s);
 // launch_gram_chol for NPAD <= 80 (chol_reg.hip): gram_chol_reg_kernel, one wave per problem; a.count = problems
 hipError_t launch_gram_chol_reg(const GramCholArgs& a, hipStream_t s);
+LmState lm_routed(const LmState& lm);      // (lm_kernels.hip) tri_ref from lm.opt: what the launches pass to their kernels
 hipError_t launch_lm_gate(const LmState& lm, int enable, hipStream_t s);   // enable: bit 0 Householder-path, bit 1 normal-equations-path problems
 hipError_t launch_lm_start(const LmState& lm, const double* Delta, const double* alpha_in,
                            hipStream_t s);
@@ -491,11 +495,14 @@ struct DogState {
   // products with it from the normal equations  J_free^T J_free newton = -g_free  (nullptr: off)
   int* csne;                              // [B]
   const double* csne_k2;                  // [B] the proven bound of the computed free-block system (rank gate of such a problem)
+  const Options* opt;     // host only: the ctx's switches (nullptr: the table's defaults)
+  int tri_ref;            // set by the launches: 1 = the three-barrier triangular solves (Options::tri_ref)
 };
 // from_gram / sel / redo: as launch_trf_prep (a Gram-path problem gets neither the compacted
 // columns S nor — yet — its Cauchy step: that comes from X in dog_gate_solve)
 hipError_t launch_dog_prep(const DogState& st, int jac_scaling, int from_gram, const int* sel,
                            int redo, hipStream_t s, const PackVecs* pk = nullptr);
+DogState dog_routed(const DogState& st);   // (lm_kernels.hip) tri_ref from st.opt
 hipError_t launch_dog_solve(const DogState& st, const int* skip, hipStream_t s);
 // path / colinfo (optional): Gram-path flags and the column-norm summary of the free block
 // done (optional [B]): problems the Cholesky kernel already finished (GramCholArgs::dog) are skipped

@@ -46,6 +46,10 @@ extern const OptInfo kOptTable[OPT_COUNT];
 
 struct Options {
   double v[OPT_COUNT];
+  // Not a switch of the table (no key, no environment variable): 1 = the blocked triangular solves of the trust-region
+  // tail run their three-barrier reference schedule instead of the look-ahead (tri_ops.h; bit-identical).  Set per ctx
+  // by blsq_debug_tri_reference, read at every launch; it exists for the tests that compare the two schedules.
+  int tri_ref = 0;
   int i(Opt k) const { return (int)v[k]; }
   bool on(Opt k) const { return v[k] != 0.0; }
   double d(Opt k) const { return v[k]; }

@@ -61,7 +61,7 @@ int trf_alloc_state(blsq_trf_plan* p) {
   HIPCHK(ctx, hipMemsetAsync(p->lm_ints.p, 0, p->lm_ints.bytes, ctx->stream));
   {
     LmState& lm = p->lm;
-    lm.B = B; lm.m = p->m_total; lm.n = p->n; lm.ld = ld;
+    lm.B = B; lm.m = p->m_total; lm.n = p->n; lm.ld = ld; lm.opt = &ctx->opt;
     lm.Raug = p->X.as<double>(); lm.sa = p->lm_sa.as<double>(); lm.Xa = p->lm_Xa.as<double>();
     lm.g_h = p->st.g_h;
     int* ii = p->lm_ints.as<int>();

@@ -11,6 +11,39 @@ namespace blsq {
 static __device__ long long g_chol_st[4][20][8];       // this file's copy (chol_debug_stamps, chol_rl.hip)
 #endif
 
+// Per-row hook of the backward solve (tri_ops.h) for the one-pass form of stage 0: every row adds the panel's share of its
+// sum_j |T_ij| dl_j (columns at and right of the diagonal) while the panel is in LDS.  Per row the contributions arrive in
+// the order of the solve's blocks.  All LDS operands are requested before the first is used (read -> wait -> fma sixteen
+// times in a row cost 0.9 us per phase, tools/cert0_stamps.py).
+struct Cert0RowSums {
+  static constexpr bool active = true;
+  double* rowsB;                         // [NPAD] LDS, zeroed by the caller
+  unsigned dl_addr;                      // LDS byte address of dl[0]
+  bool stp;                              // diagnostic builds: this workgroup takes the stamps
+  double dv[2][16];                      // dl of the column block(s) in hand
+  __device__ __forceinline__ void block(int slot, int c0) {
+    const unsigned db_ = dl_addr + 8u * (unsigned)c0;
+    static_for<0, 16>([&](auto is) { constexpr int s_ = decltype(is)::value; lds_read64_off<8 * s_>(dv[slot][s_], db_); });
+  }
+  __device__ __forceinline__ void ready() {            // (the solver has waited for lgkmcnt(0))
+    tri_lds16_tie(dv[0]);
+    tri_lds16_tie(dv[1]);
+  }
+  __device__ __forceinline__ void row(int slot, int i, const double (&rv)[16], int c0, int bs) {
+    double rs = 0.0;
+#pragma unroll
+    for (int s_ = 0; s_ < 16; ++s_)
+      if (s_ < bs && c0 + s_ >= i) rs = fma(fabs(rv[s_]), dv[slot][s_], rs);
+    rowsB[i] += rs;
+  }
+  __device__ __forceinline__ void stamp(int kb, int k) {
+#ifdef BLSQ_CHOL_STAMPS
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+    CST(stp && (w == 0 || w == 2), w == 0 ? 1 : 2, kb, k);
+#endif
+  }
+};
+
 // ---- certificate, stage 0: the comparison-matrix bound (two triangular solves instead of an inverse) ----
 // For triangular T, |T^-1| <= M(T)^-1 entrywise, M(T) the comparison matrix (diagonal |t_ii|, off-diagonal
 // -|t_ij|; Higham, ASNA 8.2), so  ||R'^-1||_inf <= max_i (M(R')^-1 e)_i  and  ||R'^-1||_1 <= max_j (M(R')^-T e)_j :
@@ -20,7 +53,7 @@ static __device__ long long g_chol_st[4][20][8];       // this file's copy (chol
 // to gram_cond_kernel, which then finds the problem flagged (cert_done) and leaves at once.  With R' = T diag(dl):
 // M(R') z = e  <=>  M(T) w = e, z = w / dl;   M(R')^T y = e  <=>  M(T)^T y = 1 / dl.  All terms are non-negative
 // (no cancellation; the result is inflated by 1e-9 for the rounding of <= 2 n additions per entry).
-__global__ __launch_bounds__(TRI_NT) void gram_cert0_kernel(GramCholArgs a) {
+__global__ __launch_bounds__(TRI_NT, 3) void gram_cert0_kernel(GramCholArgs a) {
   extern __shared__ double sh[];
   __shared__ double red[32];
   const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
@@ -54,88 +87,9 @@ __global__ __launch_bounds__(TRI_NT) void gram_cert0_kernel(GramCholArgs a) {
     for (int i = tid; i < NPAD; i += TRI_NT) { x[i] = 1.0; rowsB[i] = 0.0; }
     __syncthreads();
     CST(stp && w == 0, 0, 18, 2);
-    {
-      const int nblk = (n + 15) / 16;
-      const int bsz = 16 * NPAD;
-      int cur = 0;
-      __builtin_amdgcn_s_waitcnt(0x0F70);
-      tri_pf_issue_upper<TRI_NT>(T, NPAD, (nblk - 1) * 16, pfbuf);
-      for (int kb = nblk - 1; kb >= 0; --kb) {
-        const int c0 = kb * 16;
-        const int bs = (n - c0 < 16) ? n - c0 : 16;
-        const double* bq = pfbuf + cur * bsz;
-        CST(stp && (w == 0 || w == 2), w == 0 ? 1 : 2, kb, 1);
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        CST(stp && (w == 0 || w == 2), w == 0 ? 1 : 2, kb, 2);
-        lds_barrier();                                   // every wave's pieces have landed
-        CST(stp && (w == 0 || w == 2), w == 0 ? 1 : 2, kb, 3);
-        if (kb > 0) tri_pf_issue_upper<TRI_NT>(T, NPAD, c0 - 16, pfbuf + (cur ^ 1) * bsz);
-        CST(stp && (w == 0 || w == 2), w == 0 ? 1 : 2, kb, 4);
-        // (all LDS operands of a phase are requested before the first is used: read -> wait -> fma sixteen times in a row
-        //  cost 0.9 us per phase, tools/cert0_stamps.py)
-        const unsigned xb_ = lds_addr(x) + 8u * (unsigned)c0, db_ = lds_addr(dl) + 8u * (unsigned)c0;
-        if (tid < 64) {                                  // wave 0 (lanes >= 16 are idle copies)
-          const int i = tid & 15;
-          double bv[16], dv[16], D[16], rs = 0.0;
-          tri_v2d bt[8];
-          tri_pf_upper_issue(bt, bq, c0 + i);
-          static_for<0, 16>([&](auto is) { constexpr int s_ = decltype(is)::value; lds_read64_off<8 * s_>(dv[s_], db_); });
-          double r = (i < bs) ? x[c0 + i] : 0.0;
-          const double iv = (i < bs) ? invd[c0 + i] : 0.0;
-          tri_pf_upper_wait(bt, bv);
-          asm volatile("" : "+v"(dv[0]), "+v"(dv[1]), "+v"(dv[2]), "+v"(dv[3]), "+v"(dv[4]), "+v"(dv[5]), "+v"(dv[6]), "+v"(dv[7]),
-                            "+v"(dv[8]), "+v"(dv[9]), "+v"(dv[10]), "+v"(dv[11]), "+v"(dv[12]), "+v"(dv[13]), "+v"(dv[14]),
-                            "+v"(dv[15]));
-#pragma unroll
-          for (int s_ = 0; s_ < 16; ++s_) {
-            const double av = fabs(bv[s_]);
-            D[s_] = (i < bs && s_ < bs && s_ > i) ? -av : 0.0;
-            if (i < bs && s_ < bs && s_ >= i) rs = fma(av, dv[s_], rs);
-          }
-          CST(stp && w == 0, 3, kb, 0);
-#pragma unroll
-          for (int s_ = 15; s_ >= 0; --s_) {
-            const double xs = read_lane(r * iv, s_);
-            if (i < s_) r = fma(-D[s_], xs, r);
-          }
-          asm volatile("" : "+v"(r));
-          CST(stp && w == 0, 3, kb, 1);
-          if (tid < bs) { x[c0 + tid] = r * iv; rowsB[c0 + tid] += rs; }
-        }
-        CST(stp && (w == 0 || w == 2), w == 0 ? 1 : 2, kb, 5);
-        lds_barrier();
-        CST(stp && (w == 0 || w == 2), w == 0 ? 1 : 2, kb, 6);
-        if (tid < c0) {                                   // rows above the block (c0 <= 256 = TRI_NT: one row per thread)
-          double xv[16], dv[16];
-          static_for<0, 16>([&](auto is) { constexpr int s_ = decltype(is)::value; lds_read64_off<8 * s_>(xv[s_], xb_); });
-          static_for<0, 16>([&](auto is) { constexpr int s_ = decltype(is)::value; lds_read64_off<8 * s_>(dv[s_], db_); });
-          for (int i = tid; i < c0; i += TRI_NT) {
-            double rv[16];
-            tri_v2d rt[8];
-            tri_pf_upper_issue(rt, bq, i);
-            tri_pf_upper_wait(rt, rv);
-            asm volatile("" : "+v"(xv[0]), "+v"(xv[1]), "+v"(xv[2]), "+v"(xv[3]), "+v"(xv[4]), "+v"(xv[5]), "+v"(xv[6]), "+v"(xv[7]),
-                              "+v"(xv[8]), "+v"(xv[9]), "+v"(xv[10]), "+v"(xv[11]), "+v"(xv[12]), "+v"(xv[13]), "+v"(xv[14]),
-                              "+v"(xv[15]), "+v"(dv[0]), "+v"(dv[1]), "+v"(dv[2]), "+v"(dv[3]), "+v"(dv[4]), "+v"(dv[5]),
-                              "+v"(dv[6]), "+v"(dv[7]), "+v"(dv[8]), "+v"(dv[9]), "+v"(dv[10]), "+v"(dv[11]), "+v"(dv[12]),
-                              "+v"(dv[13]), "+v"(dv[14]), "+v"(dv[15]));
-            double acc = 0.0, rs = 0.0;
-#pragma unroll
-            for (int s_ = 0; s_ < 16; ++s_) {
-              const double av = fabs(rv[s_]);
-              acc = fma(-av, (s_ < bs) ? xv[s_] : 0.0, acc);
-              if (s_ < bs) rs = fma(av, dv[s_], rs);
-            }
-            x[i] -= acc;
-            rowsB[i] += rs;
-          }
-        }
-        CST(stp && (w == 0 || w == 2), w == 0 ? 1 : 2, kb, 7);
-        lds_barrier();
-        cur ^= 1;
-        CST(stp && (w == 0 || w == 2), w == 0 ? 1 : 2, kb, 0);
-      }
-    }
+    // (the shared backward solve on the comparison matrix; Cert0RowSums adds the row sums while a panel is in LDS)
+    tri_solve_upper_pf<TRI_NT, true, Cert0RowSums>(T, n, NPAD, invd, x, pfbuf, a.tri_ref,
+                                                   Cert0RowSums{rowsB, lds_addr(dl), stp});
     CST(stp && w == 0, 0, 18, 3);
     double zm = 0.0, rinf = 0.0;
     for (int i = tid; i < n; i += TRI_NT) { zm = nanmax2(zm, x[i] / dl[i]); rinf = fmax(rinf, rowsB[i]); }
@@ -204,8 +158,8 @@ __global__ __launch_bounds__(TRI_NT) void gram_cert0_kernel(GramCholArgs a) {
   tri_invdiag(T, n, NPAD, invd);
   for (int i = tid; i < n; i += TRI_NT) { x[i] = 1.0; y[i] = 1.0 / dl[i]; }
   __syncthreads();
-  tri_solve_upper_pf<TRI_NT, true>(T, n, NPAD, invd, x, pfbuf);
-  tri_solve_upper_t_pf<TRI_NT, true>(T, n, NPAD, invd, y, pfbuf);
+  tri_solve_upper_pf<TRI_NT, true>(T, n, NPAD, invd, x, pfbuf, a.tri_ref);
+  tri_solve_upper_t_pf<TRI_NT, true>(T, n, NPAD, invd, y, pfbuf, a.tri_ref);
   double zm = 0.0, ym = 0.0;
   for (int i = tid; i < n; i += TRI_NT) { zm = nanmax2(zm, x[i] / dl[i]); ym = nanmax2(ym, y[i]); }
   zm = block_max(zm, red);
@@ -618,6 +572,7 @@ __global__ __launch_bounds__(GR_NT, 4) void gram_cond_kernel(GramCholArgs a) {
 hipError_t launch_gram_gate(const GramCholArgs& a_in, int B, hipStream_t s, bool stage0_only) {
   GramCholArgs a = a_in;
   a.count = B;
+  a.tri_ref = options_or_default(a.opt).tri_ref;
   if (stage0_only && !(a.NPAD > 80 && a.cert_done && a.dsc && a.cert_ym)) return hipErrorInvalidValue;
   // stage 0 (N > 80; the register-resident factor kernel of the small shapes carries its own first bound):
   // BLSQ_CERT0 = 0 switches it off

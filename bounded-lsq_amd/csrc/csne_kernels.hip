@@ -404,7 +404,7 @@ __device__ __forceinline__ void cs_block_sums(double (&part)[NSUM], double* scr)
   }
 }
 
-__global__ __launch_bounds__(TRI_NT) void csne_fix_kernel(CsneState cs, TrfState st, LmState lm,
+__global__ __launch_bounds__(TRI_NT, 4) void csne_fix_kernel(CsneState cs, TrfState st, LmState lm,
                                                           const double* Delta_in, const double* alpha_in) {
   extern __shared__ double sh[];
   __shared__ double red[32];
@@ -519,8 +519,8 @@ __global__ __launch_bounds__(TRI_NT) void csne_fix_kernel(CsneState cs, TrfState
     tri_invdiag<TRI_NT>(R, n, ld, invd);
     for (int j = tid; j < n; j += TRI_NT) q[j] = -(res[j] + eps * pv[j]);
     __syncthreads();
-    tri_solve_upper_t_pf<TRI_NT>(R, n, ld, invd, q, pfbuf);
-    tri_solve_upper_pf<TRI_NT>(R, n, ld, invd, q, pfbuf);
+    tri_solve_upper_t_pf<TRI_NT>(R, n, ld, invd, q, pfbuf, lm.tri_ref);
+    tri_solve_upper_pf<TRI_NT>(R, n, ld, invd, q, pfbuf, lm.tri_ref);
     double s2[2] = {0.0, 0.0};
     for (int j = tid; j < n; j += TRI_NT) {
       const double dj = q[j];
@@ -559,7 +559,7 @@ hipError_t launch_csne_fix(const CsneState& cs, const TrfState& st, const LmStat
                            const double* alpha_in, int count, hipStream_t s) {
   if (count <= 0) return hipSuccess;
   const size_t lds = sizeof(double) * (6 + 32) * (size_t)cs.ld;
-  return launch<csne_fix_kernel>(dim3(count), dim3(TRI_NT), lds, s, cs, st, lm, Delta, alpha_in);
+  return launch<csne_fix_kernel>(dim3(count), dim3(TRI_NT), lds, s, cs, st, lm_routed(lm), Delta, alpha_in);
 }
 
 // ---- who is on the tier ---------------------------------------------------------------------------
@@ -667,7 +667,7 @@ hipError_t launch_dog_csne_scatter(const CsneState& cs, const DogState& st, int 
 
 // newton += -(X^T X)^-1 J_free^T (J_free newton + f): the residual of the cheap solve against J itself, one corrected
 // solve with the free block's factor; eta = |correction| / |newton| must stay below CSNE_ETA_MAX
-__global__ __launch_bounds__(TRI_NT) void dog_csne_fix_kernel(CsneState cs, DogState st) {
+__global__ __launch_bounds__(TRI_NT, 4) void dog_csne_fix_kernel(CsneState cs, DogState st) {
   extern __shared__ double sh[];
   __shared__ double scr[TRI_NW * 16];
   const int li = blockIdx.x;
@@ -690,8 +690,8 @@ __global__ __launch_bounds__(TRI_NT) void dog_csne_fix_kernel(CsneState cs, DogS
   }
   tri_invdiag<TRI_NT>(R, nf, ld, invd);
   __syncthreads();
-  tri_solve_upper_t_pf<TRI_NT>(R, nf, ld, invd, q, pfbuf);
-  tri_solve_upper_pf<TRI_NT>(R, nf, ld, invd, q, pfbuf);
+  tri_solve_upper_t_pf<TRI_NT>(R, nf, ld, invd, q, pfbuf, st.tri_ref);
+  tri_solve_upper_pf<TRI_NT>(R, nf, ld, invd, q, pfbuf, st.tri_ref);
   double s2[2] = {0.0, 0.0};
   for (int k = tid; k < nf; k += TRI_NT) {
     const double dk = q[k], pk = st.newton[vo + k];
@@ -710,7 +710,7 @@ __global__ __launch_bounds__(TRI_NT) void dog_csne_fix_kernel(CsneState cs, DogS
 hipError_t launch_dog_csne_fix(const CsneState& cs, const DogState& st, int count, hipStream_t s) {
   if (count <= 0) return hipSuccess;
   const size_t lds = sizeof(double) * (2 + 32) * (size_t)cs.ld;
-  return launch<dog_csne_fix_kernel>(dim3(count), dim3(TRI_NT), lds, s, cs, st);
+  return launch<dog_csne_fix_kernel>(dim3(count), dim3(TRI_NT), lds, s, cs, dog_routed(st));
 }
 
 // the problems whose acceptance failed in the last step call leave the tier for good (until the next factor call)

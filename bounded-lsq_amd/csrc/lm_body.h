@@ -46,11 +46,11 @@ __device__ __forceinline__ void lm_csne_record(const LmState& lm, int b, int k, 
     return;
   }
   __syncthreads();
-  tri_solve_upper_t_pf<NT>(R, n, ld, invd, q, pfbuf);
-  tri_solve_upper_pf<NT>(R, n, ld, invd, q, pfbuf);
+  tri_solve_upper_t_pf<NT>(R, n, ld, invd, q, pfbuf, lm.tri_ref);
+  tri_solve_upper_pf<NT>(R, n, ld, invd, q, pfbuf, lm.tri_ref);
   for (int i = tid; i < n; i += NT) rec[ld + i] = q[i];
-  tri_solve_upper_t_pf<NT>(R, n, ld, invd, q, pfbuf);
-  tri_solve_upper_pf<NT>(R, n, ld, invd, q, pfbuf);
+  tri_solve_upper_t_pf<NT>(R, n, ld, invd, q, pfbuf, lm.tri_ref);
+  tri_solve_upper_pf<NT>(R, n, ld, invd, q, pfbuf, lm.tri_ref);
   for (int i = tid; i < n; i += NT) rec[2 * ld + i] = q[i];
   if (tid == 0) { lm.csne_alpha[(long)b * CSNE_MAXE + k] = alpha; lm.csne_ne[b] = k + 1; }
   __syncthreads();
@@ -89,7 +89,7 @@ __device__ __forceinline__ int lm_start_body(const LmState& lm, int b, const dou
     tri_mtv<NT>(R, n, ld, p, q);
     gnorm = sqrt(tri_dot<NT>(q, q, n, red));
   }
-  tri_solve_upper_pf<NT>(R, n, ld, invd, p, pfbuf);                           // R^{-1} c
+  tri_solve_upper_pf<NT>(R, n, ld, invd, p, pfbuf, lm.tri_ref);                           // R^{-1} c
   const double pn = sqrt(tri_dot<NT>(p, p, n, red));
   for (int i = tid; i < n; i += NT) {
     p[i] = -p[i];
@@ -107,7 +107,7 @@ __device__ __forceinline__ int lm_start_body(const LmState& lm, int b, const dou
   // phi(0), phi'(0) -> alpha_lower (trust_region.py:121-123)
   for (int i = tid; i < n; i += NT) q[i] = p[i];
   __syncthreads();
-  tri_solve_upper_t_pf<NT>(R, n, ld, invd, q, pfbuf);
+  tri_solve_upper_t_pf<NT>(R, n, ld, invd, q, pfbuf, lm.tri_ref);
   const double qq = tri_dot<NT>(q, q, n, red);
   const double phi = pn - Delta;
   const double dphi = -qq / pn;
@@ -141,12 +141,13 @@ __device__ __forceinline__ int lm_update_body(const LmState& lm, int b, double* 
   double* invd = q + ld;
   double* pfbuf = invd + ld;                 // 2 x 16 x ld doubles: DMA staging of the solves
   double* sc = lm.sc + (long)b * 16;
-  const double Delta = sc[SC_DELTA];
+  // (Delta and pn live across a triangular solve: in scalar registers they leave the solve its vector registers)
+  const double Delta = wave_uniform(sc[SC_DELTA]);
   tri_invdiag<NT>(R, n, ld, invd);
   for (int i = tid; i < n; i += NT) p[i] = R[(long)i * ld + n];
   __syncthreads();
-  tri_solve_upper_pf<NT>(R, n, ld, invd, p, pfbuf);
-  const double pn = sqrt(tri_dot<NT>(p, p, n, red));
+  tri_solve_upper_pf<NT>(R, n, ld, invd, p, pfbuf, lm.tri_ref);
+  const double pn = wave_uniform(sqrt(tri_dot<NT>(p, p, n, red)));
   for (int i = tid; i < n; i += NT) p[i] = -p[i];
   __syncthreads();
   double alpha = sc[SC_ALPHA], lo = sc[SC_LO], hi = sc[SC_HI];
@@ -163,7 +164,7 @@ __device__ __forceinline__ int lm_update_body(const LmState& lm, int b, double* 
   } else {
     for (int i = tid; i < n; i += NT) q[i] = p[i];
     __syncthreads();
-    tri_solve_upper_t_pf<NT>(R, n, ld, invd, q, pfbuf);
+    tri_solve_upper_t_pf<NT>(R, n, ld, invd, q, pfbuf, lm.tri_ref);
     const double qq = tri_dot<NT>(q, q, n, red);
     phi = pn - Delta;
     dphi = -qq / pn;

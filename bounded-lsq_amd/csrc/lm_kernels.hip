@@ -31,8 +31,20 @@ namespace blsq {
 
 // (phases and the sc[] / st[] slots: blsq_kernels.h)
 
+// the argument structure with the schedule of the triangular solves this launch runs (Options::tri_ref, per call)
+LmState lm_routed(const LmState& lm) {
+  LmState r = lm;
+  r.tri_ref = options_or_default(lm.opt).tri_ref;
+  return r;
+}
+DogState dog_routed(const DogState& st) {
+  DogState r = st;
+  r.tri_ref = options_or_default(st.opt).tri_ref;
+  return r;
+}
+
 // ------------------------------------------------------------------- gate --
-__global__ __launch_bounds__(TRI_NT) void lm_gate_kernel(LmState lm, int enable) {
+__global__ __launch_bounds__(TRI_NT, 4) void lm_gate_kernel(LmState lm, int enable) {
   extern __shared__ double sh[];
   __shared__ double red[32];
   const int b = blockIdx.x, tid = threadIdx.x;
@@ -106,8 +118,8 @@ __global__ __launch_bounds__(TRI_NT) void lm_gate_kernel(LmState lm, int enable)
     for (int i = tid; i < n; i += TRI_NT) v[i] = (i % 3 == 0) ? s0 : -0.5 * s0;
     __syncthreads();
     for (int it = 0; it < 2; ++it) {
-      tri_solve_upper_t_pf(R, n, ld, invd, v, pfbuf);
-      tri_solve_upper_pf(R, n, ld, invd, v, pfbuf);
+      tri_solve_upper_t_pf(R, n, ld, invd, v, pfbuf, lm.tri_ref);
+      tri_solve_upper_pf(R, n, ld, invd, v, pfbuf, lm.tri_ref);
       const double nv = sqrt(tri_dot(v, v, n, red));
       smin = (nv > 0.0 && is_finite(nv)) ? 1.0 / sqrt(nv) : 0.0;   // ||(R^T R)^{-1} v|| ~ 1/s_min^2
       const double inv = (nv > 0.0 && is_finite(nv)) ? 1.0 / nv : 0.0;
@@ -128,12 +140,12 @@ __global__ __launch_bounds__(TRI_NT) void lm_gate_kernel(LmState lm, int enable)
 
 hipError_t launch_lm_gate(const LmState& lm, int enable, hipStream_t s) {
   const size_t lds = sizeof(double) * (3 + 32) * (size_t)lm.ld;
-  return launch<lm_gate_kernel>(dim3(lm.B), dim3(TRI_NT), lds, s, lm, enable);
+  return launch<lm_gate_kernel>(dim3(lm.B), dim3(TRI_NT), lds, s, lm_routed(lm), enable);
 }
 
 // ------------------------------------------------------------------ start --
 // Gauss-Newton step (alpha = 0) on R_aug, acceptance test, bracket initialisation (lm_body.h).
-__global__ __launch_bounds__(TRI_NT) void lm_start_kernel(LmState lm, const double* Delta_in,
+__global__ __launch_bounds__(TRI_NT, 4) void lm_start_kernel(LmState lm, const double* Delta_in,
                                                           const double* alpha_in) {
   extern __shared__ double sh[];
   __shared__ double red[32];
@@ -145,12 +157,12 @@ __global__ __launch_bounds__(TRI_NT) void lm_start_kernel(LmState lm, const doub
 hipError_t launch_lm_start(const LmState& lm, const double* Delta, const double* alpha_in,
                            hipStream_t s) {
   const size_t lds = sizeof(double) * (3 + 32) * (size_t)lm.ld;
-  return launch<lm_start_kernel>(dim3(lm.B), dim3(TRI_NT), lds, s, lm, Delta, alpha_in);
+  return launch<lm_start_kernel>(dim3(lm.B), dim3(TRI_NT), lds, s, lm_routed(lm), Delta, alpha_in);
 }
 
 // ----------------------------------------------------------------- update --
 // one evaluation of phi / phi' at the current alpha + the Newton update (:132-150; lm_body.h)
-__global__ __launch_bounds__(TRI_NT) void lm_update_kernel(LmState lm) {
+__global__ __launch_bounds__(TRI_NT, 4) void lm_update_kernel(LmState lm) {
   extern __shared__ double sh[];
   __shared__ double red[32];
   // launched over the compacted list of evaluation lm.round; writes the next one
@@ -163,7 +175,7 @@ __global__ __launch_bounds__(TRI_NT) void lm_update_kernel(LmState lm) {
 
 hipError_t launch_lm_update(const LmState& lm, int active, hipStream_t s) {
   const size_t lds = sizeof(double) * (3 + 32) * (size_t)lm.ld;
-  return launch<lm_update_kernel>(dim3(active), dim3(TRI_NT), lds, s, lm);
+  return launch<lm_update_kernel>(dim3(active), dim3(TRI_NT), lds, s, lm_routed(lm));
 }
 
 
@@ -173,7 +185,7 @@ hipError_t launch_lm_update(const LmState& lm, int active, hipStream_t s) {
 // rcond * s_max with rcond = eps * max(m, n_free); the gate requires the inverse-power
 // upper bound on s_min to clear that threshold by the same 1e3 margin, otherwise the
 // Jacobi SVD computes the truncated min-norm solution as before.
-__global__ __launch_bounds__(TRI_NT) void dog_gate_solve_kernel(DogState st, int* fast,
+__global__ __launch_bounds__(TRI_NT, 4) void dog_gate_solve_kernel(DogState st, int* fast,
                                                                 int* ncols_jac, int enable,
                                                                 const int* path,
                                                                 const double* colinfo, int* jac_count,
@@ -245,8 +257,8 @@ __global__ __launch_bounds__(TRI_NT) void dog_gate_solve_kernel(DogState st, int
     for (int i = tid; i < nf; i += TRI_NT) v[i] = (i % 3 == 0) ? s0 : -0.5 * s0;
     __syncthreads();
     for (int it = 0; it < 3; ++it) {
-      tri_solve_upper_t_pf(R, nf, ld, invd, v, pfbuf);
-      tri_solve_upper_pf(R, nf, ld, invd, v, pfbuf);
+      tri_solve_upper_t_pf(R, nf, ld, invd, v, pfbuf, st.tri_ref);
+      tri_solve_upper_pf(R, nf, ld, invd, v, pfbuf, st.tri_ref);
       const double nv = sqrt(tri_dot(v, v, nf, red));
       smin = (nv > 0.0 && is_finite(nv)) ? 1.0 / sqrt(nv) : 0.0;
       const double inv = (nv > 0.0 && is_finite(nv)) ? 1.0 / nv : 0.0;
@@ -259,7 +271,7 @@ __global__ __launch_bounds__(TRI_NT) void dog_gate_solve_kernel(DogState st, int
   if (ok) {
     for (int i = tid; i < nf; i += TRI_NT) v[i] = R[(long)i * ld + nf];      // c_f
     __syncthreads();
-    tri_solve_upper_pf(R, nf, ld, invd, v, pfbuf);
+    tri_solve_upper_pf(R, nf, ld, invd, v, pfbuf, st.tri_ref);
     for (int i = tid; i < nf; i += TRI_NT) st.newton[(long)b * ld + i] = -v[i];
   }
   if (tid == 0) {
@@ -275,7 +287,7 @@ hipError_t launch_dog_gate_solve(const DogState& st, int* fast, int* ncols_jac, 
   // ld > 576 (dogbox alone, n >= 577): the DMA staging of the blocked triangular solves does not fit the 160 KB of a
   // workgroup.  Such problems take the Jacobi SVD (the gate is off, the staging is neither allocated nor touched).
   if (lds > LDS_MAX_BYTES) { enable = 0; lds = sizeof(double) * 3 * (size_t)st.ld; }
-  return launch<dog_gate_solve_kernel>(dim3(st.B), dim3(TRI_NT), lds, s, st, fast,
+  return launch<dog_gate_solve_kernel>(dim3(st.B), dim3(TRI_NT), lds, s, dog_routed(st), fast,
                      ncols_jac, enable, path, colinfo, jac_count, done);
 }
 

@@ -268,6 +268,10 @@ int blsq_debug_csne_stats(blsq_ctx* ctx, uint64_t out[3], int reset);
 /* ... per problem: on_tier[b] = 1 while problem b is on the tier; eta[b] = the largest first-order correction the last
  * step call measured for it (the quantity its acceptance bounds: <= 1e-7), -1 where the tier declined.  Either may be NULL. */
 int blsq_trf_debug_csne(blsq_trf_plan* plan, int32_t* on_tier /*B*/, double* eta /*B*/);
+/* Diagnostics: on != 0 makes every later launch of this ctx run the blocked triangular solves of the trust-region tail
+ * (n > 80) in their three-barrier reference schedule instead of the look-ahead schedule; 0 (the state of a new ctx)
+ * switches back.  Both give the same bits; the tests compare them. */
+int blsq_debug_tri_reference(blsq_ctx* ctx, int on);
 /* Diagnostics of the factorisation front end: out[0] = problems factored by the
  * normal-equations fast path (Gram + equilibrated Cholesky, conditioning-gated), out[1] =
  * problems the gate handed to the Householder TSQR tree, since the last reset. */
