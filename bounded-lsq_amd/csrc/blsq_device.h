@@ -1,4 +1,12 @@
 // Device-side helpers shared by the HIP kernels (gfx950, wave64).
+//
+// Contraction rule.  trf_kernels, dogbox_kernels, outer_kernels, fd_kernels and loss_kernels are compiled with
+// -ffp-contract=off (they keep the reference's elementwise roundings); every other file contracts.  A helper in a
+// shared header (this one, mv_ops.h, tri_ops.h) is therefore compiled both ways, and must give the same bits in both:
+//   - every fused operation is spelled fma(...);
+//   - no `x * y + z` that is meant to stay unfused, unless the routine carries `#pragma clang fp contract(off)` itself.
+// (A product that feeds an fma() call, and sums of sums, have nothing to contract.)  Routines that WANT two roundings per
+// term, such as dot_dev / dot3_dev of trf_kernels.hip, stay in their -ffp-contract=off file.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -9,6 +17,13 @@ typedef double v4d __attribute__((ext_vector_type(4)));
 
 constexpr int WAVE = 64;
 constexpr int TILE = 16;          // f64 MFMA tile edge (v_mfma_f64_16x16x4_f64)
+constexpr double DBL_EPS = 2.220446049250313e-16;   // np.finfo(float).eps: the one epsilon of the device code
+
+// D = A B + C on the FP64 MFMA pipe: lane l holds A[l & 15][4 s + (l >> 4)] and B[4 s + (l >> 4)][l & 15] of k-step s,
+// and rows (l >> 4) + 4 g, column l & 15 of the accumulator
+__device__ __forceinline__ v4d mfma_f64(double a, double b, v4d c) {
+  return __builtin_amdgcn_mfma_f64_16x16x4f64(a, b, c, 0, 0, 0);
+}
 
 __device__ __forceinline__ int lane_id() { return threadIdx.x & (WAVE - 1); }
 __device__ __forceinline__ int wave_id() { return threadIdx.x >> 6; }
@@ -154,6 +169,19 @@ __device__ __forceinline__ double block_min(double v, double* red) {
   for (int w = 1; w < nw; ++w) t = nanmin2(t, red[w]);
   return t;
 }
+// (every thread's count summed: integer, so the order does not matter)
+__device__ __forceinline__ int block_sum_int(int v, double* red) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, WAVE);
+  const int nw = (blockDim.x + WAVE - 1) / WAVE;
+  int* r = reinterpret_cast<int*>(red);
+  __syncthreads();
+  if (lane_id() == 0) r[wave_id()] = v;
+  __syncthreads();
+  int t = 0;
+  for (int w = 0; w < nw; ++w) t += r[w];
+  return t;
+}
 __device__ __forceinline__ int block_or(int v, double* red) {
   int any = __any(v) ? 1 : 0;
   const int nw = (blockDim.x + WAVE - 1) / WAVE;
@@ -189,6 +217,11 @@ __device__ __forceinline__ bool is_finite(double v) {
 // ---- LDS-DMA (global -> LDS without VGPR staging) ------------------------------------------
 typedef __attribute__((address_space(1))) const void gptr_t;
 typedef __attribute__((address_space(3))) void lptr_t;
+
+// LDS byte address of a pointer into LDS (the operand of an explicit ds_read)
+__device__ __forceinline__ unsigned lds_addr(const double* p) {
+  return (unsigned)(unsigned long)(lptr_t*)p;
+}
 
 // One LDS-DMA instruction: 64 lanes x 16 B, global (per-lane address) -> LDS
 // (wave-uniform base + 16 lane).  Completion is tracked by vmcnt, in issue order.

@@ -450,7 +450,6 @@ struct LmState {
   int tri_ref;            // set by the launches: 1 = the three-barrier triangular solves (Options::tri_ref)
 };
 // rank gate of the SVD-free paths (lm_kernels.hip; the dogbox finish in chol_reg.hip)
-static constexpr double LM_EPS = 2.220446049250313e-16;
 static constexpr double LM_GATE_MARGIN = 1.0e3;
 // slots of LmState.sc / LmState.st, phases of the iteration (lm_kernels.hip; the fused rounds in chol_reg.hip)
 enum { LM_IDLE = 0, LM_EVAL = 1, LM_FINAL = 2 };

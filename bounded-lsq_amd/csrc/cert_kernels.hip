@@ -122,7 +122,7 @@ __global__ __launch_bounds__(TRI_NT, 3) void gram_cert0_kernel(GramCholArgs a) {
       if (a.lmfin.fast && passed && a.colinfo && a.lmfin.enable != 0 && a.lmfin.m >= n) {
         const double mn = a.colinfo[2 * (long)b], sm = a.colinfo[2 * (long)b + 1];
         const double smin_lb = GRAM_SMIN_PROVEN * mn, smax_ub = sqrt(sm);
-        if (is_finite(sm) && sm > 0.0 && smin_lb > LM_GATE_MARGIN * LM_EPS * a.lmfin.m * smax_ub) {
+        if (is_finite(sm) && sm > 0.0 && smin_lb > LM_GATE_MARGIN * DBL_EPS * a.lmfin.m * smax_ub) {
           a.lmfin.fast[b] = 1;
           a.lmfin.ncols_jac[b] = 0;
           a.lmfin.sc[(long)b * 16 + SC_SMAX] = smax_ub;
@@ -438,10 +438,10 @@ __global__ __launch_bounds__(GR_NT, 4) void gram_cond_kernel(GramCholArgs a) {
               bv[s] = Y[ro + 16 * j + lc];
             }
 #pragma unroll
-            for (int s = 0; s < 4; ++s) acc = gmfma(av[s] * dli, bv[s], acc);
+            for (int s = 0; s < 4; ++s) acc = mfma_f64(av[s] * dli, bv[s], acc);
           }
 #pragma unroll
-          for (int s = 0; s < 4; ++s) Yt = gmfma(-Ri[(4 * s + lr) * 16 + lc], acc[s], Yt);
+          for (int s = 0; s < 4; ++s) Yt = mfma_f64(-Ri[(4 * s + lr) * 16 + lc], acc[s], Yt);
         }
 #pragma unroll
         for (int g = 0; g < 4; ++g) {
@@ -530,7 +530,7 @@ __global__ __launch_bounds__(GR_NT, 4) void gram_cond_kernel(GramCholArgs a) {
             bv[s2] = Y[ro + 16 * j + lc];
           }
 #pragma unroll
-          for (int s2 = 0; s2 < 4; ++s2) acc = gmfma(av[s2], bv[s2], acc);
+          for (int s2 = 0; s2 < 4; ++s2) acc = mfma_f64(av[s2], bv[s2], acc);
         }
         const double z2 = (acc[0] * acc[0] + acc[1] * acc[1]) + (acc[2] * acc[2] + acc[3] * acc[3]);
         cf = fma(wgt, wave_sum(c2), cf);

@@ -47,7 +47,6 @@ __device__ __forceinline__ void rows_to_all(double v, double (&P)[4]) {
 __device__ __forceinline__ double chol16_blocked3(v4d T, double* Dt, double* Ri, int nlive, double pmin) {
   const int lane = threadIdx.x & 63, lr = lane >> 4, lc = lane & 15;
   auto wave_lds = []() { asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); };
-  auto mf = [](double a, double b, v4d c) { return __builtin_amdgcn_mfma_f64_16x16x4f64(a, b, c, 0, 0, 0); };
   double Y[4];
 #pragma unroll
   for (int q = 0; q < 4; ++q) {
@@ -82,7 +81,7 @@ __device__ __forceinline__ double chol16_blocked3(v4d T, double* Dt, double* Ri,
     double Rq = lr == 0 ? P[0] : lr == 1 ? P[1] : lr == 2 ? P[2] : P[3];
     if (lc < 4 * q + lr) Rq = 0.0;
     Dt[(4 * q + lr) * 16 + lc] = Rq;
-    if (q < 3) T = mf(-Rq, Rq, T);
+    if (q < 3) T = mfma_f64(-Rq, Rq, T);
     const double t00 = ri[0], t11 = ri[1], t22 = ri[2], t33 = ri[3];
     const double t01 = -ri[0] * (rr[0][1] * t11);
     const double t12 = -ri[1] * (rr[1][2] * t22);
@@ -104,14 +103,14 @@ __device__ __forceinline__ double chol16_blocked3(v4d T, double* Dt, double* Ri,
       for (int p = 0; p < q; ++p) {
         double a = Dt[(4 * p + lr) * 16 + 4 * q + (lc & 3)];
         if (lc >= 4) a = 0.0;
-        Wa[p] = mf(a, Y[p], v4d{0.0, 0.0, 0.0, 0.0});
+        Wa[p] = mfma_f64(a, Y[p], v4d{0.0, 0.0, 0.0, 0.0});
       }
       W = Wa[0][0];
       if (q > 1) W += Wa[1][0];
       if (q > 2) W += Wa[2][0];
     }
     const double Z = ((lc == 4 * q + lr) ? 1.0 : 0.0) - W;
-    const v4d Ya = mf(Top, Z, v4d{0.0, 0.0, 0.0, 0.0});
+    const v4d Ya = mfma_f64(Top, Z, v4d{0.0, 0.0, 0.0, 0.0});
     Y[q] = Ya[0];
     Ri[lc * 16 + 4 * q + lr] = Y[q];
   }

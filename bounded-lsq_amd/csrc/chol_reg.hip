@@ -152,7 +152,7 @@ __device__ __forceinline__ double reg_factor(v4d (&acc)[NTILE], double* Dt, doub
             acc[tix(kb, kb)] = X;
           } else {
 #pragma unroll
-            for (int s_ = 0; s_ < 4; ++s_) X = gmfma(Ri[(4 * s_ + lr) * 16 + lc], acc[tix(kb, j)][s_], X);
+            for (int s_ = 0; s_ < 4; ++s_) X = mfma_f64(Ri[(4 * s_ + lr) * 16 + lc], acc[tix(kb, j)][s_], X);
             acc[tix(kb, j)] = X;
             if (j == jn && lc == cn) {
 #pragma unroll
@@ -169,7 +169,7 @@ __device__ __forceinline__ double reg_factor(v4d (&acc)[NTILE], double* Dt, doub
           if (j < NT) {
 #pragma unroll
             for (int s_ = 0; s_ < 4; ++s_)
-              acc[tix(i, j)] = gmfma(-acc[tix(kb, i)][s_], acc[tix(kb, j)][s_], acc[tix(i, j)]);
+              acc[tix(i, j)] = mfma_f64(-acc[tix(kb, i)][s_], acc[tix(kb, j)][s_], acc[tix(i, j)]);
           }
         }
       }
@@ -423,10 +423,10 @@ __global__ __launch_bounds__(REG_NT, 1) void gram_chol_reg_kernel(GramCholArgs a
 #pragma unroll
                 for (int kk = jj; kk < i; ++kk) {
 #pragma unroll
-                  for (int s_ = 0; s_ < 4; ++s_) av = gmfma(acc[tix(kk, i)][s_], Yc[kk][s_], av);
+                  for (int s_ = 0; s_ < 4; ++s_) av = mfma_f64(acc[tix(kk, i)][s_], Yc[kk][s_], av);
                 }
 #pragma unroll
-                for (int s_ = 0; s_ < 4; ++s_) Yt = gmfma(-Ria[i * 256 + (4 * s_ + lr) * 16 + lc], av[s_], Yt);
+                for (int s_ = 0; s_ < 4; ++s_) Yt = mfma_f64(-Ria[i * 256 + (4 * s_ + lr) * 16 + lc], av[s_], Yt);
               }
 #pragma unroll
               for (int g = 0; g < 4; ++g) {
@@ -467,7 +467,7 @@ __global__ __launch_bounds__(REG_NT, 1) void gram_chol_reg_kernel(GramCholArgs a
     if (!fail && passed && a.colinfo && a.lmfin.enable != 0 && a.lmfin.m >= n) {
       const double mn = tv[0], sm = tv[1];
       const double smin_lb = GRAM_SMIN_PROVEN * mn, smax_ub = sqrt(sm);
-      if (is_finite(sm) && sm > 0.0 && smin_lb > LM_GATE_MARGIN * LM_EPS * a.lmfin.m * smax_ub) {
+      if (is_finite(sm) && sm > 0.0 && smin_lb > LM_GATE_MARGIN * DBL_EPS * a.lmfin.m * smax_ub) {
         a.lmfin.fast[b] = 1;
         a.lmfin.ncols_jac[b] = 0;
         a.lmfin.sc[(long)b * 16 + SC_SMAX] = smax_ub;
@@ -522,7 +522,7 @@ __global__ __launch_bounds__(REG_NT, 1) void gram_chol_reg_kernel(GramCholArgs a
       const double fac = -gg / uu;
       for (int q = lane; q < n; q += WAVE) a.dog.cauchy[(long)b * a.stride_vec + q] = fac * vv[q];
       const int mx = a.dog.m > n ? a.dog.m : n;
-      const bool sure = is_finite(sm) && sm > 0.0 && (GRAM_SMIN_PROVEN * mn > LM_GATE_MARGIN * LM_EPS * mx * sqrt(sm));
+      const bool sure = is_finite(sm) && sm > 0.0 && (GRAM_SMIN_PROVEN * mn > LM_GATE_MARGIN * DBL_EPS * mx * sqrt(sm));
       if (a.dog.enable != 0 && a.dog.m >= n && sure) {
         // y = R'^-1 c', newton = -sq_n dl . y
         reg_back_solve(acc, Ria, cv, yv, tv, n, lsync);

@@ -156,7 +156,7 @@ __global__ __launch_bounds__(GR_NT, 4) void gram_chol_kernel(GramCholArgs a) {
             bv[s] = Gb[ro + 16 * j + lc];
           }
 #pragma unroll
-          for (int s = 0; s < 4; ++s) S[u] = gmfma(-(av[s] * dk), bv[s] * dj, S[u]);
+          for (int s = 0; s < 4; ++s) S[u] = mfma_f64(-(av[s] * dk), bv[s] * dj, S[u]);
         }
       }
     }
@@ -186,7 +186,7 @@ __global__ __launch_bounds__(GR_NT, 4) void gram_chol_kernel(GramCholArgs a) {
           for (int g = 0; g < 4; ++g) X[g] = Dt[(lr + 4 * g) * 16 + lc];
         } else {
 #pragma unroll
-          for (int s = 0; s < 4; ++s) X = gmfma(Ri[(4 * s + lr) * 16 + lc], S[u][s], X);
+          for (int s = 0; s < 4; ++s) X = mfma_f64(Ri[(4 * s + lr) * 16 + lc], S[u][s], X);
         }
         const double sj = sq[16 * j + lc];
 #pragma unroll
@@ -534,7 +534,7 @@ __device__ __forceinline__ void chol_rl2_body(const GramCholArgs& a, const int b
           for (int g = 0; g < 4; ++g) X[g] = DtC[(lr + 4 * g) * 16 + lc];
         } else {
 #pragma unroll
-          for (int s_ = 0; s_ < 4; ++s_) X = gmfma(rf[s_], S[s_], X);
+          for (int s_ = 0; s_ < 4; ++s_) X = mfma_f64(rf[s_], S[s_], X);
         }
         const double sj = sq[16 * j + lc];
         const double dj = dl[16 * j + lc];
@@ -573,7 +573,7 @@ __device__ __forceinline__ void chol_rl2_body(const GramCholArgs& a, const int b
           if (t == t_dia) {
             v4d S = get(t);
 #pragma unroll
-            for (int s_ = 0; s_ < 4; ++s_) S = gmfma(-Ra[64 * s_], Ra[64 * s_], S);
+            for (int s_ = 0; s_ < 4; ++s_) S = mfma_f64(-Ra[64 * s_], Ra[64 * s_], S);
             put(t, S);
 #pragma unroll
             for (int g = 0; g < 4; ++g) DtN[(lr + 4 * g) * 16 + lc] = S[g];
@@ -625,7 +625,7 @@ __device__ __forceinline__ void chol_rl2_body(const GramCholArgs& a, const int b
           const double* Rb = RrowC + j * 256 + lr * 16 + lc;
           v4d S = get(t);
 #pragma unroll
-          for (int s_ = 0; s_ < 4; ++s_) S = gmfma(-Ra[64 * s_], Rb[64 * s_], S);
+          for (int s_ = 0; s_ < 4; ++s_) S = mfma_f64(-Ra[64 * s_], Rb[64 * s_], S);
           put(t, S);
         }
       }

@@ -33,6 +33,12 @@
 //                        an [rows][n] matrix: leverages h_i = (J C J^T)_ii and prediction variances diag(A C A^T)
 //                        without forming C.  Row-chunk grid, a wave per 16 rows, the products on the MFMA pipe
 //
+// cov_product_kernel, cov_pinv_product_kernel, cov_pinv_rowgram_kernel and cov_pinv_rowfactor_kernel are instances of one
+// skeleton: the CovTile prologue (cov_tile) and the loop nest cov_tile_product, parameterised by the two operand
+// loaders, the start of j and of k and the epilogue; the two *_product kernels share the symmetric scatter through perm
+// (cov_scatter_sym).  cov_rows_kernel and the MFMA loops inside cov_inverse_kernel have another nest and their own code.
+// Workgroup maxima, minima and the rank count are block_max / block_min / block_sum_int of blsq_device.h.
+//
 // Every sum has a fixed order and nothing is atomic: a problem's bits depend on its own J, mask, m and n only.
 #include "../../include/blsq.h"
 #include "blsq_device.h"
@@ -47,11 +53,6 @@ static constexpr int COV_PNT = 256;               // product kernel: four waves,
 static constexpr int COV_PNW = COV_PNT / WAVE;
 static constexpr int COV_GNT = 256;
 static constexpr int COV_TARGET_ELEMS = 8192;     // J doubles per gather workgroup
-static constexpr double COV_EPS = 2.220446049250313e-16;
-
-__device__ __forceinline__ v4d cov_mfma(double a, double b, v4d c) {
-  return __builtin_amdgcn_mfma_f64_16x16x4f64(a, b, c, 0, 0, 0);
-}
 
 // ---- masks and permutations --------------------------------------------------------------------
 __global__ __launch_bounds__(256) void cov_perm_kernel(int B, int n, const long long* __restrict__ active, int lda,
@@ -132,20 +133,6 @@ __global__ __launch_bounds__(COV_GNT) void cov_stack_kernel(int m, int n, int r0
 }
 
 // ---- inverse -----------------------------------------------------------------------------------
-// max over the workgroup in a fixed tree; NaN / Inf inputs are the caller's business (it tests them first)
-template <int NT>
-__device__ __forceinline__ double cov_wg_max(double v, double* red) {
-  const int tid = threadIdx.x;
-  __syncthreads();
-  red[tid] = v;
-  __syncthreads();
-  for (int h = NT / 2; h > 0; h >>= 1) {
-    if (tid < h) red[tid] = fmax(red[tid], red[tid + h]);
-    __syncthreads();
-  }
-  return red[0];
-}
-
 // column sums of |T| over the leading nf x nf upper triangle (thread per column, rows in ascending order)
 __device__ __forceinline__ double cov_norm1_part(const double* T, int ld, int nf, int* bad) {
   double best = 0.0;
@@ -166,7 +153,7 @@ __global__ __launch_bounds__(COV_NT) void cov_inverse_kernel(int m, int n, int N
                                                              double* Xall, const int* __restrict__ nfree,
                                                              double* __restrict__ cov, double* __restrict__ rcond,
                                                              int* __restrict__ status) {
-  __shared__ double red[COV_NT];
+  __shared__ double red[32];
   __shared__ double tsh[COV_NW][256];               // per wave: a staged tile (row-major)
   const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63;
   const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -194,7 +181,7 @@ __global__ __launch_bounds__(COV_NT) void cov_inverse_kernel(int m, int n, int N
     if (tid == 0) { rcond[b] = 0.0; status[b] = 1; }
     return;
   }
-  const double rnorm = cov_wg_max<COV_NT>(rpart, red);
+  const double rnorm = block_max(rpart, red);
   const int NTl = (nf + 15) >> 4;                    // tiles of the free block (NTl * 16 <= NPAD: nf <= n < NPAD)
   // R restricted to the free block and padded with the identity up to the tile edge
   auto ldR = [&](int r, int c) -> double {
@@ -233,7 +220,7 @@ __global__ __launch_bounds__(COV_NT) void cov_inverse_kernel(int m, int n, int N
         for (int q = 0; q < 4; ++q) {
           const double a = X[(long)(16 * i + lc) * ld + 16 * k + 4 * q + lr];
           const double bb = ldR(16 * k + 4 * q + lr, 16 * j + lc);
-          acc = cov_mfma(a, bb, acc);
+          acc = mfma_f64(a, bb, acc);
         }
       }
 #pragma unroll
@@ -244,7 +231,7 @@ __global__ __launch_bounds__(COV_NT) void cov_inverse_kernel(int m, int n, int N
       for (int q = 0; q < 4; ++q) {                  // X_ij = -T X_jj
         const double a = ts[lc * 16 + 4 * q + lr];
         const double bb = X[(long)(16 * j + 4 * q + lr) * ld + 16 * j + lc];
-        out = cov_mfma(a, bb, out);
+        out = mfma_f64(a, bb, out);
       }
 #pragma unroll
       for (int g = 0; g < 4; ++g) X[(long)(16 * i + lr + 4 * g) * ld + 16 * j + lc] = -out[g];
@@ -257,14 +244,66 @@ __global__ __launch_bounds__(COV_NT) void cov_inverse_kernel(int m, int n, int N
   int xbad = 0;
   const double xpart = cov_norm1_part(X, ld, nf, &xbad);
   xbad = __syncthreads_or(xbad);
-  const double xnorm = cov_wg_max<COV_NT>(xpart, red);
+  const double xnorm = block_max(xpart, red);
   double rc = 0.0;
   if (!xbad) rc = 1.0 / (rnorm * xnorm);
-  const double thresh = COV_EPS * (double)(m > nf ? m : nf);
+  const double thresh = DBL_EPS * (double)(m > nf ? m : nf);
   const int sing = !(rc >= thresh);
   if (tid == 0) { rcond[b] = rc; status[b] = sing; }
   if (sing) cov_fill(C, nn, __builtin_nan(""));
   else if (nf < n) cov_fill(C, nn, 0.0);
+}
+
+// ---- 16 x 16 tile products ------------------------------------------------------------------------
+// The covariance tail's four tile-product kernels are one skeleton: workgroup (i, b) owns tile row i of problem b, its
+// four waves stride the tile columns j, k runs over tiles, four MFMAs of a k-step go into one accumulator.  A kernel is
+// its two operand loaders, the start of j and of k, and what it does with a finished tile.
+struct CovTile { int b, i, w, lr, lc, nf, NTl; };
+// false: nothing to do, the caller returns (uniform) — the inverse / weights kernel has filled the output of a problem
+// whose status is not 0, and tile rows past the free block do not exist
+__device__ __forceinline__ bool cov_tile(CovTile& t, int n, const int* __restrict__ nfree,
+                                         const int* __restrict__ status) {
+  const int lane = threadIdx.x & 63;
+  t.i = blockIdx.x; t.b = blockIdx.y;
+  t.w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  if (status[t.b] != 0) return false;
+  t.nf = nfree ? nfree[t.b] : n;
+  t.NTl = (t.nf + 15) >> 4;
+  if (t.i >= t.NTl) return false;
+  t.lr = lane >> 4; t.lc = lane & 15;
+  return true;
+}
+// la(k, q) / lb(j, k, q): this lane's A[lc][4 q + lr] and B[4 q + lr][lc] of k-tile k;  k0(j): the first k-tile of
+// column j;  store(j, acc): rows lr + 4 g, column lc of the finished tile (i, j).  Sums run over k, then q, ascending.
+template <class LoadA, class LoadB, class K0, class Store>
+__device__ __forceinline__ void cov_tile_product(const CovTile& t, int j0, K0 k0, LoadA la, LoadB lb, Store store) {
+  for (int j = j0 + t.w; j < t.NTl; j += COV_PNW) {
+    v4d acc = {0.0, 0.0, 0.0, 0.0};
+    for (int k = k0(j); k < t.NTl; ++k) {
+      double a[4], bb[4];
+#pragma unroll
+      for (int q = 0; q < 4; ++q) { a[q] = la(k, q); bb[q] = lb(j, k, q); }
+#pragma unroll
+      for (int q = 0; q < 4; ++q) acc = mfma_f64(a[q], bb[q], acc);
+    }
+    store(j, acc);
+  }
+}
+// tile (i, j >= i) of the free block and its mirror image into C through perm: exactly symmetric by construction
+template <bool SCALED>
+__device__ __forceinline__ void cov_scatter_sym(const CovTile& t, int j, v4d acc, double sc, const int* pm, int n,
+                                                double* C) {
+#pragma unroll
+  for (int g = 0; g < 4; ++g) {
+    const int r = 16 * t.i + t.lr + 4 * g, c = 16 * j + t.lc;
+    if (r < t.nf && c < t.nf && r <= c) {            // (i < j: always r < c)
+      const int pr = pm ? pm[r] : r, pc = pm ? pm[c] : c;
+      double v = acc[g];
+      if constexpr (SCALED) v *= sc;
+      C[(long)pr * n + pc] = v;
+      C[(long)pc * n + pr] = v;
+    }
+  }
 }
 
 // ---- product -----------------------------------------------------------------------------------
@@ -273,38 +312,16 @@ __global__ __launch_bounds__(COV_PNT) void cov_product_kernel(int n, int NPAD, c
                                                               const int* __restrict__ perm,
                                                               const int* __restrict__ status,
                                                               double* __restrict__ cov) {
-  const int i = blockIdx.x, b = blockIdx.y, lane = threadIdx.x & 63;
-  const int w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  if (status[b] != 0) return;                        // uniform: the inverse kernel has filled the output
-  const int nf = nfree ? nfree[b] : n;
-  const int NTl = (nf + 15) >> 4;
-  if (i >= NTl) return;
+  CovTile t;
+  if (!cov_tile(t, n, nfree, status)) return;
   const int ld = NPAD;
-  const double* X = Xall + (long)b * NPAD * NPAD;
-  const int* pm = perm ? perm + (long)b * n : nullptr;
-  double* C = cov + (long)b * n * n;
-  const int lr = lane >> 4, lc = lane & 15;
-  for (int j = i + w; j < NTl; j += COV_PNW) {
-    v4d acc = {0.0, 0.0, 0.0, 0.0};
-    const double* xa = X + (long)(16 * i + lc) * ld + lr;
-    const double* xb = X + (long)(16 * j + lc) * ld + lr;
-    for (int k = j; k < NTl; ++k) {
-      double a[4], bb[4];
-#pragma unroll
-      for (int q = 0; q < 4; ++q) { a[q] = xa[16 * k + 4 * q]; bb[q] = xb[16 * k + 4 * q]; }
-#pragma unroll
-      for (int q = 0; q < 4; ++q) acc = cov_mfma(a[q], bb[q], acc);
-    }
-#pragma unroll
-    for (int g = 0; g < 4; ++g) {
-      const int r = 16 * i + lr + 4 * g, c = 16 * j + lc;
-      if (r < nf && c < nf && r <= c) {              // (i < j: always r < c)
-        const int pr = pm ? pm[r] : r, pc = pm ? pm[c] : c;
-        C[(long)pr * n + pc] = acc[g];
-        C[(long)pc * n + pr] = acc[g];
-      }
-    }
-  }
+  const double* X = Xall + (long)t.b * NPAD * NPAD;
+  const int* pm = perm ? perm + (long)t.b * n : nullptr;
+  double* C = cov + (long)t.b * n * n;
+  cov_tile_product(t, t.i, [](int j) { return j; },
+                   [&](int k, int q) { return X[(long)(16 * t.i + t.lc) * ld + t.lr + 16 * k + 4 * q]; },
+                   [&](int j, int k, int q) { return X[(long)(16 * j + t.lc) * ld + t.lr + 16 * k + 4 * q]; },
+                   [&](int j, v4d acc) { cov_scatter_sym<false>(t, j, acc, 1.0, pm, n, C); });
 }
 
 // ---- pseudo-inverse: weights and product ---------------------------------------------------------
@@ -319,8 +336,7 @@ __global__ __launch_bounds__(COV_PNT) void cov_pinv_weights_kernel(int m, int n,
                                                                    int* __restrict__ rank, double* __restrict__ rcond,
                                                                    double* __restrict__ kept_rcond,
                                                                    int* __restrict__ status) {
-  __shared__ double red[COV_PNT];
-  __shared__ int ired[COV_PNT];
+  __shared__ double red[32];
   const int b = blockIdx.x, tid = threadIdx.x;
   const int nf = nfree ? nfree[b] : n;
   const int ld = NPAD;
@@ -352,10 +368,10 @@ __global__ __launch_bounds__(COV_PNT) void cov_pinv_weights_kernel(int m, int n,
   // 2. sigma_max, sigma_min
   double mx = 0.0, mn = __builtin_inf();
   for (int i = tid; i < nf; i += COV_PNT) { mx = fmax(mx, s[i]); mn = fmin(mn, s[i]); }
-  const double smax = cov_wg_max<COV_PNT>(mx, red);
-  const double smin = -cov_wg_max<COV_PNT>(-mn, red);
+  const double smax = block_max(mx, red);
+  const double smin = block_min(mn, red);
   // 3. threshold, rank, weights, smallest kept value
-  const double thresh = COV_EPS * (double)(m > nf ? m : nf) * smax;
+  const double thresh = DBL_EPS * (double)(m > nf ? m : nf) * smax;
   int cnt = 0;
   double kmn = __builtin_inf();
   const int nrow = ((nf + 15) >> 4) << 4;            // (<= NPAD: nf <= n < NPAD)
@@ -364,15 +380,8 @@ __global__ __launch_bounds__(COV_PNT) void cov_pinv_weights_kernel(int m, int n,
     if (i < nf && s[i] > thresh) { wi = 1.0 / (s[i] * s[i]); ++cnt; kmn = fmin(kmn, s[i]); }
     w[i] = wi;
   }
-  const double kmin = -cov_wg_max<COV_PNT>(-kmn, red);
-  __syncthreads();
-  ired[tid] = cnt;
-  __syncthreads();
-  for (int h = COV_PNT / 2; h > 0; h >>= 1) {
-    if (tid < h) ired[tid] += ired[tid + h];
-    __syncthreads();
-  }
-  const int rk = ired[0];
+  const double kmin = block_min(kmn, red);
+  const int rk = block_sum_int(cnt, red);
   if (tid == 0) {
     rank[b] = rk;
     rcond[b] = smax > 0.0 ? smin / smax : 0.0;
@@ -389,47 +398,25 @@ __global__ __launch_bounds__(COV_PNT) void cov_pinv_product_kernel(int n, int NP
                                                                    const int* __restrict__ status,
                                                                    const double* __restrict__ dscale,
                                                                    double* __restrict__ cov) {
-  const int i = blockIdx.x, b = blockIdx.y, lane = threadIdx.x & 63;
-  const int w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  if (status[b] != 0) return;                        // uniform: the weights kernel has filled the output
-  const int nf = nfree ? nfree[b] : n;
-  const int NTl = (nf + 15) >> 4;
-  if (i >= NTl) return;
+  CovTile t;
+  if (!cov_tile(t, n, nfree, status)) return;
   const int ld = NPAD;
-  const double* X = Xall + (long)b * NPAD * NPAD;
-  const double* wt = wall + (long)b * ld;
-  const int* pm = perm ? perm + (long)b * n : nullptr;
-  double* C = cov + (long)b * n * n;
-  const double sc = dscale ? dscale[b] : 1.0;
-  const int lr = lane >> 4, lc = lane & 15;
-  for (int j = i + w; j < NTl; j += COV_PNW) {
-    v4d acc = {0.0, 0.0, 0.0, 0.0};
-    const double* xa = X + (long)lr * ld + 16 * i + lc;   // lanes of one lr: 16 consecutive doubles of a row
-    const double* xb = X + (long)lr * ld + 16 * j + lc;
-    for (int k = 0; k < NTl; ++k) {                  // rows 16 k .. 16 k + 15, ascending
-      double a[4], bb[4];
-#pragma unroll
-      for (int q = 0; q < 4; ++q) {
-        const int r = 16 * k + 4 * q + lr;
-        const double wr = wt[r];
-        const double va = xa[(long)(16 * k + 4 * q) * ld], vb = xb[(long)(16 * k + 4 * q) * ld];
-        a[q] = (r < nf) ? va * wr : 0.0;             // (rows >= nf of a masked problem belong to its active columns)
-        bb[q] = (r < nf) ? vb * wr : 0.0;
-      }
-#pragma unroll
-      for (int q = 0; q < 4; ++q) acc = cov_mfma(a[q], bb[q], acc);
-    }
-#pragma unroll
-    for (int g = 0; g < 4; ++g) {
-      const int r = 16 * i + lr + 4 * g, c = 16 * j + lc;
-      if (r < nf && c < nf && r <= c) {
-        const int pr = pm ? pm[r] : r, pc = pm ? pm[c] : c;
-        const double v = acc[g] * sc;
-        C[(long)pr * n + pc] = v;
-        C[(long)pc * n + pr] = v;
-      }
-    }
-  }
+  const double* X = Xall + (long)t.b * NPAD * NPAD;
+  const double* wt = wall + (long)t.b * ld;
+  const int* pm = perm ? perm + (long)t.b * n : nullptr;
+  double* C = cov + (long)t.b * n * n;
+  const double sc = dscale ? dscale[t.b] : 1.0;
+  // rows 16 k .. 16 k + 15 of Y = diag(w) [rows], ascending; lanes of one lr: 16 consecutive doubles of a row
+  // (rows >= nf of a masked problem belong to its active columns)
+  auto ldY = [&](int ct, int k, int q) {
+    const int r = 16 * k + 4 * q + t.lr;
+    const double v = X[(long)r * ld + 16 * ct + t.lc] * wt[r];
+    return (r < t.nf) ? v : 0.0;
+  };
+  cov_tile_product(t, t.i, [](int) { return 0; },
+                   [&](int k, int q) { return ldY(t.i, k, q); },
+                   [&](int j, int k, int q) { return ldY(j, k, q); },
+                   [&](int j, v4d acc) { cov_scatter_sym<true>(t, j, acc, sc, pm, n, C); });
 }
 
 // ---- row forms through the kept factor (7i) ------------------------------------------------------
@@ -453,34 +440,22 @@ __global__ __launch_bounds__(COV_PNT) void cov_pinv_rowgram_kernel(int n, int NP
                                                                    const int* __restrict__ nfree,
                                                                    const int* __restrict__ status,
                                                                    double* __restrict__ Gall) {
-  const int i = blockIdx.x, b = blockIdx.y, lane = threadIdx.x & 63;
-  const int w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  if (status[b] != 0) return;                        // uniform
-  const int nf = nfree ? nfree[b] : n;
-  const int NTl = (nf + 15) >> 4;
-  if (i >= NTl) return;
-  const int ld = NPAD;
-  const double* W = Wall + (long)b * NPAD * NPAD;
-  double* G = Gall + (long)b * NPAD * NPAD;
-  const int lr = lane >> 4, lc = lane & 15;
-  const int ra = 16 * i + lc;
-  for (int j = w; j < NTl; j += COV_PNW) {
-    const int rb = 16 * j + lc;
-    v4d acc = {0.0, 0.0, 0.0, 0.0};
-    for (int k = 0; k < NTl; ++k) {
-      double a[4], bb[4];
+  CovTile t;
+  if (!cov_tile(t, n, nfree, status)) return;
+  const int ld = NPAD, nf = t.nf;
+  const double* W = Wall + (long)t.b * NPAD * NPAD;
+  double* G = Gall + (long)t.b * NPAD * NPAD;
+  auto ldW = [&](int rt, int k, int q) {             // row 16 rt + lc of W, column 4 q + lr of k-tile k
+    const int r = 16 * rt + t.lc, c = 16 * k + 4 * q + t.lr;
+    return (r < nf && c < nf) ? W[(long)r * ld + c] : 0.0;
+  };
+  cov_tile_product(t, 0, [](int) { return 0; },
+                   [&](int k, int q) { return ldW(t.i, k, q); },
+                   [&](int j, int k, int q) { return ldW(j, k, q); },
+                   [&](int j, v4d acc) {
 #pragma unroll
-      for (int q = 0; q < 4; ++q) {
-        const int c = 16 * k + 4 * q + lr;
-        a[q] = (ra < nf && c < nf) ? W[(long)ra * ld + c] : 0.0;
-        bb[q] = (rb < nf && c < nf) ? W[(long)rb * ld + c] : 0.0;
-      }
-#pragma unroll
-      for (int q = 0; q < 4; ++q) acc = cov_mfma(a[q], bb[q], acc);
-    }
-#pragma unroll
-    for (int g = 0; g < 4; ++g) G[(long)(16 * i + lr + 4 * g) * ld + 16 * j + lc] = acc[g];
-  }
+                     for (int g = 0; g < 4; ++g) G[(long)(16 * t.i + t.lr + 4 * g) * ld + 16 * j + t.lc] = acc[g];
+                   });
 }
 
 __global__ __launch_bounds__(COV_PNT) void cov_pinv_rowfactor_kernel(int n, int NPAD, const double* __restrict__ Wall,
@@ -489,41 +464,33 @@ __global__ __launch_bounds__(COV_PNT) void cov_pinv_rowfactor_kernel(int n, int 
                                                                      const int* __restrict__ nfree,
                                                                      const int* __restrict__ status,
                                                                      double* __restrict__ Yall) {
-  const int i = blockIdx.x, b = blockIdx.y, lane = threadIdx.x & 63;
-  const int w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  if (status[b] != 0) return;                        // uniform
-  const int nf = nfree ? nfree[b] : n;
-  const int NTl = (nf + 15) >> 4;
-  if (i >= NTl) return;
-  const int ld = NPAD;
-  const double* W = Wall + (long)b * NPAD * NPAD;
-  const double* G = Gall + (long)b * NPAD * NPAD;
-  const double* wt = wall + (long)b * ld;
-  double* Y = Yall + (long)b * NPAD * NPAD;
-  const int lr = lane >> 4, lc = lane & 15;
-  const int ra = 16 * i + lc;
+  CovTile t;
+  if (!cov_tile(t, n, nfree, status)) return;
+  const int ld = NPAD, nf = t.nf;
+  const double* W = Wall + (long)t.b * NPAD * NPAD;
+  const double* G = Gall + (long)t.b * NPAD * NPAD;
+  const double* wt = wall + (long)t.b * ld;
+  double* Y = Yall + (long)t.b * NPAD * NPAD;
+  const int ra = 16 * t.i + t.lc;
   const double wa = (ra < nf) ? wt[ra] : 0.0;
-  for (int j = w; j < NTl; j += COV_PNW) {
-    const int cb = 16 * j + lc;
-    v4d acc = {0.0, 0.0, 0.0, 0.0};
-    for (int k = 0; k < NTl; ++k) {
-      double a[4], bb[4];
+  cov_tile_product(t, 0, [](int) { return 0; },
+                   [&](int k, int q) {
+                     const int c = 16 * k + 4 * q + t.lr;            // column of N = row of Y
+                     return (ra < nf && c < nf && c != ra) ? wa * G[(long)ra * ld + c] : 0.0;
+                   },
+                   [&](int j, int k, int q) {
+                     const int c = 16 * k + 4 * q + t.lr, cb = 16 * j + t.lc;
+                     return (c < nf && cb < nf) ? wt[c] * W[(long)c * ld + cb] : 0.0;
+                   },
+                   [&](int j, v4d acc) {
+                     const int cb = 16 * j + t.lc;
 #pragma unroll
-      for (int q = 0; q < 4; ++q) {
-        const int c = 16 * k + 4 * q + lr;           // column of N = row of Y
-        a[q] = (ra < nf && c < nf && c != ra) ? wa * G[(long)ra * ld + c] : 0.0;
-        bb[q] = (c < nf && cb < nf) ? wt[c] * W[(long)c * ld + cb] : 0.0;
-      }
-#pragma unroll
-      for (int q = 0; q < 4; ++q) acc = cov_mfma(a[q], bb[q], acc);
-    }
-#pragma unroll
-    for (int g = 0; g < 4; ++g) {
-      const int r = 16 * i + lr + 4 * g;
-      const double y = (r < nf && cb < nf) ? wt[r] * W[(long)r * ld + cb] : 0.0;
-      Y[(long)r * ld + cb] = (r < nf && cb < nf) ? y - acc[g] : 0.0;
-    }
-  }
+                     for (int g = 0; g < 4; ++g) {
+                       const int r = 16 * t.i + t.lr + 4 * g;
+                       const double y = (r < nf && cb < nf) ? wt[r] * W[(long)r * ld + cb] : 0.0;
+                       Y[(long)r * ld + cb] = (r < nf && cb < nf) ? y - acc[g] : 0.0;
+                     }
+                   });
 }
 
 static constexpr int COV_RNT = 256;               // four waves
@@ -591,7 +558,7 @@ __global__ __launch_bounds__(COV_RNT) void cov_rows_kernel(int rows, int n, int 
             bv[q] = (r < nf && c < nf) ? X[(long)r * ld + c] : 0.0;
           }
 #pragma unroll
-          for (int q = 0; q < 4; ++q) acc[jj] = cov_mfma(av[q], bv[q], acc[jj]);
+          for (int q = 0; q < 4; ++q) acc[jj] = mfma_f64(av[q], bv[q], acc[jj]);
         }
       }
     }

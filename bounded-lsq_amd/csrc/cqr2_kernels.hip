@@ -204,12 +204,12 @@ __device__ __forceinline__ void cqr2_wave(const Cqr2Args& a, double* lds, int b)
           const double a0 = fa[k & 1][2 * s], a1 = fa[k & 1][2 * s + 1];
           if constexpr (k < T0) {
             if (FULL || has0) {
-              acc[0][0] = gmfma(a0, B0[k][s], acc[0][0]);
-              acc[1][0] = gmfma(a1, B0[k][s], acc[1][0]);
+              acc[0][0] = mfma_f64(a0, B0[k][s], acc[0][0]);
+              acc[1][0] = mfma_f64(a1, B0[k][s], acc[1][0]);
             }
           }
-          acc[0][1] = gmfma(a0, B1[k][s], acc[0][1]);
-          acc[1][1] = gmfma(a1, B1[k][s], acc[1][1]);
+          acc[0][1] = mfma_f64(a0, B1[k][s], acc[0][1]);
+          acc[1][1] = mfma_f64(a1, B1[k][s], acc[1][1]);
         }
         __builtin_amdgcn_sched_barrier(0);
       }
@@ -344,7 +344,7 @@ __global__ __launch_bounds__(64 * CQ_CW) void cqr2_combine_kernel(Cqr2Args a, co
       bv[s] = t;
     }
 #pragma unroll
-    for (int s = 0; s < 4; ++s) out = gmfma(av[s], bv[s], out);
+    for (int s = 0; s < 4; ++s) out = mfma_f64(av[s], bv[s], out);
   }
 #pragma unroll
   for (int g = 0; g < 4; ++g) {

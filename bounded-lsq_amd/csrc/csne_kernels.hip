@@ -301,7 +301,7 @@ __global__ __launch_bounds__(CS_NT, BLSQ_CSM_OCC) void csne_pass_mfma_kernel(Csn
     v4d acc[2] = {v4d{0.0, 0.0, 0.0, 0.0}, v4d{0.0, 0.0, 0.0, 0.0}};
     const double* Xa = X + lc * S + lr;                   // A[row = lc][k = lr] of k-step 0
 #pragma unroll
-    for (int s_ = 0; s_ < NK; ++s_) acc[s_ & 1] = gmfma(Xa[4 * s_], Vb[s_], acc[s_ & 1]);
+    for (int s_ = 0; s_ < NK; ++s_) acc[s_ & 1] = mfma_f64(Xa[4 * s_], Vb[s_], acc[s_ & 1]);
     double* Ew = E + ((size_t)(ti & 1) * CS_NW + w) * (4 * WAVE);
 #pragma unroll
     for (int g = 0; g < 4; ++g) Ew[g * WAVE + lane] = acc[0][g] + acc[1][g];
@@ -320,7 +320,7 @@ __global__ __launch_bounds__(CS_NT, BLSQ_CSM_OCC) void csne_pass_mfma_kernel(Csn
 #pragma unroll
     for (int g = 0; g < 4; ++g)
 #pragma unroll
-      for (int c = 0; c < NST; ++c) yacc[c] = gmfma(u[g], Xb[4 * g * S + 16 * c], yacc[c]);
+      for (int c = 0; c < NST; ++c) yacc[c] = mfma_f64(u[g], Xb[4 * g * S + 16 * c], yacc[c]);
   };
   static_for<0, PF>([&](auto pc) __attribute__((always_inline)) {
     if (decltype(pc)::value < ntile) request(decltype(pc)::value, pc);
@@ -607,7 +607,7 @@ __global__ __launch_bounds__(256) void csne_select_kernel(CsneState cs, CsneGate
     // bound: s_min(R)^2 >= min_j h_jj / K2
     const int mx = go.mrank > n ? go.mrank : n;
     const double smin_lb = mn / sqrt(kb), smax_ub = sqrt(sm);
-    ok = ok && is_finite(sm) && sm > 0.0 && smin_lb > LM_GATE_MARGIN * LM_EPS * mx * smax_ub;
+    ok = ok && is_finite(sm) && sm > 0.0 && smin_lb > LM_GATE_MARGIN * DBL_EPS * mx * smax_ub;
     if (ok) {
       cs.flag[b] = 1; path[b] = 0; tree_mask[b] = 0;
       if (go.use_lm) {

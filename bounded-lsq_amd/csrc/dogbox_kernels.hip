@@ -12,63 +12,11 @@
 #include "blsq_device.h"
 #include "blsq_kernels.h"
 #include "blsq_launch.h"
+#include "mv_ops.h"
 
 namespace blsq {
 
 static constexpr int DG_NT = 256;
-static constexpr int DG_NW = DG_NT / WAVE;
-static constexpr double EPS = 2.220446049250313e-16;
-
-// u = R s  (R upper triangular n x n, row-major, stride ld): one wave per row, eight rows per wave pass — their
-// loads in flight together (a row at a time was a memory round trip per row: 16 in a row for n = 64, most of the step
-// kernel's 19 us), their eight totals by one transposed butterfly (wave_sum16: the tree of wave_sum for each).  Per row
-// the products are accumulated in the same order as before: same bits.
-__device__ static void tri_matvec_d(const double* R, int n, int ld, const double* svec,
-                                    double* u) {
-  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-  constexpr int RB = 8;
-  for (int i0 = w; i0 < n; i0 += DG_NW * RB) {
-    double acc[RB];
-#pragma unroll
-    for (int r = 0; r < RB; ++r) acc[r] = 0.0;
-    for (int jj = 0; i0 + jj < n; jj += WAVE) {             // (wave-uniform: the longest row, i0)
-      double rv[RB];
-#pragma unroll
-      for (int r = 0; r < RB; ++r) {
-        const int i = i0 + r * DG_NW;
-        const int ic = (i < n) ? i : n - 1;
-        const int j = ic + lane + jj;
-        rv[r] = R[(long)ic * ld + ((j < n) ? j : n - 1)];
-      }
-#pragma unroll
-      for (int r = 0; r < RB; ++r) {
-        const int i = i0 + r * DG_NW;
-        const int j = i + lane + jj;
-        if (i < n && j < n) acc[r] = fma(rv[r], svec[j], acc[r]);
-      }
-    }
-    double v[16];
-#pragma unroll
-    for (int r = 0; r < RB; ++r) { v[r] = acc[r]; v[8 + r] = 0.0; }
-    wave_sum16(v);
-    const int idx = wave_sum16_index(lane), ri = i0 + (idx & 7) * DG_NW;
-    if (lane < 16 && idx < 8 && ri < n) u[ri] = v[0];
-  }
-  __syncthreads();
-}
-
-// u = M s for a dense nf x nf block (Jacobi rows of a factor that went through the SVD)
-__device__ static void full_matvec_d(const double* M, int n, int ld, const double* svec, double* u) {
-  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-  for (int i = w; i < n; i += DG_NW) {
-    const double* row = M + (long)i * ld;
-    double acc = 0.0;
-    for (int j = lane; j < n; j += WAVE) acc = fma(row[j], svec[j], acc);
-    acc = wave_sum(acc);
-    if (lane == 0) u[i] = acc;
-  }
-  __syncthreads();
-}
 
 // ------------------------------------------------------------------ prep --
 __global__ __launch_bounds__(DG_NT) void dog_prep_kernel(DogState st, int jac_scaling, int from_gram,
@@ -162,7 +110,7 @@ __global__ __launch_bounds__(DG_NT) void dog_prep_kernel(DogState st, int jac_sc
     S[(long)row * ld + q] = (col >= row) ? Rt[(long)row * ld + col] : 0.0;
   }
   // Cauchy step (dogbox.py:198-199):  -(g.g)/(Jg.Jg) * g_free
-  tri_matvec_d(Rt, n, ld, gm, u);
+  tri_matvec<DG_NT, 8>(Rt, nullptr, n, ld, gm, u);
   double gg = 0.0, uu = 0.0;
   for (int j = tid; j < n; j += DG_NT) { gg += gm[j] * gm[j]; uu += u[j] * u[j]; }
   gg = block_sum(gg, red);
@@ -195,7 +143,7 @@ __global__ __launch_bounds__(DG_NT) void dog_solve_kernel(DogState st, const int
   const double* uf = st.uf + vo;
   double* coef = sh;
   const int mx = (st.m > nf) ? st.m : nf;
-  const double cut = (EPS * mx) * st.srange[2 * b];          // rcond * s_max
+  const double cut = (DBL_EPS * mx) * st.srange[2 * b];          // rcond * s_max
   for (int i = tid; i < nf; i += DG_NT)
     coef[i] = (sv[i] > cut) ? (uf[i] / sv[i]) / sv[i] : 0.0;
   __syncthreads();
@@ -353,7 +301,7 @@ __global__ __launch_bounds__(DG_NT) void dog_step_kernel(DogState st, const doub
     // multiple of g: not in the small singular subspace)
     //     |J s|^2 = a^2 |X c|^2 - 2 a t c.g_free - t^2 p.g_free
     const double* Xf = st.X + (long)b * ld * ld;
-    tri_matvec_d(Xf, nf, ld, cauchy, u);
+    tri_matvec<DG_NT, 8>(Xf, nullptr, nf, ld, cauchy, u);
     double cc = 0.0, cg = 0.0, pg = 0.0;
     for (int q = tid; q < nf; q += DG_NT) {
       const double gq = st.g[vo + fidx[q]];
@@ -365,15 +313,15 @@ __global__ __launch_bounds__(DG_NT) void dog_step_kernel(DogState st, const doub
     // normal-equations path: |J_free s|^2 = |X s|^2 (X: triangle of the free columns, or its Jacobi
     // rows), Js.f = s.g
     const double* Xf = st.X + (long)b * ld * ld;
-    if (st.fast && st.fast[b]) tri_matvec_d(Xf, nf, ld, stp, u);
-    else full_matvec_d(Xf, nf, ld, stp, u);
+    if (st.fast && st.fast[b]) tri_matvec<DG_NT, 8>(Xf, nullptr, nf, ld, stp, u);
+    else full_matvec<DG_NT, 1>(Xf, nf, ld, stp, u);
     for (int q = tid; q < nf; q += DG_NT) { uu += u[q] * u[q]; uc += stp[q] * st.g[vo + fidx[q]]; }
   } else {
     for (int j = tid; j < n; j += DG_NT) full[j] = 0.0;
     __syncthreads();
     for (int q = tid; q < nf; q += DG_NT) full[fidx[q]] = stp[q];
     __syncthreads();
-    tri_matvec_d(Rt, n, ld, full, u);
+    tri_matvec<DG_NT, 8>(Rt, nullptr, n, ld, full, u);
     for (int i = tid; i < n; i += DG_NT) { uu += u[i] * u[i]; uc += u[i] * Rt[(long)i * ld + n]; }
   }
   uu = block_sum(uu, red);

@@ -1,5 +1,5 @@
 // Shared by gram_kernels.hip (the Gram kernels), chol_reg.hip (N <= 80: Cholesky and fused Newton rounds),
-// chol_rl.hip (N > 80: Cholesky) and cert_kernels.hip (certificate): launch geometry, the FP64 MFMA wrapper, the
+// chol_rl.hip (N > 80: Cholesky) and cert_kernels.hip (certificate): launch geometry, the
 // explicit LDS read helpers with counted waits and the column scales of the Cholesky kernels.
 #pragma once
 #include <stdlib.h>
@@ -23,15 +23,8 @@ __device__ __forceinline__ int reg_problem(int w, int wv) { return (((w >> 3) * 
 static inline unsigned reg_grid(int B) { return (unsigned)(((B + 8 * REG_NW - 1) / (8 * REG_NW)) * 8); }
 static constexpr double GRAM_SMIN = GRAM_SMIN_PROVEN;   // early reject: a pivot of R' below what the certificate could accept
 
-__device__ __forceinline__ v4d gmfma(double a, double b, v4d c) {
-  return __builtin_amdgcn_mfma_f64_16x16x4f64(a, b, c, 0, 0, 0);
-}
-
-// LDS byte address of a pointer into the dynamic LDS array, and an explicit 8-byte LDS read whose
-// completion the CALLER waits for (counted s_waitcnt lgkmcnt)
-__device__ __forceinline__ unsigned lds_addr(const double* p) {
-  return (unsigned)(unsigned long)(lptr_t*)p;
-}
+// An explicit 8-byte LDS read (byte address: lds_addr, blsq_device.h) whose completion the CALLER waits for
+// (counted s_waitcnt lgkmcnt)
 __device__ __forceinline__ void lds_read64(double& dst, unsigned byte_addr) {
   asm volatile("ds_read_b64 %0, %1" : "=v"(dst) : "v"(byte_addr));
 }

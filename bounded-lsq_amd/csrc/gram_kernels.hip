@@ -170,7 +170,7 @@ __global__ __launch_bounds__(GR_NT, (SLOTS <= 8 ? 4 : 2)) void gram_kernel(GramA
         } else {
           asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(fa[q % 3]), "+v"(fb[q % 3]));
         }
-        acc[q % SLOTS] = gmfma(fa[q % 3], fb[q % 3], acc[q % SLOTS]);
+        acc[q % SLOTS] = mfma_f64(fa[q % 3], fb[q % 3], acc[q % SLOTS]);
       }
       if (more) commit(row0 + GR_RC, h, Xn);
     }
@@ -390,8 +390,8 @@ __device__ __forceinline__ void gram16_wave(const GramArgs& a, double* lds) {
       // 17 MFMAs; the next k-step's fragments are requested two per MFMA behind the first ones
       static_for<0, N0 + N1>([&](auto it) {
         constexpr int t = decltype(it)::value;
-        if constexpr (t < N0) acc0[t] = gmfma(fr[cur][0], fr[cur][t], acc0[t]);
-        else acc1[t - N0] = gmfma(fr[cur][A1], fr[cur][A1 + (t - N0)], acc1[t - N0]);
+        if constexpr (t < N0) acc0[t] = mfma_f64(fr[cur][0], fr[cur][t], acc0[t]);
+        else acc1[t - N0] = mfma_f64(fr[cur][A1], fr[cur][A1 + (t - N0)], acc1[t - N0]);
         if constexpr (s < 7) {
           if constexpr (2 * t < NF)
             lds_read64_off<8 * (4 * (s + 1) * LDX + 16 * (W + 2 * t))>(fr[nxt][2 * t], xb);
@@ -604,8 +604,8 @@ __device__ __forceinline__ void gram8_wave(const GramArgs& a, double* lds) {
       wait_set(fr[cur]);
       static_for<0, N0 + N1>([&](auto it) {
         constexpr int t = decltype(it)::value;
-        if constexpr (t < N0) acc0[t] = gmfma(fr[cur][0], fr[cur][t], acc0[t]);
-        else acc1[t - N0] = gmfma(fr[cur][A1], fr[cur][A1 + (t - N0)], acc1[t - N0]);
+        if constexpr (t < N0) acc0[t] = mfma_f64(fr[cur][0], fr[cur][t], acc0[t]);
+        else acc1[t - N0] = mfma_f64(fr[cur][A1], fr[cur][A1 + (t - N0)], acc1[t - N0]);
         if constexpr (q < 3 && t < NF)
           lds_read64_off<8 * (4 * (2 * (q + 1) + K) * LDX + 16 * (P + t))>(fr[nxt][t], xb);
       });
@@ -752,7 +752,7 @@ __global__ __launch_bounds__(64 * NWD, (NTT <= 2 ? 4 : 2)) void gram_direct_kern
 #pragma unroll
       for (int i = 0; i < NTT; ++i)
 #pragma unroll
-        for (int j = i; j < NTT; ++j, ++t) acc[t] = gmfma(fr[u][i], fr[u][j], acc[t]);
+        for (int j = i; j < NTT; ++j, ++t) acc[t] = mfma_f64(fr[u][i], fr[u][j], acc[t]);
       if (RHS) {
 #pragma unroll
         for (int c = 0; c < NTT; ++c) gf[c] = fma(fr[u][c], fv[u], gf[c]);
@@ -798,7 +798,7 @@ __global__ __launch_bounds__(64 * NWD, (NTT <= 2 ? 4 : 2)) void gram_direct_kern
 #pragma unroll
           for (int i = 0; i < NTT; ++i)
 #pragma unroll
-            for (int j = i; j < NTT; ++j, ++t) acc[t] = gmfma(fr[u][i], fr[u][j], acc[t]);
+            for (int j = i; j < NTT; ++j, ++t) acc[t] = mfma_f64(fr[u][i], fr[u][j], acc[t]);
 #pragma unroll
           for (int c = 0; c < NTT; ++c) gf[c] = fma(fr[u][c], fv[u], gf[c]);
           gff = fma(fv[u], fv[u], gff);
@@ -965,7 +965,7 @@ __global__ __launch_bounds__(G1_NT) void gram1_kernel(GramArgs a, int chunks, in
         const long ro = (long)rowof(sn) * ldJ;
         fa[u] = pa[ro];
         fb[u] = pb[ro];
-        acc = gmfma(av, bv, acc);
+        acc = mfma_f64(av, bv, acc);
       }
     }
 #pragma unroll

@@ -286,7 +286,7 @@ __global__ __launch_bounds__(JAC_NT) void jacobi_rows_kernel(JacobiArgs a) {
   double* dsc = sq + NROW;                   // [NROW] fast-rotation scale of each LDS row
   double* idsc = dsc + NROW;                 // [NROW] its inverse
   double* cz = idsc + NROW;                  // [NROW] carried entry (column n of the row)
-  const double tol = sqrt((double)n) * 2.220446049250313e-16;
+  const double tol = sqrt((double)n) * DBL_EPS;
   const double tol2 = tol * tol;
   const int nb = (n + RB - 1) / RB;          // row blocks (last may be partial: zero rows)
   const int NT2 = RB / 2;                    // 2-row tiles per block (<= 16 = JAC_SLOTS)

@@ -27,7 +27,7 @@
 
 namespace blsq {
 
-// (LM_EPS, LM_GATE_MARGIN: blsq_kernels.h)
+// (DBL_EPS: blsq_device.h; LM_GATE_MARGIN: blsq_kernels.h)
 
 // (phases and the sc[] / st[] slots: blsq_kernels.h)
 
@@ -68,7 +68,7 @@ __global__ __launch_bounds__(TRI_NT, 4) void lm_gate_kernel(LmState lm, int enab
   if (ok && lm.path && lm.colinfo && (lm.path[b] == 0 || qr_bound)) {
     const double mn = lm.colinfo[2 * (long)b], sm = lm.colinfo[2 * (long)b + 1];
     const double smin_lb = (qr_bound ? 1.0 / sqrt(lm.k2[b]) : GRAM_SMIN_PROVEN) * mn, smax_ub = sqrt(sm);
-    if (is_finite(sm) && sm > 0.0 && smin_lb > LM_GATE_MARGIN * LM_EPS * lm.m * smax_ub) {
+    if (is_finite(sm) && sm > 0.0 && smin_lb > LM_GATE_MARGIN * DBL_EPS * lm.m * smax_ub) {
       if (tid == 0) {
         lm.fast[b] = 1;
         lm.ncols_jac[b] = 0;
@@ -126,7 +126,7 @@ __global__ __launch_bounds__(TRI_NT, 4) void lm_gate_kernel(LmState lm, int enab
       for (int i = tid; i < n; i += TRI_NT) v[i] *= inv;
       __syncthreads();
     }
-    if (!(smin > LM_GATE_MARGIN * LM_EPS * lm.m * smax) || !is_finite(smax) || smax == 0.0) ok = 0;
+    if (!(smin > LM_GATE_MARGIN * DBL_EPS * lm.m * smax) || !is_finite(smax) || smax == 0.0) ok = 0;
   }
   if (tid == 0) {
     lm.fast[b] = ok;
@@ -212,7 +212,7 @@ __global__ __launch_bounds__(TRI_NT, 4) void dog_gate_solve_kernel(DogState st, 
     const int* fidx = st.free_idx + (long)b * ld;
     for (int q = tid; q < nf; q += TRI_NT) v[q] = st.g[(long)b * ld + fidx[q]];
     __syncthreads();
-    tri_mv(R, nf, ld, v, u);
+    tri_matvec<TRI_NT, 4>(R, nullptr, nf, ld, v, u);
     const double gg = tri_dot(v, v, nf, red);
     const double uu = tri_dot(u, u, nf, red);
     const double fac = -gg / uu;
@@ -239,15 +239,15 @@ __global__ __launch_bounds__(TRI_NT, 4) void dog_gate_solve_kernel(DogState st, 
       // (a problem on the CSNE tier: the proven bound of ITS computed system instead of the gate's)
       const double sminp = (st.csne && st.csne[b] && st.csne_k2 && st.csne_k2[b] > 0.0) ? 1.0 / sqrt(st.csne_k2[b])
                                                                                        : GRAM_SMIN_PROVEN;
-      sure = is_finite(sm) && sm > 0.0 && (sminp * mn > LM_GATE_MARGIN * LM_EPS * mx * sqrt(sm));
+      sure = is_finite(sm) && sm > 0.0 && (sminp * mn > LM_GATE_MARGIN * DBL_EPS * mx * sqrt(sm));
     }
     if (!sure) {
     for (int i = tid; i < nf; i += TRI_NT) v[i] = (i & 1) ? -s0 : s0;
     __syncthreads();
     double smax = 0.0, smin = 0.0;
     for (int it = 0; it < 2; ++it) {
-      tri_mv(R, nf, ld, v, u);
-      tri_mtv(R, nf, ld, u, v);
+      tri_matvec<TRI_NT, 4>(R, nullptr, nf, ld, v, u);
+      tri_mtv<TRI_NT>(R, nf, ld, u, v);
       const double nv = sqrt(tri_dot(v, v, nf, red));
       smax = sqrt(nv);
       const double inv = (nv > 0.0) ? 1.0 / nv : 0.0;
@@ -265,7 +265,7 @@ __global__ __launch_bounds__(TRI_NT, 4) void dog_gate_solve_kernel(DogState st, 
       for (int i = tid; i < nf; i += TRI_NT) v[i] *= inv;
       __syncthreads();
     }
-    if (!(smin > LM_GATE_MARGIN * LM_EPS * mx * smax) || !is_finite(smax) || smax == 0.0) ok = 0;
+    if (!(smin > LM_GATE_MARGIN * DBL_EPS * mx * smax) || !is_finite(smax) || smax == 0.0) ok = 0;
     }
   }
   if (ok) {

@@ -28,7 +28,6 @@ namespace blsq {
 static constexpr int LOSS_NT = 256;
 static constexpr int LOSS_MAX_ROWS = 1024;       // rows of one scale workgroup (LDS: 8 KiB of w)
 static constexpr int LOSS_TARGET_ELEMS = 8192;   // J doubles per scale workgroup (64 KiB read + 64 KiB written)
-static constexpr double LOSS_EPS = 2.220446049250313e-16;
 
 // rho0 / rho1 / rho2 at z of the five losses (scipy's IMPLEMENTED_LOSSES, from their definitions):
 //   linear  rho(z) = z
@@ -127,7 +126,7 @@ __global__ __launch_bounds__(LOSS_NT) void loss_scale_kernel(int m, int n, int l
     loss_rho12(loss, z, r1, r2);
     r2 = r2 / fs2;
     double js = r1 + (2.0 * r2) * (fi * fi);
-    if (js < LOSS_EPS) js = LOSS_EPS;
+    if (js < DBL_EPS) js = DBL_EPS;
     const double w = sqrt(js);
     fsc[row0 + r] = fi * (r1 / w);
     wsh[r] = w;

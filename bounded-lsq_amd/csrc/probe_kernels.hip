@@ -26,7 +26,7 @@ __global__ __launch_bounds__(512) void mfma_f64_probe_kernel(int iters, double* 
   for (int it = 0; it < iters; ++it) {
 #pragma unroll
     for (int t = 0; t < NACC; ++t)
-      acc[t] = __builtin_amdgcn_mfma_f64_16x16x4f64(a[t], b[t], acc[t], 0, 0, 0);
+      acc[t] = mfma_f64(a[t], b[t], acc[t]);
   }
   double s = 0.0;
 #pragma unroll

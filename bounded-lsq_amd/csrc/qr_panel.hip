@@ -63,9 +63,6 @@ __device__ unsigned long long g_cqr_stats[2];
 static constexpr int QR_NT = 512;
 static constexpr int QR_NW = QR_NT / WAVE;
 
-__device__ __forceinline__ v4d mfma_f64(double a, double b, v4d c) {
-  return __builtin_amdgcn_mfma_f64_16x16x4f64(a, b, c, 0, 0, 0);
-}
 
 // copy one 2 KB tile (two DMA instructions); lane16 = 16 * lane id (bytes)
 __device__ __forceinline__ void glds_tile(const double* src_tile_uniform, double* lds_tile,

@@ -12,12 +12,12 @@
 #include "blsq_device.h"
 #include "blsq_kernels.h"
 #include "blsq_launch.h"
+#include "mv_ops.h"
 
 namespace blsq {
 
 static constexpr int NS_NT = 256;
 static constexpr int NS_NW = NS_NT / WAVE;
-static constexpr double EPS = 2.220446049250313e-16;
 
 // ------------------------------------------------------------------ prep --
 __global__ __launch_bounds__(NS_NT) void trf_prep_kernel(TrfState st, int jac_scaling, int from_gram,
@@ -182,171 +182,8 @@ __device__ double step_to_bound_dev(const StepCtx& c, const double* xs,
   return block_min(tmin, c.red);
 }
 
-// u = R_h s = (R D) s  (R upper triangular, row-major, stride ld; D = diag(dvec)): one wave per row.
-__device__ void tri_matvec(const double* R, const double* dvec, int n, int ld, const double* svec,
-                           double* u) {
-  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-  // Eight rows per wave pass with unconditional (clamped) loads: R does not fit any cache for a
-  // whole batch, so the loads of a pass must be in flight together — one row at a time every
-  // iteration would pay a full memory round trip.  Per row the accumulation order is unchanged.
-  constexpr int RB = 8;
-  for (int i0 = w; i0 < n; i0 += NS_NW * RB) {
-    double acc[RB];
-#pragma unroll
-    for (int r = 0; r < RB; ++r) acc[r] = 0.0;
-    for (int jj = 0; i0 + lane + jj < n; jj += WAVE) {       // trip count of the longest row (i0)
-      double rv[RB];
-#pragma unroll
-      for (int r = 0; r < RB; ++r) {
-        const int i = i0 + r * NS_NW;
-        const int ic = (i < n) ? i : n - 1;
-        const int j = ic + lane + jj;
-        rv[r] = R[(long)ic * ld + ((j < n) ? j : n - 1)];
-      }
-#pragma unroll
-      for (int r = 0; r < RB; ++r) {
-        const int i = i0 + r * NS_NW;
-        const int j = i + lane + jj;
-        // (R[i][j] * d[j]) * s[j]: the same roundings as a materialised R_h = R D
-        if (i < n && j < n) acc[r] = fma(dvec ? rv[r] * dvec[j] : rv[r], svec[j], acc[r]);
-      }
-    }
-    // (the eight row totals by one transposed butterfly: the tree of wave_sum for each of them, see tri_matvec3)
-    static_assert(RB == 8, "one sixteen-value reduction");
-    double v[16];
-#pragma unroll
-    for (int r = 0; r < RB; ++r) { v[r] = acc[r]; v[8 + r] = 0.0; }
-    wave_sum16(v);
-    const int idx = wave_sum16_index(lane), ri = i0 + (idx & 7) * NS_NW;
-    if (lane < 16 && idx < 8 && ri < n) u[ri] = v[0];
-  }
-  __syncthreads();
-}
-
-// u = M s for a DENSE n x n block (row-major, stride ld): the Jacobi rows s_i v_i^T of a problem whose
-// factor went through the SVD.  One wave per row.
-__device__ void full_matvec(const double* M, int n, int ld, const double* svec, double* u) {
-  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-  constexpr int RB = 4;
-  for (int i0 = w; i0 < n; i0 += NS_NW * RB) {
-    double acc[RB];
-#pragma unroll
-    for (int r = 0; r < RB; ++r) acc[r] = 0.0;
-    for (int jj = lane; jj < n; jj += WAVE) {
-      double rv[RB];
-#pragma unroll
-      for (int r = 0; r < RB; ++r) {
-        const int i = i0 + r * NS_NW;
-        rv[r] = M[(long)((i < n) ? i : n - 1) * ld + jj];
-      }
-#pragma unroll
-      for (int r = 0; r < RB; ++r) acc[r] = fma(rv[r], svec[jj], acc[r]);
-    }
-#pragma unroll
-    for (int r = 0; r < RB; ++r) {
-      const int i = i0 + r * NS_NW;
-      const double t = wave_sum(acc[r]);
-      if (lane == 0 && i < n) u[i] = t;
-    }
-  }
-  __syncthreads();
-}
-
-// Three products with ONE pass over the matrix (the reflective branch needs J_h p_h, J_h r_h and
-// J_h (-g_h); the matrix — half a megabyte per problem at n = 256 — does not stay in any cache
-// between separate passes):  u1 = M s1,  u2 = M s2 (s2 == nullptr: skipped),  u3 = M (-g3).
-// Per row and product exactly the operations of tri_matvec / full_matvec, in the same order.
-__device__ void tri_matvec3(const double* R, const double* dvec, int n, int ld, const double* s1,
-                            double* u1, const double* s2, double* u2, const double* g3, double* u3) {
-  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-  // Four rows x four 64-column chunks per wave pass: sixteen loads in flight (a pass of eight rows x one chunk
-  // was 32 dependent memory round trips for ONE 256-variable problem — 38 of the step kernel's 52 us,
-  // tools/step_stamps.py).  Per row the products are accumulated chunk after chunk as before: same bits.
-  constexpr int RB = 8, JU = 1;
-  for (int i0 = w; i0 < n; i0 += NS_NW * RB) {
-    double a1[RB], a2[RB], a3[RB];
-#pragma unroll
-    for (int r = 0; r < RB; ++r) { a1[r] = 0.0; a2[r] = 0.0; a3[r] = 0.0; }
-    for (int jj = 0; i0 + jj < n; jj += WAVE * JU) {        // (wave-uniform: the longest row, i0)
-      double rv[JU][RB];
-#pragma unroll
-      for (int q = 0; q < JU; ++q) {
-#pragma unroll
-        for (int r = 0; r < RB; ++r) {
-          const int i = i0 + r * NS_NW;
-          const int ic = (i < n) ? i : n - 1;
-          const int j = ic + lane + jj + WAVE * q;
-          rv[q][r] = R[(long)ic * ld + ((j < n) ? j : n - 1)];
-        }
-      }
-#pragma unroll
-      for (int q = 0; q < JU; ++q) {
-#pragma unroll
-        for (int r = 0; r < RB; ++r) {
-          const int i = i0 + r * NS_NW;
-          const int j = i + lane + jj + WAVE * q;
-          if (i < n && j < n) {
-            const double rd = dvec ? rv[q][r] * dvec[j] : rv[q][r];
-            a1[r] = fma(rd, s1[j], a1[r]);
-            if (s2) a2[r] = fma(rd, s2[j], a2[r]);
-            a3[r] = fma(rd, -g3[j], a3[r]);
-          }
-        }
-      }
-    }
-    // The 24 row totals by two transposed butterflies (wave_sum16: the same tree as wave_sum for every one of them — xor 1,
-    // 2, 4, 8 inside the 16-lane rows, then (r0 + r16) + (r32 + r48) — in 15 exchanges per sixteen totals instead of 64).
-    static_assert(RB == 8, "two sixteen-value reductions");
-    double v[16];
-    const int idx = wave_sum16_index(lane), ri = i0 + (idx & 7) * NS_NW;
-#pragma unroll
-    for (int r = 0; r < RB; ++r) { v[r] = a1[r]; v[8 + r] = s2 ? a2[r] : 0.0; }
-    wave_sum16(v);
-    if (lane < 16 && ri < n) {
-      if (idx < 8) u1[ri] = v[0];
-      else if (s2) u2[ri] = v[0];
-    }
-#pragma unroll
-    for (int r = 0; r < RB; ++r) { v[r] = a3[r]; v[8 + r] = 0.0; }
-    wave_sum16(v);
-    if (lane < 16 && idx < 8 && ri < n) u3[ri] = v[0];
-  }
-  __syncthreads();
-}
-__device__ void full_matvec3(const double* M, int n, int ld, const double* s1, double* u1,
-                             const double* s2, double* u2, const double* g3, double* u3) {
-  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-  constexpr int RB = 4;
-  for (int i0 = w; i0 < n; i0 += NS_NW * RB) {
-    double a1[RB], a2[RB], a3[RB];
-#pragma unroll
-    for (int r = 0; r < RB; ++r) { a1[r] = 0.0; a2[r] = 0.0; a3[r] = 0.0; }
-    for (int jj = lane; jj < n; jj += WAVE) {
-      double rv[RB];
-#pragma unroll
-      for (int r = 0; r < RB; ++r) {
-        const int i = i0 + r * NS_NW;
-        rv[r] = M[(long)((i < n) ? i : n - 1) * ld + jj];
-      }
-#pragma unroll
-      for (int r = 0; r < RB; ++r) {
-        a1[r] = fma(rv[r], s1[jj], a1[r]);
-        if (s2) a2[r] = fma(rv[r], s2[jj], a2[r]);
-        a3[r] = fma(rv[r], -g3[jj], a3[r]);
-      }
-    }
-#pragma unroll
-    for (int r = 0; r < RB; ++r) {
-      const int i = i0 + r * NS_NW;
-      const double t1 = wave_sum(a1[r]);
-      const double t2 = s2 ? wave_sum(a2[r]) : 0.0;
-      const double t3 = wave_sum(a3[r]);
-      if (lane == 0 && i < n) { u1[i] = t1; if (s2) u2[i] = t2; u3[i] = t3; }
-    }
-  }
-  __syncthreads();
-}
-
+// Two roundings per term, as np.dot of the reference rounds a product before it is added (this file does not
+// contract): NOT tri_dot (tri_ops.h), which fuses.  The matrix-vector products are mv_ops.h's.
 __device__ double dot_dev(const double* a, const double* b, int n, double* red) {
   double acc = 0.0;
   for (int j = threadIdx.x; j < n; j += NS_NT) acc += a[j] * b[j];
@@ -437,15 +274,15 @@ __global__ __launch_bounds__(NS_NT) void trf_step_kernel(TrfState st, const int*
   // ---------------- solve_lsq_trust_region (trust_region.py:56-152) --------
   const double smax = st.srange[2 * b], smin = st.srange[2 * b + 1];
   bool full_rank = false;
-  if (m >= n) full_rank = smin > EPS * m * smax;
+  if (m >= n) full_rank = smin > DBL_EPS * m * smax;
   double alpha = 0.0;
   int n_iter = 0;
   bool have_p = false;
   const bool fast = lm_fast && lm_fast[b];       // SVD-free path already produced p (lm_kernels.hip)
   auto model_mv = [&](const double* svec, double* u) {    // u = J_h s  (resp. X s on the Gram path)
-    if (!gp) tri_matvec(Rh, dg, n, ld, svec, u);
-    else if (fast) tri_matvec(X, nullptr, n, ld, svec, u);
-    else full_matvec(X, n, ld, svec, u);
+    if (!gp) tri_matvec<NS_NT, 8>(Rh, dg, n, ld, svec, u);
+    else if (fast) tri_matvec<NS_NT, 8>(X, nullptr, n, ld, svec, u);
+    else full_matvec<NS_NT, 4>(X, n, ld, svec, u);
   };
   if (fast) {
     for (int j = tid; j < n; j += NS_NT) ph[j] = lm_ph[vo + j];
@@ -570,7 +407,7 @@ __global__ __launch_bounds__(NS_NT) void trf_step_kernel(TrfState st, const int*
     double q2;
     if (cs_) q2 = f * dot_dev(ph, hp, n, red);            // (f p)^T H (f p) = f (f p) . hp
     else {
-      if (!gp) tri_matvec(Rh, tmp, n, ld, ph, up);
+      if (!gp) tri_matvec<NS_NT, 8>(Rh, tmp, n, ld, ph, up);
       else model_mv(ph, up);
       q2 = dot_dev(up, up, n, red);
     }
@@ -638,10 +475,10 @@ __global__ __launch_bounds__(NS_NT) void trf_step_kernel(TrfState st, const int*
       //  matrix element, and from global memory every one of those reads was a dependent load in front of its fma)
       for (int j = tid; j < n; j += NS_NT) { tmp[j] = dg[j]; tmp2[j] = gh[j]; }
       __syncthreads();
-      if (!gp) tri_matvec3(Rh, tmp, n, ld, ph, up, need_r ? rh : nullptr, ur, tmp2, ug);
-      else if (cs_) tri_matvec3(X, nullptr, n, ld, ur, up, nullptr, nullptr, tmp2, ug);   // up = X p_hits
-      else if (fast) tri_matvec3(X, nullptr, n, ld, ph, up, need_r ? rh : nullptr, ur, tmp2, ug);
-      else full_matvec3(X, n, ld, ph, up, need_r ? rh : nullptr, ur, tmp2, ug);
+      if (!gp) tri_matvec3<NS_NT>(Rh, tmp, n, ld, ph, up, need_r ? rh : nullptr, ur, tmp2, ug);
+      else if (cs_) tri_matvec3<NS_NT>(X, nullptr, n, ld, ur, up, nullptr, nullptr, tmp2, ug);   // up = X p_hits
+      else if (fast) tri_matvec3<NS_NT>(X, nullptr, n, ld, ph, up, need_r ? rh : nullptr, ur, tmp2, ug);
+      else full_matvec3<NS_NT>(X, n, ld, ph, up, need_r ? rh : nullptr, ur, tmp2, ug);
     } else if (cs_) {
       model_mv(ur, up);                                      // up = X p_hits
     } else {

@@ -5,6 +5,7 @@
 #include <type_traits>
 
 #include "blsq_device.h"
+#include "mv_ops.h"             // u = R s, u = R^T s: the matrix-vector family
 
 namespace blsq {
 
@@ -37,70 +38,11 @@ __device__ __forceinline__ void tri_lds16_tie(double (&v)[16]) {       // (alrea
   asm volatile("" : "+v"(v[0]), "+v"(v[1]), "+v"(v[2]), "+v"(v[3]), "+v"(v[4]), "+v"(v[5]), "+v"(v[6]), "+v"(v[7]),
                     "+v"(v[8]), "+v"(v[9]), "+v"(v[10]), "+v"(v[11]), "+v"(v[12]), "+v"(v[13]), "+v"(v[14]), "+v"(v[15]));
 }
-__device__ __forceinline__ unsigned tri_lds_addr(const double* p) {
-  return (unsigned)(unsigned long)(lptr_t*)p;
-}
 
 static constexpr int TRI_NT = 256;
 static constexpr int TRI_NW = TRI_NT / WAVE;
 // Every routine is a template on NT, the thread count of the calling workgroup (default TRI_NT): the fused
 // Newton-round kernel of chol_reg.hip runs them with its 512 threads.
-
-// u = R s   (one wave per row, lanes stride the columns)
-template <int NT = TRI_NT>
-__device__ __forceinline__ void tri_mv(const double* R, int n, int ld, const double* s, double* u) {
-  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-  constexpr int RB = 4;                     // rows per wave pass: their loads fly together
-  for (int i0 = w; i0 < n; i0 += (NT / WAVE) * RB) {
-    double acc[RB];
-#pragma unroll
-    for (int r = 0; r < RB; ++r) acc[r] = 0.0;
-    for (int jj = 0; i0 + lane + jj < n; jj += WAVE) {
-      double rv[RB];
-#pragma unroll
-      for (int r = 0; r < RB; ++r) {
-        const int i = i0 + r * (NT / WAVE);
-        const int ic = (i < n) ? i : n - 1;
-        const int j = ic + lane + jj;
-        rv[r] = R[(long)ic * ld + ((j < n) ? j : n - 1)];
-      }
-#pragma unroll
-      for (int r = 0; r < RB; ++r) {
-        const int i = i0 + r * (NT / WAVE);
-        const int j = i + lane + jj;
-        if (i < n && j < n) acc[r] = fma(rv[r], s[j], acc[r]);
-      }
-    }
-#pragma unroll
-    for (int r = 0; r < RB; ++r) {
-      const int i = i0 + r * (NT / WAVE);
-      const double t = wave_sum(acc[r]);
-      if (lane == 0 && i < n) u[i] = t;
-    }
-  }
-  __syncthreads();
-}
-
-// u = R^T s  (thread per column j: sum_{i<=j} R[i][j] s_i; coalesced across threads)
-template <int NT = TRI_NT>
-__device__ __forceinline__ void tri_mtv(const double* R, int n, int ld, const double* s,
-                                        double* u) {
-  for (int j = threadIdx.x; j < n; j += NT) {
-    double acc = 0.0;
-    // 32 rows per pass, unconditional (clamped) loads in flight together: the passes are serialised by
-    // their waits, and the longest column has n rows (8 per pass: 32 round trips at n = 256)
-    for (int i0 = 0; i0 <= j; i0 += 32) {
-      double rv[32];
-#pragma unroll
-      for (int k = 0; k < 32; ++k) rv[k] = R[(long)((i0 + k <= j) ? i0 + k : j) * ld + j];
-#pragma unroll
-      for (int k = 0; k < 32; ++k)
-        if (i0 + k <= j) acc = fma(rv[k], s[i0 + k], acc);
-    }
-    u[j] = acc;
-  }
-  __syncthreads();
-}
 
 // invd[i] = 1 / R[i][i]
 template <int NT = TRI_NT>
@@ -220,7 +162,7 @@ __device__ __forceinline__ void tri_pf_issue_upper(const double* R, int ld, int 
 typedef double tri_v2d __attribute__((ext_vector_type(2)));
 __device__ __forceinline__ void tri_pf_upper_issue(tri_v2d (&t)[8], const double* b, int row) {
   const int r = row & 7, g1 = (row >> 3) & 1;
-  const unsigned blk = tri_lds_addr(b) + 8u * (unsigned)((row & ~7) * 16) + 128u * (unsigned)(r ^ g1);
+  const unsigned blk = lds_addr(b) + 8u * (unsigned)((row & ~7) * 16) + 128u * (unsigned)(r ^ g1);
 #define BLSQ_TRI_RD2(C) asm volatile("ds_read_b128 %0, %1" : "=v"(t[C]) : "v"(blk + 16u * (unsigned)((C) ^ r)));
   BLSQ_TRI_RD2(0) BLSQ_TRI_RD2(1) BLSQ_TRI_RD2(2) BLSQ_TRI_RD2(3) BLSQ_TRI_RD2(4) BLSQ_TRI_RD2(5) BLSQ_TRI_RD2(6) BLSQ_TRI_RD2(7)
 #undef BLSQ_TRI_RD2
@@ -336,7 +278,7 @@ __device__ __forceinline__ void tri_solve_upper_pf_ref(const double* R, int n, i
     lds_barrier();
     if (tid < c0) {                                      // rows above the block
       double xv[16];
-      tri_lds16_issue<1>(xv, tri_lds_addr(x) + 8u * (unsigned)c0);
+      tri_lds16_issue<1>(xv, lds_addr(x) + 8u * (unsigned)c0);
       hook.block(0, c0);
       for (int i = tid; i < c0; i += NT) {
         double rv[16];
@@ -378,7 +320,7 @@ __device__ __forceinline__ void tri_solve_upper_t_pf_ref(const double* R, int n,
     if (tid < 64) {
       const int i = tid & 15;               // row i of the lower-triangular block = column i of R's block
       double D[16], bv[16];
-      tri_lds16_issue_rt(bv, tri_lds_addr(b) + 8u * (unsigned)i, 8u * (unsigned)L);
+      tri_lds16_issue_rt(bv, lds_addr(b) + 8u * (unsigned)i, 8u * (unsigned)L);
       double r = (i < bs) ? y[c0 + i] : 0.0;
       const double iv = (i < bs) ? invd[c0 + i] : 0.0;
       tri_lds16_wait(bv);
@@ -397,10 +339,10 @@ __device__ __forceinline__ void tri_solve_upper_t_pf_ref(const double* R, int n,
     lds_barrier();
     if (c0 + 16 + tid < n) {                             // columns to the right of the block
       double yv[16];
-      tri_lds16_issue<1>(yv, tri_lds_addr(y) + 8u * (unsigned)c0);
+      tri_lds16_issue<1>(yv, lds_addr(y) + 8u * (unsigned)c0);
       for (int j = c0 + 16 + tid; j < n; j += NT) {
         double cv[16];
-        tri_lds16_issue_rt(cv, tri_lds_addr(b) + 8u * (unsigned)(j - c0), 8u * (unsigned)L);
+        tri_lds16_issue_rt(cv, lds_addr(b) + 8u * (unsigned)(j - c0), 8u * (unsigned)L);
         tri_lds16_wait(cv);
         tri_lds16_tie(yv);
         double acc = 0.0;
@@ -520,7 +462,7 @@ __device__ __forceinline__ void tri_solve_upper_pf_la(const double* R, int n, in
       hook.stamp(kb, 4);
       if (tid - WAVE < c0 - 16) {                        // rows above block kb-1
         double xv[16];
-        tri_lds16_issue<1>(xv, tri_lds_addr(x) + 8u * (unsigned)c0);
+        tri_lds16_issue<1>(xv, lds_addr(x) + 8u * (unsigned)c0);
         hook.block(0, c0);
         for (int r_ = tid - WAVE; r_ < c0 - 16; r_ += NB) {
           double rv[16];
@@ -596,7 +538,7 @@ __device__ __forceinline__ void tri_solve_upper_t_pf_la(const double* R, int n, 
       // columns c0+16 .. c0+31 (block kb+1, bs1 of them inside the matrix): their update from panel kb, their substitution
       const int bs1 = (n - c0 - 16 < 16) ? n - c0 - 16 : 16;
       double cv[16];
-      tri_lds16_issue_rt(cv, tri_lds_addr(b) + 8u * (unsigned)(16 + i), 8u * (unsigned)L);
+      tri_lds16_issue_rt(cv, lds_addr(b) + 8u * (unsigned)(16 + i), 8u * (unsigned)L);
       double r = (i < bs1) ? y[c0 + 16 + i] : 0.0;
       tri_lds16_wait(cv);
       double acc = 0.0;
@@ -617,10 +559,10 @@ __device__ __forceinline__ void tri_solve_upper_t_pf_la(const double* R, int n, 
       tri_pf_issue_lower<NT, 1>(R, ld, c0 + 16, buf + (cur ^ 1) * bsz, tid);
       if (c0 + 32 + tid - WAVE < n) {                    // columns to the right of block kb+1
         double yv[16];
-        tri_lds16_issue<1>(yv, tri_lds_addr(y) + 8u * (unsigned)c0);
+        tri_lds16_issue<1>(yv, lds_addr(y) + 8u * (unsigned)c0);
         for (int j = c0 + 32 + tid - WAVE; j < n; j += NB) {
           double cv[16];
-          tri_lds16_issue_rt(cv, tri_lds_addr(b) + 8u * (unsigned)(j - c0), 8u * (unsigned)L);
+          tri_lds16_issue_rt(cv, lds_addr(b) + 8u * (unsigned)(j - c0), 8u * (unsigned)L);
           tri_lds16_wait(cv);
           tri_lds16_tie(yv);
           double acc = 0.0;
