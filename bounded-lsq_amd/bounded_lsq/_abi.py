@@ -112,6 +112,9 @@ SIGNATURES = {
     "blsq_cov_rows_dev": (C.c_int, [vp, C.c_int, vp, vp, vp]),
     "blsq_cov_rows": (C.c_int, [vp, C.c_int, vp, vp, vp]),
     "blsq_outer_leverage": (C.c_int, [vp, vp, vp]),
+    "blsq_model_count": (C.c_int, []),
+    "blsq_model_info": (C.c_int, [C.c_int, C.POINTER(C.c_char_p), c_int32_p, c_int32_p, c_int32_p]),
+    "blsq_model_eval_dev": (C.c_int, [vp] + [C.c_int] * 5 + [vp, C.c_long, vp, vp, C.c_long] + [vp] * 4),
 }
 
 _lib = None

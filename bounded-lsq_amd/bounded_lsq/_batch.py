@@ -45,7 +45,9 @@ def least_squares_batch(fun, x0, jac, bounds=(-np.inf, np.inf), method='trf',
                         loss='linear', f_scale=1.0, covariance=False, _variance_scale=False, leverage=False):
     """Solve B bound-constrained least-squares problems of identical shape.
 
-    fun : callable, ``fun(X) -> (B, m)`` residuals for ``X`` (B, n)
+    fun : callable, ``fun(X) -> (B, m)`` residuals for ``X`` (B, n) — or a ``models.DeviceFit`` (a built-in model with
+          its data): residuals and Jacobians are then evaluated on the GPU and the whole solve runs through
+          ``OuterDriver.run_device`` (driver='device' only; `jac` None: the model's analytic Jacobian)
     x0  : (B, n) initial guesses;  jac : callable ``jac(X) -> (B, m, n)``, or '2-point' / '3-point' 
     bounds : pair broadcastable to (B, n);  scaling : 'jac' or broadcastable to (n,)
     diff_step : relative step of the finite-difference Jacobian (as `least_squares`, least_squares.py:357-365)
@@ -81,9 +83,19 @@ def least_squares_batch(fun, x0, jac, bounds=(-np.inf, np.inf), method='trf',
         raise ValueError("`f_scale` must be a scalar or broadcastable to (B,).")
     robust = callable(loss) or loss != 'linear'
     lb, ub = _bounds_2d(bounds, B, n)
-    if not callable(fun):
+    on_device = hasattr(fun, 'open_device')                   # device callbacks (models.DeviceFit)
+    if not callable(fun) and not on_device:
         raise ValueError("`fun` must be callable (vectorised over the batch).")
     kwargs = dict(kwargs) if kwargs else {}
+    if on_device:
+        if driver != 'device':
+            raise ValueError("device callbacks need driver='device'.")
+        if args or kwargs:
+            raise ValueError("`args` and `kwargs` are not passed to device callbacks.")
+        if jac is not None and jac not in ('2-point', '3-point'):
+            raise ValueError("`jac` must be None (analytic), '2-point' or '3-point' with device callbacks.")
+        if (fun.B, fun.n) != (B, n):
+            raise ValueError("`x0` must have shape (B, n) = (%d, %d)." % (fun.B, fun.n))
     if args or kwargs:                                        # least_squares.py:351-355, 367-371
         user_fun, user_jac = fun, jac
 
@@ -93,7 +105,9 @@ def least_squares_batch(fun, x0, jac, bounds=(-np.inf, np.inf), method='trf',
             def jac(X):                                       # noqa: F811
                 return user_jac(X, *args, **kwargs)
     fd_state = {}                                  # lazily created FdJacobian (+ ctx if we own it)
-    if isinstance(jac, str) and jac in ('2-point', '3-point'):
+    if on_device:
+        pass                                       # (run_device estimates '2-point' / '3-point' itself)
+    elif isinstance(jac, str) and jac in ('2-point', '3-point'):
         # the reference's FD Jacobian (third-party approx_derivative, least_squares.py:357-365)
         # restated for the batch on the device (`FdJacobian`: bit-identical steps, points and
         # quotients); `fun` is called once per perturbed coordinate with all B problems.  FD
@@ -137,7 +151,8 @@ def least_squares_batch(fun, x0, jac, bounds=(-np.inf, np.inf), method='trf',
     if driver == 'device':
         try:
             return _device_batch(fun, jac, X0, lb, ub, trf, use_jac, scaling, ftol, xtol, gtol,
-                                 max_nfev, ctx, loss if robust else None, fsc, covariance, _variance_scale, leverage)
+                                 max_nfev, ctx, loss if robust else None, fsc, covariance, _variance_scale, leverage,
+                                 diff_step=diff_step)
         finally:
             _release_fd()
 
@@ -323,16 +338,9 @@ def least_squares_batch(fun, x0, jac, bounds=(-np.inf, np.inf), method='trf',
         _release_fd()
 
 
-def _device_batch(fun, jac, X0, lb, ub, trf, use_jac, scaling, ftol, xtol, gtol, max_nfev, ctx,
-                  loss=None, f_scale=None, covariance=False, variance_scale=False, leverage=False):
-    """`least_squares_batch` on the device-resident outer driver (same results, same counts).  `loss`: a
-    loss name other than 'linear' (None: sum f^2), applied on the device (blsq_outer_set_loss)."""
-    from ._outer import OuterDriver
-    B, n = X0.shape
-    if trf:                                                   # trf.py:201
-        xs = np.stack([shift_into_interior(X0[b], lb[b], ub[b], rstep=1e-10) for b in range(B)])
-    else:
-        xs = X0.copy()
+def _host_callbacks(fun, jac, xs, B, n):
+    """The numpy callbacks of `_device_batch`, shape-checked: ``(run(driver) -> fetched results, m)``.  fun(x_start) is
+    evaluated here once, to learn m, and handed to the driver's first call."""
     F0 = np.ascontiguousarray(fun(xs), dtype=float)
     if F0.ndim != 2 or F0.shape[0] != B:
         raise RuntimeError("`fun` must return an array of shape (B, m).")
@@ -357,18 +365,48 @@ def _device_batch(fun, jac, X0, lb, ub, trf, use_jac, scaling, ftol, xtol, gtol,
                                "`fun` and `jac` on the first iteration.")
         return J
 
+    return (lambda drv: drv.run_host(fun_cached, jac_checked)), m
+
+
+def _device_batch(fun, jac, X0, lb, ub, trf, use_jac, scaling, ftol, xtol, gtol, max_nfev, ctx,
+                  loss=None, f_scale=None, covariance=False, variance_scale=False, leverage=False, diff_step=None):
+    """`least_squares_batch` on the device-resident outer driver (same results, same counts).  `loss`: a
+    loss name other than 'linear' (None: sum f^2), applied on the device (blsq_outer_set_loss).
+    Host callbacks (`fun`, `jac` numpy callables) go through ``run_host``; device callbacks (`fun` with
+    ``open_device(ctx, lb, ub)``, `jac` None or a finite-difference name) through ``run_device``: then nothing but
+    the counters of propose / judge crosses the boundary between start and fetch.  Both share everything else."""
+    from ._outer import OuterDriver
+    B, n = X0.shape
+    if trf:                                                   # trf.py:201
+        xs = np.stack([shift_into_interior(X0[b], lb[b], ub[b], rstep=1e-10) for b in range(B)])
+    else:
+        xs = X0.copy()
+    on_device = hasattr(fun, 'open_device')
+    if on_device:
+        m = fun.m
+    else:
+        run, m = _host_callbacks(fun, jac, xs, B, n)
     scale = np.ones((B, n)) if use_jac else np.broadcast_to(1 / np.asarray(scaling, float), (B, n))
     drv = OuterDriver('trf' if trf else 'dogbox', B, m, n, ctx=ctx)
+    dev = None
     try:
+        if on_device:
+            dev = fun.open_device(drv.ctx, lb, ub)
+
+            def run(drv):
+                return drv.run_device(dev.fun_dev, dev.jac_dev if jac is None else jac, rel_step=diff_step,
+                                      bounds_dev=dev.bounds_dev)
         if loss is not None:
             drv.set_loss(loss, f_scale)
         drv.start(X0, xs, lb, ub, scale, use_jac, ftol, xtol, gtol, max_nfev)
-        R = drv.run_host(fun_cached, jac_checked)
+        R = run(drv)
         cov_out = drv.covariance(free_only=_is_free(covariance), pinv=_is_pinv(covariance),
                                  variance_scale=variance_scale and m > n) if covariance else None
         lev_out = drv.leverage() if leverage else None
         Jfin = drv._down(drv.d_J, (B, m, n))
     finally:
+        if dev is not None:
+            dev.close()
         drv.close()
     results = []
     for b in range(B):

@@ -14,6 +14,7 @@ from scipy.optimize import OptimizeWarning
 from ._frontend import least_squares
 from ._batch import least_squares_batch
 from ._hostmath import prepare_bounds
+from . import _models
 
 __all__ = ['curve_fit', 'curve_fit_batch']
 
@@ -190,14 +191,22 @@ def curve_fit(f, xdata, ydata, p0=None, sigma=None, absolute_sigma=False, check_
 
 
 def curve_fit_batch(f, xdata, ydata, p0, sigma=None, absolute_sigma=False, bounds=(-np.inf, np.inf), method='trf',
-                    jac='2-point', driver='host', ctx=None, **kwargs):
+                    jac=None, driver='host', ctx=None, **kwargs):
     """``curve_fit`` for B data sets of one model, solved together by ``least_squares_batch``.
 
-    f : ``f(xdata, P) -> (B, m)`` for parameters ``P`` of shape (B, n): vectorised over the batch
+    f : ``f(xdata, P) -> (B, m)`` for parameters ``P`` of shape (B, n): vectorised over the batch — or the name of a
+        built-in model (``bounded_lsq.models``: 'poly', 'exp_sum', 'gauss_sum', 'lorentz_sum', 'gauss2d'; n = p0.shape[1]
+        fixes the number of terms).  A named model with driver='device' is evaluated on the GPU, residuals and
+        Jacobians alike: between the start of the solve and its results only two counters per iteration leave the
+        device.  With driver='host' the model's numpy functions are the callbacks.  `xdata` is then (m,) or (B, m)
+        — (2, m) or (B, 2, m) for 'gauss2d'.  A wrong name, an n that does not fit the model or a wrong `xdata` shape
+        is a ValueError.
     ydata : (B, m);  p0 : (B, n), required
     sigma : None, a scalar, (m,) errors shared by all problems or (B, m) per problem (a shape (B, m) is always read
             this way).  A 2-D covariance is not supported here: ValueError.
-    bounds : pair broadcastable to (B, n);  jac : '2-point', '3-point' or ``jac(xdata, P) -> (B, m, n)``
+    bounds : pair broadcastable to (B, n);  jac : '2-point', '3-point' or ``jac(xdata, P) -> (B, m, n)``; None (the
+            default) is '2-point' for a callable `f` and the analytic Jacobian for a named model, whose '2-point' /
+            '3-point' are estimated on the device from the kernel's values (a callable `jac` with a name: ValueError)
     driver, ctx, **kwargs : as ``least_squares_batch`` (tolerances, ``max_nfev`` / ``maxfev``, ``loss=``, ...).
 
     Returns ``(popt (B, n), pcov (B, n, n), results)``, `results` the B ``OptimizeResult`` of the solve.  pcov[b] is
@@ -219,6 +228,23 @@ def curve_fit_batch(f, xdata, ydata, p0, sigma=None, absolute_sigma=False, bound
     if P0.ndim != 2 or P0.shape[0] != B:
         raise ValueError("`p0` must have shape (B, n).")
     n = P0.shape[1]
+    model = None
+    if isinstance(f, str):
+        model = _models.get(f)
+        model.terms(n)
+        xdata, _ = model.check_xdata(xdata, B, m)
+        if callable(jac):
+            raise ValueError("a callable `jac` cannot be combined with the built-in model '%s'." % f)
+        if jac is not None and jac not in ('2-point', '3-point'):
+            raise ValueError("`jac` must be None, '2-point' or '3-point' with a built-in model.")
+        if driver not in ('host', 'device'):
+            raise ValueError("`driver` must be 'host' or 'device'.")
+        if driver == 'host':                     # the numpy functions through the callable path below
+            f = model.f
+            if jac is None:
+                jac = model.jac
+    elif jac is None:
+        jac = '2-point'
     if isinstance(xdata, (list, tuple, np.ndarray)):
         xdata = np.asarray(xdata, float)
 
@@ -232,7 +258,9 @@ def curve_fit_batch(f, xdata, ydata, p0, sigma=None, absolute_sigma=False, bound
         else:
             raise ValueError("`sigma` has incorrect shape.")
 
-    if transform is None:
+    if model is not None and driver == 'device':
+        func = _models.DeviceFit(model.name, n, xdata, ydata, sigma)
+    elif transform is None:
         def func(P):
             return np.asarray(f(xdata, P), float) - ydata
     else:

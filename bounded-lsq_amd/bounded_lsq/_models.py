@@ -1,0 +1,335 @@
+"""Built-in fit models (``bounded_lsq.models``): five closed-form families that ``curve_fit_batch`` evaluates on the GPU
+(blsq_model_eval_dev of include/blsq.h, csrc/model_kernels.hip).
+
+Parameter order is fixed and a constant offset ``c`` is always last:
+
+    name          model                                                        n        xdata
+    poly          sum_{k<n} p_k t^k                                            >= 1     (m,) or (B, m)
+    exp_sum       sum_k a_k exp(-r_k t) + c            (a_1, r_1, ..., c)      2K + 1   (m,) or (B, m)
+    gauss_sum     sum_k a_k exp(-z_k^2 / 2) + c,  z_k = (t - mu_k) / s_k       3K + 1   (m,) or (B, m)
+                                                       (a_1, mu_1, s_1, ..., c)
+    lorentz_sum   sum_k a_k / (1 + z_k^2) + c          same parameters         3K + 1   (m,) or (B, m)
+    gauss2d       a exp(-((u-u0)^2 + (v-v0)^2) / (2 s^2)) + c   (a, u0, v0, s, c)   5   (2, m) or (B, 2, m)
+
+The numpy functions ``MODELS[name].f(xdata, P) -> (B, m)`` and ``.jac(xdata, P) -> (B, m, n)`` below ARE the definition
+of each model: the kernel evaluates the same formulas operation by operation (it is compiled without contraction), so
+the two differ by the last bit of exp() only.  They are vectorised over the batch, keep the dtype of their inputs
+(np.longdouble inputs give a longdouble reference) and check nothing: a non-finite value (s = 0) passes through.
+They are also the ``driver='host'`` route of ``curve_fit_batch(f='name')``.
+"""
+import numpy as np
+
+from . import _abi
+
+MAX_N = 64                                   # BLSQ_MODEL_MAX_N
+
+__all__ = ['MODELS', 'NAMES', 'MAX_N', 'get', 'evaluate', 'DeviceModel', 'DeviceFit']
+
+
+def _tp(xdata, P):
+    """t broadcastable against the (B, 1) parameter columns, and P, in their common floating dtype."""
+    P = np.asarray(P)
+    t = np.asarray(xdata)
+    dt = np.result_type(P.dtype, t.dtype, np.float64)
+    return t.astype(dt, copy=False), P.astype(dt, copy=False)
+
+
+def _col(P, k):
+    return P[:, k, np.newaxis]
+
+
+def _poly_f(xdata, P):
+    t, P = _tp(xdata, P)
+    n = P.shape[1]
+    acc = np.broadcast_to(_col(P, n - 1), np.broadcast(_col(P, 0), t).shape)       # Horner
+    for k in range(n - 2, -1, -1):
+        acc = acc * t + _col(P, k)
+    return acc
+
+
+def _poly_jac(xdata, P):
+    t, P = _tp(xdata, P)
+    B, n = P.shape
+    J = np.empty((B, t.shape[-1], n), dtype=P.dtype)
+    pw = np.ones_like(t)
+    for k in range(n):                                             # t^k by repeated product
+        J[:, :, k] = pw
+        pw = pw * t
+    return J
+
+
+def _exp_terms(t, P):
+    for k in range((P.shape[1] - 1) // 2):
+        a, r = _col(P, 2 * k), _col(P, 2 * k + 1)
+        e = np.exp(-(r * t))
+        yield k, e, a * e
+
+
+def _exp_f(xdata, P):
+    t, P = _tp(xdata, P)
+    acc = None
+    for k, e, g in _exp_terms(t, P):
+        acc = g if acc is None else acc + g
+    return acc + _col(P, -1)
+
+
+def _exp_jac(xdata, P):
+    t, P = _tp(xdata, P)
+    B, n = P.shape
+    J = np.empty((B, t.shape[-1], n), dtype=P.dtype)
+    for k, e, g in _exp_terms(t, P):
+        J[:, :, 2 * k] = e
+        J[:, :, 2 * k + 1] = -(t * g)
+    J[:, :, n - 1] = 1.0
+    return J
+
+
+def _peak_terms(t, P, lorentz):
+    """k, e (d / da), g (the term), dmu, z of every peak."""
+    for k in range((P.shape[1] - 1) // 3):
+        a, mu, s = _col(P, 3 * k), _col(P, 3 * k + 1), _col(P, 3 * k + 2)
+        z = (t - mu) / s
+        if lorentz:
+            e = 1.0 / (1.0 + z * z)
+            g = a * e
+            dmu = (((2.0 * g) * e) * z) / s
+        else:
+            e = np.exp(-0.5 * (z * z))
+            g = a * e
+            dmu = (g * z) / s
+        yield k, e, g, dmu, z
+
+
+def _peak_f(lorentz):
+    def f(xdata, P):
+        t, P = _tp(xdata, P)
+        acc = None
+        for k, e, g, dmu, z in _peak_terms(t, P, lorentz):
+            acc = g if acc is None else acc + g
+        return acc + _col(P, -1)
+    return f
+
+
+def _peak_jac(lorentz):
+    def jac(xdata, P):
+        t, P = _tp(xdata, P)
+        B, n = P.shape
+        J = np.empty((B, t.shape[-1], n), dtype=P.dtype)
+        for k, e, g, dmu, z in _peak_terms(t, P, lorentz):
+            J[:, :, 3 * k] = e
+            J[:, :, 3 * k + 1] = dmu
+            J[:, :, 3 * k + 2] = dmu * z
+        J[:, :, n - 1] = 1.0
+        return J
+    return jac
+
+
+def _g2_parts(xdata, P):
+    t, P = _tp(xdata, P)
+    du = t[..., 0, :] - _col(P, 1)
+    dv = t[..., 1, :] - _col(P, 2)
+    s = _col(P, 3)
+    r2 = du * du + dv * dv
+    s2 = s * s
+    e = np.exp(-0.5 * (r2 / s2))
+    return P, du, dv, s, r2, s2, e, _col(P, 0) * e
+
+
+def _g2_f(xdata, P):
+    P, du, dv, s, r2, s2, e, g = _g2_parts(xdata, P)
+    return g + _col(P, 4)
+
+
+def _g2_jac(xdata, P):
+    P, du, dv, s, r2, s2, e, g = _g2_parts(xdata, P)
+    J = np.empty(e.shape + (5,), dtype=P.dtype)
+    J[:, :, 0] = e
+    J[:, :, 1] = (g * du) / s2
+    J[:, :, 2] = (g * dv) / s2
+    J[:, :, 3] = (g * r2) / (s2 * s)
+    J[:, :, 4] = 1.0
+    return J
+
+
+class Model:
+    """One row of the registry: ``id`` (BLSQ_MODEL_*), ``coords`` (rows of xdata per point), the rule for n
+    (``n_per_term == 0``: n == n_base; otherwise n = n_base + K * n_per_term, K >= 1) and the numpy ``f`` / ``jac``."""
+
+    def __init__(self, id, name, coords, n_base, n_per_term, f, jac):
+        self.id, self.name, self.coords, self.n_base, self.n_per_term = id, name, coords, n_base, n_per_term
+        self.f, self.jac = f, jac
+
+    def terms(self, n):
+        """Number of terms K for n parameters; ValueError if n does not fit the model."""
+        n = int(n)
+        if self.n_per_term == 0:
+            ok, K = n == self.n_base, 1
+        else:
+            K, rem = divmod(n - self.n_base, self.n_per_term)
+            ok = n > self.n_base and rem == 0
+        if not ok or not 1 <= n <= MAX_N:
+            raise ValueError("model '%s' does not take n = %d parameters (%s, n <= %d)." % (self.name, n, self.rule(), MAX_N))
+        return K
+
+    def rule(self):
+        if self.n_per_term == 0:
+            return "n = %d" % self.n_base
+        if self.n_base == 0 and self.n_per_term == 1:
+            return "n >= 1"
+        return "n = %d K + %d" % (self.n_per_term, self.n_base)
+
+    def check_xdata(self, xdata, B, m):
+        """xdata as a float64 array of shape (m,) / (B, m) — (2, m) / (B, 2, m) for two coordinates; ValueError
+        otherwise.  Returns (array, per_problem)."""
+        x = np.asarray(xdata, dtype=np.float64)
+        shared = (m,) if self.coords == 1 else (self.coords, m)
+        if x.shape == (B,) + shared:
+            return np.ascontiguousarray(x), True
+        if x.shape == shared:
+            return np.ascontiguousarray(x), False
+        raise ValueError("`xdata` of model '%s' must have shape %s or %s, not %s."
+                         % (self.name, shared, (B,) + shared, x.shape))
+
+
+MODELS = {m.name: m for m in (
+    Model(0, 'poly', 1, 0, 1, _poly_f, _poly_jac),
+    Model(1, 'exp_sum', 1, 1, 2, _exp_f, _exp_jac),
+    Model(2, 'gauss_sum', 1, 1, 3, _peak_f(False), _peak_jac(False)),
+    Model(3, 'lorentz_sum', 1, 1, 3, _peak_f(True), _peak_jac(True)),
+    Model(4, 'gauss2d', 2, 5, 0, _g2_f, _g2_jac),
+)}
+NAMES = tuple(MODELS)
+
+
+def get(name):
+    """The registry row of `name`; ValueError for anything else."""
+    if not isinstance(name, str) or name not in MODELS:
+        raise ValueError("unknown model %r: a built-in model is one of %s." % (name, ", ".join(NAMES)))
+    return MODELS[name]
+
+
+class DeviceModel:
+    """Model `name` with its data resident on the GPU: the device callbacks of ``OuterDriver.run_device``.
+
+    Uploads t = xdata, y = ydata (None: 0, plain prediction) and w = 1 / sigma (None: 1; sigma a scalar, (m,) or
+    (B, m)) once.  ``fun_dev(x_ptr, f_ptr, reps)`` and ``jac_dev(x_ptr, J_ptr, mask_ptr)`` launch the kernel on the
+    context's stream — the stream of every driver on that context, so no synchronisation is needed in between.
+    ``bounds_dev`` is the (lb_ptr, ub_ptr) pair the finite-difference route asks for, after ``set_bounds(lb, ub)``.
+    ``close()`` frees the buffers (also run when the context closes)."""
+
+    def __init__(self, ctx, name, B, m, n, xdata, ydata=None, sigma=None):
+        model = get(name)
+        model.terms(n)
+        self.model, self.B, self.m, self.n = model, int(B), int(m), int(n)
+        x, per_problem = model.check_xdata(xdata, self.B, self.m)
+        y = w = None
+        if ydata is not None:
+            y = np.ascontiguousarray(ydata, dtype=np.float64)
+            if y.shape != (self.B, self.m):
+                raise ValueError("`ydata` must have shape (B, m).")
+        self.w_stride = 0
+        if sigma is not None:
+            sg = np.asarray(sigma, dtype=np.float64)
+            if sg.shape == (self.B, self.m):
+                self.w_stride = self.m
+            elif sg.size == 1:
+                sg = np.broadcast_to(sg.reshape(()), (self.m,))
+            elif sg.shape != (self.m,):
+                raise ValueError("`sigma` has incorrect shape.")
+            w = np.ascontiguousarray(1.0 / sg)
+        self.t_stride = model.coords * self.m if per_problem else 0
+        self.ctx = ctx
+        self._bufs = []
+        self.d_t = self._upload(x)
+        self.d_y = self._upload(y)
+        self.d_w = self._upload(w)
+        self.bounds_dev = None
+        ctx.adopt(self)
+
+    def _upload(self, a):
+        if a is None:
+            return None
+        p = self.ctx.to_device(a)
+        self._bufs.append(p)
+        return p
+
+    def set_bounds(self, lb, ub):
+        self.bounds_dev = tuple(self._upload(np.ascontiguousarray(np.broadcast_to(a, (self.B, self.n)), dtype=np.float64))
+                                for a in (lb, ub))
+        return self.bounds_dev
+
+    def _eval(self, x_ptr, reps, f_ptr, J_ptr, mask_ptr):
+        self.ctx.check(self.ctx.lib.blsq_model_eval_dev(
+            self.ctx.h, self.model.id, self.B, int(reps), self.m, self.n, self.d_t, self.t_stride, self.d_y, self.d_w,
+            self.w_stride, x_ptr, f_ptr, J_ptr, mask_ptr), "blsq_model_eval_dev")
+
+    def fun_dev(self, x_ptr, f_ptr, reps=1):
+        self._eval(x_ptr, reps, f_ptr, None, None)
+
+    def jac_dev(self, x_ptr, J_ptr, mask_ptr=None):
+        self._eval(x_ptr, 1, None, J_ptr, mask_ptr)
+
+    def close(self):
+        bufs, self._bufs = getattr(self, "_bufs", []), []
+        ctx = self.ctx
+        if ctx is not None and getattr(ctx, "h", None):
+            for p in bufs:
+                ctx.free(p)
+        self.bounds_dev = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *a):
+        self.close()
+
+
+class DeviceFit:
+    """What ``least_squares_batch(fun=...)`` takes in place of a callable for a fit whose callbacks run on the device:
+    a checked (model, data) pair that opens a ``DeviceModel`` on the driver's context.  Built by ``curve_fit_batch``."""
+
+    def __init__(self, name, n, xdata, ydata, sigma=None):
+        self.model = get(name)
+        self.model.terms(n)
+        self.ydata = np.ascontiguousarray(ydata, dtype=np.float64)
+        self.B, self.m = self.ydata.shape
+        self.n = int(n)
+        self.xdata, _ = self.model.check_xdata(xdata, self.B, self.m)
+        self.sigma = sigma
+
+    def open_device(self, ctx, lb, ub):
+        dm = DeviceModel(ctx, self.model.name, self.B, self.m, self.n, self.xdata, self.ydata, self.sigma)
+        dm.set_bounds(lb, ub)
+        return dm
+
+
+def evaluate(name, xdata, P, ctx=None):
+    """Predictions ``model(xdata; P[b])`` of shape (B, m), computed on the GPU (the kernel with y = NULL, w = NULL).
+    P: (B, n); xdata: (m,) / (B, m), or (2, m) / (B, 2, m) for 'gauss2d'."""
+    model = get(name)
+    P = np.ascontiguousarray(P, dtype=np.float64)
+    if P.ndim != 2:
+        raise ValueError("`P` must have shape (B, n).")
+    B, n = P.shape
+    model.terms(n)
+    x = np.asarray(xdata, dtype=np.float64)
+    if x.ndim < 1 or x.shape[-1] == 0:
+        raise ValueError("`xdata` must not be empty.")
+    m = x.shape[-1]
+    model.check_xdata(x, B, m)
+    own = ctx is None
+    if own:
+        ctx = _abi.Context(0)
+    try:
+        with DeviceModel(ctx, name, B, m, n, x) as dm:
+            d_P = ctx.to_device(P)
+            d_f = ctx.malloc(8 * B * m)
+            try:
+                dm.fun_dev(d_P, d_f, 1)
+                return ctx.to_host(d_f, (B, m), np.float64)
+            finally:
+                ctx.free(d_P)
+                ctx.free(d_f)
+    finally:
+        if own:
+            ctx.close()

@@ -1,6 +1,6 @@
 // Device-side helpers shared by the HIP kernels (gfx950, wave64).
 //
-// Contraction rule.  trf_kernels, dogbox_kernels, outer_kernels, fd_kernels and loss_kernels are compiled with
+// Contraction rule.  trf_kernels, dogbox_kernels, outer_kernels, fd_kernels, loss_kernels and model_kernels are compiled with
 // -ffp-contract=off (they keep the reference's elementwise roundings); every other file contracts.  A helper in a
 // shared header (this one, mv_ops.h, tri_ops.h) is therefore compiled both ways, and must give the same bits in both:
 //   - every fused operation is spelled fma(...);

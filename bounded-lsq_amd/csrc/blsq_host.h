@@ -2,7 +2,7 @@
 // the factorisation front end of a plan (QrTree: Gram / certificate / CholeskyQR2 / Householder tree), the CSNE tier's
 // host state (CsneTier) and the plan structures.  blsq_ctx.hip: contexts, memory, timing, communicator, diagnostics;
 // blsq_front.hip: the bodies of QrTree and CsneTier and the plumbing the step plans' entry points share; blsq_trf.hip: TRF
-// and the row-split (TSQR) plans; blsq_dogbox.hip: dogbox plans; blsq_outer.hip: the batched outer drivers and finite differences; blsq_cov.hip: covariance plans.
+// and the row-split (TSQR) plans; blsq_dogbox.hip: dogbox plans; blsq_outer.hip: the batched outer drivers and finite differences; blsq_cov.hip: covariance plans; blsq_model.hip: the built-in fit models.
 // Internal: nothing here is part of the ABI.
 // Ownership: a plan's device memory is freed by its destructor (DevBuf / PinnedBuf, dev_buf.h) — a new buffer is a new
 // member and nothing else.  A destroy call synchronises the plan's stream, takes the plan off its ctx and deletes it.
@@ -30,11 +30,11 @@ namespace {
 constexpr int RMAX = QR_MAX_TILES * 16;   // rows a workgroup can stage (qr_panel.hip): 1024
 
 enum Slot { K_QR_LEAF = 0, K_QR_MERGE, K_PREP, K_QR_AUG, K_JACOBI, K_STEP, K_LM_GATE, K_LM_QR, K_LM_SOLVE,
-            K_GRAM, K_GRAM_CHOL, K_GRAM_GATE, K_AUG_CHOL, K_LM_CHOL, K_CQR2_APPLY, K_CQR2_COMBINE, K_CSNE_PASS,
+            K_GRAM, K_GRAM_CHOL, K_GRAM_GATE, K_AUG_CHOL, K_LM_CHOL, K_CQR2_APPLY, K_CQR2_COMBINE, K_MODEL_EVAL, K_CSNE_PASS,
             K_CSNE_FIX, K_COV_ROWS, K_COV_PINV_WEIGHTS, K_COV_PINV_PRODUCT, K_COV_GATHER, K_COV_INVERSE, K_COV_PRODUCT, K_LOSS_COST, K_LOSS_SCALE, K_NSLOT };
 static const char* const kSlotNames[K_NSLOT] = {"qr_leaf", "qr_merge", "prep", "qr_aug", "jacobi_svd", "step",
                                    "lm_gate", "lm_qr", "lm_solve", "gram", "gram_chol", "gram_gate",
-                                   "aug_chol", "lm_chol", "cqr2_apply", "cqr2_combine", "csne_pass", "csne_fix",
+                                   "aug_chol", "lm_chol", "cqr2_apply", "cqr2_combine", "model_eval", "csne_pass", "csne_fix",
                                    "cov_rows", "cov_pinv_weights", "cov_pinv_product", "cov_gather", "cov_inverse", "cov_product", "loss_cost", "loss_scale"};
 
 inline int round_up(int v, int q) { return (v + q - 1) / q * q; }

@@ -609,6 +609,13 @@ hipError_t launch_fd_assemble(int B, int m, int n, int method, const double* x, 
                               const unsigned char* one_sided, const double* f0, const double* F,
                               double* J, const int* mask, hipStream_t s);
 
+// --------------------------------------------------- built-in fit models (7j) ----
+// model_kernels.hip (blsq_model_eval_dev): f [B * reps][m] and / or J [B][m][n] (reps == 1) of model BLSQ_MODEL_* at
+// P [B * reps][n]; t_stride 0 (shared) or coords * m, w nullptr or stride 0 / m, y / mask may be nullptr.
+hipError_t launch_model_eval(int model, int B, int reps, int m, int n, const double* t, long t_stride, const double* y,
+                             const double* w, long w_stride, const double* P, double* f, double* J, const int* mask,
+                             hipStream_t s);
+
 // ---------------------------------------------------------------- probes ----
 // probe_kernels.hip: measured peaks / counter calibration (blsq_debug_probe)
 hipError_t launch_mfma_probe(int waves_per_simd, int iters, double* sink, long* n_mfma,

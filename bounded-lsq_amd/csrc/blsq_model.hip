@@ -1,0 +1,59 @@
+// Built-in fit models: the table behind blsq_model_count / blsq_model_info and the entry point blsq_model_eval_dev
+// (include/blsq.h; kernel: model_kernels.hip).
+#include "blsq_host.h"
+
+namespace {
+
+struct ModelRow {
+  const char* name;
+  int coords;        // rows of t per data point
+  int n_base;        // parameters besides the terms (the offset c; gauss2d: all five)
+  int n_per_term;    // parameters per term (0: a fixed n = n_base)
+};
+// in the order of the BLSQ_MODEL_* enum
+const ModelRow kModels[] = {
+    {"poly", 1, 0, 1}, {"exp_sum", 1, 1, 2}, {"gauss_sum", 1, 1, 3}, {"lorentz_sum", 1, 1, 3}, {"gauss2d", 2, 5, 0}};
+constexpr int kModelCount = (int)(sizeof(kModels) / sizeof(kModels[0]));
+static_assert(kModelCount == BLSQ_MODEL_GAUSS2D + 1, "one row per BLSQ_MODEL_*");
+
+bool model_n_fits(const ModelRow& r, int n) {
+  if (n < 1 || n > BLSQ_MODEL_MAX_N) return false;
+  if (r.n_per_term == 0) return n == r.n_base;
+  return n > r.n_base && (n - r.n_base) % r.n_per_term == 0;
+}
+
+}  // namespace
+
+extern "C" int blsq_model_count(void) { return kModelCount; }
+
+extern "C" int blsq_model_info(int model, const char** name, int* coords, int* n_base, int* n_per_term) {
+  if (model < 0 || model >= kModelCount) return -1;
+  const ModelRow& r = kModels[model];
+  if (name) *name = r.name;
+  if (coords) *coords = r.coords;
+  if (n_base) *n_base = r.n_base;
+  if (n_per_term) *n_per_term = r.n_per_term;
+  return 0;
+}
+
+extern "C" int blsq_model_eval_dev(blsq_ctx* ctx, int model, int B, int reps, int m, int n, const double* dt,
+                                   long t_stride, const double* dy, const double* dw, long w_stride, const double* dP,
+                                   double* df, double* dJ, const int32_t* dmask) {
+  if (!ctx) return -1;
+  if (model < 0 || model >= kModelCount) return ctx->bad(2, "model must be one of BLSQ_MODEL_*");
+  const ModelRow& r = kModels[model];
+  if (B <= 0) return ctx->bad(3, "B must be positive");
+  if (reps <= 0) return ctx->bad(4, "reps must be positive");
+  if (m <= 0) return ctx->bad(5, "m must be positive");
+  if (!model_n_fits(r, n)) return ctx->bad(6, "n does not fit the model (or exceeds BLSQ_MODEL_MAX_N)");
+  if (!dt) return ctx->bad(7, "t is NULL");
+  if (t_stride != 0 && t_stride != (long)r.coords * m) return ctx->bad(8, "t_stride must be 0 or coords * m");
+  if (dw && w_stride != 0 && w_stride != (long)m) return ctx->bad(11, "w_stride must be 0 or m");
+  if (!dP) return ctx->bad(12, "P is NULL");
+  if (!df && !dJ) return ctx->bad(13, "f and J are both NULL");
+  if (dJ && reps != 1) return ctx->bad(14, "J requires reps == 1");
+  HIPCHK(ctx, hipSetDevice(ctx->device));
+  return ctx->run(K_MODEL_EVAL, "launch_model_eval", [&] {
+    return launch_model_eval(model, B, reps, m, n, dt, t_stride, dy, dw, w_stride, dP, df, dJ, dmask, ctx->stream);
+  });
+}

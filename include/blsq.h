@@ -390,6 +390,35 @@ int blsq_loss_scale_dev(blsq_ctx* ctx, int B, int m, int n, int loss, const doub
  * lifetime rule asks. */
 int blsq_outer_set_loss(blsq_outer* o, int loss, const double* f_scale);
 
+/* ---- built-in fit models, evaluated on the device ---------------------------------------------------------------
+ * The callbacks of a curve fit (blsq_outer_*: f <- fun(x), J <- jac(x)) for five closed-form model families, so that a
+ * whole batched fit stays on the GPU.  Parameter order is fixed; a constant offset c is always last:
+ *   POLY         sum_{k<n} p_k t^k                                              any n >= 1      coords 1
+ *   EXP_SUM      sum_k a_k exp(-r_k t) + c          (a_1, r_1, ..., c)          n = 2K + 1      coords 1
+ *   GAUSS_SUM    sum_k a_k exp(-z_k^2 / 2) + c      z_k = (t - mu_k) / s_k      n = 3K + 1      coords 1
+ *                                                   (a_1, mu_1, s_1, ..., c)
+ *   LORENTZ_SUM  sum_k a_k / (1 + z_k^2) + c        same parameters             n = 3K + 1      coords 1
+ *   GAUSS2D      a exp(-((u-u0)^2 + (v-v0)^2) / (2 s^2)) + c   (a, u0, v0, s, c)   n = 5        coords 2, t is [2][m]
+ * Append only.  n <= BLSQ_MODEL_MAX_N.
+ * blsq_model_info: the name and the rule for n (n_per_term == 0: n == n_base; otherwise n = n_base + K n_per_term,
+ * K >= 1); any output may be NULL; needs no device.  Non-zero for an unknown model. */
+enum { BLSQ_MODEL_POLY = 0, BLSQ_MODEL_EXP_SUM, BLSQ_MODEL_GAUSS_SUM, BLSQ_MODEL_LORENTZ_SUM, BLSQ_MODEL_GAUSS2D };
+#define BLSQ_MODEL_MAX_N 64
+int blsq_model_count(void);
+int blsq_model_info(int model, const char** name, int* coords, int* n_base, int* n_per_term);
+/* For the points P [B * reps][n] (the points of problem b are rows b * reps .. b * reps + reps - 1; reps > 1 serves the
+ * finite-difference points of blsq_fd_points_dev):
+ *   f[q][i]    = w[b][i] * (model(t[b][.., i]; P[q]) - y[b][i])        df [B * reps][m], or NULL
+ *   J[q][i][j] = w[b][i] * d model / d p_j                             dJ [B][m][n], or NULL; reps must be 1
+ * dt: [coords][m] shared by all problems (t_stride 0) or [B][coords][m] (t_stride coords * m); dy: [B][m] or NULL (0:
+ * plain prediction); dw: NULL (1), [m] (w_stride 0) or [B][m] (w_stride m); dmask: int32 [B] or NULL: a problem with
+ * dmask[b] == 0 is left untouched in both outputs (the jac callback under a robust loss, blsq_outer_set_loss).
+ * Nothing is checked on the device: non-finite values (s = 0) pass through as IEEE arithmetic gives them.  All pointers
+ * are device pointers; asynchronous on the ctx stream.  A negative return is the index of the bad argument. */
+int blsq_model_eval_dev(blsq_ctx* ctx, int model, int B, int reps, int m, int n, const double* dt, long t_stride,
+                        const double* dy, const double* dw, long w_stride, const double* dP, double* df, double* dJ,
+                        const int32_t* dmask);
+
 /* ---- parameter covariance from the final Jacobian --------------------------------------------------------------
  * The reference documents `x_covariance` as the inverse of J^T J at the solution (least_squares.py:248-252) and fills
  * it only through its MINPACK bridge (method='lm').  Here, per problem, from a Householder triangle R of J (the TSQR
