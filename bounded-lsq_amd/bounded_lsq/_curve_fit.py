@@ -15,6 +15,7 @@ from ._frontend import least_squares
 from ._batch import least_squares_batch
 from ._hostmath import prepare_bounds
 from . import _models
+from ._params import ParamMap
 
 __all__ = ['curve_fit', 'curve_fit_batch']
 
@@ -86,8 +87,16 @@ def _wrap_jac(jac, xdata, transform):
     return lambda params: solve_triangular(transform, np.asarray(jac(xdata, *params)), lower=True)
 
 
+def _param_map(n, fixed, tied):
+    """The ParamMap of the `fixed` / `tied` keywords, or None where they hold nothing (then nothing changes)."""
+    if fixed is None and not tied:
+        return None
+    pm = ParamMap(n, fixed, tied)
+    return None if pm.identity else pm
+
+
 def curve_fit(f, xdata, ydata, p0=None, sigma=None, absolute_sigma=False, check_finite=True,
-              bounds=(-np.inf, np.inf), method=None, jac=None, full_output=False, **kwargs):
+              bounds=(-np.inf, np.inf), method=None, jac=None, full_output=False, fixed=None, tied=None, **kwargs):
     """Fit ``ydata = f(xdata, *p) + eps`` by non-linear least squares; returns ``(popt, pcov)``.
 
     Parameters, exceptions, warnings and results are scipy.optimize.curve_fit's (1.15.3):
@@ -108,7 +117,21 @@ def curve_fit(f, xdata, ydata, p0=None, sigma=None, absolute_sigma=False, check_
       * ``method=None`` always means 'trf' (scipy chooses 'lm' for an unbounded problem); ``method='lm'`` raises
         ``NotImplementedError`` here as in ``least_squares``: there is no MINPACK bridge on this step path;
       * ``nan_policy`` is not taken.
+
+    fixed, tied : hold parameters at their `p0` (a boolean mask (n,) or indices) and make parameter j a copy of
+    parameter i (``{j: i}``), as ``curve_fit_batch``; `p0` is then required (ValueError).  `f` and a callable `jac`
+    still take and return all n parameters; the solver works on the nf remaining variables (``jac=None`` differentiates
+    those), `popt` (n,) has the fixed values and tied copies filled in, `pcov` (n, n) has zero rows and columns for
+    fixed parameters and copied ones for tied parameters, and the degrees of freedom are m - nf.
     """
+    pm = None
+    if fixed is not None or tied:
+        if p0 is None:
+            raise ValueError("`p0` is required with `fixed` or `tied`.")
+        pm = _param_map(np.atleast_1d(p0).size, fixed, tied)
+    if pm is not None:
+        return _curve_fit_mapped(pm, f, xdata, ydata, p0, sigma, absolute_sigma, check_finite, bounds, method, jac,
+                                 full_output, kwargs)
     if p0 is None:
         args = getfullargspec(f).args
         if len(args) < 2:
@@ -190,8 +213,31 @@ def curve_fit(f, xdata, ydata, p0=None, sigma=None, absolute_sigma=False, check_
     return popt, pcov
 
 
+def _curve_fit_mapped(pm, f, xdata, ydata, p0, sigma, absolute_sigma, check_finite, bounds, method, jac, full_output,
+                      kwargs):
+    """``curve_fit`` over the nf variables of `pm`: the same function on wrapped callables, results expanded."""
+    Pfix = np.array(np.atleast_1d(p0), dtype=float)
+    if hasattr(bounds, 'lb') and hasattr(bounds, 'ub'):
+        bounds = (bounds.lb, bounds.ub)
+    lb, ub = prepare_bounds(bounds, np.empty(pm.n))
+    if lb.shape != (pm.n,) or ub.shape != (pm.n,):
+        raise ValueError("Inconsistent shapes between bounds and `p0`.")
+    lbr, ubr = pm.reduce_bounds(lb, ub)
+
+    def fr(x, *xv):
+        return f(x, *pm.expand_x(np.asarray(xv, dtype=float), Pfix))
+    jr = jac
+    if callable(jac):
+        def jr(x, *xv):
+            return pm.reduce_jac(np.asarray(jac(x, *pm.expand_x(np.asarray(xv, dtype=float), Pfix))))
+    out = curve_fit(fr, xdata, ydata, p0=pm.reduce_x(Pfix), sigma=sigma, absolute_sigma=absolute_sigma,
+                    check_finite=check_finite, bounds=(lbr, ubr), method=method, jac=jr, full_output=full_output,
+                    **kwargs)
+    return (pm.expand_x(out[0], Pfix), pm.expand_cov(out[1])) + tuple(out[2:])
+
+
 def curve_fit_batch(f, xdata, ydata, p0, sigma=None, absolute_sigma=False, bounds=(-np.inf, np.inf), method='trf',
-                    jac=None, driver='host', ctx=None, **kwargs):
+                    jac=None, driver='host', ctx=None, fixed=None, tied=None, **kwargs):
     """``curve_fit`` for B data sets of one model, solved together by ``least_squares_batch``.
 
     f : ``f(xdata, P) -> (B, m)`` for parameters ``P`` of shape (B, n): vectorised over the batch — or the name of a
@@ -208,6 +254,19 @@ def curve_fit_batch(f, xdata, ydata, p0, sigma=None, absolute_sigma=False, bound
             default) is '2-point' for a callable `f` and the analytic Jacobian for a named model, whose '2-point' /
             '3-point' are estimated on the device from the kernel's values (a callable `jac` with a name: ValueError)
     driver, ctx, **kwargs : as ``least_squares_batch`` (tolerances, ``max_nfev`` / ``maxfev``, ``loss=``, ...).
+    fixed : None, a boolean mask (n,) or a sequence of indices, shared by all problems: parameter j of problem b is
+            held at ``p0[b, j]`` (its bounds are ignored).
+    tied : None or ``{j: i}``: parameter j is a copy of parameter i (its own `p0` is ignored; the box of the group
+            is the intersection of its members' boxes).  See ``bounded_lsq.ParamMap`` for the rules.
+            The solver then works on the nf <= n remaining variables: `p0` and `bounds` are still given for all n,
+            a callable `f` / `jac` still takes (B, n) and returns (B, m) / (B, m, n), finite differences are taken
+            over the nf variables, and a named model with driver='device' is evaluated through the map on the GPU
+            (blsq_model_eval_map_dev: the Jacobian is computed and stored nf wide).  `popt` (B, n) has the fixed
+            values and tied copies filled in; `pcov` (B, n, n) has zero rows and columns for fixed parameters and
+            copied ones for tied parameters, and its variance factor is ``obj_value / (m - nf)``.  ``results[b]``
+            carries ``x`` (n,), ``x_free`` (nf,), ``param_map`` (n,), ``active_mask`` (n,) and ``x_covariance``
+            (n, n) expanded the same way; its ``jac`` (m, nf) is the Jacobian with respect to the SOLVER's variables
+            (a tied group's column is the sum of its members').  With both empty nothing changes.
 
     Returns ``(popt (B, n), pcov (B, n, n), results)``, `results` the B ``OptimizeResult`` of the solve.  pcov[b] is
     ``curve_fit``'s for problem b alone: the pseudo-inverse covariance of its final Jacobian, times
@@ -228,6 +287,7 @@ def curve_fit_batch(f, xdata, ydata, p0, sigma=None, absolute_sigma=False, bound
     if P0.ndim != 2 or P0.shape[0] != B:
         raise ValueError("`p0` must have shape (B, n).")
     n = P0.shape[1]
+    pm = _param_map(n, fixed, tied)
     model = None
     if isinstance(f, str):
         model = _models.get(f)
@@ -258,8 +318,22 @@ def curve_fit_batch(f, xdata, ydata, p0, sigma=None, absolute_sigma=False, bound
         else:
             raise ValueError("`sigma` has incorrect shape.")
 
+    if pm is not None:                           # the solver sees nf variables; f and jac see all n
+        if len(bounds) != 2:
+            raise ValueError("`bounds` must contain 2 elements.")
+        bounds = pm.reduce_bounds(np.broadcast_to(np.asarray(bounds[0], dtype=float), (B, n)),
+                                  np.broadcast_to(np.asarray(bounds[1], dtype=float), (B, n)))
+        x_start = pm.reduce_x(P0)
+        if callable(f):
+            f = pm.wrap_f(f, P0)
+        if callable(jac):
+            jac = pm.wrap_jac(jac, P0)
+    else:
+        x_start = P0
+    nv = x_start.shape[1]                        # solver variables: n, or nf
+
     if model is not None and driver == 'device':
-        func = _models.DeviceFit(model.name, n, xdata, ydata, sigma)
+        func = _models.DeviceFit(model.name, n, xdata, ydata, sigma, param_map=pm, Pfix=None if pm is None else P0)
     elif transform is None:
         def func(P):
             return np.asarray(f(xdata, P), float) - ydata
@@ -280,18 +354,29 @@ def curve_fit_batch(f, xdata, ydata, p0, sigma=None, absolute_sigma=False, bound
     if 'max_nfev' not in kwargs:
         kwargs['max_nfev'] = kwargs.pop('maxfev', None)
 
-    scale_on_gpu = (not absolute_sigma) and m > n
-    results = least_squares_batch(func, P0, jac, bounds=bounds, method=method, driver=driver, ctx=ctx,
+    scale_on_gpu = (not absolute_sigma) and m > nv
+    results = least_squares_batch(func, x_start, jac, bounds=bounds, method=method, driver=driver, ctx=ctx,
                                   covariance='pinv', _variance_scale=scale_on_gpu, **kwargs)
+    if pm is not None:                           # the full-size fields of the results, expanded for the batch at once
+        X_full = pm.expand_x(np.stack([r.x for r in results]), P0)
+        masks = pm.expand_mask(np.stack([np.asarray(r.active_mask) for r in results]))
+        has_cov = [b for b, r in enumerate(results) if r.x_covariance is not None]
+        covs = pm.expand_cov(np.stack([results[b].x_covariance for b in has_cov])) if has_cov else ()
+        for b, r in enumerate(results):
+            r.x_free, r.param_map = r.x, pm.pmap.copy()
+            r.x, r.active_mask = X_full[b], masks[b]
+        for b, C in zip(has_cov, covs):
+            results[b].x_covariance = C
     popt = np.full((B, n), np.nan)
     pcov = np.full((B, n, n), np.nan)
     warn_cov = False
     for b, r in enumerate(results):
         if not r.success:
             continue
-        popt[b] = r.x
         C = r.x_covariance
-        if C is None or np.isnan(C).any() or (not absolute_sigma and m <= n):
+        bad_cov = C is None or np.isnan(C).any() or (not absolute_sigma and m <= nv)
+        popt[b] = r.x
+        if bad_cov:
             pcov[b] = np.inf
             warn_cov = True
         else:

@@ -215,12 +215,20 @@ class DeviceModel:
     (B, m)) once.  ``fun_dev(x_ptr, f_ptr, reps)`` and ``jac_dev(x_ptr, J_ptr, mask_ptr)`` launch the kernel on the
     context's stream — the stream of every driver on that context, so no synchronisation is needed in between.
     ``bounds_dev`` is the (lb_ptr, ub_ptr) pair the finite-difference route asks for, after ``set_bounds(lb, ub)``.
-    ``close()`` frees the buffers (also run when the context closes)."""
+    ``close()`` frees the buffers (also run when the context closes).
 
-    def __init__(self, ctx, name, B, m, n, xdata, ydata=None, sigma=None):
+    With a ``ParamMap`` (`param_map`, and the template `Pfix` (B, n) holding the values of its fixed parameters) the
+    callbacks take the nf solver variables and go through blsq_model_eval_map_dev: ``n`` is then nf,
+    the width of x and J, and ``n_model`` the number of model parameters; `set_bounds` takes reduced bounds."""
+
+    def __init__(self, ctx, name, B, m, n, xdata, ydata=None, sigma=None, param_map=None, Pfix=None):
         model = get(name)
         model.terms(n)
-        self.model, self.B, self.m, self.n = model, int(B), int(m), int(n)
+        self.model, self.B, self.m, self.n_model = model, int(B), int(m), int(n)
+        self.param_map = param_map
+        if param_map is not None and param_map.n != self.n_model:
+            raise ValueError("`param_map` is for %d parameters, the model has %d." % (param_map.n, self.n_model))
+        self.n = self.n_model if param_map is None else param_map.nf
         x, per_problem = model.check_xdata(xdata, self.B, self.m)
         y = w = None
         if ydata is not None:
@@ -243,6 +251,16 @@ class DeviceModel:
         self.d_t = self._upload(x)
         self.d_y = self._upload(y)
         self.d_w = self._upload(w)
+        self.d_Pfix = None
+        if param_map is not None:
+            self._pmap = np.ascontiguousarray(param_map.pmap, dtype=np.int32)
+            if Pfix is None and np.any(self._pmap < 0):
+                raise ValueError("`Pfix` is required when a parameter is fixed.")
+            if Pfix is not None:
+                Pfix = np.ascontiguousarray(Pfix, dtype=np.float64)
+                if Pfix.shape != (self.B, self.n_model):
+                    raise ValueError("`Pfix` must have shape (B, n).")
+                self.d_Pfix = self._upload(Pfix)
         self.bounds_dev = None
         ctx.adopt(self)
 
@@ -259,6 +277,12 @@ class DeviceModel:
         return self.bounds_dev
 
     def _eval(self, x_ptr, reps, f_ptr, J_ptr, mask_ptr):
+        if self.param_map is not None:
+            self.ctx.check(self.ctx.lib.blsq_model_eval_map_dev(
+                self.ctx.h, self.model.id, self.B, int(reps), self.m, self.n_model, self.n,
+                self._pmap.ctypes.data_as(_abi.c_int32_p), self.d_t, self.t_stride, self.d_y, self.d_w, self.w_stride,
+                x_ptr, self.d_Pfix, f_ptr, J_ptr, mask_ptr), "blsq_model_eval_map_dev")
+            return
         self.ctx.check(self.ctx.lib.blsq_model_eval_dev(
             self.ctx.h, self.model.id, self.B, int(reps), self.m, self.n, self.d_t, self.t_stride, self.d_y, self.d_w,
             self.w_stride, x_ptr, f_ptr, J_ptr, mask_ptr), "blsq_model_eval_dev")
@@ -286,19 +310,30 @@ class DeviceModel:
 
 class DeviceFit:
     """What ``least_squares_batch(fun=...)`` takes in place of a callable for a fit whose callbacks run on the device:
-    a checked (model, data) pair that opens a ``DeviceModel`` on the driver's context.  Built by ``curve_fit_batch``."""
+    a checked (model, data) pair that opens a ``DeviceModel`` on the driver's context.  Built by ``curve_fit_batch``.
+    ``n`` is the number of solver variables (the width of x0): the model's n, or nf of `param_map`; ``n_model`` is the
+    model's number of parameters."""
 
-    def __init__(self, name, n, xdata, ydata, sigma=None):
+    def __init__(self, name, n, xdata, ydata, sigma=None, param_map=None, Pfix=None):
         self.model = get(name)
         self.model.terms(n)
         self.ydata = np.ascontiguousarray(ydata, dtype=np.float64)
         self.B, self.m = self.ydata.shape
-        self.n = int(n)
+        self.n_model = int(n)
+        self.param_map, self.Pfix = param_map, Pfix
+        if param_map is not None:
+            if param_map.n != self.n_model:
+                raise ValueError("`param_map` is for %d parameters, the model has %d." % (param_map.n, self.n_model))
+            self.Pfix = np.ascontiguousarray(Pfix, dtype=np.float64)
+            if self.Pfix.shape != (self.B, self.n_model):
+                raise ValueError("`Pfix` must have shape (B, n).")
+        self.n = self.n_model if param_map is None else param_map.nf
         self.xdata, _ = self.model.check_xdata(xdata, self.B, self.m)
         self.sigma = sigma
 
     def open_device(self, ctx, lb, ub):
-        dm = DeviceModel(ctx, self.model.name, self.B, self.m, self.n, self.xdata, self.ydata, self.sigma)
+        dm = DeviceModel(ctx, self.model.name, self.B, self.m, self.n_model, self.xdata, self.ydata, self.sigma,
+                         self.param_map, self.Pfix)
         dm.set_bounds(lb, ub)
         return dm
 

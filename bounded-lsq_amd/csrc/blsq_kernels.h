@@ -615,6 +615,11 @@ hipError_t launch_fd_assemble(int B, int m, int n, int method, const double* x, 
 hipError_t launch_model_eval(int model, int B, int reps, int m, int n, const double* t, long t_stride, const double* y,
                              const double* w, long w_stride, const double* P, double* f, double* J, const int* mask,
                              hipStream_t s);
+// The same through a parameter map (blsq_model_eval_map_dev, 7k): X [B * reps][nf], pmap [n] on the host (-1 or a slot
+// < nf, every slot used: the caller has checked), Pfix [B][n] (read where pmap[j] == -1), J [B][m][nf].
+hipError_t launch_model_eval_map(int model, int B, int reps, int m, int n, int nf, const int* pmap, const double* t,
+                                 long t_stride, const double* y, const double* w, long w_stride, const double* X,
+                                 const double* Pfix, double* f, double* J, const int* mask, hipStream_t s);
 
 // ---------------------------------------------------------------- probes ----
 // probe_kernels.hip: measured peaks / counter calibration (blsq_debug_probe)

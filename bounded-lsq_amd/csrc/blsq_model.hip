@@ -1,5 +1,5 @@
 // Built-in fit models: the table behind blsq_model_count / blsq_model_info and the entry point blsq_model_eval_dev
-// (include/blsq.h; kernel: model_kernels.hip).
+// (include/blsq.h; kernel: model_kernels.hip) and its mapped form blsq_model_eval_map_dev (7k).
 #include "blsq_host.h"
 
 namespace {
@@ -55,5 +55,41 @@ extern "C" int blsq_model_eval_dev(blsq_ctx* ctx, int model, int B, int reps, in
   HIPCHK(ctx, hipSetDevice(ctx->device));
   return ctx->run(K_MODEL_EVAL, "launch_model_eval", [&] {
     return launch_model_eval(model, B, reps, m, n, dt, t_stride, dy, dw, w_stride, dP, df, dJ, dmask, ctx->stream);
+  });
+}
+
+extern "C" int blsq_model_eval_map_dev(blsq_ctx* ctx, int model, int B, int reps, int m, int n, int nf,
+                                       const int32_t* pmap, const double* dt, long t_stride, const double* dy,
+                                       const double* dw, long w_stride, const double* dX, const double* dPfix,
+                                       double* df, double* dJ, const int32_t* dmask) {
+  if (!ctx) return -1;
+  if (model < 0 || model >= kModelCount) return ctx->bad(2, "model must be one of BLSQ_MODEL_*");
+  const ModelRow& r = kModels[model];
+  if (B <= 0) return ctx->bad(3, "B must be positive");
+  if (reps <= 0) return ctx->bad(4, "reps must be positive");
+  if (m <= 0) return ctx->bad(5, "m must be positive");
+  if (!model_n_fits(r, n)) return ctx->bad(6, "n does not fit the model (or exceeds BLSQ_MODEL_MAX_N)");
+  if (nf < 1 || nf > n) return ctx->bad(7, "nf must be in 1 .. n");
+  if (!pmap) return ctx->bad(8, "pmap is NULL");
+  bool used[BLSQ_MODEL_MAX_N] = {};
+  bool any_fixed = false;
+  for (int j = 0; j < n; ++j) {
+    if (pmap[j] < -1 || pmap[j] >= nf) return ctx->bad(19, "pmap entry outside -1 .. nf - 1");
+    if (pmap[j] < 0) any_fixed = true;
+    else used[pmap[j]] = true;
+  }
+  for (int k = 0; k < nf; ++k)
+    if (!used[k]) return ctx->bad(20, "pmap leaves a variable k < nf unused");
+  if (!dt) return ctx->bad(9, "t is NULL");
+  if (t_stride != 0 && t_stride != (long)r.coords * m) return ctx->bad(10, "t_stride must be 0 or coords * m");
+  if (dw && w_stride != 0 && w_stride != (long)m) return ctx->bad(13, "w_stride must be 0 or m");
+  if (!dX) return ctx->bad(14, "X is NULL");
+  if (any_fixed && !dPfix) return ctx->bad(15, "Pfix is NULL although pmap holds a parameter fixed");
+  if (!df && !dJ) return ctx->bad(16, "f and J are both NULL");
+  if (dJ && reps != 1) return ctx->bad(17, "J requires reps == 1");
+  HIPCHK(ctx, hipSetDevice(ctx->device));
+  return ctx->run(K_MODEL_EVAL, "launch_model_eval_map", [&] {
+    return launch_model_eval_map(model, B, reps, m, n, nf, pmap, dt, t_stride, dy, dw, w_stride, dX, dPfix, df, dJ,
+                                 dmask, ctx->stream);
   });
 }

@@ -418,6 +418,22 @@ int blsq_model_info(int model, const char** name, int* coords, int* n_base, int*
 int blsq_model_eval_dev(blsq_ctx* ctx, int model, int B, int reps, int m, int n, const double* dt, long t_stride,
                         const double* dy, const double* dw, long w_stride, const double* dP, double* df, double* dJ,
                         const int32_t* dmask);
+/* The same model through a parameter map (fixed and tied parameters of a curve fit): the n parameters of the model are a
+ * function of nf <= n solver variables X [B * reps][nf] and a per-problem template Pfix [B][n],
+ *   P_full[q][j] = X[q][pmap[j]]   if pmap[j] >= 0,      Pfix[b][j]   if pmap[j] == -1            (q = b * reps + r)
+ *   f[q][i]    = the f of blsq_model_eval_dev at P_full[q], bit for bit                            df [B * reps][m]
+ *   J[q][i][k] = sum over {j : pmap[j] == k}, in ascending j, of the J[q][i][j] of blsq_model_eval_dev at P_full[q]:
+ *                the first column of a slot is stored and the later ones are added to it, a sequential float64 sum;
+ *                columns with pmap[j] == -1 are dropped                                            dJ [B][m][nf]
+ * pmap: HOST pointer, int32 [n], read during the call (it travels in the kernel arguments: no device buffer); every
+ * entry in -1 .. nf - 1 and every k < nf used by at least one j.  The identity (nf == n, pmap[j] == j) is accepted.
+ * dPfix may be NULL when no entry is -1; where pmap[j] >= 0 its column j is not read.  Everything else as
+ * blsq_model_eval_dev.  A negative return is the index of the bad argument (ctx = 1, model, B, reps, m, n, nf = 7,
+ * pmap = 8, t, t_stride, y, w, w_stride, X = 14, Pfix = 15, f = 16, J = 17, mask), and for the contents of pmap -19 (an
+ * entry outside -1 .. nf - 1) and -20 (a k < nf that no entry names). */
+int blsq_model_eval_map_dev(blsq_ctx* ctx, int model, int B, int reps, int m, int n, int nf, const int32_t* pmap,
+                            const double* dt, long t_stride, const double* dy, const double* dw, long w_stride,
+                            const double* dX, const double* dPfix, double* df, double* dJ, const int32_t* dmask);
 
 /* ---- parameter covariance from the final Jacobian --------------------------------------------------------------
  * The reference documents `x_covariance` as the inverse of J^T J at the solution (least_squares.py:248-252) and fills

@@ -6,7 +6,12 @@ timed (host clock around a call that ends in a download: upload, solve, covarian
 after one warm-up each.  The kernel's own time per call comes from the library's event timing (slot 'model_eval') in a
 further call of the named route, so that the events do not sit inside the timed calls.
 
-usage: python tools/bench_models.py [--B 4096] [--m 64] [--repeat 5]
+With ``--fixed`` / ``--tied`` the named route takes the keywords (the mapped kernel instances) and the
+callable route is what a user has without them: the reduced model over the nf remaining variables as numpy callables
+(the model's numpy functions behind ``ParamMap.wrap_f`` / ``wrap_jac``).  ``--kernel`` times the kernel alone instead:
+`--launches` launches each of f and of J in the 'model_eval' slot, for the unmapped entry and (with a map) the mapped one.
+
+usage: python tools/bench_models.py [--B 4096] [--m 64] [--repeat 5] [--peaks 1] [--fixed 1,4] [--tied 5:2] [--kernel]
 """
 import argparse
 import json
@@ -18,17 +23,52 @@ import numpy as np
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "bounded-lsq_amd"))
-from bounded_lsq import curve_fit_batch, models, _abi                    # noqa: E402
+from bounded_lsq import curve_fit_batch, models, _abi, ParamMap          # noqa: E402
 
 
-def problems(B, m, seed=0):
+PEAKS = {1: [1.5, 0.2, 0.6, 0.3], 2: [1.5, -0.8, 0.4, 1.0, 0.7, 0.5, 0.2]}
+
+
+def problems(B, m, seed=0, peaks=1, fixed=(), tied=None):
+    """The truth satisfies the ties and p0 sits at the truth in the fixed columns."""
     rng = np.random.default_rng(seed)
-    truth = np.array([1.5, 0.2, 0.6, 0.3]) * (1 + 0.05 * rng.uniform(-1, 1, (B, 4)))
+    base = np.array(PEAKS[peaks])
+    truth = base * (1 + 0.05 * rng.uniform(-1, 1, (B, base.size)))
+    for j, i in (tied or {}).items():
+        truth[:, j] = truth[:, i]
     x = np.linspace(-2.0, 2.0, m)
     Y = models.get("gauss_sum").f(x, truth) + 0.01 * rng.standard_normal((B, m))
     P0 = truth * (1 + 0.1 * rng.choice([-1.0, 1.0], truth.shape))
+    P0[:, list(fixed)] = truth[:, list(fixed)]
     half = 0.4 * np.abs(truth) + 0.2
     return x, Y, P0, (truth - half, truth + half)
+
+
+def kernel_times(ctx, x, Y, P0, pm, launches):
+    """ms per launch of f and of J ('model_eval' slot, HIP events) for the unmapped entry at P0 and, with a map, the
+    mapped entry at reduce_x(P0)."""
+    B, m = Y.shape
+    n = P0.shape[1]
+    out = {}
+    for key, mp in (("unmapped", None),) + ((("mapped", pm),) if pm is not None else ()):
+        dm = models.DeviceModel(ctx, "gauss_sum", B, m, n, x, Y, 0.01, param_map=mp, Pfix=None if mp is None else P0)
+        X = P0 if mp is None else np.ascontiguousarray(mp.reduce_x(P0))
+        d_x, d_f, d_J = ctx.to_device(X), ctx.malloc(8 * B * m), ctx.malloc(8 * B * m * dm.n)
+        for what, call in (("f", lambda: dm.fun_dev(d_x, d_f, 1)), ("J", lambda: dm.jac_dev(d_x, d_J))):
+            call()                                                        # warm-up: the code object
+            ctx.sync()
+            ctx.timing(True, only="model_eval")
+            ctx.timing_reset()
+            for _ in range(launches):
+                call()
+            ctx.sync()
+            ms, cnt = ctx.timing_read()["model_eval"]
+            ctx.timing(False)
+            out["%s_%s_us" % (key, what)] = round(1e3 * ms / cnt, 2)
+        for p in (d_x, d_f, d_J):
+            ctx.free(p)
+        dm.close()
+    return out
 
 
 def main():
@@ -36,13 +76,35 @@ def main():
     ap.add_argument("--B", type=int, default=4096)
     ap.add_argument("--m", type=int, default=64)
     ap.add_argument("--repeat", type=int, default=5)
+    ap.add_argument("--peaks", type=int, default=1, choices=sorted(PEAKS))
+    ap.add_argument("--fixed", default="", help="indices held at p0, e.g. 1,4")
+    ap.add_argument("--tied", default="", help="j:i pairs (p_j is p_i), e.g. 5:2")
+    ap.add_argument("--kernel", action="store_true", help="time the kernel's launches alone")
+    ap.add_argument("--launches", type=int, default=50)
     a = ap.parse_args()
-    x, Y, P0, bounds = problems(a.B, a.m)
+    fixed = [int(v) for v in a.fixed.split(",") if v]
+    tied = {int(p.split(":")[0]): int(p.split(":")[1]) for p in a.tied.split(",") if p}
+    x, Y, P0, bounds = problems(a.B, a.m, peaks=a.peaks, fixed=fixed, tied=tied)
+    n = P0.shape[1]
     M = models.get("gauss_sum")
+    pm = ParamMap(n, fixed, tied) if (fixed or tied) else None
     ctx = _abi.Context(0)
+    if a.kernel:
+        res = {"model": "gauss_sum", "B": a.B, "m": a.m, "n": n, "nf": n if pm is None else pm.nf, "fixed": fixed,
+               "tied": a.tied, "launches": a.launches}
+        res.update(kernel_times(ctx, x, Y, P0, pm, a.launches))
+        ctx.close()
+        print(json.dumps(res))
+        return
     kw = dict(sigma=0.01, bounds=bounds, driver="device", ctx=ctx, ftol=1e-10, xtol=1e-10, gtol=1e-10)
-    routes = {"named": lambda: curve_fit_batch("gauss_sum", x, Y, P0, **kw),
-              "callable": lambda: curve_fit_batch(M.f, x, Y, P0, jac=M.jac, **kw)}
+    if pm is None:
+        routes = {"named": lambda: curve_fit_batch("gauss_sum", x, Y, P0, **kw),
+                  "callable": lambda: curve_fit_batch(M.f, x, Y, P0, jac=M.jac, **kw)}
+    else:
+        kw_red = dict(kw, bounds=pm.reduce_bounds(*bounds))
+        f_red, jac_red, X0 = pm.wrap_f(M.f, P0), pm.wrap_jac(M.jac, P0), pm.reduce_x(P0)
+        routes = {"named": lambda: curve_fit_batch("gauss_sum", x, Y, P0, fixed=fixed, tied=tied, **kw),
+                  "callable": lambda: curve_fit_batch(f_red, x, Y, X0, jac=jac_red, **kw_red)}
     times = {k: [] for k in routes}
     out = {}
     for k, run in routes.items():                                         # warm-up: code objects, plans
@@ -61,7 +123,8 @@ def main():
     ctx.timing(False)
     ok = {k: int(sum(r.success for r in out[k][2])) for k in routes}
     both = np.array([ra.success and rb.success for ra, rb in zip(out["named"][2], out["callable"][2])])
-    res = {"model": "gauss_sum", "B": a.B, "m": a.m, "n": 4, "driver": "device",
+    free = (lambda P: P) if pm is None else pm.reduce_x
+    res = {"model": "gauss_sum", "B": a.B, "m": a.m, "n": n, "nf": n if pm is None else pm.nf, "driver": "device",
            "named_s": round(float(np.median(times["named"])), 4),
            "callable_s": round(float(np.median(times["callable"])), 4),
            "named_all_s": [round(t, 4) for t in times["named"]],
@@ -70,7 +133,7 @@ def main():
            "kernel_ms_per_fit": round(k_ms, 3), "kernel_launches_per_fit": int(k_n),
            "kernel_us_per_launch": round(1e3 * k_ms / max(k_n, 1), 2),
            "converged": ok, "max_nfev": int(max(r.nfev for r in out["named"][2])),
-           "popt_max_rel_diff": float(np.max(np.abs(out["named"][0][both] - out["callable"][0][both])
+           "popt_max_rel_diff": float(np.max(np.abs(free(out["named"][0])[both] - out["callable"][0][both])
                                              / (np.abs(out["callable"][0][both]) + 1e-3)))}
     ctx.close()
     print(json.dumps(res))
