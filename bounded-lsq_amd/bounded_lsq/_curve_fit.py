@@ -242,7 +242,9 @@ def curve_fit_batch(f, xdata, ydata, p0, sigma=None, absolute_sigma=False, bound
 
     f : ``f(xdata, P) -> (B, m)`` for parameters ``P`` of shape (B, n): vectorised over the batch — or the name of a
         built-in model (``bounded_lsq.models``: 'poly', 'exp_sum', 'gauss_sum', 'lorentz_sum', 'gauss2d'; n = p0.shape[1]
-        fixes the number of terms).  A named model with driver='device' is evaluated on the GPU, residuals and
+        fixes the number of terms) — or a composite: a spec such as 'gauss*2+lorentz+poly*2' (``models.compose``: a sum
+        of gauss / lorentz / pvoigt / exp terms and polynomials, whose n the spec fixes) or a ``CompositeModel``,
+        treated exactly as a name.  A named model with driver='device' is evaluated on the GPU, residuals and
         Jacobians alike: between the start of the solve and its results only two counters per iteration leave the
         device.  With driver='host' the model's numpy functions are the callbacks.  `xdata` is then (m,) or (B, m)
         — (2, m) or (B, 2, m) for 'gauss2d'.  A wrong name, an n that does not fit the model or a wrong `xdata` shape
@@ -289,8 +291,9 @@ def curve_fit_batch(f, xdata, ydata, p0, sigma=None, absolute_sigma=False, bound
     n = P0.shape[1]
     pm = _param_map(n, fixed, tied)
     model = None
-    if isinstance(f, str):
-        model = _models.get(f)
+    if isinstance(f, (str, _models.CompositeModel)):
+        model = _models.resolve(f)
+        f = model.name
         model.terms(n)
         xdata, _ = model.check_xdata(xdata, B, m)
         if callable(jac):

@@ -16,14 +16,36 @@ of each model: the kernel evaluates the same formulas operation by operation (it
 the two differ by the last bit of exp() only.  They are vectorised over the batch, keep the dtype of their inputs
 (np.longdouble inputs give a longdouble reference) and check nothing: a non-finite value (s = 0) passes through.
 They are also the ``driver='host'`` route of ``curve_fit_batch(f='name')``.
+
+Composite models (``compose``; blsq_model_eval_comp_dev).  ``compose('gauss*2+lorentz+poly*2')`` is a sum of
+components chosen at run time, each ``family`` or ``family*K`` (K >= 1) of
+
+    family    term                                                             parameters per term
+    gauss     a exp(-z^2 / 2),  z = (t - mu) / s                               3: (a, mu, s)
+    lorentz   a / (1 + z^2)                                                    3: (a, mu, s)
+    pvoigt    a [G + eta (L - G)],  G = exp(-ln2 z^2),  L = 1 / (1 + z^2)      4: (a, mu, s, eta)   (s: the HWHM of both)
+    exp       a exp(-r t)                                                      2: (a, r)
+    poly      ``poly*d``: p_0 + p_1 t + ... + p_{d-1} t^{d-1} by Horner        1: d coefficients
+
+with no implicit offset (a constant is ``poly*1``), at most 8 components and 1 <= n <= 64.  The parameters are the
+concatenation of the components' slices in spec order; a component's value is the sum of its terms in ascending order,
+the model the sequential sum of the component values.  The terms are computed by the functions the five families use, so
+``gauss*K+poly*1`` is ``gauss_sum`` bit for bit (and likewise lorentz, exp and ``poly*n``).  Wherever a name is taken
+(``curve_fit_batch``, ``DeviceModel``, ``DeviceFit``, ``evaluate``) a spec string or a ``CompositeModel`` is as well
+(``resolve``).
 """
+import re
+
 import numpy as np
 
 from . import _abi
 
 MAX_N = 64                                   # BLSQ_MODEL_MAX_N
+MAX_COMP = 8                                 # BLSQ_MODEL_MAX_COMP
+LN2 = 0.6931471805599453
 
-__all__ = ['MODELS', 'NAMES', 'MAX_N', 'get', 'evaluate', 'DeviceModel', 'DeviceFit']
+__all__ = ['MODELS', 'NAMES', 'MAX_N', 'MAX_COMP', 'TERMS', 'get', 'compose', 'resolve', 'CompositeModel', 'evaluate',
+           'DeviceModel', 'DeviceFit']
 
 
 def _tp(xdata, P):
@@ -58,8 +80,9 @@ def _poly_jac(xdata, P):
     return J
 
 
-def _exp_terms(t, P):
-    for k in range((P.shape[1] - 1) // 2):
+def _exp_terms(t, P, K=None):
+    """k, e (d / da), g (the term) of the K decays at the front of P (default: all but the offset)."""
+    for k in range((P.shape[1] - 1) // 2 if K is None else K):
         a, r = _col(P, 2 * k), _col(P, 2 * k + 1)
         e = np.exp(-(r * t))
         yield k, e, a * e
@@ -84,9 +107,9 @@ def _exp_jac(xdata, P):
     return J
 
 
-def _peak_terms(t, P, lorentz):
-    """k, e (d / da), g (the term), dmu, z of every peak."""
-    for k in range((P.shape[1] - 1) // 3):
+def _peak_terms(t, P, lorentz, K=None):
+    """k, e (d / da), g (the term), dmu, z of the K peaks at the front of P (default: all but the offset)."""
+    for k in range((P.shape[1] - 1) // 3 if K is None else K):
         a, mu, s = _col(P, 3 * k), _col(P, 3 * k + 1), _col(P, 3 * k + 2)
         z = (t - mu) / s
         if lorentz:
@@ -208,8 +231,180 @@ def get(name):
     return MODELS[name]
 
 
+# ---- composite models ----------------------------------------------------------------------------------------------
+def _pvoigt_terms(t, P, K):
+    """k, h (d / da), g (the term), dmu, z, a d (d / deta) of the K pseudo-Voigt peaks at the front of P."""
+    for k in range(K):
+        a, mu, s, eta = (_col(P, 4 * k + i) for i in range(4))
+        z = (t - mu) / s
+        q = z * z
+        G = np.exp(-(LN2 * q))
+        L = 1.0 / (1.0 + q)
+        d = L - G
+        h = G + eta * d
+        g = a * h
+        lg = LN2 * G
+        u = lg + eta * (L * L - lg)
+        dmu = (((2.0 * a) * u) * z) / s
+        yield k, h, g, dmu, z, a * d
+
+
+def _fill_exp(t, P, K, J):
+    acc = None
+    for k, e, g in _exp_terms(t, P, K):
+        acc = g if acc is None else acc + g
+        if J is not None:
+            J[:, :, 2 * k] = e
+            J[:, :, 2 * k + 1] = -(t * g)
+    return acc
+
+
+def _fill_peak(lorentz):
+    def fill(t, P, K, J):
+        acc = None
+        for k, e, g, dmu, z in _peak_terms(t, P, lorentz, K):
+            acc = g if acc is None else acc + g
+            if J is not None:
+                J[:, :, 3 * k] = e
+                J[:, :, 3 * k + 1] = dmu
+                J[:, :, 3 * k + 2] = dmu * z
+        return acc
+    return fill
+
+
+def _fill_pvoigt(t, P, K, J):
+    acc = None
+    for k, h, g, dmu, z, deta in _pvoigt_terms(t, P, K):
+        acc = g if acc is None else acc + g
+        if J is not None:
+            J[:, :, 4 * k] = h
+            J[:, :, 4 * k + 1] = dmu
+            J[:, :, 4 * k + 2] = dmu * z
+            J[:, :, 4 * k + 3] = deta
+    return acc
+
+
+def _fill_poly(t, P, K, J):
+    if J is not None:
+        J[:, :, :] = _poly_jac(t, P)
+    return _poly_f(t, P)
+
+
+class Term:
+    """One row of the term table: ``id`` (BLSQ_TERM_*), ``name``, ``n_per_term``, the names of a term's parameters and
+    ``fill(t, P, K, J) -> value``: the component's value for its slice P (B, K n_per_term), its columns written into the
+    view J (B, m, K n_per_term) unless J is None."""
+
+    def __init__(self, id, name, n_per_term, params, fill):
+        self.id, self.name, self.n_per_term, self.params, self.fill = id, name, n_per_term, params, fill
+
+
+TERMS = {t.name: t for t in (
+    Term(0, 'gauss', 3, ('a', 'mu', 's'), _fill_peak(False)),
+    Term(1, 'lorentz', 3, ('a', 'mu', 's'), _fill_peak(True)),
+    Term(2, 'pvoigt', 4, ('a', 'mu', 's', 'eta'), _fill_pvoigt),
+    Term(3, 'exp', 2, ('a', 'r'), _fill_exp),
+    Term(4, 'poly', 1, None, _fill_poly),
+)}
+
+
+class CompositeModel:
+    """A sum of components ``((family, K), ...)``, built by ``compose``; offers what a ``Model`` offers its callers:
+    ``name`` (the canonical spec), ``coords`` (1), ``n``, ``terms``, ``check_xdata``, the numpy ``f`` / ``jac`` — and
+    ``components`` and ``param_names``."""
+
+    coords = 1
+    check_xdata = Model.check_xdata
+
+    def __init__(self, components):
+        self.components = tuple((str(fam), int(K)) for fam, K in components)
+        self.name = "+".join("%s*%d" % c for c in self.components)
+        self.n = sum(K * TERMS[fam].n_per_term for fam, K in self.components)
+        names, seen = [], {}                     # 'gauss1.mu': the second gauss term of the spec; 'poly0.p2'
+        for fam, K in self.components:
+            T = TERMS[fam]
+            for k in range(1 if T.params is None else K):
+                i = seen[fam] = seen.get(fam, -1) + 1
+                names += (["%s%d.p%d" % (fam, i, d) for d in range(K)] if T.params is None
+                          else ["%s%d.%s" % (fam, i, q) for q in T.params])
+        self.param_names = tuple(names)
+        self.fam_ids = np.array([TERMS[fam].id for fam, K in self.components], dtype=np.int32)
+        self.counts = np.array([K for fam, K in self.components], dtype=np.int32)
+
+    def terms(self, n):
+        """The total number of terms; ValueError unless n is the spec's n."""
+        if int(n) != self.n:
+            raise ValueError("model '%s' does not take n = %d parameters (n = %d)." % (self.name, int(n), self.n))
+        return int(self.counts.sum())
+
+    def rule(self):
+        return "n = %d" % self.n
+
+    def _walk(self, xdata, P, want_J):
+        t, P = _tp(xdata, P)
+        if P.shape[1] != self.n:
+            raise ValueError("model '%s' does not take n = %d parameters (n = %d)." % (self.name, P.shape[1], self.n))
+        J = np.empty((P.shape[0], t.shape[-1], self.n), dtype=P.dtype) if want_J else None
+        acc, o = None, 0
+        for fam, K in self.components:
+            T = TERMS[fam]
+            w = K * T.n_per_term
+            v = T.fill(t, P[:, o:o + w], K, None if J is None else J[:, :, o:o + w])
+            acc = v if acc is None else acc + v
+            o += w
+        return acc, J
+
+    def f(self, xdata, P):
+        return self._walk(xdata, P, False)[0]
+
+    def jac(self, xdata, P):
+        return self._walk(xdata, P, True)[1]
+
+    def __repr__(self):
+        return "CompositeModel(%r)" % self.name
+
+
+def compose(spec):
+    """The ``CompositeModel`` of `spec`: components ``family`` or ``family*K`` (K >= 1) joined by ``+``, whitespace
+    ignored; ValueError naming the offending piece otherwise."""
+    if not isinstance(spec, str):
+        raise ValueError("a composite model is given as a string such as 'gauss*2+poly*1', not %r." % (spec,))
+    pieces = re.sub(r"\s+", "", spec).split("+")
+    if len(pieces) > MAX_COMP:
+        raise ValueError("composite model %r has %d components, more than %d." % (spec, len(pieces), MAX_COMP))
+    comps = []
+    for piece in pieces:
+        if not piece:
+            raise ValueError("composite model %r has an empty component." % spec)
+        fam, star, count = piece.partition("*")
+        if fam not in TERMS:
+            raise ValueError("unknown family %r in composite model %r: a family is one of %s."
+                             % (fam, spec, ", ".join(TERMS)))
+        K = 1
+        if star:
+            if not re.fullmatch(r"[+-]?[0-9]+", count):
+                raise ValueError("component %r of composite model %r: the count must be an integer K >= 1." % (piece, spec))
+            K = int(count)
+        if K < 1:
+            raise ValueError("component %r of composite model %r: K must be at least 1." % (piece, spec))
+        comps.append((fam, K))
+    M = CompositeModel(comps)
+    if M.n > MAX_N:
+        raise ValueError("composite model %r has n = %d parameters, more than %d." % (spec, M.n, MAX_N))
+    return M
+
+
+def resolve(f):
+    """A ``CompositeModel`` as it is; a string holding ``+`` or ``*`` through ``compose``; anything else through ``get``."""
+    if isinstance(f, CompositeModel):
+        return f
+    if isinstance(f, str) and ("+" in f or "*" in f):
+        return compose(f)
+    return get(f)
+
+
 class DeviceModel:
-    """Model `name` with its data resident on the GPU: the device callbacks of ``OuterDriver.run_device``.
+    """Model `name` (a name, a composite spec or a ``CompositeModel``) with its data resident on the GPU: the device callbacks of ``OuterDriver.run_device``.
 
     Uploads t = xdata, y = ydata (None: 0, plain prediction) and w = 1 / sigma (None: 1; sigma a scalar, (m,) or
     (B, m)) once.  ``fun_dev(x_ptr, f_ptr, reps)`` and ``jac_dev(x_ptr, J_ptr, mask_ptr)`` launch the kernel on the
@@ -222,7 +417,7 @@ class DeviceModel:
     the width of x and J, and ``n_model`` the number of model parameters; `set_bounds` takes reduced bounds."""
 
     def __init__(self, ctx, name, B, m, n, xdata, ydata=None, sigma=None, param_map=None, Pfix=None):
-        model = get(name)
+        model = resolve(name)
         model.terms(n)
         self.model, self.B, self.m, self.n_model = model, int(B), int(m), int(n)
         self.param_map = param_map
@@ -277,6 +472,15 @@ class DeviceModel:
         return self.bounds_dev
 
     def _eval(self, x_ptr, reps, f_ptr, J_ptr, mask_ptr):
+        if isinstance(self.model, CompositeModel):            # with or without a map: one entry
+            M = self.model
+            self.ctx.check(self.ctx.lib.blsq_model_eval_comp_dev(
+                self.ctx.h, len(M.components), M.fam_ids.ctypes.data_as(_abi.c_int32_p),
+                M.counts.ctypes.data_as(_abi.c_int32_p), self.B, int(reps), self.m, self.n_model, self.n,
+                None if self.param_map is None else self._pmap.ctypes.data_as(_abi.c_int32_p), self.d_t, self.t_stride,
+                self.d_y, self.d_w, self.w_stride, x_ptr, self.d_Pfix, f_ptr, J_ptr, mask_ptr),
+                "blsq_model_eval_comp_dev")
+            return
         if self.param_map is not None:
             self.ctx.check(self.ctx.lib.blsq_model_eval_map_dev(
                 self.ctx.h, self.model.id, self.B, int(reps), self.m, self.n_model, self.n,
@@ -315,7 +519,7 @@ class DeviceFit:
     model's number of parameters."""
 
     def __init__(self, name, n, xdata, ydata, sigma=None, param_map=None, Pfix=None):
-        self.model = get(name)
+        self.model = resolve(name)
         self.model.terms(n)
         self.ydata = np.ascontiguousarray(ydata, dtype=np.float64)
         self.B, self.m = self.ydata.shape
@@ -340,8 +544,9 @@ class DeviceFit:
 
 def evaluate(name, xdata, P, ctx=None):
     """Predictions ``model(xdata; P[b])`` of shape (B, m), computed on the GPU (the kernel with y = NULL, w = NULL).
-    P: (B, n); xdata: (m,) / (B, m), or (2, m) / (B, 2, m) for 'gauss2d'."""
-    model = get(name)
+    P: (B, n); xdata: (m,) / (B, m), or (2, m) / (B, 2, m) for 'gauss2d'.  `name`: a name, a composite spec or a
+    ``CompositeModel``."""
+    model = resolve(name)
     P = np.ascontiguousarray(P, dtype=np.float64)
     if P.ndim != 2:
         raise ValueError("`P` must have shape (B, n).")
@@ -356,7 +561,7 @@ def evaluate(name, xdata, P, ctx=None):
     if own:
         ctx = _abi.Context(0)
     try:
-        with DeviceModel(ctx, name, B, m, n, x) as dm:
+        with DeviceModel(ctx, model.name, B, m, n, x) as dm:
             d_P = ctx.to_device(P)
             d_f = ctx.malloc(8 * B * m)
             try:

@@ -620,6 +620,12 @@ hipError_t launch_model_eval(int model, int B, int reps, int m, int n, const dou
 hipError_t launch_model_eval_map(int model, int B, int reps, int m, int n, int nf, const int* pmap, const double* t,
                                  long t_stride, const double* y, const double* w, long w_stride, const double* X,
                                  const double* Pfix, double* f, double* J, const int* mask, hipStream_t s);
+// A composite model (blsq_model_eval_comp_dev, 7l): ncomp <= BLSQ_MODEL_MAX_COMP components {fam[c] (BLSQ_TERM_*),
+// cnt[c]} on the host whose parameters add up to n; pmap nullptr (unmapped: X is P [B * reps][n], nf ignored) or as above.
+hipError_t launch_model_eval_comp(int ncomp, const int* fam, const int* cnt, int B, int reps, int m, int n, int nf,
+                                  const int* pmap, const double* t, long t_stride, const double* y, const double* w,
+                                  long w_stride, const double* X, const double* Pfix, double* f, double* J,
+                                  const int* mask, hipStream_t s);
 
 // ---------------------------------------------------------------- probes ----
 // probe_kernels.hip: measured peaks / counter calibration (blsq_debug_probe)

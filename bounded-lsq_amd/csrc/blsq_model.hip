@@ -1,5 +1,6 @@
 // Built-in fit models: the table behind blsq_model_count / blsq_model_info and the entry point blsq_model_eval_dev
-// (include/blsq.h; kernel: model_kernels.hip) and its mapped form blsq_model_eval_map_dev (7k).
+// (include/blsq.h; kernel: model_kernels.hip), its mapped form blsq_model_eval_map_dev (7k), and the term
+// table behind blsq_term_count / blsq_term_info with the composite entry blsq_model_eval_comp_dev (7l).
 #include "blsq_host.h"
 
 namespace {
@@ -21,6 +22,15 @@ bool model_n_fits(const ModelRow& r, int n) {
   if (r.n_per_term == 0) return n == r.n_base;
   return n > r.n_base && (n - r.n_base) % r.n_per_term == 0;
 }
+
+struct TermRow {
+  const char* name;
+  int n_per_term;
+};
+// in the order of the BLSQ_TERM_* enum
+const TermRow kTerms[] = {{"gauss", 3}, {"lorentz", 3}, {"pvoigt", 4}, {"exp", 2}, {"poly", 1}};
+constexpr int kTermCount = (int)(sizeof(kTerms) / sizeof(kTerms[0]));
+static_assert(kTermCount == BLSQ_TERM_POLY + 1, "one row per BLSQ_TERM_*");
 
 }  // namespace
 
@@ -91,5 +101,62 @@ extern "C" int blsq_model_eval_map_dev(blsq_ctx* ctx, int model, int B, int reps
   return ctx->run(K_MODEL_EVAL, "launch_model_eval_map", [&] {
     return launch_model_eval_map(model, B, reps, m, n, nf, pmap, dt, t_stride, dy, dw, w_stride, dX, dPfix, df, dJ,
                                  dmask, ctx->stream);
+  });
+}
+
+extern "C" int blsq_term_count(void) { return kTermCount; }
+
+extern "C" int blsq_term_info(int term, const char** name, int* n_per_term) {
+  if (term < 0 || term >= kTermCount) return -1;
+  if (name) *name = kTerms[term].name;
+  if (n_per_term) *n_per_term = kTerms[term].n_per_term;
+  return 0;
+}
+
+extern "C" int blsq_model_eval_comp_dev(blsq_ctx* ctx, int ncomp, const int32_t* fam, const int32_t* cnt, int B,
+                                        int reps, int m, int n, int nf, const int32_t* pmap, const double* dt,
+                                        long t_stride, const double* dy, const double* dw, long w_stride,
+                                        const double* dX, const double* dPfix, double* df, double* dJ,
+                                        const int32_t* dmask) {
+  if (!ctx) return -1;
+  if (ncomp < 1 || ncomp > BLSQ_MODEL_MAX_COMP) return ctx->bad(2, "ncomp must be in 1 .. BLSQ_MODEL_MAX_COMP");
+  if (!fam) return ctx->bad(3, "fam is NULL");
+  if (!cnt) return ctx->bad(4, "cnt is NULL");
+  long total = 0;
+  for (int c = 0; c < ncomp; ++c) {
+    if (fam[c] < 0 || fam[c] >= kTermCount) return ctx->bad(3, "fam entry must be one of BLSQ_TERM_*");
+    if (cnt[c] < 1) return ctx->bad(4, "cnt entry must be at least 1");
+    total += (long)cnt[c] * kTerms[fam[c]].n_per_term;
+  }
+  if (B <= 0) return ctx->bad(5, "B must be positive");
+  if (reps <= 0) return ctx->bad(6, "reps must be positive");
+  if (m <= 0) return ctx->bad(7, "m must be positive");
+  if (n < 1 || n > BLSQ_MODEL_MAX_N || total != n)
+    return ctx->bad(8, "n must be the parameters of the components together (and at most BLSQ_MODEL_MAX_N)");
+  bool any_fixed = false;
+  if (!pmap) {
+    if (nf != n) return ctx->bad(9, "nf must equal n without a pmap");
+  } else {
+    if (nf < 1 || nf > n) return ctx->bad(9, "nf must be in 1 .. n");
+    bool used[BLSQ_MODEL_MAX_N] = {};
+    for (int j = 0; j < n; ++j) {
+      if (pmap[j] < -1 || pmap[j] >= nf) return ctx->bad(21, "pmap entry outside -1 .. nf - 1");
+      if (pmap[j] < 0) any_fixed = true;
+      else used[pmap[j]] = true;
+    }
+    for (int k = 0; k < nf; ++k)
+      if (!used[k]) return ctx->bad(22, "pmap leaves a variable k < nf unused");
+  }
+  if (!dt) return ctx->bad(11, "t is NULL");
+  if (t_stride != 0 && t_stride != (long)m) return ctx->bad(12, "t_stride must be 0 or m");
+  if (dw && w_stride != 0 && w_stride != (long)m) return ctx->bad(15, "w_stride must be 0 or m");
+  if (!dX) return ctx->bad(16, "X is NULL");
+  if (any_fixed && !dPfix) return ctx->bad(17, "Pfix is NULL although pmap holds a parameter fixed");
+  if (!df && !dJ) return ctx->bad(18, "f and J are both NULL");
+  if (dJ && reps != 1) return ctx->bad(19, "J requires reps == 1");
+  HIPCHK(ctx, hipSetDevice(ctx->device));
+  return ctx->run(K_MODEL_EVAL, "launch_model_eval_comp", [&] {
+    return launch_model_eval_comp(ncomp, fam, cnt, B, reps, m, n, nf, pmap, dt, t_stride, dy, dw, w_stride, dX, dPfix,
+                                  df, dJ, dmask, ctx->stream);
   });
 }

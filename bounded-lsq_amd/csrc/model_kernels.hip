@@ -23,9 +23,19 @@
 // (a sequential float64 sum), a column with pmap[j] == -1 is computed and dropped.  f is the residual of the unmapped
 // instance at P_full, bit for bit.  The unmapped instances resolve row_put to the plain store and compile to the code
 // they had before the flag existed.
+//
+// Composite instances (MODEL = MODEL_COMPOSITE; blsq_model_eval_comp_dev).  The model is a sum of up to 8
+// components chosen at run time: {family BLSQ_TERM_*, count} pairs in a table that travels by value in the kernel
+// arguments, as pm[] does, so the walk over it runs on scalar loads and the switch on the family is wave-uniform.  A
+// component's terms are the *_term functions below, the ones the five closed instances are built from; its value is
+// their sum in ascending order (poly: Horner), the model the sequential sum of the component values.  Parameters and
+// Jacobian columns are the concatenation of the components' slices, so one running offset serves both.  The shell
+// (staging, barriers, stream-out) is the one kernel below for every instance.
 #include "../../include/blsq.h"
 #include "blsq_device.h"
 #include "blsq_kernels.h"
+
+#include <type_traits>
 
 namespace blsq {
 
@@ -51,8 +61,20 @@ struct ModelMapArgs : ModelArgs {
   const double* Pfix;           // [B][n]; read where pm[j] == -1 only
   signed char pm[MODEL_ROWS];
 };
-template <bool MAPPED> struct ModelArgsOf { using type = ModelArgs; };
-template <> struct ModelArgsOf<true> { using type = ModelMapArgs; };
+// The component table of a composite launch: entry c < ncomp is 16 bits, the family (BLSQ_TERM_*) in the low byte and
+// the count (terms; poly: coefficients) in the high one; entries 0 .. 3 in `lo`, 4 .. 7 in `hi`, from bit 0 upwards.  Two
+// words walked by shifts: a byte array indexed by c would be read through vector loads.
+struct CompTable {
+  int ncomp;
+  unsigned long long lo, hi;
+};
+static_assert(BLSQ_MODEL_MAX_COMP == 8, "CompTable holds 8 entries of 16 bits");
+template <class Base> struct CompArgs : Base { CompTable tab; };
+static constexpr int MODEL_COMPOSITE = -1;            // the MODEL of the composite instances (no BLSQ_MODEL_* id)
+template <bool COMP, bool MAPPED> struct ModelArgsOf { using type = ModelArgs; };
+template <> struct ModelArgsOf<false, true> { using type = ModelMapArgs; };
+template <> struct ModelArgsOf<true, false> { using type = CompArgs<ModelArgs>; };
+template <> struct ModelArgsOf<true, true> { using type = CompArgs<ModelMapArgs>; };
 
 __device__ __forceinline__ int map_nf(const ModelArgs& A) { return A.n; }
 __device__ __forceinline__ int map_nf(const ModelMapArgs& A) { return A.nf; }
@@ -73,32 +95,85 @@ __device__ __forceinline__ void row_put(double* row, const signed char* pm, int 
   }
 }
 
+// ---- the terms.  Each evaluates one term whose parameters start at p[o], writes its columns o .. of the lane's J row
+// through row_put (row == nullptr: f only) and returns the term's value.
+#define PUT(k, v) row_put<MAPPED>(row, pm, (k), (v))
+template <bool MAPPED>
+__device__ __forceinline__ double exp_term(const double* __restrict__ p, int o, double t, double wi, double* row,
+                                           const signed char* pm) {
+  const double a = p[o], r = p[o + 1];
+  const double e = exp(-(r * t));
+  const double g = a * e;
+  if (row) { PUT(o, wi * e); PUT(o + 1, wi * (-(t * g))); }
+  return g;
+}
+
+template <bool LORENTZ, bool MAPPED>
+__device__ __forceinline__ double peak_term(const double* __restrict__ p, int o, double t, double wi, double* row,
+                                            const signed char* pm) {
+  const double a = p[o], mu = p[o + 1], s = p[o + 2];
+  const double z = (t - mu) / s;
+  double e, g, dmu;
+  if (!LORENTZ) {
+    e = exp(-0.5 * (z * z));
+    g = a * e;
+    dmu = (g * z) / s;
+  } else {
+    e = 1.0 / (1.0 + z * z);
+    g = a * e;
+    dmu = (((2.0 * g) * e) * z) / s;
+  }
+  if (row) { PUT(o, wi * e); PUT(o + 1, wi * dmu); PUT(o + 2, wi * (dmu * z)); }
+  return g;
+}
+
+// pseudo-Voigt (a, mu, s, eta): s is the half width at half maximum of both parts (the operations)
+template <bool MAPPED>
+__device__ __forceinline__ double pvoigt_term(const double* __restrict__ p, int o, double t, double wi, double* row,
+                                              const signed char* pm) {
+  constexpr double LN2 = 0.6931471805599453;
+  const double a = p[o], mu = p[o + 1], s = p[o + 2], eta = p[o + 3];
+  const double z = (t - mu) / s;
+  const double q = z * z;
+  const double G = exp(-(LN2 * q));
+  const double L = 1.0 / (1.0 + q);
+  const double d = L - G;
+  const double h = G + eta * d;
+  if (row) {
+    const double lg = LN2 * G;
+    const double u = lg + eta * (L * L - lg);
+    const double dmu = (((2.0 * a) * u) * z) / s;
+    PUT(o, wi * h); PUT(o + 1, wi * dmu); PUT(o + 2, wi * (dmu * z)); PUT(o + 3, wi * (a * d));
+  }
+  return a * h;
+}
+
+// polynomial of d coefficients p[o .. o + d): the value by Horner, the columns t^k by repeated product
+template <bool MAPPED>
+__device__ __forceinline__ double poly_terms(const double* __restrict__ p, int o, int d, double t, double wi,
+                                             double* row, const signed char* pm) {
+  double acc = p[o + d - 1];
+  for (int k = d - 2; k >= 0; --k) acc = acc * t + p[o + k];          // Horner
+  if (row) {
+    double pw = 1.0;
+    for (int k = 0; k < d; ++k) { PUT(o + k, wi * pw); pw = pw * t; }
+  }
+  return acc;
+}
+
 // The terms of one row.  `row` is the lane's slice of the wave's LDS tile (nullptr: f only); returns the model value.
 template <int MODEL, bool MAPPED>
 __device__ __forceinline__ double model_row(int n, int m, const double* __restrict__ tb, int i,
                                             const double* __restrict__ p, double wi, double* row,
                                             const signed char* pm) {
-#define PUT(k, v) row_put<MAPPED>(row, pm, (k), (v))
-  if (MODEL == BLSQ_MODEL_POLY) {
-    const double t = tb[i];
-    double acc = p[n - 1];
-    for (int k = n - 2; k >= 0; --k) acc = acc * t + p[k];            // Horner
-    if (row) {
-      double pw = 1.0;
-      for (int k = 0; k < n; ++k) { PUT(k, wi * pw); pw = pw * t; }
-    }
-    return acc;
-  }
+  if (MODEL == BLSQ_MODEL_POLY) return poly_terms<MAPPED>(p, 0, n, tb[i], wi, row, pm);
   if (MODEL == BLSQ_MODEL_EXP_SUM) {
     const double t = tb[i];
     const int K = (n - 1) / 2;
     double acc = 0.0;
     for (int k = 0; k < K; ++k) {
-      const double a = p[2 * k], r = p[2 * k + 1];
-      const double e = exp(-(r * t));
-      const double g = a * e;
+      const double g = exp_term<MAPPED>(p, 2 * k, t, wi, row, pm);
       acc = (k == 0) ? g : acc + g;
-      if (row) { PUT(2 * k, wi * e); PUT(2 * k + 1, wi * (-(t * g))); }
     }
     if (row) PUT(n - 1, wi);
     return acc + p[n - 1];
@@ -108,20 +183,8 @@ __device__ __forceinline__ double model_row(int n, int m, const double* __restri
     const int K = (n - 1) / 3;
     double acc = 0.0;
     for (int k = 0; k < K; ++k) {
-      const double a = p[3 * k], mu = p[3 * k + 1], s = p[3 * k + 2];
-      const double z = (t - mu) / s;
-      double e, g, dmu;
-      if (MODEL == BLSQ_MODEL_GAUSS_SUM) {
-        e = exp(-0.5 * (z * z));
-        g = a * e;
-        dmu = (g * z) / s;
-      } else {
-        e = 1.0 / (1.0 + z * z);
-        g = a * e;
-        dmu = (((2.0 * g) * e) * z) / s;
-      }
+      const double g = peak_term<MODEL == BLSQ_MODEL_LORENTZ_SUM, MAPPED>(p, 3 * k, t, wi, row, pm);
       acc = (k == 0) ? g : acc + g;
-      if (row) { PUT(3 * k, wi * e); PUT(3 * k + 1, wi * dmu); PUT(3 * k + 2, wi * (dmu * z)); }
     }
     if (row) PUT(n - 1, wi);
     return acc + p[n - 1];
@@ -140,11 +203,58 @@ __device__ __forceinline__ double model_row(int n, int m, const double* __restri
     PUT(4, wi);
   }
   return g + p[4];
+}
 #undef PUT
+
+// The row of a composite: the walk over the table.  c, fam, cnt and the offset o are wave-uniform.
+template <bool MAPPED>
+__device__ __forceinline__ double comp_row(const CompTable& tab, double t, const double* __restrict__ p, double wi,
+                                           double* row, const signed char* pm) {
+  double acc = 0.0;
+  int o = 0;                                   // first parameter, and first column, of the component
+  unsigned long long ent = tab.lo;
+  for (int c = 0; c < tab.ncomp; ++c, ent >>= 16) {
+    if (c == 4) ent = tab.hi;
+    const int fam = (int)(ent & 0xff), cnt = (int)((ent >> 8) & 0xff);
+    double v = 0.0;
+    switch (fam) {
+      case BLSQ_TERM_GAUSS:
+        for (int k = 0; k < cnt; ++k, o += 3) {
+          const double g = peak_term<false, MAPPED>(p, o, t, wi, row, pm);
+          v = (k == 0) ? g : v + g;
+        }
+        break;
+      case BLSQ_TERM_LORENTZ:
+        for (int k = 0; k < cnt; ++k, o += 3) {
+          const double g = peak_term<true, MAPPED>(p, o, t, wi, row, pm);
+          v = (k == 0) ? g : v + g;
+        }
+        break;
+      case BLSQ_TERM_PVOIGT:
+        for (int k = 0; k < cnt; ++k, o += 4) {
+          const double g = pvoigt_term<MAPPED>(p, o, t, wi, row, pm);
+          v = (k == 0) ? g : v + g;
+        }
+        break;
+      case BLSQ_TERM_EXP:
+        for (int k = 0; k < cnt; ++k, o += 2) {
+          const double g = exp_term<MAPPED>(p, o, t, wi, row, pm);
+          v = (k == 0) ? g : v + g;
+        }
+        break;
+      default:                                 // BLSQ_TERM_POLY (the host has checked the table)
+        v = poly_terms<MAPPED>(p, o, cnt, t, wi, row, pm);
+        o += cnt;
+        break;
+    }
+    acc = (c == 0) ? v : acc + v;
+  }
+  return acc;
 }
 
 template <int MODEL, bool MAPPED>
-__global__ __launch_bounds__(256) void model_eval_kernel(typename ModelArgsOf<MAPPED>::type A) {
+__global__ __launch_bounds__(256) void model_eval_kernel(
+    typename ModelArgsOf<MODEL == MODEL_COMPOSITE, MAPPED>::type A) {
   extern __shared__ double model_tiles[];
   const int lane = threadIdx.x & (WAVE - 1);
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);            // wave-uniform, in a scalar register
@@ -180,7 +290,10 @@ __global__ __launch_bounds__(256) void model_eval_kernel(typename ModelArgsOf<MA
     const int i = r0 + lane;
     const double* tb = A.t + b * A.t_stride;
     const double wi = A.w ? A.w[b * A.w_stride + i] : 1.0;
-    const double v = model_row<MODEL, MAPPED>(n, m, tb, i, p, wi, tile ? tile + lane * ld : nullptr, map_pm(A));
+    double* row = tile ? tile + lane * ld : nullptr;
+    double v;
+    if constexpr (MODEL == MODEL_COMPOSITE) v = comp_row<MAPPED>(A.tab, tb[i], p, wi, row, map_pm(A));
+    else v = model_row<MODEL, MAPPED>(n, m, tb, i, p, wi, row, map_pm(A));
     if (A.f) {
       const double r = A.y ? v - A.y[b * m + i] : v;
       A.f[q * m + i] = A.w ? wi * r : r;
@@ -202,9 +315,9 @@ __global__ __launch_bounds__(256) void model_eval_kernel(typename ModelArgsOf<MA
 }
 
 // Waves per workgroup (4 / 2 / 1) whose LDS (wave_bytes each) fits the grant, and the launch of instance <.., MAPPED>.
-template <bool MAPPED>
-static hipError_t launch_model_instance(int model, typename ModelArgsOf<MAPPED>::type& A, size_t wave_bytes,
-                                        hipStream_t s) {
+// model == MODEL_COMPOSITE: the composite instance (A then carries the table).
+template <bool MAPPED, class Args>
+static hipError_t launch_model_instance(int model, Args& A, size_t wave_bytes, hipStream_t s) {
   int wpb = 4;
   while (wpb > 1 && wave_bytes * wpb > (size_t)MODEL_LDS_BYTES) wpb >>= 1;
   if (wave_bytes * wpb > (size_t)MODEL_LDS_BYTES) return hipErrorInvalidValue;
@@ -212,7 +325,10 @@ static hipError_t launch_model_instance(int model, typename ModelArgsOf<MAPPED>:
   if (grid <= 0 || grid > 0x7fffffffL) return hipErrorInvalidValue;
   const dim3 g((unsigned)grid), blk(64 * wpb);
   const size_t lds = wave_bytes * wpb;
-  switch (model) {
+  if constexpr (std::is_same<Args, typename ModelArgsOf<true, MAPPED>::type>::value) {
+    if (model != MODEL_COMPOSITE) return hipErrorInvalidValue;
+    hipLaunchKernelGGL((model_eval_kernel<MODEL_COMPOSITE, MAPPED>), g, blk, lds, s, A);
+  } else switch (model) {
     case BLSQ_MODEL_POLY: hipLaunchKernelGGL((model_eval_kernel<BLSQ_MODEL_POLY, MAPPED>), g, blk, lds, s, A); break;
     case BLSQ_MODEL_EXP_SUM: hipLaunchKernelGGL((model_eval_kernel<BLSQ_MODEL_EXP_SUM, MAPPED>), g, blk, lds, s, A); break;
     case BLSQ_MODEL_GAUSS_SUM:
@@ -232,6 +348,28 @@ static void fill_model_args(ModelArgs& A, int B, int reps, int m, int n, const d
   A.t = t; A.t_stride = t_stride; A.y = y; A.w = w; A.w_stride = w_stride; A.P = P; A.f = f; A.J = J; A.mask = mask;
 }
 
+// nf, Pfix and pm[] of a mapped launch from the host's pmap [n]; false where n, nf or an entry is out of range.
+static bool fill_model_map(ModelMapArgs& A, int n, int nf, const int* pmap, const double* Pfix) {
+  if (n < 1 || n > MODEL_ROWS || nf < 1 || nf > n) return false;
+  A.nf = nf; A.Pfix = Pfix;
+  bool seen[MODEL_ROWS] = {};
+  for (int j = 0; j < MODEL_ROWS; ++j) {
+    int c = -1;
+    if (j < n && pmap[j] >= 0) {
+      if (pmap[j] >= nf) return false;
+      c = seen[pmap[j]] ? MODEL_ROWS + pmap[j] : pmap[j];
+      seen[pmap[j]] = true;
+    }
+    A.pm[j] = (signed char)c;
+  }
+  return true;
+}
+
+// LDS of one wave of a mapped launch: the parameter vector, and the tile at nf | 1 when J is wanted
+static size_t mapped_wave_bytes(int nf, bool want_J) {
+  return sizeof(double) * MODEL_ROWS * (size_t)(1 + (want_J ? (nf | 1) : 0));
+}
+
 hipError_t launch_model_eval(int model, int B, int reps, int m, int n, const double* t, long t_stride, const double* y,
                              const double* w, long w_stride, const double* P, double* f, double* J, const int* mask,
                              hipStream_t s) {
@@ -244,23 +382,39 @@ hipError_t launch_model_eval(int model, int B, int reps, int m, int n, const dou
 hipError_t launch_model_eval_map(int model, int B, int reps, int m, int n, int nf, const int* pmap, const double* t,
                                  long t_stride, const double* y, const double* w, long w_stride, const double* X,
                                  const double* Pfix, double* f, double* J, const int* mask, hipStream_t s) {
-  if (n < 1 || n > MODEL_ROWS || nf < 1 || nf > n) return hipErrorInvalidValue;
   ModelMapArgs A;
   fill_model_args(A, B, reps, m, n, t, t_stride, y, w, w_stride, X, f, J, mask);
-  A.nf = nf; A.Pfix = Pfix;
-  bool seen[MODEL_ROWS] = {};
-  for (int j = 0; j < MODEL_ROWS; ++j) {
-    int c = -1;
-    if (j < n && pmap[j] >= 0) {
-      if (pmap[j] >= nf) return hipErrorInvalidValue;
-      c = seen[pmap[j]] ? MODEL_ROWS + pmap[j] : pmap[j];
-      seen[pmap[j]] = true;
-    }
-    A.pm[j] = (signed char)c;
+  if (!fill_model_map(A, n, nf, pmap, Pfix)) return hipErrorInvalidValue;
+  return launch_model_instance<true>(model, A, mapped_wave_bytes(nf, J != nullptr), s);
+}
+
+hipError_t launch_model_eval_comp(int ncomp, const int* fam, const int* cnt, int B, int reps, int m, int n, int nf,
+                                  const int* pmap, const double* t, long t_stride, const double* y, const double* w,
+                                  long w_stride, const double* X, const double* Pfix, double* f, double* J,
+                                  const int* mask, hipStream_t s) {
+  if (ncomp < 1 || ncomp > BLSQ_MODEL_MAX_COMP || n < 1 || n > MODEL_ROWS) return hipErrorInvalidValue;
+  static const int per_term[BLSQ_TERM_POLY + 1] = {3, 3, 4, 2, 1};      // in the order of BLSQ_TERM_*
+  CompTable tab = {};
+  tab.ncomp = ncomp;
+  int total = 0;
+  for (int c = 0; c < ncomp; ++c) {
+    if (fam[c] < 0 || fam[c] > BLSQ_TERM_POLY || cnt[c] < 1 || cnt[c] > MODEL_ROWS) return hipErrorInvalidValue;
+    (c < 4 ? tab.lo : tab.hi) |= (unsigned long long)(fam[c] | (cnt[c] << 8)) << (16 * (c & 3));
+    total += cnt[c] * per_term[fam[c]];
   }
-  // per wave: the parameter vector, and the tile at nf | 1 when J is wanted
-  const size_t wave_bytes = sizeof(double) * MODEL_ROWS * (size_t)(1 + (J ? (nf | 1) : 0));
-  return launch_model_instance<true>(model, A, wave_bytes, s);
+  if (total != n) return hipErrorInvalidValue;       // the kernel's offsets stay inside the n parameters and columns
+  if (!pmap) {
+    CompArgs<ModelArgs> A;
+    fill_model_args(A, B, reps, m, n, t, t_stride, y, w, w_stride, X, f, J, mask);
+    A.tab = tab;
+    const size_t tile_bytes = J ? sizeof(double) * MODEL_ROWS * (size_t)(n | 1) : 0;
+    return launch_model_instance<false>(MODEL_COMPOSITE, A, tile_bytes, s);
+  }
+  CompArgs<ModelMapArgs> A;
+  fill_model_args(A, B, reps, m, n, t, t_stride, y, w, w_stride, X, f, J, mask);
+  if (!fill_model_map(A, n, nf, pmap, Pfix)) return hipErrorInvalidValue;
+  A.tab = tab;
+  return launch_model_instance<true>(MODEL_COMPOSITE, A, mapped_wave_bytes(nf, J != nullptr), s);
 }
 
 }  // namespace blsq

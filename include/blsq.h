@@ -434,6 +434,35 @@ int blsq_model_eval_dev(blsq_ctx* ctx, int model, int B, int reps, int m, int n,
 int blsq_model_eval_map_dev(blsq_ctx* ctx, int model, int B, int reps, int m, int n, int nf, const int32_t* pmap,
                             const double* dt, long t_stride, const double* dy, const double* dw, long w_stride,
                             const double* dX, const double* dPfix, double* df, double* dJ, const int32_t* dmask);
+/* Composite models: a sum of up to BLSQ_MODEL_MAX_COMP components chosen at run time, each `cnt` terms of one family
+ * (coords 1; there is no implicit offset: a constant is POLY with cnt 1):
+ *   GAUSS    a exp(-z^2 / 2),  z = (t - mu) / s                               (a, mu, s)        3 per term
+ *   LORENTZ  a / (1 + z^2)                                                    (a, mu, s)        3 per term
+ *   PVOIGT   a [G + eta (L - G)],  G = exp(-ln2 z^2),  L = 1 / (1 + z^2)      (a, mu, s, eta)   4 per term
+ *            (s: the half width at half maximum of both parts)
+ *   EXP      a exp(-r t)                                                      (a, r)            2 per term
+ *   POLY     sum_{k<cnt} p_k t^k by Horner: cnt coefficients                                    1 per term
+ * The parameters (and the columns of J) are the concatenation of the components' slices in table order; a component's
+ * value is the sum of its terms in ascending order, the model the sequential sum of the component values.  The term
+ * formulas are those of the five closed models: {GAUSS K, POLY 1} gives the bits of GAUSS_SUM, and so on.  Append only.
+ * blsq_term_info: the family's name and its parameters per term; any output may be NULL; needs no device.  Non-zero
+ * for an unknown term. */
+enum { BLSQ_TERM_GAUSS = 0, BLSQ_TERM_LORENTZ, BLSQ_TERM_PVOIGT, BLSQ_TERM_EXP, BLSQ_TERM_POLY };
+#define BLSQ_MODEL_MAX_COMP 8
+int blsq_term_count(void);
+int blsq_term_info(int term, const char** name, int* n_per_term);
+/* f and J of the composite {fam[c], cnt[c]}, c < ncomp, as blsq_model_eval_dev (pmap == NULL: dX is P [B * reps][n] and
+ * nf must equal n) or through a parameter map as blsq_model_eval_map_dev (pmap, nf, dPfix: its rules).  fam, cnt and
+ * pmap are HOST pointers read during the call: the table travels in the kernel arguments.  ncomp in
+ * 1 .. BLSQ_MODEL_MAX_COMP, every fam[c] a BLSQ_TERM_*, every cnt[c] >= 1, sum cnt[c] * n_per_term(fam[c]) == n <=
+ * BLSQ_MODEL_MAX_N; t_stride 0 or m.  A negative return is the index of the bad argument (ctx = 1, ncomp = 2, fam = 3,
+ * cnt = 4, B, reps, m, n = 8, nf = 9, pmap = 10, t = 11, t_stride, y, w, w_stride = 15, X = 16, Pfix = 17, f = 18,
+ * J = 19, mask), and for the contents of pmap -21 (an entry outside -1 .. nf - 1) and -22 (a k < nf that no entry
+ * names); nothing is launched then. */
+int blsq_model_eval_comp_dev(blsq_ctx* ctx, int ncomp, const int32_t* fam, const int32_t* cnt, int B, int reps, int m,
+                             int n, int nf, const int32_t* pmap, const double* dt, long t_stride, const double* dy,
+                             const double* dw, long w_stride, const double* dX, const double* dPfix, double* df,
+                             double* dJ, const int32_t* dmask);
 
 /* ---- parameter covariance from the final Jacobian --------------------------------------------------------------
  * The reference documents `x_covariance` as the inverse of J^T J at the solution (least_squares.py:248-252) and fills

@@ -9,9 +9,13 @@ further call of the named route, so that the events do not sit inside the timed 
 With ``--fixed`` / ``--tied`` the named route takes the keywords (the mapped kernel instances) and the
 callable route is what a user has without them: the reduced model over the nf remaining variables as numpy callables
 (the model's numpy functions behind ``ParamMap.wrap_f`` / ``wrap_jac``).  ``--kernel`` times the kernel alone instead:
-`--launches` launches each of f and of J in the 'model_eval' slot, for the unmapped entry and (with a map) the mapped one.
+`--launches` launches each of f and of J in the 'model_eval' slot, for the unmapped entry and (with a map) the mapped one,
+and next to them for the composite 'gauss*K+poly*1' (the same model through the run-time component table
+of blsq_model_eval_comp_dev), at the same size and on the same buffers' shapes.  `--rounds` repeats the timed block: the
+figure is the median of the rounds' means, and `*_all` lists every round.
 
 usage: python tools/bench_models.py [--B 4096] [--m 64] [--repeat 5] [--peaks 1] [--fixed 1,4] [--tied 5:2] [--kernel]
+                                    [--launches 50] [--rounds 1]
 """
 import argparse
 import json
@@ -44,27 +48,36 @@ def problems(B, m, seed=0, peaks=1, fixed=(), tied=None):
     return x, Y, P0, (truth - half, truth + half)
 
 
-def kernel_times(ctx, x, Y, P0, pm, launches):
-    """ms per launch of f and of J ('model_eval' slot, HIP events) for the unmapped entry at P0 and, with a map, the
-    mapped entry at reduce_x(P0)."""
+def kernel_times(ctx, x, Y, P0, pm, launches, rounds=1):
+    """us per launch of f and of J ('model_eval' slot, HIP events) for the unmapped entry at P0 and, with a map, the
+    mapped entry at reduce_x(P0); 'composite*': the same for 'gauss*K+poly*1' through the composite entry."""
     B, m = Y.shape
     n = P0.shape[1]
+    spec = "gauss*%d+poly*1" % ((n - 1) // 3)
     out = {}
-    for key, mp in (("unmapped", None),) + ((("mapped", pm),) if pm is not None else ()):
-        dm = models.DeviceModel(ctx, "gauss_sum", B, m, n, x, Y, 0.01, param_map=mp, Pfix=None if mp is None else P0)
+    cases = [("unmapped", "gauss_sum", None), ("composite", spec, None)]
+    if pm is not None:
+        cases += [("mapped", "gauss_sum", pm), ("composite_mapped", spec, pm)]
+    for key, name, mp in cases:
+        dm = models.DeviceModel(ctx, name, B, m, n, x, Y, 0.01, param_map=mp, Pfix=None if mp is None else P0)
         X = P0 if mp is None else np.ascontiguousarray(mp.reduce_x(P0))
         d_x, d_f, d_J = ctx.to_device(X), ctx.malloc(8 * B * m), ctx.malloc(8 * B * m * dm.n)
         for what, call in (("f", lambda: dm.fun_dev(d_x, d_f, 1)), ("J", lambda: dm.jac_dev(d_x, d_J))):
             call()                                                        # warm-up: the code object
             ctx.sync()
-            ctx.timing(True, only="model_eval")
-            ctx.timing_reset()
-            for _ in range(launches):
-                call()
-            ctx.sync()
-            ms, cnt = ctx.timing_read()["model_eval"]
-            ctx.timing(False)
-            out["%s_%s_us" % (key, what)] = round(1e3 * ms / cnt, 2)
+            per_round = []
+            for _ in range(rounds):
+                ctx.timing(True, only="model_eval")
+                ctx.timing_reset()
+                for _ in range(launches):
+                    call()
+                ctx.sync()
+                ms, cnt = ctx.timing_read()["model_eval"]
+                ctx.timing(False)
+                per_round.append(round(1e3 * ms / cnt, 2))
+            out["%s_%s_us" % (key, what)] = round(float(np.median(per_round)), 2)
+            if rounds > 1:
+                out["%s_%s_us_all" % (key, what)] = per_round
         for p in (d_x, d_f, d_J):
             ctx.free(p)
         dm.close()
@@ -81,6 +94,7 @@ def main():
     ap.add_argument("--tied", default="", help="j:i pairs (p_j is p_i), e.g. 5:2")
     ap.add_argument("--kernel", action="store_true", help="time the kernel's launches alone")
     ap.add_argument("--launches", type=int, default=50)
+    ap.add_argument("--rounds", type=int, default=1, help="with --kernel: timed blocks of --launches launches each")
     a = ap.parse_args()
     fixed = [int(v) for v in a.fixed.split(",") if v]
     tied = {int(p.split(":")[0]): int(p.split(":")[1]) for p in a.tied.split(",") if p}
@@ -91,8 +105,8 @@ def main():
     ctx = _abi.Context(0)
     if a.kernel:
         res = {"model": "gauss_sum", "B": a.B, "m": a.m, "n": n, "nf": n if pm is None else pm.nf, "fixed": fixed,
-               "tied": a.tied, "launches": a.launches}
-        res.update(kernel_times(ctx, x, Y, P0, pm, a.launches))
+               "tied": a.tied, "launches": a.launches, "rounds": a.rounds}
+        res.update(kernel_times(ctx, x, Y, P0, pm, a.launches, a.rounds))
         ctx.close()
         print(json.dumps(res))
         return
