@@ -120,6 +120,8 @@ SIGNATURES = {
     "blsq_term_info": (C.c_int, [C.c_int, C.POINTER(C.c_char_p), c_int32_p]),
     "blsq_model_eval_comp_dev": (C.c_int, [vp, C.c_int, c_int32_p, c_int32_p] + [C.c_int] * 5
                                  + [c_int32_p, vp, C.c_long, vp, vp, C.c_long] + [vp] * 5),
+    "blsq_model_eval_est_dev": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, c_int32_p, c_int32_p] + [C.c_int] * 5
+                                + [c_int32_p, vp, C.c_long, vp, vp, C.c_long] + [vp] * 5),
 }
 
 _lib = None

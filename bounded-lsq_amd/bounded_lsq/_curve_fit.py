@@ -87,6 +87,19 @@ def _wrap_jac(jac, xdata, transform):
     return lambda params: solve_triangular(transform, np.asarray(jac(xdata, *params)), lower=True)
 
 
+def _check_poisson(estimator, sigma, ydata):
+    """True for estimator='poisson' (after its checks of `sigma` and `ydata`), False for 'lse'; ValueError otherwise."""
+    if _models.check_estimator(estimator) == 'lse':
+        return False
+    if sigma is not None:
+        raise ValueError("`sigma` must be None with estimator='poisson': the counts carry their own variance.")
+    if not np.all(np.isfinite(ydata)):
+        raise ValueError("`ydata` must be finite with estimator='poisson'.")
+    if np.any(ydata < 0):
+        raise ValueError("`ydata` must not be negative with estimator='poisson': it holds counts.")
+    return True
+
+
 def _param_map(n, fixed, tied):
     """The ParamMap of the `fixed` / `tied` keywords, or None where they hold nothing (then nothing changes)."""
     if fixed is None and not tied:
@@ -96,7 +109,8 @@ def _param_map(n, fixed, tied):
 
 
 def curve_fit(f, xdata, ydata, p0=None, sigma=None, absolute_sigma=False, check_finite=True,
-              bounds=(-np.inf, np.inf), method=None, jac=None, full_output=False, fixed=None, tied=None, **kwargs):
+              bounds=(-np.inf, np.inf), method=None, jac=None, full_output=False, fixed=None, tied=None,
+              estimator='lse', **kwargs):
     """Fit ``ydata = f(xdata, *p) + eps`` by non-linear least squares; returns ``(popt, pcov)``.
 
     Parameters, exceptions, warnings and results are scipy.optimize.curve_fit's (1.15.3):
@@ -123,7 +137,13 @@ def curve_fit(f, xdata, ydata, p0=None, sigma=None, absolute_sigma=False, check_
     still take and return all n parameters; the solver works on the nf remaining variables (``jac=None`` differentiates
     those), `popt` (n,) has the fixed values and tied copies filled in, `pcov` (n, n) has zero rows and columns for
     fixed parameters and copied ones for tied parameters, and the degrees of freedom are m - nf.
+
+    estimator : 'lse' (the default: everything above) or 'poisson': the Poisson maximum-likelihood fit of counts
+    ``ydata >= 0``, as ``curve_fit_batch`` describes it (deviance residuals in ``fvec``; `sigma` must be None; the
+    bounds must keep `f` positive; `absolute_sigma` True gives the Gauss-Newton form of the inverse Fisher information,
+    False the quasi-Poisson covariance).  A callable `jac` is still the Jacobian of `f`.
     """
+    _models.check_estimator(estimator)
     pm = None
     if fixed is not None or tied:
         if p0 is None:
@@ -131,7 +151,7 @@ def curve_fit(f, xdata, ydata, p0=None, sigma=None, absolute_sigma=False, check_
         pm = _param_map(np.atleast_1d(p0).size, fixed, tied)
     if pm is not None:
         return _curve_fit_mapped(pm, f, xdata, ydata, p0, sigma, absolute_sigma, check_finite, bounds, method, jac,
-                                 full_output, kwargs)
+                                 full_output, estimator, kwargs)
     if p0 is None:
         args = getfullargspec(f).args
         if len(args) < 2:
@@ -162,11 +182,21 @@ def curve_fit(f, xdata, ydata, p0=None, sigma=None, absolute_sigma=False, check_
     if ydata.size == 0:
         raise ValueError("`ydata` must not be empty!")
 
-    transform = _transform_of(sigma, ydata.size)
-    func = _memoize_first(_wrap_func(f, xdata, ydata, transform))
-    if callable(jac):
-        jac = _memoize_first(_wrap_jac(jac, xdata, transform))
-    elif jac is None:
+    if _check_poisson(estimator, sigma, ydata):
+        # the deviance residual of the counts and its Jacobian c * J (models.poisson_transform)
+        def mu_of(params):
+            return np.asarray(f(xdata, *params), float)
+        func = _memoize_first(lambda params: _models.poisson_transform(mu_of(params), ydata)[0])
+        if callable(jac):
+            user_jac = jac
+            jac = _memoize_first(lambda params: _models.poisson_transform(mu_of(params), ydata)[1][:, np.newaxis]
+                                 * np.asarray(user_jac(xdata, *params)))
+    else:
+        transform = _transform_of(sigma, ydata.size)
+        func = _memoize_first(_wrap_func(f, xdata, ydata, transform))
+        if callable(jac):
+            jac = _memoize_first(_wrap_jac(jac, xdata, transform))
+    if jac is None:
         jac = '2-point'
 
     if 'args' in kwargs:
@@ -214,7 +244,7 @@ def curve_fit(f, xdata, ydata, p0=None, sigma=None, absolute_sigma=False, check_
 
 
 def _curve_fit_mapped(pm, f, xdata, ydata, p0, sigma, absolute_sigma, check_finite, bounds, method, jac, full_output,
-                      kwargs):
+                      estimator, kwargs):
     """``curve_fit`` over the nf variables of `pm`: the same function on wrapped callables, results expanded."""
     Pfix = np.array(np.atleast_1d(p0), dtype=float)
     if hasattr(bounds, 'lb') and hasattr(bounds, 'ub'):
@@ -232,12 +262,12 @@ def _curve_fit_mapped(pm, f, xdata, ydata, p0, sigma, absolute_sigma, check_fini
             return pm.reduce_jac(np.asarray(jac(x, *pm.expand_x(np.asarray(xv, dtype=float), Pfix))))
     out = curve_fit(fr, xdata, ydata, p0=pm.reduce_x(Pfix), sigma=sigma, absolute_sigma=absolute_sigma,
                     check_finite=check_finite, bounds=(lbr, ubr), method=method, jac=jr, full_output=full_output,
-                    **kwargs)
+                    estimator=estimator, **kwargs)
     return (pm.expand_x(out[0], Pfix), pm.expand_cov(out[1])) + tuple(out[2:])
 
 
 def curve_fit_batch(f, xdata, ydata, p0, sigma=None, absolute_sigma=False, bounds=(-np.inf, np.inf), method='trf',
-                    jac=None, driver='host', ctx=None, fixed=None, tied=None, **kwargs):
+                    jac=None, driver='host', ctx=None, fixed=None, tied=None, estimator='lse', **kwargs):
     """``curve_fit`` for B data sets of one model, solved together by ``least_squares_batch``.
 
     f : ``f(xdata, P) -> (B, m)`` for parameters ``P`` of shape (B, n): vectorised over the batch — or the name of a
@@ -269,6 +299,26 @@ def curve_fit_batch(f, xdata, ydata, p0, sigma=None, absolute_sigma=False, bound
             carries ``x`` (n,), ``x_free`` (nf,), ``param_map`` (n,), ``active_mask`` (n,) and ``x_covariance``
             (n, n) expanded the same way; its ``jac`` (m, nf) is the Jacobian with respect to the SOLVER's variables
             (a tied group's column is the sum of its members').  With both empty nothing changes.
+    estimator : 'lse' (the default: least squares, everything above) or 'poisson': the Poisson maximum-likelihood fit
+            of counts.  `ydata` must be finite and >= 0 (it need not be integer) and `sigma` must be
+            None; any other string is a ValueError.  The residual of point i becomes the deviance residual
+            ``sign(mu - y) sqrt(2 [mu - y + y ln(y / mu)])`` of the model value mu, whose sum of squares is the Poisson
+            deviance, so the solver, `bounds`, ``loss=``, ``leverage=``, `fixed` / `tied` and every `jac` choice work as
+            they do for least squares and the optimum is the maximum-likelihood estimate — without the bias of least
+            squares weighted by ``sqrt(y)`` at low counts, and with ``y == 0`` allowed.  A named model with
+            driver='device' is transformed inside the model kernel (blsq_model_eval_est_dev); a callable `f` / `jac`
+            still returns the model and ITS Jacobian and is wrapped by ``models.poisson_residual`` /
+            ``models.poisson_jacobian``, as is the named model with driver='host'.  Nothing guards the model's sign:
+            the `bounds` must keep it positive (an amplitude >= 0 over an offset > 0, say), or NaN reaches the solver.
+            ``results[b].fun`` holds the deviance residuals, ``obj_value`` the deviance (the robust objective under
+            ``loss=``) and ``deviance`` the sum of their squares; ``jac`` is the Jacobian of the deviance residuals.
+            `absolute_sigma` keeps its meaning: True returns ``pinv(J^T J)`` of that Jacobian,
+            ``J^T J = sum_i c_i^2 dmu_i dmu_i^T``: the Gauss-Newton form of the Fisher information
+            ``sum_i dmu_i dmu_i^T / mu_i`` at the optimum, whose inverse is the Cramér-Rao covariance (``c^2`` is ``1 / mu`` where
+            mu == y and in expectation close to it; in an empty channel it is ``1 / (2 mu)``, which makes the variance of
+            a background of well under one count per channel come out larger, by a third in the worst of the suite's
+            problems); False (the default) multiplies it by ``obj_value / (m - nf)``, the quasi-Poisson dispersion.
+            For counts that really are Poisson pass True.
 
     Returns ``(popt (B, n), pcov (B, n, n), results)``, `results` the B ``OptimizeResult`` of the solve.  pcov[b] is
     ``curve_fit``'s for problem b alone: the pseudo-inverse covariance of its final Jacobian, times
@@ -289,6 +339,7 @@ def curve_fit_batch(f, xdata, ydata, p0, sigma=None, absolute_sigma=False, bound
     if P0.ndim != 2 or P0.shape[0] != B:
         raise ValueError("`p0` must have shape (B, n).")
     n = P0.shape[1]
+    poisson = _check_poisson(estimator, sigma, ydata)
     pm = _param_map(n, fixed, tied)
     model = None
     if isinstance(f, (str, _models.CompositeModel)):
@@ -336,7 +387,15 @@ def curve_fit_batch(f, xdata, ydata, p0, sigma=None, absolute_sigma=False, bound
     nv = x_start.shape[1]                        # solver variables: n, or nf
 
     if model is not None and driver == 'device':
-        func = _models.DeviceFit(model.name, n, xdata, ydata, sigma, param_map=pm, Pfix=None if pm is None else P0)
+        func = _models.DeviceFit(model.name, n, xdata, ydata, sigma, param_map=pm, Pfix=None if pm is None else P0,
+                                 **({'estimator': estimator} if poisson else {}))
+    elif poisson:                                # (after the map: c multiplies the summed columns)
+        if callable(jac):
+            jac = _models.poisson_jacobian(f, jac, ydata)
+        f_res = _models.poisson_residual(f, ydata)
+
+        def func(P):
+            return np.asarray(f_res(xdata, P), float)
     elif transform is None:
         def func(P):
             return np.asarray(f(xdata, P), float) - ydata
@@ -370,6 +429,9 @@ def curve_fit_batch(f, xdata, ydata, p0, sigma=None, absolute_sigma=False, bound
             r.x, r.active_mask = X_full[b], masks[b]
         for b, C in zip(has_cov, covs):
             results[b].x_covariance = C
+    if poisson:
+        for r in results:
+            r.deviance = float(np.dot(r.fun, r.fun))
     popt = np.full((B, n), np.nan)
     pcov = np.full((B, n, n), np.nan)
     warn_cov = False

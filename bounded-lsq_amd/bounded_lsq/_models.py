@@ -33,6 +33,15 @@ the model the sequential sum of the component values.  The terms are computed by
 ``gauss*K+poly*1`` is ``gauss_sum`` bit for bit (and likewise lorentz, exp and ``poly*n``).  Wherever a name is taken
 (``curve_fit_batch``, ``DeviceModel``, ``DeviceFit``, ``evaluate``) a spec string or a ``CompositeModel`` is as well
 (``resolve``).
+
+Poisson maximum likelihood (``estimator='poisson'``; blsq_model_eval_est_dev).  For counts y >= 0 and a
+model value mu > 0 the residual of a fit becomes the deviance residual ``r = sign(mu - y) sqrt(D)``,
+``D = 2 [mu - y + y ln(y / mu)]``, so that ``sum r^2`` is the Poisson deviance and its minimiser the maximum-likelihood
+estimate; the Jacobian row is the model's row times ``c = dr / dmu``.  ``poisson_transform(mu, y) -> (r, c)`` IS the
+definition, in a form that neither cancels nor divides 0 by 0 at mu == y, and the kernel follows it operation by
+operation; ``poisson_residual`` and ``poisson_jacobian`` wrap any ``f(xdata, P)`` / ``jac(xdata, P)`` with it: the
+``driver='host'`` route and the route of a callable.  Nothing is checked: mu <= 0 passes through as IEEE arithmetic gives
+it, so the bounds of a fit must keep the model positive.
 """
 import re
 
@@ -44,8 +53,13 @@ MAX_N = 64                                   # BLSQ_MODEL_MAX_N
 MAX_COMP = 8                                 # BLSQ_MODEL_MAX_COMP
 LN2 = 0.6931471805599453
 
+ESTIMATORS = ('lse', 'poisson')              # BLSQ_EST_*
+POISSON_U0 = 0.25                            # |u| below which phi(u) is its series
+POISSON_TERMS = 26                           # ... of this many terms
+
 __all__ = ['MODELS', 'NAMES', 'MAX_N', 'MAX_COMP', 'TERMS', 'get', 'compose', 'resolve', 'CompositeModel', 'evaluate',
-           'DeviceModel', 'DeviceFit']
+           'DeviceModel', 'DeviceFit', 'ESTIMATORS', 'POISSON_U0', 'POISSON_TERMS', 'check_estimator',
+           'poisson_transform', 'poisson_residual', 'poisson_jacobian']
 
 
 def _tp(xdata, P):
@@ -403,6 +417,61 @@ def resolve(f):
     return get(f)
 
 
+# ---- the Poisson estimator -------------------------------------------------------------------------------------------
+def check_estimator(estimator):
+    """`estimator` if it is one of ``ESTIMATORS``; ValueError otherwise."""
+    if not isinstance(estimator, str) or estimator not in ESTIMATORS:
+        raise ValueError("unknown estimator %r: `estimator` must be 'lse' or 'poisson'." % (estimator,))
+    return estimator
+
+
+def poisson_transform(mu, y):
+    """The deviance residual r and c = dr / dmu of counts `y` >= 0 under model values `mu` > 0 (broadcast against each
+    other; the result has their common floating dtype, so np.longdouble in gives a longdouble reference).
+
+        D = 2 [mu - y + y ln(y / mu)]    r = sign(mu - y) sqrt(D)    c = (1 - y / mu) / r   (1 / sqrt(mu) at mu == y)
+
+    evaluated, with d = mu - y, as
+        y > 0:   u = d / y,  phi(u) = (u - log1p(u)) / u^2,  s = sqrt(2 phi / y),  r = d s,  c = 1 / (mu s)
+        y == 0:  r = sqrt(2 mu),  c = 1 / r
+    where phi is computed as written for |u| >= POISSON_U0 and by POISSON_TERMS terms of its series
+    1/2 - u/3 + u^2/4 - ... (Horner) below: no cancellation, and r == 0 exactly with a finite c at mu == y.
+    The relative error of r and c in float64 is a few eps for mu >= y / 2 and grows like eps y / mu below (u is formed
+    from d / y, which forgets mu where mu << y): DESIGN.md 7m has the figures.  Nothing is checked: mu <= 0 (and a
+    negative or non-finite y) passes through as IEEE arithmetic gives it."""
+    mu, y = np.asarray(mu), np.asarray(y)
+    dt = np.result_type(mu.dtype, y.dtype, np.float64)
+    mu, y = np.broadcast_arrays(mu.astype(dt, copy=False), y.astype(dt, copy=False))
+    one = dt.type(1)
+    with np.errstate(all='ignore'):                # (both sides of every branch are evaluated; np.where picks)
+        d = mu - y
+        u = d / y
+        phi = np.full(u.shape, (-one) ** (POISSON_TERMS - 1) / dt.type(POISSON_TERMS + 1))
+        for k in range(POISSON_TERMS - 2, -1, -1):                       # Horner
+            phi = phi * u + (-one) ** k / dt.type(k + 2)
+        phi = np.where(np.abs(u) < POISSON_U0, phi, (u - np.log1p(u)) / (u * u))
+        s = np.sqrt((2 * phi) / y)
+        r0 = np.sqrt(2 * mu)
+        pos = y > 0
+        r = np.where(pos, d * s, r0)
+        c = np.where(pos, one / (mu * s), one / r0)
+    return r, c
+
+
+def poisson_residual(f, ydata):
+    """``f(xdata, P) -> (B, m)`` -> ``g(xdata, P)``: the deviance residuals of `ydata` (B, m) under the model."""
+    return lambda xdata, P: poisson_transform(np.asarray(f(xdata, P)), ydata)[0]
+
+
+def poisson_jacobian(f, jac, ydata):
+    """``jac(xdata, P) -> (B, m, n)`` -> the Jacobian of ``poisson_residual(f, ydata)``: ``c[:, :, None] * J``.  A
+    `jac` that already went through a parameter map is multiplied after the map's column sums."""
+    def g(xdata, P):
+        c = poisson_transform(np.asarray(f(xdata, P)), ydata)[1]
+        return c[:, :, np.newaxis] * np.asarray(jac(xdata, P))
+    return g
+
+
 class DeviceModel:
     """Model `name` (a name, a composite spec or a ``CompositeModel``) with its data resident on the GPU: the device callbacks of ``OuterDriver.run_device``.
 
@@ -414,11 +483,21 @@ class DeviceModel:
 
     With a ``ParamMap`` (`param_map`, and the template `Pfix` (B, n) holding the values of its fixed parameters) the
     callbacks take the nf solver variables and go through blsq_model_eval_map_dev: ``n`` is then nf,
-    the width of x and J, and ``n_model`` the number of model parameters; `set_bounds` takes reduced bounds."""
+    the width of x and J, and ``n_model`` the number of model parameters; `set_bounds` takes reduced bounds.
 
-    def __init__(self, ctx, name, B, m, n, xdata, ydata=None, sigma=None, param_map=None, Pfix=None):
+    ``estimator='poisson'``: the callbacks give the deviance residuals of the counts `ydata` and their
+    Jacobian, through blsq_model_eval_est_dev for every kind of model; `ydata` is then required and `sigma` must be
+    None (ValueError).  The bounds must keep the model positive."""
+
+    def __init__(self, ctx, name, B, m, n, xdata, ydata=None, sigma=None, param_map=None, Pfix=None, estimator='lse'):
         model = resolve(name)
         model.terms(n)
+        self.estimator = check_estimator(estimator)
+        if estimator == 'poisson':
+            if ydata is None:
+                raise ValueError("estimator='poisson' needs `ydata`: the counts.")
+            if sigma is not None:
+                raise ValueError("`sigma` must be None with estimator='poisson'.")
         self.model, self.B, self.m, self.n_model = model, int(B), int(m), int(n)
         self.param_map = param_map
         if param_map is not None and param_map.n != self.n_model:
@@ -472,6 +551,16 @@ class DeviceModel:
         return self.bounds_dev
 
     def _eval(self, x_ptr, reps, f_ptr, J_ptr, mask_ptr):
+        if self.estimator != 'lse':                           # every kind of model: one entry
+            M, comp = self.model, isinstance(self.model, CompositeModel)
+            self.ctx.check(self.ctx.lib.blsq_model_eval_est_dev(
+                self.ctx.h, ESTIMATORS.index(self.estimator), -1 if comp else M.id, len(M.components) if comp else 0,
+                M.fam_ids.ctypes.data_as(_abi.c_int32_p) if comp else None,
+                M.counts.ctypes.data_as(_abi.c_int32_p) if comp else None, self.B, int(reps), self.m, self.n_model,
+                self.n, None if self.param_map is None else self._pmap.ctypes.data_as(_abi.c_int32_p), self.d_t,
+                self.t_stride, self.d_y, self.d_w, self.w_stride, x_ptr, self.d_Pfix, f_ptr, J_ptr, mask_ptr),
+                "blsq_model_eval_est_dev")
+            return
         if isinstance(self.model, CompositeModel):            # with or without a map: one entry
             M = self.model
             self.ctx.check(self.ctx.lib.blsq_model_eval_comp_dev(
@@ -516,11 +605,14 @@ class DeviceFit:
     """What ``least_squares_batch(fun=...)`` takes in place of a callable for a fit whose callbacks run on the device:
     a checked (model, data) pair that opens a ``DeviceModel`` on the driver's context.  Built by ``curve_fit_batch``.
     ``n`` is the number of solver variables (the width of x0): the model's n, or nf of `param_map`; ``n_model`` is the
-    model's number of parameters."""
+    model's number of parameters.  ``estimator='poisson'``: as ``DeviceModel``."""
 
-    def __init__(self, name, n, xdata, ydata, sigma=None, param_map=None, Pfix=None):
+    def __init__(self, name, n, xdata, ydata, sigma=None, param_map=None, Pfix=None, estimator='lse'):
         self.model = resolve(name)
         self.model.terms(n)
+        self.estimator = check_estimator(estimator)
+        if estimator == 'poisson' and sigma is not None:
+            raise ValueError("`sigma` must be None with estimator='poisson'.")
         self.ydata = np.ascontiguousarray(ydata, dtype=np.float64)
         self.B, self.m = self.ydata.shape
         self.n_model = int(n)
@@ -537,7 +629,7 @@ class DeviceFit:
 
     def open_device(self, ctx, lb, ub):
         dm = DeviceModel(ctx, self.model.name, self.B, self.m, self.n_model, self.xdata, self.ydata, self.sigma,
-                         self.param_map, self.Pfix)
+                         self.param_map, self.Pfix, self.estimator)
         dm.set_bounds(lb, ub)
         return dm
 

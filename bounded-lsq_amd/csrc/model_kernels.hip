@@ -31,6 +31,19 @@
 // their sum in ascending order (poly: Horner), the model the sequential sum of the component values.  Parameters and
 // Jacobian columns are the concatenation of the components' slices, so one running offset serves both.  The shell
 // (staging, barriers, stream-out) is the one kernel below for every instance.
+//
+// Poisson instances (POISSON = true; blsq_model_eval_est_dev with BLSQ_EST_POISSON).  The residual is the
+// signed square root of the Poisson deviance of the count y[b][i] under the model value mu, and the Jacobian row is the
+// model's row times c = dr / dmu: poisson_rc below, operation by operation models.poisson_transform of
+// bounded_lsq/_models.py.  The terms write their columns unweighted (wi = 1, w must be NULL); once the row's value is
+// known the lane computes (r, c), stores f = r and multiplies the nc entries of its own LDS row by c (the mapped slots
+// after their sums) before the barrier.  The row pass walks the addresses the puts walked, lane * (nc | 1) + k: at an odd
+// stride both its 8-byte loads (groups of 32 lanes over 64 banks) and its stores (16 lanes over 32) find every lane of
+// a group on a bank pair of its own.  No extra memory traffic but the one read of y that the residual needs anyway; LDS
+// footprint and waves per workgroup are those of the least-squares instance.  The estimator is a template flag, not a
+// field of ModelArgs: the least-squares instances are then the instructions they were before it existed, and the 24
+// instances build in 4.3 s where the 12 took 3.8 s, next to files that take a minute, so build time does not argue for
+// a runtime field, which would put the transform's registers and branch into every least-squares instance.
 #include "../../include/blsq.h"
 #include "blsq_device.h"
 #include "blsq_kernels.h"
@@ -252,7 +265,35 @@ __device__ __forceinline__ double comp_row(const CompTable& tab, double t, const
   return acc;
 }
 
-template <int MODEL, bool MAPPED>
+// (r, c) of models.poisson_transform for the model value mu and the count y: r = sign(mu - y) sqrt(D),
+// D = 2 [mu - y + y ln(y / mu)] the deviance, c = dr / dmu, in the form that neither cancels nor divides 0 by 0 at
+// mu == y.  phi(u) = (u - log1p(u)) / u^2 directly where |u| >= POISSON_U0, by POISSON_TERMS terms of its series
+// sum_k (-u)^k / (k + 2) below (Horner; the coefficients are constants folded at compile time, correctly rounded as
+// numpy's are).  Nothing is checked: mu <= 0 passes through as IEEE arithmetic gives it.
+static constexpr double POISSON_U0 = 0.25;
+static constexpr int POISSON_TERMS = 26;
+__device__ __forceinline__ void poisson_rc(double mu, double y, double& r, double& c) {
+  if (y > 0.0) {
+    const double d = mu - y;
+    const double u = d / y;
+    double phi;
+    if (fabs(u) < POISSON_U0) {
+      phi = ((POISSON_TERMS - 1) & 1 ? -1.0 : 1.0) / (double)(POISSON_TERMS + 1);
+#pragma unroll
+      for (int k = POISSON_TERMS - 2; k >= 0; --k) phi = phi * u + (k & 1 ? -1.0 : 1.0) / (double)(k + 2);
+    } else {
+      phi = (u - log1p(u)) / (u * u);
+    }
+    const double s = sqrt((2.0 * phi) / y);
+    r = d * s;
+    c = 1.0 / (mu * s);
+  } else {
+    r = sqrt(2.0 * mu);
+    c = 1.0 / r;
+  }
+}
+
+template <int MODEL, bool MAPPED, bool POISSON>
 __global__ __launch_bounds__(256) void model_eval_kernel(
     typename ModelArgsOf<MODEL == MODEL_COMPOSITE, MAPPED>::type A) {
   extern __shared__ double model_tiles[];
@@ -289,12 +330,18 @@ __global__ __launch_bounds__(256) void model_eval_kernel(
   if (lane < nr) {
     const int i = r0 + lane;
     const double* tb = A.t + b * A.t_stride;
-    const double wi = A.w ? A.w[b * A.w_stride + i] : 1.0;
+    const double wi = (!POISSON && A.w) ? A.w[b * A.w_stride + i] : 1.0;
     double* row = tile ? tile + lane * ld : nullptr;
     double v;
     if constexpr (MODEL == MODEL_COMPOSITE) v = comp_row<MAPPED>(A.tab, tb[i], p, wi, row, map_pm(A));
     else v = model_row<MODEL, MAPPED>(n, m, tb, i, p, wi, row, map_pm(A));
-    if (A.f) {
+    if constexpr (POISSON) {
+      double r, c;
+      poisson_rc(v, A.y[b * m + i], r, c);
+      if (A.f) A.f[q * m + i] = r;
+      if (row)
+        for (int k = 0; k < nc; ++k) row[k] = c * row[k];
+    } else if (A.f) {
       const double r = A.y ? v - A.y[b * m + i] : v;
       A.f[q * m + i] = A.w ? wi * r : r;
     }
@@ -314,10 +361,20 @@ __global__ __launch_bounds__(256) void model_eval_kernel(
   }
 }
 
-// Waves per workgroup (4 / 2 / 1) whose LDS (wave_bytes each) fits the grant, and the launch of instance <.., MAPPED>.
-// model == MODEL_COMPOSITE: the composite instance (A then carries the table).
+// The launch of instance <MODEL, MAPPED, est == BLSQ_EST_POISSON>.
+template <int MODEL, bool MAPPED, class Args>
+static void launch_model_est(int est, dim3 g, dim3 blk, size_t lds, hipStream_t s, Args& A) {
+  if (est == BLSQ_EST_POISSON) hipLaunchKernelGGL((model_eval_kernel<MODEL, MAPPED, true>), g, blk, lds, s, A);
+  else hipLaunchKernelGGL((model_eval_kernel<MODEL, MAPPED, false>), g, blk, lds, s, A);
+}
+
+// Waves per workgroup (4 / 2 / 1) whose LDS (wave_bytes each) fits the grant, and the launch of instance <.., MAPPED, ..>.
+// model == MODEL_COMPOSITE: the composite instance (A then carries the table).  The Poisson instances need y and take
+// no weights.
 template <bool MAPPED, class Args>
-static hipError_t launch_model_instance(int model, Args& A, size_t wave_bytes, hipStream_t s) {
+static hipError_t launch_model_instance(int model, int est, Args& A, size_t wave_bytes, hipStream_t s) {
+  if (est != BLSQ_EST_LSE && est != BLSQ_EST_POISSON) return hipErrorInvalidValue;
+  if (est == BLSQ_EST_POISSON && (!A.y || A.w)) return hipErrorInvalidValue;
   int wpb = 4;
   while (wpb > 1 && wave_bytes * wpb > (size_t)MODEL_LDS_BYTES) wpb >>= 1;
   if (wave_bytes * wpb > (size_t)MODEL_LDS_BYTES) return hipErrorInvalidValue;
@@ -327,15 +384,13 @@ static hipError_t launch_model_instance(int model, Args& A, size_t wave_bytes, h
   const size_t lds = wave_bytes * wpb;
   if constexpr (std::is_same<Args, typename ModelArgsOf<true, MAPPED>::type>::value) {
     if (model != MODEL_COMPOSITE) return hipErrorInvalidValue;
-    hipLaunchKernelGGL((model_eval_kernel<MODEL_COMPOSITE, MAPPED>), g, blk, lds, s, A);
+    launch_model_est<MODEL_COMPOSITE, MAPPED>(est, g, blk, lds, s, A);
   } else switch (model) {
-    case BLSQ_MODEL_POLY: hipLaunchKernelGGL((model_eval_kernel<BLSQ_MODEL_POLY, MAPPED>), g, blk, lds, s, A); break;
-    case BLSQ_MODEL_EXP_SUM: hipLaunchKernelGGL((model_eval_kernel<BLSQ_MODEL_EXP_SUM, MAPPED>), g, blk, lds, s, A); break;
-    case BLSQ_MODEL_GAUSS_SUM:
-      hipLaunchKernelGGL((model_eval_kernel<BLSQ_MODEL_GAUSS_SUM, MAPPED>), g, blk, lds, s, A); break;
-    case BLSQ_MODEL_LORENTZ_SUM:
-      hipLaunchKernelGGL((model_eval_kernel<BLSQ_MODEL_LORENTZ_SUM, MAPPED>), g, blk, lds, s, A); break;
-    case BLSQ_MODEL_GAUSS2D: hipLaunchKernelGGL((model_eval_kernel<BLSQ_MODEL_GAUSS2D, MAPPED>), g, blk, lds, s, A); break;
+    case BLSQ_MODEL_POLY: launch_model_est<BLSQ_MODEL_POLY, MAPPED>(est, g, blk, lds, s, A); break;
+    case BLSQ_MODEL_EXP_SUM: launch_model_est<BLSQ_MODEL_EXP_SUM, MAPPED>(est, g, blk, lds, s, A); break;
+    case BLSQ_MODEL_GAUSS_SUM: launch_model_est<BLSQ_MODEL_GAUSS_SUM, MAPPED>(est, g, blk, lds, s, A); break;
+    case BLSQ_MODEL_LORENTZ_SUM: launch_model_est<BLSQ_MODEL_LORENTZ_SUM, MAPPED>(est, g, blk, lds, s, A); break;
+    case BLSQ_MODEL_GAUSS2D: launch_model_est<BLSQ_MODEL_GAUSS2D, MAPPED>(est, g, blk, lds, s, A); break;
     default: return hipErrorInvalidValue;
   }
   return hipGetLastError();
@@ -372,26 +427,27 @@ static size_t mapped_wave_bytes(int nf, bool want_J) {
 
 hipError_t launch_model_eval(int model, int B, int reps, int m, int n, const double* t, long t_stride, const double* y,
                              const double* w, long w_stride, const double* P, double* f, double* J, const int* mask,
-                             hipStream_t s) {
+                             hipStream_t s, int est) {
   ModelArgs A;
   fill_model_args(A, B, reps, m, n, t, t_stride, y, w, w_stride, P, f, J, mask);
   const size_t tile_bytes = J ? sizeof(double) * MODEL_ROWS * (size_t)(n | 1) : 0;
-  return launch_model_instance<false>(model, A, tile_bytes, s);
+  return launch_model_instance<false>(model, est, A, tile_bytes, s);
 }
 
 hipError_t launch_model_eval_map(int model, int B, int reps, int m, int n, int nf, const int* pmap, const double* t,
                                  long t_stride, const double* y, const double* w, long w_stride, const double* X,
-                                 const double* Pfix, double* f, double* J, const int* mask, hipStream_t s) {
+                                 const double* Pfix, double* f, double* J, const int* mask, hipStream_t s,
+                                 int est) {
   ModelMapArgs A;
   fill_model_args(A, B, reps, m, n, t, t_stride, y, w, w_stride, X, f, J, mask);
   if (!fill_model_map(A, n, nf, pmap, Pfix)) return hipErrorInvalidValue;
-  return launch_model_instance<true>(model, A, mapped_wave_bytes(nf, J != nullptr), s);
+  return launch_model_instance<true>(model, est, A, mapped_wave_bytes(nf, J != nullptr), s);
 }
 
 hipError_t launch_model_eval_comp(int ncomp, const int* fam, const int* cnt, int B, int reps, int m, int n, int nf,
                                   const int* pmap, const double* t, long t_stride, const double* y, const double* w,
                                   long w_stride, const double* X, const double* Pfix, double* f, double* J,
-                                  const int* mask, hipStream_t s) {
+                                  const int* mask, hipStream_t s, int est) {
   if (ncomp < 1 || ncomp > BLSQ_MODEL_MAX_COMP || n < 1 || n > MODEL_ROWS) return hipErrorInvalidValue;
   static const int per_term[BLSQ_TERM_POLY + 1] = {3, 3, 4, 2, 1};      // in the order of BLSQ_TERM_*
   CompTable tab = {};
@@ -408,13 +464,13 @@ hipError_t launch_model_eval_comp(int ncomp, const int* fam, const int* cnt, int
     fill_model_args(A, B, reps, m, n, t, t_stride, y, w, w_stride, X, f, J, mask);
     A.tab = tab;
     const size_t tile_bytes = J ? sizeof(double) * MODEL_ROWS * (size_t)(n | 1) : 0;
-    return launch_model_instance<false>(MODEL_COMPOSITE, A, tile_bytes, s);
+    return launch_model_instance<false>(MODEL_COMPOSITE, est, A, tile_bytes, s);
   }
   CompArgs<ModelMapArgs> A;
   fill_model_args(A, B, reps, m, n, t, t_stride, y, w, w_stride, X, f, J, mask);
   if (!fill_model_map(A, n, nf, pmap, Pfix)) return hipErrorInvalidValue;
   A.tab = tab;
-  return launch_model_instance<true>(MODEL_COMPOSITE, A, mapped_wave_bytes(nf, J != nullptr), s);
+  return launch_model_instance<true>(MODEL_COMPOSITE, est, A, mapped_wave_bytes(nf, J != nullptr), s);
 }
 
 }  // namespace blsq

@@ -463,6 +463,32 @@ int blsq_model_eval_comp_dev(blsq_ctx* ctx, int ncomp, const int32_t* fam, const
                              int n, int nf, const int32_t* pmap, const double* dt, long t_stride, const double* dy,
                              const double* dw, long w_stride, const double* dX, const double* dPfix, double* df,
                              double* dJ, const int32_t* dmask);
+/* The estimator of a fit: what the residual of the models above is.  Append only.
+ *   LSE      f = w (model - y): least squares, the three entries above.
+ *   POISSON  maximum likelihood for counts y >= 0 under a model value mu > 0, through the deviance residual
+ *              r = sign(mu - y) sqrt(D),   D = 2 [mu - y + y ln(y / mu)]   (the y ln term is 0 at y == 0)
+ *            so that sum_i r_i^2 is the Poisson deviance 2 (NLL - NLL_saturated) and its minimiser the MLE:
+ *              f[q][i]    = r(mu[q][i], y[b][i])
+ *              J[q][i][k] = c * d mu / d p_k,   c = dr / dmu = (1 - y / mu) / r   (1 / sqrt(mu) at mu == y)
+ *            with a parameter map the columns are summed first and the slot is multiplied by c.  r and c are evaluated
+ *            in a form that neither cancels nor divides 0 by 0 at mu == y (the numpy definition is
+ *            bounded_lsq.models.poisson_transform).  dy is required and dw must be NULL.  Nothing is checked on the
+ *            device: mu <= 0 passes through as IEEE arithmetic gives it (the bounds of the fit must keep the model
+ *            positive). */
+enum { BLSQ_EST_LSE = 0, BLSQ_EST_POISSON };
+/* One entry for every model instance, with the estimator.  model >= 0: the named model BLSQ_MODEL_* (ncomp must be 0;
+ * fam and cnt are not read); model == -1: the composite {fam[c], cnt[c]}, c < ncomp, by the rules of
+ * blsq_model_eval_comp_dev.  pmap == NULL: dX is P [B * reps][n] and nf must equal n; otherwise the parameter map of
+ * blsq_model_eval_map_dev (pmap, nf, dPfix: its rules).  With BLSQ_EST_LSE the outputs are those of the entry this one
+ * stands in for (blsq_model_eval_dev, _map_dev or _comp_dev), bit for bit.  Everything else as blsq_model_eval_dev.  A
+ * negative return is the index of the bad argument (ctx = 1, est = 2, model = 3, ncomp = 4, fam = 5, cnt = 6, B = 7,
+ * reps, m, n = 10, nf = 11, pmap = 12, t = 13, t_stride, y = 15, w = 16, w_stride, X = 18, Pfix = 19, f = 20, J = 21,
+ * mask), and for the contents of pmap -23 (an entry outside -1 .. nf - 1) and -24 (a k < nf that no entry names); with
+ * BLSQ_EST_POISSON dy == NULL is -15 and dw != NULL is -16.  Nothing is launched then. */
+int blsq_model_eval_est_dev(blsq_ctx* ctx, int est, int model, int ncomp, const int32_t* fam, const int32_t* cnt, int B,
+                            int reps, int m, int n, int nf, const int32_t* pmap, const double* dt, long t_stride,
+                            const double* dy, const double* dw, long w_stride, const double* dX, const double* dPfix,
+                            double* df, double* dJ, const int32_t* dmask);
 
 /* ---- parameter covariance from the final Jacobian --------------------------------------------------------------
  * The reference documents `x_covariance` as the inverse of J^T J at the solution (least_squares.py:248-252) and fills

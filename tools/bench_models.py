@@ -14,8 +14,12 @@ and next to them for the composite 'gauss*K+poly*1' (the same mode
 of blsq_model_eval_comp_dev), at the same size and on the same buffers' shapes.  `--rounds` repeats the timed block: the
 figure is the median of the rounds' means, and `*_all` lists every round.
 
+``--estimator poisson`` fits counts instead: the same lines 40 times as high (60 counts at the peak over a
+background of 12), drawn from the Poisson law, sigma None; the named route runs the Poisson kernel instances, the callable
+route the numpy wrappers.  Without it nothing here changes.
+
 usage: python tools/bench_models.py [--B 4096] [--m 64] [--repeat 5] [--peaks 1] [--fixed 1,4] [--tied 5:2] [--kernel]
-                                    [--launches 50] [--rounds 1]
+                                    [--launches 50] [--rounds 1] [--estimator lse]
 """
 import argparse
 import json
@@ -33,22 +37,31 @@ from bounded_lsq import curve_fit_batch, models, _abi, ParamMap          # noqa:
 PEAKS = {1: [1.5, 0.2, 0.6, 0.3], 2: [1.5, -0.8, 0.4, 1.0, 0.7, 0.5, 0.2]}
 
 
-def problems(B, m, seed=0, peaks=1, fixed=(), tied=None):
+COUNTS = 40.0                                  # --estimator poisson: amplitudes and offset in counts
+
+
+def problems(B, m, seed=0, peaks=1, fixed=(), tied=None, poisson=False):
     """The truth satisfies the ties and p0 sits at the truth in the fixed columns."""
     rng = np.random.default_rng(seed)
     base = np.array(PEAKS[peaks])
+    if poisson:
+        base[0:-1:3] *= COUNTS
+        base[-1] *= COUNTS
     truth = base * (1 + 0.05 * rng.uniform(-1, 1, (B, base.size)))
     for j, i in (tied or {}).items():
         truth[:, j] = truth[:, i]
     x = np.linspace(-2.0, 2.0, m)
-    Y = models.get("gauss_sum").f(x, truth) + 0.01 * rng.standard_normal((B, m))
+    if poisson:
+        Y = rng.poisson(models.get("gauss_sum").f(x, truth)).astype(float)
+    else:
+        Y = models.get("gauss_sum").f(x, truth) + 0.01 * rng.standard_normal((B, m))
     P0 = truth * (1 + 0.1 * rng.choice([-1.0, 1.0], truth.shape))
     P0[:, list(fixed)] = truth[:, list(fixed)]
     half = 0.4 * np.abs(truth) + 0.2
     return x, Y, P0, (truth - half, truth + half)
 
 
-def kernel_times(ctx, x, Y, P0, pm, launches, rounds=1):
+def kernel_times(ctx, x, Y, P0, pm, launches, rounds=1, estimator="lse"):
     """us per launch of f and of J ('model_eval' slot, HIP events) for the unmapped entry at P0 and, with a map, the
     mapped entry at reduce_x(P0); 'composite*': the same for 'gauss*K+poly*1' through the composite entry."""
     B, m = Y.shape
@@ -59,7 +72,8 @@ def kernel_times(ctx, x, Y, P0, pm, launches, rounds=1):
     if pm is not None:
         cases += [("mapped", "gauss_sum", pm), ("composite_mapped", spec, pm)]
     for key, name, mp in cases:
-        dm = models.DeviceModel(ctx, name, B, m, n, x, Y, 0.01, param_map=mp, Pfix=None if mp is None else P0)
+        dm = models.DeviceModel(ctx, name, B, m, n, x, Y, 0.01 if estimator == "lse" else None, param_map=mp,
+                                Pfix=None if mp is None else P0, estimator=estimator)
         X = P0 if mp is None else np.ascontiguousarray(mp.reduce_x(P0))
         d_x, d_f, d_J = ctx.to_device(X), ctx.malloc(8 * B * m), ctx.malloc(8 * B * m * dm.n)
         for what, call in (("f", lambda: dm.fun_dev(d_x, d_f, 1)), ("J", lambda: dm.jac_dev(d_x, d_J))):
@@ -95,22 +109,26 @@ def main():
     ap.add_argument("--kernel", action="store_true", help="time the kernel's launches alone")
     ap.add_argument("--launches", type=int, default=50)
     ap.add_argument("--rounds", type=int, default=1, help="with --kernel: timed blocks of --launches launches each")
+    ap.add_argument("--estimator", default="lse", choices=models.ESTIMATORS)
     a = ap.parse_args()
     fixed = [int(v) for v in a.fixed.split(",") if v]
     tied = {int(p.split(":")[0]): int(p.split(":")[1]) for p in a.tied.split(",") if p}
-    x, Y, P0, bounds = problems(a.B, a.m, peaks=a.peaks, fixed=fixed, tied=tied)
+    poisson = a.estimator == "poisson"
+    x, Y, P0, bounds = problems(a.B, a.m, peaks=a.peaks, fixed=fixed, tied=tied, poisson=poisson)
     n = P0.shape[1]
     M = models.get("gauss_sum")
     pm = ParamMap(n, fixed, tied) if (fixed or tied) else None
     ctx = _abi.Context(0)
     if a.kernel:
         res = {"model": "gauss_sum", "B": a.B, "m": a.m, "n": n, "nf": n if pm is None else pm.nf, "fixed": fixed,
-               "tied": a.tied, "launches": a.launches, "rounds": a.rounds}
-        res.update(kernel_times(ctx, x, Y, P0, pm, a.launches, a.rounds))
+               "tied": a.tied, "launches": a.launches, "rounds": a.rounds, "estimator": a.estimator}
+        res.update(kernel_times(ctx, x, Y, P0, pm, a.launches, a.rounds, a.estimator))
         ctx.close()
         print(json.dumps(res))
         return
     kw = dict(sigma=0.01, bounds=bounds, driver="device", ctx=ctx, ftol=1e-10, xtol=1e-10, gtol=1e-10)
+    if poisson:
+        kw.update(sigma=None, estimator="poisson")
     if pm is None:
         routes = {"named": lambda: curve_fit_batch("gauss_sum", x, Y, P0, **kw),
                   "callable": lambda: curve_fit_batch(M.f, x, Y, P0, jac=M.jac, **kw)}
@@ -139,7 +157,7 @@ def main():
     both = np.array([ra.success and rb.success for ra, rb in zip(out["named"][2], out["callable"][2])])
     free = (lambda P: P) if pm is None else pm.reduce_x
     res = {"model": "gauss_sum", "B": a.B, "m": a.m, "n": n, "nf": n if pm is None else pm.nf, "driver": "device",
-           "named_s": round(float(np.median(times["named"])), 4),
+           "estimator": a.estimator, "named_s": round(float(np.median(times["named"])), 4),
            "callable_s": round(float(np.median(times["callable"])), 4),
            "named_all_s": [round(t, 4) for t in times["named"]],
            "callable_all_s": [round(t, 4) for t in times["callable"]],
