@@ -122,6 +122,8 @@ SIGNATURES = {
                                  + [c_int32_p, vp, C.c_long, vp, vp, C.c_long] + [vp] * 5),
     "blsq_model_eval_est_dev": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, c_int32_p, c_int32_p] + [C.c_int] * 5
                                 + [c_int32_p, vp, C.c_long, vp, vp, C.c_long] + [vp] * 5),
+    "blsq_model_eval_bin_dev": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, C.c_int, c_int32_p, c_int32_p] + [C.c_int] * 5
+                                + [c_int32_p, vp, C.c_long, vp, vp, C.c_long] + [vp] * 5),
 }
 
 _lib = None

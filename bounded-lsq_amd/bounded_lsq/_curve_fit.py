@@ -267,7 +267,7 @@ def _curve_fit_mapped(pm, f, xdata, ydata, p0, sigma, absolute_sigma, check_fini
 
 
 def curve_fit_batch(f, xdata, ydata, p0, sigma=None, absolute_sigma=False, bounds=(-np.inf, np.inf), method='trf',
-                    jac=None, driver='host', ctx=None, fixed=None, tied=None, estimator='lse', **kwargs):
+                    jac=None, driver='host', ctx=None, fixed=None, tied=None, estimator='lse', binned=False, **kwargs):
     """``curve_fit`` for B data sets of one model, solved together by ``least_squares_batch``.
 
     f : ``f(xdata, P) -> (B, m)`` for parameters ``P`` of shape (B, n): vectorised over the batch — or the name of a
@@ -319,6 +319,20 @@ def curve_fit_batch(f, xdata, ydata, p0, sigma=None, absolute_sigma=False, bound
             a background of well under one count per channel come out larger, by a third in the worst of the suite's
             problems); False (the default) multiplies it by ``obj_value / (m - nf)``, the quasi-Poisson dispersion.
             For counts that really are Poisson pass True.
+    binned : False (the default: the model sampled at the points `xdata`; nothing changes) or True: `ydata` holds the
+            contents of bins (histogram channels, detector pixels) and the model is integrated over each bin,
+            ``mu_i = integral over [lo_i, hi_i] of model(t; p) dt``, in closed form (DESIGN.md 7n;
+            ``bounded_lsq.models.binned``): the model is read as a density, its parameters keep their meaning and order
+            (an amplitude is a density, a constant c contributes ``c (hi - lo)``).  Fitting ``width * model(centre)``
+            instead widens a peak by ``width^2 / 12`` in variance whenever a bin is not narrow against it.  Valid with a
+            name, a spec or a ``CompositeModel`` on both drivers (driver='device': inside the model kernel,
+            blsq_model_eval_bin_dev; driver='host': the numpy definition); with a callable `f` it is a ValueError: a
+            callable integrates itself.  `xdata` then holds the bin edges: contiguous bins as (m + 1,) or (B, m + 1)
+            edges, bins with gaps as rows ``lo, hi`` of shape (2, m) or (B, 2, m), and for 'gauss2d' the pixels as rows
+            ``ulo, uhi, vlo, vhi`` of shape (4, m) or (B, 4, m); edges that are not finite or have lo >= hi are a
+            ValueError naming the first such bin.  Everything else composes unchanged: ``estimator='poisson'`` (the
+            estimator for histogram counts), `fixed` / `tied`, ``loss=``, `bounds`, `sigma`, ``leverage=`` and
+            ``jac='2-point'`` / ``'3-point'``.
 
     Returns ``(popt (B, n), pcov (B, n, n), results)``, `results` the B ``OptimizeResult`` of the solve.  pcov[b] is
     ``curve_fit``'s for problem b alone: the pseudo-inverse covariance of its final Jacobian, times
@@ -342,11 +356,15 @@ def curve_fit_batch(f, xdata, ydata, p0, sigma=None, absolute_sigma=False, bound
     poisson = _check_poisson(estimator, sigma, ydata)
     pm = _param_map(n, fixed, tied)
     model = None
+    if binned and not isinstance(f, (str, _models.CompositeModel)):
+        raise ValueError("`binned=True` needs a built-in model (a name, a spec or a CompositeModel) as `f`: a callable "
+                         "integrates itself over its bins.")
     if isinstance(f, (str, _models.CompositeModel)):
         model = _models.resolve(f)
         f = model.name
         model.terms(n)
-        xdata, _ = model.check_xdata(xdata, B, m)
+        host_model = _models.binned(model) if binned else model         # whose numpy functions driver='host' calls
+        xdata, _ = host_model.check_xdata(xdata, B, m)
         if callable(jac):
             raise ValueError("a callable `jac` cannot be combined with the built-in model '%s'." % f)
         if jac is not None and jac not in ('2-point', '3-point'):
@@ -354,9 +372,9 @@ def curve_fit_batch(f, xdata, ydata, p0, sigma=None, absolute_sigma=False, bound
         if driver not in ('host', 'device'):
             raise ValueError("`driver` must be 'host' or 'device'.")
         if driver == 'host':                     # the numpy functions through the callable path below
-            f = model.f
+            f = host_model.f
             if jac is None:
-                jac = model.jac
+                jac = host_model.jac
     elif jac is None:
         jac = '2-point'
     if isinstance(xdata, (list, tuple, np.ndarray)):
@@ -388,7 +406,8 @@ def curve_fit_batch(f, xdata, ydata, p0, sigma=None, absolute_sigma=False, bound
 
     if model is not None and driver == 'device':
         func = _models.DeviceFit(model.name, n, xdata, ydata, sigma, param_map=pm, Pfix=None if pm is None else P0,
-                                 **({'estimator': estimator} if poisson else {}))
+                                 **({'estimator': estimator} if poisson else {}),
+                                 **({'binned': True} if binned else {}))
     elif poisson:                                # (after the map: c multiplies the summed columns)
         if callable(jac):
             jac = _models.poisson_jacobian(f, jac, ydata)

@@ -42,6 +42,13 @@ definition, in a form that neither cancels nor divides 0 by 0 at mu == y, and th
 operation; ``poisson_residual`` and ``poisson_jacobian`` wrap any ``f(xdata, P)`` / ``jac(xdata, P)`` with it: the
 ``driver='host'`` route and the route of a callable.  Nothing is checked: mu <= 0 passes through as IEEE arithmetic gives
 it, so the bounds of a fit must keep the model positive.
+
+Bin-integrated models (``binned=True``; blsq_model_eval_bin_dev).  ``binned(name)`` is the model whose row i
+is the integral of the point-sampled model over the bin [lo_i, hi_i] (gauss2d: over a pixel): the expected content of a
+histogram channel for a model read as a density, with the same parameters in the same order and the integrals of the
+columns as its Jacobian.  Its numpy ``f`` / ``jac`` ARE the definition (closed forms: ``erf_diff`` switches to erfc where
+both edges lie in one tail, atan2 for the Lorentzian, ``psi_pair`` with a series through r = 0 for a decay); the BINNED
+kernel instances follow them operation by operation.
 """
 import re
 
@@ -54,12 +61,14 @@ MAX_COMP = 8                                 # BLSQ_MODEL_MAX_COMP
 LN2 = 0.6931471805599453
 
 ESTIMATORS = ('lse', 'poisson')              # BLSQ_EST_*
+SAMPLING = ('point', 'bin')                  # BLSQ_SAMPLE_*
 POISSON_U0 = 0.25                            # |u| below which phi(u) is its series
 POISSON_TERMS = 26                           # ... of this many terms
 
 __all__ = ['MODELS', 'NAMES', 'MAX_N', 'MAX_COMP', 'TERMS', 'get', 'compose', 'resolve', 'CompositeModel', 'evaluate',
            'DeviceModel', 'DeviceFit', 'ESTIMATORS', 'POISSON_U0', 'POISSON_TERMS', 'check_estimator',
-           'poisson_transform', 'poisson_residual', 'poisson_jacobian']
+           'poisson_transform', 'poisson_residual', 'poisson_jacobian', 'binned', 'bin_rows', 'BinnedModel', 'erf_diff',
+           'psi_pair', 'PSI_X0', 'PSI_TERMS', 'SAMPLING']
 
 
 def _tp(xdata, P):
@@ -417,6 +426,278 @@ def resolve(f):
     return get(f)
 
 
+# ---- bin-integrated models -------------------------------------------------------------------------------------------
+# (BINNED instances of csrc/model_kernels.hip, blsq_model_eval_bin_dev)
+SQRT_HALF = 0.7071067811865476               # 1 / sqrt(2): erf argument of a gauss edge
+SQRT_PI_2 = 1.2533141373155001               # sqrt(pi / 2): integral of exp(-z^2 / 2) over the line, halved
+SQRT_LN2 = 0.8325546111576977                # sqrt(ln 2): erf argument of the Gaussian part of a pvoigt edge
+PV_GNORM = 1.0644670194312262                # sqrt(pi / ln 2) / 2
+PSI_X0 = 0.5                                 # |r w| below which psi and psi' are their series
+PSI_TERMS = 16                               # ... of this many terms
+
+
+def _fact(k):
+    """k! as a float (exact for k <= 18)."""
+    v = 1.0
+    for i in range(2, k + 1):
+        v *= i
+    return v
+
+
+def erf_diff(xl, xh):
+    """erf(xh) - erf(xl) without the cancellation of a tail: both arguments positive: erfc(xl) - erfc(xh); both negative:
+    erfc(-xh) - erfc(-xl); otherwise the plain difference.  scipy.special's float64 erf / erfc are the definition; another
+    dtype is computed in float64 and cast back."""
+    from scipy import special
+    xl, xh = np.broadcast_arrays(np.asarray(xl), np.asarray(xh))
+    dt = np.result_type(xl.dtype, np.float64)
+    a, b = xl.astype(np.float64), xh.astype(np.float64)
+    up = special.erfc(a) - special.erfc(b)
+    dn = special.erfc(-b) - special.erfc(-a)
+    mid = special.erf(b) - special.erf(a)
+    return np.where((a > 0) & (b > 0), up, np.where((a < 0) & (b < 0), dn, mid)).astype(dt, copy=False)
+
+
+def psi_pair(x):
+    """psi(x) = -expm1(-x) / x (psi(0) = 1) and its derivative psi'(x) = (x exp(-x) + expm1(-x)) / x^2 (-1 / 2 at 0): as
+    written where |x| >= PSI_X0, by PSI_TERMS terms of the series sum_k (-x)^k / (k + 1)! and
+    -sum_k (k + 1) (-x)^k / (k + 2)! (Horner) below."""
+    x = np.asarray(x)
+    dt = np.result_type(x.dtype, np.float64)
+    x = x.astype(dt, copy=False)
+    one = dt.type(1)
+    with np.errstate(all='ignore'):
+        T = PSI_TERMS
+        ps = np.full(x.shape, (-one) ** (T - 1) / dt.type(_fact(T)))
+        dp = np.full(x.shape, (-one) ** T * dt.type(T) / dt.type(_fact(T + 1)))
+        for k in range(T - 2, -1, -1):                                   # Horner
+            ps = ps * x + (-one) ** k / dt.type(_fact(k + 1))
+            dp = dp * x + (-one) ** (k + 1) * dt.type(k + 1) / dt.type(_fact(k + 2))
+        em = np.expm1(-x)
+        small = np.abs(x) < PSI_X0
+        ps = np.where(small, ps, -em / x)
+        dp = np.where(small, dp, (x * np.exp(-x) + em) / (x * x))
+    return ps, dp
+
+
+def _bfill_peak(lorentz):
+    def fill(lo, hi, P, K, J):
+        acc = None
+        for k in range(K):
+            a, mu, s = _col(P, 3 * k), _col(P, 3 * k + 1), _col(P, 3 * k + 2)
+            zl = (lo - mu) / s
+            zh = (hi - mu) / s
+            if lorentz:
+                el = 1.0 / (1.0 + zl * zl)
+                eh = 1.0 / (1.0 + zh * zh)
+                da = s * np.arctan2((hi - lo) / s, 1.0 + zh * zl)
+            else:
+                el = np.exp(-0.5 * (zl * zl))
+                eh = np.exp(-0.5 * (zh * zh))
+                da = (s * SQRT_PI_2) * erf_diff(zl * SQRT_HALF, zh * SQRT_HALF)
+            g = a * da
+            acc = g if acc is None else acc + g
+            if J is not None:
+                J[:, :, 3 * k] = da
+                J[:, :, 3 * k + 1] = a * (el - eh)
+                J[:, :, 3 * k + 2] = g / s - a * (zh * eh - zl * el)
+        return acc
+    return fill
+
+
+def _bfill_pvoigt(lo, hi, P, K, J):
+    acc = None
+    for k in range(K):
+        a, mu, s, eta = (_col(P, 4 * k + i) for i in range(4))
+        zl = (lo - mu) / s
+        zh = (hi - mu) / s
+        ql = zl * zl
+        qh = zh * zh
+        Gl = np.exp(-(LN2 * ql))
+        Gh = np.exp(-(LN2 * qh))
+        Ll = 1.0 / (1.0 + ql)
+        Lh = 1.0 / (1.0 + qh)
+        IG = (s * PV_GNORM) * erf_diff(zl * SQRT_LN2, zh * SQRT_LN2)
+        IL = s * np.arctan2((hi - lo) / s, 1.0 + zh * zl)
+        d = IL - IG
+        h = IG + eta * d
+        g = a * h
+        acc = g if acc is None else acc + g
+        if J is not None:
+            mG = Gl - Gh
+            uG = zh * Gh - zl * Gl
+            J[:, :, 4 * k] = h
+            J[:, :, 4 * k + 1] = a * (mG + eta * ((Ll - Lh) - mG))
+            J[:, :, 4 * k + 2] = g / s - a * (uG + eta * ((zh * Lh - zl * Ll) - uG))
+            J[:, :, 4 * k + 3] = a * d
+    return acc
+
+
+def _bfill_exp(lo, hi, P, K, J):
+    acc = None
+    w = hi - lo
+    for k in range(K):
+        a, r = _col(P, 2 * k), _col(P, 2 * k + 1)
+        ps, dp = psi_pair(r * w)
+        wE = w * np.exp(-(r * lo))
+        da = wE * ps
+        g = a * da
+        acc = g if acc is None else acc + g
+        if J is not None:
+            J[:, :, 2 * k] = da
+            J[:, :, 2 * k + 1] = (a * wE) * (w * dp - lo * ps)
+    return acc
+
+
+def _bfill_poly(lo, hi, P, K, J):
+    n = P.shape[1]
+    ph, pl = hi, lo
+    acc = None
+    for k in range(n):                                             # hi^(k+1), lo^(k+1) by repeated product
+        c = (ph - pl) / (k + 1)
+        if J is not None:
+            J[:, :, k] = c
+        v = _col(P, k) * c
+        acc = v if acc is None else acc + v
+        ph, pl = ph * hi, pl * lo
+    return acc
+
+
+_BFILL = {'gauss': _bfill_peak(False), 'lorentz': _bfill_peak(True), 'pvoigt': _bfill_pvoigt, 'exp': _bfill_exp,
+          'poly': _bfill_poly}
+_FAMILY_TERM = {'exp_sum': 'exp', 'gauss_sum': 'gauss', 'lorentz_sum': 'lorentz'}
+
+
+def bin_rows(edges):
+    """Contiguous bin edges (m + 1,) or (B, m + 1) as rows ``lo, hi``: (2, m) or (B, 2, m)."""
+    e = np.asarray(edges)
+    if e.ndim not in (1, 2) or e.shape[-1] < 2:
+        raise ValueError("`xdata`: bin edges must have shape (m + 1,) or (B, m + 1) with m >= 1, not %s." % (e.shape,))
+    return np.ascontiguousarray(np.stack([e[..., :-1], e[..., 1:]], axis=-2))
+
+
+class BinnedModel:
+    """The bin-integrated form of a ``Model`` or ``CompositeModel`` (``binned``): the value of row i is the
+    integral of the point-sampled model over the bin [lo_i, hi_i] (gauss2d: over the pixel [ulo, uhi] x [vlo, vhi]), the
+    expected content of the bin for a model read as a density.  Parameters, their order and ``n`` are the base model's;
+    the Jacobian columns are the integrals of its columns.  Offers what the base offers: ``name``, ``n`` (a composite),
+    ``terms``, ``check_xdata``, the numpy ``f`` / ``jac``, ``param_names`` (a composite), and ``base``.
+
+    ``f`` and ``jac`` take the edges as rows: (2, m) or (B, 2, m) ``lo, hi`` — (4, m) or (B, 4, m)
+    ``ulo, uhi, vlo, vhi`` for gauss2d — or, 1-D, the m + 1 contiguous edges shared by all problems (``bin_rows`` turns
+    (B, m + 1) into rows; ``check_xdata``, which knows m, takes every form).  They check nothing."""
+
+    binned = True
+
+    def __init__(self, base):
+        self.base, self.name, self.coords = base, base.name, base.coords
+        for attr in ('n', 'param_names', 'components', 'fam_ids', 'counts', 'id'):
+            if hasattr(base, attr):
+                setattr(self, attr, getattr(base, attr))
+
+    def terms(self, n):
+        return self.base.terms(n)
+
+    def rule(self):
+        return self.base.rule()
+
+    def _components(self, n):
+        if isinstance(self.base, CompositeModel):
+            return self.base.components
+        self.base.terms(n)
+        if self.base.name == 'poly':
+            return (('poly', n),)
+        fam = _FAMILY_TERM[self.base.name]
+        return ((fam, (n - 1) // TERMS[fam].n_per_term), ('poly', 1))
+
+    def _rows(self, xdata, P):
+        x, P = _tp(xdata, P)
+        if x.ndim == 1 and self.coords == 1:
+            return [x[:-1], x[1:]], P
+        return [x[..., r, :] for r in range(2 * self.coords)], P
+
+    def _walk(self, xdata, P, want_J):
+        (lo, hi), P = self._rows(xdata, P)
+        n = P.shape[1]
+        J = np.empty((P.shape[0], lo.shape[-1], n), dtype=P.dtype) if want_J else None
+        acc, o = None, 0
+        for fam, K in self._components(n):
+            w = K * TERMS[fam].n_per_term
+            v = _BFILL[fam](lo, hi, P[:, o:o + w], K, None if J is None else J[:, :, o:o + w])
+            acc = v if acc is None else acc + v
+            o += w
+        return acc, J
+
+    def _g2(self, xdata, P, want_J):
+        (ulo, uhi, vlo, vhi), P = self._rows(xdata, P)
+        a, u0, v0, s, c = (_col(P, k) for k in range(5))
+        zul, zuh = (ulo - u0) / s, (uhi - u0) / s
+        zvl, zvh = (vlo - v0) / s, (vhi - v0) / s
+        c1 = s * SQRT_PI_2
+        Iu = c1 * erf_diff(zul * SQRT_HALF, zuh * SQRT_HALF)
+        Iv = c1 * erf_diff(zvl * SQRT_HALF, zvh * SQRT_HALF)
+        da = Iu * Iv
+        ww = (uhi - ulo) * (vhi - vlo)
+        val = a * da + c * ww
+        if not want_J:
+            return val, None
+        eul, euh = np.exp(-0.5 * (zul * zul)), np.exp(-0.5 * (zuh * zuh))
+        evl, evh = np.exp(-0.5 * (zvl * zvl)), np.exp(-0.5 * (zvh * zvh))
+        J = np.empty(val.shape + (5,), dtype=P.dtype)
+        J[:, :, 0] = da
+        J[:, :, 1] = (a * (eul - euh)) * Iv
+        J[:, :, 2] = (a * (evl - evh)) * Iu
+        J[:, :, 3] = a * ((Iu / s - (zuh * euh - zul * eul)) * Iv + Iu * (Iv / s - (zvh * evh - zvl * evl)))
+        J[:, :, 4] = ww
+        return val, J
+
+    def f(self, xdata, P):
+        return (self._g2 if self.coords == 2 else self._walk)(xdata, P, False)[0]
+
+    def jac(self, xdata, P):
+        return (self._g2 if self.coords == 2 else self._walk)(xdata, P, True)[1]
+
+    def check_xdata(self, xdata, B, m):
+        """The edges as a float64 array of rows, (2 coords, m) or (B, 2 coords, m), from any accepted form: contiguous
+        edges (m + 1,) / (B, m + 1) (one coordinate only) or rows (2, m) / (B, 2, m) — (4, m) / (B, 4, m) for gauss2d.
+        ValueError for another shape, and for the first bin whose edges are not finite or have lo >= hi.  Returns
+        (array, per_problem)."""
+        x = np.asarray(xdata, dtype=np.float64)
+        R = 2 * self.coords
+        if self.coords == 1 and x.shape in ((m + 1,), (B, m + 1)):
+            x = bin_rows(x)
+        if x.shape == (B, R, m):
+            per_problem = True
+        elif x.shape == (R, m):
+            per_problem = False
+        else:
+            forms = ("(m + 1,), (B, m + 1), (2, m) or (B, 2, m)" if self.coords == 1 else "(4, m) or (B, 4, m)")
+            raise ValueError("`xdata` of binned model '%s' must have shape %s with B = %d, m = %d, not %s."
+                             % (self.name, forms, B, m, np.shape(xdata)))
+        x = np.ascontiguousarray(x)
+        for c in range(self.coords):
+            lo, hi = x[..., 2 * c, :], x[..., 2 * c + 1, :]
+            with np.errstate(invalid='ignore'):
+                bad = ~(np.isfinite(lo) & np.isfinite(hi) & (lo < hi))
+            if bad.any():
+                idx = tuple(int(i) for i in np.argwhere(bad)[0])
+                where = "bin %d" % idx[-1] + (" of problem %d" % idx[0] if per_problem else "")
+                raise ValueError("`xdata` of binned model '%s': %s%s has lo = %r, hi = %r; bin edges must be finite "
+                                 "with lo < hi." % (self.name, where, " (coordinate %d)" % c if self.coords > 1 else "",
+                                                    float(lo[idx]), float(hi[idx])))
+        return x, per_problem
+
+    def __repr__(self):
+        return "BinnedModel(%r)" % self.name
+
+
+def binned(model):
+    """The ``BinnedModel`` of a name, a composite spec, a ``Model`` or a ``CompositeModel`` (a ``BinnedModel`` as it is)."""
+    if isinstance(model, BinnedModel):
+        return model
+    return BinnedModel(model if isinstance(model, Model) else resolve(model))
+
+
 # ---- the Poisson estimator -------------------------------------------------------------------------------------------
 def check_estimator(estimator):
     """`estimator` if it is one of ``ESTIMATORS``; ValueError otherwise."""
@@ -487,11 +768,17 @@ class DeviceModel:
 
     ``estimator='poisson'``: the callbacks give the deviance residuals of the counts `ydata` and their
     Jacobian, through blsq_model_eval_est_dev for every kind of model; `ydata` is then required and `sigma` must be
-    None (ValueError).  The bounds must keep the model positive."""
+    None (ValueError).  The bounds must keep the model positive.
 
-    def __init__(self, ctx, name, B, m, n, xdata, ydata=None, sigma=None, param_map=None, Pfix=None, estimator='lse'):
+    ``binned=True``: the bin-integrated form of the model (``binned``).  `xdata` holds the bin edges in
+    any form ``BinnedModel.check_xdata`` takes (checked on the host: finite, lo < hi) and is uploaded as rows; every
+    kind of model and both estimators then go through blsq_model_eval_bin_dev."""
+
+    def __init__(self, ctx, name, B, m, n, xdata, ydata=None, sigma=None, param_map=None, Pfix=None, estimator='lse',
+                 binned=False):
         model = resolve(name)
         model.terms(n)
+        self.binned = bool(binned)
         self.estimator = check_estimator(estimator)
         if estimator == 'poisson':
             if ydata is None:
@@ -503,7 +790,7 @@ class DeviceModel:
         if param_map is not None and param_map.n != self.n_model:
             raise ValueError("`param_map` is for %d parameters, the model has %d." % (param_map.n, self.n_model))
         self.n = self.n_model if param_map is None else param_map.nf
-        x, per_problem = model.check_xdata(xdata, self.B, self.m)
+        x, per_problem = (BinnedModel(model) if self.binned else model).check_xdata(xdata, self.B, self.m)
         y = w = None
         if ydata is not None:
             y = np.ascontiguousarray(ydata, dtype=np.float64)
@@ -519,7 +806,7 @@ class DeviceModel:
             elif sg.shape != (self.m,):
                 raise ValueError("`sigma` has incorrect shape.")
             w = np.ascontiguousarray(1.0 / sg)
-        self.t_stride = model.coords * self.m if per_problem else 0
+        self.t_stride = (2 if self.binned else 1) * model.coords * self.m if per_problem else 0
         self.ctx = ctx
         self._bufs = []
         self.d_t = self._upload(x)
@@ -551,6 +838,16 @@ class DeviceModel:
         return self.bounds_dev
 
     def _eval(self, x_ptr, reps, f_ptr, J_ptr, mask_ptr):
+        if self.binned:                                       # every kind of model, both estimators: one entry
+            M, comp = self.model, isinstance(self.model, CompositeModel)
+            self.ctx.check(self.ctx.lib.blsq_model_eval_bin_dev(
+                self.ctx.h, ESTIMATORS.index(self.estimator), SAMPLING.index('bin'), -1 if comp else M.id,
+                len(M.components) if comp else 0, M.fam_ids.ctypes.data_as(_abi.c_int32_p) if comp else None,
+                M.counts.ctypes.data_as(_abi.c_int32_p) if comp else None, self.B, int(reps), self.m, self.n_model,
+                self.n, None if self.param_map is None else self._pmap.ctypes.data_as(_abi.c_int32_p), self.d_t,
+                self.t_stride, self.d_y, self.d_w, self.w_stride, x_ptr, self.d_Pfix, f_ptr, J_ptr, mask_ptr),
+                "blsq_model_eval_bin_dev")
+            return
         if self.estimator != 'lse':                           # every kind of model: one entry
             M, comp = self.model, isinstance(self.model, CompositeModel)
             self.ctx.check(self.ctx.lib.blsq_model_eval_est_dev(
@@ -605,11 +902,12 @@ class DeviceFit:
     """What ``least_squares_batch(fun=...)`` takes in place of a callable for a fit whose callbacks run on the device:
     a checked (model, data) pair that opens a ``DeviceModel`` on the driver's context.  Built by ``curve_fit_batch``.
     ``n`` is the number of solver variables (the width of x0): the model's n, or nf of `param_map`; ``n_model`` is the
-    model's number of parameters.  ``estimator='poisson'``: as ``DeviceModel``."""
+    model's number of parameters.  ``estimator='poisson'`` and ``binned=True``: as ``DeviceModel``."""
 
-    def __init__(self, name, n, xdata, ydata, sigma=None, param_map=None, Pfix=None, estimator='lse'):
+    def __init__(self, name, n, xdata, ydata, sigma=None, param_map=None, Pfix=None, estimator='lse', binned=False):
         self.model = resolve(name)
         self.model.terms(n)
+        self.binned = bool(binned)
         self.estimator = check_estimator(estimator)
         if estimator == 'poisson' and sigma is not None:
             raise ValueError("`sigma` must be None with estimator='poisson'.")
@@ -624,20 +922,23 @@ class DeviceFit:
             if self.Pfix.shape != (self.B, self.n_model):
                 raise ValueError("`Pfix` must have shape (B, n).")
         self.n = self.n_model if param_map is None else param_map.nf
-        self.xdata, _ = self.model.check_xdata(xdata, self.B, self.m)
+        checker = BinnedModel(self.model) if self.binned else self.model
+        self.xdata, _ = checker.check_xdata(xdata, self.B, self.m)
         self.sigma = sigma
 
     def open_device(self, ctx, lb, ub):
         dm = DeviceModel(ctx, self.model.name, self.B, self.m, self.n_model, self.xdata, self.ydata, self.sigma,
-                         self.param_map, self.Pfix, self.estimator)
+                         self.param_map, self.Pfix, self.estimator, **({'binned': True} if self.binned else {}))
         dm.set_bounds(lb, ub)
         return dm
 
 
-def evaluate(name, xdata, P, ctx=None):
+def evaluate(name, xdata, P, ctx=None, binned=False):
     """Predictions ``model(xdata; P[b])`` of shape (B, m), computed on the GPU (the kernel with y = NULL, w = NULL).
     P: (B, n); xdata: (m,) / (B, m), or (2, m) / (B, 2, m) for 'gauss2d'.  `name`: a name, a composite spec or a
-    ``CompositeModel``."""
+    ``CompositeModel``.  ``binned=True``: the bin contents of the bin-integrated model; `xdata` is then the m + 1
+    contiguous edges (1-D) or rows (2, m) / (B, 2, m) — (4, m) / (B, 4, m) for 'gauss2d' — as ``BinnedModel.f`` takes
+    them."""
     model = resolve(name)
     P = np.ascontiguousarray(P, dtype=np.float64)
     if P.ndim != 2:
@@ -648,12 +949,18 @@ def evaluate(name, xdata, P, ctx=None):
     if x.ndim < 1 or x.shape[-1] == 0:
         raise ValueError("`xdata` must not be empty.")
     m = x.shape[-1]
-    model.check_xdata(x, B, m)
+    if binned:
+        if x.ndim == 1 and model.coords == 1:
+            x = bin_rows(x)
+            m = x.shape[-1]
+        BinnedModel(model).check_xdata(x, B, m)
+    else:
+        model.check_xdata(x, B, m)
     own = ctx is None
     if own:
         ctx = _abi.Context(0)
     try:
-        with DeviceModel(ctx, model.name, B, m, n, x) as dm:
+        with DeviceModel(ctx, model.name, B, m, n, x, **({'binned': True} if binned else {})) as dm:
             d_P = ctx.to_device(P)
             d_f = ctx.malloc(8 * B * m)
             try:

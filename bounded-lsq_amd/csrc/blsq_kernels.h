@@ -614,21 +614,25 @@ hipError_t launch_fd_assemble(int B, int m, int n, int method, const double* x, 
 // P [B * reps][n]; t_stride 0 (shared) or coords * m, w nullptr or stride 0 / m, y / mask may be nullptr.
 // est (all three launches; blsq_model_eval_est_dev, 7m): BLSQ_EST_LSE, or BLSQ_EST_POISSON for the deviance residual
 // and its Jacobian, which needs y and w == nullptr (hipErrorInvalidValue otherwise).
+// sampling (all three launches; blsq_model_eval_bin_dev, 7n): BLSQ_SAMPLE_POINT, or BLSQ_SAMPLE_BIN for the model
+// integrated over the bins t [2 coords][m] (rows lo, hi per coordinate; t_stride 0 or 2 * coords * m).
 hipError_t launch_model_eval(int model, int B, int reps, int m, int n, const double* t, long t_stride, const double* y,
                              const double* w, long w_stride, const double* P, double* f, double* J, const int* mask,
-                             hipStream_t s, int est = 0 /* BLSQ_EST_LSE */);
+                             hipStream_t s, int est = 0 /* BLSQ_EST_LSE */,
+                             int sampling = 0 /* BLSQ_SAMPLE_POINT */);
 // The same through a parameter map (blsq_model_eval_map_dev, 7k): X [B * reps][nf], pmap [n] on the host (-1 or a slot
 // < nf, every slot used: the caller has checked), Pfix [B][n] (read where pmap[j] == -1), J [B][m][nf].
 hipError_t launch_model_eval_map(int model, int B, int reps, int m, int n, int nf, const int* pmap, const double* t,
                                  long t_stride, const double* y, const double* w, long w_stride, const double* X,
                                  const double* Pfix, double* f, double* J, const int* mask, hipStream_t s,
-                                 int est = 0 /* BLSQ_EST_LSE */);
+                                 int est = 0 /* BLSQ_EST_LSE */, int sampling = 0 /* BLSQ_SAMPLE_POINT */);
 // A composite model (blsq_model_eval_comp_dev, 7l): ncomp <= BLSQ_MODEL_MAX_COMP components {fam[c] (BLSQ_TERM_*),
 // cnt[c]} on the host whose parameters add up to n; pmap nullptr (unmapped: X is P [B * reps][n], nf ignored) or as above.
 hipError_t launch_model_eval_comp(int ncomp, const int* fam, const int* cnt, int B, int reps, int m, int n, int nf,
                                   const int* pmap, const double* t, long t_stride, const double* y, const double* w,
                                   long w_stride, const double* X, const double* Pfix, double* f, double* J,
-                                  const int* mask, hipStream_t s, int est = 0 /* BLSQ_EST_LSE */);
+                                  const int* mask, hipStream_t s, int est = 0 /* BLSQ_EST_LSE */,
+                                  int sampling = 0 /* BLSQ_SAMPLE_POINT */);
 
 // ---------------------------------------------------------------- probes ----
 // probe_kernels.hip: measured peaks / counter calibration (blsq_debug_probe)

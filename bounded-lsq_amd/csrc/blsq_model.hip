@@ -1,7 +1,8 @@
 // Built-in fit models: the table behind blsq_model_count / blsq_model_info and the entry point blsq_model_eval_dev
 // (include/blsq.h; kernel: model_kernels.hip), its mapped form blsq_model_eval_map_dev (7k), and the term
 // table behind blsq_term_count / blsq_term_info with the composite entry blsq_model_eval_comp_dev (7l), and the entry
-// that takes the estimator for all of them, blsq_model_eval_est_dev (7m).
+// that takes the estimator for all of them, blsq_model_eval_est_dev (7m), and the one that takes the sampling as well,
+// blsq_model_eval_bin_dev (7n).
 #include "blsq_host.h"
 
 namespace {
@@ -162,71 +163,99 @@ extern "C" int blsq_model_eval_comp_dev(blsq_ctx* ctx, int ncomp, const int32_t*
   });
 }
 
-// One entry for every instance, with the estimator: the checks of the three entries above under this
-// entry's own argument numbers, then the launch of the entry it stands in for.
+// One entry for every instance, with the estimator and the sampling (7n): the checks of the three entries
+// above, then the launch of the entry it stands in for.  blsq_model_eval_est_dev numbers its arguments from est = 2,
+// model = 3; blsq_model_eval_bin_dev has `sampling` in between, so every later argument is one further on (sh = 1).
+static int model_eval_checked(blsq_ctx* ctx, const char* what, int sh, int est, int sampling, int model, int ncomp,
+                              const int32_t* fam, const int32_t* cnt, int B, int reps, int m, int n, int nf,
+                              const int32_t* pmap, const double* dt, long t_stride, const double* dy, const double* dw,
+                              long w_stride, const double* dX, const double* dPfix, double* df, double* dJ,
+                              const int32_t* dmask) {
+  if (!ctx) return -1;
+  if (est != BLSQ_EST_LSE && est != BLSQ_EST_POISSON) return ctx->bad(2, "est must be one of BLSQ_EST_*");
+  if (sampling != BLSQ_SAMPLE_POINT && sampling != BLSQ_SAMPLE_BIN)
+    return ctx->bad(3, "sampling must be one of BLSQ_SAMPLE_*");
+  if (model < -1 || model >= kModelCount)
+    return ctx->bad(3 + sh, "model must be one of BLSQ_MODEL_*, or -1 for a composite");
+  const bool comp = model < 0;
+  long total = 0;
+  if (!comp) {
+    if (ncomp != 0) return ctx->bad(4 + sh, "ncomp must be 0 with a named model");
+  } else {
+    if (ncomp < 1 || ncomp > BLSQ_MODEL_MAX_COMP) return ctx->bad(4 + sh, "ncomp must be in 1 .. BLSQ_MODEL_MAX_COMP");
+    if (!fam) return ctx->bad(5 + sh, "fam is NULL");
+    if (!cnt) return ctx->bad(6 + sh, "cnt is NULL");
+    for (int c = 0; c < ncomp; ++c) {
+      if (fam[c] < 0 || fam[c] >= kTermCount) return ctx->bad(5 + sh, "fam entry must be one of BLSQ_TERM_*");
+      if (cnt[c] < 1) return ctx->bad(6 + sh, "cnt entry must be at least 1");
+      total += (long)cnt[c] * kTerms[fam[c]].n_per_term;
+    }
+  }
+  if (B <= 0) return ctx->bad(7 + sh, "B must be positive");
+  if (reps <= 0) return ctx->bad(8 + sh, "reps must be positive");
+  if (m <= 0) return ctx->bad(9 + sh, "m must be positive");
+  if (comp) {
+    if (n < 1 || n > BLSQ_MODEL_MAX_N || total != n)
+      return ctx->bad(10 + sh, "n must be the parameters of the components together (and at most BLSQ_MODEL_MAX_N)");
+  } else if (!model_n_fits(kModels[model], n)) {
+    return ctx->bad(10 + sh, "n does not fit the model (or exceeds BLSQ_MODEL_MAX_N)");
+  }
+  bool any_fixed = false;
+  if (!pmap) {
+    if (nf != n) return ctx->bad(11 + sh, "nf must equal n without a pmap");
+  } else {
+    if (nf < 1 || nf > n) return ctx->bad(11 + sh, "nf must be in 1 .. n");
+    bool used[BLSQ_MODEL_MAX_N] = {};
+    for (int j = 0; j < n; ++j) {
+      if (pmap[j] < -1 || pmap[j] >= nf) return ctx->bad(23 + sh, "pmap entry outside -1 .. nf - 1");
+      if (pmap[j] < 0) any_fixed = true;
+      else used[pmap[j]] = true;
+    }
+    for (int k = 0; k < nf; ++k)
+      if (!used[k]) return ctx->bad(24 + sh, "pmap leaves a variable k < nf unused");
+  }
+  const long coords = comp ? 1 : kModels[model].coords;
+  if (!dt) return ctx->bad(13 + sh, "t is NULL");
+  if (sampling == BLSQ_SAMPLE_BIN) {
+    if (t_stride != 0 && t_stride != 2 * coords * m)
+      return ctx->bad(14 + sh, "t_stride must be 0 or 2 * coords * m with BLSQ_SAMPLE_BIN");
+  } else if (t_stride != 0 && t_stride != coords * m) {
+    return ctx->bad(14 + sh, "t_stride must be 0 or coords * m");
+  }
+  if (est == BLSQ_EST_POISSON && !dy) return ctx->bad(15 + sh, "y is NULL: the Poisson estimator needs the counts");
+  if (est == BLSQ_EST_POISSON && dw) return ctx->bad(16 + sh, "w must be NULL with the Poisson estimator");
+  if (dw && w_stride != 0 && w_stride != (long)m) return ctx->bad(17 + sh, "w_stride must be 0 or m");
+  if (!dX) return ctx->bad(18 + sh, "X is NULL");
+  if (any_fixed && !dPfix) return ctx->bad(19 + sh, "Pfix is NULL although pmap holds a parameter fixed");
+  if (!df && !dJ) return ctx->bad(20 + sh, "f and J are both NULL");
+  if (dJ && reps != 1) return ctx->bad(21 + sh, "J requires reps == 1");
+  HIPCHK(ctx, hipSetDevice(ctx->device));
+  return ctx->run(K_MODEL_EVAL, what, [&] {
+    if (comp)
+      return launch_model_eval_comp(ncomp, fam, cnt, B, reps, m, n, nf, pmap, dt, t_stride, dy, dw, w_stride, dX, dPfix,
+                                    df, dJ, dmask, ctx->stream, est, sampling);
+    if (pmap)
+      return launch_model_eval_map(model, B, reps, m, n, nf, pmap, dt, t_stride, dy, dw, w_stride, dX, dPfix, df, dJ,
+                                   dmask, ctx->stream, est, sampling);
+    return launch_model_eval(model, B, reps, m, n, dt, t_stride, dy, dw, w_stride, dX, df, dJ, dmask, ctx->stream, est,
+                             sampling);
+  });
+}
+
 extern "C" int blsq_model_eval_est_dev(blsq_ctx* ctx, int est, int model, int ncomp, const int32_t* fam,
                                        const int32_t* cnt, int B, int reps, int m, int n, int nf, const int32_t* pmap,
                                        const double* dt, long t_stride, const double* dy, const double* dw,
                                        long w_stride, const double* dX, const double* dPfix, double* df, double* dJ,
                                        const int32_t* dmask) {
-  if (!ctx) return -1;
-  if (est != BLSQ_EST_LSE && est != BLSQ_EST_POISSON) return ctx->bad(2, "est must be one of BLSQ_EST_*");
-  if (model < -1 || model >= kModelCount) return ctx->bad(3, "model must be one of BLSQ_MODEL_*, or -1 for a composite");
-  const bool comp = model < 0;
-  long total = 0;
-  if (!comp) {
-    if (ncomp != 0) return ctx->bad(4, "ncomp must be 0 with a named model");
-  } else {
-    if (ncomp < 1 || ncomp > BLSQ_MODEL_MAX_COMP) return ctx->bad(4, "ncomp must be in 1 .. BLSQ_MODEL_MAX_COMP");
-    if (!fam) return ctx->bad(5, "fam is NULL");
-    if (!cnt) return ctx->bad(6, "cnt is NULL");
-    for (int c = 0; c < ncomp; ++c) {
-      if (fam[c] < 0 || fam[c] >= kTermCount) return ctx->bad(5, "fam entry must be one of BLSQ_TERM_*");
-      if (cnt[c] < 1) return ctx->bad(6, "cnt entry must be at least 1");
-      total += (long)cnt[c] * kTerms[fam[c]].n_per_term;
-    }
-  }
-  if (B <= 0) return ctx->bad(7, "B must be positive");
-  if (reps <= 0) return ctx->bad(8, "reps must be positive");
-  if (m <= 0) return ctx->bad(9, "m must be positive");
-  if (comp) {
-    if (n < 1 || n > BLSQ_MODEL_MAX_N || total != n)
-      return ctx->bad(10, "n must be the parameters of the components together (and at most BLSQ_MODEL_MAX_N)");
-  } else if (!model_n_fits(kModels[model], n)) {
-    return ctx->bad(10, "n does not fit the model (or exceeds BLSQ_MODEL_MAX_N)");
-  }
-  bool any_fixed = false;
-  if (!pmap) {
-    if (nf != n) return ctx->bad(11, "nf must equal n without a pmap");
-  } else {
-    if (nf < 1 || nf > n) return ctx->bad(11, "nf must be in 1 .. n");
-    bool used[BLSQ_MODEL_MAX_N] = {};
-    for (int j = 0; j < n; ++j) {
-      if (pmap[j] < -1 || pmap[j] >= nf) return ctx->bad(23, "pmap entry outside -1 .. nf - 1");
-      if (pmap[j] < 0) any_fixed = true;
-      else used[pmap[j]] = true;
-    }
-    for (int k = 0; k < nf; ++k)
-      if (!used[k]) return ctx->bad(24, "pmap leaves a variable k < nf unused");
-  }
-  const long coords = comp ? 1 : kModels[model].coords;
-  if (!dt) return ctx->bad(13, "t is NULL");
-  if (t_stride != 0 && t_stride != coords * m) return ctx->bad(14, "t_stride must be 0 or coords * m");
-  if (est == BLSQ_EST_POISSON && !dy) return ctx->bad(15, "y is NULL: the Poisson estimator needs the counts");
-  if (est == BLSQ_EST_POISSON && dw) return ctx->bad(16, "w must be NULL with the Poisson estimator");
-  if (dw && w_stride != 0 && w_stride != (long)m) return ctx->bad(17, "w_stride must be 0 or m");
-  if (!dX) return ctx->bad(18, "X is NULL");
-  if (any_fixed && !dPfix) return ctx->bad(19, "Pfix is NULL although pmap holds a parameter fixed");
-  if (!df && !dJ) return ctx->bad(20, "f and J are both NULL");
-  if (dJ && reps != 1) return ctx->bad(21, "J requires reps == 1");
-  HIPCHK(ctx, hipSetDevice(ctx->device));
-  return ctx->run(K_MODEL_EVAL, "launch_model_eval_est", [&] {
-    if (comp)
-      return launch_model_eval_comp(ncomp, fam, cnt, B, reps, m, n, nf, pmap, dt, t_stride, dy, dw, w_stride, dX, dPfix,
-                                    df, dJ, dmask, ctx->stream, est);
-    if (pmap)
-      return launch_model_eval_map(model, B, reps, m, n, nf, pmap, dt, t_stride, dy, dw, w_stride, dX, dPfix, df, dJ,
-                                   dmask, ctx->stream, est);
-    return launch_model_eval(model, B, reps, m, n, dt, t_stride, dy, dw, w_stride, dX, df, dJ, dmask, ctx->stream, est);
-  });
+  return model_eval_checked(ctx, "launch_model_eval_est", 0, est, BLSQ_SAMPLE_POINT, model, ncomp, fam, cnt, B, reps, m,
+                            n, nf, pmap, dt, t_stride, dy, dw, w_stride, dX, dPfix, df, dJ, dmask);
+}
+
+extern "C" int blsq_model_eval_bin_dev(blsq_ctx* ctx, int est, int sampling, int model, int ncomp, const int32_t* fam,
+                                       const int32_t* cnt, int B, int reps, int m, int n, int nf, const int32_t* pmap,
+                                       const double* dt, long t_stride, const double* dy, const double* dw,
+                                       long w_stride, const double* dX, const double* dPfix, double* df, double* dJ,
+                                       const int32_t* dmask) {
+  return model_eval_checked(ctx, "launch_model_eval_bin", 1, est, sampling, model, ncomp, fam, cnt, B, reps, m, n, nf,
+                            pmap, dt, t_stride, dy, dw, w_stride, dX, dPfix, df, dJ, dmask);
 }

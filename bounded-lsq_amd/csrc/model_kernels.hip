@@ -44,6 +44,14 @@
 // field of ModelArgs: the least-squares instances are then the instructions they were before it existed, and the 24
 // instances build in 4.3 s where the 12 took 3.8 s, next to files that take a minute, so build time does not argue for
 // a runtime field, which would put the transform's registers and branch into every least-squares instance.
+//
+// Bin-integrated instances (BINNED = true; blsq_model_eval_bin_dev with BLSQ_SAMPLE_BIN).  The value of
+// row i is the integral of the model over the bin [lo, hi], lo = t[b][0][i], hi = t[b][1][i] (gauss2d: the pixel
+// [t[b][0][i], t[b][1][i]] x [t[b][2][i], t[b][3][i]]), and the columns are the integrals of the point-sampled columns:
+// the *_bin functions below, operation by operation the _bfill_* functions of bounded_lsq/_models.py; erf, erfc, atan2,
+// expm1 and exp are the only differences.  They feed the same puts, so the shell, the Poisson row pass and the stream-out
+// are untouched.  A template flag for the reason given for POISSON: the point-sampled instances are the instructions
+// they were.
 #include "../../include/blsq.h"
 #include "blsq_device.h"
 #include "blsq_kernels.h"
@@ -174,6 +182,166 @@ __device__ __forceinline__ double poly_terms(const double* __restrict__ p, int o
   return acc;
 }
 
+// ---- the bin-integrated terms (models.erf_diff, models.psi_pair and the _bfill_* functions)
+static constexpr double SQRT_HALF = 0.7071067811865476;     // 1 / sqrt(2)
+static constexpr double SQRT_PI_2 = 1.2533141373155001;     // sqrt(pi / 2)
+static constexpr double SQRT_LN2 = 0.8325546111576977;      // sqrt(ln 2)
+static constexpr double PV_GNORM = 1.0644670194312262;      // sqrt(pi / ln 2) / 2
+static constexpr double PSI_X0 = 0.5;
+static constexpr int PSI_TERMS = 16;
+
+// erf(xh) - erf(xl): by erfc of the magnitudes where both arguments lie in one tail (no cancellation against 1)
+__device__ __forceinline__ double erf_diff(double xl, double xh) {
+  if (xl > 0.0 && xh > 0.0) return erfc(xl) - erfc(xh);
+  if (xl < 0.0 && xh < 0.0) return erfc(-xh) - erfc(-xl);
+  return erf(xh) - erf(xl);
+}
+
+__host__ __device__ constexpr double psi_fact(int k) {
+  double v = 1.0;
+  for (int i = 2; i <= k; ++i) v = v * (double)i;
+  return v;
+}
+
+// psi(x) = -expm1(-x) / x and psi'(x) = (x exp(-x) + expm1(-x)) / x^2: as written where |x| >= PSI_X0, by PSI_TERMS terms
+// of their series below (Horner; the coefficients are constants folded at compile time)
+__device__ __forceinline__ void psi_pair(double x, double& ps, double& dp) {
+  if (fabs(x) < PSI_X0) {
+    ps = ((PSI_TERMS - 1) & 1 ? -1.0 : 1.0) / psi_fact(PSI_TERMS);
+    dp = ((PSI_TERMS & 1 ? -1.0 : 1.0) * (double)PSI_TERMS) / psi_fact(PSI_TERMS + 1);
+#pragma unroll
+    for (int k = PSI_TERMS - 2; k >= 0; --k) {
+      ps = ps * x + (k & 1 ? -1.0 : 1.0) / psi_fact(k + 1);
+      dp = dp * x + (((k + 1) & 1 ? -1.0 : 1.0) * (double)(k + 1)) / psi_fact(k + 2);
+    }
+  } else {
+    const double em = expm1(-x);
+    ps = -em / x;
+    dp = (x * exp(-x) + em) / (x * x);
+  }
+}
+
+template <bool MAPPED>
+__device__ __forceinline__ double exp_bin(const double* __restrict__ p, int o, double lo, double hi, double wi,
+                                          double* row, const signed char* pm) {
+  const double a = p[o], r = p[o + 1];
+  const double w = hi - lo;
+  double ps, dp;
+  psi_pair(r * w, ps, dp);
+  const double wE = w * exp(-(r * lo));
+  const double da = wE * ps;
+  if (row) { PUT(o, wi * da); PUT(o + 1, wi * ((a * wE) * (w * dp - lo * ps))); }
+  return a * da;
+}
+
+template <bool LORENTZ, bool MAPPED>
+__device__ __forceinline__ double peak_bin(const double* __restrict__ p, int o, double lo, double hi, double wi,
+                                           double* row, const signed char* pm) {
+  const double a = p[o], mu = p[o + 1], s = p[o + 2];
+  const double zl = (lo - mu) / s, zh = (hi - mu) / s;
+  double da;
+  if (!LORENTZ) da = (s * SQRT_PI_2) * erf_diff(zl * SQRT_HALF, zh * SQRT_HALF);
+  else da = s * atan2((hi - lo) / s, 1.0 + zh * zl);
+  const double g = a * da;
+  if (row) {
+    double el, eh;
+    if (!LORENTZ) { el = exp(-0.5 * (zl * zl)); eh = exp(-0.5 * (zh * zh)); }
+    else { el = 1.0 / (1.0 + zl * zl); eh = 1.0 / (1.0 + zh * zh); }
+    PUT(o, wi * da);
+    PUT(o + 1, wi * (a * (el - eh)));
+    PUT(o + 2, wi * (g / s - a * (zh * eh - zl * el)));
+  }
+  return g;
+}
+
+template <bool MAPPED>
+__device__ __forceinline__ double pvoigt_bin(const double* __restrict__ p, int o, double lo, double hi, double wi,
+                                             double* row, const signed char* pm) {
+  constexpr double LN2 = 0.6931471805599453;
+  const double a = p[o], mu = p[o + 1], s = p[o + 2], eta = p[o + 3];
+  const double zl = (lo - mu) / s, zh = (hi - mu) / s;
+  const double IG = (s * PV_GNORM) * erf_diff(zl * SQRT_LN2, zh * SQRT_LN2);
+  const double IL = s * atan2((hi - lo) / s, 1.0 + zh * zl);
+  const double d = IL - IG;
+  const double h = IG + eta * d;
+  const double g = a * h;
+  if (row) {
+    const double ql = zl * zl, qh = zh * zh;
+    const double Gl = exp(-(LN2 * ql)), Gh = exp(-(LN2 * qh));
+    const double Ll = 1.0 / (1.0 + ql), Lh = 1.0 / (1.0 + qh);
+    const double mG = Gl - Gh;
+    const double uG = zh * Gh - zl * Gl;
+    PUT(o, wi * h);
+    PUT(o + 1, wi * (a * (mG + eta * ((Ll - Lh) - mG))));
+    PUT(o + 2, wi * (g / s - a * (uG + eta * ((zh * Lh - zl * Ll) - uG))));
+    PUT(o + 3, wi * (a * d));
+  }
+  return g;
+}
+
+// polynomial of d coefficients over the bin: column k is (hi^(k+1) - lo^(k+1)) / (k + 1), the powers by repeated product;
+// the value the sequential sum of p_k times its column
+template <bool MAPPED>
+__device__ __forceinline__ double poly_bin(const double* __restrict__ p, int o, int d, double lo, double hi, double wi,
+                                           double* row, const signed char* pm) {
+  double ph = hi, pl = lo, acc = 0.0;
+  for (int k = 0; k < d; ++k) {
+    const double c = (ph - pl) / (double)(k + 1);
+    if (row) PUT(o + k, wi * c);
+    const double v = p[o + k] * c;
+    acc = (k == 0) ? v : acc + v;
+    ph = ph * hi; pl = pl * lo;
+  }
+  return acc;
+}
+
+// The bin-integrated terms of one row of a named model: the family's terms and 'poly*1', as the composite walks them.
+template <int MODEL, bool MAPPED>
+__device__ __forceinline__ double model_row_bin(int n, int m, const double* __restrict__ tb, int i,
+                                                const double* __restrict__ p, double wi, double* row,
+                                                const signed char* pm) {
+  const double lo = tb[i], hi = tb[m + i];
+  if (MODEL == BLSQ_MODEL_POLY) return poly_bin<MAPPED>(p, 0, n, lo, hi, wi, row, pm);
+  if (MODEL == BLSQ_MODEL_EXP_SUM) {
+    const int K = (n - 1) / 2;
+    double acc = 0.0;
+    for (int k = 0; k < K; ++k) {
+      const double g = exp_bin<MAPPED>(p, 2 * k, lo, hi, wi, row, pm);
+      acc = (k == 0) ? g : acc + g;
+    }
+    return acc + poly_bin<MAPPED>(p, n - 1, 1, lo, hi, wi, row, pm);
+  }
+  if (MODEL == BLSQ_MODEL_GAUSS_SUM || MODEL == BLSQ_MODEL_LORENTZ_SUM) {
+    const int K = (n - 1) / 3;
+    double acc = 0.0;
+    for (int k = 0; k < K; ++k) {
+      const double g = peak_bin<MODEL == BLSQ_MODEL_LORENTZ_SUM, MAPPED>(p, 3 * k, lo, hi, wi, row, pm);
+      acc = (k == 0) ? g : acc + g;
+    }
+    return acc + poly_bin<MAPPED>(p, n - 1, 1, lo, hi, wi, row, pm);
+  }
+  // BLSQ_MODEL_GAUSS2D: t is [4][m], the pixel [lo, hi] x [vlo, vhi]
+  const double vlo = tb[2 * m + i], vhi = tb[3 * m + i];
+  const double a = p[0], u0 = p[1], v0 = p[2], s = p[3], c = p[4];
+  const double zul = (lo - u0) / s, zuh = (hi - u0) / s;
+  const double zvl = (vlo - v0) / s, zvh = (vhi - v0) / s;
+  const double c1 = s * SQRT_PI_2;
+  const double Iu = c1 * erf_diff(zul * SQRT_HALF, zuh * SQRT_HALF);
+  const double Iv = c1 * erf_diff(zvl * SQRT_HALF, zvh * SQRT_HALF);
+  const double da = Iu * Iv;
+  const double ww = (hi - lo) * (vhi - vlo);
+  if (row) {
+    const double eul = exp(-0.5 * (zul * zul)), euh = exp(-0.5 * (zuh * zuh));
+    const double evl = exp(-0.5 * (zvl * zvl)), evh = exp(-0.5 * (zvh * zvh));
+    PUT(0, wi * da);
+    PUT(1, wi * ((a * (eul - euh)) * Iv));
+    PUT(2, wi * ((a * (evl - evh)) * Iu));
+    PUT(3, wi * (a * ((Iu / s - (zuh * euh - zul * eul)) * Iv + Iu * (Iv / s - (zvh * evh - zvl * evl)))));
+    PUT(4, wi * ww);
+  }
+  return a * da + c * ww;
+}
+
 // The terms of one row.  `row` is the lane's slice of the wave's LDS tile (nullptr: f only); returns the model value.
 template <int MODEL, bool MAPPED>
 __device__ __forceinline__ double model_row(int n, int m, const double* __restrict__ tb, int i,
@@ -220,9 +388,10 @@ __device__ __forceinline__ double model_row(int n, int m, const double* __restri
 #undef PUT
 
 // The row of a composite: the walk over the table.  c, fam, cnt and the offset o are wave-uniform.
-template <bool MAPPED>
-__device__ __forceinline__ double comp_row(const CompTable& tab, double t, const double* __restrict__ p, double wi,
-                                           double* row, const signed char* pm) {
+// BINNED: t is lo and hi the bin's upper edge; otherwise hi is not read.
+template <bool MAPPED, bool BINNED>
+__device__ __forceinline__ double comp_row(const CompTable& tab, double t, double hi, const double* __restrict__ p,
+                                           double wi, double* row, const signed char* pm) {
   double acc = 0.0;
   int o = 0;                                   // first parameter, and first column, of the component
   unsigned long long ent = tab.lo;
@@ -233,30 +402,35 @@ __device__ __forceinline__ double comp_row(const CompTable& tab, double t, const
     switch (fam) {
       case BLSQ_TERM_GAUSS:
         for (int k = 0; k < cnt; ++k, o += 3) {
-          const double g = peak_term<false, MAPPED>(p, o, t, wi, row, pm);
+          const double g = BINNED ? peak_bin<false, MAPPED>(p, o, t, hi, wi, row, pm)
+                                  : peak_term<false, MAPPED>(p, o, t, wi, row, pm);
           v = (k == 0) ? g : v + g;
         }
         break;
       case BLSQ_TERM_LORENTZ:
         for (int k = 0; k < cnt; ++k, o += 3) {
-          const double g = peak_term<true, MAPPED>(p, o, t, wi, row, pm);
+          const double g = BINNED ? peak_bin<true, MAPPED>(p, o, t, hi, wi, row, pm)
+                                  : peak_term<true, MAPPED>(p, o, t, wi, row, pm);
           v = (k == 0) ? g : v + g;
         }
         break;
       case BLSQ_TERM_PVOIGT:
         for (int k = 0; k < cnt; ++k, o += 4) {
-          const double g = pvoigt_term<MAPPED>(p, o, t, wi, row, pm);
+          const double g = BINNED ? pvoigt_bin<MAPPED>(p, o, t, hi, wi, row, pm)
+                                  : pvoigt_term<MAPPED>(p, o, t, wi, row, pm);
           v = (k == 0) ? g : v + g;
         }
         break;
       case BLSQ_TERM_EXP:
         for (int k = 0; k < cnt; ++k, o += 2) {
-          const double g = exp_term<MAPPED>(p, o, t, wi, row, pm);
+          const double g = BINNED ? exp_bin<MAPPED>(p, o, t, hi, wi, row, pm)
+                                  : exp_term<MAPPED>(p, o, t, wi, row, pm);
           v = (k == 0) ? g : v + g;
         }
         break;
       default:                                 // BLSQ_TERM_POLY (the host has checked the table)
-        v = poly_terms<MAPPED>(p, o, cnt, t, wi, row, pm);
+        v = BINNED ? poly_bin<MAPPED>(p, o, cnt, t, hi, wi, row, pm)
+                   : poly_terms<MAPPED>(p, o, cnt, t, wi, row, pm);
         o += cnt;
         break;
     }
@@ -293,7 +467,7 @@ __device__ __forceinline__ void poisson_rc(double mu, double y, double& r, doubl
   }
 }
 
-template <int MODEL, bool MAPPED, bool POISSON>
+template <int MODEL, bool MAPPED, bool POISSON, bool BINNED>
 __global__ __launch_bounds__(256) void model_eval_kernel(
     typename ModelArgsOf<MODEL == MODEL_COMPOSITE, MAPPED>::type A) {
   extern __shared__ double model_tiles[];
@@ -333,7 +507,10 @@ __global__ __launch_bounds__(256) void model_eval_kernel(
     const double wi = (!POISSON && A.w) ? A.w[b * A.w_stride + i] : 1.0;
     double* row = tile ? tile + lane * ld : nullptr;
     double v;
-    if constexpr (MODEL == MODEL_COMPOSITE) v = comp_row<MAPPED>(A.tab, tb[i], p, wi, row, map_pm(A));
+    if constexpr (MODEL == MODEL_COMPOSITE && BINNED)
+      v = comp_row<MAPPED, true>(A.tab, tb[i], tb[m + i], p, wi, row, map_pm(A));
+    else if constexpr (MODEL == MODEL_COMPOSITE) v = comp_row<MAPPED, false>(A.tab, tb[i], 0.0, p, wi, row, map_pm(A));
+    else if constexpr (BINNED) v = model_row_bin<MODEL, MAPPED>(n, m, tb, i, p, wi, row, map_pm(A));
     else v = model_row<MODEL, MAPPED>(n, m, tb, i, p, wi, row, map_pm(A));
     if constexpr (POISSON) {
       double r, c;
@@ -361,19 +538,26 @@ __global__ __launch_bounds__(256) void model_eval_kernel(
   }
 }
 
-// The launch of instance <MODEL, MAPPED, est == BLSQ_EST_POISSON>.
+// The launch of instance <MODEL, MAPPED, est == BLSQ_EST_POISSON, sampling == BLSQ_SAMPLE_BIN>.
 template <int MODEL, bool MAPPED, class Args>
-static void launch_model_est(int est, dim3 g, dim3 blk, size_t lds, hipStream_t s, Args& A) {
-  if (est == BLSQ_EST_POISSON) hipLaunchKernelGGL((model_eval_kernel<MODEL, MAPPED, true>), g, blk, lds, s, A);
-  else hipLaunchKernelGGL((model_eval_kernel<MODEL, MAPPED, false>), g, blk, lds, s, A);
+static void launch_model_est(int est, int sampling, dim3 g, dim3 blk, size_t lds, hipStream_t s, Args& A) {
+  if (sampling == BLSQ_SAMPLE_BIN) {
+    if (est == BLSQ_EST_POISSON) hipLaunchKernelGGL((model_eval_kernel<MODEL, MAPPED, true, true>), g, blk, lds, s, A);
+    else hipLaunchKernelGGL((model_eval_kernel<MODEL, MAPPED, false, true>), g, blk, lds, s, A);
+  } else if (est == BLSQ_EST_POISSON) {
+    hipLaunchKernelGGL((model_eval_kernel<MODEL, MAPPED, true, false>), g, blk, lds, s, A);
+  } else {
+    hipLaunchKernelGGL((model_eval_kernel<MODEL, MAPPED, false, false>), g, blk, lds, s, A);
+  }
 }
 
 // Waves per workgroup (4 / 2 / 1) whose LDS (wave_bytes each) fits the grant, and the launch of instance <.., MAPPED, ..>.
 // model == MODEL_COMPOSITE: the composite instance (A then carries the table).  The Poisson instances need y and take
-// no weights.
+// no weights; the bin-integrated ones read 2 coords rows of t.
 template <bool MAPPED, class Args>
-static hipError_t launch_model_instance(int model, int est, Args& A, size_t wave_bytes, hipStream_t s) {
+static hipError_t launch_model_instance(int model, int est, int sampling, Args& A, size_t wave_bytes, hipStream_t s) {
   if (est != BLSQ_EST_LSE && est != BLSQ_EST_POISSON) return hipErrorInvalidValue;
+  if (sampling != BLSQ_SAMPLE_POINT && sampling != BLSQ_SAMPLE_BIN) return hipErrorInvalidValue;
   if (est == BLSQ_EST_POISSON && (!A.y || A.w)) return hipErrorInvalidValue;
   int wpb = 4;
   while (wpb > 1 && wave_bytes * wpb > (size_t)MODEL_LDS_BYTES) wpb >>= 1;
@@ -384,13 +568,13 @@ static hipError_t launch_model_instance(int model, int est, Args& A, size_t wave
   const size_t lds = wave_bytes * wpb;
   if constexpr (std::is_same<Args, typename ModelArgsOf<true, MAPPED>::type>::value) {
     if (model != MODEL_COMPOSITE) return hipErrorInvalidValue;
-    launch_model_est<MODEL_COMPOSITE, MAPPED>(est, g, blk, lds, s, A);
+    launch_model_est<MODEL_COMPOSITE, MAPPED>(est, sampling, g, blk, lds, s, A);
   } else switch (model) {
-    case BLSQ_MODEL_POLY: launch_model_est<BLSQ_MODEL_POLY, MAPPED>(est, g, blk, lds, s, A); break;
-    case BLSQ_MODEL_EXP_SUM: launch_model_est<BLSQ_MODEL_EXP_SUM, MAPPED>(est, g, blk, lds, s, A); break;
-    case BLSQ_MODEL_GAUSS_SUM: launch_model_est<BLSQ_MODEL_GAUSS_SUM, MAPPED>(est, g, blk, lds, s, A); break;
-    case BLSQ_MODEL_LORENTZ_SUM: launch_model_est<BLSQ_MODEL_LORENTZ_SUM, MAPPED>(est, g, blk, lds, s, A); break;
-    case BLSQ_MODEL_GAUSS2D: launch_model_est<BLSQ_MODEL_GAUSS2D, MAPPED>(est, g, blk, lds, s, A); break;
+    case BLSQ_MODEL_POLY: launch_model_est<BLSQ_MODEL_POLY, MAPPED>(est, sampling, g, blk, lds, s, A); break;
+    case BLSQ_MODEL_EXP_SUM: launch_model_est<BLSQ_MODEL_EXP_SUM, MAPPED>(est, sampling, g, blk, lds, s, A); break;
+    case BLSQ_MODEL_GAUSS_SUM: launch_model_est<BLSQ_MODEL_GAUSS_SUM, MAPPED>(est, sampling, g, blk, lds, s, A); break;
+    case BLSQ_MODEL_LORENTZ_SUM: launch_model_est<BLSQ_MODEL_LORENTZ_SUM, MAPPED>(est, sampling, g, blk, lds, s, A); break;
+    case BLSQ_MODEL_GAUSS2D: launch_model_est<BLSQ_MODEL_GAUSS2D, MAPPED>(est, sampling, g, blk, lds, s, A); break;
     default: return hipErrorInvalidValue;
   }
   return hipGetLastError();
@@ -427,27 +611,27 @@ static size_t mapped_wave_bytes(int nf, bool want_J) {
 
 hipError_t launch_model_eval(int model, int B, int reps, int m, int n, const double* t, long t_stride, const double* y,
                              const double* w, long w_stride, const double* P, double* f, double* J, const int* mask,
-                             hipStream_t s, int est) {
+                             hipStream_t s, int est, int sampling) {
   ModelArgs A;
   fill_model_args(A, B, reps, m, n, t, t_stride, y, w, w_stride, P, f, J, mask);
   const size_t tile_bytes = J ? sizeof(double) * MODEL_ROWS * (size_t)(n | 1) : 0;
-  return launch_model_instance<false>(model, est, A, tile_bytes, s);
+  return launch_model_instance<false>(model, est, sampling, A, tile_bytes, s);
 }
 
 hipError_t launch_model_eval_map(int model, int B, int reps, int m, int n, int nf, const int* pmap, const double* t,
                                  long t_stride, const double* y, const double* w, long w_stride, const double* X,
                                  const double* Pfix, double* f, double* J, const int* mask, hipStream_t s,
-                                 int est) {
+                                 int est, int sampling) {
   ModelMapArgs A;
   fill_model_args(A, B, reps, m, n, t, t_stride, y, w, w_stride, X, f, J, mask);
   if (!fill_model_map(A, n, nf, pmap, Pfix)) return hipErrorInvalidValue;
-  return launch_model_instance<true>(model, est, A, mapped_wave_bytes(nf, J != nullptr), s);
+  return launch_model_instance<true>(model, est, sampling, A, mapped_wave_bytes(nf, J != nullptr), s);
 }
 
 hipError_t launch_model_eval_comp(int ncomp, const int* fam, const int* cnt, int B, int reps, int m, int n, int nf,
                                   const int* pmap, const double* t, long t_stride, const double* y, const double* w,
                                   long w_stride, const double* X, const double* Pfix, double* f, double* J,
-                                  const int* mask, hipStream_t s, int est) {
+                                  const int* mask, hipStream_t s, int est, int sampling) {
   if (ncomp < 1 || ncomp > BLSQ_MODEL_MAX_COMP || n < 1 || n > MODEL_ROWS) return hipErrorInvalidValue;
   static const int per_term[BLSQ_TERM_POLY + 1] = {3, 3, 4, 2, 1};      // in the order of BLSQ_TERM_*
   CompTable tab = {};
@@ -464,13 +648,13 @@ hipError_t launch_model_eval_comp(int ncomp, const int* fam, const int* cnt, int
     fill_model_args(A, B, reps, m, n, t, t_stride, y, w, w_stride, X, f, J, mask);
     A.tab = tab;
     const size_t tile_bytes = J ? sizeof(double) * MODEL_ROWS * (size_t)(n | 1) : 0;
-    return launch_model_instance<false>(MODEL_COMPOSITE, est, A, tile_bytes, s);
+    return launch_model_instance<false>(MODEL_COMPOSITE, est, sampling, A, tile_bytes, s);
   }
   CompArgs<ModelMapArgs> A;
   fill_model_args(A, B, reps, m, n, t, t_stride, y, w, w_stride, X, f, J, mask);
   if (!fill_model_map(A, n, nf, pmap, Pfix)) return hipErrorInvalidValue;
   A.tab = tab;
-  return launch_model_instance<true>(MODEL_COMPOSITE, est, A, mapped_wave_bytes(nf, J != nullptr), s);
+  return launch_model_instance<true>(MODEL_COMPOSITE, est, sampling, A, mapped_wave_bytes(nf, J != nullptr), s);
 }
 
 }  // namespace blsq

@@ -490,6 +490,28 @@ int blsq_model_eval_est_dev(blsq_ctx* ctx, int est, int model, int ncomp, const 
                             const double* dy, const double* dw, long w_stride, const double* dX, const double* dPfix,
                             double* df, double* dJ, const int32_t* dmask);
 
+/* The sampling of a model: what the value of row i is.  Append only.
+ *   POINT  the model at the point t[b][.., i]: the entries above.
+ *   BIN    the integral of the model over the bin [lo_i, hi_i] (the expected content of a histogram channel for a model
+ *          read as a density); J holds the integrals of the point-sampled columns, a constant c contributes
+ *          c (hi - lo).  dt then holds the edges as rows: [2][m] = lo, hi per problem (coords 1), and for GAUSS2D
+ *          [4][m] = ulo, uhi, vlo, vhi, the pixel [ulo, uhi] x [vlo, vhi]; t_stride is 0 or 2 * coords * m.  Closed
+ *          forms per term (erf by erfc of the magnitudes where both edges lie in one tail, atan2, expm1 with a series
+ *          through r = 0, powers: DESIGN.md 7n; the numpy definition is bounded_lsq.models.binned).  The edges are not
+ *          checked on the device: lo < hi and finite is the caller's to see to. */
+enum { BLSQ_SAMPLE_POINT = 0, BLSQ_SAMPLE_BIN };
+/* blsq_model_eval_est_dev with the sampling: one entry for every model instance, estimator and sampling.  With
+ * BLSQ_SAMPLE_POINT the outputs are those of blsq_model_eval_est_dev, bit for bit; with BLSQ_SAMPLE_BIN dt and
+ * t_stride are as described above and everything else is unchanged (estimator, parameter map, weights, reps, mask).
+ * A negative return is the index of the bad argument (ctx = 1, est = 2, sampling = 3, model = 4, ncomp = 5, fam = 6,
+ * cnt = 7, B = 8, reps, m, n = 11, nf = 12, pmap = 13, t = 14, t_stride = 15, y = 16, w = 17, w_stride, X = 19,
+ * Pfix = 20, f = 21, J = 22, mask), and for the contents of pmap -24 (an entry outside -1 .. nf - 1) and -25 (a k < nf
+ * that no entry names); with BLSQ_EST_POISSON dy == NULL is -16 and dw != NULL is -17.  Nothing is launched then. */
+int blsq_model_eval_bin_dev(blsq_ctx* ctx, int est, int sampling, int model, int ncomp, const int32_t* fam,
+                            const int32_t* cnt, int B, int reps, int m, int n, int nf, const int32_t* pmap,
+                            const double* dt, long t_stride, const double* dy, const double* dw, long w_stride,
+                            const double* dX, const double* dPfix, double* df, double* dJ, const int32_t* dmask);
+
 /* ---- parameter covariance from the final Jacobian --------------------------------------------------------------
  * The reference documents `x_covariance` as the inverse of J^T J at the solution (least_squares.py:248-252) and fills
  * it only through its MINPACK bridge (method='lm').  Here, per problem, from a Householder triangle R of J (the TSQR

@@ -18,8 +18,13 @@ figure is the median of the rounds' means, and `*_all` lists every round.
 background of 12), drawn from the Poisson law, sigma None; the named route runs the Poisson kernel instances, the callable
 route the numpy wrappers.  Without it nothing here changes.
 
+``--binned`` fits histograms instead: `xdata` becomes the m + 1 edges of m contiguous bins over [-2, 2], the
+amplitudes and the offset are divided by the bin width so that a bin holds what a point held, and the data are the bin
+integrals; the named route runs the bin-integrated kernel instances (blsq_model_eval_bin_dev), the callable route the
+numpy functions of ``models.binned``.  It combines with every other switch.  Without it nothing here changes.
+
 usage: python tools/bench_models.py [--B 4096] [--m 64] [--repeat 5] [--peaks 1] [--fixed 1,4] [--tied 5:2] [--kernel]
-                                    [--launches 50] [--rounds 1] [--estimator lse]
+                                    [--launches 50] [--rounds 1] [--estimator lse] [--binned]
 """
 import argparse
 import json
@@ -40,28 +45,32 @@ PEAKS = {1: [1.5, 0.2, 0.6, 0.3], 2: [1.5, -0.8, 0.4, 1.0, 0.7, 0.5, 0.2]}
 COUNTS = 40.0                                  # --estimator poisson: amplitudes and offset in counts
 
 
-def problems(B, m, seed=0, peaks=1, fixed=(), tied=None, poisson=False):
+def problems(B, m, seed=0, peaks=1, fixed=(), tied=None, poisson=False, binned=False):
     """The truth satisfies the ties and p0 sits at the truth in the fixed columns."""
     rng = np.random.default_rng(seed)
     base = np.array(PEAKS[peaks])
     if poisson:
         base[0:-1:3] *= COUNTS
         base[-1] *= COUNTS
+    if binned:
+        base[0:-1:3] *= m / 4.0
+        base[-1] *= m / 4.0
     truth = base * (1 + 0.05 * rng.uniform(-1, 1, (B, base.size)))
     for j, i in (tied or {}).items():
         truth[:, j] = truth[:, i]
-    x = np.linspace(-2.0, 2.0, m)
+    x = np.linspace(-2.0, 2.0, m + 1 if binned else m)
+    M = models.binned("gauss_sum") if binned else models.get("gauss_sum")
     if poisson:
-        Y = rng.poisson(models.get("gauss_sum").f(x, truth)).astype(float)
+        Y = rng.poisson(M.f(x, truth)).astype(float)
     else:
-        Y = models.get("gauss_sum").f(x, truth) + 0.01 * rng.standard_normal((B, m))
+        Y = M.f(x, truth) + 0.01 * rng.standard_normal((B, m))
     P0 = truth * (1 + 0.1 * rng.choice([-1.0, 1.0], truth.shape))
     P0[:, list(fixed)] = truth[:, list(fixed)]
     half = 0.4 * np.abs(truth) + 0.2
     return x, Y, P0, (truth - half, truth + half)
 
 
-def kernel_times(ctx, x, Y, P0, pm, launches, rounds=1, estimator="lse"):
+def kernel_times(ctx, x, Y, P0, pm, launches, rounds=1, estimator="lse", binned=False):
     """us per launch of f and of J ('model_eval' slot, HIP events) for the unmapped entry at P0 and, with a map, the
     mapped entry at reduce_x(P0); 'composite*': the same for 'gauss*K+poly*1' through the composite entry."""
     B, m = Y.shape
@@ -73,7 +82,7 @@ def kernel_times(ctx, x, Y, P0, pm, launches, rounds=1, estimator="lse"):
         cases += [("mapped", "gauss_sum", pm), ("composite_mapped", spec, pm)]
     for key, name, mp in cases:
         dm = models.DeviceModel(ctx, name, B, m, n, x, Y, 0.01 if estimator == "lse" else None, param_map=mp,
-                                Pfix=None if mp is None else P0, estimator=estimator)
+                                Pfix=None if mp is None else P0, estimator=estimator, **({"binned": True} if binned else {}))
         X = P0 if mp is None else np.ascontiguousarray(mp.reduce_x(P0))
         d_x, d_f, d_J = ctx.to_device(X), ctx.malloc(8 * B * m), ctx.malloc(8 * B * m * dm.n)
         for what, call in (("f", lambda: dm.fun_dev(d_x, d_f, 1)), ("J", lambda: dm.jac_dev(d_x, d_J))):
@@ -110,32 +119,35 @@ def main():
     ap.add_argument("--launches", type=int, default=50)
     ap.add_argument("--rounds", type=int, default=1, help="with --kernel: timed blocks of --launches launches each")
     ap.add_argument("--estimator", default="lse", choices=models.ESTIMATORS)
+    ap.add_argument("--binned", action="store_true", help="fit bin integrals: the bin-integrated instances")
     a = ap.parse_args()
     fixed = [int(v) for v in a.fixed.split(",") if v]
     tied = {int(p.split(":")[0]): int(p.split(":")[1]) for p in a.tied.split(",") if p}
     poisson = a.estimator == "poisson"
-    x, Y, P0, bounds = problems(a.B, a.m, peaks=a.peaks, fixed=fixed, tied=tied, poisson=poisson)
+    x, Y, P0, bounds = problems(a.B, a.m, peaks=a.peaks, fixed=fixed, tied=tied, poisson=poisson, binned=a.binned)
     n = P0.shape[1]
-    M = models.get("gauss_sum")
+    M = models.binned("gauss_sum") if a.binned else models.get("gauss_sum")
     pm = ParamMap(n, fixed, tied) if (fixed or tied) else None
     ctx = _abi.Context(0)
     if a.kernel:
         res = {"model": "gauss_sum", "B": a.B, "m": a.m, "n": n, "nf": n if pm is None else pm.nf, "fixed": fixed,
-               "tied": a.tied, "launches": a.launches, "rounds": a.rounds, "estimator": a.estimator}
-        res.update(kernel_times(ctx, x, Y, P0, pm, a.launches, a.rounds, a.estimator))
+               "tied": a.tied, "launches": a.launches, "rounds": a.rounds, "estimator": a.estimator,
+               "binned": a.binned}
+        res.update(kernel_times(ctx, x, Y, P0, pm, a.launches, a.rounds, a.estimator, a.binned))
         ctx.close()
         print(json.dumps(res))
         return
     kw = dict(sigma=0.01, bounds=bounds, driver="device", ctx=ctx, ftol=1e-10, xtol=1e-10, gtol=1e-10)
     if poisson:
         kw.update(sigma=None, estimator="poisson")
+    named_kw = dict(kw, binned=True) if a.binned else kw
     if pm is None:
-        routes = {"named": lambda: curve_fit_batch("gauss_sum", x, Y, P0, **kw),
+        routes = {"named": lambda: curve_fit_batch("gauss_sum", x, Y, P0, **named_kw),
                   "callable": lambda: curve_fit_batch(M.f, x, Y, P0, jac=M.jac, **kw)}
     else:
         kw_red = dict(kw, bounds=pm.reduce_bounds(*bounds))
         f_red, jac_red, X0 = pm.wrap_f(M.f, P0), pm.wrap_jac(M.jac, P0), pm.reduce_x(P0)
-        routes = {"named": lambda: curve_fit_batch("gauss_sum", x, Y, P0, fixed=fixed, tied=tied, **kw),
+        routes = {"named": lambda: curve_fit_batch("gauss_sum", x, Y, P0, fixed=fixed, tied=tied, **named_kw),
                   "callable": lambda: curve_fit_batch(f_red, x, Y, X0, jac=jac_red, **kw_red)}
     times = {k: [] for k in routes}
     out = {}
@@ -157,7 +169,7 @@ def main():
     both = np.array([ra.success and rb.success for ra, rb in zip(out["named"][2], out["callable"][2])])
     free = (lambda P: P) if pm is None else pm.reduce_x
     res = {"model": "gauss_sum", "B": a.B, "m": a.m, "n": n, "nf": n if pm is None else pm.nf, "driver": "device",
-           "estimator": a.estimator, "named_s": round(float(np.median(times["named"])), 4),
+           "estimator": a.estimator, "binned": a.binned, "named_s": round(float(np.median(times["named"])), 4),
            "callable_s": round(float(np.median(times["callable"])), 4),
            "named_all_s": [round(t, 4) for t in times["named"]],
            "callable_all_s": [round(t, 4) for t in times["callable"]],
