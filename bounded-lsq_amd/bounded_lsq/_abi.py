@@ -109,6 +109,7 @@ SIGNATURES = {
     "blsq_cov_pinv_dev": (C.c_int, [vp] + [vp] * 8),
     "blsq_cov_pinv": (C.c_int, [vp] + [vp] * 8),
     "blsq_outer_covariance_pinv": (C.c_int, [vp, C.c_int, C.c_int, vp, vp, vp, vp, vp]),
+    "blsq_outer_covariance_pinv_nobs": (C.c_int, [vp, C.c_int, vp, vp, vp, vp, vp, vp]),
     "blsq_cov_rows_dev": (C.c_int, [vp, C.c_int, vp, vp, vp]),
     "blsq_cov_rows": (C.c_int, [vp, C.c_int, vp, vp, vp]),
     "blsq_outer_leverage": (C.c_int, [vp, vp, vp]),
@@ -124,6 +125,8 @@ SIGNATURES = {
                                 + [c_int32_p, vp, C.c_long, vp, vp, C.c_long] + [vp] * 5),
     "blsq_model_eval_bin_dev": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, C.c_int, c_int32_p, c_int32_p] + [C.c_int] * 5
                                 + [c_int32_p, vp, C.c_long, vp, vp, C.c_long] + [vp] * 5),
+    "blsq_model_eval_nan_dev": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, c_int32_p, c_int32_p]
+                                + [C.c_int] * 5 + [c_int32_p, vp, C.c_long, vp, vp, C.c_long] + [vp] * 5),
 }
 
 _lib = None

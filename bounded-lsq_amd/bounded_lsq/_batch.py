@@ -42,7 +42,8 @@ def _bounds_2d(bounds, B, n):
 def least_squares_batch(fun, x0, jac, bounds=(-np.inf, np.inf), method='trf',
                         ftol=EPS ** 0.5, xtol=EPS ** 0.5, gtol=EPS ** 0.5, max_nfev=None,
                         scaling=1.0, diff_step=None, args=(), kwargs=None, ctx=None, driver='host',
-                        loss='linear', f_scale=1.0, covariance=False, _variance_scale=False, leverage=False):
+                        loss='linear', f_scale=1.0, covariance=False, _variance_scale=False, leverage=False,
+                        _nobs=None):
     """Solve B bound-constrained least-squares problems of identical shape.
 
     fun : callable, ``fun(X) -> (B, m)`` residuals for ``X`` (B, n) — or a ``models.DeviceFit`` (a built-in model with
@@ -61,7 +62,9 @@ def least_squares_batch(fun, x0, jac, bounds=(-np.inf, np.inf), method='trf',
              problem from ONE batched call on the final Jacobians (driver='device': on the resident ones, only
              B n^2 + 2 B numbers leave the GPU).  'pinv' / 'free-pinv': the pseudo-inverse covariance of any rank
              (``x_covariance_rank``; ``x_covariance_rcond`` is then s_min / s_max, not the 1-norm figure);
-             ``_variance_scale`` (``curve_fit_batch``'s): times obj_value / (m - n), applied on the GPU.
+             ``_variance_scale`` (``curve_fit_batch``'s): times obj_value / (m - n), applied on the GPU; with
+             ``_nobs`` (B,) (its ``nan_policy='omit'``: the points each problem kept) times obj_value / (nobs[b] - n),
+             inf where nobs[b] <= n.
     leverage : True (needs a covariance mode) adds ``leverage`` (m,) to every result, as ``least_squares``: from the
              same plan call (driver='device': through the resident J, B m more numbers leave the GPU).
     Returns a list of B ``OptimizeResult`` (fields as ``least_squares``).
@@ -152,7 +155,7 @@ def least_squares_batch(fun, x0, jac, bounds=(-np.inf, np.inf), method='trf',
         try:
             return _device_batch(fun, jac, X0, lb, ub, trf, use_jac, scaling, ftol, xtol, gtol,
                                  max_nfev, ctx, loss if robust else None, fsc, covariance, _variance_scale, leverage,
-                                 diff_step=diff_step)
+                                 diff_step=diff_step, nobs=_nobs)
         finally:
             _release_fd()
 
@@ -331,7 +334,7 @@ def least_squares_batch(fun, x0, jac, bounds=(-np.inf, np.inf), method='trf',
             results.append(r)
         if covariance:
             _attach_covariance(results, covariance, ctx=solver.ctx, variance_scale=_variance_scale and m > n,
-                               leverage=leverage)
+                               leverage=leverage, nobs=_nobs)
         return results
     finally:
         solver.close()
@@ -369,7 +372,8 @@ def _host_callbacks(fun, jac, xs, B, n):
 
 
 def _device_batch(fun, jac, X0, lb, ub, trf, use_jac, scaling, ftol, xtol, gtol, max_nfev, ctx,
-                  loss=None, f_scale=None, covariance=False, variance_scale=False, leverage=False, diff_step=None):
+                  loss=None, f_scale=None, covariance=False, variance_scale=False, leverage=False, diff_step=None,
+                  nobs=None):
     """`least_squares_batch` on the device-resident outer driver (same results, same counts).  `loss`: a
     loss name other than 'linear' (None: sum f^2), applied on the device (blsq_outer_set_loss).
     Host callbacks (`fun`, `jac` numpy callables) go through ``run_host``; device callbacks (`fun` with
@@ -400,8 +404,11 @@ def _device_batch(fun, jac, X0, lb, ub, trf, use_jac, scaling, ftol, xtol, gtol,
             drv.set_loss(loss, f_scale)
         drv.start(X0, xs, lb, ub, scale, use_jac, ftol, xtol, gtol, max_nfev)
         R = run(drv)
-        cov_out = drv.covariance(free_only=_is_free(covariance), pinv=_is_pinv(covariance),
-                                 variance_scale=variance_scale and m > n) if covariance else None
+        if covariance and nobs is not None and variance_scale and m > n and _is_pinv(covariance):
+            cov_out = drv.covariance_nobs(nobs, free_only=_is_free(covariance))      # per-problem degrees of freedom
+        else:
+            cov_out = drv.covariance(free_only=_is_free(covariance), pinv=_is_pinv(covariance),
+                                     variance_scale=variance_scale and m > n) if covariance else None
         lev_out = drv.leverage() if leverage else None
         Jfin = drv._down(drv.d_J, (B, m, n))
     finally:

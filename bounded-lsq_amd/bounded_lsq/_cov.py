@@ -160,9 +160,16 @@ def fill_results(results, mode, cov, *rest):
     return results
 
 
-def variance_scales(results):
-    """obj_value / (m - n) of each result (curve_fit: "s_sq = cost / (ysize - p0.size)"); needs m > n."""
-    return np.array([r.obj_value / (r.jac.shape[0] - r.jac.shape[1]) for r in results])
+def variance_scales(results, nobs=None):
+    """obj_value / (m - n) of each result (curve_fit: "s_sq = cost / (ysize - p0.size)"); needs m > n.  nobs (B,): the
+    points each problem kept (``nan_policy='omit'``): obj_value / (nobs[b] - n), and inf where nobs[b] <= n."""
+    if nobs is None:
+        return np.array([r.obj_value / (r.jac.shape[0] - r.jac.shape[1]) for r in results])
+    nobs = np.asarray(nobs)
+    if nobs.shape != (len(results),):
+        raise ValueError("`nobs` must have shape (B,).")
+    dof = [int(k) - r.jac.shape[1] for k, r in zip(nobs, results)]
+    return np.array([r.obj_value / d if d > 0 else np.inf for d, r in zip(dof, results)])
 
 
 def fill_leverage(results, h):
@@ -181,13 +188,14 @@ def check_leverage(leverage, covariance):
     return bool(leverage)
 
 
-def attach(results, mode, ctx=None, variance_scale=False, leverage=False):
+def attach(results, mode, ctx=None, variance_scale=False, leverage=False, nobs=None):
     """One batched covariance call on the stacked final Jacobians of `results` (`mode`: as check_covariance returns
     it).  variance_scale (pinv modes): multiply problem b by obj_value / (m - n) on the GPU.  leverage: the leverages
-    of the rows of each Jacobian from the same plan call (blsq_cov_rows on the staged J; never scaled)."""
+    of the rows of each Jacobian from the same plan call (blsq_cov_rows on the staged J; never scaled).  nobs: the
+    points each problem kept, for the variance factor (``variance_scales``)."""
     J = np.stack([r.jac for r in results])
     act = np.stack([np.asarray(r.active_mask) for r in results]) if is_free(mode) else None
-    scale = variance_scales(results) if (variance_scale and is_pinv(mode)) else None
+    scale = variance_scales(results, nobs) if (variance_scale and is_pinv(mode)) else None
     Jb, act, sc, _ = checked_inputs(J, act, is_pinv(mode), scale)
     after = (lambda c, h: plan_rows(c, h, Jb.shape[0], Jb.shape[1])) if leverage else None
     out, lev = plan_call(Jb, act, sc, is_pinv(mode), ctx, after)

@@ -87,12 +87,15 @@ def _wrap_jac(jac, xdata, transform):
     return lambda params: solve_triangular(transform, np.asarray(jac(xdata, *params)), lower=True)
 
 
-def _check_poisson(estimator, sigma, ydata):
-    """True for estimator='poisson' (after its checks of `sigma` and `ydata`), False for 'lse'; ValueError otherwise."""
+def _check_poisson(estimator, sigma, ydata, omitted=None):
+    """True for estimator='poisson' (after its checks of `sigma` and `ydata`), False for 'lse'; ValueError otherwise.
+    omitted: the mask of the points ``nan_policy='omit'`` leaves out; the counts are checked at the kept points only."""
     if _models.check_estimator(estimator) == 'lse':
         return False
     if sigma is not None:
         raise ValueError("`sigma` must be None with estimator='poisson': the counts carry their own variance.")
+    if omitted is not None:
+        ydata = ydata[~omitted]
     if not np.all(np.isfinite(ydata)):
         raise ValueError("`ydata` must be finite with estimator='poisson'.")
     if np.any(ydata < 0):
@@ -108,9 +111,22 @@ def _param_map(n, fixed, tied):
     return None if pm.identity else pm
 
 
-def curve_fit(f, xdata, ydata, p0=None, sigma=None, absolute_sigma=False, check_finite=True,
+_NAN_POLICIES = [None, 'raise', 'omit']                  # scipy's list for curve_fit
+
+
+def _contains_nan(a, nan_policy):
+    """scipy's _contains_nan for a float array and curve_fit's policies: its exceptions, in its words."""
+    if nan_policy not in _NAN_POLICIES:
+        raise ValueError(f"nan_policy must be one of {set(_NAN_POLICIES)}.")
+    contains_nan = bool(a.size) and bool(np.isnan(np.max(a)))
+    if contains_nan and nan_policy == 'raise':
+        raise ValueError("The input contains nan values")
+    return contains_nan
+
+
+def curve_fit(f, xdata, ydata, p0=None, sigma=None, absolute_sigma=False, check_finite=None,
               bounds=(-np.inf, np.inf), method=None, jac=None, full_output=False, fixed=None, tied=None,
-              estimator='lse', **kwargs):
+              estimator='lse', nan_policy=None, **kwargs):
     """Fit ``ydata = f(xdata, *p) + eps`` by non-linear least squares; returns ``(popt, pcov)``.
 
     Parameters, exceptions, warnings and results are scipy.optimize.curve_fit's (1.15.3):
@@ -127,10 +143,15 @@ def curve_fit(f, xdata, ydata, p0=None, sigma=None, absolute_sigma=False, check_
     ``full_output=True`` returns ``(popt, pcov, infodict, mesg, ier)`` with infodict keys ``nfev`` and ``fvec``, and
     ``leverage`` (``least_squares``'s, of the transformed Jacobian) when ``leverage=True`` is among the keywords.
 
-    Two deliberate differences from scipy:
-      * ``method=None`` always means 'trf' (scipy chooses 'lm' for an unbounded problem); ``method='lm'`` raises
-        ``NotImplementedError`` here as in ``least_squares``: there is no MINPACK bridge on this step path;
-      * ``nan_policy`` is not taken.
+    One deliberate difference from scipy: ``method=None`` always means 'trf' (scipy chooses 'lm' for an unbounded
+    problem); ``method='lm'`` raises ``NotImplementedError`` here as in ``least_squares``: there is no MINPACK bridge on
+    this step path.
+
+    check_finite, nan_policy : scipy's pair.  `check_finite` None (the default) means True unless a `nan_policy` is
+    given.  `nan_policy` None leaves NaN to `check_finite`; 'raise' raises ``ValueError("The input contains nan
+    values")`` for a NaN in `xdata` or `ydata`; 'omit' drops the points where either is NaN before the fit, and the
+    matching entries of a 1-D `sigma` or rows and columns of a 2-D one (one problem: the points are dropped on the host,
+    ``curve_fit_batch`` omits them inside the kernel); 'propagate' is not supported, as in scipy.
 
     fixed, tied : hold parameters at their `p0` (a boolean mask (n,) or indices) and make parameter j a copy of
     parameter i (``{j: i}``), as ``curve_fit_batch``; `p0` is then required (ValueError).  `f` and a callable `jac`
@@ -151,7 +172,7 @@ def curve_fit(f, xdata, ydata, p0=None, sigma=None, absolute_sigma=False, check_
         pm = _param_map(np.atleast_1d(p0).size, fixed, tied)
     if pm is not None:
         return _curve_fit_mapped(pm, f, xdata, ydata, p0, sigma, absolute_sigma, check_finite, bounds, method, jac,
-                                 full_output, estimator, kwargs)
+                                 full_output, estimator, kwargs, nan_policy)
     if p0 is None:
         args = getfullargspec(f).args
         if len(args) < 2:
@@ -174,6 +195,9 @@ def curve_fit(f, xdata, ydata, p0=None, sigma=None, absolute_sigma=False, check_
             "method='lm' is a MINPACK bridge in the reference and is outside "
             "the MI355X step path; use 'trf' or 'dogbox'.")
 
+    if check_finite is None:
+        check_finite = True if nan_policy is None else False
+
     # optimisation may produce garbage for float32 inputs: cast to float64
     ydata = np.asarray_chkfinite(ydata, float) if check_finite else np.asarray(ydata, float)
     if isinstance(xdata, (list, tuple, np.ndarray)):
@@ -181,6 +205,26 @@ def curve_fit(f, xdata, ydata, p0=None, sigma=None, absolute_sigma=False, check_
         xdata = np.asarray_chkfinite(xdata, float) if check_finite else np.asarray(xdata, float)
     if ydata.size == 0:
         raise ValueError("`ydata` must not be empty!")
+
+    # nan handling is needed only if check_finite is False: otherwise the data hold none
+    if not check_finite and nan_policy is not None:
+        if nan_policy == "propagate":
+            raise ValueError("`nan_policy='propagate'` is not supported by this function.")
+        x_contains_nan = _contains_nan(np.asarray(xdata, float), nan_policy)
+        y_contains_nan = _contains_nan(ydata, nan_policy)
+        if (x_contains_nan or y_contains_nan) and nan_policy == 'omit':
+            has_nan = np.isnan(xdata)
+            has_nan = has_nan.any(axis=tuple(range(has_nan.ndim - 1)))
+            has_nan |= np.isnan(ydata)
+            xdata = xdata[..., ~has_nan]
+            ydata = ydata[~has_nan]
+            if sigma is not None:                # the corresponding entries of sigma
+                sigma = np.asarray(sigma)
+                if sigma.ndim == 1:
+                    sigma = sigma[~has_nan]
+                elif sigma.ndim == 2:
+                    sigma = sigma[~has_nan, :]
+                    sigma = sigma[:, ~has_nan]
 
     if _check_poisson(estimator, sigma, ydata):
         # the deviance residual of the counts and its Jacobian c * J (models.poisson_transform)
@@ -244,7 +288,7 @@ def curve_fit(f, xdata, ydata, p0=None, sigma=None, absolute_sigma=False, check_
 
 
 def _curve_fit_mapped(pm, f, xdata, ydata, p0, sigma, absolute_sigma, check_finite, bounds, method, jac, full_output,
-                      estimator, kwargs):
+                      estimator, kwargs, nan_policy=None):
     """``curve_fit`` over the nf variables of `pm`: the same function on wrapped callables, results expanded."""
     Pfix = np.array(np.atleast_1d(p0), dtype=float)
     if hasattr(bounds, 'lb') and hasattr(bounds, 'ub'):
@@ -262,12 +306,13 @@ def _curve_fit_mapped(pm, f, xdata, ydata, p0, sigma, absolute_sigma, check_fini
             return pm.reduce_jac(np.asarray(jac(x, *pm.expand_x(np.asarray(xv, dtype=float), Pfix))))
     out = curve_fit(fr, xdata, ydata, p0=pm.reduce_x(Pfix), sigma=sigma, absolute_sigma=absolute_sigma,
                     check_finite=check_finite, bounds=(lbr, ubr), method=method, jac=jr, full_output=full_output,
-                    estimator=estimator, **kwargs)
+                    estimator=estimator, nan_policy=nan_policy, **kwargs)
     return (pm.expand_x(out[0], Pfix), pm.expand_cov(out[1])) + tuple(out[2:])
 
 
 def curve_fit_batch(f, xdata, ydata, p0, sigma=None, absolute_sigma=False, bounds=(-np.inf, np.inf), method='trf',
-                    jac=None, driver='host', ctx=None, fixed=None, tied=None, estimator='lse', binned=False, **kwargs):
+                    jac=None, driver='host', ctx=None, fixed=None, tied=None, estimator='lse', binned=False,
+                    nan_policy=None, **kwargs):
     """``curve_fit`` for B data sets of one model, solved together by ``least_squares_batch``.
 
     f : ``f(xdata, P) -> (B, m)`` for parameters ``P`` of shape (B, n): vectorised over the batch — or the name of a
@@ -333,6 +378,21 @@ def curve_fit_batch(f, xdata, ydata, p0, sigma=None, absolute_sigma=False, bound
             ValueError naming the first such bin.  Everything else composes unchanged: ``estimator='poisson'`` (the
             estimator for histogram counts), `fixed` / `tied`, ``loss=``, `bounds`, `sigma`, ``leverage=`` and
             ``jac='2-point'`` / ``'3-point'``.
+    nan_policy : None (the default: nothing changes, a NaN passes through), 'raise' (a NaN in `ydata` is a ValueError)
+            or 'omit' (DESIGN.md 7o): point i of problem b is left out of the fit iff ``ydata[b, i]`` is NaN — a dead
+            channel, a blanked spike, the padding of a shorter scan (``models.pad_ragged``).  Its residual and its
+            Jacobian row are exactly 0, so it contributes nothing to the objective, the steps, the covariance or the
+            leverages (0 there); its `sigma` entry (shape (B, m)) and, for a callable or a point-sampled model, its
+            abscissa may hold anything.  ±inf is not missing data.  A named model with driver='device' omits the points
+            inside the model kernel, without evaluating them (blsq_model_eval_nan_dev); driver='host' and a callable
+            go through ``models.omit_residual`` / ``models.omit_jacobian``, the definition.  It composes with
+            everything above: ``binned=``, ``estimator='poisson'`` (whose checks of `ydata` then look at the kept
+            points), `fixed` / `tied`, ``loss=``, `sigma`, ``leverage=`` and every `jac` choice.  ``results[b]`` gains
+            ``nobs``, the number of points kept, and ``omitted``, the boolean mask (m,); the variance factor of
+            problem b is ``obj_value / (nobs[b] - nf)``, and a problem with ``nobs[b] <= nf`` gets ``pcov[b] = inf``
+            under the ``OptimizeWarning`` while its batch mates keep their results.  A problem without a single point
+            is a ValueError naming it; 'propagate' or any other string is a ValueError.  NaN in `xdata` of a binned
+            model is still rejected, and the rank tolerance of the pseudo-inverse keeps using the allocated m.
 
     Returns ``(popt (B, n), pcov (B, n, n), results)``, `results` the B ``OptimizeResult`` of the solve.  pcov[b] is
     ``curve_fit``'s for problem b alone: the pseudo-inverse covariance of its final Jacobian, times
@@ -353,7 +413,20 @@ def curve_fit_batch(f, xdata, ydata, p0, sigma=None, absolute_sigma=False, bound
     if P0.ndim != 2 or P0.shape[0] != B:
         raise ValueError("`p0` must have shape (B, n).")
     n = P0.shape[1]
-    poisson = _check_poisson(estimator, sigma, ydata)
+    omitted = nobs = None
+    if nan_policy == 'raise':
+        if np.isnan(ydata).any():
+            raise ValueError("The input contains nan values")
+    elif nan_policy == 'omit':
+        omitted = np.isnan(ydata)
+        nobs = _models.count_observed(ydata)
+        if not nobs.all():
+            raise ValueError("nan_policy='omit': problem %d has no point left, every entry of its `ydata` is NaN."
+                             % int(np.argmin(nobs != 0)))
+    elif nan_policy is not None:
+        raise ValueError("`nan_policy` must be None, 'raise' or 'omit', not %r%s." % (
+            nan_policy, " (a NaN passes through with None)" if nan_policy == 'propagate' else ""))
+    poisson = _check_poisson(estimator, sigma, ydata, omitted)
     pm = _param_map(n, fixed, tied)
     model = None
     if binned and not isinstance(f, (str, _models.CompositeModel)):
@@ -384,6 +457,8 @@ def curve_fit_batch(f, xdata, ydata, p0, sigma=None, absolute_sigma=False, bound
     if sigma is not None:
         sigma = np.asarray(sigma, float)
         if sigma.size == 1 or sigma.shape == (m,) or sigma.shape == (B, m):
+            if omitted is not None and sigma.shape == (B, m):
+                sigma = np.where(omitted, 1.0, sigma)            # never used at an omitted point
             transform = 1.0 / sigma
         elif sigma.ndim == 2:
             raise ValueError("a 2-D covariance `sigma` is not supported by `curve_fit_batch`.")
@@ -407,7 +482,8 @@ def curve_fit_batch(f, xdata, ydata, p0, sigma=None, absolute_sigma=False, bound
     if model is not None and driver == 'device':
         func = _models.DeviceFit(model.name, n, xdata, ydata, sigma, param_map=pm, Pfix=None if pm is None else P0,
                                  **({'estimator': estimator} if poisson else {}),
-                                 **({'binned': True} if binned else {}))
+                                 **({'binned': True} if binned else {}),
+                                 **({'nan_policy': 'omit'} if omitted is not None else {}))
     elif poisson:                                # (after the map: c multiplies the summed columns)
         if callable(jac):
             jac = _models.poisson_jacobian(f, jac, ydata)
@@ -430,6 +506,11 @@ def curve_fit_batch(f, xdata, ydata, p0, sigma=None, absolute_sigma=False, bound
             J = np.asarray(user_jac(xdata, P), float)
             return J if tj is None else tj * J
 
+    if omitted is not None and callable(func):   # outermost: after sigma, the Poisson transform and the map
+        func = _models.omit_residual(func, ydata)
+        if callable(jac):
+            jac = _models.omit_jacobian(jac, ydata)
+
     if 'args' in kwargs:
         raise ValueError("'args' is not a supported keyword argument.")
     if 'max_nfev' not in kwargs:
@@ -437,7 +518,11 @@ def curve_fit_batch(f, xdata, ydata, p0, sigma=None, absolute_sigma=False, bound
 
     scale_on_gpu = (not absolute_sigma) and m > nv
     results = least_squares_batch(func, x_start, jac, bounds=bounds, method=method, driver=driver, ctx=ctx,
-                                  covariance='pinv', _variance_scale=scale_on_gpu, **kwargs)
+                                  covariance='pinv', _variance_scale=scale_on_gpu,
+                                  **({'_nobs': nobs} if nobs is not None else {}), **kwargs)
+    if nobs is not None:
+        for b, r in enumerate(results):
+            r.nobs, r.omitted = int(nobs[b]), omitted[b].copy()
     if pm is not None:                           # the full-size fields of the results, expanded for the batch at once
         X_full = pm.expand_x(np.stack([r.x for r in results]), P0)
         masks = pm.expand_mask(np.stack([np.asarray(r.active_mask) for r in results]))
@@ -458,7 +543,8 @@ def curve_fit_batch(f, xdata, ydata, p0, sigma=None, absolute_sigma=False, bound
         if not r.success:
             continue
         C = r.x_covariance
-        bad_cov = C is None or np.isnan(C).any() or (not absolute_sigma and m <= nv)
+        bad_cov = (C is None or np.isnan(C).any()
+                   or (not absolute_sigma and (m if nobs is None else nobs[b]) <= nv))
         popt[b] = r.x
         if bad_cov:
             pcov[b] = np.inf

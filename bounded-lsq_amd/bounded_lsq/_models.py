@@ -49,6 +49,13 @@ histogram channel for a model read as a density, with the same parameters in the
 columns as its Jacobian.  Its numpy ``f`` / ``jac`` ARE the definition (closed forms: ``erf_diff`` switches to erfc where
 both edges lie in one tail, atan2 for the Lorentzian, ``psi_pair`` with a series through r = 0 for a decay); the BINNED
 kernel instances follow them operation by operation.
+
+Missing data (``nan_policy='omit'``; blsq_model_eval_nan_dev).  Point i of problem b is omitted iff
+``ydata[b, i]`` is NaN: its residual and its Jacobian row are exactly 0, and its `sigma` entry and abscissa are never
+looked at.  ``omit_residual`` / ``omit_jacobian`` ARE the definition (``np.where(isnan(ydata), 0, .)``, applied
+outermost) and the route of ``driver='host'`` and of callables; the OMIT kernel instances produce the same zeros without
+evaluating the row.  ``count_observed`` gives the points each problem keeps and ``pad_ragged`` turns data sets of
+unequal length into the NaN-padded batch the policy takes.
 """
 import re
 
@@ -62,13 +69,15 @@ LN2 = 0.6931471805599453
 
 ESTIMATORS = ('lse', 'poisson')              # BLSQ_EST_*
 SAMPLING = ('point', 'bin')                  # BLSQ_SAMPLE_*
+NAN_POLICIES = ('propagate', 'omit')         # BLSQ_NAN_*
 POISSON_U0 = 0.25                            # |u| below which phi(u) is its series
 POISSON_TERMS = 26                           # ... of this many terms
 
 __all__ = ['MODELS', 'NAMES', 'MAX_N', 'MAX_COMP', 'TERMS', 'get', 'compose', 'resolve', 'CompositeModel', 'evaluate',
            'DeviceModel', 'DeviceFit', 'ESTIMATORS', 'POISSON_U0', 'POISSON_TERMS', 'check_estimator',
            'poisson_transform', 'poisson_residual', 'poisson_jacobian', 'binned', 'bin_rows', 'BinnedModel', 'erf_diff',
-           'psi_pair', 'PSI_X0', 'PSI_TERMS', 'SAMPLING']
+           'psi_pair', 'PSI_X0', 'PSI_TERMS', 'SAMPLING', 'NAN_POLICIES', 'check_nan_policy', 'omit_residual',
+           'omit_jacobian', 'count_observed', 'pad_ragged']
 
 
 def _tp(xdata, P):
@@ -753,6 +762,74 @@ def poisson_jacobian(f, jac, ydata):
     return g
 
 
+# ---- missing data --------------------------------------------------------------------------------------------------
+def check_nan_policy(nan_policy):
+    """`nan_policy` if it is one of ``NAN_POLICIES``; ValueError otherwise."""
+    if not isinstance(nan_policy, str) or nan_policy not in NAN_POLICIES:
+        raise ValueError("unknown NaN policy %r: `nan_policy` must be 'propagate' or 'omit'." % (nan_policy,))
+    return nan_policy
+
+
+def omit_residual(fres, ydata):
+    """``fres(...) -> (B, m)`` -> the same function with exactly 0 wherever `ydata` (B, m) is NaN.  `fres` is the whole
+    residual (after `sigma`, the Poisson transform and a parameter map) with any signature; what it returns at an
+    omitted point is discarded, NaN included."""
+    omitted = np.isnan(np.asarray(ydata, dtype=float))
+
+    def g(*args):
+        with np.errstate(invalid='ignore'):
+            r = np.asarray(fres(*args))
+        return np.where(omitted, r.dtype.type(0), r)
+    return g
+
+
+def omit_jacobian(jres, ydata):
+    """``jres(...) -> (B, m, n)`` -> the same function with rows of exactly 0 wherever `ydata` (B, m) is NaN: the
+    Jacobian of ``omit_residual``."""
+    omitted = np.isnan(np.asarray(ydata, dtype=float))[:, :, np.newaxis]
+
+    def g(*args):
+        with np.errstate(invalid='ignore'):
+            J = np.asarray(jres(*args))
+        return np.where(omitted, J.dtype.type(0), J)
+    return g
+
+
+def count_observed(ydata):
+    """The number of points of each problem that ``nan_policy='omit'`` keeps: (B,) int32, the entries of `ydata` (B, m)
+    that are not NaN."""
+    y = np.asarray(ydata, dtype=float)
+    if y.ndim != 2:
+        raise ValueError("`ydata` must have shape (B, m).")
+    return np.sum(~np.isnan(y), axis=1).astype(np.int32)
+
+
+def pad_ragged(xs, ys):
+    """Data sets of unequal length as one batch for ``nan_policy='omit'``: `xs` and `ys` are sequences of B 1-D arrays,
+    pair b of one length m_b >= 1.  Returns ``(xdata (B, m), ydata (B, m))`` with m = max m_b: x is padded by repeating
+    its last value (a finite abscissa, never used) and y with NaN.  One coordinate and point sampling only; a pair of
+    different lengths, an empty pair or an array that is not 1-D is a ValueError."""
+    xs, ys = list(xs), list(ys)
+    if len(xs) != len(ys) or not xs:
+        raise ValueError("`xs` and `ys` must be sequences of the same, non-zero number of arrays.")
+    pairs = []
+    for b, (x, y) in enumerate(zip(xs, ys)):
+        x, y = np.asarray(x, dtype=float), np.asarray(y, dtype=float)
+        if x.ndim != 1 or y.ndim != 1 or x.size == 0:
+            raise ValueError("data set %d: x and y must be 1-D and not empty." % b)
+        if x.size != y.size:
+            raise ValueError("data set %d: x has %d points, y has %d." % (b, x.size, y.size))
+        pairs.append((x, y))
+    m = max(x.size for x, y in pairs)
+    xdata = np.empty((len(pairs), m))
+    ydata = np.full((len(pairs), m), np.nan)
+    for b, (x, y) in enumerate(pairs):
+        xdata[b, :x.size] = x
+        xdata[b, x.size:] = x[-1]
+        ydata[b, :y.size] = y
+    return xdata, ydata
+
+
 class DeviceModel:
     """Model `name` (a name, a composite spec or a ``CompositeModel``) with its data resident on the GPU: the device callbacks of ``OuterDriver.run_device``.
 
@@ -772,14 +849,21 @@ class DeviceModel:
 
     ``binned=True``: the bin-integrated form of the model (``binned``).  `xdata` holds the bin edges in
     any form ``BinnedModel.check_xdata`` takes (checked on the host: finite, lo < hi) and is uploaded as rows; every
-    kind of model and both estimators then go through blsq_model_eval_bin_dev."""
+    kind of model and both estimators then go through blsq_model_eval_bin_dev.
+
+    ``nan_policy='omit'`` (the default 'propagate' changes nothing): the points where `ydata` is NaN give
+    residuals and Jacobian rows of exactly 0, inside the kernel, through blsq_model_eval_nan_dev for every kind of
+    model; `ydata` is then required, and a `sigma` of shape (B, m) may hold anything at those points."""
 
     def __init__(self, ctx, name, B, m, n, xdata, ydata=None, sigma=None, param_map=None, Pfix=None, estimator='lse',
-                 binned=False):
+                 binned=False, nan_policy='propagate'):
         model = resolve(name)
         model.terms(n)
         self.binned = bool(binned)
         self.estimator = check_estimator(estimator)
+        self.nan_policy = check_nan_policy(nan_policy)
+        if nan_policy == 'omit' and ydata is None:
+            raise ValueError("nan_policy='omit' needs `ydata`: the missing points are its NaN.")
         if estimator == 'poisson':
             if ydata is None:
                 raise ValueError("estimator='poisson' needs `ydata`: the counts.")
@@ -801,6 +885,8 @@ class DeviceModel:
             sg = np.asarray(sigma, dtype=np.float64)
             if sg.shape == (self.B, self.m):
                 self.w_stride = self.m
+                if nan_policy == 'omit':                   # never read at an omitted point: anything may stand there
+                    sg = np.where(np.isnan(y), 1.0, sg)
             elif sg.size == 1:
                 sg = np.broadcast_to(sg.reshape(()), (self.m,))
             elif sg.shape != (self.m,):
@@ -838,6 +924,17 @@ class DeviceModel:
         return self.bounds_dev
 
     def _eval(self, x_ptr, reps, f_ptr, J_ptr, mask_ptr):
+        if self.nan_policy != 'propagate':                    # every kind of model, estimator and sampling: one entry
+            M, comp = self.model, isinstance(self.model, CompositeModel)
+            self.ctx.check(self.ctx.lib.blsq_model_eval_nan_dev(
+                self.ctx.h, ESTIMATORS.index(self.estimator), SAMPLING.index('bin' if self.binned else 'point'),
+                NAN_POLICIES.index(self.nan_policy), -1 if comp else M.id, len(M.components) if comp else 0,
+                M.fam_ids.ctypes.data_as(_abi.c_int32_p) if comp else None,
+                M.counts.ctypes.data_as(_abi.c_int32_p) if comp else None, self.B, int(reps), self.m, self.n_model,
+                self.n, None if self.param_map is None else self._pmap.ctypes.data_as(_abi.c_int32_p), self.d_t,
+                self.t_stride, self.d_y, self.d_w, self.w_stride, x_ptr, self.d_Pfix, f_ptr, J_ptr, mask_ptr),
+                "blsq_model_eval_nan_dev")
+            return
         if self.binned:                                       # every kind of model, both estimators: one entry
             M, comp = self.model, isinstance(self.model, CompositeModel)
             self.ctx.check(self.ctx.lib.blsq_model_eval_bin_dev(
@@ -902,13 +999,16 @@ class DeviceFit:
     """What ``least_squares_batch(fun=...)`` takes in place of a callable for a fit whose callbacks run on the device:
     a checked (model, data) pair that opens a ``DeviceModel`` on the driver's context.  Built by ``curve_fit_batch``.
     ``n`` is the number of solver variables (the width of x0): the model's n, or nf of `param_map`; ``n_model`` is the
-    model's number of parameters.  ``estimator='poisson'`` and ``binned=True``: as ``DeviceModel``."""
+    model's number of parameters.  ``estimator='poisson'``, ``binned=True`` and ``nan_policy='omit'``: as
+    ``DeviceModel``."""
 
-    def __init__(self, name, n, xdata, ydata, sigma=None, param_map=None, Pfix=None, estimator='lse', binned=False):
+    def __init__(self, name, n, xdata, ydata, sigma=None, param_map=None, Pfix=None, estimator='lse', binned=False,
+                 nan_policy='propagate'):
         self.model = resolve(name)
         self.model.terms(n)
         self.binned = bool(binned)
         self.estimator = check_estimator(estimator)
+        self.nan_policy = check_nan_policy(nan_policy)
         if estimator == 'poisson' and sigma is not None:
             raise ValueError("`sigma` must be None with estimator='poisson'.")
         self.ydata = np.ascontiguousarray(ydata, dtype=np.float64)
@@ -928,7 +1028,8 @@ class DeviceFit:
 
     def open_device(self, ctx, lb, ub):
         dm = DeviceModel(ctx, self.model.name, self.B, self.m, self.n_model, self.xdata, self.ydata, self.sigma,
-                         self.param_map, self.Pfix, self.estimator, **({'binned': True} if self.binned else {}))
+                         self.param_map, self.Pfix, self.estimator, **({'binned': True} if self.binned else {}),
+                         **({'nan_policy': self.nan_policy} if self.nan_policy != 'propagate' else {}))
         dm.set_bounds(lb, ub)
         return dm
 

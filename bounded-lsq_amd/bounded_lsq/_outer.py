@@ -137,6 +137,28 @@ class OuterDriver:
                                                           ptr(status)), "blsq_outer_covariance")
         return cov, rcond, status
 
+    def covariance_nobs(self, nobs, free_only=False):
+        """``covariance(pinv=True, variance_scale=True)`` with the degrees of freedom of every problem
+        (blsq_outer_covariance_pinv_nobs; ``nan_policy='omit'``): problem b is multiplied by
+        ``obj[b] / (nobs[b] - n)`` on the GPU, `nobs` (B,) integers in 0 .. m being the points each problem kept, and by
+        inf where ``nobs[b] <= n``.  A method of its own because the parameter list of ``covariance`` is fixed."""
+        B, n = self.B, self.n
+        counts = np.asarray(nobs)
+        if counts.shape != (B,) or not np.issubdtype(counts.dtype, np.integer):
+            raise ValueError("`nobs` must be integers of shape (B,).")
+        if np.any(counts < 0) or np.any(counts > self.m):
+            raise ValueError("`nobs` must lie in 0 .. m.")
+        counts = np.ascontiguousarray(counts, dtype=np.int32)
+        cov = np.empty((B, n, n))
+        rank = np.empty(B, dtype=np.int32)
+        rcond = np.empty(B)
+        kept = np.empty(B)
+        status = np.empty(B, dtype=np.int32)
+        self.ctx.check(self.ctx.lib.blsq_outer_covariance_pinv_nobs(
+            self.h, 1 if free_only else 0, ptr(counts), ptr(cov), ptr(rank), ptr(rcond), ptr(kept), ptr(status)),
+            "blsq_outer_covariance_pinv_nobs")
+        return cov, rank, rcond, kept, status
+
     def leverage(self):
         """Leverages of the rows of the resident J through the factor of the last ``covariance()`` call
         (blsq_outer_leverage): ``(h (B, m), status (B,))``, h NaN where that call's status is non-zero; never scaled.

@@ -587,6 +587,8 @@ hipError_t launch_cov_pinv_product(int B, int n, int NPAD, const double* X, cons
                                    hipStream_t st);
 // dscale[b] = obj[b] / (m - n)  (m > n)
 hipError_t launch_cov_variance(int B, int m, int n, const double* obj, double* dscale, hipStream_t st);
+// dscale[b] = obj[b] / (nobs[b] - n) where nobs[b] > n, +inf otherwise (7o: per-problem degrees of freedom)
+hipError_t launch_cov_variance_nobs(int B, int n, const double* obj, const int* nobs, double* dscale, hipStream_t st);
 // Row forms through the factor a covariance call has left (7i, blsq_cov_rows_dev): out[b][i] = dscale[b] sum_k t_ik^2 for
 // every row a_i of A [B][rows][n], read through perm (nullptr: all variables free).  pinv = 0: t_i = a_i[F] X over the
 // leading nfree x nfree triangle of X; pinv = 1: t_ik = w[k] (row k of X) . a_i[F] (w = nullptr: 1).  NaN where
@@ -616,23 +618,26 @@ hipError_t launch_fd_assemble(int B, int m, int n, int method, const double* x, 
 // and its Jacobian, which needs y and w == nullptr (hipErrorInvalidValue otherwise).
 // sampling (all three launches; blsq_model_eval_bin_dev, 7n): BLSQ_SAMPLE_POINT, or BLSQ_SAMPLE_BIN for the model
 // integrated over the bins t [2 coords][m] (rows lo, hi per coordinate; t_stride 0 or 2 * coords * m).
+// nan_policy (all three launches; blsq_model_eval_nan_dev, 7o): BLSQ_NAN_PROPAGATE, or BLSQ_NAN_OMIT for rows of zeros
+// where y is NaN, which needs y (hipErrorInvalidValue otherwise); t and w are not read there.
 hipError_t launch_model_eval(int model, int B, int reps, int m, int n, const double* t, long t_stride, const double* y,
                              const double* w, long w_stride, const double* P, double* f, double* J, const int* mask,
                              hipStream_t s, int est = 0 /* BLSQ_EST_LSE */,
-                             int sampling = 0 /* BLSQ_SAMPLE_POINT */);
+                             int sampling = 0 /* BLSQ_SAMPLE_POINT */, int nan_policy = 0 /* BLSQ_NAN_PROPAGATE */);
 // The same through a parameter map (blsq_model_eval_map_dev, 7k): X [B * reps][nf], pmap [n] on the host (-1 or a slot
 // < nf, every slot used: the caller has checked), Pfix [B][n] (read where pmap[j] == -1), J [B][m][nf].
 hipError_t launch_model_eval_map(int model, int B, int reps, int m, int n, int nf, const int* pmap, const double* t,
                                  long t_stride, const double* y, const double* w, long w_stride, const double* X,
                                  const double* Pfix, double* f, double* J, const int* mask, hipStream_t s,
-                                 int est = 0 /* BLSQ_EST_LSE */, int sampling = 0 /* BLSQ_SAMPLE_POINT */);
+                                 int est = 0 /* BLSQ_EST_LSE */, int sampling = 0 /* BLSQ_SAMPLE_POINT */,
+                                 int nan_policy = 0 /* BLSQ_NAN_PROPAGATE */);
 // A composite model (blsq_model_eval_comp_dev, 7l): ncomp <= BLSQ_MODEL_MAX_COMP components {fam[c] (BLSQ_TERM_*),
 // cnt[c]} on the host whose parameters add up to n; pmap nullptr (unmapped: X is P [B * reps][n], nf ignored) or as above.
 hipError_t launch_model_eval_comp(int ncomp, const int* fam, const int* cnt, int B, int reps, int m, int n, int nf,
                                   const int* pmap, const double* t, long t_stride, const double* y, const double* w,
                                   long w_stride, const double* X, const double* Pfix, double* f, double* J,
                                   const int* mask, hipStream_t s, int est = 0 /* BLSQ_EST_LSE */,
-                                  int sampling = 0 /* BLSQ_SAMPLE_POINT */);
+                                  int sampling = 0 /* BLSQ_SAMPLE_POINT */, int nan_policy = 0 /* BLSQ_NAN_PROPAGATE */);
 
 // ---------------------------------------------------------------- probes ----
 // probe_kernels.hip: measured peaks / counter calibration (blsq_debug_probe)

@@ -2,7 +2,7 @@
 // (include/blsq.h; kernel: model_kernels.hip), its mapped form blsq_model_eval_map_dev (7k), and the term
 // table behind blsq_term_count / blsq_term_info with the composite entry blsq_model_eval_comp_dev (7l), and the entry
 // that takes the estimator for all of them, blsq_model_eval_est_dev (7m), and the one that takes the sampling as well,
-// blsq_model_eval_bin_dev (7n).
+// blsq_model_eval_bin_dev (7n), and the one that takes the NaN policy too, blsq_model_eval_nan_dev (7o).
 #include "blsq_host.h"
 
 namespace {
@@ -165,8 +165,10 @@ extern "C" int blsq_model_eval_comp_dev(blsq_ctx* ctx, int ncomp, const int32_t*
 
 // One entry for every instance, with the estimator and the sampling (7n): the checks of the three entries
 // above, then the launch of the entry it stands in for.  blsq_model_eval_est_dev numbers its arguments from est = 2,
-// model = 3; blsq_model_eval_bin_dev has `sampling` in between, so every later argument is one further on (sh = 1).
-static int model_eval_checked(blsq_ctx* ctx, const char* what, int sh, int est, int sampling, int model, int ncomp,
+// model = 3; blsq_model_eval_bin_dev has `sampling` in between, so every later argument is one further on (sh = 1);
+// blsq_model_eval_nan_dev has `nan_policy` after that (sh = 2).
+static int model_eval_checked(blsq_ctx* ctx, const char* what, int sh, int est, int sampling, int nan_policy, int model,
+                              int ncomp,
                               const int32_t* fam, const int32_t* cnt, int B, int reps, int m, int n, int nf,
                               const int32_t* pmap, const double* dt, long t_stride, const double* dy, const double* dw,
                               long w_stride, const double* dX, const double* dPfix, double* df, double* dJ,
@@ -175,6 +177,8 @@ static int model_eval_checked(blsq_ctx* ctx, const char* what, int sh, int est, 
   if (est != BLSQ_EST_LSE && est != BLSQ_EST_POISSON) return ctx->bad(2, "est must be one of BLSQ_EST_*");
   if (sampling != BLSQ_SAMPLE_POINT && sampling != BLSQ_SAMPLE_BIN)
     return ctx->bad(3, "sampling must be one of BLSQ_SAMPLE_*");
+  if (nan_policy != BLSQ_NAN_PROPAGATE && nan_policy != BLSQ_NAN_OMIT)
+    return ctx->bad(4, "nan_policy must be one of BLSQ_NAN_*");
   if (model < -1 || model >= kModelCount)
     return ctx->bad(3 + sh, "model must be one of BLSQ_MODEL_*, or -1 for a composite");
   const bool comp = model < 0;
@@ -223,6 +227,8 @@ static int model_eval_checked(blsq_ctx* ctx, const char* what, int sh, int est, 
     return ctx->bad(14 + sh, "t_stride must be 0 or coords * m");
   }
   if (est == BLSQ_EST_POISSON && !dy) return ctx->bad(15 + sh, "y is NULL: the Poisson estimator needs the counts");
+  if (nan_policy == BLSQ_NAN_OMIT && !dy)
+    return ctx->bad(15 + sh, "y is NULL: BLSQ_NAN_OMIT reads the missing points from it");
   if (est == BLSQ_EST_POISSON && dw) return ctx->bad(16 + sh, "w must be NULL with the Poisson estimator");
   if (dw && w_stride != 0 && w_stride != (long)m) return ctx->bad(17 + sh, "w_stride must be 0 or m");
   if (!dX) return ctx->bad(18 + sh, "X is NULL");
@@ -233,12 +239,12 @@ static int model_eval_checked(blsq_ctx* ctx, const char* what, int sh, int est, 
   return ctx->run(K_MODEL_EVAL, what, [&] {
     if (comp)
       return launch_model_eval_comp(ncomp, fam, cnt, B, reps, m, n, nf, pmap, dt, t_stride, dy, dw, w_stride, dX, dPfix,
-                                    df, dJ, dmask, ctx->stream, est, sampling);
+                                    df, dJ, dmask, ctx->stream, est, sampling, nan_policy);
     if (pmap)
       return launch_model_eval_map(model, B, reps, m, n, nf, pmap, dt, t_stride, dy, dw, w_stride, dX, dPfix, df, dJ,
-                                   dmask, ctx->stream, est, sampling);
+                                   dmask, ctx->stream, est, sampling, nan_policy);
     return launch_model_eval(model, B, reps, m, n, dt, t_stride, dy, dw, w_stride, dX, df, dJ, dmask, ctx->stream, est,
-                             sampling);
+                             sampling, nan_policy);
   });
 }
 
@@ -247,8 +253,8 @@ extern "C" int blsq_model_eval_est_dev(blsq_ctx* ctx, int est, int model, int nc
                                        const double* dt, long t_stride, const double* dy, const double* dw,
                                        long w_stride, const double* dX, const double* dPfix, double* df, double* dJ,
                                        const int32_t* dmask) {
-  return model_eval_checked(ctx, "launch_model_eval_est", 0, est, BLSQ_SAMPLE_POINT, model, ncomp, fam, cnt, B, reps, m,
-                            n, nf, pmap, dt, t_stride, dy, dw, w_stride, dX, dPfix, df, dJ, dmask);
+  return model_eval_checked(ctx, "launch_model_eval_est", 0, est, BLSQ_SAMPLE_POINT, BLSQ_NAN_PROPAGATE, model, ncomp,
+                            fam, cnt, B, reps, m, n, nf, pmap, dt, t_stride, dy, dw, w_stride, dX, dPfix, df, dJ, dmask);
 }
 
 extern "C" int blsq_model_eval_bin_dev(blsq_ctx* ctx, int est, int sampling, int model, int ncomp, const int32_t* fam,
@@ -256,6 +262,15 @@ extern "C" int blsq_model_eval_bin_dev(blsq_ctx* ctx, int est, int sampling, int
                                        const double* dt, long t_stride, const double* dy, const double* dw,
                                        long w_stride, const double* dX, const double* dPfix, double* df, double* dJ,
                                        const int32_t* dmask) {
-  return model_eval_checked(ctx, "launch_model_eval_bin", 1, est, sampling, model, ncomp, fam, cnt, B, reps, m, n, nf,
-                            pmap, dt, t_stride, dy, dw, w_stride, dX, dPfix, df, dJ, dmask);
+  return model_eval_checked(ctx, "launch_model_eval_bin", 1, est, sampling, BLSQ_NAN_PROPAGATE, model, ncomp, fam, cnt,
+                            B, reps, m, n, nf, pmap, dt, t_stride, dy, dw, w_stride, dX, dPfix, df, dJ, dmask);
+}
+
+extern "C" int blsq_model_eval_nan_dev(blsq_ctx* ctx, int est, int sampling, int nan_policy, int model, int ncomp,
+                                       const int32_t* fam, const int32_t* cnt, int B, int reps, int m, int n, int nf,
+                                       const int32_t* pmap, const double* dt, long t_stride, const double* dy,
+                                       const double* dw, long w_stride, const double* dX, const double* dPfix,
+                                       double* df, double* dJ, const int32_t* dmask) {
+  return model_eval_checked(ctx, "launch_model_eval_nan", 2, est, sampling, nan_policy, model, ncomp, fam, cnt, B, reps,
+                            m, n, nf, pmap, dt, t_stride, dy, dw, w_stride, dX, dPfix, df, dJ, dmask);
 }

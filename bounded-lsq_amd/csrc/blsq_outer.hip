@@ -23,6 +23,7 @@ struct blsq_outer {
   blsq_cov_plan* cov = nullptr;        // blsq_outer_covariance: created on first use
   DevBuf covmask;                      // [B][n] int64: the active mask of a 'trf' driver (from x, as the host reports it)
   DevBuf covscale;                     // [B] obj / (m - n): blsq_outer_covariance_pinv with variance_scale
+  DevBuf covnobs;                      // [B] int: the points each problem kept (blsq_outer_covariance_pinv_nobs)
   bool scaled_early = false;           // robust loss: the accepted problems' J were scaled by blsq_outer_covariance
   bool cov_fresh = false;              // the covariance plan's factor is that of the resident J (blsq_outer_leverage);
                                        // cleared by start, begin, propose and judge
@@ -375,6 +376,43 @@ extern "C" int blsq_outer_covariance_pinv(blsq_outer* o, int free_only, int vari
     dscale = o->covscale.as<double>();
   }
   if (int rc = cov_pinv_to_host(o->cov, o->J.as<double>(), mask, lda, dscale, cov, rank, rcond, kept_rcond, status))
+    return rc;
+  o->cov_fresh = true;
+  return 0;
+}
+
+// blsq_outer_covariance_pinv with the variance factor obj[b] / (nobs[b] - n) of every problem: the counts
+// are uploaded once, the sibling of the variance kernel turns them into the scale the product kernel applies.
+extern "C" int blsq_outer_covariance_pinv_nobs(blsq_outer* o, int free_only, const int32_t* nobs, double* cov,
+                                               int32_t* rank, double* rcond, double* kept_rcond, int32_t* status) {
+  if (!o) return -1;
+  blsq_ctx* ctx = o->ctx;
+  if (!o->begun) return ctx->bad(1, "blsq_outer_begin has not been called");
+  if (!nobs) return ctx->bad(3, "nobs is NULL");
+  for (int b = 0; b < o->B; ++b)
+    if (nobs[b] < 0 || nobs[b] > o->m) return ctx->bad(3, "nobs entry outside 0 .. m");
+  if (!cov) return ctx->bad(4, "cov is NULL");
+  if (!rank) return ctx->bad(5, "rank is NULL");
+  if (!rcond) return ctx->bad(6, "rcond is NULL");
+  if (!kept_rcond) return ctx->bad(7, "kept_rcond is NULL");
+  if (!status) return ctx->bad(8, "status is NULL");
+  HIPCHK(ctx, hipSetDevice(ctx->device));
+  const long long* mask = nullptr;
+  int lda = o->n;
+  o->cov_fresh = false;
+  if (int rc = outer_cov_prepare(o, free_only, &mask, &lda)) return rc;
+  if (!o->covscale.p)
+    if (int rc = alloc_all(ctx, {{&o->covscale, sizeof(double) * (size_t)o->B, "hipMalloc(variance scale)"}}))
+      return rc;
+  if (!o->covnobs.p)
+    if (int rc = alloc_all(ctx, {{&o->covnobs, sizeof(int) * (size_t)o->B, "hipMalloc(nobs)"}})) return rc;
+  // (pageable source: the copy has left `nobs` when the call returns)
+  HIPCHK(ctx, hipMemcpyAsync(o->covnobs.p, nobs, sizeof(int) * (size_t)o->B, hipMemcpyHostToDevice, ctx->stream));
+  const hipError_t e = launch_cov_variance_nobs(o->B, o->n, o->st.obj, o->covnobs.as<int>(), o->covscale.as<double>(),
+                                                ctx->stream);
+  if (e != hipSuccess) return ctx->fail(e, "launch_cov_variance_nobs");
+  if (int rc = cov_pinv_to_host(o->cov, o->J.as<double>(), mask, lda, o->covscale.as<double>(), cov, rank, rcond,
+                                kept_rcond, status))
     return rc;
   o->cov_fresh = true;
   return 0;

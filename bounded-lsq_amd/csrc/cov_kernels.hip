@@ -597,6 +597,18 @@ __global__ __launch_bounds__(256) void cov_variance_kernel(int B, double dof, co
   if (b < B) dscale[b] = obj[b] / dof;
 }
 
+// dscale[b] = obj[b] / (nobs[b] - n), the problem's own degrees of freedom (nan_policy='omit'); +inf
+// where nobs[b] <= n: the covariance of such a problem cannot be estimated
+__global__ __launch_bounds__(256) void cov_variance_nobs_kernel(int B, int n, const double* __restrict__ obj,
+                                                                const int* __restrict__ nobs,
+                                                                double* __restrict__ dscale) {
+  const int b = blockIdx.x * blockDim.x + threadIdx.x;
+  if (b < B) {
+    const int dof = nobs[b] - n;
+    dscale[b] = dof > 0 ? obj[b] / (double)dof : __builtin_huge_val();
+  }
+}
+
 // ---- launches ----------------------------------------------------------------------------------
 hipError_t launch_cov_perm(int B, int n, const long long* active, int lda, int* perm, int* nfree, int* ncols,
                            hipStream_t s) {
@@ -667,6 +679,12 @@ hipError_t launch_cov_pinv_product(int B, int n, int NPAD, const double* X, cons
 hipError_t launch_cov_variance(int B, int m, int n, const double* obj, double* dscale, hipStream_t st) {
   if (m <= n) return hipErrorInvalidValue;
   hipLaunchKernelGGL(cov_variance_kernel, dim3((B + 255) / 256), dim3(256), 0, st, B, (double)(m - n), obj, dscale);
+  return hipGetLastError();
+}
+
+hipError_t launch_cov_variance_nobs(int B, int n, const double* obj, const int* nobs, double* dscale, hipStream_t st) {
+  if (!nobs) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(cov_variance_nobs_kernel, dim3((B + 255) / 256), dim3(256), 0, st, B, n, obj, nobs, dscale);
   return hipGetLastError();
 }
 

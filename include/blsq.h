@@ -512,6 +512,27 @@ int blsq_model_eval_bin_dev(blsq_ctx* ctx, int est, int sampling, int model, int
                             const double* dt, long t_stride, const double* dy, const double* dw, long w_stride,
                             const double* dX, const double* dPfix, double* df, double* dJ, const int32_t* dmask);
 
+/* What a NaN in y means.  Append only.
+ *   PROPAGATE  nothing special: the NaN passes through the residual as IEEE arithmetic gives it (the entries above).
+ *   OMIT       point i of problem b is left out of the fit iff y[b][i] is NaN: f[q][i] = +0.0 and row i of
+ *              J is +0.0 in every column, for every rep.  Its t, w (and bin edges) are never read and may hold anything,
+ *              NaN included; the row costs no arithmetic.  +-inf in y is not missing data and passes through.  A row of
+ *              zeros changes no singular value of J, so the solvers, the losses and the covariance run unchanged; only
+ *              the degrees of freedom differ per problem (blsq_outer_covariance_pinv_nobs).  dy is required. */
+enum { BLSQ_NAN_PROPAGATE = 0, BLSQ_NAN_OMIT };
+/* blsq_model_eval_bin_dev with the NaN policy: one entry for every model instance, estimator, sampling and policy.
+ * With BLSQ_NAN_PROPAGATE the outputs are those of blsq_model_eval_bin_dev, bit for bit; with BLSQ_NAN_OMIT the kept rows
+ * are, and the omitted ones are zeros.  A negative return is the index of the bad argument (ctx = 1, est = 2,
+ * sampling = 3, nan_policy = 4, model = 5, ncomp = 6, fam = 7, cnt = 8, B = 9, reps, m, n = 12, nf = 13, pmap = 14,
+ * t = 15, t_stride = 16, y = 17, w = 18, w_stride, X = 20, Pfix = 21, f = 22, J = 23, mask), and for the contents of
+ * pmap -25 (an entry outside -1 .. nf - 1) and -26 (a k < nf that no entry names); with BLSQ_EST_POISSON or
+ * BLSQ_NAN_OMIT dy == NULL is -17, with BLSQ_EST_POISSON dw != NULL is -18.  Nothing is launched then. */
+int blsq_model_eval_nan_dev(blsq_ctx* ctx, int est, int sampling, int nan_policy, int model, int ncomp,
+                            const int32_t* fam, const int32_t* cnt, int B, int reps, int m, int n, int nf,
+                            const int32_t* pmap, const double* dt, long t_stride, const double* dy, const double* dw,
+                            long w_stride, const double* dX, const double* dPfix, double* df, double* dJ,
+                            const int32_t* dmask);
+
 /* ---- parameter covariance from the final Jacobian --------------------------------------------------------------
  * The reference documents `x_covariance` as the inverse of J^T J at the solution (least_squares.py:248-252) and fills
  * it only through its MINPACK bridge (method='lm').  Here, per problem, from a Householder triangle R of J (the TSQR
@@ -571,6 +592,13 @@ int blsq_cov_pinv(blsq_cov_plan* plan, const double* J, const int64_t* active, c
  * error otherwise: curve_fit fills pcov with inf there, which the caller does).  Host outputs: B n^2 + 4 B numbers. */
 int blsq_outer_covariance_pinv(blsq_outer* o, int free_only, int variance_scale, double* cov, int32_t* rank,
                                double* rcond, double* kept_rcond, int32_t* status);
+/* blsq_outer_covariance_pinv with the degrees of freedom of every problem (BLSQ_NAN_OMIT): problem b is
+ * multiplied by obj[b] / (nobs[b] - n), nobs[b] the number of points it kept, and by +inf where nobs[b] <= n (its
+ * covariance cannot be estimated: the caller fills it with inf; the batch mates are not affected).  nobs: host [B], each
+ * in 0 .. m (argument error otherwise, as is NULL), uploaded once per call.  The rank tolerance keeps using the
+ * allocated m.  Everything else as blsq_outer_covariance_pinv. */
+int blsq_outer_covariance_pinv_nobs(blsq_outer* o, int free_only, const int32_t* nobs /*host [B]*/, double* cov,
+                                    int32_t* rank, double* rcond, double* kept_rcond, int32_t* status);
 
 /* ---- row forms through the covariance factor: leverages and prediction variances ---------------------------------
  * For every row a_i of a row-major matrix A [B][rows][n]:  out[b][i] = scale[b] * a_i C_b a_i^T  with C_b the (unscaled)

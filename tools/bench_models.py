@@ -23,8 +23,13 @@ amplitudes and the offset are divided by the bin width so that a bin holds what 
 integrals; the named route runs the bin-integrated kernel instances (blsq_model_eval_bin_dev), the callable route the
 numpy functions of ``models.binned``.  It combines with every other switch.  Without it nothing here changes.
 
+``--omit FRACTION`` blanks that share of `ydata` at random (NaN; a fixed seed, every problem keeps more
+points than parameters) and passes ``nan_policy='omit'`` on both routes: the named route runs the omitting kernel
+instances (blsq_model_eval_nan_dev), the callable route ``models.omit_residual`` / ``omit_jacobian``.  ``--omit 0``
+passes the keyword with no NaN: the cost of the flag alone.  Without it nothing here changes.
+
 usage: python tools/bench_models.py [--B 4096] [--m 64] [--repeat 5] [--peaks 1] [--fixed 1,4] [--tied 5:2] [--kernel]
-                                    [--launches 50] [--rounds 1] [--estimator lse] [--binned]
+                                    [--launches 50] [--rounds 1] [--estimator lse] [--binned] [--omit FRACTION]
 """
 import argparse
 import json
@@ -70,7 +75,16 @@ def problems(B, m, seed=0, peaks=1, fixed=(), tied=None, poisson=False, binned=F
     return x, Y, P0, (truth - half, truth + half)
 
 
-def kernel_times(ctx, x, Y, P0, pm, launches, rounds=1, estimator="lse", binned=False):
+def blank(Y, fraction, n, seed=1):
+    """Y with `fraction` of its entries NaN, drawn with a fixed seed; no problem is left with fewer than n + 1 points."""
+    rng = np.random.default_rng(seed)
+    om = rng.random(Y.shape) < fraction
+    short = (~om).sum(axis=1) <= n
+    om[short] = False
+    return np.where(om, np.nan, Y)
+
+
+def kernel_times(ctx, x, Y, P0, pm, launches, rounds=1, estimator="lse", binned=False, omit=False):
     """us per launch of f and of J ('model_eval' slot, HIP events) for the unmapped entry at P0 and, with a map, the
     mapped entry at reduce_x(P0); 'composite*': the same for 'gauss*K+poly*1' through the composite entry."""
     B, m = Y.shape
@@ -82,7 +96,8 @@ def kernel_times(ctx, x, Y, P0, pm, launches, rounds=1, estimator="lse", binned=
         cases += [("mapped", "gauss_sum", pm), ("composite_mapped", spec, pm)]
     for key, name, mp in cases:
         dm = models.DeviceModel(ctx, name, B, m, n, x, Y, 0.01 if estimator == "lse" else None, param_map=mp,
-                                Pfix=None if mp is None else P0, estimator=estimator, **({"binned": True} if binned else {}))
+                                Pfix=None if mp is None else P0, estimator=estimator, **({"binned": True} if binned else {}),
+                                **({"nan_policy": "omit"} if omit else {}))
         X = P0 if mp is None else np.ascontiguousarray(mp.reduce_x(P0))
         d_x, d_f, d_J = ctx.to_device(X), ctx.malloc(8 * B * m), ctx.malloc(8 * B * m * dm.n)
         for what, call in (("f", lambda: dm.fun_dev(d_x, d_f, 1)), ("J", lambda: dm.jac_dev(d_x, d_J))):
@@ -120,26 +135,35 @@ def main():
     ap.add_argument("--rounds", type=int, default=1, help="with --kernel: timed blocks of --launches launches each")
     ap.add_argument("--estimator", default="lse", choices=models.ESTIMATORS)
     ap.add_argument("--binned", action="store_true", help="fit bin integrals: the bin-integrated instances")
+    ap.add_argument("--omit", type=float, default=None, metavar="FRACTION",
+                    help="blank this share of ydata and pass nan_policy='omit' (0: the keyword with no NaN)")
     a = ap.parse_args()
+    if a.omit is not None and not 0.0 <= a.omit < 1.0:
+        ap.error("--omit takes a fraction in [0, 1)")
     fixed = [int(v) for v in a.fixed.split(",") if v]
     tied = {int(p.split(":")[0]): int(p.split(":")[1]) for p in a.tied.split(",") if p}
     poisson = a.estimator == "poisson"
     x, Y, P0, bounds = problems(a.B, a.m, peaks=a.peaks, fixed=fixed, tied=tied, poisson=poisson, binned=a.binned)
     n = P0.shape[1]
+    omit = a.omit is not None
+    if omit:
+        Y = blank(Y, a.omit, n)
     M = models.binned("gauss_sum") if a.binned else models.get("gauss_sum")
     pm = ParamMap(n, fixed, tied) if (fixed or tied) else None
     ctx = _abi.Context(0)
     if a.kernel:
         res = {"model": "gauss_sum", "B": a.B, "m": a.m, "n": n, "nf": n if pm is None else pm.nf, "fixed": fixed,
                "tied": a.tied, "launches": a.launches, "rounds": a.rounds, "estimator": a.estimator,
-               "binned": a.binned}
-        res.update(kernel_times(ctx, x, Y, P0, pm, a.launches, a.rounds, a.estimator, a.binned))
+               "binned": a.binned, "omit": a.omit}
+        res.update(kernel_times(ctx, x, Y, P0, pm, a.launches, a.rounds, a.estimator, a.binned, omit))
         ctx.close()
         print(json.dumps(res))
         return
     kw = dict(sigma=0.01, bounds=bounds, driver="device", ctx=ctx, ftol=1e-10, xtol=1e-10, gtol=1e-10)
     if poisson:
         kw.update(sigma=None, estimator="poisson")
+    if omit:
+        kw.update(nan_policy="omit")
     named_kw = dict(kw, binned=True) if a.binned else kw
     if pm is None:
         routes = {"named": lambda: curve_fit_batch("gauss_sum", x, Y, P0, **named_kw),
@@ -169,7 +193,7 @@ def main():
     both = np.array([ra.success and rb.success for ra, rb in zip(out["named"][2], out["callable"][2])])
     free = (lambda P: P) if pm is None else pm.reduce_x
     res = {"model": "gauss_sum", "B": a.B, "m": a.m, "n": n, "nf": n if pm is None else pm.nf, "driver": "device",
-           "estimator": a.estimator, "binned": a.binned, "named_s": round(float(np.median(times["named"])), 4),
+           "estimator": a.estimator, "binned": a.binned, "omit": a.omit, "named_s": round(float(np.median(times["named"])), 4),
            "callable_s": round(float(np.median(times["callable"])), 4),
            "named_all_s": [round(t, 4) for t in times["named"]],
            "callable_all_s": [round(t, 4) for t in times["callable"]],
