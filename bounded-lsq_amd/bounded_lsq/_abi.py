@@ -20,6 +20,16 @@ c_int32_p = C.POINTER(C.c_int32)
 c_uint8_p = C.POINTER(C.c_uint8)
 vp = C.c_void_p
 
+
+def _model_eval(lead, mapped=True):
+    """A blsq_model_eval*_dev entry: ctx, `lead`, B, reps, m, n (mapped: nf, pmap), t, t_stride, y, w, w_stride, X
+    (mapped: Pfix), f, J, mask."""
+    return (C.c_int, [vp] + lead + [C.c_int] * 4 + ([C.c_int, c_int32_p] if mapped else [])
+            + [vp, C.c_long, vp, vp, C.c_long, vp] + ([vp] if mapped else []) + [vp] * 3)
+
+
+_COMP = [C.c_int, c_int32_p, c_int32_p]      # ncomp, fam, cnt
+
 # every symbol include/blsq.h declares: name -> (restype, argtypes)
 SIGNATURES = {
     "blsq_version": (C.c_int, []),
@@ -115,18 +125,14 @@ SIGNATURES = {
     "blsq_outer_leverage": (C.c_int, [vp, vp, vp]),
     "blsq_model_count": (C.c_int, []),
     "blsq_model_info": (C.c_int, [C.c_int, C.POINTER(C.c_char_p), c_int32_p, c_int32_p, c_int32_p]),
-    "blsq_model_eval_dev": (C.c_int, [vp] + [C.c_int] * 5 + [vp, C.c_long, vp, vp, C.c_long] + [vp] * 4),
-    "blsq_model_eval_map_dev": (C.c_int, [vp] + [C.c_int] * 6 + [c_int32_p, vp, C.c_long, vp, vp, C.c_long] + [vp] * 5),
+    "blsq_model_eval_dev": _model_eval([C.c_int], mapped=False),                 # model
+    "blsq_model_eval_map_dev": _model_eval([C.c_int]),
     "blsq_term_count": (C.c_int, []),
     "blsq_term_info": (C.c_int, [C.c_int, C.POINTER(C.c_char_p), c_int32_p]),
-    "blsq_model_eval_comp_dev": (C.c_int, [vp, C.c_int, c_int32_p, c_int32_p] + [C.c_int] * 5
-                                 + [c_int32_p, vp, C.c_long, vp, vp, C.c_long] + [vp] * 5),
-    "blsq_model_eval_est_dev": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, c_int32_p, c_int32_p] + [C.c_int] * 5
-                                + [c_int32_p, vp, C.c_long, vp, vp, C.c_long] + [vp] * 5),
-    "blsq_model_eval_bin_dev": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, C.c_int, c_int32_p, c_int32_p] + [C.c_int] * 5
-                                + [c_int32_p, vp, C.c_long, vp, vp, C.c_long] + [vp] * 5),
-    "blsq_model_eval_nan_dev": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, c_int32_p, c_int32_p]
-                                + [C.c_int] * 5 + [c_int32_p, vp, C.c_long, vp, vp, C.c_long] + [vp] * 5),
+    "blsq_model_eval_comp_dev": _model_eval(_COMP),
+    "blsq_model_eval_est_dev": _model_eval([C.c_int] * 2 + _COMP),                # est, model
+    "blsq_model_eval_bin_dev": _model_eval([C.c_int] * 3 + _COMP),                # est, sampling, model
+    "blsq_model_eval_nan_dev": _model_eval([C.c_int] * 4 + _COMP),                # est, sampling, nan_policy, model
 }
 
 _lib = None

@@ -909,6 +909,7 @@ class DeviceModel:
                     raise ValueError("`Pfix` must have shape (B, n).")
                 self.d_Pfix = self._upload(Pfix)
         self.bounds_dev = None
+        self._bind()
         ctx.adopt(self)
 
     def _upload(self, a):
@@ -923,56 +924,38 @@ class DeviceModel:
                                 for a in (lb, ub))
         return self.bounds_dev
 
+    def _entry(self):
+        """The entry of this fit and its arguments between ctx and B: the entry of the last flag the fit sets (it takes
+        every kind of model and the flags before it); without a flag, the entry of the kind of model."""
+        M, comp = self.model, isinstance(self.model, CompositeModel)
+        table = [len(M.components), M.fam_ids.ctypes.data_as(_abi.c_int32_p),
+                 M.counts.ctypes.data_as(_abi.c_int32_p)] if comp else [0, None, None]
+        flags = [ESTIMATORS.index(self.estimator), SAMPLING.index('bin' if self.binned else 'point'),
+                 NAN_POLICIES.index(self.nan_policy)]
+        kind = [-1 if comp else M.id] + table
+        if self.nan_policy != 'propagate':
+            return "blsq_model_eval_nan_dev", flags + kind
+        if self.binned:
+            return "blsq_model_eval_bin_dev", flags[:2] + kind
+        if self.estimator != 'lse':
+            return "blsq_model_eval_est_dev", flags[:1] + kind
+        if comp:                                              # with or without a map
+            return "blsq_model_eval_comp_dev", table
+        return ("blsq_model_eval_dev" if self.param_map is None else "blsq_model_eval_map_dev"), [M.id]
+
+    def _bind(self):
+        """The entry's name and what every call passes it, fixed once the data are uploaded: the arguments from ctx to
+        reps, from reps to X, and from X to f (`_eval` has the rest)."""
+        name, lead = self._entry()
+        mapped = name != "blsq_model_eval_dev"                # every other entry has nf, pmap and Pfix
+        pmap = None if self.param_map is None else self._pmap.ctypes.data_as(_abi.c_int32_p)
+        self._call = (name, lead + [self.B], [self.m, self.n_model] + ([self.n, pmap] if mapped else [])
+                      + [self.d_t, self.t_stride, self.d_y, self.d_w, self.w_stride], [self.d_Pfix] if mapped else [])
+
     def _eval(self, x_ptr, reps, f_ptr, J_ptr, mask_ptr):
-        if self.nan_policy != 'propagate':                    # every kind of model, estimator and sampling: one entry
-            M, comp = self.model, isinstance(self.model, CompositeModel)
-            self.ctx.check(self.ctx.lib.blsq_model_eval_nan_dev(
-                self.ctx.h, ESTIMATORS.index(self.estimator), SAMPLING.index('bin' if self.binned else 'point'),
-                NAN_POLICIES.index(self.nan_policy), -1 if comp else M.id, len(M.components) if comp else 0,
-                M.fam_ids.ctypes.data_as(_abi.c_int32_p) if comp else None,
-                M.counts.ctypes.data_as(_abi.c_int32_p) if comp else None, self.B, int(reps), self.m, self.n_model,
-                self.n, None if self.param_map is None else self._pmap.ctypes.data_as(_abi.c_int32_p), self.d_t,
-                self.t_stride, self.d_y, self.d_w, self.w_stride, x_ptr, self.d_Pfix, f_ptr, J_ptr, mask_ptr),
-                "blsq_model_eval_nan_dev")
-            return
-        if self.binned:                                       # every kind of model, both estimators: one entry
-            M, comp = self.model, isinstance(self.model, CompositeModel)
-            self.ctx.check(self.ctx.lib.blsq_model_eval_bin_dev(
-                self.ctx.h, ESTIMATORS.index(self.estimator), SAMPLING.index('bin'), -1 if comp else M.id,
-                len(M.components) if comp else 0, M.fam_ids.ctypes.data_as(_abi.c_int32_p) if comp else None,
-                M.counts.ctypes.data_as(_abi.c_int32_p) if comp else None, self.B, int(reps), self.m, self.n_model,
-                self.n, None if self.param_map is None else self._pmap.ctypes.data_as(_abi.c_int32_p), self.d_t,
-                self.t_stride, self.d_y, self.d_w, self.w_stride, x_ptr, self.d_Pfix, f_ptr, J_ptr, mask_ptr),
-                "blsq_model_eval_bin_dev")
-            return
-        if self.estimator != 'lse':                           # every kind of model: one entry
-            M, comp = self.model, isinstance(self.model, CompositeModel)
-            self.ctx.check(self.ctx.lib.blsq_model_eval_est_dev(
-                self.ctx.h, ESTIMATORS.index(self.estimator), -1 if comp else M.id, len(M.components) if comp else 0,
-                M.fam_ids.ctypes.data_as(_abi.c_int32_p) if comp else None,
-                M.counts.ctypes.data_as(_abi.c_int32_p) if comp else None, self.B, int(reps), self.m, self.n_model,
-                self.n, None if self.param_map is None else self._pmap.ctypes.data_as(_abi.c_int32_p), self.d_t,
-                self.t_stride, self.d_y, self.d_w, self.w_stride, x_ptr, self.d_Pfix, f_ptr, J_ptr, mask_ptr),
-                "blsq_model_eval_est_dev")
-            return
-        if isinstance(self.model, CompositeModel):            # with or without a map: one entry
-            M = self.model
-            self.ctx.check(self.ctx.lib.blsq_model_eval_comp_dev(
-                self.ctx.h, len(M.components), M.fam_ids.ctypes.data_as(_abi.c_int32_p),
-                M.counts.ctypes.data_as(_abi.c_int32_p), self.B, int(reps), self.m, self.n_model, self.n,
-                None if self.param_map is None else self._pmap.ctypes.data_as(_abi.c_int32_p), self.d_t, self.t_stride,
-                self.d_y, self.d_w, self.w_stride, x_ptr, self.d_Pfix, f_ptr, J_ptr, mask_ptr),
-                "blsq_model_eval_comp_dev")
-            return
-        if self.param_map is not None:
-            self.ctx.check(self.ctx.lib.blsq_model_eval_map_dev(
-                self.ctx.h, self.model.id, self.B, int(reps), self.m, self.n_model, self.n,
-                self._pmap.ctypes.data_as(_abi.c_int32_p), self.d_t, self.t_stride, self.d_y, self.d_w, self.w_stride,
-                x_ptr, self.d_Pfix, f_ptr, J_ptr, mask_ptr), "blsq_model_eval_map_dev")
-            return
-        self.ctx.check(self.ctx.lib.blsq_model_eval_dev(
-            self.ctx.h, self.model.id, self.B, int(reps), self.m, self.n, self.d_t, self.t_stride, self.d_y, self.d_w,
-            self.w_stride, x_ptr, f_ptr, J_ptr, mask_ptr), "blsq_model_eval_dev")
+        name, head, data, pfix = self._call
+        self.ctx.check(getattr(self.ctx.lib, name)(self.ctx.h, *head, int(reps), *data, x_ptr, *pfix, f_ptr, J_ptr,
+                                                   mask_ptr), name)
 
     def fun_dev(self, x_ptr, f_ptr, reps=1):
         self._eval(x_ptr, reps, f_ptr, None, None)

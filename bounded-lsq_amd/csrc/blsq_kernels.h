@@ -612,32 +612,35 @@ hipError_t launch_fd_assemble(int B, int m, int n, int method, const double* x, 
                               double* J, const int* mask, hipStream_t s);
 
 // --------------------------------------------------- built-in fit models (7j) ----
-// model_kernels.hip (blsq_model_eval_dev): f [B * reps][m] and / or J [B][m][n] (reps == 1) of model BLSQ_MODEL_* at
-// P [B * reps][n]; t_stride 0 (shared) or coords * m, w nullptr or stride 0 / m, y / mask may be nullptr.
-// est (all three launches; blsq_model_eval_est_dev, 7m): BLSQ_EST_LSE, or BLSQ_EST_POISSON for the deviance residual
-// and its Jacobian, which needs y and w == nullptr (hipErrorInvalidValue otherwise).
-// sampling (all three launches; blsq_model_eval_bin_dev, 7n): BLSQ_SAMPLE_POINT, or BLSQ_SAMPLE_BIN for the model
-// integrated over the bins t [2 coords][m] (rows lo, hi per coordinate; t_stride 0 or 2 * coords * m).
-// nan_policy (all three launches; blsq_model_eval_nan_dev, 7o): BLSQ_NAN_PROPAGATE, or BLSQ_NAN_OMIT for rows of zeros
-// where y is NaN, which needs y (hipErrorInvalidValue otherwise); t and w are not read there.
-hipError_t launch_model_eval(int model, int B, int reps, int m, int n, const double* t, long t_stride, const double* y,
-                             const double* w, long w_stride, const double* P, double* f, double* J, const int* mask,
-                             hipStream_t s, int est = 0 /* BLSQ_EST_LSE */,
-                             int sampling = 0 /* BLSQ_SAMPLE_POINT */, int nan_policy = 0 /* BLSQ_NAN_PROPAGATE */);
-// The same through a parameter map (blsq_model_eval_map_dev, 7k): X [B * reps][nf], pmap [n] on the host (-1 or a slot
-// < nf, every slot used: the caller has checked), Pfix [B][n] (read where pmap[j] == -1), J [B][m][nf].
-hipError_t launch_model_eval_map(int model, int B, int reps, int m, int n, int nf, const int* pmap, const double* t,
-                                 long t_stride, const double* y, const double* w, long w_stride, const double* X,
-                                 const double* Pfix, double* f, double* J, const int* mask, hipStream_t s,
-                                 int est = 0 /* BLSQ_EST_LSE */, int sampling = 0 /* BLSQ_SAMPLE_POINT */,
-                                 int nan_policy = 0 /* BLSQ_NAN_PROPAGATE */);
-// A composite model (blsq_model_eval_comp_dev, 7l): ncomp <= BLSQ_MODEL_MAX_COMP components {fam[c] (BLSQ_TERM_*),
-// cnt[c]} on the host whose parameters add up to n; pmap nullptr (unmapped: X is P [B * reps][n], nf ignored) or as above.
-hipError_t launch_model_eval_comp(int ncomp, const int* fam, const int* cnt, int B, int reps, int m, int n, int nf,
-                                  const int* pmap, const double* t, long t_stride, const double* y, const double* w,
-                                  long w_stride, const double* X, const double* Pfix, double* f, double* J,
-                                  const int* mask, hipStream_t s, int est = 0 /* BLSQ_EST_LSE */,
-                                  int sampling = 0 /* BLSQ_SAMPLE_POINT */, int nan_policy = 0 /* BLSQ_NAN_PROPAGATE */);
+// Parameters per term of the families BLSQ_TERM_* (gauss, lorentz, pvoigt, exp, poly), in the order of the enum: the one
+// table behind blsq_term_info, the entries' check of n and the launcher's.
+constexpr int MODEL_TERM_PARAMS[] = {3, 3, 4, 2, 1};
+
+// One evaluation of model_kernels.hip (the six blsq_model_eval*_dev entries, 7j to 7o): f [B * reps][m] and / or
+// J [B][m][nf] (reps == 1) at X [B * reps][nf].  The fit's flags pick the kernel instance; everything else is data.
+struct ModelEvalCall {
+  int est;                // BLSQ_EST_*: POISSON is the deviance residual and its Jacobian; needs y, and w == nullptr
+  int sampling;           // BLSQ_SAMPLE_*: BIN integrates over the bins t [2 coords][m] (rows lo, hi per coordinate)
+  int nan_policy;         // BLSQ_NAN_*: OMIT gives rows of zeros where y is NaN; needs y; t and w are not read there
+  int model;              // BLSQ_MODEL_*, or -1 for a composite
+  int ncomp;              // composite: components {fam[c] (BLSQ_TERM_*), cnt[c]} on the host, at most
+  const int* fam;         //   BLSQ_MODEL_MAX_COMP, whose parameters add up to n
+  const int* cnt;
+  int B, reps, m, n;      // n: the model's parameters
+  int nf;                 // solver variables: the width of X and J (ignored without a pmap: n)
+  const int* pmap;        // nullptr (X is P [B * reps][n]) or [n] on the host: -1 or a slot < nf, every slot used
+  const double* t; long t_stride;   // 0 (shared) or the rows of one problem times m
+  const double* y;        // [B][m] or nullptr
+  const double* w; long w_stride;   // nullptr, or stride 0 / m
+  const double* X;
+  const double* Pfix;     // [B][n], read where pmap[j] == -1
+  double* f;
+  double* J;
+  const int* mask;        // nullptr or [B]: a problem with mask[b] == 0 is left untouched
+};
+// hipErrorInvalidValue, and nothing launched, for a flag, model or table out of range, a y the flags need, a w under
+// POISSON, or a size the grid or LDS cannot hold: the refusals that keep the kernel's offsets in bounds.
+hipError_t launch_model_eval(const ModelEvalCall& c, hipStream_t s);
 
 // ---------------------------------------------------------------- probes ----
 // probe_kernels.hip: measured peaks / counter calibration (blsq_debug_probe)

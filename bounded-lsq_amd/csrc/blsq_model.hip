@@ -1,8 +1,8 @@
-// Built-in fit models: the table behind blsq_model_count / blsq_model_info and the entry point blsq_model_eval_dev
-// (include/blsq.h; kernel: model_kernels.hip), its mapped form blsq_model_eval_map_dev (7k), and the term
-// table behind blsq_term_count / blsq_term_info with the composite entry blsq_model_eval_comp_dev (7l), and the entry
-// that takes the estimator for all of them, blsq_model_eval_est_dev (7m), and the one that takes the sampling as well,
-// blsq_model_eval_bin_dev (7n), and the one that takes the NaN policy too, blsq_model_eval_nan_dev (7o).
+// Built-in fit models (include/blsq.h; kernel: model_kernels.hip): the model and term tables behind
+// blsq_model_count / _info and blsq_term_count / _info, and the six entries blsq_model_eval_dev, _map_dev, _comp_dev,
+// _est_dev, _bin_dev and _nan_dev.  An entry fills a ModelEvalCall from its arguments (what its signature does not have
+// is the default) and hands it to model_eval_checked with its EvalEntry: one list of checks, one launcher, and per entry
+// only the argument numbers.
 #include "blsq_host.h"
 
 namespace {
@@ -25,14 +25,11 @@ bool model_n_fits(const ModelRow& r, int n) {
   return n > r.n_base && (n - r.n_base) % r.n_per_term == 0;
 }
 
-struct TermRow {
-  const char* name;
-  int n_per_term;
-};
-// in the order of the BLSQ_TERM_* enum
-const TermRow kTerms[] = {{"gauss", 3}, {"lorentz", 3}, {"pvoigt", 4}, {"exp", 2}, {"poly", 1}};
-constexpr int kTermCount = (int)(sizeof(kTerms) / sizeof(kTerms[0]));
+// in the order of the BLSQ_TERM_* enum; the parameters per term: MODEL_TERM_PARAMS (blsq_kernels.h)
+const char* const kTermNames[] = {"gauss", "lorentz", "pvoigt", "exp", "poly"};
+constexpr int kTermCount = (int)(sizeof(kTermNames) / sizeof(kTermNames[0]));
 static_assert(kTermCount == BLSQ_TERM_POLY + 1, "one row per BLSQ_TERM_*");
+static_assert(sizeof(MODEL_TERM_PARAMS) / sizeof(MODEL_TERM_PARAMS[0]) == kTermCount, "one count per BLSQ_TERM_*");
 
 }  // namespace
 
@@ -48,71 +45,125 @@ extern "C" int blsq_model_info(int model, const char** name, int* coords, int* n
   return 0;
 }
 
+extern "C" int blsq_term_count(void) { return kTermCount; }
+
+extern "C" int blsq_term_info(int term, const char** name, int* n_per_term) {
+  if (term < 0 || term >= kTermCount) return -1;
+  if (name) *name = kTermNames[term];
+  if (n_per_term) *n_per_term = MODEL_TERM_PARAMS[term];
+  return 0;
+}
+
+namespace {
+
+// What tells the six entries apart: the label of the launch, the kinds of model the entry takes, and the number a
+// bad argument is reported by: its position in the entry's signature (ctx = 1; 0: the entry has no such argument).  The
+// arguments come in runs that every signature has in the same order, so a run is given by its first number: fam and cnt
+// follow ncomp; reps, m, n follow B; pmap follows nf; t_stride, y, w, w_stride, X follow t; J follows f.  The contents of
+// pmap have no argument of their own: an entry outside -1 .. nf - 1 is `pmap_entry`, an unused variable the number after
+// (the two past the entry's last argument).
+struct EvalEntry {
+  const char* label;
+  bool composite;             // takes model == -1 with a component table (otherwise named models only)
+  bool needs_pmap;
+  int est, sampling, nan_policy, model, ncomp, B, nf, t, Pfix, f, pmap_entry;
+};
+constexpr EvalEntry kEvalDev = {"launch_model_eval", false, false, 0, 0, 0, 2, 0, 3, 0, 7, 0, 13, 0};
+constexpr EvalEntry kEvalMap = {"launch_model_eval_map", false, true, 0, 0, 0, 2, 0, 3, 7, 9, 15, 16, 19};
+constexpr EvalEntry kEvalComp = {"launch_model_eval_comp", true, false, 0, 0, 0, 0, 2, 5, 9, 11, 17, 18, 21};
+constexpr EvalEntry kEvalEst = {"launch_model_eval_est", true, false, 2, 0, 0, 3, 4, 7, 11, 13, 19, 20, 23};
+constexpr EvalEntry kEvalBin = {"launch_model_eval_bin", true, false, 2, 3, 0, 4, 5, 8, 12, 14, 20, 21, 24};
+constexpr EvalEntry kEvalNan = {"launch_model_eval_nan", true, false, 2, 3, 4, 5, 6, 9, 13, 15, 21, 22, 25};
+
+// The checks of every entry, in the order of the arguments, and the launch.  A negative return names the argument.
+int model_eval_checked(blsq_ctx* ctx, const EvalEntry& e, const ModelEvalCall& c) {
+  if (!ctx) return -1;
+  if (c.est != BLSQ_EST_LSE && c.est != BLSQ_EST_POISSON) return ctx->bad(e.est, "est must be one of BLSQ_EST_*");
+  if (c.sampling != BLSQ_SAMPLE_POINT && c.sampling != BLSQ_SAMPLE_BIN)
+    return ctx->bad(e.sampling, "sampling must be one of BLSQ_SAMPLE_*");
+  if (c.nan_policy != BLSQ_NAN_PROPAGATE && c.nan_policy != BLSQ_NAN_OMIT)
+    return ctx->bad(e.nan_policy, "nan_policy must be one of BLSQ_NAN_*");
+  if (c.model < (e.composite ? -1 : 0) || c.model >= kModelCount)
+    return ctx->bad(e.model, e.composite ? "model must be one of BLSQ_MODEL_*, or -1 for a composite"
+                                         : "model must be one of BLSQ_MODEL_*");
+  const bool comp = c.model < 0;
+  const int m = c.m, n = c.n, nf = c.nf;
+  long total = 0;
+  if (!comp) {
+    if (c.ncomp != 0) return ctx->bad(e.ncomp, "ncomp must be 0 with a named model");
+  } else {
+    if (c.ncomp < 1 || c.ncomp > BLSQ_MODEL_MAX_COMP)
+      return ctx->bad(e.ncomp, "ncomp must be in 1 .. BLSQ_MODEL_MAX_COMP");
+    if (!c.fam) return ctx->bad(e.ncomp + 1, "fam is NULL");
+    if (!c.cnt) return ctx->bad(e.ncomp + 2, "cnt is NULL");
+    for (int k = 0; k < c.ncomp; ++k) {
+      if (c.fam[k] < 0 || c.fam[k] >= kTermCount) return ctx->bad(e.ncomp + 1, "fam entry must be one of BLSQ_TERM_*");
+      if (c.cnt[k] < 1) return ctx->bad(e.ncomp + 2, "cnt entry must be at least 1");
+      total += (long)c.cnt[k] * MODEL_TERM_PARAMS[c.fam[k]];
+    }
+  }
+  if (c.B <= 0) return ctx->bad(e.B, "B must be positive");
+  if (c.reps <= 0) return ctx->bad(e.B + 1, "reps must be positive");
+  if (m <= 0) return ctx->bad(e.B + 2, "m must be positive");
+  if (comp) {
+    if (n < 1 || n > BLSQ_MODEL_MAX_N || total != n)
+      return ctx->bad(e.B + 3, "n must be the parameters of the components together (and at most BLSQ_MODEL_MAX_N)");
+  } else if (!model_n_fits(kModels[c.model], n)) {
+    return ctx->bad(e.B + 3, "n does not fit the model (or exceeds BLSQ_MODEL_MAX_N)");
+  }
+  bool any_fixed = false;
+  if (!c.pmap && !e.needs_pmap) {
+    if (nf != n) return ctx->bad(e.nf, "nf must equal n without a pmap");
+  } else {
+    if (nf < 1 || nf > n) return ctx->bad(e.nf, "nf must be in 1 .. n");
+    if (!c.pmap) return ctx->bad(e.nf + 1, "pmap is NULL");
+    bool used[BLSQ_MODEL_MAX_N] = {};
+    for (int j = 0; j < n; ++j) {
+      if (c.pmap[j] < -1 || c.pmap[j] >= nf) return ctx->bad(e.pmap_entry, "pmap entry outside -1 .. nf - 1");
+      if (c.pmap[j] < 0) any_fixed = true;
+      else used[c.pmap[j]] = true;
+    }
+    for (int k = 0; k < nf; ++k)
+      if (!used[k]) return ctx->bad(e.pmap_entry + 1, "pmap leaves a variable k < nf unused");
+  }
+  const long coords = comp ? 1 : kModels[c.model].coords;
+  if (!c.t) return ctx->bad(e.t, "t is NULL");
+  if (c.sampling == BLSQ_SAMPLE_BIN) {
+    if (c.t_stride != 0 && c.t_stride != 2 * coords * m)
+      return ctx->bad(e.t + 1, "t_stride must be 0 or 2 * coords * m with BLSQ_SAMPLE_BIN");
+  } else if (c.t_stride != 0 && c.t_stride != coords * m) {
+    return ctx->bad(e.t + 1, "t_stride must be 0 or coords * m");
+  }
+  if (c.est == BLSQ_EST_POISSON && !c.y) return ctx->bad(e.t + 2, "y is NULL: the Poisson estimator needs the counts");
+  if (c.nan_policy == BLSQ_NAN_OMIT && !c.y)
+    return ctx->bad(e.t + 2, "y is NULL: BLSQ_NAN_OMIT reads the missing points from it");
+  if (c.est == BLSQ_EST_POISSON && c.w) return ctx->bad(e.t + 3, "w must be NULL with the Poisson estimator");
+  if (c.w && c.w_stride != 0 && c.w_stride != (long)m) return ctx->bad(e.t + 4, "w_stride must be 0 or m");
+  if (!c.X) return ctx->bad(e.t + 5, "X is NULL (the parameter vectors)");
+  if (any_fixed && !c.Pfix) return ctx->bad(e.Pfix, "Pfix is NULL although pmap holds a parameter fixed");
+  if (!c.f && !c.J) return ctx->bad(e.f, "f and J are both NULL");
+  if (c.J && c.reps != 1) return ctx->bad(e.f + 1, "J requires reps == 1");
+  HIPCHK(ctx, hipSetDevice(ctx->device));
+  return ctx->run(K_MODEL_EVAL, e.label, [&] { return launch_model_eval(c, ctx->stream); });
+}
+
+}  // namespace
+
 extern "C" int blsq_model_eval_dev(blsq_ctx* ctx, int model, int B, int reps, int m, int n, const double* dt,
                                    long t_stride, const double* dy, const double* dw, long w_stride, const double* dP,
                                    double* df, double* dJ, const int32_t* dmask) {
-  if (!ctx) return -1;
-  if (model < 0 || model >= kModelCount) return ctx->bad(2, "model must be one of BLSQ_MODEL_*");
-  const ModelRow& r = kModels[model];
-  if (B <= 0) return ctx->bad(3, "B must be positive");
-  if (reps <= 0) return ctx->bad(4, "reps must be positive");
-  if (m <= 0) return ctx->bad(5, "m must be positive");
-  if (!model_n_fits(r, n)) return ctx->bad(6, "n does not fit the model (or exceeds BLSQ_MODEL_MAX_N)");
-  if (!dt) return ctx->bad(7, "t is NULL");
-  if (t_stride != 0 && t_stride != (long)r.coords * m) return ctx->bad(8, "t_stride must be 0 or coords * m");
-  if (dw && w_stride != 0 && w_stride != (long)m) return ctx->bad(11, "w_stride must be 0 or m");
-  if (!dP) return ctx->bad(12, "P is NULL");
-  if (!df && !dJ) return ctx->bad(13, "f and J are both NULL");
-  if (dJ && reps != 1) return ctx->bad(14, "J requires reps == 1");
-  HIPCHK(ctx, hipSetDevice(ctx->device));
-  return ctx->run(K_MODEL_EVAL, "launch_model_eval", [&] {
-    return launch_model_eval(model, B, reps, m, n, dt, t_stride, dy, dw, w_stride, dP, df, dJ, dmask, ctx->stream);
-  });
+  return model_eval_checked(ctx, kEvalDev, {BLSQ_EST_LSE, BLSQ_SAMPLE_POINT, BLSQ_NAN_PROPAGATE, model, 0, nullptr,
+                                            nullptr, B, reps, m, n, n, nullptr, dt, t_stride, dy, dw, w_stride, dP,
+                                            nullptr, df, dJ, dmask});
 }
 
 extern "C" int blsq_model_eval_map_dev(blsq_ctx* ctx, int model, int B, int reps, int m, int n, int nf,
                                        const int32_t* pmap, const double* dt, long t_stride, const double* dy,
                                        const double* dw, long w_stride, const double* dX, const double* dPfix,
                                        double* df, double* dJ, const int32_t* dmask) {
-  if (!ctx) return -1;
-  if (model < 0 || model >= kModelCount) return ctx->bad(2, "model must be one of BLSQ_MODEL_*");
-  const ModelRow& r = kModels[model];
-  if (B <= 0) return ctx->bad(3, "B must be positive");
-  if (reps <= 0) return ctx->bad(4, "reps must be positive");
-  if (m <= 0) return ctx->bad(5, "m must be positive");
-  if (!model_n_fits(r, n)) return ctx->bad(6, "n does not fit the model (or exceeds BLSQ_MODEL_MAX_N)");
-  if (nf < 1 || nf > n) return ctx->bad(7, "nf must be in 1 .. n");
-  if (!pmap) return ctx->bad(8, "pmap is NULL");
-  bool used[BLSQ_MODEL_MAX_N] = {};
-  bool any_fixed = false;
-  for (int j = 0; j < n; ++j) {
-    if (pmap[j] < -1 || pmap[j] >= nf) return ctx->bad(19, "pmap entry outside -1 .. nf - 1");
-    if (pmap[j] < 0) any_fixed = true;
-    else used[pmap[j]] = true;
-  }
-  for (int k = 0; k < nf; ++k)
-    if (!used[k]) return ctx->bad(20, "pmap leaves a variable k < nf unused");
-  if (!dt) return ctx->bad(9, "t is NULL");
-  if (t_stride != 0 && t_stride != (long)r.coords * m) return ctx->bad(10, "t_stride must be 0 or coords * m");
-  if (dw && w_stride != 0 && w_stride != (long)m) return ctx->bad(13, "w_stride must be 0 or m");
-  if (!dX) return ctx->bad(14, "X is NULL");
-  if (any_fixed && !dPfix) return ctx->bad(15, "Pfix is NULL although pmap holds a parameter fixed");
-  if (!df && !dJ) return ctx->bad(16, "f and J are both NULL");
-  if (dJ && reps != 1) return ctx->bad(17, "J requires reps == 1");
-  HIPCHK(ctx, hipSetDevice(ctx->device));
-  return ctx->run(K_MODEL_EVAL, "launch_model_eval_map", [&] {
-    return launch_model_eval_map(model, B, reps, m, n, nf, pmap, dt, t_stride, dy, dw, w_stride, dX, dPfix, df, dJ,
-                                 dmask, ctx->stream);
-  });
-}
-
-extern "C" int blsq_term_count(void) { return kTermCount; }
-
-extern "C" int blsq_term_info(int term, const char** name, int* n_per_term) {
-  if (term < 0 || term >= kTermCount) return -1;
-  if (name) *name = kTerms[term].name;
-  if (n_per_term) *n_per_term = kTerms[term].n_per_term;
-  return 0;
+  return model_eval_checked(ctx, kEvalMap, {BLSQ_EST_LSE, BLSQ_SAMPLE_POINT, BLSQ_NAN_PROPAGATE, model, 0, nullptr,
+                                            nullptr, B, reps, m, n, nf, pmap, dt, t_stride, dy, dw, w_stride, dX,
+                                            dPfix, df, dJ, dmask});
 }
 
 extern "C" int blsq_model_eval_comp_dev(blsq_ctx* ctx, int ncomp, const int32_t* fam, const int32_t* cnt, int B,
@@ -120,132 +171,9 @@ extern "C" int blsq_model_eval_comp_dev(blsq_ctx* ctx, int ncomp, const int32_t*
                                         long t_stride, const double* dy, const double* dw, long w_stride,
                                         const double* dX, const double* dPfix, double* df, double* dJ,
                                         const int32_t* dmask) {
-  if (!ctx) return -1;
-  if (ncomp < 1 || ncomp > BLSQ_MODEL_MAX_COMP) return ctx->bad(2, "ncomp must be in 1 .. BLSQ_MODEL_MAX_COMP");
-  if (!fam) return ctx->bad(3, "fam is NULL");
-  if (!cnt) return ctx->bad(4, "cnt is NULL");
-  long total = 0;
-  for (int c = 0; c < ncomp; ++c) {
-    if (fam[c] < 0 || fam[c] >= kTermCount) return ctx->bad(3, "fam entry must be one of BLSQ_TERM_*");
-    if (cnt[c] < 1) return ctx->bad(4, "cnt entry must be at least 1");
-    total += (long)cnt[c] * kTerms[fam[c]].n_per_term;
-  }
-  if (B <= 0) return ctx->bad(5, "B must be positive");
-  if (reps <= 0) return ctx->bad(6, "reps must be positive");
-  if (m <= 0) return ctx->bad(7, "m must be positive");
-  if (n < 1 || n > BLSQ_MODEL_MAX_N || total != n)
-    return ctx->bad(8, "n must be the parameters of the components together (and at most BLSQ_MODEL_MAX_N)");
-  bool any_fixed = false;
-  if (!pmap) {
-    if (nf != n) return ctx->bad(9, "nf must equal n without a pmap");
-  } else {
-    if (nf < 1 || nf > n) return ctx->bad(9, "nf must be in 1 .. n");
-    bool used[BLSQ_MODEL_MAX_N] = {};
-    for (int j = 0; j < n; ++j) {
-      if (pmap[j] < -1 || pmap[j] >= nf) return ctx->bad(21, "pmap entry outside -1 .. nf - 1");
-      if (pmap[j] < 0) any_fixed = true;
-      else used[pmap[j]] = true;
-    }
-    for (int k = 0; k < nf; ++k)
-      if (!used[k]) return ctx->bad(22, "pmap leaves a variable k < nf unused");
-  }
-  if (!dt) return ctx->bad(11, "t is NULL");
-  if (t_stride != 0 && t_stride != (long)m) return ctx->bad(12, "t_stride must be 0 or m");
-  if (dw && w_stride != 0 && w_stride != (long)m) return ctx->bad(15, "w_stride must be 0 or m");
-  if (!dX) return ctx->bad(16, "X is NULL");
-  if (any_fixed && !dPfix) return ctx->bad(17, "Pfix is NULL although pmap holds a parameter fixed");
-  if (!df && !dJ) return ctx->bad(18, "f and J are both NULL");
-  if (dJ && reps != 1) return ctx->bad(19, "J requires reps == 1");
-  HIPCHK(ctx, hipSetDevice(ctx->device));
-  return ctx->run(K_MODEL_EVAL, "launch_model_eval_comp", [&] {
-    return launch_model_eval_comp(ncomp, fam, cnt, B, reps, m, n, nf, pmap, dt, t_stride, dy, dw, w_stride, dX, dPfix,
-                                  df, dJ, dmask, ctx->stream);
-  });
-}
-
-// One entry for every instance, with the estimator and the sampling (7n): the checks of the three entries
-// above, then the launch of the entry it stands in for.  blsq_model_eval_est_dev numbers its arguments from est = 2,
-// model = 3; blsq_model_eval_bin_dev has `sampling` in between, so every later argument is one further on (sh = 1);
-// blsq_model_eval_nan_dev has `nan_policy` after that (sh = 2).
-static int model_eval_checked(blsq_ctx* ctx, const char* what, int sh, int est, int sampling, int nan_policy, int model,
-                              int ncomp,
-                              const int32_t* fam, const int32_t* cnt, int B, int reps, int m, int n, int nf,
-                              const int32_t* pmap, const double* dt, long t_stride, const double* dy, const double* dw,
-                              long w_stride, const double* dX, const double* dPfix, double* df, double* dJ,
-                              const int32_t* dmask) {
-  if (!ctx) return -1;
-  if (est != BLSQ_EST_LSE && est != BLSQ_EST_POISSON) return ctx->bad(2, "est must be one of BLSQ_EST_*");
-  if (sampling != BLSQ_SAMPLE_POINT && sampling != BLSQ_SAMPLE_BIN)
-    return ctx->bad(3, "sampling must be one of BLSQ_SAMPLE_*");
-  if (nan_policy != BLSQ_NAN_PROPAGATE && nan_policy != BLSQ_NAN_OMIT)
-    return ctx->bad(4, "nan_policy must be one of BLSQ_NAN_*");
-  if (model < -1 || model >= kModelCount)
-    return ctx->bad(3 + sh, "model must be one of BLSQ_MODEL_*, or -1 for a composite");
-  const bool comp = model < 0;
-  long total = 0;
-  if (!comp) {
-    if (ncomp != 0) return ctx->bad(4 + sh, "ncomp must be 0 with a named model");
-  } else {
-    if (ncomp < 1 || ncomp > BLSQ_MODEL_MAX_COMP) return ctx->bad(4 + sh, "ncomp must be in 1 .. BLSQ_MODEL_MAX_COMP");
-    if (!fam) return ctx->bad(5 + sh, "fam is NULL");
-    if (!cnt) return ctx->bad(6 + sh, "cnt is NULL");
-    for (int c = 0; c < ncomp; ++c) {
-      if (fam[c] < 0 || fam[c] >= kTermCount) return ctx->bad(5 + sh, "fam entry must be one of BLSQ_TERM_*");
-      if (cnt[c] < 1) return ctx->bad(6 + sh, "cnt entry must be at least 1");
-      total += (long)cnt[c] * kTerms[fam[c]].n_per_term;
-    }
-  }
-  if (B <= 0) return ctx->bad(7 + sh, "B must be positive");
-  if (reps <= 0) return ctx->bad(8 + sh, "reps must be positive");
-  if (m <= 0) return ctx->bad(9 + sh, "m must be positive");
-  if (comp) {
-    if (n < 1 || n > BLSQ_MODEL_MAX_N || total != n)
-      return ctx->bad(10 + sh, "n must be the parameters of the components together (and at most BLSQ_MODEL_MAX_N)");
-  } else if (!model_n_fits(kModels[model], n)) {
-    return ctx->bad(10 + sh, "n does not fit the model (or exceeds BLSQ_MODEL_MAX_N)");
-  }
-  bool any_fixed = false;
-  if (!pmap) {
-    if (nf != n) return ctx->bad(11 + sh, "nf must equal n without a pmap");
-  } else {
-    if (nf < 1 || nf > n) return ctx->bad(11 + sh, "nf must be in 1 .. n");
-    bool used[BLSQ_MODEL_MAX_N] = {};
-    for (int j = 0; j < n; ++j) {
-      if (pmap[j] < -1 || pmap[j] >= nf) return ctx->bad(23 + sh, "pmap entry outside -1 .. nf - 1");
-      if (pmap[j] < 0) any_fixed = true;
-      else used[pmap[j]] = true;
-    }
-    for (int k = 0; k < nf; ++k)
-      if (!used[k]) return ctx->bad(24 + sh, "pmap leaves a variable k < nf unused");
-  }
-  const long coords = comp ? 1 : kModels[model].coords;
-  if (!dt) return ctx->bad(13 + sh, "t is NULL");
-  if (sampling == BLSQ_SAMPLE_BIN) {
-    if (t_stride != 0 && t_stride != 2 * coords * m)
-      return ctx->bad(14 + sh, "t_stride must be 0 or 2 * coords * m with BLSQ_SAMPLE_BIN");
-  } else if (t_stride != 0 && t_stride != coords * m) {
-    return ctx->bad(14 + sh, "t_stride must be 0 or coords * m");
-  }
-  if (est == BLSQ_EST_POISSON && !dy) return ctx->bad(15 + sh, "y is NULL: the Poisson estimator needs the counts");
-  if (nan_policy == BLSQ_NAN_OMIT && !dy)
-    return ctx->bad(15 + sh, "y is NULL: BLSQ_NAN_OMIT reads the missing points from it");
-  if (est == BLSQ_EST_POISSON && dw) return ctx->bad(16 + sh, "w must be NULL with the Poisson estimator");
-  if (dw && w_stride != 0 && w_stride != (long)m) return ctx->bad(17 + sh, "w_stride must be 0 or m");
-  if (!dX) return ctx->bad(18 + sh, "X is NULL");
-  if (any_fixed && !dPfix) return ctx->bad(19 + sh, "Pfix is NULL although pmap holds a parameter fixed");
-  if (!df && !dJ) return ctx->bad(20 + sh, "f and J are both NULL");
-  if (dJ && reps != 1) return ctx->bad(21 + sh, "J requires reps == 1");
-  HIPCHK(ctx, hipSetDevice(ctx->device));
-  return ctx->run(K_MODEL_EVAL, what, [&] {
-    if (comp)
-      return launch_model_eval_comp(ncomp, fam, cnt, B, reps, m, n, nf, pmap, dt, t_stride, dy, dw, w_stride, dX, dPfix,
-                                    df, dJ, dmask, ctx->stream, est, sampling, nan_policy);
-    if (pmap)
-      return launch_model_eval_map(model, B, reps, m, n, nf, pmap, dt, t_stride, dy, dw, w_stride, dX, dPfix, df, dJ,
-                                   dmask, ctx->stream, est, sampling, nan_policy);
-    return launch_model_eval(model, B, reps, m, n, dt, t_stride, dy, dw, w_stride, dX, df, dJ, dmask, ctx->stream, est,
-                             sampling, nan_policy);
-  });
+  return model_eval_checked(ctx, kEvalComp, {BLSQ_EST_LSE, BLSQ_SAMPLE_POINT, BLSQ_NAN_PROPAGATE, -1, ncomp, fam, cnt,
+                                             B, reps, m, n, nf, pmap, dt, t_stride, dy, dw, w_stride, dX, dPfix, df,
+                                             dJ, dmask});
 }
 
 extern "C" int blsq_model_eval_est_dev(blsq_ctx* ctx, int est, int model, int ncomp, const int32_t* fam,
@@ -253,8 +181,8 @@ extern "C" int blsq_model_eval_est_dev(blsq_ctx* ctx, int est, int model, int nc
                                        const double* dt, long t_stride, const double* dy, const double* dw,
                                        long w_stride, const double* dX, const double* dPfix, double* df, double* dJ,
                                        const int32_t* dmask) {
-  return model_eval_checked(ctx, "launch_model_eval_est", 0, est, BLSQ_SAMPLE_POINT, BLSQ_NAN_PROPAGATE, model, ncomp,
-                            fam, cnt, B, reps, m, n, nf, pmap, dt, t_stride, dy, dw, w_stride, dX, dPfix, df, dJ, dmask);
+  return model_eval_checked(ctx, kEvalEst, {est, BLSQ_SAMPLE_POINT, BLSQ_NAN_PROPAGATE, model, ncomp, fam, cnt, B, reps,
+                                            m, n, nf, pmap, dt, t_stride, dy, dw, w_stride, dX, dPfix, df, dJ, dmask});
 }
 
 extern "C" int blsq_model_eval_bin_dev(blsq_ctx* ctx, int est, int sampling, int model, int ncomp, const int32_t* fam,
@@ -262,8 +190,8 @@ extern "C" int blsq_model_eval_bin_dev(blsq_ctx* ctx, int est, int sampling, int
                                        const double* dt, long t_stride, const double* dy, const double* dw,
                                        long w_stride, const double* dX, const double* dPfix, double* df, double* dJ,
                                        const int32_t* dmask) {
-  return model_eval_checked(ctx, "launch_model_eval_bin", 1, est, sampling, BLSQ_NAN_PROPAGATE, model, ncomp, fam, cnt,
-                            B, reps, m, n, nf, pmap, dt, t_stride, dy, dw, w_stride, dX, dPfix, df, dJ, dmask);
+  return model_eval_checked(ctx, kEvalBin, {est, sampling, BLSQ_NAN_PROPAGATE, model, ncomp, fam, cnt, B, reps, m, n, nf,
+                                            pmap, dt, t_stride, dy, dw, w_stride, dX, dPfix, df, dJ, dmask});
 }
 
 extern "C" int blsq_model_eval_nan_dev(blsq_ctx* ctx, int est, int sampling, int nan_policy, int model, int ncomp,
@@ -271,6 +199,6 @@ extern "C" int blsq_model_eval_nan_dev(blsq_ctx* ctx, int est, int sampling, int
                                        const int32_t* pmap, const double* dt, long t_stride, const double* dy,
                                        const double* dw, long w_stride, const double* dX, const double* dPfix,
                                        double* df, double* dJ, const int32_t* dmask) {
-  return model_eval_checked(ctx, "launch_model_eval_nan", 2, est, sampling, nan_policy, model, ncomp, fam, cnt, B, reps,
-                            m, n, nf, pmap, dt, t_stride, dy, dw, w_stride, dX, dPfix, df, dJ, dmask);
+  return model_eval_checked(ctx, kEvalNan, {est, sampling, nan_policy, model, ncomp, fam, cnt, B, reps, m, n, nf, pmap,
+                                            dt, t_stride, dy, dw, w_stride, dX, dPfix, df, dJ, dmask});
 }

@@ -559,140 +559,89 @@ __global__ __launch_bounds__(256) void model_eval_kernel(
   }
 }
 
-// The launch of instance <MODEL, MAPPED, est == BLSQ_EST_POISSON, sampling == BLSQ_SAMPLE_BIN, OMIT>.
-template <int MODEL, bool MAPPED, bool OMIT, class Args>
-static void launch_model_flags(int est, int sampling, dim3 g, dim3 blk, size_t lds, hipStream_t s, Args& A) {
-  if (sampling == BLSQ_SAMPLE_BIN) {
-    if (est == BLSQ_EST_POISSON)
-      hipLaunchKernelGGL((model_eval_kernel<MODEL, MAPPED, true, true, OMIT>), g, blk, lds, s, A);
-    else hipLaunchKernelGGL((model_eval_kernel<MODEL, MAPPED, false, true, OMIT>), g, blk, lds, s, A);
-  } else if (est == BLSQ_EST_POISSON) {
-    hipLaunchKernelGGL((model_eval_kernel<MODEL, MAPPED, true, false, OMIT>), g, blk, lds, s, A);
-  } else {
-    hipLaunchKernelGGL((model_eval_kernel<MODEL, MAPPED, false, false, OMIT>), g, blk, lds, s, A);
-  }
+// The launch of instance <MODEL, MAPPED> with the flags `inst`: POISSON | BINNED << 1 | OMIT << 2.  The eight kernels
+// take the same arguments: the part of `all` that the instance has.
+template <int MODEL, bool MAPPED>
+static void launch_model_instance(int inst, dim3 g, dim3 blk, size_t lds, hipStream_t s,
+                                  const CompArgs<ModelMapArgs>& all) {
+  using Args = typename ModelArgsOf<MODEL == MODEL_COMPOSITE, MAPPED>::type;
+  static void (*const kernels[8])(Args) = {
+      model_eval_kernel<MODEL, MAPPED, false, false, false>, model_eval_kernel<MODEL, MAPPED, true, false, false>,
+      model_eval_kernel<MODEL, MAPPED, false, true, false>,  model_eval_kernel<MODEL, MAPPED, true, true, false>,
+      model_eval_kernel<MODEL, MAPPED, false, false, true>,  model_eval_kernel<MODEL, MAPPED, true, false, true>,
+      model_eval_kernel<MODEL, MAPPED, false, true, true>,   model_eval_kernel<MODEL, MAPPED, true, true, true>};
+  Args A;
+  static_cast<typename ModelArgsOf<false, MAPPED>::type&>(A) = all;
+  if constexpr (MODEL == MODEL_COMPOSITE) A.tab = all.tab;
+  hipLaunchKernelGGL(kernels[inst], g, blk, lds, s, A);
 }
 
-// ... with nan_policy == BLSQ_NAN_OMIT as the last flag.
-template <int MODEL, bool MAPPED, class Args>
-static void launch_model_est(int est, int sampling, int nan_policy, dim3 g, dim3 blk, size_t lds, hipStream_t s,
-                             Args& A) {
-  if (nan_policy == BLSQ_NAN_OMIT) launch_model_flags<MODEL, MAPPED, true>(est, sampling, g, blk, lds, s, A);
-  else launch_model_flags<MODEL, MAPPED, false>(est, sampling, g, blk, lds, s, A);
-}
-
-// Waves per workgroup (4 / 2 / 1) whose LDS (wave_bytes each) fits the grant, and the launch of instance <.., MAPPED, ..>.
-// model == MODEL_COMPOSITE: the composite instance (A then carries the table).  The Poisson instances need y and take
-// no weights; the bin-integrated ones read 2 coords rows of t; the omitting ones need y.
-template <bool MAPPED, class Args>
-static hipError_t launch_model_instance(int model, int est, int sampling, int nan_policy, Args& A, size_t wave_bytes,
-                                        hipStream_t s) {
-  if (est != BLSQ_EST_LSE && est != BLSQ_EST_POISSON) return hipErrorInvalidValue;
-  if (sampling != BLSQ_SAMPLE_POINT && sampling != BLSQ_SAMPLE_BIN) return hipErrorInvalidValue;
-  if (nan_policy != BLSQ_NAN_PROPAGATE && nan_policy != BLSQ_NAN_OMIT) return hipErrorInvalidValue;
-  if (est == BLSQ_EST_POISSON && (!A.y || A.w)) return hipErrorInvalidValue;
-  if (nan_policy == BLSQ_NAN_OMIT && !A.y) return hipErrorInvalidValue;
-  int wpb = 4;
-  while (wpb > 1 && wave_bytes * wpb > (size_t)MODEL_LDS_BYTES) wpb >>= 1;
-  if (wave_bytes * wpb > (size_t)MODEL_LDS_BYTES) return hipErrorInvalidValue;
-  const long grid = (A.items + wpb - 1) / wpb;
-  if (grid <= 0 || grid > 0x7fffffffL) return hipErrorInvalidValue;
-  const dim3 g((unsigned)grid), blk(64 * wpb);
-  const size_t lds = wave_bytes * wpb;
-  if constexpr (std::is_same<Args, typename ModelArgsOf<true, MAPPED>::type>::value) {
-    if (model != MODEL_COMPOSITE) return hipErrorInvalidValue;
-    launch_model_est<MODEL_COMPOSITE, MAPPED>(est, sampling, nan_policy, g, blk, lds, s, A);
-  } else switch (model) {
-    case BLSQ_MODEL_POLY:
-      launch_model_est<BLSQ_MODEL_POLY, MAPPED>(est, sampling, nan_policy, g, blk, lds, s, A); break;
-    case BLSQ_MODEL_EXP_SUM:
-      launch_model_est<BLSQ_MODEL_EXP_SUM, MAPPED>(est, sampling, nan_policy, g, blk, lds, s, A); break;
-    case BLSQ_MODEL_GAUSS_SUM:
-      launch_model_est<BLSQ_MODEL_GAUSS_SUM, MAPPED>(est, sampling, nan_policy, g, blk, lds, s, A); break;
-    case BLSQ_MODEL_LORENTZ_SUM:
-      launch_model_est<BLSQ_MODEL_LORENTZ_SUM, MAPPED>(est, sampling, nan_policy, g, blk, lds, s, A); break;
-    case BLSQ_MODEL_GAUSS2D:
-      launch_model_est<BLSQ_MODEL_GAUSS2D, MAPPED>(est, sampling, nan_policy, g, blk, lds, s, A); break;
+template <bool MAPPED>
+static hipError_t launch_model_kind(int model, int inst, dim3 g, dim3 blk, size_t lds, hipStream_t s,
+                                    const CompArgs<ModelMapArgs>& all) {
+  switch (model) {
+    case MODEL_COMPOSITE: launch_model_instance<MODEL_COMPOSITE, MAPPED>(inst, g, blk, lds, s, all); break;
+    case BLSQ_MODEL_POLY: launch_model_instance<BLSQ_MODEL_POLY, MAPPED>(inst, g, blk, lds, s, all); break;
+    case BLSQ_MODEL_EXP_SUM: launch_model_instance<BLSQ_MODEL_EXP_SUM, MAPPED>(inst, g, blk, lds, s, all); break;
+    case BLSQ_MODEL_GAUSS_SUM: launch_model_instance<BLSQ_MODEL_GAUSS_SUM, MAPPED>(inst, g, blk, lds, s, all); break;
+    case BLSQ_MODEL_LORENTZ_SUM: launch_model_instance<BLSQ_MODEL_LORENTZ_SUM, MAPPED>(inst, g, blk, lds, s, all); break;
+    case BLSQ_MODEL_GAUSS2D: launch_model_instance<BLSQ_MODEL_GAUSS2D, MAPPED>(inst, g, blk, lds, s, all); break;
     default: return hipErrorInvalidValue;
   }
   return hipGetLastError();
 }
 
-static void fill_model_args(ModelArgs& A, int B, int reps, int m, int n, const double* t, long t_stride, const double* y,
-                            const double* w, long w_stride, const double* P, double* f, double* J, const int* mask) {
-  A.m = m; A.n = n; A.reps = reps; A.tiles = (m + MODEL_ROWS - 1) / MODEL_ROWS;
-  A.items = (long)B * reps * A.tiles;
-  A.t = t; A.t_stride = t_stride; A.y = y; A.w = w; A.w_stride = w_stride; A.P = P; A.f = f; A.J = J; A.mask = mask;
-}
-
-// nf, Pfix and pm[] of a mapped launch from the host's pmap [n]; false where n, nf or an entry is out of range.
-static bool fill_model_map(ModelMapArgs& A, int n, int nf, const int* pmap, const double* Pfix) {
-  if (n < 1 || n > MODEL_ROWS || nf < 1 || nf > n) return false;
-  A.nf = nf; A.Pfix = Pfix;
-  bool seen[MODEL_ROWS] = {};
-  for (int j = 0; j < MODEL_ROWS; ++j) {
-    int c = -1;
-    if (j < n && pmap[j] >= 0) {
-      if (pmap[j] >= nf) return false;
-      c = seen[pmap[j]] ? MODEL_ROWS + pmap[j] : pmap[j];
-      seen[pmap[j]] = true;
-    }
-    A.pm[j] = (signed char)c;
-  }
-  return true;
-}
-
-// LDS of one wave of a mapped launch: the parameter vector, and the tile at nf | 1 when J is wanted
-static size_t mapped_wave_bytes(int nf, bool want_J) {
-  return sizeof(double) * MODEL_ROWS * (size_t)(1 + (want_J ? (nf | 1) : 0));
-}
-
-hipError_t launch_model_eval(int model, int B, int reps, int m, int n, const double* t, long t_stride, const double* y,
-                             const double* w, long w_stride, const double* P, double* f, double* J, const int* mask,
-                             hipStream_t s, int est, int sampling, int nan_policy) {
-  ModelArgs A;
-  fill_model_args(A, B, reps, m, n, t, t_stride, y, w, w_stride, P, f, J, mask);
-  const size_t tile_bytes = J ? sizeof(double) * MODEL_ROWS * (size_t)(n | 1) : 0;
-  return launch_model_instance<false>(model, est, sampling, nan_policy, A, tile_bytes, s);
-}
-
-hipError_t launch_model_eval_map(int model, int B, int reps, int m, int n, int nf, const int* pmap, const double* t,
-                                 long t_stride, const double* y, const double* w, long w_stride, const double* X,
-                                 const double* Pfix, double* f, double* J, const int* mask, hipStream_t s,
-                                 int est, int sampling, int nan_policy) {
-  ModelMapArgs A;
-  fill_model_args(A, B, reps, m, n, t, t_stride, y, w, w_stride, X, f, J, mask);
-  if (!fill_model_map(A, n, nf, pmap, Pfix)) return hipErrorInvalidValue;
-  return launch_model_instance<true>(model, est, sampling, nan_policy, A, mapped_wave_bytes(nf, J != nullptr), s);
-}
-
-hipError_t launch_model_eval_comp(int ncomp, const int* fam, const int* cnt, int B, int reps, int m, int n, int nf,
-                                  const int* pmap, const double* t, long t_stride, const double* y, const double* w,
-                                  long w_stride, const double* X, const double* Pfix, double* f, double* J,
-                                  const int* mask, hipStream_t s, int est, int sampling, int nan_policy) {
-  if (ncomp < 1 || ncomp > BLSQ_MODEL_MAX_COMP || n < 1 || n > MODEL_ROWS) return hipErrorInvalidValue;
-  static const int per_term[BLSQ_TERM_POLY + 1] = {3, 3, 4, 2, 1};      // in the order of BLSQ_TERM_*
-  CompTable tab = {};
-  tab.ncomp = ncomp;
-  int total = 0;
-  for (int c = 0; c < ncomp; ++c) {
-    if (fam[c] < 0 || fam[c] > BLSQ_TERM_POLY || cnt[c] < 1 || cnt[c] > MODEL_ROWS) return hipErrorInvalidValue;
-    (c < 4 ? tab.lo : tab.hi) |= (unsigned long long)(fam[c] | (cnt[c] << 8)) << (16 * (c & 3));
-    total += cnt[c] * per_term[fam[c]];
-  }
-  if (total != n) return hipErrorInvalidValue;       // the kernel's offsets stay inside the n parameters and columns
-  if (!pmap) {
-    CompArgs<ModelArgs> A;
-    fill_model_args(A, B, reps, m, n, t, t_stride, y, w, w_stride, X, f, J, mask);
-    A.tab = tab;
-    const size_t tile_bytes = J ? sizeof(double) * MODEL_ROWS * (size_t)(n | 1) : 0;
-    return launch_model_instance<false>(MODEL_COMPOSITE, est, sampling, nan_policy, A, tile_bytes, s);
-  }
+hipError_t launch_model_eval(const ModelEvalCall& c, hipStream_t s) {
+  const bool poisson = c.est == BLSQ_EST_POISSON, bin = c.sampling == BLSQ_SAMPLE_BIN, omit = c.nan_policy == BLSQ_NAN_OMIT;
+  if ((!poisson && c.est != BLSQ_EST_LSE) || (!bin && c.sampling != BLSQ_SAMPLE_POINT) ||
+      (!omit && c.nan_policy != BLSQ_NAN_PROPAGATE))
+    return hipErrorInvalidValue;
+  if (((poisson || omit) && !c.y) || (poisson && c.w)) return hipErrorInvalidValue;   // both read y; Poisson takes no w
+  if (c.n < 1 || c.n > MODEL_ROWS) return hipErrorInvalidValue;
   CompArgs<ModelMapArgs> A;
-  fill_model_args(A, B, reps, m, n, t, t_stride, y, w, w_stride, X, f, J, mask);
-  if (!fill_model_map(A, n, nf, pmap, Pfix)) return hipErrorInvalidValue;
-  A.tab = tab;
-  return launch_model_instance<true>(MODEL_COMPOSITE, est, sampling, nan_policy, A, mapped_wave_bytes(nf, J != nullptr), s);
+  A.m = c.m; A.n = c.n; A.reps = c.reps; A.tiles = (c.m + MODEL_ROWS - 1) / MODEL_ROWS;
+  A.items = (long)c.B * c.reps * A.tiles;
+  A.t = c.t; A.t_stride = c.t_stride; A.y = c.y; A.w = c.w; A.w_stride = c.w_stride; A.P = c.X; A.f = c.f; A.J = c.J;
+  A.mask = c.mask;
+  int nc = c.n;                                      // columns of J
+  if (c.pmap) {                                      // nf, Pfix and pm[] from the host's pmap [n]
+    nc = A.nf = c.nf; A.Pfix = c.Pfix;
+    if (c.nf < 1 || c.nf > c.n) return hipErrorInvalidValue;
+    bool seen[MODEL_ROWS] = {};
+    for (int j = 0; j < MODEL_ROWS; ++j) {
+      int k = -1;
+      if (j < c.n && c.pmap[j] >= 0) {
+        if (c.pmap[j] >= c.nf) return hipErrorInvalidValue;
+        k = seen[c.pmap[j]] ? MODEL_ROWS + c.pmap[j] : c.pmap[j];
+        seen[c.pmap[j]] = true;
+      }
+      A.pm[j] = (signed char)k;
+    }
+  }
+  A.tab = {};
+  if (c.model == MODEL_COMPOSITE) {
+    if (c.ncomp < 1 || c.ncomp > BLSQ_MODEL_MAX_COMP) return hipErrorInvalidValue;
+    A.tab.ncomp = c.ncomp;
+    int total = 0;
+    for (int k = 0; k < c.ncomp; ++k) {
+      const int fam = c.fam[k], cnt = c.cnt[k];
+      if (fam < 0 || fam > BLSQ_TERM_POLY || cnt < 1 || cnt > MODEL_ROWS) return hipErrorInvalidValue;
+      (k < 4 ? A.tab.lo : A.tab.hi) |= (unsigned long long)(fam | (cnt << 8)) << (16 * (k & 3));
+      total += cnt * MODEL_TERM_PARAMS[fam];
+    }
+    if (total != c.n) return hipErrorInvalidValue;   // the kernel's offsets stay inside the n parameters and columns
+  }
+  // LDS of one wave: mapped, its parameter vector; with J, its tile at row stride nc | 1.  Waves per workgroup: 4 / 2 / 1
+  const size_t wave_bytes = sizeof(double) * MODEL_ROWS * (size_t)((c.pmap ? 1 : 0) + (c.J ? (nc | 1) : 0));
+  int wpb = 4;
+  while (wpb > 1 && wave_bytes * wpb > (size_t)MODEL_LDS_BYTES) wpb >>= 1;
+  if (wave_bytes * wpb > (size_t)MODEL_LDS_BYTES) return hipErrorInvalidValue;
+  const long grid = (A.items + wpb - 1) / wpb;
+  if (grid <= 0 || grid > 0x7fffffffL) return hipErrorInvalidValue;
+  const int inst = (int)poisson | (int)bin << 1 | (int)omit << 2;
+  const dim3 g((unsigned)grid), blk(64 * wpb);
+  return c.pmap ? launch_model_kind<true>(c.model, inst, g, blk, wave_bytes * wpb, s, A)
+                : launch_model_kind<false>(c.model, inst, g, blk, wave_bytes * wpb, s, A);
 }
 
 }  // namespace blsq
