@@ -133,6 +133,8 @@ SIGNATURES = {
     "blsq_model_eval_est_dev": _model_eval([C.c_int] * 2 + _COMP),                # est, model
     "blsq_model_eval_bin_dev": _model_eval([C.c_int] * 3 + _COMP),                # est, sampling, model
     "blsq_model_eval_nan_dev": _model_eval([C.c_int] * 4 + _COMP),                # est, sampling, nan_policy, model
+    # ... and after the table S, shared, t_sstride (B is G)
+    "blsq_model_eval_global_dev": _model_eval([C.c_int] * 4 + _COMP + [C.c_int, c_int32_p, C.c_long]),
 }
 
 _lib = None

@@ -1,4 +1,5 @@
-"""`curve_fit` and `curve_fit_batch`: scipy.optimize.curve_fit's model-fitting front end over this package's solvers.
+"""`curve_fit`, `curve_fit_batch` and `curve_fit_global`: scipy.optimize.curve_fit's model-fitting front end over this
+package's solvers.
 
 ``curve_fit`` follows scipy 1.15.3 ``_minpack_py.py::curve_fit`` line by line where its lines apply (the comments cite
 them); the solve is this package's ``least_squares`` and ``pcov`` is the pseudo-inverse covariance of the final Jacobian
@@ -15,9 +16,9 @@ from ._frontend import least_squares
 from ._batch import least_squares_batch
 from ._hostmath import prepare_bounds
 from . import _models
-from ._params import ParamMap
+from ._params import ParamMap, GlobalMap
 
-__all__ = ['curve_fit', 'curve_fit_batch']
+__all__ = ['curve_fit', 'curve_fit_batch', 'curve_fit_global']
 
 _COV_WARNING = 'Covariance of the parameters could not be estimated'
 
@@ -553,4 +554,194 @@ def curve_fit_batch(f, xdata, ydata, p0, sigma=None, absolute_sigma=False, bound
             pcov[b] = C
     if warn_cov:
         warnings.warn(_COV_WARNING, category=OptimizeWarning, stacklevel=2)
+    return popt, pcov, results
+
+
+GLOBAL_MAX_NV = 256                                      # BLSQ_GLOBAL_MAX_NV
+
+
+def curve_fit_global(f, xdata, ydata, p0, shared, sigma=None, absolute_sigma=False, bounds=(-np.inf, np.inf),
+                     method='trf', jac=None, driver='host', ctx=None, fixed=None, tied=None, estimator='lse',
+                     nan_policy=None, **kwargs):
+    """A global fit: S data sets of one model fitted together, with the parameters in `shared` common to all of them
+    (DESIGN.md 7p).  A decay measured at S wavelengths, a line scanned at S temperatures: the rates, the position and
+    the width have one value for the group, the amplitudes and baselines one per data set.
+
+    ydata : (S, m) for one global fit, or (G, S, m) for G independent global fits solved as one batch.
+    p0 : (..., S, n), required.  A shared parameter starts from data set 0 of its group.
+    shared : a boolean mask (n,) or a sequence of indices, the same for every group (``bounded_lsq.GlobalMap`` has the
+            rules: a shared index may not be fixed, a tied parameter is shared iff the one it follows is; an empty
+            `shared` is a ValueError that points to ``curve_fit_batch``).
+    f : a name, a composite spec or a ``CompositeModel`` of one coordinate on either driver (driver='device': residuals
+            and Jacobians of the whole group are evaluated on the GPU through blsq_model_eval_global_dev, the
+            Jacobian written into the group's column layout) — or a callable ``f(xdata, P) -> (G S, m)`` for the
+            parameters ``P`` (G S, n) of all data sets, row g S + s being data set s of group g; it goes through
+            ``GlobalMap.wrap_f`` / ``wrap_jac``, as the named model does with driver='host'.  'gauss2d' and
+            ``binned=True`` are ValueErrors.
+    xdata : (m,), (S, m) or (G, S, m); a callable receives (m,) or (G S, m).
+    sigma : None, a scalar, (m,), (S, m) or (G, S, m).  bounds : pair broadcastable to (G, S, n); the box of a shared
+            parameter is the intersection over the data sets of its group (empty: ValueError).
+    jac : None, '2-point', '3-point' (differences over the nv variables) or, with a callable `f`,
+            ``jac(xdata, P) -> (G S, m, n)``.
+    fixed, tied, estimator, nan_policy, method, driver, ctx, **kwargs (``loss=``, ``f_scale=``, tolerances,
+            ``leverage=``) : as ``curve_fit_batch``; `fixed` and `tied` act inside every data set.
+
+    The group is ONE dense problem of M = S m rows and nv = ns + S nl variables (ns shared slots, nl per data set; the
+    shared ones first, then the local ones of data set 0, 1, ...; nv <= 256, ValueError beyond).
+
+    Returns ``(popt (..., S, n), pcov (..., S, n, n), results)``.  A shared parameter comes back equal in all S rows.
+    ``pcov[g, s]`` is the (n, n) block of data set s of the group's covariance (``GlobalMap.expand_cov``); the variance
+    factor of a group is ``obj_value / (M - nv)`` — under 'omit' ``obj_value / (nobs_g - nv)`` with the points the
+    group kept — and a group without degrees of freedom gets inf under the ``OptimizeWarning``.  ``results[g]`` is the
+    group's ``OptimizeResult``: ``x`` (nv,), ``x_covariance`` (nv, nv) — the full matrix, with the terms between data
+    sets —, ``popt`` (S, n), ``global_map``, ``fun`` (M,), ``jac`` (M, nv), ``leverage`` (M,) with ``leverage=True``,
+    ``deviance`` under Poisson, ``nobs`` and ``omitted`` (S, m) under 'omit'.  A group that did not converge gives NaN
+    rows; with 'omit' a data set without a single point is a ValueError naming group and data set.
+    """
+    if kwargs.pop('binned', False):
+        raise ValueError("`binned=True` is not supported by `curve_fit_global`.")
+    ydata = np.asarray(ydata, float)
+    P0 = np.asarray(p0, float)
+    single = ydata.ndim == 2
+    if single:
+        ydata = ydata[np.newaxis]
+        if P0.ndim == 2:
+            P0 = P0[np.newaxis]
+    if ydata.ndim != 3:
+        raise ValueError("`ydata` must have shape (S, m) or (G, S, m).")
+    if ydata.size == 0:
+        raise ValueError("`ydata` must not be empty!")
+    G, S, m = ydata.shape
+    if P0.ndim != 3 or P0.shape[:2] != (G, S):
+        raise ValueError("`p0` must have shape (S, n) or (G, S, n) like `ydata`.")
+    n = P0.shape[2]
+    gm = GlobalMap(n, S, shared, fixed, tied)
+    if gm.nv > GLOBAL_MAX_NV:
+        raise ValueError("the group has nv = ns + S nl = %d + %d * %d = %d variables, more than %d."
+                         % (gm.ns, S, gm.nl, gm.nv, GLOBAL_MAX_NV))
+    M, nv = S * m, gm.nv
+    omitted = nobs = None
+    if nan_policy == 'raise':
+        if np.isnan(ydata).any():
+            raise ValueError("The input contains nan values")
+    elif nan_policy == 'omit':
+        omitted = np.isnan(ydata)
+        kept = np.sum(~omitted, axis=2)
+        if not kept.all():
+            g, s = (int(i) for i in np.argwhere(kept == 0)[0])
+            raise ValueError("nan_policy='omit': data set %d of group %d has no point left, every entry of its `ydata` "
+                             "is NaN." % (s, g))
+        nobs = kept.sum(axis=1).astype(np.int32)
+    elif nan_policy is not None:
+        raise ValueError("`nan_policy` must be None, 'raise' or 'omit', not %r." % (nan_policy,))
+    poisson = _check_poisson(estimator, sigma, ydata, omitted)
+    model = None
+    if isinstance(f, (str, _models.CompositeModel)):
+        model = _models.resolve(f)
+        model.terms(n)
+        _models._check_global(model, False, None)
+        if callable(jac):
+            raise ValueError("a callable `jac` cannot be combined with the built-in model '%s'." % model.name)
+        if jac is not None and jac not in ('2-point', '3-point'):
+            raise ValueError("`jac` must be None, '2-point' or '3-point' with a built-in model.")
+        if driver not in ('host', 'device'):
+            raise ValueError("`driver` must be 'host' or 'device'.")
+        if driver == 'host':
+            f = model.f
+            if jac is None:
+                jac = model.jac
+    elif jac is None:
+        jac = '2-point'
+    x_dev, gstride, sstride = _models.global_xdata(xdata, G, S, m)
+    # what a callable gets: (m,), or one row per data set of the batch
+    x_host = x_dev if not sstride else np.broadcast_to(x_dev, (G, S, m)).reshape(G * S, m)
+
+    Y = ydata.reshape(G, M)
+    transform = None
+    if sigma is not None:
+        sigma = np.asarray(sigma, float)
+        if sigma.size == 1:
+            transform = 1.0 / sigma
+        elif sigma.shape == (m,):
+            transform = np.tile(1.0 / sigma, S)
+        elif sigma.shape in ((S, m), (G, S, m)):
+            if omitted is not None and sigma.ndim == 3:
+                sigma = np.where(omitted, 1.0, sigma)            # never used at an omitted point
+            transform = (1.0 / sigma).reshape(sigma.shape[:-2] + (M,))
+        else:
+            raise ValueError("`sigma` has incorrect shape.")
+
+    if len(bounds) != 2:
+        raise ValueError("`bounds` must contain 2 elements.")
+    bounds = gm.reduce_bounds(np.broadcast_to(np.asarray(bounds[0], dtype=float), (G, S, n)),
+                              np.broadcast_to(np.asarray(bounds[1], dtype=float), (G, S, n)))
+    x_start = gm.reduce_x(P0)
+    if callable(f):
+        f = gm.wrap_f(f, P0)
+    if callable(jac):
+        jac = gm.wrap_jac(jac, P0)
+
+    if model is not None and driver == 'device':
+        func = _models.DeviceFit(model.name, n, x_dev, ydata, sigma, Pfix=P0, global_map=gm,
+                                 **({'estimator': estimator} if poisson else {}),
+                                 **({'nan_policy': 'omit'} if omitted is not None else {}))
+    elif poisson:                                # (after the map: c multiplies the scattered, summed columns)
+        if callable(jac):
+            jac = _models.poisson_jacobian(f, jac, Y)
+        f_res = _models.poisson_residual(f, Y)
+
+        def func(X):
+            return np.asarray(f_res(x_host, X), float)
+    elif transform is None:
+        def func(X):
+            return np.asarray(f(x_host, X), float) - Y
+    else:
+        def func(X):
+            return transform * (np.asarray(f(x_host, X), float) - Y)
+
+    if callable(jac):
+        user_jac = jac
+        tj = None if transform is None else np.broadcast_to(transform, (G, M))[:, :, np.newaxis]
+
+        def jac(X):                                                        # noqa: F811
+            J = np.asarray(user_jac(x_host, X), float)
+            return J if tj is None else tj * J
+
+    if omitted is not None and callable(func):   # outermost: after sigma, the Poisson transform and the map
+        func = _models.omit_residual(func, Y)
+        if callable(jac):
+            jac = _models.omit_jacobian(jac, Y)
+
+    if 'args' in kwargs:
+        raise ValueError("'args' is not a supported keyword argument.")
+    if 'max_nfev' not in kwargs:
+        kwargs['max_nfev'] = kwargs.pop('maxfev', None)
+
+    scale_on_gpu = (not absolute_sigma) and M > nv
+    results = least_squares_batch(func, x_start, jac, bounds=bounds, method=method, driver=driver, ctx=ctx,
+                                  covariance='pinv', _variance_scale=scale_on_gpu,
+                                  **({'_nobs': nobs} if nobs is not None else {}), **kwargs)
+    popt = np.full((G, S, n), np.nan)
+    pcov = np.full((G, S, n, n), np.nan)
+    warn_cov = False
+    for g, r in enumerate(results):
+        r.global_map = gm
+        r.popt = gm.expand_x(r.x, P0[g])
+        if nobs is not None:
+            r.nobs, r.omitted = int(nobs[g]), omitted[g].copy()
+        if poisson:
+            r.deviance = float(np.dot(r.fun, r.fun))
+        if not r.success:
+            continue
+        C = r.x_covariance
+        popt[g] = r.popt
+        if (C is None or np.isnan(C).any() or (not absolute_sigma and (M if nobs is None else nobs[g]) <= nv)):
+            pcov[g] = np.inf
+            warn_cov = True
+        else:
+            pcov[g] = gm.expand_cov(C)
+    if warn_cov:
+        warnings.warn(_COV_WARNING, category=OptimizeWarning, stacklevel=2)
+    if single:
+        return popt[0], pcov[0], results
     return popt, pcov, results

@@ -56,6 +56,11 @@ looked at.  ``omit_residual`` / ``omit_jacobian`` ARE the definition (``np.where
 outermost) and the route of ``driver='host'`` and of callables; the OMIT kernel instances produce the same zeros without
 evaluating the row.  ``count_observed`` gives the points each problem keeps and ``pad_ragged`` turns data sets of
 unequal length into the NaN-padded batch the policy takes.
+
+Global fits (``global_map=``; blsq_model_eval_global_dev).  With a ``bounded_lsq.GlobalMap`` a
+``DeviceModel`` / ``DeviceFit`` evaluates G groups of S data sets, a group being one problem of S m rows over the
+nv = ns + S nl variables of the map; ``GlobalMap`` IS the definition of the layout and the kernel follows it bit for bit.
+One coordinate and point sampling only.
 """
 import re
 
@@ -830,6 +835,41 @@ def pad_ragged(xs, ys):
     return xdata, ydata
 
 
+def _check_global(model, binned, param_map):
+    """What a global fit does not take, as ValueErrors."""
+    if binned:
+        raise ValueError("`binned=True` is not supported in a global fit.")
+    if model.coords != 1:
+        raise ValueError("model '%s' has %d coordinates: a global fit takes the models of one coordinate."
+                         % (model.name, model.coords))
+    if param_map is not None:
+        raise ValueError("`param_map` must be None with `global_map`: the GlobalMap carries its ParamMap.")
+
+
+def global_xdata(xdata, G, S, m):
+    """`xdata` of a global fit — (m,) shared, (S, m) per data set or (G, S, m) per group and data set — as a contiguous
+    float64 array with its group stride and data-set stride in doubles; ValueError for another shape."""
+    x = np.ascontiguousarray(xdata, dtype=np.float64)
+    if x.shape == (G, S, m):
+        return x, S * m, m
+    if x.shape == (S, m):
+        return x, 0, m
+    if x.shape == (m,):
+        return x, 0, 0
+    raise ValueError("`xdata` of a global fit must have shape (m,), (S, m) or (G, S, m) = %s, %s or %s, not %s."
+                     % ((m,), (S, m), (G, S, m), x.shape))
+
+
+def global_ydata(ydata, G, S, m):
+    """None, or `ydata` (G, S, m) as the contiguous (G, S m) array the group's problem reads."""
+    if ydata is None:
+        return None
+    y = np.asarray(ydata, dtype=np.float64)
+    if y.shape != (G, S, m):
+        raise ValueError("`ydata` must have shape (G, S, m).")
+    return np.ascontiguousarray(y.reshape(G, S * m))
+
+
 class DeviceModel:
     """Model `name` (a name, a composite spec or a ``CompositeModel``) with its data resident on the GPU: the device callbacks of ``OuterDriver.run_device``.
 
@@ -853,12 +893,21 @@ class DeviceModel:
 
     ``nan_policy='omit'`` (the default 'propagate' changes nothing): the points where `ydata` is NaN give
     residuals and Jacobian rows of exactly 0, inside the kernel, through blsq_model_eval_nan_dev for every kind of
-    model; `ydata` is then required, and a `sigma` of shape (B, m) may hold anything at those points."""
+    model; `ydata` is then required, and a `sigma` of shape (B, m) may hold anything at those points.
+
+    ``global_map=`` a ``GlobalMap``: B groups of ``global_map.S`` data sets of `m` points each, every
+    group one problem.  ``B`` is then the number of groups G, ``m`` becomes S m, ``n`` becomes nv (the width of x and
+    J) and ``n_model`` stays the model's n; `xdata` is (m,), (S, m) or (G, S, m), `ydata` (G, S, m), `sigma` a scalar,
+    (m,), (S, m) or (G, S, m), `Pfix` (G, S, n) (required where a parameter is fixed), `set_bounds` takes the reduced
+    bounds, and the callbacks go through blsq_model_eval_global_dev alone.  `param_map` must be None (the map has its
+    own), the model must have one coordinate and `binned` must be False (ValueError)."""
 
     def __init__(self, ctx, name, B, m, n, xdata, ydata=None, sigma=None, param_map=None, Pfix=None, estimator='lse',
-                 binned=False, nan_policy='propagate'):
+                 binned=False, nan_policy='propagate', global_map=None):
         model = resolve(name)
         model.terms(n)
+        if global_map is not None:
+            _check_global(model, binned, param_map)
         self.binned = bool(binned)
         self.estimator = check_estimator(estimator)
         self.nan_policy = check_nan_policy(nan_policy)
@@ -874,6 +923,10 @@ class DeviceModel:
         if param_map is not None and param_map.n != self.n_model:
             raise ValueError("`param_map` is for %d parameters, the model has %d." % (param_map.n, self.n_model))
         self.n = self.n_model if param_map is None else param_map.nf
+        self.global_map = global_map
+        if global_map is not None:
+            self._init_global(ctx, xdata, ydata, sigma, Pfix)
+            return
         x, per_problem = (BinnedModel(model) if self.binned else model).check_xdata(xdata, self.B, self.m)
         y = w = None
         if ydata is not None:
@@ -912,6 +965,45 @@ class DeviceModel:
         self._bind()
         ctx.adopt(self)
 
+    def _init_global(self, ctx, xdata, ydata, sigma, Pfix):
+        """The uploads of a global model: `self.m` is still the m of one data set on entry."""
+        gm = self.global_map
+        if gm.n != self.n_model:
+            raise ValueError("`global_map` is for %d parameters, the model has %d." % (gm.n, self.n_model))
+        G, S, m = self.B, gm.S, self.m
+        x, self.t_stride, self.t_sstride = global_xdata(xdata, G, S, m)
+        y, w = global_ydata(ydata, G, S, m), None
+        self.w_stride = 0
+        if sigma is not None:
+            sg = np.asarray(sigma, dtype=np.float64)
+            if sg.size == 1:
+                sg = np.broadcast_to(sg.reshape(()), (m,))
+            elif sg.shape != (m,):
+                if sg.shape not in ((S, m), (G, S, m)):
+                    raise ValueError("`sigma` has incorrect shape.")
+                sg = np.broadcast_to(sg, (G, S, m)).reshape(G, S * m)
+                self.w_stride = S * m
+                if self.nan_policy == 'omit':              # never read at an omitted point: anything may stand there
+                    sg = np.where(np.isnan(y), 1.0, sg)
+            w = np.ascontiguousarray(1.0 / sg)
+        self._m_set, self.m, self.n = m, S * m, gm.nv
+        self.ctx = ctx
+        self._bufs = []
+        self.d_t, self.d_y, self.d_w = self._upload(x), self._upload(y), self._upload(w)
+        self.d_Pfix = None
+        self._pmap = np.ascontiguousarray(gm.pm.pmap, dtype=np.int32)
+        self._shared = np.ascontiguousarray(gm.slot_shared, dtype=np.int32)
+        if Pfix is None and np.any(self._pmap < 0):
+            raise ValueError("`Pfix` is required when a parameter is fixed.")
+        if Pfix is not None:
+            Pfix = np.ascontiguousarray(Pfix, dtype=np.float64)
+            if Pfix.shape != (G, S, self.n_model):
+                raise ValueError("`Pfix` must have shape (G, S, n).")
+            self.d_Pfix = self._upload(Pfix)
+        self.bounds_dev = None
+        self._bind()
+        ctx.adopt(self)
+
     def _upload(self, a):
         if a is None:
             return None
@@ -933,6 +1025,9 @@ class DeviceModel:
         flags = [ESTIMATORS.index(self.estimator), SAMPLING.index('bin' if self.binned else 'point'),
                  NAN_POLICIES.index(self.nan_policy)]
         kind = [-1 if comp else M.id] + table
+        if self.global_map is not None:                       # ... then S, shared, t_sstride
+            return "blsq_model_eval_global_dev", flags + kind + [
+                self.global_map.S, self._shared.ctypes.data_as(_abi.c_int32_p), self.t_sstride]
         if self.nan_policy != 'propagate':
             return "blsq_model_eval_nan_dev", flags + kind
         if self.binned:
@@ -948,8 +1043,10 @@ class DeviceModel:
         reps, from reps to X, and from X to f (`_eval` has the rest)."""
         name, lead = self._entry()
         mapped = name != "blsq_model_eval_dev"                # every other entry has nf, pmap and Pfix
-        pmap = None if self.param_map is None else self._pmap.ctypes.data_as(_abi.c_int32_p)
-        self._call = (name, lead + [self.B], [self.m, self.n_model] + ([self.n, pmap] if mapped else [])
+        gm = self.global_map
+        pmap = None if self.param_map is None and gm is None else self._pmap.ctypes.data_as(_abi.c_int32_p)
+        m, nf = (self.m, self.n) if gm is None else (self._m_set, gm.nf)         # a global entry: per data set
+        self._call = (name, lead + [self.B], [m, self.n_model] + ([nf, pmap] if mapped else [])
                       + [self.d_t, self.t_stride, self.d_y, self.d_w, self.w_stride], [self.d_Pfix] if mapped else [])
 
     def _eval(self, x_ptr, reps, f_ptr, J_ptr, mask_ptr):
@@ -983,12 +1080,32 @@ class DeviceFit:
     a checked (model, data) pair that opens a ``DeviceModel`` on the driver's context.  Built by ``curve_fit_batch``.
     ``n`` is the number of solver variables (the width of x0): the model's n, or nf of `param_map`; ``n_model`` is the
     model's number of parameters.  ``estimator='poisson'``, ``binned=True`` and ``nan_policy='omit'``: as
-    ``DeviceModel``."""
+    ``DeviceModel``.  ``global_map=``: as ``DeviceModel``; `ydata` is (G, S, m), and ``B`` is G, ``m`` is S m and ``n``
+    is nv."""
 
     def __init__(self, name, n, xdata, ydata, sigma=None, param_map=None, Pfix=None, estimator='lse', binned=False,
-                 nan_policy='propagate'):
+                 nan_policy='propagate', global_map=None):
         self.model = resolve(name)
         self.model.terms(n)
+        self.global_map = global_map
+        if global_map is not None:
+            _check_global(self.model, binned, param_map)
+            self.binned, self.param_map = False, None
+            self.estimator, self.nan_policy = check_estimator(estimator), check_nan_policy(nan_policy)
+            if estimator == 'poisson' and sigma is not None:
+                raise ValueError("`sigma` must be None with estimator='poisson'.")
+            y = np.asarray(ydata, dtype=np.float64)
+            if y.ndim != 3 or y.shape[1] != global_map.S:
+                raise ValueError("`ydata` must have shape (G, S, m).")
+            self.B, S, self._m_set = y.shape
+            self.ydata = np.ascontiguousarray(y)
+            self.n_model, self.m, self.n = int(n), S * self._m_set, global_map.nv
+            if global_map.n != self.n_model:
+                raise ValueError("`global_map` is for %d parameters, the model has %d." % (global_map.n, self.n_model))
+            self.Pfix = None if Pfix is None else np.ascontiguousarray(Pfix, dtype=np.float64)
+            self.xdata = global_xdata(xdata, self.B, S, self._m_set)[0]
+            self.sigma = sigma
+            return
         self.binned = bool(binned)
         self.estimator = check_estimator(estimator)
         self.nan_policy = check_nan_policy(nan_policy)
@@ -1010,6 +1127,12 @@ class DeviceFit:
         self.sigma = sigma
 
     def open_device(self, ctx, lb, ub):
+        if self.global_map is not None:
+            dm = DeviceModel(ctx, self.model.name, self.B, self._m_set, self.n_model, self.xdata, self.ydata,
+                             self.sigma, None, self.Pfix, self.estimator, nan_policy=self.nan_policy,
+                             global_map=self.global_map)
+            dm.set_bounds(lb, ub)
+            return dm
         dm = DeviceModel(ctx, self.model.name, self.B, self.m, self.n_model, self.xdata, self.ydata, self.sigma,
                          self.param_map, self.Pfix, self.estimator, **({'binned': True} if self.binned else {}),
                          **({'nan_policy': self.nan_policy} if self.nan_policy != 'propagate' else {}))

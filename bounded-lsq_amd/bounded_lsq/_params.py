@@ -19,7 +19,7 @@ ascending order of the leaders.  Needs neither the library nor a GPU.
 """
 import numpy as np
 
-__all__ = ['ParamMap']
+__all__ = ['ParamMap', 'GlobalMap']
 
 
 class ParamMap:
@@ -173,3 +173,165 @@ class ParamMap:
     def wrap_jac(self, jac, Pfix):
         """``jac(xdata, P) -> (..., m, n)`` -> ``g(xdata, X) -> (..., m, nf)``."""
         return lambda xdata, X: self.reduce_jac(np.asarray(jac(xdata, self.expand_x(X, Pfix))))
+
+
+class GlobalMap:
+    """The map of a global fit: S data sets of one model, fitted together, share some parameters.
+
+    Every data set has the n parameters of the model and the ``ParamMap(n, fixed, tied)`` in ``self.pm`` (nf slots).  A
+    slot is *shared* iff its leader is in `shared`: it is then ONE solver variable for the whole group; every other slot
+    is *local*, one variable per data set.  The group is one dense problem of ``M = S m`` rows and ``nv = ns + S nl``
+    variables (ns shared slots, nl local ones), ordered
+
+        the shared slots in ascending slot order, then the local slots of data set 0 in ascending slot order, then those
+        of data set 1, ...
+
+    ``column(k, s)`` is the variable of slot k in data set s.  The methods below ARE the definition, in the way
+    ``ParamMap``'s are: blsq_model_eval_global_dev (csrc/model_kernels.hip) computes the same numbers bit for bit.
+
+    shared : a boolean mask (n,) or a sequence of indices.  ValueError (naming the index) for an index outside
+             0 .. n - 1, a fixed index, a tied key whose leader is not in `shared`, and an empty `shared` (nothing is
+             shared: S independent fits, which ``curve_fit_batch`` solves).  Everything shared (nl = 0) is valid.
+
+    Attributes: ``n``, ``S``, ``pm``, ``nf``, ``ns``, ``nl``, ``nv``, ``slot_shared`` (nf,) bool, ``shared_slots`` (ns,),
+    ``local_slots`` (nl,), ``cols`` (S, nf) (``cols[s, k] == column(k, s)``).  Needs neither the library nor a GPU.
+    """
+
+    def __init__(self, n, S, shared, fixed=None, tied=None):
+        self.pm = pm = ParamMap(n, fixed, tied)
+        if int(S) != S or int(S) < 1:
+            raise ValueError("`S` must be a positive integer.")
+        self.n, self.S, self.nf = pm.n, int(S), pm.nf
+        a = np.asarray(shared)
+        if a.dtype == bool:
+            if a.shape != (pm.n,):
+                raise ValueError("a boolean `shared` must have shape (n,) = (%d,), not %s." % (pm.n, a.shape))
+            idx = np.flatnonzero(a).tolist()
+        else:
+            idx = []
+            for j in np.atleast_1d(a).ravel().tolist() if a.size else []:
+                if int(j) != j or not 0 <= int(j) < pm.n:
+                    raise ValueError("`shared` index %r is outside 0 .. %d." % (j, pm.n - 1))
+                idx.append(int(j))
+        if not idx:
+            raise ValueError("`shared` is empty: nothing is shared between the data sets, so they are independent "
+                             "fits; use `curve_fit_batch`.")
+        members = set(idx)
+        for j in sorted(members):
+            if pm.fixed[j]:
+                raise ValueError("`shared` index %d is fixed." % j)
+            if j in pm.tied and pm.tied[j] not in members:
+                raise ValueError("`shared` index %d is tied to parameter %d, which is not shared." % (j, pm.tied[j]))
+        self.slot_shared = np.array([int(j) in members for j in pm.leaders], dtype=bool)
+        self.shared_slots = np.flatnonzero(self.slot_shared)
+        self.local_slots = np.flatnonzero(~self.slot_shared)
+        self.ns, self.nl = len(self.shared_slots), len(self.local_slots)
+        self.nv = self.ns + self.S * self.nl
+        rank = np.empty(pm.nf, dtype=np.intp)
+        rank[self.shared_slots] = np.arange(self.ns)
+        rank[self.local_slots] = self.ns + np.arange(self.nl)
+        self.cols = rank[None, :] + np.where(self.slot_shared, 0, self.nl)[None, :] * np.arange(self.S)[:, None]
+
+    def __repr__(self):
+        return "GlobalMap(n=%d, S=%d, ns=%d, nl=%d, nv=%d)" % (self.n, self.S, self.ns, self.nl, self.nv)
+
+    def column(self, k, s):
+        """The solver variable of slot k in data set s."""
+        if not 0 <= int(k) < self.nf or not 0 <= int(s) < self.S:
+            raise ValueError("slot %r / data set %r outside 0 .. %d / 0 .. %d." % (k, s, self.nf - 1, self.S - 1))
+        return int(self.cols[int(s), int(k)])
+
+    def _sets(self, a, width, name):
+        a = np.asarray(a)
+        if a.ndim < 2 or a.shape[-2:] != (self.S, width):
+            raise ValueError("`%s` must have shape (..., S, %d) = (..., %d, %d), not %s."
+                             % (name, width, self.S, width, a.shape))
+        return a
+
+    def reduce_x(self, P):
+        """(..., S, n) -> (..., nv): the leaders' values; a shared variable takes its start from data set 0."""
+        Xs = self.pm.reduce_x(self._sets(P, self.n, "P"))                       # (..., S, nf)
+        out = np.empty(Xs.shape[:-2] + (self.nv,), dtype=Xs.dtype)
+        out[..., :self.ns] = Xs[..., 0, self.shared_slots]
+        for s in range(self.S):
+            out[..., self.cols[s, self.local_slots]] = Xs[..., s, self.local_slots]
+        return out
+
+    def split_x(self, X):
+        """(..., nv) -> (..., S, nf): the nf variables of every data set.  Copies only."""
+        X = np.asarray(X)
+        if X.ndim < 1 or X.shape[-1] != self.nv:
+            raise ValueError("`X` must have %d entries along its last axis, not shape %s." % (self.nv, X.shape))
+        return X[..., self.cols]
+
+    def expand_x(self, X, Pfix):
+        """(..., nv) and the template (..., S, n) -> (..., S, n): copies only.  Of `Pfix` the fixed columns are read."""
+        return self.pm.expand_x(self.split_x(X), self._sets(Pfix, self.n, "Pfix"))
+
+    def reduce_jac(self, J_full):
+        """(..., S, m, n) -> (..., S m, nv): data set s fills the rows s m .. s m + m with ``ParamMap.reduce_jac`` of its
+        block, scattered into its own columns; every other entry of those rows is +0.0."""
+        J_full = np.asarray(J_full)
+        if J_full.ndim < 3 or J_full.shape[-3] != self.S or J_full.shape[-1] != self.n:
+            raise ValueError("`J_full` must have shape (..., S, m, n) = (..., %d, m, %d), not %s."
+                             % (self.S, self.n, J_full.shape))
+        Jr = self.pm.reduce_jac(J_full)                                         # (..., S, m, nf)
+        m = Jr.shape[-2]
+        out = np.zeros(Jr.shape[:-1] + (self.nv,), dtype=Jr.dtype)
+        for s in range(self.S):
+            out[..., s, :, :][..., self.cols[s]] = Jr[..., s, :, :]
+        return out.reshape(Jr.shape[:-3] + (self.S * m, self.nv))
+
+    def reduce_bounds(self, lb, ub):
+        """(..., S, n) bounds -> (..., nv): per data set ``ParamMap.reduce_bounds``; the box of a shared variable is the
+        intersection over the data sets as well.  ValueError where an intersection is empty."""
+        lo_s, hi_s = self.pm.reduce_bounds(self._sets(lb, self.n, "lb"), self._sets(ub, self.n, "ub"))
+        lo = np.empty(lo_s.shape[:-2] + (self.nv,))
+        hi = np.empty(hi_s.shape[:-2] + (self.nv,))
+        lo[..., :self.ns] = np.max(lo_s[..., self.shared_slots], axis=-2)
+        hi[..., :self.ns] = np.min(hi_s[..., self.shared_slots], axis=-2)
+        for s in range(self.S):
+            lo[..., self.cols[s, self.local_slots]] = lo_s[..., s, self.local_slots]
+            hi[..., self.cols[s, self.local_slots]] = hi_s[..., s, self.local_slots]
+        if np.any(lo[..., :self.ns] > hi[..., :self.ns]):
+            k = int(self.shared_slots[int(np.argwhere(lo[..., :self.ns] > hi[..., :self.ns])[0][-1])])
+            raise ValueError("the bounds of the shared parameters %s do not intersect over the data sets."
+                             % self.pm.group(k).tolist())
+        return lo, hi
+
+    def expand_cov(self, C):
+        """(..., nv, nv) -> (..., S, n, n): the block ``T_s C T_s^T`` of every data set (``ParamMap.expand_cov`` of the
+        rows and columns of its variables).  No arithmetic; the cross-data-set terms stay in `C`."""
+        C = np.asarray(C)
+        if C.ndim < 2 or C.shape[-2:] != (self.nv, self.nv):
+            raise ValueError("`C` must have shape (..., nv, nv) = (..., %d, %d), not %s." % (self.nv, self.nv, C.shape))
+        return np.stack([self.pm.expand_cov(C[..., c[:, None], c[None, :]]) for c in self.cols], axis=-3)
+
+    def expand_mask(self, mask):
+        """active_mask (..., nv) -> (..., S, n): 0 for a fixed parameter, its variable's value otherwise."""
+        return self.pm.expand_mask(self.split_x(mask))
+
+    def matrix(self):
+        """T (S n, nv): row s n + j has a 1 in the column of parameter j of data set s (none where j is fixed)."""
+        T = np.zeros((self.S * self.n, self.nv))
+        Tp = self.pm.matrix()
+        for s in range(self.S):
+            T[s * self.n:(s + 1) * self.n, self.cols[s]] = Tp
+        return T
+
+    # ---- numpy callables over the solver's variables -------------------------------------------------------------
+    def wrap_f(self, f, Pfix):
+        """``f(xdata, P (G S, n)) -> (G S, m)`` -> ``g(xdata, X (G, nv)) -> (G, S m)``; `Pfix` (G, S, n)."""
+        def g(xdata, X):
+            P = self.expand_x(X, Pfix)
+            F = np.asarray(f(xdata, P.reshape(-1, self.n)))
+            return F.reshape(P.shape[:-2] + (self.S * F.shape[-1],))
+        return g
+
+    def wrap_jac(self, jac, Pfix):
+        """``jac(xdata, P (G S, n)) -> (G S, m, n)`` -> ``g(xdata, X (G, nv)) -> (G, S m, nv)``."""
+        def g(xdata, X):
+            P = self.expand_x(X, Pfix)
+            J = np.asarray(jac(xdata, P.reshape(-1, self.n)))
+            return self.reduce_jac(J.reshape(P.shape[:-2] + (self.S,) + J.shape[-2:]))
+        return g

@@ -616,7 +616,7 @@ hipError_t launch_fd_assemble(int B, int m, int n, int method, const double* x, 
 // table behind blsq_term_info, the entries' check of n and the launcher's.
 constexpr int MODEL_TERM_PARAMS[] = {3, 3, 4, 2, 1};
 
-// One evaluation of model_kernels.hip (the six blsq_model_eval*_dev entries, 7j to 7o): f [B * reps][m] and / or
+// One evaluation of model_kernels.hip (the seven blsq_model_eval*_dev entries, 7j to 7p): f [B * reps][m] and / or
 // J [B][m][nf] (reps == 1) at X [B * reps][nf].  The fit's flags pick the kernel instance; everything else is data.
 struct ModelEvalCall {
   int est;                // BLSQ_EST_*: POISSON is the deviance residual and its Jacobian; needs y, and w == nullptr
@@ -637,6 +637,13 @@ struct ModelEvalCall {
   double* f;
   double* J;
   const int* mask;        // nullptr or [B]: a problem with mask[b] == 0 is left untouched
+  // A global evaluation (blsq_model_eval_global_dev, 7p) where S > 0: B groups of S data sets of m points.  The group is
+  // one problem of S m rows and nv = ns + S nl variables (ns slots with shared[k] == 1, nl = nf - ns): X is
+  // [B * reps][nv], f [B * reps][S m], J [B][S m][nv], y [B][S m], Pfix [B][S][n], mask [B].  pmap is required.
+  int S;
+  const int* shared;      // [nf] on the host: 1 where slot k is one variable of the group, 0 where one per data set
+  long t_sstride;         // t of data set s of group b: t + b * t_stride + s * t_sstride (each 0 or the rows it skips);
+                          // w: stride 0 ([m], every data set) or S m ([B][S m])
 };
 // hipErrorInvalidValue, and nothing launched, for a flag, model or table out of range, a y the flags need, a w under
 // POISSON, or a size the grid or LDS cannot hold: the refusals that keep the kernel's offsets in bounds.

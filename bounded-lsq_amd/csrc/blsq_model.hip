@@ -1,7 +1,7 @@
 // Built-in fit models (include/blsq.h; kernel: model_kernels.hip): the model and term tables behind
-// blsq_model_count / _info and blsq_term_count / _info, and the six entries blsq_model_eval_dev, _map_dev, _comp_dev,
-// _est_dev, _bin_dev and _nan_dev.  An entry fills a ModelEvalCall from its arguments (what its signature does not have
-// is the default) and hands it to model_eval_checked with its EvalEntry: one list of checks, one launcher, and per entry
+// blsq_model_count / _info and blsq_term_count / _info, and the seven entries blsq_model_eval_dev, _map_dev, _comp_dev,
+// _est_dev, _bin_dev, _nan_dev and _global_dev.  An entry fills a ModelEvalCall from its arguments (what its signature
+// does not have is the default) and hands it to model_eval_checked with its EvalEntry: one list of checks, one launcher, and per entry
 // only the argument numbers.
 #include "blsq_host.h"
 
@@ -56,17 +56,19 @@ extern "C" int blsq_term_info(int term, const char** name, int* n_per_term) {
 
 namespace {
 
-// What tells the six entries apart: the label of the launch, the kinds of model the entry takes, and the number a
+// What tells the seven entries apart: the label of the launch, the kinds of model the entry takes, and the number a
 // bad argument is reported by: its position in the entry's signature (ctx = 1; 0: the entry has no such argument).  The
 // arguments come in runs that every signature has in the same order, so a run is given by its first number: fam and cnt
 // follow ncomp; reps, m, n follow B; pmap follows nf; t_stride, y, w, w_stride, X follow t; J follows f.  The contents of
 // pmap have no argument of their own: an entry outside -1 .. nf - 1 is `pmap_entry`, an unused variable the number after
 // (the two past the entry's last argument).
+// The global entry (7p) has one more run: shared and t_sstride follow S (`S` == 0: the entry has none of the three).
 struct EvalEntry {
   const char* label;
   bool composite;             // takes model == -1 with a component table (otherwise named models only)
   bool needs_pmap;
   int est, sampling, nan_policy, model, ncomp, B, nf, t, Pfix, f, pmap_entry;
+  int S;
 };
 constexpr EvalEntry kEvalDev = {"launch_model_eval", false, false, 0, 0, 0, 2, 0, 3, 0, 7, 0, 13, 0};
 constexpr EvalEntry kEvalMap = {"launch_model_eval_map", false, true, 0, 0, 0, 2, 0, 3, 7, 9, 15, 16, 19};
@@ -74,6 +76,7 @@ constexpr EvalEntry kEvalComp = {"launch_model_eval_comp", true, false, 0, 0, 0,
 constexpr EvalEntry kEvalEst = {"launch_model_eval_est", true, false, 2, 0, 0, 3, 4, 7, 11, 13, 19, 20, 23};
 constexpr EvalEntry kEvalBin = {"launch_model_eval_bin", true, false, 2, 3, 0, 4, 5, 8, 12, 14, 20, 21, 24};
 constexpr EvalEntry kEvalNan = {"launch_model_eval_nan", true, false, 2, 3, 4, 5, 6, 9, 13, 15, 21, 22, 25};
+constexpr EvalEntry kEvalGlobal = {"launch_model_eval_global", true, true, 2, 3, 4, 5, 6, 12, 16, 18, 24, 25, 28, 9};
 
 // The checks of every entry, in the order of the arguments, and the launch.  A negative return names the argument.
 int model_eval_checked(blsq_ctx* ctx, const EvalEntry& e, const ModelEvalCall& c) {
@@ -87,6 +90,11 @@ int model_eval_checked(blsq_ctx* ctx, const EvalEntry& e, const ModelEvalCall& c
     return ctx->bad(e.model, e.composite ? "model must be one of BLSQ_MODEL_*, or -1 for a composite"
                                          : "model must be one of BLSQ_MODEL_*");
   const bool comp = c.model < 0;
+  const bool global = e.S != 0;
+  if (global && c.sampling != BLSQ_SAMPLE_POINT)
+    return ctx->bad(e.sampling, "sampling must be BLSQ_SAMPLE_POINT: a global fit takes no bin-integrated model");
+  if (global && !comp && kModels[c.model].coords != 1)
+    return ctx->bad(e.model, "a global fit takes the models of one coordinate");
   const int m = c.m, n = c.n, nf = c.nf;
   long total = 0;
   if (!comp) {
@@ -101,6 +109,10 @@ int model_eval_checked(blsq_ctx* ctx, const EvalEntry& e, const ModelEvalCall& c
       if (c.cnt[k] < 1) return ctx->bad(e.ncomp + 2, "cnt entry must be at least 1");
       total += (long)c.cnt[k] * MODEL_TERM_PARAMS[c.fam[k]];
     }
+  }
+  if (global) {
+    if (c.S < 1) return ctx->bad(e.S, "S must be positive");
+    if (!c.shared) return ctx->bad(e.S + 1, "shared is NULL");
   }
   if (c.B <= 0) return ctx->bad(e.B, "B must be positive");
   if (c.reps <= 0) return ctx->bad(e.B + 1, "reps must be positive");
@@ -126,9 +138,22 @@ int model_eval_checked(blsq_ctx* ctx, const EvalEntry& e, const ModelEvalCall& c
     for (int k = 0; k < nf; ++k)
       if (!used[k]) return ctx->bad(e.pmap_entry + 1, "pmap leaves a variable k < nf unused");
   }
+  if (global) {                              // nv = ns + S nl variables
+    long ns = 0;
+    for (int k = 0; k < nf; ++k) {
+      if (c.shared[k] != 0 && c.shared[k] != 1) return ctx->bad(e.S + 1, "shared entry must be 0 or 1");
+      ns += c.shared[k];
+    }
+    if (ns + (long)c.S * (nf - ns) > BLSQ_GLOBAL_MAX_NV)
+      return ctx->bad(e.S, "ns + S * nl exceeds BLSQ_GLOBAL_MAX_NV variables");
+    if (c.t_sstride != 0 && c.t_sstride != (long)m) return ctx->bad(e.S + 2, "t_sstride must be 0 or m");
+  }
   const long coords = comp ? 1 : kModels[c.model].coords;
   if (!c.t) return ctx->bad(e.t, "t is NULL");
-  if (c.sampling == BLSQ_SAMPLE_BIN) {
+  if (global) {
+    if (c.t_stride != 0 && c.t_stride != (c.t_sstride ? (long)c.S * m : (long)m))
+      return ctx->bad(e.t + 1, "t_stride must be 0 or the abscissae of one group (m, with t_sstride == m: S * m)");
+  } else if (c.sampling == BLSQ_SAMPLE_BIN) {
     if (c.t_stride != 0 && c.t_stride != 2 * coords * m)
       return ctx->bad(e.t + 1, "t_stride must be 0 or 2 * coords * m with BLSQ_SAMPLE_BIN");
   } else if (c.t_stride != 0 && c.t_stride != coords * m) {
@@ -138,7 +163,11 @@ int model_eval_checked(blsq_ctx* ctx, const EvalEntry& e, const ModelEvalCall& c
   if (c.nan_policy == BLSQ_NAN_OMIT && !c.y)
     return ctx->bad(e.t + 2, "y is NULL: BLSQ_NAN_OMIT reads the missing points from it");
   if (c.est == BLSQ_EST_POISSON && c.w) return ctx->bad(e.t + 3, "w must be NULL with the Poisson estimator");
-  if (c.w && c.w_stride != 0 && c.w_stride != (long)m) return ctx->bad(e.t + 4, "w_stride must be 0 or m");
+  if (c.w && global) {
+    if (c.w_stride != 0 && c.w_stride != (long)c.S * m) return ctx->bad(e.t + 4, "w_stride must be 0 or S * m");
+  } else if (c.w && c.w_stride != 0 && c.w_stride != (long)m) {
+    return ctx->bad(e.t + 4, "w_stride must be 0 or m");
+  }
   if (!c.X) return ctx->bad(e.t + 5, "X is NULL (the parameter vectors)");
   if (any_fixed && !c.Pfix) return ctx->bad(e.Pfix, "Pfix is NULL although pmap holds a parameter fixed");
   if (!c.f && !c.J) return ctx->bad(e.f, "f and J are both NULL");
@@ -201,4 +230,15 @@ extern "C" int blsq_model_eval_nan_dev(blsq_ctx* ctx, int est, int sampling, int
                                        double* df, double* dJ, const int32_t* dmask) {
   return model_eval_checked(ctx, kEvalNan, {est, sampling, nan_policy, model, ncomp, fam, cnt, B, reps, m, n, nf, pmap,
                                             dt, t_stride, dy, dw, w_stride, dX, dPfix, df, dJ, dmask});
+}
+
+extern "C" int blsq_model_eval_global_dev(blsq_ctx* ctx, int est, int sampling, int nan_policy, int model, int ncomp,
+                                          const int32_t* fam, const int32_t* cnt, int S, const int32_t* shared,
+                                          long t_sstride, int G, int reps, int m, int n, int nf, const int32_t* pmap,
+                                          const double* dt, long t_stride, const double* dy, const double* dw,
+                                          long w_stride, const double* dX, const double* dPfix, double* df, double* dJ,
+                                          const int32_t* dmask) {
+  return model_eval_checked(ctx, kEvalGlobal, {est, sampling, nan_policy, model, ncomp, fam, cnt, G, reps, m, n, nf,
+                                               pmap, dt, t_stride, dy, dw, w_stride, dX, dPfix, df, dJ, dmask, S,
+                                               shared, t_sstride});
 }

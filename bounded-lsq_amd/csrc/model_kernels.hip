@@ -60,6 +60,19 @@
 // their row run the code of the instance without the flag, whose walk over the component table stays wave-uniform.  The
 // shell is untouched, and the flag is a template flag for the reason given for POISSON: the 48 instances without it are
 // the instructions they were, and the 96 build in 18 s where the 48 took 10 s.
+//
+// Global instances (MAP == MAP_GLOBAL; blsq_model_eval_global_dev).  G groups of S data sets share some of
+// the map's slots: a group is one problem of S m rows and nv = ns + S nl variables.  The work items of a point run over
+// its data sets (items = Q S ceil(m / 64)), so a wave still owns 64 rows of ONE data set s, s is wave-uniform, and the
+// wave is a mapped wave in everything but its addresses: it expands its parameter vector from X[q][.] at the columns of
+// data set s, stages its rows nf wide at stride nf | 1 through the same row_put (the host numbers the slots shared ones
+// first, so the tile's columns are the variables [0, ns) and data set s's window in order), and runs the Poisson row
+// pass and the OMIT branch over those nf slots alone.  Only the stream-out differs: the wave's rows are one contiguous
+// block of nr nv doubles, which it writes with consecutive lanes on consecutive addresses, an element from the tile
+// where its column is one of the data set's and +0.0 elsewhere.  The zeros never pass through arithmetic (a Poisson c
+// of NaN multiplies the nf staged slots only), LDS does not depend on nv, and the waves per workgroup are the mapped
+// instance's.  MAP is a template parameter for the reason given for POISSON; the bin-integrated and gauss2d global
+// instances are not built (20 instances more: 116).
 #include "../../include/blsq.h"
 #include "blsq_device.h"
 #include "blsq_kernels.h"
@@ -98,12 +111,22 @@ struct CompTable {
   unsigned long long lo, hi;
 };
 static_assert(BLSQ_MODEL_MAX_COMP == 8, "CompTable holds 8 entries of 16 bits");
+// A global launch (7p): the map above with its slots renumbered, the ns shared ones first (pm[] then names a column of
+// the tile in that order); data set s owns the variables [0, ns) and [ns + s nl, ns + s nl + nl) of the group's nv.
+struct ModelGlobalArgs : ModelMapArgs {
+  int S, ns, nl, nv;            // P is X [Q][nv]; Pfix [B][S][n]; w_stride is 0 or m per DATA SET
+  long t_sstride;               // t of data set s of group g: t + g * t_stride + s * t_sstride
+};
 template <class Base> struct CompArgs : Base { CompTable tab; };
 static constexpr int MODEL_COMPOSITE = -1;            // the MODEL of the composite instances (no BLSQ_MODEL_* id)
-template <bool COMP, bool MAPPED> struct ModelArgsOf { using type = ModelArgs; };
-template <> struct ModelArgsOf<false, true> { using type = ModelMapArgs; };
-template <> struct ModelArgsOf<true, false> { using type = CompArgs<ModelArgs>; };
-template <> struct ModelArgsOf<true, true> { using type = CompArgs<ModelMapArgs>; };
+// MAP: how the solver's variables become the model's parameters
+static constexpr int MAP_NONE = 0, MAP_PARAM = 1, MAP_GLOBAL = 2;
+template <bool COMP, int MAP> struct ModelArgsOf { using type = ModelArgs; };
+template <> struct ModelArgsOf<false, MAP_PARAM> { using type = ModelMapArgs; };
+template <> struct ModelArgsOf<false, MAP_GLOBAL> { using type = ModelGlobalArgs; };
+template <> struct ModelArgsOf<true, MAP_NONE> { using type = CompArgs<ModelArgs>; };
+template <> struct ModelArgsOf<true, MAP_PARAM> { using type = CompArgs<ModelMapArgs>; };
+template <> struct ModelArgsOf<true, MAP_GLOBAL> { using type = CompArgs<ModelGlobalArgs>; };
 
 __device__ __forceinline__ int map_nf(const ModelArgs& A) { return A.n; }
 __device__ __forceinline__ int map_nf(const ModelMapArgs& A) { return A.nf; }
@@ -475,9 +498,10 @@ __device__ __forceinline__ void poisson_rc(double mu, double y, double& r, doubl
   }
 }
 
-template <int MODEL, bool MAPPED, bool POISSON, bool BINNED, bool OMIT>
+template <int MODEL, int MAP, bool POISSON, bool BINNED, bool OMIT>
 __global__ __launch_bounds__(256) void model_eval_kernel(
-    typename ModelArgsOf<MODEL == MODEL_COMPOSITE, MAPPED>::type A) {
+    typename ModelArgsOf<MODEL == MODEL_COMPOSITE, MAP>::type A) {
+  constexpr bool MAPPED = MAP != MAP_NONE, GLOBAL = MAP == MAP_GLOBAL;
   extern __shared__ double model_tiles[];
   const int lane = threadIdx.x & (WAVE - 1);
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);            // wave-uniform, in a scalar register
@@ -490,8 +514,17 @@ __global__ __launch_bounds__(256) void model_eval_kernel(
     q = item / A.tiles;
     r0 = (int)(item - q * A.tiles) * MODEL_ROWS;
   }
-  const long b = q / A.reps;
-  if (live && A.mask && A.mask[b] == 0) live = false;                           // a masked problem is left untouched
+  // global: the items of a point run over its S data sets, so q counts (point, data set) pairs: the row blocks of f and
+  // J.  qx is the point, g its group (the index of mask) and b the data set among all G S (the index of y, w and Pfix).
+  long b = q / A.reps, g = b, qx = q;
+  int s = 0;
+  if constexpr (GLOBAL) {
+    qx = q / A.S;
+    s = (int)(q - qx * A.S);
+    g = qx / A.reps;
+    b = g * A.S + s;
+  }
+  if (live && A.mask && A.mask[g] == 0) live = false;                           // a masked problem is left untouched
   const int n = A.n, m = A.m;
   const int nc = map_nf(A);                                                     // columns of J: n, or nf when mapped
   const int ld = nc | 1;
@@ -500,11 +533,14 @@ __global__ __launch_bounds__(256) void model_eval_kernel(
   double* tiles = MAPPED ? model_tiles + (size_t)wpb * MODEL_ROWS : model_tiles;
   double* tile = A.J ? tiles + (size_t)wave * MODEL_ROWS * ld : nullptr;
   const double* p = A.P + q * nc;
+  if constexpr (GLOBAL) p = A.P + qx * A.nv;
   if constexpr (MAPPED) {
     double* pv = model_tiles + (size_t)wave * MODEL_ROWS;
     if (live && lane < n) {
       const int c = map_pm(A)[lane];
-      pv[lane] = c < 0 ? map_pfix(A)[b * n + lane] : p[c & (MODEL_ROWS - 1)];
+      int k = c & (MODEL_ROWS - 1);
+      if constexpr (GLOBAL) k = k < A.ns ? k : k + s * A.nl;                    // a local slot: data set s's window
+      pv[lane] = c < 0 ? map_pfix(A)[b * n + lane] : p[k];
     }
     __syncthreads();                       // (the wave reads only its own vector; every wave arrives)
     p = pv;
@@ -522,7 +558,8 @@ __global__ __launch_bounds__(256) void model_eval_kernel(
       }
     }
     if (!omitted) {
-      const double* tb = A.t + b * A.t_stride;
+      const double* tb = A.t + g * A.t_stride;
+      if constexpr (GLOBAL) tb += s * A.t_sstride;
       const double wi = (!POISSON && A.w) ? A.w[b * A.w_stride + i] : 1.0;
       double* row = tile ? tile + lane * ld : nullptr;
       double v;
@@ -544,7 +581,25 @@ __global__ __launch_bounds__(256) void model_eval_kernel(
       }
     }
   }
-  if (A.J) {
+  if constexpr (GLOBAL) {
+    if (A.J) {
+      __syncthreads();
+      // the wave's rows are the contiguous block J[g][s m + r0 .. + nr)[0 .. nv): consecutive lanes on consecutive
+      // addresses; an element comes from the tile where its column is a shared one or lies in data set s's window
+      // (tile column = column - s nl there) and is +0.0 elsewhere
+      const int nv = A.nv, ns = A.ns, off = s * A.nl;
+      double* out = A.J + (q * m + r0) * (long)nv;
+      const int total = nr * nv;
+      int row = lane / nv, col = lane - row * nv;
+      const int drow = WAVE / nv, dcol = WAVE - drow * nv;
+      for (int e = lane; e < total; e += WAVE) {
+        const int k = col < ns ? col : col - off;
+        out[e] = (k < nc && (col < ns || k >= ns)) ? tile[row * ld + k] : 0.0;
+        row += drow; col += dcol;
+        if (col >= nv) { col -= nv; ++row; }
+      }
+    }
+  } else if (A.J) {
     __syncthreads();                       // (every wave of the workgroup arrives: no early return above)
     // the wave's rows are the contiguous block J[q][r0 .. r0 + nr)[0 .. nc): lane l takes elements l, l + 64, ...
     double* out = A.J + (q * m + r0) * (long)nc;
@@ -561,34 +616,44 @@ __global__ __launch_bounds__(256) void model_eval_kernel(
 
 // The launch of instance <MODEL, MAPPED> with the flags `inst`: POISSON | BINNED << 1 | OMIT << 2.  The eight kernels
 // take the same arguments: the part of `all` that the instance has.
-template <int MODEL, bool MAPPED>
-static void launch_model_instance(int inst, dim3 g, dim3 blk, size_t lds, hipStream_t s,
-                                  const CompArgs<ModelMapArgs>& all) {
-  using Args = typename ModelArgsOf<MODEL == MODEL_COMPOSITE, MAPPED>::type;
-  static void (*const kernels[8])(Args) = {
-      model_eval_kernel<MODEL, MAPPED, false, false, false>, model_eval_kernel<MODEL, MAPPED, true, false, false>,
-      model_eval_kernel<MODEL, MAPPED, false, true, false>,  model_eval_kernel<MODEL, MAPPED, true, true, false>,
-      model_eval_kernel<MODEL, MAPPED, false, false, true>,  model_eval_kernel<MODEL, MAPPED, true, false, true>,
-      model_eval_kernel<MODEL, MAPPED, false, true, true>,   model_eval_kernel<MODEL, MAPPED, true, true, true>};
-  Args A;
-  static_cast<typename ModelArgsOf<false, MAPPED>::type&>(A) = all;
-  if constexpr (MODEL == MODEL_COMPOSITE) A.tab = all.tab;
-  hipLaunchKernelGGL(kernels[inst], g, blk, lds, s, A);
+// Instance <MODEL, MAP> with the flags; nullptr for the bin-integrated global instances, which are not built.
+template <int MODEL, int MAP, bool POISSON, bool BINNED, bool OMIT>
+static constexpr auto model_instance() -> void (*)(typename ModelArgsOf<MODEL == MODEL_COMPOSITE, MAP>::type) {
+  if constexpr (MAP == MAP_GLOBAL && BINNED) return nullptr;
+  else return model_eval_kernel<MODEL, MAP, POISSON, BINNED, OMIT>;
 }
 
-template <bool MAPPED>
+template <int MODEL, int MAP>
+static hipError_t launch_model_instance(int inst, dim3 g, dim3 blk, size_t lds, hipStream_t s,
+                                        const CompArgs<ModelGlobalArgs>& all) {
+  using Args = typename ModelArgsOf<MODEL == MODEL_COMPOSITE, MAP>::type;
+  static void (*const kernels[8])(Args) = {
+      model_instance<MODEL, MAP, false, false, false>(), model_instance<MODEL, MAP, true, false, false>(),
+      model_instance<MODEL, MAP, false, true, false>(),  model_instance<MODEL, MAP, true, true, false>(),
+      model_instance<MODEL, MAP, false, false, true>(),  model_instance<MODEL, MAP, true, false, true>(),
+      model_instance<MODEL, MAP, false, true, true>(),   model_instance<MODEL, MAP, true, true, true>()};
+  if (!kernels[inst]) return hipErrorInvalidValue;
+  Args A;
+  static_cast<typename ModelArgsOf<false, MAP>::type&>(A) = all;
+  if constexpr (MODEL == MODEL_COMPOSITE) A.tab = all.tab;
+  hipLaunchKernelGGL(kernels[inst], g, blk, lds, s, A);
+  return hipGetLastError();
+}
+
+template <int MAP>
 static hipError_t launch_model_kind(int model, int inst, dim3 g, dim3 blk, size_t lds, hipStream_t s,
-                                    const CompArgs<ModelMapArgs>& all) {
+                                    const CompArgs<ModelGlobalArgs>& all) {
   switch (model) {
-    case MODEL_COMPOSITE: launch_model_instance<MODEL_COMPOSITE, MAPPED>(inst, g, blk, lds, s, all); break;
-    case BLSQ_MODEL_POLY: launch_model_instance<BLSQ_MODEL_POLY, MAPPED>(inst, g, blk, lds, s, all); break;
-    case BLSQ_MODEL_EXP_SUM: launch_model_instance<BLSQ_MODEL_EXP_SUM, MAPPED>(inst, g, blk, lds, s, all); break;
-    case BLSQ_MODEL_GAUSS_SUM: launch_model_instance<BLSQ_MODEL_GAUSS_SUM, MAPPED>(inst, g, blk, lds, s, all); break;
-    case BLSQ_MODEL_LORENTZ_SUM: launch_model_instance<BLSQ_MODEL_LORENTZ_SUM, MAPPED>(inst, g, blk, lds, s, all); break;
-    case BLSQ_MODEL_GAUSS2D: launch_model_instance<BLSQ_MODEL_GAUSS2D, MAPPED>(inst, g, blk, lds, s, all); break;
+    case MODEL_COMPOSITE: return launch_model_instance<MODEL_COMPOSITE, MAP>(inst, g, blk, lds, s, all);
+    case BLSQ_MODEL_POLY: return launch_model_instance<BLSQ_MODEL_POLY, MAP>(inst, g, blk, lds, s, all);
+    case BLSQ_MODEL_EXP_SUM: return launch_model_instance<BLSQ_MODEL_EXP_SUM, MAP>(inst, g, blk, lds, s, all);
+    case BLSQ_MODEL_GAUSS_SUM: return launch_model_instance<BLSQ_MODEL_GAUSS_SUM, MAP>(inst, g, blk, lds, s, all);
+    case BLSQ_MODEL_LORENTZ_SUM: return launch_model_instance<BLSQ_MODEL_LORENTZ_SUM, MAP>(inst, g, blk, lds, s, all);
+    case BLSQ_MODEL_GAUSS2D:                                 // two coordinates: no global instance
+      if constexpr (MAP == MAP_GLOBAL) return hipErrorInvalidValue;
+      else return launch_model_instance<BLSQ_MODEL_GAUSS2D, MAP>(inst, g, blk, lds, s, all);
     default: return hipErrorInvalidValue;
   }
-  return hipGetLastError();
 }
 
 hipError_t launch_model_eval(const ModelEvalCall& c, hipStream_t s) {
@@ -598,21 +663,35 @@ hipError_t launch_model_eval(const ModelEvalCall& c, hipStream_t s) {
     return hipErrorInvalidValue;
   if (((poisson || omit) && !c.y) || (poisson && c.w)) return hipErrorInvalidValue;   // both read y; Poisson takes no w
   if (c.n < 1 || c.n > MODEL_ROWS) return hipErrorInvalidValue;
-  CompArgs<ModelMapArgs> A;
+  const bool global = c.S > 0;
+  if (global && (bin || !c.pmap || !c.shared)) return hipErrorInvalidValue;
+  CompArgs<ModelGlobalArgs> A;
   A.m = c.m; A.n = c.n; A.reps = c.reps; A.tiles = (c.m + MODEL_ROWS - 1) / MODEL_ROWS;
-  A.items = (long)c.B * c.reps * A.tiles;
+  A.items = (long)c.B * c.reps * (global ? c.S : 1) * A.tiles;
   A.t = c.t; A.t_stride = c.t_stride; A.y = c.y; A.w = c.w; A.w_stride = c.w_stride; A.P = c.X; A.f = c.f; A.J = c.J;
   A.mask = c.mask;
   int nc = c.n;                                      // columns of J
   if (c.pmap) {                                      // nf, Pfix and pm[] from the host's pmap [n]
     nc = A.nf = c.nf; A.Pfix = c.Pfix;
     if (c.nf < 1 || c.nf > c.n) return hipErrorInvalidValue;
+    int slot[MODEL_ROWS];                            // the tile column of slot k: k, or (global) the shared slots first
+    for (int k = 0; k < c.nf; ++k) slot[k] = k;
+    if (global) {
+      int ns = 0, nl = 0;
+      for (int k = 0; k < c.nf; ++k) ns += c.shared[k] != 0;
+      A.S = c.S; A.ns = ns; A.nl = c.nf - ns; A.t_sstride = c.t_sstride;
+      const long nv = ns + (long)c.S * A.nl;
+      if (nv > BLSQ_GLOBAL_MAX_NV) return hipErrorInvalidValue;
+      A.nv = (int)nv;
+      A.w_stride = c.w_stride ? c.m : 0;             // per data set: the rows of [B][S m] are [B S][m]
+      for (int k = 0, sh = 0; k < c.nf; ++k) slot[k] = c.shared[k] ? sh++ : ns + nl++;
+    }
     bool seen[MODEL_ROWS] = {};
     for (int j = 0; j < MODEL_ROWS; ++j) {
       int k = -1;
       if (j < c.n && c.pmap[j] >= 0) {
         if (c.pmap[j] >= c.nf) return hipErrorInvalidValue;
-        k = seen[c.pmap[j]] ? MODEL_ROWS + c.pmap[j] : c.pmap[j];
+        k = seen[c.pmap[j]] ? MODEL_ROWS + slot[c.pmap[j]] : slot[c.pmap[j]];
         seen[c.pmap[j]] = true;
       }
       A.pm[j] = (signed char)k;
@@ -640,8 +719,9 @@ hipError_t launch_model_eval(const ModelEvalCall& c, hipStream_t s) {
   if (grid <= 0 || grid > 0x7fffffffL) return hipErrorInvalidValue;
   const int inst = (int)poisson | (int)bin << 1 | (int)omit << 2;
   const dim3 g((unsigned)grid), blk(64 * wpb);
-  return c.pmap ? launch_model_kind<true>(c.model, inst, g, blk, wave_bytes * wpb, s, A)
-                : launch_model_kind<false>(c.model, inst, g, blk, wave_bytes * wpb, s, A);
+  if (global) return launch_model_kind<MAP_GLOBAL>(c.model, inst, g, blk, wave_bytes * wpb, s, A);
+  return c.pmap ? launch_model_kind<MAP_PARAM>(c.model, inst, g, blk, wave_bytes * wpb, s, A)
+                : launch_model_kind<MAP_NONE>(c.model, inst, g, blk, wave_bytes * wpb, s, A);
 }
 
 }  // namespace blsq

@@ -533,6 +533,34 @@ int blsq_model_eval_nan_dev(blsq_ctx* ctx, int est, int sampling, int nan_policy
                             long w_stride, const double* dX, const double* dPfix, double* df, double* dJ,
                             const int32_t* dmask);
 
+/* Global fits: G groups of S data sets of one model, m points each.  Every data set has the n parameters
+ * of the model over the nf slots of pmap (the rules of blsq_model_eval_map_dev; pmap is required, the identity for a
+ * model without fixed or tied parameters).  A slot k with shared[k] == 1 is ONE variable of the group; a slot with
+ * shared[k] == 0 is one variable per data set.  With ns shared slots and nl = nf - ns local ones the group is one dense
+ * problem of S m rows and nv = ns + S nl <= BLSQ_GLOBAL_MAX_NV variables, ordered: the shared slots in ascending slot
+ * order, then the local slots of data set 0 in ascending slot order, then those of data set 1, ...  For the points
+ * X [G * reps][nv] (q = g * reps + r) and the template Pfix [G][S][n]:
+ *   f[q][s m + i]      = the f of blsq_model_eval_nan_dev for data set s at the parameters its variables give, bit for bit
+ *   J[g][s m + i][col] = its mapped J[i][k] where col is the variable of slot k in data set s, +0.0 (every bit zero) in
+ *                        every other column, under either estimator                               dJ [G][S m][nv]
+ * dy: [G][S m] or NULL; dt: data set s of group g reads dt + g * t_stride + s * t_sstride, with t_sstride 0 or m and
+ * t_stride 0 or the doubles of one group (S m with t_sstride == m, otherwise m); dw: NULL, [m] (w_stride 0) or [G][S m]
+ * (w_stride S m); dmask: int32 [G] or NULL, a group with dmask[g] == 0 is left untouched.  shared: HOST pointer,
+ * int32 [nf] of 0 / 1, read during the call as fam, cnt and pmap are.  sampling must be BLSQ_SAMPLE_POINT (-3) and the
+ * model one of a single coordinate (GAUSS2D: -5).  S == 1 with every slot shared gives the outputs of
+ * blsq_model_eval_nan_dev.  A negative return is the index of the bad argument (ctx = 1, est = 2, sampling = 3,
+ * nan_policy = 4, model = 5, ncomp = 6, fam = 7, cnt = 8, S = 9, shared = 10, t_sstride = 11, G = 12, reps, m, n = 15,
+ * nf = 16, pmap = 17, t = 18, t_stride = 19, y = 20, w = 21, w_stride, X = 23, Pfix = 24, f = 25, J = 26, mask); more
+ * than BLSQ_GLOBAL_MAX_NV variables is -9, and for the contents of pmap -28 and -29 as above.  Nothing is launched then.
+ * BLSQ_GLOBAL_MAX_NV is an interface limit that keeps a group inside the normal-equations front end (n + 1 <= 272,
+ * DESIGN.md 9); it is not a measured figure. */
+#define BLSQ_GLOBAL_MAX_NV 256
+int blsq_model_eval_global_dev(blsq_ctx* ctx, int est, int sampling, int nan_policy, int model, int ncomp,
+                               const int32_t* fam, const int32_t* cnt, int S, const int32_t* shared, long t_sstride,
+                               int G, int reps, int m, int n, int nf, const int32_t* pmap, const double* dt,
+                               long t_stride, const double* dy, const double* dw, long w_stride, const double* dX,
+                               const double* dPfix, double* df, double* dJ, const int32_t* dmask);
+
 /* ---- parameter covariance from the final Jacobian --------------------------------------------------------------
  * The reference documents `x_covariance` as the inverse of J^T J at the solution (least_squares.py:248-252) and fills
  * it only through its MINPACK bridge (method='lm').  Here, per problem, from a Householder triangle R of J (the TSQR

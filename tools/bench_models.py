@@ -28,8 +28,16 @@ points than parameters) and passes ``nan_policy='omit'`` on both routes: the nam
 instances (blsq_model_eval_nan_dev), the callable route ``models.omit_residual`` / ``omit_jacobian``.  ``--omit 0``
 passes the keyword with no NaN: the cost of the flag alone.  Without it nothing here changes.
 
+``--global S --shared i,j`` (DESIGN.md 7p) fits global problems instead: the B data sets become B // S groups of S, the
+parameters i, j (of 'gauss_sum': 1,2 = position and width) are one per group, and ``curve_fit_global`` runs the whole
+fit on the device route (blsq_model_eval_global_dev) against the callable route (the numpy functions behind
+``GlobalMap.wrap_f`` / ``wrap_jac``).  A further call of the device route with every slot timed gives `slots_ms`, the
+kernel time per slot, and `gram_share`, the part of it spent in the slots whose name holds 'gram': the measured case
+for or against a structured solve.  With ``--kernel``: the launches of the global entry alone, f and J.
+
 usage: python tools/bench_models.py [--B 4096] [--m 64] [--repeat 5] [--peaks 1] [--fixed 1,4] [--tied 5:2] [--kernel]
                                     [--launches 50] [--rounds 1] [--estimator lse] [--binned] [--omit FRACTION]
+                                    [--global S --shared 1,2]
 """
 import argparse
 import json
@@ -41,7 +49,7 @@ import numpy as np
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "bounded-lsq_amd"))
-from bounded_lsq import curve_fit_batch, models, _abi, ParamMap          # noqa: E402
+from bounded_lsq import curve_fit_batch, curve_fit_global, models, _abi, ParamMap, GlobalMap          # noqa: E402
 
 
 PEAKS = {1: [1.5, 0.2, 0.6, 0.3], 2: [1.5, -0.8, 0.4, 1.0, 0.7, 0.5, 0.2]}
@@ -50,8 +58,9 @@ PEAKS = {1: [1.5, 0.2, 0.6, 0.3], 2: [1.5, -0.8, 0.4, 1.0, 0.7, 0.5, 0.2]}
 COUNTS = 40.0                                  # --estimator poisson: amplitudes and offset in counts
 
 
-def problems(B, m, seed=0, peaks=1, fixed=(), tied=None, poisson=False, binned=False):
-    """The truth satisfies the ties and p0 sits at the truth in the fixed columns."""
+def problems(B, m, seed=0, peaks=1, fixed=(), tied=None, poisson=False, binned=False, common=None):
+    """The truth satisfies the ties and p0 sits at the truth in the fixed columns.  common = (S, indices): the truth of
+    those parameters is one value in every run of S problems (the groups of --global)."""
     rng = np.random.default_rng(seed)
     base = np.array(PEAKS[peaks])
     if poisson:
@@ -63,6 +72,10 @@ def problems(B, m, seed=0, peaks=1, fixed=(), tied=None, poisson=False, binned=F
     truth = base * (1 + 0.05 * rng.uniform(-1, 1, (B, base.size)))
     for j, i in (tied or {}).items():
         truth[:, j] = truth[:, i]
+    if common:
+        S, idx = common
+        for j in idx:
+            truth[:, j] = np.repeat(truth[::S, j], S)[:B]
     x = np.linspace(-2.0, 2.0, m + 1 if binned else m)
     M = models.binned("gauss_sum") if binned else models.get("gauss_sum")
     if poisson:
@@ -122,6 +135,78 @@ def kernel_times(ctx, x, Y, P0, pm, launches, rounds=1, estimator="lse", binned=
     return out
 
 
+def global_bench(a, ctx):
+    """--global: G = B // S groups of S one-peak data sets with the parameters `a.shared` common to a group."""
+    S, m = a.global_S, a.m
+    G = max(1, a.B // S)
+    shared = [int(v) for v in a.shared.split(",") if v]
+    poisson = a.estimator == "poisson"
+    x, Y, P0, (lb, ub) = problems(G * S, m, peaks=a.peaks, poisson=poisson, common=(S, shared))
+    n = P0.shape[1]
+    Y, P0, lb, ub = Y.reshape(G, S, m), P0.reshape(G, S, n), lb.reshape(G, S, n), ub.reshape(G, S, n)
+    gm = GlobalMap(n, S, shared)
+    res = {"model": "gauss_sum", "G": G, "S": S, "m": m, "n": n, "shared": shared, "M": S * m, "nv": gm.nv,
+           "estimator": a.estimator}
+    if a.kernel:
+        dm = models.DeviceModel(ctx, "gauss_sum", G, m, n, x, Y, None if poisson else 0.01, Pfix=P0,
+                                estimator=a.estimator, global_map=gm)
+        d_x = ctx.to_device(np.ascontiguousarray(gm.reduce_x(P0)))
+        d_f, d_J = ctx.malloc(8 * G * S * m), ctx.malloc(8 * G * S * m * gm.nv)
+        for what, call in (("f", lambda: dm.fun_dev(d_x, d_f, 1)), ("J", lambda: dm.jac_dev(d_x, d_J))):
+            call()
+            ctx.sync()
+            per_round = []
+            for _ in range(a.rounds):
+                ctx.timing(True, only="model_eval")
+                ctx.timing_reset()
+                for _ in range(a.launches):
+                    call()
+                ctx.sync()
+                ms, cnt = ctx.timing_read()["model_eval"]
+                ctx.timing(False)
+                per_round.append(round(1e3 * ms / cnt, 2))
+            res["global_%s_us" % what] = round(float(np.median(per_round)), 2)
+            res["global_%s_us_all" % what] = per_round
+        res["J_bytes"] = 8 * G * S * m * gm.nv
+        for p in (d_x, d_f, d_J):
+            ctx.free(p)
+        dm.close()
+        return res
+    kw = dict(sigma=None if poisson else 0.01, bounds=(lb, ub), driver="device", ctx=ctx, ftol=1e-10, xtol=1e-10,
+              gtol=1e-10, estimator=a.estimator)
+    M = models.get("gauss_sum")
+    routes = {"named": lambda: curve_fit_global("gauss_sum", x, Y, P0, shared, **kw),
+              "callable": lambda: curve_fit_global(M.f, x, Y, P0, shared, jac=M.jac, **kw)}
+    times = {k: [] for k in routes}
+    out = {k: run() for k, run in routes.items()}                         # warm-up: code objects, plans
+    for _ in range(a.repeat):
+        for k, run in routes.items():
+            ctx.sync()
+            t0 = time.perf_counter()
+            run()
+            times[k].append(time.perf_counter() - t0)
+    ctx.timing(True)
+    ctx.timing_reset()
+    routes["named"]()
+    ctx.sync()
+    slots = {k: round(ms, 3) for k, (ms, cnt) in ctx.timing_read().items() if cnt}
+    ctx.timing(False)
+    total = sum(slots.values())
+    both = np.array([ra.success and rb.success for ra, rb in zip(out["named"][2], out["callable"][2])])
+    res.update({"named_s": round(float(np.median(times["named"])), 4),
+                "callable_s": round(float(np.median(times["callable"])), 4),
+                "named_all_s": [round(t, 4) for t in times["named"]],
+                "callable_all_s": [round(t, 4) for t in times["callable"]],
+                "speedup": round(float(np.median(times["callable"]) / np.median(times["named"])), 2),
+                "slots_ms": slots, "kernels_ms": round(total, 3),
+                "gram_share": round(sum(v for k, v in slots.items() if "gram" in k) / total, 3) if total else None,
+                "converged": {k: int(sum(r.success for r in out[k][2])) for k in routes},
+                "max_nfev": int(max(r.nfev for r in out["named"][2])),
+                "popt_max_rel_diff": float(np.max(np.abs(out["named"][0][both] - out["callable"][0][both])
+                                                  / (np.abs(out["callable"][0][both]) + 1e-3)))})
+    return res
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--B", type=int, default=4096)
@@ -137,7 +222,18 @@ def main():
     ap.add_argument("--binned", action="store_true", help="fit bin integrals: the bin-integrated instances")
     ap.add_argument("--omit", type=float, default=None, metavar="FRACTION",
                     help="blank this share of ydata and pass nan_policy='omit' (0: the keyword with no NaN)")
+    ap.add_argument("--global", dest="global_S", type=int, default=0, metavar="S",
+                    help="global fits: B // S groups of S data sets (needs --shared)")
+    ap.add_argument("--shared", default="", help="with --global: the parameters common to a group, e.g. 1,2")
     a = ap.parse_args()
+    if a.global_S:
+        if a.global_S < 1 or not a.shared or a.fixed or a.tied or a.binned or a.omit is not None:
+            ap.error("--global S takes S >= 1 and --shared i,j, without --fixed, --tied, --binned and --omit")
+        ctx = _abi.Context(0)
+        res = global_bench(a, ctx)
+        ctx.close()
+        print(json.dumps(res))
+        return
     if a.omit is not None and not 0.0 <= a.omit < 1.0:
         ap.error("--omit takes a fraction in [0, 1)")
     fixed = [int(v) for v in a.fixed.split(",") if v]
