@@ -21,10 +21,11 @@ c_uint8_p = C.POINTER(C.c_uint8)
 vp = C.c_void_p
 
 
-def _model_eval(lead, mapped=True):
-    """A blsq_model_eval*_dev entry: ctx, `lead`, B, reps, m, n (mapped: nf, pmap), t, t_stride, y, w, w_stride, X
-    (mapped: Pfix), f, J, mask."""
+def _model_eval(lead, mapped=True, tie=False):
+    """A blsq_model_eval*_dev entry: ctx, `lead`, B, reps, m, n (mapped: nf, pmap; tie: tie_ratio, tie_offset), t,
+    t_stride, y, w, w_stride, X (mapped: Pfix), f, J, mask."""
     return (C.c_int, [vp] + lead + [C.c_int] * 4 + ([C.c_int, c_int32_p] if mapped else [])
+            + ([c_double_p, c_double_p] if tie else [])
             + [vp, C.c_long, vp, vp, C.c_long, vp] + ([vp] if mapped else []) + [vp] * 3)
 
 
@@ -135,6 +136,8 @@ SIGNATURES = {
     "blsq_model_eval_nan_dev": _model_eval([C.c_int] * 4 + _COMP),                # est, sampling, nan_policy, model
     # ... and after the table S, shared, t_sstride (B is G)
     "blsq_model_eval_global_dev": _model_eval([C.c_int] * 4 + _COMP + [C.c_int, c_int32_p, C.c_long]),
+    # ... and behind pmap tie_ratio, tie_offset (host doubles [n]); S == 0: a plain batch
+    "blsq_model_eval_tie_dev": _model_eval([C.c_int] * 4 + _COMP + [C.c_int, c_int32_p, C.c_long], tie=True),
 }
 
 _lib = None

@@ -155,7 +155,8 @@ def curve_fit(f, xdata, ydata, p0=None, sigma=None, absolute_sigma=False, check_
     ``curve_fit_batch`` omits them inside the kernel); 'propagate' is not supported, as in scipy.
 
     fixed, tied : hold parameters at their `p0` (a boolean mask (n,) or indices) and make parameter j a copy of
-    parameter i (``{j: i}``), as ``curve_fit_batch``; `p0` is then required (ValueError).  `f` and a callable `jac`
+    parameter i (``{j: i}``; ``{j: (i, ratio, offset)}``: p_j = ratio * p_i + offset), as ``curve_fit_batch``; `p0` is
+    then required (ValueError).  `f` and a callable `jac`
     still take and return all n parameters; the solver works on the nf remaining variables (``jac=None`` differentiates
     those), `popt` (n,) has the fixed values and tied copies filled in, `pcov` (n, n) has zero rows and columns for
     fixed parameters and copied ones for tied parameters, and the degrees of freedom are m - nf.
@@ -335,7 +336,11 @@ def curve_fit_batch(f, xdata, ydata, p0, sigma=None, absolute_sigma=False, bound
     fixed : None, a boolean mask (n,) or a sequence of indices, shared by all problems: parameter j of problem b is
             held at ``p0[b, j]`` (its bounds are ignored).
     tied : None or ``{j: i}``: parameter j is a copy of parameter i (its own `p0` is ignored; the box of the group
-            is the intersection of its members' boxes).  See ``bounded_lsq.ParamMap`` for the rules.
+            is the intersection of its members' boxes).  See ``bounded_lsq.ParamMap`` for the rules.  A value may be
+            ``(i, ratio)`` or ``(i, ratio, offset)``: p_j = ratio * p_i + offset, two floats shared by
+            all problems; `popt`, `pcov`, ``active_mask`` and ``x_covariance`` of the member carry them, its box is
+            moved through the tie before the intersection, and for a named model on the device driver the model
+            kernel applies them (blsq_model_eval_tie_dev).
             The solver then works on the nf <= n remaining variables: `p0` and `bounds` are still given for all n,
             a callable `f` / `jac` still takes (B, n) and returns (B, m) / (B, m, n), finite differences are taken
             over the nf variables, and a named model with driver='device' is evaluated through the map on the GPU

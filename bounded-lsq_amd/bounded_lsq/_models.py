@@ -61,6 +61,11 @@ Global fits (``global_map=``; blsq_model_eval_global_dev).  With a
 ``DeviceModel`` / ``DeviceFit`` evaluates G groups of S data sets, a group being one problem of S m rows over the
 nv = ns + S nl variables of the map; ``GlobalMap`` IS the definition of the layout and the kernel follows it bit for bit.
 One coordinate and point sampling only.
+
+Affine ties (``tied={j: (i, ratio, offset)}``; blsq_model_eval_tie_dev).  Where the ``ParamMap`` of a fit
+(``param_map``, or ``global_map.pm``) has ``affine`` set, ``DeviceModel`` hands its ``ratio`` and ``offset`` to the one
+entry that takes them, for batch and global fits and under every flag above; ``ParamMap`` IS the definition
+(``expand_x``: ratio * x + offset; ``reduce_jac``: the columns times their ratios) and the kernel follows it bit for bit.
 """
 import re
 
@@ -900,7 +905,11 @@ class DeviceModel:
     J) and ``n_model`` stays the model's n; `xdata` is (m,), (S, m) or (G, S, m), `ydata` (G, S, m), `sigma` a scalar,
     (m,), (S, m) or (G, S, m), `Pfix` (G, S, n) (required where a parameter is fixed), `set_bounds` takes the reduced
     bounds, and the callbacks go through blsq_model_eval_global_dev alone.  `param_map` must be None (the map has its
-    own), the model must have one coordinate and `binned` must be False (ValueError)."""
+    own), the model must have one coordinate and `binned` must be False (ValueError).
+
+    Affine ties: where ``param_map.affine`` (``global_map.pm.affine``) is true the callbacks go through
+    blsq_model_eval_tie_dev alone, whatever the other flags are, with the map's ``ratio`` and ``offset``; otherwise
+    through the entry they went through before that one existed."""
 
     def __init__(self, ctx, name, B, m, n, xdata, ydata=None, sigma=None, param_map=None, Pfix=None, estimator='lse',
                  binned=False, nan_policy='propagate', global_map=None):
@@ -1025,6 +1034,12 @@ class DeviceModel:
         flags = [ESTIMATORS.index(self.estimator), SAMPLING.index('bin' if self.binned else 'point'),
                  NAN_POLICIES.index(self.nan_policy)]
         kind = [-1 if comp else M.id] + table
+        pm = self.param_map if self.global_map is None else self.global_map.pm
+        if pm is not None and pm.affine:                      # ... then S (0: a plain batch), shared, t_sstride
+            if self.global_map is None:
+                return "blsq_model_eval_tie_dev", flags + kind + [0, None, 0]
+            return "blsq_model_eval_tie_dev", flags + kind + [
+                self.global_map.S, self._shared.ctypes.data_as(_abi.c_int32_p), self.t_sstride]
         if self.global_map is not None:                       # ... then S, shared, t_sstride
             return "blsq_model_eval_global_dev", flags + kind + [
                 self.global_map.S, self._shared.ctypes.data_as(_abi.c_int32_p), self.t_sstride]
@@ -1046,7 +1061,12 @@ class DeviceModel:
         gm = self.global_map
         pmap = None if self.param_map is None and gm is None else self._pmap.ctypes.data_as(_abi.c_int32_p)
         m, nf = (self.m, self.n) if gm is None else (self._m_set, gm.nf)         # a global entry: per data set
-        self._call = (name, lead + [self.B], [m, self.n_model] + ([nf, pmap] if mapped else [])
+        tie = []
+        if name == "blsq_model_eval_tie_dev":                 # ... and behind pmap the ratios and offsets (host arrays)
+            pm = self.param_map if gm is None else gm.pm
+            self._tie = [np.ascontiguousarray(a, dtype=np.float64) for a in (pm.ratio, pm.offset)]
+            tie = [a.ctypes.data_as(_abi.c_double_p) for a in self._tie]
+        self._call = (name, lead + [self.B], [m, self.n_model] + ([nf, pmap] if mapped else []) + tie
                       + [self.d_t, self.t_stride, self.d_y, self.d_w, self.w_stride], [self.d_Pfix] if mapped else [])
 
     def _eval(self, x_ptr, reps, f_ptr, J_ptr, mask_ptr):

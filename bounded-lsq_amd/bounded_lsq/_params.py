@@ -16,6 +16,17 @@ blsq_model_eval_map_dev) compute the same numbers bit for bit.
 A tie ``{j: i}`` makes p_j a copy of p_i.  The parameter i that a group follows is its *leader*: it is neither fixed
 nor itself tied, its value is the group's solver variable and its ``p0`` is the group's start.  Slots are numbered in
 ascending order of the leaders.  Needs neither the library nor a GPU.
+
+Affine ties.  A tie ``{j: (i, ratio)}`` or ``{j: (i, ratio, offset)}`` makes
+p_j = ratio * p_i + offset, with `ratio` (default 1, not 0) and `offset` (default 0) Python floats shared by all
+problems.  With ratio[j] and offset[j] the pair of parameter j ((1, 0) for a leader, a fixed parameter and a plain tie):
+
+    P_full[..., j]  = ratio[j] * X[..., pmap[j]] + offset[j]     the product first, then the sum; where the pair is
+                                                                 (1, 0) the plain copy above (so -0.0 stays -0.0)
+    J_map[..., k]   = sum over {j : pmap[j] == k}, in ascending j, of ratio[j] * J_full[..., j]
+
+The first column of a slot is taken as it is after its multiply; a key below its leader arrives first and carries its
+ratio.  The affine kernel instances (blsq_model_eval_tie_dev) compute these numbers bit for bit.
 """
 import numpy as np
 
@@ -26,12 +37,16 @@ class ParamMap:
     """The map of n model parameters onto nf solver variables.
 
     fixed : None, a boolean mask (n,) or a sequence of indices: parameters held at their template value
-    tied  : None or a dict ``{j: i}``: p_j is p_i.  i must be free (not fixed, not a key of `tied`), j != i.
+    tied  : None or a dict ``{j: i}``: p_j is p_i.  i must be free (not fixed, not a key of `tied`), j != i.  A value
+            may also be a tuple ``(i, ratio)`` or ``(i, ratio, offset)`` (``(i,)`` is ``i``): p_j = ratio * p_i + offset.
     ValueError (naming the index) for an index outside 0 .. n - 1, a key or target of `tied` that is fixed, a target
-    that is itself a key, j == i, and a map that leaves nothing to fit.
+    that is itself a key, j == i, and a map that leaves nothing to fit; (naming the key) for a ratio that is 0 or not
+    finite, an offset that is not finite and a tuple of the wrong length.
 
     Attributes: ``n``, ``nf``, ``pmap`` (n,) int32 (-1: fixed, else the slot), ``leaders`` (nf,) (the parameter whose
-    value is solver variable k), ``fixed`` (n,) bool, ``tied`` (the dict), ``identity`` (nothing fixed, nothing tied).
+    value is solver variable k), ``fixed`` (n,) bool, ``tied`` (the dict ``{j: i}`` of ints, whatever form the values
+    had), ``identity`` (nothing fixed, nothing tied), ``ratio`` (n,) and ``offset`` (n,) float64 (1 and 0 for leaders,
+    fixed parameters and plain ties), ``affine`` (some pair differs from (1, 0)).
     """
 
     def __init__(self, n, fixed=None, tied=None):
@@ -50,12 +65,24 @@ class ParamMap:
                     if int(j) != j or not 0 <= int(j) < n:
                         raise ValueError("`fixed` index %r is outside 0 .. %d." % (j, n - 1))
                     fx[int(j)] = True
-        td = {}
+        td, pairs = {}, {}
         for j, i in (dict(tied) if tied else {}).items():
+            r, d = 1.0, 0.0
+            if isinstance(i, (tuple, list)):
+                if not 1 <= len(i) <= 3:
+                    raise ValueError("`tied` value of key %r must be i, (i, ratio) or (i, ratio, offset), not %d "
+                                     "entries." % (j, len(i)))
+                i, r, d = (tuple(i) + (1.0, 0.0)[len(i) - 1:])
             for what, v in (("key", j), ("target", i)):
                 if int(v) != v or not 0 <= int(v) < n:
                     raise ValueError("`tied` %s %r is outside 0 .. %d." % (what, v, n - 1))
+            r, d = float(r), float(d)
+            if r == 0.0 or not np.isfinite(r):
+                raise ValueError("`tied` ratio %r of key %d must be finite and not 0." % (r, int(j)))
+            if not np.isfinite(d):
+                raise ValueError("`tied` offset %r of key %d must be finite." % (d, int(j)))
             td[int(j)] = int(i)
+            pairs[int(j)] = (r, d)
         for j, i in td.items():
             if j == i:
                 raise ValueError("`tied` ties parameter %d to itself." % j)
@@ -80,6 +107,11 @@ class ParamMap:
         self.tied = td
         self.identity = self.nf == n
         self._free = np.flatnonzero(pmap >= 0)
+        self.ratio, self.offset = np.ones(n), np.zeros(n)
+        for j, (r, d) in pairs.items():
+            self.ratio[j], self.offset[j] = r, d
+        self._aff = np.flatnonzero((self.ratio != 1.0) | (self.offset != 0.0))  # the members that are no plain copy
+        self.affine = bool(self._aff.size)
 
     def __repr__(self):
         return "ParamMap(n=%d, nf=%d, pmap=%s)" % (self.n, self.nf, self.pmap.tolist())
@@ -99,17 +131,22 @@ class ParamMap:
         return self._last(P, self.n, "P")[..., self.leaders]
 
     def expand_x(self, X, Pfix):
-        """(..., nf) and the template (..., n) -> (..., n): copies only.  Of `Pfix` the fixed columns are read."""
+        """(..., nf) and the template (..., n) -> (..., n): copies, and for a member whose (ratio, offset) is not (1, 0)
+        ``ratio * X[..., k] + offset``, the product first.  Of `Pfix` the fixed columns are read."""
         X = self._last(X, self.nf, "X")
         Pfix = self._last(Pfix, self.n, "Pfix")
         out = np.empty(np.broadcast_shapes(X.shape[:-1], Pfix.shape[:-1]) + (self.n,),
                        dtype=np.result_type(X.dtype, Pfix.dtype))
         out[...] = Pfix
         out[..., self._free] = X[..., self.pmap[self._free]]
+        if self.affine:
+            a = self._aff
+            out[..., a] = self.ratio[a] * X[..., self.pmap[a]] + self.offset[a]
         return out
 
     def reduce_jac(self, J_full):
-        """(..., m, n) -> (..., m, nf): per slot the sequential sum of its columns in ascending j."""
+        """(..., m, n) -> (..., m, nf): per slot the sequential sum, in ascending j, of ``ratio[j]`` times column j (a
+        column whose ratio is 1 is taken as it is)."""
         J_full = self._last(J_full, self.n, "J_full")
         out = np.empty(J_full.shape[:-1] + (self.nf,), dtype=J_full.dtype)
         started = np.zeros(self.nf, dtype=bool)
@@ -117,18 +154,26 @@ class ParamMap:
             k = self.pmap[j]
             if k < 0:
                 continue
+            col = J_full[..., j] if self.ratio[j] == 1.0 else self.ratio[j] * J_full[..., j]
             if started[k]:
-                out[..., k] = out[..., k] + J_full[..., j]
+                out[..., k] = out[..., k] + col
             else:
-                out[..., k] = J_full[..., j]
+                out[..., k] = col
                 started[k] = True
         return out
 
     def reduce_bounds(self, lb, ub):
         """(..., n) bounds -> (..., nf): the box of a slot is the intersection of its members' boxes; bounds of fixed
-        parameters are ignored.  ValueError naming the group where the intersection is empty."""
+        parameters are ignored.  A member with (ratio r, offset d) constrains the slot to [(lb - d) / r, (ub - d) / r],
+        the ends swapped for r < 0.  ValueError naming the group where the intersection is empty."""
         lb = self._last(lb, self.n, "lb").astype(float)
         ub = self._last(ub, self.n, "ub").astype(float)
+        if self.affine:
+            lb, ub = np.broadcast_arrays(lb, ub)
+            lb, ub = lb.copy(), ub.copy()
+            for j in self._aff:
+                lo_j, hi_j = (lb[..., j] - self.offset[j]) / self.ratio[j], (ub[..., j] - self.offset[j]) / self.ratio[j]
+                lb[..., j], ub[..., j] = (lo_j, hi_j) if self.ratio[j] > 0 else (hi_j, lo_j)
         lo = np.empty(lb.shape[:-1] + (self.nf,))
         hi = np.empty(ub.shape[:-1] + (self.nf,))
         for k in range(self.nf):
@@ -142,27 +187,34 @@ class ParamMap:
         return lo, hi
 
     def expand_cov(self, C):
-        """(..., nf, nf) -> (..., n, n) = T C T^T with T the 0/1 matrix of the map: zero rows and columns for fixed
-        parameters, copies for tied ones.  No arithmetic."""
+        """(..., nf, nf) -> (..., n, n) = T C T^T with T the matrix of the map (``matrix()``): zero rows and columns for
+        fixed parameters, ``ratio[j] * ratio[l] * C[k_j, k_l]`` for tied ones.  Without affine ties: copies, no
+        arithmetic."""
         C = self._last(C, self.nf, "C")
         if C.ndim < 2 or C.shape[-2] != self.nf:
             raise ValueError("`C` must have shape (..., nf, nf).")
         out = np.zeros(C.shape[:-2] + (self.n, self.n), dtype=C.dtype)
         s = self.pmap[self._free]
         out[..., self._free[:, None], self._free[None, :]] = C[..., s[:, None], s[None, :]]
+        if self.affine:
+            out = (self.ratio[:, None] * self.ratio[None, :]) * out
         return out
 
     def expand_mask(self, mask):
-        """active_mask (..., nf) -> (..., n): 0 for a fixed parameter, the leader's value for a tied one."""
+        """active_mask (..., nf) -> (..., n): 0 for a fixed parameter, the leader's value for a tied one, times the sign
+        of its ratio (under a negative ratio the member sits on its other bound)."""
         mask = self._last(mask, self.nf, "mask")
         out = np.zeros(mask.shape[:-1] + (self.n,), dtype=mask.dtype)
         out[..., self._free] = mask[..., self.pmap[self._free]]
+        if self.affine:
+            neg = np.flatnonzero(self.ratio < 0)
+            out[..., neg] = -out[..., neg]
         return out
 
     def matrix(self):
-        """T (n, nf): T[j, pmap[j]] = 1."""
+        """T (n, nf): T[j, pmap[j]] = ratio[j] (1 without affine ties)."""
         T = np.zeros((self.n, self.nf))
-        T[self._free, self.pmap[self._free]] = 1.0
+        T[self._free, self.pmap[self._free]] = self.ratio[self._free]
         return T
 
     # ---- numpy callables over the solver's variables -------------------------------------------------------------
@@ -188,6 +240,8 @@ class GlobalMap:
 
     ``column(k, s)`` is the variable of slot k in data set s.  The methods below ARE the definition, in the way
     ``ParamMap``'s are: blsq_model_eval_global_dev (csrc/model_kernels.hip) computes the same numbers bit for bit.
+    Affine ties (``tied={j: (i, ratio, offset)}``) act inside every data set through ``self.pm``; the
+    rules of `shared` do not change, and the kernel entry is then blsq_model_eval_tie_dev.
 
     shared : a boolean mask (n,) or a sequence of indices.  ValueError (naming the index) for an index outside
              0 .. n - 1, a fixed index, a tied key whose leader is not in `shared`, and an empty `shared` (nothing is
@@ -265,7 +319,8 @@ class GlobalMap:
         return X[..., self.cols]
 
     def expand_x(self, X, Pfix):
-        """(..., nv) and the template (..., S, n) -> (..., S, n): copies only.  Of `Pfix` the fixed columns are read."""
+        """(..., nv) and the template (..., S, n) -> (..., S, n): ``ParamMap.expand_x`` of every data set's variables
+        (copies; ``ratio * x + offset`` for an affine tie).  Of `Pfix` the fixed columns are read."""
         return self.pm.expand_x(self.split_x(X), self._sets(Pfix, self.n, "Pfix"))
 
     def reduce_jac(self, J_full):
@@ -301,18 +356,21 @@ class GlobalMap:
 
     def expand_cov(self, C):
         """(..., nv, nv) -> (..., S, n, n): the block ``T_s C T_s^T`` of every data set (``ParamMap.expand_cov`` of the
-        rows and columns of its variables).  No arithmetic; the cross-data-set terms stay in `C`."""
+        rows and columns of its variables: copies, times the ratios of affine ties).  The cross-data-set terms stay in
+        `C`."""
         C = np.asarray(C)
         if C.ndim < 2 or C.shape[-2:] != (self.nv, self.nv):
             raise ValueError("`C` must have shape (..., nv, nv) = (..., %d, %d), not %s." % (self.nv, self.nv, C.shape))
         return np.stack([self.pm.expand_cov(C[..., c[:, None], c[None, :]]) for c in self.cols], axis=-3)
 
     def expand_mask(self, mask):
-        """active_mask (..., nv) -> (..., S, n): 0 for a fixed parameter, its variable's value otherwise."""
+        """active_mask (..., nv) -> (..., S, n): 0 for a fixed parameter, its variable's value otherwise (times the sign
+        of the ratio of an affine tie)."""
         return self.pm.expand_mask(self.split_x(mask))
 
     def matrix(self):
-        """T (S n, nv): row s n + j has a 1 in the column of parameter j of data set s (none where j is fixed)."""
+        """T (S n, nv): row s n + j has ``ratio[j]`` (1 without affine ties) in the column of parameter j of data set s
+        (nothing where j is fixed)."""
         T = np.zeros((self.S * self.n, self.nv))
         Tp = self.pm.matrix()
         for s in range(self.S):

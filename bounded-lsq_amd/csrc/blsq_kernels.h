@@ -616,7 +616,7 @@ hipError_t launch_fd_assemble(int B, int m, int n, int method, const double* x, 
 // table behind blsq_term_info, the entries' check of n and the launcher's.
 constexpr int MODEL_TERM_PARAMS[] = {3, 3, 4, 2, 1};
 
-// One evaluation of model_kernels.hip (the seven blsq_model_eval*_dev entries, 7j to 7p): f [B * reps][m] and / or
+// One evaluation of model_kernels.hip (the eight blsq_model_eval*_dev entries, 7j to 7q): f [B * reps][m] and / or
 // J [B][m][nf] (reps == 1) at X [B * reps][nf].  The fit's flags pick the kernel instance; everything else is data.
 struct ModelEvalCall {
   int est;                // BLSQ_EST_*: POISSON is the deviance residual and its Jacobian; needs y, and w == nullptr
@@ -644,9 +644,15 @@ struct ModelEvalCall {
   const int* shared;      // [nf] on the host: 1 where slot k is one variable of the group, 0 where one per data set
   long t_sstride;         // t of data set s of group b: t + b * t_stride + s * t_sstride (each 0 or the rows it skips);
                           // w: stride 0 ([m], every data set) or S m ([B][S m])
+  // Affine ties (blsq_model_eval_tie_dev, 7q): both nullptr (the plain map) or both [n] on the host, next to pmap:
+  // parameter j with pmap[j] >= 0 is tie_ratio[j] * X[.][pmap[j]] + tie_offset[j], and its column of J enters its slot
+  // times tie_ratio[j].  Entries at fixed parameters are not read.  Picks the AFFINE kernel instance.
+  const double* tie_ratio;
+  const double* tie_offset;
 };
 // hipErrorInvalidValue, and nothing launched, for a flag, model or table out of range, a y the flags need, a w under
-// POISSON, or a size the grid or LDS cannot hold: the refusals that keep the kernel's offsets in bounds.
+// POISSON, tie_ratio / tie_offset of which one is missing or which come without a pmap, or a size the grid or LDS
+// cannot hold: the refusals that keep the kernel's offsets in bounds.
 hipError_t launch_model_eval(const ModelEvalCall& c, hipStream_t s);
 
 // ---------------------------------------------------------------- probes ----

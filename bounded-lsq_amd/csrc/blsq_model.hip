@@ -1,9 +1,11 @@
 // Built-in fit models (include/blsq.h; kernel: model_kernels.hip): the model and term tables behind
-// blsq_model_count / _info and blsq_term_count / _info, and the seven entries blsq_model_eval_dev, _map_dev, _comp_dev,
-// _est_dev, _bin_dev, _nan_dev and _global_dev.  An entry fills a ModelEvalCall from its arguments (what its signature
+// blsq_model_count / _info and blsq_term_count / _info, and the eight entries blsq_model_eval_dev, _map_dev, _comp_dev,
+// _est_dev, _bin_dev, _nan_dev, _global_dev and _tie_dev.  An entry fills a ModelEvalCall from its arguments (what its signature
 // does not have is the default) and hands it to model_eval_checked with its EvalEntry: one list of checks, one launcher, and per entry
 // only the argument numbers.
 #include "blsq_host.h"
+
+#include <cmath>
 
 namespace {
 
@@ -56,19 +58,23 @@ extern "C" int blsq_term_info(int term, const char** name, int* n_per_term) {
 
 namespace {
 
-// What tells the seven entries apart: the label of the launch, the kinds of model the entry takes, and the number a
+// What tells the eight entries apart: the label of the launch, the kinds of model the entry takes, and the number a
 // bad argument is reported by: its position in the entry's signature (ctx = 1; 0: the entry has no such argument).  The
 // arguments come in runs that every signature has in the same order, so a run is given by its first number: fam and cnt
 // follow ncomp; reps, m, n follow B; pmap follows nf; t_stride, y, w, w_stride, X follow t; J follows f.  The contents of
 // pmap have no argument of their own: an entry outside -1 .. nf - 1 is `pmap_entry`, an unused variable the number after
 // (the two past the entry's last argument).
 // The global entry (7p) has one more run: shared and t_sstride follow S (`S` == 0: the entry has none of the three).
+// The tie entry (7q) has that run and one more: tie_offset follows tie_ratio (`tie` == 0: the entry has neither).  Their
+// contents are reported as pmap's are, by the two numbers after pmap's two: a ratio that is 0 or not finite, an offset
+// that is not finite.  With the run of S the tie entry also takes S == 0: a plain batch, not a global evaluation.
 struct EvalEntry {
   const char* label;
   bool composite;             // takes model == -1 with a component table (otherwise named models only)
   bool needs_pmap;
   int est, sampling, nan_policy, model, ncomp, B, nf, t, Pfix, f, pmap_entry;
   int S;
+  int tie;
 };
 constexpr EvalEntry kEvalDev = {"launch_model_eval", false, false, 0, 0, 0, 2, 0, 3, 0, 7, 0, 13, 0};
 constexpr EvalEntry kEvalMap = {"launch_model_eval_map", false, true, 0, 0, 0, 2, 0, 3, 7, 9, 15, 16, 19};
@@ -77,6 +83,7 @@ constexpr EvalEntry kEvalEst = {"launch_model_eval_est", true, false, 2, 0, 0, 3
 constexpr EvalEntry kEvalBin = {"launch_model_eval_bin", true, false, 2, 3, 0, 4, 5, 8, 12, 14, 20, 21, 24};
 constexpr EvalEntry kEvalNan = {"launch_model_eval_nan", true, false, 2, 3, 4, 5, 6, 9, 13, 15, 21, 22, 25};
 constexpr EvalEntry kEvalGlobal = {"launch_model_eval_global", true, true, 2, 3, 4, 5, 6, 12, 16, 18, 24, 25, 28, 9};
+constexpr EvalEntry kEvalTie = {"launch_model_eval_tie", true, true, 2, 3, 4, 5, 6, 12, 16, 20, 26, 27, 30, 9, 18};
 
 // The checks of every entry, in the order of the arguments, and the launch.  A negative return names the argument.
 int model_eval_checked(blsq_ctx* ctx, const EvalEntry& e, const ModelEvalCall& c) {
@@ -90,7 +97,7 @@ int model_eval_checked(blsq_ctx* ctx, const EvalEntry& e, const ModelEvalCall& c
     return ctx->bad(e.model, e.composite ? "model must be one of BLSQ_MODEL_*, or -1 for a composite"
                                          : "model must be one of BLSQ_MODEL_*");
   const bool comp = c.model < 0;
-  const bool global = e.S != 0;
+  const bool global = e.S != 0 && !(e.tie != 0 && c.S == 0);      // the tie entry with S == 0: a plain batch
   if (global && c.sampling != BLSQ_SAMPLE_POINT)
     return ctx->bad(e.sampling, "sampling must be BLSQ_SAMPLE_POINT: a global fit takes no bin-integrated model");
   if (global && !comp && kModels[c.model].coords != 1)
@@ -111,8 +118,10 @@ int model_eval_checked(blsq_ctx* ctx, const EvalEntry& e, const ModelEvalCall& c
     }
   }
   if (global) {
-    if (c.S < 1) return ctx->bad(e.S, "S must be positive");
+    if (c.S < 1) return ctx->bad(e.S, e.tie ? "S must be 0 (a plain batch) or positive" : "S must be positive");
     if (!c.shared) return ctx->bad(e.S + 1, "shared is NULL");
+  } else if (e.S != 0 && c.t_sstride != 0) {
+    return ctx->bad(e.S + 2, "t_sstride must be 0 with S == 0");
   }
   if (c.B <= 0) return ctx->bad(e.B, "B must be positive");
   if (c.reps <= 0) return ctx->bad(e.B + 1, "reps must be positive");
@@ -137,6 +146,16 @@ int model_eval_checked(blsq_ctx* ctx, const EvalEntry& e, const ModelEvalCall& c
     }
     for (int k = 0; k < nf; ++k)
       if (!used[k]) return ctx->bad(e.pmap_entry + 1, "pmap leaves a variable k < nf unused");
+    if (c.tie_ratio || c.tie_offset) {         // (only the tie entry fills them)
+      if (!c.tie_ratio) return ctx->bad(e.tie, "tie_ratio is NULL although tie_offset is given");
+      if (!c.tie_offset) return ctx->bad(e.tie + 1, "tie_offset is NULL although tie_ratio is given");
+      for (int j = 0; j < n; ++j) {
+        if (c.pmap[j] < 0) continue;           // a fixed parameter: its entries are not read
+        if (c.tie_ratio[j] == 0.0 || !std::isfinite(c.tie_ratio[j]))
+          return ctx->bad(e.pmap_entry + 2, "tie_ratio entry must be finite and not 0");
+        if (!std::isfinite(c.tie_offset[j])) return ctx->bad(e.pmap_entry + 3, "tie_offset entry must be finite");
+      }
+    }
   }
   if (global) {                              // nv = ns + S nl variables
     long ns = 0;
@@ -241,4 +260,16 @@ extern "C" int blsq_model_eval_global_dev(blsq_ctx* ctx, int est, int sampling, 
   return model_eval_checked(ctx, kEvalGlobal, {est, sampling, nan_policy, model, ncomp, fam, cnt, G, reps, m, n, nf,
                                                pmap, dt, t_stride, dy, dw, w_stride, dX, dPfix, df, dJ, dmask, S,
                                                shared, t_sstride});
+}
+
+extern "C" int blsq_model_eval_tie_dev(blsq_ctx* ctx, int est, int sampling, int nan_policy, int model, int ncomp,
+                                       const int32_t* fam, const int32_t* cnt, int S, const int32_t* shared,
+                                       long t_sstride, int G, int reps, int m, int n, int nf, const int32_t* pmap,
+                                       const double* tie_ratio, const double* tie_offset, const double* dt,
+                                       long t_stride, const double* dy, const double* dw, long w_stride,
+                                       const double* dX, const double* dPfix, double* df, double* dJ,
+                                       const int32_t* dmask) {
+  return model_eval_checked(ctx, kEvalTie, {est, sampling, nan_policy, model, ncomp, fam, cnt, G, reps, m, n, nf, pmap,
+                                            dt, t_stride, dy, dw, w_stride, dX, dPfix, df, dJ, dmask, S,
+                                            S > 0 ? shared : nullptr, t_sstride, tie_ratio, tie_offset});
 }

@@ -73,6 +73,20 @@
 // of NaN multiplies the nf staged slots only), LDS does not depend on nv, and the waves per workgroup are the mapped
 // instance's.  MAP is a template parameter for the reason given for POISSON; the bin-integrated and gauss2d global
 // instances are not built (20 instances more: 116).
+//
+// Affine instances (AFFINE = true; blsq_model_eval_tie_dev with tie_ratio / tie_offset).  A tied parameter
+// follows its slot by a ratio and an offset, P_full[q][j] = ratio[j] * X[q][.] + offset[j]; ratio[] and offset[], 64
+// doubles each, travel by value in the kernel arguments behind everything the instance without the flag takes (TieArgs:
+// 1 KB more, 1504 bytes for the composite global instance, under the 4 KB of the kernarg segment), so nothing is
+// staged in LDS and the waves per workgroup are unchanged.  Two places differ.  The expansion: lane j computes v = p[k]
+// and then r * v + d, the product first, where (r, d) != (1, 0), and keeps v otherwise (a -0.0 stays -0.0); parameters
+// held at Pfix are untouched.  row_put: the value of column k is multiplied by ratio[k] before it is stored into, or
+// added to, its slot: r * (wi * e), the model's weighted column first; k is wave-uniform, so ratio[k] is a scalar load, as
+// the walk over the component table is.  The Poisson row pass, the OMIT branch and both stream-outs see slots that are
+// summed already and are untouched.  The terms take the map as a deduced type (const signed char*, or the pair TieMap), so
+// the instances without the flag are instantiated over the types they had, and AFFINE is a template flag for the reason
+// given for POISSON: the 116 instances without it are the instructions they were.  Built for every mapped and global
+// instance, gauss2d's mapped ones included (68 instances more: 184); the file builds in 13.5 s where the 116 took 8.4 s.
 #include "../../include/blsq.h"
 #include "blsq_device.h"
 #include "blsq_kernels.h"
@@ -118,20 +132,32 @@ struct ModelGlobalArgs : ModelMapArgs {
   long t_sstride;               // t of data set s of group g: t + g * t_stride + s * t_sstride
 };
 template <class Base> struct CompArgs : Base { CompTable tab; };
+// An affine launch (7q): parameter j with pm[j] >= 0 is ratio[j] * (its slot's variable) + offset[j]; (1, 0) elsewhere.
+// By value behind everything the instance without the flag takes, so that instance's arguments keep their offsets.
+template <class Base> struct TieArgs : Base { double ratio[MODEL_ROWS], offset[MODEL_ROWS]; };
 static constexpr int MODEL_COMPOSITE = -1;            // the MODEL of the composite instances (no BLSQ_MODEL_* id)
 // MAP: how the solver's variables become the model's parameters
 static constexpr int MAP_NONE = 0, MAP_PARAM = 1, MAP_GLOBAL = 2;
-template <bool COMP, int MAP> struct ModelArgsOf { using type = ModelArgs; };
-template <> struct ModelArgsOf<false, MAP_PARAM> { using type = ModelMapArgs; };
-template <> struct ModelArgsOf<false, MAP_GLOBAL> { using type = ModelGlobalArgs; };
-template <> struct ModelArgsOf<true, MAP_NONE> { using type = CompArgs<ModelArgs>; };
-template <> struct ModelArgsOf<true, MAP_PARAM> { using type = CompArgs<ModelMapArgs>; };
-template <> struct ModelArgsOf<true, MAP_GLOBAL> { using type = CompArgs<ModelGlobalArgs>; };
+template <bool COMP, int MAP> struct ModelArgsBase { using type = ModelArgs; };
+template <> struct ModelArgsBase<false, MAP_PARAM> { using type = ModelMapArgs; };
+template <> struct ModelArgsBase<false, MAP_GLOBAL> { using type = ModelGlobalArgs; };
+template <> struct ModelArgsBase<true, MAP_NONE> { using type = CompArgs<ModelArgs>; };
+template <> struct ModelArgsBase<true, MAP_PARAM> { using type = CompArgs<ModelMapArgs>; };
+template <> struct ModelArgsBase<true, MAP_GLOBAL> { using type = CompArgs<ModelGlobalArgs>; };
+template <bool COMP, int MAP, bool AFFINE = false> struct ModelArgsOf {
+  using Base = typename ModelArgsBase<COMP, MAP>::type;
+  using type = std::conditional_t<AFFINE, TieArgs<Base>, Base>;
+};
+static_assert(sizeof(TieArgs<CompArgs<ModelGlobalArgs>>) <= 4096, "the largest argument struct fits the kernarg segment");
 
 __device__ __forceinline__ int map_nf(const ModelArgs& A) { return A.n; }
 __device__ __forceinline__ int map_nf(const ModelMapArgs& A) { return A.nf; }
 __device__ __forceinline__ const signed char* map_pm(const ModelArgs&) { return nullptr; }
 __device__ __forceinline__ const signed char* map_pm(const ModelMapArgs& A) { return A.pm; }
+// What row_put needs of an affine instance's arguments: pm[] and ratio[], both indexed by the model's column.  The terms
+// below take the map as a deduced type PM: const signed char* (as map_pm gives it) or this pair.
+struct TieMap { const signed char* pm; const double* ratio; };
+template <class Base> __device__ __forceinline__ TieMap map_pm(const TieArgs<Base>& A) { return {A.pm, A.ratio}; }
 __device__ __forceinline__ const double* map_pfix(const ModelArgs&) { return nullptr; }
 __device__ __forceinline__ const double* map_pfix(const ModelMapArgs& A) { return A.Pfix; }
 
@@ -146,13 +172,18 @@ __device__ __forceinline__ void row_put(double* row, const signed char* pm, int 
     else if (c >= 0) row[c] = v;
   }
 }
+// Affine: the mapped put of ratio[k] * v.  k is wave-uniform, so ratio[k] is a scalar load from the kernel arguments.
+template <bool MAPPED>
+__device__ __forceinline__ void row_put(double* row, TieMap map, int k, double v) {
+  row_put<true>(row, map.pm, k, map.ratio[k] * v);
+}
 
 // ---- the terms.  Each evaluates one term whose parameters start at p[o], writes its columns o .. of the lane's J row
 // through row_put (row == nullptr: f only) and returns the term's value.
 #define PUT(k, v) row_put<MAPPED>(row, pm, (k), (v))
-template <bool MAPPED>
+template <bool MAPPED, class PM>
 __device__ __forceinline__ double exp_term(const double* __restrict__ p, int o, double t, double wi, double* row,
-                                           const signed char* pm) {
+                                           PM pm) {
   const double a = p[o], r = p[o + 1];
   const double e = exp(-(r * t));
   const double g = a * e;
@@ -160,9 +191,9 @@ __device__ __forceinline__ double exp_term(const double* __restrict__ p, int o, 
   return g;
 }
 
-template <bool LORENTZ, bool MAPPED>
+template <bool LORENTZ, bool MAPPED, class PM>
 __device__ __forceinline__ double peak_term(const double* __restrict__ p, int o, double t, double wi, double* row,
-                                            const signed char* pm) {
+                                            PM pm) {
   const double a = p[o], mu = p[o + 1], s = p[o + 2];
   const double z = (t - mu) / s;
   double e, g, dmu;
@@ -180,9 +211,9 @@ __device__ __forceinline__ double peak_term(const double* __restrict__ p, int o,
 }
 
 // pseudo-Voigt (a, mu, s, eta): s is the half width at half maximum of both parts (the operations)
-template <bool MAPPED>
+template <bool MAPPED, class PM>
 __device__ __forceinline__ double pvoigt_term(const double* __restrict__ p, int o, double t, double wi, double* row,
-                                              const signed char* pm) {
+                                              PM pm) {
   constexpr double LN2 = 0.6931471805599453;
   const double a = p[o], mu = p[o + 1], s = p[o + 2], eta = p[o + 3];
   const double z = (t - mu) / s;
@@ -201,9 +232,9 @@ __device__ __forceinline__ double pvoigt_term(const double* __restrict__ p, int 
 }
 
 // polynomial of d coefficients p[o .. o + d): the value by Horner, the columns t^k by repeated product
-template <bool MAPPED>
+template <bool MAPPED, class PM>
 __device__ __forceinline__ double poly_terms(const double* __restrict__ p, int o, int d, double t, double wi,
-                                             double* row, const signed char* pm) {
+                                             double* row, PM pm) {
   double acc = p[o + d - 1];
   for (int k = d - 2; k >= 0; --k) acc = acc * t + p[o + k];          // Horner
   if (row) {
@@ -252,9 +283,9 @@ __device__ __forceinline__ void psi_pair(double x, double& ps, double& dp) {
   }
 }
 
-template <bool MAPPED>
+template <bool MAPPED, class PM>
 __device__ __forceinline__ double exp_bin(const double* __restrict__ p, int o, double lo, double hi, double wi,
-                                          double* row, const signed char* pm) {
+                                          double* row, PM pm) {
   const double a = p[o], r = p[o + 1];
   const double w = hi - lo;
   double ps, dp;
@@ -265,9 +296,9 @@ __device__ __forceinline__ double exp_bin(const double* __restrict__ p, int o, d
   return a * da;
 }
 
-template <bool LORENTZ, bool MAPPED>
+template <bool LORENTZ, bool MAPPED, class PM>
 __device__ __forceinline__ double peak_bin(const double* __restrict__ p, int o, double lo, double hi, double wi,
-                                           double* row, const signed char* pm) {
+                                           double* row, PM pm) {
   const double a = p[o], mu = p[o + 1], s = p[o + 2];
   const double zl = (lo - mu) / s, zh = (hi - mu) / s;
   double da;
@@ -285,9 +316,9 @@ __device__ __forceinline__ double peak_bin(const double* __restrict__ p, int o, 
   return g;
 }
 
-template <bool MAPPED>
+template <bool MAPPED, class PM>
 __device__ __forceinline__ double pvoigt_bin(const double* __restrict__ p, int o, double lo, double hi, double wi,
-                                             double* row, const signed char* pm) {
+                                             double* row, PM pm) {
   constexpr double LN2 = 0.6931471805599453;
   const double a = p[o], mu = p[o + 1], s = p[o + 2], eta = p[o + 3];
   const double zl = (lo - mu) / s, zh = (hi - mu) / s;
@@ -312,9 +343,9 @@ __device__ __forceinline__ double pvoigt_bin(const double* __restrict__ p, int o
 
 // polynomial of d coefficients over the bin: column k is (hi^(k+1) - lo^(k+1)) / (k + 1), the powers by repeated product;
 // the value the sequential sum of p_k times its column
-template <bool MAPPED>
+template <bool MAPPED, class PM>
 __device__ __forceinline__ double poly_bin(const double* __restrict__ p, int o, int d, double lo, double hi, double wi,
-                                           double* row, const signed char* pm) {
+                                           double* row, PM pm) {
   double ph = hi, pl = lo, acc = 0.0;
   for (int k = 0; k < d; ++k) {
     const double c = (ph - pl) / (double)(k + 1);
@@ -327,10 +358,10 @@ __device__ __forceinline__ double poly_bin(const double* __restrict__ p, int o, 
 }
 
 // The bin-integrated terms of one row of a named model: the family's terms and 'poly*1', as the composite walks them.
-template <int MODEL, bool MAPPED>
+template <int MODEL, bool MAPPED, class PM>
 __device__ __forceinline__ double model_row_bin(int n, int m, const double* __restrict__ tb, int i,
                                                 const double* __restrict__ p, double wi, double* row,
-                                                const signed char* pm) {
+                                                PM pm) {
   const double lo = tb[i], hi = tb[m + i];
   if (MODEL == BLSQ_MODEL_POLY) return poly_bin<MAPPED>(p, 0, n, lo, hi, wi, row, pm);
   if (MODEL == BLSQ_MODEL_EXP_SUM) {
@@ -374,10 +405,10 @@ __device__ __forceinline__ double model_row_bin(int n, int m, const double* __re
 }
 
 // The terms of one row.  `row` is the lane's slice of the wave's LDS tile (nullptr: f only); returns the model value.
-template <int MODEL, bool MAPPED>
+template <int MODEL, bool MAPPED, class PM>
 __device__ __forceinline__ double model_row(int n, int m, const double* __restrict__ tb, int i,
                                             const double* __restrict__ p, double wi, double* row,
-                                            const signed char* pm) {
+                                            PM pm) {
   if (MODEL == BLSQ_MODEL_POLY) return poly_terms<MAPPED>(p, 0, n, tb[i], wi, row, pm);
   if (MODEL == BLSQ_MODEL_EXP_SUM) {
     const double t = tb[i];
@@ -420,9 +451,9 @@ __device__ __forceinline__ double model_row(int n, int m, const double* __restri
 
 // The row of a composite: the walk over the table.  c, fam, cnt and the offset o are wave-uniform.
 // BINNED: t is lo and hi the bin's upper edge; otherwise hi is not read.
-template <bool MAPPED, bool BINNED>
+template <bool MAPPED, bool BINNED, class PM>
 __device__ __forceinline__ double comp_row(const CompTable& tab, double t, double hi, const double* __restrict__ p,
-                                           double wi, double* row, const signed char* pm) {
+                                           double wi, double* row, PM pm) {
   double acc = 0.0;
   int o = 0;                                   // first parameter, and first column, of the component
   unsigned long long ent = tab.lo;
@@ -498,9 +529,10 @@ __device__ __forceinline__ void poisson_rc(double mu, double y, double& r, doubl
   }
 }
 
-template <int MODEL, int MAP, bool POISSON, bool BINNED, bool OMIT>
+template <int MODEL, int MAP, bool POISSON, bool BINNED, bool OMIT, bool AFFINE>
 __global__ __launch_bounds__(256) void model_eval_kernel(
-    typename ModelArgsOf<MODEL == MODEL_COMPOSITE, MAP>::type A) {
+    typename ModelArgsOf<MODEL == MODEL_COMPOSITE, MAP, AFFINE>::type A) {
+  static_assert(!AFFINE || MAP != MAP_NONE, "an affine tie is part of a map");
   constexpr bool MAPPED = MAP != MAP_NONE, GLOBAL = MAP == MAP_GLOBAL;
   extern __shared__ double model_tiles[];
   const int lane = threadIdx.x & (WAVE - 1);
@@ -537,10 +569,22 @@ __global__ __launch_bounds__(256) void model_eval_kernel(
   if constexpr (MAPPED) {
     double* pv = model_tiles + (size_t)wave * MODEL_ROWS;
     if (live && lane < n) {
-      const int c = map_pm(A)[lane];
+      const int c = A.pm[lane];
       int k = c & (MODEL_ROWS - 1);
       if constexpr (GLOBAL) k = k < A.ns ? k : k + s * A.nl;                    // a local slot: data set s's window
-      pv[lane] = c < 0 ? map_pfix(A)[b * n + lane] : p[k];
+      if constexpr (AFFINE) {              // r v + d, the product first; a plain copy where (r, d) == (1, 0)
+        double v;
+        if (c < 0) {
+          v = map_pfix(A)[b * n + lane];
+        } else {
+          v = p[k];
+          const double r = A.ratio[lane], d = A.offset[lane];
+          if (r != 1.0 || d != 0.0) v = r * v + d;
+        }
+        pv[lane] = v;
+      } else {
+        pv[lane] = c < 0 ? map_pfix(A)[b * n + lane] : p[k];
+      }
     }
     __syncthreads();                       // (the wave reads only its own vector; every wave arrives)
     p = pv;
@@ -614,44 +658,48 @@ __global__ __launch_bounds__(256) void model_eval_kernel(
   }
 }
 
-// The launch of instance <MODEL, MAPPED> with the flags `inst`: POISSON | BINNED << 1 | OMIT << 2.  The eight kernels
-// take the same arguments: the part of `all` that the instance has.
-// Instance <MODEL, MAP> with the flags; nullptr for the bin-integrated global instances, which are not built.
-template <int MODEL, int MAP, bool POISSON, bool BINNED, bool OMIT>
-static constexpr auto model_instance() -> void (*)(typename ModelArgsOf<MODEL == MODEL_COMPOSITE, MAP>::type) {
+// The launch of instance <MODEL, MAP, AFFINE> with the flags `inst`: POISSON | BINNED << 1 | OMIT << 2.  The eight
+// kernels take the same arguments: the part of `all` that the instance has.
+// Instance <MODEL, MAP, AFFINE> with the flags; nullptr for the bin-integrated global instances, which are not built.
+using AllModelArgs = TieArgs<CompArgs<ModelGlobalArgs>>;
+template <int MODEL, int MAP, bool AFFINE, bool POISSON, bool BINNED, bool OMIT>
+static constexpr auto model_instance() -> void (*)(typename ModelArgsOf<MODEL == MODEL_COMPOSITE, MAP, AFFINE>::type) {
   if constexpr (MAP == MAP_GLOBAL && BINNED) return nullptr;
-  else return model_eval_kernel<MODEL, MAP, POISSON, BINNED, OMIT>;
+  else return model_eval_kernel<MODEL, MAP, POISSON, BINNED, OMIT, AFFINE>;
 }
 
-template <int MODEL, int MAP>
+template <int MODEL, int MAP, bool AFFINE>
 static hipError_t launch_model_instance(int inst, dim3 g, dim3 blk, size_t lds, hipStream_t s,
-                                        const CompArgs<ModelGlobalArgs>& all) {
-  using Args = typename ModelArgsOf<MODEL == MODEL_COMPOSITE, MAP>::type;
+                                        const AllModelArgs& all) {
+  using Args = typename ModelArgsOf<MODEL == MODEL_COMPOSITE, MAP, AFFINE>::type;
   static void (*const kernels[8])(Args) = {
-      model_instance<MODEL, MAP, false, false, false>(), model_instance<MODEL, MAP, true, false, false>(),
-      model_instance<MODEL, MAP, false, true, false>(),  model_instance<MODEL, MAP, true, true, false>(),
-      model_instance<MODEL, MAP, false, false, true>(),  model_instance<MODEL, MAP, true, false, true>(),
-      model_instance<MODEL, MAP, false, true, true>(),   model_instance<MODEL, MAP, true, true, true>()};
+      model_instance<MODEL, MAP, AFFINE, false, false, false>(), model_instance<MODEL, MAP, AFFINE, true, false, false>(),
+      model_instance<MODEL, MAP, AFFINE, false, true, false>(),  model_instance<MODEL, MAP, AFFINE, true, true, false>(),
+      model_instance<MODEL, MAP, AFFINE, false, false, true>(),  model_instance<MODEL, MAP, AFFINE, true, false, true>(),
+      model_instance<MODEL, MAP, AFFINE, false, true, true>(),   model_instance<MODEL, MAP, AFFINE, true, true, true>()};
   if (!kernels[inst]) return hipErrorInvalidValue;
   Args A;
-  static_cast<typename ModelArgsOf<false, MAP>::type&>(A) = all;
+  static_cast<typename ModelArgsBase<false, MAP>::type&>(A) = all;
   if constexpr (MODEL == MODEL_COMPOSITE) A.tab = all.tab;
+  if constexpr (AFFINE)
+    for (int j = 0; j < MODEL_ROWS; ++j) { A.ratio[j] = all.ratio[j]; A.offset[j] = all.offset[j]; }
   hipLaunchKernelGGL(kernels[inst], g, blk, lds, s, A);
   return hipGetLastError();
 }
 
-template <int MAP>
+template <int MAP, bool AFFINE>
 static hipError_t launch_model_kind(int model, int inst, dim3 g, dim3 blk, size_t lds, hipStream_t s,
-                                    const CompArgs<ModelGlobalArgs>& all) {
+                                    const AllModelArgs& all) {
   switch (model) {
-    case MODEL_COMPOSITE: return launch_model_instance<MODEL_COMPOSITE, MAP>(inst, g, blk, lds, s, all);
-    case BLSQ_MODEL_POLY: return launch_model_instance<BLSQ_MODEL_POLY, MAP>(inst, g, blk, lds, s, all);
-    case BLSQ_MODEL_EXP_SUM: return launch_model_instance<BLSQ_MODEL_EXP_SUM, MAP>(inst, g, blk, lds, s, all);
-    case BLSQ_MODEL_GAUSS_SUM: return launch_model_instance<BLSQ_MODEL_GAUSS_SUM, MAP>(inst, g, blk, lds, s, all);
-    case BLSQ_MODEL_LORENTZ_SUM: return launch_model_instance<BLSQ_MODEL_LORENTZ_SUM, MAP>(inst, g, blk, lds, s, all);
+    case MODEL_COMPOSITE: return launch_model_instance<MODEL_COMPOSITE, MAP, AFFINE>(inst, g, blk, lds, s, all);
+    case BLSQ_MODEL_POLY: return launch_model_instance<BLSQ_MODEL_POLY, MAP, AFFINE>(inst, g, blk, lds, s, all);
+    case BLSQ_MODEL_EXP_SUM: return launch_model_instance<BLSQ_MODEL_EXP_SUM, MAP, AFFINE>(inst, g, blk, lds, s, all);
+    case BLSQ_MODEL_GAUSS_SUM: return launch_model_instance<BLSQ_MODEL_GAUSS_SUM, MAP, AFFINE>(inst, g, blk, lds, s, all);
+    case BLSQ_MODEL_LORENTZ_SUM:
+      return launch_model_instance<BLSQ_MODEL_LORENTZ_SUM, MAP, AFFINE>(inst, g, blk, lds, s, all);
     case BLSQ_MODEL_GAUSS2D:                                 // two coordinates: no global instance
       if constexpr (MAP == MAP_GLOBAL) return hipErrorInvalidValue;
-      else return launch_model_instance<BLSQ_MODEL_GAUSS2D, MAP>(inst, g, blk, lds, s, all);
+      else return launch_model_instance<BLSQ_MODEL_GAUSS2D, MAP, AFFINE>(inst, g, blk, lds, s, all);
     default: return hipErrorInvalidValue;
   }
 }
@@ -665,7 +713,9 @@ hipError_t launch_model_eval(const ModelEvalCall& c, hipStream_t s) {
   if (c.n < 1 || c.n > MODEL_ROWS) return hipErrorInvalidValue;
   const bool global = c.S > 0;
   if (global && (bin || !c.pmap || !c.shared)) return hipErrorInvalidValue;
-  CompArgs<ModelGlobalArgs> A;
+  const bool affine = c.tie_ratio || c.tie_offset;
+  if (affine && (!c.tie_ratio || !c.tie_offset || !c.pmap)) return hipErrorInvalidValue;
+  AllModelArgs A;
   A.m = c.m; A.n = c.n; A.reps = c.reps; A.tiles = (c.m + MODEL_ROWS - 1) / MODEL_ROWS;
   A.items = (long)c.B * c.reps * (global ? c.S : 1) * A.tiles;
   A.t = c.t; A.t_stride = c.t_stride; A.y = c.y; A.w = c.w; A.w_stride = c.w_stride; A.P = c.X; A.f = c.f; A.J = c.J;
@@ -695,6 +745,8 @@ hipError_t launch_model_eval(const ModelEvalCall& c, hipStream_t s) {
         seen[c.pmap[j]] = true;
       }
       A.pm[j] = (signed char)k;
+      A.ratio[j] = (affine && k >= 0) ? c.tie_ratio[j] : 1.0;      // entries of fixed parameters are not read
+      A.offset[j] = (affine && k >= 0) ? c.tie_offset[j] : 0.0;
     }
   }
   A.tab = {};
@@ -719,9 +771,13 @@ hipError_t launch_model_eval(const ModelEvalCall& c, hipStream_t s) {
   if (grid <= 0 || grid > 0x7fffffffL) return hipErrorInvalidValue;
   const int inst = (int)poisson | (int)bin << 1 | (int)omit << 2;
   const dim3 g((unsigned)grid), blk(64 * wpb);
-  if (global) return launch_model_kind<MAP_GLOBAL>(c.model, inst, g, blk, wave_bytes * wpb, s, A);
-  return c.pmap ? launch_model_kind<MAP_PARAM>(c.model, inst, g, blk, wave_bytes * wpb, s, A)
-                : launch_model_kind<MAP_NONE>(c.model, inst, g, blk, wave_bytes * wpb, s, A);
+  const size_t lds = wave_bytes * wpb;
+  if (affine)
+    return global ? launch_model_kind<MAP_GLOBAL, true>(c.model, inst, g, blk, lds, s, A)
+                  : launch_model_kind<MAP_PARAM, true>(c.model, inst, g, blk, lds, s, A);
+  if (global) return launch_model_kind<MAP_GLOBAL, false>(c.model, inst, g, blk, lds, s, A);
+  return c.pmap ? launch_model_kind<MAP_PARAM, false>(c.model, inst, g, blk, lds, s, A)
+                : launch_model_kind<MAP_NONE, false>(c.model, inst, g, blk, lds, s, A);
 }
 
 }  // namespace blsq

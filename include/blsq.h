@@ -561,6 +561,33 @@ int blsq_model_eval_global_dev(blsq_ctx* ctx, int est, int sampling, int nan_pol
                                long t_stride, const double* dy, const double* dw, long w_stride, const double* dX,
                                const double* dPfix, double* df, double* dJ, const int32_t* dmask);
 
+/* Affine ties: a tied parameter that follows its slot by a ratio and an offset,
+ *   P_full[q][j] = tie_ratio[j] * X[q][.] + tie_offset[j]   where pmap[j] >= 0 (X[q][.]: the variable of slot pmap[j], as
+ *                  in the entry this one extends; the product first, then the sum; where the pair is (1, 0) the plain
+ *                  copy, so a -0.0 stays -0.0),            Pfix[b][j] where pmap[j] == -1
+ *   f            = the f of blsq_model_eval_nan_dev at P_full, bit for bit
+ *   J[..][i][k]  = sum over {j : pmap[j] == k}, in ascending j, of tie_ratio[j] * (the J[i][j] of blsq_model_eval_nan_dev
+ *                  at P_full): the model's weighted column first, then the ratio; the first column of a slot is stored
+ *                  after its multiply and the later ones are added to it.  Under BLSQ_EST_POISSON the slot is multiplied
+ *                  by c after its sum, as without ties.
+ * The signature is that of blsq_model_eval_global_dev with tie_ratio and tie_offset directly behind pmap: HOST pointers,
+ * double [n] each, read during the call (they travel in the kernel arguments, as pmap does); entries at fixed parameters
+ * (pmap[j] == -1) are not read.  Both NULL: the plain map.  S >= 1: a global evaluation by the rules of
+ * blsq_model_eval_global_dev (and with both NULL its outputs, bit for bit).  S == 0: a plain batch of G problems by the
+ * rules of blsq_model_eval_nan_dev with a pmap (and with both NULL its outputs): shared is ignored, t_sstride must be
+ * 0, and BLSQ_SAMPLE_BIN and GAUSS2D are taken.  pmap is required.  A negative return is the index of the bad argument
+ * (ctx = 1, est = 2, sampling = 3, nan_policy = 4, model = 5, ncomp = 6, fam = 7, cnt = 8, S = 9, shared = 10,
+ * t_sstride = 11, G = 12, reps, m, n = 15, nf = 16, pmap = 17, tie_ratio = 18, tie_offset = 19, t = 20, t_stride = 21,
+ * y = 22, w = 23, w_stride, X = 25, Pfix = 26, f = 27, J = 28, mask); exactly one of tie_ratio / tie_offset NULL is the
+ * number of the NULL one; for the contents of pmap -30 and -31 as above, and for a j with pmap[j] >= 0 -32 (a ratio that
+ * is 0 or not finite) and -33 (an offset that is not finite).  Nothing is launched then. */
+int blsq_model_eval_tie_dev(blsq_ctx* ctx, int est, int sampling, int nan_policy, int model, int ncomp,
+                            const int32_t* fam, const int32_t* cnt, int S, const int32_t* shared, long t_sstride, int G,
+                            int reps, int m, int n, int nf, const int32_t* pmap, const double* tie_ratio,
+                            const double* tie_offset, const double* dt, long t_stride, const double* dy,
+                            const double* dw, long w_stride, const double* dX, const double* dPfix, double* df,
+                            double* dJ, const int32_t* dmask);
+
 /* ---- parameter covariance from the final Jacobian --------------------------------------------------------------
  * The reference documents `x_covariance` as the inverse of J^T J at the solution (least_squares.py:248-252) and fills
  * it only through its MINPACK bridge (method='lm').  Here, per problem, from a Householder triangle R of J (the TSQR

@@ -14,6 +14,12 @@ and next to them for the composite 'gauss*K+poly*1' (the same mode
 of blsq_model_eval_comp_dev), at the same size and on the same buffers' shapes.  `--rounds` repeats the timed block: the
 figure is the median of the rounds' means, and `*_all` lists every round.
 
+``--tied`` also takes ``j:i:ratio[:offset]`` (p_j = ratio * p_i + offset): the named route then runs the affine
+kernel instances (blsq_model_eval_tie_dev), the callable route the same ``wrap_f`` / ``wrap_jac``.  With ``--kernel`` the
+affine and the plain mapped instance are timed on the same map: for plain ties the keys `affine_*` are the affine
+instance with every ratio 1 and offset 0, for affine ties the keys `plain_*` are the plain instance on the map without
+its ratios and offsets.
+
 ``--estimator poisson`` fits counts instead: the same lines 40 times as high (60 counts at the peak over a
 background of 12), drawn from the Poisson law, sigma None; the named route runs the Poisson kernel instances, the callable
 route the numpy wrappers.  Without it nothing here changes.
@@ -35,7 +41,7 @@ fit on the device route (blsq_model_eval_global_dev) against the callable route 
 kernel time per slot, and `gram_share`, the part of it spent in the slots whose name holds 'gram': the measured case
 for or against a structured solve.  With ``--kernel``: the launches of the global entry alone, f and J.
 
-usage: python tools/bench_models.py [--B 4096] [--m 64] [--repeat 5] [--peaks 1] [--fixed 1,4] [--tied 5:2] [--kernel]
+usage: python tools/bench_models.py [--B 4096] [--m 64] [--repeat 5] [--peaks 1] [--fixed 1,4] [--tied 5:2,4:1:1:0.42] [--kernel]
                                     [--launches 50] [--rounds 1] [--estimator lse] [--binned] [--omit FRACTION]
                                     [--global S --shared 1,2]
 """
@@ -70,8 +76,9 @@ def problems(B, m, seed=0, peaks=1, fixed=(), tied=None, poisson=False, binned=F
         base[0:-1:3] *= m / 4.0
         base[-1] *= m / 4.0
     truth = base * (1 + 0.05 * rng.uniform(-1, 1, (B, base.size)))
-    for j, i in (tied or {}).items():
-        truth[:, j] = truth[:, i]
+    for j, v in (tied or {}).items():
+        i, r, d = (tuple(v) + (1.0, 0.0)[len(v) - 1:]) if isinstance(v, tuple) else (v, 1.0, 0.0)
+        truth[:, j] = r * truth[:, i] + d
     if common:
         S, idx = common
         for j in idx:
@@ -107,6 +114,13 @@ def kernel_times(ctx, x, Y, P0, pm, launches, rounds=1, estimator="lse", binned=
     cases = [("unmapped", "gauss_sum", None), ("composite", spec, None)]
     if pm is not None:
         cases += [("mapped", "gauss_sum", pm), ("composite_mapped", spec, pm)]
+        if pm.affine:                           # the plain instance on the same map, without its ratios and offsets
+            other = ParamMap(pm.n, pm.fixed, pm.tied)
+            cases += [("plain", "gauss_sum", other), ("composite_plain", spec, other)]
+        else:                                   # the affine instance on the same map: every ratio 1, every offset 0
+            other = ParamMap(pm.n, pm.fixed, pm.tied)
+            other.affine = True
+            cases += [("affine", "gauss_sum", other), ("composite_affine", spec, other)]
     for key, name, mp in cases:
         dm = models.DeviceModel(ctx, name, B, m, n, x, Y, 0.01 if estimator == "lse" else None, param_map=mp,
                                 Pfix=None if mp is None else P0, estimator=estimator, **({"binned": True} if binned else {}),
@@ -214,7 +228,7 @@ def main():
     ap.add_argument("--repeat", type=int, default=5)
     ap.add_argument("--peaks", type=int, default=1, choices=sorted(PEAKS))
     ap.add_argument("--fixed", default="", help="indices held at p0, e.g. 1,4")
-    ap.add_argument("--tied", default="", help="j:i pairs (p_j is p_i), e.g. 5:2")
+    ap.add_argument("--tied", default="", help="j:i pairs (p_j is p_i), e.g. 5:2, or j:i:ratio[:offset] (p_j = ratio * p_i + offset)")
     ap.add_argument("--kernel", action="store_true", help="time the kernel's launches alone")
     ap.add_argument("--launches", type=int, default=50)
     ap.add_argument("--rounds", type=int, default=1, help="with --kernel: timed blocks of --launches launches each")
@@ -237,7 +251,13 @@ def main():
     if a.omit is not None and not 0.0 <= a.omit < 1.0:
         ap.error("--omit takes a fraction in [0, 1)")
     fixed = [int(v) for v in a.fixed.split(",") if v]
-    tied = {int(p.split(":")[0]): int(p.split(":")[1]) for p in a.tied.split(",") if p}
+    tied = {}
+    for p in a.tied.split(","):
+        v = p.split(":")
+        if p and not 2 <= len(v) <= 4:
+            ap.error("--tied takes j:i, j:i:ratio or j:i:ratio:offset")
+        if p:
+            tied[int(v[0])] = int(v[1]) if len(v) == 2 else (int(v[1]),) + tuple(float(q) for q in v[2:])
     poisson = a.estimator == "poisson"
     x, Y, P0, bounds = problems(a.B, a.m, peaks=a.peaks, fixed=fixed, tied=tied, poisson=poisson, binned=a.binned)
     n = P0.shape[1]
