@@ -6,6 +6,7 @@ them); the solve is this package's ``least_squares`` and ``pcov`` is the pseudo-
 computed on the GPU (``covariance='pinv'``) where scipy takes an SVD on the host.
 """
 import warnings
+from collections import namedtuple
 from inspect import getfullargspec
 
 import numpy as np
@@ -312,6 +313,159 @@ def _curve_fit_mapped(pm, f, xdata, ydata, p0, sigma, absolute_sigma, check_fini
     return (pm.expand_x(out[0], Pfix), pm.expand_cov(out[1])) + tuple(out[2:])
 
 
+# What `_fit` needs to know of its caller's data: `lead` (B,) or (G, S), the shape in front of the m points of one data
+# set (with m: the shapes a per-problem `sigma` may have); `Y` (problems, rows), one row per problem of the solver;
+# `P0` lead + (n,), the start and the template of the map; `make_map` () -> ParamMap, GlobalMap or None;
+# `xdata` (xdata, model or None) -> (what a callable receives, what the device receives); and the texts that differ.
+_Layout = namedtuple('_Layout', 'lead m Y P0 make_map xdata none_left propagate_hint sigma_2d')
+
+
+def _fit(lay, f, xdata, sigma, absolute_sigma, bounds, method, jac, driver, ctx, estimator, binned, nan_policy, kwargs):
+    """``curve_fit_batch`` and ``curve_fit_global`` between their shape checks and their results: the checks of the
+    keywords in their order, the residual and Jacobian of the solver's variables (on the device: a ``DeviceFit``) and
+    the solve.  Returns ``(results, map, no_dof)``: `results` with ``nobs`` / ``omitted`` and ``deviance`` set,
+    `no_dof` (problems,) true where the covariance has no variance factor to be scaled by."""
+    problems, rows = lay.Y.shape
+    Y, P0 = lay.Y, lay.P0
+    ydata = Y.reshape(lay.lead + (lay.m,))
+    n = P0.shape[-1]
+    omitted = nobs = None
+    if nan_policy == 'raise':
+        if np.isnan(ydata).any():
+            raise ValueError("The input contains nan values")
+    elif nan_policy == 'omit':
+        omitted = np.isnan(ydata)
+        kept = np.sum(~omitted, axis=-1)
+        if not kept.all():
+            raise ValueError(lay.none_left % tuple(int(i) for i in np.argwhere(kept == 0)[0][::-1]))
+        nobs = kept.reshape(problems, -1).sum(axis=1).astype(np.int32)
+    elif nan_policy is not None:
+        raise ValueError("`nan_policy` must be None, 'raise' or 'omit', not %r%s." % (
+            nan_policy, lay.propagate_hint if nan_policy == 'propagate' else ""))
+    poisson = _check_poisson(estimator, sigma, ydata, omitted)
+    mp = lay.make_map()
+    model = None
+    if binned and not isinstance(f, (str, _models.CompositeModel)):
+        raise ValueError("`binned=True` needs a built-in model (a name, a spec or a CompositeModel) as `f`: a callable "
+                         "integrates itself over its bins.")
+    if isinstance(f, (str, _models.CompositeModel)):
+        model = _models.resolve(f)
+        model.terms(n)
+        host_model = _models.binned(model) if binned else model         # whose numpy functions driver='host' calls
+        x_host, x_dev = lay.xdata(xdata, host_model)
+        if callable(jac):
+            raise ValueError("a callable `jac` cannot be combined with the built-in model '%s'." % model.name)
+        if jac is not None and jac not in ('2-point', '3-point'):
+            raise ValueError("`jac` must be None, '2-point' or '3-point' with a built-in model.")
+        if driver not in ('host', 'device'):
+            raise ValueError("`driver` must be 'host' or 'device'.")
+        if driver == 'host':                     # the numpy functions through the callable path below
+            f = host_model.f
+            if jac is None:
+                jac = host_model.jac
+    else:
+        x_host, x_dev = lay.xdata(xdata, None)
+        if jac is None:
+            jac = '2-point'
+
+    transform = None
+    if sigma is not None:
+        sigma = np.asarray(sigma, float)
+        try:
+            w, per_problem = _models.sigma_weights(sigma, lay.lead, lay.m, omitted)
+        except ValueError:
+            if lay.sigma_2d is None or sigma.ndim != 2:
+                raise
+            raise ValueError(lay.sigma_2d) from None
+        # along the rows of a problem; a scalar stays one (numpy multiplies by it in one flat loop)
+        transform = w.reshape(problems, rows) if per_problem else np.tile(w, rows // lay.m) if w.ndim else w
+
+    if mp is not None:                           # the solver sees nf (nv) variables; f and jac see all n
+        if len(bounds) != 2:
+            raise ValueError("`bounds` must contain 2 elements.")
+        bounds = mp.reduce_bounds(np.broadcast_to(np.asarray(bounds[0], dtype=float), P0.shape),
+                                  np.broadcast_to(np.asarray(bounds[1], dtype=float), P0.shape))
+        x_start = mp.reduce_x(P0)
+        if callable(f):
+            f = mp.wrap_f(f, P0)
+        if callable(jac):
+            jac = mp.wrap_jac(jac, P0)
+    else:
+        x_start = P0
+    nv = x_start.shape[1]                        # solver variables: n, nf, or nv of a group
+
+    if model is not None and driver == 'device':
+        func = _models.DeviceFit(model.name, n, x_dev, ydata, sigma, Pfix=None if mp is None else P0,
+                                 **{'global_map' if isinstance(mp, GlobalMap) else 'param_map': mp},
+                                 **({'estimator': estimator} if poisson else {}),
+                                 **({'binned': True} if binned else {}),
+                                 **({'nan_policy': 'omit'} if omitted is not None else {}))
+    elif poisson:                                # (after the map: c multiplies the summed columns)
+        if callable(jac):
+            jac = _models.poisson_jacobian(f, jac, Y)
+        f_res = _models.poisson_residual(f, Y)
+
+        def func(X):
+            return np.asarray(f_res(x_host, X), float)
+    elif transform is None:
+        def func(X):
+            return np.asarray(f(x_host, X), float) - Y
+    else:
+        def func(X):
+            return transform * (np.asarray(f(x_host, X), float) - Y)
+
+    if callable(jac):
+        user_jac = jac
+        tj = None if transform is None else np.broadcast_to(transform, (problems, rows))[:, :, np.newaxis]
+
+        def jac(X):                                                        # noqa: F811
+            J = np.asarray(user_jac(x_host, X), float)
+            return J if tj is None else tj * J
+
+    if omitted is not None and callable(func):   # outermost: after sigma, the Poisson transform and the map
+        func = _models.omit_residual(func, Y)
+        if callable(jac):
+            jac = _models.omit_jacobian(jac, Y)
+
+    if 'args' in kwargs:
+        raise ValueError("'args' is not a supported keyword argument.")
+    if 'max_nfev' not in kwargs:
+        kwargs['max_nfev'] = kwargs.pop('maxfev', None)
+
+    scale_on_gpu = (not absolute_sigma) and rows > nv
+    results = least_squares_batch(func, x_start, jac, bounds=bounds, method=method, driver=driver, ctx=ctx,
+                                  covariance='pinv', _variance_scale=scale_on_gpu,
+                                  **({'_nobs': nobs} if nobs is not None else {}), **kwargs)
+    for b, r in enumerate(results):
+        if nobs is not None:
+            r.nobs, r.omitted = int(nobs[b]), omitted[b].copy()
+        if poisson:
+            r.deviance = float(np.dot(r.fun, r.fun))
+    points = np.full(problems, rows) if nobs is None else nobs
+    return results, mp, (points <= nv) & (not absolute_sigma)
+
+
+def _popt_pcov(results, shape, no_dof, popt_of, pcov_of):
+    """`popt` of `shape` and `pcov` from the results of the solve: NaN rows for a problem that did not converge, inf
+    under the ``OptimizeWarning`` where the covariance is missing, holds NaN or has no degree of freedom (`no_dof`)."""
+    popt = np.full(shape, np.nan)
+    pcov = np.full(shape + shape[-1:], np.nan)
+    warn_cov = False
+    for b, r in enumerate(results):
+        if not r.success:
+            continue
+        C = r.x_covariance
+        popt[b] = popt_of(r)
+        if C is None or np.isnan(C).any() or no_dof[b]:
+            pcov[b] = np.inf
+            warn_cov = True
+        else:
+            pcov[b] = pcov_of(C)
+    if warn_cov:
+        warnings.warn(_COV_WARNING, category=OptimizeWarning, stacklevel=3)
+    return popt, pcov
+
+
 def curve_fit_batch(f, xdata, ydata, p0, sigma=None, absolute_sigma=False, bounds=(-np.inf, np.inf), method='trf',
                     jac=None, driver='host', ctx=None, fixed=None, tied=None, estimator='lse', binned=False,
                     nan_policy=None, **kwargs):
@@ -419,116 +573,18 @@ def curve_fit_batch(f, xdata, ydata, p0, sigma=None, absolute_sigma=False, bound
     if P0.ndim != 2 or P0.shape[0] != B:
         raise ValueError("`p0` must have shape (B, n).")
     n = P0.shape[1]
-    omitted = nobs = None
-    if nan_policy == 'raise':
-        if np.isnan(ydata).any():
-            raise ValueError("The input contains nan values")
-    elif nan_policy == 'omit':
-        omitted = np.isnan(ydata)
-        nobs = _models.count_observed(ydata)
-        if not nobs.all():
-            raise ValueError("nan_policy='omit': problem %d has no point left, every entry of its `ydata` is NaN."
-                             % int(np.argmin(nobs != 0)))
-    elif nan_policy is not None:
-        raise ValueError("`nan_policy` must be None, 'raise' or 'omit', not %r%s." % (
-            nan_policy, " (a NaN passes through with None)" if nan_policy == 'propagate' else ""))
-    poisson = _check_poisson(estimator, sigma, ydata, omitted)
-    pm = _param_map(n, fixed, tied)
-    model = None
-    if binned and not isinstance(f, (str, _models.CompositeModel)):
-        raise ValueError("`binned=True` needs a built-in model (a name, a spec or a CompositeModel) as `f`: a callable "
-                         "integrates itself over its bins.")
-    if isinstance(f, (str, _models.CompositeModel)):
-        model = _models.resolve(f)
-        f = model.name
-        model.terms(n)
-        host_model = _models.binned(model) if binned else model         # whose numpy functions driver='host' calls
-        xdata, _ = host_model.check_xdata(xdata, B, m)
-        if callable(jac):
-            raise ValueError("a callable `jac` cannot be combined with the built-in model '%s'." % f)
-        if jac is not None and jac not in ('2-point', '3-point'):
-            raise ValueError("`jac` must be None, '2-point' or '3-point' with a built-in model.")
-        if driver not in ('host', 'device'):
-            raise ValueError("`driver` must be 'host' or 'device'.")
-        if driver == 'host':                     # the numpy functions through the callable path below
-            f = host_model.f
-            if jac is None:
-                jac = host_model.jac
-    elif jac is None:
-        jac = '2-point'
-    if isinstance(xdata, (list, tuple, np.ndarray)):
-        xdata = np.asarray(xdata, float)
 
-    transform = None
-    if sigma is not None:
-        sigma = np.asarray(sigma, float)
-        if sigma.size == 1 or sigma.shape == (m,) or sigma.shape == (B, m):
-            if omitted is not None and sigma.shape == (B, m):
-                sigma = np.where(omitted, 1.0, sigma)            # never used at an omitted point
-            transform = 1.0 / sigma
-        elif sigma.ndim == 2:
-            raise ValueError("a 2-D covariance `sigma` is not supported by `curve_fit_batch`.")
-        else:
-            raise ValueError("`sigma` has incorrect shape.")
-
-    if pm is not None:                           # the solver sees nf variables; f and jac see all n
-        if len(bounds) != 2:
-            raise ValueError("`bounds` must contain 2 elements.")
-        bounds = pm.reduce_bounds(np.broadcast_to(np.asarray(bounds[0], dtype=float), (B, n)),
-                                  np.broadcast_to(np.asarray(bounds[1], dtype=float), (B, n)))
-        x_start = pm.reduce_x(P0)
-        if callable(f):
-            f = pm.wrap_f(f, P0)
-        if callable(jac):
-            jac = pm.wrap_jac(jac, P0)
-    else:
-        x_start = P0
-    nv = x_start.shape[1]                        # solver variables: n, or nf
-
-    if model is not None and driver == 'device':
-        func = _models.DeviceFit(model.name, n, xdata, ydata, sigma, param_map=pm, Pfix=None if pm is None else P0,
-                                 **({'estimator': estimator} if poisson else {}),
-                                 **({'binned': True} if binned else {}),
-                                 **({'nan_policy': 'omit'} if omitted is not None else {}))
-    elif poisson:                                # (after the map: c multiplies the summed columns)
-        if callable(jac):
-            jac = _models.poisson_jacobian(f, jac, ydata)
-        f_res = _models.poisson_residual(f, ydata)
-
-        def func(P):
-            return np.asarray(f_res(xdata, P), float)
-    elif transform is None:
-        def func(P):
-            return np.asarray(f(xdata, P), float) - ydata
-    else:
-        def func(P):
-            return transform * (np.asarray(f(xdata, P), float) - ydata)
-
-    if callable(jac):
-        user_jac = jac
-        tj = None if transform is None else np.broadcast_to(transform, (B, m))[:, :, np.newaxis]
-
-        def jac(P):                                                        # noqa: F811
-            J = np.asarray(user_jac(xdata, P), float)
-            return J if tj is None else tj * J
-
-    if omitted is not None and callable(func):   # outermost: after sigma, the Poisson transform and the map
-        func = _models.omit_residual(func, ydata)
-        if callable(jac):
-            jac = _models.omit_jacobian(jac, ydata)
-
-    if 'args' in kwargs:
-        raise ValueError("'args' is not a supported keyword argument.")
-    if 'max_nfev' not in kwargs:
-        kwargs['max_nfev'] = kwargs.pop('maxfev', None)
-
-    scale_on_gpu = (not absolute_sigma) and m > nv
-    results = least_squares_batch(func, x_start, jac, bounds=bounds, method=method, driver=driver, ctx=ctx,
-                                  covariance='pinv', _variance_scale=scale_on_gpu,
-                                  **({'_nobs': nobs} if nobs is not None else {}), **kwargs)
-    if nobs is not None:
-        for b, r in enumerate(results):
-            r.nobs, r.omitted = int(nobs[b]), omitted[b].copy()
+    def xdata_of(xdata, model):                  # a named model checks its abscissae (or bin edges); one array for both
+        if model is not None:
+            xdata = model.check_xdata(xdata, B, m)[0]
+        elif isinstance(xdata, (list, tuple, np.ndarray)):
+            xdata = np.asarray(xdata, float)
+        return xdata, xdata
+    lay = _Layout((B,), m, ydata, P0, lambda: _param_map(n, fixed, tied), xdata_of,
+                  "nan_policy='omit': problem %d has no point left, every entry of its `ydata` is NaN.",
+                  " (a NaN passes through with None)", "a 2-D covariance `sigma` is not supported by `curve_fit_batch`.")
+    results, pm, no_dof = _fit(lay, f, xdata, sigma, absolute_sigma, bounds, method, jac, driver, ctx, estimator, binned,
+                               nan_policy, kwargs)
     if pm is not None:                           # the full-size fields of the results, expanded for the batch at once
         X_full = pm.expand_x(np.stack([r.x for r in results]), P0)
         masks = pm.expand_mask(np.stack([np.asarray(r.active_mask) for r in results]))
@@ -539,27 +595,7 @@ def curve_fit_batch(f, xdata, ydata, p0, sigma=None, absolute_sigma=False, bound
             r.x, r.active_mask = X_full[b], masks[b]
         for b, C in zip(has_cov, covs):
             results[b].x_covariance = C
-    if poisson:
-        for r in results:
-            r.deviance = float(np.dot(r.fun, r.fun))
-    popt = np.full((B, n), np.nan)
-    pcov = np.full((B, n, n), np.nan)
-    warn_cov = False
-    for b, r in enumerate(results):
-        if not r.success:
-            continue
-        C = r.x_covariance
-        bad_cov = (C is None or np.isnan(C).any()
-                   or (not absolute_sigma and (m if nobs is None else nobs[b]) <= nv))
-        popt[b] = r.x
-        if bad_cov:
-            pcov[b] = np.inf
-            warn_cov = True
-        else:
-            pcov[b] = C
-    if warn_cov:
-        warnings.warn(_COV_WARNING, category=OptimizeWarning, stacklevel=2)
-    return popt, pcov, results
+    return _popt_pcov(results, (B, n), no_dof, lambda r: r.x, lambda C: C) + (results,)
 
 
 GLOBAL_MAX_NV = 256                                      # BLSQ_GLOBAL_MAX_NV
@@ -624,129 +660,21 @@ def curve_fit_global(f, xdata, ydata, p0, shared, sigma=None, absolute_sigma=Fal
     if gm.nv > GLOBAL_MAX_NV:
         raise ValueError("the group has nv = ns + S nl = %d + %d * %d = %d variables, more than %d."
                          % (gm.ns, S, gm.nl, gm.nv, GLOBAL_MAX_NV))
-    M, nv = S * m, gm.nv
-    omitted = nobs = None
-    if nan_policy == 'raise':
-        if np.isnan(ydata).any():
-            raise ValueError("The input contains nan values")
-    elif nan_policy == 'omit':
-        omitted = np.isnan(ydata)
-        kept = np.sum(~omitted, axis=2)
-        if not kept.all():
-            g, s = (int(i) for i in np.argwhere(kept == 0)[0])
-            raise ValueError("nan_policy='omit': data set %d of group %d has no point left, every entry of its `ydata` "
-                             "is NaN." % (s, g))
-        nobs = kept.sum(axis=1).astype(np.int32)
-    elif nan_policy is not None:
-        raise ValueError("`nan_policy` must be None, 'raise' or 'omit', not %r." % (nan_policy,))
-    poisson = _check_poisson(estimator, sigma, ydata, omitted)
-    model = None
-    if isinstance(f, (str, _models.CompositeModel)):
-        model = _models.resolve(f)
-        model.terms(n)
-        _models._check_global(model, False, None)
-        if callable(jac):
-            raise ValueError("a callable `jac` cannot be combined with the built-in model '%s'." % model.name)
-        if jac is not None and jac not in ('2-point', '3-point'):
-            raise ValueError("`jac` must be None, '2-point' or '3-point' with a built-in model.")
-        if driver not in ('host', 'device'):
-            raise ValueError("`driver` must be 'host' or 'device'.")
-        if driver == 'host':
-            f = model.f
-            if jac is None:
-                jac = model.jac
-    elif jac is None:
-        jac = '2-point'
-    x_dev, gstride, sstride = _models.global_xdata(xdata, G, S, m)
-    # what a callable gets: (m,), or one row per data set of the batch
-    x_host = x_dev if not sstride else np.broadcast_to(x_dev, (G, S, m)).reshape(G * S, m)
 
-    Y = ydata.reshape(G, M)
-    transform = None
-    if sigma is not None:
-        sigma = np.asarray(sigma, float)
-        if sigma.size == 1:
-            transform = 1.0 / sigma
-        elif sigma.shape == (m,):
-            transform = np.tile(1.0 / sigma, S)
-        elif sigma.shape in ((S, m), (G, S, m)):
-            if omitted is not None and sigma.ndim == 3:
-                sigma = np.where(omitted, 1.0, sigma)            # never used at an omitted point
-            transform = (1.0 / sigma).reshape(sigma.shape[:-2] + (M,))
-        else:
-            raise ValueError("`sigma` has incorrect shape.")
-
-    if len(bounds) != 2:
-        raise ValueError("`bounds` must contain 2 elements.")
-    bounds = gm.reduce_bounds(np.broadcast_to(np.asarray(bounds[0], dtype=float), (G, S, n)),
-                              np.broadcast_to(np.asarray(bounds[1], dtype=float), (G, S, n)))
-    x_start = gm.reduce_x(P0)
-    if callable(f):
-        f = gm.wrap_f(f, P0)
-    if callable(jac):
-        jac = gm.wrap_jac(jac, P0)
-
-    if model is not None and driver == 'device':
-        func = _models.DeviceFit(model.name, n, x_dev, ydata, sigma, Pfix=P0, global_map=gm,
-                                 **({'estimator': estimator} if poisson else {}),
-                                 **({'nan_policy': 'omit'} if omitted is not None else {}))
-    elif poisson:                                # (after the map: c multiplies the scattered, summed columns)
-        if callable(jac):
-            jac = _models.poisson_jacobian(f, jac, Y)
-        f_res = _models.poisson_residual(f, Y)
-
-        def func(X):
-            return np.asarray(f_res(x_host, X), float)
-    elif transform is None:
-        def func(X):
-            return np.asarray(f(x_host, X), float) - Y
-    else:
-        def func(X):
-            return transform * (np.asarray(f(x_host, X), float) - Y)
-
-    if callable(jac):
-        user_jac = jac
-        tj = None if transform is None else np.broadcast_to(transform, (G, M))[:, :, np.newaxis]
-
-        def jac(X):                                                        # noqa: F811
-            J = np.asarray(user_jac(x_host, X), float)
-            return J if tj is None else tj * J
-
-    if omitted is not None and callable(func):   # outermost: after sigma, the Poisson transform and the map
-        func = _models.omit_residual(func, Y)
-        if callable(jac):
-            jac = _models.omit_jacobian(jac, Y)
-
-    if 'args' in kwargs:
-        raise ValueError("'args' is not a supported keyword argument.")
-    if 'max_nfev' not in kwargs:
-        kwargs['max_nfev'] = kwargs.pop('maxfev', None)
-
-    scale_on_gpu = (not absolute_sigma) and M > nv
-    results = least_squares_batch(func, x_start, jac, bounds=bounds, method=method, driver=driver, ctx=ctx,
-                                  covariance='pinv', _variance_scale=scale_on_gpu,
-                                  **({'_nobs': nobs} if nobs is not None else {}), **kwargs)
-    popt = np.full((G, S, n), np.nan)
-    pcov = np.full((G, S, n, n), np.nan)
-    warn_cov = False
+    def xdata_of(xdata, model):                  # a callable gets (m,), or one row per data set of the batch
+        if model is not None:
+            _models.check_global(model)
+        x_dev, _, sstride = _models.global_xdata(xdata, G, S, m)
+        return (x_dev if not sstride else np.broadcast_to(x_dev, (G, S, m)).reshape(G * S, m)), x_dev
+    lay = _Layout((G, S), m, ydata.reshape(G, S * m), P0, lambda: gm, xdata_of,
+                  "nan_policy='omit': data set %d of group %d has no point left, every entry of its `ydata` is NaN.",
+                  "", None)
+    results, _, no_dof = _fit(lay, f, xdata, sigma, absolute_sigma, bounds, method, jac, driver, ctx, estimator, False,
+                              nan_policy, kwargs)
     for g, r in enumerate(results):
         r.global_map = gm
         r.popt = gm.expand_x(r.x, P0[g])
-        if nobs is not None:
-            r.nobs, r.omitted = int(nobs[g]), omitted[g].copy()
-        if poisson:
-            r.deviance = float(np.dot(r.fun, r.fun))
-        if not r.success:
-            continue
-        C = r.x_covariance
-        popt[g] = r.popt
-        if (C is None or np.isnan(C).any() or (not absolute_sigma and (M if nobs is None else nobs[g]) <= nv)):
-            pcov[g] = np.inf
-            warn_cov = True
-        else:
-            pcov[g] = gm.expand_cov(C)
-    if warn_cov:
-        warnings.warn(_COV_WARNING, category=OptimizeWarning, stacklevel=2)
+    popt, pcov = _popt_pcov(results, (G, S, n), no_dof, lambda r: r.popt, gm.expand_cov)
     if single:
         return popt[0], pcov[0], results
     return popt, pcov, results

@@ -840,7 +840,7 @@ def pad_ragged(xs, ys):
     return xdata, ydata
 
 
-def _check_global(model, binned, param_map):
+def check_global(model, binned=False, param_map=None):
     """What a global fit does not take, as ValueErrors."""
     if binned:
         raise ValueError("`binned=True` is not supported in a global fit.")
@@ -865,14 +865,38 @@ def global_xdata(xdata, G, S, m):
                      % ((m,), (S, m), (G, S, m), x.shape))
 
 
-def global_ydata(ydata, G, S, m):
-    """None, or `ydata` (G, S, m) as the contiguous (G, S m) array the group's problem reads."""
-    if ydata is None:
-        return None
-    y = np.asarray(ydata, dtype=np.float64)
-    if y.shape != (G, S, m):
-        raise ValueError("`ydata` must have shape (G, S, m).")
-    return np.ascontiguousarray(y.reshape(G, S * m))
+def sigma_weights(sigma, lead, m, omitted=None):
+    """The weights ``1 / sigma`` of problems of shape `lead` + (m,) — `lead` is (B,), or (G, S) for the data sets of
+    global fits — and whether there is one set per problem.  `sigma` of shape `lead` + (m,), or of its last two or more
+    axes ((S, m)), is always read as per problem: the weights come back in the full shape, with 1 for sigma wherever
+    `omitted` (a mask of that shape, or None) is true — such a point is never read, anything may stand there.  A scalar
+    gives the 0-d weight and (m,) the (m,) weights all problems share.  ValueError for another shape."""
+    sg = np.asarray(sigma, dtype=np.float64)
+    full = tuple(lead) + (m,)
+    if sg.ndim >= 2 and sg.shape == full[-sg.ndim:]:
+        sg = np.broadcast_to(sg, full)
+        return 1.0 / (sg if omitted is None else np.where(omitted, 1.0, sg)), True
+    if sg.size == 1:
+        return 1.0 / sg.reshape(()), False
+    if sg.shape != (m,):
+        raise ValueError("`sigma` has incorrect shape.")
+    return 1.0 / sg, False
+
+
+# the model-eval entries (include/blsq.h) and the runs of arguments each takes besides ctx, B, reps, m, n, the data and
+# X, f, J, mask: how many of the flags est, sampling, nan_policy in front; the model id; the component table ncomp, fam,
+# cnt; nf, pmap (and Pfix behind X); the run S, shared, t_sstride; the pair tie_ratio, tie_offset
+_ENTRIES = {                      # flags  id     table  mapped  S-run  tie
+    "blsq_model_eval_dev":        (0, True,  False, False, False, False),
+    "blsq_model_eval_map_dev":    (0, True,  False, True,  False, False),
+    "blsq_model_eval_comp_dev":   (0, False, True,  True,  False, False),
+    "blsq_model_eval_est_dev":    (1, True,  True,  True,  False, False),
+    "blsq_model_eval_bin_dev":    (2, True,  True,  True,  False, False),
+    "blsq_model_eval_nan_dev":    (3, True,  True,  True,  False, False),
+    "blsq_model_eval_global_dev": (3, True,  True,  True,  True,  False),
+    "blsq_model_eval_tie_dev":    (3, True,  True,  True,  True,  True),
+}
+
 
 
 class DeviceModel:
@@ -915,8 +939,9 @@ class DeviceModel:
                  binned=False, nan_policy='propagate', global_map=None):
         model = resolve(name)
         model.terms(n)
-        if global_map is not None:
-            _check_global(model, binned, param_map)
+        gm = global_map
+        if gm is not None:
+            check_global(model, binned, param_map)
         self.binned = bool(binned)
         self.estimator = check_estimator(estimator)
         self.nan_policy = check_nan_policy(nan_policy)
@@ -927,90 +952,52 @@ class DeviceModel:
                 raise ValueError("estimator='poisson' needs `ydata`: the counts.")
             if sigma is not None:
                 raise ValueError("`sigma` must be None with estimator='poisson'.")
-        self.model, self.B, self.m, self.n_model = model, int(B), int(m), int(n)
-        self.param_map = param_map
-        if param_map is not None and param_map.n != self.n_model:
-            raise ValueError("`param_map` is for %d parameters, the model has %d." % (param_map.n, self.n_model))
-        self.n = self.n_model if param_map is None else param_map.nf
-        self.global_map = global_map
-        if global_map is not None:
-            self._init_global(ctx, xdata, ydata, sigma, Pfix)
-            return
-        x, per_problem = (BinnedModel(model) if self.binned else model).check_xdata(xdata, self.B, self.m)
+        self.model, self.B, self.n_model = model, int(B), int(n)
+        self.param_map, self.global_map = param_map, gm
+        for what, mp in (("param_map", param_map), ("global_map", gm)):
+            if mp is not None and mp.n != self.n_model:
+                raise ValueError("`%s` is for %d parameters, the model has %d." % (what, mp.n, self.n_model))
+        # what a batch and a global model differ in: `m` stays the m of one data set, `self.m` is the problem's
+        B, m = self.B, int(m)
+        if gm is None:
+            x, per_problem = (BinnedModel(model) if self.binned else model).check_xdata(xdata, B, m)
+            self.t_stride = (2 if self.binned else 1) * model.coords * m if per_problem else 0
+            self.t_sstride, lead, dims, pm, shared = 0, (B,), "B", param_map, None
+            self.m, self.n = m, self.n_model if pm is None else pm.nf
+        else:
+            x, self.t_stride, self.t_sstride = global_xdata(xdata, B, gm.S, m)
+            lead, dims, pm = (B, gm.S), "G, S", gm.pm
+            shared = np.ascontiguousarray(gm.slot_shared, dtype=np.int32)
+            self.m, self.n = gm.S * m, gm.nv
         y = w = None
         if ydata is not None:
-            y = np.ascontiguousarray(ydata, dtype=np.float64)
-            if y.shape != (self.B, self.m):
-                raise ValueError("`ydata` must have shape (B, m).")
+            y = np.asarray(ydata, dtype=np.float64)
+            if y.shape != lead + (m,):
+                raise ValueError("`ydata` must have shape (%s, m)." % dims)
         self.w_stride = 0
         if sigma is not None:
-            sg = np.asarray(sigma, dtype=np.float64)
-            if sg.shape == (self.B, self.m):
-                self.w_stride = self.m
-                if nan_policy == 'omit':                   # never read at an omitted point: anything may stand there
-                    sg = np.where(np.isnan(y), 1.0, sg)
-            elif sg.size == 1:
-                sg = np.broadcast_to(sg.reshape(()), (self.m,))
-            elif sg.shape != (self.m,):
-                raise ValueError("`sigma` has incorrect shape.")
-            w = np.ascontiguousarray(1.0 / sg)
-        self.t_stride = (2 if self.binned else 1) * model.coords * self.m if per_problem else 0
+            w, per_problem = sigma_weights(sigma, lead, m, np.isnan(y) if nan_policy == 'omit' else None)
+            if per_problem:
+                w, self.w_stride = w.reshape(B, self.m), self.m
+            else:
+                w = np.ascontiguousarray(np.broadcast_to(w, (m,)))
         self.ctx = ctx
         self._bufs = []
         self.d_t = self._upload(x)
-        self.d_y = self._upload(y)
+        self.d_y = self._upload(None if y is None else np.ascontiguousarray(y.reshape(B, self.m)))
         self.d_w = self._upload(w)
         self.d_Pfix = None
-        if param_map is not None:
-            self._pmap = np.ascontiguousarray(param_map.pmap, dtype=np.int32)
-            if Pfix is None and np.any(self._pmap < 0):
+        pmap = None if pm is None else np.ascontiguousarray(pm.pmap, dtype=np.int32)
+        if pm is not None:
+            if Pfix is None and np.any(pmap < 0):
                 raise ValueError("`Pfix` is required when a parameter is fixed.")
             if Pfix is not None:
                 Pfix = np.ascontiguousarray(Pfix, dtype=np.float64)
-                if Pfix.shape != (self.B, self.n_model):
-                    raise ValueError("`Pfix` must have shape (B, n).")
+                if Pfix.shape != lead + (self.n_model,):
+                    raise ValueError("`Pfix` must have shape (%s, n)." % dims)
                 self.d_Pfix = self._upload(Pfix)
         self.bounds_dev = None
-        self._bind()
-        ctx.adopt(self)
-
-    def _init_global(self, ctx, xdata, ydata, sigma, Pfix):
-        """The uploads of a global model: `self.m` is still the m of one data set on entry."""
-        gm = self.global_map
-        if gm.n != self.n_model:
-            raise ValueError("`global_map` is for %d parameters, the model has %d." % (gm.n, self.n_model))
-        G, S, m = self.B, gm.S, self.m
-        x, self.t_stride, self.t_sstride = global_xdata(xdata, G, S, m)
-        y, w = global_ydata(ydata, G, S, m), None
-        self.w_stride = 0
-        if sigma is not None:
-            sg = np.asarray(sigma, dtype=np.float64)
-            if sg.size == 1:
-                sg = np.broadcast_to(sg.reshape(()), (m,))
-            elif sg.shape != (m,):
-                if sg.shape not in ((S, m), (G, S, m)):
-                    raise ValueError("`sigma` has incorrect shape.")
-                sg = np.broadcast_to(sg, (G, S, m)).reshape(G, S * m)
-                self.w_stride = S * m
-                if self.nan_policy == 'omit':              # never read at an omitted point: anything may stand there
-                    sg = np.where(np.isnan(y), 1.0, sg)
-            w = np.ascontiguousarray(1.0 / sg)
-        self._m_set, self.m, self.n = m, S * m, gm.nv
-        self.ctx = ctx
-        self._bufs = []
-        self.d_t, self.d_y, self.d_w = self._upload(x), self._upload(y), self._upload(w)
-        self.d_Pfix = None
-        self._pmap = np.ascontiguousarray(gm.pm.pmap, dtype=np.int32)
-        self._shared = np.ascontiguousarray(gm.slot_shared, dtype=np.int32)
-        if Pfix is None and np.any(self._pmap < 0):
-            raise ValueError("`Pfix` is required when a parameter is fixed.")
-        if Pfix is not None:
-            Pfix = np.ascontiguousarray(Pfix, dtype=np.float64)
-            if Pfix.shape != (G, S, self.n_model):
-                raise ValueError("`Pfix` must have shape (G, S, n).")
-            self.d_Pfix = self._upload(Pfix)
-        self.bounds_dev = None
-        self._bind()
+        self._bind(m, pm, pmap, shared)
         ctx.adopt(self)
 
     def _upload(self, a):
@@ -1025,54 +1012,57 @@ class DeviceModel:
                                 for a in (lb, ub))
         return self.bounds_dev
 
-    def _entry(self):
-        """The entry of this fit and its arguments between ctx and B: the entry of the last flag the fit sets (it takes
-        every kind of model and the flags before it); without a flag, the entry of the kind of model."""
-        M, comp = self.model, isinstance(self.model, CompositeModel)
-        table = [len(M.components), M.fam_ids.ctypes.data_as(_abi.c_int32_p),
-                 M.counts.ctypes.data_as(_abi.c_int32_p)] if comp else [0, None, None]
-        flags = [ESTIMATORS.index(self.estimator), SAMPLING.index('bin' if self.binned else 'point'),
-                 NAN_POLICIES.index(self.nan_policy)]
-        kind = [-1 if comp else M.id] + table
-        pm = self.param_map if self.global_map is None else self.global_map.pm
-        if pm is not None and pm.affine:                      # ... then S (0: a plain batch), shared, t_sstride
-            if self.global_map is None:
-                return "blsq_model_eval_tie_dev", flags + kind + [0, None, 0]
-            return "blsq_model_eval_tie_dev", flags + kind + [
-                self.global_map.S, self._shared.ctypes.data_as(_abi.c_int32_p), self.t_sstride]
-        if self.global_map is not None:                       # ... then S, shared, t_sstride
-            return "blsq_model_eval_global_dev", flags + kind + [
-                self.global_map.S, self._shared.ctypes.data_as(_abi.c_int32_p), self.t_sstride]
-        if self.nan_policy != 'propagate':
-            return "blsq_model_eval_nan_dev", flags + kind
-        if self.binned:
-            return "blsq_model_eval_bin_dev", flags[:2] + kind
-        if self.estimator != 'lse':
-            return "blsq_model_eval_est_dev", flags[:1] + kind
-        if comp:                                              # with or without a map
-            return "blsq_model_eval_comp_dev", table
-        return ("blsq_model_eval_dev" if self.param_map is None else "blsq_model_eval_map_dev"), [M.id]
+    def _bind(self, m, pm, pmap, shared):
+        """The entry of this fit and every argument it takes behind ctx, fixed once the data are uploaded (`_eval`
+        fills in reps, X, f, J and mask).  The entry is the one of the last flag the fit sets (it takes every kind of
+        model and the flags before it); without a flag, the entry of the kind of model.  `m`: the points of one data
+        set; `pm`: the ParamMap of the fit (a global fit's own) or None, `pmap` its int32 map; `shared`: the int32 flags of
+        the slots a group shares, or None."""
+        M, comp, gm = self.model, isinstance(self.model, CompositeModel), self.global_map
+        if pm is not None and pm.affine:
+            name = "blsq_model_eval_tie_dev"
+        elif gm is not None:
+            name = "blsq_model_eval_global_dev"
+        elif self.nan_policy != 'propagate':
+            name = "blsq_model_eval_nan_dev"
+        elif self.binned:
+            name = "blsq_model_eval_bin_dev"
+        elif self.estimator != 'lse':
+            name = "blsq_model_eval_est_dev"
+        elif comp:                                            # with or without a map
+            name = "blsq_model_eval_comp_dev"
+        else:
+            name = "blsq_model_eval_dev" if pm is None else "blsq_model_eval_map_dev"
+        flags, has_id, table, mapped, s_run, tie = _ENTRIES[name]
+        ties = [np.ascontiguousarray(a, dtype=np.float64) for a in ((pm.ratio, pm.offset) if tie else ())]
+        self._host = (pmap, shared, ties)                     # the host arrays the entry reads: alive with the model
 
-    def _bind(self):
-        """The entry's name and what every call passes it, fixed once the data are uploaded: the arguments from ctx to
-        reps, from reps to X, and from X to f (`_eval` has the rest)."""
-        name, lead = self._entry()
-        mapped = name != "blsq_model_eval_dev"                # every other entry has nf, pmap and Pfix
-        gm = self.global_map
-        pmap = None if self.param_map is None and gm is None else self._pmap.ctypes.data_as(_abi.c_int32_p)
-        m, nf = (self.m, self.n) if gm is None else (self._m_set, gm.nf)         # a global entry: per data set
-        tie = []
-        if name == "blsq_model_eval_tie_dev":                 # ... and behind pmap the ratios and offsets (host arrays)
-            pm = self.param_map if gm is None else gm.pm
-            self._tie = [np.ascontiguousarray(a, dtype=np.float64) for a in (pm.ratio, pm.offset)]
-            tie = [a.ctypes.data_as(_abi.c_double_p) for a in self._tie]
-        self._call = (name, lead + [self.B], [m, self.n_model] + ([nf, pmap] if mapped else []) + tie
-                      + [self.d_t, self.t_stride, self.d_y, self.d_w, self.w_stride], [self.d_Pfix] if mapped else [])
+        def i32(a):
+            return None if a is None else a.ctypes.data_as(_abi.c_int32_p)
+        args = [ESTIMATORS.index(self.estimator), SAMPLING.index('bin' if self.binned else 'point'),
+                NAN_POLICIES.index(self.nan_policy)][:flags]
+        if has_id:
+            args.append(-1 if comp else M.id)
+        if table:
+            args += [len(M.components), i32(M.fam_ids), i32(M.counts)] if comp else [0, None, None]
+        if s_run:                                             # S == 0: a plain batch
+            args += [0, None, 0] if gm is None else [gm.S, i32(shared), self.t_sstride]
+        at_reps = len(args) + 1
+        args += [self.B, 1, m, self.n_model]
+        if mapped:                                            # nf: per data set in a global fit
+            args += [self.n if gm is None else gm.nf, i32(pmap)]
+        args += [a.ctypes.data_as(_abi.c_double_p) for a in ties]
+        args += [self.d_t, self.t_stride, self.d_y, self.d_w, self.w_stride, None]
+        self._call = (name, args + ([self.d_Pfix] if mapped else []) + [None, None, None], at_reps, len(args) - 1)
 
     def _eval(self, x_ptr, reps, f_ptr, J_ptr, mask_ptr):
-        name, head, data, pfix = self._call
-        self.ctx.check(getattr(self.ctx.lib, name)(self.ctx.h, *head, int(reps), *data, x_ptr, *pfix, f_ptr, J_ptr,
-                                                   mask_ptr), name)
+        name, a, at_reps, at_x = self._call
+        a[at_reps] = int(reps)
+        a[at_x] = x_ptr
+        a[-3] = f_ptr
+        a[-2] = J_ptr
+        a[-1] = mask_ptr
+        self.ctx.check(getattr(self.ctx.lib, name)(self.ctx.h, *a), name)
 
     def fun_dev(self, x_ptr, f_ptr, reps=1):
         self._eval(x_ptr, reps, f_ptr, None, None)
@@ -1107,55 +1097,42 @@ class DeviceFit:
                  nan_policy='propagate', global_map=None):
         self.model = resolve(name)
         self.model.terms(n)
-        self.global_map = global_map
-        if global_map is not None:
-            _check_global(self.model, binned, param_map)
-            self.binned, self.param_map = False, None
-            self.estimator, self.nan_policy = check_estimator(estimator), check_nan_policy(nan_policy)
-            if estimator == 'poisson' and sigma is not None:
-                raise ValueError("`sigma` must be None with estimator='poisson'.")
-            y = np.asarray(ydata, dtype=np.float64)
-            if y.ndim != 3 or y.shape[1] != global_map.S:
-                raise ValueError("`ydata` must have shape (G, S, m).")
-            self.B, S, self._m_set = y.shape
-            self.ydata = np.ascontiguousarray(y)
-            self.n_model, self.m, self.n = int(n), S * self._m_set, global_map.nv
-            if global_map.n != self.n_model:
-                raise ValueError("`global_map` is for %d parameters, the model has %d." % (global_map.n, self.n_model))
-            self.Pfix = None if Pfix is None else np.ascontiguousarray(Pfix, dtype=np.float64)
-            self.xdata = global_xdata(xdata, self.B, S, self._m_set)[0]
-            self.sigma = sigma
-            return
+        gm = self.global_map = global_map
+        if gm is not None:
+            check_global(self.model, binned, param_map)
         self.binned = bool(binned)
         self.estimator = check_estimator(estimator)
         self.nan_policy = check_nan_policy(nan_policy)
         if estimator == 'poisson' and sigma is not None:
             raise ValueError("`sigma` must be None with estimator='poisson'.")
         self.ydata = np.ascontiguousarray(ydata, dtype=np.float64)
-        self.B, self.m = self.ydata.shape
+        if gm is None:
+            self.B, self._m_set = self.ydata.shape            # (_m_set: the m of one data set)
+        elif self.ydata.ndim != 3 or self.ydata.shape[1] != gm.S:
+            raise ValueError("`ydata` must have shape (G, S, m).")
+        else:
+            self.B, _, self._m_set = self.ydata.shape
         self.n_model = int(n)
         self.param_map, self.Pfix = param_map, Pfix
-        if param_map is not None:
-            if param_map.n != self.n_model:
-                raise ValueError("`param_map` is for %d parameters, the model has %d." % (param_map.n, self.n_model))
-            self.Pfix = np.ascontiguousarray(Pfix, dtype=np.float64)
-            if self.Pfix.shape != (self.B, self.n_model):
-                raise ValueError("`Pfix` must have shape (B, n).")
-        self.n = self.n_model if param_map is None else param_map.nf
-        checker = BinnedModel(self.model) if self.binned else self.model
-        self.xdata, _ = checker.check_xdata(xdata, self.B, self.m)
+        mp, what, dims = (param_map, "param_map", "B") if gm is None else (gm, "global_map", "G, S")
+        if mp is not None:
+            if mp.n != self.n_model:
+                raise ValueError("`%s` is for %d parameters, the model has %d." % (what, mp.n, self.n_model))
+            if gm is None or Pfix is not None:                # (a global fit needs it where a parameter is fixed)
+                self.Pfix = np.ascontiguousarray(Pfix, dtype=np.float64)
+                if self.Pfix.shape != self.ydata.shape[:-1] + (self.n_model,):
+                    raise ValueError("`Pfix` must have shape (%s, n)." % dims)
+        if gm is None:
+            self.m, self.n = self._m_set, self.n_model if param_map is None else param_map.nf
+            self.xdata = (BinnedModel(self.model) if self.binned else self.model).check_xdata(xdata, self.B, self.m)[0]
+        else:
+            self.m, self.n = gm.S * self._m_set, gm.nv
+            self.xdata = global_xdata(xdata, self.B, gm.S, self._m_set)[0]
         self.sigma = sigma
 
     def open_device(self, ctx, lb, ub):
-        if self.global_map is not None:
-            dm = DeviceModel(ctx, self.model.name, self.B, self._m_set, self.n_model, self.xdata, self.ydata,
-                             self.sigma, None, self.Pfix, self.estimator, nan_policy=self.nan_policy,
-                             global_map=self.global_map)
-            dm.set_bounds(lb, ub)
-            return dm
-        dm = DeviceModel(ctx, self.model.name, self.B, self.m, self.n_model, self.xdata, self.ydata, self.sigma,
-                         self.param_map, self.Pfix, self.estimator, **({'binned': True} if self.binned else {}),
-                         **({'nan_policy': self.nan_policy} if self.nan_policy != 'propagate' else {}))
+        dm = DeviceModel(ctx, self.model.name, self.B, self._m_set, self.n_model, self.xdata, self.ydata, self.sigma,
+                         self.param_map, self.Pfix, self.estimator, self.binned, self.nan_policy, self.global_map)
         dm.set_bounds(lb, ub)
         return dm
 
