@@ -59,7 +59,7 @@ extern "C" int blsq_ctx_create(int device_id, blsq_ctx** out) {
   // (whatever exists when a step fails is given back by ~blsq_ctx)
   e = hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking);
   if (e == hipSuccess) e = hipStreamCreateWithFlags(&c->copy_stream, hipStreamNonBlocking);
-  if (e == hipSuccess) e = c->pinned.alloc(128, hipHostMallocCoherent);
+  if (e == hipSuccess) e = c->pinned.alloc(PIN_INTS, hipHostMallocCoherent);
   if (e == hipSuccess) {
     c->opt = options_from_env();
     e = c->cq_accept_dev.alloc(sizeof(unsigned long long));

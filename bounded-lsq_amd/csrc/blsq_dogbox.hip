@@ -80,13 +80,8 @@ int dog_finish(blsq_dogbox_plan* p, const int* path, bool any_qr, bool any_gram,
     p->njac = -1;
   }
   p->gate_done = false;
-  if (p->njac != 0) {
-    JacobiArgs ja{};
-    ja.X = p->st.X; ja.strideX = (long)p->ld * p->ld; ja.ld = p->ld; ja.ncols_dev = gmask;
-    ja.N = p->n + 1; ja.s = p->st.s; ja.uf = p->st.uf; ja.srange = p->st.srange;
-    ja.sweeps = p->sweeps.as<int>(); ja.max_sweeps = 40;
-    if (int rc_ = ctx->run(K_JACOBI, "launch_jacobi", [&] { return launch_jacobi(ja, p->B, ctx->stream); })) return rc_;
-  }
+  if (p->njac != 0)
+    if (int rc_ = run_jacobi(p, p->st.X, p->st.s, p->st.uf, p->st.srange, gmask)) return rc_;
   if (int rc_ = ctx->run(K_STEP, "launch_dog_solve", [&] {
         return launch_dog_solve(p->st, gfast, ctx->stream);
       })) return rc_;
@@ -107,17 +102,8 @@ int dog_after_triangle(blsq_dogbox_plan* p, int scale_mode) {
 
 GramCholArgs dog_chol_args(blsq_dogbox_plan* p, const int* mask) {
   QrTree& t = p->tree;
-  GramCholArgs c{};
-  c.opt = &p->ctx->opt;
-  c.Gsrc = t.gram_keep.as<double>(); c.G = p->st.X; c.NPAD = p->ld; c.n = p->n;
-  c.ncols_dev = p->st.ncols; c.gather = p->st.free_idx; c.stride_vec = p->ld;
-  c.mask = mask; c.fb_mask = t.fb_mask(); c.fail_count = t.fb_count(); c.path_out = t.path_rw();
-  c.fail_list = t.fb_list();
-  c.dsc = t.gram_dsc.as<double>();
-  c.rinv = t.gram_rinv.as<double>(); c.ywork = t.gram_ywork.as<double>(); c.k2_out = t.gram_k2.as<double>();
-  c.cert_done = t.gram_cert.as<int>();
-  c.k2_max = t.k2_max; c.pivot_floor = 1.0 / t.k2_max;
-  c.cert_flag = t.gram_cflag.as<int>(); c.cert_tau = t.gram_ctau.as<double>();
+  GramCholArgs c = t.gate_args(mask);
+  c.G = p->st.X; c.ncols_dev = p->st.ncols; c.gather = p->st.free_idx;
   c.colinfo = p->colinfo.as<double>();
   if (p->csne.on) c.pmin_out = p->csne.pmin.as<double>();
   if (p->ld <= 80) {                        // (the register-resident kernel also finishes the gate / Newton / Cauchy work)
@@ -135,10 +121,7 @@ GramCholArgs dog_chol_args(blsq_dogbox_plan* p, const int* mask) {
 int dog_gate_tail(blsq_dogbox_plan* p, const GramCholArgs& c) {
   blsq_ctx* ctx = p->ctx;
   QrTree& t = p->tree;
-  if (int rc_ = ctx->run(K_GRAM_GATE, "launch_gram_gate", [&] {
-        const hipError_t e = launch_gram_gate(c, p->B, ctx->stream);
-        return e == hipSuccess ? launch_gram_cert_shift(c, p->B, ctx->stream) : e;
-      })) return rc_;
+  if (int rc_ = t.run_cert(ctx, c)) return rc_;
   int* gfast = p->gate_ints.as<int>();
   p->st.fast = gfast;
   if (int rc_ = ctx->run(K_LM_GATE, "launch_dog_gate_solve", [&] {
@@ -176,8 +159,7 @@ int dog_csne_correct(blsq_dogbox_plan* p, const double* dJ, const double* df, in
   *nfail = 0;
   if (tier.count <= 0) return 0;
   cs.J = dJ; cs.strideJ = (long)p->m * ldJ; cs.ldJ = ldJ; cs.F = df; cs.strideF = p->m;
-  { int rc_ = tier.grow_part(ctx, (size_t)tier.count * cs.nchunk * ((size_t)cs.NE * p->ld + 16)); if (rc_) return rc_; }
-  HIPCHK(ctx, hipMemsetAsync(cs.counts + 1, 0, sizeof(int), ctx->stream));
+  if (int rc_ = tier.pass_begin(ctx)) return rc_;
   if (int rc_ = ctx->run(K_CSNE_PASS, "launch_csne_pass_dog", [&] {
         const hipError_t e = launch_dog_csne_scatter(cs, p->st, tier.count, ctx->stream);
         return e == hipSuccess ? launch_csne_pass_dog(cs, tier.count, ctx->stream) : e;
@@ -185,11 +167,7 @@ int dog_csne_correct(blsq_dogbox_plan* p, const double* dJ, const double* df, in
   if (int rc_ = ctx->run(K_CSNE_FIX, "launch_dog_csne_fix", [&] {
         return launch_dog_csne_fix(cs, p->st, tier.count, ctx->stream);
       })) return rc_;
-  HIPCHK(ctx, hipMemcpyAsync(ctx->pinned + 12, cs.counts + 1, sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
-  HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-  *nfail = ctx->pinned[12];
-  ctx->csne_steps += (unsigned long long)(tier.count - *nfail);
-  ctx->csne_declined += (unsigned long long)*nfail;
+  if (int rc_ = tier.pass_verdict(ctx, /*polled=*/false, nfail)) return rc_;
   if (*nfail > 0) return tier.reroute(ctx, p->tree, *nfail);
   return 0;
 }
@@ -241,8 +219,6 @@ int dog_factor_core(blsq_dogbox_plan* p, const double* dJ, const double* df, int
     return dog_after_triangle(p, scale_mode);
   }
   if ((rc = t.run_gram_only(ctx, dJ, df, ldJ, mask, false))) return rc;
-  if (!t.fb_zeroed) HIPCHK(ctx, hipMemsetAsync(t.fb_count(), 0, 3 * sizeof(int), ctx->stream));
-  t.fb_zeroed = false;
   p->st.Rt = t.Rfinal(); p->st.Gk = t.gram_keep.as<double>(); p->st.path = t.path_rw();
   const PackVecs* pk = nullptr;
   { int rc_ = take_pack(p, mask, &pk); if (rc_) return rc_; }
@@ -262,15 +238,7 @@ int dog_factor_core(blsq_dogbox_plan* p, const double* dJ, const double* df, int
   int nfb = 0;
   if (defer) {                              // guess: nobody leaves the path, nobody needs the SVD (resolve() checks)
     verdict_arm(p, skip_tail, dJ, df, ldJ, scale_mode);
-  } else {
-    HIPCHK(ctx, hipMemcpyAsync(ctx->pinned + 1, t.fb_count(), 3 * sizeof(int), hipMemcpyDeviceToHost,
-                               ctx->stream));
-    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-    nfb = ctx->pinned[1];
-    p->gate_done = (nfb == 0);
-    p->njac = p->gate_done ? ctx->pinned[2] : -1;
-    if (!mask) { p->guess_ok = (nfb == 0 && p->njac == 0); p->guess_settled = (c.unsettled && ctx->pinned[3] == 0); }
-  }
+  } else if ((rc = gate_verdict(p, /*polled=*/false, mask != nullptr, c.unsettled != nullptr, &nfb))) return rc;
   t.note_paths(ctx, nfb, mask != nullptr);
   if (!mask) p->csne.count = 0;                           // (the prep launch cleared every flag; dog_csne_select sets them anew)
   if (skip_tail) { p->gate_done = false; return 0; }
@@ -309,14 +277,8 @@ extern "C" int blsq_dogbox_factor_dev(blsq_dogbox_plan* p, const double* dJ, con
   blsq_ctx* ctx = p->ctx;
   if (int rc_ = factor_args(ctx, dJ, df, dx, dlb, dub, dscale_io, scale_mode)) return rc_;
   if (!don_bound) return ctx->bad(9, "on_bound is NULL");
-  HIPCHK(ctx, hipSetDevice(ctx->device));
-  int rc = verdict_published(p);               // (a verdict nobody read: its counters leave before they are cleared)
-  if (rc) return rc;
-  rc = put_state(p, dx, dlb, dub, dscale_io, don_bound, hipMemcpyDeviceToDevice, true);
-  if (rc) return rc;
-  p->pend_scale_io = dscale_io;
-  if ((rc = dog_factor_core(p, dJ, df, p->n, scale_mode, nullptr, true))) return rc;
-  return scale_back(p, dscale_io, scale_mode);
+  return factor_dev(p, dx, dlb, dub, dscale_io, scale_mode, don_bound,
+                    [&] { return dog_factor_core(p, dJ, df, p->n, scale_mode, nullptr, true); });
 }
 
 extern "C" int blsq_dogbox_step_dev(blsq_dogbox_plan* p, const double* dDelta) {
@@ -406,13 +368,9 @@ extern "C" int blsq_dogbox_fetch_step(blsq_dogbox_plan* p, double* step, double*
   if ((rc = get_vec(ctx, step, n, p->out.step, ld, B))) return rc;
   if ((rc = get_vec(ctx, x_new, n, p->out.x_new, ld, B))) return rc;
   if ((rc = get_vec(ctx, (long long*)on_bound_new, n, p->out.on_bound_new, ld, B))) return rc;
-  std::vector<double> sc((size_t)B * 4);
-  std::vector<int> inf((size_t)B * 4);
-  HIPCHK(ctx, hipMemcpyAsync(sc.data(), p->out.scal, sizeof(double) * sc.size(),
-                             hipMemcpyDeviceToHost, ctx->stream));
-  HIPCHK(ctx, hipMemcpyAsync(inf.data(), p->out.info, sizeof(int) * inf.size(),
-                             hipMemcpyDeviceToHost, ctx->stream));
-  if ((rc = blsq_sync(ctx))) return rc;
+  std::vector<double> sc;                   // [B][4]
+  std::vector<int> inf;                     // [B][4]
+  if ((rc = fetch_scal_info(p, &sc, &inf))) return rc;
   for (int b = 0; b < B; ++b) {
     if (predicted_reduction) predicted_reduction[b] = sc[4 * b + 0];
     if (step_scaled_norm) step_scaled_norm[b] = sc[4 * b + 1];

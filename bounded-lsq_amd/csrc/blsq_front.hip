@@ -89,31 +89,42 @@ hipError_t QrTree::gram_sum(blsq_ctx* ctx, GramArgs g, double* Gp, double* Gout,
 
 int QrTree::run_gram(blsq_ctx* ctx, const double* dJ, const double* df, int ldJ, const int* mask,
                      int* nfallback, bool collective) {
-  int* fb = gram_ints.as<int>();
-  int* cnt = fb + B;
-  HIPCHK(ctx, hipMemsetAsync(cnt, 0, sizeof(int), ctx->stream));
+  HIPCHK(ctx, hipMemsetAsync(fb_count(), 0, sizeof(int), ctx->stream));
   int rc = run_gram_only(ctx, dJ, df, ldJ, mask, collective);
   if (rc) return rc;
-  GramCholArgs c{};
-  c.opt = opt;
-  c.Gsrc = gram_keep.as<double>(); c.G = levels.back().R.as<double>(); c.NPAD = NPAD; c.n = n; c.mask = mask;
-  c.fb_mask = fb; c.fail_count = cnt;
-  c.path_out = fb + B + 4;
-  c.dsc = gram_dsc.as<double>();
-  c.rinv = gram_rinv.as<double>(); c.ywork = gram_ywork.as<double>(); c.k2_out = gram_k2.as<double>();
-  c.k2_max = k2_max; c.pivot_floor = 1.0 / k2_max;
-  c.cert_flag = gram_cflag.as<int>(); c.cert_tau = gram_ctau.as<double>();
+  // the plain Gram into the triangle slot: no diagonal modification, no list of the rejected, no in-kernel certificate
+  GramCholArgs c = gate_args(mask);
+  c.G = levels.back().R.as<double>();
+  c.stride_vec = 0; c.fail_list = nullptr; c.cert_done = nullptr;
   if (int rc_ = ctx->run(K_GRAM_CHOL, "launch_gram_chol", [&] {
         return launch_gram_chol(c, B, ctx->stream);
       })) return rc_;
-  if (int rc_ = ctx->run(K_GRAM_GATE, "launch_gram_gate", [&] {
-        const hipError_t e = launch_gram_gate(c, B, ctx->stream);
-        return e == hipSuccess ? launch_gram_cert_shift(c, B, ctx->stream) : e;
-      })) return rc_;
-  HIPCHK(ctx, hipMemcpyAsync(ctx->pinned + 1, cnt, sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
-  HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-  *nfallback = ctx->pinned[1];
+  if ((rc = run_cert(ctx, c))) return rc;
+  const int* cnt = nullptr;
+  HIPCHK(ctx, ctx->read_blocking(PIN_GATE, fb_count(), 1, &cnt));
+  *nfallback = cnt[0];
   return 0;
+}
+
+GramCholArgs QrTree::gate_args(const int* mask) const {
+  GramCholArgs c{};
+  c.opt = opt;
+  c.Gsrc = gram_keep.as<double>(); c.NPAD = NPAD; c.n = n; c.stride_vec = NPAD;
+  c.mask = mask; c.fb_mask = fb_mask(); c.fail_count = fb_count(); c.path_out = path_rw();
+  c.fail_list = fb_list();
+  c.dsc = gram_dsc.as<double>();
+  c.rinv = gram_rinv.as<double>(); c.ywork = gram_ywork.as<double>(); c.k2_out = gram_k2.as<double>();
+  c.cert_done = gram_cert.as<int>();
+  c.k2_max = k2_max; c.pivot_floor = 1.0 / k2_max;
+  c.cert_flag = gram_cflag.as<int>(); c.cert_tau = gram_ctau.as<double>();
+  return c;
+}
+
+int QrTree::run_cert(blsq_ctx* ctx, const GramCholArgs& c) {
+  return ctx->run(K_GRAM_GATE, "launch_gram_gate", [&] {
+    const hipError_t e = launch_gram_gate(c, B, ctx->stream);
+    return e == hipSuccess ? launch_gram_cert_shift(c, B, ctx->stream) : e;
+  });
 }
 
 int QrTree::run_gram_only(blsq_ctx* ctx, const double* dJ, const double* df, int ldJ, const int* mask,
@@ -331,9 +342,25 @@ int CsneTier::grow_part(blsq_ctx* ctx, size_t need) {
 int CsneTier::relist(blsq_ctx* ctx) {
   hipError_t e = launch_csne_reroute(cs, -1, nullptr, nullptr, nullptr, ctx->stream);
   if (e != hipSuccess) return ctx->fail(e, "launch_csne_reroute(relist)");
-  HIPCHK(ctx, hipMemcpyAsync(ctx->pinned + 9, cs.counts, sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
-  HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-  count = ctx->pinned[9];
+  const int* c = nullptr;
+  HIPCHK(ctx, ctx->read_blocking(PIN_CSNE_LIST, cs.counts, 1, &c));
+  count = c[0];
+  return 0;
+}
+
+int CsneTier::pass_begin(blsq_ctx* ctx) {
+  if (int rc_ = grow_part(ctx, (size_t)count * cs.nchunk * ((size_t)cs.NE * cs.ld + 16))) return rc_;
+  HIPCHK(ctx, hipMemsetAsync(cs.counts + 1, 0, sizeof(int), ctx->stream));
+  return 0;
+}
+
+int CsneTier::pass_verdict(blsq_ctx* ctx, bool polled, int* nfail) {
+  const int* c = nullptr;
+  HIPCHK(ctx, polled ? ctx->read_polled(PIN_CSNE_FAIL_POLLED, cs.counts + 1, 1, &c)
+                     : ctx->read_blocking(PIN_CSNE_FAIL, cs.counts + 1, 1, &c));
+  *nfail = c[0];
+  ctx->csne_steps += (unsigned long long)(count - *nfail);
+  ctx->csne_declined += (unsigned long long)*nfail;
   return 0;
 }
 
@@ -365,11 +392,10 @@ int CsneTier::select(blsq_ctx* ctx, QrTree& t, const GramCholArgs& chol, int nfb
   const hipError_t e = launch_select(sel);
   if (e != hipSuccess) return ctx->fail(e, "launch_csne_select");
   // two counters to the host: the problems left for the tree, the problems on the tier
-  HIPCHK(ctx, hipMemcpyAsync(ctx->pinned + 8, t.fb_count(), sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
-  HIPCHK(ctx, hipMemcpyAsync(ctx->pinned + 9, cs.counts, sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
-  HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-  *ntree = ctx->pinned[8];
-  count = ctx->pinned[9];
+  const int* c = nullptr;
+  HIPCHK(ctx, ctx->read_blocking(PIN_CSNE_LIST, t.fb_count(), 1, &c, cs.counts));
+  *ntree = c[0];
+  count = c[1];
   ctx->csne_routed += (unsigned long long)(nfb - *ntree);
   if (!masked) t.any_qr = *ntree > 0;                     // (a masked call keeps the others' paths: any_qr stays)
   t.any_gram = t.any_gram || *ntree < nfb;
@@ -483,8 +509,41 @@ int debug_cond(StepPlan* p, double* k2) {
   return fetch_resolved(p, k2, p->tree.gram_k2.p, sizeof(double));
 }
 
+int fetch_scal_info(StepPlan* p, std::vector<double>* sc, std::vector<int>* inf) {
+  blsq_ctx* ctx = p->ctx;
+  sc->resize(p->o_scal.bytes / sizeof(double));
+  inf->resize(p->o_info.bytes / sizeof(int));
+  HIPCHK(ctx, hipMemcpyAsync(sc->data(), p->o_scal.p, p->o_scal.bytes, hipMemcpyDeviceToHost, ctx->stream));
+  HIPCHK(ctx, hipMemcpyAsync(inf->data(), p->o_info.p, p->o_info.bytes, hipMemcpyDeviceToHost, ctx->stream));
+  return blsq_sync(ctx);
+}
+
+int gate_verdict(StepPlan* p, bool polled, bool masked, bool settles, int* nfb) {
+  blsq_ctx* ctx = p->ctx;
+  const int* c = nullptr;
+  HIPCHK(ctx, polled ? ctx->read_polled(PIN_GATE_POLLED, p->tree.fb_count(), 3, &c)
+                     : ctx->read_blocking(PIN_GATE, p->tree.fb_count(), 3, &c));
+  *nfb = c[0];
+  p->gate_done = (*nfb == 0);
+  p->njac = p->gate_done ? c[1] : -1;
+  if (!masked) { p->guess_ok = (*nfb == 0 && p->njac == 0); p->guess_settled = (settles && c[2] == 0); }
+  return 0;
+}
+
+int run_jacobi(StepPlan* p, double* X, double* s, double* uf, double* srange, const int* ncols_dev) {
+  blsq_ctx* ctx = p->ctx;
+  JacobiArgs ja{};
+  ja.X = X; ja.strideX = (long)p->ld * p->ld; ja.ld = p->ld; ja.ncols_dev = ncols_dev;
+  ja.N = p->n + 1; ja.s = s; ja.uf = uf; ja.srange = srange;
+  ja.sweeps = p->sweeps.as<int>(); ja.max_sweeps = 40;
+  return ctx->run(K_JACOBI, "launch_jacobi", [&] { return launch_jacobi(ja, p->B, ctx->stream); });
+}
+
 int take_pack(StepPlan* p, const int* mask, const PackVecs** pk) {
   *pk = nullptr;
+  QrTree& t = p->tree;
+  if (!t.fb_zeroed) HIPCHK(p->ctx, hipMemsetAsync(t.fb_count(), 0, 3 * sizeof(int), p->ctx->stream));
+  t.fb_zeroed = false;
   if (!p->pack_pend) return 0;
   p->pack_pend = false;
   if (!mask) { *pk = &p->pack_pv; return 0; }

@@ -37,6 +37,22 @@ static const char* const kSlotNames[K_NSLOT] = {"qr_leaf", "qr_merge", "prep", "
                                    "aug_chol", "lm_chol", "cqr2_apply", "cqr2_combine", "model_eval", "csne_pass", "csne_fix",
                                    "cov_rows", "cov_pinv_weights", "cov_pinv_product", "cov_gather", "cov_inverse", "cov_product", "loss_cost", "loss_scale"};
 
+// The ctx's pinned host ints (blsq_ctx::pinned), through which device counters reach the host: 16-byte slots, [0..2] up
+// to three counters, [3] the sequence number of a publish (a blocking read leaves it alone).  One slot per use and
+// mechanism; a slot is shared only by reads that are consumed before the next one on it starts.
+enum PinSlot {
+  PIN_OUTER = 0,          // blocking: active / accepted problems of an outer iteration (blsq_outer.hip)
+  PIN_GATE,               // blocking: the gate's counters (QrTree::run_gram: 1, the dogbox plans' verdict: 3)
+  PIN_GATE_POLLED,        // polled:   the gate's three counters (the TRF plans' verdict)
+  PIN_CSNE_LIST,          // blocking: problems left for the tree, problems on the tier (CsneTier::select); relist: the latter
+  PIN_CSNE_FAIL,          // blocking: problems the CSNE pass declined (dogbox plans, factor time)
+  PIN_CSNE_FAIL_POLLED,   // polled:   the same (TRF plans, step time)
+  PIN_LM_ROUND0,          // polled:   active problems of Newton round r in slot PIN_LM_ROUND0 + r, r = 0 .. 12
+  PIN_NSLOT = PIN_LM_ROUND0 + 13
+};
+constexpr int PIN_INTS = 128;             // what blsq_ctx_create allocates
+static_assert(4 * PIN_NSLOT <= PIN_INTS, "the last pinned slot ends inside the ctx's pinned ints");
+
 inline int round_up(int v, int q) { return (v + q - 1) / q * q; }
 // rows of the stacked systems [R D; E] / [R_aug; sqrt(alpha) I]: two blocks of
 // round_up(n, 16) rows each (the second block starts on a tile boundary, see qr_panel.hip)
@@ -84,8 +100,8 @@ struct blsq_ctx {
   struct Pending { int slot; hipEvent_t a, b; };
   std::vector<Pending> pending;
   std::vector<hipEvent_t> pool;
-  PinnedBuf<int> pinned;            // 128 pinned host ints: device -> host counters without staging
-                                    // ([0..3] one-shot read-backs, [32 + 4 r ..] the slot of Newton round r)
+  PinnedBuf<int> pinned;            // PIN_INTS pinned host ints: device -> host counters without staging (the map:
+                                    // PinSlot; touched by pin / read_blocking / read_polled only)
   int pub_seq = 0;                  // sequence number of the last publish()
   blsq::Options opt;                // the switches of this ctx (blsq_options.h: environment at creation, blsq_ctx_set_option)
   long long gram_fast = 0, gram_fallback = 0;   // problems factored by the normal equations / handed to the QR tree
@@ -117,6 +133,23 @@ struct blsq_ctx {
       }
       cpu_relax();
     }
+  }
+  // The pinned slots (PinSlot).  pin: a slot's address, for a caller that splits publish and await (trf_lm_rounds).
+  int* pin(int slot) const { return pinned + 4 * slot; }
+  // Blocking read: n <= 3 device ints into the slot by a blit, then the stream is synchronised — it is idle when this
+  // returns.  src2 (optional): one more int from elsewhere into [n], by a blit of its own.  *out = the slot.
+  hipError_t read_blocking(PinSlot slot, const int* src, int n, const int** out, const int* src2 = nullptr) {
+    *out = pin(slot);
+    hipError_t e = hipMemcpyAsync(pin(slot), src, n * sizeof(int), hipMemcpyDeviceToHost, stream);
+    if (e == hipSuccess && src2) e = hipMemcpyAsync(pin(slot) + n, src2, sizeof(int), hipMemcpyDeviceToHost, stream);
+    return e == hipSuccess ? hipStreamSynchronize(stream) : e;
+  }
+  // Polled read: publish + await on the slot — no blit, and the stream is not drained.
+  hipError_t read_polled(PinSlot slot, const int* src, int n, const int** out) {
+    *out = pin(slot);
+    int seq = 0;
+    const hipError_t e = publish(src, n, pin(slot), &seq);
+    return e == hipSuccess ? await(pin(slot), seq) : e;
   }
   int bad(int argidx, const char* what) {
     err = std::string("invalid argument: ") + what;
@@ -301,6 +334,11 @@ struct QrTree {
   int* fb_count() const { return gram_ints.as<int>() + B; }
   int* path_rw() const { return gram_ints.as<int>() + B + 4; }
   int* fb_list() const { return gram_ints.as<int>() + 2 * (size_t)B + 4; }
+  // The tree's share of a plan's factor / certificate arguments (mask: as run): Gram source, gate outputs, certificate
+  // scratch and thresholds.  The solver adds its system (G, colscale / diag_vec or ncols_dev / gather), colinfo, pmin_out
+  // and its finish block; a launch that wants fewer fields set clears the rest.
+  GramCholArgs gate_args(const int* mask) const;
+  int run_cert(blsq_ctx* ctx, const GramCholArgs& c);   // the certificate's norm stage + shifted factorisation over c
   // host bookkeeping after a gate verdict: nfb of the problems refreshed by this call failed
   void note_paths(blsq_ctx* ctx, int nfb, bool masked);
   const double* Rfinal() const { return levels.back().R.as<double>(); }
@@ -330,7 +368,7 @@ using namespace blsq_host;
 
 // The CSNE tier (csne_kernels.hip), ONE host state for the TRF and the dogbox plans: rejected problems
 // whose Gram-Cholesky factor qualifies keep it as a preconditioner, their steps corrected against J in one streaming
-// pass.  The select launch, the correction and its read-back differ between the solvers and stay with them.
+// pass.  The select launch and the launches of the correction differ between the solvers and stay with them.
 struct CsneTier {
   bool on = false;                  // the plan's shape is supported and option `csne` != 0 (build ran)
   int count = 0;                    // problems on the tier now (host copy of cs.counts[0])
@@ -344,6 +382,10 @@ struct CsneTier {
   int build(blsq_ctx* ctx, int B, int m, int n, int ld, bool with_hp);   // buffers, zeroed, and cs over them; on = true
   bool ensure_recordings();         // false: no room for them (the caller takes the tier out of service)
   int grow_part(blsq_ctx* ctx, size_t need);
+  // the streaming pass over `count` problems: room for its partial sums and a cleared fail counter in front of it; behind
+  // it *nfail, read by the caller's mechanism (polled: TRF, blocking: dogbox), into the ctx's statistics
+  int pass_begin(blsq_ctx* ctx);
+  int pass_verdict(blsq_ctx* ctx, bool polled, int* nfail);
   int relist(blsq_ctx* ctx);        // a masked factor call refreshed some problems: the list from the flags
   int reroute(blsq_ctx* ctx, QrTree& t, int nfail);   // cs.fail_list leaves the tier for t.fb_list()
   // which of the nfb problems the certificate has just rejected (t.fb_list()) the tier takes: the bound from the
@@ -494,7 +536,16 @@ int scale_back(StepPlan* p, double* dscale_io, int scale_mode);
 // resolve the plan's verdict, copy B items of `item` bytes to the host, blsq_sync
 int fetch_resolved(StepPlan* p, void* dst, const void* src, size_t item);
 int debug_cond(StepPlan* p, double* k2);   // blsq_{trf,dogbox}_debug_cond
+// o_scal / o_info of the last step call on the host, behind everything the entry has enqueued so far (blsq_sync)
+int fetch_scal_info(StepPlan* p, std::vector<double>* sc, std::vector<int>* inf);
+// The synchronous verdict of a Gram-stage factor call: the gate's three counters by the caller's read mechanism (polled:
+// TRF, blocking: dogbox) -> *nfb, gate_done, njac and, after an unmasked call, whether the next call may guess (settles:
+// the factor launch counted the problems it did not settle itself, GramCholArgs::unsettled)
+int gate_verdict(StepPlan* p, bool polled, bool masked, bool settles, int* nfb);
+// the Jacobi SVD of the triangles in X for the problems ncols_dev selects (s, uf, srange: the plan's state vectors)
+int run_jacobi(StepPlan* p, double* X, double* s, double* uf, double* srange, const int* ncols_dev);
 
+// Top of a Gram stage: the gate counters fb_count()[0..2] are cleared unless the pack launch does it (fb_zeroed), and
 // the deferred vectors of this factor call: handed to the prep launch (returns them), or — a masked call keeps the
 // other problems' state, so its prep launch cannot do the copy — packed by the stand-alone launch right here
 int take_pack(StepPlan* p, const int* mask, const PackVecs** pk);
@@ -502,6 +553,20 @@ int take_pack(StepPlan* p, const int* mask, const PackVecs** pk);
 // The counters of a pending verdict are on their way to the host (a stand-alone publish unless a step kernel has
 // taken them along) — to be called before anything waits for them or overwrites them.
 int verdict_published(StepPlan* p);
+// blsq_{trf,dogbox}_factor_dev behind their argument checks: the caller's vectors (don_bound: dogbox) into the state
+// layout, core() — the plan's factor call, which may leave its verdict pending —, the computed scale back to the caller
+template <class Core>
+int factor_dev(StepPlan* p, const double* dx, const double* dlb, const double* dub, double* dscale_io, int scale_mode,
+               const int64_t* don_bound, Core core) {
+  blsq_ctx* ctx = p->ctx;
+  HIPCHK(ctx, hipSetDevice(ctx->device));
+  int rc = verdict_published(p);               // (a verdict nobody read: its counters leave before they are cleared)
+  if (rc) return rc;
+  if ((rc = put_state(p, dx, dlb, dub, dscale_io, don_bound, hipMemcpyDeviceToDevice, true))) return rc;
+  p->pend_scale_io = dscale_io;
+  if ((rc = core())) return rc;
+  return scale_back(p, dscale_io, scale_mode);
+}
 // ... and the arguments with which the step kernel of this call takes them along (dst == nullptr: nothing to do)
 inline PublishArgs verdict_rides(StepPlan* p) {
   if (!p->pend_unpub) return PublishArgs{nullptr, 0, nullptr, 0};

@@ -237,10 +237,9 @@ extern "C" int blsq_outer_propose(blsq_outer* o, int32_t* n_active) {
   HIPCHK(ctx, hipMemsetAsync(o->st.counts, 0, sizeof(int) * 2, ctx->stream));
   e = launch_outer_trial(o->st, ctx->stream);
   if (e != hipSuccess) return ctx->fail(e, "launch_outer_trial");
-  HIPCHK(ctx, hipMemcpyAsync(ctx->pinned, o->st.counts, sizeof(int), hipMemcpyDeviceToHost,
-                             ctx->stream));
-  HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-  *n_active = ctx->pinned[0];
+  const int* c = nullptr;
+  HIPCHK(ctx, ctx->read_blocking(PIN_OUTER, o->st.counts, 1, &c));
+  *n_active = c[0];
   return 0;
 }
 
@@ -255,11 +254,10 @@ extern "C" int blsq_outer_judge(blsq_outer* o, int32_t* n_accepted) {
   if (o->loss != BLSQ_LOSS_LINEAR && (rc = outer_loss_cost(o, o->st.ft))) return rc;
   hipError_t e = launch_outer_judge(o->st, ctx->stream);
   if (e != hipSuccess) return ctx->fail(e, "launch_outer_judge");
-  HIPCHK(ctx, hipMemcpyAsync(ctx->pinned, o->st.counts + 1, sizeof(int), hipMemcpyDeviceToHost,
-                             ctx->stream));
-  HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-  *n_accepted = ctx->pinned[0];
-  o->last_accepted = ctx->pinned[0];
+  const int* c = nullptr;
+  HIPCHK(ctx, ctx->read_blocking(PIN_OUTER, o->st.counts + 1, 1, &c));
+  *n_accepted = c[0];
+  o->last_accepted = c[0];
   return 0;
 }
 

@@ -137,12 +137,7 @@ int trf_finish(blsq_trf_plan* p) {
   }
   p->gate_done = false;
   if (p->njac == 0) return 0;             // nobody needs the SVD: no launch
-  JacobiArgs ja{};
-  ja.X = p->st.X; ja.strideX = (long)p->ld * p->ld; ja.ld = p->ld; ja.ncols_dev = p->lm.ncols_jac;
-  ja.N = p->n + 1; ja.s = p->st.s; ja.uf = p->st.uf; ja.srange = p->st.srange;
-  ja.sweeps = p->sweeps.as<int>(); ja.max_sweeps = 40;
-  if (int rc_ = ctx->run(K_JACOBI, "launch_jacobi", [&] { return launch_jacobi(ja, p->B, ctx->stream); })) return rc_;
-  return 0;
+  return run_jacobi(p, p->st.X, p->st.s, p->st.uf, p->st.srange, p->lm.ncols_jac);
 }
 
 // redo: the problems were prepared from their Gram already in this factor call — start again from the
@@ -162,17 +157,8 @@ int trf_after_triangle(blsq_trf_plan* p, const double* Rt, int scale_mode, int r
 
 GramCholArgs trf_chol_args(blsq_trf_plan* p, const int* mask) {
   QrTree& t = p->tree;
-  GramCholArgs c{};
-  c.opt = &p->ctx->opt;
-  c.Gsrc = t.gram_keep.as<double>(); c.G = p->st.X; c.NPAD = p->ld; c.n = p->n;
-  c.colscale = p->st.d; c.diag_vec = p->st.ediag; c.stride_vec = p->ld;
-  c.mask = mask; c.fb_mask = t.fb_mask(); c.fail_count = t.fb_count(); c.path_out = t.path_rw();
-  c.fail_list = t.fb_list();
-  c.dsc = t.gram_dsc.as<double>();
-  c.rinv = t.gram_rinv.as<double>(); c.ywork = t.gram_ywork.as<double>(); c.k2_out = t.gram_k2.as<double>();
-  c.cert_done = t.gram_cert.as<int>();
-  c.k2_max = t.k2_max; c.pivot_floor = 1.0 / t.k2_max;
-  c.cert_flag = t.gram_cflag.as<int>(); c.cert_tau = t.gram_ctau.as<double>();
+  GramCholArgs c = t.gate_args(mask);
+  c.G = p->st.X; c.colscale = p->st.d; c.diag_vec = p->st.ediag;
   c.colinfo = p->aug_colinfo.as<double>();
   c.hmax = p->aug_hmax.as<double>(); c.lam_out = p->aug_lam.as<double>();
   if (p->csne.on) c.pmin_out = p->csne.pmin.as<double>();
@@ -194,10 +180,7 @@ GramCholArgs trf_chol_args(blsq_trf_plan* p, const int* mask) {
 int trf_gate_tail(blsq_trf_plan* p, const GramCholArgs& c, bool full = true) {
   blsq_ctx* ctx = p->ctx;
   QrTree& t = p->tree;
-  if (int rc_ = ctx->run(K_GRAM_GATE, "launch_gram_gate", [&] {
-        const hipError_t e = launch_gram_gate(c, p->B, ctx->stream);
-        return e == hipSuccess ? launch_gram_cert_shift(c, p->B, ctx->stream) : e;
-      })) return rc_;
+  if (int rc_ = t.run_cert(ctx, c)) return rc_;
   // The rank gate runs BEFORE the verdict is read back: in the common case (no problem leaves this
   // path) its result stands, and the same read-back tells whether anybody needs the Jacobi SVD at all.
   p->lm.path = t.path_rw();
@@ -218,8 +201,6 @@ int trf_gate_tail(blsq_trf_plan* p, const GramCholArgs& c, bool full = true) {
 int trf_gram_stage(blsq_trf_plan* p, int scale_mode, const int* mask, int* nfb, bool defer = false) {
   blsq_ctx* ctx = p->ctx;
   QrTree& t = p->tree;
-  if (!t.fb_zeroed) HIPCHK(ctx, hipMemsetAsync(t.fb_count(), 0, 3 * sizeof(int), ctx->stream));
-  t.fb_zeroed = false;
   p->st.Rt = t.Rfinal(); p->st.Gk = t.gram_keep.as<double>(); p->st.path = t.path_rw();
   const PackVecs* pk = nullptr;
   { int rc_ = take_pack(p, mask, &pk); if (rc_) return rc_; }
@@ -252,16 +233,9 @@ int trf_gram_stage(blsq_trf_plan* p, int scale_mode, const int* mask, int* nfb, 
   if (defer) {                              // the counters travel; the verdict is read by resolve()
     verdict_arm(p, skip_tail, p->pend_dJ, p->pend_df, p->pend_ldJ, p->pend_scale_mode);
     *nfb = 0;
-  } else {
-    // (the synchronous verdict: published and polled for — slot [4 .. 8) of the pinned ints — instead of a blit and a
+  } else {                                  // (the synchronous verdict: published and polled for instead of a blit and a
     //  stream synchronisation)
-    int seq = 0;
-    HIPCHK(ctx, ctx->publish(t.fb_count(), 3, ctx->pinned + 4, &seq));
-    HIPCHK(ctx, ctx->await(ctx->pinned + 4, seq));
-    *nfb = ctx->pinned[4];
-    p->gate_done = (*nfb == 0);
-    p->njac = p->gate_done ? ctx->pinned[5] : -1;
-    if (!mask) p->guess_settled = (c.unsettled && ctx->pinned[6] == 0);
+    if ((rc = gate_verdict(p, /*polled=*/true, mask != nullptr, c.unsettled != nullptr, nfb))) return rc;
   }
   t.note_paths(ctx, *nfb, mask != nullptr);
   p->path = t.path_rw();
@@ -340,7 +314,6 @@ int trf_factor_core(blsq_trf_plan* p, const double* dJ, const double* df, int ld
   const bool defer = may_defer && !mask && verdict_may_guess(p) && p->lm_enable && p->pend_pin;
   if ((rc = trf_gram_stage(p, scale_mode, mask, &nfb, defer))) return rc;
   if (defer) { p->pend_dJ = dJ; p->pend_df = df; p->pend_ldJ = ldJ; p->pend_scale_mode = scale_mode; }
-  else if (!mask) p->guess_ok = (nfb == 0 && p->njac == 0);
   if (nfb > 0 && (rc = trf_fallback_stage(p, dJ, df, ldJ, scale_mode, nfb, mask != nullptr))) return rc;
   if (nfb == 0 && mask && p->csne.count > 0 && (rc = p->csne.relist(ctx))) return rc;   // (refreshed problems have left the tier)
   return trf_finish(p);
@@ -385,16 +358,20 @@ int trf_lm_rounds(blsq_trf_plan* p, const double* dDelta, const double* dalpha_i
   int* counts = p->lm.active_count;
   hipError_t e;
   p->lm.fused_gram = 0;
+  auto lm_system = [&] {                                 // H = D G D + E^2 from the kept Gram, as every factor below takes it
+    GramCholArgs c{};
+    c.opt = &ctx->opt;
+    c.Gsrc = p->tree.gram_keep.as<double>(); c.NPAD = p->ld; c.n = p->n;
+    c.colscale = p->st.d; c.diag_vec = p->st.ediag; c.stride_vec = p->ld;
+    return c;
+  };
   if (p->use_chol && p->lm_enable && p->ld <= 80) {
     // N <= 80: the Gauss-Newton step, the bracket and ALL rounds of every normal-equations-path problem
     // in ONE launch (one wave per problem iterates to the end; chol_reg.hip).  Householder-path
     // problems of the same batch go through lm_start and the round loop below.
     // BLSQ_LM_FUSED = 0: lm_start + the round-by-round loop for everybody.
     if (ctx->opt.on(OPT_LM_FUSED)) {
-      GramCholArgs c{};
-      c.opt = &ctx->opt;
-      c.Gsrc = p->tree.gram_keep.as<double>(); c.NPAD = p->ld; c.n = p->n;
-      c.colscale = p->st.d; c.diag_vec = p->st.ediag; c.stride_vec = p->ld;
+      GramCholArgs c = lm_system();
       c.rinv = p->tree.gram_rinv.as<double>(); c.dsc = p->tree.gram_dsc.as<double>();
       if (int rc_ = ctx->run(K_LM_CHOL, "launch_lm_rounds_reg", [&] {
             return launch_lm_rounds_reg(c, p->lm, dDelta, dalpha_in, ctx->stream);
@@ -403,7 +380,7 @@ int trf_lm_rounds(blsq_trf_plan* p, const double* dDelta, const double* dalpha_i
       p->lm.fused_gram = 1;
     }
   }
-  int* pin = ctx->pinned + 32;                           // slot of round r: pin + 4 r
+  int* pin = ctx->pin(PIN_LM_ROUND0);                    // slot of round r (PIN_LM_ROUND0 + r): pin + 4 r
   int pin_seq[16] = {0};
   bool rides[16] = {false};
   int ride_rounds = 0;                                   // rounds [0, ride_rounds) are enqueued before their counter is read
@@ -420,10 +397,8 @@ int trf_lm_rounds(blsq_trf_plan* p, const double* dDelta, const double* dalpha_i
   auto landed = [&](int r) -> hipError_t { return ctx->await(pin + 4 * r, pin_seq[r]); };
   auto chol_round = [&](int round, int grid, const int* count_dev) -> hipError_t {
     // R_alpha = chol(D G D + E^2 + alpha I) straight from the Gram, active Gram-path problems
-    GramCholArgs c{};
-    c.opt = &ctx->opt;
-    c.Gsrc = p->tree.gram_keep.as<double>(); c.G = p->lm.Xa; c.NPAD = p->ld; c.n = p->n;
-    c.colscale = p->st.d; c.diag_vec = p->st.ediag; c.diag_sqrt = p->lm.sa; c.stride_vec = p->ld;
+    GramCholArgs c = lm_system();
+    c.G = p->lm.Xa; c.diag_sqrt = p->lm.sa;
     c.batch_list = p->lm.active_list + (size_t)(round & 1) * p->B;
     c.skip_path = p->path;
     c.qr_mask = p->lm.hmax ? p->lm.ncols_lm : nullptr;
@@ -524,8 +499,7 @@ int trf_csne_correct(blsq_trf_plan* p, const double* dDelta, const double* dalph
   blsq_ctx* ctx = p->ctx;
   CsneTier& tier = p->csne;
   CsneState& cs = tier.cs;
-  { int rc_ = tier.grow_part(ctx, (size_t)tier.count * cs.nchunk * ((size_t)cs.NE * p->ld + 16)); if (rc_) return rc_; }
-  HIPCHK(ctx, hipMemsetAsync(cs.counts + 1, 0, sizeof(int), ctx->stream));
+  if (int rc_ = tier.pass_begin(ctx)) return rc_;
   if (int rc_ = ctx->run(K_CSNE_PASS, "launch_csne_pass_trf", [&] {
         return launch_csne_pass_trf(cs, p->st.d, tier.count, ctx->stream);
       })) return rc_;
@@ -538,19 +512,14 @@ int trf_csne_correct(blsq_trf_plan* p, const double* dDelta, const double* dalph
 // ... and what became of them: problems the tier declined in this step call leave it — factored by CholeskyQR2 / the
 // Householder tree from the caller's J (still valid: the lifetime rule of the tier), prepared again from the triangle —
 // and the step runs once more (*redo).
-int trf_csne_verdict(blsq_trf_plan* p, int ncs, bool* redo) {
+int trf_csne_verdict(blsq_trf_plan* p, bool* redo) {
   blsq_ctx* ctx = p->ctx;
   const CsneState& cs = p->csne.cs;
   QrTree& t = p->tree;
-  int seq = 0;
-  HIPCHK(ctx, ctx->publish(cs.counts + 1, 1, ctx->pinned + 12, &seq));
-  HIPCHK(ctx, ctx->await(ctx->pinned + 12, seq));
-  const int nfail = ctx->pinned[12];
-  ctx->csne_steps += (unsigned long long)(ncs - nfail);
-  ctx->csne_declined += (unsigned long long)nfail;
+  int rc, nfail = 0;
+  if ((rc = p->csne.pass_verdict(ctx, /*polled=*/true, &nfail))) return rc;
   if (nfail == 0) return 0;
   *redo = true;
-  int rc;
   if ((rc = p->csne.reroute(ctx, t, nfail))) return rc;
   if ((rc = t.run_fallback(ctx, cs.J, cs.F, cs.ldJ, nfail))) return rc;
   if (int rc_ = ctx->run(K_PREP, "launch_trf_prep(csne redo)", [&] {
@@ -581,15 +550,9 @@ extern "C" int blsq_trf_factor_dev(blsq_trf_plan* p, const double* dJ, const dou
                                    const double* dx, const double* dlb, const double* dub,
                                    double* dscale_io, int scale_mode) {
   if (!p) return -1;
-  blsq_ctx* ctx = p->ctx;
-  if (int rc_ = factor_args(ctx, dJ, df, dx, dlb, dub, dscale_io, scale_mode)) return rc_;
-  HIPCHK(ctx, hipSetDevice(ctx->device));
-  int rc = verdict_published(p);               // (a verdict nobody read: its counters leave before they are cleared)
-  if (rc) return rc;
-  if ((rc = put_state(p, dx, dlb, dub, dscale_io, nullptr, hipMemcpyDeviceToDevice, true))) return rc;
-  p->pend_scale_io = dscale_io;
-  if ((rc = trf_factor_core(p, dJ, df, p->n, scale_mode, nullptr, true))) return rc;
-  return scale_back(p, dscale_io, scale_mode);
+  if (int rc_ = factor_args(p->ctx, dJ, df, dx, dlb, dub, dscale_io, scale_mode)) return rc_;
+  return factor_dev(p, dx, dlb, dub, dscale_io, scale_mode, nullptr,
+                    [&] { return trf_factor_core(p, dJ, df, p->n, scale_mode, nullptr, true); });
 }
 
 extern "C" int blsq_trf_step_dev(blsq_trf_plan* p, const double* dDelta, const double* dalpha_in,
@@ -613,7 +576,8 @@ extern "C" int blsq_trf_step_dev(blsq_trf_plan* p, const double* dDelta, const d
     p->lm_counts_clean = true;              // (the step kernel leaves the round counters zeroed)
     bool redo = false;
     if ((rc = p->resolve(&redo))) return rc;
-    if (!redo && ncs > 0 && (rc = trf_csne_verdict(p, ncs, &redo))) return rc;
+    // (no repair ran: the tier still holds the ncs problems of the pass)
+    if (!redo && ncs > 0 && (rc = trf_csne_verdict(p, &redo))) return rc;
     if (!redo) break;
   }
   return 0;
@@ -678,13 +642,9 @@ extern "C" int blsq_trf_fetch_step(blsq_trf_plan* p, double* alpha_out, double* 
   if ((rc = get_vec(ctx, p_h_tr, n, p->out.p_h_tr, ld, B))) return rc;
   if ((rc = get_vec(ctx, (long long*)hits, n, p->out.hits, ld, B))) return rc;
   if ((rc = get_vec(ctx, (long long*)active_new, n, p->out.active_new, ld, B))) return rc;
-  std::vector<double> sc((size_t)B * 8);
-  std::vector<int> inf((size_t)B * 4);
-  HIPCHK(ctx, hipMemcpyAsync(sc.data(), p->out.scal, sizeof(double) * sc.size(),
-                             hipMemcpyDeviceToHost, ctx->stream));
-  HIPCHK(ctx, hipMemcpyAsync(inf.data(), p->out.info, sizeof(int) * inf.size(),
-                             hipMemcpyDeviceToHost, ctx->stream));
-  if ((rc = blsq_sync(ctx))) return rc;
+  std::vector<double> sc;                   // [B][8]
+  std::vector<int> inf;                     // [B][4]
+  if ((rc = fetch_scal_info(p, &sc, &inf))) return rc;
   for (int b = 0; b < B; ++b) {
     if (predicted_reduction) predicted_reduction[b] = sc[8 * b + 0];
     if (step_h_norm) step_h_norm[b] = sc[8 * b + 1];
