@@ -319,7 +319,9 @@ class Context:
         return out
 
     def csne_stats(self, reset=False):
-        """-> (problems routed to the CSNE tier by factor calls, step-solves it delivered, step-solves it declined)."""
+        """-> (problems routed to the CSNE tier by factor calls, step-solves it delivered, step-solves it declined).
+        dogbox corrects at factor time, and a masked factor call of the outer driver corrects every problem on the tier
+        again, kept factors included: `delivered` counts those too."""
         out = (C.c_uint64 * 3)()
         self.check(self.lib.blsq_debug_csne_stats(self.h, out, 1 if reset else 0), "csne_stats")
         return int(out[0]), int(out[1]), int(out[2])

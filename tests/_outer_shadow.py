@@ -13,9 +13,28 @@ come from the committed CPU oracle (``oracle/blsq_oracle.py``).  Nothing here is
     (r, "orth")       as r; if the trial is accepted the fresh J is projected so that J^T f = 0 (status 1 next top)
     (r, "cols")       as r; the fresh J has its columns rescaled by 10^+-1 (the 'jac' scale update changes some
                       entries and keeps others)
+    (r, "kappa", c)   as r; the fresh J is of conditioning class c (below), or of the class after the problem's
+                      current one in KAPPA_CYCLE if c is "next"; composes with "cols"
 
-After an accept the fresh J is seeded Gaussian: J and f need not come from any function, so a 1e-10 difference in x
-between two implementations cannot steer the trajectory; only decisions can.
+After an accept the fresh J is seeded: J and f need not come from any function, so a 1e-10 difference in x between two
+implementations cannot steer the trajectory; only decisions can.
+
+Conditioning classes of a problem's current J (KAPPA): "well" is a Gaussian matrix; "tier" and "beyond" have singular
+values log-spaced over [1 / kappa, 1] sqrt(m) with kappa = 2e4 and 1.5e5 (the construction of
+``_geometry_cases._logspaced``), drawn from the problem's own stream.  ``J0_class[b]`` is the class of the first J, a
+"kappa" modifier sets the class of a fresh one; a J without either is "well".  ``sb.refreshes`` holds one entry
+(round, b, old class, new class) per fresh J, `round` being the round whose propose() factors it (the masked factor call
+of the device driver: always >= 1), and ``sb.classes[r]`` the class each problem active in round r steps on.  There is
+no rank-deficient class: the reference's step is determined by rounding noise there (tests/test_cqr2_gpu.py leaves such
+problems out of its parity check for that reason), so no implementation can be held to it.
+
+``ids``: ``ShadowBatch(..., ids=[b])`` is problem b of the batch the other arguments describe, played alone: its random
+stream is ``default_rng([seed, b])`` and its script, x0, bounds, scale and classes are row b of the batch's, so its log
+and every snapshot equal the batch's row b bit for bit (test_outer_script_cpu.py).
+
+``screen``: with ``sb.screen = k`` set before start(), every trial's step is computed again by the oracle on k copies of
+the current J with EVERY entry moved one ulp (``_geometry_cases.one_ulp``); the trial's log record gets
+``screen = (largest ||step' - step|| / ||step||, all masks / branch / choice / n_iter unchanged)``.
 
 To add a move: give it a branch in ``ShadowBatch._f_trial`` (what f_trial is) or ``_fresh_J`` (what the next J is), a
 tag in the loops' ``tags`` if it opens a new branch, and a case in ``CONFIGS`` whose script plays it;
@@ -35,6 +54,12 @@ TAGS_BOTH = ["shrink", "keep", "double", "good-but-inside", "reject", "exact-zer
              "status2", "status3", "status4", "pending-on-reject", "status-lost-to-max_nfev"]
 TAGS_DOGBOX = ["snap", "all-active", "tr_hit"]
 
+# conditioning classes of a scripted J: kappa_2(J).  "tier": the CSNE tier's own (_geometry_cases.CSNE_KAPPA); "beyond":
+# past the tier's measured bound (test_csne_gpu.py: 1.5e5 is declined) and still a decade inside what the oracle's own
+# step tolerates under one-ulp changes of J (at 1e6 numpy's Gauss-Newton step moves by 1e-10 of its norm)
+KAPPA = {"tier": 2e4, "beyond": 1.5e5}
+KAPPA_CYCLE = ["well", "tier", "beyond"]
+
 
 class Trial:
     """What the loop hands out where the reference calls fun(x_new)."""
@@ -48,7 +73,7 @@ def _snapshot(x, f, obj, g_norm, nfev, njev, on_bound, accepted):
                 on_bound=on_bound.copy(), status=0, accepted=bool(accepted))
 
 
-def trf_loop(x0, lb, ub, ftol, xtol, gtol, max_nfev, scale, log):
+def trf_loop(x0, lb, ub, ftol, xtol, gtol, max_nfev, scale, log, probe=None):
     """trf.py:201-358.  `scale`: the reference's ``1 / scaling`` (n,), or None for scaling='jac'.  Yields
     ('fun', x) / ('jac', x) / ('trial', Trial) and expects f / J / f_new back; ('judged', snapshot) after every
     trial (what a fetch must show then).  Returns the result dict.  Appends one record per trial and per top to `log`."""
@@ -93,6 +118,7 @@ def trf_loop(x0, lb, ub, ftol, xtol, gtol, max_nfev, scale, log):
         actual_reduction = -1
         while actual_reduction <= 0 and nfev < max_nfev:
             S = orc.trf_step(F, Delta, alpha)
+            screened = probe(S, J, f, x, scale, Delta, alpha, None) if probe else None
             alpha = S.alpha
             step_h, step, x_new = S.step_h, S.step, S.x_new
             predicted_reduction = S.predicted_reduction
@@ -108,7 +134,10 @@ def trf_loop(x0, lb, ub, ftol, xtol, gtol, max_nfev, scale, log):
             tags = set()
             rec = dict(kind='trial', ratio=float(ratio), tags=tags, Delta=float(Delta), shn=float(norm(step_h)),
                        pred=float(predicted_reduction), obj=float(obj_value),
-                       branch=S.branch, to_bound=S.to_bound, qp=np.array(S.qp), steps_h=S.steps_h, choice=S.choice)
+                       branch=S.branch, to_bound=S.to_bound, qp=np.array(S.qp), steps_h=S.steps_h, choice=S.choice,
+                       alpha=float(S.alpha), n_iter=int(S.n_iter), s_ratio=float(F.s[-1] / F.s[0]))
+            if screened is not None:
+                rec['screen'] = screened
             if ratio < 0.25:
                 Delta_new = 0.25 * norm(step_h)
                 alpha *= Delta / Delta_new
@@ -161,7 +190,7 @@ def trf_loop(x0, lb, ub, ftol, xtol, gtol, max_nfev, scale, log):
                 status=0)
 
 
-def dogbox_loop(x0, lb, ub, ftol, xtol, gtol, max_nfev, scale, log):
+def dogbox_loop(x0, lb, ub, ftol, xtol, gtol, max_nfev, scale, log, probe=None):
     """dogbox.py:131-272; same protocol as `trf_loop`."""
     jac_scaling = scale is None
     f = yield ('fun', x0.copy())
@@ -209,6 +238,7 @@ def dogbox_loop(x0, lb, ub, ftol, xtol, gtol, max_nfev, scale, log):
         actual_reduction = -1.0
         while actual_reduction <= 0 and nfev < max_nfev:
             S = orc.dogbox_step(F, Delta, on_bound)
+            screened = probe(S, J, f, x, scale, Delta, None, on_bound) if probe else None
             step, x_new, tr_hit = S.step, S.x_new, S.tr_hit
             predicted_reduction = S.predicted_reduction
             f_new = yield ('trial', Trial(x_new, step, predicted_reduction, 0.0, obj_value, f, x))
@@ -222,6 +252,8 @@ def dogbox_loop(x0, lb, ub, ftol, xtol, gtol, max_nfev, scale, log):
             tags = set()
             rec = dict(kind='trial', ratio=float(ratio), tags=tags, Delta=float(Delta), fallback=S.fallback,
                        pred=float(predicted_reduction), obj=float(obj_value))
+            if screened is not None:
+                rec['screen'] = screened
             if ratio < 0.25:
                 Delta = 0.25 * norm(step / scale, ord=np.inf)
                 tags.add('shrink')
@@ -287,19 +319,33 @@ class ShadowBatch:
         sb.judge(f_trial)             -> (accepted (B,) bool, expected fetch (dict of arrays), fresh J {b: (m, n)})
     """
 
-    def __init__(self, method, m, X0, lb, ub, scale, tols, max_nfev, scripts, seed, J0_mod=None):
+    def __init__(self, method, m, X0, lb, ub, scale, tols, max_nfev, scripts, seed, J0_mod=None, J0_class=None,
+                 ids=None):
         self.method = method
-        self.X0 = np.array(X0, dtype=float)
+        X0, lb, ub = np.array(X0, dtype=float), np.array(lb, dtype=float), np.array(ub, dtype=float)
+        scale = None if scale is None else np.array(scale, dtype=float)
+        J0_mod = J0_mod or {}
+        J0_class = list(J0_class) if J0_class is not None else ["well"] * len(X0)
+        self.ids = list(range(len(X0))) if ids is None else [int(i) for i in ids]
+        if ids is not None:                          # the rows `ids` of the batch, with the streams they have there
+            X0, lb, ub = X0[self.ids], lb[self.ids], ub[self.ids]
+            scale = None if scale is None else scale[self.ids]
+            scripts = [scripts[i] for i in self.ids]
+            J0_mod = {k: J0_mod[i] for k, i in enumerate(self.ids) if i in J0_mod}
+            J0_class = [J0_class[i] for i in self.ids]
+        self.X0 = X0
         self.B, self.n = self.X0.shape
         self.m = m
-        self.lb, self.ub = np.array(lb, dtype=float), np.array(ub, dtype=float)
+        self.lb, self.ub = lb, ub
         self.jac_scaling = scale is None
-        self.scale = np.ones((self.B, self.n)) if scale is None else np.array(scale, dtype=float)
+        self.scale = np.ones((self.B, self.n)) if scale is None else scale
         self.ftol, self.xtol, self.gtol = tols
         self.max_nfev = max_nfev
         self.scripts = scripts
         self.seed = seed
-        self.J0_mod = J0_mod or {}
+        self.J0_mod = J0_mod
+        self.J0_class = J0_class
+        self.screen = 0
         self.trf = method == 'trf'
         if self.trf:
             self.Xs = np.stack([orc.nudge_inside(self.X0[b], self.lb[b], self.ub[b], rstep=1e-10)
@@ -328,16 +374,54 @@ class ShadowBatch:
         u = self.rng[b].standard_normal(self.m)
         return u * math.sqrt(target / np.dot(u, u))
 
+    def _class_J(self, b, cls):
+        """A J of conditioning class `cls` from the problem's own stream ("well": the Gaussian draw)."""
+        rng, m, n = self.rng[b], self.m, self.n
+        if cls == "well":
+            return rng.standard_normal((m, n))
+        U, _ = np.linalg.qr(rng.standard_normal((m, n)))      # (_geometry_cases._logspaced)
+        V, _ = np.linalg.qr(rng.standard_normal((n, n)))
+        return (U * np.logspace(0, -np.log10(KAPPA[cls]), n)) @ V.T * np.sqrt(m)
+
     def _fresh_J(self, b, f):
-        J = self.rng[b].standard_normal((self.m, self.n))
-        if "cols" in self.mods[b]:
+        mods = self.mods[b]
+        new = "well"
+        if "kappa" in mods:
+            new = mods[mods.index("kappa") + 1]
+            if new == "next":
+                new = KAPPA_CYCLE[(KAPPA_CYCLE.index(self.cls[b]) + 1) % len(KAPPA_CYCLE)]
+        self.refreshes.append((self.rounds, self.ids[b], self.cls[b], new))
+        self.cls[b] = new
+        J = self._class_J(b, new)
+        if "cols" in mods:
             J = J * 10.0 ** self.rng[b].choice([-1.0, 1.0], size=self.n)
-        if "orth" in self.mods[b]:
+        if "orth" in mods:
             J = J - np.outer(f, f.dot(J)) / np.dot(f, f)
         return np.ascontiguousarray(J)
 
+    def _probe(self, b):
+        """The sensitivity screen of one trial (see the module's docstring); None when the screen is off."""
+        if not self.screen:
+            return None
+        import _geometry_cases as gc
+
+        def probe(S, J, f, x, scale, Delta, alpha, on_bound):
+            move, same = 0.0, True
+            for pat in range(self.screen):
+                Jp = gc.one_ulp(J, pat)
+                if self.trf:
+                    T = orc.trf_step(orc.trf_factor(Jp, f, x, self.lb[b], self.ub[b], scale), Delta, alpha)
+                    same = same and gc.trf_same(S, T)
+                else:
+                    T = orc.dogbox_step(orc.dogbox_factor(Jp, f, x, self.lb[b], self.ub[b], scale, on_bound), Delta,
+                                        on_bound)
+                    same = same and gc.dog_same(S, T)
+                move = max(move, float(norm(T.step - S.step) / norm(S.step)))
+            return move, same
+        return probe
+
     def _first_J(self, b, f, x0):
-        J = self.rng[b].standard_normal((self.m, self.n))
+        J = self._class_J(b, self.cls[b])
         mod = self.J0_mod.get(b)
         if mod is not None:                      # wanted sign of the gradient per variable (0: leave)
             g = J.T.dot(f)
@@ -371,7 +455,10 @@ class ShadowBatch:
         B, m, n = self.B, self.m, self.n
         loop = trf_loop if self.trf else dogbox_loop
         self.log = [[] for _ in range(B)]
-        self.rng = [np.random.default_rng([self.seed, b]) for b in range(B)]
+        self.rng = [np.random.default_rng([self.seed, i]) for i in self.ids]
+        self.cls = list(self.J0_class)
+        self.refreshes = []
+        self.classes = []
         self.pos = [0] * B
         self.mods = [()] * B
         self.moves = [None] * B
@@ -385,7 +472,7 @@ class ShadowBatch:
         for b in range(B):
             sc = None if self.jac_scaling else self.scale[b]
             g = loop(self.X0[b], self.lb[b], self.ub[b], self.ftol, self.xtol, self.gtol, self.max_nfev, sc,
-                     self.log[b])
+                     self.log[b], self._probe(b))
             self.gen.append(g)
             ev = next(g)
             assert ev[0] == 'fun'
@@ -418,6 +505,7 @@ class ShadowBatch:
 
     def judge(self, ft):
         B = self.B
+        self.classes.append({self.ids[b]: self.cls[b] for b in range(B) if self.trial[b] is not None})
         self.rounds += 1
         states, fresh = [None] * B, {}
         for b in range(B):
@@ -586,9 +674,83 @@ for _m in ('trf', 'dogbox'):
         CONFIGS['termination-%s-%s' % (_m, _c)] = (lambda _m=_m, _c=_c: _termination(_m, _c, 21))
     CONFIGS['shape-%s-3x300x257' % _m] = (lambda _m=_m: _shape(_m, 3, 300, 257, 31))
     CONFIGS['shape-%s-4x1x1' % _m] = (lambda _m=_m: _shape(_m, 4, 1, 1, 34))
+
+
+# ---- one configuration per factorisation route a masked factor call can take (test_outer_route_gpu.py) -------------
+# route -> (library switches, shapes, whether the conditioning cycle is played)
+ROUTES = {
+    "rl":    ({},                ((160, 96), (300, 256)), False),
+    "tree":  ({"gram": 0},       ((160, 96),),            False),
+    "svd":   ({"no_svdfree": 1}, ((90, 33),),             False),
+    "short": ({},                ((40, 60),),             False),
+    "tier":  ({},                ((600, 96),),            True),
+    "cqr2":  ({"csne": 0},       ((600, 96),),            True),
+}
+ROUTE_NFEV = 12
+# the cycle's scripts: every move that can be accepted advances the problem's class.  Rotation and first class per
+# problem were searched (on the accept pattern of BASE alone, no numbers involved) for the coverage that
+# test_outer_script_cpu.py::test_conditioning_cycle_covers_the_masked_branches asserts.
+CYCLE_BASE = [(mv, "kappa", "next") if isinstance(mv, float) else mv for mv in BASE]
+CYCLE_ROT = (1, 3, 4, 6, 8, 9)
+CYCLE_START = ("beyond", "beyond", "tier", "well", "tier", "beyond")
+
+
+def _route_bounds(method, route, rng, B, n):
+    cycle = ROUTES[route][2]
+    if not cycle:
+        if method == 'trf' and route == 'short':
+            # m < n: without bounds the augmented matrix of trf.py:264-268 has rank m and, with Delta beyond the
+            # minimum-norm step, the reference's own step is decided by LAPACK's null-space outputs (noise,
+            # not a parity case); with two-sided bounds and a carried alpha its sub-problem solver leaves the bracket
+            # and raises (trust_region.py:28-35, cf. _geometry_cases.RAISED).  One-sided bounds: about half the
+            # variables are regularised by the Coleman-Li block, the matrix has full column rank
+            # (test_outer_script_cpu.py::test_short_trf_steps_are_determined holds every trial to that)
+            return _mixed_bounds(rng, B, n, kinds=(1, 2))
+        return _mixed_bounds(rng, B, n, kinds=(0, 1, 2, 3, 4, 5) if B >= 6 else (0, 1, 2))
+    if method == 'trf':                         # the bound kinds the tier takes: unbounded and upper bounds only
+        return _mixed_bounds(rng, B, n, kinds=(0, 2))
+    # dogbox: unbounded, and wide two-sided bounds with a tenth of the variables sitting on the lower one
+    X0 = rng.standard_normal((B, n))
+    lb, ub = X0 - rng.uniform(50.0, 500.0, (B, n)), X0 + rng.uniform(50.0, 500.0, (B, n))
+    for b in range(B):
+        if b % 2 == 0:
+            lb[b], ub[b] = -np.inf, np.inf
+        else:
+            idx = rng.choice(n, n // 10, replace=False)
+            X0[b, idx] = lb[b, idx]
+    return X0, lb, ub
+
+
+def _route(method, route, m, n, seed, ids=None):
+    cycle = ROUTES[route][2]
+    B = 3 if n >= 256 else 6
+    rng = np.random.default_rng([seed, 5])
+    X0, lb, ub = _route_bounds(method, route, rng, B, n)
+    if cycle:
+        scripts = [_rot(CYCLE_BASE, CYCLE_ROT[b]) for b in range(B)]
+        start = CYCLE_START[:B]
+    else:                                       # (B = 6: rotations that leave accepts AND rejects in every round)
+        scripts = [_rot(BASE, k) for k in ((0, 1, 2, 3, 4, 6) if B >= 6 else (0, 3, 6))]
+        start = None
+    return ShadowBatch(method, m, X0, lb, ub, np.ones((B, n)), (OFF, OFF, OFF), ROUTE_NFEV, scripts, seed,
+                       J0_class=start, ids=ids)
+
+
+ROUTE_SEED = 51
+for _m in ('trf', 'dogbox'):
+    for _r, (_o, _shapes, _c) in ROUTES.items():
+        for (_mm, _nn) in _shapes:
+            CONFIGS['route-%s-%s-%dx%d' % (_m, _r, _mm, _nn)] = (
+                lambda ids=None, _m=_m, _r=_r, _mm=_mm, _nn=_nn: _route(_m, _r, _mm, _nn, ROUTE_SEED, ids))
 CONFIGS['shape-trf-300x6x3'] = lambda: _shape('trf', 300, 6, 3, 32, max_nfev=8, base=BASE_300, kinds=(0, 1, 2, 4, 5))
 CONFIGS['starts-dogbox'] = lambda: _dogbox_starts(41)
 
 
 def method_of(name):
     return 'dogbox' if 'dogbox' in name else 'trf'
+
+
+def route_of(name):
+    """The route of a 'route-<method>-<route>-<m>x<n>' configuration (None for the others)."""
+    parts = name.split('-')
+    return parts[2] if parts[0] == 'route' else None

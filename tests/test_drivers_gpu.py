@@ -315,18 +315,10 @@ def test_device_outer_driver_torch_callbacks_subprocess():
     assert any(l.startswith("dogbox: device driver, torch callbacks") for l in lines)
 
 
-@pytest.mark.parametrize("method", ["2-point", "3-point"])
-@pytest.mark.parametrize("case", ["unbounded", "bounded", "at_bounds", "rel_step"])
-def test_fd_jacobian_matches_scipy_approx_derivative(method, case):
-    """blsq_fd_points_dev / blsq_fd_assemble_dev restate scipy's approx_derivative (the
-    third-party routine behind the reference's jac='2-point'|'3-point', least_squares.py:357-365)
-    for a batch: same steps (bounds-aware, one-sided switching), same points, same quotient —
-    bit for bit, problem by problem."""
-    from scipy.optimize._numdiff import approx_derivative
-    from bounded_lsq import _abi
-    from bounded_lsq._fd import FdJacobian
+def _fd_problem(case, shape):
+    """The inputs of the finite-difference tests: (fun_b, fun_points, X, F0, lb, ub, rel)."""
     rng = np.random.default_rng(3)
-    B, m, n = 5, 37, 9
+    B, m, n = shape
     A = rng.standard_normal((B, m, n))
     Y = rng.standard_normal((B, m))
     X = rng.uniform(-2.0, 2.0, (B, n))
@@ -339,10 +331,10 @@ def test_fd_jacobian_matches_scipy_approx_derivative(method, case):
         ub[:, ::2] = X[:, ::2]
         lb[:, 1::3] = X[:, 1::3]
     if case in ("bounded", "at_bounds"):
-        lb[1] = -np.inf                                      # half-bounded problems
-        ub[2] = np.inf
+        lb[1 % B] = -np.inf                                  # half-bounded problems
+        ub[2 % B] = np.inf
     if case == "rel_step":
-        rel = np.full(n, 1e-6); rel[3] = 0.0                 # 0 -> scipy substitutes its default
+        rel = np.full(n, 1e-6); rel[min(3, n - 1)] = 0.0     # 0 -> scipy substitutes its default
 
     def fun_b(x, b):
         return A[b] @ np.tanh(x) + 0.1 * (x @ x) - Y[b]
@@ -351,6 +343,15 @@ def test_fd_jacobian_matches_scipy_approx_derivative(method, case):
         return np.stack([np.stack([fun_b(Xp[b, p], b) for p in range(Xp.shape[1])]) for b in range(B)])
 
     F0 = np.stack([fun_b(X[b], b) for b in range(B)])
+    return fun_b, fun_points, X, F0, lb, ub, rel
+
+
+def _fd_against_scipy(method, case, shape):
+    from scipy.optimize._numdiff import approx_derivative
+    from bounded_lsq import _abi
+    from bounded_lsq._fd import FdJacobian
+    B, m, n = shape
+    fun_b, fun_points, X, F0, lb, ub, rel = _fd_problem(case, shape)
     ctx = _abi.Context(0)
     fd = FdJacobian(ctx, B, m, n, method, rel)
     try:
@@ -360,7 +361,70 @@ def test_fd_jacobian_matches_scipy_approx_derivative(method, case):
     for b in range(B):
         Jref = approx_derivative(lambda x: fun_b(x, b), X[b], method=method, rel_step=rel,
                                  f0=F0[b], bounds=(lb[b], ub[b]))
-        np.testing.assert_array_equal(J[b], Jref)
+        np.testing.assert_array_equal(J[b], np.atleast_2d(Jref))       # (m = 1: scipy returns the row alone)
+
+
+def _fd_methods_and_cases(fn):
+    """Both difference schemes over the four bound / step cases (ids: ...-<case>-<method>)."""
+    fn = pytest.mark.parametrize("case", ["unbounded", "bounded", "at_bounds", "rel_step"])(fn)
+    return pytest.mark.parametrize("method", ["2-point", "3-point"])(fn)
+
+
+@_fd_methods_and_cases
+def test_fd_jacobian_matches_scipy_approx_derivative(method, case):
+    """blsq_fd_points_dev / blsq_fd_assemble_dev restate scipy's approx_derivative (the
+    third-party routine behind the reference's jac='2-point'|'3-point', least_squares.py:357-365)
+    for a batch: same steps (bounds-aware, one-sided switching), same points, same quotient —
+    bit for bit, problem by problem."""
+    _fd_against_scipy(method, case, (5, 37, 9))
+
+
+@_fd_methods_and_cases
+@pytest.mark.parametrize("shape", [(3, 65, 33), (2, 64, 64), (2, 33, 32), (4, 1, 1)])
+def test_fd_jacobian_tiles_match_scipy_approx_derivative(method, case, shape):
+    """The same, bit for bit, at the shapes the 32 x 32 transpose of fd_assemble_kernel goes wrong at first: a second
+    tile of rows and of columns with one row / column in it, full tiles only, a full column tile beside a ragged row
+    tile, and the 1 x 1 problem."""
+    _fd_against_scipy(method, case, shape)
+
+
+@pytest.mark.parametrize("method", ["2-point", "3-point"])
+def test_fd_assemble_with_a_mask_leaves_the_other_problems_alone(method):
+    """blsq_fd_assemble_dev with the mask of the driver's masked `jac` callback: a problem with mask[b] == 0 keeps what
+    its J held, byte for byte; the others equal scipy's approx_derivative."""
+    from scipy.optimize._numdiff import approx_derivative
+    from bounded_lsq import _abi
+    from bounded_lsq._abi import ptr
+    from bounded_lsq._fd import FdJacobian
+    shape = B, m, n = 5, 37, 33
+    fun_b, fun_points, X, F0, lb, ub, rel = _fd_problem("bounded", shape)
+    mask = np.array([1, 0, 7, 0, 1], dtype=np.int32)
+    sentinel = np.random.default_rng(4).standard_normal((B, m, n))
+    sentinel[1, 0, 0] = np.nan
+    ctx = _abi.Context(0)
+    fd = FdJacobian(ctx, B, m, n, method, rel)
+    held = []
+    try:
+        d = [ctx.to_device(a) for a in (X, lb, ub)]
+        held += d
+        d_f0, d_J, d_mask = ctx.to_device(F0), ctx.to_device(sentinel), ctx.to_device(mask)
+        held += [d_f0, d_J, d_mask]
+        fd.points(*d)
+        Fp = np.ascontiguousarray(fun_points(ctx.to_host(fd.d_X, (B, fd.P, n), np.float64)))
+        ctx.check(ctx.lib.blsq_memcpy_h2d(ctx.h, fd.d_F, ptr(Fp), Fp.nbytes), "h2d(F)")
+        fd.assemble(d[0], d_f0, d_J, d_mask)
+        J = ctx.to_host(d_J, (B, m, n), np.float64)
+    finally:
+        for p_ in held:
+            ctx.free(p_)
+        fd.close(); ctx.close()
+    for b in range(B):
+        if mask[b] == 0:
+            assert J[b].tobytes() == sentinel[b].tobytes(), b
+        else:
+            Jref = approx_derivative(lambda x: fun_b(x, b), X[b], method=method, rel_step=rel,
+                                     f0=F0[b], bounds=(lb[b], ub[b]))
+            np.testing.assert_array_equal(J[b], Jref)
 
 
 @pytest.mark.parametrize("method", ["trf", "dogbox"])
