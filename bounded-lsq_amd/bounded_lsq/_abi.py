@@ -21,15 +21,63 @@ c_uint8_p = C.POINTER(C.c_uint8)
 vp = C.c_void_p
 
 
-def _model_eval(lead, mapped=True, tie=False):
-    """A blsq_model_eval*_dev entry: ctx, `lead`, B, reps, m, n (mapped: nf, pmap; tie: tie_ratio, tie_offset), t,
-    t_stride, y, w, w_stride, X (mapped: Pfix), f, J, mask."""
-    return (C.c_int, [vp] + lead + [C.c_int] * 4 + ([C.c_int, c_int32_p] if mapped else [])
-            + ([c_double_p, c_double_p] if tie else [])
-            + [vp, C.c_long, vp, vp, C.c_long, vp] + ([vp] if mapped else []) + [vp] * 3)
+# The model-eval entries (include/blsq.h): the arguments each takes behind ctx, by name and in header order (dt, dy, ...
+# of the header without the d; dX / dP is X; G is B).  A new entry is one row here.
+MODEL_EVAL_ARGS = {name: tuple(args.split()) for name, args in {
+    "blsq_model_eval_dev":
+        "model B reps m n t t_stride y w w_stride X f J mask",
+    "blsq_model_eval_map_dev":
+        "model B reps m n nf pmap t t_stride y w w_stride X Pfix f J mask",
+    "blsq_model_eval_comp_dev":
+        "ncomp fam cnt B reps m n nf pmap t t_stride y w w_stride X Pfix f J mask",
+    "blsq_model_eval_est_dev":
+        "est model ncomp fam cnt B reps m n nf pmap t t_stride y w w_stride X Pfix f J mask",
+    "blsq_model_eval_bin_dev":
+        "est sampling model ncomp fam cnt B reps m n nf pmap t t_stride y w w_stride X Pfix f J mask",
+    "blsq_model_eval_nan_dev":
+        "est sampling nan_policy model ncomp fam cnt B reps m n nf pmap t t_stride y w w_stride X Pfix f J mask",
+    "blsq_model_eval_global_dev":
+        "est sampling nan_policy model ncomp fam cnt S shared t_sstride B reps m n nf pmap t t_stride y w w_stride X "
+        "Pfix f J mask",
+    "blsq_model_eval_tie_dev":
+        "est sampling nan_policy model ncomp fam cnt S shared t_sstride B reps m n nf pmap tie_ratio tie_offset t "
+        "t_stride y w w_stride X Pfix f J mask",
+}.items()}
+# ... and the C type of each name: device pointers are void*, the host tables typed pointers
+MODEL_EVAL_TYPES = dict(
+    [(k, C.c_int) for k in "est sampling nan_policy model ncomp S B reps m n nf".split()]
+    + [(k, C.c_long) for k in "t_sstride t_stride w_stride".split()]
+    + [(k, c_int32_p) for k in "fam cnt shared pmap".split()]
+    + [(k, c_double_p) for k in "tie_ratio tie_offset".split()]
+    + [(k, vp) for k in "t y w X Pfix f J mask".split()])
+# what a name holds when the feature it belongs to is off: an entry without the name can still serve such a call
+# (`nf` is neutral when it equals n: no map)
+_MODEL_EVAL_NEUTRAL = dict(est=0, sampling=0, nan_policy=0, model=-1, ncomp=0, fam=None, cnt=None, S=0, shared=None,
+                           t_sstride=0, pmap=None, tie_ratio=None, tie_offset=None, Pfix=None)
 
 
-_COMP = [C.c_int, c_int32_p, c_int32_p]      # ncomp, fam, cnt
+def model_eval_args(entry, values, strict=True):
+    """The positional arguments of `entry` behind ctx from `values` by name, passed through verbatim.  A name of
+    another entry that `entry` does not take: strict, it must be absent or at its neutral value (ValueError naming it
+    otherwise: the entry cannot do what the caller asks); not strict, it is dropped.  A name no entry takes, or a
+    missing one, is a TypeError either way."""
+    names = MODEL_EVAL_ARGS[entry]
+
+    def neutral(k, v):
+        if k == "nf":
+            return v == values.get("n")
+        ref = _MODEL_EVAL_NEUTRAL.get(k, ())                  # (): a name with no neutral value
+        return v is None if ref is None else v == ref
+    for k, v in values.items():
+        if k not in MODEL_EVAL_TYPES:
+            raise TypeError("%s: no model-eval entry takes an argument %r" % (entry, k))
+        if strict and k not in names and not neutral(k, v):
+            raise ValueError("%s takes no `%s` (got %r)" % (entry, k, v))
+    missing = [k for k in names if k not in values]
+    if missing:
+        raise TypeError("%s needs %s" % (entry, ", ".join(missing)))
+    return [values[k] for k in names]
+
 
 # every symbol include/blsq.h declares: name -> (restype, argtypes)
 SIGNATURES = {
@@ -126,19 +174,11 @@ SIGNATURES = {
     "blsq_outer_leverage": (C.c_int, [vp, vp, vp]),
     "blsq_model_count": (C.c_int, []),
     "blsq_model_info": (C.c_int, [C.c_int, C.POINTER(C.c_char_p), c_int32_p, c_int32_p, c_int32_p]),
-    "blsq_model_eval_dev": _model_eval([C.c_int], mapped=False),                 # model
-    "blsq_model_eval_map_dev": _model_eval([C.c_int]),
     "blsq_term_count": (C.c_int, []),
     "blsq_term_info": (C.c_int, [C.c_int, C.POINTER(C.c_char_p), c_int32_p]),
-    "blsq_model_eval_comp_dev": _model_eval(_COMP),
-    "blsq_model_eval_est_dev": _model_eval([C.c_int] * 2 + _COMP),                # est, model
-    "blsq_model_eval_bin_dev": _model_eval([C.c_int] * 3 + _COMP),                # est, sampling, model
-    "blsq_model_eval_nan_dev": _model_eval([C.c_int] * 4 + _COMP),                # est, sampling, nan_policy, model
-    # ... and after the table S, shared, t_sstride (B is G)
-    "blsq_model_eval_global_dev": _model_eval([C.c_int] * 4 + _COMP + [C.c_int, c_int32_p, C.c_long]),
-    # ... and behind pmap tie_ratio, tie_offset (host doubles [n]); S == 0: a plain batch
-    "blsq_model_eval_tie_dev": _model_eval([C.c_int] * 4 + _COMP + [C.c_int, c_int32_p, C.c_long], tie=True),
 }
+SIGNATURES.update((name, (C.c_int, [vp] + [MODEL_EVAL_TYPES[k] for k in args]))
+                  for name, args in MODEL_EVAL_ARGS.items())
 
 _lib = None
 

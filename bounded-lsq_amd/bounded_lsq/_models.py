@@ -883,22 +883,6 @@ def sigma_weights(sigma, lead, m, omitted=None):
     return 1.0 / sg, False
 
 
-# the model-eval entries (include/blsq.h) and the runs of arguments each takes besides ctx, B, reps, m, n, the data and
-# X, f, J, mask: how many of the flags est, sampling, nan_policy in front; the model id; the component table ncomp, fam,
-# cnt; nf, pmap (and Pfix behind X); the run S, shared, t_sstride; the pair tie_ratio, tie_offset
-_ENTRIES = {                      # flags  id     table  mapped  S-run  tie
-    "blsq_model_eval_dev":        (0, True,  False, False, False, False),
-    "blsq_model_eval_map_dev":    (0, True,  False, True,  False, False),
-    "blsq_model_eval_comp_dev":   (0, False, True,  True,  False, False),
-    "blsq_model_eval_est_dev":    (1, True,  True,  True,  False, False),
-    "blsq_model_eval_bin_dev":    (2, True,  True,  True,  False, False),
-    "blsq_model_eval_nan_dev":    (3, True,  True,  True,  False, False),
-    "blsq_model_eval_global_dev": (3, True,  True,  True,  True,  False),
-    "blsq_model_eval_tie_dev":    (3, True,  True,  True,  True,  True),
-}
-
-
-
 class DeviceModel:
     """Model `name` (a name, a composite spec or a ``CompositeModel``) with its data resident on the GPU: the device callbacks of ``OuterDriver.run_device``.
 
@@ -1013,8 +997,8 @@ class DeviceModel:
         return self.bounds_dev
 
     def _bind(self, m, pm, pmap, shared):
-        """The entry of this fit and every argument it takes behind ctx, fixed once the data are uploaded (`_eval`
-        fills in reps, X, f, J and mask).  The entry is the one of the last flag the fit sets (it takes every kind of
+        """The entry of this fit and every argument it takes behind ctx, fixed once the data are uploaded (`self._eval`,
+        made here, fills in reps, X, f, J and mask).  The entry is the one of the last flag the fit sets (it takes every kind of
         model and the flags before it); without a flag, the entry of the kind of model.  `m`: the points of one data
         set; `pm`: the ParamMap of the fit (a global fit's own) or None, `pmap` its int32 map; `shared`: the int32 flags of
         the slots a group shares, or None."""
@@ -1033,36 +1017,36 @@ class DeviceModel:
             name = "blsq_model_eval_comp_dev"
         else:
             name = "blsq_model_eval_dev" if pm is None else "blsq_model_eval_map_dev"
-        flags, has_id, table, mapped, s_run, tie = _ENTRIES[name]
-        ties = [np.ascontiguousarray(a, dtype=np.float64) for a in ((pm.ratio, pm.offset) if tie else ())]
-        self._host = (pmap, shared, ties)                     # the host arrays the entry reads: alive with the model
+        tie = name == "blsq_model_eval_tie_dev"
+        ratio, offset = ((np.ascontiguousarray(a, dtype=np.float64) for a in (pm.ratio, pm.offset)) if tie
+                         else (None, None))
+        self._host = (pmap, shared, ratio, offset)            # the host arrays the entry reads: alive with the model
 
-        def i32(a):
-            return None if a is None else a.ctypes.data_as(_abi.c_int32_p)
-        args = [ESTIMATORS.index(self.estimator), SAMPLING.index('bin' if self.binned else 'point'),
-                NAN_POLICIES.index(self.nan_policy)][:flags]
-        if has_id:
-            args.append(-1 if comp else M.id)
-        if table:
-            args += [len(M.components), i32(M.fam_ids), i32(M.counts)] if comp else [0, None, None]
-        if s_run:                                             # S == 0: a plain batch
-            args += [0, None, 0] if gm is None else [gm.S, i32(shared), self.t_sstride]
-        at_reps = len(args) + 1
-        args += [self.B, 1, m, self.n_model]
-        if mapped:                                            # nf: per data set in a global fit
-            args += [self.n if gm is None else gm.nf, i32(pmap)]
-        args += [a.ctypes.data_as(_abi.c_double_p) for a in ties]
-        args += [self.d_t, self.t_stride, self.d_y, self.d_w, self.w_stride, None]
-        self._call = (name, args + ([self.d_Pfix] if mapped else []) + [None, None, None], at_reps, len(args) - 1)
+        def host(a, ptr_type=_abi.c_int32_p):
+            return None if a is None else a.ctypes.data_as(ptr_type)
+        values = dict(
+            est=ESTIMATORS.index(self.estimator), sampling=SAMPLING.index('bin' if self.binned else 'point'),
+            nan_policy=NAN_POLICIES.index(self.nan_policy), model=-1 if comp else M.id,
+            ncomp=len(M.components) if comp else 0, fam=host(M.fam_ids) if comp else None,
+            cnt=host(M.counts) if comp else None,
+            S=0 if gm is None else gm.S, shared=host(shared), t_sstride=self.t_sstride,       # S == 0: a plain batch
+            B=self.B, reps=1, m=m, n=self.n_model,
+            nf=self.n if gm is None else gm.nf, pmap=host(pmap),                              # nf: per data set
+            tie_ratio=host(ratio, _abi.c_double_p), tie_offset=host(offset, _abi.c_double_p),
+            t=self.d_t, t_stride=self.t_stride, y=self.d_y, w=self.d_w, w_stride=self.w_stride, X=None,
+            Pfix=self.d_Pfix, f=None, J=None, mask=None)
+        # strict: the entry chosen above has a slot for everything this fit sets, or this raises
+        a, ctx = _abi.model_eval_args(name, values), self.ctx
+        at_reps, at_x, at_f, at_J, at_mask = (_abi.MODEL_EVAL_ARGS[name].index(k) for k in ("reps", "X", "f", "J", "mask"))
 
-    def _eval(self, x_ptr, reps, f_ptr, J_ptr, mask_ptr):
-        name, a, at_reps, at_x = self._call
-        a[at_reps] = int(reps)
-        a[at_x] = x_ptr
-        a[-3] = f_ptr
-        a[-2] = J_ptr
-        a[-1] = mask_ptr
-        self.ctx.check(getattr(self.ctx.lib, name)(self.ctx.h, *a), name)
+        def _eval(x_ptr, reps, f_ptr, J_ptr, mask_ptr):       # twice per outer iteration: five stores and the call
+            a[at_reps] = int(reps)
+            a[at_x] = x_ptr
+            a[at_f] = f_ptr
+            a[at_J] = J_ptr
+            a[at_mask] = mask_ptr
+            ctx.check(getattr(ctx.lib, name)(ctx.h, *a), name)
+        self._eval = _eval
 
     def fun_dev(self, x_ptr, f_ptr, reps=1):
         self._eval(x_ptr, reps, f_ptr, None, None)

@@ -1,12 +1,15 @@
 """Inputs shared by tests/test_binned_cpu.py and tests/test_binned_gpu.py: the grid, the 40-digit
 quadrature reference and the measured error figures of the definition test; the model instances, seeded inputs and
 first-order error bound of the kernel-level comparison; and the histogram problems of the end-to-end fits."""
+import functools
+
 import numpy as np
 from scipy import special
 
-from bounded_lsq import ParamMap, models
+from bounded_lsq import models
 
 import _poisson_cases as pc
+from _model_cases import worst_ratio  # noqa: F401  (handed on to the tests)
 
 EPS = np.finfo(float).eps
 
@@ -195,17 +198,9 @@ INSTANCES = {
 }
 
 
-def is_composite(label):
-    return "+" in INSTANCES[label][0]
-
-
-def model_of(label):
-    return models.resolve(INSTANCES[label][0])
-
-
-def map_of(label):
-    name, n, fixed, tied, rng = INSTANCES[label]
-    return None if fixed is None and tied is None else ParamMap(n, fixed, tied)
+is_composite = functools.partial(pc.mc.is_composite, INSTANCES)
+model_of = functools.partial(pc.mc.model_of, INSTANCES)
+map_of = functools.partial(pc.mc.map_of, INSTANCES)
 
 
 def components_of(label):
@@ -477,14 +472,6 @@ def expected(label, case, est, reps, weighted=True):
         cq = Q(cc, np.abs(cc) * (2 * EPS * T_c + v.e / np.abs(v.v)))
         Jq = [cq * c for c in cols]
     return (f.v, np.stack([c.v for c in Jq], axis=-1), f.e, np.stack([c.e for c in Jq], axis=-1))
-
-
-def worst_ratio(got, ref, tol):
-    """max |got - ref| / tol; where tol is 0 the values must be equal (0), or the ratio is inf."""
-    d = np.abs(np.asarray(got) - ref)
-    with np.errstate(all="ignore"):
-        ratio = np.where(tol > 0, d / np.where(tol > 0, tol, 1), np.where(d == 0, 0.0, np.inf))
-    return float(np.max(ratio))
 
 
 # ---- end to end ----------------------------------------------------------------------------------------------------

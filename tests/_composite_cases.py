@@ -6,6 +6,8 @@ import numpy as np
 
 from bounded_lsq import models
 
+from _model_cases import worst_ratio  # noqa: F401  (the case modules hand it on)
+
 LD = np.longdouble
 EPS = np.finfo(float).eps
 
@@ -147,13 +149,6 @@ def numpy_weighted(spec, x, P, w, y, reps, per_problem):
     yr = 0.0 if y is None else np.repeat(y, reps, axis=0)
     wj = wr if np.ndim(wr) == 0 else np.asarray(wr)[..., np.newaxis]
     return wr * (M.f(xr, P) - yr), wj * M.jac(xr, P)
-
-
-def worst_ratio(got, ref, tol):
-    """max |got - ref| / tol; inf where tol is 0 and the values differ."""
-    ratio = np.abs(np.asarray(got).astype(LD) - ref) / np.where(tol > 0, tol, 1)
-    ratio = np.where(tol > 0, ratio, np.where(got == ref, 0, np.inf))
-    return float(np.max(ratio))
 
 
 # ---- end-to-end fit problems ---------------------------------------------------------------------------------------

@@ -2,10 +2,34 @@
 comparisons, the rounding-error bound of one model evaluation, and the seeded fit problems of the end-to-end tests."""
 import numpy as np
 
-from bounded_lsq import models
+from bounded_lsq import ParamMap, models
 
 LD = np.longdouble
 EPS = np.finfo(float).eps
+
+
+# ---- the instance tables of the case modules: label -> (name or spec, n, fixed, tied, ...) -------------------------------
+def is_composite(instances, label):
+    return "+" in instances[label][0]
+
+
+def model_of(instances, label):
+    return models.resolve(instances[label][0])
+
+
+def map_of(instances, label):
+    name, n, fixed, tied = instances[label][:4]
+    return None if fixed is None and tied is None else ParamMap(n, fixed, tied)
+
+
+def worst_ratio(got, ref, tol):
+    """max |got - ref| / tol, the difference taken in the precision of `ref`; where tol is 0 the values must be equal
+    (0), or the ratio is inf."""
+    got = np.asarray(got)
+    d = np.abs(got.astype(np.result_type(got, ref)) - ref)
+    with np.errstate(all="ignore"):
+        ratio = np.where(tol > 0, d / np.where(tol > 0, tol, 1), np.where(d == 0, 0.0, np.inf))
+    return float(np.max(ratio))
 
 
 def case_inputs(name, n, B, m, seed=0, per_problem=False):

@@ -1,36 +1,35 @@
 """Cases of the missing-data tests (nan_policy='omit'): the kernel instances, their inputs and NaN
 patterns for tests/test_nan_policy_gpu.py, and the fit problems with their per-problem patterns, which
 tests/test_nan_policy_cpu.py vets on the host (every problem keeps more points than it has free parameters)."""
+import functools
+
 import numpy as np
 
-from bounded_lsq import ParamMap, models
+from bounded_lsq import models
+
+import _model_cases as mc
 
 ROWS = [1, 63, 64, 65, 130]                       # the edges of the 64-row tile
 SENTINEL = 1234.5                                 # what f and J hold before a launch
 
-# label -> (name or spec, n, keywords of the ParamMap or None)
+# label -> (name or spec, n, fixed, tied)
 INSTANCES = {
-    "gauss_sum": ("gauss_sum", 4, None),
-    "poly": ("poly", 3, None),
-    "gauss2d": ("gauss2d", 5, None),
-    "composite": ("gauss*2+lorentz+pvoigt+poly*3", 16, None),
-    "wide": ("pvoigt*15+poly*4", 64, None),                   # n = 64: one wave per workgroup
-    "mapped": ("gauss_sum", 7, dict(fixed=[6], tied={5: 2})),   # nf = 5 < n = 7
+    "gauss_sum": ("gauss_sum", 4, None, None),
+    "poly": ("poly", 3, None, None),
+    "gauss2d": ("gauss2d", 5, None, None),
+    "composite": ("gauss*2+lorentz+pvoigt+poly*3", 16, None, None),
+    "wide": ("pvoigt*15+poly*4", 64, None, None),             # n = 64: one wave per workgroup
+    "mapped": ("gauss_sum", 7, [6], {5: 2}),                  # nf = 5 < n = 7
 }
 PATTERNS = ["none", "first", "last", "seam", "alternate", "tile", "problem"]
 
 
-def model_of(label):
-    return models.resolve(INSTANCES[label][0])
-
-
-def map_of(label):
-    name, n, kw = INSTANCES[label]
-    return None if kw is None else ParamMap(n, **kw)
+model_of = functools.partial(mc.model_of, INSTANCES)
+map_of = functools.partial(mc.map_of, INSTANCES)
 
 
 def _roles(label):
-    name, n, _ = INSTANCES[label]
+    name, n = INSTANCES[label][:2]
     M = model_of(label)
     if isinstance(M, models.CompositeModel):
         out = []

@@ -2,9 +2,11 @@
 precision reference of the transform test, the model instances, seeded inputs and error bound of the kernel-level
 comparison (the derivation is in the docstring of test_poisson_gpu.py::test_kernel_against_definition), and the seeded
 count data of the end-to-end fits."""
+import functools
+
 import numpy as np
 
-from bounded_lsq import ParamMap, models
+from bounded_lsq import models
 
 import _composite_cases as cc
 import _model_cases as mc
@@ -100,17 +102,9 @@ B = 3
 LOG1P_ULP = 2                # the error allowed to the device's log1p, in ulp
 
 
-def is_composite(label):
-    return "+" in INSTANCES[label][0]
-
-
-def model_of(label):
-    return models.resolve(INSTANCES[label][0])
-
-
-def map_of(label):
-    name, n, fixed, tied = INSTANCES[label]
-    return None if fixed is None and tied is None else ParamMap(n, fixed, tied)
+is_composite = functools.partial(mc.is_composite, INSTANCES)
+model_of = functools.partial(mc.model_of, INSTANCES)
+map_of = functools.partial(mc.map_of, INSTANCES)
 
 
 def kernel_case(label, m, reps, per_problem):

@@ -20,6 +20,8 @@ import bounded_lsq
 from bounded_lsq import GlobalMap, ParamMap, models
 
 import _affine_tie_cases as ac
+import _model_eval as me
+from _model_eval import bits, ctx, same_bits  # noqa: F401  (ctx: the module's fixture)
 
 pytestmark = pytest.mark.gpu
 
@@ -29,56 +31,6 @@ PROPAGATE, OMIT = 0, 1                                   # BLSQ_NAN_*
 FLAGS = [(LSE, PROPAGATE), (LSE, OMIT), (POISSON, PROPAGATE), (POISSON, OMIT)]
 SENTINEL = -77.25
 EPS = np.finfo(float).eps
-
-
-@pytest.fixture(scope="module")
-def ctx():
-    from bounded_lsq import _abi
-    c = _abi.Context(0)
-    yield c
-    c.close()
-
-
-def bits(a):
-    return np.ascontiguousarray(a).view(np.int64)
-
-
-def same_bits(a, b):
-    return a.shape == b.shape and np.array_equal(bits(a), bits(b))
-
-
-class Dev:
-    """Device copies of a test's arrays, freed together."""
-
-    def __init__(self, ctx):
-        self.ctx, self.ptrs = ctx, []
-
-    def up(self, a):
-        if a is None:
-            return None
-        p = self.ctx.to_device(np.ascontiguousarray(a))
-        self.ptrs.append(p)
-        return p
-
-    def close(self):
-        for p in self.ptrs:
-            self.ctx.free(p)
-
-
-def i32(a):
-    from bounded_lsq import _abi
-    if a is None:
-        return None, None
-    a = np.ascontiguousarray(a, dtype=np.int32)
-    return a, a.ctypes.data_as(_abi.c_int32_p)
-
-
-def f64(a):
-    from bounded_lsq import _abi
-    if a is None:
-        return None, None
-    a = np.ascontiguousarray(a, dtype=np.float64)
-    return a, a.ctypes.data_as(_abi.c_double_p)
 
 
 def rows_of(case, sampling):
@@ -106,23 +58,19 @@ def points(case, reps, seed=1):
     return np.ascontiguousarray(X.reshape(-1, X.shape[-1]))
 
 
-def model_args(M):
-    comp = isinstance(M, models.CompositeModel)
-    fam, fam_p = i32(M.fam_ids if comp else None)
-    cnt, cnt_p = i32(M.counts if comp else None)
-    return (fam, cnt), [-1 if comp else M.id, len(M.components) if comp else 0, fam_p, cnt_p]
+ENTRIES = {"tie": "blsq_model_eval_tie_dev", "global": "blsq_model_eval_global_dev", "nan": "blsq_model_eval_nan_dev",
+           "map": "blsq_model_eval_map_dev"}
 
 
 def run_tie(ctx, case, est, policy, reps, X, sampling=POINT, want_f=True, want_J=False, mask=None, fill=np.nan,
             ties="map", entry="tie", **bad):
     """blsq_model_eval_tie_dev on the case -> (rc, f, J).  ties: 'map' (the map's ratio and offset), 'null' (both NULL).
     entry: 'tie', or 'global' / 'nan' / 'map' for the existing entry with the same arguments less the tie pair (and,
-    for 'nan' / 'map', the run of S).  Under POISSON w is NULL; y holds NaN at the omitted points under OMIT only."""
+    for 'nan' / 'map', the run of S).  Under POISSON w is NULL; y holds NaN at the omitted points under OMIT only.
+    `bad` overrides arguments by name (G: the header's name of B)."""
     pm, gm = maps(case)
-    M = models.resolve(case["spec"])
     B, S, m, n = case["B"], case["S"], case["m"], case["n"]
     Se = max(S, 1)
-    y = np.where(case["omitted"], np.nan, case["y"]) if policy == OMIT else case["y"]
     w = None if est == POISSON else case["w"]
     t = rows_of(case, sampling)
     rows = t.shape[-2]
@@ -131,59 +79,26 @@ def run_tie(ctx, case, est, policy, reps, X, sampling=POINT, want_f=True, want_J
     else:
         tg, ts = (rows * m if t.ndim == 4 else 0), 0
     nv = gm.nv if gm is not None else pm.nf
-    Q = B * reps
-    d = Dev(ctx)
-    try:
-        keep, kind = model_args(M)
-        pmv, pm_p = i32(pm.pmap)
-        shv, sh_p = i32(gm.slot_shared if gm is not None else None)
-        rv, r_p = f64(pm.ratio if ties == "map" else None)
-        ov, o_p = f64(pm.offset if ties == "map" else None)
-        a = dict(est=est, sampling=sampling, nan_policy=policy, model=kind[0], ncomp=kind[1], fam=kind[2], cnt=kind[3],
-                 S=S, shared=sh_p, t_sstride=ts, G=B, reps=reps, m=m, n=n, nf=pm.nf, pmap=pm_p, tie_ratio=r_p,
-                 tie_offset=o_p, t=d.up(t), t_stride=tg, y=d.up(y), w=d.up(w),
-                 w_stride=0 if w is None or w.ndim == 1 else Se * m, X=d.up(X), Pfix=d.up(case["P"]),
-                 f=d.up(np.full((Q, Se * m), fill)) if want_f else None,
-                 J=d.up(np.full((B, Se * m, nv), fill)) if want_J else None,
-                 mask=d.up(None if mask is None else np.asarray(mask, dtype=np.int32)))
-        held = []                                          # (the host arrays behind the pointers stay alive)
-        for k, v in bad.items():
-            if isinstance(v, (list, np.ndarray)):
-                held.append(f64(v) if k.startswith("tie_") else i32(v))
-                v = held[-1][1]
-            a[k] = v
-        if entry != "tie":
-            del a["tie_ratio"], a["tie_offset"]
-        if entry in ("nan", "map"):
-            del a["S"], a["shared"], a["t_sstride"]
-        if entry == "map":
-            for k in ("est", "sampling", "nan_policy", "ncomp", "fam", "cnt"):
-                del a[k]
-        name = {"tie": "blsq_model_eval_tie_dev", "global": "blsq_model_eval_global_dev",
-                "nan": "blsq_model_eval_nan_dev", "map": "blsq_model_eval_map_dev"}[entry]
-        rc = getattr(ctx.lib, name)(ctx.h, *a.values())
-        if rc != 0:
-            return rc, None, None
-        return (0, ctx.to_host(a["f"], (Q, Se * m), np.float64) if want_f else None,
-                ctx.to_host(a["J"], (B, Se * m, nv), np.float64) if want_J else None)
-    finally:
-        d.close()
+    a = dict(est=est, sampling=sampling, nan_policy=policy, **me.model_args(models.resolve(case["spec"])), S=S,
+             shared=gm.slot_shared if gm is not None else None, t_sstride=ts, B=B, reps=reps, m=m, n=n, nf=pm.nf,
+             pmap=pm.pmap, tie_ratio=pm.ratio if ties == "map" else None,
+             tie_offset=pm.offset if ties == "map" else None, t=t, t_stride=tg,
+             y=np.where(case["omitted"], np.nan, case["y"]) if policy == OMIT else case["y"], w=w,
+             w_stride=0 if w is None or w.ndim == 1 else Se * m, X=X, Pfix=case["P"], mask=mask)
+    if "G" in bad:
+        bad["B"] = bad.pop("G")
+    a.update(bad)
+    return me.run(ctx, ENTRIES[entry], (B * reps, Se * m), (B, Se * m, nv), want_f, want_J, fill, strict=entry == "tie",
+                  **a)
 
 
 def unmapped(ctx, M, est, sampling, policy, Bt, reps, m, n, t, t_stride, y, w, w_stride, P, want_J):
     """blsq_model_eval_nan_dev without a map on Bt problems -> f (Bt reps, m), J (Bt, m, n) or None."""
-    d = Dev(ctx)
-    try:
-        keep, kind = model_args(M)
-        d_f = d.up(np.full((Bt * reps, m), np.nan))
-        d_J = d.up(np.full((Bt, m, n), np.nan)) if want_J else None
-        rc = ctx.lib.blsq_model_eval_nan_dev(ctx.h, est, sampling, policy, *kind, Bt, reps, m, n, n, None, d.up(t),
-                                             t_stride, d.up(y), d.up(w), w_stride, d.up(P), None, d_f, d_J, None)
-        assert rc == 0, rc
-        return (ctx.to_host(d_f, (Bt * reps, m), np.float64),
-                ctx.to_host(d_J, (Bt, m, n), np.float64) if want_J else None)
-    finally:
-        d.close()
+    rc, f, J = me.run(ctx, "blsq_model_eval_nan_dev", (Bt * reps, m), (Bt, m, n), True, want_J, strict=True, est=est,
+                      sampling=sampling, nan_policy=policy, **me.model_args(M), B=Bt, reps=reps, m=m, n=n, nf=n, pmap=None,
+                      t=t, t_stride=t_stride, y=y, w=w, w_stride=w_stride, X=P, Pfix=None, mask=None)
+    assert rc == 0, rc
+    return f, J
 
 
 def reference(ctx, case, est, policy, reps, X, sampling=POINT, want_J=False):
@@ -515,15 +430,7 @@ def test_device_route_goes_through_the_new_entry_alone(ctx, monkeypatch):
     monkeypatch.setattr(_outer.OuterDriver, "run_host", boom)
     monkeypatch.setattr(_models.CompositeModel, "f", boom)
     monkeypatch.setattr(_models.CompositeModel, "jac", boom)
-    entries = {}
-    lib = ctx.lib
-
-    class Counting:
-        def __getattr__(self, name):
-            if name.startswith("blsq_model_eval"):
-                entries[name] = entries.get(name, 0) + 1
-            return getattr(lib, name)
-    monkeypatch.setattr(ctx, "lib", Counting())
+    entries = me.count_entries(ctx, monkeypatch)
     got = fit(ctx, case, "device")
     assert np.array_equal(got[0], before[0]) and np.array_equal(got[1], before[1])
     assert set(entries) == {"blsq_model_eval_tie_dev"}

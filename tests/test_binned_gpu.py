@@ -10,6 +10,8 @@ import bounded_lsq
 from bounded_lsq import ParamMap, models
 
 import _binned_cases as bc
+import _model_eval as me
+from _model_eval import Dev, agree, ctx  # noqa: F401  (ctx: the module's fixture)
 
 pytestmark = pytest.mark.gpu
 LSE, POISSON = 0, 1                                    # BLSQ_EST_*
@@ -17,74 +19,20 @@ POINT, BIN = 0, 1                                      # BLSQ_SAMPLE_*
 EPS = bc.EPS
 
 
-@pytest.fixture(scope="module")
-def ctx():
-    from bounded_lsq import _abi
-    c = _abi.Context(0)
-    yield c
-    c.close()
-
-
 # ---- kernel level --------------------------------------------------------------------------------------------------
-class Dev:
-    """Device copies of a test's arrays, freed together."""
-
-    def __init__(self, ctx):
-        self.ctx, self.ptrs = ctx, []
-
-    def up(self, a):
-        if a is None:
-            return None
-        p = self.ctx.to_device(np.ascontiguousarray(a))
-        self.ptrs.append(p)
-        return p
-
-    def close(self):
-        for p in self.ptrs:
-            self.ctx.free(p)
-
-
-def i32(a):
-    from bounded_lsq import _abi
-    if a is None:
-        return None, None
-    a = np.ascontiguousarray(a, dtype=np.int32)
-    return a, a.ctypes.data_as(_abi.c_int32_p)
-
-
 def eval_bin(ctx, label, est, sampling, reps, m, x, per_problem, y, w, X, Pfix=None, want_f=True, want_J=False,
              mask=None, fill=None, entry="bin"):
     """blsq_model_eval_bin_dev for the instance `label` on host arrays -> (rc, f or None, J or None); entry='est': the
     same call (without the sampling) through blsq_model_eval_est_dev.  fill: the value f and J hold before."""
     M, pm = bc.model_of(label), bc.map_of(label)
-    comp = bc.is_composite(label)
     n = bc.INSTANCES[label][1]
     nc = n if pm is None else pm.nf
-    B, Q = bc.B, bc.B * reps
-    d = Dev(ctx)
-    try:
-        d_f = d.up(np.full((Q, m), np.nan if fill is None else fill)) if want_f else None
-        d_J = d.up(np.full((Q, m, nc), np.nan if fill is None else fill)) if want_J else None
-        ws = m if (w is not None and np.ndim(w) == 2) else 0
-        ts = (2 if sampling == BIN else 1) * M.coords * m if per_problem else 0
-        fam, fam_p = i32(M.fam_ids if comp else None)
-        cnt, cnt_p = i32(M.counts if comp else None)
-        pmv, pm_p = i32(None if pm is None else pm.pmap)
-        d_t, d_y, d_w, d_X, d_F = d.up(x), d.up(y), d.up(w), d.up(X), d.up(Pfix if pm is not None else None)
-        d_m = d.up(None if mask is None else np.asarray(mask, dtype=np.int32))
-        lib, h = ctx.lib, ctx.h
-        head = (-1 if comp else M.id, len(M.components) if comp else 0, fam_p, cnt_p, B, reps, m, n, nc, pm_p, d_t, ts,
-                d_y, d_w, ws, d_X, d_F, d_f, d_J, d_m)
-        if entry == "bin":
-            rc = lib.blsq_model_eval_bin_dev(h, est, sampling, *head)
-        else:
-            rc = lib.blsq_model_eval_est_dev(h, est, *head)
-        if rc != 0:
-            return rc, None, None
-        return (0, ctx.to_host(d_f, (Q, m), np.float64) if want_f else None,
-                ctx.to_host(d_J, (Q, m, nc), np.float64) if want_J else None)
-    finally:
-        d.close()
+    Q = bc.B * reps
+    return me.run(ctx, "blsq_model_eval_%s_dev" % entry, (Q, m), (Q, m, nc), want_f, want_J,
+                  np.nan if fill is None else fill, est=est, sampling=sampling, **me.model_args(M), B=bc.B, reps=reps,
+                  m=m, n=n, nf=nc, pmap=None if pm is None else pm.pmap, t=x,
+                  t_stride=(2 if sampling == BIN else 1) * M.coords * m if per_problem else 0, y=y, w=w,
+                  w_stride=me.w_stride(w, m), X=X, Pfix=Pfix if pm is not None else None, mask=mask)
 
 
 def test_device_functions_stay_inside_their_allowance(ctx):
@@ -106,18 +54,12 @@ def test_device_functions_stay_inside_their_allowance(ctx):
 
     def run(label_spec, n, x, P):
         M = models.compose(label_spec)
-        d = Dev(ctx)
-        try:
-            fam, fam_p = i32(M.fam_ids)
-            cnt, cnt_p = i32(M.counts)
-            m = x.shape[-1]
-            d_f, d_J = d.up(np.zeros((1, m))), d.up(np.zeros((1, m, n)))
-            rc = ctx.lib.blsq_model_eval_bin_dev(ctx.h, LSE, BIN, -1, 1, fam_p, cnt_p, 1, 1, m, n, n, None, d.up(x), 0,
-                                                 None, None, 0, d.up(P), None, d_f, d_J, None)
-            assert rc == 0
-            return ctx.to_host(d_f, (1, m), np.float64)[0], ctx.to_host(d_J, (1, m, n), np.float64)[0]
-        finally:
-            d.close()
+        m = x.shape[-1]
+        rc, f, J = me.run(ctx, "blsq_model_eval_bin_dev", (1, m), (1, m, n), True, True, 0.0, strict=True, est=LSE,
+                          sampling=BIN, **me.model_args(M), B=1, reps=1, m=m, n=n, nf=n, pmap=None, t=x, t_stride=0,
+                          y=None, w=None, w_stride=0, X=P, Pfix=None, mask=None)
+        assert rc == 0
+        return f[0], J[0]
     # erf: straddling bins; erfc: both edges in one tail (either sign)
     lo = -rng.uniform(0.0, 6.0, G)
     x_mid = np.stack([lo, rng.uniform(0.0, 6.0, G)])
@@ -250,17 +192,13 @@ def test_argument_errors_name_the_argument(ctx):
     try:
         buf, bufP = d.up(np.arange(64.0)), d.up(np.ones(64))
         out, outJ = d.up(np.full(64, -7.0)), d.up(np.full(64, -7.0))
-        keep = []
 
         def call(est=POISSON, sampling=BIN, model=2, fam=None, cnt=None, ncomp=None, B=1, reps=1, m=4, n=4, nf=4,
                  pmap=None, t=buf, ts=0, y=bufP, w=None, ws=0, X=bufP, Pfix=None, f=out, J=None):
-            fa, fp = i32(fam)
-            ca, cp = i32(cnt)
-            pa, pp = i32(pmap)
-            keep.append((fa, ca, pa))
             nc = ncomp if ncomp is not None else (0 if fam is None else len(fam))
-            return lib.blsq_model_eval_bin_dev(h, est, sampling, model, nc, fp, cp, B, reps, m, n, nf, pp, t, ts, y, w, ws,
-                                               X, Pfix, f, J, None)
+            return me.call(ctx, "blsq_model_eval_bin_dev", True, est=est, sampling=sampling, model=model, ncomp=nc,
+                           fam=fam, cnt=cnt, B=B, reps=reps, m=m, n=n, nf=nf, pmap=pmap, t=t, t_stride=ts, y=y, w=w,
+                           w_stride=ws, X=X, Pfix=Pfix, f=f, J=J, mask=None)
         comp = dict(model=-1, fam=(0, 4), cnt=(1, 1))
         bad = [(dict(est=2), -2), (dict(sampling=2), -3), (dict(sampling=-1), -3), (dict(model=5), -4),
                (dict(model=-2), -4), (dict(ncomp=1), -5), (dict(model=-1), -5),
@@ -309,19 +247,6 @@ def test_evaluate_binned_equals_the_definition(ctx, label):
 
 
 # ---- end to end ----------------------------------------------------------------------------------------------------
-def normalised(pcov, free):
-    C = pcov[:, free][:, :, free]
-    d = np.sqrt(np.einsum("bii->bi", C))
-    return C / (d[:, :, None] * d[:, None, :])
-
-
-def agree(a, b, what, rtol_p=1e-6, atol_p=1e-9):
-    """``agree`` of tests/test_poisson_gpu.py (popt rtol 1e-6, normalised pcov atol 1e-6), over the free parameters."""
-    free = np.flatnonzero(np.all(np.einsum("bii->bi", a[1]) > 0, axis=0))
-    np.testing.assert_allclose(b[0], a[0], rtol=rtol_p, atol=atol_p, err_msg=str(what))
-    np.testing.assert_allclose(normalised(b[1], free), normalised(a[1], free), rtol=0, atol=1e-6, err_msg=str(what))
-
-
 def fit(ctx, f, x, pr, driver, **kw):
     common = dict(bounds=pr["bounds"], ctx=ctx, binned=True, **bc.TOL)
     common.update(kw)
@@ -451,15 +376,7 @@ def test_device_route_goes_through_the_new_entry_alone(ctx, histogram, device_fi
         monkeypatch.setattr(cls, "f", boom)
         monkeypatch.setattr(cls, "jac", boom)
     monkeypatch.setattr(_models, "poisson_transform", boom)
-    entries = {}
-    lib = ctx.lib
-
-    class Counting:
-        def __getattr__(self, name):
-            if name.startswith("blsq_model_eval"):
-                entries[name] = entries.get(name, 0) + 1
-            return getattr(lib, name)
-    monkeypatch.setattr(ctx, "lib", Counting())
+    entries = me.count_entries(ctx, monkeypatch)
     pr = histogram
     got = fit(ctx, pr["spec"], pr["edges"], pr, "device", estimator="poisson", absolute_sigma=True)
     assert np.array_equal(got[0], device_fit[0]) and np.array_equal(got[1], device_fit[1])

@@ -11,85 +11,33 @@ from bounded_lsq import ParamMap, models
 
 import _composite_cases as cc
 import _model_cases as mc
+import _model_eval as me
+from _model_eval import Dev, agree, ctx  # noqa: F401  (ctx: the module's fixture)
 
 pytestmark = pytest.mark.gpu
 LD = np.longdouble
 
 
-@pytest.fixture(scope="module")
-def ctx():
-    from bounded_lsq import _abi
-    c = _abi.Context(0)
-    yield c
-    c.close()
-
-
 # ---- kernel level --------------------------------------------------------------------------------------------------
-class Dev:
-    """Device copies of a test's arrays, freed together."""
-
-    def __init__(self, ctx):
-        self.ctx, self.ptrs = ctx, []
-
-    def up(self, a):
-        if a is None:
-            return None
-        p = self.ctx.to_device(np.ascontiguousarray(a))
-        self.ptrs.append(p)
-        return p
-
-    def close(self):
-        for p in self.ptrs:
-            self.ctx.free(p)
-
-
-def i32(a):
-    from bounded_lsq import _abi
-    a = np.ascontiguousarray(a, dtype=np.int32)
-    return a, a.ctypes.data_as(_abi.c_int32_p)
-
-
 def eval_comp(ctx, spec, B, reps, m, x, per_problem, y, w, X, want_f=True, want_J=False, mask=None, fill=None,
               pmap=None, nf=None, Pfix=None):
     """blsq_model_eval_comp_dev on host arrays -> (rc, f or None, J or None).  fill: the value f and J hold before.
     pmap: None (unmapped: X is P) or the int map [n] with nf and Pfix."""
     M = models.compose(spec)
-    d = Dev(ctx)
-    try:
-        Q = B * reps
-        nc = M.n if pmap is None else nf
-        f0 = np.full((Q, m), np.nan if fill is None else fill)
-        J0 = np.full((Q, m, nc), np.nan if fill is None else fill)
-        d_f = d.up(f0) if want_f else None
-        d_J = d.up(J0) if want_J else None
-        w_stride = m if (w is not None and np.ndim(w) == 2) else 0
-        fam, fam_p = i32(M.fam_ids)
-        cnt, cnt_p = i32(M.counts)
-        pm, pm_p = (None, None) if pmap is None else i32(pmap)
-        rc = ctx.lib.blsq_model_eval_comp_dev(
-            ctx.h, len(M.components), fam_p, cnt_p, B, reps, m, M.n, nc, pm_p, d.up(x), m if per_problem else 0, d.up(y),
-            d.up(w), w_stride, d.up(X), d.up(Pfix), d_f, d_J,
-            d.up(None if mask is None else np.asarray(mask, dtype=np.int32)))
-        if rc != 0:
-            return rc, None, None
-        return (0, ctx.to_host(d_f, (Q, m), np.float64) if want_f else None,
-                ctx.to_host(d_J, (Q, m, nc), np.float64) if want_J else None)
-    finally:
-        d.close()
+    Q = B * reps
+    nc = M.n if pmap is None else nf
+    return me.run(ctx, "blsq_model_eval_comp_dev", (Q, m), (Q, m, nc), want_f, want_J, np.nan if fill is None else fill,
+                  strict=True, **me.model_args(M), B=B, reps=reps, m=m, n=M.n, nf=nc, pmap=pmap, t=x,
+                  t_stride=m if per_problem else 0, y=y, w=w, w_stride=me.w_stride(w, m), X=X, Pfix=Pfix, mask=mask)
 
 
 def eval_named(ctx, name, B, m, n, x, per_problem, P):
     """f and J of blsq_model_eval_dev (y = w = NULL)."""
-    M = models.get(name)
-    d = Dev(ctx)
-    try:
-        d_f, d_J = d.up(np.full((B, m), np.nan)), d.up(np.full((B, m, n), np.nan))
-        rc = ctx.lib.blsq_model_eval_dev(ctx.h, M.id, B, 1, m, n, d.up(x), m if per_problem else 0, None, None, 0,
-                                         d.up(P), d_f, d_J, None)
-        assert rc == 0
-        return ctx.to_host(d_f, (B, m), np.float64), ctx.to_host(d_J, (B, m, n), np.float64)
-    finally:
-        d.close()
+    rc, f, J = me.run(ctx, "blsq_model_eval_dev", (B, m), (B, m, n), True, True, strict=True, model=models.get(name).id,
+                      B=B, reps=1, m=m, n=n, t=x, t_stride=m if per_problem else 0, y=None, w=None, w_stride=0, X=P,
+                      mask=None)
+    assert rc == 0
+    return f, J
 
 
 @pytest.mark.parametrize("m", cc.ROWS)
@@ -259,17 +207,12 @@ def test_argument_errors_name_the_argument(ctx):
     try:
         buf, bufP = d.up(np.zeros(64)), d.up(np.ones(64))
         out, outJ = d.up(np.full(64, -7.0)), d.up(np.full(64, -7.0))
-        keep = []
 
         def call(fam=(0, 4), cnt=(1, 1), ncomp=None, B=1, reps=1, m=4, n=4, nf=4, pmap=None, t=buf, ts=0, y=None,
                  w=None, ws=0, X=bufP, Pfix=None, f=out, J=None):
-            fa, fp = (None, None) if fam is None else i32(fam)
-            ca, cp = (None, None) if cnt is None else i32(cnt)
-            pa, pp = (None, None) if pmap is None else i32(pmap)
-            keep.append((fa, ca, pa))
             nc = ncomp if ncomp is not None else len(fam)
-            return lib.blsq_model_eval_comp_dev(h, nc, fp, cp, B, reps, m, n, nf, pp, t, ts, y, w, ws, X, Pfix, f, J,
-                                                None)
+            return me.call(ctx, "blsq_model_eval_comp_dev", True, ncomp=nc, fam=fam, cnt=cnt, B=B, reps=reps, m=m, n=n,
+                           nf=nf, pmap=pmap, t=t, t_stride=ts, y=y, w=w, w_stride=ws, X=X, Pfix=Pfix, f=f, J=J, mask=None)
         bad = [(dict(ncomp=0), -2), (dict(ncomp=9, fam=(4,) * 9, cnt=(1,) * 9, n=9, nf=9), -2),
                (dict(fam=None, ncomp=2), -3), (dict(fam=(0, 5)), -3), (dict(fam=(-1, 4)), -3),
                (dict(cnt=None), -4), (dict(cnt=(0, 1)), -4), (dict(cnt=(1, -2)), -4),
@@ -323,18 +266,6 @@ def fit(ctx, pr, route, method, **kw):
             return bounded_lsq.curve_fit_batch(M.f, pr["x"], pr["Y"], pr["P0"], jac=M.jac, driver="device", **common)
         return bounded_lsq.curve_fit_batch(pr["spec"], pr["x"], pr["Y"], pr["P0"],
                                            driver="device" if route == "B" else "host", **common)
-
-
-def normalised(pcov, free):
-    C = pcov[:, free][:, :, free]
-    d = np.sqrt(np.einsum("bii->bi", C))
-    return C / (d[:, :, None] * d[:, None, :])
-
-
-def agree(a, b, what, rtol_p=1e-6, atol_p=1e-9):
-    free = np.flatnonzero(np.all(np.einsum("bii->bi", a[1]) > 0, axis=0))
-    np.testing.assert_allclose(b[0], a[0], rtol=rtol_p, atol=atol_p, err_msg=str(what))
-    np.testing.assert_allclose(normalised(b[1], free), normalised(a[1], free), rtol=0, atol=1e-6, err_msg=str(what))
 
 
 @pytest.fixture(scope="module")
@@ -445,22 +376,10 @@ def test_spec_device_route_calls_no_host_callback(ctx, monkeypatch):
     real = _outer.OuterDriver.run_device
     monkeypatch.setattr(_outer.OuterDriver, "run_device",
                         lambda self, *a, **k: (calls.append(1), real(self, *a, **k))[1])
-    entries = {"comp": 0, "named": 0}
-    lib = ctx.lib
-
-    class Counting:
-        def __init__(self, lib):
-            self._lib = lib
-
-        def __getattr__(self, name):
-            fn = getattr(self._lib, name)
-            if name == "blsq_model_eval_comp_dev":
-                entries["comp"] += 1
-            elif name in ("blsq_model_eval_dev", "blsq_model_eval_map_dev"):
-                entries["named"] += 1
-            return fn
-    monkeypatch.setattr(ctx, "lib", Counting(lib))
+    counts = me.count_entries(ctx, monkeypatch)
     got = fit(ctx, pr, "B", "trf")
+    entries = {"comp": counts.get("blsq_model_eval_comp_dev", 0),
+               "named": counts.get("blsq_model_eval_dev", 0) + counts.get("blsq_model_eval_map_dev", 0)}
     assert calls == [1] and np.array_equal(got[0], want[0]) and np.array_equal(got[1], want[1])
     assert entries["comp"] > 0 and entries["named"] == 0
     got_fd = fit(ctx, pr, "B", "trf", jac="2-point")

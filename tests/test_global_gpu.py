@@ -10,6 +10,8 @@ import bounded_lsq
 from bounded_lsq import GlobalMap, models
 
 import _global_cases as gc
+import _model_eval as me
+from _model_eval import bits, ctx, same_bits  # noqa: F401  (ctx: the module's fixture)
 
 pytestmark = pytest.mark.gpu
 
@@ -17,48 +19,6 @@ LSE, POISSON = 0, 1                                      # BLSQ_EST_*
 PROPAGATE, OMIT = 0, 1                                   # BLSQ_NAN_*
 FLAGS = [(LSE, PROPAGATE), (LSE, OMIT), (POISSON, PROPAGATE), (POISSON, OMIT)]
 SENTINEL = -77.25
-
-
-@pytest.fixture(scope="module")
-def ctx():
-    from bounded_lsq import _abi
-    c = _abi.Context(0)
-    yield c
-    c.close()
-
-
-def bits(a):
-    return np.ascontiguousarray(a).view(np.int64)
-
-
-def same_bits(a, b):
-    return a.shape == b.shape and np.array_equal(bits(a), bits(b))
-
-
-class Dev:
-    """Device copies of a test's arrays, freed together."""
-
-    def __init__(self, ctx):
-        self.ctx, self.ptrs = ctx, []
-
-    def up(self, a):
-        if a is None:
-            return None
-        p = self.ctx.to_device(np.ascontiguousarray(a))
-        self.ptrs.append(p)
-        return p
-
-    def close(self):
-        for p in self.ptrs:
-            self.ctx.free(p)
-
-
-def i32(a):
-    from bounded_lsq import _abi
-    if a is None:
-        return None, None
-    a = np.ascontiguousarray(a, dtype=np.int32)
-    return a, a.ctypes.data_as(_abi.c_int32_p)
 
 
 def setup(case):
@@ -74,78 +34,41 @@ def setup(case):
 def run_global(ctx, case, est, policy, reps, X, want_f=True, want_J=False, mask=None, fill=np.nan, **bad):
     """blsq_model_eval_global_dev on the case -> (rc, f (G reps, S m) or None, J (G, S m, nv) or None).  Under POISSON w is
     NULL; under OMIT y holds NaN at the case's omitted points (under PROPAGATE as well: they pass through).  `bad`
-    overrides arguments by name."""
+    overrides arguments by name (G: the header's name of B)."""
     gm, M, G, S, m, t, (tg, ts) = setup(case)
-    comp = isinstance(M, models.CompositeModel)
-    y = np.where(case["omitted"], np.nan, case["y"])
     w = None if est == POISSON else case["w"]
-    Q = G * reps
-    d = Dev(ctx)
-    try:
-        fam, fam_p = i32(M.fam_ids if comp else None)
-        cnt, cnt_p = i32(M.counts if comp else None)
-        pmv, pm_p = i32(gm.pm.pmap)
-        shv, sh_p = i32(gm.slot_shared)
-        a = dict(est=est, sampling=0, nan_policy=policy, model=-1 if comp else M.id,
-                 ncomp=len(M.components) if comp else 0, fam=fam_p, cnt=cnt_p, S=S, shared=sh_p, t_sstride=ts, G=G,
-                 reps=reps, m=m, n=case["n"], nf=gm.nf, pmap=pm_p, t=d.up(t), t_stride=tg, y=d.up(y), w=d.up(w),
-                 w_stride=0 if w is None or w.ndim == 1 else S * m, X=d.up(X), Pfix=d.up(case["P"]),
-                 f=d.up(np.full((Q, S * m), fill)) if want_f else None,
-                 J=d.up(np.full((G, S * m, gm.nv), fill)) if want_J else None,
-                 mask=d.up(None if mask is None else np.asarray(mask, dtype=np.int32)))
-        keep = []                                           # (the host arrays behind the pointers stay alive)
-        for k, v in bad.items():
-            if isinstance(v, (list, np.ndarray)):
-                keep.append(i32(v))
-                v = keep[-1][1]
-            a[k] = v
-        rc = ctx.lib.blsq_model_eval_global_dev(ctx.h, *a.values())
-        if rc != 0:
-            return rc, None, None
-        return (0, ctx.to_host(a["f"], (Q, S * m), np.float64) if want_f else None,
-                ctx.to_host(a["J"], (G, S * m, gm.nv), np.float64) if want_J else None)
-    finally:
-        d.close()
+    a = dict(est=est, sampling=0, nan_policy=policy, **me.model_args(M), S=S, shared=gm.slot_shared, t_sstride=ts, B=G,
+             reps=reps, m=m, n=case["n"], nf=gm.nf, pmap=gm.pm.pmap, t=t, t_stride=tg,
+             y=np.where(case["omitted"], np.nan, case["y"]), w=w, w_stride=0 if w is None or w.ndim == 1 else S * m, X=X,
+             Pfix=case["P"], mask=mask)
+    if "G" in bad:
+        bad["B"] = bad.pop("G")
+    a.update(bad)
+    return me.run(ctx, "blsq_model_eval_global_dev", (G * reps, S * m), (G, S * m, gm.nv), want_f, want_J, fill,
+                  strict=True, **a)
 
 
 def run_sets(ctx, case, est, policy, reps, X, want_f=True, want_J=False, entry="nan"):
     """The reference: the G S data sets as G S problems of the existing entry (blsq_model_eval_nan_dev; entry='map':
     blsq_model_eval_map_dev) at expand_x(X), brought into the group's shape by reshape / ``GlobalMap.reduce_jac``."""
     gm, M, G, S, m, t, (tg, ts) = setup(case)
-    comp = isinstance(M, models.CompositeModel)
     B, nf = G * S, gm.nf
-    y = np.where(case["omitted"], np.nan, case["y"]).reshape(B, m)
     w = None if est == POISSON else case["w"]
     if w is not None and w.ndim == 2:
         w = w.reshape(B, m)
-    tb = t if t.ndim == 1 else np.broadcast_to(t, (G, S, m)).reshape(B, m)
     # the points of problem (g, s): its own nf variables of every rep
     Xs = gm.split_x(X.reshape(G, reps, gm.nv)).transpose(0, 2, 1, 3).reshape(B * reps, nf)
-    d = Dev(ctx)
-    try:
-        fam, fam_p = i32(M.fam_ids if comp else None)
-        cnt, cnt_p = i32(M.counts if comp else None)
-        pmv, pm_p = i32(gm.pm.pmap)
-        d_f = d.up(np.full((B * reps, m), np.nan)) if want_f else None
-        d_J = d.up(np.full((B, m, nf), np.nan)) if want_J else None
-        tail = (B, reps, m, case["n"], nf, pm_p, d.up(tb), 0 if t.ndim == 1 else m, d.up(y), d.up(w),
-                0 if w is None or w.ndim == 1 else m, d.up(Xs), d.up(case["P"].reshape(B, -1)), d_f, d_J, None)
-        if entry == "map":
-            rc = ctx.lib.blsq_model_eval_map_dev(ctx.h, M.id, *tail)
-        else:
-            rc = ctx.lib.blsq_model_eval_nan_dev(ctx.h, est, 0, policy, -1 if comp else M.id,
-                                                 len(M.components) if comp else 0, fam_p, cnt_p, *tail)
-        assert rc == 0, rc
-        f = J = None
-        if want_f:
-            f = ctx.to_host(d_f, (B * reps, m), np.float64).reshape(G, S, reps, m).transpose(0, 2, 1, 3)
-            f = np.ascontiguousarray(f).reshape(G * reps, S * m)
-        if want_J:                                          # a pure scatter: the identity map over the nf slots
-            scatter = GlobalMap(nf, S, np.flatnonzero(gm.slot_shared))
-            J = scatter.reduce_jac(ctx.to_host(d_J, (B, m, nf), np.float64).reshape(G, S, m, nf))
-        return f, J
-    finally:
-        d.close()
+    rc, f, J = me.run(ctx, "blsq_model_eval_%s_dev" % entry, (B * reps, m), (B, m, nf), want_f, want_J, est=est,
+                      sampling=0, nan_policy=policy, **me.model_args(M), B=B, reps=reps, m=m, n=case["n"], nf=nf,
+                      pmap=gm.pm.pmap, t=t if t.ndim == 1 else np.broadcast_to(t, (G, S, m)).reshape(B, m),
+                      t_stride=0 if t.ndim == 1 else m, y=np.where(case["omitted"], np.nan, case["y"]).reshape(B, m), w=w,
+                      w_stride=0 if w is None or w.ndim == 1 else m, X=Xs, Pfix=case["P"].reshape(B, -1), mask=None)
+    assert rc == 0, rc
+    if want_f:
+        f = np.ascontiguousarray(f.reshape(G, S, reps, m).transpose(0, 2, 1, 3)).reshape(G * reps, S * m)
+    if want_J:                                              # a pure scatter: the identity map over the nf slots
+        J = GlobalMap(nf, S, np.flatnonzero(gm.slot_shared)).reduce_jac(J.reshape(G, S, m, nf))
+    return f, J
 
 
 def points(case, reps, seed=1):
@@ -363,15 +286,7 @@ def test_device_route_goes_through_the_new_entry_alone(ctx, monkeypatch):
     monkeypatch.setattr(_outer.OuterDriver, "run_host", boom)
     monkeypatch.setattr(_models.CompositeModel, "f", boom)
     monkeypatch.setattr(_models.CompositeModel, "jac", boom)
-    entries = {}
-    lib = ctx.lib
-
-    class Counting:
-        def __getattr__(self, name):
-            if name.startswith("blsq_model_eval"):
-                entries[name] = entries.get(name, 0) + 1
-            return getattr(lib, name)
-    monkeypatch.setattr(ctx, "lib", Counting())
+    entries = me.count_entries(ctx, monkeypatch)
     got = fit(ctx, case, "device")
     assert np.array_equal(got[0], before[0]) and np.array_equal(got[1], before[1])
     assert set(entries) == {"blsq_model_eval_global_dev"}

@@ -12,6 +12,8 @@ from bounded_lsq import TrfStepSolver, DogboxStepSolver, _abi, _synth
 from bounded_lsq._abi import ptr, vp
 from bounded_lsq._outer import OuterDriver
 
+from _model_eval import same_bits
+
 pytestmark = pytest.mark.gpu
 CYCLES = 3
 
@@ -21,11 +23,6 @@ def ctx():
     c = _abi.Context(0)
     yield c
     c.close()
-
-
-def same_bits(a, b):
-    a, b = np.ascontiguousarray(a), np.ascontiguousarray(b)
-    return a.shape == b.shape and a.dtype == b.dtype and a.tobytes() == b.tobytes()
 
 
 def cycles(one):

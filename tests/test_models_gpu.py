@@ -9,58 +9,21 @@ import bounded_lsq
 from bounded_lsq import models
 
 import _model_cases as mc
+import _model_eval as me
+from _model_eval import Dev, ctx  # noqa: F401  (ctx: the module's fixture)
 
 pytestmark = pytest.mark.gpu
 LD = np.longdouble
 
 
-@pytest.fixture(scope="module")
-def ctx():
-    from bounded_lsq import _abi
-    c = _abi.Context(0)
-    yield c
-    c.close()
-
-
 # ---- kernel level --------------------------------------------------------------------------------------------------
-class Dev:
-    """Device copies of a test's arrays, freed together."""
-
-    def __init__(self, ctx):
-        self.ctx, self.ptrs = ctx, []
-
-    def up(self, a):
-        if a is None:
-            return None
-        p = self.ctx.to_device(np.ascontiguousarray(a))
-        self.ptrs.append(p)
-        return p
-
-    def close(self):
-        for p in self.ptrs:
-            self.ctx.free(p)
-
-
 def eval_dev(ctx, name, B, reps, m, n, x, per_problem, y, w, P, want_f=True, want_J=False, mask=None, fill=None):
     """blsq_model_eval_dev on host arrays -> (rc, f or None, J or None).  fill: the value f and J hold before."""
     M = models.get(name)
-    d = Dev(ctx)
-    try:
-        Q = B * reps
-        f0 = np.full((Q, m), np.nan if fill is None else fill)
-        J0 = np.full((Q, m, n), np.nan if fill is None else fill)
-        d_f = d.up(f0) if want_f else None
-        d_J = d.up(J0) if want_J else None
-        w_stride = m if (w is not None and np.ndim(w) == 2) else 0
-        rc = ctx.lib.blsq_model_eval_dev(
-            ctx.h, M.id, B, reps, m, n, d.up(x), M.coords * m if per_problem else 0, d.up(y), d.up(w), w_stride,
-            d.up(P), d_f, d_J, d.up(None if mask is None else np.asarray(mask, dtype=np.int32)))
-        if rc != 0:
-            return rc, None, None
-        return (0, ctx.to_host(d_f, (Q, m), np.float64) if want_f else None,
-                ctx.to_host(d_J, (Q, m, n), np.float64) if want_J else None)
-    finally:
-        d.close()
+    Q = B * reps
+    return me.run(ctx, "blsq_model_eval_dev", (Q, m), (Q, m, n), want_f, want_J, np.nan if fill is None else fill,
+                  strict=True, model=M.id, B=B, reps=reps, m=m, n=n, t=x, t_stride=M.coords * m if per_problem else 0,
+                  y=y, w=w, w_stride=me.w_stride(w, m), X=P, mask=mask)
 
 
 # name, n: poly n = 1, 7, 64; exp_sum K = 1, 3; gauss_sum K = 1, 5, 21 (n = 64); lorentz_sum K = 2; gauss2d
@@ -170,7 +133,8 @@ def test_argument_errors_name_the_argument(ctx):
         buf, bufP, out = d.up(np.zeros(64)), d.up(np.ones(64)), d.up(np.zeros(64))
 
         def call(model=2, B=1, reps=1, m=4, n=4, t=buf, ts=0, y=None, w=None, ws=0, P=bufP, f=out, J=None):
-            return lib.blsq_model_eval_dev(h, model, B, reps, m, n, t, ts, y, w, ws, P, f, J, None)
+            return me.call(ctx, "blsq_model_eval_dev", True, model=model, B=B, reps=reps, m=m, n=n, t=t, t_stride=ts,
+                           y=y, w=w, w_stride=ws, X=P, f=f, J=J, mask=None)
         assert call() == 0
         ctx.sync()
         assert call(model=5) == -2 and call(model=-1) == -2

@@ -14,6 +14,8 @@ import bounded_lsq
 from bounded_lsq import models
 
 import _nan_cases as nc
+import _model_eval as me
+from _model_eval import Dev, bits, ctx  # noqa: F401  (ctx: the module's fixture)
 
 pytestmark = pytest.mark.gpu
 LSE, POISSON = 0, 1                                    # BLSQ_EST_*
@@ -21,73 +23,21 @@ POINT, BIN = 0, 1                                      # BLSQ_SAMPLE_*
 PROPAGATE, OMIT = 0, 1                                 # BLSQ_NAN_*
 
 
-@pytest.fixture(scope="module")
-def ctx():
-    from bounded_lsq import _abi
-    c = _abi.Context(0)
-    yield c
-    c.close()
-
-
 # ---- kernel level --------------------------------------------------------------------------------------------------
-class Dev:
-    """Device copies of a test's arrays, freed together."""
-
-    def __init__(self, ctx):
-        self.ctx, self.ptrs = ctx, []
-
-    def up(self, a):
-        if a is None:
-            return None
-        p = self.ctx.to_device(np.ascontiguousarray(a))
-        self.ptrs.append(p)
-        return p
-
-    def close(self):
-        for p in self.ptrs:
-            self.ctx.free(p)
-
-
-def i32(a):
-    from bounded_lsq import _abi
-    if a is None:
-        return None, None
-    a = np.ascontiguousarray(a, dtype=np.int32)
-    return a, a.ctypes.data_as(_abi.c_int32_p)
-
-
-def bits(a):
-    return np.ascontiguousarray(a).view(np.uint64)
-
-
 def evaluate(ctx, label, est, sampling, policy, B, reps, m, t, ts, y, w, X, Pfix, want_J, mask=None):
     """One launch on host arrays, f and J pre-filled with the sentinel -> (rc, f [B reps][m], J [B][m][nc] or None).
     policy None: blsq_model_eval_bin_dev (the entry of the parent); otherwise blsq_model_eval_nan_dev."""
     M, pm = nc.model_of(label), nc.map_of(label)
-    comp = isinstance(M, models.CompositeModel)
     n = nc.INSTANCES[label][1]
     ncol = n if pm is None else pm.nf
     Q = B * reps
-    d = Dev(ctx)
-    try:
-        d_f = d.up(np.full((Q, m), nc.SENTINEL))
-        d_J = d.up(np.full((Q, m, ncol), nc.SENTINEL)) if want_J else None
-        ws = m if (w is not None and np.ndim(w) == 2) else 0
-        fam, fam_p = i32(M.fam_ids if comp else None)
-        cnt, cnt_p = i32(M.counts if comp else None)
-        pmv, pm_p = i32(None if pm is None else pm.pmap)
-        head = (-1 if comp else M.id, len(M.components) if comp else 0, fam_p, cnt_p, B, reps, m, n, ncol, pm_p, d.up(t),
-                ts, d.up(y), d.up(w), ws, d.up(X), d.up(Pfix), d_f, d_J,
-                d.up(None if mask is None else np.asarray(mask, dtype=np.int32)))
-        if policy is None:
-            rc = ctx.lib.blsq_model_eval_bin_dev(ctx.h, est, sampling, *head)
-        else:
-            rc = ctx.lib.blsq_model_eval_nan_dev(ctx.h, est, sampling, policy, *head)
-        if rc != 0:
-            return rc, None, None
-        return (0, ctx.to_host(d_f, (Q, m), np.float64), ctx.to_host(d_J, (Q, m, ncol), np.float64) if want_J else None)
-    finally:
-        d.close()
+    name, flags = "blsq_model_eval_nan_dev", dict(est=est, sampling=sampling, nan_policy=policy)
+    if policy is None:
+        name = "blsq_model_eval_bin_dev"
+        del flags["nan_policy"]
+    return me.run(ctx, name, (Q, m), (Q, m, ncol), True, want_J, nc.SENTINEL, strict=True, **flags, **me.model_args(M),
+                  B=B, reps=reps, m=m, n=n, nf=ncol, pmap=None if pm is None else pm.pmap, t=t, t_stride=ts, y=y, w=w,
+                  w_stride=me.w_stride(w, m), X=X, Pfix=Pfix, mask=mask)
 
 
 def poisoned(case, om, w_kind, per_problem, sampling):
@@ -196,16 +146,12 @@ def test_argument_errors_name_the_argument(ctx):
     try:
         buf, bufP = d.up(np.ones(64)), d.up(np.ones(64))
         out, outJ = d.up(np.full(64, -7.0)), d.up(np.full(64, -7.0))
-        keep = []
 
         def call(est=LSE, sampling=POINT, policy=OMIT, model=2, ncomp=0, fam=None, cnt=None, B=1, reps=1, m=4, n=4, nf=4,
                  pmap=None, t=buf, ts=0, y=buf, w=None, ws=0, X=bufP, Pfix=None, f=out, J=None):
-            fa, fp = i32(fam)
-            ca, cp = i32(cnt)
-            pa, pp = i32(pmap)
-            keep.append((fa, ca, pa))
-            return lib.blsq_model_eval_nan_dev(h, est, sampling, policy, model, ncomp, fp, cp, B, reps, m, n, nf, pp, t, ts,
-                                               y, w, ws, X, Pfix, f, J, None)
+            return me.call(ctx, "blsq_model_eval_nan_dev", True, est=est, sampling=sampling, nan_policy=policy,
+                           model=model, ncomp=ncomp, fam=fam, cnt=cnt, B=B, reps=reps, m=m, n=n, nf=nf, pmap=pmap, t=t,
+                           t_stride=ts, y=y, w=w, w_stride=ws, X=X, Pfix=Pfix, f=f, J=J, mask=None)
         bad = [(dict(est=2), -2, b"est"), (dict(sampling=2), -3, b"sampling"),
                (dict(policy=2), -4, b"nan_policy"), (dict(policy=-1), -4, b"nan_policy"),
                (dict(model=5), -5, b"model"), (dict(model=-2), -5, b"model"), (dict(ncomp=1), -6, b"ncomp"),
@@ -498,24 +444,17 @@ def test_device_route_calls_the_new_entry_alone(ctx, monkeypatch):
     monkeypatch.setattr(_models, "omit_jacobian", boom)
     for T in _models.TERMS.values():
         monkeypatch.setattr(T, "fill", boom)
-    entries = {"nan": 0, "other": 0}
-    lib = ctx.lib
+    counts = me.count_entries(ctx, monkeypatch)
 
-    class Counting:
-        def __init__(self, lib):
-            self._lib = lib
-
-        def __getattr__(self, name):
-            if name == "blsq_model_eval_nan_dev":
-                entries["nan"] += 1
-            elif name.startswith("blsq_model_eval"):
-                entries["other"] += 1
-            return getattr(self._lib, name)
-    monkeypatch.setattr(ctx, "lib", Counting(lib))
+    def tally():
+        return {"nan": counts.get("blsq_model_eval_nan_dev", 0),
+                "other": sum(v for k, v in counts.items() if k != "blsq_model_eval_nan_dev")}
     got = batch_fit(*args, "device", "trf", **kw)
+    entries = tally()
     assert np.array_equal(got[0], want[0]) and np.array_equal(got[1], want[1])
     assert entries["nan"] > 0 and entries["other"] == 0
     fd = batch_fit(*args, "device", "trf", jac="2-point", **kw)
+    entries = tally()
     assert all(r.success for r in fd[2]) and entries["other"] == 0
     with pytest.raises(AssertionError, match="host callback"):
         batch_fit(*args, "host", "trf", **kw)

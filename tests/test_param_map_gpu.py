@@ -1,7 +1,6 @@
 """Fixed and tied parameters on the GPU: the mapped kernel instances (blsq_model_eval_map_dev) bit for bit against the
 existing entry, and ``curve_fit_batch(f='name', fixed=, tied=)`` end to end against the reduced model written out by hand
 — as numpy callables on the device driver (the route a user has without the keywords) and through scipy."""
-import ctypes as C
 import warnings
 
 import numpy as np
@@ -14,70 +13,30 @@ from bounded_lsq._params import ParamMap
 
 import _model_cases as mc
 import _param_map_cases as pc
+import _model_eval as me
+from _model_eval import Dev, ctx  # noqa: F401  (ctx: the module's fixture)
 
 pytestmark = pytest.mark.gpu
 
 
-@pytest.fixture(scope="module")
-def ctx():
-    from bounded_lsq import _abi
-    c = _abi.Context(0)
-    yield c
-    c.close()
-
-
 # ---- kernel level --------------------------------------------------------------------------------------------------
-class Dev:
-    """Device copies of a test's arrays, freed together."""
-
-    def __init__(self, ctx):
-        self.ctx, self.ptrs = ctx, []
-
-    def up(self, a):
-        if a is None:
-            return None
-        p = self.ctx.to_device(np.ascontiguousarray(a))
-        self.ptrs.append(p)
-        return p
-
-    def close(self):
-        for p in self.ptrs:
-            self.ctx.free(p)
-
-
-def _i32(a):
-    return None if a is None else np.ascontiguousarray(a, dtype=np.int32).ctypes.data_as(C.POINTER(C.c_int32))
-
-
 def eval_both(ctx, name, B, reps, m, n, x, per_problem, y, w, P_full, maps, want_J, mask=None, fill=np.nan):
     """blsq_model_eval_dev at P_full, and blsq_model_eval_map_dev for every (pmap, nf, X, Pfix) of `maps`, on one set of
     device copies of the data -> (f_full, J_full), [(f_map, J_map), ...]."""
     M = models.get(name)
-    d = Dev(ctx)
-    try:
-        Q = B * reps
-        d_t, d_y, d_w = d.up(x), d.up(y), d.up(w)
-        d_mask = d.up(None if mask is None else np.asarray(mask, dtype=np.int32))
-        ts = M.coords * m if per_problem else 0
-        ws = m if (w is not None and np.ndim(w) == 2) else 0
+    Q = B * reps
+    with Dev(ctx) as d:
+        data = dict(model=M.id, B=B, reps=reps, m=m, n=n, t=d.up(x), t_stride=M.coords * m if per_problem else 0,
+                    y=d.up(y), w=d.up(w), w_stride=me.w_stride(w, m),
+                    mask=d.up(None if mask is None else np.asarray(mask, dtype=np.int32)))
 
-        def run(call, width):
-            d_f = d.up(np.full((Q, m), fill))
-            d_J = d.up(np.full((Q, m, width), fill)) if want_J else None
-            assert call(d_f, d_J) == 0, ctx.lib.blsq_last_error(ctx.h)
-            return (ctx.to_host(d_f, (Q, m), np.float64),
-                    ctx.to_host(d_J, (Q, m, width), np.float64) if want_J else None)
-        d_P = d.up(P_full)
-        full = run(lambda f, J: ctx.lib.blsq_model_eval_dev(ctx.h, M.id, B, reps, m, n, d_t, ts, d_y, d_w, ws, d_P, f, J,
-                                                            d_mask), n)
-        got = []
-        for pmap, nf, X, Pfix in maps:
-            d_X, d_F = d.up(X), d.up(Pfix)
-            got.append(run(lambda f, J: ctx.lib.blsq_model_eval_map_dev(
-                ctx.h, M.id, B, reps, m, n, nf, _i32(pmap), d_t, ts, d_y, d_w, ws, d_X, d_F, f, J, d_mask), nf))
+        def run(entry, width, **more):
+            rc, f, J = me.run(ctx, entry, (Q, m), (Q, m, width), True, want_J, fill, dev=d, strict=True, **data, **more)
+            assert rc == 0, ctx.lib.blsq_last_error(ctx.h)
+            return f, J
+        full = run("blsq_model_eval_dev", n, X=P_full)
+        got = [run("blsq_model_eval_map_dev", nf, nf=nf, pmap=pmap, X=X, Pfix=Pfix) for pmap, nf, X, Pfix in maps]
         return full, got
-    finally:
-        d.close()
 
 
 def split(pm, P, reps):
@@ -192,8 +151,8 @@ def test_argument_errors_name_the_argument(ctx):
 
         def call(model=2, B=1, reps=1, m=4, n=4, nf=2, pmap=(0, -1, 1, 1), t=buf, ts=0, y=None, w=None, ws=0, X=bufX,
                  F=bufF, f=out, J=None):
-            return lib.blsq_model_eval_map_dev(h, model, B, reps, m, n, nf, _i32(pmap), t, ts, y, w, ws, X, F, f, J,
-                                               None)
+            return me.call(ctx, "blsq_model_eval_map_dev", True, model=model, B=B, reps=reps, m=m, n=n, nf=nf, pmap=pmap,
+                           t=t, t_stride=ts, y=y, w=w, w_stride=ws, X=X, Pfix=F, f=f, J=J, mask=None)
 
         def err():
             return lib.blsq_last_error(h)
@@ -414,27 +373,11 @@ def test_mapped_device_route_calls_no_host_callback(ctx, monkeypatch):
         fit_mapped(ctx, pr, fixed, tied, "trf", driver="host")
 
 
-class _Counting:
-    """The library with its two model entries counted."""
-
-    def __init__(self, lib):
-        self._lib, self.counts = lib, {"blsq_model_eval_dev": 0, "blsq_model_eval_map_dev": 0}
-
-    def __getattr__(self, name):
-        fn = getattr(self._lib, name)
-        if name in self.counts:
-            def counted(*a):
-                self.counts[name] += 1
-                return fn(*a)
-            return counted
-        return fn
-
-
 def test_nothing_changes_without_the_keywords(ctx, monkeypatch):
     """fixed=[] / tied={} and the keywords absent: the same bits, through the unmapped entry; with a map: the mapped
     entry alone."""
     pr = mc.fit_problem("gauss2", 33)
-    lib = _Counting(ctx.lib)
+    lib = me.Counting(ctx.lib, ("blsq_model_eval_dev", "blsq_model_eval_map_dev"))
     monkeypatch.setattr(ctx, "lib", lib)
 
     def run(**kw):

@@ -10,86 +10,34 @@ import bounded_lsq
 from bounded_lsq import ParamMap, models
 
 import _poisson_cases as pc
+import _model_eval as me
+from _model_eval import Dev, agree, ctx  # noqa: F401  (ctx: the module's fixture)
 
 pytestmark = pytest.mark.gpu
 LD = np.longdouble
 LSE, POISSON = 0, 1                                    # BLSQ_EST_*
 
 
-@pytest.fixture(scope="module")
-def ctx():
-    from bounded_lsq import _abi
-    c = _abi.Context(0)
-    yield c
-    c.close()
-
-
 # ---- kernel level --------------------------------------------------------------------------------------------------
-class Dev:
-    """Device copies of a test's arrays, freed together."""
-
-    def __init__(self, ctx):
-        self.ctx, self.ptrs = ctx, []
-
-    def up(self, a):
-        if a is None:
-            return None
-        p = self.ctx.to_device(np.ascontiguousarray(a))
-        self.ptrs.append(p)
-        return p
-
-    def close(self):
-        for p in self.ptrs:
-            self.ctx.free(p)
-
-
-def i32(a):
-    from bounded_lsq import _abi
-    if a is None:
-        return None, None
-    a = np.ascontiguousarray(a, dtype=np.int32)
-    return a, a.ctypes.data_as(_abi.c_int32_p)
-
-
 def eval_est(ctx, label, est, reps, m, x, per_problem, y, w, X, Pfix=None, want_f=True, want_J=False, mask=None,
              fill=None, entry="est"):
     """blsq_model_eval_est_dev for the instance `label` on host arrays -> (rc, f or None, J or None); entry='old': the
     same call through the entry it stands in for (blsq_model_eval_dev, _map_dev or _comp_dev).  fill: the value f and J
     hold before."""
     M, pm = pc.model_of(label), pc.map_of(label)
-    comp = pc.is_composite(label)
     n = pc.INSTANCES[label][1]
     nc = n if pm is None else pm.nf
-    B, Q = pc.B, pc.B * reps
-    d = Dev(ctx)
-    try:
-        d_f = d.up(np.full((Q, m), np.nan if fill is None else fill)) if want_f else None
-        d_J = d.up(np.full((Q, m, nc), np.nan if fill is None else fill)) if want_J else None
-        ws = m if (w is not None and np.ndim(w) == 2) else 0
-        ts = M.coords * m if per_problem else 0
-        fam, fam_p = i32(M.fam_ids if comp else None)
-        cnt, cnt_p = i32(M.counts if comp else None)
-        pmv, pm_p = i32(None if pm is None else pm.pmap)
-        d_t, d_y, d_w, d_X, d_F = d.up(x), d.up(y), d.up(w), d.up(X), d.up(Pfix if pm is not None else None)
-        d_m = d.up(None if mask is None else np.asarray(mask, dtype=np.int32))
-        lib, h = ctx.lib, ctx.h
-        if entry == "est":
-            rc = lib.blsq_model_eval_est_dev(h, est, -1 if comp else M.id, len(M.components) if comp else 0, fam_p, cnt_p,
-                                             B, reps, m, n, nc, pm_p, d_t, ts, d_y, d_w, ws, d_X, d_F, d_f, d_J, d_m)
-        elif comp:
-            rc = lib.blsq_model_eval_comp_dev(h, len(M.components), fam_p, cnt_p, B, reps, m, n, nc, pm_p, d_t, ts, d_y,
-                                              d_w, ws, d_X, d_F, d_f, d_J, d_m)
-        elif pm is not None:
-            rc = lib.blsq_model_eval_map_dev(h, M.id, B, reps, m, n, nc, pm_p, d_t, ts, d_y, d_w, ws, d_X, d_F, d_f, d_J,
-                                             d_m)
-        else:
-            rc = lib.blsq_model_eval_dev(h, M.id, B, reps, m, n, d_t, ts, d_y, d_w, ws, d_X, d_f, d_J, d_m)
-        if rc != 0:
-            return rc, None, None
-        return (0, ctx.to_host(d_f, (Q, m), np.float64) if want_f else None,
-                ctx.to_host(d_J, (Q, m, nc), np.float64) if want_J else None)
-    finally:
-        d.close()
+    Q = pc.B * reps
+    if entry == "est":
+        name = "blsq_model_eval_est_dev"
+    elif pc.is_composite(label):
+        name = "blsq_model_eval_comp_dev"
+    else:
+        name = "blsq_model_eval_dev" if pm is None else "blsq_model_eval_map_dev"
+    return me.run(ctx, name, (Q, m), (Q, m, nc), want_f, want_J, np.nan if fill is None else fill, est=est,
+                  **me.model_args(M), B=pc.B, reps=reps, m=m, n=n, nf=nc, pmap=None if pm is None else pm.pmap, t=x,
+                  t_stride=M.coords * m if per_problem else 0, y=y, w=w, w_stride=me.w_stride(w, m), X=X,
+                  Pfix=Pfix if pm is not None else None, mask=mask)
 
 
 @pytest.mark.parametrize("m", pc.ROWS)
@@ -198,17 +146,13 @@ def test_argument_errors_name_the_argument(ctx):
     try:
         buf, bufP = d.up(np.zeros(64)), d.up(np.ones(64))
         out, outJ = d.up(np.full(64, -7.0)), d.up(np.full(64, -7.0))
-        keep = []
 
         def call(est=POISSON, model=2, fam=None, cnt=None, ncomp=None, B=1, reps=1, m=4, n=4, nf=4, pmap=None, t=buf,
                  ts=0, y=bufP, w=None, ws=0, X=bufP, Pfix=None, f=out, J=None):
-            fa, fp = i32(fam)
-            ca, cp = i32(cnt)
-            pa, pp = i32(pmap)
-            keep.append((fa, ca, pa))
             nc = ncomp if ncomp is not None else (0 if fam is None else len(fam))
-            return lib.blsq_model_eval_est_dev(h, est, model, nc, fp, cp, B, reps, m, n, nf, pp, t, ts, y, w, ws, X, Pfix,
-                                               f, J, None)
+            return me.call(ctx, "blsq_model_eval_est_dev", True, est=est, model=model, ncomp=nc, fam=fam, cnt=cnt, B=B,
+                           reps=reps, m=m, n=n, nf=nf, pmap=pmap, t=t, t_stride=ts, y=y, w=w, w_stride=ws, X=X, Pfix=Pfix,
+                           f=f, J=J, mask=None)
         comp = dict(model=-1, fam=(0, 4), cnt=(1, 1))
         bad = [(dict(est=2), -2), (dict(est=-1), -2), (dict(model=5), -3), (dict(model=-2), -3),
                (dict(ncomp=1), -4), (dict(model=-1), -4), (dict(model=-1, ncomp=9, fam=(4,) * 9, cnt=(1,) * 9), -4),
@@ -258,19 +202,6 @@ def fit(ctx, pr, route, **kw):
             return bounded_lsq.curve_fit_batch(M.f, pr["x"], pr["Y"], pr["P0"], driver="device", **common)
         return bounded_lsq.curve_fit_batch(pr["spec"], pr["x"], pr["Y"], pr["P0"],
                                            driver="device" if route == "B" else "host", **common)
-
-
-def normalised(pcov, free):
-    C = pcov[:, free][:, :, free]
-    d = np.sqrt(np.einsum("bii->bi", C))
-    return C / (d[:, :, None] * d[:, None, :])
-
-
-def agree(a, b, what, rtol_p=1e-6, atol_p=1e-9):
-    """``agree`` of tests/test_models_gpu.py (popt rtol 1e-6, normalised pcov atol 1e-6), over the free parameters."""
-    free = np.flatnonzero(np.all(np.einsum("bii->bi", a[1]) > 0, axis=0))
-    np.testing.assert_allclose(b[0], a[0], rtol=rtol_p, atol=atol_p, err_msg=str(what))
-    np.testing.assert_allclose(normalised(b[1], free), normalised(a[1], free), rtol=0, atol=1e-6, err_msg=str(what))
 
 
 @pytest.fixture(scope="module")
@@ -401,15 +332,7 @@ def test_device_route_goes_through_the_new_entry_alone(ctx, problem, device_fit,
     monkeypatch.setattr(_models.CompositeModel, "f", boom)
     monkeypatch.setattr(_models.CompositeModel, "jac", boom)
     monkeypatch.setattr(_models, "poisson_transform", boom)
-    entries = {}
-    lib = ctx.lib
-
-    class Counting:
-        def __getattr__(self, name):
-            if name.startswith("blsq_model_eval"):
-                entries[name] = entries.get(name, 0) + 1
-            return getattr(lib, name)
-    monkeypatch.setattr(ctx, "lib", Counting())
+    entries = me.count_entries(ctx, monkeypatch)
     got = fit(ctx, problem, "B")
     assert np.array_equal(got[0], device_fit[0]) and np.array_equal(got[1], device_fit[1])
     assert set(entries) == {"blsq_model_eval_est_dev"}
