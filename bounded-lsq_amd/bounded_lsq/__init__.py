@@ -15,6 +15,7 @@ from ._outer import OuterDriver  # noqa: F401
 from ._cov import covariance  # noqa: F401
 from ._leverage import leverage, prediction_variance, influence  # noqa: F401
 from ._curve_fit import curve_fit, curve_fit_batch, curve_fit_global  # noqa: F401
+from ._linear import lsq_linear, lsq_linear_batch, LinearFit, LinearDeviceModel  # noqa: F401
 from . import _models as models  # noqa: F401
 from ._params import ParamMap, GlobalMap  # noqa: F401
 from ._hostmath import (active_mask as find_active_constraints,  # noqa: F401
@@ -24,4 +25,5 @@ from ._hostmath import (active_mask as find_active_constraints,  # noqa: F401
 __all__ = ['dogbox', 'trf', 'find_active_constraints', 'CL_optimality', 'prepare_bounds',
            'make_strictly_feasible', 'least_squares', 'least_squares_batch', 'TrfStepSolver', 'DogboxStepSolver',
            'OuterDriver', 'covariance', 'curve_fit', 'curve_fit_batch', 'leverage', 'prediction_variance',
-           'influence', 'models', 'ParamMap', 'GlobalMap', 'curve_fit_global']
+           'influence', 'models', 'ParamMap', 'GlobalMap', 'curve_fit_global', 'lsq_linear', 'lsq_linear_batch',
+           'LinearFit', 'LinearDeviceModel']

@@ -176,6 +176,8 @@ SIGNATURES = {
     "blsq_model_info": (C.c_int, [C.c_int, C.POINTER(C.c_char_p), c_int32_p, c_int32_p, c_int32_p]),
     "blsq_term_count": (C.c_int, []),
     "blsq_term_info": (C.c_int, [C.c_int, C.POINTER(C.c_char_p), c_int32_p]),
+    # ctx, B, reps, m, n, A, A_stride, y, w, w_stride, X, f, J, mask (no model, no table: not a row of MODEL_EVAL_ARGS)
+    "blsq_linear_eval_dev": (C.c_int, [vp] + [C.c_int] * 4 + [vp, C.c_long, vp, vp, C.c_long, vp, vp, vp, vp]),
 }
 SIGNATURES.update((name, (C.c_int, [vp] + [MODEL_EVAL_TYPES[k] for k in args]))
                   for name, args in MODEL_EVAL_ARGS.items())

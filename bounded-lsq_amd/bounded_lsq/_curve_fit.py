@@ -15,24 +15,13 @@ from scipy.optimize import OptimizeWarning
 
 from ._frontend import least_squares
 from ._batch import least_squares_batch
-from ._hostmath import prepare_bounds
+from ._hostmath import prepare_bounds, _initialize_feasible
 from . import _models
 from ._params import ParamMap, GlobalMap
 
 __all__ = ['curve_fit', 'curve_fit_batch', 'curve_fit_global']
 
 _COV_WARNING = 'Covariance of the parameters could not be estimated'
-
-
-def _initialize_feasible(lb, ub):
-    """scipy's start point when p0 is None: 1, or the middle of / one unit inside the finite bounds."""
-    p0 = np.ones_like(lb)
-    lo, hi = np.isfinite(lb), np.isfinite(ub)
-    both = lo & hi
-    p0[both] = 0.5 * (lb[both] + ub[both])
-    p0[lo & ~hi] = lb[lo & ~hi] + 1
-    p0[~lo & hi] = ub[~lo & hi] - 1
-    return p0
 
 
 def _memoize_first(fn):

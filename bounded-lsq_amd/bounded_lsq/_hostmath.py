@@ -19,6 +19,17 @@ def prepare_bounds(bounds, x0):
     return lb, ub
 
 
+def _initialize_feasible(lb, ub):
+    """scipy's start point when p0 is None: 1, or the middle of / one unit inside the finite bounds."""
+    p0 = np.ones_like(lb)
+    lo, hi = np.isfinite(lb), np.isfinite(ub)
+    both = lo & hi
+    p0[both] = 0.5 * (lb[both] + ub[both])
+    p0[lo & ~hi] = lb[lo & ~hi] + 1
+    p0[~lo & hi] = ub[~lo & hi] - 1
+    return p0
+
+
 def shift_into_interior(x, lb, ub, rstep=0.0):
     """bounds.py:79-103 (make_strictly_feasible)."""
     out = np.array(x, dtype=float, copy=True)

@@ -655,6 +655,24 @@ struct ModelEvalCall {
 // cannot hold: the refusals that keep the kernel's offsets in bounds.
 hipError_t launch_model_eval(const ModelEvalCall& c, hipStream_t s);
 
+// ------------------------------------------------------ linear residuals (7r) ----
+// One evaluation of linear_kernels.hip (blsq_linear_eval_dev): f [B * reps][m] = w (A x - y) at X [B * reps][n] and / or
+// J [B][m][n] = diag(w) A (reps == 1; problems with mask[b] == 0 are neither read nor written; f takes no mask).
+struct LinearEvalCall {
+  int B, reps, m, n;
+  const double* A; long A_stride;   // row-major [m][n]; stride 0 (one matrix for all problems) or m n
+  const double* y;        // [B][m] or nullptr (0)
+  const double* w; long w_stride;   // nullptr (1), or stride 0 / m
+  const double* X;
+  double* f;
+  double* J;
+  const int* mask;        // nullptr or [B]
+};
+// hipErrorInvalidValue, and nothing launched, for a size below 1, n above BLSQ_LINEAR_MAX_N, a stride other than the two
+// its array has, a missing A or X, no output, J with reps != 1, or a batch the grid cannot hold: the refusals that keep
+// the kernels' offsets in bounds.
+hipError_t launch_linear_eval(const LinearEvalCall& c, hipStream_t s);
+
 // ---------------------------------------------------------------- probes ----
 // probe_kernels.hip: measured peaks / counter calibration (blsq_debug_probe)
 hipError_t launch_mfma_probe(int waves_per_simd, int iters, double* sink, long* n_mfma,

@@ -273,3 +273,24 @@ extern "C" int blsq_model_eval_tie_dev(blsq_ctx* ctx, int est, int sampling, int
                                             dt, t_stride, dy, dw, w_stride, dX, dPfix, df, dJ, dmask, S,
                                             S > 0 ? shared : nullptr, t_sstride, tie_ratio, tie_offset});
 }
+
+// Linear residuals (linear_kernels.hip): no model, no table: the checks in the order of the arguments, then
+// the launches (f, then J) as one timed call in the slot of the model evaluations.
+extern "C" int blsq_linear_eval_dev(blsq_ctx* ctx, int B, int reps, int m, int n, const double* dA, long A_stride,
+                                    const double* dy, const double* dw, long w_stride, const double* dX, double* df,
+                                    double* dJ, const int32_t* dmask) {
+  if (!ctx) return -1;
+  if (B <= 0) return ctx->bad(2, "B must be positive");
+  if (reps <= 0) return ctx->bad(3, "reps must be positive");
+  if (m <= 0) return ctx->bad(4, "m must be positive");
+  if (n < 1 || n > BLSQ_LINEAR_MAX_N) return ctx->bad(5, "n must be in 1 .. BLSQ_LINEAR_MAX_N");
+  if (!dA) return ctx->bad(6, "A is NULL");
+  if (A_stride != 0 && A_stride != (long)m * n) return ctx->bad(7, "A_stride must be 0 or m * n");
+  if (w_stride != 0 && w_stride != (long)m) return ctx->bad(10, "w_stride must be 0 or m");
+  if (!dX) return ctx->bad(11, "X is NULL (the points)");
+  if (!df && !dJ) return ctx->bad(12, "f and J are both NULL");
+  if (dJ && reps != 1) return ctx->bad(13, "J requires reps == 1");
+  HIPCHK(ctx, hipSetDevice(ctx->device));
+  const LinearEvalCall c{B, reps, m, n, dA, A_stride, dy, dw, w_stride, dX, df, dJ, dmask};
+  return ctx->run(K_MODEL_EVAL, "launch_linear_eval", [&] { return launch_linear_eval(c, ctx->stream); });
+}

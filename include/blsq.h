@@ -588,6 +588,27 @@ int blsq_model_eval_tie_dev(blsq_ctx* ctx, int est, int sampling, int nan_policy
                             const double* dw, long w_stride, const double* dX, const double* dPfix, double* df,
                             double* dJ, const int32_t* dmask);
 
+/* ---- linear residuals, evaluated on the device -----------------------------------------------------
+ * The callbacks of a bounded linear least-squares solve, min 1/2 |A x - y|^2 with lb <= x <= ub (blsq_outer_*:
+ * f <- fun(x), J <- jac(x)), so that the whole batched solve stays on the GPU.  For the points X [B * reps][n] (the
+ * points of problem b are rows b * reps .. b * reps + reps - 1, as blsq_model_eval_dev):
+ *   f[q][i] = w[b][i] * (sum_j A[b][i][j] * X[q][j] - y[b][i])          df [B * reps][m], or NULL
+ *   J[b]    = diag(w[b]) * A[b]                                         dJ [B][m][n], or NULL; reps must be 1
+ * dA: row-major [m][n], the layout of J: ONE matrix shared by all problems (A_stride 0) or [B][m][n] (A_stride m * n);
+ * dy: [B][m] or NULL (0: a plain product); dw: NULL (1), [m] (w_stride 0) or [B][m] (w_stride m); dmask: int32 [B] or
+ * NULL: J[b] of a problem with dmask[b] == 0 is not touched at all (f takes no mask).  The sum is a chain of fma() per
+ * lane and a fixed tree over the lanes, a function of n alone: a problem's f does not depend on B, reps, the strides or
+ * its batch mates, and f for a shared A equals, bit for bit, f for that matrix replicated.  With dw == NULL J[b] is A[b]
+ * bit for bit; with dw every element is multiplied once.  Nothing is checked on the device: non-finite values pass
+ * through as IEEE arithmetic gives them.  1 <= n <= BLSQ_LINEAR_MAX_N (the widest plan), m >= 1.  All pointers are device
+ * pointers; asynchronous on the ctx stream; timed in the `model_eval` slot.  A negative return is the index of the bad
+ * argument (ctx = 1, B = 2, reps = 3, m = 4, n = 5, A = 6, A_stride = 7, y, w = 9, w_stride = 10, X = 11, f = 12: f and
+ * J both NULL, J = 13: reps != 1, mask); nothing is launched then. */
+#define BLSQ_LINEAR_MAX_N 1023
+int blsq_linear_eval_dev(blsq_ctx* ctx, int B, int reps, int m, int n, const double* dA, long A_stride,
+                         const double* dy, const double* dw, long w_stride, const double* dX, double* df, double* dJ,
+                         const int32_t* dmask);
+
 /* ---- parameter covariance from the final Jacobian --------------------------------------------------------------
  * The reference documents `x_covariance` as the inverse of J^T J at the solution (least_squares.py:248-252) and fills
  * it only through its MINPACK bridge (method='lm').  Here, per problem, from a Householder triangle R of J (the TSQR
