@@ -178,6 +178,8 @@ SIGNATURES = {
     "blsq_term_info": (C.c_int, [C.c_int, C.POINTER(C.c_char_p), c_int32_p]),
     # ctx, B, reps, m, n, A, A_stride, y, w, w_stride, X, f, J, mask (no model, no table: not a row of MODEL_EVAL_ARGS)
     "blsq_linear_eval_dev": (C.c_int, [vp] + [C.c_int] * 4 + [vp, C.c_long, vp, vp, C.c_long, vp, vp, vp, vp]),
+    # ctx, est, nan_policy, B, reps, m, nc, L, origin, h, h_stride, g, G, y, w, w_stride, f, J, mask
+    "blsq_response_apply_dev": (C.c_int, [vp] + [C.c_int] * 8 + [vp, C.c_long, vp, vp, vp, vp, C.c_long, vp, vp, vp]),
 }
 SIGNATURES.update((name, (C.c_int, [vp] + [MODEL_EVAL_TYPES[k] for k in args]))
                   for name, args in MODEL_EVAL_ARGS.items())

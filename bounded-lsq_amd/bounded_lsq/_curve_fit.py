@@ -7,7 +7,7 @@ computed on the GPU (``covariance='pinv'``) where scipy takes an S
 """
 import warnings
 from collections import namedtuple
-from inspect import getfullargspec
+from inspect import getfullargspec, signature
 
 import numpy as np
 from scipy.linalg import cholesky, solve_triangular, LinAlgError
@@ -94,6 +94,45 @@ def _check_poisson(estimator, sigma, ydata, omitted=None):
     return True
 
 
+def _response_single(f, jac, xdata, ydata, sigma, nan_policy, response, response_origin):
+    """``curve_fit`` through an instrument response: `f` and a callable `jac` wrapped so that they return the convolved
+    model, with `f`'s signature kept (p0=None counts its arguments).  Under 'omit' the wrappers evaluate on the whole
+    grid and drop the NaN points of `ydata` after the convolution; the data are shortened here to match."""
+    h, origin = _models.check_response(response, response_origin)
+    if h.ndim != 1:
+        raise ValueError("`response` must have shape (L,) in `curve_fit`: there is one problem.")
+    keep = None
+    if nan_policy == 'omit':
+        y = np.asarray(ydata, float)
+        if isinstance(xdata, (list, tuple, np.ndarray)) and np.isnan(np.asarray(xdata, float)).any():
+            raise ValueError("`xdata` must not contain NaN with `response` and nan_policy='omit': the model is "
+                             "evaluated on the whole grid.")
+        if y.ndim == 1 and np.isnan(y).any():
+            keep = ~np.isnan(y)
+    x_full, user_f, user_jac = xdata, f, jac
+
+    def fc(x, *params):
+        mu = _models.apply_response(np.asarray(user_f(x_full, *params), float), h, origin)
+        return mu if keep is None else mu[keep]
+    fc.__signature__ = signature(user_f)
+    jc = jac
+    if callable(jac):
+        def jc(x, *params):
+            J = _models.apply_response(np.asarray(user_jac(x_full, *params), float).T, h, origin).T
+            return J if keep is None else J[keep]
+    if keep is not None:
+        ydata = y[keep]
+        if isinstance(xdata, (list, tuple, np.ndarray)):
+            xdata = np.asarray(xdata, float)[..., keep]      # (the wrappers do not read it: x_full is the grid)
+        if sigma is not None:
+            sigma = np.asarray(sigma)
+            if sigma.ndim == 1:
+                sigma = sigma[keep]
+            elif sigma.ndim == 2:
+                sigma = sigma[keep][:, keep]
+    return fc, jc, xdata, ydata, sigma
+
+
 def _param_map(n, fixed, tied):
     """The ParamMap of the `fixed` / `tied` keywords, or None where they hold nothing (then nothing changes)."""
     if fixed is None and not tied:
@@ -117,7 +156,7 @@ def _contains_nan(a, nan_policy):
 
 def curve_fit(f, xdata, ydata, p0=None, sigma=None, absolute_sigma=False, check_finite=None,
               bounds=(-np.inf, np.inf), method=None, jac=None, full_output=False, fixed=None, tied=None,
-              estimator='lse', nan_policy=None, **kwargs):
+              estimator='lse', nan_policy=None, response=None, response_origin=0, **kwargs):
     """Fit ``ydata = f(xdata, *p) + eps`` by non-linear least squares; returns ``(popt, pcov)``.
 
     Parameters, exceptions, warnings and results are scipy.optimize.curve_fit's (1.15.3):
@@ -155,8 +194,17 @@ def curve_fit(f, xdata, ydata, p0=None, sigma=None, absolute_sigma=False, check_
     ``ydata >= 0``, as ``curve_fit_batch`` describes it (deviance residuals in ``fvec``; `sigma` must be None; the
     bounds must keep `f` positive; `absolute_sigma` True gives the Gauss-Newton form of the inverse Fisher information,
     False the quasi-Poisson covariance).  A callable `jac` is still the Jacobian of `f`.
+
+    response, response_origin : a measured kernel (L,) the model is convolved with before it is compared with `ydata`
+    (``models.apply_response``: over the sample index, zeros past both ends), as ``curve_fit_batch`` describes it.  `f`
+    and a callable `jac` still return the model and ITS Jacobian.  With ``nan_policy='omit'`` the model is evaluated and
+    convolved on the whole grid and the points where `ydata` is NaN are dropped afterwards; `xdata` must then be free of
+    NaN.
     """
     _models.check_estimator(estimator)
+    if response is not None:
+        f, jac, xdata, ydata, sigma = _response_single(f, jac, xdata, ydata, sigma, nan_policy, response,
+                                                       response_origin)
     pm = None
     if fixed is not None or tied:
         if p0 is None:
@@ -309,7 +357,8 @@ def _curve_fit_mapped(pm, f, xdata, ydata, p0, sigma, absolute_sigma, check_fini
 _Layout = namedtuple('_Layout', 'lead m Y P0 make_map xdata none_left propagate_hint sigma_2d')
 
 
-def _fit(lay, f, xdata, sigma, absolute_sigma, bounds, method, jac, driver, ctx, estimator, binned, nan_policy, kwargs):
+def _fit(lay, f, xdata, sigma, absolute_sigma, bounds, method, jac, driver, ctx, estimator, binned, nan_policy, kwargs,
+         response=None, response_origin=0):
     """``curve_fit_batch`` and ``curve_fit_global`` between their shape checks and their results: the checks of the
     keywords in their order, the residual and Jacobian of the solver's variables (on the device: a ``DeviceFit``) and
     the solve.  Returns ``(results, map, no_dof)``: `results` with ``nobs`` / ``omitted`` and ``deviance`` set,
@@ -334,6 +383,10 @@ def _fit(lay, f, xdata, sigma, absolute_sigma, bounds, method, jac, driver, ctx,
     poisson = _check_poisson(estimator, sigma, ydata, omitted)
     mp = lay.make_map()
     model = None
+    if response is not None:                     # (curve_fit_batch alone passes one: `lead` is (B,))
+        response, response_origin = _models.check_response(response, response_origin, problems)
+        _models.check_response_model(_models.resolve(f) if isinstance(f, (str, _models.CompositeModel)) else None,
+                                     problems, lay.m, xdata, binned)
     if binned and not isinstance(f, (str, _models.CompositeModel)):
         raise ValueError("`binned=True` needs a built-in model (a name, a spec or a CompositeModel) as `f`: a callable "
                          "integrates itself over its bins.")
@@ -383,9 +436,18 @@ def _fit(lay, f, xdata, sigma, absolute_sigma, bounds, method, jac, driver, ctx,
         x_start = P0
     nv = x_start.shape[1]                        # solver variables: n, nf, or nv of a group
 
-    if model is not None and driver == 'device':
-        func = _models.DeviceFit(model.name, n, x_dev, ydata, sigma, Pfix=None if mp is None else P0,
+    on_device = model is not None and driver == 'device'
+    if response is not None and not on_device:   # after the map's column sums, before the data: the device's order
+        if callable(jac):
+            jac = _models.response_jacobian(jac, response, response_origin)
+        f = _models.response_residual(f, response, response_origin)
+
+    if on_device:
+        func = _models.DeviceFit(model.name, n, xdata if (binned and response is not None) else x_dev, ydata, sigma,
+                                 Pfix=None if mp is None else P0,
                                  **{'global_map' if isinstance(mp, GlobalMap) else 'param_map': mp},
+                                 **({} if response is None
+                                    else {'response': response, 'response_origin': response_origin}),
                                  **({'estimator': estimator} if poisson else {}),
                                  **({'binned': True} if binned else {}),
                                  **({'nan_policy': 'omit'} if omitted is not None else {}))
@@ -457,7 +519,7 @@ def _popt_pcov(results, shape, no_dof, popt_of, pcov_of):
 
 def curve_fit_batch(f, xdata, ydata, p0, sigma=None, absolute_sigma=False, bounds=(-np.inf, np.inf), method='trf',
                     jac=None, driver='host', ctx=None, fixed=None, tied=None, estimator='lse', binned=False,
-                    nan_policy=None, **kwargs):
+                    nan_policy=None, response=None, response_origin=0, **kwargs):
     """``curve_fit`` for B data sets of one model, solved together by ``least_squares_batch``.
 
     f : ``f(xdata, P) -> (B, m)`` for parameters ``P`` of shape (B, n): vectorised over the batch — or the name of a
@@ -542,6 +604,26 @@ def curve_fit_batch(f, xdata, ydata, p0, sigma=None, absolute_sigma=False, bound
             under the ``OptimizeWarning`` while its batch mates keep their results.  A problem without a single point
             is a ValueError naming it; 'propagate' or any other string is a ValueError.  NaN in `xdata` of a binned
             model is still rejected, and the rank tolerance of the pseudo-inverse keeps using the allocated m.
+    response, response_origin : None (the default: nothing changes, bit for bit) or a measured kernel the model is
+            convolved with before it is compared with `ydata`: the instrument response function of a
+            detector under a decay, the resolution function of a spectrometer over a line.  `response` has shape (L,),
+            shared by all problems, or (B, L), 1 <= L <= 1024, finite and not all zero (L may exceed m);
+            ``mu[i] = sum_k response[k] * model[i + response_origin - k]`` with the terms outside [0, m) dropped
+            (``models.apply_response``, the definition): ``response_origin=0`` is the causal convolution, whose delay
+            lives in the kernel; ``response_origin=L // 2`` with odd L is ``np.convolve(model, response, 'same')``.  The
+            convolution is over the SAMPLE INDEX: `xdata` on a uniform grid, and the kernel sampled at its spacing and
+            normalised as wanted, are the caller's business.  Past both ends the model counts as zero, so with a
+            baseline the outermost L points see an edge that is not in the data: set them to NaN under
+            ``nan_policy='omit'`` (the model is still evaluated there, its neighbours need it).  The residual is
+            ``w (mu - y)``, under ``estimator='poisson'`` the deviance residual of mu, and the Jacobian the convolved
+            columns times w (times c).  A named model with driver='device' is convolved by a kernel of its own behind
+            the model kernel (blsq_response_apply_dev); a callable `f` / `jac` still returns the model and ITS
+            Jacobian and is wrapped by ``models.response_residual`` / ``models.response_jacobian``, as is the named
+            model with driver='host'.  Composite models, `fixed` / `tied`, ``binned=True`` with contiguous edges
+            (bin integrals, then a convolution over the bins), `sigma`, ``loss=``, ``leverage=``, `bounds` and every
+            `jac` choice compose unchanged, and so do the results and the variance factor.  'gauss2d' (any model of
+            two coordinates) and binned edges given as rows ``lo, hi`` are ValueErrors, as are a kernel of another
+            shape, one that is not finite or all zero, and an origin outside 0 .. L - 1.
 
     Returns ``(popt (B, n), pcov (B, n, n), results)``, `results` the B ``OptimizeResult`` of the solve.  pcov[b] is
     ``curve_fit``'s for problem b alone: the pseudo-inverse covariance of its final Jacobian, times
@@ -573,7 +655,7 @@ def curve_fit_batch(f, xdata, ydata, p0, sigma=None, absolute_sigma=False, bound
                   "nan_policy='omit': problem %d has no point left, every entry of its `ydata` is NaN.",
                   " (a NaN passes through with None)", "a 2-D covariance `sigma` is not supported by `curve_fit_batch`.")
     results, pm, no_dof = _fit(lay, f, xdata, sigma, absolute_sigma, bounds, method, jac, driver, ctx, estimator, binned,
-                               nan_policy, kwargs)
+                               nan_policy, kwargs, response, response_origin)
     if pm is not None:                           # the full-size fields of the results, expanded for the batch at once
         X_full = pm.expand_x(np.stack([r.x for r in results]), P0)
         masks = pm.expand_mask(np.stack([np.asarray(r.active_mask) for r in results]))
@@ -607,7 +689,7 @@ def curve_fit_global(f, xdata, ydata, p0, shared, sigma=None, absolute_sigma=Fal
             Jacobian written into the group's column layout) — or a callable ``f(xdata, P) -> (G S, m)`` for the
             parameters ``P`` (G S, n) of all data sets, row g S + s being data set s of group g; it goes through
             ``GlobalMap.wrap_f`` / ``wrap_jac``, as the named model does with driver='host'.  'gauss2d' and
-            ``binned=True`` are ValueErrors.
+            ``binned=True`` are ValueErrors, and so is ``response=`` (not built for global fits).
     xdata : (m,), (S, m) or (G, S, m); a callable receives (m,) or (G S, m).
     sigma : None, a scalar, (m,), (S, m) or (G, S, m).  bounds : pair broadcastable to (G, S, n); the box of a shared
             parameter is the intersection over the data sets of its group (empty: ValueError).
@@ -630,6 +712,9 @@ def curve_fit_global(f, xdata, ydata, p0, shared, sigma=None, absolute_sigma=Fal
     """
     if kwargs.pop('binned', False):
         raise ValueError("`binned=True` is not supported by `curve_fit_global`.")
+    if kwargs.pop('response', None) is not None or kwargs.pop('response_origin', 0) != 0:
+        raise ValueError("`response` is not supported by `curve_fit_global`: an instrument response is not built for "
+                         "global fits.")
     ydata = np.asarray(ydata, float)
     P0 = np.asarray(p0, float)
     single = ydata.ndim == 2

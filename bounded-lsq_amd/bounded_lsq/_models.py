@@ -66,6 +66,14 @@ Affine ties (``tied={j: (i, ratio, offset)}``; blsq_model_eval_tie
 (``param_map``, or ``global_map.pm``) has ``affine`` set, ``DeviceModel`` hands its ``ratio`` and ``offset`` to the one
 entry that takes them, for batch and global fits and under every flag above; ``ParamMap`` IS the definition
 (``expand_x``: ratio * x + offset; ``reduce_jac``: the columns times their ratios) and the kernel follows it bit for bit.
+
+Instrument response (``response=``, ``response_origin=``; blsq_response_apply_dev).  The model is convolved
+with a measured kernel h before it meets the data: ``apply_response(g, h, origin)`` IS the definition,
+``mu[i] = sum_k h[k] g[i + origin - k]`` with the terms outside [0, m) dropped, over the SAMPLE INDEX: a uniform grid,
+and h sampled at its spacing, are the caller's business.  ``response_residual`` / ``response_jacobian`` wrap any
+``f(xdata, P)`` / ``jac(xdata, P)`` with it: the ``driver='host'`` route and the route of a callable.  On the device
+the convolution is a second stage behind the model kernel, which is called as ``evaluate`` calls it; data, weights,
+estimator and omission are applied by the second stage.
 """
 import re
 
@@ -82,12 +90,14 @@ SAMPLING = ('point', 'bin')                  # BLSQ_SAMPLE_*
 NAN_POLICIES = ('propagate', 'omit')         # BLSQ_NAN_*
 POISSON_U0 = 0.25                            # |u| below which phi(u) is its series
 POISSON_TERMS = 26                           # ... of this many terms
+RESPONSE_MAX_L = 1024                        # BLSQ_RESPONSE_MAX_L
 
 __all__ = ['MODELS', 'NAMES', 'MAX_N', 'MAX_COMP', 'TERMS', 'get', 'compose', 'resolve', 'CompositeModel', 'evaluate',
            'DeviceModel', 'DeviceFit', 'ESTIMATORS', 'POISSON_U0', 'POISSON_TERMS', 'check_estimator',
            'poisson_transform', 'poisson_residual', 'poisson_jacobian', 'binned', 'bin_rows', 'BinnedModel', 'erf_diff',
            'psi_pair', 'PSI_X0', 'PSI_TERMS', 'SAMPLING', 'NAN_POLICIES', 'check_nan_policy', 'omit_residual',
-           'omit_jacobian', 'count_observed', 'pad_ragged']
+           'omit_jacobian', 'count_observed', 'pad_ragged', 'RESPONSE_MAX_L', 'check_response', 'apply_response',
+           'response_residual', 'response_jacobian']
 
 
 def _tp(xdata, P):
@@ -840,6 +850,89 @@ def pad_ragged(xs, ys):
     return xdata, ydata
 
 
+# ---- instrument response ---------------------------------------------------------------------------------------------
+def check_response(response, origin=0, B=None):
+    """The kernel of an instrument response as a contiguous float64 array (L,) or (B, L), and `origin` as an int.
+    ValueError unless: `response` is 1-D, or 2-D with B rows (`B` None: any number); 1 <= L <= RESPONSE_MAX_L; every
+    entry is finite and not all are zero; `origin` is an integer with 0 <= origin < L.  L may exceed m."""
+    try:
+        h = np.asarray(response, dtype=np.float64)
+    except (TypeError, ValueError):
+        raise ValueError("`response` must be an array of numbers of shape (L,) or (B, L).") from None
+    if h.ndim not in (1, 2) or (h.ndim == 2 and B is not None and h.shape[0] != B):
+        raise ValueError("`response` must have shape (L,) or (B, L)%s, not %s."
+                         % ("" if B is None else " with B = %d" % B, h.shape))
+    h = np.ascontiguousarray(h)
+    L = h.shape[-1]
+    if not 1 <= L <= RESPONSE_MAX_L:
+        raise ValueError("`response` has L = %d taps: L must be in 1 .. %d." % (L, RESPONSE_MAX_L))
+    if not np.all(np.isfinite(h)):
+        raise ValueError("`response` must be finite.")
+    if not np.any(h):
+        raise ValueError("`response` must not be all zero.")
+    if isinstance(origin, (bool, np.bool_)) or not isinstance(origin, (int, np.integer)):
+        raise ValueError("`response_origin` must be an integer, not %r." % (origin,))
+    if not 0 <= origin < L:
+        raise ValueError("`response_origin` = %d: it must be in 0 .. L - 1 = %d." % (origin, L - 1))
+    return h, int(origin)
+
+
+def apply_response(g, h, origin=0):
+    """The model values `g` (..., m) — or one Jacobian column moved to the last axis — convolved with the kernel `h`
+    of shape (L,), or (B, L) matching the leading axis of `g`:
+
+        mu[..., i] = sum_{k = 0}^{L - 1} h[k] * g[..., i + origin - k]
+
+    where a term whose index i + origin - k lies outside [0, m) is dropped: ``np.convolve(g, h)[origin : origin + m]``
+    with zeros past the end.  ``origin=0`` is the causal convolution of a decay with an instrument response function
+    (whose delay lives in `h`); ``origin=L // 2`` with odd L is ``np.convolve(g, h, 'same')``, a centred resolution
+    kernel.  The convolution is over the sample index: a uniform grid, and `h` sampled at its spacing, are the caller's
+    business.  The taps are added in ascending k; the result has the common floating dtype of `g` and `h` (np.longdouble
+    in gives a longdouble reference).  `h` and `origin` are checked by ``check_response``; L may exceed m."""
+    g, hh = np.asarray(g), np.asarray(h)
+    check_response(hh, origin, g.shape[0] if hh.ndim == 2 and g.ndim >= 1 else None)
+    dt = np.result_type(g.dtype, hh.dtype, np.float64)
+    g, hh = g.astype(dt, copy=False), hh.astype(dt, copy=False)
+    if hh.ndim == 2 and g.ndim < 2:
+        raise ValueError("a per-problem `response` (B, L) needs model values of shape (B, ..., m).")
+    m, L = g.shape[-1], hh.shape[-1]
+    mu = np.zeros(g.shape, dtype=dt)
+    for k in range(L):
+        s = origin - k                                         # mu[i] takes g[i + s]
+        lo, hi = max(0, -s), min(m, m - s)
+        if lo >= hi:
+            continue
+        hk = hh[k] if hh.ndim == 1 else hh[:, k].reshape((-1,) + (1,) * (g.ndim - 1))
+        mu[..., lo:hi] += hk * g[..., lo + s:hi + s]
+    return mu
+
+
+def response_residual(f, h, origin=0):
+    """``f(xdata, P) -> (B, m)`` -> the same model convolved with the response: ``apply_response(f(xdata, P), h, origin)``."""
+    return lambda xdata, P: apply_response(np.asarray(f(xdata, P)), h, origin)
+
+
+def response_jacobian(jac, h, origin=0):
+    """``jac(xdata, P) -> (B, m, n)`` -> the Jacobian of ``response_residual``: every column convolved along the points.
+    A `jac` that already went through a parameter map is convolved after the map's column sums."""
+    def g(xdata, P):
+        J = np.asarray(jac(xdata, P))
+        return np.moveaxis(apply_response(np.moveaxis(J, 1, -1), h, origin), -1, 1)
+    return g
+
+
+def check_response_model(model, B, m, xdata=None, binned=False, global_map=None):
+    """What a fit through an instrument response does not take, as ValueErrors."""
+    if global_map is not None:
+        raise ValueError("`response` is not supported in a global fit.")
+    if model is not None and model.coords != 1:
+        raise ValueError("model '%s' has %d coordinates: `response` is a convolution along one coordinate."
+                         % (model.name, model.coords))
+    if binned and np.shape(xdata) not in ((m + 1,), (B, m + 1)):
+        raise ValueError("`response` with `binned=True` needs contiguous bins, edges of shape (m + 1,) or (B, m + 1): "
+                         "a convolution over bins with gaps (rows lo, hi) is not defined.")
+
+
 def check_global(model, binned=False, param_map=None):
     """What a global fit does not take, as ValueErrors."""
     if binned:
@@ -917,15 +1010,25 @@ class DeviceModel:
 
     Affine ties: where ``param_map.affine`` (``global_map.pm.affine``) is true the callbacks go through
     blsq_model_eval_tie_dev alone, whatever the other flags are, with the map's ``ratio`` and ``offset``; otherwise
-    through the entry they went through before that one existed."""
+    through the entry they went through before that one existed.
+
+    ``response=`` a kernel (L,) or (B, L), with ``response_origin=``: the model convolved with it
+    (``apply_response``, over the sample index).  The entry above is then bound as ``evaluate`` binds it — without
+    `ydata`, `sigma`, the estimator and the omission — and writes raw model values and the raw Jacobian into two scratch
+    buffers of this object; blsq_response_apply_dev, launched behind it on the same stream, convolves them and applies
+    what was withheld.  One coordinate, no `global_map`, and `binned` with contiguous edges only (ValueError)."""
 
     def __init__(self, ctx, name, B, m, n, xdata, ydata=None, sigma=None, param_map=None, Pfix=None, estimator='lse',
-                 binned=False, nan_policy='propagate', global_map=None):
+                 binned=False, nan_policy='propagate', global_map=None, response=None, response_origin=0):
         model = resolve(name)
         model.terms(n)
         gm = global_map
         if gm is not None:
             check_global(model, binned, param_map)
+        self.response = None
+        if response is not None:
+            self.response, self.response_origin = check_response(response, response_origin, int(B))
+            check_response_model(model, int(B), int(m), xdata, binned, gm)
         self.binned = bool(binned)
         self.estimator = check_estimator(estimator)
         self.nan_policy = check_nan_policy(nan_policy)
@@ -982,6 +1085,8 @@ class DeviceModel:
                 self.d_Pfix = self._upload(Pfix)
         self.bounds_dev = None
         self._bind(m, pm, pmap, shared)
+        if self.response is not None:
+            self._bind_response()
         ctx.adopt(self)
 
     def _upload(self, a):
@@ -1003,15 +1108,19 @@ class DeviceModel:
         set; `pm`: the ParamMap of the fit (a global fit's own) or None, `pmap` its int32 map; `shared`: the int32 flags of
         the slots a group shares, or None."""
         M, comp, gm = self.model, isinstance(self.model, CompositeModel), self.global_map
+        # behind an instrument response the entry gives the raw model: data, weights, estimator and omission are withheld
+        estimator, nan_policy, d_y, d_w, w_stride = (
+            (self.estimator, self.nan_policy, self.d_y, self.d_w, self.w_stride) if self.response is None
+            else ('lse', 'propagate', None, None, 0))
         if pm is not None and pm.affine:
             name = "blsq_model_eval_tie_dev"
         elif gm is not None:
             name = "blsq_model_eval_global_dev"
-        elif self.nan_policy != 'propagate':
+        elif nan_policy != 'propagate':
             name = "blsq_model_eval_nan_dev"
         elif self.binned:
             name = "blsq_model_eval_bin_dev"
-        elif self.estimator != 'lse':
+        elif estimator != 'lse':
             name = "blsq_model_eval_est_dev"
         elif comp:                                            # with or without a map
             name = "blsq_model_eval_comp_dev"
@@ -1025,15 +1134,15 @@ class DeviceModel:
         def host(a, ptr_type=_abi.c_int32_p):
             return None if a is None else a.ctypes.data_as(ptr_type)
         values = dict(
-            est=ESTIMATORS.index(self.estimator), sampling=SAMPLING.index('bin' if self.binned else 'point'),
-            nan_policy=NAN_POLICIES.index(self.nan_policy), model=-1 if comp else M.id,
+            est=ESTIMATORS.index(estimator), sampling=SAMPLING.index('bin' if self.binned else 'point'),
+            nan_policy=NAN_POLICIES.index(nan_policy), model=-1 if comp else M.id,
             ncomp=len(M.components) if comp else 0, fam=host(M.fam_ids) if comp else None,
             cnt=host(M.counts) if comp else None,
             S=0 if gm is None else gm.S, shared=host(shared), t_sstride=self.t_sstride,       # S == 0: a plain batch
             B=self.B, reps=1, m=m, n=self.n_model,
             nf=self.n if gm is None else gm.nf, pmap=host(pmap),                              # nf: per data set
             tie_ratio=host(ratio, _abi.c_double_p), tie_offset=host(offset, _abi.c_double_p),
-            t=self.d_t, t_stride=self.t_stride, y=self.d_y, w=self.d_w, w_stride=self.w_stride, X=None,
+            t=self.d_t, t_stride=self.t_stride, y=d_y, w=d_w, w_stride=w_stride, X=None,
             Pfix=self.d_Pfix, f=None, J=None, mask=None)
         # strict: the entry chosen above has a slot for everything this fit sets, or this raises
         a, ctx = _abi.model_eval_args(name, values), self.ctx
@@ -1046,6 +1155,45 @@ class DeviceModel:
             a[at_J] = J_ptr
             a[at_mask] = mask_ptr
             ctx.check(getattr(ctx.lib, name)(ctx.h, *a), name)
+        self._eval = _eval
+
+    def _bind_response(self):
+        """The second stage: h uploaded once, the scratch buffers g (grown to the largest `reps` seen) and G (B m n
+        doubles, n the solver width; allocated by the first analytic Jacobian), and `self._eval` replaced by the pair of
+        launches.  Both go onto the context's stream, so nothing synchronises in between."""
+        ctx, inner, h = self.ctx, self._eval, self.response
+        B, m, n = self.B, self.m, self.n
+        L = h.shape[-1]
+        d_h = self._upload(h)
+        poisson = self.estimator == 'poisson'
+        head = [ESTIMATORS.index(self.estimator), NAN_POLICIES.index(self.nan_policy), B]
+        tail = [self.d_y, self.d_w, self.w_stride]
+        self._g, self._g_reps, self._G = None, 0, None
+
+        def scratch_g(reps):
+            if reps > self._g_reps:                           # (blsq_dev_free waits for the work that reads the old one)
+                if self._g is not None:
+                    self._bufs.remove(self._g)
+                    ctx.free(self._g)
+                self._g = ctx.malloc(8 * B * reps * m)
+                self._bufs.append(self._g)
+                self._g_reps = reps
+            return self._g
+
+        def _eval(x_ptr, reps, f_ptr, J_ptr, mask_ptr):
+            reps = int(reps)
+            g = G = None
+            if f_ptr is not None or poisson:                  # (c of the Poisson Jacobian is a function of mu)
+                g = scratch_g(reps)
+            if J_ptr is not None:
+                if self._G is None:
+                    self._G = ctx.malloc(8 * B * m * n)
+                    self._bufs.append(self._G)
+                G = self._G
+            inner(x_ptr, reps, g, G, mask_ptr)
+            ctx.check(ctx.lib.blsq_response_apply_dev(ctx.h, *head, reps, m, n, L, self.response_origin, d_h,
+                                                      L if h.ndim == 2 else 0, g, G, *tail, f_ptr, J_ptr, mask_ptr),
+                      "blsq_response_apply_dev")
         self._eval = _eval
 
     def fun_dev(self, x_ptr, f_ptr, reps=1):
@@ -1075,15 +1223,24 @@ class DeviceFit:
     ``n`` is the number of solver variables (the width of x0): the model's n, or nf of `param_map`; ``n_model`` is the
     model's number of parameters.  ``estimator='poisson'``, ``binned=True`` and ``nan_policy='omit'``: as
     ``DeviceModel``.  ``global_map=``: as ``DeviceModel``; `ydata` is (G, S, m), and ``B`` is G, ``m`` is S m and ``n``
-    is nv."""
+    is nv.  ``response=``, ``response_origin=``: as ``DeviceModel`` (checked here, before any GPU is touched)."""
 
     def __init__(self, name, n, xdata, ydata, sigma=None, param_map=None, Pfix=None, estimator='lse', binned=False,
-                 nan_policy='propagate', global_map=None):
+                 nan_policy='propagate', global_map=None, response=None, response_origin=0):
         self.model = resolve(name)
         self.model.terms(n)
         gm = self.global_map = global_map
         if gm is not None:
             check_global(self.model, binned, param_map)
+        self.response, self.response_origin = None, 0
+        if response is not None:
+            check_response_model(self.model, 0, 0, None, False, gm)
+            shape = np.shape(ydata)
+            if len(shape) != 2:
+                raise ValueError("`ydata` must have shape (B, m).")
+            self.response, self.response_origin = check_response(response, response_origin, shape[0])
+            check_response_model(self.model, shape[0], shape[1], xdata, binned, gm)
+            self._xdata_given = xdata            # (contiguous edges stay recognisable to the DeviceModel's own check)
         self.binned = bool(binned)
         self.estimator = check_estimator(estimator)
         self.nan_policy = check_nan_policy(nan_policy)
@@ -1115,18 +1272,22 @@ class DeviceFit:
         self.sigma = sigma
 
     def open_device(self, ctx, lb, ub):
-        dm = DeviceModel(ctx, self.model.name, self.B, self._m_set, self.n_model, self.xdata, self.ydata, self.sigma,
-                         self.param_map, self.Pfix, self.estimator, self.binned, self.nan_policy, self.global_map)
+        xdata = self.xdata if self.response is None else self._xdata_given
+        dm = DeviceModel(ctx, self.model.name, self.B, self._m_set, self.n_model, xdata, self.ydata, self.sigma,
+                         self.param_map, self.Pfix, self.estimator, self.binned, self.nan_policy, self.global_map,
+                         **({} if self.response is None
+                            else {'response': self.response, 'response_origin': self.response_origin}))
         dm.set_bounds(lb, ub)
         return dm
 
 
-def evaluate(name, xdata, P, ctx=None, binned=False):
+def evaluate(name, xdata, P, ctx=None, binned=False, response=None, response_origin=0):
     """Predictions ``model(xdata; P[b])`` of shape (B, m), computed on the GPU (the kernel with y = NULL, w = NULL).
     P: (B, n); xdata: (m,) / (B, m), or (2, m) / (B, 2, m) for 'gauss2d'.  `name`: a name, a composite spec or a
     ``CompositeModel``.  ``binned=True``: the bin contents of the bin-integrated model; `xdata` is then the m + 1
     contiguous edges (1-D) or rows (2, m) / (B, 2, m) — (4, m) / (B, 4, m) for 'gauss2d' — as ``BinnedModel.f`` takes
-    them."""
+    them.  ``response=`` (L,) or (B, L) with ``response_origin=``: the prediction convolved with the kernel, over the
+    sample index (``apply_response``): what a fit with the same keywords compares with its data."""
     model = resolve(name)
     P = np.ascontiguousarray(P, dtype=np.float64)
     if P.ndim != 2:
@@ -1137,6 +1298,7 @@ def evaluate(name, xdata, P, ctx=None, binned=False):
     if x.ndim < 1 or x.shape[-1] == 0:
         raise ValueError("`xdata` must not be empty.")
     m = x.shape[-1]
+    edges = x                                    # (contiguous edges as given: what a response needs to see)
     if binned:
         if x.ndim == 1 and model.coords == 1:
             x = bin_rows(x)
@@ -1144,11 +1306,17 @@ def evaluate(name, xdata, P, ctx=None, binned=False):
         BinnedModel(model).check_xdata(x, B, m)
     else:
         model.check_xdata(x, B, m)
+    resp = {}
+    if response is not None:
+        h, origin = check_response(response, response_origin, B)
+        check_response_model(model, B, m, edges, binned)
+        resp = {'response': h, 'response_origin': origin}
+        x = edges
     own = ctx is None
     if own:
         ctx = _abi.Context(0)
     try:
-        with DeviceModel(ctx, model.name, B, m, n, x, **({'binned': True} if binned else {})) as dm:
+        with DeviceModel(ctx, model.name, B, m, n, x, **({'binned': True} if binned else {}), **resp) as dm:
             d_P = ctx.to_device(P)
             d_f = ctx.malloc(8 * B * m)
             try:

@@ -673,6 +673,28 @@ struct LinearEvalCall {
 // the kernels' offsets in bounds.
 hipError_t launch_linear_eval(const LinearEvalCall& c, hipStream_t s);
 
+// ------------------------------------------------- instrument response (7s) ----
+// One call of response_kernels.hip (blsq_response_apply_dev): the raw model values g [B * reps][m] and / or the raw
+// Jacobian G [B][m][nc] convolved with the kernel h along the rows, then the epilogue of a model evaluation: f [B * reps][m]
+// and / or J [B][m][nc] (reps == 1; problems with mask[b] == 0 are neither read nor written; f takes no mask).
+struct ResponseCall {
+  int est, nan_policy;    // BLSQ_EST_*, BLSQ_NAN_*
+  int B, reps, m, nc, L, origin;
+  const double* h; long h_stride;   // [L] (stride 0: one kernel for all problems) or [B][L] (stride L)
+  const double* g;        // needed for f, and for J under the Poisson estimator (c is a function of mu)
+  const double* G;        // needed for J
+  const double* y;        // [B][m] or nullptr (0)
+  const double* w; long w_stride;   // nullptr (1), or stride 0 / m
+  double* f;
+  double* J;
+  const int* mask;        // nullptr or [B]
+};
+// hipErrorInvalidValue, and nothing launched, for an unknown flag, a size below 1, L above BLSQ_RESPONSE_MAX_L, an origin
+// outside [0, L), a stride other than the two its array has, a missing h, g or G, no output, J with reps != 1, the
+// Poisson estimator or OMIT without y, the Poisson estimator with w, or a batch the grid cannot hold: the refusals that
+// keep the kernel's offsets in bounds.
+hipError_t launch_response_apply(const ResponseCall& c, hipStream_t s);
+
 // ---------------------------------------------------------------- probes ----
 // probe_kernels.hip: measured peaks / counter calibration (blsq_debug_probe)
 hipError_t launch_mfma_probe(int waves_per_simd, int iters, double* sink, long* n_mfma,

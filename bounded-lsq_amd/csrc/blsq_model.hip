@@ -1,5 +1,5 @@
 // Built-in fit models (include/blsq.h; kernel: model_kernels.hip): the model and term tables behind
-// blsq_model_count / _info and blsq_term_count / _info, and the eight entries blsq_model_eval_dev, _map_dev, _comp_dev,
+// blsq_model_count / _info and blsq_term_count / _info, the entries blsq_linear_eval_dev and blsq_response_apply_dev, and the eight entries blsq_model_eval_dev, _map_dev, _comp_dev,
 // _est_dev, _bin_dev, _nan_dev, _global_dev and _tie_dev.  An entry fills a ModelEvalCall from its arguments (what its signature
 // does not have is the default) and hands it to model_eval_checked with its EvalEntry: one list of checks, one launcher, and per entry
 // only the argument numbers.
@@ -293,4 +293,38 @@ extern "C" int blsq_linear_eval_dev(blsq_ctx* ctx, int B, int reps, int m, int n
   HIPCHK(ctx, hipSetDevice(ctx->device));
   const LinearEvalCall c{B, reps, m, n, dA, A_stride, dy, dw, w_stride, dX, df, dJ, dmask};
   return ctx->run(K_MODEL_EVAL, "launch_linear_eval", [&] { return launch_linear_eval(c, ctx->stream); });
+}
+
+// Instrument response (response_kernels.hip): the convolution of raw model values and of a raw Jacobian
+// with a measured kernel, and the epilogue of a model evaluation behind it.  The checks in the order of the arguments,
+// then the launches (f, then J) as one timed call in the slot of the model evaluations.
+extern "C" int blsq_response_apply_dev(blsq_ctx* ctx, int est, int nan_policy, int B, int reps, int m, int nc, int L,
+                                       int origin, const double* dh, long h_stride, const double* dg, const double* dG,
+                                       const double* dy, const double* dw, long w_stride, double* df, double* dJ,
+                                       const int32_t* dmask) {
+  if (!ctx) return -1;
+  if (est != BLSQ_EST_LSE && est != BLSQ_EST_POISSON) return ctx->bad(2, "est must be one of BLSQ_EST_*");
+  if (nan_policy != BLSQ_NAN_PROPAGATE && nan_policy != BLSQ_NAN_OMIT)
+    return ctx->bad(3, "nan_policy must be one of BLSQ_NAN_*");
+  if (B <= 0) return ctx->bad(4, "B must be positive");
+  if (reps <= 0) return ctx->bad(5, "reps must be positive");
+  if (m <= 0 || m > BLSQ_RESPONSE_MAX_M) return ctx->bad(6, "m must be in 1 .. BLSQ_RESPONSE_MAX_M");
+  if (nc <= 0) return ctx->bad(7, "nc must be positive");
+  if (L < 1 || L > BLSQ_RESPONSE_MAX_L) return ctx->bad(8, "L must be in 1 .. BLSQ_RESPONSE_MAX_L");
+  if (origin < 0 || origin >= L) return ctx->bad(9, "origin must be in 0 .. L - 1");
+  if (!dh) return ctx->bad(10, "h is NULL (the kernel)");
+  if (h_stride != 0 && h_stride != (long)L) return ctx->bad(11, "h_stride must be 0 or L");
+  if (!dg && df) return ctx->bad(12, "g is NULL although f is asked for");
+  if (!dg && dJ && est == BLSQ_EST_POISSON)
+    return ctx->bad(12, "g is NULL: the Jacobian of the Poisson estimator needs the model values");
+  if (!dG && dJ) return ctx->bad(13, "G is NULL although J is asked for");
+  if (est == BLSQ_EST_POISSON && !dy) return ctx->bad(14, "y is NULL: the Poisson estimator needs the counts");
+  if (nan_policy == BLSQ_NAN_OMIT && !dy) return ctx->bad(14, "y is NULL: BLSQ_NAN_OMIT reads the missing points from it");
+  if (est == BLSQ_EST_POISSON && dw) return ctx->bad(15, "w must be NULL with the Poisson estimator");
+  if (dw && w_stride != 0 && w_stride != (long)m) return ctx->bad(16, "w_stride must be 0 or m");
+  if (!df && !dJ) return ctx->bad(17, "f and J are both NULL");
+  if (dJ && reps != 1) return ctx->bad(18, "J requires reps == 1");
+  HIPCHK(ctx, hipSetDevice(ctx->device));
+  const ResponseCall c{est, nan_policy, B, reps, m, nc, L, origin, dh, h_stride, dg, dG, dy, dw, w_stride, df, dJ, dmask};
+  return ctx->run(K_MODEL_EVAL, "launch_response_apply", [&] { return launch_response_apply(c, ctx->stream); });
 }

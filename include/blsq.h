@@ -609,6 +609,36 @@ int blsq_linear_eval_dev(blsq_ctx* ctx, int B, int reps, int m, int n, const dou
                          const double* dy, const double* dw, long w_stride, const double* dX, double* df, double* dJ,
                          const int32_t* dmask);
 
+/* ---- instrument response: a model convolved with a measured kernel -----------------------------------
+ * The second stage of a fit whose model passes through an instrument before it meets the data (a decay through the
+ * response of a detector, a line through the resolution of a spectrometer).  The first stage is any blsq_model_eval*_dev
+ * entry called with y = NULL, w = NULL, no estimator and no omission: it writes the raw model values dg [B * reps][m]
+ * and the raw Jacobian dG [B][m][nc] (nc: n, or nf of a map).  This entry convolves both along the rows,
+ *   mu[q][i]    = sum_{k < L} h[b][k] * g[q][i + origin - k]               q = b * reps + r, r < reps
+ *   HG[b][i][j] = sum_{k < L} h[b][k] * G[b][i + origin - k][j]
+ * where a term whose index i + origin - k lies outside [0, m) is dropped (zeros past both ends; origin 0: the causal
+ * convolution, origin L / 2 with odd L: a centred kernel), and applies what the first stage was not given:
+ *   BLSQ_EST_LSE:      f = w (mu - y),  J = w HG            (dy NULL: 0; dw NULL: 1)
+ *   BLSQ_EST_POISSON:  (r, c) of the deviance residual at (mu, y):  f = r,  J = c HG   (dy required, dw must be NULL;
+ *                      dg is then needed for J as well)
+ *   BLSQ_NAN_OMIT:     f and the row of J are +0.0 where y is NaN (dy required); the model is still evaluated there
+ * into df [B * reps][m] and / or dJ [B][m][nc] (reps must be 1).  dh: [L] shared by all problems (h_stride 0) or [B][L]
+ * (h_stride L); dw: NULL, [m] (w_stride 0) or [B][m] (w_stride m); dmask: int32 [B] or NULL: dJ[b] of a problem with
+ * dmask[b] == 0 is not touched and nothing of the problem is read (f takes no mask).  The convolution is over the
+ * sample index: a uniform grid, and h sampled at its spacing, are the caller's business.  The sum of row i takes its
+ * taps in ascending k, the first as a product and the others by fma(): a function of (L, origin, i, m) alone, not of B,
+ * reps, nc, the strides or the batch mates; with h = [1.0] the stage is the identity in every bit.  Nothing is checked
+ * on the device.  1 <= L <= BLSQ_RESPONSE_MAX_L, 0 <= origin < L, 1 <= m <= BLSQ_RESPONSE_MAX_M, nc >= 1 (L may exceed
+ * m).  All pointers are device pointers; asynchronous on the ctx stream; f and J of one call are one unit of the
+ * `model_eval` slot.  A negative return is the index of the bad argument (ctx = 1, est = 2, nan_policy = 3, B = 4,
+ * reps = 5, m = 6, nc = 7, L = 8, origin = 9, h = 10, h_stride = 11, g = 12, G = 13, y = 14, w = 15, w_stride = 16,
+ * f = 17: f and J both NULL, J = 18: reps != 1, mask); nothing is launched then. */
+#define BLSQ_RESPONSE_MAX_L 1024
+#define BLSQ_RESPONSE_MAX_M 0x7fff0000
+int blsq_response_apply_dev(blsq_ctx* ctx, int est, int nan_policy, int B, int reps, int m, int nc, int L, int origin,
+                            const double* dh, long h_stride, const double* dg, const double* dG, const double* dy,
+                            const double* dw, long w_stride, double* df, double* dJ, const int32_t* dmask);
+
 /* ---- parameter covariance from the final Jacobian --------------------------------------------------------------
  * The reference documents `x_covariance` as the inverse of J^T J at the solution (least_squares.py:248-252) and fills
  * it only through its MINPACK bridge (method='lm').  Here, per problem, from a Householder triangle R of J (the TSQR

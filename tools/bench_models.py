@@ -41,9 +41,17 @@ fit on the device route (blsq_model_eval_global_dev) against the callable route 
 kernel time per slot, and `gram_share`, the part of it spent in the slots whose name holds 'gram': the measured case
 for or against a structured solve.  With ``--kernel``: the launches of the global entry alone, f and J.
 
+``--response L`` fits through an instrument response: the lines are convolved with a Gaussian kernel of L
+taps (sigma L / 10 channels, centred at tap L / 3, sum 1, origin 0) before the noise is added.  Three routes are timed,
+alternating: `named`, the spec on the device with ``response=`` (the model kernel, then blsq_response_apply_dev);
+`plain`, the same route on unconvolved data without the keyword (what the second stage adds to a fit); `callable`, the
+numpy functions with ``response=`` (``models.response_residual`` / ``response_jacobian`` on the host).  With ``--kernel``:
+the response entry alone on random buffers of `--B` problems, `--m` rows and `--n` columns, f and J per launch in the
+'model_eval' slot, and the bytes per second of J (G read, J written: 16 B m n bytes).
+
 usage: python tools/bench_models.py [--B 4096] [--m 64] [--repeat 5] [--peaks 1] [--fixed 1,4] [--tied 5:2,4:1:1:0.42] [--kernel]
                                     [--launches 50] [--rounds 1] [--estimator lse] [--binned] [--omit FRACTION]
-                                    [--global S --shared 1,2]
+                                    [--global S --shared 1,2] [--response L [--n 4]]
 """
 import argparse
 import json
@@ -221,6 +229,86 @@ def global_bench(a, ctx):
     return res
 
 
+def response_kernel(L):
+    h = np.exp(-0.5 * ((np.arange(L) - L / 3.0) / max(L / 10.0, 0.5)) ** 2)
+    return h / h.sum()
+
+
+def response_bench(a, ctx):
+    """--response L: whole fits through the response against the plain fit and the callable route; with --kernel the
+    launches of blsq_response_apply_dev alone."""
+    B, m, L = a.B, a.m, a.response
+    h = response_kernel(L)
+    res = {"B": B, "m": m, "L": L, "origin": 0}
+    if a.kernel:
+        nc = a.n
+        rng = np.random.default_rng(0)
+        d_g, d_G = ctx.to_device(rng.standard_normal((B, m))), ctx.to_device(rng.standard_normal((B, m, nc)))
+        d_y, d_w, d_h = ctx.to_device(rng.standard_normal((B, m))), ctx.to_device(rng.uniform(0.5, 2, m)), ctx.to_device(h)
+        d_f, d_J = ctx.malloc(8 * B * m), ctx.malloc(8 * B * m * nc)
+
+        def call(f, J):
+            ctx.check(ctx.lib.blsq_response_apply_dev(ctx.h, 0, 0, B, 1, m, nc, L, 0, d_h, 0, d_g, d_G, d_y, d_w, 0, f, J,
+                                                      None), "blsq_response_apply_dev")
+        res.update({"n": nc, "launches": a.launches, "rounds": a.rounds, "J_bytes": 16 * B * m * nc})
+        for what, run in (("f", lambda: call(d_f, None)), ("J", lambda: call(None, d_J))):
+            run()
+            ctx.sync()
+            per_round = []
+            for _ in range(a.rounds):
+                ctx.timing(True, only="model_eval")
+                ctx.timing_reset()
+                for _ in range(a.launches):
+                    run()
+                ctx.sync()
+                ms, cnt = ctx.timing_read()["model_eval"]
+                ctx.timing(False)
+                per_round.append(round(1e3 * ms / cnt, 2))
+            res["response_%s_us" % what] = round(float(np.median(per_round)), 2)
+            res["response_%s_us_all" % what] = per_round
+        res["J_TB_per_s"] = round(res["J_bytes"] / (res["response_J_us"] * 1e-6) / 1e12, 3)
+        res["J_gflops"] = round(2.0 * B * m * nc * L / (res["response_J_us"] * 1e-6) / 1e9, 1)
+        for p in (d_g, d_G, d_y, d_w, d_h, d_f, d_J):
+            ctx.free(p)
+        return res
+    x, Y_plain, P0, bounds = problems(B, m, peaks=a.peaks)
+    rng = np.random.default_rng(1)
+    M = models.get("gauss_sum")
+    truth = (bounds[0] + bounds[1]) / 2                                    # (the box of `problems` is centred on it)
+    Y = models.apply_response(M.f(x, truth), h, 0) + 0.01 * rng.standard_normal((B, m))
+    kw = dict(sigma=0.01, bounds=bounds, driver="device", ctx=ctx, ftol=1e-10, xtol=1e-10, gtol=1e-10)
+    routes = {"named": lambda: curve_fit_batch("gauss_sum", x, Y, P0, response=h, **kw),
+              "plain": lambda: curve_fit_batch("gauss_sum", x, Y_plain, P0, **kw),
+              "callable": lambda: curve_fit_batch(M.f, x, Y, P0, jac=M.jac, response=h, **kw)}
+    times = {k: [] for k in routes}
+    out = {k: run() for k, run in routes.items()}                         # warm-up: code objects, plans
+    for _ in range(a.repeat):
+        for k, run in routes.items():
+            ctx.sync()
+            t0 = time.perf_counter()
+            run()
+            times[k].append(time.perf_counter() - t0)
+    ctx.timing(True, only="model_eval")
+    ctx.timing_reset()
+    routes["named"]()
+    ctx.sync()
+    k_ms, k_n = ctx.timing_read()["model_eval"]
+    ctx.timing(False)
+    both = np.array([ra.success and rb.success for ra, rb in zip(out["named"][2], out["callable"][2])])
+    med = {k: float(np.median(v)) for k, v in times.items()}
+    res.update({"model": "gauss_sum", "n": P0.shape[1],
+                **{k + "_s": round(v, 4) for k, v in med.items()},
+                **{k + "_all_s": [round(t, 4) for t in v] for k, v in times.items()},
+                "named_over_plain": round(med["named"] / med["plain"], 3),
+                "speedup_over_callable": round(med["callable"] / med["named"], 2),
+                "model_eval_ms_per_fit": round(k_ms, 3), "model_eval_units_per_fit": int(k_n),
+                "converged": {k: int(sum(r.success for r in out[k][2])) for k in routes},
+                "nfev": {k: int(max(r.nfev for r in out[k][2])) for k in routes},
+                "popt_max_rel_diff": float(np.max(np.abs(out["named"][0][both] - out["callable"][0][both])
+                                                  / (np.abs(out["callable"][0][both]) + 1e-3)))})
+    return res
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--B", type=int, default=4096)
@@ -239,7 +327,19 @@ def main():
     ap.add_argument("--global", dest="global_S", type=int, default=0, metavar="S",
                     help="global fits: B // S groups of S data sets (needs --shared)")
     ap.add_argument("--shared", default="", help="with --global: the parameters common to a group, e.g. 1,2")
+    ap.add_argument("--response", type=int, default=0, metavar="L",
+                    help="fit through an instrument response of L taps (with --kernel: the response entry alone)")
+    ap.add_argument("--n", type=int, default=4, help="with --response --kernel: the columns of G and J")
     a = ap.parse_args()
+    if a.response:
+        if (not 1 <= a.response <= models.RESPONSE_MAX_L or a.global_S or a.fixed or a.tied or a.binned
+                or a.omit is not None or a.estimator != "lse"):
+            ap.error("--response L takes 1 <= L <= %d, without the other switches" % models.RESPONSE_MAX_L)
+        ctx = _abi.Context(0)
+        res = response_bench(a, ctx)
+        ctx.close()
+        print(json.dumps(res))
+        return
     if a.global_S:
         if a.global_S < 1 or not a.shared or a.fixed or a.tied or a.binned or a.omit is not None:
             ap.error("--global S takes S >= 1 and --shared i,j, without --fixed, --tied, --binned and --omit")
