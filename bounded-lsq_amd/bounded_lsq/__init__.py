@@ -16,6 +16,8 @@ from ._cov import covariance  # noqa: F401
 from ._leverage import leverage, prediction_variance, influence  # noqa: F401
 from ._curve_fit import curve_fit, curve_fit_batch, curve_fit_global  # noqa: F401
 from ._linear import lsq_linear, lsq_linear_batch, LinearFit, LinearDeviceModel  # noqa: F401
+from ._bvls import (bvls, bvls_batch, nnls_batch, bvls_gram_batch, bvls_reference,  # noqa: F401
+                    BvlsResult)
 from . import _models as models  # noqa: F401
 from ._params import ParamMap, GlobalMap  # noqa: F401
 from ._hostmath import (active_mask as find_active_constraints,  # noqa: F401
@@ -26,4 +28,5 @@ __all__ = ['dogbox', 'trf', 'find_active_constraints', 'CL_optimality', 'prepare
            'make_strictly_feasible', 'least_squares', 'least_squares_batch', 'TrfStepSolver', 'DogboxStepSolver',
            'OuterDriver', 'covariance', 'curve_fit', 'curve_fit_batch', 'leverage', 'prediction_variance',
            'influence', 'models', 'ParamMap', 'GlobalMap', 'curve_fit_global', 'lsq_linear', 'lsq_linear_batch',
-           'LinearFit', 'LinearDeviceModel']
+           'LinearFit', 'LinearDeviceModel', 'bvls', 'bvls_batch', 'nnls_batch', 'bvls_gram_batch', 'bvls_reference',
+           'BvlsResult']

@@ -180,6 +180,12 @@ SIGNATURES = {
     "blsq_linear_eval_dev": (C.c_int, [vp] + [C.c_int] * 4 + [vp, C.c_long, vp, vp, C.c_long, vp, vp, vp, vp]),
     # ctx, est, nan_policy, B, reps, m, nc, L, origin, h, h_stride, g, G, y, w, w_stride, f, J, mask
     "blsq_response_apply_dev": (C.c_int, [vp] + [C.c_int] * 8 + [vp, C.c_long, vp, vp, vp, vp, C.c_long, vp, vp, vp]),
+    # ctx, B, m, n, A, A_stride, y, w, w_stride, G, G_stride, c
+    "blsq_bvls_moments_dev": (C.c_int, [vp] + [C.c_int] * 3 + [vp, C.c_long, vp, vp, C.c_long, vp, C.c_long, vp]),
+    # ctx, B, m, n, G, G_stride, c, lb, ub, tol, max_pass, A, A_stride, y, w, w_stride, x, on_bound, fun, grad,
+    # optimality, stat
+    "blsq_bvls_solve_dev": (C.c_int, [vp] + [C.c_int] * 3 + [vp, C.c_long, vp, vp, vp, C.c_double, C.c_int, vp, C.c_long,
+                                             vp, vp, C.c_long] + [vp] * 6),
 }
 SIGNATURES.update((name, (C.c_int, [vp] + [MODEL_EVAL_TYPES[k] for k in args]))
                   for name, args in MODEL_EVAL_ARGS.items())

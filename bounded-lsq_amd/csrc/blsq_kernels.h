@@ -695,6 +695,42 @@ struct ResponseCall {
 // keep the kernel's offsets in bounds.
 hipError_t launch_response_apply(const ResponseCall& c, hipStream_t s);
 
+// ------------------------------------------------------- BVLS / NNLS (7t) ----
+// bvls_kernels.hip.  The moments G = A^T W^2 A and c = A^T W^2 y of a batch (blsq_bvls_moments_dev) ...
+struct BvlsMomentsCall {
+  int B, m, n;
+  const double* A; long A_stride;   // row-major [m][n]; stride 0 (one matrix for all problems) or m n
+  const double* y;        // [B][m]
+  const double* w; long w_stride;   // nullptr (1), or stride 0 / m
+  double* G; long G_stride;         // [n][n] (stride 0: A shared and w not per problem) or [B][n][n] (stride n n)
+  double* c;              // [B][n]
+};
+// ... and the whole active-set solve of every problem, one workgroup each (blsq_bvls_solve_dev)
+struct BvlsSolveCall {
+  int B, m, n;
+  const double* G; long G_stride;
+  const double* c;
+  const double* lb;       // [B][n]
+  const double* ub;
+  double tol;
+  int max_pass;
+  const double* A; long A_stride;   // nullptr: (G, c) alone; m, y, w and fun are then unused
+  const double* y;
+  const double* w; long w_stride;
+  double* x;              // [B][n]
+  int* on_bound;          // [B][n]
+  double* fun;            // [B][m] or nullptr
+  double* grad;           // [B][n]
+  double* opt;            // [B][2]: optimality, cost
+  int* stat;              // [B][3]: status, release passes, factorisations
+};
+// hipErrorInvalidValue, and nothing launched, for a size below 1, n above BLSQ_BVLS_MAX_N, a stride other than the two
+// its array has, one G for per-problem A or w, a missing pointer, fun without A, a negative max_pass, or a batch the
+// grid cannot hold: the refusals that keep the kernels' offsets in bounds.
+hipError_t launch_bvls_moments(const BvlsMomentsCall& c, hipStream_t s);
+hipError_t launch_bvls_solve(const BvlsSolveCall& c, hipStream_t s);
+size_t bvls_solve_lds_bytes(int n);   // dynamic LDS of one problem
+
 // ---------------------------------------------------------------- probes ----
 // probe_kernels.hip: measured peaks / counter calibration (blsq_debug_probe)
 hipError_t launch_mfma_probe(int waves_per_simd, int iters, double* sink, long* n_mfma,

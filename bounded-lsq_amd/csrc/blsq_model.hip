@@ -1,5 +1,5 @@
 // Built-in fit models (include/blsq.h; kernel: model_kernels.hip): the model and term tables behind
-// blsq_model_count / _info and blsq_term_count / _info, the entries blsq_linear_eval_dev and blsq_response_apply_dev, and the eight entries blsq_model_eval_dev, _map_dev, _comp_dev,
+// blsq_model_count / _info and blsq_term_count / _info, the entries blsq_linear_eval_dev, blsq_bvls_moments_dev, blsq_bvls_solve_dev and blsq_response_apply_dev, and the eight entries blsq_model_eval_dev, _map_dev, _comp_dev,
 // _est_dev, _bin_dev, _nan_dev, _global_dev and _tie_dev.  An entry fills a ModelEvalCall from its arguments (what its signature
 // does not have is the default) and hands it to model_eval_checked with its EvalEntry: one list of checks, one launcher, and per entry
 // only the argument numbers.
@@ -293,6 +293,63 @@ extern "C" int blsq_linear_eval_dev(blsq_ctx* ctx, int B, int reps, int m, int n
   HIPCHK(ctx, hipSetDevice(ctx->device));
   const LinearEvalCall c{B, reps, m, n, dA, A_stride, dy, dw, w_stride, dX, df, dJ, dmask};
   return ctx->run(K_MODEL_EVAL, "launch_linear_eval", [&] { return launch_linear_eval(c, ctx->stream); });
+}
+
+// BVLS / NNLS (bvls_kernels.hip): the moments of a batch, and the whole active-set solve of every problem
+// in one kernel.  The checks in the order of the arguments; each entry is one timed call in the slot of the model
+// evaluations.
+extern "C" int blsq_bvls_moments_dev(blsq_ctx* ctx, int B, int m, int n, const double* dA, long A_stride,
+                                     const double* dy, const double* dw, long w_stride, double* dG, long G_stride,
+                                     double* dc) {
+  if (!ctx) return -1;
+  if (B <= 0) return ctx->bad(2, "B must be positive");
+  if (m <= 0) return ctx->bad(3, "m must be positive");
+  if (n < 1 || n > BLSQ_BVLS_MAX_N) return ctx->bad(4, "n must be in 1 .. BLSQ_BVLS_MAX_N");
+  if (!dA) return ctx->bad(5, "A is NULL");
+  if (A_stride != 0 && A_stride != (long)m * n) return ctx->bad(6, "A_stride must be 0 or m * n");
+  if (!dy) return ctx->bad(7, "y is NULL");
+  if (w_stride != 0 && w_stride != (long)m) return ctx->bad(9, "w_stride must be 0 or m");
+  if (!dG) return ctx->bad(10, "G is NULL");
+  if (G_stride != 0 && G_stride != (long)n * n) return ctx->bad(11, "G_stride must be 0 or n * n");
+  if (G_stride == 0 && (A_stride != 0 || (dw && w_stride != 0)))
+    return ctx->bad(11, "G_stride must be n * n with a matrix or weights per problem");
+  if (!dc) return ctx->bad(12, "c is NULL");
+  HIPCHK(ctx, hipSetDevice(ctx->device));
+  const BvlsMomentsCall c{B, m, n, dA, A_stride, dy, dw, w_stride, dG, G_stride, dc};
+  return ctx->run(K_MODEL_EVAL, "launch_bvls_moments", [&] { return launch_bvls_moments(c, ctx->stream); });
+}
+
+extern "C" int blsq_bvls_solve_dev(blsq_ctx* ctx, int B, int m, int n, const double* dG, long G_stride,
+                                   const double* dc, const double* dlb, const double* dub, double tol, int max_pass,
+                                   const double* dA, long A_stride, const double* dy, const double* dw, long w_stride,
+                                   double* dx, int32_t* don_bound, double* dfun, double* dgrad, double* doptimality,
+                                   int32_t* dstat) {
+  if (!ctx) return -1;
+  if (B <= 0) return ctx->bad(2, "B must be positive");
+  if (dA ? m <= 0 : m < 0) return ctx->bad(3, "m must be positive (without A: not negative; it is not read)");
+  if (n < 1 || n > BLSQ_BVLS_MAX_N) return ctx->bad(4, "n must be in 1 .. BLSQ_BVLS_MAX_N");
+  if (!dG) return ctx->bad(5, "G is NULL");
+  if (G_stride != 0 && G_stride != (long)n * n) return ctx->bad(6, "G_stride must be 0 or n * n");
+  if (!dc) return ctx->bad(7, "c is NULL");
+  if (!dlb) return ctx->bad(8, "lb is NULL");
+  if (!dub) return ctx->bad(9, "ub is NULL");
+  if (tol != tol) return ctx->bad(10, "tol is not a number");
+  if (max_pass < 0) return ctx->bad(11, "max_pass must not be negative");
+  if (dA) {
+    if (A_stride != 0 && A_stride != (long)m * n) return ctx->bad(13, "A_stride must be 0 or m * n");
+    if (!dy) return ctx->bad(14, "y is NULL although A is given");
+    if (w_stride != 0 && w_stride != (long)m) return ctx->bad(16, "w_stride must be 0 or m");
+  }
+  if (!dx) return ctx->bad(17, "x is NULL");
+  if (!don_bound) return ctx->bad(18, "on_bound is NULL");
+  if (dfun && !dA) return ctx->bad(19, "fun must be NULL without A");
+  if (!dgrad) return ctx->bad(20, "grad is NULL");
+  if (!doptimality) return ctx->bad(21, "optimality is NULL");
+  if (!dstat) return ctx->bad(22, "stat is NULL");
+  HIPCHK(ctx, hipSetDevice(ctx->device));
+  const BvlsSolveCall c{B, m, n, dG, G_stride, dc, dlb, dub, tol, max_pass, dA, dA ? A_stride : 0, dA ? dy : nullptr,
+                        dA ? dw : nullptr, dA ? w_stride : 0, dx, don_bound, dfun, dgrad, doptimality, dstat};
+  return ctx->run(K_MODEL_EVAL, "launch_bvls_solve", [&] { return launch_bvls_solve(c, ctx->stream); });
 }
 
 // Instrument response (response_kernels.hip): the convolution of raw model values and of a raw Jacobian

@@ -639,6 +639,43 @@ int blsq_response_apply_dev(blsq_ctx* ctx, int est, int nan_policy, int B, int r
                             const double* dh, long h_stride, const double* dg, const double* dG, const double* dy,
                             const double* dw, long w_stride, double* df, double* dJ, const int32_t* dmask);
 
+/* ---- BVLS and NNLS: an exact active-set solver, a batch in two calls ---------------------------------
+ * min 1/2 |W (A x - y)|^2 with lb <= x <= ub is a strictly convex quadratic programme in the moments G = A^T W^2 A and
+ * c = A^T W^2 y.  blsq_bvls_moments_dev forms them; blsq_bvls_solve_dev runs the active-set iteration of Stark and
+ * Parker (Lawson and Hanson's NNLS for bounds (0, inf)) for every problem in a workgroup of its own, to the exact
+ * minimiser and the exact active set: a variable on a bound holds lb or ub bit for bit.  The first call launches one or
+ * two kernels (G and c apart for a shared A), the second one; no host round trip inside or between them.
+ *
+ * Moments.  dA: row-major [m][n], ONE matrix (A_stride 0) or [B][m][n] (A_stride m * n); dy: [B][m]; dw: NULL (1), [m]
+ * (w_stride 0) or [B][m] (w_stride m).  dG: [n][n] for the whole batch (G_stride 0; only with A_stride 0 and w not per
+ * problem) or [B][n][n] (G_stride n * n); dc: [B][n].  FP64 MFMA; the summation order is a function of m alone, a
+ * problem's c does not depend on its batch mates, and G is symmetric in every bit.
+ *
+ * Solve.  dG / G_stride / dc as above (G symmetric positive definite: both triangles are read); dlb, dub: [B][n],
+ * lb < ub, infinities allowed; a variable on a bound leaves it when the gradient pushes it inwards by more than tol;
+ * max_pass: the most release passes per problem.  Outputs: dx [B][n]; don_bound int32 [B][n] in {-1, 0, 1}; dgrad
+ * [B][n]; doptimality [B][2]: max(max over free |g_j|, max over bound g_j on_bound_j, 0), and the cost 1/2 sum fun^2
+ * (0 without A); dstat int32 [B][3]: status, release passes, factorisations.  Status 1: the optimality conditions hold;
+ * 0: max_pass passes used (a variable barred against cycling is asked again before 1 is returned); -1: a pivot of a free block was <= 0 or not finite, or a value was not finite (x is then the
+ * last feasible iterate).  Every loop on the device has a structural bound.
+ * dA == NULL: the solve on (G, c) alone: g = G x - c; m, dy, dw and the strides are not read and dfun must be NULL.
+ * dA != NULL (with dy, dw and the strides of the moments call): after the iteration x_F is corrected once against A,
+ * x_F += (G_FF)^-1 A_F^T W^2 (y - A x), and clamped; then dfun [B][m] = w (A x - y) (or NULL: not written) and
+ * g = A^T w fun come from A itself.  The status is that of the iteration.
+ * 1 <= n <= BLSQ_BVLS_MAX_N.  All pointers are device pointers; asynchronous on the ctx stream; each call is one unit of
+ * the `model_eval` slot.  A negative return is the index of the bad argument, checked in this order (moments: ctx = 1,
+ * B = 2, m = 3, n = 4, A = 5, A_stride = 6, y = 7, w, w_stride = 9, G = 10, G_stride = 11, c = 12; solve: ctx = 1,
+ * B = 2, m = 3, n = 4, G = 5, G_stride = 6, c = 7, lb = 8, ub = 9, tol = 10: not a number, max_pass = 11, A,
+ * A_stride = 13, y = 14, w, w_stride = 16, x = 17, on_bound = 18, fun = 19: given without A, grad = 20,
+ * optimality = 21, stat = 22); nothing is launched then. */
+#define BLSQ_BVLS_MAX_N 128
+int blsq_bvls_moments_dev(blsq_ctx* ctx, int B, int m, int n, const double* dA, long A_stride, const double* dy,
+                          const double* dw, long w_stride, double* dG, long G_stride, double* dc);
+int blsq_bvls_solve_dev(blsq_ctx* ctx, int B, int m, int n, const double* dG, long G_stride, const double* dc,
+                        const double* dlb, const double* dub, double tol, int max_pass, const double* dA,
+                        long A_stride, const double* dy, const double* dw, long w_stride, double* dx,
+                        int32_t* don_bound, double* dfun, double* dgrad, double* doptimality, int32_t* dstat);
+
 /* ---- parameter covariance from the final Jacobian --------------------------------------------------------------
  * The reference documents `x_covariance` as the inverse of J^T J at the solution (least_squares.py:248-252) and fills
  * it only through its MINPACK bridge (method='lm').  Here, per problem, from a Householder triangle R of J (the TSQR

@@ -11,6 +11,12 @@ GPU, same process, alternating; whole calls are timed (host clock around a call 
 'model_eval' slot, `--rounds` timed blocks (the figure is the median of the rounds' means), for a shared and for
 per-problem matrices on buffers of the same shapes.
 
+``--method bvls`` (bvls_kernels.hip) times ``bvls_batch`` on the same batch against
+``lsq_linear_batch`` with 'trf' and with 'dogbox' in one process (one block of repeats per route after its warm-up),
+and prints the release passes and the
+factorisations per problem as max and mean; with ``--kernel`` it times the moments launch and the solve launch
+separately instead (`--rounds` blocks of `--launches` launches each, the median of the blocks' means; no weights).
+
 usage: python tools/bench_linear.py [--B 4096] [--m 64] [--n 16] [--method trf] [--own] [--repeat 5]
                                     [--kernel] [--launches 200] [--rounds 5]
 """
@@ -24,7 +30,10 @@ import numpy as np
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "bounded-lsq_amd"))
-from bounded_lsq import lsq_linear_batch, least_squares_batch, LinearDeviceModel, _abi, _linear      # noqa: E402
+from bounded_lsq import (lsq_linear_batch, least_squares_batch, bvls_batch, LinearDeviceModel, _abi, _bvls,  # noqa: E402
+                         _linear)
+
+METHODS = _linear.METHODS + ('bvls',)           # of this tool: lsq_linear_batch itself does not take 'bvls'
 
 
 def problems(B, m, n, own, seed=0):
@@ -75,12 +84,93 @@ def kernel_times(ctx, A, b, launches, rounds):
     return out
 
 
+def bvls_kernel_times(ctx, A, b, lb, ub, launches, rounds):
+    """The moments launch and the solve launch of one ``bvls_batch`` (no weights), each alone in the 'model_eval' slot:
+    `rounds` timed blocks of `launches` launches after a warm-up, the median of the blocks' means, in ms."""
+    B, m = b.shape
+    n = A.shape[-1]
+    A_stride = m * n if A.ndim == 3 else 0
+    G_stride = n * n if A_stride else 0
+    need = _bvls._Buffers.need(A, b, lb, ub, 8 * n * n * (B if G_stride else 1), 8 * B * n,
+                               *_bvls._output_bytes(B, m, n, True))
+    with _bvls._Buffers(ctx, need) as buf:
+        d_A, d_y, d_lb, d_ub = buf.up(A), buf.up(b), buf.up(lb), buf.up(ub)
+        d_G, d_c = buf.new(8 * n * n * (B if G_stride else 1)), buf.new(8 * B * n)
+        d_x, d_on, d_fun, d_grad = buf.new(8 * B * n), buf.new(4 * B * n), buf.new(8 * B * m), buf.new(8 * B * n)
+        d_opt, d_stat = buf.new(16 * B), buf.new(12 * B)
+        calls = {"moments": lambda: ctx.check(ctx.lib.blsq_bvls_moments_dev(ctx.h, B, m, n, d_A, A_stride, d_y, None, 0,
+                                                                           d_G, G_stride, d_c), "moments"),
+                 "solve": lambda: ctx.check(ctx.lib.blsq_bvls_solve_dev(ctx.h, B, m, n, d_G, G_stride, d_c, d_lb, d_ub,
+                                                                       1e-10, 5 * n, d_A, A_stride, d_y, None, 0, d_x,
+                                                                       d_on, d_fun, d_grad, d_opt, d_stat), "solve")}
+        out = {}
+        for name, call in calls.items():
+            call()
+            ctx.sync()
+            ms_all = []
+            for _ in range(rounds):
+                ctx.timing(True, only="model_eval")
+                ctx.timing_reset()
+                for _ in range(launches):
+                    call()
+                ctx.sync()
+                ms, cnt = ctx.timing_read()["model_eval"]
+                ms_all.append(round(ms / cnt, 4))
+                ctx.timing(False)
+            out[name + "_ms"] = float(np.median(ms_all))
+            out[name + "_ms_all"] = ms_all
+        stat = ctx.to_host(d_stat, (B, 3), np.int32)
+    out["factorisations"] = int(stat[:, 2].sum())
+    out["factorisations_mean"] = round(float(stat[:, 2].mean()), 3)
+    # the chip's throughput: the solve launch over all factorisations of the batch (gradients and ratio tests included)
+    out["solve_ns_per_factorisation"] = round(1e6 * out["solve_ms"] / max(int(stat[:, 2].sum()), 1), 1)
+    return out
+
+
+def bvls_main(a, A, b, ctx, res):
+    lb, ub = np.zeros((a.B, a.n)), np.ones((a.B, a.n))
+    if a.kernel:
+        res.update(launches=a.launches, rounds=a.rounds)
+        res.update(bvls_kernel_times(ctx, A, b, lb, ub, a.launches, a.rounds))
+        return
+    tol = 1e-10
+    x0 = np.full((a.B, a.n), 0.5)
+    routes = {"bvls": lambda: bvls_batch(A, b, (lb, ub), tol=tol, ctx=ctx),
+              "trf": lambda: lsq_linear_batch(A, b, bounds=(lb, ub), method="trf", tol=tol, x0=x0, ctx=ctx),
+              "dogbox": lambda: lsq_linear_batch(A, b, bounds=(lb, ub), method="dogbox", tol=tol, x0=x0, ctx=ctx)}
+    times = {k: [] for k in routes}
+    out = {}
+    for k, run in routes.items():                                         # one block per route: a route's big device
+        out[k] = run()                                                    # buffers, released, slow the next allocations
+        for _ in range(a.repeat):                                         # of any route
+            ctx.sync()
+            t0 = time.perf_counter()
+            run()
+            times[k].append(time.perf_counter() - t0)
+    r = out["bvls"]
+    for k in routes:
+        res[k + "_s"] = round(float(np.median(times[k])), 4)
+        res[k + "_all_s"] = [round(t, 4) for t in times[k]]
+    X = {k: np.stack([q.x for q in out[k]]) for k in ("trf", "dogbox")}
+    res.update({"speedup_over_trf": round(res["trf_s"] / res["bvls_s"], 2),
+                "speedup_over_dogbox": round(res["dogbox_s"] / res["bvls_s"], 2),
+                "status": sorted(set(int(v) for v in r.status)),
+                "passes": {"max": int(r.nit.max()), "mean": round(float(r.nit.mean()), 3)},
+                "factorisations": {"max": int(r.nfact.max()), "mean": round(float(r.nfact.mean()), 3)},
+                "active_share": round(float(np.mean(r.active_mask != 0)), 3),
+                "max_optimality": float(r.optimality.max()),
+                "x_max_abs_diff": {k: float(np.max(np.abs(r.x - X[k]))) for k in X},
+                # cost of the other route less the cost here, over the problems: [min, max] (an exact minimiser: >= 0)
+                "cost_excess": {k: [float(f(np.array([q.cost for q in out[k]]) - r.cost)) for f in (np.min, np.max)]
+                                for k in X}})
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--B", type=int, default=4096)
     ap.add_argument("--m", type=int, default=64)
     ap.add_argument("--n", type=int, default=16)
-    ap.add_argument("--method", default="trf", choices=_linear.METHODS)
+    ap.add_argument("--method", default="trf", choices=METHODS)
     ap.add_argument("--own", action="store_true", help="one matrix per problem instead of one for all")
     ap.add_argument("--repeat", type=int, default=5)
     ap.add_argument("--kernel", action="store_true", help="time the kernel's launches alone")
@@ -90,6 +180,11 @@ def main():
     A, b = problems(a.B, a.m, a.n, a.own)
     ctx = _abi.Context(0)
     res = {"B": a.B, "m": a.m, "n": a.n, "shared": not a.own, "method": a.method}
+    if a.method == "bvls":
+        bvls_main(a, A, b, ctx, res)
+        ctx.close()
+        print(json.dumps(res))
+        return
     if a.kernel:
         res.update(launches=a.launches, rounds=a.rounds)
         res.update(kernel_times(ctx, A, b, a.launches, a.rounds))
