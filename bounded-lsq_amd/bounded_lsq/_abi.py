@@ -186,6 +186,12 @@ SIGNATURES = {
     # optimality, stat
     "blsq_bvls_solve_dev": (C.c_int, [vp] + [C.c_int] * 3 + [vp, C.c_long, vp, vp, vp, C.c_double, C.c_int, vp, C.c_long,
                                              vp, vp, C.c_long] + [vp] * 6),
+    # nops, ops, root, nconst, nf, npfix, ncoord (no ctx, no device)
+    "blsq_expr_check": (C.c_int, [C.c_int, C.POINTER(C.c_uint64), C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]),
+    # ctx, est, nan_policy, B, reps, m, nf, npfix, ncoord, nops, ops, root, nconst, consts, t, t_stride, y, w, w_stride,
+    # X, Pfix, f, J, mask (ops and consts on the host: not a row of MODEL_EVAL_ARGS)
+    "blsq_expr_eval_dev": (C.c_int, [vp] + [C.c_int] * 9 + [C.POINTER(C.c_uint64), C.c_int, C.c_int, c_double_p, vp,
+                                            C.c_long, vp, vp, C.c_long, vp, vp, vp, vp, vp]),
 }
 SIGNATURES.update((name, (C.c_int, [vp] + [MODEL_EVAL_TYPES[k] for k in args]))
                   for name, args in MODEL_EVAL_ARGS.items())

@@ -385,12 +385,15 @@ def _fit(lay, f, xdata, sigma, absolute_sigma, bounds, method, jac, driver, ctx,
     model = None
     if response is not None:                     # (curve_fit_batch alone passes one: `lead` is (B,))
         response, response_origin = _models.check_response(response, response_origin, problems)
-        _models.check_response_model(_models.resolve(f) if isinstance(f, (str, _models.CompositeModel)) else None,
-                                     problems, lay.m, xdata, binned)
-    if binned and not isinstance(f, (str, _models.CompositeModel)):
+        _models.check_response_model(
+            _models.resolve(f) if isinstance(f, (str, _models.CompositeModel, _models.ExprModel)) else None,
+            problems, lay.m, xdata, binned)
+    if binned and not isinstance(f, (str, _models.CompositeModel, _models.ExprModel)):
         raise ValueError("`binned=True` needs a built-in model (a name, a spec or a CompositeModel) as `f`: a callable "
                          "integrates itself over its bins.")
-    if isinstance(f, (str, _models.CompositeModel)):
+    if isinstance(f, _models.ExprModel):         # (before any GPU is touched)
+        _models.check_expr_model(f, binned, isinstance(mp, GlobalMap))
+    if isinstance(f, (str, _models.CompositeModel, _models.ExprModel)):
         model = _models.resolve(f)
         model.terms(n)
         host_model = _models.binned(model) if binned else model         # whose numpy functions driver='host' calls
@@ -443,7 +446,8 @@ def _fit(lay, f, xdata, sigma, absolute_sigma, bounds, method, jac, driver, ctx,
         f = _models.response_residual(f, response, response_origin)
 
     if on_device:
-        func = _models.DeviceFit(model.name, n, xdata if (binned and response is not None) else x_dev, ydata, sigma,
+        func = _models.DeviceFit(_models.resolvable(model), n, xdata if (binned and response is not None) else x_dev,
+                                 ydata, sigma,
                                  Pfix=None if mp is None else P0,
                                  **{'global_map' if isinstance(mp, GlobalMap) else 'param_map': mp},
                                  **({} if response is None
@@ -526,7 +530,10 @@ def curve_fit_batch(f, xdata, ydata, p0, sigma=None, absolute_sigma=False, bound
         built-in model (``bounded_lsq.models``: 'poly', 'exp_sum', 'gauss_sum', 'lorentz_sum', 'gauss2d'; n = p0.shape[1]
         fixes the number of terms) — or a composite: a spec such as 'gauss*2+lorentz+poly*2' (``models.compose``: a sum
         of gauss / lorentz / pvoigt / exp terms and polynomials, whose n the spec fixes) or a ``CompositeModel``,
-        treated exactly as a name.  A named model with driver='device' is evaluated on the GPU, residuals and
+        treated exactly as a name — or an ``ExprModel``: a formula of the caller's own, ``models.expression('a*exp(-t/tau)+c',
+        ('a', 'tau', 'c'))`` (DESIGN.md 7u: interpreted on the GPU by a kernel of its own, with the exact Jacobian;
+        `xdata` (C, m) or (B, C, m) for its C > 1 coordinates; every keyword below but ``binned=True``, which is a
+        ValueError with it).  A named model with driver='device' is evaluated on the GPU, residuals and
         Jacobians alike: between the start of the solve and its results only two counters per iteration leave the
         device.  With driver='host' the model's numpy functions are the callbacks.  `xdata` is then (m,) or (B, m)
         — (2, m) or (B, 2, m) for 'gauss2d'.  A wrong name, an n that does not fit the model or a wrong `xdata` shape

@@ -74,12 +74,19 @@ and h sampled at its spacing, are the caller's business.  ``response_residual`` 
 ``f(xdata, P)`` / ``jac(xdata, P)`` with it: the ``driver='host'`` route and the route of a callable.  On the device
 the convolution is a second stage behind the model kernel, which is called as ``evaluate`` calls it; data, weights,
 estimator and omission are applied by the second stage.
+
+Expression models (``expression``; blsq_expr_eval_dev).  ``expression('a*exp(-t/tau)+c', ('a', 'tau',
+'c'))`` is a model given as a formula: an ``ExprModel``, compiled on the host into a short program that a kernel of its
+own interprets per row, with the exact Jacobian from a reverse sweep.  bounded_lsq/_expr.py has the language and the
+numpy interpreter that IS the definition.  An ``ExprModel`` is taken wherever a ``CompositeModel`` is, except by
+``binned=True`` and by global fits (ValueError).
 """
 import re
 
 import numpy as np
 
 from . import _abi
+from ._expr import ExprModel, expression
 
 MAX_N = 64                                   # BLSQ_MODEL_MAX_N
 MAX_COMP = 8                                 # BLSQ_MODEL_MAX_COMP
@@ -97,7 +104,7 @@ __all__ = ['MODELS', 'NAMES', 'MAX_N', 'MAX_COMP', 'TERMS', 'get', 'compose', 'r
            'poisson_transform', 'poisson_residual', 'poisson_jacobian', 'binned', 'bin_rows', 'BinnedModel', 'erf_diff',
            'psi_pair', 'PSI_X0', 'PSI_TERMS', 'SAMPLING', 'NAN_POLICIES', 'check_nan_policy', 'omit_residual',
            'omit_jacobian', 'count_observed', 'pad_ragged', 'RESPONSE_MAX_L', 'check_response', 'apply_response',
-           'response_residual', 'response_jacobian']
+           'response_residual', 'response_jacobian', 'expression', 'ExprModel']
 
 
 def _tp(xdata, P):
@@ -447,12 +454,19 @@ def compose(spec):
 
 
 def resolve(f):
-    """A ``CompositeModel`` as it is; a string holding ``+`` or ``*`` through ``compose``; anything else through ``get``."""
-    if isinstance(f, CompositeModel):
+    """A ``CompositeModel`` or an ``ExprModel`` as it is; a string holding ``+`` or ``*`` through ``compose``; anything
+    else through ``get``."""
+    if isinstance(f, (CompositeModel, ExprModel)):
         return f
     if isinstance(f, str) and ("+" in f or "*" in f):
         return compose(f)
     return get(f)
+
+
+def resolvable(model):
+    """What ``resolve`` turns back into `model`: the object itself for an ``ExprModel`` (its name is no spec), the name
+    otherwise."""
+    return model if isinstance(model, ExprModel) else model.name
 
 
 # ---- bin-integrated models -------------------------------------------------------------------------------------------
@@ -724,6 +738,7 @@ def binned(model):
     """The ``BinnedModel`` of a name, a composite spec, a ``Model`` or a ``CompositeModel`` (a ``BinnedModel`` as it is)."""
     if isinstance(model, BinnedModel):
         return model
+    check_expr_model(model, binned=True)
     return BinnedModel(model if isinstance(model, Model) else resolve(model))
 
 
@@ -933,8 +948,19 @@ def check_response_model(model, B, m, xdata=None, binned=False, global_map=None)
                          "a convolution over bins with gaps (rows lo, hi) is not defined.")
 
 
+def check_expr_model(model, binned=False, global_fit=False):
+    """What an ``ExprModel`` does not take, as ValueErrors: bin integration and global fits."""
+    if isinstance(model, ExprModel):
+        if binned:
+            raise ValueError("`binned=True` is not supported with the expression model '%s': a formula is not "
+                             "integrated over its bins." % model.name)
+        if global_fit:
+            raise ValueError("the expression model '%s' is not supported in a global fit." % model.name)
+
+
 def check_global(model, binned=False, param_map=None):
     """What a global fit does not take, as ValueErrors."""
+    check_expr_model(model, global_fit=True)
     if binned:
         raise ValueError("`binned=True` is not supported in a global fit.")
     if model.coords != 1:
@@ -977,7 +1003,7 @@ def sigma_weights(sigma, lead, m, omitted=None):
 
 
 class DeviceModel:
-    """Model `name` (a name, a composite spec or a ``CompositeModel``) with its data resident on the GPU: the device callbacks of ``OuterDriver.run_device``.
+    """Model `name` (a name, a composite spec, a ``CompositeModel`` or an ``ExprModel``) with its data resident on the GPU: the device callbacks of ``OuterDriver.run_device``.
 
     Uploads t = xdata, y = ydata (None: 0, plain prediction) and w = 1 / sigma (None: 1; sigma a scalar, (m,) or
     (B, m)) once.  ``fun_dev(x_ptr, f_ptr, reps)`` and ``jac_dev(x_ptr, J_ptr, mask_ptr)`` launch the kernel on the
@@ -1016,13 +1042,18 @@ class DeviceModel:
     (``apply_response``, over the sample index).  The entry above is then bound as ``evaluate`` binds it — without
     `ydata`, `sigma`, the estimator and the omission — and writes raw model values and the raw Jacobian into two scratch
     buffers of this object; blsq_response_apply_dev, launched behind it on the same stream, convolves them and applies
-    what was withheld.  One coordinate, no `global_map`, and `binned` with contiguous edges only (ValueError)."""
+    what was withheld.  One coordinate, no `global_map`, and `binned` with contiguous edges only (ValueError).
+
+    An ``ExprModel``: the callbacks go through blsq_expr_eval_dev alone, with the program of
+    ``model.bind(param_map)`` (fixed and tied parameters are leaves of the program: the entry takes no map), under
+    every flag above but `binned` and `global_map` (ValueError)."""
 
     def __init__(self, ctx, name, B, m, n, xdata, ydata=None, sigma=None, param_map=None, Pfix=None, estimator='lse',
                  binned=False, nan_policy='propagate', global_map=None, response=None, response_origin=0):
         model = resolve(name)
         model.terms(n)
         gm = global_map
+        check_expr_model(model, binned)
         if gm is not None:
             check_global(model, binned, param_map)
         self.response = None
@@ -1112,6 +1143,23 @@ class DeviceModel:
         estimator, nan_policy, d_y, d_w, w_stride = (
             (self.estimator, self.nan_policy, self.d_y, self.d_w, self.w_stride) if self.response is None
             else ('lse', 'propagate', None, None, 0))
+        if isinstance(M, ExprModel):                          # the program behind the map, and the one entry that runs it
+            prog = M.bind(pm).program
+            ops, consts = np.ascontiguousarray(prog.ops, dtype=np.uint64), np.ascontiguousarray(prog.consts)
+            self._host = (ops, consts)                        # the host arrays the entry reads: alive with the model
+            a = [ESTIMATORS.index(estimator), NAN_POLICIES.index(nan_policy), self.B, 1, m, self.n, self.n_model,
+                 M.coords, len(ops), ops.ctypes.data_as(_abi.C.POINTER(_abi.C.c_uint64)), int(prog.root), len(consts),
+                 consts.ctypes.data_as(_abi.c_double_p), self.d_t, self.t_stride, d_y, d_w, w_stride, None, self.d_Pfix,
+                 None, None, None]
+            ctx = self.ctx
+
+            def _eval(x_ptr, reps, f_ptr, J_ptr, mask_ptr):
+                a[3] = int(reps)
+                a[18] = x_ptr
+                a[20:23] = f_ptr, J_ptr, mask_ptr
+                ctx.check(ctx.lib.blsq_expr_eval_dev(ctx.h, *a), "blsq_expr_eval_dev")
+            self._eval = _eval
+            return
         if pm is not None and pm.affine:
             name = "blsq_model_eval_tie_dev"
         elif gm is not None:
@@ -1230,6 +1278,7 @@ class DeviceFit:
         self.model = resolve(name)
         self.model.terms(n)
         gm = self.global_map = global_map
+        check_expr_model(self.model, binned)
         if gm is not None:
             check_global(self.model, binned, param_map)
         self.response, self.response_origin = None, 0
@@ -1273,7 +1322,7 @@ class DeviceFit:
 
     def open_device(self, ctx, lb, ub):
         xdata = self.xdata if self.response is None else self._xdata_given
-        dm = DeviceModel(ctx, self.model.name, self.B, self._m_set, self.n_model, xdata, self.ydata, self.sigma,
+        dm = DeviceModel(ctx, resolvable(self.model), self.B, self._m_set, self.n_model, xdata, self.ydata, self.sigma,
                          self.param_map, self.Pfix, self.estimator, self.binned, self.nan_policy, self.global_map,
                          **({} if self.response is None
                             else {'response': self.response, 'response_origin': self.response_origin}))
@@ -1283,10 +1332,10 @@ class DeviceFit:
 
 def evaluate(name, xdata, P, ctx=None, binned=False, response=None, response_origin=0):
     """Predictions ``model(xdata; P[b])`` of shape (B, m), computed on the GPU (the kernel with y = NULL, w = NULL).
-    P: (B, n); xdata: (m,) / (B, m), or (2, m) / (B, 2, m) for 'gauss2d'.  `name`: a name, a composite spec or a
-    ``CompositeModel``.  ``binned=True``: the bin contents of the bin-integrated model; `xdata` is then the m + 1
-    contiguous edges (1-D) or rows (2, m) / (B, 2, m) — (4, m) / (B, 4, m) for 'gauss2d' — as ``BinnedModel.f`` takes
-    them.  ``response=`` (L,) or (B, L) with ``response_origin=``: the prediction convolved with the kernel, over the
+    P: (B, n); xdata: (m,) / (B, m), or (2, m) / (B, 2, m) for 'gauss2d'.  `name`: a name, a composite spec, a
+    ``CompositeModel`` or an ``ExprModel`` (xdata (C, m) / (B, C, m) for its C > 1 coordinates).  ``binned=True``: the
+    bin contents of the bin-integrated model; `xdata` is then the m + 1 contiguous edges (1-D) or rows (2, m) /
+    (B, 2, m) — (4, m) / (B, 4, m) for 'gauss2d' — as ``BinnedModel.f`` takes them.  ``response=`` (L,) or (B, L) with ``response_origin=``: the prediction convolved with the kernel, over the
     sample index (``apply_response``): what a fit with the same keywords compares with its data."""
     model = resolve(name)
     P = np.ascontiguousarray(P, dtype=np.float64)
@@ -1316,7 +1365,7 @@ def evaluate(name, xdata, P, ctx=None, binned=False, response=None, response_ori
     if own:
         ctx = _abi.Context(0)
     try:
-        with DeviceModel(ctx, model.name, B, m, n, x, **({'binned': True} if binned else {}), **resp) as dm:
+        with DeviceModel(ctx, resolvable(model), B, m, n, x, **({'binned': True} if binned else {}), **resp) as dm:
             d_P = ctx.to_device(P)
             d_f = ctx.malloc(8 * B * m)
             try:

@@ -673,6 +673,41 @@ struct LinearEvalCall {
 // the kernels' offsets in bounds.
 hipError_t launch_linear_eval(const LinearEvalCall& c, hipStream_t s);
 
+// ------------------------------------------------- expression models (7u) ----
+// One evaluation of expr_kernels.hip (blsq_expr_eval_dev): the program (ops, consts, root; include/blsq.h has the format)
+// interpreted per row: f [B * reps][m] and / or J [B][m][nf] (reps == 1) at X [B * reps][nf].
+struct ExprEvalCall {
+  int est;                // BLSQ_EST_*: POISSON needs y, and w == nullptr
+  int nan_policy;         // BLSQ_NAN_*: OMIT needs y
+  int B, reps, m;
+  int nf;                 // solver variables: the width of X and J
+  int npfix;              // the width of Pfix: the model's parameters
+  int ncoord;             // rows of t per problem
+  int nops;
+  const unsigned long long* ops;    // [nops] on the host
+  int root;
+  int nconst;
+  const double* consts;   // [nconst] on the host
+  const double* t; long t_stride;   // 0 (shared) or ncoord * m
+  const double* y;        // [B][m] or nullptr
+  const double* w; long w_stride;   // nullptr, or stride 0 / m
+  const double* X;
+  const double* Pfix;     // [B][npfix], read for PFIX operands only
+  double* f;
+  double* J;
+  const int* mask;        // nullptr or [B]: a problem with mask[b] == 0 is left untouched
+};
+// Which argument of a program is the first bad one, in the order blsq_expr_check documents; 0: the program is sound: no
+// operand leaves the tape, the variables, Pfix, the constants or the coordinates.
+enum { EXPR_BAD_NOPS = 1, EXPR_BAD_OPS, EXPR_BAD_ROOT, EXPR_BAD_NCONST, EXPR_BAD_NF, EXPR_BAD_NPFIX, EXPR_BAD_NCOORD };
+int expr_program_bad(int nops, const unsigned long long* ops, int root, int nconst, int nf, int npfix, int ncoord);
+bool expr_reads_pfix(int nops, const unsigned long long* ops, int root);   // (of a sound program)
+// hipErrorInvalidValue, and nothing launched, for an unknown flag, a size below 1, a program that is not sound, missing
+// constants, t, X or (with a PFIX operand) Pfix, a stride other than the two its array has, no output, J with reps != 1,
+// the Poisson estimator or OMIT without y, the Poisson estimator with w, or a batch the grid cannot hold: the refusals
+// that keep the kernel's offsets in bounds.
+hipError_t launch_expr_eval(const ExprEvalCall& c, hipStream_t s);
+
 // ------------------------------------------------- instrument response (7s) ----
 // One call of response_kernels.hip (blsq_response_apply_dev): the raw model values g [B * reps][m] and / or the raw
 // Jacobian G [B][m][nc] convolved with the kernel h along the rows, then the epilogue of a model evaluation: f [B * reps][m]

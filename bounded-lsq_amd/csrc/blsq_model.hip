@@ -1,5 +1,5 @@
 // Built-in fit models (include/blsq.h; kernel: model_kernels.hip): the model and term tables behind
-// blsq_model_count / _info and blsq_term_count / _info, the entries blsq_linear_eval_dev, blsq_bvls_moments_dev, blsq_bvls_solve_dev and blsq_response_apply_dev, and the eight entries blsq_model_eval_dev, _map_dev, _comp_dev,
+// blsq_model_count / _info and blsq_term_count / _info, the entries blsq_linear_eval_dev, blsq_expr_check, blsq_expr_eval_dev, blsq_bvls_moments_dev, blsq_bvls_solve_dev and blsq_response_apply_dev, and the eight entries blsq_model_eval_dev, _map_dev, _comp_dev,
 // _est_dev, _bin_dev, _nan_dev, _global_dev and _tie_dev.  An entry fills a ModelEvalCall from its arguments (what its signature
 // does not have is the default) and hands it to model_eval_checked with its EvalEntry: one list of checks, one launcher, and per entry
 // only the argument numbers.
@@ -293,6 +293,49 @@ extern "C" int blsq_linear_eval_dev(blsq_ctx* ctx, int B, int reps, int m, int n
   HIPCHK(ctx, hipSetDevice(ctx->device));
   const LinearEvalCall c{B, reps, m, n, dA, A_stride, dy, dw, w_stride, dX, df, dJ, dmask};
   return ctx->run(K_MODEL_EVAL, "launch_linear_eval", [&] { return launch_linear_eval(c, ctx->stream); });
+}
+
+// Expression models (expr_kernels.hip): a program checked on the host alone, and its evaluation: the
+// checks in the order of the arguments (the program's by expr_program_bad, whose finding `at` maps onto the entry's
+// positions), then one timed call in the slot of the model evaluations.
+extern "C" int blsq_expr_check(int nops, const uint64_t* ops, int root, int nconst, int nf, int npfix, int ncoord) {
+  static const int at[] = {0, 1, 2, 3, 4, 5, 6, 7};          // EXPR_BAD_* -> the position in this signature
+  return -at[expr_program_bad(nops, reinterpret_cast<const unsigned long long*>(ops), root, nconst, nf, npfix, ncoord)];
+}
+
+extern "C" int blsq_expr_eval_dev(blsq_ctx* ctx, int est, int nan_policy, int B, int reps, int m, int nf, int npfix,
+                                  int ncoord, int nops, const uint64_t* ops, int root, int nconst, const double* consts,
+                                  const double* dt, long t_stride, const double* dy, const double* dw, long w_stride,
+                                  const double* dX, const double* dPfix, double* df, double* dJ, const int32_t* dmask) {
+  if (!ctx) return -1;
+  if (est != BLSQ_EST_LSE && est != BLSQ_EST_POISSON) return ctx->bad(2, "est must be one of BLSQ_EST_*");
+  if (nan_policy != BLSQ_NAN_PROPAGATE && nan_policy != BLSQ_NAN_OMIT)
+    return ctx->bad(3, "nan_policy must be one of BLSQ_NAN_*");
+  if (B <= 0) return ctx->bad(4, "B must be positive");
+  if (reps <= 0) return ctx->bad(5, "reps must be positive");
+  if (m <= 0) return ctx->bad(6, "m must be positive");
+  const unsigned long long* words = reinterpret_cast<const unsigned long long*>(ops);
+  static const int at[] = {0, 10, 11, 12, 13, 7, 8, 9};      // EXPR_BAD_* -> the position in this signature
+  static const char* const why[] = {
+      "", "nops must be in 0 .. BLSQ_EXPR_MAX_OPS", "ops is NULL, or an op has an unknown opcode or an operand out of range",
+      "root is not a valid operand", "nconst must be in 0 .. BLSQ_EXPR_MAX_CONST", "nf must be in 1 .. BLSQ_MODEL_MAX_N",
+      "npfix must be in 0 .. BLSQ_MODEL_MAX_N", "ncoord must be in 1 .. BLSQ_EXPR_MAX_COORD"};
+  if (const int bad = expr_program_bad(nops, words, root, nconst, nf, npfix, ncoord)) return ctx->bad(at[bad], why[bad]);
+  if (nconst > 0 && !consts) return ctx->bad(14, "consts is NULL");
+  if (!dt) return ctx->bad(15, "t is NULL");
+  if (t_stride != 0 && t_stride != (long)ncoord * m) return ctx->bad(16, "t_stride must be 0 or ncoord * m");
+  if (est == BLSQ_EST_POISSON && !dy) return ctx->bad(17, "y is NULL: the Poisson estimator needs the counts");
+  if (nan_policy == BLSQ_NAN_OMIT && !dy) return ctx->bad(17, "y is NULL: BLSQ_NAN_OMIT reads the missing points from it");
+  if (est == BLSQ_EST_POISSON && dw) return ctx->bad(18, "w must be NULL with the Poisson estimator");
+  if (dw && w_stride != 0 && w_stride != (long)m) return ctx->bad(19, "w_stride must be 0 or m");
+  if (!dX) return ctx->bad(20, "X is NULL (the points)");
+  if (!dPfix && expr_reads_pfix(nops, words, root)) return ctx->bad(21, "Pfix is NULL although the program has a PFIX operand");
+  if (!df && !dJ) return ctx->bad(22, "f and J are both NULL");
+  if (dJ && reps != 1) return ctx->bad(23, "J requires reps == 1");
+  HIPCHK(ctx, hipSetDevice(ctx->device));
+  const ExprEvalCall c{est, nan_policy, B, reps, m, nf, npfix, ncoord, nops, words, root, nconst, consts, dt, t_stride,
+                       dy, dw, w_stride, dX, dPfix, df, dJ, dmask};
+  return ctx->run(K_MODEL_EVAL, "launch_expr_eval", [&] { return launch_expr_eval(c, ctx->stream); });
 }
 
 // BVLS / NNLS (bvls_kernels.hip): the moments of a batch, and the whole active-set solve of every problem

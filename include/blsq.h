@@ -676,6 +676,59 @@ int blsq_bvls_solve_dev(blsq_ctx* ctx, int B, int m, int n, const double* dG, lo
                         long A_stride, const double* dy, const double* dw, long w_stride, double* dx,
                         int32_t* don_bound, double* dfun, double* dgrad, double* doptimality, int32_t* dstat);
 
+/* ---- expression models: a formula interpreted on the device -----------------------------------------
+ * A model that is none of the built-in ones, given as a short straight-line program (compiled on the host from the
+ * user's formula; bounded_lsq/_expr.py has the language and IS the definition of every value below).  A program is
+ * (ops[nops], consts[nconst], root), 0 <= nops <= BLSQ_EXPR_MAX_OPS, 0 <= nconst <= BLSQ_EXPR_MAX_CONST.
+ * An operand is 16 bits, its kind in the high byte and an index in the low one:
+ *   TAPE k   the result of the earlier op k          PFIX j   model parameter j, held per problem: Pfix[b][j]
+ *   VAR k    solver variable k: X[q][k]              CONST i  consts[i]             COORD r  coordinate r: t[b][r][i]
+ * An op is one 64-bit word: the opcode in bits 0-7, operand a in bits 8-23, operand b in bits 24-39 (ADD SUB MUL DIV
+ * and POWC take two operands, the others one: b is then not read; the b of POWC, the exponent, is a CONST).  root is an
+ * operand and may be a leaf.
+ * Forward: val[k] for k ascending; the model value v is the value of root.  Reverse, for the row of J: adjoints and row
+ * start at +0.0, 1 is pushed to root, then k descending with g = adj[k], a pushed before b; a push is dst = dst +
+ * contribution, dst being adj[.] of a TAPE operand whose op depends on a variable and column k of the row for VAR k; a
+ * push to anything else is dropped and an op that depends on no variable is skipped.  Contributions to a and b:
+ *   ADD g, g    SUB g, -g    MUL g*vb, g*va    DIV g/vb, -((g*v)/vb)    NEG -g    EXP g*v    LOG g/va    SQRT (0.5*g)/v
+ *   SIN g*cos(va)    COS -(g*sin(va))    ATAN g/(1+va*va)    ERF g*(C*exp(-(va*va))), C = 1.1283791670955126
+ *   ERFC the negative of ERF's    POWC g*(c*pow(va, c-1))
+ * Then f = w (v - y) (y NULL: v) and the row is multiplied by w as a whole; under BLSQ_EST_POISSON f = r and the row is
+ * multiplied by c of the deviance residual (blsq_model_eval_est_dev).  Compiled without contraction: the device differs
+ * from the definition in the last bits of exp, log, sin, cos, atan, erf, erfc and pow only.
+ *
+ * blsq_expr_check: takes no context and no device.  0, or minus the position of the first bad argument, looked at in
+ * this order: nops (1: outside 0 .. BLSQ_EXPR_MAX_OPS), ops (2: NULL with nops > 0), nconst (4: outside
+ * 0 .. BLSQ_EXPR_MAX_CONST), nf (5: outside 1 .. BLSQ_MODEL_MAX_N), npfix (6: outside 0 .. BLSQ_MODEL_MAX_N), ncoord
+ * (7: outside 1 .. BLSQ_EXPR_MAX_COORD), then the contents of ops (2: an unknown opcode, a TAPE operand that does not
+ * name a strictly earlier op, VAR >= nf, PFIX >= npfix, CONST >= nconst, COORD >= ncoord, an unknown kind, a POWC whose
+ * b is not a CONST), then root (3: not a valid operand, TAPE >= nops).
+ *
+ * blsq_expr_eval_dev: f [B * reps][m] and / or J [B][m][nf] (reps must be 1) at X [B * reps][nf], as blsq_model_eval_dev
+ * and with its rules: dt [ncoord][m] shared (t_stride 0) or [B][ncoord][m] (t_stride ncoord * m); dy [B][m] or NULL; dw
+ * NULL, [m] (w_stride 0) or [B][m] (w_stride m); dPfix [B][npfix], read for PFIX operands only (NULL without one);
+ * dmask int32 [B] or NULL: a problem with dmask[b] == 0 is left untouched.  est: BLSQ_EST_*; POISSON needs dy and takes no
+ * dw.  nan_policy: BLSQ_NAN_*; OMIT needs dy: a row whose y is NaN is +0.0 in f and in every slot of J and nothing of
+ * it is evaluated.  ops and consts are HOST pointers read during the call: the program travels in the kernel arguments.
+ * All other pointers are device pointers; asynchronous on the ctx stream; timed in the `model_eval` slot.  A negative
+ * return is the index of the bad argument (ctx = 1, est = 2, nan_policy = 3, B = 4, reps = 5, m = 6, nf = 7, npfix = 8,
+ * ncoord = 9, nops = 10, ops = 11, root = 12, nconst = 13, consts = 14: NULL with nconst > 0, t = 15, t_stride = 16,
+ * y = 17, w = 18, w_stride = 19, X = 20, Pfix = 21, f = 22: f and J both NULL, J = 23: reps != 1, mask); the program is
+ * checked as blsq_expr_check checks it, behind est, nan_policy, B, reps and m; nothing is launched then. */
+#define BLSQ_EXPR_MAX_OPS 64
+#define BLSQ_EXPR_MAX_CONST 32
+#define BLSQ_EXPR_MAX_COORD 4
+enum {
+  BLSQ_EXPR_ADD = 0, BLSQ_EXPR_SUB, BLSQ_EXPR_MUL, BLSQ_EXPR_DIV, BLSQ_EXPR_NEG, BLSQ_EXPR_EXP, BLSQ_EXPR_LOG,
+  BLSQ_EXPR_SQRT, BLSQ_EXPR_SIN, BLSQ_EXPR_COS, BLSQ_EXPR_ATAN, BLSQ_EXPR_ERF, BLSQ_EXPR_ERFC, BLSQ_EXPR_POWC
+};
+enum { BLSQ_EXPR_TAPE = 0, BLSQ_EXPR_VAR, BLSQ_EXPR_PFIX, BLSQ_EXPR_CONST, BLSQ_EXPR_COORD };
+int blsq_expr_check(int nops, const uint64_t* ops, int root, int nconst, int nf, int npfix, int ncoord);
+int blsq_expr_eval_dev(blsq_ctx* ctx, int est, int nan_policy, int B, int reps, int m, int nf, int npfix, int ncoord,
+                       int nops, const uint64_t* ops, int root, int nconst, const double* consts, const double* dt,
+                       long t_stride, const double* dy, const double* dw, long w_stride, const double* dX,
+                       const double* dPfix, double* df, double* dJ, const int32_t* dmask);
+
 /* ---- parameter covariance from the final Jacobian --------------------------------------------------------------
  * The reference documents `x_covariance` as the inverse of J^T J at the solution (least_squares.py:248-252) and fills
  * it only through its MINPACK bridge (method='lm').  Here, per problem, from a Householder triangle R of J (the TSQR

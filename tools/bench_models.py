@@ -49,9 +49,20 @@ numpy functions with ``response=`` (``models.response_residual`` / ``response_ja
 the response entry alone on random buffers of `--B` problems, `--m` rows and `--n` columns, f and J per launch in the
 'model_eval' slot, and the bytes per second of J (G read, J written: 16 B m n bytes).
 
+``--expr TEXT --params a,b,c`` fits an expression model instead: ``models.expression(TEXT, params)`` on
+`--m` points of [0, 6], the truth `--truth v1,v2,...` jittered by 5 % per problem, noise of 0.01, p0 10 % off.  Routes,
+alternating: `expr`, the ExprModel on the device (blsq_expr_eval_dev); `callable`, the same formula as numpy callables
+``f(x, P)`` / ``jac(x, P)`` on the device driver, the only route there was before (the Jacobian crosses to the device on
+every accepted step).  Without ``--truth`` TEXT must be the default, the two-component decay
+``a*(f*exp(-t/t1)+(1-f)*exp(-t/t2))+bg``: its callables are written out by hand, and a third route `composite` fits
+the equivalent 'exp*2+poly*1' (a f, 1 / t1, a (1 - f), 1 / t2, bg) for orientation.  For another TEXT the callables are
+the model's numpy definition.  With ``--kernel``: the launches of blsq_expr_eval_dev alone, f and J apart (and, for the
+default decay, those of the composite entry at the same shape).
+
 usage: python tools/bench_models.py [--B 4096] [--m 64] [--repeat 5] [--peaks 1] [--fixed 1,4] [--tied 5:2,4:1:1:0.42] [--kernel]
                                     [--launches 50] [--rounds 1] [--estimator lse] [--binned] [--omit FRACTION]
                                     [--global S --shared 1,2] [--response L [--n 4]]
+                                    [--expr TEXT --params a,b,c [--truth 3,0.4,0.5,2.5,0.2] [--kernel]]
 """
 import argparse
 import json
@@ -309,6 +320,112 @@ def response_bench(a, ctx):
     return res
 
 
+DECAY_TEXT = "a*(f*exp(-t/t1)+(1-f)*exp(-t/t2))+bg"
+DECAY_PARAMS = "a,f,t1,t2,bg"
+DECAY_TRUTH = [3.0, 0.4, 0.5, 2.5, 0.2]
+
+
+def decay_f(x, P):
+    a, f, t1, t2, bg = (P[:, k, np.newaxis] for k in range(5))
+    return a * (f * np.exp(-x / t1) + (1 - f) * np.exp(-x / t2)) + bg
+
+
+def decay_jac(x, P):
+    a, f, t1, t2, bg = (P[:, k, np.newaxis] for k in range(5))
+    e1, e2 = np.exp(-x / t1), np.exp(-x / t2)
+    J = np.empty((P.shape[0], x.shape[-1], 5))
+    J[:, :, 0] = f * e1 + (1 - f) * e2
+    J[:, :, 1] = a * (e1 - e2)
+    J[:, :, 2] = a * f * e1 * x / (t1 * t1)
+    J[:, :, 3] = a * (1 - f) * e2 * x / (t2 * t2)
+    J[:, :, 4] = 1.0
+    return J
+
+
+def expr_bench(a, ctx):
+    """--expr: whole fits of the ExprModel on the device against the formula as numpy callables (and, for the default
+    decay, against the equivalent composite)."""
+    text = a.expr.replace(" ", "")
+    decay = text == DECAY_TEXT and a.params == DECAY_PARAMS and not a.truth
+    if not a.truth and not decay:
+        raise SystemExit("--expr with a formula of your own needs --truth v1,v2,...")
+    M = models.expression(a.expr, tuple(a.params.split(",")))
+    base = np.array(DECAY_TRUTH if decay else [float(v) for v in a.truth.split(",")])
+    if base.size != M.n:
+        raise SystemExit("--truth has %d values, the model %d parameters" % (base.size, M.n))
+    B, m = a.B, a.m
+    rng = np.random.default_rng(0)
+    truth = base * (1 + 0.05 * rng.uniform(-1, 1, (B, base.size)))
+    x = np.linspace(0.0, 6.0, m)
+    Y = M.f(x, truth) + 0.01 * rng.standard_normal((B, m))
+    P0 = truth * (1 + 0.1 * rng.choice([-1.0, 1.0], truth.shape))
+    half = 0.4 * np.abs(truth) + 0.2
+    if decay:
+        def comp(P):
+            return np.column_stack([P[:, 0] * P[:, 1], 1 / P[:, 2], P[:, 0] * (1 - P[:, 1]), 1 / P[:, 3], P[:, 4]])
+    p = M.program
+    head = {"expr": M.name, "nops": p.nops, "nconst": len(p.consts), "nact": int(p.active().sum()), "B": B, "m": m,
+            "n": M.n}
+    if a.kernel:                                   # the launches alone, f and J apart, in the 'model_eval' slot
+        head.update({"launches": a.launches, "rounds": a.rounds, "J_bytes": 8 * B * m * M.n})
+        for key, name, X in [("expr", M, P0)] + ([("composite", "exp*2+poly*1", comp(P0))] if decay else []):
+            dm = models.DeviceModel(ctx, name, B, m, M.n, x, Y, 0.01)
+            d_x, d_f, d_J = ctx.to_device(np.ascontiguousarray(X)), ctx.malloc(8 * B * m), ctx.malloc(8 * B * m * M.n)
+            for what, call in (("f", lambda: dm.fun_dev(d_x, d_f, 1)), ("J", lambda: dm.jac_dev(d_x, d_J))):
+                call()                                                    # warm-up: the code object
+                ctx.sync()
+                per_round = []
+                for _ in range(a.rounds):
+                    ctx.timing(True, only="model_eval")
+                    ctx.timing_reset()
+                    for _ in range(a.launches):
+                        call()
+                    ctx.sync()
+                    ms, cnt = ctx.timing_read()["model_eval"]
+                    ctx.timing(False)
+                    per_round.append(round(1e3 * ms / cnt, 2))
+                head["%s_%s_us" % (key, what)] = round(float(np.median(per_round)), 2)
+                head["%s_%s_us_all" % (key, what)] = per_round
+            for q in (d_x, d_f, d_J):
+                ctx.free(q)
+            dm.close()
+        return head
+    kw = dict(sigma=0.01, driver="device", ctx=ctx, ftol=1e-10, xtol=1e-10, gtol=1e-10)
+    f, jac = (decay_f, decay_jac) if decay else (M.f, M.jac)
+    routes = {"expr": lambda: curve_fit_batch(M, x, Y, P0, bounds=(truth - half, truth + half), **kw),
+              "callable": lambda: curve_fit_batch(f, x, Y, P0, jac=jac, bounds=(truth - half, truth + half), **kw)}
+    if decay:
+        C, C0 = comp(truth), comp(P0)
+        chalf = 0.6 * np.abs(C) + 0.2
+        routes["composite"] = lambda: curve_fit_batch("exp*2+poly*1", x, Y, C0, bounds=(C - chalf, C + chalf), **kw)
+    times = {k: [] for k in routes}
+    out = {k: run() for k, run in routes.items()}                         # warm-up: code objects, plans
+    for _ in range(a.repeat):
+        for k, run in routes.items():
+            ctx.sync()
+            t0 = time.perf_counter()
+            run()
+            times[k].append(time.perf_counter() - t0)
+    ctx.timing(True, only="model_eval")
+    ctx.timing_reset()
+    routes["expr"]()
+    ctx.sync()
+    k_ms, k_n = ctx.timing_read()["model_eval"]
+    ctx.timing(False)
+    both = np.array([ra.success and rb.success for ra, rb in zip(out["expr"][2], out["callable"][2])])
+    med = {k: float(np.median(v)) for k, v in times.items()}
+    return {**head, "driver": "device",
+            **{k + "_s": round(v, 4) for k, v in med.items()},
+            **{k + "_all_s": [round(t, 4) for t in v] for k, v in times.items()},
+            "speedup_over_callable": round(med["callable"] / med["expr"], 2),
+            "kernel_ms_per_fit": round(k_ms, 3), "kernel_launches_per_fit": int(k_n),
+            "kernel_us_per_launch": round(1e3 * k_ms / max(k_n, 1), 2),
+            "converged": {k: int(sum(r.success for r in out[k][2])) for k in routes},
+            "nfev": {k: int(max(r.nfev for r in out[k][2])) for k in routes},
+            "popt_max_rel_diff": float(np.max(np.abs(out["expr"][0][both] - out["callable"][0][both])
+                                              / (np.abs(out["callable"][0][both]) + 1e-3)))}
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--B", type=int, default=4096)
@@ -330,7 +447,19 @@ def main():
     ap.add_argument("--response", type=int, default=0, metavar="L",
                     help="fit through an instrument response of L taps (with --kernel: the response entry alone)")
     ap.add_argument("--n", type=int, default=4, help="with --response --kernel: the columns of G and J")
+    ap.add_argument("--expr", nargs="?", const=DECAY_TEXT, default=None, metavar="TEXT",
+                    help="fit an expression model (default TEXT: the two-component decay)")
+    ap.add_argument("--params", default=DECAY_PARAMS, help="with --expr: the parameter names, e.g. a,b,c")
+    ap.add_argument("--truth", default="", help="with --expr: the parameter values the data are drawn from")
     a = ap.parse_args()
+    if a.expr is not None:
+        if a.response or a.global_S or a.fixed or a.tied or a.binned or a.omit is not None or a.estimator != "lse":
+            ap.error("--expr TEXT takes --params, --truth, --B, --m, --repeat and --kernel (--launches, --rounds) only")
+        ctx = _abi.Context(0)
+        res = expr_bench(a, ctx)
+        ctx.close()
+        print(json.dumps(res))
+        return
     if a.response:
         if (not 1 <= a.response <= models.RESPONSE_MAX_L or a.global_S or a.fixed or a.tied or a.binned
                 or a.omit is not None or a.estimator != "lse"):
