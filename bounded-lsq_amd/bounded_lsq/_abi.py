@@ -136,6 +136,7 @@ SIGNATURES = {
     "blsq_debug_cqr_stats": (C.c_int, [vp, C.POINTER(C.c_uint64), C.c_int]),
     "blsq_debug_gram_stats": (C.c_int, [vp, C.POINTER(C.c_uint64), C.c_int]),
     "blsq_debug_tri_reference": (C.c_int, [vp, C.c_int]),
+    "blsq_debug_gram_regstage": (C.c_int, [vp, C.c_int]),
     "blsq_debug_cqr2_stats": (C.c_int, [vp, C.POINTER(C.c_uint64), C.c_int]),
     "blsq_debug_gram_route": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, C.c_int, c_int32_p]),
     "blsq_option_count": (C.c_int, []),
@@ -337,6 +338,11 @@ class Context:
         """on: the three-barrier reference schedule of the blocked triangular solves (n > 80) for this ctx's later
         launches; off (a new ctx's state): the look-ahead schedule.  Same bits."""
         self.check(self.lib.blsq_debug_tri_reference(self.h, 1 if on else 0), "tri_reference")
+
+    def gram_regstage(self, on):
+        """on: the 16-tile Gram (n = 256) stages its rows through registers in this ctx's later launches even where
+        it qualifies for the LDS-DMA staging; off (a new ctx's state): LDS-DMA where the operands allow.  Same bits."""
+        self.check(self.lib.blsq_debug_gram_regstage(self.h, 1 if on else 0), "gram_regstage")
 
     def gram_stats(self, reset=False):
         """-> (problems factored by the normal-equations fast path, problems handed to the QR tree)."""

@@ -330,6 +330,12 @@ extern "C" int blsq_debug_tri_reference(blsq_ctx* ctx, int on) {
   return 0;
 }
 
+extern "C" int blsq_debug_gram_regstage(blsq_ctx* ctx, int on) {
+  if (!ctx) return -1;
+  ctx->opt.gram_regstage = on ? 1 : 0;
+  return 0;
+}
+
 extern "C" int blsq_debug_gram_stats(blsq_ctx* ctx, uint64_t* out2, int reset) {
   if (!ctx) return -1;
   if (!out2) return ctx->bad(2, "out is NULL");

@@ -233,6 +233,15 @@ __device__ __forceinline__ void glds16(const double* base_uniform, unsigned byte
                                    (lptr_t*)lds_uniform, 16, 0, 0);
 }
 
+// ... with an immediate byte offset, which the instruction adds to BOTH addresses: the next 1 KB piece of a row costs
+// no second LDS base (M0) and no second address
+template <int OFF>
+__device__ __forceinline__ void glds16_off(const double* base_uniform, unsigned byte_off_lane,
+                                           double* lds_uniform) {
+  __builtin_amdgcn_global_load_lds((gptr_t*)((const char*)base_uniform + byte_off_lane),
+                                   (lptr_t*)lds_uniform, 16, OFF, 0);
+}
+
 // workgroup barrier that orders LDS traffic only: DMA loads stay in flight across it
 __device__ __forceinline__ void lds_barrier() {
   asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");

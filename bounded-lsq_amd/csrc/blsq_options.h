@@ -50,6 +50,10 @@ struct Options {
   // tail run their three-barrier reference schedule instead of the look-ahead (tri_ops.h; bit-identical).  Set per ctx
   // by blsq_debug_tri_reference, read at every launch; it exists for the tests that compare the two schedules.
   int tri_ref = 0;
+  // Not a switch of the table either: 1 = the 16-tile Gram stages its rows through registers even where the launch
+  // qualifies for the LDS-DMA instances (gram_kernels.hip, launch_gram; bit-identical).  Set per ctx by
+  // blsq_debug_gram_regstage, read at every launch; it exists for the tests that compare the two stagings.
+  int gram_regstage = 0;
   int i(Opt k) const { return (int)v[k]; }
   bool on(Opt k) const { return v[k] != 0.0; }
   double d(Opt k) const { return v[k]; }

@@ -229,14 +229,26 @@ __global__ __launch_bounds__(GR_NT, (SLOTS <= 8 ? 4 : 2)) void gram_kernel(GramA
 // chunk boundary the accumulators go to the output slot and restart from zero, at the end the first
 // chunk's tiles are read back and added — (0 + P0) + P1, exactly what gram_reduce_kernel computes
 // from two partial Grams, without writing the second one, reading both and a launch in between.
+// DMA (n = 256 with 16-byte aligned J and f, even strides and row counts: launch_gram): the kernel has no registers
+// left to request rows earlier than half a chunk ahead (256 VGPRs, 18 of them spilled, with the staging registers), so a
+// wave met its own s_waitcnt vmcnt about 2 us per chunk.  The DMA body fills the two buffers without registers: behind
+// the barrier that ends chunk c every wave requests ITS rows of chunk c + 1 (the rows it commits in the register body:
+// W, W + 8, W + 16, W + 24) straight into the other buffer, two global_load_lds_dwordx4 per row (1 KB each, lane-linear,
+// inside the padded row), and wave 7 the chunk's 32 values of f into a stage behind the buffers; one s_waitcnt vmcnt(0)
+// in front of the next barrier retires them — eight k-steps later, with nothing in between that waits for memory (no
+// ordinary load, no LDS write; the LDS reads of the loop are explicit, so the compiler has no reason to drain the DMA).
+// One chunk is in flight and retired before the barrier, so the barrier stays a plain __syncthreads().  The rhs column
+// is taken from LDS during the chunk that owns the rows, same fma chain per wave: same bits as the register body, which
+// stays for every other operand layout and behind Options::gram_regstage.
 #ifdef BLSQ_CHOL_STAMPS
 __device__ long long g_gram_st[8][130][4];             // [wave][chunk][phase] of ONE workgroup (diagnostic build)
 #define GST(c, i) do { if (stp && lane == 0 && (c) < 130) g_gram_st[W][c][i] = (long long)wall_clock64(); } while (0)
 #else
 #define GST(c, i) do { } while (0)
 #endif
-template <int W, bool RHS, bool PAIR>
+template <int W, bool RHS, bool PAIR, bool DMA>
 __device__ __forceinline__ void gram16_wave(const GramArgs& a, double* lds) {
+  static_assert(RHS || !DMA, "the LDS-DMA staging exists for n = 256 only (rhs column beside the tiles)");
   constexpr int LDX = 272, NCB = 4;
   constexpr int NF = 16 - W;                            // fragments per k-step: column tiles W .. 15
   constexpr int N0 = 16 - W, N1 = W + 1;                // tiles of tile row W / of tile row 15 - W
@@ -296,6 +308,70 @@ __device__ __forceinline__ void gram16_wave(const GramArgs& a, double* lds) {
       else if (lane == 0) X[lrow * LDX + n] = fv;
     }
   };
+  // DMA (n = 256; launch_gram has checked alignment and parity): the same rows per wave, but global -> LDS without
+  // registers, a whole chunk ahead.  A row is two 1 KB pieces, each one instruction writing lane-linear inside the
+  // padded row; the chunk's 32 values of f follow as 16 lanes x 16 B of wave 7 into a stage behind the row buffers.
+  // Rows >= m are requested from row m - 1 and pairs of f beyond m from (m - 2, m - 1): no byte outside the problem.
+  double* FS = lds + 2 * GR_RC * LDX;                   // [2][GR_RC]
+  auto request = [&](int row0, double* X, double* fs) {
+    static_for<0, GR_RC / GR_NW>([&](auto ij) {
+      constexpr int lrow = W + GR_NW * decltype(ij)::value;
+      const int row = row0 + lrow;
+      const double* src = Jb + (long)(row < m ? row : m - 1) * a.ldJ;   // (wave-uniform)
+      glds16_off<0>(src, 16u * (unsigned)lane, X + lrow * LDX);
+      glds16_off<1024>(src, 16u * (unsigned)lane, X + lrow * LDX);
+    });
+    if constexpr (W == GR_NW - 1) {
+      if (lane < GR_RC / 2) {
+        const int r = row0 + 2 * lane;                  // (row0 and m are even: a pair lies inside or outside)
+        glds16(Fb + row0, 8u * (unsigned)((r < m ? r : m - 2) - row0), fs);
+      }
+    }
+  };
+  // ... the owning wave clears its rows >= m of a ragged chunk once its own requests have landed
+  auto zero_tail = [&](int row0, double* X) {
+    if (row0 + GR_RC <= m) return;
+#pragma unroll
+    for (int j = 0; j < GR_RC / GR_NW; ++j) {
+      const int lrow = W + GR_NW * j;
+      if (row0 + lrow >= m) {
+#pragma unroll
+        for (int cb = 0; cb < NCB; ++cb) X[lrow * LDX + lane + 64 * cb] = 0.0;
+      }
+    }
+  };
+  // ... and the rhs column comes from LDS during the chunk that owns the rows: the entries commit() takes from the
+  // staging registers — a row >= m is read where its clamped request came from, local row m - 1 - row0 — in the same
+  // order, read behind the MFMAs of k-steps 3 (rows W, W + 8) and 7 (rows W + 16, W + 24) with a wait of their own
+  double jv[HR][NCB], fq[HR];
+  auto rhs_read = [&](int row0, auto hc, const double* X, const double* fs) {
+    static_for<0, HR>([&](auto ir) {
+      constexpr int rr = decltype(ir)::value, lrow = W + GR_NW * (HR * decltype(hc)::value + rr);
+      const int lsrc = row0 + lrow < m ? lrow : m - 1 - row0;
+      const unsigned ad = lds_addr(X) + 8u * (unsigned)(lsrc * LDX + lane);
+      static_for<0, NCB>([&](auto ib) { lds_read64_off<512 * decltype(ib)::value>(jv[rr][decltype(ib)::value], ad); });
+      lds_read64(fq[rr], lds_addr(fs) + 8u * (unsigned)lrow);
+    });
+  };
+  auto rhs_use = [&](int row0, auto hc) {
+    static_assert(HR == 2 && NCB == 4, "the wait below names every register of the two rows");
+    asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(jv[0][0]), "+v"(jv[0][1]), "+v"(jv[0][2]), "+v"(jv[0][3]), "+v"(fq[0]),
+                 "+v"(jv[1][0]), "+v"(jv[1][1]), "+v"(jv[1][2]), "+v"(jv[1][3]), "+v"(fq[1]));
+    if (PAIR && decltype(hc)::value == 0 && row0 == boundary) {   // (uniform) the rows of the second chunk start here
+#pragma unroll
+      for (int cb = 0; cb < NCB; ++cb) { scr[W * 256 + 64 * cb + lane] = gf[cb]; gf[cb] = 0.0; }
+      if (lane == 0) scr[GR_NW * 256 + W] = gff;
+      gff = 0.0;
+    }
+#pragma unroll
+    for (int rr = 0; rr < HR; ++rr) {
+      const bool in = row0 + W + GR_NW * (HR * decltype(hc)::value + rr) < m;
+      const double fv = in ? fq[rr] : 0.0;
+#pragma unroll
+      for (int cb = 0; cb < NCB; ++cb) gf[cb] = fma(jv[rr][cb], fv, gf[cb]);
+      gff = fma(fv, fv, gff);
+    }
+  };
 
   v4d acc0[N0], acc1[N1];
 #pragma unroll
@@ -313,8 +389,14 @@ __device__ __forceinline__ void gram16_wave(const GramArgs& a, double* lds) {
     for (int r = tid; r < 2 * GR_RC; r += GR_NT) lds[r * LDX + n] = 0.0;
   }
   if (r_lo < m) {
+    if constexpr (DMA) {
+      request(r_lo, X0, FS);
+      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+      zero_tail(r_lo, X0);
+    } else {
 #pragma unroll
-    for (int h = 0; h < 2; ++h) { issue(r_lo, h); commit(r_lo, h, X0); }
+      for (int h = 0; h < 2; ++h) { issue(r_lo, h); commit(r_lo, h, X0); }
+    }
   }
   __syncthreads();
 
@@ -374,6 +456,13 @@ __device__ __forceinline__ void gram16_wave(const GramArgs& a, double* lds) {
     const double* X = (cidx & 1) ? X1 : X0;
     double* Xn = (cidx & 1) ? X0 : X1;
     const unsigned xb = lds_addr(X) + 8u * (unsigned)(lr * LDX + lc);
+    const double* fsc = FS + ((cidx & 1) ? GR_RC : 0);
+    if constexpr (DMA) {
+      // the whole next chunk, requested behind the barrier that freed its buffer and retired in front of the next one:
+      // nothing in between waits for it (no ordinary load, and every LDS read of the loop is an explicit one)
+      if (more) request(row0 + GR_RC, Xn, FS + ((cidx & 1) ? 0 : GR_RC));
+      __builtin_amdgcn_sched_barrier(0);
+    }
     GST(cidx, 0);
     // fragments of the chunk's first k-step (its latency is exposed once per chunk)
     static_for<0, NF>([&](auto ic) {
@@ -383,10 +472,11 @@ __device__ __forceinline__ void gram16_wave(const GramArgs& a, double* lds) {
     static_for<0, 8>([&](auto is) {
       constexpr int s = decltype(is)::value;            // k-step of the chunk
       constexpr int cur = s & 1, nxt = cur ^ 1;
-      if constexpr (s == 0 || s == 4) {
+      if constexpr (!DMA && (s == 0 || s == 4)) {
         if (more) issue(row0 + GR_RC, s / 4);
       }
       wait_set(fr[cur]);
+      if constexpr (DMA && (s == 3 || s == 7)) rhs_read(row0, std::integral_constant<int, s / 4>{}, X, fsc);
       // 17 MFMAs; the next k-step's fragments are requested two per MFMA behind the first ones
       static_for<0, N0 + N1>([&](auto it) {
         constexpr int t = decltype(it)::value;
@@ -401,10 +491,15 @@ __device__ __forceinline__ void gram16_wave(const GramArgs& a, double* lds) {
       });
       if constexpr (s == 3) GST(cidx, 1);
       if constexpr (s == 3 || s == 7) {
-        if (more) commit(row0 + GR_RC, s / 4, Xn);
+        if constexpr (DMA) rhs_use(row0, std::integral_constant<int, s / 4>{});
+        else if (more) commit(row0 + GR_RC, s / 4, Xn);
       }
     });
     GST(cidx, 2);
+    if constexpr (DMA) {
+      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // this wave's requests have landed
+      if (more) zero_tail(row0 + GR_RC, Xn);
+    }
     __syncthreads();
     GST(cidx, 3);
   }
@@ -467,20 +562,20 @@ __device__ __forceinline__ void gram16_wave(const GramArgs& a, double* lds) {
   }
 }
 
-template <bool RHS, bool PAIR>
+template <bool RHS, bool PAIR, bool DMA = false>
 __global__ __launch_bounds__(GR_NT, 2) void gram16_kernel(GramArgs a) {
   extern __shared__ double lds[];
   if (a.mask && a.mask[a.list ? a.list[blockIdx.y] : (int)blockIdx.y] <= 1) return;
   const int w = __builtin_amdgcn_readfirstlane((int)threadIdx.x >> 6);
   switch (w) {
-    case 0: gram16_wave<0, RHS, PAIR>(a, lds); break;
-    case 1: gram16_wave<1, RHS, PAIR>(a, lds); break;
-    case 2: gram16_wave<2, RHS, PAIR>(a, lds); break;
-    case 3: gram16_wave<3, RHS, PAIR>(a, lds); break;
-    case 4: gram16_wave<4, RHS, PAIR>(a, lds); break;
-    case 5: gram16_wave<5, RHS, PAIR>(a, lds); break;
-    case 6: gram16_wave<6, RHS, PAIR>(a, lds); break;
-    default: gram16_wave<7, RHS, PAIR>(a, lds); break;
+    case 0: gram16_wave<0, RHS, PAIR, DMA>(a, lds); break;
+    case 1: gram16_wave<1, RHS, PAIR, DMA>(a, lds); break;
+    case 2: gram16_wave<2, RHS, PAIR, DMA>(a, lds); break;
+    case 3: gram16_wave<3, RHS, PAIR, DMA>(a, lds); break;
+    case 4: gram16_wave<4, RHS, PAIR, DMA>(a, lds); break;
+    case 5: gram16_wave<5, RHS, PAIR, DMA>(a, lds); break;
+    case 6: gram16_wave<6, RHS, PAIR, DMA>(a, lds); break;
+    default: gram16_wave<7, RHS, PAIR, DMA>(a, lds); break;
   }
 }
 
@@ -1188,6 +1283,9 @@ GramRoute gram_route(int m, int n, int chunks, int B, bool has_final, const Opti
     r.key[0] = r.rhs_valu; r.key[1] = pair;
     r.fused = pair;
     if (pair) r.grid[0] = 1;
+    // (n = 256: the stage of f behind the row buffers, for the LDS-DMA instances launch_gram may choose — key[2],
+    //  which depends on the operands' alignment and so is not decided here)
+    if (r.rhs_valu) r.lds += sizeof(double) * 2 * GR_RC;
     return r;
   }
   const int per = (((ntile + tg - 1) / tg) + GR_NW - 1) / GR_NW;   // tile slots a wave needs
@@ -1207,7 +1305,18 @@ GramRoute gram_route(int m, int n, int chunks, int B, bool has_final, const Opti
 
 // The dispatch table: one line per kernel instance, keyed by the route.
 hipError_t launch_gram(const GramArgs& a_in, int chunks, int B, hipStream_t s, double* Gfinal, bool* fused) {
-  const GramRoute r = gram_route(a_in.m, a_in.n, chunks, B, Gfinal != nullptr, options_or_default(a_in.opt));
+  const Options& opt = options_or_default(a_in.opt);
+  GramRoute r = gram_route(a_in.m, a_in.n, chunks, B, Gfinal != nullptr, opt);
+  // 16 column tiles at n = 256: rows and f by LDS-DMA (16 B per lane) where every row of J and every pair of f the
+  // kernel requests is 16-byte aligned — bases aligned, strides even, and m and rows_per_chunk even so that a chunk
+  // starts on an even row and a pair of f lies inside the problem or outside.  Narrower n would drag the next row's
+  // data into the padding columns.  Same bits either way (Options::gram_regstage keeps the register staging).
+  if (r.family == GRAM_16 && r.rhs_valu && !opt.gram_regstage) {
+    const auto even = [](long long v) { return (v & 1) == 0; };
+    if ((((uintptr_t)a_in.J | (uintptr_t)a_in.F) & 15) == 0 && even(a_in.ldJ) && even(a_in.strideJ) &&
+        even(a_in.strideF) && even(a_in.m) && even(r.rows_per_chunk))
+      r.key[2] = 1;
+  }
   GramArgs a = a_in;
   a.rows_per_chunk = r.rows_per_chunk;
   a.rhs_valu = r.rhs_valu;
@@ -1256,6 +1365,8 @@ hipError_t launch_gram(const GramArgs& a_in, int chunks, int B, hipStream_t s, d
         case 10: return launch<gram16_kernel<false, true>>(g, b, r.lds, s, a);
         case 100: return launch<gram16_kernel<true, false>>(g, b, r.lds, s, a);
         case 110: return launch<gram16_kernel<true, true>>(g, b, r.lds, s, a);
+        case 101: return launch<gram16_kernel<true, false, true>>(g, b, r.lds, s, a);
+        case 111: return launch<gram16_kernel<true, true, true>>(g, b, r.lds, s, a);
       }
       break;
     case GRAM_GENERIC:

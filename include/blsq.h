@@ -272,6 +272,10 @@ int blsq_trf_debug_csne(blsq_trf_plan* plan, int32_t* on_tier /*B*/, double* eta
  * (n > 80) in their three-barrier reference schedule instead of the look-ahead schedule; 0 (the state of a new ctx)
  * switches back.  Both give the same bits; the tests compare them. */
 int blsq_debug_tri_reference(blsq_ctx* ctx, int on);
+/* Diagnostics: on != 0 makes every later 16-tile Gram launch of this ctx (n = 256) stage its rows through registers even
+ * where it qualifies for the LDS-DMA staging (16-byte aligned J and f, even strides and row count); 0 (the state of a
+ * new ctx) switches back.  Both give the same bits; the tests compare them. */
+int blsq_debug_gram_regstage(blsq_ctx* ctx, int on);
 /* Diagnostics of the factorisation front end: out[0] = problems factored by the
  * normal-equations fast path (Gram + equilibrated Cholesky, conditioning-gated), out[1] =
  * problems the gate handed to the Householder TSQR tree, since the last reset. */
