@@ -187,6 +187,10 @@ SIGNATURES = {
     # optimality, stat
     "blsq_bvls_solve_dev": (C.c_int, [vp] + [C.c_int] * 3 + [vp, C.c_long, vp, vp, vp, C.c_double, C.c_int, vp, C.c_long,
                                              vp, vp, C.c_long] + [vp] * 6),
+    # ctx, B, n, nl, lin, X, P (lin on the host)
+    "blsq_varpro_expand_dev": (C.c_int, [vp] + [C.c_int] * 3 + [c_int32_p, vp, vp]),
+    # ctx, B, m, n, nl, lin, owner, G, y, w, w_stride, f, J, c, info, mask (lin and owner on the host)
+    "blsq_varpro_reduce_dev": (C.c_int, [vp] + [C.c_int] * 4 + [c_int32_p, c_int32_p, vp, vp, vp, C.c_long] + [vp] * 5),
     # nops, ops, root, nconst, nf, npfix, ncoord (no ctx, no device)
     "blsq_expr_check": (C.c_int, [C.c_int, C.POINTER(C.c_uint64), C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]),
     # ctx, est, nan_policy, B, reps, m, nf, npfix, ncoord, nops, ops, root, nconst, consts, t, t_stride, y, w, w_stride,

@@ -523,7 +523,7 @@ def _popt_pcov(results, shape, no_dof, popt_of, pcov_of):
 
 def curve_fit_batch(f, xdata, ydata, p0, sigma=None, absolute_sigma=False, bounds=(-np.inf, np.inf), method='trf',
                     jac=None, driver='host', ctx=None, fixed=None, tied=None, estimator='lse', binned=False,
-                    nan_policy=None, response=None, response_origin=0, **kwargs):
+                    nan_policy=None, response=None, response_origin=0, separable=False, **kwargs):
     """``curve_fit`` for B data sets of one model, solved together by ``least_squares_batch``.
 
     f : ``f(xdata, P) -> (B, m)`` for parameters ``P`` of shape (B, n): vectorised over the batch — or the name of a
@@ -631,6 +631,33 @@ def curve_fit_batch(f, xdata, ydata, p0, sigma=None, absolute_sigma=False, bound
             `jac` choice compose unchanged, and so do the results and the variance factor.  'gauss2d' (any model of
             two coordinates) and binned edges given as rows ``lo, hi`` are ValueErrors, as are a kernel of another
             shape, one that is not finite or all zero, and an origin outside 0 .. L - 1.
+    separable : False (the default: nothing changes, bit for bit) or True: variable projection.  The
+            parameters the model is linear in (``models.linear_params``: the amplitudes of gauss / lorentz / pvoigt / exp
+            terms, every coefficient of a ``poly*d``, the ``a_k`` and ``c`` of 'exp_sum' / 'gauss_sum' / 'lorentz_sum',
+            ``a`` and ``c`` of 'gauss2d') are removed from the solver: for the other parameters alpha they are the
+            solution c(alpha) of a small linear least-squares problem, and the solver minimises over alpha alone, with
+            Kaufman's Jacobian.  Fewer variables, a better-conditioned problem, and no start values for amplitudes and
+            baselines: `p0` and `bounds` keep all n entries, but the linear entries of `p0` are ignored (they may be
+            NaN) and the linear entries of `bounds` must be infinite (ValueError naming the parameter: a bounded
+            amplitude needs the plain fit).  `f` is a name, a spec or a ``CompositeModel`` on either driver
+            (driver='device': three launches per evaluation, blsq_varpro_expand_dev, the model kernel and
+            blsq_varpro_reduce_dev; driver='host': ``models.separable_residual`` / ``separable_jacobian``, the
+            definition).  `sigma` in all its shapes, `absolute_sigma`, bounds on the non-linear parameters, both
+            methods and ``binned=True`` compose.  `popt` (B, n) is alpha* with c(alpha*) filled in.  `pcov` is the
+            covariance of the FULL problem at `popt`, a stationary point of it: the pseudo-inverse covariance of the
+            plain model's Jacobian evaluated once at `popt` on the GPU, times ``obj_value / (m - n)`` unless
+            `absolute_sigma`, inf under the ``OptimizeWarning`` where m <= n.  ``results[b]`` carries ``x`` (n,),
+            ``x_nonlinear`` (n - nl,), ``linear_params`` (nl,) indices, ``active_mask`` (n,) with zeros at the linear
+            entries, ``fun`` (the reduced residual, which is the full residual at `popt`), ``jac`` (m, n - nl)
+            Kaufman's Jacobian, ``x_covariance`` (n, n), and ``status`` / ``nfev`` / ``njev`` / ``optimality`` of the
+            reduced solve.  Where the basis functions are linearly dependent at a point the solver visits (two peaks
+            on one position and width) the reduced residual there is NaN, which the solver treats as it treats NaN from
+            any model: the objective of such a trial point is NaN, the strict accept test fails and the radius update
+            compares false, so the point is rejected and proposed again until ``max_nfev`` ends the problem with
+            status 0 (no success: NaN rows in `popt` and `pcov`); a start point with NaN residuals ends the same way.
+            The batch mates are not affected.  Not yet supported, each a ValueError: a callable or an ``ExprModel`` as `f`,
+            ``jac='2-point'`` / ``'3-point'``, ``loss=`` other than 'linear', ``estimator='poisson'``,
+            ``nan_policy='omit'``, `fixed` / `tied`, ``response=`` and ``leverage=True``.
 
     Returns ``(popt (B, n), pcov (B, n, n), results)``, `results` the B ``OptimizeResult`` of the solve.  pcov[b] is
     ``curve_fit``'s for problem b alone: the pseudo-inverse covariance of its final Jacobian, times
@@ -651,6 +678,11 @@ def curve_fit_batch(f, xdata, ydata, p0, sigma=None, absolute_sigma=False, bound
     if P0.ndim != 2 or P0.shape[0] != B:
         raise ValueError("`p0` must have shape (B, n).")
     n = P0.shape[1]
+    if not isinstance(separable, (bool, np.bool_)):
+        raise ValueError("`separable` must be False or True.")
+    if separable:
+        return _fit_separable(f, xdata, ydata, P0, sigma, absolute_sigma, bounds, method, jac, driver, ctx, fixed, tied,
+                              estimator, binned, nan_policy, response, kwargs)
 
     def xdata_of(xdata, model):                  # a named model checks its abscissae (or bin edges); one array for both
         if model is not None:
@@ -673,6 +705,149 @@ def curve_fit_batch(f, xdata, ydata, p0, sigma=None, absolute_sigma=False, bound
             r.x, r.active_mask = X_full[b], masks[b]
         for b, C in zip(has_cov, covs):
             results[b].x_covariance = C
+    return _popt_pcov(results, (B, n), no_dof, lambda r: r.x, lambda C: C) + (results,)
+
+
+def _full_covariance(ctx, model, n, x, ydata, sigma, binned, popt, scale):
+    """The pseudo-inverse covariance of the plain model's Jacobian at `popt` (B, n), computed on the device (the model
+    kernel, then blsq_cov_pinv_dev with `scale` (B,) or None): ``(cov (B, n, n), rank, rcond, status)``.  B n^2 + 3 B
+    numbers come back."""
+    import ctypes as C
+    from ._abi import vp
+    B, m = ydata.shape
+    bufs, h = [], vp()
+    try:
+        with _models.DeviceModel(ctx, _models.resolvable(model), B, m, n, x, ydata, sigma,
+                                 **({'binned': True} if binned else {})) as dm:
+            def dev(nbytes):
+                bufs.append(ctx.malloc(nbytes))
+                return bufs[-1]
+            d_P = ctx.to_device(np.ascontiguousarray(popt, dtype=np.float64))
+            bufs.append(d_P)
+            d_J, d_cov, d_rcond, d_kept = dev(8 * B * m * n), dev(8 * B * n * n), dev(8 * B), dev(8 * B)
+            d_rank, d_status = dev(4 * B), dev(4 * B)
+            d_scale = None
+            if scale is not None:
+                d_scale = ctx.to_device(np.ascontiguousarray(scale, dtype=np.float64))
+                bufs.append(d_scale)
+            dm.jac_dev(d_P, d_J)
+            ctx.check(ctx.lib.blsq_cov_plan_create(ctx.h, B, m, n, C.byref(h)), "blsq_cov_plan_create")
+            ctx.check(ctx.lib.blsq_cov_pinv_dev(h, d_J, None, d_scale, d_cov, d_rank, d_rcond, d_kept, d_status),
+                      "blsq_cov_pinv_dev")
+            ctx.sync()
+            return (ctx.to_host(d_cov, (B, n, n), np.float64), ctx.to_host(d_rank, (B,), np.int32),
+                    ctx.to_host(d_rcond, (B,), np.float64), ctx.to_host(d_status, (B,), np.int32))
+    finally:
+        if h:
+            ctx.lib.blsq_cov_plan_destroy(h)
+        for p in bufs:
+            ctx.free(p)
+
+
+def _fit_separable(f, xdata, ydata, P0, sigma, absolute_sigma, bounds, method, jac, driver, ctx, fixed, tied, estimator,
+                   binned, nan_policy, response, kwargs):
+    """``curve_fit_batch(separable=True)``: the checks, the solve over the non-linear parameters, the
+    linear ones filled in and the covariance of the full problem at the result."""
+    B, m = ydata.shape
+    n = P0.shape[1]
+    if isinstance(f, _models.ExprModel):
+        raise ValueError("`separable=True` is not yet supported with the expression model '%s': the structure of a "
+                         "formula is not known." % f.name)
+    if not isinstance(f, (str, _models.CompositeModel)):
+        raise ValueError("`separable=True` needs a built-in model (a name, a spec or a CompositeModel) as `f`: the "
+                         "linear parameters of a callable are not known.")
+    if jac is not None:
+        raise ValueError("`jac` must be None with `separable=True`: Kaufman's Jacobian comes from the model's analytic "
+                         "one ('2-point' / '3-point' and a callable are not yet supported).")
+    if kwargs.get('loss', 'linear') != 'linear':
+        raise ValueError("`loss` must be 'linear' with `separable=True`: a robust loss is not yet supported.")
+    if _models.check_estimator(estimator) != 'lse':
+        raise ValueError("estimator='poisson' is not yet supported with `separable=True`.")
+    if nan_policy == 'omit':
+        raise ValueError("nan_policy='omit' is not yet supported with `separable=True`.")
+    if nan_policy == 'raise':
+        if np.isnan(ydata).any():
+            raise ValueError("The input contains nan values")
+    elif nan_policy is not None:
+        raise ValueError("`nan_policy` must be None or 'raise' with `separable=True`, not %r." % (nan_policy,))
+    if fixed is not None or tied:
+        raise ValueError("`fixed` / `tied` are not yet supported with `separable=True`.")
+    if response is not None:
+        raise ValueError("`response` is not yet supported with `separable=True`.")
+    if kwargs.get('leverage', False):
+        raise ValueError("leverage=True is not yet supported with `separable=True`.")
+    if driver not in ('host', 'device'):
+        raise ValueError("`driver` must be 'host' or 'device'.")
+    if 'args' in kwargs:
+        raise ValueError("'args' is not a supported keyword argument.")
+    kwargs = dict(kwargs)
+    if 'max_nfev' not in kwargs:
+        kwargs['max_nfev'] = kwargs.pop('maxfev', None)
+    model = _models.resolve(f)
+    model.terms(n)
+    lin, owner = _models.linear_params(model, n)
+    if m <= lin.size:
+        raise ValueError("`separable=True` needs more points than linear parameters: m = %d, nl = %d." % (m, lin.size))
+    host_model = _models.binned(model) if binned else model
+    x = host_model.check_xdata(xdata, B, m)[0]
+    if len(bounds) != 2:
+        raise ValueError("`bounds` must contain 2 elements.")
+    try:
+        lb = np.broadcast_to(np.asarray(bounds[0], dtype=float), (B, n))
+        ub = np.broadcast_to(np.asarray(bounds[1], dtype=float), (B, n))
+    except ValueError:
+        raise ValueError("`bounds` must be broadcastable to (B, n): they keep all n parameters.") from None
+    names = getattr(model, 'param_names', None)
+    for k in lin:
+        if not (np.all(lb[:, k] == -np.inf) and np.all(ub[:, k] == np.inf)):
+            raise ValueError("`separable=True`: parameter %d%s is linear and is projected out, so its bounds must be "
+                             "infinite; fit without `separable=True` to bound it."
+                             % (k, " ('%s')" % names[k] if names else ""))
+    if sigma is not None:
+        sigma = np.asarray(sigma, float)
+        try:
+            _models.sigma_weights(sigma, (B,), m)
+        except ValueError:
+            if sigma.ndim != 2:
+                raise
+            raise ValueError("a 2-D covariance `sigma` is not supported by `curve_fit_batch`.") from None
+    non = np.nonzero(owner >= 0)[0]
+    X0, red = np.ascontiguousarray(P0[:, non]), (lb[:, non], ub[:, non])
+    if ctx is None:
+        from ._hip_step import default_context
+        ctx = default_context()
+    spec = _models.resolvable(model)
+    on = {'binned': True} if binned else {}
+    if driver == 'device':
+        func = _models.DeviceFit(spec, n, x, ydata, sigma, separable=True, **on)
+        results = least_squares_batch(func, X0, None, bounds=red, method=method, driver=driver, ctx=ctx, **kwargs)
+        X = np.stack([r.x for r in results])
+        with _models.DeviceModel(ctx, spec, B, m, n, x, ydata, sigma, separable=True, **on) as dm:
+            d_X = ctx.to_device(X)
+            try:
+                c = dm.linear_coefficients(d_X)
+            finally:
+                ctx.free(d_X)
+    else:
+        from ._varpro import _HostStage
+        stage = _HostStage(model, ydata, sigma, n, binned)
+        results = least_squares_batch(lambda X: stage(x, X)[0], X0, lambda X: stage(x, X)[1], bounds=red, method=method,
+                                      driver=driver, ctx=ctx, **kwargs)
+        X = np.stack([r.x for r in results])
+        c = stage(x, X)[2]
+    popt = _models.varpro_expand(X, lin, n)
+    popt[:, lin] = c
+    obj = np.array([r.obj_value for r in results], dtype=float)
+    scale = obj / (m - n) if (m > n and not absolute_sigma) else None
+    cov, rank, rcond, status = _full_covariance(ctx, model, n, x, ydata, sigma, binned, popt, scale)
+    for b, r in enumerate(results):
+        mask = np.zeros(n, dtype=np.asarray(r.active_mask).dtype)
+        mask[non] = r.active_mask
+        r.x_nonlinear, r.linear_params = r.x, lin.copy()
+        r.x, r.active_mask = popt[b].copy(), mask
+        r.x_covariance = None if int(status[b]) != 0 else cov[b]
+        r.x_covariance_rank, r.x_covariance_rcond = int(rank[b]), float(rcond[b])
+    no_dof = np.full(B, (m <= n) and not absolute_sigma)
     return _popt_pcov(results, (B, n), no_dof, lambda r: r.x, lambda C: C) + (results,)
 
 

@@ -80,6 +80,11 @@ Expression models (``expression``; blsq_expr_eval_dev).  ``express
 own interprets per row, with the exact Jacobian from a reverse sweep.  bounded_lsq/_expr.py has the language and the
 numpy interpreter that IS the definition.  An ``ExprModel`` is taken wherever a ``CompositeModel`` is, except by
 ``binned=True`` and by global fits (ValueError).
+
+Separable fits (``separable=True``; blsq_varpro_expand_dev, blsq_varpro_reduce_dev).  The parameters a model
+is linear in (``linear_params``: amplitudes, polynomial coefficients, offsets) are projected out, so that the solver sees
+the others alone: bounded_lsq/_varpro.py has the scheme and ``varpro_reduce``, which IS the definition; on the device
+the projection is a second stage behind the model kernel, which is called for the raw Jacobian at unit linear parameters.
 """
 import re
 
@@ -87,6 +92,8 @@ import numpy as np
 
 from . import _abi
 from ._expr import ExprModel, expression
+from ._varpro import (VARPRO_MAX_NL, VARPRO_PIVOT_TOL, linear_params, varpro_reduce, varpro_expand, separable_residual,
+                      separable_jacobian, separable_coefficients)
 
 MAX_N = 64                                   # BLSQ_MODEL_MAX_N
 MAX_COMP = 8                                 # BLSQ_MODEL_MAX_COMP
@@ -104,7 +111,9 @@ __all__ = ['MODELS', 'NAMES', 'MAX_N', 'MAX_COMP', 'TERMS', 'get', 'compose', 'r
            'poisson_transform', 'poisson_residual', 'poisson_jacobian', 'binned', 'bin_rows', 'BinnedModel', 'erf_diff',
            'psi_pair', 'PSI_X0', 'PSI_TERMS', 'SAMPLING', 'NAN_POLICIES', 'check_nan_policy', 'omit_residual',
            'omit_jacobian', 'count_observed', 'pad_ragged', 'RESPONSE_MAX_L', 'check_response', 'apply_response',
-           'response_residual', 'response_jacobian', 'expression', 'ExprModel']
+           'response_residual', 'response_jacobian', 'expression', 'ExprModel', 'VARPRO_MAX_NL', 'VARPRO_PIVOT_TOL',
+           'linear_params', 'varpro_reduce', 'varpro_expand', 'separable_residual', 'separable_jacobian',
+           'separable_coefficients', 'check_separable']
 
 
 def _tp(xdata, P):
@@ -958,6 +967,18 @@ def check_expr_model(model, binned=False, global_fit=False):
             raise ValueError("the expression model '%s' is not supported in a global fit." % model.name)
 
 
+def check_separable(model, n, param_map=None, estimator='lse', nan_policy='propagate', global_map=None, response=None):
+    """``linear_params(model, n)`` after what a separable fit does not take, as ValueErrors: a parameter
+    map, the Poisson estimator, omission, a global fit and an instrument response (an ``ExprModel`` and a model without
+    a non-linear parameter are refused by ``linear_params``)."""
+    for what, given in (("`fixed` / `tied` (a parameter map)", param_map is not None),
+                        ("estimator='poisson'", estimator != 'lse'), ("nan_policy='omit'", nan_policy != 'propagate'),
+                        ("a global fit", global_map is not None), ("`response`", response is not None)):
+        if given:
+            raise ValueError("%s is not yet supported with `separable=True`." % what)
+    return linear_params(model, n)
+
+
 def check_global(model, binned=False, param_map=None):
     """What a global fit does not take, as ValueErrors."""
     check_expr_model(model, global_fit=True)
@@ -1046,14 +1067,28 @@ class DeviceModel:
 
     An ``ExprModel``: the callbacks go through blsq_expr_eval_dev alone, with the program of
     ``model.bind(param_map)`` (fixed and tied parameters are leaves of the program: the entry takes no map), under
-    every flag above but `binned` and `global_map` (ValueError)."""
+    every flag above but `binned` and `global_map` (ValueError).
+
+    ``separable=True``: the linear parameters of the model (``linear_params``) are projected out.  ``n``
+    is then the number of the others, the width of x and J, and ``n_model`` stays n; the entry above is bound as
+    ``evaluate`` binds it and writes the raw Jacobian at unit linear parameters into a scratch buffer of this object,
+    between blsq_varpro_expand_dev and blsq_varpro_reduce_dev on the same stream: three launches per evaluation, for
+    ``fun_dev`` and ``jac_dev`` alike (f needs Phi too); `reps` must be 1.  ``linear_coefficients(x_ptr)`` runs the stage
+    at x and returns c (B, nl), ``rank_info(x_ptr)`` its info flags.  `ydata` is required; `binned` and `sigma` compose;
+    a map, the Poisson estimator, omission, `global_map`, `response` and an ``ExprModel`` are ValueErrors."""
 
     def __init__(self, ctx, name, B, m, n, xdata, ydata=None, sigma=None, param_map=None, Pfix=None, estimator='lse',
-                 binned=False, nan_policy='propagate', global_map=None, response=None, response_origin=0):
+                 binned=False, nan_policy='propagate', global_map=None, response=None, response_origin=0,
+                 separable=False):
         model = resolve(name)
         model.terms(n)
         gm = global_map
         check_expr_model(model, binned)
+        self.separable = bool(separable)
+        if self.separable:
+            self.lin, self.owner = check_separable(model, n, param_map, estimator, nan_policy, gm, response)
+            if ydata is None:
+                raise ValueError("`separable=True` needs `ydata`: the linear parameters are fitted to it.")
         if gm is not None:
             check_global(model, binned, param_map)
         self.response = None
@@ -1082,6 +1117,11 @@ class DeviceModel:
             self.t_stride = (2 if self.binned else 1) * model.coords * m if per_problem else 0
             self.t_sstride, lead, dims, pm, shared = 0, (B,), "B", param_map, None
             self.m, self.n = m, self.n_model if pm is None else pm.nf
+            if self.separable:
+                self.n = self.n_model - len(self.lin)
+                if m <= len(self.lin):
+                    raise ValueError("`separable=True` needs more points than linear parameters: m = %d, nl = %d."
+                                     % (m, len(self.lin)))
         else:
             x, self.t_stride, self.t_sstride = global_xdata(xdata, B, gm.S, m)
             lead, dims, pm = (B, gm.S), "G, S", gm.pm
@@ -1118,6 +1158,8 @@ class DeviceModel:
         self._bind(m, pm, pmap, shared)
         if self.response is not None:
             self._bind_response()
+        if self.separable:
+            self._bind_separable()
         ctx.adopt(self)
 
     def _upload(self, a):
@@ -1139,10 +1181,11 @@ class DeviceModel:
         set; `pm`: the ParamMap of the fit (a global fit's own) or None, `pmap` its int32 map; `shared`: the int32 flags of
         the slots a group shares, or None."""
         M, comp, gm = self.model, isinstance(self.model, CompositeModel), self.global_map
-        # behind an instrument response the entry gives the raw model: data, weights, estimator and omission are withheld
+        # behind an instrument response or the projection of a separable fit the entry gives the raw model: data,
+        # weights, estimator and omission are withheld
         estimator, nan_policy, d_y, d_w, w_stride = (
-            (self.estimator, self.nan_policy, self.d_y, self.d_w, self.w_stride) if self.response is None
-            else ('lse', 'propagate', None, None, 0))
+            (self.estimator, self.nan_policy, self.d_y, self.d_w, self.w_stride)
+            if self.response is None and not self.separable else ('lse', 'propagate', None, None, 0))
         if isinstance(M, ExprModel):                          # the program behind the map, and the one entry that runs it
             prog = M.bind(pm).program
             ops, consts = np.ascontiguousarray(prog.ops, dtype=np.uint64), np.ascontiguousarray(prog.consts)
@@ -1188,7 +1231,7 @@ class DeviceModel:
             cnt=host(M.counts) if comp else None,
             S=0 if gm is None else gm.S, shared=host(shared), t_sstride=self.t_sstride,       # S == 0: a plain batch
             B=self.B, reps=1, m=m, n=self.n_model,
-            nf=self.n if gm is None else gm.nf, pmap=host(pmap),                              # nf: per data set
+            nf=(self.n_model if self.separable else self.n) if gm is None else gm.nf, pmap=host(pmap),   # nf: per data set
             tie_ratio=host(ratio, _abi.c_double_p), tie_offset=host(offset, _abi.c_double_p),
             t=self.d_t, t_stride=self.t_stride, y=d_y, w=d_w, w_stride=w_stride, X=None,
             Pfix=self.d_Pfix, f=None, J=None, mask=None)
@@ -1244,6 +1287,45 @@ class DeviceModel:
                       "blsq_response_apply_dev")
         self._eval = _eval
 
+    def _bind_separable(self):
+        """The stages around the model kernel: the scratch buffers P (B, n) and G (B, m, n), and `self._eval` replaced
+        by the three launches expand -> model kernel (Jacobian) -> reduce.  All go onto the context's stream, so nothing
+        synchronises in between."""
+        ctx, inner = self.ctx, self._eval
+        B, m, n, nl = self.B, self.m, self.n_model, len(self.lin)
+        lin, owner = (np.ascontiguousarray(a, dtype=np.int32) for a in (self.lin, self.owner))
+        self._host_sep = (lin, owner)                         # the host arrays the entries read: alive with the model
+        p_lin, p_owner = lin.ctypes.data_as(_abi.c_int32_p), owner.ctypes.data_as(_abi.c_int32_p)
+        d_P, d_G = ctx.malloc(8 * B * n), ctx.malloc(8 * B * m * n)
+        self._bufs += [d_P, d_G]
+        tail = [self.d_y, self.d_w, self.w_stride]
+
+        def _eval(x_ptr, reps, f_ptr, J_ptr, mask_ptr, c_ptr=None, info_ptr=None):
+            if int(reps) != 1:
+                raise ValueError("`separable=True` evaluates one point per problem: reps must be 1 (finite-difference "
+                                 "Jacobians are not supported).")
+            ctx.check(ctx.lib.blsq_varpro_expand_dev(ctx.h, B, n, nl, p_lin, x_ptr, d_P), "blsq_varpro_expand_dev")
+            inner(d_P, 1, None, d_G, mask_ptr)
+            ctx.check(ctx.lib.blsq_varpro_reduce_dev(ctx.h, B, m, n, nl, p_lin, p_owner, d_G, *tail, f_ptr, J_ptr, c_ptr,
+                                                     info_ptr, mask_ptr), "blsq_varpro_reduce_dev")
+        self._eval = _eval
+
+    def linear_coefficients(self, x_ptr, with_info=False):
+        """c (B, nl) of a separable model at the device vectors x [B][n]: the stage is run there, because the driver's
+        last evaluation may have been at a rejected trial point.  ``with_info=True``: ``(c, info)``, info (B,) int32
+        with 1 where Phi is rank deficient at x (c is NaN there)."""
+        if not self.separable:
+            raise ValueError("the model was not opened with `separable=True`.")
+        ctx, B, nl = self.ctx, self.B, len(self.lin)
+        d_c, d_info = ctx.malloc(8 * nl * B), ctx.malloc(4 * B)
+        try:
+            self._eval(x_ptr, 1, None, None, None, c_ptr=d_c, info_ptr=d_info)
+            c = ctx.to_host(d_c, (B, nl), np.float64)
+            return (c, ctx.to_host(d_info, (B,), np.int32)) if with_info else c
+        finally:
+            ctx.free(d_c)
+            ctx.free(d_info)
+
     def fun_dev(self, x_ptr, f_ptr, reps=1):
         self._eval(x_ptr, reps, f_ptr, None, None)
 
@@ -1271,14 +1353,19 @@ class DeviceFit:
     ``n`` is the number of solver variables (the width of x0): the model's n, or nf of `param_map`; ``n_model`` is the
     model's number of parameters.  ``estimator='poisson'``, ``binned=True`` and ``nan_policy='omit'``: as
     ``DeviceModel``.  ``global_map=``: as ``DeviceModel``; `ydata` is (G, S, m), and ``B`` is G, ``m`` is S m and ``n``
-    is nv.  ``response=``, ``response_origin=``: as ``DeviceModel`` (checked here, before any GPU is touched)."""
+    is nv.  ``response=``, ``response_origin=``: as ``DeviceModel`` (checked here, before any GPU is touched).
+    ``separable=True``: as ``DeviceModel``; ``n`` is the number of non-linear parameters and ``lin`` / ``owner`` are
+    those of ``linear_params``."""
 
     def __init__(self, name, n, xdata, ydata, sigma=None, param_map=None, Pfix=None, estimator='lse', binned=False,
-                 nan_policy='propagate', global_map=None, response=None, response_origin=0):
+                 nan_policy='propagate', global_map=None, response=None, response_origin=0, separable=False):
         self.model = resolve(name)
         self.model.terms(n)
         gm = self.global_map = global_map
         check_expr_model(self.model, binned)
+        self.separable = bool(separable)
+        if self.separable:
+            self.lin, self.owner = check_separable(self.model, n, param_map, estimator, nan_policy, gm, response)
         if gm is not None:
             check_global(self.model, binned, param_map)
         self.response, self.response_origin = None, 0
@@ -1315,6 +1402,11 @@ class DeviceFit:
         if gm is None:
             self.m, self.n = self._m_set, self.n_model if param_map is None else param_map.nf
             self.xdata = (BinnedModel(self.model) if self.binned else self.model).check_xdata(xdata, self.B, self.m)[0]
+            if self.separable:
+                self.n = self.n_model - len(self.lin)
+                if self.m <= len(self.lin):
+                    raise ValueError("`separable=True` needs more points than linear parameters: m = %d, nl = %d."
+                                     % (self.m, len(self.lin)))
         else:
             self.m, self.n = gm.S * self._m_set, gm.nv
             self.xdata = global_xdata(xdata, self.B, gm.S, self._m_set)[0]
@@ -1325,7 +1417,8 @@ class DeviceFit:
         dm = DeviceModel(ctx, resolvable(self.model), self.B, self._m_set, self.n_model, xdata, self.ydata, self.sigma,
                          self.param_map, self.Pfix, self.estimator, self.binned, self.nan_policy, self.global_map,
                          **({} if self.response is None
-                            else {'response': self.response, 'response_origin': self.response_origin}))
+                            else {'response': self.response, 'response_origin': self.response_origin}),
+                         **({'separable': True} if self.separable else {}))
         dm.set_bounds(lb, ub)
         return dm
 

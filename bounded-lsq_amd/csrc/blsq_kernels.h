@@ -766,6 +766,39 @@ hipError_t launch_bvls_moments(const BvlsMomentsCall& c, hipStream_t s);
 hipError_t launch_bvls_solve(const BvlsSolveCall& c, hipStream_t s);
 size_t bvls_solve_lds_bytes(int n);   // dynamic LDS of one problem
 
+// ---------------------------------------------------- separable fits (7v) ----
+// varpro_kernels.hip.  The model parameters P [B][n] of the solver variables X [B][n - nl]: 1.0 in the slots lin
+// (blsq_varpro_expand_dev) ...
+struct VarproExpandCall {
+  int B, n, nl;
+  const int* lin;         // host [nl], ascending
+  const double* X;
+  double* P;
+};
+// ... and the projection behind the model kernel's raw Jacobian G [B][m][n] (blsq_varpro_reduce_dev): the reduced
+// residual f [B][m], Kaufman's Jacobian J [B][m][n - nl], the linear parameters c [B][nl] and info [B] (1: Phi rank
+// deficient, the outputs NaN), each or nullptr; problems with mask[b] == 0 are neither read nor written.
+struct VarproReduceCall {
+  int B, m, n, nl;
+  const int* lin;         // host [nl], ascending
+  const int* owner;       // host [n]: -1 on lin, elsewhere the position in lin of the column's amplitude
+  const double* G;
+  const double* y;        // [B][m]
+  const double* w; long w_stride;   // nullptr (1), or stride 0 / m
+  double* f;
+  double* J;
+  double* c;
+  int* info;
+  const int* mask;        // nullptr or [B]
+};
+// hipErrorInvalidValue, and nothing launched, for a size below 1, n above BLSQ_MODEL_MAX_N, nl outside
+// 1 .. BLSQ_VARPRO_MAX_NL or not below n, m <= nl, lin not ascending within 0 .. n - 1, an owner that contradicts lin,
+// a missing lin, owner, G, y, X or P, no output, or a stride other than the two w has: the refusals that keep the
+// kernels' offsets in bounds.
+hipError_t launch_varpro_expand(const VarproExpandCall& c, hipStream_t s);
+hipError_t launch_varpro_reduce(const VarproReduceCall& c, hipStream_t s);
+size_t varpro_lds_bytes(int na);      // dynamic LDS of one problem with na = n - nl non-linear columns
+
 // ---------------------------------------------------------------- probes ----
 // probe_kernels.hip: measured peaks / counter calibration (blsq_debug_probe)
 hipError_t launch_mfma_probe(int waves_per_simd, int iters, double* sink, long* n_mfma,

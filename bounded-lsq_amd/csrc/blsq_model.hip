@@ -1,5 +1,5 @@
 // Built-in fit models (include/blsq.h; kernel: model_kernels.hip): the model and term tables behind
-// blsq_model_count / _info and blsq_term_count / _info, the entries blsq_linear_eval_dev, blsq_expr_check, blsq_expr_eval_dev, blsq_bvls_moments_dev, blsq_bvls_solve_dev and blsq_response_apply_dev, and the eight entries blsq_model_eval_dev, _map_dev, _comp_dev,
+// blsq_model_count / _info and blsq_term_count / _info, the entries blsq_linear_eval_dev, blsq_expr_check, blsq_expr_eval_dev, blsq_bvls_moments_dev, blsq_bvls_solve_dev, blsq_response_apply_dev, blsq_varpro_expand_dev and blsq_varpro_reduce_dev, and the eight entries blsq_model_eval_dev, _map_dev, _comp_dev,
 // _est_dev, _bin_dev, _nan_dev, _global_dev and _tie_dev.  An entry fills a ModelEvalCall from its arguments (what its signature
 // does not have is the default) and hands it to model_eval_checked with its EvalEntry: one list of checks, one launcher, and per entry
 // only the argument numbers.
@@ -427,4 +427,63 @@ extern "C" int blsq_response_apply_dev(blsq_ctx* ctx, int est, int nan_policy, i
   HIPCHK(ctx, hipSetDevice(ctx->device));
   const ResponseCall c{est, nan_policy, B, reps, m, nc, L, origin, dh, h_stride, dg, dG, dy, dw, w_stride, df, dJ, dmask};
   return ctx->run(K_MODEL_EVAL, "launch_response_apply", [&] { return launch_response_apply(c, ctx->stream); });
+}
+
+// Separable fits (varpro_kernels.hip): the solver variables expanded to model parameters with 1.0 in the
+// linear slots, and the projection behind the model kernel's raw Jacobian.  lin and owner are host arrays that travel
+// in the kernel arguments.  The checks in the order of the arguments; each entry is one timed call in the slot of the
+// model evaluations.
+namespace {
+
+// lin is NULL, not ascending or leaves 0 .. n - 1
+bool varpro_lin_bad(int n, int nl, const int32_t* lin) {
+  if (!lin) return true;
+  for (int k = 0; k < nl; ++k)
+    if (lin[k] < 0 || lin[k] >= n || (k > 0 && lin[k] <= lin[k - 1])) return true;
+  return false;
+}
+
+}  // namespace
+
+extern "C" int blsq_varpro_expand_dev(blsq_ctx* ctx, int B, int n, int nl, const int32_t* lin, const double* dX,
+                                      double* dP) {
+  if (!ctx) return -1;
+  if (B <= 0) return ctx->bad(2, "B must be positive");
+  if (n < 2 || n > BLSQ_MODEL_MAX_N) return ctx->bad(3, "n must be in 2 .. BLSQ_MODEL_MAX_N");
+  if (nl < 1 || nl > BLSQ_VARPRO_MAX_NL || nl >= n)
+    return ctx->bad(4, "nl must be in 1 .. BLSQ_VARPRO_MAX_NL and leave a non-linear parameter (nl < n)");
+  if (varpro_lin_bad(n, nl, lin)) return ctx->bad(5, "lin is NULL or not ascending within 0 .. n - 1");
+  if (!dX) return ctx->bad(6, "X is NULL (the solver variables)");
+  if (!dP) return ctx->bad(7, "P is NULL");
+  HIPCHK(ctx, hipSetDevice(ctx->device));
+  const VarproExpandCall c{B, n, nl, lin, dX, dP};
+  return ctx->run(K_MODEL_EVAL, "launch_varpro_expand", [&] { return launch_varpro_expand(c, ctx->stream); });
+}
+
+extern "C" int blsq_varpro_reduce_dev(blsq_ctx* ctx, int B, int m, int n, int nl, const int32_t* lin,
+                                      const int32_t* owner, const double* dG, const double* dy, const double* dw,
+                                      long w_stride, double* df, double* dJ, double* dc, int32_t* dinfo,
+                                      const int32_t* dmask) {
+  if (!ctx) return -1;
+  if (B <= 0) return ctx->bad(2, "B must be positive");
+  if (m <= 0) return ctx->bad(3, "m must be positive");
+  if (n < 2 || n > BLSQ_MODEL_MAX_N) return ctx->bad(4, "n must be in 2 .. BLSQ_MODEL_MAX_N");
+  if (nl < 1 || nl > BLSQ_VARPRO_MAX_NL || nl >= n)
+    return ctx->bad(5, "nl must be in 1 .. BLSQ_VARPRO_MAX_NL and leave a non-linear parameter (nl < n)");
+  if (m <= nl) return ctx->bad(3, "m must exceed nl: the linear parameters must leave a residual");
+  if (varpro_lin_bad(n, nl, lin)) return ctx->bad(6, "lin is NULL or not ascending within 0 .. n - 1");
+  if (!owner) return ctx->bad(7, "owner is NULL");
+  for (int j = 0, at = 0; j < n; ++j) {
+    const bool linear = at < nl && lin[at] == j;
+    if (linear) ++at;
+    if (linear ? owner[j] != -1 : (owner[j] < 0 || owner[j] >= nl))
+      return ctx->bad(7, "owner must be -1 on lin and a position 0 .. nl - 1 in lin elsewhere");
+  }
+  if (!dG) return ctx->bad(8, "G is NULL (the raw Jacobian)");
+  if (!dy) return ctx->bad(9, "y is NULL");
+  if (dw && w_stride != 0 && w_stride != (long)m) return ctx->bad(11, "w_stride must be 0 or m");
+  if (!df && !dJ && !dc) return ctx->bad(12, "f, J and c are all NULL");
+  HIPCHK(ctx, hipSetDevice(ctx->device));
+  const VarproReduceCall c{B, m, n, nl, lin, owner, dG, dy, dw, w_stride, df, dJ, dc, dinfo, dmask};
+  return ctx->run(K_MODEL_EVAL, "launch_varpro_reduce", [&] { return launch_varpro_reduce(c, ctx->stream); });
 }

@@ -733,6 +733,45 @@ int blsq_expr_eval_dev(blsq_ctx* ctx, int est, int nan_policy, int B, int reps, 
                        long t_stride, const double* dy, const double* dw, long w_stride, const double* dX,
                        const double* dPfix, double* df, double* dJ, const int32_t* dmask);
 
+/* ---- separable fits: variable projection of the linear parameters -----------------------------------
+ * A model sum_k c_k phi_k(t; alpha) is linear in nl of its n parameters (amplitudes, polynomial coefficients, offsets).
+ * For given alpha the best c solves a small linear least-squares problem, so the solver sees the na = n - nl others
+ * alone (Golub and Pereyra), with Kaufman's Jacobian.  Three calls per evaluation: blsq_varpro_expand_dev, any
+ * blsq_model_eval*_dev entry called for J with y = NULL, w = NULL, no estimator and no omission, and
+ * blsq_varpro_reduce_dev.
+ *
+ * lin: HOST int32 [nl], the ascending indices of the linear parameters.  owner: HOST int32 [n], -1 on lin and, for
+ * every other parameter, the position in lin of the amplitude its column scales with (mu, s and eta of a pvoigt term:
+ * its a).  Both are read during the call and travel in the kernel arguments.  bounded_lsq/_varpro.py (linear_params,
+ * varpro_expand, varpro_reduce) IS the definition.
+ *
+ * blsq_varpro_expand_dev: dP [B][n] = 1.0 in the slots lin and dX [B][na] in the others, in ascending order: bit-exact.
+ *
+ * blsq_varpro_reduce_dev: dG [B][m][n] is the raw Jacobian at dP, so dG[:, lin] = Phi.  With Phi_w = w Phi,
+ * A_w = [w G[:, non] | w y] and S = Phi_w^T Phi_w:
+ *   T  = S^-1 Phi_w^T A_w     E  = A_w - Phi_w T
+ *   T2 = S^-1 Phi_w^T E       E <- E - Phi_w T2,  T <- T + T2          (one correction against Phi_w itself)
+ *   dc = T[:, last]   df = -E[:, last] = w (Phi c - y)   dJ[:, i] = c[owner[non[i]]] E[:, i]
+ * dJ^T df is the exact gradient of 1/2 |df|^2.  The correction keeps the error of every output at a small multiple of
+ * kappa(Phi_w) eps; without it the error is kappa^2 eps.  S is scaled to unit diagonal before its Cholesky factor;
+ * a diagonal entry of S that is not positive and finite, or a pivot of the scaled matrix that is not above 64 eps, marks
+ * Phi as rank deficient: dinfo[b] = 1 and every output of problem b is NaN; dinfo[b] = 0 otherwise.
+ * dy: [B][m]; dw: NULL (1), [m] (w_stride 0) or [B][m] (w_stride m); df [B][m], dJ [B][m][na], dc [B][nl], dinfo [B]:
+ * each may be NULL (not all of df, dJ, dc).  dmask: int32 [B] or NULL: a problem with dmask[b] == 0 is left untouched
+ * and nothing of it is read.  One workgroup per problem; the moments and both projections run on the FP64 MFMA pipe.
+ * The summation order is a function of m and the layout (lin, owner) alone: a problem's bits do not depend on B or on
+ * its position in the batch.  1 <= nl <= BLSQ_VARPRO_MAX_NL, na >= 1, n <= BLSQ_MODEL_MAX_N, m > nl.
+ * All other pointers are device pointers; asynchronous on the ctx stream; each call is one unit of the `model_eval`
+ * slot.  A negative return is the index of the bad argument (expand: ctx = 1, B = 2, n = 3, nl = 4, lin = 5: NULL, not
+ * ascending or out of range, X = 6, P = 7; reduce: ctx = 1, B = 2, m = 3: not positive or m <= nl, n = 4, nl = 5:
+ * outside 1 .. BLSQ_VARPRO_MAX_NL or nl >= n, lin = 6, owner = 7: NULL or inconsistent with lin, G = 8, y = 9, w,
+ * w_stride = 11, f = 12: f, J and c all NULL, J, c, info, mask); nothing is launched then. */
+#define BLSQ_VARPRO_MAX_NL 16
+int blsq_varpro_expand_dev(blsq_ctx* ctx, int B, int n, int nl, const int32_t* lin, const double* dX, double* dP);
+int blsq_varpro_reduce_dev(blsq_ctx* ctx, int B, int m, int n, int nl, const int32_t* lin, const int32_t* owner,
+                           const double* dG, const double* dy, const double* dw, long w_stride, double* df, double* dJ,
+                           double* dc, int32_t* dinfo, const int32_t* dmask);
+
 /* ---- parameter covariance from the final Jacobian --------------------------------------------------------------
  * The reference documents `x_covariance` as the inverse of J^T J at the solution (least_squares.py:248-252) and fills
  * it only through its MINPACK bridge (method='lm').  Here, per problem, from a Householder triangle R of J (the TSQR

@@ -59,10 +59,20 @@ the equivalent 'exp*2+poly*1' (a f, 1 / t1, a (1 - f), 1 / t2, bg) for orientati
 the model's numpy definition.  With ``--kernel``: the launches of blsq_expr_eval_dev alone, f and J apart (and, for the
 default decay, those of the composite entry at the same shape).
 
+``--separable`` fits with the linear parameters projected out: the default problems ('gauss_sum', or
+``--peaks 2``), sigma 0.01, no bounds.  Routes, alternating: `separable`, ``curve_fit_batch(separable=True)`` on the
+device with NaN in the linear entries of p0 (expand, the model kernel, blsq_varpro_reduce_dev per evaluation, then c and
+the covariance of the full problem); `plain`, the same fit without the keyword from the same non-linear start, its linear
+entries 10 % off the truth.  Reported: the median time of a call, the mean and the largest nfev of each route, and the
+problems that converged.  With ``--kernel``: the time per evaluation in the 'model_eval' slot (HIP events) of the three
+launches of the separable stage against the plain model kernel, f and J apart.  It takes --B, --m, --peaks, --repeat,
+--kernel, --launches and --rounds only.
+
 usage: python tools/bench_models.py [--B 4096] [--m 64] [--repeat 5] [--peaks 1] [--fixed 1,4] [--tied 5:2,4:1:1:0.42] [--kernel]
                                     [--launches 50] [--rounds 1] [--estimator lse] [--binned] [--omit FRACTION]
                                     [--global S --shared 1,2] [--response L [--n 4]]
                                     [--expr TEXT --params a,b,c [--truth 3,0.4,0.5,2.5,0.2] [--kernel]]
+                                    [--separable [--kernel]]
 """
 import argparse
 import json
@@ -426,6 +436,66 @@ def expr_bench(a, ctx):
                                               / (np.abs(out["callable"][0][both]) + 1e-3)))}
 
 
+def separable_bench(a, ctx):
+    """--separable: the separable fit against the plain one, or (--kernel) the three launches against the model kernel."""
+    x, Y, P0, _ = problems(a.B, a.m, peaks=a.peaks)
+    B, m = Y.shape
+    n = P0.shape[1]
+    lin, owner = models.linear_params("gauss_sum", n)
+    non = np.flatnonzero(owner >= 0)
+    res = {"model": "gauss_sum", "separable": True, "B": B, "m": m, "n": n, "nl": int(lin.size), "na": int(non.size)}
+    if a.kernel:
+        res.update(launches=a.launches, rounds=a.rounds)
+        for key, sep in (("plain", False), ("separable", True)):
+            dm = models.DeviceModel(ctx, "gauss_sum", B, m, n, x, Y, 0.01, **({"separable": True} if sep else {}))
+            X = np.ascontiguousarray(P0[:, non]) if sep else P0
+            d_x, d_f, d_J = ctx.to_device(X), ctx.malloc(8 * B * m), ctx.malloc(8 * B * m * dm.n)
+            for what, call in (("f", lambda: dm.fun_dev(d_x, d_f, 1)), ("J", lambda: dm.jac_dev(d_x, d_J))):
+                call()                                                    # warm-up: the code objects
+                ctx.sync()
+                per_round = []
+                for _ in range(a.rounds):
+                    ctx.timing(True, only="model_eval")
+                    ctx.timing_reset()
+                    for _ in range(a.launches):
+                        call()
+                    ctx.sync()
+                    ms, cnt = ctx.timing_read()["model_eval"]
+                    ctx.timing(False)
+                    per_round.append(round(1e3 * ms / a.launches, 2))      # per evaluation: one launch, or three
+                    res["%s_%s_launches_per_eval" % (key, what)] = cnt // a.launches
+                res["%s_%s_us" % (key, what)] = round(float(np.median(per_round)), 2)
+                if a.rounds > 1:
+                    res["%s_%s_us_all" % (key, what)] = per_round
+            for p in (d_x, d_f, d_J):
+                ctx.free(p)
+            dm.close()
+        return res
+    kw = dict(sigma=0.01, driver="device", ctx=ctx, ftol=1e-10, xtol=1e-10, gtol=1e-10)
+    P0_sep = P0.copy()
+    P0_sep[:, lin] = np.nan
+    routes = {"separable": lambda: curve_fit_batch("gauss_sum", x, Y, P0_sep, separable=True, **kw),
+              "plain": lambda: curve_fit_batch("gauss_sum", x, Y, P0, **kw)}
+    times = {k: [] for k in routes}
+    out = {k: run() for k, run in routes.items()}                         # warm-up: code objects, plans
+    for _ in range(a.repeat):
+        for k, run in routes.items():
+            ctx.sync()
+            t0 = time.perf_counter()
+            run()
+            times[k].append(time.perf_counter() - t0)
+    both = np.array([ra.success and rb.success for ra, rb in zip(out["separable"][2], out["plain"][2])])
+    for k in routes:
+        nfev = np.array([r.nfev for r in out[k][2]])
+        res.update({k + "_s": round(float(np.median(times[k])), 4), k + "_all_s": [round(t, 4) for t in times[k]],
+                    k + "_nfev_mean": round(float(nfev.mean()), 2), k + "_nfev_max": int(nfev.max()),
+                    k + "_converged": int(sum(r.success for r in out[k][2]))})
+    res["speedup"] = round(res["plain_s"] / res["separable_s"], 2)
+    res["popt_max_rel_diff"] = float(np.max(np.abs(out["separable"][0][both] - out["plain"][0][both])
+                                            / (np.abs(out["plain"][0][both]) + 1e-3)))
+    return res
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--B", type=int, default=4096)
@@ -451,7 +521,18 @@ def main():
                     help="fit an expression model (default TEXT: the two-component decay)")
     ap.add_argument("--params", default=DECAY_PARAMS, help="with --expr: the parameter names, e.g. a,b,c")
     ap.add_argument("--truth", default="", help="with --expr: the parameter values the data are drawn from")
+    ap.add_argument("--separable", action="store_true",
+                    help="fit with the linear parameters projected out (with --kernel: the three launches per evaluation)")
     a = ap.parse_args()
+    if a.separable:
+        if (a.expr is not None or a.response or a.global_S or a.fixed or a.tied or a.binned or a.omit is not None
+                or a.estimator != "lse"):
+            ap.error("--separable takes --B, --m, --peaks, --repeat and --kernel (--launches, --rounds) only")
+        ctx = _abi.Context(0)
+        res = separable_bench(a, ctx)
+        ctx.close()
+        print(json.dumps(res))
+        return
     if a.expr is not None:
         if a.response or a.global_S or a.fixed or a.tied or a.binned or a.omit is not None or a.estimator != "lse":
             ap.error("--expr TEXT takes --params, --truth, --B, --m, --repeat and --kernel (--launches, --rounds) only")
