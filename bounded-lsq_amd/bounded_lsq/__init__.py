@@ -16,8 +16,8 @@ from ._cov import covariance  # noqa: F401
 from ._leverage import leverage, prediction_variance, influence  # noqa: F401
 from ._curve_fit import curve_fit, curve_fit_batch, curve_fit_global  # noqa: F401
 from ._linear import lsq_linear, lsq_linear_batch, LinearFit, LinearDeviceModel  # noqa: F401
-from ._bvls import (bvls, bvls_batch, nnls_batch, bvls_gram_batch, bvls_reference,  # noqa: F401
-                    BvlsResult)
+from ._bvls import (bvls, bvls_batch, nnls_batch, fcls_batch, bvls_gram_batch,  # noqa: F401
+                    bvls_reference, BvlsResult)
 from . import _models as models  # noqa: F401
 from ._params import ParamMap, GlobalMap  # noqa: F401
 from ._hostmath import (active_mask as find_active_constraints,  # noqa: F401
@@ -29,4 +29,4 @@ __all__ = ['dogbox', 'trf', 'find_active_constraints', 'CL_optimality', 'prepare
            'OuterDriver', 'covariance', 'curve_fit', 'curve_fit_batch', 'leverage', 'prediction_variance',
            'influence', 'models', 'ParamMap', 'GlobalMap', 'curve_fit_global', 'lsq_linear', 'lsq_linear_batch',
            'LinearFit', 'LinearDeviceModel', 'bvls', 'bvls_batch', 'nnls_batch', 'bvls_gram_batch', 'bvls_reference',
-           'BvlsResult']
+           'BvlsResult', 'fcls_batch']

@@ -187,6 +187,9 @@ SIGNATURES = {
     # optimality, stat
     "blsq_bvls_solve_dev": (C.c_int, [vp] + [C.c_int] * 3 + [vp, C.c_long, vp, vp, vp, C.c_double, C.c_int, vp, C.c_long,
                                              vp, vp, C.c_long] + [vp] * 6),
+    # the arguments of blsq_bvls_solve_dev, then e, e_stride, d, multiplier
+    "blsq_bvls_solve_eq_dev": (C.c_int, [vp] + [C.c_int] * 3 + [vp, C.c_long, vp, vp, vp, C.c_double, C.c_int, vp,
+                                                C.c_long, vp, vp, C.c_long] + [vp] * 6 + [vp, C.c_long, vp, vp]),
     # ctx, B, n, nl, lin, X, P (lin on the host)
     "blsq_varpro_expand_dev": (C.c_int, [vp] + [C.c_int] * 3 + [c_int32_p, vp, vp]),
     # ctx, B, m, n, nl, lin, owner, G, y, w, w_stride, f, J, c, info, mask (lin and owner on the host)

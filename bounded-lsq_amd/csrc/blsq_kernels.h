@@ -764,7 +764,15 @@ struct BvlsSolveCall {
 // grid cannot hold: the refusals that keep the kernels' offsets in bounds.
 hipError_t launch_bvls_moments(const BvlsMomentsCall& c, hipStream_t s);
 hipError_t launch_bvls_solve(const BvlsSolveCall& c, hipStream_t s);
-size_t bvls_solve_lds_bytes(int n);   // dynamic LDS of one problem
+// ... and the same solve under one equality e^T x = d per problem (blsq_bvls_solve_eq_dev; 7w)
+struct BvlsEqCall {
+  const double* e; long e_stride;   // [n] (stride 0: one e for all problems) or [B][n] (stride n)
+  const double* d;        // [B]
+  double* multiplier;     // [B]
+};
+// as launch_bvls_solve, and for a missing e, d or multiplier or an e_stride other than 0 or n
+hipError_t launch_bvls_solve_eq(const BvlsSolveCall& c, const BvlsEqCall& q, hipStream_t s);
+size_t bvls_solve_lds_bytes(int n, bool eq);   // dynamic LDS of one problem
 
 // ---------------------------------------------------- separable fits (7v) ----
 // varpro_kernels.hip.  The model parameters P [B][n] of the solver variables X [B][n - nl]: 1.0 in the slots lin

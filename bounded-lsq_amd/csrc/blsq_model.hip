@@ -1,5 +1,5 @@
 // Built-in fit models (include/blsq.h; kernel: model_kernels.hip): the model and term tables behind
-// blsq_model_count / _info and blsq_term_count / _info, the entries blsq_linear_eval_dev, blsq_expr_check, blsq_expr_eval_dev, blsq_bvls_moments_dev, blsq_bvls_solve_dev, blsq_response_apply_dev, blsq_varpro_expand_dev and blsq_varpro_reduce_dev, and the eight entries blsq_model_eval_dev, _map_dev, _comp_dev,
+// blsq_model_count / _info and blsq_term_count / _info, the entries blsq_linear_eval_dev, blsq_expr_check, blsq_expr_eval_dev, blsq_bvls_moments_dev, blsq_bvls_solve_dev, blsq_bvls_solve_eq_dev, blsq_response_apply_dev, blsq_varpro_expand_dev and blsq_varpro_reduce_dev, and the eight entries blsq_model_eval_dev, _map_dev, _comp_dev,
 // _est_dev, _bin_dev, _nan_dev, _global_dev and _tie_dev.  An entry fills a ModelEvalCall from its arguments (what its signature
 // does not have is the default) and hands it to model_eval_checked with its EvalEntry: one list of checks, one launcher, and per entry
 // only the argument numbers.
@@ -362,12 +362,11 @@ extern "C" int blsq_bvls_moments_dev(blsq_ctx* ctx, int B, int m, int n, const d
   return ctx->run(K_MODEL_EVAL, "launch_bvls_moments", [&] { return launch_bvls_moments(c, ctx->stream); });
 }
 
-extern "C" int blsq_bvls_solve_dev(blsq_ctx* ctx, int B, int m, int n, const double* dG, long G_stride,
-                                   const double* dc, const double* dlb, const double* dub, double tol, int max_pass,
-                                   const double* dA, long A_stride, const double* dy, const double* dw, long w_stride,
-                                   double* dx, int32_t* don_bound, double* dfun, double* dgrad, double* doptimality,
-                                   int32_t* dstat) {
-  if (!ctx) return -1;
+// the checks the two solve entries share (arguments 2 .. 22) -> 0, or the negative position
+static int bvls_solve_args(blsq_ctx* ctx, int B, int m, int n, const double* dG, long G_stride, const double* dc,
+                           const double* dlb, const double* dub, double tol, int max_pass, const double* dA,
+                           long A_stride, const double* dy, long w_stride, double* dx, int32_t* don_bound,
+                           double* dfun, double* dgrad, double* doptimality, int32_t* dstat) {
   if (B <= 0) return ctx->bad(2, "B must be positive");
   if (dA ? m <= 0 : m < 0) return ctx->bad(3, "m must be positive (without A: not negative; it is not read)");
   if (n < 1 || n > BLSQ_BVLS_MAX_N) return ctx->bad(4, "n must be in 1 .. BLSQ_BVLS_MAX_N");
@@ -389,10 +388,45 @@ extern "C" int blsq_bvls_solve_dev(blsq_ctx* ctx, int B, int m, int n, const dou
   if (!dgrad) return ctx->bad(20, "grad is NULL");
   if (!doptimality) return ctx->bad(21, "optimality is NULL");
   if (!dstat) return ctx->bad(22, "stat is NULL");
+  return 0;
+}
+
+extern "C" int blsq_bvls_solve_dev(blsq_ctx* ctx, int B, int m, int n, const double* dG, long G_stride,
+                                   const double* dc, const double* dlb, const double* dub, double tol, int max_pass,
+                                   const double* dA, long A_stride, const double* dy, const double* dw, long w_stride,
+                                   double* dx, int32_t* don_bound, double* dfun, double* dgrad, double* doptimality,
+                                   int32_t* dstat) {
+  if (!ctx) return -1;
+  const int bad = bvls_solve_args(ctx, B, m, n, dG, G_stride, dc, dlb, dub, tol, max_pass, dA, A_stride, dy, w_stride,
+                                  dx, don_bound, dfun, dgrad, doptimality, dstat);
+  if (bad != 0) return bad;
   HIPCHK(ctx, hipSetDevice(ctx->device));
   const BvlsSolveCall c{B, m, n, dG, G_stride, dc, dlb, dub, tol, max_pass, dA, dA ? A_stride : 0, dA ? dy : nullptr,
                         dA ? dw : nullptr, dA ? w_stride : 0, dx, don_bound, dfun, dgrad, doptimality, dstat};
   return ctx->run(K_MODEL_EVAL, "launch_bvls_solve", [&] { return launch_bvls_solve(c, ctx->stream); });
+}
+
+// The solve under one equality e^T x = d per problem: the arguments of blsq_bvls_solve_dev, then e,
+// e_stride, d and the multiplier.
+extern "C" int blsq_bvls_solve_eq_dev(blsq_ctx* ctx, int B, int m, int n, const double* dG, long G_stride,
+                                      const double* dc, const double* dlb, const double* dub, double tol,
+                                      int max_pass, const double* dA, long A_stride, const double* dy,
+                                      const double* dw, long w_stride, double* dx, int32_t* don_bound, double* dfun,
+                                      double* dgrad, double* doptimality, int32_t* dstat, const double* de,
+                                      long e_stride, const double* dd, double* dmultiplier) {
+  if (!ctx) return -1;
+  const int bad = bvls_solve_args(ctx, B, m, n, dG, G_stride, dc, dlb, dub, tol, max_pass, dA, A_stride, dy, w_stride,
+                                  dx, don_bound, dfun, dgrad, doptimality, dstat);
+  if (bad != 0) return bad;
+  if (!de) return ctx->bad(23, "e is NULL");
+  if (e_stride != 0 && e_stride != (long)n) return ctx->bad(24, "e_stride must be 0 or n");
+  if (!dd) return ctx->bad(25, "d is NULL");
+  if (!dmultiplier) return ctx->bad(26, "multiplier is NULL");
+  HIPCHK(ctx, hipSetDevice(ctx->device));
+  const BvlsSolveCall c{B, m, n, dG, G_stride, dc, dlb, dub, tol, max_pass, dA, dA ? A_stride : 0, dA ? dy : nullptr,
+                        dA ? dw : nullptr, dA ? w_stride : 0, dx, don_bound, dfun, dgrad, doptimality, dstat};
+  const BvlsEqCall q{de, e_stride, dd, dmultiplier};
+  return ctx->run(K_MODEL_EVAL, "launch_bvls_solve_eq", [&] { return launch_bvls_solve_eq(c, q, ctx->stream); });
 }
 
 // Instrument response (response_kernels.hip): the convolution of raw model values and of a raw Jacobian

@@ -23,6 +23,13 @@
 //                        rounds, the release choice: asked at most twice), and a pivot <= 0 or not finite, or a value
 //                        not finite, ends the problem with status -1: nothing spins.
 //
+// bvls_solve_kernel<true> (blsq_bvls_solve_eq_dev) is the same iteration under one equality e^T x = d:
+// the feasible start in place of the clip-in start, a second right-hand side v = G_FF^-1 e_F per factorisation (both
+// substitutions share one walk over the factor), the multiplier lambda, the reduced gradient g + lambda e in the
+// release test and the projected correction against A.  LDS: two more n-vectors, e (by variable) and v (by the place
+// of the variable in the free set).  bvls_solve_kernel<false> is the kernel described above, instruction for
+// instruction: everything the equality adds stands behind `if constexpr (EQ)`.
+//
 // Compiled with -ffp-contract=off (EXACT_SRCS): every fused operation of this file is spelled fma(), so the stated
 // summation orders and the exact bound values do not depend on what the compiler would contract.  The decisions are
 // those of bounded_lsq._bvls.bvls_reference wherever no comparison is decided by rounding; the sums themselves are not
@@ -225,6 +232,51 @@ struct BvlsState {
     }
   }
 
+  // tri_solve for two right-hand sides in one walk over Lt (the operations on each are those of tri_solve)
+  __device__ void tri_solve2(int k, double& v0, double& v1, double& w0, double& w1) {
+    const int i0 = lane, i1 = lane + WAVE;
+    if (i0 >= k) v0 = w0 = 0.0;
+    if (i1 >= k) v1 = w1 = 0.0;
+    int off = 0;
+    for (int t = 0; t < k; ++t) {
+      const double piv = Lt[off];
+      const double yt = (t < WAVE ? read_lane(v0, t & 63) : read_lane(v1, t & 63)) / piv;
+      const double qt = (t < WAVE ? read_lane(w0, t & 63) : read_lane(w1, t & 63)) / piv;
+      if (i0 == t) { v0 = yt; w0 = qt; }
+      if (i1 == t) { v1 = yt; w1 = qt; }
+      if (i0 > t && i0 < k) {
+        const double l = Lt[off + i0 - t];
+        v0 = fma(-l, yt, v0);
+        w0 = fma(-l, qt, w0);
+      }
+      if (i1 > t && i1 < k) {
+        const double l = Lt[off + i1 - t];
+        v1 = fma(-l, yt, v1);
+        w1 = fma(-l, qt, w1);
+      }
+      off += k - t;
+    }
+    const int c0 = i0 * k - i0 * (i0 - 1) / 2 - i0, c1 = i1 * k - i1 * (i1 - 1) / 2 - i1;
+    for (int t = k - 1; t >= 0; --t) {
+      off -= k - t;
+      const double piv = Lt[off];
+      const double zt = (t < WAVE ? read_lane(v0, t & 63) : read_lane(v1, t & 63)) / piv;
+      const double qt = (t < WAVE ? read_lane(w0, t & 63) : read_lane(w1, t & 63)) / piv;
+      if (i0 == t) { v0 = zt; w0 = qt; }
+      if (i1 == t) { v1 = zt; w1 = qt; }
+      if (i0 < t) {
+        const double l = Lt[c0 + t];
+        v0 = fma(-l, zt, v0);
+        w0 = fma(-l, qt, w0);
+      }
+      if (i1 < t) {
+        const double l = Lt[c1 + t];
+        v1 = fma(-l, zt, v1);
+        w1 = fma(-l, qt, w1);
+      }
+    }
+  }
+
   // zs[f_i] = the solution of G_FF z = c_F - G_FB x_B; false: not positive definite, or a value not finite
   __device__ bool solve(int k) {
     if (!factor(k)) return false;
@@ -276,6 +328,222 @@ struct BvlsState {
   }
 };
 
+// What the equality e^T x = d adds to the state (bvls_solve_kernel<true> only); every member function is called by the
+// whole wave in uniform control flow.  Dot products over the free set: lane l forms fma(e_1, a_1, e_0 a_0) of its two
+// entries (places l and l + 64), then wave_sum; the sums over all variables that feed a DECISION of the start (the gap
+// d - e^T x) run in ascending j on every lane alike.
+struct BvlsEq {
+  double* es;             // [n] e, by variable
+  double* vs;             // [n] v = G_FF^-1 e_F of the last solve, by place in the free set
+  double d;
+  double lam;             // lambda of the last accepted solve
+  double lam_z;           // lambda of the last solve
+  double ev;              // e_F^T v of the last solve
+
+  // d - sum over the variables with on != 0 (BOUND_ONLY) or over all of them of e_j x_j, ascending j
+  template <bool BOUND_ONLY>
+  __device__ double gap(const BvlsState& st) const {
+    double acc = d;
+    for (int j = 0; j < st.n; ++j)
+      if (!BOUND_ONLY || st.on[j] != 0) acc = fma(-es[j], st.xs[j], acc);
+    return acc;
+  }
+
+  __device__ static double dot2(double e0, double a0, double e1, double a1) { return wave_sum(fma(e1, a1, e0 * a0)); }
+
+  // x = clip(0, lb, ub) (already in xs) and the gap walked off in ascending j -> 2, or -1 / -2 with xs the clipped start
+  __device__ int feasible_start(BvlsState& st) {
+    const int n = st.n, lane = st.lane;
+    bool bad = false;
+    for (int j = lane; j < n; j += WAVE) bad |= !is_finite(es[j]) || es[j] == 0.0;
+    int ret = (__any(bad) || !is_finite(d)) ? -1 : 2;
+    if (ret == 2) {
+      double g = gap<false>(st);
+      for (int j = 0; j < n; ++j) {                                   // (uniform: every lane holds the same g)
+        if (g == 0.0) break;
+        const double ej = es[j], step = g / ej;
+        if (!is_finite(g) || !is_finite(step)) { ret = -1; break; }
+        const double xj = st.xs[j], lo = st.lbs[j], hi = st.ubs[j];
+        const double bound = step > 0.0 ? hi : lo, room = bound - xj;
+        double nx;
+        if (fabs(step) <= fabs(room)) {
+          nx = fmin(fmax(xj + step, lo), hi);
+          g = 0.0;
+        } else {
+          nx = bound;
+          g = fma(-ej, room, g);
+        }
+        if (lane == 0) st.xs[j] = nx;                                 // (xs[j] is read at step j only)
+        if (g == 0.0) break;
+      }
+      if (ret == 2 && !is_finite(g)) ret = -1;
+      if (ret == 2 && g != 0.0) ret = -2;
+    }
+    __syncthreads();
+    for (int j = lane; j < n; j += WAVE) {
+      if (ret != 2) st.xs[j] = fmin(fmax(0.0, st.lbs[j]), st.ubs[j]);
+      const double x = st.xs[j];
+      st.on[j] = x == st.lbs[j] ? -1 : (x == st.ubs[j] ? 1 : 0);
+    }
+    __syncthreads();
+    return ret;
+  }
+
+  // Lt holds the factor of the free block: v into vs and registers, ev = e_F^T v -> false: ev <= 0 or not finite
+  __device__ bool project(BvlsState& st, int k, double (&v)[2]) {
+    for (int h = 0; h < 2; ++h) {
+      const int i = st.lane + h * WAVE;
+      v[h] = i < k ? es[st.fidx[i]] : 0.0;
+    }
+    const double e0 = v[0], e1 = v[1];
+    st.tri_solve(k, v[0], v[1]);
+    ev = dot2(e0, v[0], e1, v[1]);
+    for (int h = 0; h < 2; ++h)
+      if (st.lane + h * WAVE < k) vs[st.lane + h * WAVE] = v[h];
+    __syncthreads();
+    return ev > 0.0 && is_finite(ev);
+  }
+
+  // zs[f_i] = z_F = u - lambda v (a free set of one variable j: (d - e_B^T x_B) / e_j clamped into its box); lam_z = lambda
+  // false: not positive definite, e_F^T v <= 0, or a value not finite
+  __device__ bool solve(BvlsState& st, int k) {
+    if (!st.factor(k)) return false;
+    const int n = st.n, lane = st.lane;
+    double u[2], v[2], e[2];
+    for (int h = 0; h < 2; ++h) {
+      const int i = lane + h * WAVE;
+      double acc = 0.0, ei = 0.0;
+      if (i < k) {
+        const int fi = st.fidx[i];
+        acc = st.c[fi];
+        for (int j = 0; j < n; ++j)
+          if (st.on[j] != 0) acc = fma(-st.G[(long)j * n + fi], st.xs[j], acc);
+        ei = es[fi];
+      }
+      u[h] = acc;
+      v[h] = e[h] = ei;
+    }
+    st.tri_solve2(k, u[0], u[1], v[0], v[1]);
+    const double dF = gap<true>(st);
+    const double eu = dot2(e[0], u[0], e[1], u[1]);
+    ev = dot2(e[0], v[0], e[1], v[1]);
+    if (!(ev > 0.0) || !is_finite(ev)) return false;
+    const double l = (eu - dF) / ev;
+    bool bad = !is_finite(l);
+    for (int h = 0; h < 2; ++h) {
+      const int i = lane + h * WAVE;
+      if (i < k) {
+        const int fi = st.fidx[i];
+        double z = fma(-l, v[h], u[h]);
+        bad |= !is_finite(z);
+        if (k == 1) z = fmin(fmax(dF / e[h], st.lbs[fi]), st.ubs[fi]);
+        st.zs[fi] = z;
+        vs[i] = v[h];
+      }
+    }
+    __syncthreads();
+    lam_z = l;
+    return !__any(bad);
+  }
+
+  // The first pass: a drop loop with nothing released, so without the bars and the zero-step end of the kernel's own;
+  // the ratio test, the clamp and the exact bound values are those.  At most n + 1 rounds.
+  __device__ void first_pass(BvlsState& st, int& k, int& nfact, int& status, bool& valid) {
+    const int n = st.n, lane = st.lane;
+    for (int round = 0; round <= n; ++round) {
+      k = st.build_free();
+      if (k == 0) return;
+      ++nfact;
+      if (!solve(st, k)) { status = -1; return; }
+      double abest = INFINITY;
+      int ibest = INT_MAX;
+      for (int j = lane; j < n; j += WAVE) {
+        if (st.on[j] != 0) continue;
+        const double z = st.zs[j], x = st.xs[j];
+        double bound;
+        if (z < st.lbs[j]) bound = st.lbs[j];
+        else if (z > st.ubs[j]) bound = st.ubs[j];
+        else continue;
+        const double a = (bound - x) / (z - x);
+        if (ibest == INT_MAX || a < abest) { abest = a; ibest = j; }
+      }
+      if (!__any(ibest != INT_MAX)) {             // accepted
+        for (int j = lane; j < n; j += WAVE)
+          if (st.on[j] == 0) st.xs[j] = st.zs[j];
+        __syncthreads();
+        lam = lam_z;
+        valid = true;
+        return;
+      }
+      const double amin = wave_min(abest);
+      const int id = wave_min_int((ibest != INT_MAX && abest == amin) ? ibest : INT_MAX);
+      if (id == INT_MAX) { status = -1; return; }
+      const double al = fmin(fmax(amin, 0.0), 1.0);
+      for (int j = lane; j < n; j += WAVE) {
+        if (st.on[j] != 0) continue;
+        const double x = st.xs[j];
+        st.xs[j] = fmin(fmax(x + al * (st.zs[j] - x), st.lbs[j]), st.ubs[j]);
+      }
+      __syncthreads();
+      if (lane == 0) {
+        const bool low = st.zs[id] < st.lbs[id];
+        st.on[id] = low ? -1 : 1;
+        st.xs[id] = low ? st.lbs[id] : st.ubs[id];
+      }
+      __syncthreads();
+    }
+    status = -1;                                  // (unreachable: every round removes a variable)
+  }
+
+  // every variable is on a bound: the interval [lo, hi] of the multipliers no bound variable objects to (from gs)
+  __device__ void interval(const BvlsState& st, double& lo, double& hi) const {
+    lo = -INFINITY;
+    hi = INFINITY;
+    for (int j = st.lane; j < st.n; j += WAVE) {
+      if (st.on[j] == 0) continue;
+      const double q = -st.gs[j] / es[j];
+      if ((double)st.on[j] * es[j] > 0.0) hi = fmin(hi, q);
+      else lo = fmax(lo, q);
+    }
+    lo = wave_max(lo);
+    hi = wave_min(hi);
+  }
+
+  __device__ bool any_free(const BvlsState& st) const {
+    bool fr = false;
+    for (int j = st.lane; j < st.n; j += WAVE) fr |= st.on[j] == 0;
+    return __any(fr);
+  }
+
+  // the multiplier reported, from gs: -e_F^T g_F / e_F^T e_F; F empty: the midpoint of the interval, or its finite end
+  __device__ double multiplier(const BvlsState& st) const {
+    if (any_free(st)) {
+      double e[2] = {0.0, 0.0}, g[2] = {0.0, 0.0};
+      for (int h = 0; h < 2; ++h) {
+        const int j = st.lane + h * WAVE;
+        if (j < st.n && st.on[j] == 0) { e[h] = es[j]; g[h] = st.gs[j]; }
+      }
+      return -dot2(e[0], g[0], e[1], g[1]) / dot2(e[0], e[0], e[1], e[1]);
+    }
+    double lo, hi;
+    interval(st, lo, hi);
+    if (is_finite(lo) && is_finite(hi)) return 0.5 * (lo + hi);
+    return is_finite(lo) ? lo : (is_finite(hi) ? hi : 0.0);
+  }
+
+  // max(max over free |g_j + l e_j|, max over bound (g_j + l e_j) on_j, 0) of gs
+  __device__ double optimality(const BvlsState& st, double l) const {
+    double v = 0.0;
+    for (int j = st.lane; j < st.n; j += WAVE) {
+      const double r = fma(l, es[j], st.gs[j]);
+      v = nanmax2(v, st.on[j] == 0 ? fabs(r) : r * (double)st.on[j]);
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v = nanmax2(v, __shfl_xor(v, o, WAVE));
+    return v;
+  }
+};
+
 // One pass over the rows of A with x = st.xs:  f_i = w_i (sum_j A_ij x_j - y_i), u_i = (CORRECT ? -w_i : w_i) f_i,
 // st.ts[j] = sum_i A_ij u_i; FINAL (not CORRECT) also writes fun (where given) and returns sum f_i^2.  A row belongs to
 // a group of Gs = 2^lg lanes (Gs >= min(n, 64)): coalesced along j; lane g of the group runs fma(A_ij, x_j, .) over
@@ -320,7 +588,8 @@ __device__ double bvls_a_pass(BvlsState& st, int m, int lg, const double* __rest
   return CORRECT ? 0.0 : wave_sum(ss);
 }
 
-__global__ __launch_bounds__(BV_NT) void bvls_solve_kernel(BvlsSolveCall c, int lg) {
+template <bool EQ>
+__global__ __launch_bounds__(BV_NT) void bvls_solve_kernel(BvlsSolveCall c, int lg, BvlsEqCall ec) {
   extern __shared__ __attribute__((aligned(16))) char bv_smem[];
   const int n = c.n, lane = threadIdx.x;
   const long b = blockIdx.x;
@@ -342,6 +611,16 @@ __global__ __launch_bounds__(BV_NT) void bvls_solve_kernel(BvlsSolveCall c, int 
   st.fidx = q; q += n;
   st.on = q; q += n;
   st.barred = q;
+  BvlsEq eq;
+  if constexpr (EQ) {
+    double* de = reinterpret_cast<double*>(q + n + (n & 1));          // (8-byte aligned behind the three int vectors)
+    eq.es = de;
+    eq.vs = de + n;
+    eq.d = ec.d[b];
+    eq.lam = 0.0;
+    eq.ev = 0.0;
+    for (int j = lane; j < n; j += WAVE) eq.es[j] = ec.e[b * ec.e_stride + j];
+  }
 
   for (int j = lane; j < n; j += WAVE) {
     const double lo = c.lb[b * n + j], hi = c.ub[b * n + j];
@@ -358,8 +637,13 @@ __global__ __launch_bounds__(BV_NT) void bvls_solve_kernel(BvlsSolveCall c, int 
   bool valid = false;                             // Lt holds the factor of the current free block
   int k = 0;
 
-  // (1) clip-in start
-  for (int it = 0; it <= n; ++it) {
+  // (1) clip-in start; under the equality the feasible start, and a first pass that is a drop loop with no release
+  if constexpr (EQ) {
+    const int ret = eq.feasible_start(st);
+    if (ret != 2) status = ret;
+    else eq.first_pass(st, k, nfact, status, valid);
+  }
+  for (int it = 0; !EQ && it <= n; ++it) {
     k = st.build_free();
     if (k == 0) break;
     ++nfact;
@@ -379,6 +663,16 @@ __global__ __launch_bounds__(BV_NT) void bvls_solve_kernel(BvlsSolveCall c, int 
   // (2) release passes
   while (status == 2) {
     if (!st.gradient()) { status = -1; break; }
+    double lam = 0.0;                             // (EQ) the multiplier the release test reads
+    if constexpr (EQ) {
+      lam = eq.lam;
+      if (!eq.any_free(st)) {
+        double lo, hi;
+        eq.interval(st, lo, hi);
+        if (lo <= hi + c.tol) { status = 1; break; }
+        lam = 0.5 * (lo + hi);
+      }
+    }
     // the variable that wants to leave its bound most, of those not barred; when none of them does, the bars are
     // cleared and the barred ones are asked again: status 1 means that NO variable on a bound wants to leave it
     double vmax = -INFINITY;
@@ -390,7 +684,9 @@ __global__ __launch_bounds__(BV_NT) void bvls_solve_kernel(BvlsSolveCall c, int 
       for (int j = lane; j < n; j += WAVE) {
         if (st.on[j] == 0) continue;
         if (st.barred[j]) { any_barred = true; continue; }
-        const double v = st.gs[j] * (double)st.on[j];
+        double v;
+        if constexpr (EQ) v = fma(lam, eq.es[j], st.gs[j]) * (double)st.on[j];
+        else v = st.gs[j] * (double)st.on[j];
         if (jbest == INT_MAX || v > vbest) { vbest = v; jbest = j; }
       }
       vmax = wave_max(vbest);
@@ -420,7 +716,11 @@ __global__ __launch_bounds__(BV_NT) void bvls_solve_kernel(BvlsSolveCall c, int 
         break;
       }
       ++nfact;
-      if (!st.solve(k)) { status = -1; break; }
+      if constexpr (EQ) {
+        if (!eq.solve(st, k)) { status = -1; break; }
+      } else {
+        if (!st.solve(k)) { status = -1; break; }
+      }
       double abest = INFINITY;
       int ibest = INT_MAX;
       for (int j = lane; j < n; j += WAVE) {
@@ -439,6 +739,7 @@ __global__ __launch_bounds__(BV_NT) void bvls_solve_kernel(BvlsSolveCall c, int 
           st.barred[j] = 0;
         }
         __syncthreads();
+        if constexpr (EQ) eq.lam = eq.lam_z;
         valid = true;
         ended = true;
         break;
@@ -474,7 +775,45 @@ __global__ __launch_bounds__(BV_NT) void bvls_solve_kernel(BvlsSolveCall c, int 
     const double* y = c.y + b * (long)c.m;
     const double* w = c.w ? c.w + b * c.w_stride : nullptr;
     // one corrected-semi-normal-equations step on the final free block: x_F += (G_FF)^-1 A_F^T W^2 (y - A x)
-    if (status != -1) {
+    if constexpr (EQ) {
+      // under the equality the step is projected: with t = A^T W^2 (y - A x), s = (G_FF)^-1 t_F and the v of this free
+      // block, x_F += s - mu v, mu = (e_F^T s - (d - e^T x)) / (e_F^T v): the sum is restored as well
+      if (status >= 0) {
+        bool ok = valid;
+        double v[2];
+        if (valid) {
+          v[0] = lane < k ? eq.vs[lane] : 0.0;
+          v[1] = lane + WAVE < k ? eq.vs[lane + WAVE] : 0.0;
+        } else {
+          k = st.build_free();
+          if (k > 0) {
+            ++nfact;
+            ok = st.factor(k) && eq.project(st, k, v);
+          }
+        }
+        if (ok && k > 0) {
+          bvls_a_pass<true>(st, c.m, lg, A, y, w, nullptr);
+          double s0 = lane < k ? st.ts[st.fidx[lane]] : 0.0;
+          double s1 = lane + WAVE < k ? st.ts[st.fidx[lane + WAVE]] : 0.0;
+          const double e0 = lane < k ? eq.es[st.fidx[lane]] : 0.0;
+          const double e1 = lane + WAVE < k ? eq.es[st.fidx[lane + WAVE]] : 0.0;
+          st.tri_solve(k, s0, s1);
+          const double mu = (BvlsEq::dot2(e0, s0, e1, s1) - eq.template gap<false>(st)) / eq.ev;
+          s0 = fma(-mu, v[0], s0);
+          s1 = fma(-mu, v[1], s1);
+          const bool fin = !__any((lane < k && !is_finite(s0)) || (lane + WAVE < k && !is_finite(s1)));
+          if (fin) {                              // (a correction that is not finite is not applied)
+            for (int h = 0; h < 2; ++h) {
+              const int i = lane + h * WAVE;
+              if (i >= k) continue;
+              const int j = st.fidx[i];
+              st.xs[j] = fmin(fmax(st.xs[j] + (h ? s1 : s0), st.lbs[j]), st.ubs[j]);
+            }
+          }
+          __syncthreads();
+        }
+      }
+    } else if (status != -1) {
       bool ok = valid;
       if (!valid) {
         k = st.build_free();
@@ -507,7 +846,13 @@ __global__ __launch_bounds__(BV_NT) void bvls_solve_kernel(BvlsSolveCall c, int 
   } else {
     st.gradient();
   }
-  opt = st.optimality();
+  double mult = 0.0;
+  if constexpr (EQ) {
+    mult = eq.multiplier(st);
+    opt = eq.optimality(st, mult);
+  } else {
+    opt = st.optimality();
+  }
   for (int j = lane; j < n; j += WAVE) {
     c.x[b * n + j] = st.xs[j];
     c.on_bound[b * n + j] = st.on[j];
@@ -519,14 +864,16 @@ __global__ __launch_bounds__(BV_NT) void bvls_solve_kernel(BvlsSolveCall c, int 
     c.stat[3 * b] = status;
     c.stat[3 * b + 1] = nit;
     c.stat[3 * b + 2] = nfact;
+    if constexpr (EQ) ec.multiplier[b] = mult;
   }
 }
 
-size_t bvls_solve_lds_bytes(int n) {
-  return sizeof(double) * ((size_t)n * (n + 1) / 2 + 6 * (size_t)n) + sizeof(int) * 3 * (size_t)n;
+size_t bvls_solve_lds_bytes(int n, bool eq) {
+  const size_t base = sizeof(double) * ((size_t)n * (n + 1) / 2 + 6 * (size_t)n) + sizeof(int) * 3 * (size_t)n;
+  return eq ? base + sizeof(int) * (size_t)(n & 1) + sizeof(double) * 2 * (size_t)n : base;
 }
 
-hipError_t launch_bvls_solve(const BvlsSolveCall& c, hipStream_t s) {
+static hipError_t checked_solve_call(const BvlsSolveCall& c) {
   if (c.B < 1 || c.n < 1 || c.n > BLSQ_BVLS_MAX_N || c.max_pass < 0) return hipErrorInvalidValue;
   if (!c.G || !c.c || !c.lb || !c.ub || !c.x || !c.on_bound || !c.grad || !c.opt || !c.stat) return hipErrorInvalidValue;
   if (c.G_stride != 0 && c.G_stride != (long)c.n * c.n) return hipErrorInvalidValue;
@@ -537,9 +884,28 @@ hipError_t launch_bvls_solve(const BvlsSolveCall& c, hipStream_t s) {
   } else if (c.fun) {
     return hipErrorInvalidValue;
   }
+  return hipSuccess;
+}
+
+static int group_log2(int n) {
   int lg = 0;
-  while (lg < 6 && (1 << lg) < c.n) ++lg;
-  return launch<bvls_solve_kernel>(dim3((unsigned)c.B), dim3(BV_NT), bvls_solve_lds_bytes(c.n), s, c, lg);
+  while (lg < 6 && (1 << lg) < n) ++lg;
+  return lg;
+}
+
+hipError_t launch_bvls_solve(const BvlsSolveCall& c, hipStream_t s) {
+  const hipError_t e = checked_solve_call(c);
+  if (e != hipSuccess) return e;
+  return launch<bvls_solve_kernel<false>>(dim3((unsigned)c.B), dim3(BV_NT), bvls_solve_lds_bytes(c.n, false), s, c,
+                                          group_log2(c.n), BvlsEqCall{nullptr, 0, nullptr, nullptr});
+}
+
+hipError_t launch_bvls_solve_eq(const BvlsSolveCall& c, const BvlsEqCall& q, hipStream_t s) {
+  const hipError_t e = checked_solve_call(c);
+  if (e != hipSuccess) return e;
+  if (!q.e || !q.d || !q.multiplier || (q.e_stride != 0 && q.e_stride != (long)c.n)) return hipErrorInvalidValue;
+  return launch<bvls_solve_kernel<true>>(dim3((unsigned)c.B), dim3(BV_NT), bvls_solve_lds_bytes(c.n, true), s, c,
+                                         group_log2(c.n), q);
 }
 
 }  // namespace blsq

@@ -671,7 +671,22 @@ int blsq_response_apply_dev(blsq_ctx* ctx, int est, int nan_policy, int B, int r
  * B = 2, m = 3, n = 4, A = 5, A_stride = 6, y = 7, w, w_stride = 9, G = 10, G_stride = 11, c = 12; solve: ctx = 1,
  * B = 2, m = 3, n = 4, G = 5, G_stride = 6, c = 7, lb = 8, ub = 9, tol = 10: not a number, max_pass = 11, A,
  * A_stride = 13, y = 14, w, w_stride = 16, x = 17, on_bound = 18, fun = 19: given without A, grad = 20,
- * optimality = 21, stat = 22); nothing is launched then. */
+ * optimality = 21, stat = 22); nothing is launched then.
+ *
+ * Solve under a sum constraint.  blsq_bvls_solve_eq_dev is the solve above with one linear equality per
+ * problem, e^T x = d: the arguments of blsq_bvls_solve_dev in their order and with their checks and numbers, then de:
+ * [n] for the whole batch (e_stride 0) or [B][n] (e_stride n), every e_j finite and not zero; dd: [B]; dmultiplier:
+ * [B], out: the multiplier lambda of the equality, so that g + lambda e vanishes on the free variables and
+ * (g_j + lambda e_j) on_bound_j <= 0 on the others (least squares over the free set, -e_F^T g_F / e_F^T e_F; with no
+ * free variable the midpoint of the admissible interval, or its finite end).  The iteration starts from a feasible
+ * point (x = clip(0, lb, ub), the gap d - e^T x walked off in ascending j), solves G_FF z + lambda e_F = c_F - G_FB x_B,
+ * e_F^T z = d - e_B^T x_B on the free set from ONE factorisation, and releases on the reduced gradient g + lambda e;
+ * with dA the correction against A is projected, x_F += s - mu v, so that the sum is restored as well.  doptimality[b][0]
+ * is max(max over free |g_j + lambda e_j|, max over bound (g_j + lambda e_j) on_bound_j, 0); dgrad stays the plain
+ * gradient.  Status as above, and for THIS entry alone -2: the equality cannot be met inside the bounds (x is then
+ * clip(0, lb, ub)); an e_j that is zero or not finite, a d that is not finite, or e_F^T (G_FF)^-1 e_F not positive is
+ * status -1.  One kernel, one unit of the `model_eval` slot.  Bad arguments: 1 .. 22 as blsq_bvls_solve_dev, then
+ * e = 23, e_stride = 24, d = 25, multiplier = 26. */
 #define BLSQ_BVLS_MAX_N 128
 int blsq_bvls_moments_dev(blsq_ctx* ctx, int B, int m, int n, const double* dA, long A_stride, const double* dy,
                           const double* dw, long w_stride, double* dG, long G_stride, double* dc);
@@ -679,6 +694,11 @@ int blsq_bvls_solve_dev(blsq_ctx* ctx, int B, int m, int n, const double* dG, lo
                         const double* dlb, const double* dub, double tol, int max_pass, const double* dA,
                         long A_stride, const double* dy, const double* dw, long w_stride, double* dx,
                         int32_t* don_bound, double* dfun, double* dgrad, double* doptimality, int32_t* dstat);
+int blsq_bvls_solve_eq_dev(blsq_ctx* ctx, int B, int m, int n, const double* dG, long G_stride, const double* dc,
+                           const double* dlb, const double* dub, double tol, int max_pass, const double* dA,
+                           long A_stride, const double* dy, const double* dw, long w_stride, double* dx,
+                           int32_t* don_bound, double* dfun, double* dgrad, double* doptimality, int32_t* dstat,
+                           const double* de, long e_stride, const double* dd, double* dmultiplier);
 
 /* ---- expression models: a formula interpreted on the device -----------------------------------------
  * A model that is none of the built-in ones, given as a short straight-line program (compiled on the host from the

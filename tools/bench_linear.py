@@ -16,9 +16,13 @@ per-problem matrices on buffers of the same shapes.
 and prints the release passes and the
 factorisations per problem as max and mean; with ``--kernel`` it times the moments launch and the solve launch
 separately instead (`--rounds` blocks of `--launches` launches each, the median of the blocks' means; no weights).
+``--method bvls --sum-to D`` adds the equality ``sum x = D``: ``bvls_batch(..., equality=(1, D))`` is timed
+against the unconstrained ``bvls_batch`` of the same data in the same run (problems per second, release passes and
+factorisations of both); with ``--kernel`` the solve launch of blsq_bvls_solve_eq_dev is timed beside the one of
+blsq_bvls_solve_dev, each with its factorisations and its time per factorisation.
 
 usage: python tools/bench_linear.py [--B 4096] [--m 64] [--n 16] [--method trf] [--own] [--repeat 5]
-                                    [--kernel] [--launches 200] [--rounds 5]
+                                    [--kernel] [--launches 200] [--rounds 5] [--sum-to D]
 """
 import argparse
 import json
@@ -84,15 +88,17 @@ def kernel_times(ctx, A, b, launches, rounds):
     return out
 
 
-def bvls_kernel_times(ctx, A, b, lb, ub, launches, rounds):
+def bvls_kernel_times(ctx, A, b, lb, ub, launches, rounds, sum_to=None):
     """The moments launch and the solve launch of one ``bvls_batch`` (no weights), each alone in the 'model_eval' slot:
-    `rounds` timed blocks of `launches` launches after a warm-up, the median of the blocks' means, in ms."""
+    `rounds` timed blocks of `launches` launches after a warm-up, the median of the blocks' means, in ms.  `sum_to`: the
+    solve launch under ``sum x = sum_to`` as well (``solve_eq_*``), on the same moments."""
     B, m = b.shape
     n = A.shape[-1]
     A_stride = m * n if A.ndim == 3 else 0
     G_stride = n * n if A_stride else 0
+    eq = None if sum_to is None else (np.ones(n), np.full(B, float(sum_to)))
     need = _bvls._Buffers.need(A, b, lb, ub, 8 * n * n * (B if G_stride else 1), 8 * B * n,
-                               *_bvls._output_bytes(B, m, n, True))
+                               *_bvls._output_bytes(B, m, n, True), *_bvls._equality_bytes(eq, B))
     with _bvls._Buffers(ctx, need) as buf:
         d_A, d_y, d_lb, d_ub = buf.up(A), buf.up(b), buf.up(lb), buf.up(ub)
         d_G, d_c = buf.new(8 * n * n * (B if G_stride else 1)), buf.new(8 * B * n)
@@ -103,7 +109,12 @@ def bvls_kernel_times(ctx, A, b, lb, ub, launches, rounds):
                  "solve": lambda: ctx.check(ctx.lib.blsq_bvls_solve_dev(ctx.h, B, m, n, d_G, G_stride, d_c, d_lb, d_ub,
                                                                        1e-10, 5 * n, d_A, A_stride, d_y, None, 0, d_x,
                                                                        d_on, d_fun, d_grad, d_opt, d_stat), "solve")}
-        out = {}
+        if eq is not None:
+            d_e, d_d, d_mult = buf.up(eq[0]), buf.up(eq[1]), buf.new(8 * B)
+            calls["solve_eq"] = lambda: ctx.check(ctx.lib.blsq_bvls_solve_eq_dev(
+                ctx.h, B, m, n, d_G, G_stride, d_c, d_lb, d_ub, 1e-10, 5 * n, d_A, A_stride, d_y, None, 0, d_x, d_on,
+                d_fun, d_grad, d_opt, d_stat, d_e, 0, d_d, d_mult), "solve_eq")
+        out, stats = {}, {}
         for name, call in calls.items():
             call()
             ctx.sync()
@@ -119,19 +130,62 @@ def bvls_kernel_times(ctx, A, b, lb, ub, launches, rounds):
                 ctx.timing(False)
             out[name + "_ms"] = float(np.median(ms_all))
             out[name + "_ms_all"] = ms_all
-        stat = ctx.to_host(d_stat, (B, 3), np.int32)
+            if name != "moments":
+                stats[name] = ctx.to_host(d_stat, (B, 3), np.int32)
+    stat = stats["solve"]
     out["factorisations"] = int(stat[:, 2].sum())
     out["factorisations_mean"] = round(float(stat[:, 2].mean()), 3)
     # the chip's throughput: the solve launch over all factorisations of the batch (gradients and ratio tests included)
     out["solve_ns_per_factorisation"] = round(1e6 * out["solve_ms"] / max(int(stat[:, 2].sum()), 1), 1)
+    if eq is not None:
+        stat = stats["solve_eq"]
+        out.update({"sum_to": float(sum_to), "passes_mean": round(float(stats["solve"][:, 1].mean()), 3),
+                    "solve_eq_status": sorted(set(int(v) for v in stat[:, 0])),
+                    "solve_eq_passes_mean": round(float(stat[:, 1].mean()), 3),
+                    "solve_eq_factorisations": int(stat[:, 2].sum()),
+                    "solve_eq_factorisations_mean": round(float(stat[:, 2].mean()), 3),
+                    "solve_eq_ns_per_factorisation": round(1e6 * out["solve_eq_ms"] / max(int(stat[:, 2].sum()), 1), 1),
+                    "solve_problems_per_s": round(1e3 * B / out["solve_ms"]),
+                    "solve_eq_problems_per_s": round(1e3 * B / out["solve_eq_ms"])})
+        out["ns_per_factorisation_ratio"] = round(out["solve_eq_ns_per_factorisation"]
+                                                  / out["solve_ns_per_factorisation"], 3)
     return out
+
+
+def bvls_sum_main(a, A, b, ctx, res, lb, ub):
+    """``bvls_batch`` under ``sum x = a.sum_to`` against the unconstrained ``bvls_batch`` of the same data, alternating
+    blocks in one process: whole calls, the median of `--repeat` after one warm-up each."""
+    routes = {"bvls": lambda: bvls_batch(A, b, (lb, ub), ctx=ctx),
+              "bvls_eq": lambda: bvls_batch(A, b, (lb, ub), ctx=ctx, equality=(1.0, a.sum_to))}
+    times = {k: [] for k in routes}
+    out = {k: run() for k, run in routes.items()}
+    for _ in range(a.repeat):
+        for k, run in routes.items():
+            ctx.sync()
+            t0 = time.perf_counter()
+            run()
+            times[k].append(time.perf_counter() - t0)
+    res["sum_to"] = a.sum_to
+    for k, r in out.items():
+        t = float(np.median(times[k]))
+        res[k] = {"s": round(t, 4), "all_s": [round(v, 4) for v in times[k]], "problems_per_s": round(a.B / t),
+                  "status": {str(v): int(np.sum(r.status == v)) for v in sorted(set(int(v) for v in r.status))},
+                  "passes_mean": round(float(r.nit.mean()), 3), "factorisations_mean": round(float(r.nfact.mean()), 3),
+                  "active_share": round(float(np.mean(r.active_mask != 0)), 3),
+                  "max_optimality": float(np.max(r.optimality[r.status == 1], initial=0.0))}
+    r = out["bvls_eq"]
+    ok = r.status == 1
+    res["bvls_eq"]["max_sum_error"] = float(np.max(np.abs(r.x[ok].sum(axis=1) - a.sum_to), initial=0.0))
 
 
 def bvls_main(a, A, b, ctx, res):
     lb, ub = np.zeros((a.B, a.n)), np.ones((a.B, a.n))
     if a.kernel:
         res.update(launches=a.launches, rounds=a.rounds)
-        res.update(bvls_kernel_times(ctx, A, b, lb, ub, a.launches, a.rounds))
+        res.update(bvls_kernel_times(ctx, A, b, lb, ub, a.launches, a.rounds, a.sum_to))
+        return
+    if a.sum_to is not None:
+        bvls_sum_main(a, A, b, ctx, res, lb, ub)
         return
     tol = 1e-10
     x0 = np.full((a.B, a.n), 0.5)
@@ -176,7 +230,11 @@ def main():
     ap.add_argument("--kernel", action="store_true", help="time the kernel's launches alone")
     ap.add_argument("--launches", type=int, default=200)
     ap.add_argument("--rounds", type=int, default=5, help="with --kernel: timed blocks of --launches launches each")
+    ap.add_argument("--sum-to", type=float, default=None, dest="sum_to",
+                    help="with --method bvls: the equality sum x = SUM_TO as well")
     a = ap.parse_args()
+    if a.sum_to is not None and a.method != "bvls":
+        ap.error("--sum-to goes with --method bvls")
     A, b = problems(a.B, a.m, a.n, a.own)
     ctx = _abi.Context(0)
     res = {"B": a.B, "m": a.m, "n": a.n, "shared": not a.own, "method": a.method}
