@@ -194,6 +194,13 @@ SIGNATURES = {
     "blsq_varpro_expand_dev": (C.c_int, [vp] + [C.c_int] * 3 + [c_int32_p, vp, vp]),
     # ctx, B, m, n, nl, lin, owner, G, y, w, w_stride, f, J, c, info, mask (lin and owner on the host)
     "blsq_varpro_reduce_dev": (C.c_int, [vp] + [C.c_int] * 4 + [c_int32_p, c_int32_p, vp, vp, vp, C.c_long] + [vp] * 5),
+    # ctx, G, S, n, nl, lin, shared, X, P (lin and shared on the host)
+    "blsq_varpro_expand_global_dev": (C.c_int, [vp] + [C.c_int] * 4 + [c_int32_p, c_int32_p, vp, vp]),
+    # ctx, G, S, m, n, nl, lin, owner, shared, G, y, w, w_stride, f, J, c, info, Sinv, TD, mask
+    "blsq_varpro_reduce_global_dev": (C.c_int, [vp] + [C.c_int] * 5 + [c_int32_p, c_int32_p, c_int32_p, vp, vp, vp,
+                                                       C.c_long] + [vp] * 7),
+    # ctx, G, S, n, nl, lin, shared, C, Sinv, TD, scale, info, status, cov
+    "blsq_varpro_cov_blocks_dev": (C.c_int, [vp] + [C.c_int] * 4 + [c_int32_p, c_int32_p] + [vp] * 7),
     # nops, ops, root, nconst, nf, npfix, ncoord (no ctx, no device)
     "blsq_expr_check": (C.c_int, [C.c_int, C.POINTER(C.c_uint64), C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]),
     # ctx, est, nan_policy, B, reps, m, nf, npfix, ncoord, nops, ops, root, nconst, consts, t, t_stride, y, w, w_stride,

@@ -854,9 +854,156 @@ def _fit_separable(f, xdata, ydata, P0, sigma, absolute_sigma, bounds, method, j
 GLOBAL_MAX_NV = 256                                      # BLSQ_GLOBAL_MAX_NV
 
 
+def _fit_separable_global(f, xdata, ydata, p0, shared, sigma, absolute_sigma, bounds, method, jac, driver, ctx, fixed,
+                          tied, estimator, nan_policy, kwargs):
+    """``curve_fit_global(separable=True)``: the checks, the solve over the non-linear parameters in the
+    layout of ``models.separable_global_map``, the linear ones filled in and the blocks of the full covariance."""
+    kwargs = dict(kwargs)
+    if kwargs.pop('binned', False):
+        raise ValueError("`binned=True` is not supported by `curve_fit_global`.")
+    if kwargs.pop('response', None) is not None or kwargs.pop('response_origin', 0) != 0:
+        raise ValueError("`response` is not supported by `curve_fit_global`: an instrument response is not built for "
+                         "global fits.")
+    if isinstance(f, _models.ExprModel):
+        raise ValueError("`separable=True` is not yet supported with the expression model '%s': the structure of a "
+                         "formula is not known." % f.name)
+    if not isinstance(f, (str, _models.CompositeModel)):
+        raise ValueError("`separable=True` needs a built-in model (a name, a spec or a CompositeModel) as `f`: the "
+                         "linear parameters of a callable are not known.")
+    if jac is not None:
+        raise ValueError("`jac` must be None with `separable=True`: Kaufman's Jacobian comes from the model's analytic "
+                         "one ('2-point' / '3-point' and a callable are not yet supported).")
+    if kwargs.get('loss', 'linear') != 'linear':
+        raise ValueError("`loss` must be 'linear' with `separable=True`: a robust loss is not yet supported.")
+    if _models.check_estimator(estimator) != 'lse':
+        raise ValueError("estimator='poisson' is not yet supported with `separable=True`.")
+    if nan_policy == 'omit':
+        raise ValueError("nan_policy='omit' is not yet supported with `separable=True`.")
+    if nan_policy not in (None, 'raise'):
+        raise ValueError("`nan_policy` must be None or 'raise' with `separable=True`, not %r." % (nan_policy,))
+    if fixed is not None or tied:
+        raise ValueError("`fixed` / `tied` are not yet supported with `separable=True`.")
+    if kwargs.get('leverage', False):
+        raise ValueError("leverage=True is not yet supported with `separable=True`.")
+    if driver not in ('host', 'device'):
+        raise ValueError("`driver` must be 'host' or 'device'.")
+    if 'args' in kwargs:
+        raise ValueError("'args' is not a supported keyword argument.")
+    if 'max_nfev' not in kwargs:
+        kwargs['max_nfev'] = kwargs.pop('maxfev', None)
+    ydata = np.asarray(ydata, float)
+    P0 = np.asarray(p0, float)
+    single = ydata.ndim == 2
+    if single:
+        ydata = ydata[np.newaxis]
+        if P0.ndim == 2:
+            P0 = P0[np.newaxis]
+    if ydata.ndim != 3:
+        raise ValueError("`ydata` must have shape (S, m) or (G, S, m).")
+    if ydata.size == 0:
+        raise ValueError("`ydata` must not be empty!")
+    if nan_policy == 'raise' and np.isnan(ydata).any():
+        raise ValueError("The input contains nan values")
+    G, S, m = ydata.shape
+    if P0.ndim != 3 or P0.shape[:2] != (G, S):
+        raise ValueError("`p0` must have shape (S, n) or (G, S, n) like `ydata`.")
+    n = P0.shape[2]
+    model = _models.resolve(f)
+    model.terms(n)
+    _models.check_global(model)
+    gm, lin, owner, non = _models.separable_global_map(model, n, S, shared)
+    nl, nv = lin.size, gm.nv
+    if nv > GLOBAL_MAX_NV:
+        raise ValueError("the group has nv = nsh + S nloc = %d + %d * %d = %d non-linear variables, more than %d."
+                         % (gm.ns, S, gm.nl, nv, GLOBAL_MAX_NV))
+    if m <= nl:
+        raise ValueError("`separable=True` needs more points than linear parameters: m = %d, nl = %d." % (m, nl))
+    x_dev, _, sstride = _models.global_xdata(xdata, G, S, m)
+    if len(bounds) != 2:
+        raise ValueError("`bounds` must contain 2 elements.")
+    try:
+        lb = np.broadcast_to(np.asarray(bounds[0], dtype=float), (G, S, n))
+        ub = np.broadcast_to(np.asarray(bounds[1], dtype=float), (G, S, n))
+    except ValueError:
+        raise ValueError("`bounds` must be broadcastable to (G, S, n): they keep all n parameters.") from None
+    names = getattr(model, 'param_names', None)
+    for k in lin:
+        if not (np.all(lb[..., k] == -np.inf) and np.all(ub[..., k] == np.inf)):
+            raise ValueError("`separable=True`: parameter %d%s is linear and is projected out, so its bounds must be "
+                             "infinite; fit without `separable=True` to bound it."
+                             % (k, " ('%s')" % names[k] if names else ""))
+    if sigma is not None:
+        sigma = np.asarray(sigma, float)
+        _models.sigma_weights(sigma, (G, S), m)
+    red = gm.reduce_bounds(lb[..., non], ub[..., non])
+    X0 = np.ascontiguousarray(gm.reduce_x(P0[..., non]))
+    if ctx is None:
+        from ._hip_step import default_context
+        ctx = default_context()
+    spec = _models.resolvable(model)
+    M, dof = S * m, S * m - nv - S * nl
+    want = dict(bounds=red, method=method, driver=driver, ctx=ctx, covariance='pinv', _variance_scale=False, **kwargs)
+
+    def factor(results):
+        """(scale (G,) or None, status (G,)): the variance factor of every group, and 1 where its covariance is
+        missing."""
+        status = np.array([0 if (r.success and r.x_covariance is not None and not np.isnan(r.x_covariance).any())
+                           else 1 for r in results], dtype=np.int32)
+        if absolute_sigma or dof <= 0:
+            return None, status
+        return np.array([r.obj_value for r in results], dtype=float) / dof, status
+
+    if driver == 'device':
+        func = _models.DeviceFit(spec, n, x_dev, ydata, sigma, separable=True, global_map=gm)
+        results = least_squares_batch(func, X0, None, **want)
+        X = np.stack([r.x for r in results])
+        scale, status = factor(results)
+        Cred = np.stack([r.x_covariance if st == 0 else np.full((nv, nv), np.nan) for r, st in zip(results, status)])
+        with _models.DeviceModel(ctx, spec, G, m, n, x_dev, ydata, sigma, separable=True, global_map=gm) as dm:
+            d_X, d_C = ctx.to_device(X), ctx.to_device(np.ascontiguousarray(Cred))
+            try:
+                cov, c, info = dm.covariance_blocks(d_X, d_C, scale, status)
+            finally:
+                ctx.free(d_X)
+                ctx.free(d_C)
+    else:
+        from ._varpro import _HostGlobalStage
+        stage = _HostGlobalStage(model, ydata, shared, sigma, n)
+        results = least_squares_batch(lambda X: stage(x_dev, X)[0], X0, lambda X: stage(x_dev, X)[1], **want)
+        X = np.stack([r.x for r in results])
+        scale, status = factor(results)
+        Cred = np.stack([r.x_covariance if st == 0 else np.full((nv, nv), np.nan) for r, st in zip(results, status)])
+        _, _, c, info, Sinv, TD = stage(x_dev, X)
+        cov = _models.separable_global_cov(Cred, Sinv, TD, gm, scale, lin)
+    popt = np.full((G, S, n), np.nan)
+    pcov = np.full((G, S, n, n), np.nan)
+    alpha = gm.split_x(X)                                    # (G, S, na)
+    warn_cov = False
+    for g, r in enumerate(results):
+        r.global_map, r.linear_params = gm, lin.copy()
+        r.popt = _models.varpro_expand(alpha[g], lin, n)
+        r.popt[:, lin] = c[g]
+        r.linear_coefficients = c[g].copy()
+        if r.x_covariance is not None and scale is not None:
+            r.x_covariance = r.x_covariance * scale[g]
+        if not r.success:
+            continue
+        popt[g] = r.popt
+        if status[g] != 0 or (dof <= 0 and not absolute_sigma) or np.isnan(cov[g]).any():
+            pcov[g] = np.inf
+            warn_cov = True
+        else:
+            pcov[g] = cov[g]
+    if warn_cov:
+        warnings.warn(_COV_WARNING, category=OptimizeWarning, stacklevel=3)
+    if single:
+        return popt[0], pcov[0], results
+    return popt, pcov, results
+
+
 def curve_fit_global(f, xdata, ydata, p0, shared, sigma=None, absolute_sigma=False, bounds=(-np.inf, np.inf),
                      method='trf', jac=None, driver='host', ctx=None, fixed=None, tied=None, estimator='lse',
-                     nan_policy=None, **kwargs):
+                     nan_policy=None, separable=False, **kwargs):
     """A global fit: S data sets of one model fitted together, with the parameters in `shared` common to all of them
     (DESIGN.md 7p).  A decay measured at S wavelengths, a line scanned at S temperatures: the rates, the position and
     the width have one value for the group, the amplitudes and baselines one per data set.
@@ -891,7 +1038,38 @@ def curve_fit_global(f, xdata, ydata, p0, shared, sigma=None, absolute_sigma=Fal
     sets —, ``popt`` (S, n), ``global_map``, ``fun`` (M,), ``jac`` (M, nv), ``leverage`` (M,) with ``leverage=True``,
     ``deviance`` under Poisson, ``nobs`` and ``omitted`` (S, m) under 'omit'.  A group that did not converge gives NaN
     rows; with 'omit' a data set without a single point is a ValueError naming group and data set.
+
+    separable : False (the default: nothing changes, bit for bit) or True: the classical algorithm of
+            global analysis.  The linear parameters of the model (``models.linear_params``) are projected out per data
+            set, so the solver sees the non-linear ones alone: nv = nsh + S nloc variables (nsh shared, nloc local
+            non-linear parameters; the layout is ``models.separable_global_map``'s ``GlobalMap`` over the non-linear
+            parameters).  nv <= 256 holds for THIS count: with every non-linear parameter shared a group of any S is
+            a problem of nsh columns, and the full count nv + S nl has no limit.  Every index in `shared` must be
+            non-linear (a shared amplitude would couple the projections: ValueError naming it).  `f` is a name, a spec
+            or a ``CompositeModel`` of one coordinate, on either driver (driver='device': blsq_varpro_expand_global_dev,
+            the model kernel on the G S data sets and blsq_varpro_reduce_global_dev per evaluation; driver='host':
+            ``models.separable_global_residual`` / ``_jacobian``, the definition).  `p0`, `bounds`, `popt` and `pcov`
+            keep all n parameters per data set; the linear entries of `p0` are ignored (they may be NaN) and those of
+            `bounds` must be infinite; the box of a shared parameter is the intersection over the group.  `sigma` in
+            the shapes above, `absolute_sigma`, bounds on the non-linear parameters and both methods compose.  `popt`
+            has c(alpha*) filled in.  ``pcov[g, s]`` is the (n, n) block of data set s of the covariance of the FULL
+            problem: Kaufman's ``J^T J`` is the Schur complement of the full Gauss-Newton matrix, so the covariance of
+            the reduced group is the exact alpha-alpha block and the others follow from (nl, nl) and (nl, n - nl)
+            matrices of the projection (``models.separable_global_cov``; on the device blsq_varpro_cov_blocks_dev) —
+            nothing of the full size is formed.  Its variance factor is ``obj_value / (S m - nv - S nl)`` unless
+            `absolute_sigma`; a group without a degree of freedom, or whose reduced covariance is missing, gets inf
+            under the ``OptimizeWarning``.  ``results[g]`` carries ``x`` (nv,), ``x_covariance`` (nv, nv) — the reduced
+            matrix, the exact alpha-alpha block of the full covariance, with the same factor —, ``popt`` (S, n),
+            ``linear_coefficients`` (S, nl), ``linear_params``, ``global_map``, ``fun`` (S m,) and ``jac`` (S m, nv).
+            Each a ValueError of its own: a callable or an ``ExprModel`` as `f`, ``jac=`` other than None, ``loss=``
+            other than 'linear', ``estimator='poisson'``, ``nan_policy='omit'``, `fixed` / `tied`, ``leverage=True``,
+            m <= nl and a model with nothing non-linear.
     """
+    if not isinstance(separable, (bool, np.bool_)):
+        raise ValueError("`separable` must be False or True.")
+    if separable:
+        return _fit_separable_global(f, xdata, ydata, p0, shared, sigma, absolute_sigma, bounds, method, jac, driver,
+                                     ctx, fixed, tied, estimator, nan_policy, kwargs)
     if kwargs.pop('binned', False):
         raise ValueError("`binned=True` is not supported by `curve_fit_global`.")
     if kwargs.pop('response', None) is not None or kwargs.pop('response_origin', 0) != 0:

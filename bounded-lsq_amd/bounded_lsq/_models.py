@@ -93,7 +93,8 @@ import numpy as np
 from . import _abi
 from ._expr import ExprModel, expression
 from ._varpro import (VARPRO_MAX_NL, VARPRO_PIVOT_TOL, linear_params, varpro_reduce, varpro_expand, separable_residual,
-                      separable_jacobian, separable_coefficients)
+                      separable_jacobian, separable_coefficients, separable_global_map, separable_global_residual,
+                      separable_global_jacobian, separable_global_coefficients, separable_global_cov)
 
 MAX_N = 64                                   # BLSQ_MODEL_MAX_N
 MAX_COMP = 8                                 # BLSQ_MODEL_MAX_COMP
@@ -113,7 +114,8 @@ __all__ = ['MODELS', 'NAMES', 'MAX_N', 'MAX_COMP', 'TERMS', 'get', 'compose', 'r
            'omit_jacobian', 'count_observed', 'pad_ragged', 'RESPONSE_MAX_L', 'check_response', 'apply_response',
            'response_residual', 'response_jacobian', 'expression', 'ExprModel', 'VARPRO_MAX_NL', 'VARPRO_PIVOT_TOL',
            'linear_params', 'varpro_reduce', 'varpro_expand', 'separable_residual', 'separable_jacobian',
-           'separable_coefficients', 'check_separable']
+           'separable_coefficients', 'check_separable', 'separable_global_map', 'separable_global_residual',
+           'separable_global_jacobian', 'separable_global_coefficients', 'separable_global_cov']
 
 
 def _tp(xdata, P):
@@ -969,14 +971,21 @@ def check_expr_model(model, binned=False, global_fit=False):
 
 def check_separable(model, n, param_map=None, estimator='lse', nan_policy='propagate', global_map=None, response=None):
     """``linear_params(model, n)`` after what a separable fit does not take, as ValueErrors: a parameter
-    map, the Poisson estimator, omission, a global fit and an instrument response (an ``ExprModel`` and a model without
-    a non-linear parameter are refused by ``linear_params``)."""
+    map, the Poisson estimator, omission and an instrument response (an ``ExprModel`` and a model without a non-linear
+    parameter are refused by ``linear_params``).  A `global_map` is the ``GlobalMap`` over the n - nl
+    NON-LINEAR parameters (``separable_global_map``), without fixed or tied slots."""
     for what, given in (("`fixed` / `tied` (a parameter map)", param_map is not None),
                         ("estimator='poisson'", estimator != 'lse'), ("nan_policy='omit'", nan_policy != 'propagate'),
-                        ("a global fit", global_map is not None), ("`response`", response is not None)):
+                        ("`response`", response is not None)):
         if given:
             raise ValueError("%s is not yet supported with `separable=True`." % what)
-    return linear_params(model, n)
+    lin, owner = linear_params(model, n)
+    if global_map is not None:
+        gm = global_map
+        if gm.n != owner.size - lin.size or gm.nf != gm.n or gm.pm.affine:
+            raise ValueError("`global_map` of a separable fit must be the GlobalMap over the %d non-linear parameters "
+                             "(models.separable_global_map), without fixed or tied ones." % (owner.size - lin.size))
+    return lin, owner
 
 
 def check_global(model, binned=False, param_map=None):
@@ -1075,7 +1084,15 @@ class DeviceModel:
     between blsq_varpro_expand_dev and blsq_varpro_reduce_dev on the same stream: three launches per evaluation, for
     ``fun_dev`` and ``jac_dev`` alike (f needs Phi too); `reps` must be 1.  ``linear_coefficients(x_ptr)`` runs the stage
     at x and returns c (B, nl), ``rank_info(x_ptr)`` its info flags.  `ydata` is required; `binned` and `sigma` compose;
-    a map, the Poisson estimator, omission, `global_map`, `response` and an ``ExprModel`` are ValueErrors."""
+    a map, the Poisson estimator, omission, `response` and an ``ExprModel`` are ValueErrors.
+
+    ``separable=True`` with ``global_map=``: the ``GlobalMap`` over the NON-LINEAR parameters
+    (``separable_global_map``).  B is the number of groups G, ``m`` becomes S m and ``n`` becomes nv, as for a global
+    fit; `xdata`, `ydata` and `sigma` have its shapes.  An evaluation is blsq_varpro_expand_global_dev, the plain batch
+    entry of the model on the G S data sets (raw, as above) and blsq_varpro_reduce_global_dev, which writes Kaufman's
+    Jacobian straight into the group's layout; `reps` must be 1.  ``linear_coefficients(x_ptr)`` gives c (G, S, nl) and
+    ``covariance_blocks(x_ptr, C_ptr, scale)`` the (G, S, n, n) blocks of the full covariance at x from the reduced
+    covariance C [G][nv][nv] (blsq_varpro_cov_blocks_dev)."""
 
     def __init__(self, ctx, name, B, m, n, xdata, ydata=None, sigma=None, param_map=None, Pfix=None, estimator='lse',
                  binned=False, nan_policy='propagate', global_map=None, response=None, response_origin=0,
@@ -1107,7 +1124,9 @@ class DeviceModel:
                 raise ValueError("`sigma` must be None with estimator='poisson'.")
         self.model, self.B, self.n_model = model, int(B), int(n)
         self.param_map, self.global_map = param_map, gm
-        for what, mp in (("param_map", param_map), ("global_map", gm)):
+        sep_global = self.separable and gm is not None       # (its map is over the non-linear parameters: checked above)
+        self._B_eval = self.B * gm.S if sep_global else self.B   # the problems of the model entry
+        for what, mp in (("param_map", param_map), ("global_map", None if sep_global else gm)):
             if mp is not None and mp.n != self.n_model:
                 raise ValueError("`%s` is for %d parameters, the model has %d." % (what, mp.n, self.n_model))
         # what a batch and a global model differ in: `m` stays the m of one data set, `self.m` is the problem's
@@ -1122,6 +1141,16 @@ class DeviceModel:
                 if m <= len(self.lin):
                     raise ValueError("`separable=True` needs more points than linear parameters: m = %d, nl = %d."
                                      % (m, len(self.lin)))
+        elif sep_global:                         # the model entry sees a plain batch of G S data sets
+            x, _, sstride = global_xdata(xdata, B, gm.S, m)
+            if sstride:
+                x = np.ascontiguousarray(np.broadcast_to(x, (B, gm.S, m))).reshape(B * gm.S, m)
+            self.t_stride, self.t_sstride = (m if sstride else 0), 0
+            lead, dims, pm, shared = (B, gm.S), "G, S", None, None
+            self.m, self.n = gm.S * m, gm.nv
+            if m <= len(self.lin):
+                raise ValueError("`separable=True` needs more points than linear parameters: m = %d, nl = %d."
+                                 % (m, len(self.lin)))
         else:
             x, self.t_stride, self.t_sstride = global_xdata(xdata, B, gm.S, m)
             lead, dims, pm = (B, gm.S), "G, S", gm.pm
@@ -1158,7 +1187,9 @@ class DeviceModel:
         self._bind(m, pm, pmap, shared)
         if self.response is not None:
             self._bind_response()
-        if self.separable:
+        if sep_global:
+            self._bind_separable_global(m)
+        elif self.separable:
             self._bind_separable()
         ctx.adopt(self)
 
@@ -1180,7 +1211,8 @@ class DeviceModel:
         model and the flags before it); without a flag, the entry of the kind of model.  `m`: the points of one data
         set; `pm`: the ParamMap of the fit (a global fit's own) or None, `pmap` its int32 map; `shared`: the int32 flags of
         the slots a group shares, or None."""
-        M, comp, gm = self.model, isinstance(self.model, CompositeModel), self.global_map
+        M, comp = self.model, isinstance(self.model, CompositeModel)
+        gm = None if self.separable else self.global_map      # (a separable global fit binds the plain batch entry)
         # behind an instrument response or the projection of a separable fit the entry gives the raw model: data,
         # weights, estimator and omission are withheld
         estimator, nan_policy, d_y, d_w, w_stride = (
@@ -1230,7 +1262,7 @@ class DeviceModel:
             ncomp=len(M.components) if comp else 0, fam=host(M.fam_ids) if comp else None,
             cnt=host(M.counts) if comp else None,
             S=0 if gm is None else gm.S, shared=host(shared), t_sstride=self.t_sstride,       # S == 0: a plain batch
-            B=self.B, reps=1, m=m, n=self.n_model,
+            B=self._B_eval, reps=1, m=m, n=self.n_model,
             nf=(self.n_model if self.separable else self.n) if gm is None else gm.nf, pmap=host(pmap),   # nf: per data set
             tie_ratio=host(ratio, _abi.c_double_p), tie_offset=host(offset, _abi.c_double_p),
             t=self.d_t, t_stride=self.t_stride, y=d_y, w=d_w, w_stride=w_stride, X=None,
@@ -1310,18 +1342,79 @@ class DeviceModel:
                                                      info_ptr, mask_ptr), "blsq_varpro_reduce_dev")
         self._eval = _eval
 
+    def _bind_separable_global(self, m):
+        """As ``_bind_separable`` for G groups of S data sets of `m` points: P (G S, n) and G (G S, m, n),
+        and expand-global -> model kernel on the G S data sets -> reduce-global, which writes J in the group's layout."""
+        ctx, inner, gm = self.ctx, self._eval, self.global_map
+        G, S, n, nl = self.B, gm.S, self.n_model, len(self.lin)
+        lin, owner = (np.ascontiguousarray(a, dtype=np.int32) for a in (self.lin, self.owner))
+        shared = np.zeros(n, dtype=np.int32)
+        shared[np.flatnonzero(owner >= 0)[gm.shared_slots]] = 1
+        self._host_sep = (lin, owner, shared)                 # the host arrays the entries read: alive with the model
+        p_lin, p_owner, p_shared = (a.ctypes.data_as(_abi.c_int32_p) for a in self._host_sep)
+        d_P, d_G = ctx.malloc(8 * G * S * n), ctx.malloc(8 * G * S * m * n)
+        self._bufs += [d_P, d_G]
+        tail = [self.d_y, self.d_w, self.w_stride]            # (w_stride: 0 or S m)
+        self._layout_args = (G, S, n, nl, p_lin, p_shared)
+
+        def _eval(x_ptr, reps, f_ptr, J_ptr, mask_ptr, c_ptr=None, info_ptr=None, Sinv_ptr=None, TD_ptr=None):
+            if int(reps) != 1:
+                raise ValueError("`separable=True` evaluates one point per problem: reps must be 1 (finite-difference "
+                                 "Jacobians are not supported).")
+            ctx.check(ctx.lib.blsq_varpro_expand_global_dev(ctx.h, G, S, n, nl, p_lin, p_shared, x_ptr, d_P),
+                      "blsq_varpro_expand_global_dev")
+            inner(d_P, 1, None, d_G, None)                    # (the mask is per group: every data set is evaluated)
+            ctx.check(ctx.lib.blsq_varpro_reduce_global_dev(ctx.h, G, S, m, n, nl, p_lin, p_owner, p_shared, d_G, *tail,
+                                                            f_ptr, J_ptr, c_ptr, info_ptr, Sinv_ptr, TD_ptr, mask_ptr),
+                      "blsq_varpro_reduce_global_dev")
+        self._eval = _eval
+
+    def covariance_blocks(self, x_ptr, C_ptr, scale=None, status=None):
+        """The blocks (G, S, n, n) of the full covariance of a separable global fit at the device vectors x [G][nv],
+        from the covariance C [G][nv][nv] of the reduced group on the device: the stage is run at x for
+        Sinv and TD, then blsq_varpro_cov_blocks_dev.  `scale` (G,) or None multiplies group g; `status` (G,) int or
+        None: a group with a nonzero entry, like a data set that is rank deficient at x, gets NaN.  Returns
+        ``(cov, c (G, S, nl), info (G, S))``."""
+        if not (self.separable and self.global_map is not None):
+            raise ValueError("the model was not opened with `separable=True` and a `global_map`.")
+        ctx, gm = self.ctx, self.global_map
+        G, S, n, nl, p_lin, p_shared = self._layout_args
+        GS, na = G * S, n - nl
+        bufs = [ctx.malloc(8 * GS * nl), ctx.malloc(4 * GS), ctx.malloc(8 * GS * nl * nl), ctx.malloc(8 * GS * nl * na),
+                ctx.malloc(8 * GS * n * n)]
+        d_c, d_info, d_Sinv, d_TD, d_cov = bufs
+        try:
+            d_scale = d_status = None
+            if scale is not None:
+                d_scale = ctx.to_device(np.ascontiguousarray(np.broadcast_to(scale, (G,)), dtype=np.float64))
+                bufs.append(d_scale)
+            if status is not None:
+                d_status = ctx.to_device(np.ascontiguousarray(np.broadcast_to(status, (G,)), dtype=np.int32))
+                bufs.append(d_status)
+            self._eval(x_ptr, 1, None, None, None, c_ptr=d_c, info_ptr=d_info, Sinv_ptr=d_Sinv, TD_ptr=d_TD)
+            ctx.check(ctx.lib.blsq_varpro_cov_blocks_dev(ctx.h, G, S, n, nl, p_lin, p_shared, C_ptr, d_Sinv, d_TD, d_scale,
+                                                         d_info, d_status, d_cov), "blsq_varpro_cov_blocks_dev")
+            ctx.sync()
+            return (ctx.to_host(d_cov, (G, S, n, n), np.float64), ctx.to_host(d_c, (G, S, nl), np.float64),
+                    ctx.to_host(d_info, (G, S), np.int32))
+        finally:
+            for p in bufs:
+                ctx.free(p)
+
     def linear_coefficients(self, x_ptr, with_info=False):
         """c (B, nl) of a separable model at the device vectors x [B][n]: the stage is run there, because the driver's
         last evaluation may have been at a rejected trial point.  ``with_info=True``: ``(c, info)``, info (B,) int32
-        with 1 where Phi is rank deficient at x (c is NaN there)."""
+        with 1 where Phi is rank deficient at x (c is NaN there).  With a `global_map`: c (G, S, nl), info (G, S)."""
         if not self.separable:
             raise ValueError("the model was not opened with `separable=True`.")
-        ctx, B, nl = self.ctx, self.B, len(self.lin)
+        ctx, nl = self.ctx, len(self.lin)
+        lead = (self.B,) if self.global_map is None else (self.B, self.global_map.S)
+        B = int(np.prod(lead))
         d_c, d_info = ctx.malloc(8 * nl * B), ctx.malloc(4 * B)
         try:
             self._eval(x_ptr, 1, None, None, None, c_ptr=d_c, info_ptr=d_info)
-            c = ctx.to_host(d_c, (B, nl), np.float64)
-            return (c, ctx.to_host(d_info, (B,), np.int32)) if with_info else c
+            c = ctx.to_host(d_c, lead + (nl,), np.float64)
+            return (c, ctx.to_host(d_info, lead, np.int32)) if with_info else c
         finally:
             ctx.free(d_c)
             ctx.free(d_info)
@@ -1355,7 +1448,8 @@ class DeviceFit:
     ``DeviceModel``.  ``global_map=``: as ``DeviceModel``; `ydata` is (G, S, m), and ``B`` is G, ``m`` is S m and ``n``
     is nv.  ``response=``, ``response_origin=``: as ``DeviceModel`` (checked here, before any GPU is touched).
     ``separable=True``: as ``DeviceModel``; ``n`` is the number of non-linear parameters and ``lin`` / ``owner`` are
-    those of ``linear_params``."""
+    those of ``linear_params``.  With ``global_map=`` as well (DESIGN.md 7x): the map over the non-linear parameters;
+    ``B`` is G, ``m`` is S m and ``n`` is nv."""
 
     def __init__(self, name, n, xdata, ydata, sigma=None, param_map=None, Pfix=None, estimator='lse', binned=False,
                  nan_policy='propagate', global_map=None, response=None, response_origin=0, separable=False):
@@ -1392,7 +1486,7 @@ class DeviceFit:
         self.n_model = int(n)
         self.param_map, self.Pfix = param_map, Pfix
         mp, what, dims = (param_map, "param_map", "B") if gm is None else (gm, "global_map", "G, S")
-        if mp is not None:
+        if mp is not None and not (self.separable and gm is not None):    # (that map is over the non-linear ones)
             if mp.n != self.n_model:
                 raise ValueError("`%s` is for %d parameters, the model has %d." % (what, mp.n, self.n_model))
             if gm is None or Pfix is not None:                # (a global fit needs it where a parameter is fixed)
@@ -1410,6 +1504,9 @@ class DeviceFit:
         else:
             self.m, self.n = gm.S * self._m_set, gm.nv
             self.xdata = global_xdata(xdata, self.B, gm.S, self._m_set)[0]
+            if self.separable and self._m_set <= len(self.lin):
+                raise ValueError("`separable=True` needs more points than linear parameters: m = %d, nl = %d."
+                                 % (self._m_set, len(self.lin)))
         self.sigma = sigma
 
     def open_device(self, ctx, lb, ub):

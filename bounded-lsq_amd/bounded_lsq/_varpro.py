@@ -37,7 +37,9 @@ VARPRO_MAX_NL = 16                           # BLSQ_VARPRO_MAX_NL
 VARPRO_PIVOT_TOL = 64.0                      # ... in units of eps of the working precision
 
 __all__ = ['VARPRO_MAX_NL', 'VARPRO_PIVOT_TOL', 'linear_params', 'varpro_reduce', 'varpro_expand',
-           'separable_residual', 'separable_jacobian', 'separable_coefficients']
+           'separable_residual', 'separable_jacobian', 'separable_coefficients', 'separable_global_map',
+           'separable_global_residual', 'separable_global_jacobian', 'separable_global_coefficients',
+           'separable_global_cov']
 
 _USE_LINEAR = ("model '%s' has no non-linear parameter left: it is a linear least-squares problem, use `lsq_linear`.")
 
@@ -188,6 +190,14 @@ def varpro_reduce(G, y, w, lin, owner):
     at unit linear parameters; `y`: (B, m); `w`: None (1), (m,) or (B, m) weights 1 / sigma; `lin`, `owner`: as
     ``linear_params`` returns them.  ``info[b] = 1``, and NaN in f, J_K and c of problem b, where Phi is rank deficient
     (two identical peaks, a column of zeros).  The result has the common floating dtype of G, y and w."""
+    return _reduce_full(G, y, w, lin, owner)[:4]
+
+
+def _reduce_full(G, y, w, lin, owner):
+    """``varpro_reduce`` and the two small matrices a separable global fit finishes its covariance with:
+    ``(f, J_K, c, info, Sinv, TD)`` with ``Sinv = (Phi_w^T Phi_w)^-1`` (B, nl, nl) through the same factor and
+    ``TD[:, :, i] = c[owner[non[i]]] (T + T2)[:, :, i]`` (B, nl, n - nl), computed from T after one more correction
+    whose residual is formed in np.longdouble; NaN where info is 1."""
     G, y = np.asarray(G), np.asarray(y)
     if G.ndim != 3 or y.shape != G.shape[:2]:
         raise ValueError("`G` must have shape (B, m, n) and `y` (B, m).")
@@ -220,9 +230,22 @@ def varpro_reduce(G, y, w, lin, owner):
         c = T[:, :, -1].copy()
         f = -E[:, :, -1]
         J = c[:, owner[non]][:, None, :] * E[:, :, :-1]
+        Sinv = _solve(d, R, np.broadcast_to(np.eye(nl, dtype=dt), (B, nl, nl)).copy())
+        Sinv = (Sinv + np.swapaxes(Sinv, 1, 2)) / dt.type(2)
+        # TD needs T beyond kappa eps |T| (a column of T solves for a column of G, with a residual as large as the
+        # column): one more correction with the residual in extended precision, on the unrounded w G
+        xt = np.longdouble
+        wx = None if w is None else w.astype(xt)
+        Px = G[:, :, lin].astype(xt) if w is None else wx[:, :, None] * G[:, :, lin].astype(xt)
+        Ax = np.concatenate([G[:, :, non].astype(xt), y.astype(xt)[:, :, None]], axis=2)
+        if w is not None:
+            Ax = wx[:, :, None] * Ax
+        r = np.einsum('bip,biq->bpq', Px, Ax - np.einsum('bip,bpq->biq', Px, T.astype(xt)))
+        T3 = T + _solve(d, R, r.astype(dt))
+        TD = T3[:, :, -1][:, owner[non]][:, None, :] * T3[:, :, :-1]
     nan = dt.type(np.nan)
-    f[bad], J[bad], c[bad] = nan, nan, nan
-    return f, J, c, bad.astype(np.int32)
+    f[bad], J[bad], c[bad], Sinv[bad], TD[bad] = nan, nan, nan, nan, nan
+    return f, J, c, bad.astype(np.int32), Sinv, TD
 
 
 class _HostStage:
@@ -277,3 +300,146 @@ def separable_coefficients(model, ydata, sigma=None, n=None, binned=False, _stag
     """``coef(xdata, X) -> (B, nl)``: the linear parameters c(X) that ``separable_residual`` projects out."""
     stage = _stage or _HostStage(model, ydata, sigma, n, binned)
     return lambda xdata, X: stage(xdata, X)[2]
+
+
+# ---- separable global fits (DESIGN.md 7x) ----------------------------------------------------------------------------
+def separable_global_map(model, n, S, shared):
+    """``(gmap, lin, owner, non)`` of a separable global fit: `gmap` the ``GlobalMap(na, S, positions of `shared` within
+    non)`` over the na non-linear parameters — THE layout of the group's nv = nsh + S nloc solver variables, the shared
+    ones first, then the window of data set 0, 1, ...  `shared`: a boolean mask (n,) or indices of MODEL parameters.
+    ValueError for a shared linear parameter (it would couple the projections of the data sets), naming it."""
+    from ._params import GlobalMap
+    lin, owner = linear_params(model, n)
+    n = owner.size
+    a = np.asarray(shared)
+    if a.dtype == bool:
+        if a.shape != (n,):
+            raise ValueError("a boolean `shared` must have shape (n,) = (%d,), not %s." % (n, a.shape))
+        idx = np.flatnonzero(a).tolist()
+    else:
+        idx = []
+        for j in np.atleast_1d(a).ravel().tolist() if a.size else []:
+            if int(j) != j or not 0 <= int(j) < n:
+                raise ValueError("`shared` index %r is outside 0 .. %d." % (j, n - 1))
+            idx.append(int(j))
+    non = np.flatnonzero(owner >= 0)
+    pos = {int(j): i for i, j in enumerate(non)}
+    for j in idx:
+        if j not in pos:
+            raise ValueError("`shared` index %d is a linear parameter: with `separable=True` it is projected out per "
+                             "data set and cannot be shared (sharing it would couple the projections); fit without "
+                             "`separable=True` to share it." % j)
+    return GlobalMap(non.size, S, [pos[j] for j in idx]), lin, owner, non
+
+
+class _HostGlobalStage:
+    """The ``driver='host'`` route of a separable global fit, and its definition: every data set of every group reduced
+    by ``varpro_reduce`` at its own alpha (the shared values and its window), f concatenated and Kaufman's Jacobians
+    laid out by ``GlobalMap.reduce_jac``.  One evaluation is remembered."""
+
+    def __init__(self, model, ydata, shared, sigma=None, n=None):
+        from . import _models
+        if not isinstance(model, (_models.Model, _models.CompositeModel)):
+            model = _models.resolve(model)
+        self.y = np.asarray(ydata)
+        if self.y.ndim != 3:
+            raise ValueError("`ydata` must have shape (G, S, m).")
+        G, S, m = self.y.shape
+        self.gmap, self.lin, self.owner, self.non = separable_global_map(model, n, S, shared)
+        self.n = self.owner.size
+        self.jac_of = model.jac
+        self.w = None
+        if sigma is not None:
+            w, per_set = _models.sigma_weights(sigma, (G, S), m)
+            self.w = np.asarray(w).reshape(G * S, m) if per_set else np.broadcast_to(w, (m,))
+        self._at = self._out = None
+
+    def __call__(self, xdata, X):
+        X = np.asarray(X)
+        if self._at is None or self._at.shape != X.shape or not np.array_equal(self._at, X, equal_nan=True):
+            gm = self.gmap
+            G, S, m = self.y.shape
+            if X.shape != (G, gm.nv):
+                raise ValueError("`X` must have shape (G, nv) = (%d, %d), not %s." % (G, gm.nv, X.shape))
+            alpha = gm.split_x(X).reshape(G * S, gm.n)
+            x = np.asarray(xdata)
+            if x.ndim > 1:
+                x = np.broadcast_to(x, (G, S, m)).reshape(G * S, m)
+            Graw = self.jac_of(x, varpro_expand(alpha, self.lin, self.n))
+            f, J, c, info, Sinv, TD = _reduce_full(Graw, self.y.reshape(G * S, m), self.w, self.lin, self.owner)
+            nl = self.lin.size
+            self._out = (f.reshape(G, S * m), gm.reduce_jac(J.reshape(G, S, m, gm.n)), c.reshape(G, S, nl),
+                         info.reshape(G, S), Sinv.reshape(G, S, nl, nl), TD.reshape(G, S, nl, gm.n))
+            self._at = X.copy()
+        return self._out
+
+
+def separable_global_residual(model, ydata, shared, sigma=None, n=None, _stage=None):
+    """``f(xdata, X) -> (G, S m)`` over the nv solver variables X (G, nv) of ``separable_global_map``: the reduced
+    residuals of the S data sets of every group, concatenated.  `ydata` (G, S, m); `sigma` None, a scalar, (m,),
+    (S, m) or (G, S, m); `xdata` (m,), (S, m) or (G, S, m).  NaN in the rows of a data set whose Phi is rank deficient."""
+    stage = _stage or _HostGlobalStage(model, ydata, shared, sigma, n)
+    return lambda xdata, X: stage(xdata, X)[0]
+
+
+def separable_global_jacobian(model, ydata, shared, sigma=None, n=None, _stage=None):
+    """``jac(xdata, X) -> (G, S m, nv)``: ``GlobalMap.reduce_jac`` of Kaufman's Jacobians of the data sets, +0.0 outside
+    a data set's columns (same arguments as ``separable_global_residual``)."""
+    stage = _stage or _HostGlobalStage(model, ydata, shared, sigma, n)
+    return lambda xdata, X: stage(xdata, X)[1]
+
+
+def separable_global_coefficients(model, ydata, shared, sigma=None, n=None, _stage=None):
+    """``coef(xdata, X) -> (G, S, nl)``: the linear parameters of every data set at X."""
+    stage = _stage or _HostGlobalStage(model, ydata, shared, sigma, n)
+    return lambda xdata, X: stage(xdata, X)[2]
+
+
+def _mirror(A):
+    """The upper triangle of (..., k, k) and its mirror image."""
+    U = np.triu(A)
+    return U + np.swapaxes(np.triu(A, 1), -1, -2)
+
+
+def separable_global_cov(C, Sinv, TD, gmap, scale=None, lin=None):
+    """The per-data-set blocks of the covariance of a separable global fit: (..., S, n, n) from the covariance `C`
+    (..., nv, nv) of the reduced group, ``Sinv`` (..., S, nl, nl) and ``TD`` (..., S, nl, na) of every data set
+    (``_reduce_full``), the layout `gmap` and `lin`, the ascending model indices of the nl linear parameters
+    (n = na + nl).  Kaufman's ``J_K^T J_K`` is the Schur complement of the full Gauss-Newton matrix onto the non-linear
+    variables, so C is the exact alpha-alpha block of the full covariance, and with C_s its restriction to the na
+    columns of data set s
+
+        alpha-alpha = C_s,   c-alpha = -TD_s C_s,   c-c = Sinv_s + TD_s C_s TD_s^T
+
+    are the other blocks of data set s.  Everything is multiplied by ``scale`` (...,) where given.  The terms between
+    two data sets are not formed.  Of C_s and of the c-c block the upper triangle is taken and mirrored, as the kernel
+    does: the blocks are exactly symmetric."""
+    if lin is None:
+        raise ValueError("`lin` is required: the model indices of the linear parameters.")
+    C, Sinv, TD = np.asarray(C), np.asarray(Sinv), np.asarray(TD)
+    lin = np.asarray(lin, dtype=np.int64).reshape(-1)
+    na, nl, S = gmap.n, lin.size, gmap.S
+    n = na + nl
+    if C.shape[-2:] != (gmap.nv, gmap.nv):
+        raise ValueError("`C` must have shape (..., nv, nv) = (..., %d, %d), not %s." % (gmap.nv, gmap.nv, C.shape))
+    lead = C.shape[:-2]
+    if Sinv.shape != lead + (S, nl, nl) or TD.shape != lead + (S, nl, na):
+        raise ValueError("`Sinv` and `TD` must have shapes (..., S, nl, nl) and (..., S, nl, na).")
+    keep = np.ones(n, dtype=bool)
+    keep[lin] = False
+    non = np.flatnonzero(keep)
+    dt = np.result_type(C.dtype, Sinv.dtype, TD.dtype, np.float64)
+    out = np.zeros(lead + (S, n, n), dtype=dt)
+    for s in range(S):
+        cols = gmap.cols[s]
+        Cs = _mirror(C[..., cols[:, None], cols[None, :]].astype(dt))
+        W = np.einsum('...pi,...ia->...pa', TD[..., s, :, :], Cs)
+        cc = _mirror(Sinv[..., s, :, :] + np.einsum('...pa,...qa->...pq', W, TD[..., s, :, :]))
+        blk = out[..., s, :, :]
+        blk[..., non[:, None], non[None, :]] = Cs
+        blk[..., lin[:, None], non[None, :]] = -W
+        blk[..., non[:, None], lin[None, :]] = -np.swapaxes(W, -1, -2)
+        blk[..., lin[:, None], lin[None, :]] = cc
+    if scale is not None:
+        out *= np.asarray(scale, dtype=dt)[..., None, None, None]
+    return out

@@ -807,6 +807,37 @@ hipError_t launch_varpro_expand(const VarproExpandCall& c, hipStream_t s);
 hipError_t launch_varpro_reduce(const VarproReduceCall& c, hipStream_t s);
 size_t varpro_lds_bytes(int na);      // dynamic LDS of one problem with na = n - nl non-linear columns
 
+// ---------------------------------------------- separable global fits (7x) ----
+// The same two stages for G groups of S data sets (blsq_varpro_expand_global_dev, blsq_varpro_reduce_global_dev): the
+// calls above with B = G, X [G][nv], P [G S][n], G [G S][m][n], y and f [G][S m], w_stride 0 or S m, J [G][S m][nv] in
+// the group's layout (+0.0 outside a data set's columns), c [G S][nl], info [G S], mask [G] ...
+struct VarproGlobalCall {
+  int S;
+  const int* shared;      // host [n]: 1 for a non-linear parameter the group shares, 0 elsewhere
+  double* Sinv;           // [G S][nl][nl] or nullptr: (Phi_w^T Phi_w)^-1
+  double* TD;             // [G S][nl][n - nl] or nullptr: c[owner] (T + T2)
+};
+// ... and the per-data-set blocks of the full covariance from the reduced one (blsq_varpro_cov_blocks_dev)
+struct VarproCovCall {
+  int G, S, n, nl;
+  const int* lin;         // host [nl]
+  const int* shared;      // host [n]
+  const double* C;        // [G][nv][nv]
+  const double* Sinv;     // [G S][nl][nl]
+  const double* TD;       // [G S][nl][n - nl]
+  const double* scale;    // [G] or nullptr (1)
+  const int* info;        // [G S] or nullptr
+  const int* status;      // [G] or nullptr
+  double* cov;            // [G S][n][n]
+};
+// hipErrorInvalidValue, and nothing launched, for what the two launches above refuse and for S < 1, a shared flag that
+// is not 0 / 1 or is set on a linear parameter, nv = nsh + S nloc above BLSQ_GLOBAL_MAX_NV, more than 2^31 - 1 data
+// sets, a w_stride other than 0 or S m, or a missing C, Sinv, TD or cov.
+hipError_t launch_varpro_expand_global(const VarproExpandCall& c, const VarproGlobalCall& q, hipStream_t s);
+hipError_t launch_varpro_reduce_global(const VarproReduceCall& c, const VarproGlobalCall& q, hipStream_t s);
+hipError_t launch_varpro_cov_blocks(const VarproCovCall& c, hipStream_t s);
+int varpro_global_nv(int S, int n, int nl, const int* lin, const int* shared);   // nv of the layout, -1: refused
+
 // ---------------------------------------------------------------- probes ----
 // probe_kernels.hip: measured peaks / counter calibration (blsq_debug_probe)
 hipError_t launch_mfma_probe(int waves_per_simd, int iters, double* sink, long* n_mfma,

@@ -1,5 +1,5 @@
 // Built-in fit models (include/blsq.h; kernel: model_kernels.hip): the model and term tables behind
-// blsq_model_count / _info and blsq_term_count / _info, the entries blsq_linear_eval_dev, blsq_expr_check, blsq_expr_eval_dev, blsq_bvls_moments_dev, blsq_bvls_solve_dev, blsq_bvls_solve_eq_dev, blsq_response_apply_dev, blsq_varpro_expand_dev and blsq_varpro_reduce_dev, and the eight entries blsq_model_eval_dev, _map_dev, _comp_dev,
+// blsq_model_count / _info and blsq_term_count / _info, the entries blsq_linear_eval_dev, blsq_expr_check, blsq_expr_eval_dev, blsq_bvls_moments_dev, blsq_bvls_solve_dev, blsq_bvls_solve_eq_dev, blsq_response_apply_dev, blsq_varpro_expand_dev, blsq_varpro_reduce_dev, blsq_varpro_expand_global_dev, blsq_varpro_reduce_global_dev and blsq_varpro_cov_blocks_dev, and the eight entries blsq_model_eval_dev, _map_dev, _comp_dev,
 // _est_dev, _bin_dev, _nan_dev, _global_dev and _tie_dev.  An entry fills a ModelEvalCall from its arguments (what its signature
 // does not have is the default) and hands it to model_eval_checked with its EvalEntry: one list of checks, one launcher, and per entry
 // only the argument numbers.
@@ -520,4 +520,100 @@ extern "C" int blsq_varpro_reduce_dev(blsq_ctx* ctx, int B, int m, int n, int nl
   HIPCHK(ctx, hipSetDevice(ctx->device));
   const VarproReduceCall c{B, m, n, nl, lin, owner, dG, dy, dw, w_stride, df, dJ, dc, dinfo, dmask};
   return ctx->run(K_MODEL_EVAL, "launch_varpro_reduce", [&] { return launch_varpro_reduce(c, ctx->stream); });
+}
+
+// Separable global fits (varpro_kernels.hip): the two stages above for G groups of S data sets that share
+// some non-linear parameters, and the per-data-set blocks of the full covariance from the reduced one.  shared is a host
+// array [n] of 0 / 1 flags over the model parameters, like lin and owner read during the call.
+namespace {
+
+// 0, or the position (S_at or shared_at) of what is wrong with the layout of a group
+int varpro_global_bad(blsq_ctx* ctx, int S_at, int shared_at, int S, int n, int nl, const int32_t* lin,
+                      const int32_t* shared) {
+  if (S < 1) return ctx->bad(S_at, "S must be positive");
+  if (!shared) return ctx->bad(shared_at, "shared is NULL");
+  for (int j = 0, at = 0; j < n; ++j) {
+    const bool linear = at < nl && lin[at] == j;
+    if (linear) ++at;
+    if (shared[j] != 0 && shared[j] != 1) return ctx->bad(shared_at, "shared must hold 0 or 1");
+    if (linear && shared[j]) return ctx->bad(shared_at, "shared is set on a linear parameter");
+  }
+  if (varpro_global_nv(S, n, nl, lin, shared) < 0)
+    return ctx->bad(S_at, "nv = nsh + S nloc exceeds BLSQ_GLOBAL_MAX_NV");
+  return 0;
+}
+
+}  // namespace
+
+extern "C" int blsq_varpro_expand_global_dev(blsq_ctx* ctx, int G, int S, int n, int nl, const int32_t* lin,
+                                             const int32_t* shared, const double* dX, double* dP) {
+  if (!ctx) return -1;
+  if (G <= 0) return ctx->bad(2, "G must be positive");
+  if (S > 0 && (long)G * S > 0x7fffffffL) return ctx->bad(3, "G S must fit an int");
+  if (n < 2 || n > BLSQ_MODEL_MAX_N) return ctx->bad(4, "n must be in 2 .. BLSQ_MODEL_MAX_N");
+  if (nl < 1 || nl > BLSQ_VARPRO_MAX_NL || nl >= n)
+    return ctx->bad(5, "nl must be in 1 .. BLSQ_VARPRO_MAX_NL and leave a non-linear parameter (nl < n)");
+  if (varpro_lin_bad(n, nl, lin)) return ctx->bad(6, "lin is NULL or not ascending within 0 .. n - 1");
+  if (int rc = varpro_global_bad(ctx, 3, 7, S, n, nl, lin, shared)) return rc;
+  if (!dX) return ctx->bad(8, "X is NULL (the solver variables)");
+  if (!dP) return ctx->bad(9, "P is NULL");
+  HIPCHK(ctx, hipSetDevice(ctx->device));
+  const VarproExpandCall c{G, n, nl, lin, dX, dP};
+  const VarproGlobalCall q{S, shared, nullptr, nullptr};
+  return ctx->run(K_MODEL_EVAL, "launch_varpro_expand_global",
+                  [&] { return launch_varpro_expand_global(c, q, ctx->stream); });
+}
+
+extern "C" int blsq_varpro_reduce_global_dev(blsq_ctx* ctx, int G, int S, int m, int n, int nl, const int32_t* lin,
+                                             const int32_t* owner, const int32_t* shared, const double* dG,
+                                             const double* dy, const double* dw, long w_stride, double* df, double* dJ,
+                                             double* dc, int32_t* dinfo, double* dSinv, double* dTD,
+                                             const int32_t* dmask) {
+  if (!ctx) return -1;
+  if (G <= 0) return ctx->bad(2, "G must be positive");
+  if (S > 0 && (long)G * S > 0x7fffffffL) return ctx->bad(3, "G S must fit an int");
+  if (m <= 0) return ctx->bad(4, "m must be positive");
+  if (n < 2 || n > BLSQ_MODEL_MAX_N) return ctx->bad(5, "n must be in 2 .. BLSQ_MODEL_MAX_N");
+  if (nl < 1 || nl > BLSQ_VARPRO_MAX_NL || nl >= n)
+    return ctx->bad(6, "nl must be in 1 .. BLSQ_VARPRO_MAX_NL and leave a non-linear parameter (nl < n)");
+  if (m <= nl) return ctx->bad(4, "m must exceed nl: the linear parameters must leave a residual");
+  if (varpro_lin_bad(n, nl, lin)) return ctx->bad(7, "lin is NULL or not ascending within 0 .. n - 1");
+  if (!owner) return ctx->bad(8, "owner is NULL");
+  for (int j = 0, at = 0; j < n; ++j) {
+    const bool linear = at < nl && lin[at] == j;
+    if (linear) ++at;
+    if (linear ? owner[j] != -1 : (owner[j] < 0 || owner[j] >= nl))
+      return ctx->bad(8, "owner must be -1 on lin and a position 0 .. nl - 1 in lin elsewhere");
+  }
+  if (int rc = varpro_global_bad(ctx, 3, 9, S, n, nl, lin, shared)) return rc;
+  if (!dG) return ctx->bad(10, "G is NULL (the raw Jacobian)");
+  if (!dy) return ctx->bad(11, "y is NULL");
+  if (dw && w_stride != 0 && w_stride != (long)S * m) return ctx->bad(13, "w_stride must be 0 or S m");
+  if (!df && !dJ && !dc && !dSinv && !dTD) return ctx->bad(14, "f, J, c, Sinv and TD are all NULL");
+  HIPCHK(ctx, hipSetDevice(ctx->device));
+  const VarproReduceCall c{G, m, n, nl, lin, owner, dG, dy, dw, w_stride, df, dJ, dc, dinfo, dmask};
+  const VarproGlobalCall q{S, shared, dSinv, dTD};
+  return ctx->run(K_MODEL_EVAL, "launch_varpro_reduce_global",
+                  [&] { return launch_varpro_reduce_global(c, q, ctx->stream); });
+}
+
+extern "C" int blsq_varpro_cov_blocks_dev(blsq_ctx* ctx, int G, int S, int n, int nl, const int32_t* lin,
+                                          const int32_t* shared, const double* dC, const double* dSinv,
+                                          const double* dTD, const double* dscale, const int32_t* dinfo,
+                                          const int32_t* dstatus, double* dcov) {
+  if (!ctx) return -1;
+  if (G <= 0) return ctx->bad(2, "G must be positive");
+  if (S > 0 && (long)G * S > 0x7fffffffL) return ctx->bad(3, "G S must fit an int");
+  if (n < 2 || n > BLSQ_MODEL_MAX_N) return ctx->bad(4, "n must be in 2 .. BLSQ_MODEL_MAX_N");
+  if (nl < 1 || nl > BLSQ_VARPRO_MAX_NL || nl >= n)
+    return ctx->bad(5, "nl must be in 1 .. BLSQ_VARPRO_MAX_NL and leave a non-linear parameter (nl < n)");
+  if (varpro_lin_bad(n, nl, lin)) return ctx->bad(6, "lin is NULL or not ascending within 0 .. n - 1");
+  if (int rc = varpro_global_bad(ctx, 3, 7, S, n, nl, lin, shared)) return rc;
+  if (!dC) return ctx->bad(8, "C is NULL (the covariance of the reduced group)");
+  if (!dSinv) return ctx->bad(9, "Sinv is NULL");
+  if (!dTD) return ctx->bad(10, "TD is NULL");
+  if (!dcov) return ctx->bad(14, "cov is NULL");
+  HIPCHK(ctx, hipSetDevice(ctx->device));
+  const VarproCovCall c{G, S, n, nl, lin, shared, dC, dSinv, dTD, dscale, dinfo, dstatus, dcov};
+  return ctx->run(K_MODEL_EVAL, "launch_varpro_cov_blocks", [&] { return launch_varpro_cov_blocks(c, ctx->stream); });
 }

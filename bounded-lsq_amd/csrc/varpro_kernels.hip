@@ -45,6 +45,7 @@ static constexpr int VP_PAD = 255, VP_YCOL = 254;
 static constexpr double VP_PIVOT_TOL = 64.0 * DBL_EPS;   // VARPRO_PIVOT_TOL of bounded_lsq/_varpro.py
 
 struct VarproArgs {
+  static constexpr bool global = false;
   int m, n, nl, na, nt;         // nt: tiles of the work layout
   const double* G;
   const double* y;
@@ -53,6 +54,25 @@ struct VarproArgs {
   const int* mask;
   unsigned char col[16 * VP_MAX_TILES];   // work column -> column of G, VP_YCOL (w y) or VP_PAD (zeros)
   signed char own[BLSQ_MODEL_MAX_N];      // non-linear column i -> position in lin of the amplitude it scales with
+};
+
+// What a separable global fit adds: workgroup b = g S + s is data set s of group g.  The nv = nsh + S nloc
+// solver variables of a group are the shared non-linear parameters, then the window of nloc local ones of data set 0,
+// 1, ... (GlobalMap of bounded_lsq/_params.py over the non-linear parameters).
+struct VarproGlobalArgs {
+  int S, nv, nsh, nloc;
+  double* Sinv;                           // [G S][nl][nl] or nullptr
+  double* TD;                             // [G S][nl][na] or nullptr
+  unsigned char vcol[BLSQ_MODEL_MAX_N];   // non-linear column i -> its variable in data set 0
+  unsigned char vloc[BLSQ_MODEL_MAX_N];   // 1: local (data set s: vcol + s nloc), 0: shared
+
+  __device__ __forceinline__ int column(int i, int s) const { return vcol[i] + (vloc[i] ? s * nloc : 0); }
+  __device__ __forceinline__ bool owns(int v, int s) const { return v < nsh || (v - nsh) / nloc == s; }
+};
+
+struct VarproReduceGlobalArgs : VarproArgs {
+  static constexpr bool global = true;
+  VarproGlobalArgs q;
 };
 
 struct VarproExpandArgs {
@@ -69,6 +89,40 @@ __global__ __launch_bounds__(256) void varpro_expand_kernel(VarproExpandArgs A, 
   const int j = (int)(e - b * A.n);
   const int s = A.src[j];
   A.P[e] = s < 0 ? 1.0 : A.X[b * A.na + s];
+}
+
+__global__ __launch_bounds__(256) void varpro_expand_global_kernel(VarproExpandArgs A, VarproGlobalArgs Q, long total) {
+  const long e = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (e >= total) return;
+  const long b = e / A.n;
+  const int j = (int)(e - b * A.n);
+  const int i = A.src[j];
+  const long g = b / Q.S;
+  A.P[e] = i < 0 ? 1.0 : A.X[g * Q.nv + Q.column(i, (int)(b - g * Q.S))];
+}
+
+// double-double arithmetic for the one extra correction of TD (7x): error-free sum and product, FMA for the latter
+// (no contraction of their own sums and products: the error terms are exact only for the operations as written)
+struct dd { double hi, lo; };
+__device__ __forceinline__ dd dd_add(dd x, dd y) {
+#pragma clang fp contract(off)
+  const double s = x.hi + y.hi, bb = s - x.hi;
+  const double e = ((x.hi - (s - bb)) + (y.hi - bb)) + (x.lo + y.lo);
+  const double hi = s + e;
+  return {hi, e - (hi - s)};
+}
+__device__ __forceinline__ dd dd_mul(dd x, double d) {
+#pragma clang fp contract(off)
+  const double p = x.hi * d;
+  const double e = fma(x.lo, d, fma(x.hi, d, -p));
+  const double hi = p + e;
+  return {hi, e - (hi - p)};
+}
+// x - a b
+__device__ __forceinline__ dd dd_sub_prod(dd x, double a, double b) {
+#pragma clang fp contract(off)
+  const double p = -a * b;
+  return dd_add(x, dd{p, fma(-a, b, -p)});
 }
 
 // rows [i0, i0 + 64) of the problem in the work layout (rows past m: zeros).  Holds two barriers.
@@ -138,10 +192,22 @@ __device__ __forceinline__ v4d varpro_project(const double* tile, int ld, int r0
   return E;
 }
 
-__global__ __launch_bounds__(VP_NT) void varpro_reduce_kernel(VarproArgs A) {
+// Args = VarproReduceGlobalArgs (GLOBAL; blsq_varpro_reduce_global_dev, 7x): problem b is data set s = b % S of group g = b / S.  G, y, w, f, c and
+// info are indexed by b as they are without it (y and f [G][S m] are [G S][m]); the mask is per group; J goes into the
+// group's layout [g][s m + i][nv], Kaufman's columns at q.column(k, s) and +0.0 in every column of those rows that is
+// not one of data set s, so that the workgroups of a group together write every element of its J exactly once; and
+// Sinv = D Ri Ri^T D and TD = c[own] (T + T2) leave the LDS they are in after pass 2, TD after one more correction of
+// T in double-double arithmetic (below).
+template <class Args>
+__global__ __launch_bounds__(VP_NT) void varpro_reduce_kernel(Args A) {
+  constexpr bool GLOBAL = Args::global;
   extern __shared__ double vp_lds[];
   const long b = blockIdx.x;
-  if (A.mask && A.mask[b] == 0) return;           // a masked problem: nothing of it is read or written
+  if constexpr (GLOBAL) {
+    if (A.mask && A.mask[b / A.q.S] == 0) return; // a masked group: nothing of it is read or written
+  } else {
+    if (A.mask && A.mask[b] == 0) return;         // a masked problem: nothing of it is read or written
+  }
   const int m = A.m, n = A.n, nl = A.nl, na = A.na, nt = A.nt;
   const int nc = TILE * nt, ld = nc + 1;
   double* tile = vp_lds;                          // 64 x ld
@@ -161,6 +227,16 @@ __global__ __launch_bounds__(VP_NT) void varpro_reduce_kernel(VarproArgs A) {
   const int r0 = TILE * wv;
   const v4d zero = {0.0, 0.0, 0.0, 0.0};
   v4d acc[VP_MAX_TILES];
+  int ds = 0;                                     // GLOBAL: the data set within its group
+  if constexpr (GLOBAL) {
+    ds = (int)(b % A.q.S);
+    if (A.J) {                                    // the columns of the other data sets, in this one's rows
+      const int nv = A.q.nv;
+      double* Jb = A.J + b * (long)m * nv;
+      for (long e = tid; e < (long)m * nv; e += VP_NT)
+        if (!A.q.owns((int)(e % nv), ds)) Jb[e] = 0.0;
+    }
+  }
 
   // ---- pass 1: Phi_w^T [Phi_w | A_w] ----
 #pragma unroll
@@ -197,7 +273,15 @@ __global__ __launch_bounds__(VP_NT) void varpro_reduce_kernel(VarproArgs A) {
   if (flag[0] != 0.0 || flag[1] != 0.0) {         // rank deficient: NaN everywhere (uniform per workgroup)
     const double nan = __builtin_nan("");
     if (A.f) for (int i = tid; i < m; i += VP_NT) A.f[b * (long)m + i] = nan;
-    if (A.J) for (long e = tid; e < (long)m * na; e += VP_NT) A.J[b * (long)m * na + e] = nan;
+    if constexpr (GLOBAL) {
+      if (A.J)
+        for (long e = tid; e < (long)m * na; e += VP_NT)
+          A.J[(b * (long)m + e / na) * A.q.nv + A.q.column((int)(e % na), ds)] = nan;
+      if (A.q.Sinv) for (int e = tid; e < nl * nl; e += VP_NT) A.q.Sinv[b * (long)nl * nl + e] = nan;
+      if (A.q.TD) for (int e = tid; e < nl * na; e += VP_NT) A.q.TD[b * (long)nl * na + e] = nan;
+    } else {
+      if (A.J) for (long e = tid; e < (long)m * na; e += VP_NT) A.J[b * (long)m * na + e] = nan;
+    }
     if (A.c && tid < nl) A.c[b * (long)nl + tid] = nan;
     if (A.info && tid == 0) A.info[b] = 1;
     return;
@@ -227,6 +311,48 @@ __global__ __launch_bounds__(VP_NT) void varpro_reduce_kernel(VarproArgs A) {
   __syncthreads();
   if (A.c && tid < nl) A.c[b * (long)nl + tid] = cs[tid];
   if (A.info && tid == 0) A.info[b] = 0;
+  if constexpr (GLOBAL) {
+    if (A.q.Sinv)                                  // (Ri Ri^T)[p][q] = sum over k >= max(p, q), ascending; mirrored
+      for (int e = tid; e < nl * nl; e += VP_NT) {
+        const int p = e / nl, q = e - p * nl, lo = p < q ? p : q, hi = p < q ? q : p;
+        double v = 0.0;
+        for (int k = hi; k < nl; ++k) v = fma(Ri[lo * TILE + k], Ri[hi * TILE + k], v);
+        A.q.Sinv[b * (long)nl * nl + e] = dsc[lo] * dsc[hi] * v;
+      }
+    if (A.q.TD) {
+      // TD = c[own] T needs T beyond the kappa eps |T| of the scheme: a column of T is the least-squares solution for
+      // a column of G, whose residual is as large as the column, and |T| reaches |G_i| / sigma_min(Phi_w).  One more
+      // correction, T3 = (T + T2) + S^-1 Phi_w^T (A_w - Phi_w (T + T2)), with the residual and its moments in
+      // double-double arithmetic on the unrounded w G (read from global memory, not from the staged block): the
+      // solve through the factor contracts the error by kappa^2 eps per step, so one step leaves the rounding of the
+      // sum.  Column na (w y) gives the c that multiplies; the outputs c, f and J are not touched.
+      for (int e = tid; e < TILE * nc; e += VP_NT) Mo[e] = 0.0;
+      __syncthreads();
+      const int wide = na + 1;
+      for (int e = tid; e < nl * wide; e += VP_NT) {
+        const int p = e / wide, k = e - p * wide;
+        const int src = A.col[TILE + k], cp = A.col[p];
+        dd acc = {0.0, 0.0};
+        for (int i = 0; i < m; ++i) {
+          const double* row = Gb + (long)i * n;
+          dd r = {src == VP_YCOL ? yb[i] : row[src], 0.0};
+          for (int q = 0; q < nl; ++q)
+            r = dd_sub_prod(r, row[A.col[q]], T[q * nc + TILE + k] + T2[q * nc + TILE + k]);
+          if (wb) r = dd_mul(dd_mul(r, wb[i]), wb[i]);
+          acc = dd_add(acc, dd_mul(r, row[cp]));
+        }
+        Mo[p * nc + TILE + k] = acc.hi + acc.lo;
+      }
+      __syncthreads();
+      varpro_solve(Mo, Z, Mo, Ri, dsc, 1, nc);      // (in place: the second half reads Z alone)
+      for (int e = tid; e < nl * na; e += VP_NT) {
+        const int p = e / na, i = e - p * na, o = A.own[i];
+        const double c3 = (T[o * nc + TILE + na] + T2[o * nc + TILE + na]) + Mo[o * nc + TILE + na];
+        A.q.TD[b * (long)nl * na + e] = c3 * ((T[p * nc + TILE + i] + T2[p * nc + TILE + i]) + Mo[p * nc + TILE + i]);
+      }
+      __syncthreads();
+    }
+  }
   if (!A.f && !A.J) return;
 
   // ---- pass 3: E - Phi_w T2 and the outputs ----
@@ -245,10 +371,82 @@ __global__ __launch_bounds__(VP_NT) void varpro_reduce_kernel(VarproArgs A) {
 #pragma unroll
       for (int g = 0; g < 4; ++g) {
         const long i = (long)i0 + r0 + lr + 4 * g;
-        if (i < m && k < na && A.J) A.J[(b * (long)m + i) * na + k] = scale * E[g];
+        if constexpr (GLOBAL) {
+          if (i < m && k < na && A.J) A.J[(b * (long)m + i) * A.q.nv + A.q.column(k, ds)] = scale * E[g];
+        } else {
+          if (i < m && k < na && A.J) A.J[(b * (long)m + i) * na + k] = scale * E[g];
+        }
         if (i < m && k == na && A.f) A.f[b * (long)m + i] = -E[g];
       }
     }
+  }
+}
+
+// The per-data-set blocks of the covariance of a separable global fit (blsq_varpro_cov_blocks_dev, 7x): one workgroup
+// per data set b = g S + s.  C_s, the rows and columns of the group's reduced covariance C [nv][nv] that belong to data
+// set s (read from the upper triangle, so C_s is symmetric), TD_s, W = TD_s C_s and Sinv_s stay in LDS:
+//   alpha-alpha = C_s    c-alpha = -W    c-c = Sinv_s + W TD_s^T
+// every sum in ascending order; element (j, k) and (k, j) are computed from the same operands in the same order, so the
+// block is exactly symmetric.  NaN for a data set with info = 1 or a group with status != 0.
+struct VarproCovArgs {
+  int n, nl, na;
+  const double* C; const double* Sinv; const double* TD; const double* scale;
+  const int* info; const int* status;
+  double* cov;
+  signed char src[BLSQ_MODEL_MAX_N];      // parameter j -> its position in non, or -1
+  signed char pos[BLSQ_MODEL_MAX_N];      // parameter j -> its position in lin, or -1
+};
+
+__global__ __launch_bounds__(256) void varpro_cov_blocks_kernel(VarproCovArgs A, VarproGlobalArgs Q) {
+  extern __shared__ double vc_lds[];
+  const long b = blockIdx.x;
+  const long g = b / Q.S;
+  const int s = (int)(b - g * Q.S);
+  const int n = A.n, nl = A.nl, na = A.na, nv = Q.nv, tid = threadIdx.x;
+  double* out = A.cov + b * (long)n * n;
+  if ((A.info && A.info[b] != 0) || (A.status && A.status[g] != 0)) {
+    const double nan = __builtin_nan("");
+    for (int e = tid; e < n * n; e += 256) out[e] = nan;
+    return;
+  }
+  double* Cs = vc_lds;                            // na x na
+  double* Td = Cs + na * na;                      // nl x na
+  double* W = Td + nl * na;                       // nl x na
+  double* Si = W + nl * na;                       // nl x nl
+  const double* Cg = A.C + g * (long)nv * nv;
+  for (int e = tid; e < na * na; e += 256) {
+    const int a = e / na, c = e - a * na;
+    const int va = Q.column(a, s), vb = Q.column(c, s);
+    Cs[e] = Cg[(long)(va < vb ? va : vb) * nv + (va < vb ? vb : va)];
+  }
+  for (int e = tid; e < nl * na; e += 256) Td[e] = A.TD[b * (long)nl * na + e];
+  for (int e = tid; e < nl * nl; e += 256) {
+    const int p = e / nl, q = e - p * nl;
+    Si[e] = A.Sinv[b * (long)nl * nl + (p < q ? p * nl + q : q * nl + p)];
+  }
+  __syncthreads();
+  for (int e = tid; e < nl * na; e += 256) {
+    const int p = e / na, a = e - p * na;
+    double v = 0.0;
+    for (int i = 0; i < na; ++i) v = fma(Td[p * na + i], Cs[i * na + a], v);
+    W[e] = v;
+  }
+  __syncthreads();
+  const double sc = A.scale ? A.scale[g] : 1.0;
+  for (int e = tid; e < n * n; e += 256) {
+    const int j = e / n, k = e - j * n, lo = j < k ? j : k, hi = j < k ? k : j;
+    const int a = A.src[lo], c = A.src[hi], p = A.pos[lo], q = A.pos[hi];
+    double v;
+    if (a >= 0 && c >= 0) {
+      v = Cs[a * na + c];
+    } else if (p >= 0 && q >= 0) {
+      double t = 0.0;
+      for (int i = 0; i < na; ++i) t = fma(W[p * na + i], Td[q * na + i], t);
+      v = Si[p * nl + q] + t;
+    } else {
+      v = -(p >= 0 ? W[p * na + c] : W[q * na + a]);
+    }
+    out[e] = sc * v;
   }
 }
 
@@ -276,13 +474,12 @@ hipError_t launch_varpro_expand(const VarproExpandCall& c, hipStream_t s) {
   return hipGetLastError();
 }
 
-hipError_t launch_varpro_reduce(const VarproReduceCall& c, hipStream_t s) {
-  if (c.B < 1 || c.n < 2 || c.n > BLSQ_MODEL_MAX_N || c.nl < 1 || c.nl > BLSQ_VARPRO_MAX_NL || c.nl >= c.n ||
+// the arguments of the reduce kernel from a call (B problems): false for what launch_varpro_reduce refuses
+static bool varpro_reduce_args(const VarproReduceCall& c, long B, VarproArgs& A) {
+  if (B < 1 || c.n < 2 || c.n > BLSQ_MODEL_MAX_N || c.nl < 1 || c.nl > BLSQ_VARPRO_MAX_NL || c.nl >= c.n ||
       c.m <= c.nl)
-    return hipErrorInvalidValue;
-  if (!c.lin || !c.owner || !c.G || !c.y || (!c.f && !c.J && !c.c)) return hipErrorInvalidValue;
-  if (c.w && c.w_stride != 0 && c.w_stride != (long)c.m) return hipErrorInvalidValue;
-  VarproArgs A;
+    return false;
+  if (!c.lin || !c.owner || !c.G || !c.y) return false;
   A.m = c.m; A.n = c.n; A.nl = c.nl; A.na = c.n - c.nl;
   A.nt = 1 + (A.na + 1 + TILE - 1) / TILE;
   A.G = c.G; A.y = c.y; A.w = c.w; A.w_stride = c.w ? c.w_stride : 0;
@@ -292,17 +489,104 @@ hipError_t launch_varpro_reduce(const VarproReduceCall& c, hipStream_t s) {
   int at = 0, v = 0;
   for (int j = 0; j < c.n; ++j) {
     if (at < c.nl && c.lin[at] == j) {
-      if (c.owner[j] != -1) return hipErrorInvalidValue;
+      if (c.owner[j] != -1) return false;
       A.col[at++] = (unsigned char)j;
     } else {
-      if (c.owner[j] < 0 || c.owner[j] >= c.nl) return hipErrorInvalidValue;
+      if (c.owner[j] < 0 || c.owner[j] >= c.nl) return false;
       A.own[v] = (signed char)c.owner[j];
       A.col[TILE + v++] = (unsigned char)j;
     }
   }
-  if (at != c.nl) return hipErrorInvalidValue;    // lin not ascending within 0 .. n - 1
+  if (at != c.nl) return false;                   // lin not ascending within 0 .. n - 1
   A.col[TILE + A.na] = VP_YCOL;
-  return launch<varpro_reduce_kernel>(dim3((unsigned)c.B), dim3(VP_NT), varpro_lds_bytes(A.na), s, A);
+  return true;
+}
+
+hipError_t launch_varpro_reduce(const VarproReduceCall& c, hipStream_t s) {
+  if (!c.f && !c.J && !c.c) return hipErrorInvalidValue;
+  if (c.w && c.w_stride != 0 && c.w_stride != (long)c.m) return hipErrorInvalidValue;
+  VarproArgs A;
+  if (!varpro_reduce_args(c, c.B, A)) return hipErrorInvalidValue;
+  return launch<varpro_reduce_kernel<VarproArgs>>(dim3((unsigned)c.B), dim3(VP_NT), varpro_lds_bytes(A.na), s, A);
+}
+
+// the layout of a group from lin and the 0 / 1 flags shared [n] of the model parameters: false for a flag that is
+// neither, a flag set on a linear parameter, or nv above BLSQ_GLOBAL_MAX_NV.  src: parameter -> position in non or -1.
+static bool varpro_global_layout(int S, int n, int nl, const int* lin, const int* shared, VarproGlobalArgs& Q,
+                                 signed char* src, signed char* pos) {
+  if (S < 1 || !lin || !shared) return false;
+  Q.S = S; Q.nsh = 0; Q.nloc = 0; Q.Sinv = nullptr; Q.TD = nullptr;
+  for (int i = 0; i < BLSQ_MODEL_MAX_N; ++i) { Q.vcol[i] = 0; Q.vloc[i] = 0; src[i] = -1; if (pos) pos[i] = -1; }
+  int at = 0, v = 0;
+  for (int j = 0; j < n; ++j) {
+    if (shared[j] != 0 && shared[j] != 1) return false;
+    if (at < nl && lin[at] == j) {
+      if (shared[j]) return false;
+      if (pos) pos[j] = (signed char)at;
+      ++at;
+      continue;
+    }
+    Q.vloc[v] = shared[j] ? 0 : 1;
+    Q.vcol[v] = (unsigned char)(shared[j] ? Q.nsh++ : Q.nloc++);
+    src[j] = (signed char)v++;
+  }
+  if (at != nl) return false;
+  for (int i = 0; i < v; ++i)
+    if (Q.vloc[i]) Q.vcol[i] = (unsigned char)(Q.vcol[i] + Q.nsh);
+  const long nv = (long)Q.nsh + (long)S * Q.nloc;
+  if (nv > BLSQ_GLOBAL_MAX_NV) return false;
+  Q.nv = (int)nv;
+  if (Q.nloc == 0) Q.nloc = 1;                    // (the divisor of owns(); nothing is local then)
+  return true;
+}
+
+int varpro_global_nv(int S, int n, int nl, const int* lin, const int* shared) {
+  VarproGlobalArgs Q;
+  signed char src[BLSQ_MODEL_MAX_N];
+  if (n < 2 || n > BLSQ_MODEL_MAX_N || nl < 1 || nl >= n) return -1;
+  return varpro_global_layout(S, n, nl, lin, shared, Q, src, nullptr) ? Q.nv : -1;
+}
+
+hipError_t launch_varpro_expand_global(const VarproExpandCall& c, const VarproGlobalCall& q, hipStream_t s) {
+  if (c.B < 1 || c.n < 2 || c.n > BLSQ_MODEL_MAX_N || c.nl < 1 || c.nl >= c.n || !c.lin || !c.X || !c.P)
+    return hipErrorInvalidValue;
+  VarproExpandArgs A;
+  VarproGlobalArgs Q;
+  if (!varpro_global_layout(q.S, c.n, c.nl, c.lin, q.shared, Q, A.src, nullptr)) return hipErrorInvalidValue;
+  A.n = c.n; A.na = c.n - c.nl; A.X = c.X; A.P = c.P;
+  const long total = (long)c.B * q.S * c.n;       // c.B: the groups
+  const long blocks = (total + 255) / 256;
+  if ((long)c.B * q.S > 0x7fffffffL || blocks > 0x7fffffffL) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(varpro_expand_global_kernel, dim3((unsigned)blocks), dim3(256), 0, s, A, Q, total);
+  return hipGetLastError();
+}
+
+hipError_t launch_varpro_reduce_global(const VarproReduceCall& c, const VarproGlobalCall& q, hipStream_t s) {
+  // c.B: the groups; c.w_stride: 0 or S m, the stride of a group, which is m per data set
+  if (c.B < 1 || q.S < 1 || (long)c.B * q.S > 0x7fffffffL) return hipErrorInvalidValue;
+  if (!c.f && !c.J && !c.c && !q.Sinv && !q.TD) return hipErrorInvalidValue;
+  if (c.w && c.w_stride != 0 && c.w_stride != (long)q.S * c.m) return hipErrorInvalidValue;
+  VarproReduceGlobalArgs A;
+  signed char src[BLSQ_MODEL_MAX_N];
+  if (!varpro_reduce_args(c, (long)c.B * q.S, A)) return hipErrorInvalidValue;
+  if (!varpro_global_layout(q.S, c.n, c.nl, c.lin, q.shared, A.q, src, nullptr)) return hipErrorInvalidValue;
+  A.w_stride = (c.w && c.w_stride != 0) ? (long)c.m : 0;
+  A.q.Sinv = q.Sinv; A.q.TD = q.TD;
+  return launch<varpro_reduce_kernel<VarproReduceGlobalArgs>>(dim3((unsigned)((long)c.B * q.S)), dim3(VP_NT),
+                                                              varpro_lds_bytes(A.na), s, A);
+}
+
+hipError_t launch_varpro_cov_blocks(const VarproCovCall& c, hipStream_t s) {
+  if (c.G < 1 || c.S < 1 || (long)c.G * c.S > 0x7fffffffL || c.n < 2 || c.n > BLSQ_MODEL_MAX_N || c.nl < 1 ||
+      c.nl > BLSQ_VARPRO_MAX_NL || c.nl >= c.n || !c.lin || !c.shared || !c.C || !c.Sinv || !c.TD || !c.cov)
+    return hipErrorInvalidValue;
+  VarproCovArgs A;
+  VarproGlobalArgs Q;
+  if (!varpro_global_layout(c.S, c.n, c.nl, c.lin, c.shared, Q, A.src, A.pos)) return hipErrorInvalidValue;
+  A.n = c.n; A.nl = c.nl; A.na = c.n - c.nl;
+  A.C = c.C; A.Sinv = c.Sinv; A.TD = c.TD; A.scale = c.scale; A.info = c.info; A.status = c.status; A.cov = c.cov;
+  const size_t lds = sizeof(double) * ((size_t)A.na * A.na + 2 * (size_t)A.nl * A.na + (size_t)A.nl * A.nl);
+  return launch<varpro_cov_blocks_kernel>(dim3((unsigned)((long)c.G * c.S)), dim3(256), lds, s, A, Q);
 }
 
 }  // namespace blsq

@@ -792,6 +792,56 @@ int blsq_varpro_reduce_dev(blsq_ctx* ctx, int B, int m, int n, int nl, const int
                            const double* dG, const double* dy, const double* dw, long w_stride, double* df, double* dJ,
                            double* dc, int32_t* dinfo, const int32_t* dmask);
 
+/* ---- separable global fits: shared non-linear parameters, projected linear ones ---------------------
+ * G groups of S data sets of one model.  Some NON-LINEAR parameters are shared by the data sets of a group; the linear
+ * ones are projected out per data set as above.  shared: HOST int32 [n], 1 for a shared parameter and 0 elsewhere
+ * (a flag that is neither, or one set on a linear parameter, is an error).  With nsh shared and nloc local non-linear
+ * parameters the group has nv = nsh + S nloc <= BLSQ_GLOBAL_MAX_NV solver variables: the shared ones in ascending
+ * order, then the nloc local ones of data set 0, 1, ... (bounded_lsq.GlobalMap over the non-linear parameters;
+ * bounded_lsq/_varpro.py: separable_global_map, separable_global_residual / _jacobian / _cov ARE the definition).
+ * The full count nv + S nl has no limit.  Data set s of group g is problem b = g S + s.
+ *
+ * blsq_varpro_expand_global_dev: dX [G][nv] -> dP [G S][n]: 1.0 in the slots lin, the shared variables and the window
+ * of data set s in the others.  Bit-exact.
+ *
+ * blsq_varpro_reduce_global_dev: the arithmetic of blsq_varpro_reduce_dev, bit for bit, on the G S data sets of
+ * dG [G S][m][n] (the raw Jacobian at dP).  dy and df are [G][S m]; dw is NULL, [m] (w_stride 0) or [G][S m]
+ * (w_stride S m); dJ is [G][S m][nv], the group's layout: Kaufman's columns of data set s in its rows s m .. s m + m - 1
+ * at its variables, and the literal +0.0 in every other column of those rows, stored by the same workgroup: every
+ * element of a group's J is written exactly once per call and no memset is relied on.  dc [G S][nl], dinfo [G S].
+ * dSinv [G S][nl][nl] = (Phi_w^T Phi_w)^-1 (from the factor: D Ri Ri^T D, exactly symmetric) and dTD [G S][nl][na],
+ * TD[:, i] = c[owner[non[i]]] (T + T2)[:, i], are what the covariance below needs; TD is formed from T after one more
+ * correction whose residual is computed in double-double arithmetic (a column of T solves for a column of G with a
+ * residual as large as the column: kappa eps |T| would not do), at a cost that only a call asking for dTD pays.  Each output may be NULL (not all).
+ * dmask: int32 [G] or NULL: a group with dmask[g] == 0 is neither read nor written.  A rank-deficient data set gets
+ * dinfo = 1 and NaN in its rows of f, its own columns of those rows of J, its c, Sinv and TD; its other columns are
+ * still +0.0 and its group mates are unaffected.
+ *
+ * blsq_varpro_cov_blocks_dev: Kaufman's J_K^T J_K is the Schur complement of the full Gauss-Newton matrix onto the
+ * non-linear variables, so the covariance dC [G][nv][nv] of the reduced group is the exact alpha-alpha block of the full
+ * covariance.  With C_s its rows and columns of data set s (the upper triangle of dC is read), per data set:
+ *   alpha-alpha = C_s     c-alpha = -TD_s C_s     c-c = Sinv_s + TD_s C_s TD_s^T
+ * placed at the model's parameter indices in dcov [G S][n][n], exactly symmetric, times dscale[g] (NULL: 1); sums in
+ * ascending order.  NaN for a data set with dinfo[b] != 0 (NULL: none) or a group with dstatus[g] != 0 (NULL: none).
+ * Nothing of the full size nv + S nl is ever formed.
+ *
+ * One workgroup per data set; asynchronous on the ctx stream; each call is one unit of the `model_eval` slot.  A
+ * negative return is the index of the bad argument, nothing is launched then (expand_global: ctx = 1, G = 2, S = 3:
+ * below 1, G S above 2^31 - 1 or nv above BLSQ_GLOBAL_MAX_NV, n = 4, nl = 5, lin = 6, shared = 7, X = 8, P = 9;
+ * reduce_global: ctx = 1, G = 2, S = 3, m = 4: not positive or m <= nl, n = 5, nl = 6, lin = 7, owner = 8, shared = 9,
+ * G = 10, y = 11, w, w_stride = 13: neither 0 nor S m, f = 14: every output NULL, J, c, info, Sinv, TD, mask;
+ * cov_blocks: ctx = 1, G = 2, S = 3, n = 4, nl = 5, lin = 6, shared = 7, C = 8, Sinv = 9, TD = 10, scale, info, status,
+ * cov = 14). */
+int blsq_varpro_expand_global_dev(blsq_ctx* ctx, int G, int S, int n, int nl, const int32_t* lin, const int32_t* shared,
+                                  const double* dX, double* dP);
+int blsq_varpro_reduce_global_dev(blsq_ctx* ctx, int G, int S, int m, int n, int nl, const int32_t* lin,
+                                  const int32_t* owner, const int32_t* shared, const double* dG, const double* dy,
+                                  const double* dw, long w_stride, double* df, double* dJ, double* dc, int32_t* dinfo,
+                                  double* dSinv, double* dTD, const int32_t* dmask);
+int blsq_varpro_cov_blocks_dev(blsq_ctx* ctx, int G, int S, int n, int nl, const int32_t* lin, const int32_t* shared,
+                               const double* dC, const double* dSinv, const double* dTD, const double* dscale,
+                               const int32_t* dinfo, const int32_t* dstatus, double* dcov);
+
 /* ---- parameter covariance from the final Jacobian --------------------------------------------------------------
  * The reference documents `x_covariance` as the inverse of J^T J at the solution (least_squares.py:248-252) and fills
  * it only through its MINPACK bridge (method='lm').  Here, per problem, from a Householder triangle R of J (the TSQR

@@ -65,14 +65,17 @@ device with NaN in the linear entries of p0 (expand, the model kernel, blsq_varp
 the covariance of the full problem); `plain`, the same fit without the keyword from the same non-linear start, its linear
 entries 10 % off the truth.  Reported: the median time of a call, the mean and the largest nfev of each route, and the
 problems that converged.  With ``--kernel``: the time per evaluation in the 'model_eval' slot (HIP events) of the three
-launches of the separable stage against the plain model kernel, f and J apart.  It takes --B, --m, --peaks, --repeat,
+launches of the separable stage against the plain model kernel, f and J apart.  With ``--global S --shared i,j`` as
+well: ``curve_fit_global(separable=True)`` against the plain global fit, whole fit and `model_eval`
+slot — alone where the plain route cannot take the group (nv > 256, e.g. ``--global 300``) — and, with ``--kernel``,
+the launches of the separable global stage against the global entry with the bytes of J each writes.  It takes --B, --m, --peaks, --repeat,
 --kernel, --launches and --rounds only.
 
 usage: python tools/bench_models.py [--B 4096] [--m 64] [--repeat 5] [--peaks 1] [--fixed 1,4] [--tied 5:2,4:1:1:0.42] [--kernel]
                                     [--launches 50] [--rounds 1] [--estimator lse] [--binned] [--omit FRACTION]
                                     [--global S --shared 1,2] [--response L [--n 4]]
                                     [--expr TEXT --params a,b,c [--truth 3,0.4,0.5,2.5,0.2] [--kernel]]
-                                    [--separable [--kernel]]
+                                    [--separable [--kernel] [--global S --shared 1,2]]
 """
 import argparse
 import json
@@ -496,6 +499,87 @@ def separable_bench(a, ctx):
     return res
 
 
+def separable_global_bench(a, ctx):
+    """--global S --shared i,j --separable: ``curve_fit_global(separable=True)`` against the plain global
+    fit — alone where the plain route cannot take the group (nv = ns + S nl > 256) — or (--kernel) the launches of the
+    separable global stage against the global entry, f and J apart, with the bytes of J each writes."""
+    S, m = a.global_S, a.m
+    G = max(1, a.B // S)
+    shared = [int(v) for v in a.shared.split(",") if v]
+    x, Y, P0, _ = problems(G * S, m, peaks=a.peaks, common=(S, shared))
+    n = P0.shape[1]
+    Y, P0 = Y.reshape(G, S, m), P0.reshape(G, S, n)
+    gm_full = GlobalMap(n, S, shared)
+    gm, lin, owner, non = models.separable_global_map("gauss_sum", n, S, shared)
+    plain_fits = gm_full.nv <= 256
+    res = {"model": "gauss_sum", "separable": True, "G": G, "S": S, "m": m, "n": n, "shared": shared, "M": S * m,
+           "nv": gm.nv, "nv_plain": gm_full.nv, "J_bytes": 8 * G * S * m * gm.nv,
+           "J_bytes_plain": 8 * G * S * m * gm_full.nv}
+    if a.kernel:
+        res.update(launches=a.launches, rounds=a.rounds)
+        for key, sep in (("plain", False), ("separable", True)):
+            if not sep and not plain_fits:
+                continue
+            mp = gm if sep else gm_full
+            dm = models.DeviceModel(ctx, "gauss_sum", G, m, n, x, Y, 0.01, global_map=mp,
+                                    **({"separable": True} if sep else {"Pfix": P0}))
+            X = np.ascontiguousarray(mp.reduce_x(P0[..., non] if sep else P0))
+            d_x, d_f, d_J = ctx.to_device(X), ctx.malloc(8 * G * S * m), ctx.malloc(8 * G * S * m * mp.nv)
+            for what, call in (("f", lambda: dm.fun_dev(d_x, d_f, 1)), ("J", lambda: dm.jac_dev(d_x, d_J))):
+                call()
+                ctx.sync()
+                per_round = []
+                for _ in range(a.rounds):
+                    ctx.timing(True, only="model_eval")
+                    ctx.timing_reset()
+                    for _ in range(a.launches):
+                        call()
+                    ctx.sync()
+                    ms, cnt = ctx.timing_read()["model_eval"]
+                    ctx.timing(False)
+                    per_round.append(round(1e3 * ms / a.launches, 2))
+                    res["%s_%s_launches_per_eval" % (key, what)] = cnt // a.launches
+                res["%s_%s_us" % (key, what)] = round(float(np.median(per_round)), 2)
+                if a.rounds > 1:
+                    res["%s_%s_us_all" % (key, what)] = per_round
+            for p in (d_x, d_f, d_J):
+                ctx.free(p)
+            dm.close()
+        return res
+    kw = dict(sigma=0.01, driver="device", ctx=ctx, ftol=1e-10, xtol=1e-10, gtol=1e-10)
+    P0_sep = P0.copy()
+    P0_sep[..., lin] = np.nan
+    routes = {"separable": lambda: curve_fit_global("gauss_sum", x, Y, P0_sep, shared, separable=True, **kw)}
+    if plain_fits:
+        routes["plain"] = lambda: curve_fit_global("gauss_sum", x, Y, P0, shared, **kw)
+    times = {k: [] for k in routes}
+    out = {k: run() for k, run in routes.items()}                         # warm-up: code objects, plans
+    for _ in range(a.repeat):
+        for k, run in routes.items():
+            ctx.sync()
+            t0 = time.perf_counter()
+            run()
+            times[k].append(time.perf_counter() - t0)
+    for k, run in routes.items():
+        ctx.timing(True)
+        ctx.timing_reset()
+        run()
+        ctx.sync()
+        slots = {s: round(ms, 3) for s, (ms, cnt) in ctx.timing_read().items() if cnt}
+        ctx.timing(False)
+        nfev = np.array([r.nfev for r in out[k][2]])
+        res.update({k + "_s": round(float(np.median(times[k])), 4), k + "_all_s": [round(t, 4) for t in times[k]],
+                    k + "_nfev_mean": round(float(nfev.mean()), 2), k + "_nfev_max": int(nfev.max()),
+                    k + "_converged": int(sum(r.success for r in out[k][2])), k + "_slots_ms": slots,
+                    k + "_model_eval_ms": slots.get("model_eval")})
+    if plain_fits:
+        both = np.array([ra.success and rb.success for ra, rb in zip(out["separable"][2], out["plain"][2])])
+        res["speedup"] = round(res["plain_s"] / res["separable_s"], 2)
+        res["popt_max_rel_diff"] = float(np.max(np.abs(out["separable"][0][both] - out["plain"][0][both])
+                                                / (np.abs(out["plain"][0][both]) + 1e-3)))
+    return res
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--B", type=int, default=4096)
@@ -525,11 +609,12 @@ def main():
                     help="fit with the linear parameters projected out (with --kernel: the three launches per evaluation)")
     a = ap.parse_args()
     if a.separable:
-        if (a.expr is not None or a.response or a.global_S or a.fixed or a.tied or a.binned or a.omit is not None
-                or a.estimator != "lse"):
-            ap.error("--separable takes --B, --m, --peaks, --repeat and --kernel (--launches, --rounds) only")
+        if (a.expr is not None or a.response or a.fixed or a.tied or a.binned or a.omit is not None
+                or a.estimator != "lse" or (a.global_S and (a.global_S < 1 or not a.shared))):
+            ap.error("--separable takes --B, --m, --peaks, --repeat, --kernel (--launches, --rounds) and "
+                     "--global S --shared i,j only")
         ctx = _abi.Context(0)
-        res = separable_bench(a, ctx)
+        res = separable_global_bench(a, ctx) if a.global_S else separable_bench(a, ctx)
         ctx.close()
         print(json.dumps(res))
         return
